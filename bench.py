@@ -1,18 +1,21 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the MI355X tile encoder (BASELINE.json metric: encode Mpixels/s at quality 3.5).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload raise|1080p|8k] [--quality Q] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload raise|1080p|8k] [--quality Q] [--dump-outputs DIR]
+                    [--full [--no-cpu] [--no-e2e]]
 
 A *step* is one pass of the hot path over one batch of synthetic frames that are already resident in HBM:
 RGB in HBM -> tile encode (mp_pursuit_kernel, one launch) -> stream assembly and the per-symbol work of the entropy stage on the
-device, one code table per stream on the host -> container bytes in host memory (byte-identical to the reference's encodeImage:
-after the timed region the containers are hashed against tests/golden/frames.json, `bytes_match_golden`).
+device, one code table per stream on the host -> container bytes in host memory (byte-identical to the reference's encodeImage).
 N = 1: one frame per step; default workload = the north_star's: 4928x3264 synthetic RGB, K = 32, quality 3.5; consecutive steps
 take DISTINCT frames (seeds 12345 + f, a cycle of up to 8).  The K steps of the timed region go through the library's frame
 pipeline in one call (mpc_encode_images_device): the host's table building of step i overlaps the device work of step i + 1, as
-in any steady-state use.  Beside `value` the line carries SURVEY 8(d)'s PCIe-inclusive figures, measured after the timed region:
+in any steady-state use.
+A plain run sets up, warms up, times the K steps, writes the last step's container with --dump-outputs DIR (DIR/container.npy,
+float32 byte values; DIR/container_rank<r>.npy per rank for N > 1) and prints the line.  --full adds the untimed legs behind the
+timed region: the containers hashed against tests/golden/frames.json (`bytes_match_golden`), SURVEY 8(d)'s PCIe-inclusive figures
 `host_to_bytes_Mpix_s` (pageable host RGB -> container bytes through mpc_encode_images, the same frames, pipelined) and
-`single_frame_ms` (one mpc_encode_image call).
+`single_frame_ms` (one mpc_encode_image call), the device stage alone with the roofline, and `cpu_baseline`.
 N > 1: one rank per GPU, launched by torch.distributed.run -- or by this script itself: `python bench.py --gpus N` without a
 launcher starts N child processes (fresh interpreters, before anything here touches a GPU) with RANK / LOCAL_RANK / WORLD_SIZE /
 MASTER_* set, relays rank 0's line and fails if any rank fails.  Weak scaling, N frames per step.  Every frame is row-striped over
@@ -163,6 +166,59 @@ def golden_of(workload, q, seed):
     return None
 
 
+def headline(args, world, frames, W, H, K, q, elapsed, container_bytes):
+    """The fields of the line a plain run prints: the timed region's figure and what it was measured on."""
+    pixels_per_step = frames * W * H if world > 1 else W * H
+    value = pixels_per_step * args.steps / elapsed / 1e6
+    return {
+        "metric": "encode Mpixels/s at quality=3.5" if q == 3.5 else f"encode Mpixels/s at quality={q}",
+        "value": round(value, 3),
+        "unit": "Mpixels/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32" if args.fast else "f64",
+        "data": "synthetic",
+        "config": {"workload": (f"{frames} x {W}x{H} synthetic RGB per step" if world > 1 else f"{W}x{H} synthetic RGB, {frames} distinct frames in turn")
+                               + f" (mt19937 seed 12345+f), quality {q}, K={K} atoms/tile-channel, 8x8 tiles"
+                               + (f", row-striped over {world} GPUs" if world > 1 else ""),
+                   "stage": "frames resident in HBM -> tile encode, stream assembly and the per-symbol work of the entropy stage "
+                            "(run lengths, histograms, code writing) on the device; the host builds one code table per stream -> "
+                            "container bytes in host memory "
+                            + ("(the ...Fast / float flavour: PARITY UNPINNED against the reference's Eigen results; bit-identical to "
+                               "oracle/mpo_fast.c, PSNR / size equivalent to the double path)" if args.fast else
+                               "(byte-identical to the reference's encodeImage)")
+                            + ("; stripes' records exchanged between ranks so that rank f produces frame f's container" if world > 1 else
+                               "; the steps of the timed region are pipelined (table building of step i beside the device work of step i+1)"),
+                   "container_bytes": container_bytes, "bpp": round(8.0 * container_bytes / (W * H), 4)},
+        "hbm_resident_Mpix_s": round(value, 3),
+    }
+
+
+DUMP_BUDGET = 60 * 10 ** 6            # bytes of .npy data one --dump-outputs run may write, all ranks together (limit: 64 MB)
+
+
+def dump_outputs(out_dir, container, world, rank):
+    """The container of the last timed step, one float32 per byte: DIR/container.npy (N = 1) or DIR/container_rank<r>.npy.
+    A container beyond this rank's share of DUMP_BUDGET is written as a fixed sample (seeded positions, sorted) with its
+    positions beside it in <name>_index.npy (float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    name = "container" if world == 1 else f"container_rank{rank}"
+    data = np.asarray(container, dtype=np.uint8).reshape(-1)
+    share = DUMP_BUDGET // world
+    if data.size * 4 <= share:
+        np.save(os.path.join(out_dir, name + ".npy"), data.astype(np.float32))
+        return
+    keep = share // (4 + 8)
+    index = np.sort(np.random.default_rng(12345).choice(data.size, keep, replace=False))
+    np.save(os.path.join(out_dir, name + ".npy"), data[index].astype(np.float32))
+    np.save(os.path.join(out_dir, name + "_index.npy"), index.astype(np.float64))
+
+
 def launch_ranks(n, argv):
     """`python bench.py --gpus N` without a launcher: N fresh child processes, one rank each, started BEFORE this process has touched a
     GPU (it never does: it only relays).  Rank 0's stdout is passed on; a failing rank ends the others and the run."""
@@ -201,6 +257,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="raise", choices=sorted(WORKLOADS))
     ap.add_argument("--quality", type=float, default=None, help="bpp allocation (BASELINE configs[2] sweeps 2.0 .. 6.0); default 3.5")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: golden check, PCIe-inclusive legs, device stage + roofline, cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the container of the last timed step as DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--fast", action="store_true",
                     help="the `...Fast` (float) flavour of the tile path (SURVEY 8f N3): NOT the driver's line -- parity unpinned "
@@ -266,9 +326,10 @@ def main():
         def run(n):                                          # n steps, software-pipelined on the rank's stream
             return striped.run(d_rgb, stream, n, views=True)
 
-    # HIP events around every launch of the dominant kernel IN the timed region, on the stream it is launched on (the library's
-    # pursuit stream): roofline.achieved below is priced on these durations.  (On during the warm-up too: the events exist then.)
-    timed_events = os.environ.get("BENCH_TIMED_EVENTS", "1") != "0"
+    # --full: HIP events around every launch of the dominant kernel IN the timed region, on the stream it is launched on (the
+    # library's pursuit stream): roofline.achieved below is priced on these durations.  (On during the warm-up too: the events
+    # exist then.)
+    timed_events = args.full and os.environ.get("BENCH_TIMED_EVENTS", "1") != "0"
     if timed_events:
         ctx.kernel_timing(True)
     run(args.warmup)
@@ -289,8 +350,17 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     container_bytes = len(containers[-1])
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, containers[-1], world, rank)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline(args, world, frames, W, H, K, q, elapsed, container_bytes)), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
-    # ---- untimed: the bytes of the timed region against the oracle's (tests/golden/frames.json) --------------------------------
+    # ---- untimed (--full): the bytes of the timed region against the oracle's (tests/golden/frames.json) -----------------------
     # N = 1: container i is frame i % frames (seed 12345 + i % frames); N > 1: every container of this rank is frame `rank`
     checked, matched = 0, 0
     if not args.fast:
@@ -360,7 +430,6 @@ def main():
 
     if rank == 0:
         pixels_per_step = frames * W * H if world > 1 else W * H
-        value = pixels_per_step * args.steps / elapsed / 1e6
         launches_per_step = kern_launches // dev_steps
         standalone_flops = mfma_instr * MFMA_FLOP / max(kern_launches, 1)
         standalone_ms = kern_ms_total / max(kern_launches, 1)
@@ -432,40 +501,16 @@ def main():
                     "binds: per-step latency does, and with every CU at work the device's power limit (stamps build: shader clock "
                     "2.37 GHz on 64 workgroups, about 1.8 GHz on 256, profiles/r03_stamps.txt -- against the MFMA peak at that clock "
                     "frac would be about 0.31; DESIGN.md 3, 9)"}
-        line = {
-            "metric": "encode Mpixels/s at quality=3.5" if q == 3.5 else f"encode Mpixels/s at quality={q}",
-            "value": round(value, 3),
-            "unit": "Mpixels/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32" if args.fast else "f64",
-            "data": "synthetic",
-            "config": {"workload": (f"{frames} x {W}x{H} synthetic RGB per step" if world > 1 else f"{W}x{H} synthetic RGB, {frames} distinct frames in turn")
-                                   + f" (mt19937 seed 12345+f), quality {q}, K={K} atoms/tile-channel, 8x8 tiles"
-                                   + (f", row-striped over {world} GPUs" if world > 1 else ""),
-                       "stage": "frames resident in HBM -> tile encode, stream assembly and the per-symbol work of the entropy stage "
-                                "(run lengths, histograms, code writing) on the device; the host builds one code table per stream -> "
-                                "container bytes in host memory "
-                                + ("(the ...Fast / float flavour: PARITY UNPINNED against the reference's Eigen results; bit-identical to "
-                                   "oracle/mpo_fast.c, PSNR / size equivalent to the double path)" if args.fast else
-                                   "(byte-identical to the reference's encodeImage)")
-                                + ("; stripes' records exchanged between ranks so that rank f produces frame f's container" if world > 1 else
-                                   "; the steps of the timed region are pipelined (table building of step i beside the device work of step i+1)"),
-                       "container_bytes": container_bytes, "bpp": round(8.0 * container_bytes / (W * H), 4)},
+        line = headline(args, world, frames, W, H, K, q, elapsed, container_bytes)
+        line.update({
             "bytes_match_golden": bytes_match,
             "golden_containers_checked": checked,
-            "hbm_resident_Mpix_s": round(value, 3),
             "host_to_bytes_Mpix_s": round(host_to_bytes, 3) if host_to_bytes else None,
             "single_frame_ms": round(single_ms, 4) if single_ms else None,
             "device_stage_Mpix_s": round(pixels_per_step / world / dev_elapsed / 1e6, 3) if world > 1 else round(pixels_per_step / dev_elapsed / 1e6, 3),
             "device_stage_ms": round(dev_elapsed * 1e3, 4),
             "roofline": roof,
-        }
+        })
         if not args.no_cpu and world == 1:
             line["cpu_baseline"] = cpu_baseline(W, H, K, q, host_frames[0], args.cpu_seconds)      # the double oracle, either way
         print(json.dumps(line), flush=True)

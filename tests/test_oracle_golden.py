@@ -114,10 +114,8 @@ def test_variance_constants_match_stats_txt(oracle):
 
 
 def test_decode_mn_against_jpeg(oracle, mn_bytes):
-    """decodeImage :783 of the fixture vs the committed JPEG of the same photo (reference tree only)."""
-    jpg = "/root/reference/Data/r0c1de5e1t.jpg"
-    if not os.path.exists(jpg):
-        pytest.skip("reference Data/ not present")
+    """decodeImage :783 of the fixture vs the committed JPEG of the same photo (Data/r0c1de5e1t.jpg, kept in tests/golden)."""
+    jpg = os.path.join(GOLDEN, "r0c1de5e1t.jpg")
     from PIL import Image
     img = oracle.decode_image(mn_bytes)
     ref = np.ascontiguousarray(np.array(Image.open(jpg).convert("RGB")))

@@ -4,6 +4,6 @@
 for rep in 1 2 3; do
   for setting in "$@"; do
     if [ "$setting" = "-" ]; then s=""; else s="$setting"; fi
-    env $s python bench.py --steps 20 --warmup 5 --no-cpu --no-e2e $BENCH_ARGS 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('[$setting]', d['value'], d['ms_per_step'], d['bytes_match_golden'])"
+    env $s python bench.py --full --steps 20 --warmup 5 --no-cpu --no-e2e $BENCH_ARGS 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('[$setting]', d['value'], d['ms_per_step'], d['bytes_match_golden'])"
   done
 done

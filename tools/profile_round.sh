@@ -25,7 +25,7 @@ for w in raise 1080p 8k; do
   echo "pmc $w done"
 done
 # the whole pipeline of bench.py's value (pursuit, stream assembly, entropy kernels, the container's copy) in one trace
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/${tag}_stats_pipeline -- python3 $R/bench.py --steps 14 --warmup 4 --no-cpu --no-e2e > $O/${tag}_stats_pipeline.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/${tag}_stats_pipeline -- python3 $R/bench.py --full --steps 14 --warmup 4 --no-cpu --no-e2e > $O/${tag}_stats_pipeline.log 2>&1
 cp $O/${tag}_stats_pipeline/*/*kernel_stats.csv $P/${tag}_kernel_stats_pipeline_raise.csv
 python3 $R/tools/pipeline_timeline.py $O/${tag}_stats_pipeline/*/*kernel_trace.csv $P/${tag}_timeline_pipeline_raise.txt
 echo "pipeline stats done"
@@ -35,13 +35,13 @@ python3 $R/tools/pmc_sq_summary.py $O/${tag}_pmc_sq/*/*counter_collection.csv $P
 cp $P/${tag}_pmc_sq_raise.json $R/profiles/${tag}_pmc_sq_raise.json      # bench.py quotes it in roofline.limited_by
 echo "pmc sq done"
 cd $R
-python3 bench.py > $P/${tag}_bench_raise.json 2> $O/${tag}_bench_raise.err
-python3 bench.py --workload 1080p --no-cpu > $P/${tag}_bench_1080p.json 2>/dev/null
-python3 bench.py --workload 8k --no-cpu > $P/${tag}_bench_8k.json 2>/dev/null
+python3 bench.py --full > $P/${tag}_bench_raise.json 2> $O/${tag}_bench_raise.err
+python3 bench.py --full --workload 1080p --no-cpu > $P/${tag}_bench_1080p.json 2>/dev/null
+python3 bench.py --full --workload 8k --no-cpu > $P/${tag}_bench_8k.json 2>/dev/null
 echo "bench lines done"
 : > $P/${tag}_quality_sweep.jsonl
 for q in 2.0 2.5 3.0 3.5 4.0 4.5 5.0 5.5 6.0; do
-  python3 bench.py --quality $q --no-cpu --steps 10 --warmup 2 2>/dev/null | python3 -c "
+  python3 bench.py --full --quality $q --no-cpu --steps 10 --warmup 2 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 print(json.dumps({'quality':$q,'value_Mpix_s':d['value'],'ms_per_step':d['ms_per_step'],'device_stage_Mpix_s':d['device_stage_Mpix_s'],'container_bytes':d['config']['container_bytes'],'bpp':d['config']['bpp'],'mfma_frac':d['roofline']['frac'],'tile_channel_steps':d['roofline']['tile_channel_steps_per_step']}))" >> $P/${tag}_quality_sweep.jsonl
@@ -51,7 +51,7 @@ python3 tools/e2e_timing.py > $P/${tag}_e2e_timing.txt 2>/dev/null
 # the frame pipeline's sensitivity to how the runtime maps its streams onto hardware queues
 : > $P/${tag}_hw_queues.txt
 for nq in 1 2 4 8; do
-  GPU_MAX_HW_QUEUES=$nq python3 bench.py --steps 20 --warmup 5 --no-cpu --no-e2e 2>/dev/null | python3 -c "
+  GPU_MAX_HW_QUEUES=$nq python3 bench.py --full --steps 20 --warmup 5 --no-cpu --no-e2e 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 print('GPU_MAX_HW_QUEUES=$nq value', d['value'], 'Mpix/s ms_per_step', d['ms_per_step'], 'bytes_match_golden', d['bytes_match_golden'])" >> $P/${tag}_hw_queues.txt
