@@ -147,6 +147,11 @@ def _bind_bitstream(L):
     L.mpc_format_double.argtypes = [C.c_double, C.c_char_p, C.c_int]
     L.mpc_psnr.argtypes = [_u8p, _u8p, C.c_int, C.c_int]
     L.mpc_psnr.restype = C.c_double
+    _ullp_ = C.POINTER(C.c_ulonglong)
+    L.mpc_quant_tables.argtypes = [C.c_int, C.c_int, C.c_double, _dp]
+    L.mpc_distortion_device.argtypes = [vp, vp, vp, _dp, vp, C.c_int, C.c_int, vp, vp, vp]
+    for f in ("mpc_rate_distortion", "mpc_rate_distortion_device"):
+        getattr(L, f).argtypes = [vp, vp, C.c_int, C.c_int, _dp, C.c_int, C.POINTER(C.c_size_t), _ullp_, _dp, C.POINTER(_u8p)]
 
 
 def _take_bytes(L, p, n):
@@ -329,6 +334,58 @@ def calculate_psnr(original, decoded):
     a = np.ascontiguousarray(original, np.uint8)
     b = np.ascontiguousarray(decoded, np.uint8)
     return L.mpc_psnr(a.ctypes.data_as(_u8p), b.ctypes.data_as(_u8p), a.shape[1], a.shape[0])
+
+
+def quant_tables(K, bpp, block_size=8):
+    """createQuantizationTables (CompressedImage.cpp:124-166) without a context -> float64 [3, K] (Y, U, V)."""
+    L = load_library()
+    q = np.zeros((3, int(K)), np.float64)
+    _check(L.mpc_quant_tables(int(K), int(block_size), float(bpp), q.ctypes.data_as(_dp)))
+    return q
+
+
+def parse_qualities(qualities, K, block_size=8):
+    """The levels of a rate-distortion sweep -> (labels, quants float64 [n, 3, K]).  An item is a bpp allocation (a number:
+    createQuantizationTables' table), "max" (every step 1.0, Compression.cpp:104-110) or an explicit [3, K] table (label
+    "table").  A single item may be given without a list."""
+    if isinstance(qualities, (str, bytes, int, float, np.floating, np.integer)) or (
+            isinstance(qualities, np.ndarray) and qualities.ndim == 2):
+        qualities = [qualities]
+    labels, tables = [], []
+    for q in qualities:
+        if isinstance(q, str):
+            if q != "max":
+                raise ValueError(f"quality {q!r}: a bpp allocation, 'max' or a [3, {K}] table")
+            labels.append("max")
+            tables.append(np.ones((3, K)))
+        elif isinstance(q, (int, float, np.floating, np.integer)) and not isinstance(q, bool):
+            if not np.isfinite(q):
+                raise ValueError(f"quality {q!r}: bpp allocation must be finite")
+            labels.append(float(q))
+            tables.append(quant_tables(K, float(q), block_size))
+        else:
+            a = np.asarray(q, np.float64)
+            if a.shape != (3, K):
+                raise ValueError(f"quality table of shape {a.shape}, expected (3, {K})")
+            labels.append("table")
+            tables.append(a)
+    if not tables:
+        raise ValueError("no quality levels")
+    return labels, np.ascontiguousarray(np.stack(tables), np.float64)
+
+
+class RatePoint:
+    """One level of a rate-distortion sweep (Compression.cpp -g's row): quality label, container size in bytes, bpp =
+    8 * size / (width * height) as Compression.cpp:177 computes it, the exact squared error, calculatePSNR's value and
+    (keep_bytes) the container."""
+    __slots__ = ("quality", "quant", "size", "bpp", "sse", "psnr", "container")
+
+    def __init__(self, quality, quant, size, bpp, sse, psnr, container):
+        self.quality, self.quant, self.size, self.bpp, self.sse, self.psnr, self.container = (
+            quality, quant, size, bpp, sse, psnr, container)
+
+    def __repr__(self):
+        return f"RatePoint(quality={self.quality!r}, size={self.size}, bpp={self.bpp!r}, sse={self.sse}, psnr={self.psnr!r})"
 
 
 def format_double(v):
@@ -622,6 +679,46 @@ class CompressionContext:
     def container_job_cancel(self, slot):
         """mpc_container_job_cancel: give the slot up whatever step its job is at."""
         _check(self.L.mpc_container_job_cancel(self.h, slot))
+
+    # -- rate-distortion sweep (Compression.cpp -n / -g) ------------------------------------------
+    def _rate_distortion(self, fn, frame, width, height, qualities, keep_bytes):
+        labels, quants = parse_qualities(qualities, self.K, self.block_size)
+        n = len(labels)
+        sizes = (C.c_size_t * n)()
+        sse = np.zeros(n, np.uint64)
+        psnr = np.zeros(n, np.float64)
+        outs = (_u8p * n)() if keep_bytes else None
+        _check(fn(self.h, frame, int(width), int(height), quants.ctypes.data_as(_dp), n, sizes,
+                  sse.ctypes.data_as(C.POINTER(C.c_ulonglong)), psnr.ctypes.data_as(_dp), outs))
+        pixels = float(int(width) * int(height))
+        points = []
+        for i in range(n):
+            blob = _take_bytes(self.L, outs[i], C.c_size_t(sizes[i])) if keep_bytes else None
+            points.append(RatePoint(labels[i], quants[i], int(sizes[i]), float(8 * int(sizes[i])) / pixels, int(sse[i]),
+                                    float(psnr[i]), blob))
+        return points
+
+    def rate_distortion(self, rgb, qualities, keep_bytes=False):
+        """mpc_rate_distortion: one frame (uint8 [H, W, 3]) at every level of `qualities` (see parse_qualities) -> a list of
+        RatePoint: per level the container's size (the container itself with keep_bytes), bpp, the exact squared error against
+        what decode_image would reconstruct and its PSNR (bit-equal to calculate_psnr)."""
+        rgb = np.ascontiguousarray(rgb, np.uint8)
+        H, W = rgb.shape[:2]
+        return self._rate_distortion(self.L.mpc_rate_distortion, rgb.ctypes.data_as(C.c_void_p), W, H, qualities, keep_bytes)
+
+    def rate_distortion_device(self, d_rgb, width, height, qualities, keep_bytes=False):
+        """mpc_rate_distortion_device: the same with the frame in device memory (int from tensor.data_ptr(), tightly packed RGB)."""
+        return self._rate_distortion(self.L.mpc_rate_distortion_device, C.c_void_p(int(d_rgb)), width, height, qualities, keep_bytes)
+
+    def distortion_device(self, d_counts, d_choices, d_rgb, width, height, d_sse, d_tile_sse=None, quant=None, stream=0):
+        """mpc_distortion_device: whole-frame records and the frame they came from (device pointers) -> *d_sse (u64) += the squared
+        error of the decoder's reconstruction (quant truncated to u16 as the container carries it); d_tile_sse: per tile (u32)."""
+        qp = None
+        if quant is not None:
+            quant = np.ascontiguousarray(quant, np.float64).reshape(3, self.K)
+            qp = quant.ctypes.data_as(_dp)
+        _check(self.L.mpc_distortion_device(self.h, d_counts, d_choices, qp, d_rgb, width, height, d_sse, d_tile_sse or None,
+                                            stream or None))
 
     def calc_mp(self, channel, vectors, quant_k=None):
         """matching::CalcMPDynamic (MatchingPursuit.h:22) on the device for vectors[n,64].

@@ -1233,7 +1233,7 @@ BitWriter container_head(int width, int height, int K, int block_size, const dou
     head.put(static_cast<uint8_t>(K), 8);
     head.put(static_cast<uint8_t>(block_size), 8);
     for (int ch = 0; ch < 3; ++ch)
-        for (int i = 0; i < K; ++i) head.put(static_cast<uint16_t>(quant[ch * K + i]), 16);    // :420 u16 of an integral double
+        for (int i = 0; i < K; ++i) head.put(header_quant(quant[ch * K + i]), 16);    // :420 u16 of an integral double
     return head;
 }
 
@@ -1303,7 +1303,7 @@ void code_records(int width, int height, int K, int block_size, const double* qu
     out.put(static_cast<uint8_t>(K), 8);
     out.put(static_cast<uint8_t>(block_size), 8);
     for (int ch = 0; ch < 3; ++ch)
-        for (int i = 0; i < K; ++i) out.put(static_cast<uint16_t>(quant[ch * K + i]), 16);    // :420 u16 of an integral double
+        for (int i = 0; i < K; ++i) out.put(header_quant(quant[ch * K + i]), 16);    // :420 u16 of an integral double
     parts.assign(static_cast<size_t>(6 * K + 1), BitWriter());
     auto code_stream = [](const std::vector<uint16_t>& stream, bool dc, std::vector<uint16_t>& scratch, BitWriter& w) {
         const std::vector<uint16_t>* src = &stream;
@@ -1428,7 +1428,7 @@ uint8_t* encode_symbol_streams_malloc(int width, int height, int K, int block_si
     head.put(static_cast<uint8_t>(K), 8);
     head.put(static_cast<uint8_t>(block_size), 8);
     for (int ch = 0; ch < 3; ++ch)
-        for (int i = 0; i < K; ++i) head.put(static_cast<uint16_t>(quant[ch * K + i]), 16);    // :420 u16 of an integral double
+        for (int i = 0; i < K; ++i) head.put(header_quant(quant[ch * K + i]), 16);    // :420 u16 of an integral double
     std::vector<BitWriter> parts(static_cast<size_t>(6 * K + 1));
     // longest jobs first: the lengths stream, then the streams in the order of their sizes
     std::vector<int> order(static_cast<size_t>(6 * K));
@@ -1611,7 +1611,7 @@ Streams assemble_streams(int width, int height, int K, int block_size, const dou
     s.K = K;
     s.block_size = block_size;
     for (int ch = 0; ch < 3; ++ch)
-        for (int i = 0; i < K; ++i) s.quant[ch][i] = static_cast<uint16_t>(quant[ch * K + i]);   // :420 u16 of an integral double
+        for (int i = 0; i < K; ++i) s.quant[ch][i] = header_quant(quant[ch * K + i]);   // :420 u16 of an integral double
     const size_t tiles = static_cast<size_t>((width + block_size - 1) / block_size) *
                          static_cast<size_t>((height + block_size - 1) / block_size);
     s.lengths.resize(3 * tiles);

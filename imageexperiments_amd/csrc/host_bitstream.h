@@ -14,6 +14,11 @@
 
 namespace mpc {
 
+// The quantiser step as the container header carries it: writeCompressed stores static_cast<uint16_t>(quant)
+// (CompressedImage.cpp:419-427) and readCompressed reads that back (:656-662), so a decoder reconstructs with these
+// values, not with the encoder's doubles.  Every header writer and the distortion path (mpc_distortion_device) use it.
+inline uint16_t header_quant(double q) { return static_cast<uint16_t>(q); }
+
 class BitWriter {
 public:
     void put(uint64_t value, int width);            // MSB first; width 0..64

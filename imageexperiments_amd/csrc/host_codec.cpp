@@ -16,6 +16,10 @@ double psnr(const uint8_t* a, const uint8_t* b, int W, int H) {
             const double bl = static_cast<double>(pb[2]) - static_cast<double>(pa[2]);
             se += r * r + g * g + bl * bl;
         }
+    return psnr_from_sse(se, W, H);
+}
+
+double psnr_from_sse(double se, int W, int H) {
     const double mse = se / static_cast<double>(static_cast<size_t>(W) * static_cast<size_t>(H));
     return 20.0 * std::log10(3.0 * 255.0) - 10.0 * std::log10(mse);
 }

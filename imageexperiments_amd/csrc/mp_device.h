@@ -125,6 +125,20 @@ struct DecodeParams {
 };
 int launch_decode(const DictDevice& dict, const DecodeParams& p, void* stream);
 
+// distortion (mp_kernels.hip: mp_distortion_kernel): the decode kernel's reconstruction compared with the original frame
+struct DistortionParams {
+    const uint16_t* counts;          // [tiles][3], tile t = tx*tiles_y + ty
+    const uint32_t* choices;         // [tiles][3][K]
+    const double* quant;             // [3][K] (device), the values the container header carries
+    int K;
+    int width, height, tiles_x, tiles_y;
+    const uint8_t* original;         // [height][width][3] (device)
+    unsigned long long* sse;         // += sum over the frame of dr^2 + dg^2 + db^2
+    uint32_t* tile_sse;              // [tiles] or null: each tile's sum
+    int fast;                        // != 0: FromCoeffsDynamicFast (float)
+};
+int launch_distortion(const DictDevice& dict, const DistortionParams& p, void* stream);
+
 // ---- persistent pursuit (mp_pursuit.hip): one launch runs all K steps of every tile-channel of a batch ----
 constexpr int kMaxPairs = 32;           // (tile-channel, unlocked block other than DetailBasis[0]) pairs a tile-channel can hold (< K)
 

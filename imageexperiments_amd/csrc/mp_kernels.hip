@@ -696,74 +696,136 @@ __global__ __launch_bounds__(256) void mp_histogram_kernel(const HistParams p, i
 // --------------------------------------------------------------------------------------------------
 // T = float: FromCoeffsDynamicFast (MatchingPursuit.cpp:130-147) on the dictionary rounded to float; RGBFromYUV on the floats
 // widened to double (CompressedImage.cpp:877-881).
+// One tile's reconstruction for one lane (= pixel dx + 8*dy): the records of the three channels replayed, then RGBFromYUV's
+// rounding and clamp.  rgb[] receives the pixel as the decoder stores it (whole numbers 0..255).  Shared by mp_decode_kernel
+// and mp_distortion_kernel so that what the distortion measures is, by construction, what the decoder writes.  A record
+// outside its dynamic dictionary skips that step and sets *error_flag (when given).
 template <class T>
-__global__ __launch_bounds__(64) void mp_decode_kernel(const DictDevice dict, const DecodeParams p)
+__device__ inline void reconstruct_tile_pixel(const DictDevice& dict, const uint16_t* __restrict__ counts, const uint32_t* __restrict__ choices,
+                                              const double* __restrict__ quant, int K, long long t, int lane, int* error_flag, double rgb[3])
 {
     constexpr bool kFast = std::is_same<T, float>::value;
     const T* const base_rows = reinterpret_cast<const T*>(kFast ? static_cast<const void*>(dict.base32) : static_cast<const void*>(dict.base));
     const T* const detail_rows = reinterpret_cast<const T*>(kFast ? static_cast<const void*>(dict.detail32) : static_cast<const void*>(dict.detail));
+    double yuv[3];
+    for (int ch = 0; ch < 3; ++ch) {
+        const int count = counts[t * 3 + ch];
+        const int n = count < K ? count : K;
+        const uint32_t* rec = choices + (t * 3 + ch) * K;
+        // lane i < n takes record i: its choice (the running sum of the zig-zag deltas, the first delta taken as is) by a wave
+        // scan, then its row in the dynamic dictionary -- the block walk of every step at once instead of one after another
+        const uint32_t r = lane < n ? rec[lane] : 0u;
+        const unsigned delta = r & 0xFFFFu;
+        int choice = lane == 0 ? (int)delta : (int)((delta >> 1) ^ (0u - (delta & 1u)));
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int up = __shfl_up(choice, o);
+            if (lane >= o) choice += up;
+        }
+        // the reference builds the dynamic dictionary from ALL `count` choices before summing (FromCoeffsDynamic :111),
+        // so a detail row is resolved against the full list
+        long long row_at = -1;          // element offset of this lane's row; -1: outside the dictionary
+        int in_base = 0;
+        if (choice >= 0 && choice < dict.num_base) {
+            row_at = (long long)choice * N;
+            in_base = 1;
+        }
+        int off = dict.num_base;
+        bool open = lane < n && choice >= dict.num_base;
+        for (int k = 0; k < n; ++k) {
+            const int walk = __shfl(choice, k);
+            if (walk >= 0 && walk < dict.num_base) {
+                const int rows = dict.block_rows[walk];
+                if (open && choice < off + rows) {
+                    row_at = ((long long)ch * dict.detail_rows + dict.block_row_off[walk] + (choice - off)) * N;
+                    open = false;
+                }
+                off += rows;
+            }
+        }
+        T acc = 0;
+        for (int i = 0; i < n; ++i) {
+            const uint32_t ri = (uint32_t)__shfl((int)r, i);
+            const unsigned zz = ri >> 16;
+            const int q = (int)((zz >> 1) ^ (0u - (zz & 1u)));
+            const T coeff = (T)quant[ch * K + i] * (T)q;
+            const long long at = __shfl(row_at, i);
+            if (at < 0) {
+                if (lane == 0 && error_flag) *error_flag = 1;
+                continue;
+            }
+            const T* row = (__shfl(in_base, i) ? base_rows : detail_rows) + at;
+            const T term = row[lane] * coeff;
+            acc = acc + term;
+        }
+        yuv[ch] = (double)acc;
+    }
+    const double Y = yuv[0], U = yuv[1], V = yuv[2];
+    double rr = __builtin_round(Y + 1.13983 * V);
+    double gg = __builtin_round(Y - 0.39466 * U - 0.58060 * V);
+    double bb = __builtin_round(Y + 2.03211 * U);
+    rgb[0] = rr < 0.0 ? 0.0 : (rr > 255.0 ? 255.0 : rr);
+    rgb[1] = gg < 0.0 ? 0.0 : (gg > 255.0 ? 255.0 : gg);
+    rgb[2] = bb < 0.0 ? 0.0 : (bb > 255.0 ? 255.0 : bb);
+}
+
+template <class T>
+__global__ __launch_bounds__(64) void mp_decode_kernel(const DictDevice dict, const DecodeParams p)
+{
     const int lane = threadIdx.x;
     const long long tiles = (long long)p.tiles_x * p.tiles_y;
     for (long long t = blockIdx.x; t < tiles; t += gridDim.x) {
-        double yuv[3];
-        for (int ch = 0; ch < 3; ++ch) {
-            const int count = p.counts[t * 3 + ch];
-            const uint32_t* rec = p.choices + (t * 3 + ch) * p.K;
-            T acc = 0;
-            int choice = 0;
-            for (int i = 0; i < count && i < p.K; ++i) {
-                const uint32_t r = rec[i];
-                const unsigned delta = r & 0xFFFFu, zz = r >> 16;
-                const int d = (int)((delta >> 1) ^ (0u - (delta & 1u)));
-                choice = (i > 0) ? choice + d : (int)delta;
-                const int q = (int)((zz >> 1) ^ (0u - (zz & 1u)));
-                const T coeff = (T)p.quant[ch * p.K + i] * (T)q;
-                // locate row `choice` in the dynamic dictionary of this tile-channel; the reference builds it from
-                // ALL `count` choices before summing (FromCoeffsDynamic :111), so resolve against the full list
-                const T* row = nullptr;
-                if (choice >= 0 && choice < dict.num_base) {
-                    row = base_rows + (long long)choice * N;
-                } else if (choice >= dict.num_base) {
-                    int off = dict.num_base;
-                    int walk = 0;
-                    for (int k = 0; k < count && k < p.K; ++k) {
-                        const uint32_t rk = rec[k];
-                        const unsigned dk = rk & 0xFFFFu;
-                        walk = (k > 0) ? walk + (int)((dk >> 1) ^ (0u - (dk & 1u))) : (int)dk;
-                        if (walk >= 0 && walk < dict.num_base) {
-                            const int rows = dict.block_rows[walk];
-                            if (choice < off + rows) {
-                                row = detail_rows + ((long long)ch * dict.detail_rows + dict.block_row_off[walk] + (choice - off)) * N;
-                                break;
-                            }
-                            off += rows;
-                        }
-                    }
-                }
-                if (!row) {
-                    if (lane == 0) *p.error_flag = 1;
-                    continue;
-                }
-                const T term = row[lane] * coeff;
-                acc = acc + term;
-            }
-            yuv[ch] = (double)acc;
-        }
+        double px_rgb[3];
+        reconstruct_tile_pixel<T>(dict, p.counts, p.choices, p.quant, p.K, t, lane, p.error_flag, px_rgb);
         const int tx = (int)(t / p.tiles_y), ty = (int)(t - (long long)tx * p.tiles_y);
         const int u = tx * 8 + (lane & 7), v = ty * 8 + (lane >> 3);          // block index = dx + 8*dy
         if (u < p.width && v < p.height) {
-            const double Y = yuv[0], U = yuv[1], V = yuv[2];
-            double rr = __builtin_round(Y + 1.13983 * V);
-            double gg = __builtin_round(Y - 0.39466 * U - 0.58060 * V);
-            double bb = __builtin_round(Y + 2.03211 * U);
-            rr = rr < 0.0 ? 0.0 : (rr > 255.0 ? 255.0 : rr);
-            gg = gg < 0.0 ? 0.0 : (gg > 255.0 ? 255.0 : gg);
-            bb = bb < 0.0 ? 0.0 : (bb > 255.0 ? 255.0 : bb);
             uint8_t* px = p.rgb + 3 * ((long long)v * p.width + u);
-            px[0] = (uint8_t)rr;
-            px[1] = (uint8_t)gg;
-            px[2] = (uint8_t)bb;
+            px[0] = (uint8_t)px_rgb[0];
+            px[1] = (uint8_t)px_rgb[1];
+            px[2] = (uint8_t)px_rgb[2];
         }
+    }
+}
+
+// --------------------------------------------------------------------------------------------------
+// distortion: the decoder's reconstruction compared with the original frame instead of stored.  Four waves per
+// workgroup, one tile per wave at a time, LANE = PIXEL as in mp_decode_kernel.  Every lane inside the frame adds the
+// integer dr^2 + dg^2 + db^2 (<= 195075); a wave's 64 terms are summed by shuffles (<= 12.5e6: u32), the tile sums of
+// a wave in u64, the four waves' sums in LDS, and the workgroup adds its total to the frame's with ONE 64-bit integer
+// atomic.  Integer sums: the result does not depend on the order, and equals calculatePSNR's double sum exactly
+// (CompressedImage.cpp:343-357 adds integers, exact below 2^53).
+// --------------------------------------------------------------------------------------------------
+constexpr int kDistortionWaves = 4;
+template <class T>
+__global__ __launch_bounds__(64 * kDistortionWaves) void mp_distortion_kernel(const DictDevice dict, const DistortionParams p)
+{
+    __shared__ unsigned long long wave_sum[kDistortionWaves];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long tiles = (long long)p.tiles_x * p.tiles_y;
+    unsigned long long mine = 0;
+    for (long long t = (long long)blockIdx.x * kDistortionWaves + wave; t < tiles; t += (long long)gridDim.x * kDistortionWaves) {
+        double px_rgb[3];
+        reconstruct_tile_pixel<T>(dict, p.counts, p.choices, p.quant, p.K, t, lane, nullptr, px_rgb);
+        const int tx = (int)(t / p.tiles_y), ty = (int)(t - (long long)tx * p.tiles_y);
+        const int u = tx * 8 + (lane & 7), v = ty * 8 + (lane >> 3);
+        int e = 0;
+        if (u < p.width && v < p.height) {
+            const uint8_t* px = p.original + 3 * ((long long)v * p.width + u);
+            const int dr = (int)px_rgb[0] - (int)px[0], dg = (int)px_rgb[1] - (int)px[1], db = (int)px_rgb[2] - (int)px[2];
+            e = dr * dr + dg * dg + db * db;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) e += __shfl_xor(e, o);
+        if (p.tile_sse && lane == 0) p.tile_sse[t] = (uint32_t)e;
+        mine += (unsigned long long)(unsigned)e;
+    }
+    if (lane == 0) wave_sum[wave] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long total = 0;
+        for (int w = 0; w < kDistortionWaves; ++w) total += wave_sum[w];
+        if (total) atomicAdd(p.sse, total);
     }
 }
 
@@ -971,6 +1033,17 @@ int launch_decode(const DictDevice& dict, const DecodeParams& p, void* stream)
     if (blocks < 1) blocks = 1;
     if (p.fast) hipLaunchKernelGGL(mp_decode_kernel<float>, dim3(blocks), dim3(64), 0, (hipStream_t)stream, dict, p);
     else hipLaunchKernelGGL(mp_decode_kernel<double>, dim3(blocks), dim3(64), 0, (hipStream_t)stream, dict, p);
+    return (int)hipGetLastError();
+}
+
+int launch_distortion(const DictDevice& dict, const DistortionParams& p, void* stream)
+{
+    const long long tiles = (long long)p.tiles_x * p.tiles_y;
+    long long groups = (tiles + kDistortionWaves - 1) / kDistortionWaves;
+    unsigned blocks = (unsigned)(groups < 4096 ? groups : 4096);
+    if (blocks < 1) blocks = 1;
+    if (p.fast) hipLaunchKernelGGL(mp_distortion_kernel<float>, dim3(blocks), dim3(64 * kDistortionWaves), 0, (hipStream_t)stream, dict, p);
+    else hipLaunchKernelGGL(mp_distortion_kernel<double>, dim3(blocks), dim3(64 * kDistortionWaves), 0, (hipStream_t)stream, dict, p);
     return (int)hipGetLastError();
 }
 

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <cmath>
 #include <chrono>
 #include <cstdarg>
 #include <cstdio>
@@ -1006,7 +1007,7 @@ mpc_status mpc_write_compressed(int width, int height, int K, int block_size, co
     mpc::Streams s;
     s.width = width; s.height = height; s.K = K; s.block_size = block_size;
     for (int ch = 0; ch < 3; ++ch)
-        for (int i = 0; i < K; ++i) s.quant[ch][i] = static_cast<uint16_t>(quant[ch * K + i]);
+        for (int i = 0; i < K; ++i) s.quant[ch][i] = mpc::header_quant(quant[ch * K + i]);
     s.lengths.assign(lengths, lengths + n_lengths);
     s.codes.resize(static_cast<size_t>(6 * K));
     for (int i = 0; i < 6 * K; ++i) s.codes[i].assign(codes[i], codes[i] + code_lengths[i]);
@@ -2157,6 +2158,55 @@ mpc_status mpc_decode_tiles_device(mpc_context* c, const uint16_t* d_counts, con
     return decode_tiles_on_device(c, d_counts, reinterpret_cast<const uint32_t*>(d_choices), d_q, c->K, width, height, d_rgb,
                                   stream);
 }
+
+// the decoder's reconstruction compared with the original frame on the device (mp_distortion_kernel); the quantiser steps are
+// the container header's (mpc::header_quant), not the encoder's doubles
+mpc_status mpc_distortion_device(mpc_context* c, const uint16_t* d_counts, const mpc_basis_choice* d_choices, const double* quant,
+                                 const uint8_t* d_rgb, int width, int height, unsigned long long* d_sse, uint32_t* d_tile_sse,
+                                 void* stream) {
+    return guarded([&]() -> mpc_status {
+    if (!c || !d_counts || !d_choices || !d_rgb || !d_sse) return fail(MPC_ERR_ARGUMENT, "null argument");
+    if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback");
+    if (width < 1 || height < 1) return fail(MPC_ERR_ARGUMENT, "bad geometry %dx%d", width, height);
+    const long long tiles = static_cast<long long>((width + 7) / 8) * ((height + 7) / 8);
+    if (tiles * 3 >= (1LL << 31)) return fail(MPC_ERR_ARGUMENT, "frame too large");
+    HIP_TRY(hipSetDevice(c->device));
+    const double* q = quant ? quant : c->quant.data();
+    std::vector<double> carried(3 * static_cast<size_t>(c->K));
+    for (size_t i = 0; i < carried.size(); ++i) carried[i] = static_cast<double>(mpc::header_quant(q[i]));
+    const double* d_q = nullptr;
+    if (const mpc_status qs = call_quant(c, carried.data(), static_cast<hipStream_t>(stream), &d_q); qs != MPC_OK) return qs;
+    mpc::DistortionParams p{};
+    p.counts = d_counts;
+    p.choices = reinterpret_cast<const uint32_t*>(d_choices);
+    p.quant = d_q;
+    p.K = c->K;
+    p.width = width;
+    p.height = height;
+    p.tiles_x = (width + 7) / 8;
+    p.tiles_y = (height + 7) / 8;
+    p.original = d_rgb;
+    p.sse = d_sse;
+    p.tile_sse = d_tile_sse;
+    p.fast = c->fast ? 1 : 0;
+    const int err = mpc::launch_distortion(dict_device(c), p, stream);
+    if (err != 0) return fail(MPC_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(static_cast<hipError_t>(err)));
+    return MPC_OK;
+    });
+}
+
+mpc_status mpc_quant_tables(int K, int block_size, double bpp_allocation, double* quant) {
+    return guarded([&]() -> mpc_status {
+    if (!quant) return fail(MPC_ERR_ARGUMENT, "null argument");
+    if (K < 1 || K > MPC_MAX_K) return fail(MPC_ERR_ARGUMENT, "K=%d out of range 1..%d", K, MPC_MAX_K);
+    if (block_size < 1 || block_size > 8) return fail(MPC_ERR_ARGUMENT, "block size %d out of range 1..8", block_size);
+    if (!std::isfinite(bpp_allocation)) return fail(MPC_ERR_ARGUMENT, "bpp allocation must be finite");
+    mpc::quantisation_tables(K, block_size, bpp_allocation, quant);
+    return MPC_OK;
+    });
+}
+
+int mpc_context_tile_encode_workgroups(const mpc_context* c) { return c ? c->user_workgroups.load() : 0; }
 
 // compressed::decodeImage: container parsing on the host, tile reconstruction on the device.  The stream's own
 // K and quantisation table are used (they need not match the context's); there is no host reconstruction.

@@ -29,6 +29,10 @@
  *   mpc_decode_image          compressed::decodeImage                     CompressedImage.h:75
  *   mpc_decode_tiles_device   matching::FromCoeffsDynamic per tile        MatchingPursuit.h:25, CompressedImage.cpp:797-831
  *   mpc_psnr                  compressed::calculatePSNR                   CompressedImage.h:57
+ *   mpc_quant_tables          compressed::createQuantizationTables        CompressedImage.cpp:124-166 (without a context)
+ *   mpc_distortion_device     (new) calculatePSNR's sum of squares of decodeImage's reconstruction, from the records
+ *   mpc_rate_distortion       Compression.cpp -n / -g for one frame        Compression.cpp:144-182, :303-350
+ *   mpc_rate_distortion_device (same, frame already in device memory)
  *   mpc_huffman_encode/decode huffman::huffmanEncode / huffmanDecode      Huffman.h:15-19
  *   mpc_rle_encode/decode     huffman::runLengthEncode / runLengthDecode  Huffman.h:12-13
  */
@@ -341,6 +345,36 @@ int mpc_format_double(double v, char* buf, int cap);
 
 /* compressed::calculatePSNR (CompressedImage.h:57) */
 double mpc_psnr(const uint8_t* original, const uint8_t* decoded, int width, int height);
+
+/* ---- rate-distortion curves: Compression.cpp -n (:144-182) and -g (:303-350) without the container coming back in ----
+ * createQuantizationTables (CompressedImage.cpp:124-166) without a context: quant[3*K], Y then U then V, what
+ * mpc_context_create(K, block_size, bpp_allocation, ...) installs.  K 1..32, block size 1..8, bpp finite.  Host only. */
+mpc_status mpc_quant_tables(int K, int block_size, double bpp_allocation, double* quant);
+
+/* Squared reconstruction error of whole-frame records (tile t = tx*tiles_y + ty, what mpc_encode_tiles_device returns for
+ * tile rows [0, tiles_y)) against the RGB frame they were encoded from (3*width bytes per row), all in device memory: exactly
+ * calculatePSNR's sum (CompressedImage.cpp:343-357) between that frame and what mpc_decode_image reconstructs from the
+ * container of these records.  The reconstruction is the decoder's (mp_decode_kernel; the context's fast flag selects the
+ * flavour) with the quantiser steps the container header carries: quant (host [3*K], NULL = the context's tables) truncated to
+ * u16 as writeCompressed stores them (:419-427), not the encoder's doubles.  *d_sse (u64) += the frame's sum (the caller zeroes
+ * it); d_tile_sse[tiles] (u32, optional) = each tile's.  Asynchronous on `stream`. */
+mpc_status mpc_distortion_device(mpc_context* ctx, const uint16_t* d_counts, const mpc_basis_choice* d_choices, const double* quant,
+                                 const uint8_t* d_rgb, int width, int height, unsigned long long* d_sse, uint32_t* d_tile_sse,
+                                 void* stream);
+
+/* One frame (host, 3*width bytes per row) at n_levels quantiser tables quants[n_levels][3*K]: per level i
+ *   nbytes[i]  the container's size; bytes[i] (bytes != NULL; mpc_free) the container, byte-identical to
+ *              mpc_encode_image(ctx, rgb, width, height, quants + 3*K*i)
+ *   sse[i]     (optional) the exact integer sum of squared differences between rgb and mpc_decode_image(bytes[i])
+ *   psnr[i]    (optional) calculatePSNR's value from it, bit-identical to mpc_psnr (+inf for a lossless level)
+ * Levels are pipelined: level i+1's tile encode runs while the host builds level i's code tables; the decoded frames never
+ * exist.  The call uses container job slots 0..2 of the context (they must be idle) and leaves its quant tables, fast flag and
+ * tile-encode workgroups as it found them.  On failure nothing is returned. */
+mpc_status mpc_rate_distortion(mpc_context* ctx, const uint8_t* rgb, int width, int height, const double* quants, int n_levels,
+                               size_t* nbytes, unsigned long long* sse, double* psnr, uint8_t** bytes);
+/* The same with the frame already in device memory (3*width bytes per row, tightly packed). */
+mpc_status mpc_rate_distortion_device(mpc_context* ctx, const uint8_t* d_rgb, int width, int height, const double* quants,
+                                      int n_levels, size_t* nbytes, unsigned long long* sse, double* psnr, uint8_t** bytes);
 
 #ifdef __cplusplus
 }
