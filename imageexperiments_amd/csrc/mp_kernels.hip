@@ -943,12 +943,9 @@ __global__ __launch_bounds__(64) void mp_energy_kernel(const Workspace ws, const
 
 int enqueue_pursuit(const DictDevice& dict, const Workspace& ws, const FrameInput& in, const Outputs& out,
                     const double* quant_dev, int K, long long tc_begin, int n, int parts, int row_parts, int sweep_waves,
-                    void* stream_, void** base_events, void* side_stream_, void* fork_event_, void* join_event_)
+                    void* stream_, void** base_events)
 {
     hipStream_t s = static_cast<hipStream_t>(stream_);
-    hipStream_t side = static_cast<hipStream_t>(side_stream_);
-    hipEvent_t ev_fork = static_cast<hipEvent_t>(fork_event_), ev_join = static_cast<hipEvent_t>(join_event_);
-    const bool forked = side != nullptr && ev_fork != nullptr && ev_join != nullptr;
     if (n < 1 || n > ws.cap) return (int)hipErrorInvalidValue;
     if (parts < 1) parts = 1;
     if (parts > kMaxParts) parts = kMaxParts;
@@ -965,10 +962,8 @@ int enqueue_pursuit(const DictDevice& dict, const Workspace& ws, const FrameInpu
     hipLaunchKernelGGL(mp_init_kernel, dim3(clampu((unsigned)((n + 2) / 3), 16384u)), dim3(64), 0, s, ws, in, tc_begin, n);
     for (int step = 0; step < K; ++step) {
         const int cur = step & 1;
-        if (step > 0) {
+        if (step > 0)
             hipLaunchKernelGGL(mp_fill_kernel, dim3(clampu(max_slabs, 2048u)), dim3(256), 0, s, ws, cur, step & 1);
-            if (forked) (void)hipStreamWaitEvent(s, ev_join, 0);   // the previous step's residual update
-        }
         if (base_events) (void)hipEventRecord(static_cast<hipEvent_t>(base_events[2 * step]), s);
         hipLaunchKernelGGL(mp_base_kernel, dim3(clampu(max_groups * (unsigned)(parts + 1), slots)), dim3(64), 0, s, ws, dict,
                            cur, parts, step > 0 ? 1 : 0, (int)slots);
@@ -978,18 +973,8 @@ int enqueue_pursuit(const DictDevice& dict, const Workspace& ws, const FrameInpu
                                dict, row_parts, (int)slots, ws.cand_val);
         hipLaunchKernelGGL(mp_finish_kernel, dim3(clampu(max_slabs, 2048u)), dim3(256), 0, s, ws, dict, out, quant_dev, K,
                            step, cur, parts, row_parts, (int)slots);
-        if (step + 1 < K) {
-            // The residual update and the next step's bucket + fill only depend on the finish kernel, not on each other:
-            // with a side stream the update runs beside them and is joined in front of the next sweep.
-            if (forked) {
-                (void)hipEventRecord(ev_fork, s);
-                (void)hipStreamWaitEvent(side, ev_fork, 0);
-                hipLaunchKernelGGL(mp_update_kernel, dim3(clampu(max_groups, 4096u)), dim3(64), 0, side, ws, dict, cur);
-                (void)hipEventRecord(ev_join, side);
-            } else {
-                hipLaunchKernelGGL(mp_update_kernel, dim3(clampu(max_groups, 4096u)), dim3(64), 0, s, ws, dict, cur);
-            }
-        }
+        if (step + 1 < K)
+            hipLaunchKernelGGL(mp_update_kernel, dim3(clampu(max_groups, 4096u)), dim3(64), 0, s, ws, dict, cur);
     }
     if (out.energy)
         hipLaunchKernelGGL(mp_energy_kernel, dim3(clampu((unsigned)((n + kEnergyGroup - 1) / kEnergyGroup), 8192u)), dim3(64), 0, s, ws, dict, out, n);

@@ -1,9 +1,341 @@
 // mpc_internal.h -- product: what the translation units of libmpcodec.so share besides the public C ABI (include/mpcodec.h).
+//   mpcodec_context.cpp    device dictionary, context, quantiser tables, pursuit launches, tile encode, timing, tuning switches
+//   mpcodec_container.cpp  records on the device -> container (ContainerJob), the mpc_container_job_* API, the frame pipeline
+//   mpcodec_bitstream.cpp  host-only bitstream entry points
+//   mpcodec_decode.cpp     decode, distortion, patch statistics
 #pragma once
 
-// the text mpc_last_error() returns on the calling thread (mpcodec_capi.cpp)
+#include "../../include/mpcodec.h"
+
+#include <hip/hip_runtime.h>
+
+#include <atomic>
+#include <cstdlib>
+#include <functional>
+#include <memory>
+#include <mutex>
+#include <stdexcept>
+#include <vector>
+
+#include "host_bitstream.h"
+#include "host_dictionary.h"
+#include "mp_device.h"
+
+// the text mpc_last_error() returns on the calling thread (mpcodec_context.cpp)
 extern "C" void mpc_set_error_text(const char* text);
 
 struct mpc_context;
 // what mpc_context_set_tile_encode_workgroups last set (0 = all CUs); mpc_rate_distortion restores it
 extern "C" int mpc_context_tile_encode_workgroups(const mpc_context* ctx);
+
+#pragma GCC visibility push(hidden)
+
+// sets the calling thread's mpc_last_error() text, returns `st`
+mpc_status fail(mpc_status st, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+
+#define HIP_TRY(call)                                                                         \
+    do {                                                                                      \
+        hipError_t e_ = (call);                                                               \
+        if (e_ != hipSuccess) return fail(MPC_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
+    } while (0)
+
+inline mpc_status launch_failed(int err) {
+    return fail(MPC_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(static_cast<hipError_t>(err)));
+}
+
+// No exception crosses the C ABI (the reference throws heap-allocated std::range_error*; here: status codes)
+template <class F>
+mpc_status guarded(F&& body) {
+    try {
+        return body();
+    } catch (const std::bad_alloc&) {
+        return fail(MPC_ERR_ALLOC, "out of memory");
+    } catch (const std::length_error& e) {
+        return fail(MPC_ERR_ALLOC, "allocation size out of range: %s", e.what());
+    } catch (const std::exception& e) {
+        return fail(MPC_ERR_BITSTREAM, "%s", e.what());
+    } catch (...) {
+        return fail(MPC_ERR_BITSTREAM, "unknown failure");
+    }
+}
+
+constexpr long long kMaxBatchDefault = 3LL * 524288;   // tile-channels in flight per call (an 8K frame in one go; ~1.5 GB of workspace)
+constexpr unsigned kTripleCap = 1u << 20;              // (symbol, count, first position) triples the device entropy tables hold
+
+// Environment switches of the library ("Environment switches").  None is needed in normal use and none changes a
+// result; they exist for measurements and for tests that force rare paths.  read_tuning() reads them all, once per public
+// entry call, on the calling thread; worker threads get what that thread read.
+//   switch                        field            effect (default)
+//   MPC_PATH=steps, MPC_FILTER=0  steps_path       the step-synchronous exhaustive f64 sweeps instead of the persistent kernel
+//   MPC_PIPES                     pipes            concurrent sub-batches of those sweeps (by batch size, 1 - 4)
+//   MPC_MAX_BATCH_TILES           max_batch        tiles in flight per sub-batch round of those sweeps (524288)
+//   MPC_WORKGROUPS                workgroups       pursuit workgroups of every launch (all CUs)
+//   MPC_SEQ_WORKGROUPS            seq_workgroups   pursuit workgroups of a frame sequence (7/8 of the CUs; 0 = all)
+//   MPC_SIDE_PRIORITY             side_priority    the frame pipeline's side streams outrank its pursuits (on)
+//   MPC_SHARED_SIDE_STREAMS       shared_sides     two side streams shared by all slots (on)
+//   MPC_LAG_ASSEMBLY              lag_assembly     pursuit(f) waits for assembly + phase 1 of frame f - this (2)
+//   MPC_LAG_PHASE2                lag_phase2       ... and for phase 2 of frame f - this (3)
+//   MPC_SINGLE_STRIPES            single_stripes   row stripes of a single host frame (1 below 32 MB, 3, 4 from 80 MB)
+//   MPC_HOST_ENTROPY=1            host_entropy     the entropy stage on the host
+//   MPC_ENTROPY_TRIPLES           triple_limit     distinct symbols per frame above which a frame takes the host route (2^20)
+//   MPC_TRACE=1                   trace            per-frame time stamps of the pipeline and the decoder on stderr
+// MPC_HOST_THREADS (worker threads of the host's table building) is read by host_bitstream.cpp, which also builds on its own.
+struct Tuning {
+    bool steps_path = false, side_priority = true, host_entropy = false, trace = false;
+    int pipes = 0, workgroups = 0, single_stripes = 0;          // > 0: forced
+    int seq_workgroups = -1, shared_sides = -1;                 // >= 0: forced
+    int lag_assembly = 2, lag_phase2 = 3;
+    long long max_batch = kMaxBatchDefault;
+    unsigned triple_limit = kTripleCap;
+};
+Tuning read_tuning();
+
+double trace_ms();                      // milliseconds since the first call (MPC_TRACE)
+
+// A grow-only device, pinned or mapped pinned buffer.  Growing frees the old buffer after a device synchronisation (the device
+// may still read it): free in steady state, where nothing grows.
+struct GrowBuffer {
+    enum Kind { kDevice, kPinned, kMapped };
+    Kind kind;
+    void* p = nullptr;
+    size_t bytes = 0;
+    explicit GrowBuffer(Kind k) : kind(k) {}
+    GrowBuffer(const GrowBuffer&) = delete;
+    GrowBuffer& operator=(const GrowBuffer&) = delete;
+    ~GrowBuffer() { release(); }
+    // at least `need` bytes; *grown (optional): the buffer is a new one
+    mpc_status reserve(size_t need, const char* what, bool* grown = nullptr);
+    void release();
+    char* data() const { return static_cast<char*>(p); }
+};
+
+// a device allocation for the length of one call
+struct DeviceTemp {
+    void* p = nullptr;
+    ~DeviceTemp() { (void)hipFree(p); }
+};
+
+// Hands out 256-byte aligned pieces of one allocation in order; on a null base it only adds up their sizes.
+struct Carve {
+    char* base = nullptr;
+    size_t at = 0;
+    static size_t up(size_t v) { return (v + 255) & ~static_cast<size_t>(255); }
+    template <class T>
+    T* take(size_t count) {
+        T* p = base ? reinterpret_cast<T*>(base + at) : nullptr;
+        at += up(sizeof(T) * count);
+        return p;
+    }
+};
+
+// The stream assembly's buffers in a slot, after the records: block_live | sizes, and for the assembly (not the decoder's gather)
+// | stream offsets | symbols (worst case: every record alive) | dc.  Fills the StreamArgs pointers.
+void carve_stream_buffers(Carve& cv, long long tiles, int K, bool assembly, mpc::StreamArgs* sa);
+
+// [lo, hi) of a host frame to `dst` on `stream` through `pinned` (same offsets), in at least 1 MiB chunks, about `parts` of them, on
+// a few threads: a chunk goes to the device as soon as it is in pinned memory (the caller's memory is pageable: the runtime would
+// stage it through one thread at a few GB/s)
+hipError_t staged_upload(int device, const uint8_t* src, uint8_t* pinned, uint8_t* dst, size_t lo, size_t hi, size_t parts,
+                         hipStream_t stream);
+
+#pragma GCC visibility pop
+
+// Everything on the device that depends only on (device, block size): the dictionary in double, its filter copies, the
+// Gram table and the persistent kernel's scratch, streams and queues.  Shared by every context of the process on that
+// device (a context adds K and the quantisation tables): the Gram table alone is 12.6 GB.  All persistent-kernel launches
+// of the process go through the three per-channel streams held here, which also serialises their use of the scratch.
+struct DeviceDict {
+    int device = -1;
+    int base_rows_padded = 0, num_base = 0, num_cus = 0;
+    long long detail_rows = 0;
+    double* d_base = nullptr;
+    double* d_detail = nullptr;
+    float* d_base32 = nullptr;        // the same rows rounded to float (the `...Fast` flavour), same layout
+    float* d_detail32 = nullptr;
+    int32_t* d_rows = nullptr;
+    int32_t* d_rowoff = nullptr;
+    uint16_t* d_base_t1 = nullptr;    // split-bf16 filter copies in MFMA operand order (persistent kernel)
+    uint16_t* d_detail_t1 = nullptr;
+    uint8_t* d_shadow = nullptr;      // [3][detail_rows]
+    float* d_gram = nullptr;          // [3][num_base + detail_rows][num_base * 64]
+    std::mutex launch_lock;           // one enqueue sequence at a time
+    hipEvent_t done[1] = {};          // recorded behind every launch: the next one (any stream) waits for it
+    int workgroups = 0;               // scratch is sized for this many workgroups per launch
+    float* pair_p = nullptr;          // per-wave scratch of the persistent kernel (pairs: approximations, meta, bounds)
+    unsigned* pair_meta = nullptr;
+    float* pair_e = nullptr;
+    unsigned* queues = nullptr;       // [3]
+    unsigned long long* stats = nullptr;   // [2]: MFMA instructions, tile-channel-steps executed by the persistent kernel since the last reset
+    ~DeviceDict() {
+        if (device < 0) return;
+        (void)hipSetDevice(device);
+        (void)hipDeviceSynchronize();
+        (void)hipFree(d_base); (void)hipFree(d_rows); (void)hipFree(d_rowoff);      // d_detail / d_detail32: inside d_base / d_base32
+        (void)hipFree(d_base32);
+        (void)hipFree(d_base_t1); (void)hipFree(d_detail_t1);
+        (void)hipFree(d_shadow); (void)hipFree(d_gram); (void)hipFree(queues); (void)hipFree(stats);
+        (void)hipFree(pair_p); (void)hipFree(pair_meta); (void)hipFree(pair_e);
+        if (done[0]) (void)hipEventDestroy(done[0]);
+    }
+};
+
+#pragma GCC visibility push(hidden)
+
+// ---- device entropy stage (mpcodec_container.cpp) ----
+// a slot's grow-only buffers; `tiles`, `K`: the geometry the tables inside `dev` were last cleared for
+struct EntropySlot {
+    GrowBuffer dev{GrowBuffer::kDevice};
+    GrowBuffer host{GrowBuffer::kMapped};
+    size_t tiles = 0;
+    int K = 0;
+};
+
+struct EntropyBuffers {
+    mpc::EntropyArgs args{};
+    uint8_t* d_out = nullptr;
+    size_t out_capacity = 0;             // bytes, device and host
+    unsigned long long capacity_symbols = 0;
+    // pinned
+    mpc::EntStream* h_streams = nullptr;
+    unsigned* h_totals = nullptr;
+    unsigned* h_triples = nullptr;
+    unsigned* h_entries = nullptr;
+    uint8_t* h_out = nullptr;
+};
+
+// carve (and grow) a slot's entropy buffers for frames of `tiles` tiles; the symbols of the streams live in the caller's buffers
+mpc_status entropy_buffers(EntropySlot& e, size_t tiles, int K, EntropyBuffers* b);
+
+// What the host keeps of a frame between the tables step and the collect step of the device route.
+struct EntropyPending {
+    std::vector<mpc::StreamPlan> plans;
+    mpc::BitWriter head;
+    size_t total_bytes = 0;
+};
+
+// Records on the device -> container bytes: the only code that does this (the frame pipeline, mpc_container_job_*,
+// mpc_code_symbol_streams_device).  The caller sets the first block of fields, then runs the steps in order:
+//   container_begin    stream assembly (unless the symbols are given) and entropy phase 1 on `side`, then `phase1`
+//   container_tables   waits for `phase1`, builds the code tables, enqueues phase 2 and the container's copy on `down`, then
+//                      `done`; `enqueued` (optional) is called once that is on the stream or clear that it will not be.  The
+//                      host route (MPC_HOST_ENTROPY, or a frame the device tables cannot hold) makes the container here instead.
+//   container_collect  waits for `done`, patches the head and the streams' pre and post bits in
+struct ContainerJob {
+    hipStream_t side = nullptr, down = nullptr;
+    hipEvent_t phase1 = nullptr, done = nullptr;
+    bool spin = false;                   // poll the events (a single frame) instead of sleeping on them
+    GrowBuffer* host_stage = nullptr;    // the host route downloads counts, offsets and symbols to here, from `host_offset` on ...
+    size_t host_offset = 0;
+    const uint16_t* h_counts = nullptr;  // ... unless they are on the host already
+    const unsigned long long* h_stream_off = nullptr;
+    const uint16_t* h_symbols = nullptr;
+    // set by container_begin
+    int width = 0, height = 0, K = 0, block_size = 0;
+    std::vector<double> quant;
+    mpc::StreamArgs sa{};
+    bool device_entropy = false;         // false: the host route
+    EntropyBuffers eb{};
+    unsigned triple_limit = kTripleCap;
+    EntropyPending pending;
+    uint8_t* blob = nullptr;             // the host route's container
+    size_t nblob = 0;
+    double stamps[5] = {};               // MPC_TRACE: phase 1 done, statistics read, tables built, symbols on the host, bytes on the host
+    ~ContainerJob() { std::free(blob); }
+};
+
+// `buffers`: where the stream assembly's are carved (carve_stream_buffers), or null when d_symbols / d_stream_off hold the
+// streams already; `eb`: the entropy slot's buffers (entropy_buffers), null for the host route
+mpc_status container_begin(ContainerJob& j, const mpc_context* c, const EntropyBuffers* eb, unsigned triple_limit, char* buffers,
+                           const uint16_t* d_counts, const uint32_t* d_choices, uint16_t* d_symbols,
+                           unsigned long long* d_stream_off, int width, int height, const double* quant);
+mpc_status container_tables(ContainerJob& j, const std::function<void()>& enqueued = nullptr);
+mpc_status container_collect(ContainerJob& j, uint8_t** bytes, size_t* nbytes);
+
+// A slot of the mpc_container_job_* API.  Its buffers are its own: the context's entropy slots and staging belong to the frame
+// pipeline (mpc_encode_image(s)) and to mpc_code_symbol_streams_device, which may run -- and re-carve or clear their tables --
+// between `begin` and `collect`.
+struct JobSlot {
+    int stage = 0;                       // 0 idle, 1 begun, 2 tables done
+    ContainerJob job;
+    EntropySlot ent;
+    GrowBuffer dev{GrowBuffer::kDevice}; // stream assembly buffers
+    ~JobSlot() {
+        if (job.phase1) (void)hipEventDestroy(job.phase1);
+        if (job.done) (void)hipEventDestroy(job.done);
+    }
+};
+
+#pragma GCC visibility pop
+
+struct mpc_context {
+    int K = 0, block_size = 0, device = -1;
+    double bpp = 0.0;
+    bool fast = false;                // the `...Fast` (float) flavour of the tile path (mpc_context_set_fast)
+    mpc::Dictionary dict;
+    std::vector<double> quant;        // [3*K]
+    std::shared_ptr<DeviceDict> dd;   // owns the dictionary's device residents
+    double* d_quant = nullptr;        // the context's tables; only mpc_context_set_quant changes them
+    // per-call quantiser overrides (the `quant` argument of the encode / decode entry points) go to a ring of device
+    // slots of their own, so that a later call with quant == NULL still quantises with the context's tables
+    static constexpr int kQuantSlots = 16;
+    double* d_quant_ring = nullptr;   // [kQuantSlots][3 * MPC_MAX_K]
+    unsigned quant_next = 0;
+    std::recursive_mutex host_calls;  // the host-buffer entry points share the staging buffers below
+    int* d_flag = nullptr;            // decode: set when a record indexes outside its dictionary
+    // grow-only staging for the host-buffer entry points (mpc_encode_tiles / mpc_encode_image(s) / mpc_decode_image): allocating
+    // and freeing them per call cost several times the encode itself
+    GrowBuffer stage{GrowBuffer::kDevice};
+    GrowBuffer host_stage{GrowBuffer::kPinned};
+    // mpc_encode_images: upload / compute / download streams and per-slot events (upload done, pursuit done, download done)
+    hipStream_t seq_up = nullptr, seq_compute = nullptr;
+    bool seq_prioritised = false;                    // the side streams outrank the pursuits' (encode_sequence)
+    // read by device-pointer encodes, which do not take `host_calls`: a stale value costs or gains a few workgroups, nothing else
+    std::atomic<int> seq_workgroups{0};              // > 0: the pursuits of a frame sequence leave CUs to the kernels behind them
+    std::atomic<int> user_workgroups{0};             // > 0: mpc_context_set_tile_encode_workgroups
+    static constexpr int kSeqSlots = 6;              // frames in flight in mpc_encode_images (a frame's container is ready about
+                                                     // three pursuits after its own started)
+    hipEvent_t seq_events[kSeqSlots][3] = {};
+    static constexpr int kSingleStripes = 4;
+    hipEvent_t seq_stripe_up[kSingleStripes] = {};   // a single host frame goes up and is encoded in row stripes (encode_sequence)
+    hipEvent_t seq_pursuit_done[kSeqSlots] = {};      // behind a slot's pursuit, for the slot's own stream to wait on
+    hipStream_t seq_down[kSeqSlots] = {};             // one download stream per slot: its worker thread drives it
+    // device-side entropy stage (mp_entropy.hip): per-slot buffers of the frame pipeline and mpc_code_symbol_streams_device
+    EntropySlot ent[kSeqSlots];
+    std::unique_ptr<JobSlot> jobs[kSeqSlots];        // mpc_container_job_*: records on the device -> container, in steps
+    // The exhaustive path's pursuit of a call is cut into sub-batches that run on `pipes` internal streams, each with its own
+    // workspace: the latency-bound bookkeeping kernels of one sub-batch (finish, update, bucket, fill) overlap the
+    // machine-filling sweeps of the other.  Fork/join with events on the caller's stream: still no host synchronisation,
+    // still capturable.
+    struct Pipe {
+        hipStream_t stream = nullptr;
+        hipEvent_t done = nullptr;
+        void* mem = nullptr;
+        mpc::Workspace ws{};
+    };
+    std::vector<Pipe> pipes;
+    hipEvent_t fork = nullptr;
+    int ws_cap = 0;                   // tile-channels per pipe workspace
+    int max_waves = 0;
+    int num_cus = 0;
+    // optional live timing of the base-sweep launches (mpc_kernel_timing_*)
+    bool timing = false;
+    std::vector<hipEvent_t> timing_events;      // 2 per launch, grown on demand
+    size_t timing_used = 0;
+    hipEvent_t timing_ref = nullptr;            // common time origin for the union of launch intervals
+};
+
+#pragma GCC visibility push(hidden)
+
+// ---- context and tile encode (mpcodec_context.cpp) ----
+mpc::DictDevice dict_device(const mpc_context* c);
+// device table a call quantises with: the context's, or a ring slot holding the call's override (copied on `s`)
+mpc_status call_quant(mpc_context* c, const double* quant, hipStream_t s, const double** d_q);
+mpc_status ensure_workspace(mpc_context* c, const Tuning& t, long long tile_channels);
+// whole_frame_order: the records go where one launch over the whole frame would put them (FrameInput::out_tile_rows) and the
+// caller has zeroed d_choices for the whole frame (stripes of one frame encoded one by one, encode_sequence's single frames)
+mpc_status encode_batch_device(mpc_context* c, const Tuning& t, const uint8_t* d_rgb, int frames, size_t frame_stride, int width,
+                               int height, size_t row_stride, int tile_row_begin, int tile_row_end, const double* quant,
+                               uint16_t* d_counts, mpc_basis_choice* d_choices, double* d_energy, uint32_t* d_swept, void* stream,
+                               bool whole_frame_order);
+
+#pragma GCC visibility pop

@@ -1,0 +1,744 @@
+// mpcodec_container.cpp -- product: records on the device -> container bytes (ContainerJob: stream assembly, the entropy stage
+// with its per-symbol work on the device, the host route), the mpc_container_job_* API over it, and the frame pipeline
+// (mpc_encode_image(s)[_device]) that feeds it.
+//
+// Entropy stage (mp_entropy.hip): phase 1 is enqueued behind the stream assembly; the host then reads the per-stream statistics,
+// builds the tables (host_bitstream.cpp: plan_stream), sends them back and enqueues phase 2, which writes the codes into the
+// container on the device; only the finished bytes cross PCIe.  MPC_HOST_ENTROPY=1 keeps the whole stage on the host (the
+// symbols cross instead); the same route is taken when a stream is outside what the device tables hold (more distinct symbols
+// than the triple list, a code longer than 32 bits).
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+#include <future>
+#include <utility>
+
+#include "mpc_internal.h"
+
+mpc_status entropy_buffers(EntropySlot& e, size_t tiles, int K, EntropyBuffers* b) {
+    const int S = 6 * K + 1;
+    const size_t n_tc = 3 * tiles;
+    const unsigned long long cap_symbols = n_tc + 2ULL * n_tc * K;
+    const size_t blocks = mpc::entropy_max_blocks(cap_symbols, S);
+    const size_t table_words = 65536 * static_cast<size_t>(S);          // dense code tables, histogram, first positions: [S][65536]
+    const size_t out_bytes = Carve::up(sizeof(uint16_t) * 2 * n_tc * K) + 65536;
+    mpc::EntropyArgs& a = b->args;
+    a = mpc::EntropyArgs{};
+    auto device_layout = [&](char* base) {
+        Carve cv{base};
+        a.streams = cv.take<mpc::EntStream>(S);
+        a.totals = cv.take<unsigned>(4);
+        for (unsigned** p : {&a.blk_stream, &a.blk_lead, &a.blk_inner, &a.blk_tail, &a.blk_carry, &a.blk_out, &a.blk_bits})
+            *p = cv.take<unsigned>(blocks);
+        a.blk_bit_off = cv.take<unsigned long long>(blocks);
+        a.packed = cv.take<uint16_t>(2 * n_tc * K);
+        a.tcode = cv.take<unsigned>(table_words);
+        a.tlen = cv.take<uint8_t>(table_words);
+        b->d_out = cv.take<uint8_t>(out_bytes);
+        a.ghist = cv.take<unsigned>(table_words);
+        a.gfirst = cv.take<unsigned>(table_words);
+        return cv.at;
+    };
+    auto host_layout = [&](char* base) {
+        Carve cv{base};
+        b->h_streams = cv.take<mpc::EntStream>(S);
+        b->h_totals = cv.take<unsigned>(4);
+        b->h_triples = cv.take<unsigned>(3 * static_cast<size_t>(kTripleCap));
+        b->h_entries = cv.take<unsigned>(3 * static_cast<size_t>(kTripleCap));
+        b->h_out = cv.take<uint8_t>(out_bytes);
+        return cv.at;
+    };
+    bool grown = false;
+    if (const mpc_status st = e.dev.reserve(device_layout(nullptr), "entropy stage buffers", &grown); st != MPC_OK) return st;
+    if (const mpc_status st = e.host.reserve(host_layout(nullptr), "pinned entropy stage buffers"); st != MPC_OK) return st;
+    if (grown) e.tiles = 0;
+    device_layout(e.dev.data());
+    host_layout(e.host.data());
+    // the kernels read and write the small host-side tables in place (mapped, coherent host memory)
+    char* mapped = nullptr;
+    HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&mapped), e.host.p, 0));
+    auto on_device = [&](void* h) { return mapped + (static_cast<char*>(h) - e.host.data()); };
+    a.host_streams = reinterpret_cast<mpc::EntStream*>(on_device(b->h_streams));
+    a.host_totals = reinterpret_cast<unsigned*>(on_device(b->h_totals));
+    a.triples = reinterpret_cast<unsigned*>(on_device(b->h_triples));
+    a.entries = reinterpret_cast<const unsigned*>(on_device(b->h_entries));
+    a.n_lengths = static_cast<unsigned>(n_tc);
+    a.n_streams = S;
+    a.triple_cap = kTripleCap;
+    a.out32 = reinterpret_cast<unsigned*>(b->d_out);
+    if (e.tiles != tiles || e.K != K) {
+        // the dense code tables and the histogram are zero between frames (the kernels clear what they set), the first
+        // positions all ones; a slot carved for another geometry holds them elsewhere
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipMemset(a.tcode, 0, sizeof(unsigned) * table_words));
+        HIP_TRY(hipMemset(a.tlen, 0, table_words));
+        HIP_TRY(hipMemset(a.ghist, 0, sizeof(unsigned) * table_words));
+        HIP_TRY(hipMemset(a.gfirst, 0xFF, sizeof(unsigned) * table_words));
+        e.tiles = tiles;
+        e.K = K;
+    }
+    b->out_capacity = out_bytes;
+    b->capacity_symbols = cap_symbols;
+    return MPC_OK;
+}
+
+namespace {
+enum class EntropyResult { kDone, kNeedsHost, kFailed };
+
+// Wait for an event.  `spin`: poll it (a single frame's latency is a chain of such waits, and a sleeping thread takes tens of
+// microseconds to come back); otherwise let the thread sleep -- in the frame pipeline the table building wants the cores.
+hipError_t wait_event(hipEvent_t ev, bool spin) {
+    if (!spin) return hipEventSynchronize(ev);
+    for (;;) {
+        const hipError_t e = hipEventQuery(ev);
+        if (e != hipErrorNotReady) return e;
+        __builtin_ia32_pause();
+    }
+}
+
+// The host's part and phase 2, in two steps.  Phase 1 has completed (the caller waited for an event behind it): the
+// statistics are in the slot's host mirrors.
+//   entropy_tables   builds the code tables and enqueues on `s`, in order: table import, the code kernels, the container's way
+//                    to the host, `done`.  kNeedsHost: nothing enqueued, take the host route.
+//   entropy_collect  waits for `done`, checks the device's bit counts against the tables', patches the host's pieces in.
+EntropyResult entropy_tables(const EntropyBuffers& b, int device_block_size, int width, int height, int K, const double* quant,
+                             unsigned triple_limit, hipStream_t s, hipEvent_t done, EntropyPending* pending, double* stamps) {
+    const mpc::EntropyArgs& a = b.args;
+    const int S = a.n_streams;
+    if (b.h_totals[3] != 0 || b.h_totals[2] > triple_limit) return EntropyResult::kNeedsHost;
+    stamps[0] = trace_ms();
+    std::vector<mpc::StreamPlan>& plans = pending->plans;
+    plans.assign(static_cast<size_t>(S), mpc::StreamPlan());
+    std::vector<int> order(static_cast<size_t>(S));             // the streams with the most symbols to build a tree from first
+    for (int j = 0; j < S; ++j) order[static_cast<size_t>(j)] = j;
+    std::sort(order.begin(), order.end(), [&](int x, int y) { return b.h_streams[x].distinct > b.h_streams[y].distinct; });
+    mpc::parallel_jobs(S, [&](int job) {
+        const int j = order[static_cast<size_t>(job)];
+        const mpc::EntStream& st = b.h_streams[j];
+        mpc::plan_stream(j != 0, st.shorter != 0, st.rle_size, st.eff_n, st.largest, b.h_triples + 3 * static_cast<size_t>(st.triple_off),
+                         st.distinct, plans[static_cast<size_t>(j)]);
+    });
+    pending->head = mpc::container_head(width, height, K, device_block_size, quant);
+    unsigned long long bit = pending->head.bit_size(), raw_symbols = 0;
+    size_t n_entries = 0;
+    for (int j = 0; j < S; ++j) {
+        const mpc::StreamPlan& p = plans[static_cast<size_t>(j)];
+        if (p.mode == 0 && p.max_code_length > 32) return EntropyResult::kNeedsHost;
+        mpc::EntStream& st = b.h_streams[j];
+        bit += p.pre.bit_size();
+        st.bit_off = bit;
+        st.mode = static_cast<unsigned>(p.mode);
+        st.m = p.m;
+        bit += p.payload_bits + p.post.bit_size();
+        raw_symbols += st.n;
+        n_entries += p.entries.size() / 3;
+    }
+    const size_t total_bytes = static_cast<size_t>((bit + 7) / 8), out_words = (total_bytes + 3) / 4;
+    if (out_words * 4 > b.out_capacity || n_entries > kTripleCap) return EntropyResult::kNeedsHost;
+    pending->total_bytes = total_bytes;
+    size_t at = 0;
+    for (int j = 0; j < S; ++j) {
+        const std::vector<uint32_t>& e = plans[static_cast<size_t>(j)].entries;
+        for (size_t k = 0; k < e.size(); k += 3) {
+            b.h_entries[at++] = (static_cast<unsigned>(j) << 16) | e[k];
+            b.h_entries[at++] = e[k + 1];
+            b.h_entries[at++] = e[k + 2];
+        }
+    }
+    stamps[1] = trace_ms();                                     // tables built
+    mpc::EntropyArgs a2 = a;
+    a2.n_entries = static_cast<unsigned>(n_entries);
+    a2.out_words = out_words;
+    const bool ok = hipMemsetAsync(b.d_out, 0, out_words * 4, s) == hipSuccess && mpc::launch_entropy_phase2(a2, raw_symbols, s) == 0 &&
+                    hipMemcpyAsync(b.h_out, b.d_out, out_words * 4, hipMemcpyDeviceToHost, s) == hipSuccess &&
+                    hipEventRecord(done, s) == hipSuccess;
+    return ok ? EntropyResult::kDone : EntropyResult::kFailed;
+}
+
+EntropyResult entropy_collect(const EntropyBuffers& b, const EntropyPending& pending, hipEvent_t done, bool spin, uint8_t** blob,
+                              size_t* nbytes, double* stamp) {
+    if (wait_event(done, spin) != hipSuccess) return EntropyResult::kFailed;
+    *stamp = trace_ms();                                        // codes written, bytes on the host
+    const int S = b.args.n_streams;
+    for (int j = 0; j < S; ++j)                                 // the device wrote exactly the bits the tables promise
+        if (b.h_streams[j].coded_bits != pending.plans[static_cast<size_t>(j)].payload_bits) return EntropyResult::kFailed;
+    mpc::or_bits(b.h_out, b.out_capacity, 0, pending.head);
+    for (int j = 0; j < S; ++j) {
+        const mpc::StreamPlan& p = pending.plans[static_cast<size_t>(j)];
+        const unsigned long long payload = b.h_streams[j].bit_off;
+        mpc::or_bits(b.h_out, b.out_capacity, static_cast<size_t>(payload - p.pre.bit_size()), p.pre);
+        mpc::or_bits(b.h_out, b.out_capacity, static_cast<size_t>(payload + p.payload_bits), p.post);
+    }
+    uint8_t* out = static_cast<uint8_t*>(std::malloc(pending.total_bytes ? pending.total_bytes : 1));
+    if (!out) return EntropyResult::kFailed;
+    {   // fresh pages: a few threads fault them in and copy
+        const size_t total = pending.total_bytes, piece = ((total + 7) / 8 + 4095) & ~static_cast<size_t>(4095);
+        const uint8_t* src = b.h_out;
+        mpc::parallel_jobs(total > (1u << 20) ? 8 : 1, [&](int k) {
+            const size_t lo = std::min(total, piece * static_cast<size_t>(k));
+            const size_t hi = total > (1u << 20) ? std::min(total, lo + piece) : total;
+            if (hi > lo) std::memcpy(out + lo, src + lo, hi - lo);
+        });
+    }
+    *blob = out;
+    *nbytes = pending.total_bytes;
+    return EntropyResult::kDone;
+}
+
+// the host route's pinned buffers: counts | stream offsets | symbols (worst case: every record alive)
+struct HostRoute {
+    uint16_t* counts;
+    unsigned long long* stream_off;
+    uint16_t* symbols;
+};
+size_t host_route_layout(char* base, size_t n_tc, int K, HostRoute* r) {
+    Carve cv{base};
+    r->counts = cv.take<uint16_t>(n_tc);
+    r->stream_off = cv.take<unsigned long long>(6 * static_cast<size_t>(K) + 1);
+    r->symbols = cv.take<uint16_t>(2 * n_tc * K);
+    return cv.at;
+}
+
+// the host route: the streams cross PCIe (unless they are on the host already), the entropy stage runs on the host (synchronous)
+mpc_status container_on_host(ContainerJob& j) {
+    const size_t n_tc = 3 * static_cast<size_t>(j.sa.tiles);
+    const uint16_t* counts = j.h_counts;
+    const unsigned long long* off = j.h_stream_off;
+    const uint16_t* symbols = j.h_symbols;
+    if (!counts) {
+        HostRoute r;
+        if (const mpc_status st = j.host_stage->reserve(j.host_offset + host_route_layout(nullptr, n_tc, j.K, &r), "pinned staging");
+            st != MPC_OK)
+            return st;
+        host_route_layout(j.host_stage->data() + j.host_offset, n_tc, j.K, &r);
+        const size_t n_off = 6 * static_cast<size_t>(j.K) + 1;
+        HIP_TRY(hipMemcpyAsync(r.stream_off, j.sa.stream_off, sizeof(unsigned long long) * n_off, hipMemcpyDeviceToHost, j.down));
+        HIP_TRY(hipMemcpyAsync(r.counts, j.sa.counts, sizeof(uint16_t) * n_tc, hipMemcpyDeviceToHost, j.down));
+        HIP_TRY(hipEventRecord(j.done, j.down));
+        HIP_TRY(hipEventSynchronize(j.done));
+        const unsigned long long total = r.stream_off[n_off - 1];
+        if (total > 2ULL * n_tc * static_cast<unsigned long long>(j.K)) return fail(MPC_ERR_HIP, "stream assembly returned an impossible size");
+        if (total) HIP_TRY(hipMemcpyAsync(r.symbols, j.sa.symbols, sizeof(uint16_t) * total, hipMemcpyDeviceToHost, j.down));
+        HIP_TRY(hipEventRecord(j.done, j.down));
+        HIP_TRY(hipEventSynchronize(j.done));
+        counts = r.counts;
+        off = r.stream_off;
+        symbols = r.symbols;
+    }
+    j.stamps[3] = trace_ms();
+    j.blob = mpc::encode_symbol_streams_malloc(j.width, j.height, j.K, j.block_size, j.quant.data(), counts, symbols, off, &j.nblob);
+    return j.blob ? MPC_OK : fail(MPC_ERR_ALLOC, "out of memory");
+}
+}  // namespace
+
+mpc_status container_begin(ContainerJob& j, const mpc_context* c, const EntropyBuffers* eb, unsigned triple_limit, char* buffers,
+                           const uint16_t* d_counts, const uint32_t* d_choices, uint16_t* d_symbols,
+                           unsigned long long* d_stream_off, int width, int height, const double* quant) {
+    const long long tiles = static_cast<long long>((width + 7) / 8) * ((height + 7) / 8);
+    j.width = width;
+    j.height = height;
+    j.K = c->K;
+    j.block_size = c->block_size;
+    const double* q = quant ? quant : c->quant.data();
+    j.quant.assign(q, q + 3 * static_cast<size_t>(c->K));
+    j.device_entropy = eb != nullptr;
+    if (eb) j.eb = *eb;
+    j.triple_limit = triple_limit;
+    std::free(j.blob);
+    j.blob = nullptr;
+    j.nblob = 0;
+    mpc::StreamArgs& sa = j.sa;
+    sa = mpc::StreamArgs{};
+    sa.counts = d_counts;
+    sa.choices = d_choices;
+    if (buffers) {
+        Carve cv{buffers};
+        carve_stream_buffers(cv, tiles, c->K, true, &sa);
+        if (const int err = mpc::launch_stream_assembly(sa, j.side); err != 0) return launch_failed(err);
+    } else {
+        sa.tiles = tiles;
+        sa.K = c->K;
+        sa.symbols = d_symbols;
+        sa.stream_off = d_stream_off;
+    }
+    if (j.device_entropy) {
+        j.eb.args.counts = d_counts;
+        j.eb.args.symbols = sa.symbols;
+        j.eb.args.stream_off = sa.stream_off;
+        if (const int err = mpc::launch_entropy_phase1(j.eb.args, j.eb.capacity_symbols, j.side); err != 0) return launch_failed(err);
+    }
+    HIP_TRY(hipEventRecord(j.phase1, j.side));
+    return MPC_OK;
+}
+
+mpc_status container_tables(ContainerJob& j, const std::function<void()>& enqueued) {
+    if (wait_event(j.phase1, j.spin) != hipSuccess) return fail(MPC_ERR_HIP, "stream assembly or entropy phase 1 failed");
+    j.stamps[0] = trace_ms();
+    EntropyResult r = EntropyResult::kNeedsHost;
+    if (j.device_entropy)
+        r = entropy_tables(j.eb, j.block_size, j.width, j.height, j.K, j.quant.data(), j.triple_limit, j.down, j.done, &j.pending,
+                           j.stamps + 1);
+    if (enqueued) enqueued();
+    if (r == EntropyResult::kFailed) return fail(MPC_ERR_HIP, "device entropy stage failed: %s", hipGetErrorString(hipGetLastError()));
+    if (r == EntropyResult::kDone) return MPC_OK;
+    j.device_entropy = false;
+    return container_on_host(j);
+}
+
+mpc_status container_collect(ContainerJob& j, uint8_t** bytes, size_t* nbytes) {
+    if (!j.device_entropy) {
+        *bytes = j.blob;
+        *nbytes = j.nblob;
+        j.blob = nullptr;
+        j.nblob = 0;
+        return MPC_OK;
+    }
+    const EntropyResult r = entropy_collect(j.eb, j.pending, j.done, j.spin, bytes, nbytes, &j.stamps[4]);
+    return r == EntropyResult::kDone ? MPC_OK : fail(MPC_ERR_HIP, "device entropy stage failed: %s", hipGetErrorString(hipGetLastError()));
+}
+
+namespace {
+// compressed::encodeImage for a sequence of equally sized frames: device tile encode, then records -> container (ContainerJob)
+// -- pipelined over kSeqSlots slots.  Frames come from host memory (uploaded through the slot's pinned image on an upload
+// stream) or are already resident on the device.
+mpc_status encode_sequence(mpc_context* c, const uint8_t* const* frames, bool on_device, int n_frames, int width, int height,
+                           const double* quant, uint8_t** bytes, size_t* nbytes) {
+    if (!c || !frames || !bytes || !nbytes || n_frames < 1) return fail(MPC_ERR_ARGUMENT, "bad argument");
+    if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback");
+    if (width < 1 || height < 1) return fail(MPC_ERR_ARGUMENT, "bad geometry");
+    for (int f = 0; f < n_frames; ++f) {
+        if (!frames[f]) return fail(MPC_ERR_ARGUMENT, "null frame");
+        bytes[f] = nullptr;
+        nbytes[f] = 0;
+    }
+    const Tuning t = read_tuning();
+    const int tiles_y = (height + 7) / 8;
+    const size_t tiles = static_cast<size_t>((width + 7) / 8) * tiles_y;
+    const size_t n_tc = tiles * 3;
+    const int K = c->K;
+    std::lock_guard<std::recursive_mutex> one_host_call(c->host_calls);
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t img_bytes = static_cast<size_t>(3) * width * height;
+    // device slot: [image] | counts | records | stream assembly;  host slot: [image] | the host route's counts, offsets, symbols
+    Carve dev, host;
+    (void)dev.take<uint8_t>(on_device ? 0 : img_bytes);
+    (void)host.take<uint8_t>(on_device ? 0 : img_bytes);
+    const size_t counts_at = dev.at;
+    (void)dev.take<uint16_t>(n_tc);
+    const size_t choices_at = dev.at;
+    (void)dev.take<mpc_basis_choice>(n_tc * K);
+    const size_t streams_at = dev.at;
+    mpc::StreamArgs measured{};
+    carve_stream_buffers(dev, static_cast<long long>(tiles), K, true, &measured);
+    HostRoute unused;
+    const size_t route_at = host.at, dev_slot = dev.at, host_slot = route_at + host_route_layout(nullptr, n_tc, K, &unused);
+    constexpr size_t S = mpc_context::kSeqSlots;
+    const size_t slots = std::min<size_t>(S, static_cast<size_t>(n_frames));
+    // a sequence gets every slot's buffers at once: a later, longer call then finds them (allocating pinned memory takes
+    // tens of milliseconds)
+    const size_t alloc_slots = n_frames > 1 ? S : 1;
+    if (const mpc_status gs = c->host_stage.reserve(alloc_slots * host_slot, "pinned staging"); gs != MPC_OK) return gs;
+    if (const mpc_status gs = c->stage.reserve(alloc_slots * dev_slot, "device staging"); gs != MPC_OK) return gs;
+    if (!c->seq_up) {
+        // The side streams at the highest priority, the pursuits' at the lowest: CUs a pursuit gives up at its end go to the
+        // waiting chains of small kernels before the next pursuit's workgroups (MPC_SIDE_PRIORITY=0: all equal).  Measured at
+        // 4928x3264 (tools/ab_env_bench.sh): 4 740 against 4 660 Mpix/s, with two side streams for all slots (below).
+        int least = 0, greatest = 0;
+        (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
+        const bool prio = t.side_priority && least != greatest;
+        c->seq_prioritised = prio;
+        HIP_TRY(hipStreamCreateWithFlags(&c->seq_up, hipStreamNonBlocking));
+        HIP_TRY(prio ? hipStreamCreateWithPriority(&c->seq_compute, hipStreamNonBlocking, least) : hipStreamCreateWithFlags(&c->seq_compute, hipStreamNonBlocking));
+        for (auto& s : c->seq_down)
+            HIP_TRY(prio ? hipStreamCreateWithPriority(&s, hipStreamNonBlocking, greatest) : hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        for (hipEvent_t& e : c->seq_pursuit_done) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        for (hipEvent_t& e : c->seq_stripe_up) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        // blocking events: a thread waiting for the device sleeps instead of spinning (the entropy stage wants the cores)
+        for (auto& slot : c->seq_events)
+            for (hipEvent_t& e : slot) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventBlockingSync));
+    }
+    if (const mpc_status ws = ensure_workspace(c, t, static_cast<long long>(n_tc)); ws != MPC_OK) return ws;
+    // a single frame: nothing to overlap with, so its worker runs on the calling thread (no thread to start and to join) and
+    // polls the device instead of sleeping
+    const bool single = n_frames == 1;
+    // A pursuit on every CU leaves the small kernels behind the previous frames' pursuits (stream assembly, entropy phases: ~8 %
+    // of a frame's CU time) nowhere to run but the gap between two pursuits, where they are latency-bound and the chip idles for
+    // ~0.45 ms per 16 Mpixel frame.  With one CU in eight left free they run beside the pursuit instead.  Measured on one box
+    // (tools/ab_env_bench.sh, MPC_SEQ_WORKGROUPS = pursuit workgroups of 256): 4928x3264 K=32  256: 4 780, 240: 4 620, 224: 5 060,
+    // 216: 4 980, 208: 4 870 Mpix/s; 1920x1080 K=8  256: 3 300 - 3 790, 224: 4 150; 7680x4320 K=16  256: 5 570, 224: 5 860 (with
+    // 16 CUs the chains cannot keep up and the pursuits wait for them).
+    struct SeqWorkgroups {
+        mpc_context* c;
+        ~SeqWorkgroups() { c->seq_workgroups = 0; }
+    } seq_workgroups{c};
+    if (!single && c->num_cus >= 16) c->seq_workgroups = t.seq_workgroups >= 0 ? t.seq_workgroups : c->num_cus - c->num_cus / 8;
+    // The pipeline's streams.  `seq_compute`: the pursuits, one behind the other.  Side stream A: behind pursuit(f) (an event) the
+    // stream assembly and entropy phase 1 of frame f.  Side stream B: phase 2 and the container's copy of frame f, enqueued by the
+    // frame's worker once it has built the code tables from phase 1's statistics (mapped host memory written by the kernels
+    // themselves; the host waits on events only).  Pursuit(f) waits (events) for the assembly + phase 1 of frame f - 2 and for
+    // the phase 2 of frame f - 3, so nothing piles up; with the CUs the pursuits leave free (above) both chains run beside the
+    // pursuits of the following frames.  The shapes this replaced -- everything on one ordered queue; phase 2 alone on a side
+    // stream -- are in DESIGN.md 4 and 9.
+    hipStream_t pursuit_stream = c->seq_compute;
+    // Two side streams for all slots (MPC_SHARED_SIDE_STREAMS=0: one per slot): the runtime maps streams onto a handful
+    // of hardware queues, and a slot stream that lands on the pursuit stream's queue lines its kernels up behind the next
+    // pursuit -- with three streams in all nothing has to share.  `side_a`: stream assembly + phase 1;
+    // `down`: phase 2, the container's copy, the host route's copies.
+    // Measured in round 2 (all streams at one priority): per-slot streams are 4 % faster on 16 Mpixel frames (4 440 against
+    // 4 270 Mpix/s) and bimodal on 2 Mpixel frames, where the chains are as long as the pursuit's tail (2 960 or 2 260 Mpix/s
+    // from run to run; shared: 2 780 every time) -- so small frames share.  With the side streams prioritised (round 3) two
+    // shared ones are the faster choice for large frames too (4 740 against 4 690 Mpix/s with one per slot).
+    const bool shared_sides = t.shared_sides >= 0 ? t.shared_sides != 0 : (c->seq_prioritised || tiles < 100000);
+    std::future<void> phase2_enqueued[S];
+    EntropyBuffers ent[S];
+    if (!t.host_entropy)
+        for (size_t sl = 0; sl < alloc_slots; ++sl)
+            if (const mpc_status es = entropy_buffers(c->ent[sl], tiles, K, &ent[sl]); es != MPC_OK) return es;
+    ContainerJob jobs[S];
+    struct Pending {
+        std::future<std::pair<uint8_t*, size_t>> result;     // malloc'ed container, or {nullptr, 0}
+        int frame = -1;
+    } pending[S];
+    mpc_status st = MPC_OK;
+    auto collect = [&](Pending& p) {
+        if (p.frame < 0) return;
+        const std::pair<uint8_t*, size_t> blob = p.result.get();
+        if (st == MPC_OK && !blob.first) st = fail(MPC_ERR_HIP, "record download or container allocation failed");
+        if (st == MPC_OK) {
+            bytes[p.frame] = blob.first;
+            nbytes[p.frame] = blob.second;
+        } else {
+            std::free(blob.first);
+        }
+        p.frame = -1;
+    };
+#define MPC_SEQ_TRY(call)                                                                         \
+    {                                                                                             \
+        const hipError_t e_ = (call);                                                             \
+        if (e_ != hipSuccess) { st = fail(MPC_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); break; } \
+    }
+    auto dev_slot_base = [&](size_t sl) { return c->stage.data() + sl * dev_slot; };
+    auto host_slot_base = [&](size_t sl) { return c->host_stage.data() + sl * host_slot; };
+    // Host frames: frame g is copied into its slot's pinned image by a few threads and sent to the device while frame g - 1 is
+    // still being enqueued and encoded; its pursuit waits for the event behind the copy.
+    std::future<hipError_t> uploads[S];
+    auto start_upload = [&](int g) {
+        const int usl = g % static_cast<int>(slots);
+        collect(pending[usl]);            // the slot's previous frame is through
+        uint8_t* d_img = reinterpret_cast<uint8_t*>(dev_slot_base(usl));
+        uint8_t* pinned_rgb = reinterpret_cast<uint8_t*>(host_slot_base(usl));
+        const uint8_t* src = frames[g];
+        hipEvent_t ev_up = c->seq_events[usl][0];
+        hipStream_t up_stream = c->seq_up;
+        const int device = c->device;
+        uploads[usl] = std::async(single ? std::launch::deferred : std::launch::async, [=]() -> hipError_t {
+            // a 16 Mpixel frame: 48 MB staged at memcpy speed in 32 pieces, sent at PCIe speed behind them
+            hipError_t e = staged_upload(device, src, pinned_rgb, d_img, 0, img_bytes, 32, up_stream);
+            if (e == hipSuccess) e = hipSetDevice(device);
+            if (e == hipSuccess) e = hipEventRecord(ev_up, up_stream);
+            return e;
+        });
+    };
+    // a single host frame in row stripes (below); needs the persistent kernel (the step-synchronous cross-check path writes
+    // stripe order only).  Measured (tools/single_frame_trace.py, host RGB -> bytes): 4928x3264  1 / 2 / 3 / 4 stripes: 5.69 /
+    // 5.25 / 4.92 / 5.20 ms; 1920x1080: 1.24 / 1.42 / 1.45 / 1.63 ms -- every further launch costs a prologue (144 KiB of LDS per
+    // workgroup) and a tail, more than a 6 MB copy takes; 7680x4320: 9.5 / 8.3 / 8.1 ms with 1 / 3 / 4
+    const int single_stripes = t.single_stripes > 0 ? t.single_stripes
+                                                    : (img_bytes >= (size_t(80) << 20) ? 4 : (img_bytes >= (size_t(32) << 20) ? 3 : 1));
+    const bool striped_single = single && !on_device && single_stripes > 1 && tiles_y >= 4 * single_stripes && !t.steps_path;
+    if (!on_device && !striped_single) start_upload(0);
+    for (int f = 0; f < n_frames && st == MPC_OK; ++f) {
+        const int sl = f % static_cast<int>(slots);
+        Pending& slot = pending[sl];
+        collect(slot);                    // frame f - slots is done with this slot: its download and its entropy stage have finished
+        if (st != MPC_OK) break;
+        // how far the pursuits may run ahead of the small kernels behind them: pursuit(f) waits for the stream assembly + phase 1
+        // of frame f - lag_assembly and for the phase 2 of frame f - lag_phase2.  Measured (tools/ab_env_bench.sh, 4928x3264)
+        // while the pursuits still filled every CU: lags 2 / 3 -> 4 660 Mpix/s, 3 / 3 -> 4 610 - 4 690, 3 / 4 -> 4 000 - 4 300,
+        // 4 / 5 -> 4 090 - 4 680 (more slack let the chains of several frames pile up in front of one pursuit's end); with CUs
+        // left free for the chains 2 / 2, 2 / 3 and 3 / 4 are within 1 % of each other.
+        const int back = t.lag_phase2;
+        if (f >= back && phase2_enqueued[(f - back) % static_cast<int>(slots)].valid()) {
+            // frame f - back's phase 2 is on its slot's stream by now: this frame's pursuit starts behind it (the event is the one
+            // its worker recorded behind the container's copy; on the host route it is an old one and the wait is empty)
+            phase2_enqueued[(f - back) % static_cast<int>(slots)].get();
+            MPC_SEQ_TRY(hipStreamWaitEvent(pursuit_stream, c->seq_events[(f - back) % static_cast<int>(slots)][2], 0));
+        }
+        if (f >= t.lag_assembly)
+            MPC_SEQ_TRY(hipStreamWaitEvent(pursuit_stream, c->seq_events[(f - t.lag_assembly) % static_cast<int>(slots)][1], 0));
+        char* dbase = dev_slot_base(sl);
+        uint8_t* d_img = reinterpret_cast<uint8_t*>(dbase);
+        uint16_t* d_counts = reinterpret_cast<uint16_t*>(dbase + counts_at);
+        mpc_basis_choice* d_choices = reinterpret_cast<mpc_basis_choice*>(dbase + choices_at);
+        if (striped_single) {
+            // One frame from host memory: nothing to overlap its upload with but its own tile encode.  The frame goes up in row
+            // stripes and each stripe's tile encode starts behind its own copy (an event), writing its records where one launch
+            // over the whole frame would put them: the copy of stripe s + 1 runs beside the encode of stripe s.
+            uint8_t* pinned_rgb = reinterpret_cast<uint8_t*>(host_slot_base(sl));
+            MPC_SEQ_TRY(hipMemsetAsync(d_choices, 0, sizeof(mpc_basis_choice) * n_tc * K, pursuit_stream));
+            const size_t row_bytes = static_cast<size_t>(3) * width;
+            for (int sp = 0; sp < single_stripes && st == MPC_OK; ++sp) {
+                const int rb = static_cast<int>(static_cast<long long>(tiles_y) * sp / single_stripes);
+                const int re = static_cast<int>(static_cast<long long>(tiles_y) * (sp + 1) / single_stripes);
+                const size_t lo = row_bytes * static_cast<size_t>(8 * rb), hi = row_bytes * static_cast<size_t>(std::min(height, 8 * re));
+                MPC_SEQ_TRY(staged_upload(c->device, frames[f], pinned_rgb, d_img, lo, hi, 8, c->seq_up));
+                MPC_SEQ_TRY(hipEventRecord(c->seq_stripe_up[sp], c->seq_up));
+                MPC_SEQ_TRY(hipStreamWaitEvent(pursuit_stream, c->seq_stripe_up[sp], 0));
+                st = encode_batch_device(c, t, d_img, 1, 0, width, height, row_bytes, rb, re, quant, d_counts, d_choices, nullptr, nullptr,
+                                         pursuit_stream, true);
+            }
+        } else {
+            const uint8_t* d_rgb = frames[f];
+            if (!on_device) {
+                MPC_SEQ_TRY(uploads[sl].get());
+                MPC_SEQ_TRY(hipStreamWaitEvent(pursuit_stream, c->seq_events[sl][0], 0));
+                if (f + 1 < n_frames) start_upload(f + 1);
+                if (st != MPC_OK) break;
+                d_rgb = d_img;
+            }
+            st = encode_batch_device(c, t, d_rgb, 1, 0, width, height, static_cast<size_t>(3) * width, 0, tiles_y, quant, d_counts,
+                                     d_choices, nullptr, nullptr, pursuit_stream, false);
+        }
+        if (st != MPC_OK) break;
+        ContainerJob& job = jobs[sl];
+        job.side = shared_sides ? c->seq_down[0] : c->seq_down[sl];
+        job.down = shared_sides ? c->seq_down[1] : c->seq_down[sl];
+        job.phase1 = c->seq_events[sl][1];
+        job.done = c->seq_events[sl][2];
+        job.spin = single;
+        job.host_stage = &c->host_stage;
+        job.host_offset = sl * host_slot + route_at;
+        MPC_SEQ_TRY(hipEventRecord(c->seq_pursuit_done[sl], pursuit_stream));
+        MPC_SEQ_TRY(hipStreamWaitEvent(job.side, c->seq_pursuit_done[sl], 0));
+        st = container_begin(job, c, t.host_entropy ? nullptr : &ent[sl], t.triple_limit, dbase + streams_at, d_counts,
+                             reinterpret_cast<const uint32_t*>(d_choices), nullptr, nullptr, width, height, quant);
+        if (st != MPC_OK) break;
+        auto told = std::make_shared<std::promise<void>>();
+        phase2_enqueued[sl] = told->get_future();
+        slot.frame = f;
+        // the slot's worker: wait for the device, build the code tables, enqueue phase 2, collect the container
+        const int device = c->device;
+        const bool trace = t.trace;
+        const double t_enq = trace_ms();
+        ContainerJob* jp = &job;
+        slot.result = std::async(single ? std::launch::deferred : std::launch::async, [=]() -> std::pair<uint8_t*, size_t> {
+            struct Tell {                                      // whatever happens, the enqueuing thread is released once
+                std::shared_ptr<std::promise<void>> p;
+                bool done = false;
+                void operator()() { if (!done) p->set_value(); done = true; }
+                ~Tell() { (*this)(); }
+            } tell{told};
+            std::pair<uint8_t*, size_t> blob{nullptr, 0};
+            if (hipSetDevice(device) == hipSuccess && container_tables(*jp, [&] { tell(); }) == MPC_OK)
+                (void)container_collect(*jp, &blob.first, &blob.second);
+            if (trace) {
+                const double* e = jp->stamps;
+                std::fprintf(stderr, "[trace] frame %d enqueued %.2f | device done %.2f | symbols on host %.2f | coded %.2f | entropy: stats %.2f tables %.2f bytes %.2f\n",
+                             f, t_enq, e[0], jp->device_entropy ? e[4] : e[3], trace_ms(), e[1], e[2], e[4]);
+            }
+            return blob;
+        });
+    }
+#undef MPC_SEQ_TRY
+    for (auto& u : uploads)
+        if (u.valid()) (void)u.get();
+    for (int f = n_frames; f < n_frames + static_cast<int>(slots); ++f) collect(pending[f % static_cast<int>(slots)]);   // oldest first
+    (void)hipStreamSynchronize(c->seq_up);
+    (void)hipStreamSynchronize(pursuit_stream);
+    for (size_t sl = 0; sl < slots; ++sl) (void)hipStreamSynchronize(c->seq_down[sl]);
+    if (st != MPC_OK) {
+        for (int f = 0; f < n_frames; ++f) { std::free(bytes[f]); bytes[f] = nullptr; nbytes[f] = 0; }
+    }
+    return st;
+}
+
+JobSlot* job_slot(mpc_context* c, int slot) {
+    if (!c->jobs[slot]) c->jobs[slot] = std::make_unique<JobSlot>();
+    return c->jobs[slot].get();
+}
+}  // namespace
+
+extern "C" {
+
+// ---- records that are already on the device in whole-frame order -> container (the owner of a frame in the multi-GPU path,
+// after the stripe exchange; the rate-distortion sweep), in three steps so that the caller can keep the device busy meanwhile:
+//   begin    stream assembly + entropy phase 1 enqueued on `stream`; nothing is waited for
+//   tables   waits for phase 1, builds the code tables, enqueues phase 2 and the container's copy on the same stream
+//   collect  waits for the copy; the container
+// One job per slot at a time.  mpc_records_to_container_device is the three in a row on slot 0.
+mpc_status mpc_container_job_begin(mpc_context* c, int slot, const uint16_t* d_counts, const mpc_basis_choice* d_choices, int width,
+                                   int height, const double* quant, void* stream) {
+    return guarded([&]() -> mpc_status {
+    if (!c || !d_counts || !d_choices || slot < 0 || slot >= mpc_context::kSeqSlots) return fail(MPC_ERR_ARGUMENT, "bad argument");
+    if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device");
+    if (width < 1 || height < 1) return fail(MPC_ERR_ARGUMENT, "bad geometry");
+    const Tuning t = read_tuning();
+    const long long tiles = static_cast<long long>((width + 7) / 8) * ((height + 7) / 8);
+    std::lock_guard<std::recursive_mutex> one_host_call(c->host_calls);
+    HIP_TRY(hipSetDevice(c->device));
+    JobSlot* js = job_slot(c, slot);
+    if (js->stage != 0) return fail(MPC_ERR_ARGUMENT, "container job slot %d is busy", slot);
+    Carve measure;
+    mpc::StreamArgs measured{};
+    carve_stream_buffers(measure, tiles, c->K, true, &measured);
+    if (const mpc_status gs = js->dev.reserve(measure.at, "device staging"); gs != MPC_OK) return gs;
+    ContainerJob& j = js->job;
+    if (!j.phase1) {
+        HIP_TRY(hipEventCreateWithFlags(&j.phase1, hipEventDisableTiming | hipEventBlockingSync));
+        HIP_TRY(hipEventCreateWithFlags(&j.done, hipEventDisableTiming | hipEventBlockingSync));
+    }
+    j.side = j.down = static_cast<hipStream_t>(stream);
+    j.host_stage = &c->host_stage;
+    EntropyBuffers eb;
+    if (!t.host_entropy)
+        if (const mpc_status es = entropy_buffers(js->ent, static_cast<size_t>(tiles), c->K, &eb); es != MPC_OK) return es;
+    const mpc_status st = container_begin(j, c, t.host_entropy ? nullptr : &eb, t.triple_limit, js->dev.data(), d_counts,
+                                          reinterpret_cast<const uint32_t*>(d_choices), nullptr, nullptr, width, height, quant);
+    if (st == MPC_OK) js->stage = 1;
+    return st;
+    });
+}
+
+mpc_status mpc_container_job_tables(mpc_context* c, int slot) {
+    return guarded([&]() -> mpc_status {
+    if (!c || slot < 0 || slot >= mpc_context::kSeqSlots) return fail(MPC_ERR_ARGUMENT, "bad argument");
+    std::lock_guard<std::recursive_mutex> one_host_call(c->host_calls);
+    JobSlot* js = job_slot(c, slot);
+    if (js->stage != 1) return fail(MPC_ERR_ARGUMENT, "container job slot %d has not begun", slot);
+    HIP_TRY(hipSetDevice(c->device));
+    const mpc_status st = container_tables(js->job);
+    js->stage = st == MPC_OK ? 2 : 0;
+    return st;
+    });
+}
+
+mpc_status mpc_container_job_collect(mpc_context* c, int slot, uint8_t** bytes, size_t* nbytes) {
+    return guarded([&]() -> mpc_status {
+    if (!c || !bytes || !nbytes || slot < 0 || slot >= mpc_context::kSeqSlots) return fail(MPC_ERR_ARGUMENT, "bad argument");
+    std::lock_guard<std::recursive_mutex> one_host_call(c->host_calls);
+    JobSlot* js = job_slot(c, slot);
+    if (js->stage != 2) return fail(MPC_ERR_ARGUMENT, "container job slot %d has no tables yet", slot);
+    HIP_TRY(hipSetDevice(c->device));
+    js->stage = 0;
+    return container_collect(js->job, bytes, nbytes);
+    });
+}
+
+mpc_status mpc_container_job_cancel(mpc_context* c, int slot) {
+    return guarded([&]() -> mpc_status {
+    if (!c || slot < 0 || slot >= mpc_context::kSeqSlots) return fail(MPC_ERR_ARGUMENT, "bad argument");
+    std::lock_guard<std::recursive_mutex> one_host_call(c->host_calls);
+    if (!c->jobs[slot]) return MPC_OK;
+    JobSlot* js = job_slot(c, slot);
+    if (js->stage != 0 && c->device >= 0) {
+        HIP_TRY(hipSetDevice(c->device));
+        HIP_TRY(hipStreamSynchronize(js->job.side));       // whatever the job has enqueued has left its buffers
+    }
+    std::free(js->job.blob);
+    js->job.blob = nullptr;
+    js->job.nblob = 0;
+    js->stage = 0;
+    return MPC_OK;
+    });
+}
+
+mpc_status mpc_interleave_stripe_device(mpc_context* c, const uint16_t* d_part_counts, const mpc_basis_choice* d_part_choices, int width,
+                                        int height, int tile_row_begin, int tile_row_end, uint16_t* d_frame_counts,
+                                        mpc_basis_choice* d_frame_choices, void* stream) {
+    if (!c || !d_part_counts || !d_part_choices || !d_frame_counts || !d_frame_choices) return fail(MPC_ERR_ARGUMENT, "null argument");
+    if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device");
+    if (width < 1 || height < 1) return fail(MPC_ERR_ARGUMENT, "bad geometry");
+    const int tiles_x = (width + 7) / 8, tiles_y = (height + 7) / 8;
+    if (tile_row_begin < 0 || tile_row_end > tiles_y || tile_row_begin >= tile_row_end)
+        return fail(MPC_ERR_ARGUMENT, "tile rows [%d,%d) outside 0..%d", tile_row_begin, tile_row_end, tiles_y);
+    HIP_TRY(hipSetDevice(c->device));
+    const int err = mpc::launch_interleave_stripe(d_part_counts, reinterpret_cast<const uint32_t*>(d_part_choices), tiles_x, tiles_y, tile_row_begin,
+                                                  tile_row_end - tile_row_begin, c->K, d_frame_counts, reinterpret_cast<uint32_t*>(d_frame_choices), stream);
+    if (err != 0) return launch_failed(err);
+    return MPC_OK;
+}
+
+mpc_status mpc_records_to_container_device(mpc_context* c, const uint16_t* d_counts, const mpc_basis_choice* d_choices, int width,
+                                           int height, const double* quant, void* stream, uint8_t** bytes, size_t* nbytes) {
+    if (!bytes || !nbytes) return fail(MPC_ERR_ARGUMENT, "null argument");
+    if (!c) return fail(MPC_ERR_ARGUMENT, "null context");
+    std::lock_guard<std::recursive_mutex> one_host_call(c->host_calls);
+    mpc_status st = mpc_container_job_begin(c, 0, d_counts, d_choices, width, height, quant, stream);
+    if (st == MPC_OK) st = mpc_container_job_tables(c, 0);
+    if (st == MPC_OK) st = mpc_container_job_collect(c, 0, bytes, nbytes);
+    return st;
+}
+
+// The entropy stage alone, on streams the caller holds in host memory (what mpc_assemble_symbol_streams codes on the host):
+// upload, device entropy stage, container bytes.  *route (optional): 0 = coded on the device, 1 = the host route was taken.
+mpc_status mpc_code_symbol_streams_device(mpc_context* c, int width, int height, const double* quant, const uint16_t* counts,
+                                          const uint16_t* symbols, const unsigned long long* stream_off, uint8_t** bytes, size_t* nbytes,
+                                          int* route) {
+    return guarded([&]() -> mpc_status {
+    if (!c || !counts || !stream_off || !bytes || !nbytes || width < 1 || height < 1) return fail(MPC_ERR_ARGUMENT, "bad argument");
+    if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device");
+    const int K = c->K;
+    const size_t tiles = static_cast<size_t>((width + 7) / 8) * ((height + 7) / 8), n_tc = tiles * 3;
+    for (int s = 0; s < 6 * K; ++s)
+        if (stream_off[s + 1] < stream_off[s]) return fail(MPC_ERR_ARGUMENT, "stream offsets must not decrease");
+    const unsigned long long total = stream_off[6 * K];
+    if (stream_off[0] != 0 || total > 2ULL * n_tc * K || (total && !symbols)) return fail(MPC_ERR_ARGUMENT, "streams larger than a frame of this size can hold");
+    const Tuning t = read_tuning();
+    std::lock_guard<std::recursive_mutex> one_host_call(c->host_calls);
+    HIP_TRY(hipSetDevice(c->device));
+    if (route) *route = 1;
+    DeviceTemp d_counts, d_symbols, d_off;
+    struct Job : ContainerJob {                                 // on the null stream; the host route codes the caller's streams
+        ~Job() { if (phase1) (void)hipEventDestroy(phase1); if (done) (void)hipEventDestroy(done); }
+    } j;
+    j.h_counts = counts;
+    j.h_stream_off = stream_off;
+    j.h_symbols = symbols;
+    HIP_TRY(hipEventCreateWithFlags(&j.phase1, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&j.done, hipEventDisableTiming));
+    EntropyBuffers eb;
+    if (!t.host_entropy) {
+        if (const mpc_status es = entropy_buffers(c->ent[0], tiles, K, &eb); es != MPC_OK) return es;
+        const size_t n_off = 6 * static_cast<size_t>(K) + 1;
+        HIP_TRY(hipMalloc(&d_counts.p, sizeof(uint16_t) * n_tc));
+        HIP_TRY(hipMalloc(&d_symbols.p, sizeof(uint16_t) * (total ? total : 1)));
+        HIP_TRY(hipMalloc(&d_off.p, sizeof(unsigned long long) * n_off));
+        HIP_TRY(hipMemcpy(d_counts.p, counts, sizeof(uint16_t) * n_tc, hipMemcpyHostToDevice));
+        if (total) HIP_TRY(hipMemcpy(d_symbols.p, symbols, sizeof(uint16_t) * total, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_off.p, stream_off, sizeof(unsigned long long) * n_off, hipMemcpyHostToDevice));
+    }
+    mpc_status st = container_begin(j, c, t.host_entropy ? nullptr : &eb, t.triple_limit, nullptr, static_cast<const uint16_t*>(d_counts.p),
+                                    nullptr, static_cast<uint16_t*>(d_symbols.p), static_cast<unsigned long long*>(d_off.p), width, height,
+                                    quant);
+    if (st == MPC_OK) st = container_tables(j);
+    if (st == MPC_OK) st = container_collect(j, bytes, nbytes);
+    if (st == MPC_OK && route && j.device_entropy) *route = 0;
+    HIP_TRY(hipDeviceSynchronize());
+    return st;
+    });
+}
+
+mpc_status mpc_encode_images(mpc_context* c, const uint8_t* const* rgb_frames, int n_frames, int width, int height,
+                             const double* quant, uint8_t** bytes, size_t* nbytes) {
+    return guarded([&]() -> mpc_status { return encode_sequence(c, rgb_frames, false, n_frames, width, height, quant, bytes, nbytes); });
+}
+
+mpc_status mpc_encode_images_device(mpc_context* c, const uint8_t* const* d_rgb_frames, int n_frames, int width, int height,
+                                    const double* quant, uint8_t** bytes, size_t* nbytes) {
+    return guarded([&]() -> mpc_status { return encode_sequence(c, d_rgb_frames, true, n_frames, width, height, quant, bytes, nbytes); });
+}
+
+// compressed::encodeImage: one frame through the same stages
+mpc_status mpc_encode_image(mpc_context* c, const uint8_t* rgb, int width, int height, const double* quant,
+                            uint8_t** bytes, size_t* nbytes) {
+    if (!rgb || !bytes || !nbytes) return fail(MPC_ERR_ARGUMENT, "null argument");
+    return guarded([&]() -> mpc_status { return encode_sequence(c, &rgb, false, 1, width, height, quant, bytes, nbytes); });
+}
+
+mpc_status mpc_encode_image_device(mpc_context* c, const uint8_t* d_rgb, int width, int height, const double* quant,
+                                   uint8_t** bytes, size_t* nbytes) {
+    if (!d_rgb || !bytes || !nbytes) return fail(MPC_ERR_ARGUMENT, "null argument");
+    return guarded([&]() -> mpc_status { return encode_sequence(c, &d_rgb, true, 1, width, height, quant, bytes, nbytes); });
+}
+
+}  // extern "C"

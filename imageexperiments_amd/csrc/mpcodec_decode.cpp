@@ -1,0 +1,276 @@
+// mpcodec_decode.cpp -- product: the C ABI's decoder (container parsing on the host, tile reconstruction on the device), the
+// device distortion of the rate-distortion sweep, and the "-s" patch statistics.
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+#include <string>
+
+#include "host_codec.h"
+#include "host_stats.h"
+#include "mpc_internal.h"
+
+namespace {
+// FromCoeffsDynamic + RGBFromYUV for whole tiles on the device; d_quant: [3][K] doubles on the device
+mpc_status decode_tiles_on_device(mpc_context* c, const uint16_t* d_counts, const uint32_t* d_choices, const double* d_quant,
+                                         int K, int width, int height, uint8_t* d_rgb, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!c->d_flag) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_flag), sizeof(int)));
+    HIP_TRY(hipMemsetAsync(c->d_flag, 0, sizeof(int), s));
+    mpc::DecodeParams p{};
+    p.counts = d_counts;
+    p.choices = d_choices;
+    p.quant = d_quant;
+    p.K = K;
+    p.width = width;
+    p.height = height;
+    p.tiles_x = (width + 7) / 8;
+    p.tiles_y = (height + 7) / 8;
+    p.rgb = d_rgb;
+    p.error_flag = c->d_flag;
+    p.fast = c->fast ? 1 : 0;
+    const int err = mpc::launch_decode(dict_device(c), p, stream);
+    if (err != 0) return launch_failed(err);
+    return MPC_OK;
+}
+}  // namespace
+
+extern "C" {
+
+mpc_status mpc_decode_tiles_device(mpc_context* c, const uint16_t* d_counts, const mpc_basis_choice* d_choices,
+                                   const double* quant, int width, int height, uint8_t* d_rgb, void* stream) {
+    if (!c || !d_counts || !d_choices || !d_rgb) return fail(MPC_ERR_ARGUMENT, "null argument");
+    if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device");
+    if (width < 1 || height < 1) return fail(MPC_ERR_ARGUMENT, "bad geometry");
+    HIP_TRY(hipSetDevice(c->device));
+    const double* d_q = nullptr;
+    if (const mpc_status qs = call_quant(c, quant, static_cast<hipStream_t>(stream), &d_q); qs != MPC_OK) return qs;
+    return decode_tiles_on_device(c, d_counts, reinterpret_cast<const uint32_t*>(d_choices), d_q, c->K, width, height, d_rgb,
+                                  stream);
+}
+
+// the decoder's reconstruction compared with the original frame on the device (mp_distortion_kernel); the quantiser steps are
+// the container header's (mpc::header_quant), not the encoder's doubles
+mpc_status mpc_distortion_device(mpc_context* c, const uint16_t* d_counts, const mpc_basis_choice* d_choices, const double* quant,
+                                 const uint8_t* d_rgb, int width, int height, unsigned long long* d_sse, uint32_t* d_tile_sse,
+                                 void* stream) {
+    return guarded([&]() -> mpc_status {
+    if (!c || !d_counts || !d_choices || !d_rgb || !d_sse) return fail(MPC_ERR_ARGUMENT, "null argument");
+    if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback");
+    if (width < 1 || height < 1) return fail(MPC_ERR_ARGUMENT, "bad geometry %dx%d", width, height);
+    const long long tiles = static_cast<long long>((width + 7) / 8) * ((height + 7) / 8);
+    if (tiles * 3 >= (1LL << 31)) return fail(MPC_ERR_ARGUMENT, "frame too large");
+    HIP_TRY(hipSetDevice(c->device));
+    const double* q = quant ? quant : c->quant.data();
+    std::vector<double> carried(3 * static_cast<size_t>(c->K));
+    for (size_t i = 0; i < carried.size(); ++i) carried[i] = static_cast<double>(mpc::header_quant(q[i]));
+    const double* d_q = nullptr;
+    if (const mpc_status qs = call_quant(c, carried.data(), static_cast<hipStream_t>(stream), &d_q); qs != MPC_OK) return qs;
+    mpc::DistortionParams p{};
+    p.counts = d_counts;
+    p.choices = reinterpret_cast<const uint32_t*>(d_choices);
+    p.quant = d_q;
+    p.K = c->K;
+    p.width = width;
+    p.height = height;
+    p.tiles_x = (width + 7) / 8;
+    p.tiles_y = (height + 7) / 8;
+    p.original = d_rgb;
+    p.sse = d_sse;
+    p.tile_sse = d_tile_sse;
+    p.fast = c->fast ? 1 : 0;
+    const int err = mpc::launch_distortion(dict_device(c), p, stream);
+    if (err != 0) return launch_failed(err);
+    return MPC_OK;
+    });
+}
+
+// compressed::decodeImage: container parsing on the host, tile reconstruction on the device.  The stream's own
+// K and quantisation table are used (they need not match the context's); there is no host reconstruction.
+mpc_status mpc_decode_image(const mpc_context* cc, const uint8_t* bytes, size_t nbytes, uint8_t** rgb, int* width, int* height) {
+    return guarded([&]() -> mpc_status {
+    if (!cc || !bytes || !rgb || !width || !height) return fail(MPC_ERR_ARGUMENT, "null argument");
+    mpc_context* c = const_cast<mpc_context*>(cc);
+    if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback");
+    const bool trace = read_tuning().trace;
+    const double t_begin = trace_ms();
+    mpc::Streams s;
+    if (!mpc::read_compressed(bytes, nbytes, s)) return fail(MPC_ERR_BITSTREAM, "Invalid input data");
+    const double t_parsed = trace_ms();
+    std::lock_guard<std::recursive_mutex> one_host_call(c->host_calls);     // concurrent decodes share the staging buffers
+    if (s.block_size != c->block_size) return fail(MPC_ERR_ARGUMENT, "stream block size %d, context block size %d", s.block_size, c->block_size);
+    // The streams -- not the records -- cross PCIe (21 MB instead of 97 for a 16 Mpixel K = 32 frame) through the context's pinned
+    // host buffer and device staging area (grow-only, shared with the encoder); the records are rebuilt on the device
+    // (mp_stream_gather_kernel: the stream assembly's positions, read the other way).
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n_tc = s.lengths.size();
+    const size_t tiles = n_tc / 3;
+    if (n_tc != 3 * tiles || s.codes.size() != static_cast<size_t>(6 * s.K)) return fail(MPC_ERR_BITSTREAM, "Invalid bitstream");
+    std::vector<size_t> stream_at(static_cast<size_t>(6 * s.K) + 1, 0);
+    for (int i = 0; i < 6 * s.K; ++i) {
+        if ((i & 1) && s.codes[i].size() != s.codes[i - 1].size()) return fail(MPC_ERR_BITSTREAM, "Invalid bitstream");
+        stream_at[i + 1] = stream_at[i] + s.codes[i].size();
+    }
+    const size_t n_symbols = stream_at[6 * s.K];
+    for (size_t o = 0; o < n_tc; ++o)
+        if (s.lengths[o] > s.K) return fail(MPC_ERR_BITSTREAM, "Invalid bitstream");
+    const size_t px = static_cast<size_t>(s.width) * s.height * 3;
+    // uploaded (pinned, then the same layout on the device): counts | symbols | quant;  then on the device: records | the
+    // gather's scratch | pixels.  The pinned buffer holds the streams on their way in, later the pixels on their way out.
+    uint16_t* counts;
+    uint16_t* symbols;
+    double* q;
+    auto upload_layout = [&](char* base) {
+        Carve cv{base};
+        counts = cv.take<uint16_t>(n_tc);
+        symbols = cv.take<uint16_t>(n_symbols ? n_symbols : 1);
+        q = cv.take<double>(3 * static_cast<size_t>(s.K));
+        return cv.at;
+    };
+    const size_t upload_bytes = upload_layout(nullptr);
+    uint32_t* d_choices;
+    uint8_t* d_rgb;
+    mpc::StreamArgs sa{};
+    auto device_layout = [&](char* base) {
+        Carve cv{base};
+        cv.at = upload_bytes;
+        d_choices = cv.take<uint32_t>(n_tc * s.K);
+        carve_stream_buffers(cv, static_cast<long long>(tiles), s.K, false, &sa);
+        d_rgb = cv.take<uint8_t>(px);
+        return cv.at;
+    };
+    if (const mpc_status gs = c->host_stage.reserve(std::max(upload_bytes, Carve::up(px)), "pinned staging"); gs != MPC_OK) return gs;
+    if (const mpc_status gs = c->stage.reserve(device_layout(nullptr), "device staging"); gs != MPC_OK) return gs;
+    char* hbase = c->host_stage.data();
+    upload_layout(hbase);
+    mpc::parallel_jobs(6 * s.K + 1, [&](int job) {
+        if (job == 0) std::memcpy(counts, s.lengths.data(), sizeof(uint16_t) * n_tc);
+        else if (!s.codes[job - 1].empty())
+            std::memcpy(symbols + stream_at[job - 1], s.codes[job - 1].data(), sizeof(uint16_t) * s.codes[job - 1].size());
+    });
+    for (int ch = 0; ch < 3; ++ch)
+        for (int i = 0; i < s.K; ++i) q[ch * s.K + i] = static_cast<double>(s.quant[ch][i]);
+    char* dbase = c->stage.data();
+    upload_layout(dbase);                                       // counts, symbols, q: their device copies now
+    device_layout(dbase);
+    const double t_staged = trace_ms();
+    HIP_TRY(hipMemcpyAsync(dbase, hbase, upload_bytes, hipMemcpyHostToDevice, nullptr));
+    sa.counts = counts;
+    sa.symbols = symbols;
+    const int ge = mpc::launch_stream_gather(sa, d_choices, nullptr);
+    if (ge != 0) return launch_failed(ge);
+    const mpc_status st = decode_tiles_on_device(c, counts, d_choices, q, s.K, s.width, s.height, d_rgb, nullptr);
+    if (st != MPC_OK) return st;
+    HIP_TRY(hipDeviceSynchronize());
+    const double t_device = trace_ms();
+    int flag = 0;
+    HIP_TRY(hipMemcpy(&flag, c->d_flag, sizeof(int), hipMemcpyDeviceToHost));
+    if (flag) return fail(MPC_ERR_BITSTREAM, "Invalid bitstream");
+    uint8_t* out = static_cast<uint8_t*>(std::malloc(px ? px : 1));
+    if (!out) return fail(MPC_ERR_ALLOC, "out of memory");
+    // through pinned memory (a copy into fresh pageable pages is staged by the runtime on one thread), then a few threads fault
+    // the caller's pages in and copy
+    const hipError_t e = hipMemcpy(hbase, d_rgb, px, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { std::free(out); return fail(MPC_ERR_HIP, "HIP failure: %s", hipGetErrorString(e)); }
+    {
+        const uint8_t* src = reinterpret_cast<const uint8_t*>(hbase);
+        const size_t piece = ((px + 15) / 16 + 4095) & ~static_cast<size_t>(4095);
+        mpc::parallel_jobs(piece ? static_cast<int>((px + piece - 1) / piece) : 0, [&](int k) {
+            const size_t lo = piece * static_cast<size_t>(k), hi = std::min(px, lo + piece);
+            std::memcpy(out + lo, src + lo, hi - lo);
+        });
+    }
+    if (trace)
+        std::fprintf(stderr, "[trace] decode: parse %.2f ms | streams staged %.2f | upload + gather + reconstruct %.2f | pixels to the caller %.2f\n",
+                     t_parsed - t_begin, t_staged - t_parsed, t_device - t_staged, trace_ms() - t_device);
+    *rgb = out;
+    *width = s.width;
+    *height = s.height;
+    return MPC_OK;
+    });
+}
+
+// ---- "-s" patch statistics (Compression.cpp:200-302) ----
+struct mpc_patch_stats {
+    mpc_context* ctx;
+    mpc::PatchStats stats;
+    std::vector<uint8_t> mosaic;
+    std::vector<uint16_t> counts;
+    std::vector<uint32_t> choices;
+    mpc_patch_stats(mpc_context* c, unsigned seed) : ctx(c), stats(c->K, c->block_size, seed) {}
+};
+
+mpc_status mpc_patch_stats_create(mpc_context* c, unsigned seed, mpc_patch_stats** out) {
+    if (!c || !out) return fail(MPC_ERR_ARGUMENT, "null argument");
+    if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback");
+    try {
+        *out = new mpc_patch_stats(c, seed);
+    } catch (const std::bad_alloc&) { return fail(MPC_ERR_ALLOC, "out of memory"); }
+    return MPC_OK;
+}
+
+void mpc_patch_stats_destroy(mpc_patch_stats* s) { delete s; }
+
+mpc_status mpc_patch_stats_add_image(mpc_patch_stats* s, const uint8_t* rgb, int width, int height, int patches) {
+    return guarded([&]() -> mpc_status {
+    if (!s || !rgb) return fail(MPC_ERR_ARGUMENT, "null argument");
+    const int bs = s->stats.block_size, K = s->stats.K;
+    if (width < bs || height < bs || patches <= 0) return MPC_OK;            // Compression.cpp:233-236
+    if (width == bs || height == bs) return fail(MPC_ERR_ARGUMENT, "image of exactly one block: rand() %% 0 in the reference");
+    std::vector<int> xs, ys;
+    s->stats.sample_origins(width, height, patches, xs, ys);
+    // the patches as the tiles of a one-tile-high mosaic: tile p = patch p (tile order tx*1 + 0)
+    const size_t row = static_cast<size_t>(patches) * bs * 3;
+    s->mosaic.resize(row * bs);
+    for (int p = 0; p < patches; ++p)
+        for (int dy = 0; dy < bs; ++dy)
+            std::memcpy(s->mosaic.data() + dy * row + static_cast<size_t>(p) * bs * 3,
+                        rgb + 3 * (static_cast<size_t>(ys[p] + dy) * width + xs[p]), static_cast<size_t>(bs) * 3);
+    s->counts.resize(static_cast<size_t>(patches) * 3);
+    s->choices.resize(static_cast<size_t>(patches) * 3 * K);
+    const std::vector<double> ones(3 * static_cast<size_t>(K), 1.0);          // Compression.cpp:221-225
+    const mpc_status st = mpc_encode_tiles(s->ctx, s->mosaic.data(), patches * bs, bs, row, 0, 1, ones.data(), s->counts.data(),
+                                           reinterpret_cast<mpc_basis_choice*>(s->choices.data()), nullptr, nullptr);
+    if (st != MPC_OK) return st;
+    s->stats.accumulate(s->counts.data(), s->choices.data(), patches);
+    return MPC_OK;
+    });
+}
+
+mpc_status mpc_patch_stats_read(const mpc_patch_stats* s, double* out) {
+    if (!s || !out) return fail(MPC_ERR_ARGUMENT, "null argument");
+    const int K = s->stats.K;
+    for (int ch = 0; ch < 3; ++ch)
+        for (int kind = 0; kind < 2; ++kind)
+            for (int i = 0; i < K; ++i) {
+                const mpc::RunningStat& r = kind == 0 ? s->stats.coeff[ch][i] : s->stats.select[ch][i];
+                double* o = out + ((static_cast<size_t>(ch) * 2 + kind) * K + i) * 5;
+                o[0] = r.N; o[1] = r.min; o[2] = r.max; o[3] = r.mean; o[4] = r.sumSq;
+            }
+    return MPC_OK;
+}
+
+mpc_status mpc_patch_stats_report(const mpc_patch_stats* s, char** text, size_t* nbytes) {
+    return guarded([&]() -> mpc_status {
+    if (!s || !text || !nbytes) return fail(MPC_ERR_ARGUMENT, "null argument");
+    const std::string r = s->stats.report();
+    char* p = static_cast<char*>(std::malloc(r.size() + 1));
+    if (!p) return fail(MPC_ERR_ALLOC, "out of memory");
+    std::memcpy(p, r.c_str(), r.size() + 1);
+    *text = p;
+    *nbytes = r.size();
+    return MPC_OK;
+    });
+}
+
+int mpc_format_double(double v, char* buf, int cap) {
+    const std::string t = mpc::format_double(v);
+    if (!buf || cap <= static_cast<int>(t.size())) return -1;
+    std::memcpy(buf, t.c_str(), t.size() + 1);
+    return static_cast<int>(t.size());
+}
+
+double mpc_psnr(const uint8_t* original, const uint8_t* decoded, int width, int height) {
+    return mpc::psnr(original, decoded, width, height);
+}
+
+}  // extern "C"

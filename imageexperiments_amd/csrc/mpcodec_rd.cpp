@@ -25,16 +25,6 @@ namespace {
 constexpr int kSlots = 3;       // levels in flight: encoding, tables being built, container being collected
 static_assert(kSlots <= MPC_JOB_SLOTS, "one container job slot per level in flight");
 
-mpc_status fail(mpc_status st, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    std::vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    mpc_set_error_text(buf);
-    return st;
-}
-
 // everything a call owns; released (after the streams drained) on every way out
 struct Sweep {
     mpc_context* ctx = nullptr;

@@ -429,9 +429,9 @@ def test_natural_image_crops_bytes_equal_oracle(gpu, oracle, ctx32, octx32, mn_b
         assert bytes(ctx32.encode_image(crop)) == bytes(octx32.encode_image(crop)), (x0, y0)
 
 
-@pytest.mark.parametrize("env", [{"MPC_NO_SMALL": "1"}, {"MPC_PIPES": "1"}, {"MPC_PIPES": "4"}, {"MPC_FILTER": "0"}])
+@pytest.mark.parametrize("env", [{"MPC_PATH": "steps"}, {"MPC_PIPES": "1"}, {"MPC_PIPES": "4"}, {"MPC_FILTER": "0"}])
 def test_launch_configurations_do_not_change_records(gpu, oracle, monkeypatch, env):
-    """the large-batch kernel instantiation on a small frame, other sub-batch counts, the exhaustive sweep: same records"""
+    """the exhaustive sweep under both of its switch names, other sub-batch counts: same records"""
     import imageexperiments_amd as ia
     for k, v in env.items():
         monkeypatch.setenv(k, v)
