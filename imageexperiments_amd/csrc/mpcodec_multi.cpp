@@ -103,12 +103,30 @@ extern "C" mpc_status mpc_encode_images_multi(mpc_context* const* ctxs, int n_de
     const int tiles_x = (width + 7) / 8, tiles_y = (height + 7) / 8;
     if (n_devices == 1) return mpc_encode_images(ctxs[0], rgb_frames, n_frames, width, height, quant, bytes, nbytes);
     if (n_devices > tiles_y) return MPC_ERR_ARGUMENT;                    // a lane without a tile row
+    if (!ctxs[0]) return MPC_ERR_NO_DEVICE;
     const int N = n_devices, K = mpc_context_K(ctxs[0]);
+    // A frame's stripes come from different lanes and meet in ONE container whose header carries the owner's tables: lanes that
+    // differ in flavour (double / float) or, without a table for the call, in their own tables would mix two encoders in it.
+    const int fast0 = mpc_context_is_fast(ctxs[0]);
+    std::vector<double> quant0(3 * static_cast<size_t>(K)), quant_r(quant0.size());
+    if (!quant && mpc_context_get_quant(ctxs[0], quant0.data()) != MPC_OK) return MPC_ERR_ARGUMENT;
     for (int r = 0; r < N; ++r) {
         if (!ctxs[r] || mpc_context_device(ctxs[r]) < 0) return MPC_ERR_NO_DEVICE;
         if (mpc_context_K(ctxs[r]) != K || mpc_context_block_size(ctxs[r]) != 8) return MPC_ERR_ARGUMENT;
         for (int q = 0; q < r; ++q)
             if (ctxs[q] == ctxs[r]) return MPC_ERR_ARGUMENT;             // one context per lane (two lanes may share a DEVICE)
+        if (mpc_context_is_fast(ctxs[r]) != fast0) {
+            mpc_set_error_text(text("lane %d is %s, lane 0 is %s: all lanes must run the same flavour", r, fast0 ? "double" : "float",
+                                    fast0 ? "float" : "double").c_str());
+            return MPC_ERR_ARGUMENT;
+        }
+        if (!quant && r > 0) {
+            if (mpc_context_get_quant(ctxs[r], quant_r.data()) != MPC_OK) return MPC_ERR_ARGUMENT;
+            if (std::memcmp(quant_r.data(), quant0.data(), sizeof(double) * quant0.size()) != 0) {
+                mpc_set_error_text(text("lane %d's quantiser tables differ from lane 0's and the call gives none", r).c_str());
+                return MPC_ERR_ARGUMENT;
+            }
+        }
     }
     const size_t row_bytes = static_cast<size_t>(3) * width, frame_bytes = row_bytes * height;
     const size_t tiles = static_cast<size_t>(tiles_x) * tiles_y;

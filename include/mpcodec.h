@@ -273,7 +273,10 @@ mpc_status mpc_encode_images_device(mpc_context* ctx, const uint8_t* const* d_rg
 
 /* compressed::encodeImage for a sequence of equally sized frames on SEVERAL GPUs of one node from one process (what a
  * Compression.cpp-style caller gets with MPC_DEVICES=0,1,...: dropin/compressionlib_dropin.cpp).  ctxs[0 .. n_devices): one context
- * per lane, each created on the device the lane shall use (two lanes may name the same device, not the same context), same K.
+ * per lane, each created on the device the lane shall use (two lanes may name the same device, not the same context), same K and
+ * the same flavour (mpc_context_set_fast), and with quant == NULL the same quantiser tables: a frame's stripes meet in one
+ * container, so lanes that differ in any of these are refused with MPC_ERR_ARGUMENT (an explicit `quant` makes different context
+ * tables harmless and is allowed).
  * Every frame's tile rows are striped over the lanes (contiguous stripes, remainder to the first lanes); a step takes
  * n_devices frames, frame f of a step is owned by lane f, which pulls the other lanes' stripes of it (hipMemcpyPeerAsync), puts
  * them into the reference's tile order and produces the container.  bytes[i] / nbytes[i]: frame i's container (mpc_free),

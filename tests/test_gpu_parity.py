@@ -4,6 +4,8 @@ north_star's 1e-5 relative tolerance AND bit-exactly (the kernel keeps the oracl
 import numpy as np
 import pytest
 
+from pursuit_cases import adversarial_vectors as _adversarial_vectors, degenerate_frames, nan_vectors, near_tie_vectors
+
 pytestmark = pytest.mark.gpu
 
 REL_TOL_ENERGY = 1e-5      # BASELINE.json north_star: "within 1e-5 relative for the float residual energy"
@@ -329,27 +331,6 @@ def test_quality_sweep_on_a_crop_bytes_equal_oracle(gpu, oracle, bpp):
 
 # ---- the MFMA filter: records must not depend on it ------------------------------------------------------------------
 
-def _adversarial_vectors():
-    """Inputs that stress the filter's threshold logic: exact ties (mirror-symmetric and constant tiles), magnitudes from
-    the f32 subnormal range to beyond the f32 range, impulses, residuals that are rounding noise after the DC atom."""
-    rng = np.random.default_rng(2024)
-    v = []
-    x, y = np.meshgrid(np.arange(8), np.arange(8))
-    for f in (x, y, x + y, x - y, (x - 3.5) ** 2, np.abs(x - 3.5) + np.abs(y - 3.5), (x ^ y) & 1, (x // 4) * 2 + (y // 4)):
-        v.append(f.reshape(-1).astype(np.float64) * 17.0)                       # symmetric patterns: exact ties
-        v.append(f.T.reshape(-1).astype(np.float64) * 17.0 + 3.0)
-    for c in (1.0, 128.0, 255.0, 0.1, 1e-3):
-        v.append(np.full(64, c))                                               # flat: residual after DC is rounding noise
-    for k in (0, 7, 27, 63):
-        e = np.zeros(64); e[k] = 200.0; v.append(e)                             # impulses
-    base = rng.integers(0, 256, (6, 64)).astype(np.float64)
-    for scale in (1e-300, 1e-160, 1e-45, 1e-38, 1e-30, 1e-10, 1.0, 1e10, 1e30, 1e38, 1e39, 1e150, 1e300):
-        v.extend(list(base * scale))                                           # f32 under/overflow on the filter side
-    v.extend(list(rng.standard_normal((40, 64)) * 1e-20))
-    v.append(np.zeros(64))
-    return np.array(v)
-
-
 @pytest.mark.parametrize("channel", [0, 2])
 def test_filter_adversarial_vectors_bit_exact(ctx32, octx32, channel):
     v = _adversarial_vectors()
@@ -480,21 +461,8 @@ def test_degenerate_frames_bytes_equal_oracle(gpu, oracle, K):
     import imageexperiments_amd as ia
     ctx = ia.create_compression_context(K, 8, 3.5, device=0)
     octx = oracle.OracleContext(K, 8, 3.5)
-    H, W = 24, 40
-    yy, xx = np.mgrid[0:H, 0:W]
-    rng = np.random.default_rng(K)
-    frames = {
-        "black": np.zeros((H, W, 3), np.uint8),
-        "white": np.full((H, W, 3), 255, np.uint8),
-        "grey": np.full((H, W, 3), 128, np.uint8),
-        "checker": np.repeat((((xx + yy) & 1) * 255).astype(np.uint8)[:, :, None], 3, axis=2),
-        "stripes": np.stack([((xx & 1) * 255), ((yy & 1) * 255), (((xx >> 2) & 1) * 255)], axis=2).astype(np.uint8),
-        "hard noise": (rng.integers(0, 2, (H, W, 3)) * 255).astype(np.uint8),
-        "one pixel": np.array([[[200, 30, 90]]], np.uint8),
-        "one column": rng.integers(0, 256, (19, 1, 3)).astype(np.uint8),
-    }
+    frames = degenerate_frames(K)
     for name, rgb in frames.items():
-        rgb = np.ascontiguousarray(rgb)
         blob, ref = ctx.encode_image(rgb), octx.encode_image(rgb)
         assert blob == ref, name
         assert (ia.decode_image(blob, ctx) == oracle.decode_image(ref)).all(), name
@@ -541,13 +509,7 @@ def test_nan_vectors_end_the_pursuit_like_the_reference(ctx32, octx32):
     and CalcMPDynamic returns 0 (MatchingPursuit.cpp:50-54).  The filter must not lose that: NaN approximations keep
     every row as a survivor and the exact evaluations decide.  (Infinities are left out: round(inf / q) -> int is
     undefined behaviour in the reference.)"""
-    rng = np.random.default_rng(77)
-    v = rng.integers(0, 256, (12, 64)).astype(np.float64)
-    v[0, :] = np.nan
-    v[1, 0] = np.nan
-    v[2, 63] = np.nan
-    v[3, 17] = -np.nan
-    v[4, ::2] = np.nan
+    v = nan_vectors()
     for channel in (0, 1):
         counts, choices, energy, swept = ctx32.calc_mp(channel, v)
         for i in range(v.shape[0]):
@@ -564,15 +526,7 @@ def test_many_near_ties_on_one_lane(ctx32, octx32):
     """ADVICE r1 (survivor queue): residuals built as equal-weight sums of several base rows give a tile-channel three or
     more rows inside the filter window at once, next to clear neighbours in the same column group."""
     base, rows, det = ctx32.dictionary()
-    rng = np.random.default_rng(123)
-    v = []
-    for rep in range(48):
-        r0 = int(rng.integers(1, 500))
-        picks = [r0, r0 + 1, r0 + 2, r0 + 3, r0 + 4][: 3 + rep % 3]         # adjacent rows: the four rows of one lane
-        w = sum(base[p] for p in picks) * 300.0
-        v.append(w)
-        v.append(rng.integers(0, 256, 64).astype(np.float64))               # a clear neighbour
-    v = np.array(v)
+    v = near_tie_vectors(base)
     counts, choices, energy, swept = ctx32.calc_mp(0, v)
     for i in range(v.shape[0]):
         cnt, d, k, res, S = octx32.calc_mp(0, v[i])

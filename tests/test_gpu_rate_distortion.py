@@ -1,7 +1,7 @@
 """Rate-distortion sweep on the device (run with -m gpu): mpc_rate_distortion[_device] and mpc_distortion_device.
 
 For every level of a sweep: the container equals mpc_encode_image's with that table, the SSE equals numpy's exact sum against
-decode_image(container), and the PSNR equals calculate_psnr bit for bit.  Double contexts at K = 8 and 32 and one fast context."""
+decode_image(container), and the PSNR equals calculate_psnr bit for bit.  Double and fast contexts at K = 8 and 32."""
 import ctypes as C
 import hashlib
 import json
@@ -63,7 +63,7 @@ def _synthetic(oracle, W, H, seed):
     return oracle.synth_frame(W, H, seed)
 
 
-@pytest.mark.parametrize("K,fast", [(8, False), (32, False), (8, True)])
+@pytest.mark.parametrize("K,fast", [(8, False), (32, False), (8, True), (32, True)])
 def test_sweep_identities_on_ragged_frames(ia, oracle, photo, K, fast):
     ctx = _context(ia, K, fast)
     frames = [_synthetic(oracle, 203, 117, 11), _synthetic(oracle, 1, 1, 12), _synthetic(oracle, 9, 8, 13),
@@ -112,7 +112,7 @@ def _decode_tiles(ia, ctx, d_counts, d_choices, quant, W, H):
     return out.cpu().numpy()
 
 
-@pytest.mark.parametrize("K,fast", [(8, False), (32, False), (8, True)])
+@pytest.mark.parametrize("K,fast", [(8, False), (32, False), (8, True), (32, True)])
 def test_non_integer_table_uses_the_header_values(ia, oracle, K, fast):
     ctx = _context(ia, K, fast)
     rgb = _synthetic(oracle, 203, 117, 21)
@@ -140,7 +140,7 @@ def test_all_zero_frame_is_lossless(ia):
         assert ia.calculate_psnr(rgb, decoded) == float("inf")
 
 
-@pytest.mark.parametrize("K,fast", [(8, False), (32, False), (8, True)])
+@pytest.mark.parametrize("K,fast", [(8, False), (32, False), (8, True), (32, True)])
 def test_tile_sums_in_reference_order(ia, oracle, K, fast):
     import torch
     ctx = _context(ia, K, fast)
