@@ -109,6 +109,17 @@ def _bind_bitstream(L):
     L.mpc_streams_length.restype = C.c_size_t
     L.mpc_streams_copy.argtypes = [vp, C.c_int, _u16p]
     L.mpc_streams_free.argtypes = [vp]
+    L.mpc_read_compressed_coded.argtypes = [_u8p, C.c_size_t, C.POINTER(vp)]
+    L.mpc_streams_packed.argtypes = [vp, C.c_int]
+    L.mpc_streams_expected.argtypes = [vp, C.c_int]
+    L.mpc_streams_expected.restype = C.c_size_t
+    L.mpc_container_info.argtypes = [_u8p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.mpc_decode_images.argtypes = [vp, C.POINTER(_u8p), C.POINTER(C.c_size_t), C.c_int, C.POINTER(_u8p), C.POINTER(C.c_int),
+                                    C.POINTER(C.c_int)]
+    L.mpc_decode_images_device.argtypes = [vp, C.POINTER(_u8p), C.POINTER(C.c_size_t), C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t),
+                                           C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.mpc_decode_image_device.argtypes = [vp, _u8p, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.mpc_unpack_symbol_streams_device.argtypes = [vp, C.c_int, _u16p, _ullp, _u8p, _ullp, C.POINTER(_u16p), C.POINTER(C.c_size_t)]
     L.mpc_huffman_encode.argtypes = [_u16p, C.c_size_t, C.POINTER(_u8p), C.POINTER(C.c_size_t)]
     L.mpc_huffman_decode.argtypes = [_u8p, C.c_size_t, C.POINTER(_u16p), C.POINTER(C.c_size_t)]
     L.mpc_rle_encode.argtypes = [_u16p, C.c_size_t, C.POINTER(_u16p), C.POINTER(C.c_size_t)]
@@ -293,12 +304,24 @@ def assemble_symbol_streams(width, height, K, block_size, quant, counts, streams
     return _take_bytes(L, out, n)
 
 
-def read_compressed(blob):
-    """compressed::readCompressed (CompressedImage.cpp:635) -> dict(W,H,K,bs,quant[3,K],lengths,codes[6K])."""
+def container_info(blob):
+    """mpc_container_info: the container's header alone -> (width, height, K, block_size); MpcError(MPC_ERR_BITSTREAM) for a
+    header read_compressed refuses."""
+    L = load_library()
+    buf = np.frombuffer(blob, np.uint8)
+    W, H, K, bs = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    _check(L.mpc_container_info(buf.ctypes.data_as(_u8p), buf.size, C.byref(W), C.byref(H), C.byref(K), C.byref(bs)))
+    return W.value, H.value, K.value, bs.value
+
+
+def read_compressed(blob, coded=False):
+    """compressed::readCompressed (CompressedImage.cpp:635) -> dict(W,H,K,bs,quant[3,K],lengths,codes[6K]).
+    coded=True: the serial half alone (mpc_read_compressed_coded): codes as entropy-decoded -- still run-length packed where
+    packed[i], the step-0 coefficient streams still difference coded -- plus packed[6K] and expect[6K]."""
     L = load_library()
     buf = np.frombuffer(bytes(blob), np.uint8)
     h = C.c_void_p()
-    _check(L.mpc_read_compressed(buf.ctypes.data_as(_u8p), buf.size, C.byref(h)))
+    _check((L.mpc_read_compressed_coded if coded else L.mpc_read_compressed)(buf.ctypes.data_as(_u8p), buf.size, C.byref(h)))
     try:
         W, H, K, bs = C.c_int(), C.c_int(), C.c_int(), C.c_int()
         _check(L.mpc_streams_info(h, C.byref(W), C.byref(H), C.byref(K), C.byref(bs)))
@@ -310,8 +333,12 @@ def read_compressed(blob):
             if a.size:
                 _check(L.mpc_streams_copy(h, i, a.ctypes.data_as(_u16p)))
             return a
-        return dict(W=W.value, H=H.value, K=K.value, bs=bs.value, quant=quant, lengths=stream(-1),
-                    codes=[stream(i) for i in range(6 * K.value)])
+        out = dict(W=W.value, H=H.value, K=K.value, bs=bs.value, quant=quant, lengths=stream(-1),
+                   codes=[stream(i) for i in range(6 * K.value)])
+        if coded:
+            out["packed"] = [bool(L.mpc_streams_packed(h, i)) for i in range(6 * K.value)]
+            out["expect"] = [int(L.mpc_streams_expected(h, i)) for i in range(6 * K.value)]
+        return out
     finally:
         L.mpc_streams_free(h)
 
@@ -627,6 +654,64 @@ class CompressionContext:
 
     def encode_image_device(self, d_rgb, width, height, quant=None):
         return self.encode_images_device([d_rgb], width, height, quant)[0]
+
+    # -- sequence decode ---------------------------------------------------------------------------
+    @staticmethod
+    def _containers(blobs):
+        bufs = [np.frombuffer(b, np.uint8) for b in blobs]       # no copy: bytes, bytearray and arrays alike
+        n = len(bufs)
+        return bufs, (_u8p * n)(*[b.ctypes.data_as(_u8p) for b in bufs]), (C.c_size_t * n)(*[b.size for b in bufs])
+
+    def decode_images(self, blobs):
+        """mpc_decode_images: decodeImage for a list of containers in one call (parsed side by side, pipelined on the device).
+        Returns a list of uint8 [H,W,3] arrays on the library's buffers, as decode_image returns them."""
+        bufs, ptrs, sizes = self._containers(blobs)
+        n = len(bufs)
+        outs, W, H = (_u8p * n)(), (C.c_int * n)(), (C.c_int * n)()
+        _check(self.L.mpc_decode_images(self.h, ptrs, sizes, n, outs, W, H))
+        return [_take_view(self.L, outs[i], C.c_size_t(3 * W[i] * H[i])).reshape(H[i], W[i], 3) for i in range(n)]
+
+    def decode_images_device(self, blobs, out=None):
+        """mpc_decode_images_device: the same with the pixels left on the context's device.  out: a list of contiguous uint8
+        torch tensors there, each of at least 3*W*H elements (bytes behind that are left alone); None = allocated here from
+        container_info.  Returns a list of uint8 [H,W,3] tensors (views of `out` where given)."""
+        import torch
+        bufs, ptrs, sizes = self._containers(blobs)
+        n = len(bufs)
+        if out is None:
+            out = []
+            for b in bufs:
+                try:
+                    w, h, _, _ = container_info(b)
+                except MpcError:                                 # the call itself refuses the frame, in its turn, by its index
+                    w, h = 1, 1
+                out.append(torch.empty(3 * w * h, dtype=torch.uint8, device=f"cuda:{self.device}"))
+        if len(out) != n or any(t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous() for t in out):
+            raise ValueError("out: one contiguous uint8 device tensor per container")
+        d_ptrs = (C.c_void_p * n)(*[C.c_void_p(t.data_ptr()) for t in out])
+        caps = (C.c_size_t * n)(*[t.numel() for t in out])
+        W, H = (C.c_int * n)(), (C.c_int * n)()
+        torch.cuda.synchronize(self.device)                      # `out` may still be being written by the caller's streams
+        _check(self.L.mpc_decode_images_device(self.h, ptrs, sizes, n, d_ptrs, caps, W, H))
+        return [out[i].view(-1)[:3 * W[i] * H[i]].view(H[i], W[i], 3) for i in range(n)]
+
+    def decode_image_device(self, blob, out=None):
+        return self.decode_images_device([blob], None if out is None else [out])[0]
+
+    def unpack_symbol_streams_device(self, coded, packed, expect):
+        """mpc_unpack_symbol_streams_device: coded[6K] = the streams as entropy-decoded, packed[6K] = run-length packed or not,
+        expect[6K] = the symbols each must expand to -> all streams expanded and the step-0 coefficient streams summed, back to
+        back (uint16); MpcError(MPC_ERR_BITSTREAM) when a stream does not expand to exactly expect[i] symbols."""
+        K = len(coded) // 6                                      # the streams' own K, not the context's
+        symbols, off = _symbol_streams(K, coded)
+        flags = np.ascontiguousarray(packed, np.uint8)
+        want = np.ascontiguousarray(expect, np.uint64)
+        assert flags.size == 6 * K and want.size == 6 * K
+        out, n = _u16p(), C.c_size_t(0)
+        _check(self.L.mpc_unpack_symbol_streams_device(self.h, K, symbols.ctypes.data_as(_u16p),
+                                                       off.ctypes.data_as(C.POINTER(C.c_ulonglong)), flags.ctypes.data_as(_u8p),
+                                                       want.ctypes.data_as(C.POINTER(C.c_ulonglong)), C.byref(out), C.byref(n)))
+        return _take_u16(self.L, out, n)
 
     def interleave_stripe_device(self, d_part_counts, d_part_choices, width, height, tile_row_begin, tile_row_end, d_frame_counts,
                                  d_frame_choices, stream=0):

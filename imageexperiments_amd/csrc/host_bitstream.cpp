@@ -1239,6 +1239,8 @@ BitWriter container_head(int width, int height, int K, int block_size, const dou
 
 void parallel_jobs(int n, const std::function<void(int)>& body) { parallel_for(n, body); }
 
+int host_thread_count() { return host_threads(); }
+
 void parallel_io_jobs(int n, int workers, const std::function<void(int)>& body) {
     workers = std::min(std::min(workers, host_threads()), n);
     if (workers <= 1) {
@@ -1530,7 +1532,10 @@ uint8_t* encode_planar_records_malloc(int width, int height, int K, int block_si
 }
 
 
-bool read_compressed(const uint8_t* bytes, size_t nbytes, Streams& s) {
+// The serial half of readCompressed: everything the format chains from one code to the next (the codes are self-delimiting and
+// a stream's table sits where the stream before it ended), and nothing else.  No worker pool, no shared state: safe on several
+// threads at once.
+bool read_compressed_coded(const uint8_t* bytes, size_t nbytes, CodedStreams& s) {
     BitReader in(bytes, nbytes);
     if (static_cast<uint32_t>(in.get(32)) != kMagic) return false;
     s.width = static_cast<int>(in.get(32));
@@ -1566,28 +1571,42 @@ bool read_compressed(const uint8_t* bytes, size_t nbytes, Streams& s) {
             }
         }
     }
-    // The codes are self-delimiting, so the bit stream is parsed serially -- but only the entropy codes: run-length expansion
-    // (:660-678) and the DC sums (:690-705) of a stream need nothing from the streams behind it and run on the pool afterwards.
-    std::vector<std::vector<uint16_t>> packed(static_cast<size_t>(6 * K));
-    std::vector<char> is_packed(static_cast<size_t>(6 * K), 0);
-    std::vector<size_t> expect(static_cast<size_t>(6 * K), 0);
+    // Only the entropy codes are undone here: run-length expansion (:660-678) and the DC sums (:690-705) of a stream need nothing
+    // from the streams behind it (read_compressed does them on the pool, the sequence decoder on the device).
+    s.packed.assign(static_cast<size_t>(6 * K), 0);
+    s.expect.assign(static_cast<size_t>(6 * K), 0);
     for (int i = 0; i < 6 * K; ++i) {
-        expect[i] = expect_of[(static_cast<size_t>(i / 2) / K) * static_cast<size_t>(K) + static_cast<size_t>(i / 2) % K];
+        s.expect[i] = expect_of[(static_cast<size_t>(i / 2) / K) * static_cast<size_t>(K) + static_cast<size_t>(i / 2) % K];
         if (in.get(1) == 1) {
             const size_t packed_len = static_cast<size_t>(in.get(32));
-            is_packed[i] = 1;
-            if (!read_huffman_or_golomb(in, packed_len, packed[i])) return false;
+            s.packed[i] = 1;
+            if (!read_huffman_or_golomb(in, packed_len, s.codes[i])) return false;
+            // At most every third symbol of a run-length coded stream is a count and every other symbol expands to itself: a
+            // stream of n symbols expands to at least n - n/3.  More than the lengths stream allows cannot be valid, and whoever
+            // expands the stream may size its buffers by `expect`.
+            if (s.codes[i].size() - s.codes[i].size() / 3 > s.expect[i]) return false;
         } else {
-            if (!read_huffman_or_golomb(in, expect[i], s.codes[i])) return false;
+            if (!read_huffman_or_golomb(in, s.expect[i], s.codes[i])) return false;
         }
     }
+    return true;
+}
+
+bool read_compressed(const uint8_t* bytes, size_t nbytes, Streams& s) {
+    CodedStreams c;
+    if (!read_compressed_coded(bytes, nbytes, c)) return false;
+    const std::vector<uint8_t> is_packed = std::move(c.packed);
+    const std::vector<size_t> expect = std::move(c.expect);
+    s = std::move(static_cast<Streams&>(c));
+    const int K = s.K;
     std::vector<char> bad(static_cast<size_t>(6 * K), 0);
     parallel_for(6 * K, [&](int i) {
         if (is_packed[i]) {
             // run lengths come from the data: refuse to expand beyond what the lengths stream allows for this stream
+            const std::vector<uint16_t> packed = std::move(s.codes[i]);
             size_t expanded = 0;
-            if (!rle_decoded_size(packed[i].data(), packed[i].size(), expect[i], &expanded)) { bad[i] = 1; return; }
-            s.codes[i] = rle_decode(packed[i].data(), packed[i].size());
+            if (!rle_decoded_size(packed.data(), packed.size(), expect[i], &expanded)) { bad[i] = 1; return; }
+            s.codes[i] = rle_decode(packed.data(), packed.size());
         }
         if (s.codes[i].size() != expect[i]) { bad[i] = 1; return; }
         if (i == 1 || i == 2 * K + 1 || i == 4 * K + 1) {       // :690-705
@@ -1601,6 +1620,18 @@ bool read_compressed(const uint8_t* bytes, size_t nbytes, Streams& s) {
     for (int i = 0; i < 6 * K; ++i)
         if (bad[i]) return false;
     return true;
+}
+
+// the header alone (CompressedImage.cpp:640-655), with read_compressed's checks of it
+bool container_info(const uint8_t* bytes, size_t nbytes, int* width, int* height, int* K, int* block_size) {
+    if (nbytes < 14) return false;
+    BitReader in(bytes, nbytes);
+    if (static_cast<uint32_t>(in.get(32)) != kMagic) return false;
+    *width = static_cast<int>(in.get(32));
+    *height = static_cast<int>(in.get(32));
+    *K = static_cast<int>(in.get(8));
+    *block_size = static_cast<int>(in.get(8));
+    return !(*K < 1 || *K > 32 || *block_size < 1 || *block_size > 8 || *width < 1 || *height < 1);
 }
 
 Streams assemble_streams(int width, int height, int K, int block_size, const double* quant, const uint16_t* counts,

@@ -86,6 +86,20 @@ std::vector<uint8_t> write_compressed(const Streams& s);
 // readCompressed: codes come back with the DC differencing undone; false = invalid data
 bool read_compressed(const uint8_t* bytes, size_t nbytes, Streams& out);
 
+// The streams as entropy-decoded: codes[i] still run-length packed where packed[i] (the container's flag), the three step-0
+// coefficient streams (1, 2K + 1, 4K + 1) still difference coded; expect[i] = the symbols stream i must expand to.
+struct CodedStreams : Streams {
+    std::vector<uint8_t> packed;                    // [6K]
+    std::vector<size_t> expect;                     // [6K]
+};
+// The serial half of read_compressed (which is this + run-length expansion + DC sums on the worker pool): uses no pool and no
+// shared state, so several threads may parse containers side by side.  false = invalid data
+bool read_compressed_coded(const uint8_t* bytes, size_t nbytes, CodedStreams& out);
+// the header alone; false = not a container read_compressed would accept the header of
+bool container_info(const uint8_t* bytes, size_t nbytes, int* width, int* height, int* K, int* block_size);
+// worker threads of the host stages (MPC_HOST_THREADS, else the machine's, at most 16)
+int host_thread_count();
+
 // Build the streams from per-tile records in the reference's visiting order (tile t = tx*tiles_y + ty):
 // counts[t*3+ch], choices[(t*3+ch)*K + i] = deltaId | intCoeff << 16.   (encodeImage, CompressedImage.cpp:555-572)
 Streams assemble_streams(int width, int height, int K, int block_size, const double* quant /*[3*K]*/,

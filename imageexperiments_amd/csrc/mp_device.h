@@ -6,6 +6,7 @@
 //                    blocks, exact evaluation of the survivors in the reference's arithmetic (PursuitArgs, launch_pursuit)
 //   mp_streams.hip   stream assembly: the records -> the container's 6K symbol streams, live symbols only (StreamArgs)
 //   mp_entropy.hip   the per-symbol work of the entropy stage: run lengths, histograms, first appearances, code writing (EntropyArgs)
+//   mp_unpack.hip    the decoder's mirror of those two: run-length expansion and DC sums of coded streams (UnpackArgs)
 //   mp_kernels.hip   the decoder, the symbol histogram, and the product's own cross-check of the tile encoder: a STEP-SYNCHRONOUS
 //                    pursuit that correlates every row exactly (a short sequence of kernels per MP step over the active
 //                    tile-channels: init, fill, base sweep, detail sweep, finish, update), behind MPC_PATH=steps / MPC_FILTER=0
@@ -209,6 +210,36 @@ int launch_stream_gather(const StreamArgs& a, uint32_t* choices, void* stream);
 // records of the tile rows [row_begin, row_begin + rows) in stripe order -> their places in the whole frame's records
 int launch_interleave_stripe(const uint16_t* part_counts, const uint32_t* part_choices, int tiles_x, int tiles_y, int row_begin, int rows,
                              int K, uint16_t* frame_counts, uint32_t* frame_choices, void* stream);
+
+// ---- the decoder's per-symbol work in front of the gather (mp_unpack.hip): run-length expansion, DC sums ----
+constexpr int kUnpackBlock = 2048;      // coded symbols per workgroup
+constexpr unsigned kUnpackPacked = 1u;  // UnpackStream::flags: the stream is run-length packed
+
+struct UnpackStream {                   // one per stream, built by the host from sizes it has checked; [n_streams] is a sentinel
+    unsigned long long coded_off;       // first symbol of the stream in `coded`
+    unsigned long long coded_len;       // its symbols as entropy-decoded
+    unsigned long long expect;          // symbols it must expand to (from the lengths stream)
+    unsigned long long out_off;         // its first symbol in `symbols`: the sum of `expect` of the streams in front of it
+    unsigned blk_begin;                 // its first block; it has ceil(coded_len / kUnpackBlock) of them.  Sentinel: n_blocks
+    unsigned flags;
+};
+
+struct UnpackArgs {
+    const uint16_t* coded;              // the streams as entropy-decoded, back to back; an even number of symbols is allocated
+    const UnpackStream* streams;        // [n_streams + 1]
+    int n_streams;                      // 6K
+    unsigned n_blocks;
+    unsigned* blk_piece;                // [n_blocks][4] scratch, 16-byte aligned: state map and symbols emitted per entry state
+    unsigned* blk_entry;                // [n_blocks] scratch: the state a block is entered in
+    unsigned long long* blk_out;        // [n_blocks] scratch: the block's first output position in its stream
+    unsigned* stream_ok;                // [n_streams] scratch: the stream expands to exactly `expect` symbols
+    uint16_t* symbols;                  // out: sum(expect) symbols (an even number allocated), the layout launch_stream_gather reads
+    int* error;                         // |= 1 when a stream does not expand to `expect` symbols; nothing is written for that stream
+    int dc_stream[3];                   // the step-0 coefficient streams: 1, 2K + 1, 4K + 1
+    unsigned dc_blk_begin[4];           // their blocks of kUnpackBlock expanded symbols: prefix sums of ceil(expect / kUnpackBlock)
+    unsigned* dc_part;                  // [dc_blk_begin[3]] scratch: each block's sum of differences
+};
+int launch_unpack(const UnpackArgs& a, void* stream);                // hipError_t as int
 
 // ---- device-side entropy stage (mp_entropy.hip): everything that touches every symbol of the 1 + 6K streams ----
 constexpr int kEntBlock = 4096;         // symbols per scan block

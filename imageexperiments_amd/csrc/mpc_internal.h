@@ -3,6 +3,7 @@
 //   mpcodec_container.cpp  records on the device -> container (ContainerJob), the mpc_container_job_* API, the frame pipeline
 //   mpcodec_bitstream.cpp  host-only bitstream entry points
 //   mpcodec_decode.cpp     decode, distortion, patch statistics
+//   mpcodec_decode_seq.cpp the sequence decoder (mpc_decode_images*), the device unpack of coded streams
 #pragma once
 
 #include "../../include/mpcodec.h"
@@ -267,6 +268,24 @@ struct JobSlot {
 
 #pragma GCC visibility pop
 
+#pragma GCC visibility push(hidden)
+// A frame in flight in mpc_decode_images*: its own stream, buffers, error words and event, so that frames overlap and a call
+// waits for nothing but its own work.
+struct DecodeSlot {
+    GrowBuffer pinned{GrowBuffer::kPinned};   // the error words; the coded streams on their way in, later the pixels on their way out
+    GrowBuffer dev{GrowBuffer::kDevice};
+    hipStream_t stream = nullptr;
+    hipEvent_t done = nullptr;
+    hipEvent_t stamp[5] = {};                 // MPC_TRACE: before the upload, the unpack, the gather, the pixels' copy, after it
+    ~DecodeSlot() {
+        if (stream) (void)hipStreamDestroy(stream);
+        if (done) (void)hipEventDestroy(done);
+        for (hipEvent_t e : stamp)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+#pragma GCC visibility pop
+
 struct mpc_context {
     int K = 0, block_size = 0, device = -1;
     double bpp = 0.0;
@@ -302,6 +321,8 @@ struct mpc_context {
     // device-side entropy stage (mp_entropy.hip): per-slot buffers of the frame pipeline and mpc_code_symbol_streams_device
     EntropySlot ent[kSeqSlots];
     std::unique_ptr<JobSlot> jobs[kSeqSlots];        // mpc_container_job_*: records on the device -> container, in steps
+    static constexpr int kDecodeSlots = 6;           // frames in flight on the device in mpc_decode_images*
+    std::unique_ptr<DecodeSlot> dec[kDecodeSlots];   // created on first use
     // The exhaustive path's pursuit of a call is cut into sub-batches that run on `pipes` internal streams, each with its own
     // workspace: the latency-bound bookkeeping kernels of one sub-batch (finish, update, bucket, fill) overlap the
     // machine-filling sweeps of the other.  Fork/join with events on the caller's stream: still no host synchronisation,
@@ -325,6 +346,12 @@ struct mpc_context {
 };
 
 #pragma GCC visibility push(hidden)
+
+// ---- decode (mpcodec_decode.cpp) ----
+// FromCoeffsDynamic + RGBFromYUV for whole tiles on `stream`; d_quant: [3][K] doubles on the device; d_flag: the caller's error
+// word (zeroed on `stream` first, set when a record indexes outside its dictionary)
+mpc_status decode_tiles_on_device(mpc_context* c, const uint16_t* d_counts, const uint32_t* d_choices, const double* d_quant, int K,
+                                  int width, int height, uint8_t* d_rgb, int* d_flag, void* stream);
 
 // ---- context and tile encode (mpcodec_context.cpp) ----
 mpc::DictDevice dict_device(const mpc_context* c);

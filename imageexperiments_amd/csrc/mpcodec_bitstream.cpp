@@ -6,7 +6,7 @@
 #include "mpc_internal.h"
 
 struct mpc_streams {
-    mpc::Streams s;
+    mpc::CodedStreams s;            // `packed` and `expect` are empty in a handle of mpc_read_compressed
 };
 
 namespace {
@@ -100,6 +100,31 @@ mpc_status mpc_read_compressed(const uint8_t* bytes, size_t nbytes, mpc_streams*
     *out = h.release();
     return MPC_OK;
     });
+}
+
+mpc_status mpc_read_compressed_coded(const uint8_t* bytes, size_t nbytes, mpc_streams** out) {
+    return guarded([&]() -> mpc_status {
+    if (!bytes || !out) return fail(MPC_ERR_ARGUMENT, "null argument");
+    std::unique_ptr<mpc_streams> h(new mpc_streams);
+    if (!mpc::read_compressed_coded(bytes, nbytes, h->s)) return fail(MPC_ERR_BITSTREAM, "Invalid input data");
+    *out = h.release();
+    return MPC_OK;
+    });
+}
+
+int mpc_streams_packed(const mpc_streams* h, int index) {
+    return h && index >= 0 && index < static_cast<int>(h->s.packed.size()) ? h->s.packed[index] : 0;
+}
+
+size_t mpc_streams_expected(const mpc_streams* h, int index) {
+    if (!h || index < 0 || index >= static_cast<int>(h->s.codes.size())) return 0;
+    return index < static_cast<int>(h->s.expect.size()) ? h->s.expect[index] : h->s.codes[index].size();
+}
+
+mpc_status mpc_container_info(const uint8_t* bytes, size_t nbytes, int* width, int* height, int* K, int* block_size) {
+    if (!bytes || !width || !height || !K || !block_size) return fail(MPC_ERR_ARGUMENT, "null argument");
+    if (!mpc::container_info(bytes, nbytes, width, height, K, block_size)) return fail(MPC_ERR_BITSTREAM, "Invalid input data");
+    return MPC_OK;
 }
 
 mpc_status mpc_streams_info(const mpc_streams* h, int* width, int* height, int* K, int* block_size) {

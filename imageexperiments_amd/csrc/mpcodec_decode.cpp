@@ -9,13 +9,11 @@
 #include "host_stats.h"
 #include "mpc_internal.h"
 
-namespace {
-// FromCoeffsDynamic + RGBFromYUV for whole tiles on the device; d_quant: [3][K] doubles on the device
+// FromCoeffsDynamic + RGBFromYUV for whole tiles on the device
 mpc_status decode_tiles_on_device(mpc_context* c, const uint16_t* d_counts, const uint32_t* d_choices, const double* d_quant,
-                                         int K, int width, int height, uint8_t* d_rgb, void* stream) {
+                                  int K, int width, int height, uint8_t* d_rgb, int* d_flag, void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (!c->d_flag) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_flag), sizeof(int)));
-    HIP_TRY(hipMemsetAsync(c->d_flag, 0, sizeof(int), s));
+    HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(int), s));
     mpc::DecodeParams p{};
     p.counts = d_counts;
     p.choices = d_choices;
@@ -26,10 +24,17 @@ mpc_status decode_tiles_on_device(mpc_context* c, const uint16_t* d_counts, cons
     p.tiles_x = (width + 7) / 8;
     p.tiles_y = (height + 7) / 8;
     p.rgb = d_rgb;
-    p.error_flag = c->d_flag;
+    p.error_flag = d_flag;
     p.fast = c->fast ? 1 : 0;
     const int err = mpc::launch_decode(dict_device(c), p, stream);
     if (err != 0) return launch_failed(err);
+    return MPC_OK;
+}
+
+namespace {
+// the context's own error word (the single-frame entry points)
+mpc_status context_flag(mpc_context* c) {
+    if (!c->d_flag) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_flag), sizeof(int)));
     return MPC_OK;
 }
 }  // namespace
@@ -44,8 +49,9 @@ mpc_status mpc_decode_tiles_device(mpc_context* c, const uint16_t* d_counts, con
     HIP_TRY(hipSetDevice(c->device));
     const double* d_q = nullptr;
     if (const mpc_status qs = call_quant(c, quant, static_cast<hipStream_t>(stream), &d_q); qs != MPC_OK) return qs;
+    if (const mpc_status fs = context_flag(c); fs != MPC_OK) return fs;
     return decode_tiles_on_device(c, d_counts, reinterpret_cast<const uint32_t*>(d_choices), d_q, c->K, width, height, d_rgb,
-                                  stream);
+                                  c->d_flag, stream);
 }
 
 // the decoder's reconstruction compared with the original frame on the device (mp_distortion_kernel); the quantiser steps are
@@ -158,7 +164,8 @@ mpc_status mpc_decode_image(const mpc_context* cc, const uint8_t* bytes, size_t 
     sa.symbols = symbols;
     const int ge = mpc::launch_stream_gather(sa, d_choices, nullptr);
     if (ge != 0) return launch_failed(ge);
-    const mpc_status st = decode_tiles_on_device(c, counts, d_choices, q, s.K, s.width, s.height, d_rgb, nullptr);
+    if (const mpc_status fs = context_flag(c); fs != MPC_OK) return fs;
+    const mpc_status st = decode_tiles_on_device(c, counts, d_choices, q, s.K, s.width, s.height, d_rgb, c->d_flag, nullptr);
     if (st != MPC_OK) return st;
     HIP_TRY(hipDeviceSynchronize());
     const double t_device = trace_ms();

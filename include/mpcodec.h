@@ -227,6 +227,20 @@ size_t mpc_streams_length(const mpc_streams* s, int index);
 mpc_status mpc_streams_copy(const mpc_streams* s, int index, uint16_t* dst);
 void mpc_streams_free(mpc_streams* s);
 
+/* The serial half of readCompressed on its own (host only; uses no worker pool and no shared state: containers may be parsed on
+ * several threads side by side): an mpc_streams handle whose streams are the CODED ones, as entropy-decoded: still run-length
+ * packed where the container's flag says so, the three step-0 coefficient streams (1, 2K + 1, 4K + 1) still difference coded.
+ * mpc_streams_length / _copy / _info / _quant / _free work on it as on mpc_read_compressed's (index -1 = lengths, the same in
+ * both). */
+mpc_status mpc_read_compressed_coded(const uint8_t* bytes, size_t nbytes, mpc_streams** out);
+/* 1 = stream `index` is run-length packed; 0 for every stream of a handle of mpc_read_compressed */
+int mpc_streams_packed(const mpc_streams* s, int index);
+/* symbols stream `index` must expand to (from the lengths stream) */
+size_t mpc_streams_expected(const mpc_streams* s, int index);
+/* The container's header alone (host only): lets a caller size device buffers.  MPC_ERR_BITSTREAM for a header
+ * mpc_read_compressed refuses (too short, wrong magic, K, block size or geometry out of range). */
+mpc_status mpc_container_info(const uint8_t* bytes, size_t nbytes, int* width, int* height, int* K, int* block_size);
+
 /* huffman::huffmanEncode / huffmanDecode (Huffman.h:15-19), runLengthEncode / runLengthDecode (:12-13) */
 mpc_status mpc_huffman_encode(const uint16_t* data, size_t n, uint8_t** bytes, size_t* nbytes);
 mpc_status mpc_huffman_decode(const uint8_t* bytes, size_t nbytes, uint16_t** data, size_t* n);
@@ -325,6 +339,29 @@ mpc_status mpc_decode_tiles_device(mpc_context* ctx, const uint16_t* d_counts, c
  * reconstruction. */
 mpc_status mpc_decode_image(const mpc_context* ctx, const uint8_t* bytes, size_t nbytes, uint8_t** rgb, int* width,
                             int* height);
+
+/* compressed::decodeImage for n containers in one call (sizes, K and tables may differ from frame to frame; the block size must
+ * be the context's): the containers are parsed side by side on threads of the call's own (only what the format makes serial: the
+ * entropy codes), the coded streams cross PCIe, run lengths and DC differences are undone on the device (mp_unpack.hip) in
+ * front of the gather and the reconstruction, frames pipelined over slots.  rgb[i] (mpc_free) / width[i] / height[i] per frame;
+ * byte-identical to n calls of mpc_decode_image.  n_frames < 1 is MPC_ERR_ARGUMENT.  On failure nothing is returned;
+ * mpc_last_error names the first failing frame, the status is what mpc_decode_image gives for that container. */
+mpc_status mpc_decode_images(mpc_context* ctx, const uint8_t* const* bytes, const size_t* nbytes, int n_frames, uint8_t** rgb,
+                             int* width, int* height);
+/* The same with the pixels left in device memory: d_rgb[i] is caller-allocated on ctx's device, capacity[i] bytes >= 3*w*h of
+ * frame i (else MPC_ERR_ARGUMENT before anything is enqueued; mpc_container_info gives w and h), rows tightly packed; bytes
+ * behind 3*w*h are not touched.  Returns when every frame's pixels are complete. */
+mpc_status mpc_decode_images_device(mpc_context* ctx, const uint8_t* const* bytes, const size_t* nbytes, int n_frames,
+                                    uint8_t* const* d_rgb, const size_t* capacity, int* width, int* height);
+mpc_status mpc_decode_image_device(mpc_context* ctx, const uint8_t* bytes, size_t nbytes, uint8_t* d_rgb, size_t capacity,
+                                   int* width, int* height);
+/* The device half of that on its own, for tests (the counterpart of mpc_code_symbol_streams_device): host buffers in and out.
+ * coded = the 6K streams as entropy-decoded, back to back, stream i at [coded_off[i], coded_off[i + 1]); is_packed[6K];
+ * expect[6K].  symbols (mpc_free): sum(expect) u16, the streams expanded and the DC streams summed, back to back.  A stream
+ * that does not expand to exactly expect[i] symbols: MPC_ERR_BITSTREAM. */
+mpc_status mpc_unpack_symbol_streams_device(mpc_context* ctx, int K, const uint16_t* coded, const unsigned long long* coded_off,
+                                            const uint8_t* is_packed, const unsigned long long* expect, uint16_t** symbols,
+                                            size_t* n_symbols);
 
 /* ---- "-s" patch statistics, Compression.cpp:200-302 ----
  * The reference seeds one std::mt19937, and for every image draws `patches` origins x = rand() % (width - bs),
