@@ -83,7 +83,10 @@ struct Streams {
 
 // writeCompressed: codes are taken as the encoder holds them (DC coefficients not yet differenced)
 std::vector<uint8_t> write_compressed(const Streams& s);
-// readCompressed: codes come back with the DC differencing undone; false = invalid data
+// readCompressed: codes come back with the DC differencing undone; false = invalid data.  The decoder expands the streams on
+// the device and calls this on one refusal path only (a wrong block size or a length above K, to learn whether the streams
+// expand at all): it is the reference for what a decoder accepts (mpc_read_compressed, the host tests), and the decoder
+// holds itself to its verdict.
 bool read_compressed(const uint8_t* bytes, size_t nbytes, Streams& out);
 
 // The streams as entropy-decoded: codes[i] still run-length packed where packed[i] (the container's flag), the three step-0

@@ -2,8 +2,8 @@
 //   mpcodec_context.cpp    device dictionary, context, quantiser tables, pursuit launches, tile encode, timing, tuning switches
 //   mpcodec_container.cpp  records on the device -> container (ContainerJob), the mpc_container_job_* API, the frame pipeline
 //   mpcodec_bitstream.cpp  host-only bitstream entry points
-//   mpcodec_decode.cpp     decode, distortion, patch statistics
-//   mpcodec_decode_seq.cpp the sequence decoder (mpc_decode_images*), the device unpack of coded streams
+//   mpcodec_decode.cpp     tile reconstruction from records (mpc_decode_tiles_device), distortion, patch statistics
+//   mpcodec_decode_seq.cpp the decoder of containers (mpc_decode_image, mpc_decode_images*), the device unpack of coded streams
 #pragma once
 
 #include "../../include/mpcodec.h"
@@ -269,7 +269,7 @@ struct JobSlot {
 #pragma GCC visibility pop
 
 #pragma GCC visibility push(hidden)
-// A frame in flight in mpc_decode_images*: its own stream, buffers, error words and event, so that frames overlap and a call
+// A frame in flight in the decoder (mpc_decode_image, mpc_decode_images*; a call of one frame uses slot 0): its own stream, buffers, error words and event, so that frames overlap and a call
 // waits for nothing but its own work.
 struct DecodeSlot {
     GrowBuffer pinned{GrowBuffer::kPinned};   // the error words; the coded streams on their way in, later the pixels on their way out
@@ -300,9 +300,9 @@ struct mpc_context {
     double* d_quant_ring = nullptr;   // [kQuantSlots][3 * MPC_MAX_K]
     unsigned quant_next = 0;
     std::recursive_mutex host_calls;  // the host-buffer entry points share the staging buffers below
-    int* d_flag = nullptr;            // decode: set when a record indexes outside its dictionary
-    // grow-only staging for the host-buffer entry points (mpc_encode_tiles / mpc_encode_image(s) / mpc_decode_image): allocating
-    // and freeing them per call cost several times the encode itself
+    int* d_flag = nullptr;            // mpc_decode_tiles_device: set when a record indexes outside its dictionary
+    // grow-only staging for the host-buffer encode entry points (mpc_encode_tiles / mpc_encode_image(s)): allocating and freeing
+    // them per call cost several times the encode itself.  The decoder stages in its slots' own buffers (DecodeSlot).
     GrowBuffer stage{GrowBuffer::kDevice};
     GrowBuffer host_stage{GrowBuffer::kPinned};
     // mpc_encode_images: upload / compute / download streams and per-slot events (upload done, pursuit done, download done)
@@ -321,7 +321,7 @@ struct mpc_context {
     // device-side entropy stage (mp_entropy.hip): per-slot buffers of the frame pipeline and mpc_code_symbol_streams_device
     EntropySlot ent[kSeqSlots];
     std::unique_ptr<JobSlot> jobs[kSeqSlots];        // mpc_container_job_*: records on the device -> container, in steps
-    static constexpr int kDecodeSlots = 6;           // frames in flight on the device in mpc_decode_images*
+    static constexpr int kDecodeSlots = 6;           // frames in flight on the device in a decode call
     std::unique_ptr<DecodeSlot> dec[kDecodeSlots];   // created on first use
     // The exhaustive path's pursuit of a call is cut into sub-batches that run on `pipes` internal streams, each with its own
     // workspace: the latency-bound bookkeeping kernels of one sub-batch (finish, update, bucket, fill) overlap the

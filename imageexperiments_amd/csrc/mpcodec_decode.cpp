@@ -1,7 +1,7 @@
-// mpcodec_decode.cpp -- product: the C ABI's decoder (container parsing on the host, tile reconstruction on the device), the
-// device distortion of the rate-distortion sweep, and the "-s" patch statistics.
+// mpcodec_decode.cpp -- product: tile reconstruction on the device from records (decode_tiles_on_device, which the container
+// decoder of mpcodec_decode_seq.cpp ends in, and mpc_decode_tiles_device), the device distortion of the rate-distortion sweep, and
+// the "-s" patch statistics.
 #include <algorithm>
-#include <cstdio>
 #include <cstring>
 #include <string>
 
@@ -32,7 +32,7 @@ mpc_status decode_tiles_on_device(mpc_context* c, const uint16_t* d_counts, cons
 }
 
 namespace {
-// the context's own error word (the single-frame entry points)
+// the context's own error word (mpc_decode_tiles_device)
 mpc_status context_flag(mpc_context* c) {
     if (!c->d_flag) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_flag), sizeof(int)));
     return MPC_OK;
@@ -86,112 +86,6 @@ mpc_status mpc_distortion_device(mpc_context* c, const uint16_t* d_counts, const
     p.fast = c->fast ? 1 : 0;
     const int err = mpc::launch_distortion(dict_device(c), p, stream);
     if (err != 0) return launch_failed(err);
-    return MPC_OK;
-    });
-}
-
-// compressed::decodeImage: container parsing on the host, tile reconstruction on the device.  The stream's own
-// K and quantisation table are used (they need not match the context's); there is no host reconstruction.
-mpc_status mpc_decode_image(const mpc_context* cc, const uint8_t* bytes, size_t nbytes, uint8_t** rgb, int* width, int* height) {
-    return guarded([&]() -> mpc_status {
-    if (!cc || !bytes || !rgb || !width || !height) return fail(MPC_ERR_ARGUMENT, "null argument");
-    mpc_context* c = const_cast<mpc_context*>(cc);
-    if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback");
-    const bool trace = read_tuning().trace;
-    const double t_begin = trace_ms();
-    mpc::Streams s;
-    if (!mpc::read_compressed(bytes, nbytes, s)) return fail(MPC_ERR_BITSTREAM, "Invalid input data");
-    const double t_parsed = trace_ms();
-    std::lock_guard<std::recursive_mutex> one_host_call(c->host_calls);     // concurrent decodes share the staging buffers
-    if (s.block_size != c->block_size) return fail(MPC_ERR_ARGUMENT, "stream block size %d, context block size %d", s.block_size, c->block_size);
-    // The streams -- not the records -- cross PCIe (21 MB instead of 97 for a 16 Mpixel K = 32 frame) through the context's pinned
-    // host buffer and device staging area (grow-only, shared with the encoder); the records are rebuilt on the device
-    // (mp_stream_gather_kernel: the stream assembly's positions, read the other way).
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t n_tc = s.lengths.size();
-    const size_t tiles = n_tc / 3;
-    if (n_tc != 3 * tiles || s.codes.size() != static_cast<size_t>(6 * s.K)) return fail(MPC_ERR_BITSTREAM, "Invalid bitstream");
-    std::vector<size_t> stream_at(static_cast<size_t>(6 * s.K) + 1, 0);
-    for (int i = 0; i < 6 * s.K; ++i) {
-        if ((i & 1) && s.codes[i].size() != s.codes[i - 1].size()) return fail(MPC_ERR_BITSTREAM, "Invalid bitstream");
-        stream_at[i + 1] = stream_at[i] + s.codes[i].size();
-    }
-    const size_t n_symbols = stream_at[6 * s.K];
-    for (size_t o = 0; o < n_tc; ++o)
-        if (s.lengths[o] > s.K) return fail(MPC_ERR_BITSTREAM, "Invalid bitstream");
-    const size_t px = static_cast<size_t>(s.width) * s.height * 3;
-    // uploaded (pinned, then the same layout on the device): counts | symbols | quant;  then on the device: records | the
-    // gather's scratch | pixels.  The pinned buffer holds the streams on their way in, later the pixels on their way out.
-    uint16_t* counts;
-    uint16_t* symbols;
-    double* q;
-    auto upload_layout = [&](char* base) {
-        Carve cv{base};
-        counts = cv.take<uint16_t>(n_tc);
-        symbols = cv.take<uint16_t>(n_symbols ? n_symbols : 1);
-        q = cv.take<double>(3 * static_cast<size_t>(s.K));
-        return cv.at;
-    };
-    const size_t upload_bytes = upload_layout(nullptr);
-    uint32_t* d_choices;
-    uint8_t* d_rgb;
-    mpc::StreamArgs sa{};
-    auto device_layout = [&](char* base) {
-        Carve cv{base};
-        cv.at = upload_bytes;
-        d_choices = cv.take<uint32_t>(n_tc * s.K);
-        carve_stream_buffers(cv, static_cast<long long>(tiles), s.K, false, &sa);
-        d_rgb = cv.take<uint8_t>(px);
-        return cv.at;
-    };
-    if (const mpc_status gs = c->host_stage.reserve(std::max(upload_bytes, Carve::up(px)), "pinned staging"); gs != MPC_OK) return gs;
-    if (const mpc_status gs = c->stage.reserve(device_layout(nullptr), "device staging"); gs != MPC_OK) return gs;
-    char* hbase = c->host_stage.data();
-    upload_layout(hbase);
-    mpc::parallel_jobs(6 * s.K + 1, [&](int job) {
-        if (job == 0) std::memcpy(counts, s.lengths.data(), sizeof(uint16_t) * n_tc);
-        else if (!s.codes[job - 1].empty())
-            std::memcpy(symbols + stream_at[job - 1], s.codes[job - 1].data(), sizeof(uint16_t) * s.codes[job - 1].size());
-    });
-    for (int ch = 0; ch < 3; ++ch)
-        for (int i = 0; i < s.K; ++i) q[ch * s.K + i] = static_cast<double>(s.quant[ch][i]);
-    char* dbase = c->stage.data();
-    upload_layout(dbase);                                       // counts, symbols, q: their device copies now
-    device_layout(dbase);
-    const double t_staged = trace_ms();
-    HIP_TRY(hipMemcpyAsync(dbase, hbase, upload_bytes, hipMemcpyHostToDevice, nullptr));
-    sa.counts = counts;
-    sa.symbols = symbols;
-    const int ge = mpc::launch_stream_gather(sa, d_choices, nullptr);
-    if (ge != 0) return launch_failed(ge);
-    if (const mpc_status fs = context_flag(c); fs != MPC_OK) return fs;
-    const mpc_status st = decode_tiles_on_device(c, counts, d_choices, q, s.K, s.width, s.height, d_rgb, c->d_flag, nullptr);
-    if (st != MPC_OK) return st;
-    HIP_TRY(hipDeviceSynchronize());
-    const double t_device = trace_ms();
-    int flag = 0;
-    HIP_TRY(hipMemcpy(&flag, c->d_flag, sizeof(int), hipMemcpyDeviceToHost));
-    if (flag) return fail(MPC_ERR_BITSTREAM, "Invalid bitstream");
-    uint8_t* out = static_cast<uint8_t*>(std::malloc(px ? px : 1));
-    if (!out) return fail(MPC_ERR_ALLOC, "out of memory");
-    // through pinned memory (a copy into fresh pageable pages is staged by the runtime on one thread), then a few threads fault
-    // the caller's pages in and copy
-    const hipError_t e = hipMemcpy(hbase, d_rgb, px, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { std::free(out); return fail(MPC_ERR_HIP, "HIP failure: %s", hipGetErrorString(e)); }
-    {
-        const uint8_t* src = reinterpret_cast<const uint8_t*>(hbase);
-        const size_t piece = ((px + 15) / 16 + 4095) & ~static_cast<size_t>(4095);
-        mpc::parallel_jobs(piece ? static_cast<int>((px + piece - 1) / piece) : 0, [&](int k) {
-            const size_t lo = piece * static_cast<size_t>(k), hi = std::min(px, lo + piece);
-            std::memcpy(out + lo, src + lo, hi - lo);
-        });
-    }
-    if (trace)
-        std::fprintf(stderr, "[trace] decode: parse %.2f ms | streams staged %.2f | upload + gather + reconstruct %.2f | pixels to the caller %.2f\n",
-                     t_parsed - t_begin, t_staged - t_parsed, t_device - t_staged, trace_ms() - t_device);
-    *rgb = out;
-    *width = s.width;
-    *height = s.height;
     return MPC_OK;
     });
 }

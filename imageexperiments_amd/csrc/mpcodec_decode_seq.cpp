@@ -1,8 +1,9 @@
-// mpcodec_decode_seq.cpp -- product: the C ABI's sequence decoder.  mpc_decode_image parses a container on one host thread
-// while the device waits; nothing in the format is serial BETWEEN frames, so here the containers of a call are parsed side by
-// side on threads of the call's own, each doing only what the format chains from code to code (mpc::read_compressed_coded: the
-// entropy codes).  The coded streams cross PCIe and the per-symbol rest -- run-length expansion, DC sums -- happens on the
-// device (mp_unpack.hip) in front of the gather and the reconstruction, frames pipelined over slots of their own streams.
+// mpcodec_decode_seq.cpp -- product: the C ABI's decoder of containers: mpc_decode_image, mpc_decode_images, mpc_decode_images_device,
+// mpc_decode_image_device, all one call of decode_sequence.  Nothing in the format is serial BETWEEN frames, so the containers of a
+// call are parsed side by side on threads of the call's own (a call of one frame: on the calling thread), each doing only what the
+// format chains from code to code (mpc::read_compressed_coded: the entropy codes).  The coded streams cross PCIe and the per-symbol
+// rest -- run-length expansion, DC sums -- happens on the device (mp_unpack.hip) in front of the gather and the reconstruction,
+// frames pipelined over slots of their own streams.
 #include <algorithm>
 #include <atomic>
 #include <climits>
@@ -83,6 +84,7 @@ struct Sequence {
     mpc_context* c = nullptr;
     Tuning tuning;
     int n = 0, slots = 0;
+    bool single = false;                        // mpc_decode_image: the error text carries no "frame 0: "
     const uint8_t* const* bytes = nullptr;
     const size_t* nbytes = nullptr;
     uint8_t** rgb = nullptr;                    // host form: the results
@@ -113,6 +115,80 @@ struct Sequence {
     }
 };
 
+// One upload-and-unpack on a decode slot: the coded streams and the caller's own pieces through the slot's pinned buffer to the
+// device, the unpack kernels behind them on the slot's stream.  The caller sets the first block of fields.
+struct UnpackJob {
+    const UnpackPlan* plan = nullptr;
+    int K = 0;
+    const uint16_t* streams[6 * MPC_MAX_K] = {};    // the coded streams on the host, plan->table[i].coded_len symbols each
+    const void* extra[2] = {};                      // uploaded with them (the frame decoder's counts and quantiser steps)
+    size_t extra_bytes[2] = {};
+    size_t behind_bytes = 0;                        // device bytes the caller carves behind the unpack kernels' buffers
+    size_t result_bytes = 0;                        // what the caller brings back through `h_result`
+    bool pooled = false, trace = false;             // copy on the worker pool; stamp the slot's events 0 - 2
+    // set by upload_and_unpack
+    int* h_flags = nullptr;                         // pinned, preset to -1: where the caller copies ua.error[0..1] back to
+    char* h_result = nullptr;                       // pinned: free once the upload has left it (stream order)
+    const void* d_extra[2] = {};
+    char* d_behind = nullptr;
+    mpc::UnpackArgs ua{};
+    double staged_ms = 0.0;                         // trace_ms() with everything in pinned memory, nothing enqueued yet
+};
+
+mpc_status upload_and_unpack(DecodeSlot& slot, UnpackJob& j) {
+    const UnpackPlan& plan = *j.plan;
+    const int n = 6 * j.K;
+    constexpr size_t kHead = 256;                                   // the pinned buffer's head: the two error words coming back
+    uint16_t* coded;
+    mpc::UnpackStream* table;
+    char* extra[2];
+    auto upload_layout = [&](char* base) {                          // the same in pinned memory and on the device
+        Carve cv{base};
+        coded = cv.take<uint16_t>(plan.n_coded + 2);
+        table = cv.take<mpc::UnpackStream>(plan.table.size());
+        for (int k = 0; k < 2; ++k) extra[k] = cv.take<char>(j.extra_bytes[k]);
+        return cv.at;
+    };
+    const size_t upload_bytes = upload_layout(nullptr);
+    Carve scratch{nullptr, upload_bytes};
+    carve_unpack(scratch, plan, j.K, &j.ua);
+    const size_t behind_at = scratch.at;
+    if (const mpc_status gs = slot.pinned.reserve(kHead + std::max(upload_bytes, Carve::up(j.result_bytes)), "pinned decode staging"); gs != MPC_OK)
+        return gs;
+    if (const mpc_status gs = slot.dev.reserve(behind_at + j.behind_bytes, "device decode staging"); gs != MPC_OK) return gs;
+    j.h_flags = reinterpret_cast<int*>(slot.pinned.data());
+    j.h_result = slot.pinned.data() + kHead;
+    upload_layout(j.h_result);
+    const auto stage = [&](int job) {
+        if (job < 2) {
+            if (j.extra_bytes[job]) std::memcpy(extra[job], j.extra[job], j.extra_bytes[job]);
+        } else if (const mpc::UnpackStream& s = plan.table[job - 2]; s.coded_len)
+            std::memcpy(coded + s.coded_off, j.streams[job - 2], sizeof(uint16_t) * s.coded_len);
+    };
+    if (j.pooled) mpc::parallel_jobs(n + 2, stage);
+    else
+        for (int job = 0; job < n + 2; ++job) stage(job);
+    std::memcpy(table, plan.table.data(), sizeof(mpc::UnpackStream) * plan.table.size());
+    j.h_flags[0] = j.h_flags[1] = -1;
+    char* dbase = slot.dev.data();
+    upload_layout(dbase);                                           // coded, table, extra: their device copies now
+    scratch = Carve{dbase, upload_bytes};
+    carve_unpack(scratch, plan, j.K, &j.ua);
+    j.ua.coded = coded;
+    j.ua.streams = table;
+    for (int k = 0; k < 2; ++k) j.d_extra[k] = extra[k];
+    j.d_behind = dbase + behind_at;
+    j.staged_ms = trace_ms();
+    hipStream_t st = slot.stream;
+    if (j.trace) HIP_TRY(hipEventRecord(slot.stamp[0], st));
+    HIP_TRY(hipMemsetAsync(j.ua.error, 0, 2 * sizeof(int), st));
+    HIP_TRY(hipMemcpyAsync(dbase, j.h_result, upload_bytes, hipMemcpyHostToDevice, st));
+    if (j.trace) HIP_TRY(hipEventRecord(slot.stamp[1], st));
+    if (const int e = mpc::launch_unpack(j.ua, st); e != 0) return launch_failed(e);
+    if (j.trace) HIP_TRY(hipEventRecord(slot.stamp[2], st));
+    return MPC_OK;
+}
+
 // upload | unpack | gather | reconstruct | (host form) pixels down, on the slot's stream; returns with the frame complete
 mpc_status frame_on_slot(Sequence& q, int f, DecodeSlot& slot, const mpc::CodedStreams& s, const UnpackPlan& plan, double stamps[3]) {
     mpc_context* c = q.c;
@@ -120,88 +196,67 @@ mpc_status frame_on_slot(Sequence& q, int f, DecodeSlot& slot, const mpc::CodedS
     const int K = s.K;
     const size_t n_tc = s.lengths.size(), tiles = n_tc / 3;
     const size_t px = static_cast<size_t>(s.width) * s.height * 3;
-    constexpr size_t kHead = 256;                                   // the pinned buffer's head: the two error words coming back
-    uint16_t* counts;
-    uint16_t* coded;
-    mpc::UnpackStream* table;
-    double* quant;
-    auto upload_layout = [&](char* base) {
-        Carve cv{base};
-        counts = cv.take<uint16_t>(n_tc);
-        coded = cv.take<uint16_t>(plan.n_coded + 2);
-        table = cv.take<mpc::UnpackStream>(plan.table.size());
-        quant = cv.take<double>(3 * static_cast<size_t>(K));
-        return cv.at;
-    };
-    const size_t upload_bytes = upload_layout(nullptr);
-    mpc::UnpackArgs ua{};
+    // read_compressed_coded refuses any other K; `quant` and UnpackJob::streams are sized by MPC_MAX_K and must not lean on that
+    if (K < 1 || K > MPC_MAX_K) return fail(MPC_ERR_BITSTREAM, "Invalid input data");
+    double quant[3 * MPC_MAX_K];
+    for (int ch = 0; ch < 3; ++ch)
+        for (int i = 0; i < K; ++i) quant[ch * K + i] = static_cast<double>(s.quant[ch][i]);
     mpc::StreamArgs sa{};
     uint32_t* d_choices;
     uint8_t* d_pixels = nullptr;
-    auto device_layout = [&](char* base) {
+    auto behind_layout = [&](char* base) {                          // behind the unpacked streams: records | the gather's scratch | pixels
         Carve cv{base};
-        cv.at = upload_bytes;
-        carve_unpack(cv, plan, K, &ua);
         d_choices = cv.take<uint32_t>(n_tc * K);
         carve_stream_buffers(cv, static_cast<long long>(tiles), K, false, &sa);
         if (!q.d_rgb) d_pixels = cv.take<uint8_t>(px);
         return cv.at;
     };
-    if (const mpc_status gs = slot.pinned.reserve(kHead + std::max(upload_bytes, Carve::up(px)), "pinned decode staging"); gs != MPC_OK) return gs;
-    if (const mpc_status gs = slot.dev.reserve(device_layout(nullptr), "device decode staging"); gs != MPC_OK) return gs;
-    char* hbase = slot.pinned.data() + kHead;
-    int* h_flags = reinterpret_cast<int*>(slot.pinned.data());
-    upload_layout(hbase);
-    // A call of one frame has no other frame's thread to share the cores with: its copies go through the worker pool, as
-    // mpc_decode_image's do.  Otherwise every frame's thread copies its own.
+    UnpackJob j;
+    j.plan = &plan;
+    j.K = K;
+    for (int i = 0; i < 6 * K; ++i) j.streams[i] = s.codes[i].data();
+    j.extra[0] = s.lengths.data();
+    j.extra_bytes[0] = sizeof(uint16_t) * n_tc;
+    j.extra[1] = quant;
+    j.extra_bytes[1] = sizeof(double) * 3 * static_cast<size_t>(K);
+    j.behind_bytes = behind_layout(nullptr);
+    j.result_bytes = q.d_rgb ? 0 : px;
+    // A call of one frame has no other frame's thread to share the cores with: its copies go through the worker pool.  Otherwise
+    // every frame's thread copies its own.
     const bool pooled = q.n == 1;
-    const auto stage = [&](int job) {
-        if (job == 0) std::memcpy(counts, s.lengths.data(), sizeof(uint16_t) * n_tc);
-        else if (!s.codes[job - 1].empty())
-            std::memcpy(coded + plan.table[job - 1].coded_off, s.codes[job - 1].data(), sizeof(uint16_t) * s.codes[job - 1].size());
-    };
-    if (pooled) mpc::parallel_jobs(6 * K + 1, stage);
-    else
-        for (int job = 0; job <= 6 * K; ++job) stage(job);
-    std::memcpy(table, plan.table.data(), sizeof(mpc::UnpackStream) * plan.table.size());
-    for (int ch = 0; ch < 3; ++ch)
-        for (int i = 0; i < K; ++i) quant[ch * K + i] = static_cast<double>(s.quant[ch][i]);
-    h_flags[0] = h_flags[1] = -1;
-    char* dbase = slot.dev.data();
-    upload_layout(dbase);                                           // counts, coded, table, quant: their device copies now
-    device_layout(dbase);
+    j.pooled = pooled;
+    j.trace = trace;
+    if (const mpc_status us = upload_and_unpack(slot, j); us != MPC_OK) return us;
+    stamps[0] = j.staged_ms;
+    const uint16_t* counts = static_cast<const uint16_t*>(j.d_extra[0]);
+    behind_layout(j.d_behind);
     if (q.d_rgb) d_pixels = q.d_rgb[f];
-    stamps[0] = trace_ms();
     hipStream_t st = slot.stream;
-    if (trace) HIP_TRY(hipEventRecord(slot.stamp[0], st));
-    HIP_TRY(hipMemsetAsync(ua.error, 0, 2 * sizeof(int), st));
-    HIP_TRY(hipMemcpyAsync(dbase, hbase, upload_bytes, hipMemcpyHostToDevice, st));
-    if (trace) HIP_TRY(hipEventRecord(slot.stamp[1], st));
-    ua.coded = coded;
-    ua.streams = table;
-    if (const int e = mpc::launch_unpack(ua, st); e != 0) return launch_failed(e);
-    if (trace) HIP_TRY(hipEventRecord(slot.stamp[2], st));
     sa.counts = counts;
-    sa.symbols = ua.symbols;
+    sa.symbols = j.ua.symbols;
     if (const int e = mpc::launch_stream_gather(sa, d_choices, st); e != 0) return launch_failed(e);
-    if (const mpc_status ds = decode_tiles_on_device(c, counts, d_choices, quant, K, s.width, s.height, d_pixels, ua.error + 1, st);
+    if (const mpc_status ds = decode_tiles_on_device(c, counts, d_choices, static_cast<const double*>(j.d_extra[1]), K, s.width, s.height,
+                                                     d_pixels, j.ua.error + 1, st);
         ds != MPC_OK)
         return ds;
     if (trace) HIP_TRY(hipEventRecord(slot.stamp[3], st));
-    HIP_TRY(hipMemcpyAsync(h_flags, ua.error, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
-    if (!q.d_rgb) HIP_TRY(hipMemcpyAsync(hbase, d_pixels, px, hipMemcpyDeviceToHost, st));    // the upload has left the buffer: stream order
+    HIP_TRY(hipMemcpyAsync(j.h_flags, j.ua.error, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (!q.d_rgb) HIP_TRY(hipMemcpyAsync(j.h_result, d_pixels, px, hipMemcpyDeviceToHost, st));    // the upload has left the buffer: stream order
     if (trace) HIP_TRY(hipEventRecord(slot.stamp[4], st));
     HIP_TRY(hipEventRecord(slot.done, st));
     HIP_TRY(hipEventSynchronize(slot.done));                        // this frame's work only: no other context's, no other slot's
     stamps[1] = trace_ms();
-    if (h_flags[0] != 0 || h_flags[1] != 0) return fail(MPC_ERR_BITSTREAM, "Invalid bitstream");
+    // a stream that does not expand to its size is what mpc::read_compressed refuses, a record outside its dictionary the reconstruction
+    if (j.h_flags[0] != 0) return fail(MPC_ERR_BITSTREAM, "Invalid input data");
+    if (j.h_flags[1] != 0) return fail(MPC_ERR_BITSTREAM, "Invalid bitstream");
     if (!q.d_rgb) {
         uint8_t* out = static_cast<uint8_t*>(std::malloc(px ? px : 1));
         if (!out) return fail(MPC_ERR_ALLOC, "out of memory");
+        // a few threads fault the caller's fresh pages in and copy
         const size_t piece = pooled ? ((px + 15) / 16 + 4095) & ~static_cast<size_t>(4095) : px;
         const auto copy = [&](int k) {
             const size_t lo = piece * static_cast<size_t>(k), hi = std::min(px, lo + piece);
-            std::memcpy(out + lo, hbase + lo, hi - lo);
+            std::memcpy(out + lo, j.h_result + lo, hi - lo);
         };
         if (pooled && px) mpc::parallel_jobs(static_cast<int>((px + piece - 1) / piece), copy);
         else if (px) copy(0);                                       // the frames' copies run side by side on the call's threads
@@ -236,10 +291,18 @@ void parse_worker(Sequence& q) {
             if (q.failed_before(f)) return MPC_OK;
             HIP_TRY(hipSetDevice(c->device));
             if (!mpc::read_compressed_coded(q.bytes[f], q.nbytes[f], s)) return fail(MPC_ERR_BITSTREAM, "Invalid input data");
-            if (s.block_size != c->block_size)
-                return fail(MPC_ERR_ARGUMENT, "stream block size %d, context block size %d", s.block_size, c->block_size);
-            for (uint16_t length : s.lengths)
-                if (length > s.K) return fail(MPC_ERR_BITSTREAM, "Invalid bitstream");
+            const bool block_size_differs = s.block_size != c->block_size;
+            const bool too_long = std::any_of(s.lengths.begin(), s.lengths.end(), [&](uint16_t length) { return length > s.K; });
+            if (block_size_differs || too_long) {
+                // Refused here, before the device has expanded a stream.  A container whose streams do not expand either is
+                // invalid data first, whatever else is wrong with it: the host's expansion (the reference for what a decoder
+                // accepts) gives that verdict, on this path alone.
+                mpc::Streams expanded;
+                if (!mpc::read_compressed(q.bytes[f], q.nbytes[f], expanded)) return fail(MPC_ERR_BITSTREAM, "Invalid input data");
+                if (block_size_differs)
+                    return fail(MPC_ERR_ARGUMENT, "stream block size %d, context block size %d", s.block_size, c->block_size);
+                return fail(MPC_ERR_BITSTREAM, "Invalid bitstream");
+            }
             if (q.d_rgb && static_cast<size_t>(s.width) * s.height * 3 > q.capacity[f])
                 return fail(MPC_ERR_ARGUMENT, "capacity %zu for a frame of %dx%d", q.capacity[f], s.width, s.height);
             if (!plan_unpack(s.K, [&](int i) { return static_cast<unsigned long long>(s.codes[i].size()); }, s.packed.data(), nullptr,
@@ -283,8 +346,9 @@ mpc_status ensure_slots(mpc_context* c, int slots) {
     return MPC_OK;
 }
 
+// single: the call is mpc_decode_image's; its error text names no frame
 mpc_status decode_sequence(mpc_context* c, const uint8_t* const* bytes, const size_t* nbytes, int n_frames, uint8_t** rgb,
-                           uint8_t* const* d_rgb, const size_t* capacity, int* width, int* height) {
+                           uint8_t* const* d_rgb, const size_t* capacity, int* width, int* height, bool single = false) {
     if (!c || !bytes || !nbytes || !width || !height || (!rgb && !d_rgb) || (d_rgb && !capacity)) return fail(MPC_ERR_ARGUMENT, "null argument");
     if (n_frames < 1) return fail(MPC_ERR_ARGUMENT, "n_frames must be at least 1");
     if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback");
@@ -302,6 +366,7 @@ mpc_status decode_sequence(mpc_context* c, const uint8_t* const* bytes, const si
     q.c = c;
     q.tuning = read_tuning();
     q.n = n_frames;
+    q.single = single;
     q.slots = mpc_context::kDecodeSlots;
     q.bytes = bytes;
     q.nbytes = nbytes;
@@ -324,12 +389,22 @@ mpc_status decode_sequence(mpc_context* c, const uint8_t* const* bytes, const si
             std::free(rgb[f]);
             rgb[f] = nullptr;
         }
+    if (q.single) return fail(q.failed_status, "%s", q.failed_text.c_str());
     return fail(q.failed_status, "frame %d: %s", q.failed_frame, q.failed_text.c_str());
 }
 
 }  // namespace
 
 extern "C" {
+
+// compressed::decodeImage: one frame through the sequence decoder in its host form.  The stream's own K and quantisation table are
+// used (they need not match the context's); there is no host reconstruction.
+mpc_status mpc_decode_image(const mpc_context* c, const uint8_t* bytes, size_t nbytes, uint8_t** rgb, int* width, int* height) {
+    return guarded([&]() -> mpc_status {
+        if (!c || !bytes || !rgb || !width || !height) return fail(MPC_ERR_ARGUMENT, "null argument");
+        return decode_sequence(const_cast<mpc_context*>(c), &bytes, &nbytes, 1, rgb, nullptr, nullptr, width, height, true);
+    });
+}
 
 mpc_status mpc_decode_images(mpc_context* c, const uint8_t* const* bytes, const size_t* nbytes, int n_frames, uint8_t** rgb, int* width,
                              int* height) {
@@ -369,50 +444,22 @@ mpc_status mpc_unpack_symbol_streams_device(mpc_context* c, int K, const uint16_
         HIP_TRY(hipSetDevice(c->device));
         if (const mpc_status ss = ensure_slots(c, 1); ss != MPC_OK) return ss;
         DecodeSlot& slot = *c->dec[0];
-        uint16_t* up_coded;
-        mpc::UnpackStream* up_table;
-        auto upload_layout = [&](char* base) {
-            Carve cv{base};
-            up_coded = cv.take<uint16_t>(plan.n_coded + 2);
-            up_table = cv.take<mpc::UnpackStream>(plan.table.size());
-            return cv.at;
-        };
-        const size_t upload_bytes = upload_layout(nullptr);
-        mpc::UnpackArgs ua{};
-        auto device_layout = [&](char* base) {
-            Carve cv{base};
-            cv.at = upload_bytes;
-            carve_unpack(cv, plan, K, &ua);
-            return cv.at;
-        };
         const size_t out_bytes = sizeof(uint16_t) * plan.n_symbols;
-        constexpr size_t kHead = 256;
-        if (const mpc_status gs = slot.pinned.reserve(kHead + std::max(upload_bytes, Carve::up(out_bytes)), "pinned decode staging"); gs != MPC_OK)
-            return gs;
-        if (const mpc_status gs = slot.dev.reserve(device_layout(nullptr), "device decode staging"); gs != MPC_OK) return gs;
-        char* hbase = slot.pinned.data() + kHead;
-        int* h_flags = reinterpret_cast<int*>(slot.pinned.data());
-        upload_layout(hbase);
-        if (plan.n_coded) std::memcpy(up_coded, coded, sizeof(uint16_t) * plan.n_coded);
-        std::memcpy(up_table, plan.table.data(), sizeof(mpc::UnpackStream) * plan.table.size());
-        h_flags[0] = -1;
-        char* dbase = slot.dev.data();
-        upload_layout(dbase);
-        device_layout(dbase);
-        ua.coded = up_coded;
-        ua.streams = up_table;
+        UnpackJob j;
+        j.plan = &plan;
+        j.K = K;
+        for (int i = 0; i < 6 * K; ++i) j.streams[i] = coded + coded_off[i];
+        j.result_bytes = out_bytes;
+        if (const mpc_status us = upload_and_unpack(slot, j); us != MPC_OK) return us;
         hipStream_t st = slot.stream;
-        HIP_TRY(hipMemsetAsync(ua.error, 0, 2 * sizeof(int), st));
-        HIP_TRY(hipMemcpyAsync(dbase, hbase, upload_bytes, hipMemcpyHostToDevice, st));
-        if (const int e = mpc::launch_unpack(ua, st); e != 0) return launch_failed(e);
-        HIP_TRY(hipMemcpyAsync(h_flags, ua.error, sizeof(int), hipMemcpyDeviceToHost, st));
-        if (out_bytes) HIP_TRY(hipMemcpyAsync(hbase, ua.symbols, out_bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(j.h_flags, j.ua.error, sizeof(int), hipMemcpyDeviceToHost, st));
+        if (out_bytes) HIP_TRY(hipMemcpyAsync(j.h_result, j.ua.symbols, out_bytes, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipEventRecord(slot.done, st));
         HIP_TRY(hipEventSynchronize(slot.done));
-        if (h_flags[0] != 0) return fail(MPC_ERR_BITSTREAM, "Invalid bitstream");
+        if (j.h_flags[0] != 0) return fail(MPC_ERR_BITSTREAM, "Invalid bitstream");
         uint16_t* out = static_cast<uint16_t*>(std::malloc(out_bytes ? out_bytes : 2));
         if (!out) return fail(MPC_ERR_ALLOC, "out of memory");
-        if (out_bytes) std::memcpy(out, hbase, out_bytes);
+        if (out_bytes) std::memcpy(out, j.h_result, out_bytes);
         *symbols = out;
         *n_symbols = plan.n_symbols;
         return MPC_OK;

@@ -219,7 +219,9 @@ mpc_status mpc_code_symbol_streams_device(mpc_context* ctx, int width, int heigh
                                           int* route);
 
 /* readCompressed (CompressedImage.cpp:635): parse a container; streams come back with the DC differencing
- * undone.  index -1 = lengths, 0..6K-1 = codes[index]. */
+ * undone.  index -1 = lengths, 0..6K-1 = codes[index].  The expansion runs on the host.  The decoder expands on the device
+ * and uses this only to name the status of a container it refuses for its block size or a length above K; it is the
+ * reference for what the decoder accepts. */
 mpc_status mpc_read_compressed(const uint8_t* bytes, size_t nbytes, mpc_streams** out);
 mpc_status mpc_streams_info(const mpc_streams* s, int* width, int* height, int* K, int* block_size);
 mpc_status mpc_streams_quant(const mpc_streams* s, uint16_t* quant /* [3*K] */);
@@ -333,10 +335,12 @@ mpc_status mpc_container_job_cancel(mpc_context* ctx, int slot);
 mpc_status mpc_decode_tiles_device(mpc_context* ctx, const uint16_t* d_counts, const mpc_basis_choice* d_choices,
                                    const double* quant, int width, int height, uint8_t* d_rgb, void* stream);
 
-/* compressed::decodeImage (CompressedImage.h:75).  The container is parsed on the host and the tiles are
- * reconstructed on ctx's device with the K and quantisation tables the stream carries (they need not equal the
- * context's; the block size must).  A context without a device gets MPC_ERR_NO_DEVICE: there is no host
- * reconstruction. */
+/* compressed::decodeImage (CompressedImage.h:75): mpc_decode_images below, entered with one frame (the same code; the parse
+ * runs on the calling thread).  The entropy codes are parsed on the host, everything behind them happens on ctx's device, with
+ * the K and quantisation tables the stream carries (they need not equal the context's; the block size must).  Returns when
+ * this frame's pixels are complete; it waits for no other work on the device.  On failure *rgb holds no buffer and
+ * mpc_last_error says what was wrong (no frame index in front).  A context without a device gets MPC_ERR_NO_DEVICE: there
+ * is no host reconstruction. */
 mpc_status mpc_decode_image(const mpc_context* ctx, const uint8_t* bytes, size_t nbytes, uint8_t** rgb, int* width,
                             int* height);
 
@@ -344,8 +348,10 @@ mpc_status mpc_decode_image(const mpc_context* ctx, const uint8_t* bytes, size_t
  * be the context's): the containers are parsed side by side on threads of the call's own (only what the format makes serial: the
  * entropy codes), the coded streams cross PCIe, run lengths and DC differences are undone on the device (mp_unpack.hip) in
  * front of the gather and the reconstruction, frames pipelined over slots.  rgb[i] (mpc_free) / width[i] / height[i] per frame;
- * byte-identical to n calls of mpc_decode_image.  n_frames < 1 is MPC_ERR_ARGUMENT.  On failure nothing is returned;
- * mpc_last_error names the first failing frame, the status is what mpc_decode_image gives for that container. */
+ * one implementation serves every n, so a frame's pixels do not depend on the call it was decoded in.  n_frames < 1 is
+ * MPC_ERR_ARGUMENT.  On failure nothing is returned; mpc_last_error names the first failing frame ("frame N: ..."), the status is
+ * that container's: MPC_ERR_BITSTREAM for whatever mpc_read_compressed refuses and for a record outside its dictionary,
+ * MPC_ERR_ARGUMENT for a block size that is not the context's. */
 mpc_status mpc_decode_images(mpc_context* ctx, const uint8_t* const* bytes, const size_t* nbytes, int n_frames, uint8_t** rgb,
                              int* width, int* height);
 /* The same with the pixels left in device memory: d_rgb[i] is caller-allocated on ctx's device, capacity[i] bytes >= 3*w*h of

@@ -1,6 +1,6 @@
-"""The sequence decoder on the GPU (run with -m gpu): the unpack kernels (run-length expansion, DC sums) against the host's
-streams, mpc_decode_images / _device against single-frame decodes and the oracle, refusals that leave the context usable.
-Every equality is exact."""
+"""The container decoder on the GPU (run with -m gpu): the unpack kernels (run-length expansion, DC sums) against the host's
+streams, mpc_decode_image / mpc_decode_images / _device (one implementation, entered with one frame or many) against the oracle,
+refusals that leave the context usable and that are exactly the host parser's and the record rule's.  Every equality is exact."""
 import hashlib
 
 import numpy as np
@@ -176,14 +176,15 @@ def test_float_flavour(ia, oracle, blobs):
     fast.close()
 
 
-def test_three_full_size_frames(ia):
+def test_three_full_size_frames(ia, oracle):
     import bench
     W, H, K, q = bench.WORKLOADS["raise"]
     assert (W, H, K) == (4928, 3264, 32)
     ctx32 = ia.create_compression_context(K, 8, q, device=0)
     containers = ctx32.encode_images([bench.synth_frame(W, H, 12345 + f) for f in range(3)])
-    single = [hashlib.sha256(ia.decode_image(b, ctx32).tobytes()).hexdigest() for b in containers]
+    single = [hashlib.sha256(oracle.decode_image(b).tobytes()).hexdigest() for b in containers]     # the independent answer
     assert len(set(single)) == 3
+    assert [hashlib.sha256(ia.decode_image(b, ctx32).tobytes()).hexdigest() for b in containers] == single
     got = ctx32.decode_images(containers)
     assert [g.shape for g in got] == [(H, W, 3)] * 3
     assert [hashlib.sha256(g.tobytes()).hexdigest() for g in got] == single
@@ -208,9 +209,14 @@ def test_bad_frame_in_a_sequence(ia, ctx, oracle, small_blobs):
     good = (small_blobs * 3)[:9]
     assert len(good) == 9
     want = [oracle.decode_image(b) for b in good]
-    for bad in _bad_containers(ia, ctx, small_blobs):
+    # by the rule mpc_decode_image followed while it was a decoder of its own (read from that code: the host parser's refusal,
+    # then the record check; all three MPC_ERR_BITSTREAM)
+    expected = [ia.api.MPC_ERR_BITSTREAM] * 3
+    for bad, status in zip(_bad_containers(ia, ctx, small_blobs), expected):
         with pytest.raises(ia.MpcError) as alone:
             ia.decode_image(bad, ctx)
+        assert alone.value.status == status
+        assert "frame " not in str(alone.value), str(alone.value)
         for at in (0, 4, 9):
             seq = good[:at] + [bad] + good[at:]
             for call in (ctx.decode_images, ctx.decode_images_device):
@@ -219,6 +225,131 @@ def test_bad_frame_in_a_sequence(ia, ctx, oracle, small_blobs):
                 assert e.value.status == alone.value.status
                 assert f"frame {at}:" in str(e.value), str(e.value)
                 _equal_frames([np.asarray(x.cpu()) if hasattr(x, "cpu") else x for x in call(good)], want)
+
+
+# ---- the decoder refuses exactly what the host parser and the record rule refuse ----
+HOST_REFUSES, BLOCK_SIZE, LENGTH_ABOVE_K, RECORD_OUTSIDE, ACCEPT = range(5)
+
+
+def _verdict(ia, det_rows, x):
+    """What the decoder must do with container x, computed on the host from ia.read_compressed's streams (the host's own
+    expansion, no part of the decoder) and the oracle's block-row table; the first rule that matches decides."""
+    try:
+        s = ia.read_compressed(x)
+    except ia.MpcError as e:
+        assert e.status == ia.api.MPC_ERR_BITSTREAM
+        return HOST_REFUSES
+    if s["bs"] != 8:
+        return BLOCK_SIZE
+    K, nb = s["K"], len(det_rows)
+    lengths = s["lengths"].reshape(-1, 3).astype(np.int64)
+    if (lengths > K).any():
+        return LENGTH_ABOVE_K
+    for ch in range(3):
+        n = lengths[:, ch]
+        delta = np.zeros((len(n), K), np.int64)
+        for i in range(K):                      # stream i holds the tiles with more than i steps, in tile order
+            live = n > i
+            d = s["codes"][2 * K * ch + 2 * i].astype(np.int64)
+            assert d.size == live.sum()
+            delta[live, i] = d if i == 0 else (d >> 1) ^ -(d & 1)
+        choice = np.cumsum(delta, axis=1)
+        steps = np.arange(K)[None, :] < n[:, None]
+        in_base = steps & (choice >= 0) & (choice < nb)
+        # reconstruct_tile_pixel's rule (mp_kernels.hip): the dynamic dictionary is the base rows and the detail rows of every
+        # base row the tile-channel chose
+        size = nb + np.where(in_base, det_rows[np.clip(choice, 0, nb - 1)], 0).sum(axis=1)
+        if (steps & ((choice < 0) | (choice >= size[:, None]))).any():
+            return RECORD_OUTSIDE
+    return ACCEPT
+
+
+def _corpus(oracle):
+    """(index in FRAMES, [96 inputs]) of the eight containers below 100 000 bytes: 16 truncations, 64 single-bit flips anywhere,
+    16 in the header and the quantiser table"""
+    for n in (0, 1, 2, 5, 6, 7, 8, 10):
+        W, H, K, quality = FRAMES[n]
+        octx = oracle.OracleContext(K, 8, 0.0 if quality == "max" else quality)
+        blob = octx.encode_image(oracle.synth_frame(W, H, 100 + n), quant=np.ones((3, K)) if quality == "max" else None)
+        assert len(blob) < 100000
+        a = np.frombuffer(blob, np.uint8)
+        rng = np.random.default_rng([20241102, n])
+        xs = [bytes(a[:len(a) * k // 16]) for k in range(16)]
+        for bits, count in ((8 * len(a), 64), (8 * (14 + 6 * K), 16)):
+            for pos in rng.integers(0, bits, count):
+                c = a.copy()
+                c[pos // 8] ^= 1 << (pos % 8)
+                xs.append(bytes(c))
+        yield n, blob, xs
+
+
+def test_decoder_refuses_what_the_host_refuses(ia, ctx, oracle):
+    """768 damaged containers, each with exactly one expected outcome computed on the host (_verdict).  While mpc_decode_image
+    was mpc::read_compressed plus three checks this held by construction; the device now does the expansion, and this test is
+    what holds the decoder to the host parser.  Verdicts per container (index: host refuses, length above K, record outside, accepted): 0: 65, 3, 0, 28; 1: 49, 0, 3,
+    44; 2: 28, 0, 14, 54; 5: 34, 0, 0, 62; 6: 59, 1, 0, 36; 7: 36, 0, 15, 45; 8: 67, 0, 0, 29; 10: 62, 0, 0, 34."""
+    api = ia.api
+    det_rows = oracle.OracleContext(1, 8, 3.5).det_rows.astype(np.int64)
+    status_of = {HOST_REFUSES: api.MPC_ERR_BITSTREAM, BLOCK_SIZE: api.MPC_ERR_ARGUMENT, LENGTH_ABOVE_K: api.MPC_ERR_BITSTREAM,
+                 RECORD_OUTSIDE: api.MPC_ERR_BITSTREAM}
+    totals = [0] * 5
+    refused = accepted = compared = 0
+
+    def still_usable(blob):
+        assert np.array_equal(ia.decode_image(blob, ctx), oracle.decode_image(blob))
+
+    def check(x, verdict, sequences_too=False):
+        nonlocal refused, accepted, compared
+        totals[verdict] += 1
+        if verdict == ACCEPT:
+            w, h, _, _ = ia.container_info(x)
+            got = ia.decode_image(x, ctx)
+            assert got.shape == (h, w, 3)
+            if accepted % 8 == 0:
+                assert np.array_equal(got, oracle.decode_image(x))
+                compared += 1
+            assert ctx.decode_images([x])[0].shape == (h, w, 3)
+            assert tuple(ctx.decode_images_device([x])[0].shape) == (h, w, 3)
+            accepted += 1
+            return
+        with pytest.raises(ia.MpcError) as e:
+            ia.decode_image(x, ctx)
+        assert e.value.status == status_of[verdict], (verdict, str(e.value))
+        assert "frame " not in str(e.value), str(e.value)
+        if refused % 16 == 0 or sequences_too:
+            for call in (ctx.decode_images, ctx.decode_images_device):
+                with pytest.raises(ia.MpcError) as e:
+                    call([x])
+                assert e.value.status == status_of[verdict], (verdict, str(e.value))
+                assert "frame 0:" in str(e.value), str(e.value)
+        refused += 1
+
+    for n, blob, xs in _corpus(oracle):
+        assert _verdict(ia, det_rows, blob) == ACCEPT
+        for x in xs:
+            check(x, _verdict(ia, det_rows, x))
+        if n == 5:
+            still_usable(blob)                  # in the middle of the refusals
+    still_usable(blob)
+    assert totals == [400, 0, 4, 32, 332]
+    assert (refused, accepted, compared) == (436, 332, 42)
+    # The corpus leaves the block-size class empty: every flip of the header's block size also changes the tile count, and the
+    # host parser refuses first.  One hand-made input to fill it: byte 13 (the block size) of a valid container set to 4.
+    # The host parser refuses that too -- the lengths stream then describes a quarter of the tiles it must --, so it is
+    # verdict 1 like the flips and the class stays empty.
+    x = bytearray(blob)
+    x[13] = 4
+    x = bytes(x)
+    assert _verdict(ia, det_rows, x) == HOST_REFUSES
+    check(x, HOST_REFUSES, sequences_too=True)
+    # A frame of one tile at either block size keeps its lengths stream whole: the host parser accepts it and the block size is
+    # all that is wrong with it.
+    x = bytearray(oracle.OracleContext(8, 8, 3.5).encode_image(oracle.synth_frame(4, 3, 7)))
+    x[13] = 4
+    x = bytes(x)
+    assert _verdict(ia, det_rows, x) == BLOCK_SIZE
+    check(x, BLOCK_SIZE, sequences_too=True)
+    still_usable(blob)
 
 
 def test_container_job_survives_a_sequence_decode(ia, oracle, small_blobs):

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""decode_throughput.py -- the sequence decoder against the single-frame decoder, in one process.
+"""decode_throughput.py -- decoding n containers in one call against n single-frame calls (one decoder behind both), in one process.
     python tools/decode_throughput.py [--workloads raise,1080p] [--frames 1,4,16,32] [--rounds 5] [--once]
 For n distinct containers of a workload (bench.py's: synthetic frames, seeds 12345 + f, encoded untimed here):
-    a  a loop of decode_image          (mpc_decode_image: one frame, host pixels; the baseline)
+    a  a loop of decode_image          (mpc_decode_image: one frame a call, host pixels; the baseline)
     b  decode_images                   (mpc_decode_images: host pixels)
     c  decode_images_device            (mpc_decode_images_device: pixels left in device memory, buffers allocated before the clock)
 After a warm-up of every shape the three alternate, `rounds` times; host clock around calls that return with the pixels

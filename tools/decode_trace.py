@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""decode_trace.py -- mpc_decode_image with MPC_TRACE=1 on the reference's .mn fixture and on a synthetic 16 Mpixel frame (tuning aid)."""
+"""decode_trace.py -- mpc_decode_image with MPC_TRACE=1 (the decoder's per-frame line: parse, wait for the slot, staging, the device's
+upload / unpack / gather + reconstruct / copy-out, pixels to the caller) on the reference's .mn fixture and on a synthetic 16 Mpixel
+frame (tuning aid)."""
 import os
 import sys
 import time
