@@ -1,16 +1,9 @@
-// host_bitstream.cpp -- product host code: entropy stage + container (see host_bitstream.h).
+// host_bitstream.cpp -- product host code: everything of the entropy stage that touches symbols or bits one by one (see
+// host_bitstream.h).  Built without LTO: no per-symbol loop calls out of this file.
 #include "host_bitstream.h"
 
 #include <algorithm>
-#include <atomic>
-#include <condition_variable>
-#include <functional>
-#include <mutex>
-#include <cstdlib>
 #include <cstring>
-#include <exception>
-#include <numeric>
-#include <thread>
 
 namespace mpc {
 
@@ -193,11 +186,11 @@ uint32_t golomb_read(uint32_t m, BitReader& in) {
     return q * m + rem;
 }
 
-namespace {
+void golomb_encode(const uint16_t* data, size_t n, uint32_t m, BitWriter& out) {
+    for (size_t i = 0; i < n; ++i) golomb_write(data[i], m, out);
+}
 
 // Elias-Fano coding of a non-decreasing u16 sequence (BitBuffer.cpp:292-354)
-}  // namespace
-
 uint32_t elias_fano_length(size_t n, uint16_t max_symbol) {
     if (n == 0) return 0;
     const uint32_t m = bit_width(max_symbol), nb = bit_width(static_cast<uint32_t>(n));
@@ -389,9 +382,6 @@ struct Entry {
     uint32_t code;
 };
 
-}  // namespace
-
-namespace {
 // One pass over a stream: histogram (only as large as the largest symbol: no 64K-entry tables to clear per stream) and
 // the distinct symbols in order of first appearance -- the order the reference inserts them into its unordered_map.
 struct SymbolStats {
@@ -436,45 +426,6 @@ SymbolStats gather_stats(const uint16_t* data, size_t n) {
     return st;
 }
 
-// Number of symbols runLengthEncode would emit, without emitting them: a maximal run of L equal symbols becomes 1 symbol
-// (L = 1) or 3 (symbol, symbol, L - 2); runs beyond 0x8001 symbols are cut by the reference's counter limit (Huffman.cpp:
-// 262-267) -- if any run can be that long the literal state machine decides.
-size_t rle_encoded_size(const uint16_t* data, size_t n) {
-    if (n == 0) return 0;
-    size_t equal = 0, long_starts = 0;                          // data[i] == data[i-1]; ... and data[i-1] != data[i-2]
-    for (size_t i = 1; i < n; ++i) {
-        const bool e = data[i] == data[i - 1];
-        const bool before = i >= 2 && data[i - 1] == data[i - 2];
-        equal += e;
-        long_starts += e && !before;
-    }
-    if (equal < 0x8000) return (n - equal) + 2 * long_starts;
-    size_t packed = 0;
-    uint16_t prev = 0, run = 0;
-    bool fresh = true;
-    for (size_t i = 0; i < n; ++i) {
-        const uint16_t v = data[i];
-        if (v == prev && !fresh) {
-            if (++run == 1) ++packed;
-            else if (run >= 0x8000) { ++packed; run = 0; fresh = true; }
-        } else {
-            fresh = false;
-            if (run > 0) { ++packed; run = 0; }
-            prev = v;
-            ++packed;
-        }
-    }
-    if (run > 0) ++packed;
-    return packed;
-}
-
-void huffman_encode_with(const SymbolStats& st, const uint16_t* data, size_t n, BitWriter& out);
-}  // namespace
-
-// Huffman.cpp:46-163
-void huffman_encode(const uint16_t* data, size_t n, BitWriter& out) { huffman_encode_with(gather_stats(data, n), data, n, out); }
-
-namespace {
 // Everything of huffmanEncode that does not touch the symbols one by one: tree, canonical codes, the table header
 // written to `out`; codes and lengths by symbol (dense up to st.largest), the pseudo-EOF code, and the payload's bits.
 struct HuffmanTable {
@@ -587,13 +538,15 @@ void huffman_table(const SymbolStats& st, size_t n, BitWriter& out, HuffmanTable
     for (int l = 0; l < eof_leaf; ++l) t.payload_bits += freq[l] * static_cast<size_t>(t.length_of[symbols[l]]);
 }
 
-void huffman_encode_with(const SymbolStats& st, const uint16_t* data, size_t n, BitWriter& out) {
+}  // namespace
+
+// Huffman.cpp:46-163
+void huffman_encode(const uint16_t* data, size_t n, BitWriter& out) {
     HuffmanTable t;
-    huffman_table(st, n, out, t);
+    huffman_table(gather_stats(data, n), n, out, t);
     out.put_codes(data, n, t.code_of.data(), t.length_of.data(), t.payload_bits);
     out.put(t.eof_code, t.eof_length);
 }
-}  // namespace
 
 // Huffman.cpp:173-244
 bool huffman_decode(BitReader& in, std::vector<uint16_t>& out) {
@@ -856,98 +809,141 @@ bool huffman_decode(BitReader& in, std::vector<uint16_t>& out) {
     }
 }
 
-// Huffman.cpp:246-310
-std::vector<uint16_t> rle_encode(const uint16_t* data, size_t n) {
-    std::vector<uint16_t> out;
-    out.reserve(n);
+// ------------------------------------------------------------------------------------------------
+// run lengths (Huffman.cpp:246-310)
+// ------------------------------------------------------------------------------------------------
+namespace {
+// runLengthEncode's state machine: emit(symbol) for every symbol of the packed stream.  A maximal run of L equal symbols becomes
+// 1 symbol (L = 1) or 3 (symbol, symbol, L - 2); runs beyond 0x8001 symbols are cut by the reference's counter limit (:262-267).
+template <class Emit>
+void rle_pack(const uint16_t* data, size_t n, Emit&& emit) {
     uint16_t prev = 0, run = 0;
     bool fresh = true;
     for (size_t i = 0; i < n; ++i) {
         const uint16_t v = data[i];
         if (v == prev && !fresh) {
-            if (++run == 1) out.push_back(v);
-            else if (run >= 0x8000) { out.push_back(static_cast<uint16_t>(run - 1)); run = 0; fresh = true; }
+            if (++run == 1) emit(v);
+            else if (run >= 0x8000) { emit(static_cast<uint16_t>(run - 1)); run = 0; fresh = true; }
         } else {
             fresh = false;
-            if (run > 0) { out.push_back(static_cast<uint16_t>(run - 1)); run = 0; }
+            if (run > 0) { emit(static_cast<uint16_t>(run - 1)); run = 0; }
             prev = v;
-            out.push_back(v);
+            emit(v);
         }
     }
-    if (run > 0) out.push_back(static_cast<uint16_t>(run - 1));
+    if (run > 0) emit(static_cast<uint16_t>(run - 1));
+}
+
+// runLengthDecode's: emit(symbol, copies) for every packed symbol, copies = 1 for a symbol that stands for itself, the count
+// (0 included) for one that follows a pair; stops with false as soon as emit returns false
+template <class Emit>
+bool rle_unpack(const uint16_t* data, size_t n, Emit&& emit) {
+    uint16_t prev = 0;
+    bool expect_count = false, fresh = true;
+    for (size_t i = 0; i < n; ++i) {
+        const uint16_t v = data[i];
+        if (expect_count) {
+            if (!emit(prev, static_cast<size_t>(v))) return false;
+            expect_count = false;
+            fresh = true;
+        } else {
+            if (!emit(v, size_t(1))) return false;
+            if (v == prev && !fresh) expect_count = true;
+            fresh = false;
+            prev = v;
+        }
+    }
+    return true;
+}
+}  // namespace
+
+std::vector<uint16_t> rle_encode(const uint16_t* data, size_t n) {
+    std::vector<uint16_t> out;
+    out.reserve(n);
+    rle_pack(data, n, [&](uint16_t v) { out.push_back(v); });
     return out;
+}
+
+size_t rle_encoded_size(const uint16_t* data, size_t n) {
+    if (n == 0) return 0;
+    size_t equal = 0, long_starts = 0;                          // data[i] == data[i-1]; ... and data[i-1] != data[i-2]
+    for (size_t i = 1; i < n; ++i) {
+        const bool e = data[i] == data[i - 1];
+        const bool before = i >= 2 && data[i - 1] == data[i - 2];
+        equal += e;
+        long_starts += e && !before;
+    }
+    if (equal < 0x8000) return (n - equal) + 2 * long_starts;   // no run can reach the counter limit: the closed form
+    size_t packed = 0;
+    rle_pack(data, n, [&](uint16_t) { ++packed; });
+    return packed;
 }
 
 std::vector<uint16_t> rle_decode(const uint16_t* data, size_t n) {
     std::vector<uint16_t> out;
     out.reserve(n);
-    uint16_t prev = 0;
-    bool expect_count = false, fresh = true;
-    for (size_t i = 0; i < n; ++i) {
-        const uint16_t v = data[i];
-        if (expect_count) {
-            out.insert(out.end(), v, prev);
-            expect_count = false;
-            fresh = true;
-        } else {
-            out.push_back(v);
-            if (v == prev && !fresh) expect_count = true;
-            fresh = false;
-            prev = v;
-        }
-    }
+    rle_unpack(data, n, [&](uint16_t v, size_t copies) {
+        if (copies == 1) out.push_back(v);
+        else out.insert(out.end(), copies, v);
+        return true;
+    });
     return out;
 }
 
-// size rle_decode would produce, or false once it exceeds `limit`
 bool rle_decoded_size(const uint16_t* data, size_t n, size_t limit, size_t* size) {
     size_t total = 0;
-    uint16_t prev = 0;
-    bool expect_count = false, fresh = true;
-    for (size_t i = 0; i < n; ++i) {
-        const uint16_t v = data[i];
-        if (expect_count) {
-            total += v;
-            expect_count = false;
-            fresh = true;
-        } else {
-            ++total;
-            if (v == prev && !fresh) expect_count = true;
-            fresh = false;
-            prev = v;
-        }
-        if (total > limit) return false;
-    }
+    if (!rle_unpack(data, n, [&](uint16_t, size_t copies) { return (total += copies) <= limit; })) return false;
     *size = total;
     return true;
 }
 
-// CompressedImage.cpp:359-401.  The Golomb cost of each candidate M is the sum over DISTINCT symbols of
-// count x length -- same number as the reference's per-symbol loop.
-void write_huffman_or_golomb(const uint16_t* data, size_t n, BitWriter& out) {
-    const SymbolStats st = gather_stats(data, n);
-    BitWriter huff;
-    huffman_encode_with(st, data, n, huff);
-    size_t best = huff.bit_size();
-    int best_m = -1;
+// ------------------------------------------------------------------------------------------------
+// Huffman or Golomb (CompressedImage.cpp:359-401)
+// ------------------------------------------------------------------------------------------------
+namespace {
+// writeHuffmanOrGolomb's decision from a stream's statistics alone.  The Huffman cost is table + sum of count x length +
+// pseudo-EOF -- the size of the payload the reference codes in full to measure it; the Golomb cost of each candidate M is the
+// sum over DISTINCT symbols of count x length, the same number as the reference's per-symbol loop.
+struct CodeChoice {
+    HuffmanTable table;
+    BitWriter table_bits;            // the Huffman table as the stream carries it
+    size_t huffman_bits = 0;         // table + codes + pseudo-EOF
+    int m = -1;                      // the Golomb parameter that beats Huffman and every M before it; -1 = Huffman
+    size_t golomb_bits = 0;          // 16 bits of M + codes
+};
+
+void choose_code(const SymbolStats& st, size_t n, CodeChoice& c) {
+    huffman_table(st, n, c.table_bits, c.table);
+    c.huffman_bits = c.table_bits.bit_size() + c.table.payload_bits + c.table.eof_length;
+    size_t best = c.huffman_bits;
     for (int m = 1; m < 2048; m = (m & 1) ? m + 1 : (m << 1) - 1) {
         size_t estimate = 16;
-        for (uint16_t s : st.distinct) estimate += static_cast<size_t>(st.hist[s]) * golomb_length(s, static_cast<uint32_t>(m));
-        if (estimate < best) { best = estimate; best_m = m; }
+        for (uint16_t s : st.distinct) {                        // a candidate is out as soon as its partial sum reaches the best so far
+            estimate += static_cast<size_t>(st.hist[s]) * golomb_length(s, static_cast<uint32_t>(m));
+            if (estimate >= best) break;
+        }
+        if (estimate < best) { best = c.golomb_bits = estimate; c.m = m; }
     }
-    if (best_m < 0) {
+}
+}  // namespace
+
+void write_huffman_or_golomb(const uint16_t* data, size_t n, BitWriter& out) {
+    CodeChoice c;
+    choose_code(gather_stats(data, n), n, c);
+    if (c.m < 0) {
         out.put(0, 1);
-        out.append(huff);
+        out.append(c.table_bits);
+        out.put_codes(data, n, c.table.code_of.data(), c.table.length_of.data(), c.table.payload_bits);
+        out.put(c.table.eof_code, c.table.eof_length);
     } else {
         out.put(1, 1);
-        out.put(static_cast<uint16_t>(best_m), 16);
-        for (size_t i = 0; i < n; ++i) golomb_write(data[i], static_cast<uint32_t>(best_m), out);
+        out.put(static_cast<uint16_t>(c.m), 16);
+        golomb_encode(data, n, static_cast<uint32_t>(c.m), out);
     }
 }
 
-// writeHuffmanOrGolomb and the run-length wrapper of writeCompressed (:449-453) decided from a stream's statistics alone --
-// the device has counted (mp_entropy.hip) and will write the codes; the host builds the table.  Same decisions, same bits:
-// the Huffman cost is table + sum of count x length + pseudo-EOF, the Golomb cost as in write_huffman_or_golomb.
+// write_huffman_or_golomb and the run-length wrapper of writeCompressed (:449-453) with the per-symbol work left out -- the
+// device has counted (mp_entropy.hip) and will write the codes; the host builds the table.  Same decision, same bits.
 void plan_stream(bool rle_flag, bool shorter, uint32_t rle_size, size_t n, uint32_t largest, const uint32_t* triples, size_t distinct,
                  StreamPlan& plan) {
     SymbolStats st;
@@ -983,38 +979,27 @@ void plan_stream(bool rle_flag, bool shorter, uint32_t rle_size, size_t n, uint3
         plan.pre.put(shorter ? 1 : 0, 1);
         if (shorter) plan.pre.put(rle_size, 32);
     }
-    BitWriter table_bits;
-    HuffmanTable t;
-    huffman_table(st, n, table_bits, t);
-    size_t best = table_bits.bit_size() + t.payload_bits + t.eof_length;
-    int best_m = -1;
-    for (int m = 1; m < 2048; m = (m & 1) ? m + 1 : (m << 1) - 1) {
-        size_t estimate = 16;
-        for (uint16_t s : st.distinct) {                        // a candidate is out as soon as its partial sum reaches the best so far
-            estimate += static_cast<size_t>(st.hist[s]) * golomb_length(s, static_cast<uint32_t>(m));
-            if (estimate >= best) break;
-        }
-        if (estimate < best) { best = estimate; best_m = m; }
-    }
-    if (best_m < 0) {
+    CodeChoice c;
+    choose_code(st, n, c);
+    if (c.m < 0) {
         plan.pre.put(0, 1);
-        plan.pre.append(table_bits);
-        plan.post.put(t.eof_code, t.eof_length);
-        plan.payload_bits = t.payload_bits;
+        plan.pre.append(c.table_bits);
+        plan.post.put(c.table.eof_code, c.table.eof_length);
+        plan.payload_bits = c.table.payload_bits;
         plan.mode = 0;
-        plan.max_code_length = t.max_length;
+        plan.max_code_length = c.table.max_length;
         plan.entries.reserve(3 * distinct);
         for (uint16_t s : st.distinct) {
             plan.entries.push_back(s);
-            plan.entries.push_back(t.code_of[s]);
-            plan.entries.push_back(t.length_of[s]);
+            plan.entries.push_back(c.table.code_of[s]);
+            plan.entries.push_back(c.table.length_of[s]);
         }
     } else {
         plan.pre.put(1, 1);
-        plan.pre.put(static_cast<uint16_t>(best_m), 16);
-        plan.payload_bits = best - 16;
+        plan.pre.put(static_cast<uint16_t>(c.m), 16);
+        plan.payload_bits = c.golomb_bits - 16;
         plan.mode = 1;
-        plan.m = static_cast<uint32_t>(best_m);
+        plan.m = static_cast<uint32_t>(c.m);
     }
 }
 
@@ -1087,659 +1072,6 @@ bool read_huffman_or_golomb(BitReader& in, size_t length, std::vector<uint16_t>&
     }
     for (; i < length; ++i) dst[i] = static_cast<uint16_t>(golomb_read(m, in));
     return true;
-}
-
-namespace {
-constexpr uint32_t kMagic = 0x4D4E3234u;        // CompressedImage.cpp:14
-
-std::vector<uint16_t> dc_difference(const std::vector<uint16_t>& v) {       // :428-446
-    std::vector<uint16_t> out(v.size());
-    int32_t prev = 0;
-    for (size_t i = 0; i < v.size(); ++i) {
-        out[i] = static_cast<uint16_t>(zigzag_encode(static_cast<int32_t>(v[i]) - prev));
-        prev = static_cast<int32_t>(v[i]);
-    }
-    return out;
-}
-}  // namespace
-
-namespace {
-// The 1 + 6K streams of a container are coded independently and only concatenated bit-wise afterwards, so
-// they are coded on a small thread pool (the reference is single-threaded; the bytes do not depend on it).
-int host_threads() {
-    if (const char* v = std::getenv("MPC_HOST_THREADS")) {
-        const int n = std::atoi(v);
-        if (n > 0) return n;
-    }
-    const unsigned hc = std::thread::hardware_concurrency();
-    return static_cast<int>(hc == 0 ? 1 : (hc > 16 ? 16 : hc));
-}
-
-// A small persistent pool: the workers are created on first use and sleep between calls (creating and joining 16
-// threads per call cost more than coding a 1080p frame's streams).  One parallel_for at a time (callers serialise on
-// `submit_`); the calling thread works too.
-class WorkerPool {
-public:
-    static WorkerPool& instance() {
-        static WorkerPool pool;
-        return pool;
-    }
-    static WorkerPool& io_instance() {                      // a second pool: frame uploads run beside the entropy stage's jobs
-        static WorkerPool pool;
-        return pool;
-    }
-    void run(int n, int workers, const std::function<void(int)>& body) {
-        std::lock_guard<std::mutex> one_at_a_time(submit_);
-        ensure(workers - 1);
-        {
-            std::lock_guard<std::mutex> hold(lock_);
-            body_ = &body;
-            total_ = n;
-            next_.store(0);
-            pending_ = std::min<int>(workers - 1, static_cast<int>(threads_.size()));
-            active_limit_ = pending_;
-            ++generation_;
-        }
-        wake_.notify_all();
-        work(body, n);
-        // Whatever a job threw, the generation is drained before `body` (the caller's stack) goes away; the first exception is
-        // then rethrown on the calling thread, where the C ABI's `guarded` turns it into a status.
-        std::exception_ptr first;
-        {
-            std::unique_lock<std::mutex> hold(lock_);
-            done_.wait(hold, [&] { return pending_ == 0; });
-            body_ = nullptr;
-            first = error_;
-            error_ = nullptr;
-        }
-        if (first) std::rethrow_exception(first);
-    }
-    ~WorkerPool() {
-        {
-            std::lock_guard<std::mutex> hold(lock_);
-            stop_ = true;
-            ++generation_;
-        }
-        wake_.notify_all();
-        for (auto& t : threads_) t.join();
-    }
-
-private:
-    // this thread's share of the jobs; a job that throws ends the call's remaining jobs (nobody starts another) and is remembered
-    void work(const std::function<void(int)>& body, int total) {
-        try {
-            for (int i = next_.fetch_add(1); i < total; i = next_.fetch_add(1)) body(i);
-        } catch (...) {
-            next_.store(total);
-            std::lock_guard<std::mutex> hold(lock_);
-            if (!error_) error_ = std::current_exception();
-        }
-    }
-    void ensure(int count) {
-        while (static_cast<int>(threads_.size()) < count) {
-            const int id = static_cast<int>(threads_.size());
-            threads_.emplace_back([this, id] { loop(id); });
-        }
-    }
-    void loop(int id) {
-        unsigned long long seen = 0;
-        for (;;) {
-            const std::function<void(int)>* body = nullptr;
-            int total = 0;
-            {
-                std::unique_lock<std::mutex> hold(lock_);
-                wake_.wait(hold, [&] { return stop_ || generation_ != seen; });
-                if (stop_) return;
-                seen = generation_;
-                if (id >= active_limit_) continue;             // this call wants fewer workers
-                body = body_;
-                total = total_;
-            }
-            work(*body, total);
-            {
-                std::lock_guard<std::mutex> hold(lock_);
-                if (--pending_ == 0) done_.notify_one();
-            }
-        }
-    }
-    std::mutex submit_, lock_;
-    std::condition_variable wake_, done_;
-    std::vector<std::thread> threads_;
-    const std::function<void(int)>* body_ = nullptr;
-    std::atomic<int> next_{0};
-    int total_ = 0, pending_ = 0, active_limit_ = 0;
-    unsigned long long generation_ = 0;
-    bool stop_ = false;
-    std::exception_ptr error_;
-};
-
-template <class F>
-void parallel_for(int n, F&& body) {
-    const int workers = std::min(host_threads(), n);
-    if (workers <= 1) {
-        for (int i = 0; i < n; ++i) body(i);
-        return;
-    }
-    const std::function<void(int)> fn = [&](int i) { body(i); };
-    WorkerPool::instance().run(n, workers, fn);
-}
-}  // namespace
-
-BitWriter container_head(int width, int height, int K, int block_size, const double* quant) {
-    BitWriter head;
-    head.put(kMagic, 32);
-    head.put(static_cast<uint32_t>(width), 32);
-    head.put(static_cast<uint32_t>(height), 32);
-    head.put(static_cast<uint8_t>(K), 8);
-    head.put(static_cast<uint8_t>(block_size), 8);
-    for (int ch = 0; ch < 3; ++ch)
-        for (int i = 0; i < K; ++i) head.put(header_quant(quant[ch * K + i]), 16);    // :420 u16 of an integral double
-    return head;
-}
-
-void parallel_jobs(int n, const std::function<void(int)>& body) { parallel_for(n, body); }
-
-int host_thread_count() { return host_threads(); }
-
-void parallel_io_jobs(int n, int workers, const std::function<void(int)>& body) {
-    workers = std::min(std::min(workers, host_threads()), n);
-    if (workers <= 1) {
-        for (int i = 0; i < n; ++i) body(i);
-        return;
-    }
-    WorkerPool::io_instance().run(n, workers, body);
-}
-
-std::vector<uint8_t> write_compressed(const Streams& s) {
-    const int K = s.K;
-    BitWriter out;
-    out.put(kMagic, 32);
-    out.put(static_cast<uint32_t>(s.width), 32);
-    out.put(static_cast<uint32_t>(s.height), 32);
-    out.put(static_cast<uint8_t>(K), 8);
-    out.put(static_cast<uint8_t>(s.block_size), 8);
-    for (int ch = 0; ch < 3; ++ch)
-        for (int i = 0; i < K; ++i) out.put(s.quant[ch][i], 16);
-    std::vector<BitWriter> parts(static_cast<size_t>(6 * K + 1));
-    parallel_for(6 * K + 1, [&](int job) {
-        BitWriter& w = parts[static_cast<size_t>(job)];
-        if (job == 0) {
-            write_huffman_or_golomb(s.lengths.data(), s.lengths.size(), w);
-            return;
-        }
-        const int i = job - 1;
-        const bool dc = (i == 1 || i == 2 * K + 1 || i == 4 * K + 1);
-        const std::vector<uint16_t> diffed = dc ? dc_difference(s.codes[i]) : std::vector<uint16_t>();
-        const std::vector<uint16_t>& stream = dc ? diffed : s.codes[i];
-        const bool shorter = rle_encoded_size(stream.data(), stream.size()) + 4 < stream.size();
-        const std::vector<uint16_t> packed = shorter ? rle_encode(stream.data(), stream.size()) : std::vector<uint16_t>();
-        if (shorter) {                                           // :450
-            w.put(1, 1);
-            w.put(static_cast<uint32_t>(packed.size()), 32);
-            write_huffman_or_golomb(packed.data(), packed.size(), w);
-        } else {
-            w.put(0, 1);
-            write_huffman_or_golomb(stream.data(), stream.size(), w);
-        }
-    });
-    for (const BitWriter& w : parts) out.append(w);
-    return out.bytes();
-}
-
-// assemble_streams + write_compressed in one go, without materialising the 6K streams of a frame (hundreds of MB of
-// freshly faulted pages at K = 32): one job per (channel, step) gathers its two streams into buffers the worker thread
-// keeps between calls and codes them straight into its part of the container.  Same bytes as the two-step route.
-namespace {
-// record (tile t, channel ch, step i) = choices[t * tile_stride + ch * channel_stride + i * step_stride]
-struct RecordLayout {
-    size_t tile_stride, channel_stride, step_stride;
-};
-
-void code_records(int width, int height, int K, int block_size, const double* quant, const uint16_t* counts, const uint32_t* choices,
-                  const RecordLayout& layout, BitWriter& out, std::vector<BitWriter>& parts) {
-    const size_t tiles = static_cast<size_t>((width + block_size - 1) / block_size) *
-                         static_cast<size_t>((height + block_size - 1) / block_size);
-    out.put(kMagic, 32);
-    out.put(static_cast<uint32_t>(width), 32);
-    out.put(static_cast<uint32_t>(height), 32);
-    out.put(static_cast<uint8_t>(K), 8);
-    out.put(static_cast<uint8_t>(block_size), 8);
-    for (int ch = 0; ch < 3; ++ch)
-        for (int i = 0; i < K; ++i) out.put(header_quant(quant[ch * K + i]), 16);    // :420 u16 of an integral double
-    parts.assign(static_cast<size_t>(6 * K + 1), BitWriter());
-    auto code_stream = [](const std::vector<uint16_t>& stream, bool dc, std::vector<uint16_t>& scratch, BitWriter& w) {
-        const std::vector<uint16_t>* src = &stream;
-        if (dc) {
-            scratch = dc_difference(stream);
-            src = &scratch;
-        }
-        const bool shorter = rle_encoded_size(src->data(), src->size()) + 4 < src->size();
-        const std::vector<uint16_t> packed = shorter ? rle_encode(src->data(), src->size()) : std::vector<uint16_t>();
-        if (shorter) {                                          // :450
-            w.put(1, 1);
-            w.put(static_cast<uint32_t>(packed.size()), 32);
-            write_huffman_or_golomb(packed.data(), packed.size(), w);
-        } else {
-            w.put(0, 1);
-            write_huffman_or_golomb(src->data(), src->size(), w);
-        }
-    };
-    // the big jobs first: step 0 of every channel holds every tile-channel, later steps fewer
-    parallel_for(3 * K + 1, [&](int job0) {
-        if (job0 == 0) {
-            write_huffman_or_golomb(counts, 3 * tiles, parts[0]);                              // the lengths stream: the longest
-            return;
-        }
-        const int job = job0 - 1;
-        const int i = job / 3, ch = job - 3 * i;                 // job order: (step 0: Y U V), (step 1: Y U V), ...
-        thread_local std::vector<uint16_t> d, c, scratch;
-        const uint32_t* mine = choices + static_cast<size_t>(ch) * layout.channel_stride + static_cast<size_t>(i) * layout.step_stride;
-        const size_t tile_stride = layout.tile_stride;
-        d.clear();
-        c.clear();
-        for (size_t t = 0; t < tiles; ++t) {
-            if (counts[3 * t + static_cast<size_t>(ch)] > i) {
-                const uint32_t rec = mine[t * tile_stride];
-                d.push_back(static_cast<uint16_t>(rec & 0xFFFFu));
-                c.push_back(static_cast<uint16_t>(rec >> 16));
-            }
-        }
-        const int index = 2 * K * ch + 2 * i;                    // codes[index] = deltaId, [index + 1] = intCoeff
-        code_stream(d, false, scratch, parts[static_cast<size_t>(index + 1)]);
-        code_stream(c, i == 0, scratch, parts[static_cast<size_t>(index + 2)]);   // DC: the step-0 coefficients (:428-446)
-    });
-}
-
-// Concatenate head and parts bit-wise into big-endian bytes in a malloc'ed buffer.  Every part knows its bit offset, so
-// the parts are shifted into place in parallel; only the two words a part may share with its neighbours are merged
-// with atomic ORs (into words cleared beforehand), everything in between is a plain store.
-uint8_t* concat_malloc(const BitWriter& head, const std::vector<BitWriter>& parts, size_t* nbytes) {
-    std::vector<size_t> offset(parts.size() + 1);
-    size_t total = head.bit_size();
-    for (size_t p = 0; p < parts.size(); ++p) {
-        offset[p] = total;
-        total += parts[p].bit_size();
-    }
-    offset[parts.size()] = total;
-    const size_t nwords = (total + 63) / 64;
-    uint64_t* dst = static_cast<uint64_t*>(std::malloc((nwords ? nwords : 1) * sizeof(uint64_t)));
-    if (!dst) return nullptr;
-    auto place = [dst](const BitWriter& w, size_t bit_offset) {
-        const size_t nbits = w.bit_size();
-        if (nbits == 0) return;
-        const uint64_t* src = w.words();
-        const size_t src_words = (nbits + 63) / 64;
-        const size_t w0 = bit_offset >> 6, last = (bit_offset + nbits - 1) >> 6;
-        const int shift = static_cast<int>(bit_offset & 63);
-        for (size_t d = w0; d <= last; ++d) {                   // destination word d = source bits [64(d-w0) - shift, +64)
-            const size_t i = d - w0;
-            uint64_t v = 0;
-            if (shift == 0) v = i < src_words ? src[i] : 0;
-            else {
-                if (i < src_words) v |= src[i] >> shift;
-                if (i >= 1 && i - 1 < src_words) v |= src[i - 1] << (64 - shift);
-            }
-            const uint64_t be = __builtin_bswap64(v);            // MSB-first bit order = big-endian bytes
-            if (d == w0 || d == last) __atomic_fetch_or(&dst[d], be, __ATOMIC_RELAXED);
-            else dst[d] = be;
-        }
-    };
-    // clear the words that can be shared between neighbours (first and last word of every piece)
-    auto clear_ends = [dst](size_t bit_offset, size_t nbits) {
-        if (nbits == 0) return;
-        dst[bit_offset >> 6] = 0;
-        dst[(bit_offset + nbits - 1) >> 6] = 0;
-    };
-    clear_ends(0, head.bit_size());
-    for (size_t p = 0; p < parts.size(); ++p) clear_ends(offset[p], parts[p].bit_size());
-    place(head, 0);
-    parallel_for(static_cast<int>(parts.size()), [&](int p) { place(parts[static_cast<size_t>(p)], offset[static_cast<size_t>(p)]); });
-    *nbytes = (total + 7) / 8;
-    return reinterpret_cast<uint8_t*>(dst);
-}
-}  // namespace
-
-std::vector<uint8_t> encode_records(int width, int height, int K, int block_size, const double* quant, const uint16_t* counts,
-                                    const uint32_t* choices) {
-    BitWriter out;
-    std::vector<BitWriter> parts;
-    code_records(width, height, K, block_size, quant, counts, choices, RecordLayout{3 * static_cast<size_t>(K), static_cast<size_t>(K), 1}, out, parts);
-    for (const BitWriter& w : parts) out.append(w);
-    return out.bytes();
-}
-
-uint8_t* encode_records_malloc(int width, int height, int K, int block_size, const double* quant, const uint16_t* counts,
-                               const uint32_t* choices, size_t* nbytes) {
-    BitWriter head;
-    std::vector<BitWriter> parts;
-    code_records(width, height, K, block_size, quant, counts, choices, RecordLayout{3 * static_cast<size_t>(K), static_cast<size_t>(K), 1}, head, parts);
-    return concat_malloc(head, parts, nbytes);
-}
-
-// The container from streams the device has already assembled (mp_streams.hip): `symbols` holds codes[0], codes[1], ... codes[6K-1]
-// back to back (stream s = symbols[off[s] .. off[s+1])), live symbols only, in the reference's tile order, the three step-0
-// coefficient streams already difference coded.  One job per stream (the lengths stream first: the longest).
-uint8_t* encode_symbol_streams_malloc(int width, int height, int K, int block_size, const double* quant, const uint16_t* counts,
-                                      const uint16_t* symbols, const unsigned long long* off, size_t* nbytes) {
-    const size_t tiles = static_cast<size_t>((width + block_size - 1) / block_size) *
-                         static_cast<size_t>((height + block_size - 1) / block_size);
-    BitWriter head;
-    head.put(kMagic, 32);
-    head.put(static_cast<uint32_t>(width), 32);
-    head.put(static_cast<uint32_t>(height), 32);
-    head.put(static_cast<uint8_t>(K), 8);
-    head.put(static_cast<uint8_t>(block_size), 8);
-    for (int ch = 0; ch < 3; ++ch)
-        for (int i = 0; i < K; ++i) head.put(header_quant(quant[ch * K + i]), 16);    // :420 u16 of an integral double
-    std::vector<BitWriter> parts(static_cast<size_t>(6 * K + 1));
-    // longest jobs first: the lengths stream, then the streams in the order of their sizes
-    std::vector<int> order(static_cast<size_t>(6 * K));
-    for (int s = 0; s < 6 * K; ++s) order[static_cast<size_t>(s)] = s;
-    std::sort(order.begin(), order.end(), [&](int x, int y) { return off[x + 1] - off[x] > off[y + 1] - off[y]; });
-    parallel_for(6 * K + 1, [&](int job) {
-        if (job == 0) {
-            write_huffman_or_golomb(counts, 3 * tiles, parts[0]);
-            return;
-        }
-        const int s = order[static_cast<size_t>(job - 1)];
-        const uint16_t* data = symbols + off[s];
-        const size_t n = static_cast<size_t>(off[s + 1] - off[s]);
-        BitWriter& w = parts[static_cast<size_t>(s + 1)];
-        const bool shorter = rle_encoded_size(data, n) + 4 < n;
-        const std::vector<uint16_t> packed = shorter ? rle_encode(data, n) : std::vector<uint16_t>();
-        if (shorter) {                                            // CompressedImage.cpp:450
-            w.put(1, 1);
-            w.put(static_cast<uint32_t>(packed.size()), 32);
-            write_huffman_or_golomb(packed.data(), packed.size(), w);
-        } else {
-            w.put(0, 1);
-            write_huffman_or_golomb(data, n, w);
-        }
-    });
-    return concat_malloc(head, parts, nbytes);
-}
-
-// encode_symbol_streams_malloc by the route the device-side entropy stage takes, with the device's share done here on the
-// host: per-stream statistics -> plan_stream -> codes at the planned bit offsets -> OR the pieces into place.  Exists so that
-// the planning half can be checked against the direct route without a GPU (tests/test_host_bitstream.py).
-uint8_t* encode_symbol_streams_by_plan_malloc(int width, int height, int K, int block_size, const double* quant, const uint16_t* counts,
-                                              const uint16_t* symbols, const unsigned long long* off, size_t* nbytes) {
-    const size_t tiles = static_cast<size_t>((width + block_size - 1) / block_size) *
-                         static_cast<size_t>((height + block_size - 1) / block_size);
-    const int S = 6 * K + 1;
-    std::vector<StreamPlan> plans(static_cast<size_t>(S));
-    std::vector<BitWriter> payload(static_cast<size_t>(S));
-    for (int j = 0; j < S; ++j) {
-        const uint16_t* data = j == 0 ? counts : symbols + off[j - 1];
-        const size_t n = j == 0 ? 3 * tiles : static_cast<size_t>(off[j] - off[j - 1]);
-        const size_t rle_size = j == 0 ? n : rle_encoded_size(data, n);
-        const bool shorter = j != 0 && rle_size + 4 < n;
-        const std::vector<uint16_t> packed = shorter ? rle_encode(data, n) : std::vector<uint16_t>();
-        const uint16_t* coded = shorter ? packed.data() : data;
-        const size_t coded_n = shorter ? packed.size() : n;
-        std::vector<uint32_t> hist(65536, 0), first(65536, 0), triples;
-        uint32_t largest = 0;
-        for (size_t i = 0; i < coded_n; ++i) {
-            if (hist[coded[i]]++ == 0) first[coded[i]] = static_cast<uint32_t>(i);
-            largest = std::max<uint32_t>(largest, coded[i]);
-        }
-        for (uint32_t v = 0; v < 65536; ++v)
-            if (hist[v]) { triples.push_back(v); triples.push_back(hist[v]); triples.push_back(first[v]); }
-        StreamPlan& p = plans[static_cast<size_t>(j)];
-        plan_stream(j != 0, shorter, static_cast<uint32_t>(rle_size), coded_n, largest, triples.data(), triples.size() / 3, p);
-        BitWriter& w = payload[static_cast<size_t>(j)];
-        if (p.mode == 0) {
-            std::vector<uint32_t> code_of(static_cast<size_t>(largest) + 1, 0);
-            std::vector<uint8_t> length_of(static_cast<size_t>(largest) + 1, 0);
-            for (size_t k = 0; k < p.entries.size(); k += 3) {
-                code_of[p.entries[k]] = p.entries[k + 1];
-                length_of[p.entries[k]] = static_cast<uint8_t>(p.entries[k + 2]);
-            }
-            w.put_codes(coded, coded_n, code_of.data(), length_of.data(), p.payload_bits);
-        } else {
-            for (size_t i = 0; i < coded_n; ++i) golomb_write(coded[i], p.m, w);
-        }
-        if (w.bit_size() != p.payload_bits) return nullptr;
-    }
-    const BitWriter head = container_head(width, height, K, block_size, quant);
-    size_t total = head.bit_size();
-    for (int j = 0; j < S; ++j) total += plans[static_cast<size_t>(j)].pre.bit_size() + plans[static_cast<size_t>(j)].payload_bits + plans[static_cast<size_t>(j)].post.bit_size();
-    *nbytes = (total + 7) / 8;
-    uint8_t* dst = static_cast<uint8_t*>(std::calloc(*nbytes ? *nbytes : 1, 1));
-    if (!dst) return nullptr;
-    or_bits(dst, *nbytes, 0, head);
-    size_t at = head.bit_size();
-    for (int j = 0; j < S; ++j) {
-        const StreamPlan& p = plans[static_cast<size_t>(j)];
-        or_bits(dst, *nbytes, at, p.pre);
-        at += p.pre.bit_size();
-        or_bits(dst, *nbytes, at, payload[static_cast<size_t>(j)]);
-        at += p.payload_bits;
-        or_bits(dst, *nbytes, at, p.post);
-        at += p.post.bit_size();
-    }
-    return dst;
-}
-
-uint8_t* encode_planar_records_malloc(int width, int height, int K, int block_size, const double* quant, const uint16_t* counts,
-                                      const uint32_t* planar, size_t* nbytes) {
-    const size_t tiles = static_cast<size_t>((width + block_size - 1) / block_size) *
-                         static_cast<size_t>((height + block_size - 1) / block_size);
-    BitWriter head;
-    std::vector<BitWriter> parts;
-    code_records(width, height, K, block_size, quant, counts, planar, RecordLayout{1, static_cast<size_t>(K) * tiles, tiles}, head, parts);
-    return concat_malloc(head, parts, nbytes);
-}
-
-
-// The serial half of readCompressed: everything the format chains from one code to the next (the codes are self-delimiting and
-// a stream's table sits where the stream before it ended), and nothing else.  No worker pool, no shared state: safe on several
-// threads at once.
-bool read_compressed_coded(const uint8_t* bytes, size_t nbytes, CodedStreams& s) {
-    BitReader in(bytes, nbytes);
-    if (static_cast<uint32_t>(in.get(32)) != kMagic) return false;
-    s.width = static_cast<int>(in.get(32));
-    s.height = static_cast<int>(in.get(32));
-    s.K = static_cast<int>(in.get(8));
-    s.block_size = static_cast<int>(in.get(8));
-    if (s.K < 1 || s.K > 32 || s.block_size < 1 || s.block_size > 8 || s.width < 1 || s.height < 1) return false;
-    const int K = s.K;
-    for (int ch = 0; ch < 3; ++ch)
-        for (int i = 0; i < K; ++i) s.quant[ch][i] = static_cast<uint16_t>(in.get(16));
-    const size_t tiles = static_cast<size_t>((s.width + s.block_size - 1) / s.block_size) *
-                         static_cast<size_t>((s.height + s.block_size - 1) / s.block_size);
-    s.lengths.clear();
-    if (tiles > (static_cast<size_t>(1) << 40) / 3) return false;
-    if (!read_huffman_or_golomb(in, 3 * tiles, s.lengths)) return false;
-    // a Huffman-coded lengths stream carries its own end: it must still describe exactly this frame's tiles (the
-    // device decoder walks tiles_x * tiles_y records)
-    if (s.lengths.size() != 3 * tiles) return false;
-    s.codes.assign(static_cast<size_t>(6 * K), {});
-    // length of an un-packed stream = tile-channels of its layer with more than `depth` atoms (:680-685): suffix sums
-    // of the histogram of lengths, once for all 6K streams
-    std::vector<size_t> expect_of(static_cast<size_t>(3 * K), 0);
-    {
-        std::vector<size_t> hist(static_cast<size_t>(3) * 65536, 0);
-        for (size_t t = 0; t < s.lengths.size() / 3; ++t)
-            for (size_t layer = 0; layer < 3; ++layer) ++hist[layer * 65536 + s.lengths[3 * t + layer]];
-        for (size_t layer = 0; layer < 3; ++layer) {
-            size_t above = 0;
-            for (int v = 65535; v > K; --v) above += hist[layer * 65536 + static_cast<size_t>(v)];
-            for (int depth = K - 1; depth >= 0; --depth) {
-                above += hist[layer * 65536 + static_cast<size_t>(depth + 1)];
-                expect_of[layer * static_cast<size_t>(K) + static_cast<size_t>(depth)] = above;
-            }
-        }
-    }
-    // Only the entropy codes are undone here: run-length expansion (:660-678) and the DC sums (:690-705) of a stream need nothing
-    // from the streams behind it (read_compressed does them on the pool, the sequence decoder on the device).
-    s.packed.assign(static_cast<size_t>(6 * K), 0);
-    s.expect.assign(static_cast<size_t>(6 * K), 0);
-    for (int i = 0; i < 6 * K; ++i) {
-        s.expect[i] = expect_of[(static_cast<size_t>(i / 2) / K) * static_cast<size_t>(K) + static_cast<size_t>(i / 2) % K];
-        if (in.get(1) == 1) {
-            const size_t packed_len = static_cast<size_t>(in.get(32));
-            s.packed[i] = 1;
-            if (!read_huffman_or_golomb(in, packed_len, s.codes[i])) return false;
-            // At most every third symbol of a run-length coded stream is a count and every other symbol expands to itself: a
-            // stream of n symbols expands to at least n - n/3.  More than the lengths stream allows cannot be valid, and whoever
-            // expands the stream may size its buffers by `expect`.
-            if (s.codes[i].size() - s.codes[i].size() / 3 > s.expect[i]) return false;
-        } else {
-            if (!read_huffman_or_golomb(in, s.expect[i], s.codes[i])) return false;
-        }
-    }
-    return true;
-}
-
-bool read_compressed(const uint8_t* bytes, size_t nbytes, Streams& s) {
-    CodedStreams c;
-    if (!read_compressed_coded(bytes, nbytes, c)) return false;
-    const std::vector<uint8_t> is_packed = std::move(c.packed);
-    const std::vector<size_t> expect = std::move(c.expect);
-    s = std::move(static_cast<Streams&>(c));
-    const int K = s.K;
-    std::vector<char> bad(static_cast<size_t>(6 * K), 0);
-    parallel_for(6 * K, [&](int i) {
-        if (is_packed[i]) {
-            // run lengths come from the data: refuse to expand beyond what the lengths stream allows for this stream
-            const std::vector<uint16_t> packed = std::move(s.codes[i]);
-            size_t expanded = 0;
-            if (!rle_decoded_size(packed.data(), packed.size(), expect[i], &expanded)) { bad[i] = 1; return; }
-            s.codes[i] = rle_decode(packed.data(), packed.size());
-        }
-        if (s.codes[i].size() != expect[i]) { bad[i] = 1; return; }
-        if (i == 1 || i == 2 * K + 1 || i == 4 * K + 1) {       // :690-705
-            int32_t acc = 0;
-            for (uint16_t& c : s.codes[i]) {
-                acc += zigzag_decode(c);
-                c = static_cast<uint16_t>(acc);
-            }
-        }
-    });
-    for (int i = 0; i < 6 * K; ++i)
-        if (bad[i]) return false;
-    return true;
-}
-
-// the header alone (CompressedImage.cpp:640-655), with read_compressed's checks of it
-bool container_info(const uint8_t* bytes, size_t nbytes, int* width, int* height, int* K, int* block_size) {
-    if (nbytes < 14) return false;
-    BitReader in(bytes, nbytes);
-    if (static_cast<uint32_t>(in.get(32)) != kMagic) return false;
-    *width = static_cast<int>(in.get(32));
-    *height = static_cast<int>(in.get(32));
-    *K = static_cast<int>(in.get(8));
-    *block_size = static_cast<int>(in.get(8));
-    return !(*K < 1 || *K > 32 || *block_size < 1 || *block_size > 8 || *width < 1 || *height < 1);
-}
-
-Streams assemble_streams(int width, int height, int K, int block_size, const double* quant, const uint16_t* counts,
-                         const uint32_t* choices) {
-    Streams s;
-    s.width = width;
-    s.height = height;
-    s.K = K;
-    s.block_size = block_size;
-    for (int ch = 0; ch < 3; ++ch)
-        for (int i = 0; i < K; ++i) s.quant[ch][i] = header_quant(quant[ch * K + i]);   // :420 u16 of an integral double
-    const size_t tiles = static_cast<size_t>((width + block_size - 1) / block_size) *
-                         static_cast<size_t>((height + block_size - 1) / block_size);
-    s.lengths.resize(3 * tiles);
-    s.codes.assign(static_cast<size_t>(6 * K), {});
-    // stream sizes first, then fill: no reallocation on multi-megabyte streams.  Step i of a channel holds one symbol
-    // per tile-channel with count > i: suffix sums of the histogram of counts.
-    std::vector<size_t> sizes(static_cast<size_t>(3 * K), 0);
-    {
-        std::vector<size_t> hist(static_cast<size_t>(3 * (K + 1)), 0);
-        for (size_t o = 0; o < 3 * tiles; ++o) {
-            s.lengths[o] = counts[o];
-            ++hist[(o % 3) * static_cast<size_t>(K + 1) + std::min<size_t>(counts[o], static_cast<size_t>(K))];
-        }
-        for (int ch = 0; ch < 3; ++ch) {
-            size_t above = 0;
-            for (int i = K - 1; i >= 0; --i) {
-                above += hist[static_cast<size_t>(ch) * (K + 1) + static_cast<size_t>(i + 1)];
-                sizes[static_cast<size_t>(ch * K + i)] = above;
-            }
-        }
-    }
-    for (int ch = 0; ch < 3; ++ch)
-        for (int i = 0; i < K; ++i) {
-            s.codes[2 * K * ch + 2 * i].reserve(sizes[ch * K + i]);
-            s.codes[2 * K * ch + 2 * i + 1].reserve(sizes[ch * K + i]);
-        }
-    // one job per (channel, step): each fills its own pair of streams by scanning that channel's counts
-    parallel_for(3 * K, [&](int job) {
-        const int ch = job / K, i = job - ch * K;
-        std::vector<uint16_t>& d = s.codes[2 * K * ch + 2 * i];
-        std::vector<uint16_t>& c = s.codes[2 * K * ch + 2 * i + 1];
-        const uint32_t* mine = choices + static_cast<size_t>(ch) * K + static_cast<size_t>(i);
-        const size_t tile_stride = 3 * static_cast<size_t>(K);
-        for (size_t t = 0; t < tiles; ++t) {
-            if (counts[3 * t + static_cast<size_t>(ch)] > i) {
-                const uint32_t rec = mine[t * tile_stride];
-                d.push_back(static_cast<uint16_t>(rec & 0xFFFFu));
-                c.push_back(static_cast<uint16_t>(rec >> 16));
-            }
-        }
-    });
-    return s;
-}
-
-bool disassemble_streams(const Streams& s, uint16_t* counts, uint32_t* choices) {
-    const int K = s.K;
-    const size_t n = s.lengths.size(), tiles = n / 3;
-    if (n % 3 != 0) return false;
-    for (int i = 0; i < 6 * K; i += 2)
-        if (s.codes[i].size() != s.codes[i + 1].size()) return false;
-    // Blocks of tiles in parallel: where a block starts in each of the 3K stream pairs = tile-channels of the blocks in front of
-    // it with more than `step` atoms (suffix sums of a histogram of the block's counts, then a running sum over the blocks).
-    const size_t block = 4096, blocks = (tiles + block - 1) / block;
-    std::vector<size_t> start((blocks + 1) * static_cast<size_t>(3 * K), 0);
-    std::vector<char> bad(blocks, 0);
-    parallel_for(static_cast<int>(blocks), [&](int b) {
-        std::vector<size_t> hist(static_cast<size_t>(3 * (K + 1)), 0);
-        const size_t lo = block * static_cast<size_t>(b), hi = std::min(tiles, lo + block);
-        for (size_t o = 3 * lo; o < 3 * hi; ++o) {
-            if (s.lengths[o] > K) { bad[b] = 1; return; }
-            ++hist[(o % 3) * static_cast<size_t>(K + 1) + s.lengths[o]];
-        }
-        size_t* mine = start.data() + (static_cast<size_t>(b) + 1) * static_cast<size_t>(3 * K);
-        for (int ch = 0; ch < 3; ++ch) {
-            size_t above = 0;
-            for (int i = K - 1; i >= 0; --i) {
-                above += hist[static_cast<size_t>(ch) * (K + 1) + static_cast<size_t>(i + 1)];
-                mine[ch * K + i] = above;
-            }
-        }
-    });
-    for (size_t b = 0; b < blocks; ++b)
-        if (bad[b]) return false;
-    for (size_t b = 1; b <= blocks; ++b)
-        for (int p = 0; p < 3 * K; ++p) start[b * static_cast<size_t>(3 * K) + p] += start[(b - 1) * static_cast<size_t>(3 * K) + p];
-    for (int p = 0; p < 3 * K; ++p)                                 // every stream must hold what the lengths promise
-        if (start[blocks * static_cast<size_t>(3 * K) + p] > s.codes[2 * p].size()) return false;
-    parallel_for(static_cast<int>(blocks), [&](int b) {
-        std::vector<size_t> cursor(start.begin() + static_cast<size_t>(b) * (3 * K), start.begin() + (static_cast<size_t>(b) + 1) * (3 * K));
-        const size_t lo = block * static_cast<size_t>(b), hi = std::min(tiles, lo + block);
-        for (size_t o = 3 * lo; o < 3 * hi; ++o) {
-            const int ch = static_cast<int>(o % 3);
-            const int count = s.lengths[o];
-            counts[o] = s.lengths[o];
-            for (int i = 0; i < count; ++i) {
-                const size_t at = cursor[static_cast<size_t>(ch * K + i)]++;
-                choices[o * K + i] = static_cast<uint32_t>(s.codes[2 * K * ch + 2 * i][at]) | (static_cast<uint32_t>(s.codes[2 * K * ch + 2 * i + 1][at]) << 16);
-            }
-        }
-    });
-    return true;
-}
-
-bool disassemble_streams(const Streams& s, std::vector<uint16_t>& counts, std::vector<uint32_t>& choices) {
-    counts.assign(s.lengths.size(), 0);
-    choices.assign(s.lengths.size() * static_cast<size_t>(s.K), 0);
-    return disassemble_streams(s, counts.data(), choices.data());
 }
 
 }  // namespace mpc

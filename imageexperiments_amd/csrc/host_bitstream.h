@@ -1,11 +1,15 @@
-// host_bitstream.h -- product host code: the entropy stage and the ".mn" container of the
-// CompressionLib codec.  It stays on the host (BASELINE.json north_star) and must emit the
-// reference's bytes exactly:
+// host_bitstream.h -- product host code: the host's share of the entropy stage and the ".mn" container of the
+// CompressionLib codec.  The device does whatever touches every symbol of an encode or a decode (mp_streams.hip,
+// mp_entropy.hip, mp_unpack.hip); the host builds one code table per stream, writes the container's small pieces
+// and parses containers -- and holds the whole stage once more, for frames the device stage cannot take and for
+// the tests.  Every route must emit the reference's bytes exactly:
 //   bit buffer, zigzag, Golomb, Elias-Fano     CompressionLib/src/BitBuffer.cpp, inc/BitBuffer.h
 //   canonical Huffman + u16 run-length code     CompressionLib/src/Huffman.cpp
 //   Huffman-or-Golomb choice, container layout  CompressionLib/src/CompressedImage.cpp:359-460, 635-707
 // Huffman ties are broken the way the reference's only toolchain (MSVC STL) breaks them; see
-// MsvcHashOrder in the .cpp.
+// MsvcHashOrder in host_bitstream.cpp.
+// Three sources behind this one header: host_bitstream.cpp (everything per symbol or per bit), host_container.cpp
+// (the container, once per stream) and host_pool.cpp (the worker pool).
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -59,6 +63,7 @@ inline int32_t zigzag_decode(uint32_t x) { return static_cast<int32_t>((x >> 1) 
 uint32_t golomb_length(uint32_t value, uint32_t m);
 void golomb_write(uint32_t value, uint32_t m, BitWriter& out);
 uint32_t golomb_read(uint32_t m, BitReader& in);
+void golomb_encode(const uint16_t* data, size_t n, uint32_t m, BitWriter& out);      // golomb_write of every symbol
 
 // Elias-Fano code of a sorted sequence (BitBuffer.cpp:292-354): the Huffman symbol table uses it where it is shorter than raw
 uint32_t elias_fano_length(size_t n, uint16_t max_symbol);
@@ -70,6 +75,9 @@ bool huffman_decode(BitReader& in, std::vector<uint16_t>& out);          // fals
 
 std::vector<uint16_t> rle_encode(const uint16_t* data, size_t n);
 std::vector<uint16_t> rle_decode(const uint16_t* data, size_t n);
+// the sizes rle_encode / rle_decode would produce, without producing them; rle_decoded_size: false once it exceeds `limit`
+size_t rle_encoded_size(const uint16_t* data, size_t n);
+bool rle_decoded_size(const uint16_t* data, size_t n, size_t limit, size_t* size);
 
 void write_huffman_or_golomb(const uint16_t* data, size_t n, BitWriter& out);
 bool read_huffman_or_golomb(BitReader& in, size_t length, std::vector<uint16_t>& out);
@@ -103,19 +111,13 @@ bool container_info(const uint8_t* bytes, size_t nbytes, int* width, int* height
 // worker threads of the host stages (MPC_HOST_THREADS, else the machine's, at most 16)
 int host_thread_count();
 
-// Build the streams from per-tile records in the reference's visiting order (tile t = tx*tiles_y + ty):
-// counts[t*3+ch], choices[(t*3+ch)*K + i] = deltaId | intCoeff << 16.   (encodeImage, CompressedImage.cpp:555-572)
-Streams assemble_streams(int width, int height, int K, int block_size, const double* quant /*[3*K]*/,
-                         const uint16_t* counts, const uint32_t* choices);
-
-// assemble_streams + write_compressed without the intermediate streams (what mpc_assemble_streams / mpc_encode_image use)
-std::vector<uint8_t> encode_records(int width, int height, int K, int block_size, const double* quant /*[3*K]*/,
-                                    const uint16_t* counts, const uint32_t* choices);
-// the same into a malloc'ed buffer (release with free); nullptr = out of memory
+// The container from per-tile records in the reference's visiting order (tile t = tx*tiles_y + ty): counts[t*3+ch],
+// choices[(t*3+ch)*K + i] = deltaId | intCoeff << 16 (encodeImage, CompressedImage.cpp:555-572, + writeCompressed), in a
+// malloc'ed buffer (release with free); nullptr = out of memory.  What mpc_assemble_streams uses.
 uint8_t* encode_records_malloc(int width, int height, int K, int block_size, const double* quant, const uint16_t* counts,
                                const uint32_t* choices, size_t* nbytes);
 // same container from records in planar order, planar[(ch * K + i) * tiles + t]: every (channel, step) job then reads
-// one contiguous run instead of one word per 12*K bytes (what mpc_encode_image downloads after the device transposes)
+// one contiguous run instead of one word per 12*K bytes (mpc_assemble_planar_streams)
 uint8_t* encode_planar_records_malloc(int width, int height, int K, int block_size, const double* quant, const uint16_t* counts,
                                       const uint32_t* planar, size_t* nbytes);
 
@@ -150,7 +152,7 @@ void parallel_io_jobs(int n, int workers, const std::function<void(int)>& body);
 uint8_t* encode_symbol_streams_by_plan_malloc(int width, int height, int K, int block_size, const double* quant, const uint16_t* counts,
                                               const uint16_t* symbols, const unsigned long long* off, size_t* nbytes);
 
-// Inverse of assemble_streams: per-tile records in the reference's visiting order.  counts[3*tiles],
+// Inverse of encode_records_malloc's gathering: per-tile records in the reference's visiting order.  counts[3*tiles],
 // choices[3*tiles*K] (deltaId | intCoeff << 16, zero beyond count).  false = streams inconsistent with `lengths`.
 bool disassemble_streams(const Streams& s, std::vector<uint16_t>& counts, std::vector<uint32_t>& choices);
 // same into caller-provided storage (3*tiles and 3*tiles*K elements); entries beyond a count are left untouched

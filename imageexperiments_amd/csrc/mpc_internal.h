@@ -2,6 +2,10 @@
 //   mpcodec_context.cpp    device dictionary, context, quantiser tables, pursuit launches, tile encode, timing, tuning switches
 //   mpcodec_container.cpp  records on the device -> container (ContainerJob), the mpc_container_job_* API, the frame pipeline
 //   mpcodec_bitstream.cpp  host-only bitstream entry points
+// and, behind host_bitstream.h (they know neither HIP nor the C ABI and also build on their own):
+//   host_bitstream.cpp     bits, Golomb, Elias-Fano, Huffman, run lengths, the Huffman-or-Golomb choice, plan_stream, or_bits
+//   host_container.cpp     the container: header, per-stream wrapper, the routes to a container, the parser
+//   host_pool.cpp          the worker pool of the host stages
 //   mpcodec_decode.cpp     tile reconstruction from records (mpc_decode_tiles_device), distortion, patch statistics
 //   mpcodec_decode_seq.cpp the decoder of containers (mpc_decode_image, mpc_decode_images*), the device unpack of coded streams
 #pragma once
@@ -80,7 +84,7 @@ constexpr unsigned kTripleCap = 1u << 20;              // (symbol, count, first 
 //   MPC_HOST_ENTROPY=1            host_entropy     the entropy stage on the host
 //   MPC_ENTROPY_TRIPLES           triple_limit     distinct symbols per frame above which a frame takes the host route (2^20)
 //   MPC_TRACE=1                   trace            per-frame time stamps of the pipeline and the decoder on stderr
-// MPC_HOST_THREADS (worker threads of the host's table building) is read by host_bitstream.cpp, which also builds on its own.
+// MPC_HOST_THREADS (worker threads of the host's table building and parsing) is read by host_pool.cpp (host_thread_count).
 struct Tuning {
     bool steps_path = false, side_priority = true, host_entropy = false, trace = false;
     int pipes = 0, workgroups = 0, single_stripes = 0;          // > 0: forced

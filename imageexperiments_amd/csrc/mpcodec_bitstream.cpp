@@ -22,6 +22,16 @@ uint16_t* give_u16(const std::vector<uint16_t>& v, size_t* n) {
     *n = v.size();
     return p;
 }
+// the arguments of the two symbol-stream entry points; MPC_OK = usable
+mpc_status check_symbol_streams(int width, int height, int K, int block_size, const double* quant, const uint16_t* counts,
+                                const uint16_t* symbols, const unsigned long long* stream_off, uint8_t** bytes, size_t* nbytes) {
+    if (!quant || !counts || (!symbols && stream_off && stream_off[6 * K]) || !stream_off || !bytes || !nbytes || K < 1 || K > MPC_MAX_K ||
+        block_size < 1 || width < 1 || height < 1)
+        return fail(MPC_ERR_ARGUMENT, "bad argument");
+    for (int s = 0; s < 6 * K; ++s)
+        if (stream_off[s + 1] < stream_off[s]) return fail(MPC_ERR_ARGUMENT, "stream offsets must not decrease");
+    return MPC_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -69,11 +79,7 @@ mpc_status mpc_assemble_planar_streams(int width, int height, int K, int block_s
 mpc_status mpc_assemble_symbol_streams(int width, int height, int K, int block_size, const double* quant, const uint16_t* counts,
                                        const uint16_t* symbols, const unsigned long long* stream_off, uint8_t** bytes, size_t* nbytes) {
     return guarded([&]() -> mpc_status {
-    if (!quant || !counts || (!symbols && stream_off && stream_off[6 * K]) || !stream_off || !bytes || !nbytes || K < 1 || K > MPC_MAX_K ||
-        block_size < 1 || width < 1 || height < 1)
-        return fail(MPC_ERR_ARGUMENT, "bad argument");
-    for (int s = 0; s < 6 * K; ++s)
-        if (stream_off[s + 1] < stream_off[s]) return fail(MPC_ERR_ARGUMENT, "stream offsets must not decrease");
+    if (const mpc_status bad = check_symbol_streams(width, height, K, block_size, quant, counts, symbols, stream_off, bytes, nbytes)) return bad;
     *bytes = mpc::encode_symbol_streams_malloc(width, height, K, block_size, quant, counts, symbols, stream_off, nbytes);
     return *bytes ? MPC_OK : fail(MPC_ERR_ALLOC, "out of memory");
     });
@@ -82,11 +88,7 @@ mpc_status mpc_assemble_symbol_streams(int width, int height, int K, int block_s
 mpc_status mpc_assemble_symbol_streams_by_plan(int width, int height, int K, int block_size, const double* quant, const uint16_t* counts,
                                                const uint16_t* symbols, const unsigned long long* stream_off, uint8_t** bytes, size_t* nbytes) {
     return guarded([&]() -> mpc_status {
-    if (!quant || !counts || (!symbols && stream_off && stream_off[6 * K]) || !stream_off || !bytes || !nbytes || K < 1 || K > MPC_MAX_K ||
-        block_size < 1 || width < 1 || height < 1)
-        return fail(MPC_ERR_ARGUMENT, "bad argument");
-    for (int s = 0; s < 6 * K; ++s)
-        if (stream_off[s + 1] < stream_off[s]) return fail(MPC_ERR_ARGUMENT, "stream offsets must not decrease");
+    if (const mpc_status bad = check_symbol_streams(width, height, K, block_size, quant, counts, symbols, stream_off, bytes, nbytes)) return bad;
     *bytes = mpc::encode_symbol_streams_by_plan_malloc(width, height, K, block_size, quant, counts, symbols, stream_off, nbytes);
     return *bytes ? MPC_OK : fail(MPC_ERR_ALLOC, "out of memory or inconsistent plan");
     });

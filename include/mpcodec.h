@@ -191,8 +191,8 @@ mpc_status mpc_write_compressed(int width, int height, int K, int block_size, co
 mpc_status mpc_assemble_streams(int width, int height, int K, int block_size, const double* quant,
                                 const uint16_t* counts, const mpc_basis_choice* choices, uint8_t** bytes, size_t* nbytes);
 
-/* Same container from records in planar order, planar[(channel * K + step) * tiles + t] (what mpc_encode_image
- * downloads after transposing on the device: each stream's records are then one contiguous run for the host). */
+/* Same container from records in planar order, planar[(channel * K + step) * tiles + t]: each stream's records are
+ * then one contiguous run for the host.  (mpc_encode_image assembles its streams on the device and uses neither.) */
 mpc_status mpc_assemble_planar_streams(int width, int height, int K, int block_size, const double* quant,
                                        const uint16_t* counts, const mpc_basis_choice* planar, uint8_t** bytes, size_t* nbytes);
 

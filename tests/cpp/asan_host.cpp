@@ -4,7 +4,9 @@
 // bit-flipped containers (small ones made here, plus prefixes of the reference's 3.7 MB .mn when its path is given).
 #include "../../imageexperiments_amd/csrc/host_bitstream.cpp"
 #include "../../imageexperiments_amd/csrc/host_codec.cpp"
+#include "../../imageexperiments_amd/csrc/host_container.cpp"
 #include "../../imageexperiments_amd/csrc/host_dictionary.cpp"
+#include "../../imageexperiments_amd/csrc/host_pool.cpp"
 #include "../../imageexperiments_amd/csrc/host_stats.cpp"
 
 #include <cstdio>
@@ -33,7 +35,11 @@ static std::vector<uint8_t> random_container(std::mt19937& rng, int W, int H, in
     }
     std::vector<double> quant(3 * static_cast<size_t>(K));
     mpc::quantisation_tables(K, 8, 3.5, quant.data());
-    std::vector<uint8_t> blob = mpc::encode_records(W, H, K, 8, quant.data(), counts.data(), choices.data());
+    size_t n1 = 0;
+    uint8_t* b1 = mpc::encode_records_malloc(W, H, K, 8, quant.data(), counts.data(), choices.data(), &n1);
+    CHECK(b1);
+    const std::vector<uint8_t> blob(b1, b1 + (b1 ? n1 : 0));
+    std::free(b1);
     mpc::Streams s;
     CHECK(mpc::read_compressed(blob.data(), blob.size(), s));
     std::vector<uint16_t> c2;

@@ -1,9 +1,12 @@
 """The host half of the sequence decoder (no GPU): the container's header alone, and the serial half of readCompressed on its
 own -- the streams as entropy-decoded, still run-length packed and difference coded -- against the whole parser."""
+import hashlib
 import threading
 
 import numpy as np
 import pytest
+
+import container_cases
 
 # the streams of the reference's 16 Mpixel fixture the container's flag marks as run-length packed (the reference's size rule
 # replayed on its streams): all three step-0 coefficient streams (1, 65, 129) among them
@@ -86,6 +89,53 @@ def test_coded_parse_refuses_what_the_parser_refuses(mn_bytes):
             with pytest.raises(ia.MpcError) as e:
                 ia.read_compressed(bad, coded=coded)
             assert e.value.status == ia.api.MPC_ERR_BITSTREAM
+
+
+# Per damaged-container corpus (index in container_cases.FRAMES): inputs of 96 that read_compressed, read_compressed(coded=True)
+# and container_info refuse, and the SHA-256 over `lengths` and all `codes` (their bytes, in that order, input after input) of
+# the inputs read_compressed accepts.  Recorded from the library as it was before the host coder was split into three sources.
+CORPUS_PARSE = {
+    0: (65, 65, 21, "13d8ffcd4da55bba4673afb8af161419d9d0275152a253c5e3b13af134acb036"),
+    1: (49, 49, 2, "8c2a3836c712ab78158aa368b6faba295ce212643b012ee0148ab7055875dbc3"),
+    2: (28, 22, 1, "4b608623be3785f9f5ec512fd48e4f8dab88b64bc1f7304d488abb7f55dd8764"),
+    5: (34, 34, 2, "0676e7094e072f1b3700c67015682bac886144509224deb2754c955136ac701e"),
+    6: (59, 59, 17, "d3a009aa2f32158035ece947218dafc2f76f6b2d244dc1cf478181dc4bdce3a7"),
+    7: (36, 28, 3, "1a907f268dddf2b81f070ba17bdfa63f580dea73fb81497aab9a9d08f2c818cc"),
+    8: (67, 44, 5, "bb759e6f5f44dfa3e4b6554b43f6516cc142c3ce5190f68069808c7a323fc70f"),
+    10: (62, 51, 5, "19af970485fc713b21021e0adfb3c9b62d78bc1d0ee8d92f3f79de9c825ce3d1"),
+}
+
+
+def test_parser_verdicts_and_streams_on_the_damaged_corpus(oracle):
+    """The 768 damaged containers the device decoder is held to (test_gpu_decode_sequence), on the host parser alone: which of
+    them each entry point refuses (always MPC_ERR_BITSTREAM), and what read_compressed makes of the rest, pinned to the bytes."""
+    import imageexperiments_amd as ia
+
+    def refuses(call, x):
+        try:
+            return False, call(x)
+        except ia.MpcError as e:
+            assert e.status == ia.api.MPC_ERR_BITSTREAM
+            return True, None
+
+    seen = {}
+    for n, blob, xs in container_cases.corpus(oracle):
+        assert len(xs) == 96
+        digest = hashlib.sha256()
+        whole = coded = info = 0
+        for x in xs:
+            refused, s = refuses(ia.read_compressed, x)
+            whole += refused
+            if not refused:
+                digest.update(s["lengths"].tobytes())
+                for c in s["codes"]:
+                    digest.update(c.tobytes())
+            coded += refuses(lambda b: ia.read_compressed(b, coded=True), x)[0]
+            info += refuses(ia.container_info, x)[0]
+        seen[n] = (whole, coded, info, digest.hexdigest())
+        print(n, seen[n])
+    assert seen == CORPUS_PARSE
+    assert sum(v[0] for v in seen.values()) == 400
 
 
 def test_coded_parse_on_eight_threads(mn_bytes, oracle_blobs):
