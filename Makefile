@@ -5,6 +5,8 @@
 #                         in one translation unit, driven through round trips and a corpus of truncated / bit-flipped containers
 #                      2. the oracle built with the sanitizers, its golden-fixture tests run with libasan preloaded
 #   make asan-host   step 1 only (what tests/test_asan_host.py runs)
+#   make asan-index  tests/cpp/asan_index: the seek index's builder, validator and host chunk decoder on damaged containers and
+#                    damaged indexes (what tests/test_asan_index.py runs)
 #
 # GPU AddressSanitizer is not available on the test pool; the kernels are covered by the parity suite instead.
 SAN = -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer
@@ -16,6 +18,12 @@ tests/cpp/asan_host_bin: tests/cpp/asan_host.cpp $(wildcard imageexperiments_amd
 asan-host: tests/cpp/asan_host_bin
 	ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=print_stacktrace=1 MPC_HOST_THREADS=4 ./tests/cpp/asan_host_bin $(GOLDEN_MN)
 
+tests/cpp/asan_index_bin: tests/cpp/asan_index.cpp $(wildcard imageexperiments_amd/csrc/host_*.cpp imageexperiments_amd/csrc/host_*.h)
+	g++ -std=c++17 -O1 -g $(SAN) -ffp-contract=off -pthread -Wall -Wno-unused-function tests/cpp/asan_index.cpp -o $@
+
+asan-index: tests/cpp/asan_index_bin
+	ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=print_stacktrace=1 MPC_HOST_THREADS=4 ./tests/cpp/asan_index_bin $(GOLDEN_MN)
+
 oracle/_build/liboracle_asan.so: $(wildcard oracle/*.c oracle/*.h)
 	mkdir -p oracle/_build
 	gcc -std=c11 -O1 -g $(SAN) -ffp-contract=off -fPIC -shared -o $@ oracle/mpo_*.c -lm
@@ -24,6 +32,6 @@ asan-oracle: oracle/_build/liboracle_asan.so
 	LD_PRELOAD=$$(gcc -print-file-name=libasan.so) ASAN_OPTIONS=detect_leaks=0 ORACLE_LIB=$(CURDIR)/oracle/_build/liboracle_asan.so \
 	    python -m pytest tests/test_oracle_golden.py -x -q -p no:cacheprovider
 
-asan: asan-host asan-oracle
+asan: asan-host asan-index asan-oracle
 
-.PHONY: asan asan-host asan-oracle
+.PHONY: asan asan-host asan-index asan-oracle

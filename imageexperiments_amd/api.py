@@ -36,6 +36,16 @@ _dp = C.POINTER(C.c_double)
 _i32p = C.POINTER(C.c_int32)
 
 
+class _IndexHeader(C.Structure):                     # mpc_index_header
+    _fields_ = [("interval", C.c_int), ("n_streams", C.c_int), ("serial_only", C.c_int), ("width", C.c_int), ("height", C.c_int),
+                ("K", C.c_int), ("block_size", C.c_int), ("container_bytes", C.c_size_t)]
+
+
+class _IndexStreamInfo(C.Structure):                 # mpc_index_stream_info
+    _fields_ = [("mode", C.c_int), ("packed", C.c_int), ("m", C.c_uint32), ("n_coded", C.c_uint64), ("expect", C.c_uint64),
+                ("wrapper_bit", C.c_uint64), ("end_bit", C.c_uint64), ("n_checkpoints", C.c_uint64)]
+
+
 def load_library():
     """Load libmpcodec.so; raises (loudly) if the HIP extension has not been built."""
     global _lib
@@ -120,6 +130,15 @@ def _bind_bitstream(L):
                                            C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.mpc_decode_image_device.argtypes = [vp, _u8p, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.mpc_unpack_symbol_streams_device.argtypes = [vp, C.c_int, _u16p, _ullp, _u8p, _ullp, C.POINTER(_u16p), C.POINTER(C.c_size_t)]
+    L.mpc_container_index.argtypes = [_u8p, C.c_size_t, C.c_int, C.POINTER(_u8p), C.POINTER(C.c_size_t)]
+    L.mpc_index_info.argtypes = [_u8p, C.c_size_t, C.POINTER(_IndexHeader)]
+    L.mpc_index_stream.argtypes = [_u8p, C.c_size_t, C.c_int, C.POINTER(_IndexStreamInfo), C.POINTER(C.c_uint64), C.c_size_t]
+    L.mpc_parse_container_by_index.argtypes = [_u8p, C.c_size_t, _u8p, C.c_size_t, C.POINTER(_u16p), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
+    L.mpc_parse_container_device.argtypes = [vp, _u8p, C.c_size_t, _u8p, C.c_size_t, C.POINTER(_u16p), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
+    L.mpc_decode_images_indexed.argtypes = [vp, C.POINTER(_u8p), C.POINTER(C.c_size_t), C.POINTER(_u8p), C.POINTER(C.c_size_t), C.c_int,
+                                            C.POINTER(_u8p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.mpc_decode_images_indexed_device.argtypes = [vp, C.POINTER(_u8p), C.POINTER(C.c_size_t), C.POINTER(_u8p), C.POINTER(C.c_size_t), C.c_int,
+                                                   C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.mpc_huffman_encode.argtypes = [_u16p, C.c_size_t, C.POINTER(_u8p), C.POINTER(C.c_size_t)]
     L.mpc_huffman_decode.argtypes = [_u8p, C.c_size_t, C.POINTER(_u16p), C.POINTER(C.c_size_t)]
     L.mpc_rle_encode.argtypes = [_u16p, C.c_size_t, C.POINTER(_u16p), C.POINTER(C.c_size_t)]
@@ -341,6 +360,49 @@ def read_compressed(blob, coded=False):
         return out
     finally:
         L.mpc_streams_free(h)
+
+
+def container_index(blob, interval=0):
+    """mpc_container_index: the seek index of a container -> bytes.  interval: coded symbols per checkpoint, 32 ... 65536,
+    0 = the library's default.  MpcError(MPC_ERR_BITSTREAM) for whatever read_compressed(coded=True) refuses."""
+    L = load_library()
+    buf = np.frombuffer(blob, np.uint8)
+    out, n = _u8p(), C.c_size_t(0)
+    _check(L.mpc_container_index(buf.ctypes.data_as(_u8p), buf.size, int(interval), C.byref(out), C.byref(n)))
+    return _take_bytes(L, out, n)
+
+
+def index_info(index):
+    """mpc_index_info / mpc_index_stream: an index read back -> dict(interval, serial_only, nbytes, W, H, K, bs, streams), streams
+    = one dict per stream (the lengths stream first): mode (0 Huffman, 1 Golomb), m, packed, n_coded, expect, wrapper_bit,
+    end_bit, checkpoints (uint64 array).  MpcError(MPC_ERR_BITSTREAM) if it is not an index."""
+    L = load_library()
+    buf = np.frombuffer(index, np.uint8)
+    ptr = buf.ctypes.data_as(_u8p)
+    h = _IndexHeader()
+    _check(L.mpc_index_info(ptr, buf.size, C.byref(h)))
+    streams = []
+    for j in range(h.n_streams):
+        si = _IndexStreamInfo()
+        _check(L.mpc_index_stream(ptr, buf.size, j, C.byref(si), None, 0))
+        cp = np.zeros(si.n_checkpoints, np.uint64)
+        _check(L.mpc_index_stream(ptr, buf.size, j, C.byref(si), cp.ctypes.data_as(C.POINTER(C.c_uint64)), cp.size))
+        streams.append(dict(mode=si.mode, m=si.m, packed=bool(si.packed), n_coded=si.n_coded, expect=si.expect,
+                            wrapper_bit=si.wrapper_bit, end_bit=si.end_bit, checkpoints=cp))
+    return dict(interval=h.interval, serial_only=bool(h.serial_only), nbytes=h.container_bytes, W=h.width, H=h.height, K=h.K,
+                bs=h.block_size, streams=streams)
+
+
+def parse_container_by_index(blob, index):
+    """mpc_parse_container_by_index: the chunked parse on the host -> (symbols, route): the lengths stream and the 6K coded
+    streams of read_compressed(coded=True) back to back (uint16); route 0 = the index was used, 1 = refused, the serial parse's
+    result.  MpcError as read_compressed(coded=True) raises it."""
+    L = load_library()
+    buf, idx = np.frombuffer(blob, np.uint8), np.frombuffer(index, np.uint8)
+    out, n, route = _u16p(), C.c_size_t(0), C.c_int(-1)
+    _check(L.mpc_parse_container_by_index(buf.ctypes.data_as(_u8p), buf.size, idx.ctypes.data_as(_u8p), idx.size, C.byref(out),
+                                          C.byref(n), C.byref(route)))
+    return _take_u16(L, out, n), route.value
 
 
 def decode_image(blob, ctx):
@@ -697,6 +759,58 @@ class CompressionContext:
 
     def decode_image_device(self, blob, out=None):
         return self.decode_images_device([blob], None if out is None else [out])[0]
+
+    @staticmethod
+    def _indexes(indexes, n):
+        if len(indexes) != n:
+            raise ValueError("one index (or None) per container")
+        bufs = [None if x is None else np.frombuffer(x, np.uint8) for x in indexes]
+        ptrs = (_u8p * n)(*[_u8p() if b is None else b.ctypes.data_as(_u8p) for b in bufs])
+        return bufs, ptrs, (C.c_size_t * n)(*[0 if b is None else b.size for b in bufs])
+
+    def decode_images_indexed(self, blobs, indexes):
+        """mpc_decode_images_indexed: decode_images with a seek index (container_index) per container, None = without: a frame
+        with an index has its entropy codes parsed on the device.  Returns (frames, routes), routes[f] 0 = parsed on the device,
+        1 = the serial route.  Pixels and errors are decode_images's, whatever an index holds."""
+        bufs, ptrs, sizes = self._containers(blobs)
+        n = len(bufs)
+        ibufs, iptrs, isizes = self._indexes(indexes, n)
+        outs, W, H, routes = (_u8p * n)(), (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)()
+        _check(self.L.mpc_decode_images_indexed(self.h, ptrs, sizes, iptrs, isizes, n, outs, W, H, routes))
+        return [_take_view(self.L, outs[i], C.c_size_t(3 * W[i] * H[i])).reshape(H[i], W[i], 3) for i in range(n)], list(routes)
+
+    def decode_images_indexed_device(self, blobs, indexes, out=None):
+        """mpc_decode_images_indexed_device: the same with the pixels left on the context's device (`out` as for
+        decode_images_device).  Returns (frames, routes)."""
+        import torch
+        bufs, ptrs, sizes = self._containers(blobs)
+        n = len(bufs)
+        ibufs, iptrs, isizes = self._indexes(indexes, n)
+        if out is None:
+            out = []
+            for b in bufs:
+                try:
+                    w, h, _, _ = container_info(b)
+                except MpcError:                                 # the call itself refuses the frame, in its turn, by its index
+                    w, h = 1, 1
+                out.append(torch.empty(3 * w * h, dtype=torch.uint8, device=f"cuda:{self.device}"))
+        if len(out) != n or any(t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous() for t in out):
+            raise ValueError("out: one contiguous uint8 device tensor per container")
+        d_ptrs = (C.c_void_p * n)(*[C.c_void_p(t.data_ptr()) for t in out])
+        caps = (C.c_size_t * n)(*[t.numel() for t in out])
+        W, H, routes = (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)()
+        torch.cuda.synchronize(self.device)                      # `out` may still be being written by the caller's streams
+        _check(self.L.mpc_decode_images_indexed_device(self.h, ptrs, sizes, iptrs, isizes, n, d_ptrs, caps, W, H, routes))
+        return [out[i].view(-1)[:3 * W[i] * H[i]].view(H[i], W[i], 3) for i in range(n)], list(routes)
+
+    def parse_container_device(self, blob, index):
+        """mpc_parse_container_device: parse_container_by_index with the chunks decoded on the device (the decoder's own
+        upload-and-parse step) -> (symbols, route)."""
+        buf, idx = np.frombuffer(blob, np.uint8), np.frombuffer(index, np.uint8)
+        out, n, route = _u16p(), C.c_size_t(0), C.c_int(-1)
+        _check(self.L.mpc_parse_container_device(self.h, buf.ctypes.data_as(_u8p), buf.size, idx.ctypes.data_as(_u8p), idx.size,
+                                                 C.byref(out), C.byref(n), C.byref(route)))
+        return _take_u16(self.L, out, n), route.value
 
     def unpack_symbol_streams_device(self, coded, packed, expect):
         """mpc_unpack_symbol_streams_device: coded[6K] = the streams as entropy-decoded, packed[6K] = run-length packed or not,

@@ -548,10 +548,12 @@ void huffman_encode(const uint16_t* data, size_t n, BitWriter& out) {
     out.put(t.eof_code, t.eof_length);
 }
 
-// Huffman.cpp:173-244
-bool huffman_decode(BitReader& in, std::vector<uint16_t>& out) {
-    const int max_length = static_cast<int>(in.get(8));
-    std::vector<uint16_t> counts(static_cast<size_t>(max_length));
+// The table in front of a Huffman stream's codes (Huffman.cpp:173-200) and what the decoders derive from it
+bool read_huffman_codebook(BitReader& in, HuffmanCodebook& cb) {
+    cb.max_length = static_cast<int>(in.get(8));
+    const int max_length = cb.max_length;
+    std::vector<uint16_t>& counts = cb.counts;
+    counts.assign(static_cast<size_t>(max_length), 0);
     size_t entries = 0;
     for (int l = 0; l < max_length; ++l) {
         counts[l] = static_cast<uint16_t>(in.get(16));
@@ -561,11 +563,13 @@ bool huffman_decode(BitReader& in, std::vector<uint16_t>& out) {
     // cannot come from its encoder; a symbol width above 16 overflows its mask.  Both are invalid data here.
     if (entries > 65535) return false;
     const uint16_t total = static_cast<uint16_t>(entries);
+    cb.total = total;
     const int symbol_bits = static_cast<int>(in.get(8));
     if (symbol_bits < 1 || symbol_bits > 16) return false;
     if (entries > in.remaining()) return false;                 // every table entry takes at least one bit
     const uint16_t mask = static_cast<uint16_t>((1u << symbol_bits) - 1u);
-    std::vector<uint16_t> table(total);
+    std::vector<uint16_t>& table = cb.table;
+    table.assign(total, 0);
     size_t at = 0;
     for (int l = 0; l < max_length; ++l) {
         const uint16_t size = counts[l];
@@ -577,22 +581,50 @@ bool huffman_decode(BitReader& in, std::vector<uint16_t>& out) {
         at += size;
     }
     if (total == 0 || table[total - 1u] != mask) return false;      // the last entry must be the pseudo-EOF
-    std::vector<uint32_t> first_code(static_cast<size_t>(max_length) + 1, 0), first_index(static_cast<size_t>(max_length) + 1, 0);
+    cb.first_code.assign(static_cast<size_t>(max_length) + 1, 0);
+    cb.first_index.assign(static_cast<size_t>(max_length) + 1, 0);
     uint32_t code = 0, index = 0;
     int prev = 0;
     for (int l = 1; l <= max_length; ++l) {
         if (!counts[l - 1]) continue;
         code <<= (l - prev);
-        first_code[l] = code;
-        first_index[l] = index;
+        cb.first_code[l] = code;
+        cb.first_index[l] = index;
         code += counts[l - 1];
         index += counts[l - 1];
         prev = l;
     }
+    cb.lut.clear();
+    if (max_length > 32) return true;                           // no encoder writes this: the literal bit-by-bit walk, no window
+    // codes of up to kLutBits bits through a table, filled shortest length first, so an over-subscribed table still resolves
+    // to the first match
+    constexpr int kLutBits = HuffmanCodebook::kLutBits;
+    cb.lut.assign(static_cast<size_t>(1) << kLutBits, 0);
+    for (int l = 1; l <= std::min(max_length, kLutBits); ++l) {
+        for (uint32_t k = 0; k < counts[l - 1]; ++k) {
+            const uint64_t value = static_cast<uint64_t>(cb.first_code[l]) + k;
+            if (value >> l) break;                                              // not an l-bit number: can never match
+            const uint32_t lo = static_cast<uint32_t>(value) << (kLutBits - l);
+            for (uint32_t fill = 0; fill < (1u << (kLutBits - l)); ++fill)
+                if (cb.lut[lo + fill] == 0) cb.lut[lo + fill] = ((cb.first_index[l] + k) << 5) | static_cast<uint32_t>(l);
+        }
+    }
+    return true;
+}
+
+// Huffman.cpp:173-244
+bool huffman_decode(BitReader& in, std::vector<uint16_t>& out) {
+    HuffmanCodebook cb;
+    if (!read_huffman_codebook(in, cb)) return false;
+    const int max_length = cb.max_length;
+    const uint16_t total = cb.total;
+    const std::vector<uint16_t>& counts = cb.counts;
+    const std::vector<uint16_t>& table = cb.table;
+    const std::vector<uint32_t>& first_code = cb.first_code;
+    const std::vector<uint32_t>& first_index = cb.first_index;
     // The reference shifts bits in one at a time and takes the first length at which the accumulated value is a code
-    // of that length.  Same decisions here from a 32-bit look-ahead: codes of up to kLutBits bits through a table
-    // (filled shortest length first, so an over-subscribed table still resolves to the first match), longer ones by
-    // the reference's test per length.
+    // of that length.  Same decisions here from a 32-bit look-ahead: codes of up to kLutBits bits through the codebook's
+    // window table, longer ones by the reference's test per length.
     if (max_length > 32) {                                      // no encoder writes this; keep the literal bit-by-bit walk
         uint64_t acc = 0;
         int bits = 0;
@@ -609,17 +641,8 @@ bool huffman_decode(BitReader& in, std::vector<uint16_t>& out) {
         }
         return false;
     }
-    constexpr int kLutBits = 11;
-    std::vector<uint32_t> lut(static_cast<size_t>(1) << kLutBits, 0);           // (entry << 5) | length, 0 = no short code
-    for (int l = 1; l <= std::min(max_length, kLutBits); ++l) {
-        for (uint32_t k = 0; k < counts[l - 1]; ++k) {
-            const uint64_t value = static_cast<uint64_t>(first_code[l]) + k;
-            if (value >> l) break;                                              // not an l-bit number: can never match
-            const uint32_t lo = static_cast<uint32_t>(value) << (kLutBits - l);
-            for (uint32_t fill = 0; fill < (1u << (kLutBits - l)); ++fill)
-                if (lut[lo + fill] == 0) lut[lo + fill] = ((first_index[l] + k) << 5) | static_cast<uint32_t>(l);
-        }
-    }
+    constexpr int kLutBits = HuffmanCodebook::kLutBits;
+    const std::vector<uint32_t>& lut = cb.lut;                                  // (entry << 5) | length, 0 = no short code
     // two symbols per look-up where two whole codes (neither the pseudo-EOF) fit the window: same symbols in the same order
     std::vector<uint32_t> pair_symbols(lut.size(), 0);
     std::vector<uint8_t> pair_bits(lut.size(), 0);
@@ -1072,6 +1095,90 @@ bool read_huffman_or_golomb(BitReader& in, size_t length, std::vector<uint16_t>&
     }
     for (; i < length; ++i) dst[i] = static_cast<uint16_t>(golomb_read(m, in));
     return true;
+}
+
+// ------------------------------------------------------------------------------------------------
+// One code at a time, from any bit: what a decode by seek index is made of (host_container.cpp; mp_parse.hip does the same on
+// the device).  Both take the serial decoders' decisions exactly and, unlike them, never read at or behind bit `end`.
+// ------------------------------------------------------------------------------------------------
+bool huffman_step(const HuffmanCodebook& cb, BitReader& in, size_t end, uint32_t* entry) {
+    constexpr int kLutBits = HuffmanCodebook::kLutBits;
+    if (cb.lut.empty() || in.position() >= end) return false;
+    const size_t left = end - in.position();
+    const uint32_t window = in.peek32();
+    const uint32_t hit = cb.lut[window >> (32 - kLutBits)];
+    uint32_t e = 0;
+    int used = 0;
+    if (hit != 0) {
+        e = hit >> 5;
+        used = static_cast<int>(hit & 31u);
+    } else {
+        for (int l = kLutBits + 1; l <= cb.max_length; ++l) {       // the reference's test per length, shortest first
+            const uint32_t acc = window >> (32 - l);
+            if (cb.counts[l - 1] && acc >= cb.first_code[l] && acc - cb.first_code[l] < cb.counts[l - 1]) {
+                e = cb.first_index[l] + (acc - cb.first_code[l]);
+                used = l;
+                break;
+            }
+        }
+    }
+    // a window entry longer than what is left: huffman_decode goes on to other lengths there; a seek index never leads there
+    if (used == 0 || static_cast<size_t>(used) > left) return false;
+    in.skip(static_cast<size_t>(used));
+    *entry = e;
+    return true;
+}
+
+bool golomb_step(uint32_t m, BitReader& in, size_t end, uint32_t* value) {
+    uint32_t q = 0;
+    for (;;) {
+        if (in.position() >= end) return false;
+        const size_t left = end - in.position();
+        const uint32_t ones = static_cast<uint32_t>(__builtin_clz(~in.peek32() | 1u));      // leading ones, 31 at most counted here
+        if (ones >= 31 && left > 31) { q += 31; in.skip(31); continue; }
+        if (ones >= left) return false;                         // the terminating zero lies behind `end`
+        q += ones;
+        in.skip(static_cast<size_t>(ones) + 1);
+        break;
+    }
+    const uint32_t b = bit_width(m);
+    const uint32_t limit = (1u << (b + 1)) - m;
+    if (end - in.position() < b) return false;
+    const uint32_t first = static_cast<uint32_t>(in.get(static_cast<int>(b)));
+    uint32_t rem = first;
+    if (first >= limit) {
+        if (in.position() >= end) return false;
+        rem = (first << 1) + static_cast<uint32_t>(in.get(1)) - limit;
+    }
+    *value = q * m + rem;
+    return true;
+}
+
+bool huffman_decode_chunk(const HuffmanCodebook& cb, const uint8_t* bytes, size_t nbytes, size_t begin, size_t end, size_t count,
+                          bool last, uint16_t* out) {
+    if (begin > end || end > 8 * nbytes || cb.total == 0) return false;
+    BitReader in(bytes, nbytes);
+    in.set_position(begin);
+    const uint32_t eof = static_cast<uint32_t>(cb.total) - 1u;
+    uint32_t entry = 0;
+    for (size_t i = 0; i < count; ++i) {
+        if (!huffman_step(cb, in, end, &entry) || entry == eof) return false;
+        out[i] = cb.table[entry];
+    }
+    if (last && (!huffman_step(cb, in, end, &entry) || entry != eof)) return false;
+    return in.position() == end;
+}
+
+bool golomb_decode_chunk(uint32_t m, const uint8_t* bytes, size_t nbytes, size_t begin, size_t end, size_t count, uint16_t* out) {
+    if (begin > end || end > 8 * nbytes || m == 0) return false;
+    BitReader in(bytes, nbytes);
+    in.set_position(begin);
+    uint32_t value = 0;
+    for (size_t i = 0; i < count; ++i) {
+        if (!golomb_step(m, in, end, &value)) return false;
+        out[i] = static_cast<uint16_t>(value);
+    }
+    return in.position() == end;
 }
 
 }  // namespace mpc

@@ -73,6 +73,28 @@ bool elias_fano_read(uint16_t* dst, size_t n, uint16_t max_symbol, BitReader& in
 void huffman_encode(const uint16_t* data, size_t n, BitWriter& out);
 bool huffman_decode(BitReader& in, std::vector<uint16_t>& out);          // false = "Invalid bitstream"
 
+// The table in front of a Huffman stream's codes, and what a decoder derives from it
+struct HuffmanCodebook {
+    static constexpr int kLutBits = 11;
+    int max_length = 0;
+    uint16_t total = 0;                             // entries; the last one is the pseudo-EOF
+    std::vector<uint16_t> counts;                   // [max_length] codes of each length
+    std::vector<uint16_t> table;                    // [total] entry -> symbol, in order of (length, symbol)
+    std::vector<uint32_t> first_code, first_index;  // [max_length + 1] of each used length
+    std::vector<uint32_t> lut;                      // [1 << kLutBits] by the next bits: (entry << 5) | length, 0 = no code this
+                                                    // short; filled shortest length first.  Empty when max_length > 32
+};
+bool read_huffman_codebook(BitReader& in, HuffmanCodebook& cb);          // false = what huffman_decode refuses a table for
+// One code at in's position, with huffman_decode's / golomb_read's decision, that ends at or before bit `end` (<= the data's
+// bits); false = there is none.  *entry indexes cb.table (total - 1 = the pseudo-EOF); *value is not yet cut to 16 bits.
+bool huffman_step(const HuffmanCodebook& cb, BitReader& in, size_t end, uint32_t* entry);
+bool golomb_step(uint32_t m, BitReader& in, size_t end, uint32_t* value);
+// `count` codes from bit `begin` that end exactly on bit `end`, none of them the pseudo-EOF; last: the pseudo-EOF follows them
+// and it is what ends on `end`.  false = not so; out[0 .. count) may then hold anything
+bool huffman_decode_chunk(const HuffmanCodebook& cb, const uint8_t* bytes, size_t nbytes, size_t begin, size_t end, size_t count,
+                          bool last, uint16_t* out);
+bool golomb_decode_chunk(uint32_t m, const uint8_t* bytes, size_t nbytes, size_t begin, size_t end, size_t count, uint16_t* out);
+
 std::vector<uint16_t> rle_encode(const uint16_t* data, size_t n);
 std::vector<uint16_t> rle_decode(const uint16_t* data, size_t n);
 // the sizes rle_encode / rle_decode would produce, without producing them; rle_decoded_size: false once it exceeds `limit`
@@ -106,6 +128,53 @@ struct CodedStreams : Streams {
 // The serial half of read_compressed (which is this + run-length expansion + DC sums on the worker pool): uses no pool and no
 // shared state, so several threads may parse containers side by side.  false = invalid data
 bool read_compressed_coded(const uint8_t* bytes, size_t nbytes, CodedStreams& out);
+// ---- seek index ("Seek index"): where every stream and every interval-th code of it begins ----
+struct StreamWrapper {                              // what stands in front of a stream's codes
+    bool packed = false;                            // the run-length flag (never set for the lengths stream, which has none)
+    uint64_t packed_size = 0;
+    int mode = 0;                                   // 0 = Huffman, 1 = Golomb
+    uint32_t m = 0;
+    HuffmanCodebook cb;
+    size_t first_code_bit = 0;
+};
+// false = what the serial parser refuses at this point (a bad table, M = 0)
+bool read_stream_wrapper(BitReader& in, bool has_flag, StreamWrapper& w);
+
+struct IndexStream {
+    uint64_t wrapper_bit = 0, end_bit = 0, n_coded = 0, expect = 0;
+    uint32_t packed = 0, mode = 0, m = 0;
+    std::vector<uint64_t> checkpoints;              // bit of coded symbol j * interval
+};
+struct ContainerIndex {
+    uint32_t interval = 0;
+    bool serial_only = false;                       // a Huffman table with codes longer than 32 bits: no checkpoints
+    uint64_t nbytes = 0;
+    int width = 0, height = 0, K = 0, block_size = 0;
+    std::vector<IndexStream> streams;               // [1 + 6K], the lengths stream first
+};
+constexpr uint32_t kIndexIntervalMin = 32, kIndexIntervalMax = 65536, kIndexIntervalDefault = 128;
+// One serial parse of the container, positions recorded; false = what read_compressed_coded refuses.  interval 0 = the default
+bool build_container_index(const uint8_t* bytes, size_t nbytes, uint32_t interval, std::vector<uint8_t>& blob);
+// the blob alone: magic, version, sizes.  Says nothing about any container
+bool read_container_index(const uint8_t* index, size_t index_bytes, ContainerIndex& out);
+// An index checked against its container as far as the host can without decoding a code (the acceptance rule's first half):
+// the wrappers read from the container, the tables built.  false = the index is not used.
+struct IndexedPlan {
+    ContainerIndex index;
+    std::vector<StreamWrapper> wrappers;            // [1 + 6K]
+    size_t tiles = 0;
+    uint16_t quant[3][32] = {};
+};
+// pooled: the streams' wrappers are read on the worker pool (a caller with the machine to itself: a single frame)
+bool plan_indexed_parse(const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes, IndexedPlan& plan,
+                        bool pooled = false);
+// what the lengths stream says the 6K streams expand to (read_compressed_coded's `expect`)
+std::vector<size_t> expected_sizes(const std::vector<uint16_t>& lengths, int K);
+// read_compressed_coded chunk by chunk from the index; *route = 0: the index was used, 1: it was refused and the serial parse
+// gave the result.  Returns what read_compressed_coded returns, `out` what it gives.
+bool read_compressed_coded_by_index(const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes, CodedStreams& out,
+                                    int* route);
+
 // the header alone; false = not a container read_compressed would accept the header of
 bool container_info(const uint8_t* bytes, size_t nbytes, int* width, int* height, int* K, int* block_size);
 // worker threads of the host stages (MPC_HOST_THREADS, else the machine's, at most 16)

@@ -283,7 +283,9 @@ uint8_t* encode_symbol_streams_by_plan_malloc(int width, int height, int K, int 
 // The serial half of readCompressed: everything the format chains from one code to the next (the codes are self-delimiting and
 // a stream's table sits where the stream before it ended), and nothing else.  No worker pool, no shared state: safe on several
 // threads at once.
-bool read_compressed_coded(const uint8_t* bytes, size_t nbytes, CodedStreams& s) {
+namespace {
+// read_compressed_coded; bounds (optional): [1 + 6K + 1] the bit each stream's wrapper begins at, and the bit behind the last stream
+bool parse_coded(const uint8_t* bytes, size_t nbytes, CodedStreams& s, std::vector<size_t>* bounds) {
     BitReader in(bytes, nbytes);
     if (!read_header(in, &s.width, &s.height, &s.K, &s.block_size)) return false;
     const int K = s.K;
@@ -292,33 +294,18 @@ bool read_compressed_coded(const uint8_t* bytes, size_t nbytes, CodedStreams& s)
     const size_t tiles = tile_count(s.width, s.height, s.block_size);
     s.lengths.clear();
     if (tiles > (static_cast<size_t>(1) << 40) / 3) return false;
+    if (bounds) bounds->assign(1, in.position());
     if (!read_huffman_or_golomb(in, 3 * tiles, s.lengths)) return false;
     // a Huffman-coded lengths stream carries its own end: it must still describe exactly this frame's tiles (the
     // device decoder walks tiles_x * tiles_y records)
     if (s.lengths.size() != 3 * tiles) return false;
     s.codes.assign(static_cast<size_t>(6 * K), {});
-    // length of an un-packed stream = tile-channels of its layer with more than `depth` atoms (:680-685): suffix sums
-    // of the histogram of lengths, once for all 6K streams
-    std::vector<size_t> expect_of(static_cast<size_t>(3 * K), 0);
-    {
-        std::vector<size_t> hist(static_cast<size_t>(3) * 65536, 0);
-        for (size_t t = 0; t < s.lengths.size() / 3; ++t)
-            for (size_t layer = 0; layer < 3; ++layer) ++hist[layer * 65536 + s.lengths[3 * t + layer]];
-        for (size_t layer = 0; layer < 3; ++layer) {
-            size_t above = 0;
-            for (int v = 65535; v > K; --v) above += hist[layer * 65536 + static_cast<size_t>(v)];
-            for (int depth = K - 1; depth >= 0; --depth) {
-                above += hist[layer * 65536 + static_cast<size_t>(depth + 1)];
-                expect_of[layer * static_cast<size_t>(K) + static_cast<size_t>(depth)] = above;
-            }
-        }
-    }
     // Only the entropy codes are undone here: run-length expansion (:660-678) and the DC sums (:690-705) of a stream need nothing
     // from the streams behind it (read_compressed does them on the pool, the sequence decoder on the device).
     s.packed.assign(static_cast<size_t>(6 * K), 0);
-    s.expect.assign(static_cast<size_t>(6 * K), 0);
+    s.expect = expected_sizes(s.lengths, K);
     for (int i = 0; i < 6 * K; ++i) {
-        s.expect[i] = expect_of[(static_cast<size_t>(i / 2) / K) * static_cast<size_t>(K) + static_cast<size_t>(i / 2) % K];
+        if (bounds) bounds->push_back(in.position());
         if (in.get(1) == 1) {
             const size_t packed_len = static_cast<size_t>(in.get(32));
             s.packed[i] = 1;
@@ -331,7 +318,284 @@ bool read_compressed_coded(const uint8_t* bytes, size_t nbytes, CodedStreams& s)
             if (!read_huffman_or_golomb(in, s.expect[i], s.codes[i])) return false;
         }
     }
+    if (bounds) bounds->push_back(in.position());
     return true;
+}
+}  // namespace
+
+// length of an un-packed stream = tile-channels of its layer with more than `depth` atoms (:680-685): suffix sums
+// of the histogram of lengths, once for all 6K streams
+std::vector<size_t> expected_sizes(const std::vector<uint16_t>& lengths, int K) {
+    std::vector<size_t> expect_of(static_cast<size_t>(3 * K), 0);
+    std::vector<size_t> hist(static_cast<size_t>(3) * 65536, 0);
+    for (size_t t = 0; t < lengths.size() / 3; ++t)
+        for (size_t layer = 0; layer < 3; ++layer) ++hist[layer * 65536 + lengths[3 * t + layer]];
+    for (size_t layer = 0; layer < 3; ++layer) {
+        size_t above = 0;
+        for (int v = 65535; v > K; --v) above += hist[layer * 65536 + static_cast<size_t>(v)];
+        for (int depth = K - 1; depth >= 0; --depth) {
+            above += hist[layer * 65536 + static_cast<size_t>(depth + 1)];
+            expect_of[layer * static_cast<size_t>(K) + static_cast<size_t>(depth)] = above;
+        }
+    }
+    std::vector<size_t> expect(static_cast<size_t>(6 * K), 0);
+    for (int i = 0; i < 6 * K; ++i)
+        expect[i] = expect_of[(static_cast<size_t>(i / 2) / K) * static_cast<size_t>(K) + static_cast<size_t>(i / 2) % K];
+    return expect;
+}
+
+bool read_compressed_coded(const uint8_t* bytes, size_t nbytes, CodedStreams& s) { return parse_coded(bytes, nbytes, s, nullptr); }
+
+// ------------------------------------------------------------------------------------------------
+// The seek index.  The format chains a stream's first bit to the stream before it and a code's first bit to the code before it,
+// and nothing else: with the bit of every stream's wrapper and of every interval-th code, every chunk of `interval` codes
+// decodes on its own.  The index is a hint: plan_indexed_parse and the chunk decoders accept it only where the serial parser,
+// started at bit 0, provably passes through every position it names with the same symbols.
+//
+// Blob, little-endian:   0 u32 magic "MPIX"  4 u32 version  8 u32 interval  12 u32 flags (1 = serial only)  16 u64 container bytes
+//   24 u32 width  28 u32 height  32 u32 K  36 u32 block size  40 u32 streams (1 + 6K)  44 u32 0  48 u64 checkpoints in all
+//   56 per stream, 64 bytes: u64 wrapper bit, end bit, coded symbols, expected symbols, first checkpoint, checkpoints;
+//      u32 packed, mode, M, 0
+//   then u64 per checkpoint
+// ------------------------------------------------------------------------------------------------
+namespace {
+constexpr uint32_t kIndexMagic = 0x5849504Du, kIndexVersion = 1;
+constexpr size_t kIndexHead = 56, kIndexStream = 64;
+
+void put32(std::vector<uint8_t>& b, uint32_t v) { for (int k = 0; k < 4; ++k) b.push_back(static_cast<uint8_t>(v >> (8 * k))); }
+void put64(std::vector<uint8_t>& b, uint64_t v) { for (int k = 0; k < 8; ++k) b.push_back(static_cast<uint8_t>(v >> (8 * k))); }
+uint32_t get32(const uint8_t* p) { return p[0] | (uint32_t(p[1]) << 8) | (uint32_t(p[2]) << 16) | (uint32_t(p[3]) << 24); }
+uint64_t get64(const uint8_t* p) { return get32(p) | (static_cast<uint64_t>(get32(p + 4)) << 32); }
+
+std::vector<uint8_t> index_blob(const ContainerIndex& x) {
+    std::vector<uint8_t> b;
+    uint64_t total = 0;
+    for (const IndexStream& s : x.streams) total += s.checkpoints.size();
+    b.reserve(kIndexHead + kIndexStream * x.streams.size() + 8 * total);
+    put32(b, kIndexMagic); put32(b, kIndexVersion); put32(b, x.interval); put32(b, x.serial_only ? 1u : 0u);
+    put64(b, x.nbytes);
+    put32(b, static_cast<uint32_t>(x.width)); put32(b, static_cast<uint32_t>(x.height));
+    put32(b, static_cast<uint32_t>(x.K)); put32(b, static_cast<uint32_t>(x.block_size));
+    put32(b, static_cast<uint32_t>(x.streams.size())); put32(b, 0);
+    put64(b, total);
+    uint64_t first = 0;
+    for (const IndexStream& s : x.streams) {
+        put64(b, s.wrapper_bit); put64(b, s.end_bit); put64(b, s.n_coded); put64(b, s.expect);
+        put64(b, first); put64(b, s.checkpoints.size());
+        put32(b, s.packed); put32(b, s.mode); put32(b, s.m); put32(b, 0);
+        first += s.checkpoints.size();
+    }
+    for (const IndexStream& s : x.streams)
+        for (uint64_t c : s.checkpoints) put64(b, c);
+    return b;
+}
+}  // namespace
+
+bool read_stream_wrapper(BitReader& in, bool has_flag, StreamWrapper& w) {
+    w = StreamWrapper();
+    if (has_flag && in.get(1) == 1) {
+        w.packed = true;
+        w.packed_size = in.get(32);
+    }
+    w.mode = static_cast<int>(in.get(1));
+    if (w.mode == 0) {
+        if (!read_huffman_codebook(in, w.cb)) return false;
+    } else {
+        w.m = static_cast<uint32_t>(in.get(16));
+        if (w.m == 0) return false;
+    }
+    w.first_code_bit = in.position();
+    return true;
+}
+
+bool build_container_index(const uint8_t* bytes, size_t nbytes, uint32_t interval, std::vector<uint8_t>& blob) {
+    if (interval == 0) interval = kIndexIntervalDefault;
+    CodedStreams s;
+    std::vector<size_t> bounds;
+    if (!parse_coded(bytes, nbytes, s, &bounds)) return false;
+    const int n_streams = 6 * s.K + 1;
+    ContainerIndex x;
+    x.interval = interval;
+    x.nbytes = nbytes;
+    x.width = s.width; x.height = s.height; x.K = s.K; x.block_size = s.block_size;
+    x.streams.resize(static_cast<size_t>(n_streams));
+    // The positions inside a stream: its codes once more, one at a time, by the chunk decoders' own step.  Whatever that walk
+    // cannot reproduce (codes longer than 32 bits; anything else would be a defect here) leaves an index that says
+    // "serial only": still valid, never wrong.
+    for (int j = 0; j < n_streams; ++j) {
+        IndexStream& is = x.streams[static_cast<size_t>(j)];
+        const std::vector<uint16_t>& want = j == 0 ? s.lengths : s.codes[static_cast<size_t>(j - 1)];
+        is.wrapper_bit = bounds[static_cast<size_t>(j)];
+        is.end_bit = bounds[static_cast<size_t>(j) + 1];
+        is.n_coded = want.size();
+        is.expect = j == 0 ? want.size() : s.expect[static_cast<size_t>(j - 1)];
+        is.packed = j != 0 && s.packed[static_cast<size_t>(j - 1)];
+        BitReader in(bytes, nbytes);
+        in.set_position(is.wrapper_bit);
+        StreamWrapper w;
+        if (!read_stream_wrapper(in, j != 0, w)) { x.serial_only = true; continue; }
+        is.mode = static_cast<uint32_t>(w.mode);
+        is.m = w.m;
+        if (x.serial_only) continue;
+        bool same = true;
+        uint32_t v = 0;
+        for (size_t i = 0; i < want.size() && same; ++i) {
+            if (i % interval == 0) is.checkpoints.push_back(in.position());
+            if (w.mode == 0) same = huffman_step(w.cb, in, is.end_bit, &v) && v + 1u != w.cb.total && w.cb.table[v] == want[i];
+            else same = golomb_step(w.m, in, is.end_bit, &v) && static_cast<uint16_t>(v) == want[i];
+        }
+        if (same && w.mode == 0) same = huffman_step(w.cb, in, is.end_bit, &v) && v + 1u == w.cb.total;
+        if (!same || in.position() != is.end_bit) x.serial_only = true;
+    }
+    if (x.serial_only)
+        for (IndexStream& is : x.streams) is.checkpoints.clear();
+    blob = index_blob(x);
+    return true;
+}
+
+bool read_container_index(const uint8_t* index, size_t index_bytes, ContainerIndex& x) {
+    if (!index || index_bytes < kIndexHead) return false;
+    if (get32(index) != kIndexMagic || get32(index + 4) != kIndexVersion) return false;
+    x = ContainerIndex();
+    x.interval = get32(index + 8);
+    const uint32_t flags = get32(index + 12);
+    x.serial_only = (flags & 1u) != 0;
+    x.nbytes = get64(index + 16);
+    const uint32_t width = get32(index + 24), height = get32(index + 28), K = get32(index + 32), bs = get32(index + 36);
+    const uint32_t n_streams = get32(index + 40);
+    const uint64_t total = get64(index + 48);
+    if (flags > 1u || get32(index + 44) != 0) return false;
+    if (x.interval < kIndexIntervalMin || x.interval > kIndexIntervalMax) return false;
+    if (K < 1 || K > 32 || bs < 1 || bs > 8 || width < 1 || height < 1 || width > 0x7FFFFFFFu || height > 0x7FFFFFFFu) return false;
+    if (n_streams != 6 * K + 1) return false;
+    const size_t fixed = kIndexHead + kIndexStream * n_streams;
+    if (index_bytes < fixed || total != (index_bytes - fixed) / 8 || (index_bytes - fixed) % 8 != 0) return false;
+    x.width = static_cast<int>(width); x.height = static_cast<int>(height); x.K = static_cast<int>(K); x.block_size = static_cast<int>(bs);
+    x.streams.resize(n_streams);
+    uint64_t first = 0;
+    for (uint32_t j = 0; j < n_streams; ++j) {
+        const uint8_t* r = index + kIndexHead + kIndexStream * j;
+        IndexStream& is = x.streams[j];
+        is.wrapper_bit = get64(r); is.end_bit = get64(r + 8); is.n_coded = get64(r + 16); is.expect = get64(r + 24);
+        const uint64_t at = get64(r + 32), n_cp = get64(r + 40);
+        is.packed = get32(r + 48); is.mode = get32(r + 52); is.m = get32(r + 56);
+        if (at != first || n_cp > total - first || is.packed > 1u || is.mode > 1u || get32(r + 60) != 0) return false;
+        is.checkpoints.resize(static_cast<size_t>(n_cp));
+        for (uint64_t k = 0; k < n_cp; ++k) is.checkpoints[static_cast<size_t>(k)] = get64(index + fixed + 8 * (first + k));
+        first += n_cp;
+    }
+    return first == total;
+}
+
+bool plan_indexed_parse(const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes, IndexedPlan& plan, bool pooled) {
+    ContainerIndex& x = plan.index;
+    if (!read_container_index(index, index_bytes, x) || x.serial_only) return false;
+    // the container's own header
+    BitReader in(bytes, nbytes);
+    int width, height, K, block_size;
+    if (!read_header(in, &width, &height, &K, &block_size)) return false;
+    if (x.nbytes != nbytes || x.width != width || x.height != height || x.K != K || x.block_size != block_size) return false;
+    for (int ch = 0; ch < 3; ++ch)
+        for (int i = 0; i < K; ++i) plan.quant[ch][i] = static_cast<uint16_t>(in.get(16));
+    const size_t tiles = tile_count(width, height, block_size);
+    if (tiles > (static_cast<size_t>(1) << 40) / 3) return false;
+    plan.tiles = tiles;
+    const uint64_t total_bits = 8 * static_cast<uint64_t>(nbytes);
+    const size_t n_streams = x.streams.size();
+    if (x.streams[0].wrapper_bit != in.position() || x.streams[0].n_coded != 3 * tiles || x.streams[0].packed) return false;
+    plan.wrappers.resize(n_streams);
+    // per stream: nothing here needs another stream's result (the index says where each wrapper begins)
+    auto check_stream = [&](size_t j) -> bool {
+        const IndexStream& is = x.streams[j];
+        // positions: inside the container, strictly ordered, one checkpoint per `interval` codes, stream behind stream
+        if (is.end_bit > total_bits || is.wrapper_bit >= is.end_bit) return false;
+        if (j + 1 < n_streams && x.streams[j + 1].wrapper_bit != is.end_bit) return false;
+        if (is.n_coded > is.end_bit - is.wrapper_bit) return false;            // every code takes at least one bit
+        if (is.checkpoints.size() != (is.n_coded + x.interval - 1) / x.interval) return false;
+        uint64_t before = is.wrapper_bit;
+        for (uint64_t c : is.checkpoints) {
+            if (c <= before || c >= is.end_bit) return false;
+            before = c;
+        }
+        // the serial parser's own size checks
+        if (j != 0) {
+            if (is.expect > tiles) return false;
+            if (is.packed ? is.n_coded - is.n_coded / 3 > is.expect : is.n_coded != is.expect) return false;
+        }
+        // the wrapper, from the container
+        StreamWrapper& w = plan.wrappers[j];
+        BitReader at(bytes, nbytes);
+        at.set_position(static_cast<size_t>(is.wrapper_bit));
+        if (!read_stream_wrapper(at, j != 0, w)) return false;
+        if (w.packed != (is.packed != 0) || (w.packed && w.packed_size != is.n_coded)) return false;
+        if (w.mode == 0 && w.cb.lut.empty()) return false;
+        if (w.first_code_bit > is.end_bit) return false;
+        if (!is.checkpoints.empty() && is.checkpoints[0] != w.first_code_bit) return false;
+        if (is.checkpoints.empty()) {                           // a stream without codes: what must follow its wrapper, checked here
+            uint16_t none;
+            if (w.mode == 0 ? !huffman_decode_chunk(w.cb, bytes, nbytes, w.first_code_bit, static_cast<size_t>(is.end_bit), 0, true, &none)
+                            : w.first_code_bit != is.end_bit)
+                return false;
+        }
+        return true;
+    };
+    if (!pooled) {
+        for (size_t j = 0; j < n_streams; ++j)
+            if (!check_stream(j)) return false;
+        return true;
+    }
+    std::vector<char> ok(n_streams, 0);
+    parallel_jobs(static_cast<int>(n_streams), [&](int j) { ok[static_cast<size_t>(j)] = check_stream(static_cast<size_t>(j)) ? 1 : 0; });
+    return std::find(ok.begin(), ok.end(), 0) == ok.end();
+}
+
+bool read_compressed_coded_by_index(const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes, CodedStreams& out,
+                                    int* route) {
+    *route = 1;
+    IndexedPlan plan;
+    auto by_index = [&]() -> bool {
+        if (!plan_indexed_parse(bytes, nbytes, index, index_bytes, plan)) return false;
+        const ContainerIndex& x = plan.index;
+        const int K = x.K;
+        auto decode_stream = [&](size_t j, std::vector<uint16_t>& dst) -> bool {
+            const IndexStream& is = x.streams[j];
+            const StreamWrapper& w = plan.wrappers[j];
+            dst.assign(static_cast<size_t>(is.n_coded), 0);
+            const size_t chunks = is.checkpoints.size();
+            for (size_t c = 0; c < chunks; ++c) {
+                const bool last = c + 1 == chunks;
+                const size_t begin = static_cast<size_t>(is.checkpoints[c]);
+                const size_t end = static_cast<size_t>(last ? is.end_bit : is.checkpoints[c + 1]);
+                const size_t first = c * x.interval, count = std::min<size_t>(x.interval, dst.size() - first);
+                if (w.mode == 0 ? !huffman_decode_chunk(w.cb, bytes, nbytes, begin, end, count, last, dst.data() + first)
+                                : !golomb_decode_chunk(w.m, bytes, nbytes, begin, end, count, dst.data() + first))
+                    return false;
+            }
+            return true;
+        };
+        out = CodedStreams();
+        out.width = x.width; out.height = x.height; out.K = K; out.block_size = x.block_size;
+        std::memcpy(out.quant, plan.quant, sizeof(out.quant));
+        if (!decode_stream(0, out.lengths)) return false;
+        for (uint16_t length : out.lengths)
+            if (length > K) return false;
+        out.expect = expected_sizes(out.lengths, K);
+        for (int i = 0; i < 6 * K; ++i)
+            if (out.expect[i] != x.streams[static_cast<size_t>(i) + 1].expect) return false;
+        out.codes.assign(static_cast<size_t>(6 * K), {});
+        out.packed.assign(static_cast<size_t>(6 * K), 0);
+        for (int i = 0; i < 6 * K; ++i) {
+            out.packed[i] = static_cast<uint8_t>(x.streams[static_cast<size_t>(i) + 1].packed);
+            if (!decode_stream(static_cast<size_t>(i) + 1, out.codes[i])) return false;
+        }
+        return true;
+    };
+    if (by_index()) {
+        *route = 0;
+        return true;
+    }
+    out = CodedStreams();
+    return read_compressed_coded(bytes, nbytes, out);
 }
 
 bool read_compressed(const uint8_t* bytes, size_t nbytes, Streams& s) {

@@ -7,6 +7,7 @@
 //   mp_streams.hip   stream assembly: the records -> the container's 6K symbol streams, live symbols only (StreamArgs)
 //   mp_entropy.hip   the per-symbol work of the entropy stage: run lengths, histograms, first appearances, code writing (EntropyArgs)
 //   mp_unpack.hip    the decoder's mirror of those two: run-length expansion and DC sums of coded streams (UnpackArgs)
+//   mp_parse.hip     the entropy codes of a container undone chunk by chunk from a seek index (ParseArgs)
 //   mp_kernels.hip   the decoder, the symbol histogram, and the product's own cross-check of the tile encoder: a STEP-SYNCHRONOUS
 //                    pursuit that correlates every row exactly (a short sequence of kernels per MP step over the active
 //                    tile-channels: init, fill, base sweep, detail sweep, finish, update), behind MPC_PATH=steps / MPC_FILTER=0
@@ -240,6 +241,52 @@ struct UnpackArgs {
     unsigned* dc_part;                  // [dc_blk_begin[3]] scratch: each block's sum of differences
 };
 int launch_unpack(const UnpackArgs& a, void* stream);                // hipError_t as int
+
+// ---- the entropy codes of a container parsed on the device, chunk by chunk from a seek index (mp_parse.hip) ----
+constexpr int kParseLutBits = 11;       // the Huffman window, HuffmanCodebook::kLutBits
+constexpr int kParseGroup = 64;         // chunks a wave decodes, one a lane: consecutive chunks of one stream
+constexpr unsigned kParseGolomb = 1u;   // ParseStream::flags
+constexpr unsigned kParseLengths = 2u;  // the lengths stream: its symbols go to `counts`, cut to K
+constexpr unsigned kParseLutEof = 1u << 24;
+
+struct ParseStream {                    // one per stream (the lengths stream first), built by the host from an index it has checked
+    unsigned long long out_off;         // its first symbol in `coded` (UnpackStream::coded_off); the lengths stream: 0, in `counts`
+    unsigned long long n_coded;         // symbols its codes yield
+    unsigned long long end_bit;         // the bit behind the stream (behind the pseudo-EOF for Huffman), <= 8 * the container's bytes
+    unsigned long long cp_off;          // its first checkpoint in `checkpoints`; it has n_chunks of them
+    unsigned long long expect;          // symbols it must expand to, as the index says: checked against the decoded lengths
+    unsigned n_chunks;                  // ceil(n_coded / interval)
+    unsigned group_begin;               // its first group of kParseGroup chunks.  Sentinel [n_streams]: n_groups
+    unsigned flags;
+    unsigned m;                         // Golomb parameter (>= 1)
+    unsigned lut_off;                   // Huffman: its window table in `luts`, 1 << kParseLutBits entries:
+                                        //   symbol | length << 16 | kParseLutEof for the pseudo-EOF; 0 = no code this short
+    unsigned len_off;                   // ... its per-length table in `lens`: [33][3] = codes of length l, first code, first entry
+    unsigned table_off;                 // ... its entry -> symbol table in `tables`, `total` entries
+    unsigned total;                     // ... entries; total - 1 is the pseudo-EOF
+    unsigned max_length;                // ... <= 32
+    unsigned reserved;
+};
+
+struct ParseArgs {
+    const uint32_t* words;              // the container's bytes, zero-padded to a whole word and 16 bytes beyond
+    const unsigned long long* checkpoints;
+    const ParseStream* streams;         // [n_streams + 1]
+    const uint32_t* luts;
+    const uint32_t* lens;
+    const uint16_t* tables;
+    int n_streams;                      // 6K + 1
+    int K;
+    unsigned interval;
+    unsigned n_groups;
+    unsigned long long n_counts;        // 3 * tiles
+    uint16_t* coded;                    // out: UnpackArgs::coded
+    uint16_t* counts;                   // out: the lengths, every one <= K (an even number of symbols allocated, as for `coded`)
+    unsigned* hist;                     // [3][kMaxDeviceK + 1] + 1 scratch: the lengths' histogram per channel; [last]: sizes differ
+    int* error;                         // |= 1: a chunk did not decode to exactly its symbols and its end, a length above K,
+                                        // or stream sizes other than the index says
+};
+int launch_parse(const ParseArgs& a, void* stream);                  // hipError_t as int
 
 // ---- device-side entropy stage (mp_entropy.hip): everything that touches every symbol of the 1 + 6K streams ----
 constexpr int kEntBlock = 4096;         // symbols per scan block

@@ -8,6 +8,7 @@
 //   host_pool.cpp          the worker pool of the host stages
 //   mpcodec_decode.cpp     tile reconstruction from records (mpc_decode_tiles_device), distortion, patch statistics
 //   mpcodec_decode_seq.cpp the decoder of containers (mpc_decode_image, mpc_decode_images*), the device unpack of coded streams
+//   mpcodec_index.cpp      the seek index's host-only entry points (mpc_container_index, mpc_parse_container_by_index)
 #pragma once
 
 #include "../../include/mpcodec.h"
@@ -280,7 +281,8 @@ struct DecodeSlot {
     GrowBuffer dev{GrowBuffer::kDevice};
     hipStream_t stream = nullptr;
     hipEvent_t done = nullptr;
-    hipEvent_t stamp[5] = {};                 // MPC_TRACE: before the upload, the unpack, the gather, the pixels' copy, after it
+    hipEvent_t stamp[6] = {};                 // MPC_TRACE: before the upload, the unpack, the gather, the pixels' copy, after it;
+                                              // [5]: behind the device parse (a frame with a seek index), in front of the unpack
     ~DecodeSlot() {
         if (stream) (void)hipStreamDestroy(stream);
         if (done) (void)hipEventDestroy(done);

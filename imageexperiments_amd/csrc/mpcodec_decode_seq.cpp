@@ -3,7 +3,9 @@
 // call are parsed side by side on threads of the call's own (a call of one frame: on the calling thread), each doing only what the
 // format chains from code to code (mpc::read_compressed_coded: the entropy codes).  The coded streams cross PCIe and the per-symbol
 // rest -- run-length expansion, DC sums -- happens on the device (mp_unpack.hip) in front of the gather and the reconstruction,
-// frames pipelined over slots of their own streams.
+// frames pipelined over slots of their own streams.  A frame that comes with a seek index (mpc_decode_images_indexed*) skips the
+// serial parse: its container's bytes go up as they are and the device undoes the entropy codes chunk by chunk (mp_parse.hip)
+// into the same buffers; whatever makes the index unusable sends the frame down the serial route from the start.
 #include <algorithm>
 #include <atomic>
 #include <climits>
@@ -68,7 +70,7 @@ bool plan_unpack(int K, Len coded_len, const uint8_t* is_packed, const unsigned 
 void carve_unpack(Carve& cv, const UnpackPlan& p, int K, mpc::UnpackArgs* a) {
     a->n_streams = 6 * K;
     a->n_blocks = p.n_blocks;
-    a->error = cv.take<int>(2);                                     // [1]: the reconstruction's error word
+    a->error = cv.take<int>(3);                                     // [1]: the reconstruction's error word, [2]: the device parse's
     a->symbols = cv.take<uint16_t>(p.n_symbols + 2);                // the kernels touch whole words: an even number of symbols
     a->blk_piece = cv.take<unsigned>(4 * static_cast<size_t>(p.n_blocks) + 4);
     a->blk_entry = cv.take<unsigned>(static_cast<size_t>(p.n_blocks) + 1);
@@ -90,6 +92,9 @@ struct Sequence {
     uint8_t** rgb = nullptr;                    // host form: the results
     uint8_t* const* d_rgb = nullptr;            // device form: the caller's buffers
     const size_t* capacity = nullptr;
+    const uint8_t* const* indexes = nullptr;    // optional, and optional per frame: the seek index of frame f
+    const size_t* index_bytes = nullptr;
+    int* routes = nullptr;                      // optional: per frame 0 = parsed on the device, 1 = the serial route
     int* width = nullptr;
     int* height = nullptr;
     std::atomic<int> next{0};                   // frames are handed out in order
@@ -181,7 +186,7 @@ mpc_status upload_and_unpack(DecodeSlot& slot, UnpackJob& j) {
     j.staged_ms = trace_ms();
     hipStream_t st = slot.stream;
     if (j.trace) HIP_TRY(hipEventRecord(slot.stamp[0], st));
-    HIP_TRY(hipMemsetAsync(j.ua.error, 0, 2 * sizeof(int), st));
+    HIP_TRY(hipMemsetAsync(j.ua.error, 0, 3 * sizeof(int), st));
     HIP_TRY(hipMemcpyAsync(dbase, j.h_result, upload_bytes, hipMemcpyHostToDevice, st));
     if (j.trace) HIP_TRY(hipEventRecord(slot.stamp[1], st));
     if (const int e = mpc::launch_unpack(j.ua, st); e != 0) return launch_failed(e);
@@ -189,12 +194,197 @@ mpc_status upload_and_unpack(DecodeSlot& slot, UnpackJob& j) {
     return MPC_OK;
 }
 
-// upload | unpack | gather | reconstruct | (host form) pixels down, on the slot's stream; returns with the frame complete
-mpc_status frame_on_slot(Sequence& q, int f, DecodeSlot& slot, const mpc::CodedStreams& s, const UnpackPlan& plan, double stamps[3]) {
+// ---- the indexed route: the container's bytes up, the entropy codes undone on the device ----
+// What the parse kernels need, from an index the host has checked against its container (mpc::plan_indexed_parse)
+struct ParsePlan {
+    mpc::IndexedPlan ip;
+    std::vector<mpc::ParseStream> streams;      // [6K + 2]
+    std::vector<uint32_t> luts, lens;
+    std::vector<uint16_t> tables;
+    size_t n_checkpoints = 0, n_counts = 0;
+    unsigned n_groups = 0;
+    UnpackPlan unpack;
+};
+
+// false = the index is not used (the serial route decides what becomes of the frame)
+bool plan_parse(const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes, bool pooled, ParsePlan& p) {
+    if (!mpc::plan_indexed_parse(bytes, nbytes, index, index_bytes, p.ip, pooled)) return false;
+    const mpc::ContainerIndex& x = p.ip.index;
+    const int K = x.K, n = 6 * K;
+    if (K < 1 || K > MPC_MAX_K) return false;
+    std::vector<uint8_t> is_packed(static_cast<size_t>(n));
+    std::vector<unsigned long long> expect(static_cast<size_t>(n));
+    for (int i = 0; i < n; ++i) {
+        is_packed[i] = static_cast<uint8_t>(x.streams[static_cast<size_t>(i) + 1].packed);
+        expect[i] = x.streams[static_cast<size_t>(i) + 1].expect;
+    }
+    if (!plan_unpack(K, [&](int i) { return static_cast<unsigned long long>(x.streams[static_cast<size_t>(i) + 1].n_coded); }, is_packed.data(),
+                     expect.data(), nullptr, p.unpack))
+        return false;
+    p.n_counts = 3 * p.ip.tiles;
+    p.streams.assign(x.streams.size() + 1, mpc::ParseStream{});
+    unsigned long long groups = 0, checkpoints = 0;
+    constexpr size_t kLut = size_t(1) << mpc::kParseLutBits;
+    for (size_t j = 0; j < x.streams.size(); ++j) {
+        const mpc::IndexStream& is = x.streams[j];
+        const mpc::StreamWrapper& w = p.ip.wrappers[j];
+        mpc::ParseStream& ps = p.streams[j];
+        if (is.checkpoints.size() > 0xFFFFFFFFull) return false;
+        ps.out_off = j == 0 ? 0 : p.unpack.table[j - 1].coded_off;
+        ps.n_coded = is.n_coded;
+        ps.end_bit = is.end_bit;
+        ps.cp_off = checkpoints;
+        ps.expect = is.expect;
+        ps.n_chunks = static_cast<unsigned>(is.checkpoints.size());
+        ps.group_begin = static_cast<unsigned>(groups);
+        ps.flags = (w.mode == 1 ? mpc::kParseGolomb : 0u) | (j == 0 ? mpc::kParseLengths : 0u);
+        ps.m = w.m;
+        checkpoints += is.checkpoints.size();
+        groups += (is.checkpoints.size() + mpc::kParseGroup - 1) / mpc::kParseGroup;
+        if (groups > 0x7FFFFFFFull) return false;
+        if (w.mode != 0 || ps.n_chunks == 0) continue;
+        const mpc::HuffmanCodebook& cb = w.cb;
+        const uint32_t eof = static_cast<uint32_t>(cb.total) - 1u;
+        ps.total = cb.total;
+        ps.max_length = static_cast<unsigned>(cb.max_length);
+        ps.lut_off = static_cast<unsigned>(p.luts.size());
+        p.luts.resize(p.luts.size() + kLut);
+        uint32_t* lut = p.luts.data() + ps.lut_off;
+        for (size_t k = 0; k < kLut; ++k) {                         // (entry << 5) | length -> symbol | length << 16 | pseudo-EOF
+            const uint32_t hit = cb.lut[k];
+            if (hit) lut[k] = cb.table[hit >> 5] | ((hit & 31u) << 16) | ((hit >> 5) == eof ? mpc::kParseLutEof : 0u);
+        }
+        if (cb.max_length <= mpc::kParseLutBits) continue;          // the window resolves every code: no per-length test, no entry table
+        ps.len_off = static_cast<unsigned>(p.lens.size());
+        p.lens.resize(p.lens.size() + 3 * 33, 0);
+        for (int l = 1; l <= cb.max_length; ++l) {
+            uint32_t* row = p.lens.data() + ps.len_off + 3 * l;
+            row[0] = cb.counts[l - 1];
+            row[1] = cb.first_code[l];
+            row[2] = cb.first_index[l];
+        }
+        ps.table_off = static_cast<unsigned>(p.tables.size());
+        p.tables.insert(p.tables.end(), cb.table.begin(), cb.table.end());
+    }
+    p.streams.back().group_begin = static_cast<unsigned>(groups);
+    p.n_groups = static_cast<unsigned>(groups);
+    p.n_checkpoints = static_cast<size_t>(checkpoints);
+    return true;
+}
+
+// upload_and_unpack's counterpart: the container, the checkpoints and the code tables through the slot's pinned buffer to the
+// device, the parse kernels behind them; they leave the coded streams and the lengths where upload_and_unpack puts them
+// (j.ua.coded, j.d_extra[0]).  j.extra[0] is not used; the unpack kernels are the caller's to launch.  stamp[5]: behind the parse
+mpc_status upload_and_parse(DecodeSlot& slot, UnpackJob& j, const ParsePlan& pp, const uint8_t* bytes, size_t nbytes) {
+    const UnpackPlan& plan = *j.plan;
+    constexpr size_t kHead = 256;
+    const size_t padded = ((nbytes + 3) & ~static_cast<size_t>(3)) + 16;      // a lane's window reads up to 12 bytes behind the last bit
+    uint8_t* words;
+    unsigned long long* checkpoints;
+    mpc::ParseStream* streams;
+    uint32_t *luts, *lens;
+    uint16_t* tables;
+    mpc::UnpackStream* table;
+    char* extra;
+    auto upload_layout = [&](char* base) {                          // the same in pinned memory and on the device
+        Carve cv{base};
+        words = cv.take<uint8_t>(padded);
+        checkpoints = cv.take<unsigned long long>(pp.n_checkpoints + 1);
+        streams = cv.take<mpc::ParseStream>(pp.streams.size());
+        luts = cv.take<uint32_t>(pp.luts.size() + 4);
+        lens = cv.take<uint32_t>(pp.lens.size() + 1);
+        tables = cv.take<uint16_t>(pp.tables.size() + 1);
+        table = cv.take<mpc::UnpackStream>(plan.table.size());
+        extra = cv.take<char>(j.extra_bytes[1]);
+        return cv.at;
+    };
+    const size_t upload_bytes = upload_layout(nullptr);
+    mpc::ParseArgs pa{};
+    uint16_t* coded;
+    auto device_layout = [&](char* base) {                          // behind the upload: the parse kernels' output, then the unpack kernels'
+        Carve cv{base, upload_bytes};
+        coded = cv.take<uint16_t>(plan.n_coded + 2);
+        pa.counts = cv.take<uint16_t>(pp.n_counts + 2);
+        pa.hist = cv.take<unsigned>(3 * (mpc::kMaxDeviceK + 1) + 1);
+        carve_unpack(cv, plan, j.K, &j.ua);
+        return cv.at;
+    };
+    const size_t behind_at = device_layout(nullptr);
+    if (const mpc_status gs = slot.pinned.reserve(kHead + std::max(upload_bytes, Carve::up(j.result_bytes)), "pinned decode staging"); gs != MPC_OK)
+        return gs;
+    if (const mpc_status gs = slot.dev.reserve(behind_at + j.behind_bytes, "device decode staging"); gs != MPC_OK) return gs;
+    j.h_flags = reinterpret_cast<int*>(slot.pinned.data());
+    j.h_result = slot.pinned.data() + kHead;
+    upload_layout(j.h_result);
+    const size_t piece = size_t(1) << 20, pieces = (nbytes + piece - 1) / piece;
+    const auto stage = [&](int job) {
+        const size_t lo = piece * static_cast<size_t>(job), hi = std::min(nbytes, lo + piece);
+        std::memcpy(words + lo, bytes + lo, hi - lo);
+    };
+    if (j.pooled && pieces > 1) mpc::parallel_jobs(static_cast<int>(pieces), stage);
+    else
+        for (size_t job = 0; job < pieces; ++job) stage(static_cast<int>(job));
+    std::memset(words + nbytes, 0, padded - nbytes);
+    size_t at = 0;
+    for (const mpc::IndexStream& is : pp.ip.index.streams) {
+        if (!is.checkpoints.empty()) std::memcpy(checkpoints + at, is.checkpoints.data(), sizeof(unsigned long long) * is.checkpoints.size());
+        at += is.checkpoints.size();
+    }
+    std::memcpy(streams, pp.streams.data(), sizeof(mpc::ParseStream) * pp.streams.size());
+    if (!pp.luts.empty()) std::memcpy(luts, pp.luts.data(), sizeof(uint32_t) * pp.luts.size());
+    if (!pp.lens.empty()) std::memcpy(lens, pp.lens.data(), sizeof(uint32_t) * pp.lens.size());
+    if (!pp.tables.empty()) std::memcpy(tables, pp.tables.data(), sizeof(uint16_t) * pp.tables.size());
+    std::memcpy(table, plan.table.data(), sizeof(mpc::UnpackStream) * plan.table.size());
+    if (j.extra_bytes[1]) std::memcpy(extra, j.extra[1], j.extra_bytes[1]);
+    j.h_flags[0] = j.h_flags[1] = j.h_flags[2] = -1;
+    char* dbase = slot.dev.data();
+    upload_layout(dbase);
+    device_layout(dbase);
+    pa.words = reinterpret_cast<const uint32_t*>(words);
+    pa.checkpoints = checkpoints;
+    pa.streams = streams;
+    pa.luts = luts;
+    pa.lens = lens;
+    pa.tables = tables;
+    pa.n_streams = static_cast<int>(pp.streams.size()) - 1;
+    pa.K = j.K;
+    pa.interval = pp.ip.index.interval;
+    pa.n_groups = pp.n_groups;
+    pa.n_counts = pp.n_counts;
+    pa.coded = coded;
+    pa.error = j.ua.error + 2;
+    j.ua.coded = coded;
+    j.ua.streams = table;
+    j.d_extra[0] = pa.counts;
+    j.d_extra[1] = extra;
+    j.d_behind = dbase + behind_at;
+    j.staged_ms = trace_ms();
+    hipStream_t st = slot.stream;
+    if (j.trace) HIP_TRY(hipEventRecord(slot.stamp[0], st));
+    HIP_TRY(hipMemsetAsync(j.ua.error, 0, 3 * sizeof(int), st));
+    HIP_TRY(hipMemcpyAsync(dbase, j.h_result, upload_bytes, hipMemcpyHostToDevice, st));
+    if (j.trace) HIP_TRY(hipEventRecord(slot.stamp[1], st));
+    if (const int e = mpc::launch_parse(pa, st); e != 0) return launch_failed(e);
+    if (j.trace) HIP_TRY(hipEventRecord(slot.stamp[5], st));
+    return MPC_OK;
+}
+
+// what frame_on_slot needs of a frame's header, whichever route parsed it
+struct FrameHead {
+    int width = 0, height = 0, K = 0;
+    size_t n_tc = 0;                            // 3 * tiles
+    const uint16_t (*quant)[32] = nullptr;
+};
+
+// upload | (parse) | unpack | gather | reconstruct | (host form) pixels down, on the slot's stream; returns with the frame complete.
+// s: the serially parsed streams, or pp: the checked index (then *refused = true with MPC_OK says that the device's half of the
+// acceptance rule failed: nothing of the frame counts, the serial route starts over)
+mpc_status frame_on_slot(Sequence& q, int f, DecodeSlot& slot, const FrameHead& s, const UnpackPlan& plan, const mpc::CodedStreams* serial,
+                         const ParsePlan* pp, double stamps[3], bool* refused) {
     mpc_context* c = q.c;
     const bool trace = q.tuning.trace;
     const int K = s.K;
-    const size_t n_tc = s.lengths.size(), tiles = n_tc / 3;
+    const size_t n_tc = s.n_tc, tiles = n_tc / 3;
     const size_t px = static_cast<size_t>(s.width) * s.height * 3;
     // read_compressed_coded refuses any other K; `quant` and UnpackJob::streams are sized by MPC_MAX_K and must not lean on that
     if (K < 1 || K > MPC_MAX_K) return fail(MPC_ERR_BITSTREAM, "Invalid input data");
@@ -214,9 +404,11 @@ mpc_status frame_on_slot(Sequence& q, int f, DecodeSlot& slot, const mpc::CodedS
     UnpackJob j;
     j.plan = &plan;
     j.K = K;
-    for (int i = 0; i < 6 * K; ++i) j.streams[i] = s.codes[i].data();
-    j.extra[0] = s.lengths.data();
-    j.extra_bytes[0] = sizeof(uint16_t) * n_tc;
+    if (serial) {
+        for (int i = 0; i < 6 * K; ++i) j.streams[i] = serial->codes[i].data();
+        j.extra[0] = serial->lengths.data();
+        j.extra_bytes[0] = sizeof(uint16_t) * n_tc;
+    }
     j.extra[1] = quant;
     j.extra_bytes[1] = sizeof(double) * 3 * static_cast<size_t>(K);
     j.behind_bytes = behind_layout(nullptr);
@@ -226,12 +418,18 @@ mpc_status frame_on_slot(Sequence& q, int f, DecodeSlot& slot, const mpc::CodedS
     const bool pooled = q.n == 1;
     j.pooled = pooled;
     j.trace = trace;
-    if (const mpc_status us = upload_and_unpack(slot, j); us != MPC_OK) return us;
+    hipStream_t st = slot.stream;
+    if (serial) {
+        if (const mpc_status us = upload_and_unpack(slot, j); us != MPC_OK) return us;
+    } else {
+        if (const mpc_status us = upload_and_parse(slot, j, *pp, q.bytes[f], q.nbytes[f]); us != MPC_OK) return us;
+        if (const int e = mpc::launch_unpack(j.ua, st); e != 0) return launch_failed(e);
+        if (trace) HIP_TRY(hipEventRecord(slot.stamp[2], st));
+    }
     stamps[0] = j.staged_ms;
     const uint16_t* counts = static_cast<const uint16_t*>(j.d_extra[0]);
     behind_layout(j.d_behind);
     if (q.d_rgb) d_pixels = q.d_rgb[f];
-    hipStream_t st = slot.stream;
     sa.counts = counts;
     sa.symbols = j.ua.symbols;
     if (const int e = mpc::launch_stream_gather(sa, d_choices, st); e != 0) return launch_failed(e);
@@ -240,12 +438,16 @@ mpc_status frame_on_slot(Sequence& q, int f, DecodeSlot& slot, const mpc::CodedS
         ds != MPC_OK)
         return ds;
     if (trace) HIP_TRY(hipEventRecord(slot.stamp[3], st));
-    HIP_TRY(hipMemcpyAsync(j.h_flags, j.ua.error, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(j.h_flags, j.ua.error, 3 * sizeof(int), hipMemcpyDeviceToHost, st));
     if (!q.d_rgb) HIP_TRY(hipMemcpyAsync(j.h_result, d_pixels, px, hipMemcpyDeviceToHost, st));    // the upload has left the buffer: stream order
     if (trace) HIP_TRY(hipEventRecord(slot.stamp[4], st));
     HIP_TRY(hipEventRecord(slot.done, st));
     HIP_TRY(hipEventSynchronize(slot.done));                        // this frame's work only: no other context's, no other slot's
     stamps[1] = trace_ms();
+    if (pp && j.h_flags[2] != 0) {                                  // a chunk, a length or a stream size is not what the index says
+        *refused = true;                                            // (the caller passes `refused` whenever it passes `pp`)
+        return MPC_OK;
+    }
     // a stream that does not expand to its size is what mpc::read_compressed refuses, a record outside its dictionary the reconstruction
     if (j.h_flags[0] != 0) return fail(MPC_ERR_BITSTREAM, "Invalid input data");
     if (j.h_flags[1] != 0) return fail(MPC_ERR_BITSTREAM, "Invalid bitstream");
@@ -268,11 +470,23 @@ mpc_status frame_on_slot(Sequence& q, int f, DecodeSlot& slot, const mpc::CodedS
     return MPC_OK;
 }
 
-void trace_frame(int f, int slot_index, DecodeSlot& slot, const double host[6]) {
+void trace_frame(int f, int slot_index, DecodeSlot& slot, const double host[6], bool indexed) {
     float dev[4] = {};
     for (int k = 0; k < 4; ++k) (void)hipEventElapsedTime(&dev[k], slot.stamp[k], slot.stamp[k + 1]);
+    if (indexed) {
+        float parse = 0.f, unpack = 0.f;
+        (void)hipEventElapsedTime(&parse, slot.stamp[1], slot.stamp[5]);
+        (void)hipEventElapsedTime(&unpack, slot.stamp[5], slot.stamp[2]);
+        std::fprintf(stderr,
+                     "[trace] decode frame %d slot %d, route device: parse: tables %.2f ms, kernels %.2f | wait for the slot %.2f | staged %.2f | "
+                     "on the device %.2f (upload %.2f, parse %.2f, unpack %.2f, gather + reconstruct %.2f, copy-out %.2f) | pixels to the "
+                     "caller %.2f\n",
+                     f, slot_index, host[1] - host[0], parse, host[2] - host[1], host[3] - host[2], host[4] - host[3], dev[0], parse, unpack,
+                     dev[2], dev[3], host[5] - host[4]);
+        return;
+    }
     std::fprintf(stderr,
-                 "[trace] decode frame %d slot %d: parse %.2f ms | wait for the slot %.2f | staged %.2f | on the device %.2f (upload %.2f, "
+                 "[trace] decode frame %d slot %d, route serial: parse %.2f ms | wait for the slot %.2f | staged %.2f | on the device %.2f (upload %.2f, "
                  "unpack %.2f, gather + reconstruct %.2f, copy-out %.2f) | pixels to the caller %.2f\n",
                  f, slot_index, host[1] - host[0], host[2] - host[1], host[3] - host[2], host[4] - host[3], dev[0], dev[1], dev[2], dev[3],
                  host[5] - host[4]);
@@ -287,7 +501,10 @@ void parse_worker(Sequence& q) {
         host[0] = trace_ms();
         mpc::CodedStreams s;
         UnpackPlan plan;
-        mpc_status st = guarded([&]() -> mpc_status {
+        ParsePlan pp;
+        FrameHead head;
+        // the serial route's parse: what the format chains from code to code, on this thread
+        const auto parse_serial = [&]() -> mpc_status {
             if (q.failed_before(f)) return MPC_OK;
             HIP_TRY(hipSetDevice(c->device));
             if (!mpc::read_compressed_coded(q.bytes[f], q.nbytes[f], s)) return fail(MPC_ERR_BITSTREAM, "Invalid input data");
@@ -308,7 +525,32 @@ void parse_worker(Sequence& q) {
             if (!plan_unpack(s.K, [&](int i) { return static_cast<unsigned long long>(s.codes[i].size()); }, s.packed.data(), nullptr,
                              s.expect.data(), plan))
                 return fail(MPC_ERR_BITSTREAM, "Invalid bitstream");
+            head.width = s.width;
+            head.height = s.height;
+            head.K = s.K;
+            head.n_tc = s.lengths.size();
+            head.quant = s.quant;
             return MPC_OK;
+        };
+        // The indexed route's share of the host: the index checked against the container, the code tables built.  It refuses nothing
+        // itself: whatever it cannot take, the serial route decides.
+        bool indexed = false;
+        mpc_status st = guarded([&]() -> mpc_status {
+            if (q.indexes && q.indexes[f] && !q.failed_before(f)) {
+                HIP_TRY(hipSetDevice(c->device));
+                const mpc::ContainerIndex& x = pp.ip.index;
+                indexed = plan_parse(q.bytes[f], q.nbytes[f], q.indexes[f], q.index_bytes[f], q.n == 1, pp) && x.block_size == c->block_size &&
+                          !(q.d_rgb && static_cast<size_t>(x.width) * x.height * 3 > q.capacity[f]);
+                if (indexed) {
+                    head.width = x.width;
+                    head.height = x.height;
+                    head.K = x.K;
+                    head.n_tc = pp.n_counts;
+                    head.quant = pp.ip.quant;
+                    return MPC_OK;
+                }
+            }
+            return parse_serial();
         });
         host[1] = trace_ms();
         // The slot is taken in frame order whatever became of the parse: the frames behind count this slot's uses.
@@ -320,11 +562,24 @@ void parse_worker(Sequence& q) {
         host[2] = trace_ms();
         bool ran = false;
         if (st == MPC_OK && !q.failed_before(f)) {
-            st = guarded([&]() -> mpc_status { return frame_on_slot(q, f, *c->dec[slot_index], s, plan, host + 3); });
-            ran = st == MPC_OK;
-            if (!ran) (void)hipStreamSynchronize(c->dec[slot_index]->stream);      // nothing of this frame is left on the slot's stream
+            DecodeSlot& slot = *c->dec[slot_index];
+            bool refused = false, decoded = true;
+            st = guarded([&]() -> mpc_status {
+                return frame_on_slot(q, f, slot, head, indexed ? pp.unpack : plan, indexed ? nullptr : &s, indexed ? &pp : nullptr, host + 3, &refused);
+            });
+            if (st == MPC_OK && refused) {                          // the serial route from the start, on the slot this frame holds
+                indexed = false;
+                host[0] = trace_ms();
+                st = guarded(parse_serial);
+                host[1] = host[2] = trace_ms();
+                decoded = st == MPC_OK && !q.failed_before(f);      // parse_serial parses nothing once a frame in front has failed
+                if (decoded) st = guarded([&]() -> mpc_status { return frame_on_slot(q, f, slot, head, plan, &s, nullptr, host + 3, nullptr); });
+            }
+            ran = st == MPC_OK && decoded;
+            if (st != MPC_OK) (void)hipStreamSynchronize(slot.stream);             // nothing of this frame is left on the slot's stream
         }
-        if (ran && q.tuning.trace) trace_frame(f, slot_index, *c->dec[slot_index], host);
+        if (ran && q.routes) q.routes[f] = indexed ? 0 : 1;
+        if (ran && q.tuning.trace) trace_frame(f, slot_index, *c->dec[slot_index], host, indexed);
         {
             std::lock_guard<std::mutex> hold(q.lock);
             ++q.slot_uses[slot_index];
@@ -348,7 +603,9 @@ mpc_status ensure_slots(mpc_context* c, int slots) {
 
 // single: the call is mpc_decode_image's; its error text names no frame
 mpc_status decode_sequence(mpc_context* c, const uint8_t* const* bytes, const size_t* nbytes, int n_frames, uint8_t** rgb,
-                           uint8_t* const* d_rgb, const size_t* capacity, int* width, int* height, bool single = false) {
+                           uint8_t* const* d_rgb, const size_t* capacity, int* width, int* height, bool single = false,
+                           const uint8_t* const* indexes = nullptr, const size_t* index_bytes = nullptr, int* routes = nullptr) {
+    if (indexes && !index_bytes) return fail(MPC_ERR_ARGUMENT, "null argument");
     if (!c || !bytes || !nbytes || !width || !height || (!rgb && !d_rgb) || (d_rgb && !capacity)) return fail(MPC_ERR_ARGUMENT, "null argument");
     if (n_frames < 1) return fail(MPC_ERR_ARGUMENT, "n_frames must be at least 1");
     if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback");
@@ -373,6 +630,10 @@ mpc_status decode_sequence(mpc_context* c, const uint8_t* const* bytes, const si
     q.rgb = rgb;
     q.d_rgb = d_rgb;
     q.capacity = capacity;
+    q.indexes = indexes;
+    q.index_bytes = index_bytes;
+    q.routes = routes;
+    if (routes) std::fill(routes, routes + n_frames, 1);
     q.width = width;
     q.height = height;
     if (const mpc_status ss = ensure_slots(c, q.slots); ss != MPC_OK) return ss;
@@ -425,6 +686,79 @@ mpc_status mpc_decode_images_device(mpc_context* c, const uint8_t* const* bytes,
 mpc_status mpc_decode_image_device(mpc_context* c, const uint8_t* bytes, size_t nbytes, uint8_t* d_rgb, size_t capacity, int* width,
                                    int* height) {
     return mpc_decode_images_device(c, &bytes, &nbytes, 1, &d_rgb, &capacity, width, height);
+}
+
+mpc_status mpc_decode_images_indexed(mpc_context* c, const uint8_t* const* bytes, const size_t* nbytes, const uint8_t* const* indexes,
+                                     const size_t* index_bytes, int n_frames, uint8_t** rgb, int* width, int* height, int* routes) {
+    return guarded([&]() -> mpc_status {
+        if (!rgb) return fail(MPC_ERR_ARGUMENT, "null argument");
+        return decode_sequence(c, bytes, nbytes, n_frames, rgb, nullptr, nullptr, width, height, false, indexes, index_bytes, routes);
+    });
+}
+
+mpc_status mpc_decode_images_indexed_device(mpc_context* c, const uint8_t* const* bytes, const size_t* nbytes, const uint8_t* const* indexes,
+                                            const size_t* index_bytes, int n_frames, uint8_t* const* d_rgb, const size_t* capacity,
+                                            int* width, int* height, int* routes) {
+    return guarded([&]() -> mpc_status {
+        if (!d_rgb) return fail(MPC_ERR_ARGUMENT, "null argument");
+        return decode_sequence(c, bytes, nbytes, n_frames, nullptr, d_rgb, capacity, width, height, false, indexes, index_bytes, routes);
+    });
+}
+
+mpc_status mpc_parse_container_device(mpc_context* c, const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes,
+                                      uint16_t** symbols, size_t* n_symbols, int* route) {
+    return guarded([&]() -> mpc_status {
+        if (!c || !bytes || !index || !symbols || !n_symbols || !route) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback");
+        // the serial parse's result in this call's form: what every refusal of the index comes down to
+        const auto serial = [&]() -> mpc_status {
+            *route = 1;
+            mpc::CodedStreams s;
+            if (!mpc::read_compressed_coded(bytes, nbytes, s)) return fail(MPC_ERR_BITSTREAM, "Invalid input data");
+            size_t total = s.lengths.size();
+            for (const std::vector<uint16_t>& v : s.codes) total += v.size();
+            uint16_t* out = static_cast<uint16_t*>(std::malloc(total ? 2 * total : 2));
+            if (!out) return fail(MPC_ERR_ALLOC, "out of memory");
+            size_t at = 0;
+            if (!s.lengths.empty()) std::memcpy(out, s.lengths.data(), 2 * s.lengths.size());
+            at += s.lengths.size();
+            for (const std::vector<uint16_t>& v : s.codes) {
+                if (!v.empty()) std::memcpy(out + at, v.data(), 2 * v.size());
+                at += v.size();
+            }
+            *symbols = out;
+            *n_symbols = total;
+            return MPC_OK;
+        };
+        ParsePlan pp;
+        if (!plan_parse(bytes, nbytes, index, index_bytes, false, pp)) return serial();
+        std::lock_guard<std::recursive_mutex> one_host_call(c->host_calls);
+        HIP_TRY(hipSetDevice(c->device));
+        if (const mpc_status ss = ensure_slots(c, 1); ss != MPC_OK) return ss;
+        DecodeSlot& slot = *c->dec[0];
+        const size_t n_counts = pp.n_counts, n_coded = pp.unpack.n_coded;
+        UnpackJob j;
+        j.plan = &pp.unpack;
+        j.K = pp.ip.index.K;
+        j.result_bytes = sizeof(uint16_t) * (n_counts + n_coded + 2);
+        if (const mpc_status us = upload_and_parse(slot, j, pp, bytes, nbytes); us != MPC_OK) return us;
+        hipStream_t st = slot.stream;
+        uint16_t* h_counts = reinterpret_cast<uint16_t*>(j.h_result);
+        HIP_TRY(hipMemcpyAsync(j.h_flags, j.ua.error, 3 * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(h_counts, j.d_extra[0], sizeof(uint16_t) * n_counts, hipMemcpyDeviceToHost, st));
+        if (n_coded) HIP_TRY(hipMemcpyAsync(h_counts + n_counts, j.ua.coded, sizeof(uint16_t) * n_coded, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipEventRecord(slot.done, st));
+        HIP_TRY(hipEventSynchronize(slot.done));
+        if (j.h_flags[2] != 0) return serial();
+        const size_t total = n_counts + n_coded;
+        uint16_t* out = static_cast<uint16_t*>(std::malloc(2 * total));
+        if (!out) return fail(MPC_ERR_ALLOC, "out of memory");
+        std::memcpy(out, h_counts, 2 * total);
+        *symbols = out;
+        *n_symbols = total;
+        *route = 0;
+        return MPC_OK;
+    });
 }
 
 mpc_status mpc_unpack_symbol_streams_device(mpc_context* c, int K, const uint16_t* coded, const unsigned long long* coded_off,

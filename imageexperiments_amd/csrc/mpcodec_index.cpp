@@ -1,0 +1,89 @@
+// mpcodec_index.cpp -- product: the C ABI's host-only entry points of the seek index (host_container.cpp): build one, read one
+// back, and the chunked parse on the host that defines what the device parse (mp_parse.hip) computes.
+#include <cstring>
+
+#include "mpc_internal.h"
+
+extern "C" {
+
+mpc_status mpc_container_index(const uint8_t* bytes, size_t nbytes, int interval, uint8_t** index, size_t* index_bytes) {
+    return guarded([&]() -> mpc_status {
+        if (!bytes || !index || !index_bytes) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (interval != 0 && (interval < static_cast<int>(mpc::kIndexIntervalMin) || interval > static_cast<int>(mpc::kIndexIntervalMax)))
+            return fail(MPC_ERR_ARGUMENT, "interval %d: 0 or %u to %u", interval, mpc::kIndexIntervalMin, mpc::kIndexIntervalMax);
+        std::vector<uint8_t> blob;
+        if (!mpc::build_container_index(bytes, nbytes, static_cast<uint32_t>(interval), blob)) return fail(MPC_ERR_BITSTREAM, "Invalid input data");
+        uint8_t* p = static_cast<uint8_t*>(std::malloc(blob.size()));
+        if (!p) return fail(MPC_ERR_ALLOC, "out of memory");
+        std::memcpy(p, blob.data(), blob.size());
+        *index = p;
+        *index_bytes = blob.size();
+        return MPC_OK;
+    });
+}
+
+mpc_status mpc_index_info(const uint8_t* index, size_t index_bytes, mpc_index_header* info) {
+    return guarded([&]() -> mpc_status {
+        if (!index || !info) return fail(MPC_ERR_ARGUMENT, "null argument");
+        mpc::ContainerIndex x;
+        if (!mpc::read_container_index(index, index_bytes, x)) return fail(MPC_ERR_BITSTREAM, "not a seek index");
+        info->interval = static_cast<int>(x.interval);
+        info->n_streams = static_cast<int>(x.streams.size());
+        info->serial_only = x.serial_only ? 1 : 0;
+        info->width = x.width;
+        info->height = x.height;
+        info->K = x.K;
+        info->block_size = x.block_size;
+        info->container_bytes = x.nbytes;
+        return MPC_OK;
+    });
+}
+
+mpc_status mpc_index_stream(const uint8_t* index, size_t index_bytes, int stream, mpc_index_stream_info* info, uint64_t* checkpoints,
+                            size_t capacity) {
+    return guarded([&]() -> mpc_status {
+        if (!index || !info) return fail(MPC_ERR_ARGUMENT, "null argument");
+        mpc::ContainerIndex x;
+        if (!mpc::read_container_index(index, index_bytes, x)) return fail(MPC_ERR_BITSTREAM, "not a seek index");
+        if (stream < 0 || stream >= static_cast<int>(x.streams.size())) return fail(MPC_ERR_ARGUMENT, "stream index %d out of range", stream);
+        const mpc::IndexStream& s = x.streams[static_cast<size_t>(stream)];
+        info->mode = static_cast<int>(s.mode);
+        info->packed = static_cast<int>(s.packed);
+        info->m = s.m;
+        info->n_coded = s.n_coded;
+        info->expect = s.expect;
+        info->wrapper_bit = s.wrapper_bit;
+        info->end_bit = s.end_bit;
+        info->n_checkpoints = s.checkpoints.size();
+        if (checkpoints) {
+            if (capacity < s.checkpoints.size()) return fail(MPC_ERR_ARGUMENT, "capacity %zu for %zu checkpoints", capacity, s.checkpoints.size());
+            if (!s.checkpoints.empty()) std::memcpy(checkpoints, s.checkpoints.data(), 8 * s.checkpoints.size());
+        }
+        return MPC_OK;
+    });
+}
+
+mpc_status mpc_parse_container_by_index(const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes, uint16_t** symbols,
+                                        size_t* n_symbols, int* route) {
+    return guarded([&]() -> mpc_status {
+        if (!bytes || !index || !symbols || !n_symbols || !route) return fail(MPC_ERR_ARGUMENT, "null argument");
+        mpc::CodedStreams s;
+        if (!mpc::read_compressed_coded_by_index(bytes, nbytes, index, index_bytes, s, route)) return fail(MPC_ERR_BITSTREAM, "Invalid input data");
+        size_t total = s.lengths.size();
+        for (const std::vector<uint16_t>& v : s.codes) total += v.size();
+        uint16_t* out = static_cast<uint16_t*>(std::malloc(total ? 2 * total : 2));
+        if (!out) return fail(MPC_ERR_ALLOC, "out of memory");
+        size_t at = 0;
+        auto add = [&](const std::vector<uint16_t>& v) {
+            if (!v.empty()) std::memcpy(out + at, v.data(), 2 * v.size());
+            at += v.size();
+        };
+        add(s.lengths);
+        for (const std::vector<uint16_t>& v : s.codes) add(v);
+        *symbols = out;
+        *n_symbols = total;
+        return MPC_OK;
+    });
+}
+
+}  // extern "C"

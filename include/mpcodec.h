@@ -369,6 +369,64 @@ mpc_status mpc_unpack_symbol_streams_device(mpc_context* ctx, int K, const uint1
                                             const uint8_t* is_packed, const unsigned long long* expect, uint16_t** symbols,
                                             size_t* n_symbols);
 
+/* ---- seek index: the entropy codes parsed on the device ("Seek index") ----
+ * The container format is serial for one reason: a stream's first bit is known once the stream before it has been decoded, and
+ * a code's first bit once the code before it has.  An index holds where every one of the 1 + 6K streams begins and where every
+ * interval-th coded symbol of it begins; with it every chunk of `interval` symbols decodes on its own.  The container's bytes
+ * stay the reference's; the index is a separate blob a caller keeps beside a container it will decode more than once.
+ * An index is a hint, never an authority: a decode with one gives the pixels, status and error text of a decode without one,
+ * whatever the index holds (a damaged one, another container's).  Its structure is checked against the container on the host,
+ * every chunk must yield exactly its symbols and end exactly where the next begins (on the pseudo-EOF and the stream's end for
+ * the last), and the expected stream sizes are recomputed from the decoded lengths; by induction the serial parser passes
+ * through every position the index names.  Whatever fails sends the frame down the serial route from the start.
+ *
+ * mpc_container_index: host only, no context, safe on several threads: one serial parse that records the positions.  interval:
+ * coded symbols per checkpoint, 32 ... 65536, 0 = the library's default.  index: flat, little-endian, versioned
+ * (layout in DESIGN.md), release with mpc_free.  MPC_ERR_BITSTREAM for whatever mpc_read_compressed_coded refuses.  A container
+ * with a Huffman table of codes longer than 32 bits (no encoder writes one) gets a valid index that says "serial only". */
+mpc_status mpc_container_index(const uint8_t* bytes, size_t nbytes, int interval, uint8_t** index, size_t* index_bytes);
+typedef struct mpc_index_header {
+    int interval, n_streams;        /* n_streams = 1 + 6K, the lengths stream first */
+    int serial_only;                /* 1: no checkpoints; every decode with this index takes the serial route */
+    int width, height, K, block_size;
+    size_t container_bytes;
+} mpc_index_header;
+typedef struct mpc_index_stream_info {
+    int mode;                       /* 0 Huffman, 1 Golomb */
+    int packed;                     /* the container's run-length flag */
+    uint32_t m;                     /* Golomb parameter */
+    uint64_t n_coded;               /* symbols the entropy decode yields */
+    uint64_t expect;                /* symbols the stream expands to */
+    uint64_t wrapper_bit;           /* where the stream's wrapper begins: run-length flag, packed size, Huffman/Golomb bit, table or M */
+    uint64_t end_bit;               /* behind its last bit (behind the pseudo-EOF for Huffman) = the next stream's wrapper_bit */
+    uint64_t n_checkpoints;         /* ceil(n_coded / interval); checkpoint j = the bit of coded symbol j * interval */
+} mpc_index_stream_info;
+/* An index read back (its own consistency only; nothing is said about any container): MPC_ERR_BITSTREAM if it is not one.
+ * checkpoints: NULL, or room for `capacity` >= n_checkpoints values. */
+mpc_status mpc_index_info(const uint8_t* index, size_t index_bytes, mpc_index_header* info);
+mpc_status mpc_index_stream(const uint8_t* index, size_t index_bytes, int stream, mpc_index_stream_info* info, uint64_t* checkpoints,
+                            size_t capacity);
+/* The chunked parse on the host: what mpc_read_compressed_coded yields -- the lengths stream and the 6K coded streams back to back
+ * (symbols, mpc_free) -- with every chunk decoded from its checkpoint alone and accepted only under the rule above.  It defines
+ * what the device parse computes, checkable without a GPU.  route: 0 = the index was used, 1 = it was refused and the serial
+ * parse produced the result.  Status and text are mpc_read_compressed_coded's. */
+mpc_status mpc_parse_container_by_index(const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes,
+                                        uint16_t** symbols, size_t* n_symbols, int* route);
+/* The same on the device (mp_parse.hip), for tests: the decoder's own upload-and-parse step with host buffers in and out. */
+mpc_status mpc_parse_container_device(mpc_context* ctx, const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes,
+                                      uint16_t** symbols, size_t* n_symbols, int* route);
+/* mpc_decode_images / mpc_decode_images_device with an optional index per frame: indexes[f] == NULL (or indexes == NULL) = the
+ * serial route for frame f.  A frame with an index uploads the container's bytes instead of its parsed streams and has its
+ * entropy codes parsed by the device.  routes: NULL, or per frame 0 = parsed on the device, 1 = serial (no index, or the index
+ * was refused).  Pixels, statuses and error texts are those of the calls without indexes.  As with those calls, the content of
+ * d_rgb[f] after a call that failed is unspecified (a frame whose index the device refused has been written once before the
+ * serial route decides about it). */
+mpc_status mpc_decode_images_indexed(mpc_context* ctx, const uint8_t* const* bytes, const size_t* nbytes, const uint8_t* const* indexes,
+                                     const size_t* index_bytes, int n_frames, uint8_t** rgb, int* width, int* height, int* routes);
+mpc_status mpc_decode_images_indexed_device(mpc_context* ctx, const uint8_t* const* bytes, const size_t* nbytes,
+                                            const uint8_t* const* indexes, const size_t* index_bytes, int n_frames, uint8_t* const* d_rgb,
+                                            const size_t* capacity, int* width, int* height, int* routes);
+
 /* ---- "-s" patch statistics, Compression.cpp:200-302 ----
  * The reference seeds one std::mt19937, and for every image draws `patches` origins x = rand() % (width - bs),
  * y = rand() % (height - bs), runs CalcMPDynamic on the Y, U and V patch with every quantiser 1.0 and feeds
