@@ -51,8 +51,9 @@ constexpr float kHuge = 1.0e30f;                 // beyond this the f32 side may
 #define MPC_REFILL_AT 16
 #endif
 // Finished slots of a wave are refilled from the queue once this many are free.  Measured (MI355X, 16 Mpixel frames): 1, 2, 4, 8
-// and 16 all within 3 % of each other, 16 the best on the natural frame (2.57 ms vs 2.66 at 4) -- filling the slots early keeps
-// 14+ of 16 busy instead of 11.6, but slots at different steps make every wave-step pay for its oldest slot's pair list.
+// and 16 all within 3 % of each other -- filling the slots early keeps 14+ of 16 busy instead of 11.6.  With the pair updates in
+// packed rounds (8b) a wave-step no longer pays for its oldest slot's pair list; measured again: 4 is 1.2 % faster than 16 on the
+// synthetic frame and 2.4 % slower on the natural one, 8 the other way round: 16 stays.
 constexpr int kRefillAt = MPC_REFILL_AT;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -182,18 +183,12 @@ struct TopKeys {
         k1 = __uint_as_float(k1b > key ? k1b : key);
     }
 };
-// The mask of a key lives in a VECTOR register: v_and_or_b32 may read one scalar operand only (the code, a loop counter), so a
+// The mask of a key lives in a VECTOR register: v_and_or_b32 may read one scalar operand only (the code: an inline constant or a counter), so a
 // scalar or literal mask would split every key into v_and + v_or -- one more VALU instruction per tracked value.
 __device__ __forceinline__ unsigned in_vgpr(unsigned x)
 {
     unsigned v;
     asm volatile("v_mov_b32 %0, %1" : "=v"(v) : "s"(x));
-    return v;
-}
-__device__ __forceinline__ unsigned in_sgpr(unsigned x)          // x is wave-uniform; keeps the compiler from folding it into a literal
-{
-    unsigned v;
-    asm volatile("s_mov_b32 %0, %1" : "=s"(v) : "s"(x));
     return v;
 }
 constexpr unsigned kKeepRow = 0x7FFFFF80u;        // |value| with 7 code bits: tile (5) and row within the lane's four (2)
@@ -323,6 +318,11 @@ __global__ __launch_bounds__(64 * kWaves, kWaves / 4) void mp_pursuit_kernel(con
     // wave to leave the home channel makes its next channel the home (see the channel switch below).
     __shared__ int s_home;                                          // home channel; -1 while tiles 32 .. 35 are being replaced
     __shared__ int s_on[3];                                         // waves of this workgroup at work on each channel
+    // The pair rounds of (8b), per wave: the 16 items of the current round, and where their results are merged for the owning slots
+    __shared__ unsigned s_item[16 * kWaves];                        // slot (4 bits) | pair (5) | block (9) | rows (7)
+    __shared__ unsigned s_k1[64 * kWaves], s_k2[64 * kWaves];       // per lane (slot, h): the two largest keys of the slot's pair rows in lane row h
+    __shared__ float s_lb[16 * kWaves];                             // per slot: the largest lower bound of its pairs
+    __shared__ unsigned s_oddm[kWaves];                             // slots with a pair that cannot be screened (huge coefficient or bound)
     const int ch_first = a.n_tc[0] > 0 ? 0 : (a.n_tc[1] > 0 ? 1 : 2);
     const T* const base_rows = reinterpret_cast<const T*>(kFast ? static_cast<const void*>(a.base32) : static_cast<const void*>(a.base));
     {
@@ -423,34 +423,13 @@ __global__ __launch_bounds__(64 * kWaves, kWaves / 4) void mp_pursuit_kernel(con
     float rbound[kGroups];
 #pragma unroll
     for (int g = 0; g < kGroups; ++g) { lbmax[g] = -3.0e38f; oddp[g] = false; rbound[g] = 0.0f; }
-    // same_p: p is the same in every lane (a loop counter): every key's code then sits in a scalar register of its own
-    auto pair_update = [&](auto gc, auto same_p, int p, bool upd, unsigned info, float4 (&pv)[4], const float4 (&gv)[4], float E) {
-        constexpr int g = decltype(gc)::value;
-        FRESH_LANE
-        const long long pi = (long long)(g * 16 + slot) * kMaxPairs + p;
-        const int rows = (int)((info >> 9) & 127u);
-        if (upd) {
-            const float c32 = (float)tc[g].coeff;
-            float4* pp = reinterpret_cast<float4*>(my_p + pi * 64 + 4 * h);
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                pv[t].x = fmaf(-c32, gv[t].x, pv[t].x);
-                pv[t].y = fmaf(-c32, gv[t].y, pv[t].y);
-                pv[t].z = fmaf(-c32, gv[t].z, pv[t].z);
-                pv[t].w = fmaf(-c32, gv[t].w, pv[t].w);
-                pp[4 * t] = pv[t];
-            }
-            // |P_b - <b, r>| grows by at most 2^-23 |c| (rounding of c and of G) + 2^-24 (|r| + E) (the fma's result)
-            E = (E + 0x1p-21f * (fabsf(c32) + rbound[g])) * 1.000001f;
-            if (h == 0) my_e[pi] = E;
-            oddp[g] = oddp[g] || !(fabsf(c32) < kHuge);
-        }
-        oddp[g] = oddp[g] || !(E < kHuge);
+    // Upper-bound keys |P_b| + E of the 16 rows a lane holds of one pair (tile t, row v of its four: code_of(t, v) names them), tracked
+    // into `top`; `biggest` = the largest |P_b| among them (the pair's lower bound is biggest - E).
+    auto pair_keys = [&](int h, int rows, const float4 (&pv)[4], float E, auto code_of, TopKeys& top, float& biggest) {
         // rows 62 and 63 of a block can be pads (blocks have 62 or 63 rows): lane row h = 3, tile 3, v = 2, 3.  Their P and G
         // are exactly 0; their upper bound must be 0 too (not E), or a pad could pass for a survivor.
         const bool pad2 = h == 3 && rows < 63, pad3 = h == 3 && rows < 64;
         const unsigned keepp = keep_pair_mask;
-        float biggest = 0.0f;                                   // of this pair's |P|: its lower bound is biggest - E
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             const float vals[4] = {pv[t].x, pv[t].y, pv[t].z, pv[t].w};
@@ -460,13 +439,28 @@ __global__ __launch_bounds__(64 * kWaves, kWaves / 4) void mp_pursuit_kernel(con
                 float ub = m + E;
                 if (t == 3 && v == 2) ub = pad2 ? 0.0f : ub;
                 if (t == 3 && v == 3) ub = pad3 ? 0.0f : ub;
-                const unsigned code = (unsigned)((p << 4) | (t << 2) | v);
-                tp[g].see(__float_as_uint(ub), keepp, decltype(same_p)::value ? in_sgpr((unsigned)__builtin_amdgcn_readfirstlane((int)code)) : code);
+                top.see(__float_as_uint(ub), keepp, code_of(t, v));
                 biggest = __builtin_amdgcn_fmed3f(biggest, m, __builtin_inff());
             }
         }
+    };
+    // a pair that was not updated (the fresh one of (2c)): its keys join the lane's own registers
+    auto pair_fresh = [&](auto gc, int p, unsigned info, const float4 (&pv)[4], float E) {
+        constexpr int g = decltype(gc)::value;
+        FRESH_LANE
+        oddp[g] = oddp[g] || !(E < kHuge);
+        float biggest = 0.0f;
+        pair_keys(h, (int)((info >> 9) & 127u), pv, E, [&](int t, int v) { return (unsigned)((p << 4) | (t << 2) | v); }, tp[g], biggest);
         lbmax[g] = __builtin_amdgcn_fmed3f(lbmax[g], biggest - E, __builtin_inff());
     };
+    // the wave's part of the pair rounds' LDS (see (8b)): empty between the steps
+    {
+        FRESH_LANE
+        s_k1[64 * wave + lane] = 0u;
+        s_k2[64 * wave + lane] = 0u;
+        if (h == 0) s_lb[16 * wave + slot] = -3.0e38f;
+        if (lane == 0) s_oddm[wave] = 0u;
+    }
     for (;;) {
         // ---- (1) refill: slots whose tile-channel has ended take the next tile-channels from the queue, kRefillAt or more at
         //      a time (one atomic per refill; a wave whose slots are all free refills at once)
@@ -654,8 +648,7 @@ __global__ __launch_bounds__(64 * kWaves, kWaves / 4) void mp_pursuit_kernel(con
 #pragma unroll
                 for (int t = 0; t < 4; ++t) dst[4 * t] = pnew[t];
                 if (h == 0) my_e[(g * 16 + slot) * kMaxPairs + tc[g].fresh] = Eb[g];
-                const float4 none[4] = {};
-                pair_update(gc, std::false_type{}, tc[g].fresh, false, fresh_info, pnew, none, Eb[g]);
+                pair_fresh(gc, tc[g].fresh, fresh_info, pnew, Eb[g]);
             }
         });
         STAMP(3)
@@ -1010,69 +1003,118 @@ __global__ __launch_bounds__(64 * kWaves, kWaves / 4) void mp_pursuit_kernel(con
         });
         STAMP(10)
 
-        // ---- (8b) the pairs of the tile-channels that go on, for the NEXT step (see `pair_update`): pair 0's P, G and E first
-        float4 pv0[kGroups][4], gv0[kGroups][4];
-        float E0[kGroups];
-        bool on0[kGroups], upd0[kGroups];
-        unsigned info0[kGroups];
-#pragma unroll
-        for (int g = 0; g < kGroups; ++g) {
-            FRESH_LANE
-            on0[g] = unit[g] >= 0 && tc[g].live && !ended[g] && tc[g].npairs > 0 && tc[g].fresh != 0;
-            upd0[g] = on0[g] && tc[g].coeff != 0.0;
-            info0[g] = tc[g].packed(0);
-            const long long pi = (long long)(g * 16 + slot) * kMaxPairs;
-            const float4* pp = reinterpret_cast<const float4*>(my_p + pi * 64 + 4 * h);
-            const float4* gp = reinterpret_cast<const float4*>(gram + (upd0[g] ? (long long)tc[g].sel_g * a.gram_stride + (int)(info0[g] & 511u) * 64 : 0) + 4 * h);
-#pragma unroll
-            for (int t = 0; t < 4; ++t) { pv0[g][t] = pp[4 * t]; gv0[g][t] = gp[4 * t]; }
-            E0[g] = my_e[pi];
-        }
-#pragma unroll
-        for (int g = 0; g < kGroups; ++g) { tp[g] = TopKeys(); lbmax[g] = -3.0e38f; oddp[g] = false; }
+        // ---- (8b) the pairs of the tile-channels that go on, for the NEXT step (see above `pair_keys`).  The wave's pair updates are
+        //      ITEMS (slot, p): pair p of a slot that is live and has not ended, p < npairs, p != fresh.  They are numbered level by
+        //      level (all p = 0 by slot, then all p = 1, ...: a level's slots are a ballot, its first number a running sum of
+        //      popcounts, an owner's rank the popcount under its slot bit -- all scalar), and item j is worked on in round j >> 4 by
+        //      quad j & 15, the lanes q, q + 16, q + 32, q + 48 (lane row h as in the owning slot: the survivor codes' row 4 h + v
+        //      stays).  So a round updates up to 16 pairs whichever slots own them, instead of one pair of every slot that has one.
+        //      Owners post their items of the round in the wave's 16 words of s_item; the results go back to the owner's lanes
+        //      through LDS atomics (s_k1 / s_k2 per lane, s_lb per slot, s_oddm) which only this wave touches: program order is enough.
         static_for<kGroups>([&](auto gc) {
             constexpr int g = decltype(gc)::value;
-            if (__ballot(on0[g])) { COUNT(17, 1) COUNT(18, __popcll(__ballot(on0[g]) & 0xFFFFull)) }
-            if (on0[g]) pair_update(gc, std::true_type{}, 0, upd0[g], info0[g], pv0[g], gv0[g], E0[g]);
-        });
+            tp[g] = TopKeys(); lbmax[g] = -3.0e38f; oddp[g] = false;
+            if (unit[g] < 0) return;
+            const bool goes_on = tc[g].live && !ended[g];
+            if (!__ballot(goes_on && tc[g].npairs > 0)) return;
+            const unsigned updm = (unsigned)(__ballot(goes_on && tc[g].coeff != 0.0) & 0xFFFFull);     // lane row 0 speaks for its slot
+            const float c32 = (float)tc[g].coeff;
+            int p = 0, base = 0, round = 0;                         // level; number of its first item; scalar, like `total`
+            bool exhausted = false;
 #pragma unroll 1
-        for (int p = 1;; ++p) {                                     // further pairs: both groups' loads of a round issued together
-            bool on[kGroups];
-            bool any = false;
+            for (;;) {
+                int total = base;
+                {
+                    FRESH_LANE
+#pragma unroll 1
+                    for (;;) {                                      // post the items of this round, level by level
+                        const bool has = goes_on && p < tc[g].npairs;
+                        if (!__ballot(has)) { exhausted = true; break; }
+                        const bool item = has && p != tc[g].fresh;
+                        const unsigned m = (unsigned)(__ballot(item) & 0xFFFFull);
+                        const int j = base + __popc(m & ((1u << slot) - 1u));
+                        if (item && h == 0 && (j >> 4) == round)
+                            s_item[16 * wave + (j & 15)] = (unsigned)slot | ((unsigned)p << 4) | ((p < 4 ? tc[g].packed(p) : 0u) << 9);
+                        total = base + __popc(m);
+                        if (total > 16 * (round + 1)) break;        // the level goes on in the next round: posted from there
+                        base = total;
+                        ++p;
+                        if (total == 16 * (round + 1)) break;
+                    }
+                }
+                const int n = total - 16 * round < 16 ? total - 16 * round : 16;
+                if (n <= 0) break;
+                COUNT(17, 1) COUNT(18, n)
+                __builtin_amdgcn_wave_barrier();
+                {
+                    FRESH_LANE                                      // `slot` is the quad's number here
+                    const bool act = slot < n;
+                    const unsigned w = act ? s_item[16 * wave + slot] : 0u;
+                    const int os = (int)(w & 15u), ip = (int)((w >> 4) & 31u);      // the item: owner slot and pair
+                    const long long pi = (long long)(g * 16 + os) * kMaxPairs + ip;
+                    unsigned info = w >> 9;                         // block | rows << 9 of pairs 0 .. 3
+                    if (__ballot(ip >= 4)) info = ip >= 4 ? (my_meta[2 * pi] & 0xFFFFu) : info;
+                    const float ic = __shfl(c32, os), irb = __shfl(rbound[g], os);
+                    const int isel = __shfl(tc[g].sel_g, os);
+                    const bool upd = act && ((updm >> os) & 1u) != 0u;
+                    float4* pp = reinterpret_cast<float4*>(my_p + pi * 64 + 4 * h);
+                    const float4* gp = reinterpret_cast<const float4*>(gram + (upd ? (long long)isel * a.gram_stride + (int)(info & 511u) * 64 : 0) + 4 * h);
+                    float4 pv[4], gv[4];
 #pragma unroll
-            for (int g = 0; g < kGroups; ++g) {
-                on[g] = unit[g] >= 0 && tc[g].live && !ended[g] && p < tc[g].npairs && p != tc[g].fresh;
-                any = any || (unit[g] >= 0 && tc[g].live && !ended[g] && p < tc[g].npairs);
+                    for (int t = 0; t < 4; ++t) { pv[t] = pp[4 * t]; gv[t] = gp[4 * t]; }
+                    float E = my_e[pi];
+                    if (act) {
+                        if (upd) {
+#pragma unroll
+                            for (int t = 0; t < 4; ++t) {
+                                pv[t].x = fmaf(-ic, gv[t].x, pv[t].x);
+                                pv[t].y = fmaf(-ic, gv[t].y, pv[t].y);
+                                pv[t].z = fmaf(-ic, gv[t].z, pv[t].z);
+                                pv[t].w = fmaf(-ic, gv[t].w, pv[t].w);
+                                pp[4 * t] = pv[t];
+                            }
+                            // |P_b - <b, r>| grows by at most 2^-23 |c| (rounding of c and of G) + 2^-24 (|r| + E) (the fma's result)
+                            E = (E + 0x1p-21f * (fabsf(ic) + irb)) * 1.000001f;
+                            if (h == 0) my_e[pi] = E;
+                        }
+                        const bool oddi = (upd && !(fabsf(ic) < kHuge)) || !(E < kHuge);
+                        TopKeys top;
+                        float biggest = 0.0f;                       // of this pair's |P|: its lower bound is biggest - E
+                        pair_keys(h, (int)((info >> 9) & 127u), pv, E, [](int t, int v) { return (unsigned)((t << 2) | v); }, top, biggest);
+                        // the pair's number joins the two keys afterwards (below the value's bits, above tile and row: order kept)
+                        const unsigned k1 = __float_as_uint(top.k1) | ((unsigned)ip << 4), k2 = __float_as_uint(top.k2) | ((unsigned)ip << 4);
+                        // (K1, K2) stay the two largest of everything merged, in any order, also when two quads serve one slot
+                        const int own = 64 * wave + os + 16 * h;
+                        const unsigned old = __hip_atomic_fetch_max(&s_k1[own], k1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                        const unsigned lower = old < k1 ? old : k1;
+                        __hip_atomic_fetch_max(&s_k2[own], lower > k2 ? lower : k2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                        __hip_atomic_fetch_max(&s_lb[16 * wave + os], biggest - E, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                        if (oddi && h == 0) __hip_atomic_fetch_or(&s_oddm[wave], 1u << os, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                    }
+                }
+                __builtin_amdgcn_wave_barrier();
+                ++round;
+                if (exhausted) break;
             }
-            if (!__ballot(any)) break;
-            unsigned info[kGroups];
-            float4 pv[kGroups][4], gv[kGroups][4];
-            float E[kGroups];
-            bool upd[kGroups];
-#pragma unroll
-            for (int g = 0; g < kGroups; ++g) {
+            if (round > 0) {                                        // hand-over to the owners' registers; the LDS is left empty
                 FRESH_LANE
-                const long long pi = (long long)(g * 16 + slot) * kMaxPairs + (on[g] ? p : 0);
-                info[g] = p < 4 ? tc[g].packed(p) : (my_meta[2 * pi] & 0xFFFFu);
-                upd[g] = on[g] && tc[g].coeff != 0.0;
-                const float4* pp = reinterpret_cast<const float4*>(my_p + pi * 64 + 4 * h);
-                const float4* gp = reinterpret_cast<const float4*>(gram + (upd[g] ? (long long)tc[g].sel_g * a.gram_stride + (int)(info[g] & 511u) * 64 : 0) + 4 * h);
-#pragma unroll
-                for (int t = 0; t < 4; ++t) { pv[g][t] = pp[4 * t]; gv[g][t] = gp[4 * t]; }
-                E[g] = my_e[pi];
+                tp[g].k1 = __uint_as_float(s_k1[64 * wave + lane]);
+                tp[g].k2 = __uint_as_float(s_k2[64 * wave + lane]);
+                lbmax[g] = s_lb[16 * wave + slot];
+                oddp[g] = ((s_oddm[wave] >> slot) & 1u) != 0u;
+                __builtin_amdgcn_wave_barrier();
+                s_k1[64 * wave + lane] = 0u;
+                s_k2[64 * wave + lane] = 0u;
+                if (h == 0) s_lb[16 * wave + slot] = -3.0e38f;
+                if (lane == 0) s_oddm[wave] = 0u;
             }
-            static_for<kGroups>([&](auto gc) {
-                constexpr int g = decltype(gc)::value;
-                COUNT(17, 1) COUNT(18, __popcll(__ballot(on[g]) & 0xFFFFull))
-                if (on[g]) pair_update(gc, std::true_type{}, p, upd[g], info[g], pv[g], gv[g], E[g]);
-            });
-        }
+        });
         STAMP(2)
-
 
         // ---- (9) residual update r -= (q * quant) * row: Vector::Scale then Vector::Subtract, two roundings.  Behind it, what
         //      the next step will read from far away is pulled towards the cache by LDS-DMA into a landing zone nobody reads (no
-        //      register, no wait): the Gram rows of the pairs, the filter tiles of a new pair.
+        //      register, no wait): the filter tiles of a new pair.  (The Gram rows of the pairs are not touched here: their update
+        //      runs in (8b), before this phase.)
         static_for<kGroups>([&](auto gc) {
             constexpr int g = decltype(gc)::value;
             if (unit[g] < 0) return;
