@@ -7,6 +7,8 @@
 #   make asan-host   step 1 only (what tests/test_asan_host.py runs)
 #   make asan-index  tests/cpp/asan_index: the seek index's builder, validator and host chunk decoder on damaged containers and
 #                    damaged indexes (what tests/test_asan_index.py runs)
+#   make asan-encode-index  tests/cpp/asan_encode_index: the encoder's seek index on the host -- the by-plan route that records the
+#                    checkpoints, index_from_plan -- against the parsed index (what tests/test_asan_encode_index.py runs)
 #
 # GPU AddressSanitizer is not available on the test pool; the kernels are covered by the parity suite instead.
 SAN = -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer
@@ -24,6 +26,12 @@ tests/cpp/asan_index_bin: tests/cpp/asan_index.cpp $(wildcard imageexperiments_a
 asan-index: tests/cpp/asan_index_bin
 	ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=print_stacktrace=1 MPC_HOST_THREADS=4 ./tests/cpp/asan_index_bin $(GOLDEN_MN)
 
+tests/cpp/asan_encode_index_bin: tests/cpp/asan_encode_index.cpp $(wildcard imageexperiments_amd/csrc/host_*.cpp imageexperiments_amd/csrc/host_*.h)
+	g++ -std=c++17 -O1 -g $(SAN) -ffp-contract=off -pthread -Wall -Wno-unused-function tests/cpp/asan_encode_index.cpp -o $@
+
+asan-encode-index: tests/cpp/asan_encode_index_bin
+	ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=print_stacktrace=1 MPC_HOST_THREADS=4 ./tests/cpp/asan_encode_index_bin
+
 oracle/_build/liboracle_asan.so: $(wildcard oracle/*.c oracle/*.h)
 	mkdir -p oracle/_build
 	gcc -std=c11 -O1 -g $(SAN) -ffp-contract=off -fPIC -shared -o $@ oracle/mpo_*.c -lm
@@ -32,6 +40,6 @@ asan-oracle: oracle/_build/liboracle_asan.so
 	LD_PRELOAD=$$(gcc -print-file-name=libasan.so) ASAN_OPTIONS=detect_leaks=0 ORACLE_LIB=$(CURDIR)/oracle/_build/liboracle_asan.so \
 	    python -m pytest tests/test_oracle_golden.py -x -q -p no:cacheprovider
 
-asan: asan-host asan-index asan-oracle
+asan: asan-host asan-index asan-encode-index asan-oracle
 
-.PHONY: asan asan-host asan-index asan-oracle
+.PHONY: asan asan-host asan-index asan-encode-index asan-oracle

@@ -112,6 +112,18 @@ def _bind_bitstream(L):
         getattr(L, f).argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, _dp, _u16p, _u16p, _ullp, C.POINTER(_u8p), C.POINTER(C.c_size_t)]
     L.mpc_code_symbol_streams_device.argtypes = [vp, C.c_int, C.c_int, _dp, _u16p, _u16p, _ullp, C.POINTER(_u8p), C.POINTER(C.c_size_t),
                                                  C.POINTER(C.c_int)]
+    try:
+        L.mpc_assemble_symbol_streams_by_plan_indexed.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, _dp, _u16p, _u16p, _ullp, C.c_int,
+                                                                  C.POINTER(_u8p), C.POINTER(C.c_size_t), C.POINTER(_u8p), C.POINTER(C.c_size_t)]
+        L.mpc_code_symbol_streams_device_indexed.argtypes = [vp, C.c_int, C.c_int, _dp, _u16p, _u16p, _ullp, C.c_int, C.POINTER(_u8p),
+                                                             C.POINTER(C.c_size_t), C.POINTER(_u8p), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
+        L.mpc_encode_images_indexed.argtypes = [vp, C.POINTER(_u8p), C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.POINTER(_u8p),
+                                                C.POINTER(C.c_size_t), C.POINTER(_u8p), C.POINTER(C.c_size_t)]
+        L.mpc_encode_images_indexed_device.argtypes = [vp, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.POINTER(_u8p),
+                                                       C.POINTER(C.c_size_t), C.POINTER(_u8p), C.POINTER(C.c_size_t)]
+    except AttributeError:
+        if not os.environ.get("MPCODEC_LIB"):             # an older build may be loaded for A/B timing only
+            raise
     L.mpc_read_compressed.argtypes = [_u8p, C.c_size_t, C.POINTER(vp)]
     L.mpc_streams_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.mpc_streams_quant.argtypes = [vp, _u16p]
@@ -321,6 +333,21 @@ def assemble_symbol_streams(width, height, K, block_size, quant, counts, streams
     _check(fn(width, height, K, block_size, q.ctypes.data_as(_dp), cp, symbols.ctypes.data_as(_u16p),
               off.ctypes.data_as(C.POINTER(C.c_ulonglong)), C.byref(out), C.byref(n)))
     return _take_bytes(L, out, n)
+
+
+def assemble_symbol_streams_by_plan_indexed(width, height, K, block_size, quant, counts, streams, interval=0):
+    """mpc_assemble_symbol_streams_by_plan_indexed: assemble_symbol_streams(by_plan=True) with the container's seek index recorded
+    while the codes are written -> (container, index): index == container_index(container, interval), or None for streams
+    that do not hold what `counts` implies (no parser accepts their container)."""
+    L = load_library()
+    q = np.ascontiguousarray(quant, np.float64).reshape(3 * K)
+    cn, cp = _u16(counts)
+    symbols, off = _symbol_streams(K, streams)
+    out, n, idx, ni = _u8p(), C.c_size_t(0), _u8p(), C.c_size_t(0)
+    _check(L.mpc_assemble_symbol_streams_by_plan_indexed(width, height, K, block_size, q.ctypes.data_as(_dp), cp, symbols.ctypes.data_as(_u16p),
+                                                         off.ctypes.data_as(C.POINTER(C.c_ulonglong)), int(interval), C.byref(out), C.byref(n),
+                                                         C.byref(idx), C.byref(ni)))
+    return _take_bytes(L, out, n), (_take_bytes(L, idx, ni) if idx else None)
 
 
 def container_info(blob):
@@ -714,6 +741,32 @@ class CompressionContext:
         take = _take_view if views else _take_bytes
         return [take(self.L, outs[i], C.c_size_t(sizes[i])) for i in range(n)]
 
+    def _indexed(self, fn, ptrs, n, width, height, interval, quant):
+        qp = None
+        if quant is not None:
+            quant = np.ascontiguousarray(quant, np.float64).reshape(3, self.K)
+            qp = quant.ctypes.data_as(_dp)
+        outs, sizes, idx, isizes = (_u8p * n)(), (C.c_size_t * n)(), (_u8p * n)(), (C.c_size_t * n)()
+        _check(fn(self.h, ptrs, n, width, height, qp, int(interval), outs, sizes, idx, isizes))
+        return [(_take_bytes(self.L, outs[i], C.c_size_t(sizes[i])), _take_bytes(self.L, idx[i], C.c_size_t(isizes[i]))) for i in range(n)]
+
+    def encode_images_indexed(self, frames, interval=0, quant=None):
+        """mpc_encode_images_indexed: encode_images with every container's seek index from the entropy stage itself ->
+        [(container, index)], index == container_index(container, interval).  interval: 0 = the default, else 32 ... 65536."""
+        frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
+        H, W = frames[0].shape[:2]
+        if any(f.shape[:2] != (H, W) for f in frames):
+            raise ValueError("frames must have the same size")
+        n = len(frames)
+        ptrs = (_u8p * n)(*[f.ctypes.data_as(_u8p) for f in frames])
+        return self._indexed(self.L.mpc_encode_images_indexed, ptrs, n, W, H, interval, quant)
+
+    def encode_images_indexed_device(self, d_frames, width, height, interval=0, quant=None):
+        """mpc_encode_images_indexed_device: the same for frames in device memory (as encode_images_device takes them)."""
+        n = len(d_frames)
+        ptrs = (C.c_void_p * n)(*[C.c_void_p(int(p)) for p in d_frames])
+        return self._indexed(self.L.mpc_encode_images_indexed_device, ptrs, n, width, height, interval, quant)
+
     def encode_image_device(self, d_rgb, width, height, quant=None):
         return self.encode_images_device([d_rgb], width, height, quant)[0]
 
@@ -856,6 +909,21 @@ class CompressionContext:
         _check(self.L.mpc_code_symbol_streams_device(self.h, width, height, qp, cp, symbols.ctypes.data_as(_u16p),
                                                      off.ctypes.data_as(C.POINTER(C.c_ulonglong)), C.byref(out), C.byref(n), C.byref(route)))
         return _take_bytes(self.L, out, n), route.value
+
+    def code_symbol_streams_device_indexed(self, width, height, counts, streams, interval=0, quant=None):
+        """mpc_code_symbol_streams_device_indexed: code_symbol_streams_device with the container's seek index ->
+        (container, index or None, route); None for streams that do not hold what `counts` implies."""
+        qp = None
+        if quant is not None:
+            quant = np.ascontiguousarray(quant, np.float64).reshape(3, self.K)
+            qp = quant.ctypes.data_as(_dp)
+        cn, cp = _u16(counts)
+        symbols, off = _symbol_streams(self.K, streams)
+        out, n, idx, ni, route = _u8p(), C.c_size_t(0), _u8p(), C.c_size_t(0), C.c_int(-1)
+        _check(self.L.mpc_code_symbol_streams_device_indexed(self.h, width, height, qp, cp, symbols.ctypes.data_as(_u16p),
+                                                             off.ctypes.data_as(C.POINTER(C.c_ulonglong)), int(interval), C.byref(out),
+                                                             C.byref(n), C.byref(idx), C.byref(ni), C.byref(route)))
+        return _take_bytes(self.L, out, n), (_take_bytes(self.L, idx, ni) if idx else None), route.value
 
     def container_job_begin(self, slot, d_counts, d_choices, width, height, quant=None, stream=0):
         """mpc_container_job_begin: stream assembly + entropy phase 1 of whole-frame records in device memory, enqueued only."""

@@ -175,6 +175,25 @@ std::vector<size_t> expected_sizes(const std::vector<uint16_t>& lengths, int K);
 bool read_compressed_coded_by_index(const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes, CodedStreams& out,
                                     int* route);
 
+// The same index from what an encoder holds when it has just written the container, without parsing anything: the plans of
+// plan_stream, where each stream's codes begin, and the bit of every interval-th coded symbol as the code writer passed it.
+struct StreamPlan;                                  // below
+struct PlannedStream {                              // one per stream, the lengths stream first
+    uint64_t first_code_bit = 0;                    // where the stream's codes begin in the container (behind its wrapper)
+    uint64_t n = 0, eff_n = 0;                      // symbols as assembled; symbols that were coded (after run-length packing)
+    bool shorter = false;                           // the run-length packed stream is what was coded
+};
+// checkpoints: stream behind stream, ceil(eff_n / interval) each (the blob's own order).  The blob build_container_index gives
+// for that container, provided the streams hold what the lengths stream implies (streams_match_lengths) and no Huffman code is
+// longer than 32 bits.  false = the positions contradict the plans (head_bits, stream behind stream, checkpoints in order);
+// `blob` is then empty
+bool index_from_plan(uint32_t interval, size_t nbytes, int width, int height, int K, int block_size, size_t head_bits,
+                     const StreamPlan* plans, const PlannedStream* streams, int n_streams, const uint64_t* checkpoints,
+                     std::vector<uint8_t>& blob);
+// every one of the 6K streams holds as many symbols as the lengths stream implies (expected_sizes): what the serial parser
+// goes by.  lengths[3 * tiles], off[6K + 1]
+bool streams_match_lengths(const uint16_t* lengths, size_t tiles, int K, const unsigned long long* off);
+
 // the header alone; false = not a container read_compressed would accept the header of
 bool container_info(const uint8_t* bytes, size_t nbytes, int* width, int* height, int* K, int* block_size);
 // worker threads of the host stages (MPC_HOST_THREADS, else the machine's, at most 16)
@@ -220,6 +239,13 @@ void parallel_io_jobs(int n, int workers, const std::function<void(int)>& body);
 // encode_symbol_streams_malloc through plan_stream / or_bits, the device's share (statistics, code writing) done on the host
 uint8_t* encode_symbol_streams_by_plan_malloc(int width, int height, int K, int block_size, const double* quant, const uint16_t* counts,
                                               const uint16_t* symbols, const unsigned long long* off, size_t* nbytes);
+
+// The same container together with its seek index, the checkpoints recorded while the codes are written: this defines what
+// the device's code kernel records (mp_entropy.hip).  Streams that do not match the lengths stream: the container alone,
+// `index` empty.  A Huffman code longer than 32 bits: build_container_index of the finished container.  interval: 32 ... 65536
+uint8_t* encode_symbol_streams_by_plan_indexed_malloc(int width, int height, int K, int block_size, const double* quant,
+                                                      const uint16_t* counts, const uint16_t* symbols, const unsigned long long* off,
+                                                      uint32_t interval, size_t* nbytes, std::vector<uint8_t>& index);
 
 // Inverse of encode_records_malloc's gathering: per-tile records in the reference's visiting order.  counts[3*tiles],
 // choices[3*tiles*K] (deltaId | intCoeff << 16, zero beyond count).  false = streams inconsistent with `lengths`.

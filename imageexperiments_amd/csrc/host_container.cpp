@@ -222,12 +222,20 @@ uint8_t* encode_symbol_streams_malloc(int width, int height, int K, int block_si
 // encode_symbol_streams_malloc by the route the device-side entropy stage takes, with the device's share done here on the
 // host: per-stream statistics -> plan_stream -> codes at the planned bit offsets -> OR the pieces into place.  Exists so that
 // the planning half can be checked against the direct route without a GPU (tests/test_host_bitstream.py).
-uint8_t* encode_symbol_streams_by_plan_malloc(int width, int height, int K, int block_size, const double* quant, const uint16_t* counts,
-                                              const uint16_t* symbols, const unsigned long long* off, size_t* nbytes) {
+namespace {
+// interval 0: the container alone.  Otherwise cps gets, stream behind stream, the container bit of every interval-th coded
+// symbol, and `planned` where each stream's codes begin; *wide: a Huffman code longer than 32 bits, nothing recorded
+uint8_t* encode_by_plan(int width, int height, int K, int block_size, const double* quant, const uint16_t* counts, const uint16_t* symbols,
+                        const unsigned long long* off, uint32_t interval, size_t* nbytes, std::vector<StreamPlan>& plans,
+                        std::vector<PlannedStream>& planned, std::vector<uint64_t>& cps, bool* wide) {
     const size_t tiles = tile_count(width, height, block_size);
     const int S = 6 * K + 1;
-    std::vector<StreamPlan> plans(static_cast<size_t>(S));
+    plans.assign(static_cast<size_t>(S), StreamPlan());
+    planned.assign(static_cast<size_t>(S), PlannedStream());
+    cps.clear();
+    *wide = false;
     std::vector<BitWriter> payload(static_cast<size_t>(S));
+    size_t bit = container_head(width, height, K, block_size, quant).bit_size();
     for (int j = 0; j < S; ++j) {
         const uint16_t* data = j == 0 ? counts : symbols + off[j - 1];
         const size_t n = j == 0 ? 3 * tiles : static_cast<size_t>(off[j] - off[j - 1]);
@@ -246,6 +254,14 @@ uint8_t* encode_symbol_streams_by_plan_malloc(int width, int height, int K, int 
             if (hist[v]) { triples.push_back(v); triples.push_back(hist[v]); triples.push_back(first[v]); }
         StreamPlan& p = plans[static_cast<size_t>(j)];
         plan_stream(j != 0, shorter, static_cast<uint32_t>(rle_size), coded_n, largest, triples.data(), triples.size() / 3, p);
+        PlannedStream& ps = planned[static_cast<size_t>(j)];
+        bit += p.pre.bit_size();
+        ps.first_code_bit = bit;
+        ps.n = n;
+        ps.eff_n = coded_n;
+        ps.shorter = shorter;
+        if (p.mode == 0 && p.max_code_length > 32) *wide = true;
+        const bool record = interval != 0 && !*wide;
         BitWriter& w = payload[static_cast<size_t>(j)];
         if (p.mode == 0) {
             std::vector<uint32_t> code_of(static_cast<size_t>(largest) + 1, 0);
@@ -254,28 +270,67 @@ uint8_t* encode_symbol_streams_by_plan_malloc(int width, int height, int K, int 
                 code_of[p.entries[k]] = p.entries[k + 1];
                 length_of[p.entries[k]] = static_cast<uint8_t>(p.entries[k + 2]);
             }
-            w.put_codes(coded, coded_n, code_of.data(), length_of.data(), p.payload_bits);
-        } else {
+            if (!record) w.put_codes(coded, coded_n, code_of.data(), length_of.data(), p.payload_bits);
+            else
+                for (size_t i = 0; i < coded_n; ++i) {           // the device's walk: the position in front of every code
+                    if (i % interval == 0) cps.push_back(bit + w.bit_size());
+                    w.put(code_of[coded[i]], length_of[coded[i]]);
+                }
+        } else if (!record) {
             golomb_encode(coded, coded_n, p.m, w);
+        } else {
+            for (size_t i = 0; i < coded_n; ++i) {
+                if (i % interval == 0) cps.push_back(bit + w.bit_size());
+                golomb_write(coded[i], p.m, w);
+            }
         }
         if (w.bit_size() != p.payload_bits) return nullptr;
+        bit += p.payload_bits + p.post.bit_size();
     }
     const BitWriter head = container_head(width, height, K, block_size, quant);
-    size_t total = head.bit_size();
-    for (int j = 0; j < S; ++j) total += plans[static_cast<size_t>(j)].pre.bit_size() + plans[static_cast<size_t>(j)].payload_bits + plans[static_cast<size_t>(j)].post.bit_size();
-    *nbytes = (total + 7) / 8;
+    *nbytes = (bit + 7) / 8;
     uint8_t* dst = static_cast<uint8_t*>(std::calloc(*nbytes ? *nbytes : 1, 1));
     if (!dst) return nullptr;
     or_bits(dst, *nbytes, 0, head);
-    size_t at = head.bit_size();
     for (int j = 0; j < S; ++j) {
         const StreamPlan& p = plans[static_cast<size_t>(j)];
-        or_bits(dst, *nbytes, at, p.pre);
-        at += p.pre.bit_size();
+        const size_t at = static_cast<size_t>(planned[static_cast<size_t>(j)].first_code_bit);
+        or_bits(dst, *nbytes, at - p.pre.bit_size(), p.pre);
         or_bits(dst, *nbytes, at, payload[static_cast<size_t>(j)]);
-        at += p.payload_bits;
-        or_bits(dst, *nbytes, at, p.post);
-        at += p.post.bit_size();
+        or_bits(dst, *nbytes, at + p.payload_bits, p.post);
+    }
+    return dst;
+}
+}  // namespace
+
+uint8_t* encode_symbol_streams_by_plan_malloc(int width, int height, int K, int block_size, const double* quant, const uint16_t* counts,
+                                              const uint16_t* symbols, const unsigned long long* off, size_t* nbytes) {
+    std::vector<StreamPlan> plans;
+    std::vector<PlannedStream> planned;
+    std::vector<uint64_t> cps;
+    bool wide;
+    return encode_by_plan(width, height, K, block_size, quant, counts, symbols, off, 0, nbytes, plans, planned, cps, &wide);
+}
+
+uint8_t* encode_symbol_streams_by_plan_indexed_malloc(int width, int height, int K, int block_size, const double* quant,
+                                                      const uint16_t* counts, const uint16_t* symbols, const unsigned long long* off,
+                                                      uint32_t interval, size_t* nbytes, std::vector<uint8_t>& index) {
+    index.clear();
+    const bool consistent = streams_match_lengths(counts, tile_count(width, height, block_size), K, off);
+    std::vector<StreamPlan> plans;
+    std::vector<PlannedStream> planned;
+    std::vector<uint64_t> cps;
+    bool wide = false;
+    uint8_t* dst = encode_by_plan(width, height, K, block_size, quant, counts, symbols, off, consistent ? interval : 0, nbytes, plans,
+                                  planned, cps, &wide);
+    if (!dst || !consistent) return dst;
+    const size_t head_bits = container_head(width, height, K, block_size, quant).bit_size();
+    const bool ok = wide ? build_container_index(dst, *nbytes, interval, index)
+                         : index_from_plan(interval, *nbytes, width, height, K, block_size, head_bits, plans.data(), planned.data(),
+                                           6 * K + 1, cps.data(), index);
+    if (!ok) {
+        std::free(dst);
+        return nullptr;
     }
     return dst;
 }
@@ -449,6 +504,54 @@ bool build_container_index(const uint8_t* bytes, size_t nbytes, uint32_t interva
     }
     if (x.serial_only)
         for (IndexStream& is : x.streams) is.checkpoints.clear();
+    blob = index_blob(x);
+    return true;
+}
+
+bool streams_match_lengths(const uint16_t* lengths, size_t tiles, int K, const unsigned long long* off) {
+    const std::vector<size_t> expect = expected_sizes(std::vector<uint16_t>(lengths, lengths + 3 * tiles), K);
+    for (int i = 0; i < 6 * K; ++i)
+        if (off[i + 1] - off[i] != expect[static_cast<size_t>(i)]) return false;
+    return true;
+}
+
+bool index_from_plan(uint32_t interval, size_t nbytes, int width, int height, int K, int block_size, size_t head_bits,
+                     const StreamPlan* plans, const PlannedStream* streams, int n_streams, const uint64_t* checkpoints,
+                     std::vector<uint8_t>& blob) {
+    blob.clear();
+    if (interval < kIndexIntervalMin || interval > kIndexIntervalMax || n_streams != 6 * K + 1) return false;
+    ContainerIndex x;
+    x.interval = interval;
+    x.nbytes = nbytes;
+    x.width = width; x.height = height; x.K = K; x.block_size = block_size;
+    x.streams.resize(static_cast<size_t>(n_streams));
+    uint64_t bit = head_bits;
+    const uint64_t* cp = checkpoints;
+    for (int j = 0; j < n_streams; ++j) {
+        const StreamPlan& p = plans[j];
+        const PlannedStream& ps = streams[j];
+        IndexStream& is = x.streams[static_cast<size_t>(j)];
+        is.wrapper_bit = ps.first_code_bit - p.pre.bit_size();
+        is.end_bit = ps.first_code_bit + p.payload_bits + p.post.bit_size();
+        if (is.wrapper_bit != bit) return false;                // stream behind stream, the first behind the head
+        bit = is.end_bit;
+        is.n_coded = ps.eff_n;
+        is.expect = ps.n;
+        is.packed = j != 0 && ps.shorter;
+        is.mode = static_cast<uint32_t>(p.mode);
+        is.m = p.mode ? p.m : 0u;
+        const size_t n_cp = static_cast<size_t>((ps.eff_n + interval - 1) / interval);
+        // the code writer's positions: the first code's, then strictly forward, inside the stream's codes
+        uint64_t before = ps.first_code_bit;
+        for (size_t c = 0; c < n_cp; ++c) {
+            if (c == 0 ? cp[c] != before : cp[c] <= before) return false;
+            before = cp[c];
+        }
+        if (n_cp && before >= ps.first_code_bit + p.payload_bits) return false;
+        is.checkpoints.assign(cp, cp + n_cp);
+        cp += n_cp;
+    }
+    if ((bit + 7) / 8 != nbytes) return false;
     blob = index_blob(x);
     return true;
 }

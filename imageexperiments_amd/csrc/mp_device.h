@@ -304,7 +304,7 @@ struct EntStream {                      // one per stream; the device fills the 
     unsigned distinct, triple_off;      // its (symbol, count, first position) triples in `triples`
     unsigned mode;                      // host: 0 = Huffman (dense table), 1 = Golomb
     unsigned m;                         // host: Golomb parameter
-    unsigned reserved;
+    unsigned reserved;                  // phase 1: the compaction's write cursor.  Phase 2, host: its first slot in `checkpoints`
     unsigned long long bit_off;         // host: bit offset of the stream's first code in the container
     unsigned long long coded_bits;      // device: bits written for the stream's symbols
 };
@@ -336,13 +336,21 @@ struct EntropyArgs {
     uint8_t* tlen;                      // [n_streams][65536]
     const unsigned* entries;            // [n_entries][3]: stream << 16 | symbol, code, length (may be mapped host memory)
     unsigned n_entries;
+    unsigned cp_interval;               // seek index: coded symbols per checkpoint, 32 ... 65536 (read only where `checkpoints` is set)
     unsigned* out32;                    // the container, zeroed
     unsigned long long out_words;
+    // seek index (null: none): the container bit of coded symbol c * cp_interval of stream s at [streams[s].reserved + c], stream
+    // behind stream -- the index blob's own layout.  cp_capacity entries; nothing is written beyond them
+    unsigned long long* checkpoints;
+    unsigned cp_capacity;
 };
 size_t entropy_max_blocks(unsigned long long symbols, int n_streams);
+// checkpoints the streams of a frame can have at most, whatever the interval (>= 32): sum of ceil(eff_n / interval)
+size_t entropy_max_checkpoints(unsigned long long capacity_symbols, int n_streams);
 // capacity_symbols: upper bound of the symbols in all streams (lengths included); hipError_t as int
 int launch_entropy_phase1(const EntropyArgs& a, unsigned long long capacity_symbols, void* stream);
-// raw_symbols: symbols in all streams as assembled (sum of EntStream::n)
+// raw_symbols: symbols in all streams as assembled (sum of EntStream::n).  With a.checkpoints set the code-writing pass also
+// records the seek index's checkpoints; otherwise the launches are exactly those of a call without an index
 int launch_entropy_phase2(const EntropyArgs& a, unsigned long long raw_symbols, void* stream);
 
 // bytes of workspace needed for `cap` tile-channels and K steps

@@ -22,7 +22,8 @@
 //   phase 2
 //     tables   the host's part of the per-stream records in; scatter the (symbol -> code, length) entries into dense per-stream tables
 //     count    code bits per block;  offsets  exclusive scan per stream, from the stream's bit offset
-//     write    the codes, MSB first, into the zeroed container (32-bit atomic ORs of byte-swapped words)
+//     write    the codes, MSB first, into the zeroed container (32-bit atomic ORs of byte-swapped words); for a caller who
+//              wants the seek index, the bit of every interval-th coded symbol as well (kIndex)
 //     clear    the table entries, for the next frame; the per-stream records (bit counts) back to host memory
 // Integer work, HBM/L2-bound; 2 bytes per symbol and pass, ~10 M symbols per 16 Mpixel frame.
 #include <hip/hip_runtime.h>
@@ -546,8 +547,9 @@ __device__ __forceinline__ unsigned golomb_bits(unsigned value, unsigned m, unsi
 }
 }  // namespace
 
-// kWrite = false: code bits per block;  kWrite = true: the codes themselves
-template <bool kWrite>
+// kWrite = false: code bits per block;  kWrite = true: the codes themselves;  kIndex (with kWrite): also the seek index's
+// checkpoints -- the container bit of every cp_interval-th coded symbol of the stream, which is a position this pass holds anyway
+template <bool kWrite, bool kIndex = false>
 __global__ __launch_bounds__(kThreads) void ent_code_kernel(const EntropyArgs a)
 {
     __shared__ unsigned scratch[kThreads / 64];
@@ -587,7 +589,19 @@ __global__ __launch_bounds__(kThreads) void ent_code_kernel(const EntropyArgs a)
         if (threadIdx.x == 0) a.blk_bits[b] = total;
         return;
     }
-    if (bits == 0) return;
+    // The thread's symbols are begin + t0 .. + 15 of the stream and the interval is at least 32: at most one of them starts a
+    // chunk of the index.  cp_k: which (kPer = none); it goes to the stream's slot (its number / interval).
+    int cp_k = kPer;
+    unsigned cp_slot = 0;
+    if (kIndex && t0 < len) {
+        const unsigned first = begin + t0, chunk = (first + a.cp_interval - 1) / a.cp_interval;
+        const unsigned k = chunk * a.cp_interval - first;
+        if (k < (unsigned)kPer && t0 + k < len && s.reserved + chunk < a.cp_capacity) {
+            cp_k = (int)k;
+            cp_slot = s.reserved + chunk;
+        }
+    }
+    if (bits == 0 && cp_k == kPer) return;
     // MSB-first bit position P lives in byte P >> 3; a 32-bit big-endian word is OR-ed in byte-swapped
     unsigned long long pos = a.blk_bit_off[b] + before;
     unsigned long long w = pos >> 5;
@@ -612,6 +626,7 @@ __global__ __launch_bounds__(kThreads) void ent_code_kernel(const EntropyArgs a)
 #pragma unroll
     for (int k = 0; k < kPer; ++k) {
         if (t0 + k < len) {
+            if (kIndex && k == cp_k) a.checkpoints[cp_slot] = (w << 5) | fill;       // the bit this symbol's code begins at
             if (!golomb) {
                 const unsigned n = tlen[sym[k]];
                 if (n) append(tcode[sym[k]], n);
@@ -650,6 +665,11 @@ __global__ __launch_bounds__(64) void ent_bit_offsets_kernel(const EntropyArgs a
     if (lane == 0) a.streams[j].coded_bits = at - s.bit_off;
 }
 
+size_t entropy_max_checkpoints(unsigned long long capacity_symbols, int n_streams)
+{
+    return (size_t)(capacity_symbols / 32) + (size_t)n_streams;
+}
+
 size_t entropy_max_blocks(unsigned long long capacity_symbols, int n_streams)
 {
     return (size_t)((capacity_symbols + kEntBlock - 1) / kEntBlock) + (size_t)n_streams;
@@ -682,7 +702,12 @@ int launch_entropy_phase2(const EntropyArgs& a, unsigned long long raw_symbols, 
     hipLaunchKernelGGL(ent_tables_kernel, dim3(eblocks + 1), dim3(kThreads), 0, st, a, 0);
     hipLaunchKernelGGL(ent_code_kernel<false>, dim3(blocks), dim3(kThreads), 0, st, a);
     hipLaunchKernelGGL(ent_bit_offsets_kernel, dim3((unsigned)a.n_streams), dim3(64), 0, st, a);
-    hipLaunchKernelGGL(ent_code_kernel<true>, dim3(blocks), dim3(kThreads), 0, st, a);
+    if (a.checkpoints) {
+        if (a.cp_interval < 32) return (int)hipErrorInvalidValue;      // two checkpoints among a thread's symbols
+        hipLaunchKernelGGL((ent_code_kernel<true, true>), dim3(blocks), dim3(kThreads), 0, st, a);
+    } else {
+        hipLaunchKernelGGL(ent_code_kernel<true>, dim3(blocks), dim3(kThreads), 0, st, a);
+    }
     hipLaunchKernelGGL(ent_tables_kernel, dim3(eblocks + 1), dim3(kThreads), 0, st, a, 1);
     return (int)hipGetLastError();
 }

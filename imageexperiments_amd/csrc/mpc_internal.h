@@ -207,10 +207,14 @@ struct EntropyBuffers {
     unsigned* h_triples = nullptr;
     unsigned* h_entries = nullptr;
     uint8_t* h_out = nullptr;
+    // the seek index's checkpoints (with_index only): args.checkpoints on the device, their pinned copy
+    unsigned long long* h_checkpoints = nullptr;
 };
 
-// carve (and grow) a slot's entropy buffers for frames of `tiles` tiles; the symbols of the streams live in the caller's buffers
-mpc_status entropy_buffers(EntropySlot& e, size_t tiles, int K, EntropyBuffers* b);
+// carve (and grow) a slot's entropy buffers for frames of `tiles` tiles; the symbols of the streams live in the caller's buffers.
+// with_index: the checkpoint arrays as well, behind everything else -- a slot never used with an index holds none, and one that
+// was keeps them (grow-only) without moving anything when a call comes without
+mpc_status entropy_buffers(EntropySlot& e, size_t tiles, int K, EntropyBuffers* b, bool with_index = false);
 
 // What the host keeps of a frame between the tables step and the collect step of the device route.
 struct EntropyPending {
@@ -226,6 +230,10 @@ struct EntropyPending {
 //                      `done`; `enqueued` (optional) is called once that is on the stream or clear that it will not be.  The
 //                      host route (MPC_HOST_ENTROPY, or a frame the device tables cannot hold) makes the container here instead.
 //   container_collect  waits for `done`, patches the head and the streams' pre and post bits in
+// With index_interval set the job also leaves the container's seek index in `index`, the blob mpc_container_index would build
+// from the finished container: on the device route from the plans and the checkpoints the code kernel recorded (index_from_plan;
+// the pinned copy of the checkpoints travels on `down` behind the container's, in front of `done`), on the host route by
+// build_container_index.
 struct ContainerJob {
     hipStream_t side = nullptr, down = nullptr;
     hipEvent_t phase1 = nullptr, done = nullptr;
@@ -235,6 +243,7 @@ struct ContainerJob {
     const uint16_t* h_counts = nullptr;  // ... unless they are on the host already
     const unsigned long long* h_stream_off = nullptr;
     const uint16_t* h_symbols = nullptr;
+    unsigned index_interval = 0;         // 0 = no index, else 32 ... 65536; needs `eb` carved with_index
     // set by container_begin
     int width = 0, height = 0, K = 0, block_size = 0;
     std::vector<double> quant;
@@ -245,6 +254,7 @@ struct ContainerJob {
     EntropyPending pending;
     uint8_t* blob = nullptr;             // the host route's container
     size_t nblob = 0;
+    std::vector<uint8_t> index;          // the result with index_interval set, complete after container_collect
     double stamps[5] = {};               // MPC_TRACE: phase 1 done, statistics read, tables built, symbols on the host, bytes on the host
     ~ContainerJob() { std::free(blob); }
 };

@@ -94,6 +94,34 @@ mpc_status mpc_assemble_symbol_streams_by_plan(int width, int height, int K, int
     });
 }
 
+mpc_status mpc_assemble_symbol_streams_by_plan_indexed(int width, int height, int K, int block_size, const double* quant,
+                                                       const uint16_t* counts, const uint16_t* symbols, const unsigned long long* stream_off,
+                                                       int interval, uint8_t** bytes, size_t* nbytes, uint8_t** index, size_t* index_bytes) {
+    return guarded([&]() -> mpc_status {
+    if (!index || !index_bytes) return fail(MPC_ERR_ARGUMENT, "bad argument");
+    if (const mpc_status bad = check_symbol_streams(width, height, K, block_size, quant, counts, symbols, stream_off, bytes, nbytes)) return bad;
+    if (interval != 0 && (interval < static_cast<int>(mpc::kIndexIntervalMin) || interval > static_cast<int>(mpc::kIndexIntervalMax)))
+        return fail(MPC_ERR_ARGUMENT, "interval %d: 0 or %u to %u", interval, mpc::kIndexIntervalMin, mpc::kIndexIntervalMax);
+    *index = nullptr;
+    *index_bytes = 0;
+    std::vector<uint8_t> blob;
+    uint8_t* container = mpc::encode_symbol_streams_by_plan_indexed_malloc(
+        width, height, K, block_size, quant, counts, symbols, stream_off, interval ? static_cast<uint32_t>(interval) : mpc::kIndexIntervalDefault,
+        nbytes, blob);
+    if (!container) return fail(MPC_ERR_ALLOC, "out of memory or inconsistent plan");
+    if (!blob.empty()) {
+        *index = give_bytes(blob, index_bytes);
+        if (!*index) {
+            std::free(container);
+            *index_bytes = 0;
+            return fail(MPC_ERR_ALLOC, "out of memory");
+        }
+    }
+    *bytes = container;
+    return MPC_OK;
+    });
+}
+
 mpc_status mpc_read_compressed(const uint8_t* bytes, size_t nbytes, mpc_streams** out) {
     return guarded([&]() -> mpc_status {
     if (!bytes || !out) return fail(MPC_ERR_ARGUMENT, "null argument");

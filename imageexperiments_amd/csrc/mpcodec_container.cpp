@@ -15,15 +15,17 @@
 
 #include "mpc_internal.h"
 
-mpc_status entropy_buffers(EntropySlot& e, size_t tiles, int K, EntropyBuffers* b) {
+mpc_status entropy_buffers(EntropySlot& e, size_t tiles, int K, EntropyBuffers* b, bool with_index) {
     const int S = 6 * K + 1;
     const size_t n_tc = 3 * tiles;
     const unsigned long long cap_symbols = n_tc + 2ULL * n_tc * K;
     const size_t blocks = mpc::entropy_max_blocks(cap_symbols, S);
     const size_t table_words = 65536 * static_cast<size_t>(S);          // dense code tables, histogram, first positions: [S][65536]
     const size_t out_bytes = Carve::up(sizeof(uint16_t) * 2 * n_tc * K) + 65536;
+    const size_t max_cp = with_index ? mpc::entropy_max_checkpoints(cap_symbols, S) : 0;
     mpc::EntropyArgs& a = b->args;
     a = mpc::EntropyArgs{};
+    b->h_checkpoints = nullptr;
     auto device_layout = [&](char* base) {
         Carve cv{base};
         a.streams = cv.take<mpc::EntStream>(S);
@@ -37,6 +39,7 @@ mpc_status entropy_buffers(EntropySlot& e, size_t tiles, int K, EntropyBuffers* 
         b->d_out = cv.take<uint8_t>(out_bytes);
         a.ghist = cv.take<unsigned>(table_words);
         a.gfirst = cv.take<unsigned>(table_words);
+        if (with_index) a.checkpoints = cv.take<unsigned long long>(max_cp);
         return cv.at;
     };
     auto host_layout = [&](char* base) {
@@ -46,6 +49,7 @@ mpc_status entropy_buffers(EntropySlot& e, size_t tiles, int K, EntropyBuffers* 
         b->h_triples = cv.take<unsigned>(3 * static_cast<size_t>(kTripleCap));
         b->h_entries = cv.take<unsigned>(3 * static_cast<size_t>(kTripleCap));
         b->h_out = cv.take<uint8_t>(out_bytes);
+        if (with_index) b->h_checkpoints = cv.take<unsigned long long>(max_cp);
         return cv.at;
     };
     bool grown = false;
@@ -66,6 +70,7 @@ mpc_status entropy_buffers(EntropySlot& e, size_t tiles, int K, EntropyBuffers* 
     a.n_streams = S;
     a.triple_cap = kTripleCap;
     a.out32 = reinterpret_cast<unsigned*>(b->d_out);
+    a.cp_capacity = static_cast<unsigned>(max_cp);
     if (e.tiles != tiles || e.K != K) {
         // the dense code tables and the histogram are zero between frames (the kernels clear what they set), the first
         // positions all ones; a slot carved for another geometry holds them elsewhere
@@ -102,7 +107,8 @@ hipError_t wait_event(hipEvent_t ev, bool spin) {
 //                    to the host, `done`.  kNeedsHost: nothing enqueued, take the host route.
 //   entropy_collect  waits for `done`, checks the device's bit counts against the tables', patches the host's pieces in.
 EntropyResult entropy_tables(const EntropyBuffers& b, int device_block_size, int width, int height, int K, const double* quant,
-                             unsigned triple_limit, hipStream_t s, hipEvent_t done, EntropyPending* pending, double* stamps) {
+                             unsigned triple_limit, unsigned index_interval, hipStream_t s, hipEvent_t done, EntropyPending* pending,
+                             double* stamps) {
     const mpc::EntropyArgs& a = b.args;
     const int S = a.n_streams;
     if (b.h_totals[3] != 0 || b.h_totals[2] > triple_limit) return EntropyResult::kNeedsHost;
@@ -120,7 +126,8 @@ EntropyResult entropy_tables(const EntropyBuffers& b, int device_block_size, int
     });
     pending->head = mpc::container_head(width, height, K, device_block_size, quant);
     unsigned long long bit = pending->head.bit_size(), raw_symbols = 0;
-    size_t n_entries = 0;
+    size_t n_entries = 0, n_cp = 0;
+    if (index_interval && !(a.checkpoints && b.h_checkpoints)) return EntropyResult::kFailed;
     for (int j = 0; j < S; ++j) {
         const mpc::StreamPlan& p = plans[static_cast<size_t>(j)];
         if (p.mode == 0 && p.max_code_length > 32) return EntropyResult::kNeedsHost;
@@ -129,12 +136,16 @@ EntropyResult entropy_tables(const EntropyBuffers& b, int device_block_size, int
         st.bit_off = bit;
         st.mode = static_cast<unsigned>(p.mode);
         st.m = p.m;
+        if (index_interval) {                                   // the stream's checkpoints: behind those of the streams before it
+            st.reserved = static_cast<unsigned>(n_cp);
+            n_cp += (static_cast<size_t>(st.eff_n) + index_interval - 1) / index_interval;
+        }
         bit += p.payload_bits + p.post.bit_size();
         raw_symbols += st.n;
         n_entries += p.entries.size() / 3;
     }
     const size_t total_bytes = static_cast<size_t>((bit + 7) / 8), out_words = (total_bytes + 3) / 4;
-    if (out_words * 4 > b.out_capacity || n_entries > kTripleCap) return EntropyResult::kNeedsHost;
+    if (out_words * 4 > b.out_capacity || n_entries > kTripleCap || n_cp > a.cp_capacity) return EntropyResult::kNeedsHost;
     pending->total_bytes = total_bytes;
     size_t at = 0;
     for (int j = 0; j < S; ++j) {
@@ -149,14 +160,18 @@ EntropyResult entropy_tables(const EntropyBuffers& b, int device_block_size, int
     mpc::EntropyArgs a2 = a;
     a2.n_entries = static_cast<unsigned>(n_entries);
     a2.out_words = out_words;
+    a2.cp_interval = index_interval;
+    if (!index_interval) a2.checkpoints = nullptr;              // a slot carved for an index, a call without: the usual kernels
     const bool ok = hipMemsetAsync(b.d_out, 0, out_words * 4, s) == hipSuccess && mpc::launch_entropy_phase2(a2, raw_symbols, s) == 0 &&
                     hipMemcpyAsync(b.h_out, b.d_out, out_words * 4, hipMemcpyDeviceToHost, s) == hipSuccess &&
+                    (n_cp == 0 || hipMemcpyAsync(b.h_checkpoints, a.checkpoints, sizeof(unsigned long long) * n_cp, hipMemcpyDeviceToHost,
+                                                 s) == hipSuccess) &&
                     hipEventRecord(done, s) == hipSuccess;
     return ok ? EntropyResult::kDone : EntropyResult::kFailed;
 }
 
-EntropyResult entropy_collect(const EntropyBuffers& b, const EntropyPending& pending, hipEvent_t done, bool spin, uint8_t** blob,
-                              size_t* nbytes, double* stamp) {
+EntropyResult entropy_collect(const EntropyBuffers& b, const EntropyPending& pending, const ContainerJob& job, hipEvent_t done, bool spin,
+                              uint8_t** blob, size_t* nbytes, std::vector<uint8_t>* index, double* stamp) {
     if (wait_event(done, spin) != hipSuccess) return EntropyResult::kFailed;
     *stamp = trace_ms();                                        // codes written, bytes on the host
     const int S = b.args.n_streams;
@@ -168,6 +183,22 @@ EntropyResult entropy_collect(const EntropyBuffers& b, const EntropyPending& pen
         const unsigned long long payload = b.h_streams[j].bit_off;
         mpc::or_bits(b.h_out, b.out_capacity, static_cast<size_t>(payload - p.pre.bit_size()), p.pre);
         mpc::or_bits(b.h_out, b.out_capacity, static_cast<size_t>(payload + p.payload_bits), p.post);
+    }
+    if (job.index_interval) {
+        // the index from what the stage holds: nothing of the container is parsed (host_container.cpp: index_from_plan)
+        std::vector<mpc::PlannedStream> planned(static_cast<size_t>(S));
+        for (int j = 0; j < S; ++j) {
+            const mpc::EntStream& st = b.h_streams[j];
+            mpc::PlannedStream& ps = planned[static_cast<size_t>(j)];
+            ps.first_code_bit = st.bit_off;
+            ps.n = st.n;
+            ps.eff_n = st.eff_n;
+            ps.shorter = st.shorter != 0;
+        }
+        if (!mpc::index_from_plan(job.index_interval, pending.total_bytes, job.width, job.height, job.K, job.block_size,
+                                  pending.head.bit_size(), pending.plans.data(), planned.data(), S,
+                                  reinterpret_cast<const uint64_t*>(b.h_checkpoints), *index))
+            return EntropyResult::kFailed;
     }
     uint8_t* out = static_cast<uint8_t*>(std::malloc(pending.total_bytes ? pending.total_bytes : 1));
     if (!out) return EntropyResult::kFailed;
@@ -227,7 +258,11 @@ mpc_status container_on_host(ContainerJob& j) {
     }
     j.stamps[3] = trace_ms();
     j.blob = mpc::encode_symbol_streams_malloc(j.width, j.height, j.K, j.block_size, j.quant.data(), counts, symbols, off, &j.nblob);
-    return j.blob ? MPC_OK : fail(MPC_ERR_ALLOC, "out of memory");
+    if (!j.blob) return fail(MPC_ERR_ALLOC, "out of memory");
+    // the host route's index: the finished container parsed (rare; this is also where a "serial only" index comes from)
+    if (j.index_interval && !mpc::build_container_index(j.blob, j.nblob, j.index_interval, j.index))
+        return fail(MPC_ERR_BITSTREAM, "the container of the host route does not parse: no index");
+    return MPC_OK;
 }
 }  // namespace
 
@@ -247,6 +282,7 @@ mpc_status container_begin(ContainerJob& j, const mpc_context* c, const EntropyB
     std::free(j.blob);
     j.blob = nullptr;
     j.nblob = 0;
+    j.index.clear();
     mpc::StreamArgs& sa = j.sa;
     sa = mpc::StreamArgs{};
     sa.counts = d_counts;
@@ -276,8 +312,8 @@ mpc_status container_tables(ContainerJob& j, const std::function<void()>& enqueu
     j.stamps[0] = trace_ms();
     EntropyResult r = EntropyResult::kNeedsHost;
     if (j.device_entropy)
-        r = entropy_tables(j.eb, j.block_size, j.width, j.height, j.K, j.quant.data(), j.triple_limit, j.down, j.done, &j.pending,
-                           j.stamps + 1);
+        r = entropy_tables(j.eb, j.block_size, j.width, j.height, j.K, j.quant.data(), j.triple_limit, j.index_interval, j.down, j.done,
+                           &j.pending, j.stamps + 1);
     if (enqueued) enqueued();
     if (r == EntropyResult::kFailed) return fail(MPC_ERR_HIP, "device entropy stage failed: %s", hipGetErrorString(hipGetLastError()));
     if (r == EntropyResult::kDone) return MPC_OK;
@@ -293,23 +329,29 @@ mpc_status container_collect(ContainerJob& j, uint8_t** bytes, size_t* nbytes) {
         j.nblob = 0;
         return MPC_OK;
     }
-    const EntropyResult r = entropy_collect(j.eb, j.pending, j.done, j.spin, bytes, nbytes, &j.stamps[4]);
+    const EntropyResult r = entropy_collect(j.eb, j.pending, j, j.done, j.spin, bytes, nbytes, &j.index, &j.stamps[4]);
     return r == EntropyResult::kDone ? MPC_OK : fail(MPC_ERR_HIP, "device entropy stage failed: %s", hipGetErrorString(hipGetLastError()));
 }
 
 namespace {
 // compressed::encodeImage for a sequence of equally sized frames: device tile encode, then records -> container (ContainerJob)
 // -- pipelined over kSeqSlots slots.  Frames come from host memory (uploaded through the slot's pinned image on an upload
-// stream) or are already resident on the device.
+// stream) or are already resident on the device.  index_interval != 0: every frame's seek index as well (indexes, index_bytes).
 mpc_status encode_sequence(mpc_context* c, const uint8_t* const* frames, bool on_device, int n_frames, int width, int height,
-                           const double* quant, uint8_t** bytes, size_t* nbytes) {
+                           const double* quant, uint8_t** bytes, size_t* nbytes, unsigned index_interval = 0, uint8_t** indexes = nullptr,
+                           size_t* index_bytes = nullptr) {
     if (!c || !frames || !bytes || !nbytes || n_frames < 1) return fail(MPC_ERR_ARGUMENT, "bad argument");
+    if (index_interval && (!indexes || !index_bytes)) return fail(MPC_ERR_ARGUMENT, "bad argument");
     if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback");
     if (width < 1 || height < 1) return fail(MPC_ERR_ARGUMENT, "bad geometry");
     for (int f = 0; f < n_frames; ++f) {
         if (!frames[f]) return fail(MPC_ERR_ARGUMENT, "null frame");
         bytes[f] = nullptr;
         nbytes[f] = 0;
+        if (index_interval) {
+            indexes[f] = nullptr;
+            index_bytes[f] = 0;
+        }
     }
     const Tuning t = read_tuning();
     const int tiles_y = (height + 7) / 8;
@@ -393,7 +435,7 @@ mpc_status encode_sequence(mpc_context* c, const uint8_t* const* frames, bool on
     EntropyBuffers ent[S];
     if (!t.host_entropy)
         for (size_t sl = 0; sl < alloc_slots; ++sl)
-            if (const mpc_status es = entropy_buffers(c->ent[sl], tiles, K, &ent[sl]); es != MPC_OK) return es;
+            if (const mpc_status es = entropy_buffers(c->ent[sl], tiles, K, &ent[sl], index_interval != 0); es != MPC_OK) return es;
     ContainerJob jobs[S];
     struct Pending {
         std::future<std::pair<uint8_t*, size_t>> result;     // malloc'ed container, or {nullptr, 0}
@@ -404,6 +446,17 @@ mpc_status encode_sequence(mpc_context* c, const uint8_t* const* frames, bool on
         if (p.frame < 0) return;
         const std::pair<uint8_t*, size_t> blob = p.result.get();
         if (st == MPC_OK && !blob.first) st = fail(MPC_ERR_HIP, "record download or container allocation failed");
+        if (st == MPC_OK && index_interval) {                  // the slot's job holds the frame's index until the slot's next frame
+            const std::vector<uint8_t>& index = jobs[&p - pending].index;
+            uint8_t* copy = index.empty() ? nullptr : static_cast<uint8_t*>(std::malloc(index.size()));
+            if (!copy) {
+                st = fail(MPC_ERR_ALLOC, "no seek index for frame %d", p.frame);
+            } else {
+                std::memcpy(copy, index.data(), index.size());
+                indexes[p.frame] = copy;
+                index_bytes[p.frame] = index.size();
+            }
+        }
         if (st == MPC_OK) {
             bytes[p.frame] = blob.first;
             nbytes[p.frame] = blob.second;
@@ -508,6 +561,7 @@ mpc_status encode_sequence(mpc_context* c, const uint8_t* const* frames, bool on
         job.spin = single;
         job.host_stage = &c->host_stage;
         job.host_offset = sl * host_slot + route_at;
+        job.index_interval = index_interval;
         MPC_SEQ_TRY(hipEventRecord(c->seq_pursuit_done[sl], pursuit_stream));
         MPC_SEQ_TRY(hipStreamWaitEvent(job.side, c->seq_pursuit_done[sl], 0));
         st = container_begin(job, c, t.host_entropy ? nullptr : &ent[sl], t.triple_limit, dbase + streams_at, d_counts,
@@ -548,13 +602,90 @@ mpc_status encode_sequence(mpc_context* c, const uint8_t* const* frames, bool on
     for (size_t sl = 0; sl < slots; ++sl) (void)hipStreamSynchronize(c->seq_down[sl]);
     if (st != MPC_OK) {
         for (int f = 0; f < n_frames; ++f) { std::free(bytes[f]); bytes[f] = nullptr; nbytes[f] = 0; }
+        if (index_interval)
+            for (int f = 0; f < n_frames; ++f) { std::free(indexes[f]); indexes[f] = nullptr; index_bytes[f] = 0; }
     }
     return st;
+}
+
+// the `interval` argument of the indexed entry points as mpc_container_index takes it: 0 = the default
+mpc_status index_interval_of(int interval, unsigned* out) {
+    if (interval != 0 && (interval < static_cast<int>(mpc::kIndexIntervalMin) || interval > static_cast<int>(mpc::kIndexIntervalMax)))
+        return fail(MPC_ERR_ARGUMENT, "interval %d: 0 or %u to %u", interval, mpc::kIndexIntervalMin, mpc::kIndexIntervalMax);
+    *out = interval ? static_cast<unsigned>(interval) : mpc::kIndexIntervalDefault;
+    return MPC_OK;
 }
 
 JobSlot* job_slot(mpc_context* c, int slot) {
     if (!c->jobs[slot]) c->jobs[slot] = std::make_unique<JobSlot>();
     return c->jobs[slot].get();
+}
+
+// mpc_code_symbol_streams_device[_indexed]; index_interval != 0: with the container's seek index
+mpc_status code_symbol_streams(mpc_context* c, int width, int height, const double* quant, const uint16_t* counts, const uint16_t* symbols,
+                               const unsigned long long* stream_off, unsigned index_interval, uint8_t** bytes, size_t* nbytes,
+                               uint8_t** index, size_t* index_bytes, int* route) {
+    return guarded([&]() -> mpc_status {
+    if (!c || !counts || !stream_off || !bytes || !nbytes || width < 1 || height < 1) return fail(MPC_ERR_ARGUMENT, "bad argument");
+    if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device");
+    const int K = c->K;
+    const size_t tiles = static_cast<size_t>((width + 7) / 8) * ((height + 7) / 8), n_tc = tiles * 3;
+    for (int s = 0; s < 6 * K; ++s)
+        if (stream_off[s + 1] < stream_off[s]) return fail(MPC_ERR_ARGUMENT, "stream offsets must not decrease");
+    const unsigned long long total = stream_off[6 * K];
+    if (stream_off[0] != 0 || total > 2ULL * n_tc * K || (total && !symbols)) return fail(MPC_ERR_ARGUMENT, "streams larger than a frame of this size can hold");
+    if (index_interval) {
+        *index = nullptr;
+        *index_bytes = 0;
+        if (!mpc::streams_match_lengths(counts, tiles, K, stream_off)) index_interval = 0;
+    }
+    const Tuning t = read_tuning();
+    std::lock_guard<std::recursive_mutex> one_host_call(c->host_calls);
+    HIP_TRY(hipSetDevice(c->device));
+    if (route) *route = 1;
+    DeviceTemp d_counts, d_symbols, d_off;
+    struct Job : ContainerJob {                                 // on the null stream; the host route codes the caller's streams
+        ~Job() { if (phase1) (void)hipEventDestroy(phase1); if (done) (void)hipEventDestroy(done); }
+    } j;
+    j.h_counts = counts;
+    j.h_stream_off = stream_off;
+    j.h_symbols = symbols;
+    j.index_interval = index_interval;
+    HIP_TRY(hipEventCreateWithFlags(&j.phase1, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&j.done, hipEventDisableTiming));
+    EntropyBuffers eb;
+    if (!t.host_entropy) {
+        if (const mpc_status es = entropy_buffers(c->ent[0], tiles, K, &eb, index_interval != 0); es != MPC_OK) return es;
+        const size_t n_off = 6 * static_cast<size_t>(K) + 1;
+        HIP_TRY(hipMalloc(&d_counts.p, sizeof(uint16_t) * n_tc));
+        HIP_TRY(hipMalloc(&d_symbols.p, sizeof(uint16_t) * (total ? total : 1)));
+        HIP_TRY(hipMalloc(&d_off.p, sizeof(unsigned long long) * n_off));
+        HIP_TRY(hipMemcpy(d_counts.p, counts, sizeof(uint16_t) * n_tc, hipMemcpyHostToDevice));
+        if (total) HIP_TRY(hipMemcpy(d_symbols.p, symbols, sizeof(uint16_t) * total, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_off.p, stream_off, sizeof(unsigned long long) * n_off, hipMemcpyHostToDevice));
+    }
+    mpc_status st = container_begin(j, c, t.host_entropy ? nullptr : &eb, t.triple_limit, nullptr, static_cast<const uint16_t*>(d_counts.p),
+                                    nullptr, static_cast<uint16_t*>(d_symbols.p), static_cast<unsigned long long*>(d_off.p), width, height,
+                                    quant);
+    if (st == MPC_OK) st = container_tables(j);
+    if (st == MPC_OK) st = container_collect(j, bytes, nbytes);
+    if (st == MPC_OK && index_interval) {
+        uint8_t* copy = j.index.empty() ? nullptr : static_cast<uint8_t*>(std::malloc(j.index.size()));
+        if (copy) {
+            std::memcpy(copy, j.index.data(), j.index.size());
+            *index = copy;
+            *index_bytes = j.index.size();
+        } else {
+            std::free(*bytes);
+            *bytes = nullptr;
+            *nbytes = 0;
+            st = fail(MPC_ERR_ALLOC, "no seek index");
+        }
+    }
+    if (st == MPC_OK && route && j.device_entropy) *route = 0;
+    HIP_TRY(hipDeviceSynchronize());
+    return st;
+    });
 }
 }  // namespace
 
@@ -674,48 +805,18 @@ mpc_status mpc_records_to_container_device(mpc_context* c, const uint16_t* d_cou
 mpc_status mpc_code_symbol_streams_device(mpc_context* c, int width, int height, const double* quant, const uint16_t* counts,
                                           const uint16_t* symbols, const unsigned long long* stream_off, uint8_t** bytes, size_t* nbytes,
                                           int* route) {
-    return guarded([&]() -> mpc_status {
-    if (!c || !counts || !stream_off || !bytes || !nbytes || width < 1 || height < 1) return fail(MPC_ERR_ARGUMENT, "bad argument");
-    if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device");
-    const int K = c->K;
-    const size_t tiles = static_cast<size_t>((width + 7) / 8) * ((height + 7) / 8), n_tc = tiles * 3;
-    for (int s = 0; s < 6 * K; ++s)
-        if (stream_off[s + 1] < stream_off[s]) return fail(MPC_ERR_ARGUMENT, "stream offsets must not decrease");
-    const unsigned long long total = stream_off[6 * K];
-    if (stream_off[0] != 0 || total > 2ULL * n_tc * K || (total && !symbols)) return fail(MPC_ERR_ARGUMENT, "streams larger than a frame of this size can hold");
-    const Tuning t = read_tuning();
-    std::lock_guard<std::recursive_mutex> one_host_call(c->host_calls);
-    HIP_TRY(hipSetDevice(c->device));
-    if (route) *route = 1;
-    DeviceTemp d_counts, d_symbols, d_off;
-    struct Job : ContainerJob {                                 // on the null stream; the host route codes the caller's streams
-        ~Job() { if (phase1) (void)hipEventDestroy(phase1); if (done) (void)hipEventDestroy(done); }
-    } j;
-    j.h_counts = counts;
-    j.h_stream_off = stream_off;
-    j.h_symbols = symbols;
-    HIP_TRY(hipEventCreateWithFlags(&j.phase1, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&j.done, hipEventDisableTiming));
-    EntropyBuffers eb;
-    if (!t.host_entropy) {
-        if (const mpc_status es = entropy_buffers(c->ent[0], tiles, K, &eb); es != MPC_OK) return es;
-        const size_t n_off = 6 * static_cast<size_t>(K) + 1;
-        HIP_TRY(hipMalloc(&d_counts.p, sizeof(uint16_t) * n_tc));
-        HIP_TRY(hipMalloc(&d_symbols.p, sizeof(uint16_t) * (total ? total : 1)));
-        HIP_TRY(hipMalloc(&d_off.p, sizeof(unsigned long long) * n_off));
-        HIP_TRY(hipMemcpy(d_counts.p, counts, sizeof(uint16_t) * n_tc, hipMemcpyHostToDevice));
-        if (total) HIP_TRY(hipMemcpy(d_symbols.p, symbols, sizeof(uint16_t) * total, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_off.p, stream_off, sizeof(unsigned long long) * n_off, hipMemcpyHostToDevice));
-    }
-    mpc_status st = container_begin(j, c, t.host_entropy ? nullptr : &eb, t.triple_limit, nullptr, static_cast<const uint16_t*>(d_counts.p),
-                                    nullptr, static_cast<uint16_t*>(d_symbols.p), static_cast<unsigned long long*>(d_off.p), width, height,
-                                    quant);
-    if (st == MPC_OK) st = container_tables(j);
-    if (st == MPC_OK) st = container_collect(j, bytes, nbytes);
-    if (st == MPC_OK && route && j.device_entropy) *route = 0;
-    HIP_TRY(hipDeviceSynchronize());
-    return st;
-    });
+    return code_symbol_streams(c, width, height, quant, counts, symbols, stream_off, 0, bytes, nbytes, nullptr, nullptr, route);
+}
+
+// The same with the container's seek index.  Streams that do not hold what `counts` implies (only a test makes such) give a
+// container no parser accepts: it comes back alone, *index = NULL.
+mpc_status mpc_code_symbol_streams_device_indexed(mpc_context* c, int width, int height, const double* quant, const uint16_t* counts,
+                                                  const uint16_t* symbols, const unsigned long long* stream_off, int interval,
+                                                  uint8_t** bytes, size_t* nbytes, uint8_t** index, size_t* index_bytes, int* route) {
+    unsigned every = 0;
+    if (!index || !index_bytes) return fail(MPC_ERR_ARGUMENT, "bad argument");
+    if (const mpc_status bad = index_interval_of(interval, &every)) return bad;
+    return code_symbol_streams(c, width, height, quant, counts, symbols, stream_off, every, bytes, nbytes, index, index_bytes, route);
 }
 
 mpc_status mpc_encode_images(mpc_context* c, const uint8_t* const* rgb_frames, int n_frames, int width, int height,
@@ -726,6 +827,29 @@ mpc_status mpc_encode_images(mpc_context* c, const uint8_t* const* rgb_frames, i
 mpc_status mpc_encode_images_device(mpc_context* c, const uint8_t* const* d_rgb_frames, int n_frames, int width, int height,
                                     const double* quant, uint8_t** bytes, size_t* nbytes) {
     return guarded([&]() -> mpc_status { return encode_sequence(c, d_rgb_frames, true, n_frames, width, height, quant, bytes, nbytes); });
+}
+
+// the same with every frame's seek index; n_frames == 1 is the single-frame route
+mpc_status mpc_encode_images_indexed(mpc_context* c, const uint8_t* const* rgb_frames, int n_frames, int width, int height,
+                                     const double* quant, int interval, uint8_t** bytes, size_t* nbytes, uint8_t** indexes,
+                                     size_t* index_bytes) {
+    return guarded([&]() -> mpc_status {
+        unsigned every = 0;
+        if (!indexes || !index_bytes) return fail(MPC_ERR_ARGUMENT, "bad argument");
+        if (const mpc_status bad = index_interval_of(interval, &every)) return bad;
+        return encode_sequence(c, rgb_frames, false, n_frames, width, height, quant, bytes, nbytes, every, indexes, index_bytes);
+    });
+}
+
+mpc_status mpc_encode_images_indexed_device(mpc_context* c, const uint8_t* const* d_rgb_frames, int n_frames, int width, int height,
+                                            const double* quant, int interval, uint8_t** bytes, size_t* nbytes, uint8_t** indexes,
+                                            size_t* index_bytes) {
+    return guarded([&]() -> mpc_status {
+        unsigned every = 0;
+        if (!indexes || !index_bytes) return fail(MPC_ERR_ARGUMENT, "bad argument");
+        if (const mpc_status bad = index_interval_of(interval, &every)) return bad;
+        return encode_sequence(c, d_rgb_frames, true, n_frames, width, height, quant, bytes, nbytes, every, indexes, index_bytes);
+    });
 }
 
 // compressed::encodeImage: one frame through the same stages

@@ -26,6 +26,10 @@
  *   mpc_encode_image          compressed::encodeImage                     CompressedImage.h:59
  *   mpc_encode_images         (same, a sequence of frames, host and device stages overlapped)
  *   mpc_encode_image(s)_device (same, frames already in device memory)
+ *   mpc_encode_images_indexed[_device] (same, each container together with its seek index: the blob mpc_container_index
+ *                             would build from it, emitted by the entropy stage instead of parsed out of the finished bytes;
+ *                             mpc_code_symbol_streams_device_indexed, mpc_assemble_symbol_streams_by_plan_indexed: the
+ *                             entropy stage alone, on the device and on the host)
  *   mpc_decode_image          compressed::decodeImage                     CompressedImage.h:75
  *   mpc_decode_tiles_device   matching::FromCoeffsDynamic per tile        MatchingPursuit.h:25, CompressedImage.cpp:797-831
  *   mpc_psnr                  compressed::calculatePSNR                   CompressedImage.h:57
@@ -218,6 +222,18 @@ mpc_status mpc_code_symbol_streams_device(mpc_context* ctx, int width, int heigh
                                           const uint16_t* symbols, const unsigned long long* stream_off, uint8_t** bytes, size_t* nbytes,
                                           int* route);
 
+/* The two above with the container's seek index (mpc_encode_images_indexed): *index / *index_bytes receive what
+ * mpc_container_index(*bytes, *nbytes, interval, ...) would return.  The by-plan form records the checkpoints while it writes the
+ * codes on the host and so defines, without a GPU, what the device's code kernel records.  Both accept streams that do not hold
+ * what `counts` implies (every stream as many symbols as tiles of its channel have more atoms than its step; only a test makes
+ * other streams): no parser accepts that container, so it comes back alone, *index = NULL, *index_bytes = 0, MPC_OK. */
+mpc_status mpc_assemble_symbol_streams_by_plan_indexed(int width, int height, int K, int block_size, const double* quant,
+                                                       const uint16_t* counts, const uint16_t* symbols, const unsigned long long* stream_off,
+                                                       int interval, uint8_t** bytes, size_t* nbytes, uint8_t** index, size_t* index_bytes);
+mpc_status mpc_code_symbol_streams_device_indexed(mpc_context* ctx, int width, int height, const double* quant, const uint16_t* counts,
+                                                  const uint16_t* symbols, const unsigned long long* stream_off, int interval,
+                                                  uint8_t** bytes, size_t* nbytes, uint8_t** index, size_t* index_bytes, int* route);
+
 /* readCompressed (CompressedImage.cpp:635): parse a container; streams come back with the DC differencing
  * undone.  index -1 = lengths, 0..6K-1 = codes[index].  The expansion runs on the host.  The decoder expands on the device
  * and uses this only to name the status of a container it refuses for its block size or a length above K; it is the
@@ -286,6 +302,21 @@ mpc_status mpc_encode_image_device(mpc_context* ctx, const uint8_t* d_rgb, int w
                                    uint8_t** bytes, size_t* nbytes);
 mpc_status mpc_encode_images_device(mpc_context* ctx, const uint8_t* const* d_rgb_frames, int n_frames, int width, int height,
                                     const double* quant, uint8_t** bytes, size_t* nbytes);
+
+/* mpc_encode_images / mpc_encode_images_device with every frame's seek index (see "Seek index" below): indexes[i] /
+ * index_bytes[i] receive the blob mpc_container_index(bytes[i], nbytes[i], interval, ...) would return, byte for byte, without
+ * the container being parsed: the entropy stage knows where every stream begins and its code-writing kernel passes every
+ * interval-th coded symbol's bit anyway.  The containers are those of the calls without an index.  interval as for
+ * mpc_container_index (0 = the default; anything else outside 32 ... 65536 is MPC_ERR_ARGUMENT before anything is enqueued).
+ * A frame that takes the host route for its entropy stage gets its index from the finished container on the host.
+ * n_frames == 1 is the single-frame route (mpc_encode_image).  Every buffer is released with mpc_free; on failure nothing is
+ * returned. */
+mpc_status mpc_encode_images_indexed(mpc_context* ctx, const uint8_t* const* rgb_frames, int n_frames, int width, int height,
+                                     const double* quant, int interval, uint8_t** bytes, size_t* nbytes, uint8_t** indexes,
+                                     size_t* index_bytes);
+mpc_status mpc_encode_images_indexed_device(mpc_context* ctx, const uint8_t* const* d_rgb_frames, int n_frames, int width, int height,
+                                            const double* quant, int interval, uint8_t** bytes, size_t* nbytes, uint8_t** indexes,
+                                            size_t* index_bytes);
 
 /* compressed::encodeImage for a sequence of equally sized frames on SEVERAL GPUs of one node from one process (what a
  * Compression.cpp-style caller gets with MPC_DEVICES=0,1,...: dropin/compressionlib_dropin.cpp).  ctxs[0 .. n_devices): one context
