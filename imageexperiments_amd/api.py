@@ -41,6 +41,10 @@ class _IndexHeader(C.Structure):                     # mpc_index_header
                 ("K", C.c_int), ("block_size", C.c_int), ("container_bytes", C.c_size_t)]
 
 
+class MpcRect(C.Structure):                          # mpc_rect
+    _fields_ = [("x", C.c_int), ("y", C.c_int), ("width", C.c_int), ("height", C.c_int)]
+
+
 class _IndexStreamInfo(C.Structure):                 # mpc_index_stream_info
     _fields_ = [("mode", C.c_int), ("packed", C.c_int), ("m", C.c_uint32), ("n_coded", C.c_uint64), ("expect", C.c_uint64),
                 ("wrapper_bit", C.c_uint64), ("end_bit", C.c_uint64), ("n_checkpoints", C.c_uint64)]
@@ -147,6 +151,14 @@ def _bind_bitstream(L):
     L.mpc_index_stream.argtypes = [_u8p, C.c_size_t, C.c_int, C.POINTER(_IndexStreamInfo), C.POINTER(C.c_uint64), C.c_size_t]
     L.mpc_parse_container_by_index.argtypes = [_u8p, C.c_size_t, _u8p, C.c_size_t, C.POINTER(_u16p), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
     L.mpc_parse_container_device.argtypes = [vp, _u8p, C.c_size_t, _u8p, C.c_size_t, C.POINTER(_u16p), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
+    _rp = C.POINTER(MpcRect)
+    _win = [_u8p, C.c_size_t, _u8p, C.c_size_t, _rp, C.c_uint, C.POINTER(_u16p), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
+    L.mpc_parse_container_window_by_index.argtypes = _win
+    L.mpc_parse_container_window_device.argtypes = [vp] + _win
+    L.mpc_decode_regions_indexed.argtypes = [vp, C.POINTER(_u8p), C.POINTER(C.c_size_t), C.POINTER(_u8p), C.POINTER(C.c_size_t), _rp, C.c_int,
+                                             C.c_uint, C.POINTER(_u8p), C.POINTER(C.c_int)]
+    L.mpc_decode_regions_indexed_device.argtypes = [vp, C.POINTER(_u8p), C.POINTER(C.c_size_t), C.POINTER(_u8p), C.POINTER(C.c_size_t), _rp,
+                                                    C.c_int, C.c_uint, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
     L.mpc_decode_images_indexed.argtypes = [vp, C.POINTER(_u8p), C.POINTER(C.c_size_t), C.POINTER(_u8p), C.POINTER(C.c_size_t), C.c_int,
                                             C.POINTER(_u8p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.mpc_decode_images_indexed_device.argtypes = [vp, C.POINTER(_u8p), C.POINTER(C.c_size_t), C.POINTER(_u8p), C.POINTER(C.c_size_t), C.c_int,
@@ -418,6 +430,25 @@ def index_info(index):
                             wrapper_bit=si.wrapper_bit, end_bit=si.end_bit, checkpoints=cp))
     return dict(interval=h.interval, serial_only=bool(h.serial_only), nbytes=h.container_bytes, W=h.width, H=h.height, K=h.K,
                 bs=h.block_size, streams=streams)
+
+
+def _window_parse(fn, head, buf, idx, rect, parse_all):
+    _, _, K, _ = container_info(buf)
+    rc = MpcRect(*[int(v) for v in rect])
+    ranges = np.zeros((3 * K, 2), np.uint64)
+    out, n, route = _u16p(), C.c_size_t(0), C.c_int(-1)
+    _check(fn(*head, buf.ctypes.data_as(_u8p), buf.size, idx.ctypes.data_as(_u8p), idx.size, C.byref(rc), 1 if parse_all else 0, C.byref(out),
+              C.byref(n), ranges.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(route)))
+    return _take_u16(load_library(), out, n), ranges, route.value
+
+
+def parse_container_window_by_index(blob, index, rect, parse_all=False):
+    """mpc_parse_container_window_by_index: the windowed parse on the host for the pixel rectangle rect = (x, y, width, height) ->
+    (symbols, ranges, route): the lengths stream whole, then of each of the 6K streams the expanded symbols [r0, r1) (run lengths
+    undone, step-0 coefficients summed); ranges[3K, 2] = (r0, r1) per (channel, step); route 0 = by the index, 1 = the index
+    was refused and the serial parse gave the result."""
+    buf, idx = np.frombuffer(blob, np.uint8), np.frombuffer(index, np.uint8)
+    return _window_parse(load_library().mpc_parse_container_window_by_index, (), buf, idx, rect, parse_all)
 
 
 def parse_container_by_index(blob, index):
@@ -855,6 +886,53 @@ class CompressionContext:
         torch.cuda.synchronize(self.device)                      # `out` may still be being written by the caller's streams
         _check(self.L.mpc_decode_images_indexed_device(self.h, ptrs, sizes, iptrs, isizes, n, d_ptrs, caps, W, H, routes))
         return [out[i].view(-1)[:3 * W[i] * H[i]].view(H[i], W[i], 3) for i in range(n)], list(routes)
+
+    @staticmethod
+    def _rects(rects, n):
+        if len(rects) != n:
+            raise ValueError("one rectangle (x, y, width, height) per container")
+        return (MpcRect * n)(*[MpcRect(*[int(v) for v in r]) for r in rects])
+
+    def decode_regions(self, blobs, indexes, rects, parse_all=False):
+        """mpc_decode_regions_indexed: the pixel rectangle rects[f] = (x, y, width, height) of every frame, through the frame's
+        seek index (None = without) -> (frames, routes): uint8 [height, width, 3] arrays, routes[f] 0 = only the rectangle's window
+        of the streams was parsed and reconstructed, 1 = the whole frame by the serial route, cropped.  parse_all: every chunk of
+        every stream is parsed (MPC_REGION_PARSE_ALL: the index is then a hint only, as for a whole frame)."""
+        bufs, ptrs, sizes = self._containers(blobs)
+        n = len(bufs)
+        ibufs, iptrs, isizes = self._indexes(indexes, n)
+        rc = self._rects(rects, n)
+        outs, routes = (_u8p * n)(), (C.c_int * n)()
+        _check(self.L.mpc_decode_regions_indexed(self.h, ptrs, sizes, iptrs, isizes, rc, n, 1 if parse_all else 0, outs, routes))
+        return [_take_view(self.L, outs[i], C.c_size_t(3 * rc[i].width * rc[i].height)).reshape(rc[i].height, rc[i].width, 3)
+                for i in range(n)], list(routes)
+
+    def decode_regions_device(self, blobs, indexes, rects, parse_all=False, out=None):
+        """mpc_decode_regions_indexed_device: the same with the pixels left on the context's device.  out: a list of contiguous
+        uint8 torch tensors there, each of at least 3 * width * height elements of its rectangle (bytes behind that are left
+        alone); None = allocated here.  Returns (frames, routes), the frames uint8 [height, width, 3] tensors."""
+        import torch
+        bufs, ptrs, sizes = self._containers(blobs)
+        n = len(bufs)
+        ibufs, iptrs, isizes = self._indexes(indexes, n)
+        rc = self._rects(rects, n)
+        if out is None:
+            out = [torch.empty(3 * max(r.width, 1) * max(r.height, 1), dtype=torch.uint8, device=f"cuda:{self.device}") for r in rc]
+        if len(out) != n or any(t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous() for t in out):
+            raise ValueError("out: one contiguous uint8 device tensor per container")
+        d_ptrs = (C.c_void_p * n)(*[C.c_void_p(t.data_ptr()) for t in out])
+        caps = (C.c_size_t * n)(*[t.numel() for t in out])
+        routes = (C.c_int * n)()
+        torch.cuda.synchronize(self.device)                      # `out` may still be being written by the caller's streams
+        _check(self.L.mpc_decode_regions_indexed_device(self.h, ptrs, sizes, iptrs, isizes, rc, n, 1 if parse_all else 0, d_ptrs, caps,
+                                                        routes))
+        return [out[i].view(-1)[:3 * rc[i].width * rc[i].height].view(rc[i].height, rc[i].width, 3) for i in range(n)], list(routes)
+
+    def parse_container_window_device(self, blob, index, rect, parse_all=False):
+        """mpc_parse_container_window_device: parse_container_window_by_index with the device's lengths parse, ranks, windowed
+        parse and windowed unpack -> (symbols, ranges, route)."""
+        buf, idx = np.frombuffer(blob, np.uint8), np.frombuffer(index, np.uint8)
+        return _window_parse(self.L.mpc_parse_container_window_device, (self.h,), buf, idx, rect, parse_all)
 
     def parse_container_device(self, blob, index):
         """mpc_parse_container_device: parse_container_by_index with the chunks decoded on the device (the decoder's own

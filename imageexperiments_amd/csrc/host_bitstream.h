@@ -175,6 +175,25 @@ std::vector<size_t> expected_sizes(const std::vector<uint16_t>& lengths, int K);
 bool read_compressed_coded_by_index(const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes, CodedStreams& out,
                                     int* route);
 
+// ---- a pixel rectangle of a frame through the index ("Decoder: regions") ----
+// The tiles a rectangle touches: the grid [tx0, tx1) x [ty0, ty1), inside the contiguous tile range [t0, t1) of the streams' order
+// (t = tx * tiles_y + ty).  false = the rectangle is empty or not inside the frame
+struct TileWindow {
+    int tx0 = 0, ty0 = 0, tx1 = 0, ty1 = 0, tiles_y = 0;
+    size_t t0 = 0, t1 = 0;
+};
+bool tile_window(int width, int height, int block_size, int x, int y, int w, int h, TileWindow& win);
+// ranges[2 * (ch * K + i)], [+ 1]: the tiles in front of t0 / of t1 whose length, cut to K, exceeds step i -- the positions the
+// window owns in the two streams of that pair.  lengths[3 * tiles]
+void window_ranges(const uint16_t* lengths, int K, size_t t0, size_t t1, uint64_t* ranges);
+// What the device's windowed parse computes, on the host: the lengths whole, then of every one of the 6K streams the EXPANDED symbols
+// [r0, r1) (run lengths undone, step-0 coefficients summed), back to back.  Of a stream that is neither packed nor a step-0
+// coefficient stream only the chunks that hold [r0, r1) are decoded, unless parse_all.  *route = 0: by the index; 1: the index was
+// refused (plan_indexed_parse, a chunk, the lengths, a packed stream's size) and read_compressed gave the result.
+// Returns 0, 1 = invalid data (read_compressed's verdict), 2 = the rectangle is empty or not inside the frame
+int read_window_by_index(const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes, int x, int y, int w, int h,
+                         bool parse_all, std::vector<uint16_t>& symbols, std::vector<uint64_t>& ranges, int* route);
+
 // The same index from what an encoder holds when it has just written the container, without parsing anything: the plans of
 // plan_stream, where each stream's codes begin, and the bit of every interval-th coded symbol as the code writer passed it.
 struct StreamPlan;                                  // below

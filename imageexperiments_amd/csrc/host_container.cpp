@@ -701,6 +701,124 @@ bool read_compressed_coded_by_index(const uint8_t* bytes, size_t nbytes, const u
     return read_compressed_coded(bytes, nbytes, out);
 }
 
+bool tile_window(int width, int height, int block_size, int x, int y, int w, int h, TileWindow& win) {
+    if (width < 1 || height < 1 || block_size < 1 || x < 0 || y < 0 || w < 1 || h < 1 || w > width - x || h > height - y) return false;
+    win.tiles_y = (height + block_size - 1) / block_size;
+    win.tx0 = x / block_size;
+    win.ty0 = y / block_size;
+    win.tx1 = (x + w + block_size - 1) / block_size;
+    win.ty1 = (y + h + block_size - 1) / block_size;
+    win.t0 = static_cast<size_t>(win.tx0) * win.tiles_y + win.ty0;
+    win.t1 = static_cast<size_t>(win.tx1 - 1) * win.tiles_y + win.ty1;
+    return true;
+}
+
+void window_ranges(const uint16_t* lengths, int K, size_t t0, size_t t1, uint64_t* ranges) {
+    for (int ch = 0; ch < 3; ++ch) {
+        std::vector<uint64_t> hist(static_cast<size_t>(K) + 1, 0);
+        auto write = [&](int which) {                           // tiles so far with more than i atoms: a suffix sum
+            uint64_t above = 0;
+            for (int i = K - 1; i >= 0; --i) {
+                above += hist[static_cast<size_t>(i) + 1];
+                ranges[2 * (static_cast<size_t>(ch) * K + i) + which] = above;
+            }
+        };
+        for (size_t t = 0; t < t1; ++t) {
+            if (t == t0) write(0);
+            ++hist[std::min<size_t>(lengths[3 * t + ch], static_cast<size_t>(K))];
+        }
+        write(1);                                               // t0 < t1: write(0) has run
+    }
+}
+
+int read_window_by_index(const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes, int x, int y, int w, int h,
+                         bool parse_all, std::vector<uint16_t>& symbols, std::vector<uint64_t>& ranges, int* route) {
+    *route = 1;
+    int width, height, K, block_size;
+    if (!container_info(bytes, nbytes, &width, &height, &K, &block_size)) return 1;
+    TileWindow win;
+    if (!tile_window(width, height, block_size, x, y, w, h, win)) return 2;
+    ranges.assign(6 * static_cast<size_t>(K), 0);
+    // the slices [r0, r1) of expanded streams behind the lengths
+    auto emit = [&](const std::vector<uint16_t>& lengths, const std::function<const uint16_t*(int)>& expanded) {
+        size_t total = lengths.size();
+        for (int p = 0; p < 3 * K; ++p) total += 2 * static_cast<size_t>(ranges[2 * p + 1] - ranges[2 * p]);
+        symbols.clear();
+        symbols.reserve(total);
+        symbols.insert(symbols.end(), lengths.begin(), lengths.end());
+        for (int i = 0; i < 6 * K; ++i) {
+            const uint64_t r0 = ranges[2 * (i / 2)], r1 = ranges[2 * (i / 2) + 1];
+            const uint16_t* src = expanded(i);
+            if (r1 > r0) symbols.insert(symbols.end(), src + r0, src + r1);
+        }
+    };
+    IndexedPlan plan;
+    std::vector<uint16_t> lengths;
+    std::vector<std::vector<uint16_t>> codes;
+    auto by_index = [&]() -> bool {
+        if (!plan_indexed_parse(bytes, nbytes, index, index_bytes, plan)) return false;
+        const ContainerIndex& ix = plan.index;
+        // chunks [c0, c1) of stream j into their places in dst (n_coded symbols; the rest stays zero and is never looked at)
+        auto decode_chunks = [&](size_t j, size_t c0, size_t c1, std::vector<uint16_t>& dst) -> bool {
+            const IndexStream& is = ix.streams[j];
+            const StreamWrapper& wr = plan.wrappers[j];
+            dst.assign(static_cast<size_t>(is.n_coded), 0);
+            const size_t chunks = is.checkpoints.size();
+            for (size_t c = c0; c < c1 && c < chunks; ++c) {
+                const bool last = c + 1 == chunks;
+                const size_t begin = static_cast<size_t>(is.checkpoints[c]);
+                const size_t end = static_cast<size_t>(last ? is.end_bit : is.checkpoints[c + 1]);
+                const size_t first = c * ix.interval, count = std::min<size_t>(ix.interval, dst.size() - first);
+                if (wr.mode == 0 ? !huffman_decode_chunk(wr.cb, bytes, nbytes, begin, end, count, last, dst.data() + first)
+                                 : !golomb_decode_chunk(wr.m, bytes, nbytes, begin, end, count, dst.data() + first))
+                    return false;
+            }
+            return true;
+        };
+        if (!decode_chunks(0, 0, ix.streams[0].checkpoints.size(), lengths)) return false;
+        for (uint16_t length : lengths)
+            if (length > K) return false;
+        const std::vector<size_t> expect = expected_sizes(lengths, K);
+        for (int i = 0; i < 6 * K; ++i)
+            if (expect[i] != ix.streams[static_cast<size_t>(i) + 1].expect) return false;
+        window_ranges(lengths.data(), K, win.t0, win.t1, ranges.data());
+        codes.assign(static_cast<size_t>(6 * K), {});
+        for (int i = 0; i < 6 * K; ++i) {
+            const IndexStream& is = ix.streams[static_cast<size_t>(i) + 1];
+            const bool dc = i % (2 * K) == 1, whole = parse_all || is.packed || dc;
+            const uint64_t r0 = ranges[2 * (i / 2)], r1 = ranges[2 * (i / 2) + 1];
+            const size_t c0 = whole ? 0 : static_cast<size_t>(r0 / ix.interval);
+            const size_t c1 = whole ? is.checkpoints.size() : static_cast<size_t>((r1 + ix.interval - 1) / ix.interval);
+            std::vector<uint16_t>& v = codes[i];
+            if (!decode_chunks(static_cast<size_t>(i) + 1, c0, c1, v)) return false;
+            if (is.packed) {                                    // whole: its size is what the lengths allow, or the serial route decides
+                size_t expanded = 0;
+                if (!rle_decoded_size(v.data(), v.size(), expect[i], &expanded) || expanded != expect[i]) return false;
+                v = rle_decode(v.data(), v.size());
+            }
+            if (v.size() != expect[i]) return false;
+            if (dc) {
+                int32_t acc = 0;
+                for (uint16_t& c : v) {
+                    acc += zigzag_decode(c);
+                    c = static_cast<uint16_t>(acc);
+                }
+            }
+        }
+        return true;
+    };
+    if (by_index()) {
+        *route = 0;
+        emit(lengths, [&](int i) { return codes[i].data(); });
+        return 0;
+    }
+    Streams s;
+    if (!read_compressed(bytes, nbytes, s)) return 1;
+    window_ranges(s.lengths.data(), K, win.t0, win.t1, ranges.data());
+    emit(s.lengths, [&](int i) { return s.codes[i].data(); });
+    return 0;
+}
+
 bool read_compressed(const uint8_t* bytes, size_t nbytes, Streams& s) {
     CodedStreams c;
     if (!read_compressed_coded(bytes, nbytes, c)) return false;

@@ -124,6 +124,14 @@ struct DecodeParams {
     int fast;                        // != 0: FromCoeffsDynamicFast (float)
 };
 int launch_decode(const DictDevice& dict, const DecodeParams& p, void* stream);
+// The same for the tiles a pixel rectangle touches (mp_decode_window_kernel): p.rgb receives the rectangle alone, rect_h rows of
+// rect_w pixels tightly packed; p.counts / p.choices are the whole frame's, of which only the tiles [tx0, tx1) x [ty0, ty1) are read.
+// The caller guarantees 0 <= rect_x, rect_x + rect_w <= p.width, the same for y, and rect_w, rect_h >= 1.
+struct DecodeWindow {
+    int rect_x, rect_y, rect_w, rect_h;
+    int tx0, ty0, tx1, ty1;
+};
+int launch_decode_window(const DictDevice& dict, const DecodeParams& p, const DecodeWindow& w, void* stream);
 
 // distortion (mp_kernels.hip: mp_distortion_kernel): the decode kernel's reconstruction compared with the original frame
 struct DistortionParams {
@@ -208,6 +216,31 @@ int launch_stream_assembly(const StreamArgs& a, void* stream);
 // the decoder's way back: counts + the 6K streams (in `symbols`, container order, DC coefficients already summed) -> records
 // [tiles][3][K], dead steps zero.  Uses a.counts, a.symbols (read), a.block_live and a.sizes (scratch); not a.stream_off / a.dc_tmp
 int launch_stream_gather(const StreamArgs& a, uint32_t* choices, void* stream);
+
+// ---- a pixel rectangle's share of the streams (mpc_decode_regions_indexed) ----
+// The streams are compactions of the records in tile order, so the tiles [t0, t1) own the positions [r0, r1) of stream pair
+// (channel, step): r = the tiles in front with more atoms than the step.  One WindowStream per stream of the 6K, on the device.
+struct WindowStream {
+    unsigned long long r0, r1;          // the window's expanded positions in the stream, r0 <= r1 <= the stream's size by the lengths
+    unsigned c0, c1;                    // the chunks to parse, [r0 / interval, ceil(r1 / interval)) cut to the stream's chunks; a stream
+                                        // that cannot be cut (run-length packed, a step-0 coefficient stream, "parse all"): all of them
+};
+struct UnpackStream;
+struct ParseStream;
+struct WindowArgs {
+    StreamArgs sa;                      // counts, tiles, K; block_live and sizes as the count and scan kernels leave them
+    const UnpackStream* unpack;         // [6K]: which streams are packed
+    const ParseStream* parse;           // [6K + 1]: every stream's chunks
+    unsigned interval;
+    int parse_all;                      // != 0: every stream whole
+    long long t0, t1;                   // 0 <= t0 < t1 <= tiles
+    WindowStream* window;               // out [6K]
+};
+// count + scan over all tiles (cheap; every 1024-tile block's offset in every stream), then the ranks of t0 and t1
+int launch_window_rank(const WindowArgs& w, void* stream);
+// the gather for the blocks that hold the tiles [t0, t1) alone: other tiles' records are not written (nor their symbols read).
+// a.block_live / a.sizes as launch_window_rank leaves them
+int launch_stream_gather_window(const StreamArgs& a, uint32_t* choices, long long t0, long long t1, void* stream);
 // records of the tile rows [row_begin, row_begin + rows) in stripe order -> their places in the whole frame's records
 int launch_interleave_stripe(const uint16_t* part_counts, const uint32_t* part_choices, int tiles_x, int tiles_y, int row_begin, int rows,
                              int K, uint16_t* frame_counts, uint32_t* frame_choices, void* stream);
@@ -239,8 +272,12 @@ struct UnpackArgs {
     int dc_stream[3];                   // the step-0 coefficient streams: 1, 2K + 1, 4K + 1
     unsigned dc_blk_begin[4];           // their blocks of kUnpackBlock expanded symbols: prefix sums of ceil(expect / kUnpackBlock)
     unsigned* dc_part;                  // [dc_blk_begin[3]] scratch: each block's sum of differences
+    const WindowStream* window;         // launch_unpack_window alone: [n_streams], on the device
 };
 int launch_unpack(const UnpackArgs& a, void* stream);                // hipError_t as int
+// the same with the copy of a stream that is neither packed nor a step-0 coefficient stream limited to the blocks that hold its
+// window [r0, r1); packed streams and the DC sums as in launch_unpack
+int launch_unpack_window(const UnpackArgs& a, void* stream);
 
 // ---- the entropy codes of a container parsed on the device, chunk by chunk from a seek index (mp_parse.hip) ----
 constexpr int kParseLutBits = 11;       // the Huffman window, HuffmanCodebook::kLutBits
@@ -285,8 +322,14 @@ struct ParseArgs {
     unsigned* hist;                     // [3][kMaxDeviceK + 1] + 1 scratch: the lengths' histogram per channel; [last]: sizes differ
     int* error;                         // |= 1: a chunk did not decode to exactly its symbols and its end, a length above K,
                                         // or stream sizes other than the index says
+    const WindowStream* window;         // launch_parse_window alone: [n_streams - 1], on the device, for streams 1 .. 6K
+    unsigned group_first;               // ... the first group of its grid: streams[1].group_begin
 };
 int launch_parse(const ParseArgs& a, void* stream);                  // hipError_t as int
+// launch_parse in two halves for a frame of which a window is wanted: the lengths stream's groups with hist / verify / void, and --
+// once launch_window_rank has written a.window -- the 6K streams' groups, of which only the chunks [c0, c1) of each stream are read
+int launch_parse_lengths(const ParseArgs& a, void* stream);
+int launch_parse_window(const ParseArgs& a, void* stream);
 
 // ---- device-side entropy stage (mp_entropy.hip): everything that touches every symbol of the 1 + 6K streams ----
 constexpr int kEntBlock = 4096;         // symbols per scan block

@@ -788,6 +788,31 @@ __global__ __launch_bounds__(64) void mp_decode_kernel(const DictDevice dict, co
     }
 }
 
+// The tiles a pixel rectangle touches, one wave per tile of the grid [tx0, tx1) x [ty0, ty1) at a time (tile columns outer, as the
+// records lie), the same reconstruction; a pixel is stored only if it lies inside the rectangle, at its place in the rectangle's
+// own tightly packed rows.  u - rect_x < rect_w and v - rect_y < rect_h bound every store; the records read are the grid's tiles,
+// which lie inside the frame's (the host derives the grid from a rectangle inside the frame).
+template <class T>
+__global__ __launch_bounds__(64) void mp_decode_window_kernel(const DictDevice dict, const DecodeParams p, const DecodeWindow w)
+{
+    const int lane = threadIdx.x;
+    const int rows = w.ty1 - w.ty0;
+    const long long tiles = (long long)(w.tx1 - w.tx0) * rows;
+    for (long long k = blockIdx.x; k < tiles; k += gridDim.x) {
+        const int tx = w.tx0 + (int)(k / rows), ty = w.ty0 + (int)(k % rows);
+        const long long t = (long long)tx * p.tiles_y + ty;
+        double px_rgb[3];
+        reconstruct_tile_pixel<T>(dict, p.counts, p.choices, p.quant, p.K, t, lane, p.error_flag, px_rgb);
+        const int u = tx * 8 + (lane & 7) - w.rect_x, v = ty * 8 + (lane >> 3) - w.rect_y;
+        if (u >= 0 && u < w.rect_w && v >= 0 && v < w.rect_h) {
+            uint8_t* px = p.rgb + 3 * ((long long)v * w.rect_w + u);
+            px[0] = (uint8_t)px_rgb[0];
+            px[1] = (uint8_t)px_rgb[1];
+            px[2] = (uint8_t)px_rgb[2];
+        }
+    }
+}
+
 // --------------------------------------------------------------------------------------------------
 // distortion: the decoder's reconstruction compared with the original frame instead of stored.  Four waves per
 // workgroup, one tile per wave at a time, LANE = PIXEL as in mp_decode_kernel.  Every lane inside the frame adds the
@@ -988,6 +1013,18 @@ int launch_decode(const DictDevice& dict, const DecodeParams& p, void* stream)
     if (blocks < 1) blocks = 1;
     if (p.fast) hipLaunchKernelGGL(mp_decode_kernel<float>, dim3(blocks), dim3(64), 0, (hipStream_t)stream, dict, p);
     else hipLaunchKernelGGL(mp_decode_kernel<double>, dim3(blocks), dim3(64), 0, (hipStream_t)stream, dict, p);
+    return (int)hipGetLastError();
+}
+
+int launch_decode_window(const DictDevice& dict, const DecodeParams& p, const DecodeWindow& w, void* stream)
+{
+    if (w.tx0 < 0 || w.ty0 < 0 || w.tx0 >= w.tx1 || w.ty0 >= w.ty1 || w.tx1 > p.tiles_x || w.ty1 > p.tiles_y || w.rect_w < 1 || w.rect_h < 1 ||
+        w.rect_x < 0 || w.rect_y < 0)
+        return (int)hipErrorInvalidValue;
+    const long long tiles = (long long)(w.tx1 - w.tx0) * (w.ty1 - w.ty0);
+    const unsigned blocks = (unsigned)(tiles < 16384 ? tiles : 16384);
+    if (p.fast) hipLaunchKernelGGL(mp_decode_window_kernel<float>, dim3(blocks), dim3(64), 0, (hipStream_t)stream, dict, p, w);
+    else hipLaunchKernelGGL(mp_decode_window_kernel<double>, dim3(blocks), dim3(64), 0, (hipStream_t)stream, dict, p, w);
     return (int)hipGetLastError();
 }
 

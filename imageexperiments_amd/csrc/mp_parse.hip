@@ -146,24 +146,38 @@ __device__ __forceinline__ bool golomb_one(unsigned m, unsigned b, unsigned limi
 }
 }  // namespace
 
+// kWindow (launch_parse_window): the grid is the 6K streams' groups, the first of them a.group_first, and of stream s only the
+// chunks [c0, c1) of a.window[s - 1] are wanted (mp_window_rank_kernel wrote them, cut to the stream's chunks; they are cut again
+// here).  A group that holds none of them leaves before it fills its table; in a group that straddles the range the chunks outside
+// it are what chunks behind the stream's last are: no lane reads them, no row of theirs is written.  Positions are the whole
+// frame's, so the symbols of unparsed chunks are simply never written.
+template <bool kWindow>
 __global__ __launch_bounds__(64) void mp_parse_kernel(const ParseArgs a)
 {
     __shared__ uint32_t lut[kLutSize];
     __shared__ uint16_t stage[kParseGroup * kRow];
-    const unsigned g = blockIdx.x;                                  // < n_groups (the grid)
+    const unsigned g = kWindow ? blockIdx.x + a.group_first : blockIdx.x;     // < n_groups (the grid)
     const int lane = threadIdx.x;
-    const ParseStream st = a.streams[stream_of_group(a, g)];
+    const int si = stream_of_group(a, g);
+    const ParseStream st = a.streams[si];
     const bool golomb = (st.flags & kParseGolomb) != 0u, lengths = (st.flags & kParseLengths) != 0u;
     const unsigned long long interval = a.interval;
     const unsigned long long j0 = (unsigned long long)(g - st.group_begin) * kParseGroup;     // < n_chunks: the stream has ceil(n_chunks / 64) groups
+    unsigned long long c0 = 0, c1 = st.n_chunks;
+    if (kWindow) {                                                  // group_first = streams[1].group_begin: si >= 1
+        const WindowStream win = a.window[si - 1];
+        c0 = win.c0;
+        c1 = win.c1 < st.n_chunks ? win.c1 : st.n_chunks;
+        if (j0 + kParseGroup <= c0 || j0 >= c1) return;             // the whole wave
+    }
     // chunk j of the stream: symbols [j * interval, j * interval + rows(j))
     auto symbols_of = [&](unsigned long long j) -> unsigned {
-        if (j >= st.n_chunks) return 0u;
+        if (j >= c1 || j < c0) return 0u;
         const unsigned long long rest = st.n_coded - j * interval;  // > 0: n_chunks = ceil(n_coded / interval)
         return (unsigned)(rest < interval ? rest : interval);
     };
     const unsigned long long j = j0 + lane;
-    const bool active = j < st.n_chunks;
+    const bool active = j >= c0 && j < c1;
     const bool last = active && j + 1 == st.n_chunks;
     const unsigned n = symbols_of(j);
     if (!golomb) {
@@ -182,7 +196,7 @@ __global__ __launch_bounds__(64) void mp_parse_kernel(const ParseArgs a)
     const unsigned limit = golomb ? (1u << (b + 1u)) - st.m : 0u;
     bool bad = false, beyond_k = false;
     __syncthreads();
-    const unsigned n_first = symbols_of(j0);                         // the group's longest chunk: only a stream's last one is shorter
+    const unsigned n_first = symbols_of(j0 < c0 ? c0 : j0);           // the group's longest chunk: only a stream's last one is shorter
     uint16_t* const out = lengths ? a.counts : a.coded;
     for (unsigned t0 = 0; t0 < n_first; t0 += kTile) {
         for (unsigned t = 0; t < (unsigned)kTile; ++t) {
@@ -266,19 +280,42 @@ __global__ __launch_bounds__(256) void mp_parse_void_kernel(const ParseArgs a)
         a.counts[i] = 0;
 }
 
-int launch_parse(const ParseArgs& a, void* stream_)
+namespace {
+bool parse_args_ok(const ParseArgs& a) {
+    return !(a.n_streams < 2 || a.n_streams > 6 * kMaxDeviceK + 1 || a.K < 1 || a.K > kMaxDeviceK || a.interval < 1 || a.n_counts < 3);
+}
+// groups [0, lengths_groups) of the grid are the lengths stream's when it is launched alone
+int launch_parse_front(const ParseArgs& a, unsigned groups, hipStream_t s)
 {
-    hipStream_t s = static_cast<hipStream_t>(stream_);
-    if (a.n_streams < 2 || a.n_streams > 6 * kMaxDeviceK + 1 || a.K < 1 || a.K > kMaxDeviceK || a.interval < 1 || a.n_counts < 3)
-        return (int)hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(a.hist, 0, sizeof(unsigned) * (kSizesDiffer + 1), s);
     if (e != hipSuccess) return (int)e;
-    if (a.n_groups) hipLaunchKernelGGL(mp_parse_kernel, dim3(a.n_groups), dim3(64), 0, s, a);
+    if (groups) hipLaunchKernelGGL(mp_parse_kernel<false>, dim3(groups), dim3(64), 0, s, a);
     const unsigned long long want = (a.n_counts + 255) / 256;
     const unsigned blocks = (unsigned)(want < 1024 ? want : 1024);
     hipLaunchKernelGGL(mp_parse_hist_kernel, dim3(blocks), dim3(256), 0, s, a);
     hipLaunchKernelGGL(mp_parse_verify_kernel, dim3(1), dim3(128), 0, s, a);
     hipLaunchKernelGGL(mp_parse_void_kernel, dim3(blocks), dim3(256), 0, s, a);
+    return (int)hipGetLastError();
+}
+}  // namespace
+
+int launch_parse(const ParseArgs& a, void* stream_)
+{
+    if (!parse_args_ok(a)) return (int)hipErrorInvalidValue;
+    return launch_parse_front(a, a.n_groups, static_cast<hipStream_t>(stream_));
+}
+
+int launch_parse_lengths(const ParseArgs& a, void* stream_)
+{
+    if (!parse_args_ok(a) || a.group_first > a.n_groups) return (int)hipErrorInvalidValue;
+    return launch_parse_front(a, a.group_first, static_cast<hipStream_t>(stream_));
+}
+
+int launch_parse_window(const ParseArgs& a, void* stream_)
+{
+    if (!parse_args_ok(a) || a.group_first > a.n_groups || !a.window) return (int)hipErrorInvalidValue;
+    if (a.n_groups > a.group_first)
+        hipLaunchKernelGGL(mp_parse_kernel<true>, dim3(a.n_groups - a.group_first), dim3(64), 0, static_cast<hipStream_t>(stream_), a);
     return (int)hipGetLastError();
 }
 

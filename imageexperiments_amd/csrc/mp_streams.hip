@@ -155,14 +155,21 @@ __global__ __launch_bounds__(kBlockTiles) void mp_stream_scatter_kernel(const St
 // positions -- block offset + rank inside the block -- but the symbols are READ from the 6K streams (`symbols`, laid out as the
 // scatter writes them; the step-0 coefficients already summed up by the host) and every tile's records written whole, dead steps
 // as zeros.
-__global__ __launch_bounds__(kBlockTiles) void mp_stream_gather_kernel(const StreamArgs a, uint32_t* __restrict__ choices)
+// kWindow: a launch over the blocks that hold the tiles [t0, t1), the first of them block_first.  Every tile of those blocks still
+// counts in the ballots (a position is a rank among ALL tiles in front), but only the window's tiles read symbols and write
+// records: the streams outside the window were never parsed.
+template <bool kWindow>
+__global__ __launch_bounds__(kBlockTiles) void mp_stream_gather_kernel(const StreamArgs a, uint32_t* __restrict__ choices, unsigned block_first,
+                                                                       long long t0, long long t1)
 {
     __shared__ unsigned wave_live[kWavesPerBlock][kMaxDeviceK];
     __shared__ unsigned long long off[6 * kMaxDeviceK + 1];
     stream_layout(a, off);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long long t = (long long)blockIdx.x * kBlockTiles + threadIdx.x;
+    const long long block = kWindow ? (long long)blockIdx.x + block_first : (long long)blockIdx.x;
+    const long long t = block * kBlockTiles + threadIdx.x;
     const bool in = t < a.tiles;
+    const bool wanted = kWindow ? in && t >= t0 && t < t1 : in;
     const unsigned long long below = (1ULL << lane) - 1ULL;
     for (int ch = 0; ch < 3; ++ch) {
         const int c = in ? (int)a.counts[t * 3 + ch] : 0;
@@ -183,15 +190,15 @@ __global__ __launch_bounds__(kBlockTiles) void mp_stream_gather_kernel(const Str
                 if (!live) continue;
                 unsigned before = 0;
                 for (int w = 0; w < wave; ++w) before += wave_live[w][i];
-                if (c > i) {
-                    const unsigned long long pos = (unsigned long long)a.block_live[((long long)blockIdx.x * 3 + ch) * a.K + i] + before +
+                if (c > i && wanted) {
+                    const unsigned long long pos = (unsigned long long)a.block_live[(block * 3 + ch) * a.K + i] + before +
                                                    (unsigned)__popcll(live & below);
                     const unsigned long long od = off[2 * (ch * a.K + i)], oc = off[2 * (ch * a.K + i) + 1];
                     rec[i] = (uint32_t)a.symbols[od + pos] | ((uint32_t)a.symbols[oc + pos] << 16);
                 }
             }
         }
-        if (in) {
+        if (wanted) {
             uint32_t* dst = choices + (t * 3 + ch) * a.K;
             if ((a.K & 3) == 0) {
 #pragma unroll
@@ -204,6 +211,53 @@ __global__ __launch_bounds__(kBlockTiles) void mp_stream_gather_kernel(const Str
             }
         }
     }
+}
+
+// The window of the tiles [t0, t1) in every stream, for a decode of a pixel rectangle (mpc_decode_regions_indexed).  Behind count
+// and scan: block_live holds every 1024-tile block's offset in every stream pair, sizes the pairs' totals.  The rank of an edge t
+// in pair (ch, i) = its block's offset + the tiles of that block in front of t with more than i atoms, by ballots as in the
+// gather; an edge at the frame's end (t1 == tiles, which may lie behind the last block) has the pair's size.  One workgroup does
+// both edges: a block-aligned t0 simply finds no tile in front of it.  Then a thread per stream writes (r0, r1) and the chunks
+// that hold them -- or all chunks of a stream that cannot be cut.  Every value written is bounded here, by the host's n_chunks:
+// the parse kernel trusts nothing else of it.
+__global__ __launch_bounds__(kBlockTiles) void mp_window_rank_kernel(const WindowArgs w)
+{
+    __shared__ unsigned rank[2][3 * kMaxDeviceK];
+    const StreamArgs& a = w.sa;
+    const int lane = threadIdx.x & 63, pairs = 3 * a.K;
+    for (int e = 0; e < 2; ++e) {
+        const long long edge = e ? w.t1 : w.t0;                   // 0 <= edge <= tiles (the host)
+        const bool at_end = edge >= a.tiles;                      // uniform
+        const long long b = at_end ? 0 : edge / kBlockTiles;      // < blocks
+        if ((int)threadIdx.x < pairs) rank[e][threadIdx.x] = at_end ? a.sizes[threadIdx.x] : a.block_live[b * pairs + threadIdx.x];
+        __syncthreads();
+        if (at_end) continue;
+        const long long t = b * kBlockTiles + threadIdx.x;
+        const bool front = t < edge;                              // then t < tiles
+        if (!__ballot(front)) continue;                           // a wave behind the edge adds nothing
+        for (int ch = 0; ch < 3; ++ch) {
+            const int c = front ? min((int)a.counts[t * 3 + ch], a.K) : 0;
+#pragma unroll
+            for (int i = 0; i < kMaxDeviceK; ++i)
+                if (i < a.K) {
+                    const unsigned long long live = __ballot(c > i);
+                    if (lane == 0 && live) atomicAdd(&rank[e][ch * a.K + i], (unsigned)__popcll(live));
+                }
+        }
+    }
+    __syncthreads();
+    const int s = threadIdx.x;                                    // stream 2 * pair + (0 deltaId | 1 intCoeff)
+    if (s >= 2 * pairs) return;
+    const unsigned long long r0 = rank[0][s >> 1], r1 = rank[1][s >> 1] > r0 ? rank[1][s >> 1] : r0;
+    const unsigned n_chunks = w.parse[s + 1].n_chunks;
+    const bool whole = w.parse_all || (w.unpack[s].flags & kUnpackPacked) != 0u || s % (2 * a.K) == 1;
+    const unsigned long long first = r0 / w.interval, behind = (r1 + w.interval - 1) / w.interval;
+    WindowStream out;
+    out.r0 = r0;
+    out.r1 = r1;
+    out.c0 = whole ? 0u : (unsigned)(first < n_chunks ? first : n_chunks);
+    out.c1 = whole ? n_chunks : (unsigned)(behind < n_chunks ? behind : n_chunks);
+    w.window[s] = out;
 }
 
 __global__ __launch_bounds__(256) void mp_stream_dc_kernel(const StreamArgs a)
@@ -258,7 +312,28 @@ int launch_stream_gather(const StreamArgs& a, uint32_t* choices, void* stream_)
     if (blocks < 1 || a.K < 1 || a.K > kMaxDeviceK) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(mp_stream_count_kernel, dim3((unsigned)blocks), dim3(kBlockTiles), 0, s, a);
     hipLaunchKernelGGL(mp_stream_scan_kernel, dim3((unsigned)(3 * a.K)), dim3(64), 0, s, a, blocks);
-    hipLaunchKernelGGL(mp_stream_gather_kernel, dim3((unsigned)blocks), dim3(kBlockTiles), 0, s, a, choices);
+    hipLaunchKernelGGL(mp_stream_gather_kernel<false>, dim3((unsigned)blocks), dim3(kBlockTiles), 0, s, a, choices, 0u, 0LL, 0LL);
+    return (int)hipGetLastError();
+}
+
+int launch_window_rank(const WindowArgs& w, void* stream_)
+{
+    hipStream_t s = static_cast<hipStream_t>(stream_);
+    const StreamArgs& a = w.sa;
+    const int blocks = (int)((a.tiles + kBlockTiles - 1) / kBlockTiles);
+    if (blocks < 1 || a.K < 1 || a.K > kMaxDeviceK || w.interval < 1 || w.t0 < 0 || w.t0 >= w.t1 || w.t1 > a.tiles) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(mp_stream_count_kernel, dim3((unsigned)blocks), dim3(kBlockTiles), 0, s, a);
+    hipLaunchKernelGGL(mp_stream_scan_kernel, dim3((unsigned)(3 * a.K)), dim3(64), 0, s, a, blocks);
+    hipLaunchKernelGGL(mp_window_rank_kernel, dim3(1), dim3(kBlockTiles), 0, s, w);
+    return (int)hipGetLastError();
+}
+
+int launch_stream_gather_window(const StreamArgs& a, uint32_t* choices, long long t0, long long t1, void* stream_)
+{
+    hipStream_t s = static_cast<hipStream_t>(stream_);
+    if (a.K < 1 || a.K > kMaxDeviceK || t0 < 0 || t0 >= t1 || t1 > a.tiles) return (int)hipErrorInvalidValue;
+    const long long first = t0 / kBlockTiles, behind = (t1 + kBlockTiles - 1) / kBlockTiles;
+    hipLaunchKernelGGL(mp_stream_gather_kernel<true>, dim3((unsigned)(behind - first)), dim3(kBlockTiles), 0, s, a, choices, (unsigned)first, t0, t1);
     return (int)hipGetLastError();
 }
 

@@ -238,6 +238,10 @@ __global__ __launch_bounds__(64) void mp_unpack_carry_kernel(const UnpackArgs a)
     }
 }
 
+// kWindow (launch_unpack_window): of a stream that is copied and not summed -- not packed, no step-0 coefficient stream -- only the
+// blocks that hold the window's positions [r0, r1) are copied: coded and expanded positions are the same there, and the rest of
+// the stream may never have been parsed.  (r0, r1) only choose among the blocks; what a block reads and writes is bounded as before.
+template <bool kWindow>
 __global__ __launch_bounds__(kThreads) void mp_unpack_fill_kernel(const UnpackArgs a)
 {
     __shared__ uint16_t sym[kUnpackBlock + 2];
@@ -248,6 +252,11 @@ __global__ __launch_bounds__(kThreads) void mp_unpack_fill_kernel(const UnpackAr
     const int si = stream_of_block(a, b);
     const UnpackStream& st = a.streams[si];
     if (!a.stream_ok[si]) return;                                 // nothing is written for a stream whose size is not the expected one
+    if (kWindow && !(st.flags & kUnpackPacked) && si != a.dc_stream[0] && si != a.dc_stream[1] && si != a.dc_stream[2]) {
+        const WindowStream win = a.window[si];                    // si < n_streams
+        const unsigned long long first = (unsigned long long)(b - st.blk_begin) * kUnpackBlock;
+        if (first + kUnpackBlock <= win.r0 || first >= win.r1) return;       // the whole workgroup
+    }
     const BlockSpan s = load_block(a, st, b, sym);
     if (!(st.flags & kUnpackPacked)) {
         // stream_ok: coded_len == expect, so first + n <= expect and the span ends inside the stream's [out_off, out_off + expect)
@@ -391,18 +400,24 @@ __global__ __launch_bounds__(kThreads) void mp_unpack_dc_scan_kernel(const Unpac
     store_span(a.symbols, st.out_off + first, n, sym);            // this block's own symbols only
 }
 
-int launch_unpack(const UnpackArgs& a, void* stream_)
+namespace {
+template <bool kWindow>
+int launch_unpack_as(const UnpackArgs& a, void* stream_)
 {
     hipStream_t s = static_cast<hipStream_t>(stream_);
-    if (a.n_streams < 1 || a.n_streams > 6 * kMaxDeviceK) return (int)hipErrorInvalidValue;
+    if (a.n_streams < 1 || a.n_streams > 6 * kMaxDeviceK || (kWindow && !a.window)) return (int)hipErrorInvalidValue;
     if (a.n_blocks) hipLaunchKernelGGL(mp_unpack_map_kernel, dim3(a.n_blocks), dim3(kThreads), 0, s, a);
     hipLaunchKernelGGL(mp_unpack_carry_kernel, dim3((unsigned)a.n_streams), dim3(64), 0, s, a);
-    if (a.n_blocks) hipLaunchKernelGGL(mp_unpack_fill_kernel, dim3(a.n_blocks), dim3(kThreads), 0, s, a);
+    if (a.n_blocks) hipLaunchKernelGGL(mp_unpack_fill_kernel<kWindow>, dim3(a.n_blocks), dim3(kThreads), 0, s, a);
     if (a.dc_blk_begin[3]) {
         hipLaunchKernelGGL(mp_unpack_dc_sum_kernel, dim3(a.dc_blk_begin[3]), dim3(kThreads), 0, s, a);
         hipLaunchKernelGGL(mp_unpack_dc_scan_kernel, dim3(a.dc_blk_begin[3]), dim3(kThreads), 0, s, a);
     }
     return (int)hipGetLastError();
 }
+}  // namespace
+
+int launch_unpack(const UnpackArgs& a, void* stream) { return launch_unpack_as<false>(a, stream); }
+int launch_unpack_window(const UnpackArgs& a, void* stream) { return launch_unpack_as<true>(a, stream); }
 
 }  // namespace mpc

@@ -291,8 +291,9 @@ struct DecodeSlot {
     GrowBuffer dev{GrowBuffer::kDevice};
     hipStream_t stream = nullptr;
     hipEvent_t done = nullptr;
-    hipEvent_t stamp[6] = {};                 // MPC_TRACE: before the upload, the unpack, the gather, the pixels' copy, after it;
-                                              // [5]: behind the device parse (a frame with a seek index), in front of the unpack
+    hipEvent_t stamp[7] = {};                 // MPC_TRACE: before the upload, the unpack, the gather, the pixels' copy, after it;
+                                              // [5]: behind the device parse (a frame with a seek index), in front of the unpack;
+                                              // [6]: a window of a frame: behind the lengths stream's parse and the ranks
     ~DecodeSlot() {
         if (stream) (void)hipStreamDestroy(stream);
         if (done) (void)hipEventDestroy(done);
@@ -367,7 +368,7 @@ struct mpc_context {
 // FromCoeffsDynamic + RGBFromYUV for whole tiles on `stream`; d_quant: [3][K] doubles on the device; d_flag: the caller's error
 // word (zeroed on `stream` first, set when a record indexes outside its dictionary)
 mpc_status decode_tiles_on_device(mpc_context* c, const uint16_t* d_counts, const uint32_t* d_choices, const double* d_quant, int K,
-                                  int width, int height, uint8_t* d_rgb, int* d_flag, void* stream);
+                                  int width, int height, uint8_t* d_rgb, int* d_flag, void* stream, const mpc::DecodeWindow* window = nullptr);
 
 // ---- context and tile encode (mpcodec_context.cpp) ----
 mpc::DictDevice dict_device(const mpc_context* c);

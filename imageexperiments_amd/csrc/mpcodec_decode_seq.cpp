@@ -5,7 +5,9 @@
 // rest -- run-length expansion, DC sums -- happens on the device (mp_unpack.hip) in front of the gather and the reconstruction,
 // frames pipelined over slots of their own streams.  A frame that comes with a seek index (mpc_decode_images_indexed*) skips the
 // serial parse: its container's bytes go up as they are and the device undoes the entropy codes chunk by chunk (mp_parse.hip)
-// into the same buffers; whatever makes the index unusable sends the frame down the serial route from the start.
+// into the same buffers; whatever makes the index unusable sends the frame down the serial route from the start.  A call that wants
+// a pixel rectangle of each frame (mpc_decode_regions_indexed*) is one more caller of the same sequence: with an index the window's
+// share of every stage behind the lengths stream (route 0), without one the whole frame by the serial route and a 2-D copy (route 1).
 #include <algorithm>
 #include <atomic>
 #include <climits>
@@ -95,6 +97,8 @@ struct Sequence {
     const uint8_t* const* indexes = nullptr;    // optional, and optional per frame: the seek index of frame f
     const size_t* index_bytes = nullptr;
     int* routes = nullptr;                      // optional: per frame 0 = parsed on the device, 1 = the serial route
+    const mpc_rect* rects = nullptr;            // mpc_decode_regions_indexed*: the rectangle wanted of frame f
+    bool parse_all = false;                     // ... MPC_REGION_PARSE_ALL
     int* width = nullptr;
     int* height = nullptr;
     std::atomic<int> next{0};                   // frames are handed out in order
@@ -105,6 +109,11 @@ struct Sequence {
     mpc_status failed_status = MPC_OK;
     std::string failed_text;
 
+    // the bytes frame f's pixels take at the caller's, the frame being width x height
+    size_t out_bytes(int f, int width, int height) const {
+        if (rects) return static_cast<size_t>(rects[f].width) * static_cast<size_t>(rects[f].height) * 3;
+        return static_cast<size_t>(width) * height * 3;
+    }
     bool failed_before(int f) {
         std::lock_guard<std::mutex> hold(lock);
         return failed_frame < f;
@@ -275,7 +284,9 @@ bool plan_parse(const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_
 // upload_and_unpack's counterpart: the container, the checkpoints and the code tables through the slot's pinned buffer to the
 // device, the parse kernels behind them; they leave the coded streams and the lengths where upload_and_unpack puts them
 // (j.ua.coded, j.d_extra[0]).  j.extra[0] is not used; the unpack kernels are the caller's to launch.  stamp[5]: behind the parse
-mpc_status upload_and_parse(DecodeSlot& slot, UnpackJob& j, const ParsePlan& pp, const uint8_t* bytes, size_t nbytes) {
+// deferred: the parse kernels are the caller's to launch as well, from *deferred (a frame of which a window is wanted)
+mpc_status upload_and_parse(DecodeSlot& slot, UnpackJob& j, const ParsePlan& pp, const uint8_t* bytes, size_t nbytes,
+                            mpc::ParseArgs* deferred = nullptr) {
     const UnpackPlan& plan = *j.plan;
     constexpr size_t kHead = 256;
     const size_t padded = ((nbytes + 3) & ~static_cast<size_t>(3)) + 16;      // a lane's window reads up to 12 bytes behind the last bit
@@ -364,8 +375,43 @@ mpc_status upload_and_parse(DecodeSlot& slot, UnpackJob& j, const ParsePlan& pp,
     HIP_TRY(hipMemsetAsync(j.ua.error, 0, 3 * sizeof(int), st));
     HIP_TRY(hipMemcpyAsync(dbase, j.h_result, upload_bytes, hipMemcpyHostToDevice, st));
     if (j.trace) HIP_TRY(hipEventRecord(slot.stamp[1], st));
+    if (deferred) {
+        *deferred = pa;
+        return MPC_OK;
+    }
     if (const int e = mpc::launch_parse(pa, st); e != 0) return launch_failed(e);
     if (j.trace) HIP_TRY(hipEventRecord(slot.stamp[5], st));
+    return MPC_OK;
+}
+
+// Behind upload_and_parse(deferred) for a window of tiles [t0, t1): the lengths stream's parse with hist / verify / void, count and
+// scan over all tiles, the ranks of t0 and t1 (d_window, on the device: no round trip), the parse of the window's chunks and the
+// unpack of the window's blocks.  sa: block_live and sizes carved, counts and symbols set here.  stamp[6]: behind the ranks,
+// [5]: behind the parse, [2]: behind the unpack
+mpc_status parse_and_unpack_window(DecodeSlot& slot, UnpackJob& j, const ParsePlan& pp, mpc::ParseArgs pa, mpc::StreamArgs& sa,
+                                   mpc::WindowStream* d_window, const mpc::TileWindow& win, bool parse_all) {
+    hipStream_t st = slot.stream;
+    sa.counts = pa.counts;
+    sa.symbols = j.ua.symbols;
+    pa.window = d_window;
+    pa.group_first = pp.streams[1].group_begin;                     // the lengths stream's groups come first
+    if (const int e = mpc::launch_parse_lengths(pa, st); e != 0) return launch_failed(e);
+    mpc::WindowArgs wa{};
+    wa.sa = sa;
+    wa.unpack = j.ua.streams;
+    wa.parse = pa.streams;
+    wa.interval = pa.interval;
+    wa.parse_all = parse_all ? 1 : 0;
+    wa.t0 = static_cast<long long>(win.t0);
+    wa.t1 = static_cast<long long>(win.t1);
+    wa.window = d_window;
+    if (const int e = mpc::launch_window_rank(wa, st); e != 0) return launch_failed(e);
+    if (j.trace) HIP_TRY(hipEventRecord(slot.stamp[6], st));
+    if (const int e = mpc::launch_parse_window(pa, st); e != 0) return launch_failed(e);
+    if (j.trace) HIP_TRY(hipEventRecord(slot.stamp[5], st));
+    j.ua.window = d_window;
+    if (const int e = mpc::launch_unpack_window(j.ua, st); e != 0) return launch_failed(e);
+    if (j.trace) HIP_TRY(hipEventRecord(slot.stamp[2], st));
     return MPC_OK;
 }
 
@@ -386,6 +432,14 @@ mpc_status frame_on_slot(Sequence& q, int f, DecodeSlot& slot, const FrameHead& 
     const int K = s.K;
     const size_t n_tc = s.n_tc, tiles = n_tc / 3;
     const size_t px = static_cast<size_t>(s.width) * s.height * 3;
+    // A rectangle of the frame: with a checked index the window alone (`windowed`), else the whole frame into the slot's own memory
+    // and a 2-D copy (`crop`).  The call has checked the rectangle against the container's header; this is the frame's own.
+    const mpc_rect* rc = q.rects ? &q.rects[f] : nullptr;
+    mpc::TileWindow win;
+    if (rc && !mpc::tile_window(s.width, s.height, c->block_size, rc->x, rc->y, rc->width, rc->height, win))
+        return fail(MPC_ERR_ARGUMENT, "rectangle %dx%d at (%d, %d) in a frame of %dx%d", rc->width, rc->height, rc->x, rc->y, s.width, s.height);
+    const bool windowed = rc && pp, crop = rc && !pp;
+    const size_t out_px = q.out_bytes(f, s.width, s.height);
     // read_compressed_coded refuses any other K; `quant` and UnpackJob::streams are sized by MPC_MAX_K and must not lean on that
     if (K < 1 || K > MPC_MAX_K) return fail(MPC_ERR_BITSTREAM, "Invalid input data");
     double quant[3 * MPC_MAX_K];
@@ -393,12 +447,15 @@ mpc_status frame_on_slot(Sequence& q, int f, DecodeSlot& slot, const FrameHead& 
         for (int i = 0; i < K; ++i) quant[ch * K + i] = static_cast<double>(s.quant[ch][i]);
     mpc::StreamArgs sa{};
     uint32_t* d_choices;
-    uint8_t* d_pixels = nullptr;
+    uint8_t *d_pixels = nullptr, *d_full = nullptr;
+    mpc::WindowStream* d_window = nullptr;
     auto behind_layout = [&](char* base) {                          // behind the unpacked streams: records | the gather's scratch | pixels
         Carve cv{base};
         d_choices = cv.take<uint32_t>(n_tc * K);
         carve_stream_buffers(cv, static_cast<long long>(tiles), K, false, &sa);
-        if (!q.d_rgb) d_pixels = cv.take<uint8_t>(px);
+        if (windowed) d_window = cv.take<mpc::WindowStream>(6 * static_cast<size_t>(K));
+        if (crop) d_full = cv.take<uint8_t>(px);                    // the whole frame, of which the rectangle is copied out
+        else if (!q.d_rgb) d_pixels = cv.take<uint8_t>(out_px);
         return cv.at;
     };
     UnpackJob j;
@@ -412,7 +469,7 @@ mpc_status frame_on_slot(Sequence& q, int f, DecodeSlot& slot, const FrameHead& 
     j.extra[1] = quant;
     j.extra_bytes[1] = sizeof(double) * 3 * static_cast<size_t>(K);
     j.behind_bytes = behind_layout(nullptr);
-    j.result_bytes = q.d_rgb ? 0 : px;
+    j.result_bytes = q.d_rgb ? 0 : out_px;
     // A call of one frame has no other frame's thread to share the cores with: its copies go through the worker pool.  Otherwise
     // every frame's thread copies its own.
     const bool pooled = q.n == 1;
@@ -421,30 +478,49 @@ mpc_status frame_on_slot(Sequence& q, int f, DecodeSlot& slot, const FrameHead& 
     hipStream_t st = slot.stream;
     if (serial) {
         if (const mpc_status us = upload_and_unpack(slot, j); us != MPC_OK) return us;
-    } else {
+    } else if (!windowed) {
         if (const mpc_status us = upload_and_parse(slot, j, *pp, q.bytes[f], q.nbytes[f]); us != MPC_OK) return us;
         if (const int e = mpc::launch_unpack(j.ua, st); e != 0) return launch_failed(e);
         if (trace) HIP_TRY(hipEventRecord(slot.stamp[2], st));
+    } else {
+        mpc::ParseArgs pa{};
+        if (const mpc_status us = upload_and_parse(slot, j, *pp, q.bytes[f], q.nbytes[f], &pa); us != MPC_OK) return us;
+        behind_layout(j.d_behind);
+        if (const mpc_status ws = parse_and_unpack_window(slot, j, *pp, pa, sa, d_window, win, q.parse_all); ws != MPC_OK) return ws;
     }
     stamps[0] = j.staged_ms;
     const uint16_t* counts = static_cast<const uint16_t*>(j.d_extra[0]);
     behind_layout(j.d_behind);
-    if (q.d_rgb) d_pixels = q.d_rgb[f];
+    if (q.d_rgb && !crop) d_pixels = q.d_rgb[f];
     sa.counts = counts;
     sa.symbols = j.ua.symbols;
-    if (const int e = mpc::launch_stream_gather(sa, d_choices, st); e != 0) return launch_failed(e);
+    mpc::DecodeWindow dw{};
+    if (windowed) {
+        dw = mpc::DecodeWindow{rc->x, rc->y, rc->width, rc->height, win.tx0, win.ty0, win.tx1, win.ty1};
+        if (const int e = mpc::launch_stream_gather_window(sa, d_choices, static_cast<long long>(win.t0), static_cast<long long>(win.t1), st); e != 0)
+            return launch_failed(e);
+    } else if (const int e = mpc::launch_stream_gather(sa, d_choices, st); e != 0)
+        return launch_failed(e);
     if (const mpc_status ds = decode_tiles_on_device(c, counts, d_choices, static_cast<const double*>(j.d_extra[1]), K, s.width, s.height,
-                                                     d_pixels, j.ua.error + 1, st);
+                                                     crop ? d_full : d_pixels, j.ua.error + 1, st, windowed ? &dw : nullptr);
         ds != MPC_OK)
         return ds;
     if (trace) HIP_TRY(hipEventRecord(slot.stamp[3], st));
     HIP_TRY(hipMemcpyAsync(j.h_flags, j.ua.error, 3 * sizeof(int), hipMemcpyDeviceToHost, st));
-    if (!q.d_rgb) HIP_TRY(hipMemcpyAsync(j.h_result, d_pixels, px, hipMemcpyDeviceToHost, st));    // the upload has left the buffer: stream order
+    if (crop) {                                                     // rows of the rectangle out of the whole frame's
+        const size_t row = 3 * static_cast<size_t>(rc->width), pitch = 3 * static_cast<size_t>(s.width);
+        const uint8_t* from = d_full + 3 * (static_cast<size_t>(rc->y) * s.width + rc->x);
+        HIP_TRY(hipMemcpy2DAsync(q.d_rgb ? static_cast<void*>(q.d_rgb[f]) : static_cast<void*>(j.h_result), row, from, pitch, row,
+                                 static_cast<size_t>(rc->height), q.d_rgb ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+    } else if (!q.d_rgb)
+        HIP_TRY(hipMemcpyAsync(j.h_result, d_pixels, out_px, hipMemcpyDeviceToHost, st));          // the upload has left the buffer: stream order
     if (trace) HIP_TRY(hipEventRecord(slot.stamp[4], st));
     HIP_TRY(hipEventRecord(slot.done, st));
     HIP_TRY(hipEventSynchronize(slot.done));                        // this frame's work only: no other context's, no other slot's
     stamps[1] = trace_ms();
-    if (pp && j.h_flags[2] != 0) {                                  // a chunk, a length or a stream size is not what the index says
+    // a chunk, a length or a stream size is not what the index says; for a window also a packed stream that does not expand to its
+    // size: not every chunk in front of it need have been parsed, so that verdict is the serial route's to give
+    if (pp && (j.h_flags[2] != 0 || (windowed && j.h_flags[0] != 0))) {
         *refused = true;                                            // (the caller passes `refused` whenever it passes `pp`)
         return MPC_OK;
     }
@@ -452,16 +528,16 @@ mpc_status frame_on_slot(Sequence& q, int f, DecodeSlot& slot, const FrameHead& 
     if (j.h_flags[0] != 0) return fail(MPC_ERR_BITSTREAM, "Invalid input data");
     if (j.h_flags[1] != 0) return fail(MPC_ERR_BITSTREAM, "Invalid bitstream");
     if (!q.d_rgb) {
-        uint8_t* out = static_cast<uint8_t*>(std::malloc(px ? px : 1));
+        uint8_t* out = static_cast<uint8_t*>(std::malloc(out_px ? out_px : 1));
         if (!out) return fail(MPC_ERR_ALLOC, "out of memory");
         // a few threads fault the caller's fresh pages in and copy
-        const size_t piece = pooled ? ((px + 15) / 16 + 4095) & ~static_cast<size_t>(4095) : px;
+        const size_t piece = pooled ? ((out_px + 15) / 16 + 4095) & ~static_cast<size_t>(4095) : out_px;
         const auto copy = [&](int k) {
-            const size_t lo = piece * static_cast<size_t>(k), hi = std::min(px, lo + piece);
+            const size_t lo = piece * static_cast<size_t>(k), hi = std::min(out_px, lo + piece);
             std::memcpy(out + lo, j.h_result + lo, hi - lo);
         };
-        if (pooled && px) mpc::parallel_jobs(static_cast<int>((px + piece - 1) / piece), copy);
-        else if (px) copy(0);                                       // the frames' copies run side by side on the call's threads
+        if (pooled && out_px) mpc::parallel_jobs(static_cast<int>((out_px + piece - 1) / piece), copy);
+        else if (out_px) copy(0);                                       // the frames' copies run side by side on the call's threads
         q.rgb[f] = out;
     }
     q.width[f] = s.width;
@@ -470,9 +546,22 @@ mpc_status frame_on_slot(Sequence& q, int f, DecodeSlot& slot, const FrameHead& 
     return MPC_OK;
 }
 
-void trace_frame(int f, int slot_index, DecodeSlot& slot, const double host[6], bool indexed) {
+void trace_frame(int f, int slot_index, DecodeSlot& slot, const double host[6], bool indexed, bool windowed) {
     float dev[4] = {};
     for (int k = 0; k < 4; ++k) (void)hipEventElapsedTime(&dev[k], slot.stamp[k], slot.stamp[k + 1]);
+    if (windowed) {
+        float lengths = 0.f, parse = 0.f, unpack = 0.f;
+        (void)hipEventElapsedTime(&lengths, slot.stamp[1], slot.stamp[6]);
+        (void)hipEventElapsedTime(&parse, slot.stamp[6], slot.stamp[5]);
+        (void)hipEventElapsedTime(&unpack, slot.stamp[5], slot.stamp[2]);
+        std::fprintf(stderr,
+                     "[trace] decode frame %d slot %d, route window: parse: tables %.2f ms | wait for the slot %.2f | staged %.2f | on the "
+                     "device %.2f (upload %.2f, lengths parse + ranks %.2f, windowed parse %.2f, unpack %.2f, gather + reconstruct %.2f, "
+                     "copy-out %.2f) | pixels to the caller %.2f\n",
+                     f, slot_index, host[1] - host[0], host[2] - host[1], host[3] - host[2], host[4] - host[3], dev[0], lengths, parse, unpack,
+                     dev[2], dev[3], host[5] - host[4]);
+        return;
+    }
     if (indexed) {
         float parse = 0.f, unpack = 0.f;
         (void)hipEventElapsedTime(&parse, slot.stamp[1], slot.stamp[5]);
@@ -520,7 +609,7 @@ void parse_worker(Sequence& q) {
                     return fail(MPC_ERR_ARGUMENT, "stream block size %d, context block size %d", s.block_size, c->block_size);
                 return fail(MPC_ERR_BITSTREAM, "Invalid bitstream");
             }
-            if (q.d_rgb && static_cast<size_t>(s.width) * s.height * 3 > q.capacity[f])
+            if (q.d_rgb && !q.rects && q.out_bytes(f, s.width, s.height) > q.capacity[f])
                 return fail(MPC_ERR_ARGUMENT, "capacity %zu for a frame of %dx%d", q.capacity[f], s.width, s.height);
             if (!plan_unpack(s.K, [&](int i) { return static_cast<unsigned long long>(s.codes[i].size()); }, s.packed.data(), nullptr,
                              s.expect.data(), plan))
@@ -540,7 +629,7 @@ void parse_worker(Sequence& q) {
                 HIP_TRY(hipSetDevice(c->device));
                 const mpc::ContainerIndex& x = pp.ip.index;
                 indexed = plan_parse(q.bytes[f], q.nbytes[f], q.indexes[f], q.index_bytes[f], q.n == 1, pp) && x.block_size == c->block_size &&
-                          !(q.d_rgb && static_cast<size_t>(x.width) * x.height * 3 > q.capacity[f]);
+                          !(q.d_rgb && q.out_bytes(f, x.width, x.height) > q.capacity[f]);
                 if (indexed) {
                     head.width = x.width;
                     head.height = x.height;
@@ -579,7 +668,7 @@ void parse_worker(Sequence& q) {
             if (st != MPC_OK) (void)hipStreamSynchronize(slot.stream);             // nothing of this frame is left on the slot's stream
         }
         if (ran && q.routes) q.routes[f] = indexed ? 0 : 1;
-        if (ran && q.tuning.trace) trace_frame(f, slot_index, *c->dec[slot_index], host, indexed);
+        if (ran && q.tuning.trace) trace_frame(f, slot_index, *c->dec[slot_index], host, indexed, indexed && q.rects);
         {
             std::lock_guard<std::mutex> hold(q.lock);
             ++q.slot_uses[slot_index];
@@ -604,14 +693,27 @@ mpc_status ensure_slots(mpc_context* c, int slots) {
 // single: the call is mpc_decode_image's; its error text names no frame
 mpc_status decode_sequence(mpc_context* c, const uint8_t* const* bytes, const size_t* nbytes, int n_frames, uint8_t** rgb,
                            uint8_t* const* d_rgb, const size_t* capacity, int* width, int* height, bool single = false,
-                           const uint8_t* const* indexes = nullptr, const size_t* index_bytes = nullptr, int* routes = nullptr) {
+                           const uint8_t* const* indexes = nullptr, const size_t* index_bytes = nullptr, int* routes = nullptr,
+                           const mpc_rect* rects = nullptr, unsigned region_flags = 0) {
     if (indexes && !index_bytes) return fail(MPC_ERR_ARGUMENT, "null argument");
     if (!c || !bytes || !nbytes || !width || !height || (!rgb && !d_rgb) || (d_rgb && !capacity)) return fail(MPC_ERR_ARGUMENT, "null argument");
     if (n_frames < 1) return fail(MPC_ERR_ARGUMENT, "n_frames must be at least 1");
     if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback");
     for (int f = 0; f < n_frames; ++f)
         if (!bytes[f] || (d_rgb && !d_rgb[f])) return fail(MPC_ERR_ARGUMENT, "frame %d: null argument", f);
-    if (d_rgb)                                                      // before anything is enqueued; a header that does not parse fails in its turn
+    if (rects)                                                      // the same for rectangles: the container's own width and height
+        for (int f = 0; f < n_frames; ++f) {
+            const mpc_rect& r = rects[f];
+            if (r.width < 1 || r.height < 1) return fail(MPC_ERR_ARGUMENT, "frame %d: rectangle %dx%d is empty", f, r.width, r.height);
+            int w, h, K, bs;
+            mpc::TileWindow win;
+            if (mpc::container_info(bytes[f], nbytes[f], &w, &h, &K, &bs) && !mpc::tile_window(w, h, bs, r.x, r.y, r.width, r.height, win))
+                return fail(MPC_ERR_ARGUMENT, "frame %d: rectangle %dx%d at (%d, %d) is not inside a frame of %dx%d", f, r.width, r.height, r.x,
+                            r.y, w, h);
+            if (d_rgb && static_cast<size_t>(r.width) * static_cast<size_t>(r.height) * 3 > capacity[f])
+                return fail(MPC_ERR_ARGUMENT, "frame %d: capacity %zu for a rectangle of %dx%d", f, capacity[f], r.width, r.height);
+        }
+    else if (d_rgb)                                                 // before anything is enqueued; a header that does not parse fails in its turn
         for (int f = 0; f < n_frames; ++f) {
             int w, h, K, bs;
             if (mpc::container_info(bytes[f], nbytes[f], &w, &h, &K, &bs) && static_cast<size_t>(w) * h * 3 > capacity[f])
@@ -633,6 +735,8 @@ mpc_status decode_sequence(mpc_context* c, const uint8_t* const* bytes, const si
     q.indexes = indexes;
     q.index_bytes = index_bytes;
     q.routes = routes;
+    q.rects = rects;
+    q.parse_all = (region_flags & MPC_REGION_PARSE_ALL) != 0;
     if (routes) std::fill(routes, routes + n_frames, 1);
     q.width = width;
     q.height = height;
@@ -702,6 +806,118 @@ mpc_status mpc_decode_images_indexed_device(mpc_context* c, const uint8_t* const
     return guarded([&]() -> mpc_status {
         if (!d_rgb) return fail(MPC_ERR_ARGUMENT, "null argument");
         return decode_sequence(c, bytes, nbytes, n_frames, nullptr, d_rgb, capacity, width, height, false, indexes, index_bytes, routes);
+    });
+}
+
+mpc_status mpc_decode_regions_indexed(mpc_context* c, const uint8_t* const* bytes, const size_t* nbytes, const uint8_t* const* indexes,
+                                      const size_t* index_bytes, const mpc_rect* rects, int n_frames, unsigned flags, uint8_t** rgb,
+                                      int* routes) {
+    return guarded([&]() -> mpc_status {
+        if (!rgb || !rects) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (flags & ~MPC_REGION_PARSE_ALL) return fail(MPC_ERR_ARGUMENT, "flags 0x%x", flags);
+        std::vector<int> wh(2 * static_cast<size_t>(std::max(n_frames, 1)));
+        return decode_sequence(c, bytes, nbytes, n_frames, rgb, nullptr, nullptr, wh.data(), wh.data() + std::max(n_frames, 1), false, indexes,
+                               index_bytes, routes, rects, flags);
+    });
+}
+
+mpc_status mpc_decode_regions_indexed_device(mpc_context* c, const uint8_t* const* bytes, const size_t* nbytes, const uint8_t* const* indexes,
+                                             const size_t* index_bytes, const mpc_rect* rects, int n_frames, unsigned flags,
+                                             uint8_t* const* d_rgb, const size_t* capacity, int* routes) {
+    return guarded([&]() -> mpc_status {
+        if (!d_rgb || !rects) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (flags & ~MPC_REGION_PARSE_ALL) return fail(MPC_ERR_ARGUMENT, "flags 0x%x", flags);
+        std::vector<int> wh(2 * static_cast<size_t>(std::max(n_frames, 1)));
+        return decode_sequence(c, bytes, nbytes, n_frames, nullptr, d_rgb, capacity, wh.data(), wh.data() + std::max(n_frames, 1), false,
+                               indexes, index_bytes, routes, rects, flags);
+    });
+}
+
+mpc_status mpc_parse_container_window_device(mpc_context* c, const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes,
+                                             const mpc_rect* rect, unsigned flags, uint16_t** symbols, size_t* n_symbols, uint64_t* ranges,
+                                             int* route) {
+    return guarded([&]() -> mpc_status {
+        if (!c || !bytes || !index || !rect || !symbols || !n_symbols || !ranges || !route) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (flags & ~MPC_REGION_PARSE_ALL) return fail(MPC_ERR_ARGUMENT, "flags 0x%x", flags);
+        if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback");
+        const bool parse_all = (flags & MPC_REGION_PARSE_ALL) != 0;
+        const auto give = [&](const std::vector<uint16_t>& got) -> mpc_status {
+            uint16_t* out = static_cast<uint16_t*>(std::malloc(got.empty() ? 2 : 2 * got.size()));
+            if (!out) return fail(MPC_ERR_ALLOC, "out of memory");
+            if (!got.empty()) std::memcpy(out, got.data(), 2 * got.size());
+            *symbols = out;
+            *n_symbols = got.size();
+            return MPC_OK;
+        };
+        // every refusal of the index: the host definition's own route 1 (no index at all)
+        const auto serial = [&]() -> mpc_status {
+            std::vector<uint16_t> got;
+            std::vector<uint64_t> r;
+            const int verdict = mpc::read_window_by_index(bytes, nbytes, nullptr, 0, rect->x, rect->y, rect->width, rect->height, parse_all, got, r, route);
+            if (verdict == 1) return fail(MPC_ERR_BITSTREAM, "Invalid input data");
+            if (verdict == 2)
+                return fail(MPC_ERR_ARGUMENT, "rectangle %dx%d at (%d, %d) is empty or not inside the frame", rect->width, rect->height, rect->x, rect->y);
+            std::memcpy(ranges, r.data(), sizeof(uint64_t) * r.size());
+            return give(got);
+        };
+        ParsePlan pp;
+        if (!plan_parse(bytes, nbytes, index, index_bytes, false, pp)) return serial();
+        const mpc::ContainerIndex& x = pp.ip.index;
+        mpc::TileWindow win;
+        if (!mpc::tile_window(x.width, x.height, x.block_size, rect->x, rect->y, rect->width, rect->height, win)) return serial();
+        std::lock_guard<std::recursive_mutex> one_host_call(c->host_calls);
+        HIP_TRY(hipSetDevice(c->device));
+        if (const mpc_status ss = ensure_slots(c, 1); ss != MPC_OK) return ss;
+        DecodeSlot& slot = *c->dec[0];
+        const int K = x.K;
+        const size_t n_counts = pp.n_counts, n_out = pp.unpack.n_symbols, n_streams = 6 * static_cast<size_t>(K);
+        mpc::StreamArgs sa{};
+        mpc::WindowStream* d_window;
+        auto behind_layout = [&](char* base) {
+            Carve cv{base};
+            carve_stream_buffers(cv, static_cast<long long>(pp.ip.tiles), K, false, &sa);
+            d_window = cv.take<mpc::WindowStream>(n_streams);
+            return cv.at;
+        };
+        uint16_t* h_counts;
+        uint16_t* h_symbols;
+        mpc::WindowStream* h_window;
+        auto result_layout = [&](char* base) {
+            Carve cv{base};
+            h_counts = cv.take<uint16_t>(n_counts + 2);
+            h_symbols = cv.take<uint16_t>(n_out + 2);
+            h_window = cv.take<mpc::WindowStream>(n_streams);
+            return cv.at;
+        };
+        UnpackJob j;
+        j.plan = &pp.unpack;
+        j.K = K;
+        j.behind_bytes = behind_layout(nullptr);
+        j.result_bytes = result_layout(nullptr);
+        mpc::ParseArgs pa{};
+        if (const mpc_status us = upload_and_parse(slot, j, pp, bytes, nbytes, &pa); us != MPC_OK) return us;
+        behind_layout(j.d_behind);
+        result_layout(j.h_result);
+        if (const mpc_status ws = parse_and_unpack_window(slot, j, pp, pa, sa, d_window, win, parse_all); ws != MPC_OK) return ws;
+        hipStream_t st = slot.stream;
+        HIP_TRY(hipMemcpyAsync(j.h_flags, j.ua.error, 3 * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(h_counts, pa.counts, sizeof(uint16_t) * n_counts, hipMemcpyDeviceToHost, st));
+        if (n_out) HIP_TRY(hipMemcpyAsync(h_symbols, j.ua.symbols, sizeof(uint16_t) * n_out, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(h_window, d_window, sizeof(mpc::WindowStream) * n_streams, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipEventRecord(slot.done, st));
+        HIP_TRY(hipEventSynchronize(slot.done));
+        if (j.h_flags[2] != 0 || j.h_flags[0] != 0) return serial();
+        // the window's slice of every expanded stream; (r0, r1) are the device's, held to the host's sizes
+        std::vector<uint16_t> got(h_counts, h_counts + n_counts);
+        for (size_t i = 0; i < n_streams; ++i) {
+            const mpc::UnpackStream& us = pp.unpack.table[i];
+            const unsigned long long r1 = std::min<unsigned long long>(h_window[i].r1, us.expect), r0 = std::min<unsigned long long>(h_window[i].r0, r1);
+            got.insert(got.end(), h_symbols + us.out_off + r0, h_symbols + us.out_off + r1);
+            ranges[2 * (i / 2)] = r0;
+            ranges[2 * (i / 2) + 1] = r1;
+        }
+        *route = 0;
+        return give(got);
     });
 }
 

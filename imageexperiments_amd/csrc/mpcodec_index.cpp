@@ -1,5 +1,6 @@
 // mpcodec_index.cpp -- product: the C ABI's host-only entry points of the seek index (host_container.cpp): build one, read one
-// back, and the chunked parse on the host that defines what the device parse (mp_parse.hip) computes.
+// back, and the chunked parses on the host -- of a whole frame, of a pixel rectangle's window -- that define what the device parse
+// (mp_parse.hip) computes.
 #include <cstring>
 
 #include "mpc_internal.h"
@@ -82,6 +83,28 @@ mpc_status mpc_parse_container_by_index(const uint8_t* bytes, size_t nbytes, con
         for (const std::vector<uint16_t>& v : s.codes) add(v);
         *symbols = out;
         *n_symbols = total;
+        return MPC_OK;
+    });
+}
+
+mpc_status mpc_parse_container_window_by_index(const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes,
+                                               const mpc_rect* rect, unsigned flags, uint16_t** symbols, size_t* n_symbols,
+                                               uint64_t* ranges, int* route) {
+    return guarded([&]() -> mpc_status {
+        if (!bytes || !index || !rect || !symbols || !n_symbols || !ranges || !route) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (flags & ~MPC_REGION_PARSE_ALL) return fail(MPC_ERR_ARGUMENT, "flags 0x%x", flags);
+        std::vector<uint16_t> got;
+        std::vector<uint64_t> r;
+        const int verdict = mpc::read_window_by_index(bytes, nbytes, index, index_bytes, rect->x, rect->y, rect->width, rect->height,
+                                                      (flags & MPC_REGION_PARSE_ALL) != 0, got, r, route);
+        if (verdict == 1) return fail(MPC_ERR_BITSTREAM, "Invalid input data");
+        if (verdict == 2) return fail(MPC_ERR_ARGUMENT, "rectangle %dx%d at (%d, %d) is empty or not inside the frame", rect->width, rect->height, rect->x, rect->y);
+        uint16_t* out = static_cast<uint16_t*>(std::malloc(got.empty() ? 2 : 2 * got.size()));
+        if (!out) return fail(MPC_ERR_ALLOC, "out of memory");
+        if (!got.empty()) std::memcpy(out, got.data(), 2 * got.size());
+        std::memcpy(ranges, r.data(), sizeof(uint64_t) * r.size());
+        *symbols = out;
+        *n_symbols = got.size();
         return MPC_OK;
     });
 }

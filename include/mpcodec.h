@@ -458,6 +458,61 @@ mpc_status mpc_decode_images_indexed_device(mpc_context* ctx, const uint8_t* con
                                             const uint8_t* const* indexes, const size_t* index_bytes, int n_frames, uint8_t* const* d_rgb,
                                             const size_t* capacity, int* width, int* height, int* routes);
 
+/* ---- a pixel rectangle of a frame through its seek index ("Decoder: regions") ----
+ * What a viewer or a cache of compressed frames asks for: rects[f] of frame f instead of the whole frame.  rgb[f] (mpc_free) /
+ * d_rgb[f] receive rects[f].height x rects[f].width x 3 bytes, tightly packed; capacity[f] must be at least that, and bytes behind
+ * it are untouched.  A rectangle that is empty or not inside the frame's own width and height is MPC_ERR_ARGUMENT, reported
+ * before anything is enqueued ("frame N: ..."); so is a capacity too small for it.
+ *
+ * The window.  The 6K streams are compactions of the records in tile order, column-major (t = tx * tiles_y + ty).  For a
+ * rectangle (x, y, w, h): tx0 = x / 8, tx1 = ceil((x + w) / 8), ty0 = y / 8, ty1 = ceil((y + h) / 8); its tiles, the grid
+ * [tx0, tx1) x [ty0, ty1), lie in the one contiguous range [t0, t1) = [tx0 * tiles_y + ty0, (tx1 - 1) * tiles_y + ty1), and that
+ * range owns the positions [r0, r1) of the stream pair (channel, step): r = the tiles in front whose length, cut to K, exceeds the
+ * step.  The lengths stream (3 symbols a tile) is parsed whole and gives every r; of a stream that is neither run-length packed
+ * nor difference coded only the chunks [r0 / interval, ceil(r1 / interval)) are parsed, and everything behind the parse -- the
+ * copy of unpacked streams, the gather, the reconstruction, the pixels' way back -- handles the window alone.
+ * The cost follows the rectangle's HORIZONTAL extent: [t0, t1) spans every tile column the rectangle touches from top to bottom
+ * (but for the first and last), so a wide, short strip spans nearly every column's whole range; ranges per tile column are not
+ * built.  Known limit: a run-length packed stream (coded positions are not expanded positions) and the three step-0 coefficient
+ * streams (prefix sums) are parsed and expanded whole, whatever the rectangle.
+ *
+ * What is trusted.  Without MPC_REGION_PARSE_ALL the chunks outside the window are never read, so the whole-frame rule "a hint,
+ * never an authority" cannot hold in full.  What holds instead: (1) every structural check of the whole-frame route is kept --
+ * the index against the container on the host; the lengths stream, every packed stream and the three step-0 coefficient streams
+ * parsed whole and checked as for a whole frame; the stream sizes recomputed from the decoded lengths equal to the index's;
+ * every parsed chunk yielding exactly its symbols and ending on the next checkpoint (on the pseudo-EOF and the stream's end for a
+ * last chunk).  Any failure sends the frame to route 1.  (2) With an index that mpc_container_index or the indexed encoders made
+ * for this container the result is exactly the crop of the full decode; with any other index that passes all of (1) the pixels
+ * are unspecified.  Nothing is read or written out of bounds either way: every bound still comes from the host's tables.
+ * With MPC_REGION_PARSE_ALL every chunk of every stream is parsed, the whole-frame acceptance rule applies unchanged, and only
+ * the stages behind the parse are windowed.  In either mode the reconstruction's "Invalid bitstream" verdict (a record outside
+ * its dictionary) speaks for the window's tiles only.
+ *
+ * routes (NULL, or per frame): 0 = windowed; 1 = the whole frame decoded by the serial route into the decode slot's own device
+ * memory and cropped by a 2-D copy -- no index (indexes == NULL or indexes[f] == NULL), a refused index, "serial only".  Route 1
+ * exists so that the call always answers; statuses and texts of a frame that does not decode are those of mpc_decode_images. */
+typedef struct mpc_rect { int x, y, width, height; } mpc_rect;
+#define MPC_REGION_PARSE_ALL 1u
+mpc_status mpc_decode_regions_indexed(mpc_context* ctx, const uint8_t* const* bytes, const size_t* nbytes, const uint8_t* const* indexes,
+                                      const size_t* index_bytes, const mpc_rect* rects, int n_frames, unsigned flags, uint8_t** rgb,
+                                      int* routes);
+mpc_status mpc_decode_regions_indexed_device(mpc_context* ctx, const uint8_t* const* bytes, const size_t* nbytes,
+                                             const uint8_t* const* indexes, const size_t* index_bytes, const mpc_rect* rects, int n_frames,
+                                             unsigned flags, uint8_t* const* d_rgb, const size_t* capacity, int* routes);
+/* The windowed parse on the host, the role mpc_parse_container_by_index plays for the whole frame: the same plan, the same chunk
+ * decoders and the same acceptance as the device route, checkable without a GPU.  symbols (mpc_free): the lengths whole, then for
+ * each of the 6K streams its EXPANDED symbols [r0, r1) back to back -- run lengths undone, step-0 coefficients summed: a slice of
+ * the whole-frame expansion whichever streams were cut.  ranges[3K][2]: (r0, r1) of every (channel, step) pair.  route as above
+ * (1: mpc_read_compressed gave the result).  MPC_ERR_BITSTREAM for a container mpc_read_compressed refuses, MPC_ERR_ARGUMENT for
+ * a rectangle that is empty or not inside the frame. */
+mpc_status mpc_parse_container_window_by_index(const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes,
+                                               const mpc_rect* rect, unsigned flags, uint16_t** symbols, size_t* n_symbols,
+                                               uint64_t* ranges, int* route);
+/* The device half (upload, lengths parse, rank, windowed parse, windowed unpack), for tests: host buffers in and out. */
+mpc_status mpc_parse_container_window_device(mpc_context* ctx, const uint8_t* bytes, size_t nbytes, const uint8_t* index,
+                                             size_t index_bytes, const mpc_rect* rect, unsigned flags, uint16_t** symbols,
+                                             size_t* n_symbols, uint64_t* ranges, int* route);
+
 /* ---- "-s" patch statistics, Compression.cpp:200-302 ----
  * The reference seeds one std::mt19937, and for every image draws `patches` origins x = rand() % (width - bs),
  * y = rand() % (height - bs), runs CalcMPDynamic on the Y, U and V patch with every quantiser 1.0 and feeds

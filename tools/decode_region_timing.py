@@ -1,0 +1,102 @@
+#!/usr/bin/env python3
+"""decode_region_timing.py -- a pixel rectangle of a frame through its seek index against the whole frame, in one process.
+    python tools/decode_region_timing.py [--workloads raise,1080p] [--frames 1,16] [--rounds 5] [--interval 0] [--once]
+For n distinct containers of a workload (bench.py's: synthetic frames, seeds 12345 + f, encoded with their indexes untimed here):
+    a  decode_images_indexed_device     (the whole frame, pixels left in device memory: the baseline of b)
+    b  decode_regions_device            for a centred 512x512 rectangle, a full-height band 512 wide, and the whole frame
+    c  decode_images_indexed            (the whole frame, host pixels: the baseline of d)
+    d  decode_regions                   for the same three rectangles
+Output buffers are allocated before the clock.  After a warm-up of every shape the legs alternate, `rounds` times; host clock
+around calls that return with the pixels complete.  Prints median and range of ms per frame and each against its baseline.
+--once: a warm-up and one pass of leg b over n frames of the first --frames value with one rectangle (--rect centre, band or
+whole), nothing else (for MPC_TRACE=1)."""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--workloads", default="raise,1080p")
+    ap.add_argument("--frames", default="1,16")
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--interval", type=int, default=0)
+    ap.add_argument("--once", action="store_true")
+    ap.add_argument("--rect", default="centre", choices=["centre", "band", "whole"])
+    args = ap.parse_args()
+    import torch
+    import imageexperiments_amd as ia
+    from bench import WORKLOADS, synth_frame
+    counts = [int(v) for v in args.frames.split(",")]
+    for name in args.workloads.split(","):
+        W, H, K, q = WORKLOADS[name]
+        ctx = ia.create_compression_context(K, 8, q, device=0)
+        n_max = max(counts)
+        pairs = []
+        for lo in range(0, n_max, 8):                              # encoded eight at a time: 8 x 48 MB of frames in host memory
+            pairs += ctx.encode_images_indexed([synth_frame(W, H, 12345 + f) for f in range(lo, min(n_max, lo + 8))], args.interval)
+        containers, indexes = [p[0] for p in pairs], [p[1] for p in pairs]
+        side = min(512, W, H)
+        rects = {"centre": ((W - side) // 2, (H - side) // 2, side, side), "band": ((W - side) // 2, 0, side, H), "whole": (0, 0, W, H)}
+        print(f"# {name}: {W}x{H} K={K} quality {q}, {n_max} containers, {sum(len(b) for b in containers) / n_max / 1e6:.2f} MB each, index "
+              f"{sum(len(x) for x in indexes) / n_max / 1e3:.1f} kB each at interval {ia.index_info(indexes[0])['interval']}", flush=True)
+        out = [torch.empty(3 * W * H, dtype=torch.uint8, device="cuda:0") for _ in range(n_max)]
+
+        def whole_device(n):
+            frames, routes = ctx.decode_images_indexed_device(containers[:n], indexes[:n], out=out[:n])
+            assert not any(routes), routes
+            return frames
+
+        def whole_host(n):
+            frames, routes = ctx.decode_images_indexed(containers[:n], indexes[:n])
+            assert not any(routes), routes
+            return frames
+
+        def region(rect, device):
+            def run(n):
+                if device:
+                    frames, routes = ctx.decode_regions_device(containers[:n], indexes[:n], [rect] * n, out=out[:n])
+                else:
+                    frames, routes = ctx.decode_regions(containers[:n], indexes[:n], [rect] * n)
+                assert not any(routes), routes
+                return frames
+            return run
+        if args.once:
+            n, leg = counts[0], region(rects[args.rect], True)
+            leg(n)
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            leg(n)
+            print(f"{name} b {args.rect} n={n}: {(time.perf_counter() - t) * 1e3 / n:.2f} ms/frame", flush=True)
+            ctx.close()
+            continue
+        legs = [("a", whole_device, "decode_images_indexed_device", "a")]
+        legs += [(f"b {k}", region(r, True), f"decode_regions_device {r[2]}x{r[3]}", "a") for k, r in rects.items()]
+        legs += [("c", whole_host, "decode_images_indexed", "c")]
+        legs += [(f"d {k}", region(r, False), f"decode_regions {r[2]}x{r[3]}", "c") for k, r in rects.items()]
+        for n in counts:
+            for _, fn, _, _ in legs:                                # warm-up of every shape: buffers grown, pages touched
+                fn(n)
+            ms = {key: [] for key, _, _, _ in legs}
+            for _ in range(args.rounds):
+                for key, fn, _, _ in legs:
+                    torch.cuda.synchronize()
+                    t = time.perf_counter()
+                    res = fn(n)
+                    ms[key].append((time.perf_counter() - t) * 1e3 / n)
+                    del res
+            med = {k: statistics.median(v) for k, v in ms.items()}
+            for key, _, label, base in legs:
+                v = ms[key]
+                print(f"{name} n={n:2d} {key:9s} {label:36s} {med[key]:7.2f} ms/frame (range {min(v):.2f} - {max(v):.2f})  "
+                      f"x{med[base] / med[key]:.2f} of {base}", flush=True)
+        ctx.close()
+
+
+if __name__ == "__main__":
+    main()
