@@ -11,6 +11,9 @@
 #                    checkpoints, index_from_plan -- against the parsed index (what tests/test_asan_encode_index.py runs)
 #   make asan-region  tests/cpp/asan_region: the windowed parse on the host (a pixel rectangle through the seek index) on damaged
 #                    indexes, damaged containers and rectangles of every kind (what tests/test_asan_region.py runs)
+#   make asan-index2  tests/cpp/asan_index2: index version 2 on the host -- the aux section's builder and reader, the extension of a
+#                    version-1 index, the windowed parse through the aux entries -- on damaged indexes and damaged containers
+#                    (what tests/test_asan_index2.py runs)
 #
 # GPU AddressSanitizer is not available on the test pool; the kernels are covered by the parity suite instead.
 SAN = -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer
@@ -40,6 +43,12 @@ tests/cpp/asan_region_bin: tests/cpp/asan_region.cpp $(wildcard imageexperiments
 asan-region: tests/cpp/asan_region_bin
 	ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=print_stacktrace=1 MPC_HOST_THREADS=4 ./tests/cpp/asan_region_bin
 
+tests/cpp/asan_index2_bin: tests/cpp/asan_index2.cpp $(wildcard imageexperiments_amd/csrc/host_*.cpp imageexperiments_amd/csrc/host_*.h)
+	g++ -std=c++17 -O1 -g $(SAN) -ffp-contract=off -pthread -Wall -Wno-unused-function tests/cpp/asan_index2.cpp -o $@
+
+asan-index2: tests/cpp/asan_index2_bin
+	ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=print_stacktrace=1 MPC_HOST_THREADS=4 ./tests/cpp/asan_index2_bin
+
 oracle/_build/liboracle_asan.so: $(wildcard oracle/*.c oracle/*.h)
 	mkdir -p oracle/_build
 	gcc -std=c11 -O1 -g $(SAN) -ffp-contract=off -fPIC -shared -o $@ oracle/mpo_*.c -lm
@@ -48,6 +57,6 @@ asan-oracle: oracle/_build/liboracle_asan.so
 	LD_PRELOAD=$$(gcc -print-file-name=libasan.so) ASAN_OPTIONS=detect_leaks=0 ORACLE_LIB=$(CURDIR)/oracle/_build/liboracle_asan.so \
 	    python -m pytest tests/test_oracle_golden.py -x -q -p no:cacheprovider
 
-asan: asan-host asan-index asan-encode-index asan-region asan-oracle
+asan: asan-host asan-index asan-encode-index asan-region asan-index2 asan-oracle
 
-.PHONY: asan asan-host asan-index asan-encode-index asan-region asan-oracle
+.PHONY: asan asan-host asan-index asan-encode-index asan-region asan-index2 asan-oracle

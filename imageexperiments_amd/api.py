@@ -147,6 +147,11 @@ def _bind_bitstream(L):
     L.mpc_decode_image_device.argtypes = [vp, _u8p, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.mpc_unpack_symbol_streams_device.argtypes = [vp, C.c_int, _u16p, _ullp, _u8p, _ullp, C.POINTER(_u16p), C.POINTER(C.c_size_t)]
     L.mpc_container_index.argtypes = [_u8p, C.c_size_t, C.c_int, C.POINTER(_u8p), C.POINTER(C.c_size_t)]
+    L.mpc_container_index2.argtypes = [_u8p, C.c_size_t, C.c_int, C.c_uint, C.POINTER(_u8p), C.POINTER(C.c_size_t)]
+    L.mpc_index_extend.argtypes = [_u8p, C.c_size_t, _u8p, C.c_size_t, C.POINTER(_u8p), C.POINTER(C.c_size_t)]
+    L.mpc_index_version.argtypes = [_u8p, C.c_size_t]
+    L.mpc_index_version.restype = C.c_int
+    L.mpc_index_aux.argtypes = [_u8p, C.c_size_t, C.c_int, C.POINTER(C.c_uint64), _u16p, _u8p, _u16p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.mpc_index_info.argtypes = [_u8p, C.c_size_t, C.POINTER(_IndexHeader)]
     L.mpc_index_stream.argtypes = [_u8p, C.c_size_t, C.c_int, C.POINTER(_IndexStreamInfo), C.POINTER(C.c_uint64), C.c_size_t]
     L.mpc_parse_container_by_index.argtypes = [_u8p, C.c_size_t, _u8p, C.c_size_t, C.POINTER(_u16p), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
@@ -155,6 +160,9 @@ def _bind_bitstream(L):
     _win = [_u8p, C.c_size_t, _u8p, C.c_size_t, _rp, C.c_uint, C.POINTER(_u16p), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
     L.mpc_parse_container_window_by_index.argtypes = _win
     L.mpc_parse_container_window_device.argtypes = [vp] + _win
+    _chunks = [_u8p, C.c_size_t, _u8p, C.c_size_t, _rp, C.c_uint, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
+    L.mpc_window_chunks_by_index.argtypes = _chunks
+    L.mpc_window_chunks_device.argtypes = [vp] + _chunks
     L.mpc_decode_regions_indexed.argtypes = [vp, C.POINTER(_u8p), C.POINTER(C.c_size_t), C.POINTER(_u8p), C.POINTER(C.c_size_t), _rp, C.c_int,
                                              C.c_uint, C.POINTER(_u8p), C.POINTER(C.c_int)]
     L.mpc_decode_regions_indexed_device.argtypes = [vp, C.POINTER(_u8p), C.POINTER(C.c_size_t), C.POINTER(_u8p), C.POINTER(C.c_size_t), _rp,
@@ -401,14 +409,77 @@ def read_compressed(blob, coded=False):
         L.mpc_streams_free(h)
 
 
-def container_index(blob, interval=0):
+def container_index(blob, interval=0, expanded=False):
     """mpc_container_index: the seek index of a container -> bytes.  interval: coded symbols per checkpoint, 32 ... 65536,
-    0 = the library's default.  MpcError(MPC_ERR_BITSTREAM) for whatever read_compressed(coded=True) refuses."""
+    0 = the library's default.  expanded: index version 2 (mpc_container_index2 with MPC_INDEX_EXPANDED), whose aux section lets a
+    region decode cut run-length packed and step-0 coefficient streams too.  MpcError(MPC_ERR_BITSTREAM) for whatever
+    read_compressed(coded=True) refuses."""
     L = load_library()
     buf = np.frombuffer(blob, np.uint8)
     out, n = _u8p(), C.c_size_t(0)
-    _check(L.mpc_container_index(buf.ctypes.data_as(_u8p), buf.size, int(interval), C.byref(out), C.byref(n)))
+    if expanded:
+        _check(L.mpc_container_index2(buf.ctypes.data_as(_u8p), buf.size, int(interval), 1, C.byref(out), C.byref(n)))
+    else:
+        _check(L.mpc_container_index(buf.ctypes.data_as(_u8p), buf.size, int(interval), C.byref(out), C.byref(n)))
     return _take_bytes(L, out, n)
+
+
+def container_index2(blob, interval=0, flags=0):
+    """mpc_container_index2 as it is: flags 0 = container_index's bytes, 1 (MPC_INDEX_EXPANDED) = version 2"""
+    L = load_library()
+    buf = np.frombuffer(blob, np.uint8)
+    out, n = _u8p(), C.c_size_t(0)
+    _check(L.mpc_container_index2(buf.ctypes.data_as(_u8p), buf.size, int(interval), int(flags), C.byref(out), C.byref(n)))
+    return _take_bytes(L, out, n)
+
+
+def index_extend(blob, index):
+    """mpc_index_extend: the version-2 index container_index(blob, interval of `index`, expanded=True) gives, from a version-1
+    index of the container (what the indexed encoders return), without the serial parse -> bytes.  An index that is refused is
+    answered from the serial parse; a version-2 index comes back as a copy."""
+    L = load_library()
+    buf, idx = np.frombuffer(blob, np.uint8), np.frombuffer(index, np.uint8)
+    out, n = _u8p(), C.c_size_t(0)
+    _check(L.mpc_index_extend(buf.ctypes.data_as(_u8p), buf.size, idx.ctypes.data_as(_u8p), idx.size, C.byref(out), C.byref(n)))
+    return _take_bytes(L, out, n)
+
+
+def index_version(index):
+    """mpc_index_version: 1 or 2; 0 = not an index"""
+    idx = np.frombuffer(index, np.uint8)
+    return load_library().mpc_index_version(idx.ctypes.data_as(_u8p), idx.size)
+
+
+def index_aux(index, stream):
+    """mpc_index_aux: the aux entries of stream `stream` (0 = the lengths stream) of a version-2 index -> dict(out uint64, prev
+    uint16, state uint8, dc uint16), one value per checkpoint; empty arrays for a version-1 index or a stream without entries."""
+    L = load_library()
+    idx = np.frombuffer(index, np.uint8)
+    ptr = idx.ctypes.data_as(_u8p)
+    n = C.c_size_t(0)
+    _check(L.mpc_index_aux(ptr, idx.size, int(stream), None, None, None, None, 0, C.byref(n)))
+    out, prev, state, dc = np.zeros(n.value, np.uint64), np.zeros(n.value, np.uint16), np.zeros(n.value, np.uint8), np.zeros(n.value, np.uint16)
+    if n.value:
+        _check(L.mpc_index_aux(ptr, idx.size, int(stream), out.ctypes.data_as(C.POINTER(C.c_uint64)), prev.ctypes.data_as(_u16p),
+                               state.ctypes.data_as(_u8p), dc.ctypes.data_as(_u16p), n.value, C.byref(n)))
+    return dict(out=out, prev=prev, state=state, dc=dc)
+
+
+def _window_chunks(fn, head, blob, index, rect, parse_all):
+    buf, idx = np.frombuffer(blob, np.uint8), np.frombuffer(index, np.uint8)
+    _, _, K, _ = container_info(buf)
+    rc = MpcRect(*[int(v) for v in rect])
+    chunks = np.zeros((6 * K, 2), np.uint64)
+    route = C.c_int(-1)
+    _check(fn(*head, buf.ctypes.data_as(_u8p), buf.size, idx.ctypes.data_as(_u8p), idx.size, C.byref(rc), 1 if parse_all else 0,
+              chunks.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(route)))
+    return chunks, route.value
+
+
+def window_chunks_by_index(blob, index, rect, parse_all=False):
+    """mpc_window_chunks_by_index: the chunks [c0, c1) of each of the 6K streams the windowed parse reads for rect -> (chunks[6K, 2],
+    route); route 1 = nothing is parsed by the index (all zero)."""
+    return _window_chunks(load_library().mpc_window_chunks_by_index, (), blob, index, rect, parse_all)
 
 
 def index_info(index):
@@ -933,6 +1004,10 @@ class CompressionContext:
         parse and windowed unpack -> (symbols, ranges, route)."""
         buf, idx = np.frombuffer(blob, np.uint8), np.frombuffer(index, np.uint8)
         return _window_parse(self.L.mpc_parse_container_window_device, (self.h,), buf, idx, rect, parse_all)
+
+    def window_chunks_device(self, blob, index, rect, parse_all=False):
+        """mpc_window_chunks_device: window_chunks_by_index as the device's rank kernel writes it -> (chunks[6K, 2], route)"""
+        return _window_chunks(self.L.mpc_window_chunks_device, (self.h,), blob, index, rect, parse_all)
 
     def parse_container_device(self, blob, index):
         """mpc_parse_container_device: parse_container_by_index with the chunks decoded on the device (the decoder's own

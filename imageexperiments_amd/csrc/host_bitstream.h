@@ -140,12 +140,24 @@ struct StreamWrapper {                              // what stands in front of a
 // false = what the serial parser refuses at this point (a bad table, M = 0)
 bool read_stream_wrapper(BitReader& in, bool has_flag, StreamWrapper& w);
 
+// Index version 2: what the expansion behind the codes has reached at a checkpoint, for the streams whose coded positions are
+// not their expanded positions (run-length packed) or whose symbols are prefix sums (the step-0 coefficient streams)
+struct IndexAux {
+    uint64_t out = 0;                               // expanded symbols emitted by the coded symbols in front of the checkpoint
+    uint16_t prev = 0;                              // the coded symbol in front of it (0 at the stream's start and if not packed)
+    uint16_t dc = 0;                                // step-0 coefficient stream: low 16 bits of the sum of zigzagDecode over those `out`
+    uint8_t state = 0;                              // runLengthDecode's state the checkpoint's symbol is met in: 0 fresh, 1 value, 2 count
+};
 struct IndexStream {
     uint64_t wrapper_bit = 0, end_bit = 0, n_coded = 0, expect = 0;
     uint32_t packed = 0, mode = 0, m = 0;
     std::vector<uint64_t> checkpoints;              // bit of coded symbol j * interval
+    std::vector<IndexAux> aux;                      // version 2, and only for a packed or step-0 coefficient stream: one per checkpoint
 };
+// stream j of 1 + 6K (the lengths stream first) has aux entries in a version-2 index
+inline bool index_stream_has_aux(size_t j, int K, bool packed) { return j != 0 && (packed || (j - 1) % (2 * static_cast<size_t>(K)) == 1); }
 struct ContainerIndex {
+    uint32_t version = 1;
     uint32_t interval = 0;
     bool serial_only = false;                       // a Huffman table with codes longer than 32 bits: no checkpoints
     uint64_t nbytes = 0;
@@ -153,10 +165,25 @@ struct ContainerIndex {
     std::vector<IndexStream> streams;               // [1 + 6K], the lengths stream first
 };
 constexpr uint32_t kIndexIntervalMin = 32, kIndexIntervalMax = 65536, kIndexIntervalDefault = 128;
-// One serial parse of the container, positions recorded; false = what read_compressed_coded refuses.  interval 0 = the default
-bool build_container_index(const uint8_t* bytes, size_t nbytes, uint32_t interval, std::vector<uint8_t>& blob);
-// the blob alone: magic, version, sizes.  Says nothing about any container
+// One serial parse of the container, positions recorded; false = what read_compressed_coded refuses.  interval 0 = the default.
+// expanded: version 2 (the aux section behind the checkpoints: one more linear pass over the packed and step-0 streams)
+bool build_container_index(const uint8_t* bytes, size_t nbytes, uint32_t interval, std::vector<uint8_t>& blob, bool expanded = false);
+// The version-2 blob build_container_index(..., interval of `index`, expanded) gives, from a version-1 index of this container:
+// the coded streams by read_compressed_coded_by_index (no serial parse unless the index is refused), then the aux pass.  A
+// version-2 index comes back as a copy.  false = what read_compressed_coded refuses, or not an index at all
+bool extend_container_index(const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes, std::vector<uint8_t>& blob);
+// the blob alone: magic, version, sizes; for version 2 the aux section's own consistency (count, out[0] = 0, strictly increasing,
+// <= expect, j * interval for an unpacked stream, state <= 2, entry 0 fresh, unused bits zero).  Says nothing about any container
 bool read_container_index(const uint8_t* index, size_t index_bytes, ContainerIndex& out);
+// A stream's window [r0, r1) of expanded positions in chunks [*c0, *c1): by expanded position where the stream has aux entries (c0
+// the last checkpoint at or in front of r0, c1 the first behind c0 at or behind r1, else all that follow; nothing if r0 == r1),
+// by coded position otherwise
+void window_chunks(const IndexStream& is, uint32_t interval, uint64_t r0, uint64_t r1, size_t* c0, size_t* c1);
+// the chunk range read_window_by_index parses of each of the 6K streams (all chunks where it parses a stream whole): from the
+// lengths stream alone.  Returns 0, 1 = not a container's header, 2 = the rectangle; *route = 1: the index is refused or the
+// lengths are not what it says -- nothing is parsed by it, chunks[] all zero.  chunks[2 * i], [2 * i + 1] = c0, c1 of stream i
+int window_chunks_by_index(const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes, int x, int y, int w, int h,
+                           bool parse_all, std::vector<uint64_t>& chunks, int* route);
 // An index checked against its container as far as the host can without decoding a code (the acceptance rule's first half):
 // the wrappers read from the container, the tables built.  false = the index is not used.
 struct IndexedPlan {
@@ -188,8 +215,11 @@ bool tile_window(int width, int height, int block_size, int x, int y, int w, int
 void window_ranges(const uint16_t* lengths, int K, size_t t0, size_t t1, uint64_t* ranges);
 // What the device's windowed parse computes, on the host: the lengths whole, then of every one of the 6K streams the EXPANDED symbols
 // [r0, r1) (run lengths undone, step-0 coefficients summed), back to back.  Of a stream that is neither packed nor a step-0
-// coefficient stream only the chunks that hold [r0, r1) are decoded, unless parse_all.  *route = 0: by the index; 1: the index was
-// refused (plan_indexed_parse, a chunk, the lengths, a packed stream's size) and read_compressed gave the result.
+// coefficient stream only the chunks that hold [r0, r1) are decoded, unless parse_all.  A packed or step-0 stream is decoded whole
+// with a version-1 index; with version 2 (and not parse_all) only its chunks [c0, c1) of window_chunks, the expansion entered with
+// aux entry c0 and held to aux entry c1 (position, state, the symbol in front, the DC sum; the stream's size where c1 is its end).
+// *route = 0: by the index; 1: the index was refused (plan_indexed_parse, a chunk, the lengths, a packed stream's size, an
+// end-of-range check) and read_compressed gave the result.
 // Returns 0, 1 = invalid data (read_compressed's verdict), 2 = the rectangle is empty or not inside the frame
 int read_window_by_index(const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes, int x, int y, int w, int h,
                          bool parse_all, std::vector<uint16_t>& symbols, std::vector<uint64_t>& ranges, int* route);

@@ -412,10 +412,13 @@ bool read_compressed_coded(const uint8_t* bytes, size_t nbytes, CodedStreams& s)
 //   56 per stream, 64 bytes: u64 wrapper bit, end bit, coded symbols, expected symbols, first checkpoint, checkpoints;
 //      u32 packed, mode, M, 0
 //   then u64 per checkpoint
+// Version 2 is that blob with version = 2, followed by the aux section: u64 aux entries in all, then -- stream behind stream in the
+// blob's order, only for the streams that are run-length packed or step-0 coefficient streams -- 16 bytes per checkpoint:
+//   u64 out (expanded symbols in front of the checkpoint), u64 prev | dc << 16 | state << 32 (IndexAux; the other bits zero)
 // ------------------------------------------------------------------------------------------------
 namespace {
-constexpr uint32_t kIndexMagic = 0x5849504Du, kIndexVersion = 1;
-constexpr size_t kIndexHead = 56, kIndexStream = 64;
+constexpr uint32_t kIndexMagic = 0x5849504Du, kIndexVersion = 1, kIndexVersionExpanded = 2;
+constexpr size_t kIndexHead = 56, kIndexStream = 64, kIndexAux = 16;
 
 void put32(std::vector<uint8_t>& b, uint32_t v) { for (int k = 0; k < 4; ++k) b.push_back(static_cast<uint8_t>(v >> (8 * k))); }
 void put64(std::vector<uint8_t>& b, uint64_t v) { for (int k = 0; k < 8; ++k) b.push_back(static_cast<uint8_t>(v >> (8 * k))); }
@@ -427,7 +430,7 @@ std::vector<uint8_t> index_blob(const ContainerIndex& x) {
     uint64_t total = 0;
     for (const IndexStream& s : x.streams) total += s.checkpoints.size();
     b.reserve(kIndexHead + kIndexStream * x.streams.size() + 8 * total);
-    put32(b, kIndexMagic); put32(b, kIndexVersion); put32(b, x.interval); put32(b, x.serial_only ? 1u : 0u);
+    put32(b, kIndexMagic); put32(b, x.version); put32(b, x.interval); put32(b, x.serial_only ? 1u : 0u);
     put64(b, x.nbytes);
     put32(b, static_cast<uint32_t>(x.width)); put32(b, static_cast<uint32_t>(x.height));
     put32(b, static_cast<uint32_t>(x.K)); put32(b, static_cast<uint32_t>(x.block_size));
@@ -442,7 +445,71 @@ std::vector<uint8_t> index_blob(const ContainerIndex& x) {
     }
     for (const IndexStream& s : x.streams)
         for (uint64_t c : s.checkpoints) put64(b, c);
+    if (x.version == kIndexVersionExpanded) {
+        uint64_t entries = 0;
+        for (const IndexStream& s : x.streams) entries += s.aux.size();
+        put64(b, entries);
+        for (const IndexStream& s : x.streams)
+            for (const IndexAux& a : s.aux) {
+                put64(b, a.out);
+                put64(b, static_cast<uint64_t>(a.prev) | (static_cast<uint64_t>(a.dc) << 16) | (static_cast<uint64_t>(a.state) << 32));
+            }
+    }
     return b;
+}
+
+// runLengthDecode's machine (rle_unpack; mp_unpack.hip's states) one coded symbol on: what it emits.  before: the coded symbol
+// in front of v (looked at in states 1 and 2 only, where there is one)
+struct RunMachine {
+    unsigned state = 0;                                         // 0 fresh, 1 value, 2 count
+    // the symbol emitted and how often
+    void step(uint16_t v, uint16_t before, uint16_t* symbol, uint64_t* copies) {
+        if (state == 2) {
+            *symbol = before;
+            *copies = v;
+            state = 0;
+        } else {
+            *symbol = v;
+            *copies = 1;
+            state = state == 1 && v == before ? 2u : 1u;
+        }
+    }
+};
+
+// The aux entries of one stream: one linear pass over its coded symbols.  The blob is a pure function of (container, interval):
+// nothing but the parsed symbols goes in
+void index_aux_pass(const uint16_t* v, size_t n, uint32_t interval, bool packed, bool dc, std::vector<IndexAux>& aux) {
+    aux.clear();
+    aux.reserve((n + interval - 1) / interval);
+    RunMachine run;
+    uint64_t out = 0;
+    uint32_t sum = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (i % interval == 0) {
+            IndexAux a;
+            a.out = out;
+            a.prev = packed && i ? v[i - 1] : uint16_t(0);
+            a.state = static_cast<uint8_t>(packed ? run.state : 0u);
+            a.dc = dc ? static_cast<uint16_t>(sum) : uint16_t(0);
+            aux.push_back(a);
+        }
+        uint16_t symbol = v[i];
+        uint64_t copies = 1;
+        if (packed) run.step(v[i], i ? v[i - 1] : uint16_t(0), &symbol, &copies);
+        out += copies;
+        if (dc) sum += static_cast<uint32_t>(copies) * static_cast<uint32_t>(zigzag_decode(symbol));
+    }
+}
+
+void index_add_aux(ContainerIndex& x, const CodedStreams& s) {
+    x.version = kIndexVersionExpanded;
+    for (size_t j = 1; j < x.streams.size(); ++j) {
+        IndexStream& is = x.streams[j];
+        is.aux.clear();
+        if (x.serial_only || !index_stream_has_aux(j, x.K, is.packed != 0)) continue;
+        const std::vector<uint16_t>& v = s.codes[j - 1];
+        index_aux_pass(v.data(), v.size(), x.interval, is.packed != 0, (j - 1) % (2 * static_cast<size_t>(x.K)) == 1, is.aux);
+    }
 }
 }  // namespace
 
@@ -463,7 +530,7 @@ bool read_stream_wrapper(BitReader& in, bool has_flag, StreamWrapper& w) {
     return true;
 }
 
-bool build_container_index(const uint8_t* bytes, size_t nbytes, uint32_t interval, std::vector<uint8_t>& blob) {
+bool build_container_index(const uint8_t* bytes, size_t nbytes, uint32_t interval, std::vector<uint8_t>& blob, bool expanded) {
     if (interval == 0) interval = kIndexIntervalDefault;
     CodedStreams s;
     std::vector<size_t> bounds;
@@ -504,6 +571,37 @@ bool build_container_index(const uint8_t* bytes, size_t nbytes, uint32_t interva
     }
     if (x.serial_only)
         for (IndexStream& is : x.streams) is.checkpoints.clear();
+    if (expanded) index_add_aux(x, s);
+    blob = index_blob(x);
+    return true;
+}
+
+bool extend_container_index(const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes, std::vector<uint8_t>& blob) {
+    ContainerIndex x;
+    const bool readable = read_container_index(index, index_bytes, x);
+    if (readable && x.version == kIndexVersionExpanded) {
+        blob.assign(index, index + index_bytes);
+        return true;
+    }
+    // the interval is the index's own word, whatever else of it is damaged; one that is no interval at all: the default
+    uint32_t interval = readable ? x.interval : index && index_bytes >= 12 ? get32(index + 8) : 0u;
+    if (interval < kIndexIntervalMin || interval > kIndexIntervalMax) interval = kIndexIntervalDefault;
+    CodedStreams s;
+    int route = 1;
+    if (!read_compressed_coded_by_index(bytes, nbytes, index, index_bytes, s, &route)) return false;
+    if (route != 0) return build_container_index(bytes, nbytes, interval, blob, true);
+    // An accepted index: its positions and sizes are the serial parse's.  Mode and M are there for readers only and no decode
+    // looks at them, so they are taken from the container's wrappers again
+    for (size_t j = 0; j < x.streams.size(); ++j) {
+        IndexStream& is = x.streams[j];
+        BitReader in(bytes, nbytes);
+        in.set_position(static_cast<size_t>(is.wrapper_bit));
+        StreamWrapper w;
+        if (!read_stream_wrapper(in, j != 0, w)) return build_container_index(bytes, nbytes, interval, blob, true);
+        is.mode = static_cast<uint32_t>(w.mode);
+        is.m = w.m;
+    }
+    index_add_aux(x, s);
     blob = index_blob(x);
     return true;
 }
@@ -558,8 +656,10 @@ bool index_from_plan(uint32_t interval, size_t nbytes, int width, int height, in
 
 bool read_container_index(const uint8_t* index, size_t index_bytes, ContainerIndex& x) {
     if (!index || index_bytes < kIndexHead) return false;
-    if (get32(index) != kIndexMagic || get32(index + 4) != kIndexVersion) return false;
+    const uint32_t version = get32(index + 4);
+    if (get32(index) != kIndexMagic || (version != kIndexVersion && version != kIndexVersionExpanded)) return false;
     x = ContainerIndex();
+    x.version = version;
     x.interval = get32(index + 8);
     const uint32_t flags = get32(index + 12);
     x.serial_only = (flags & 1u) != 0;
@@ -572,7 +672,8 @@ bool read_container_index(const uint8_t* index, size_t index_bytes, ContainerInd
     if (K < 1 || K > 32 || bs < 1 || bs > 8 || width < 1 || height < 1 || width > 0x7FFFFFFFu || height > 0x7FFFFFFFu) return false;
     if (n_streams != 6 * K + 1) return false;
     const size_t fixed = kIndexHead + kIndexStream * n_streams;
-    if (index_bytes < fixed || total != (index_bytes - fixed) / 8 || (index_bytes - fixed) % 8 != 0) return false;
+    if (index_bytes < fixed || (index_bytes - fixed) % 8 != 0) return false;
+    if (version == kIndexVersion ? total != (index_bytes - fixed) / 8 : total >= (index_bytes - fixed) / 8) return false;
     x.width = static_cast<int>(width); x.height = static_cast<int>(height); x.K = static_cast<int>(K); x.block_size = static_cast<int>(bs);
     x.streams.resize(n_streams);
     uint64_t first = 0;
@@ -587,7 +688,36 @@ bool read_container_index(const uint8_t* index, size_t index_bytes, ContainerInd
         for (uint64_t k = 0; k < n_cp; ++k) is.checkpoints[static_cast<size_t>(k)] = get64(index + fixed + 8 * (first + k));
         first += n_cp;
     }
-    return first == total;
+    if (first != total) return false;
+    if (version == kIndexVersion) return true;
+    // The aux section: its size exact, an entry per checkpoint of every stream that has entries, and each stream's own order
+    const uint8_t* at = index + fixed + 8 * static_cast<size_t>(total);          // total < (index_bytes - fixed) / 8: the count is inside
+    const uint64_t entries = get64(at);
+    const size_t room = index_bytes - fixed - 8 * static_cast<size_t>(total) - 8;
+    if (room % kIndexAux != 0 || entries != room / kIndexAux) return false;
+    uint64_t need = 0;
+    for (uint32_t j = 1; j < n_streams; ++j)
+        if (index_stream_has_aux(j, x.K, x.streams[j].packed != 0)) need += x.streams[j].checkpoints.size();
+    if (need != entries) return false;
+    at += 8;
+    for (uint32_t j = 1; j < n_streams; ++j) {
+        IndexStream& is = x.streams[j];
+        if (!index_stream_has_aux(j, x.K, is.packed != 0)) continue;
+        is.aux.resize(is.checkpoints.size());
+        for (size_t k = 0; k < is.aux.size(); ++k, at += kIndexAux) {
+            IndexAux& a = is.aux[k];
+            const uint64_t word = get64(at + 8);
+            a.out = get64(at);
+            a.prev = static_cast<uint16_t>(word);
+            a.dc = static_cast<uint16_t>(word >> 16);
+            if ((word >> 32) > 2u) return false;                // the state, and the unused bits behind it
+            a.state = static_cast<uint8_t>(word >> 32);
+            if (k == 0 ? a.out != 0 || a.state != 0 || a.prev != 0 || a.dc != 0 : a.out <= is.aux[k - 1].out) return false;
+            if (a.out > is.expect || (a.dc != 0 && (j - 1) % (2 * K) != 1)) return false;
+            if (!is.packed && (a.out != static_cast<uint64_t>(k) * x.interval || a.state != 0 || a.prev != 0)) return false;
+        }
+    }
+    return true;
 }
 
 bool plan_indexed_parse(const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes, IndexedPlan& plan, bool pooled) {
@@ -731,6 +861,83 @@ void window_ranges(const uint16_t* lengths, int K, size_t t0, size_t t1, uint64_
     }
 }
 
+void window_chunks(const IndexStream& is, uint32_t interval, uint64_t r0, uint64_t r1, size_t* c0, size_t* c1) {
+    const size_t n = is.checkpoints.size();
+    if (is.aux.size() != n || n == 0) {                         // by coded position
+        *c0 = std::min<uint64_t>(r0 / interval, n);
+        *c1 = std::min<uint64_t>((r1 + interval - 1) / interval, n);
+        return;
+    }
+    *c0 = *c1 = 0;
+    if (r0 >= r1) return;
+    // out[] is strictly increasing from out[0] = 0 (read_container_index)
+    const auto out_less = [](uint64_t r, const IndexAux& a) { return r < a.out; };
+    *c0 = static_cast<size_t>(std::upper_bound(is.aux.begin(), is.aux.end(), r0, out_less) - is.aux.begin()) - 1;
+    const auto less_out = [](const IndexAux& a, uint64_t r) { return a.out < r; };
+    *c1 = static_cast<size_t>(std::lower_bound(is.aux.begin() + static_cast<std::ptrdiff_t>(*c0) + 1, is.aux.end(), r1, less_out) - is.aux.begin());
+}
+
+namespace {
+// chunks [c0, c1) of stream j of a planned index into their places in dst (n_coded symbols; the rest stays zero and is never
+// looked at), each accepted under the per-chunk rule
+bool decode_index_chunks(const IndexedPlan& plan, const uint8_t* bytes, size_t nbytes, size_t j, size_t c0, size_t c1, std::vector<uint16_t>& dst) {
+    const ContainerIndex& ix = plan.index;
+    const IndexStream& is = ix.streams[j];
+    const StreamWrapper& wr = plan.wrappers[j];
+    dst.assign(static_cast<size_t>(is.n_coded), 0);
+    const size_t chunks = is.checkpoints.size();
+    for (size_t c = c0; c < c1 && c < chunks; ++c) {
+        const bool last = c + 1 == chunks;
+        const size_t begin = static_cast<size_t>(is.checkpoints[c]);
+        const size_t end = static_cast<size_t>(last ? is.end_bit : is.checkpoints[c + 1]);
+        const size_t first = c * ix.interval, count = std::min<size_t>(ix.interval, dst.size() - first);
+        if (wr.mode == 0 ? !huffman_decode_chunk(wr.cb, bytes, nbytes, begin, end, count, last, dst.data() + first)
+                         : !golomb_decode_chunk(wr.m, bytes, nbytes, begin, end, count, dst.data() + first))
+            return false;
+    }
+    return true;
+}
+// The window route's first step: the lengths stream whole, no length above K, and the stream sizes they imply equal to the index's
+bool lengths_by_index(const IndexedPlan& plan, const uint8_t* bytes, size_t nbytes, std::vector<uint16_t>& lengths, std::vector<size_t>& expect) {
+    const ContainerIndex& ix = plan.index;
+    if (!decode_index_chunks(plan, bytes, nbytes, 0, 0, ix.streams[0].checkpoints.size(), lengths)) return false;
+    for (uint16_t length : lengths)
+        if (length > ix.K) return false;
+    expect = expected_sizes(lengths, ix.K);
+    for (int i = 0; i < 6 * ix.K; ++i)
+        if (expect[i] != ix.streams[static_cast<size_t>(i) + 1].expect) return false;
+    return true;
+}
+}  // namespace
+
+int window_chunks_by_index(const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes, int x, int y, int w, int h,
+                           bool parse_all, std::vector<uint64_t>& chunks, int* route) {
+    *route = 1;
+    int width, height, K, block_size;
+    if (!container_info(bytes, nbytes, &width, &height, &K, &block_size)) return 1;
+    TileWindow win;
+    if (!tile_window(width, height, block_size, x, y, w, h, win)) return 2;
+    chunks.assign(12 * static_cast<size_t>(K), 0);
+    IndexedPlan plan;
+    if (!plan_indexed_parse(bytes, nbytes, index, index_bytes, plan)) return 0;
+    const ContainerIndex& ix = plan.index;
+    std::vector<uint16_t> lengths;
+    std::vector<size_t> expect;
+    if (!lengths_by_index(plan, bytes, nbytes, lengths, expect)) return 0;
+    std::vector<uint64_t> ranges(6 * static_cast<size_t>(K), 0);
+    window_ranges(lengths.data(), K, win.t0, win.t1, ranges.data());
+    for (int i = 0; i < 6 * K; ++i) {
+        const IndexStream& is = ix.streams[static_cast<size_t>(i) + 1];
+        const bool whole = parse_all || (is.aux.empty() && (is.packed || i % (2 * K) == 1));
+        size_t c0 = 0, c1 = is.checkpoints.size();
+        if (!whole) window_chunks(is, ix.interval, ranges[2 * (i / 2)], ranges[2 * (i / 2) + 1], &c0, &c1);
+        chunks[2 * static_cast<size_t>(i)] = c0;
+        chunks[2 * static_cast<size_t>(i) + 1] = c1;
+    }
+    *route = 0;
+    return 0;
+}
+
 int read_window_by_index(const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes, int x, int y, int w, int h,
                          bool parse_all, std::vector<uint16_t>& symbols, std::vector<uint64_t>& ranges, int* route) {
     *route = 1;
@@ -758,38 +965,63 @@ int read_window_by_index(const uint8_t* bytes, size_t nbytes, const uint8_t* ind
     auto by_index = [&]() -> bool {
         if (!plan_indexed_parse(bytes, nbytes, index, index_bytes, plan)) return false;
         const ContainerIndex& ix = plan.index;
-        // chunks [c0, c1) of stream j into their places in dst (n_coded symbols; the rest stays zero and is never looked at)
         auto decode_chunks = [&](size_t j, size_t c0, size_t c1, std::vector<uint16_t>& dst) -> bool {
-            const IndexStream& is = ix.streams[j];
-            const StreamWrapper& wr = plan.wrappers[j];
-            dst.assign(static_cast<size_t>(is.n_coded), 0);
-            const size_t chunks = is.checkpoints.size();
-            for (size_t c = c0; c < c1 && c < chunks; ++c) {
-                const bool last = c + 1 == chunks;
-                const size_t begin = static_cast<size_t>(is.checkpoints[c]);
-                const size_t end = static_cast<size_t>(last ? is.end_bit : is.checkpoints[c + 1]);
-                const size_t first = c * ix.interval, count = std::min<size_t>(ix.interval, dst.size() - first);
-                if (wr.mode == 0 ? !huffman_decode_chunk(wr.cb, bytes, nbytes, begin, end, count, last, dst.data() + first)
-                                 : !golomb_decode_chunk(wr.m, bytes, nbytes, begin, end, count, dst.data() + first))
-                    return false;
-            }
-            return true;
+            return decode_index_chunks(plan, bytes, nbytes, j, c0, c1, dst);
         };
-        if (!decode_chunks(0, 0, ix.streams[0].checkpoints.size(), lengths)) return false;
-        for (uint16_t length : lengths)
-            if (length > K) return false;
-        const std::vector<size_t> expect = expected_sizes(lengths, K);
-        for (int i = 0; i < 6 * K; ++i)
-            if (expect[i] != ix.streams[static_cast<size_t>(i) + 1].expect) return false;
+        // A stream with aux entries: chunks [c0, c1) alone, the expansion entered at checkpoint c0 in the state, at the position
+        // and with the sum the index names, and held to what it names for checkpoint c1 (to the stream's size where the range
+        // ends with the stream).  dst: `expect` symbols of which [out[c0], the exit position) are filled; [r0, r1) lies inside
+        auto expand_window = [&](const IndexStream& is, int i, uint64_t r0, uint64_t r1, bool dc, std::vector<uint16_t>& dst) -> bool {
+            size_t c0 = 0, c1 = 0;
+            window_chunks(is, ix.interval, r0, r1, &c0, &c1);
+            dst.assign(static_cast<size_t>(is.expect), 0);
+            if (c0 == c1) return true;
+            std::vector<uint16_t> v;
+            if (!decode_chunks(static_cast<size_t>(i) + 1, c0, c1, v)) return false;
+            const bool open_end = c1 == is.checkpoints.size();
+            const size_t s0 = c0 * ix.interval, s1 = open_end ? v.size() : c1 * ix.interval;
+            const IndexAux& in = is.aux[c0];
+            const uint64_t limit = open_end ? is.expect : is.aux[c1].out;          // <= expect (read_container_index)
+            RunMachine run;
+            run.state = is.packed ? in.state : 0u;
+            uint64_t at = in.out;
+            uint32_t sum = in.dc;
+            for (size_t k = s0; k < s1; ++k) {
+                uint16_t symbol = v[k];
+                uint64_t copies = 1;
+                if (is.packed) run.step(v[k], k == s0 ? in.prev : v[k - 1], &symbol, &copies);
+                if (copies > limit - at) return false;          // before anything of it is written
+                for (uint64_t e = 0; e < copies; ++e) {
+                    if (dc) {
+                        sum += static_cast<uint32_t>(zigzag_decode(symbol));
+                        dst[static_cast<size_t>(at + e)] = static_cast<uint16_t>(sum);
+                    } else
+                        dst[static_cast<size_t>(at + e)] = symbol;
+                }
+                at += copies;
+            }
+            if (at != limit) return false;                      // a count left dangling at the stream's end is dropped, as by rle_decode
+            if (open_end) return true;
+            const IndexAux& ex = is.aux[c1];
+            return (is.packed ? run.state : 0u) == ex.state && (is.packed ? v[s1 - 1] : uint16_t(0)) == ex.prev &&
+                   (dc ? static_cast<uint16_t>(sum) : uint16_t(0)) == ex.dc;
+        };
+        std::vector<size_t> expect;
+        if (!lengths_by_index(plan, bytes, nbytes, lengths, expect)) return false;
         window_ranges(lengths.data(), K, win.t0, win.t1, ranges.data());
         codes.assign(static_cast<size_t>(6 * K), {});
         for (int i = 0; i < 6 * K; ++i) {
             const IndexStream& is = ix.streams[static_cast<size_t>(i) + 1];
-            const bool dc = i % (2 * K) == 1, whole = parse_all || is.packed || dc;
+            const bool dc = i % (2 * K) == 1;
             const uint64_t r0 = ranges[2 * (i / 2)], r1 = ranges[2 * (i / 2) + 1];
-            const size_t c0 = whole ? 0 : static_cast<size_t>(r0 / ix.interval);
-            const size_t c1 = whole ? is.checkpoints.size() : static_cast<size_t>((r1 + ix.interval - 1) / ix.interval);
             std::vector<uint16_t>& v = codes[i];
+            if (!parse_all && !is.aux.empty()) {                // version 2: cut by expanded position
+                if (!expand_window(is, i, r0, r1, dc, v)) return false;
+                continue;
+            }
+            const bool whole = parse_all || is.packed || dc;
+            size_t c0 = 0, c1 = is.checkpoints.size();
+            if (!whole) window_chunks(is, ix.interval, r0, r1, &c0, &c1);
             if (!decode_chunks(static_cast<size_t>(i) + 1, c0, c1, v)) return false;
             if (is.packed) {                                    // whole: its size is what the lengths allow, or the serial route decides
                 size_t expanded = 0;

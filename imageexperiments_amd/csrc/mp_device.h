@@ -225,6 +225,17 @@ struct WindowStream {
     unsigned c0, c1;                    // the chunks to parse, [r0 / interval, ceil(r1 / interval)) cut to the stream's chunks; a stream
                                         // that cannot be cut (run-length packed, a step-0 coefficient stream, "parse all"): all of them
 };
+// Index version 2: what a stream with aux entries (run-length packed, or a step-0 coefficient stream) is entered with at chunk c0
+// and held to at chunk c1.  One per stream of the 6K, written by mp_window_rank_kernel<true>, every value cut to the host's sizes.
+constexpr unsigned kSpanCut = 1u;       // WindowSpan::flags: the stream is cut by its aux entries (else: as without them)
+constexpr unsigned kSpanCheck = 2u;     // ... c1 < n_chunks: the exit values are checkpoint c1's (else the stream's end: out1 = expect)
+struct WindowSpan {
+    unsigned long long s0, s1;          // the coded symbols parsed, [c0 * interval, min(c1 * interval, n_coded))
+    unsigned long long out0, out1;      // the expansion's position in front of s0 and behind s1 - 1, out0 <= out1 <= expect
+    unsigned state0, prev0, dc0;        // runLengthDecode's state at s0, coded symbol s0 - 1, the DC sum in front of out0
+    unsigned state1, prev1, dc1;        // what must hold behind s1 - 1 (kSpanCheck)
+    unsigned flags, reserved;
+};
 struct UnpackStream;
 struct ParseStream;
 struct WindowArgs {
@@ -235,6 +246,10 @@ struct WindowArgs {
     int parse_all;                      // != 0: every stream whole
     long long t0, t1;                   // 0 <= t0 < t1 <= tiles
     WindowStream* window;               // out [6K]
+    // index version 2 (span != null; launch_window_rank then runs mp_window_rank_kernel<true>), else unused
+    const unsigned long long* aux;      // the aux entries as in the blob: (out, prev | dc << 16 | state << 32) each, checked by the host
+    const unsigned long long* aux_off;  // [6K]: the stream's first entry (it has n_chunks of them), ~0 = it has none
+    WindowSpan* span;                   // out [6K]
 };
 // count + scan over all tiles (cheap; every 1024-tile block's offset in every stream), then the ranks of t0 and t1
 int launch_window_rank(const WindowArgs& w, void* stream);
@@ -278,6 +293,13 @@ int launch_unpack(const UnpackArgs& a, void* stream);                // hipError
 // the same with the copy of a stream that is neither packed nor a step-0 coefficient stream limited to the blocks that hold its
 // window [r0, r1); packed streams and the DC sums as in launch_unpack
 int launch_unpack_window(const UnpackArgs& a, void* stream);
+// Index version 2: launch_unpack_window where, besides, a stream with kSpanCut is expanded (and summed) from its entry values over
+// the coded symbols [s0, s1) alone and held to its exit values before anything of it is written; a.window and span on the device
+struct UnpackWindowArgs {
+    UnpackArgs a;
+    const WindowSpan* span;             // [n_streams]
+};
+int launch_unpack_window_cut(const UnpackWindowArgs& w, void* stream);
 
 // ---- the entropy codes of a container parsed on the device, chunk by chunk from a seek index (mp_parse.hip) ----
 constexpr int kParseLutBits = 11;       // the Huffman window, HuffmanCodebook::kLutBits

@@ -220,6 +220,12 @@ __global__ __launch_bounds__(kBlockTiles) void mp_stream_gather_kernel(const Str
 // both edges: a block-aligned t0 simply finds no tile in front of it.  Then a thread per stream writes (r0, r1) and the chunks
 // that hold them -- or all chunks of a stream that cannot be cut.  Every value written is bounded here, by the host's n_chunks:
 // the parse kernel trusts nothing else of it.
+//
+// kAux (index version 2): a stream with aux entries -- run-length packed, or a step-0 coefficient stream -- is cut as well, by its
+// EXPANDED positions: c0 = the last checkpoint whose out[] is at or in front of r0, c1 = the first behind c0 whose out[] is at or
+// behind r1, else n_chunks; nothing if r0 == r1.  Two binary searches over the stream's own n_chunks entries, which the host has
+// checked (out[0] = 0, strictly increasing, <= expect); the entry and exit values go to the stream's WindowSpan, cut once more.
+template <bool kAux>
 __global__ __launch_bounds__(kBlockTiles) void mp_window_rank_kernel(const WindowArgs w)
 {
     __shared__ unsigned rank[2][3 * kMaxDeviceK];
@@ -257,6 +263,52 @@ __global__ __launch_bounds__(kBlockTiles) void mp_window_rank_kernel(const Windo
     out.r1 = r1;
     out.c0 = whole ? 0u : (unsigned)(first < n_chunks ? first : n_chunks);
     out.c1 = whole ? n_chunks : (unsigned)(behind < n_chunks ? behind : n_chunks);
+    if (kAux) {
+        WindowSpan sp{};
+        const unsigned long long off = w.aux_off[s];                // s < 6K
+        if (!w.parse_all && off != ~0ull && n_chunks) {
+            // entry j of the stream: aux[2 * (off + j)], [+ 1], j < n_chunks: the host laid n_chunks entries out for it
+            const unsigned long long* e = w.aux + 2 * off;
+            const unsigned long long n_coded = w.parse[s + 1].n_coded, expect = w.parse[s + 1].expect;
+            unsigned c0 = 0, c1 = 0;
+            if (r0 < r1) {
+                unsigned lo = 0, hi = n_chunks;                     // out[lo] <= r0 (out[0] = 0), out[hi] > r0 or hi = n_chunks
+                while (hi - lo > 1) {
+                    const unsigned mid = lo + (hi - lo) / 2;        // 0 < mid < n_chunks
+                    if (e[2 * (unsigned long long)mid] <= r0) lo = mid; else hi = mid;
+                }
+                c0 = lo;
+                hi = n_chunks;                                      // out[lo] < r1 (out[c0] <= r0 < r1), out[hi] >= r1 or hi = n_chunks
+                while (hi - lo > 1) {
+                    const unsigned mid = lo + (hi - lo) / 2;
+                    if (e[2 * (unsigned long long)mid] >= r1) hi = mid; else lo = mid;
+                }
+                c1 = hi;                                            // c0 < c1 <= n_chunks
+            }
+            out.c0 = c0;
+            out.c1 = c1;
+            const unsigned long long s1 = (unsigned long long)c1 * w.interval;
+            sp.s0 = (unsigned long long)c0 * w.interval;           // <= n_coded: c0 < n_chunks
+            sp.s1 = s1 < n_coded ? s1 : n_coded;
+            const unsigned long long o0 = e[2 * (unsigned long long)c0], w0 = e[2 * (unsigned long long)c0 + 1];       // c0 < n_chunks
+            sp.out0 = o0 < expect ? o0 : expect;
+            sp.state0 = (unsigned)(w0 >> 32) < 2u ? (unsigned)(w0 >> 32) : 2u;
+            sp.prev0 = (unsigned)(w0 & 0xFFFFu);
+            sp.dc0 = (unsigned)((w0 >> 16) & 0xFFFFu);
+            sp.out1 = expect;
+            sp.flags = kSpanCut;
+            if (c1 < n_chunks) {
+                const unsigned long long o1 = e[2 * (unsigned long long)c1], w1 = e[2 * (unsigned long long)c1 + 1];
+                sp.out1 = o1 < expect ? o1 : expect;
+                sp.state1 = (unsigned)(w1 >> 32);
+                sp.prev1 = (unsigned)(w1 & 0xFFFFu);
+                sp.dc1 = (unsigned)((w1 >> 16) & 0xFFFFu);
+                sp.flags |= kSpanCheck;
+            }
+            if (sp.out1 < sp.out0) sp.out1 = sp.out0;
+        }
+        w.span[s] = sp;
+    }
     w.window[s] = out;
 }
 
@@ -324,7 +376,11 @@ int launch_window_rank(const WindowArgs& w, void* stream_)
     if (blocks < 1 || a.K < 1 || a.K > kMaxDeviceK || w.interval < 1 || w.t0 < 0 || w.t0 >= w.t1 || w.t1 > a.tiles) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(mp_stream_count_kernel, dim3((unsigned)blocks), dim3(kBlockTiles), 0, s, a);
     hipLaunchKernelGGL(mp_stream_scan_kernel, dim3((unsigned)(3 * a.K)), dim3(64), 0, s, a, blocks);
-    hipLaunchKernelGGL(mp_window_rank_kernel, dim3(1), dim3(kBlockTiles), 0, s, w);
+    if (w.span) {
+        if (!w.aux || !w.aux_off) return (int)hipErrorInvalidValue;
+        hipLaunchKernelGGL(mp_window_rank_kernel<true>, dim3(1), dim3(kBlockTiles), 0, s, w);
+    } else
+        hipLaunchKernelGGL(mp_window_rank_kernel<false>, dim3(1), dim3(kBlockTiles), 0, s, w);
     return (int)hipGetLastError();
 }
 

@@ -400,6 +400,291 @@ __global__ __launch_bounds__(kThreads) void mp_unpack_dc_scan_kernel(const Unpac
     store_span(a.symbols, st.out_off + first, n, sym);            // this block's own symbols only
 }
 
+
+// ------------------------------------------------------------------------------------------------
+// The window of a version-2 index (launch_unpack_window_cut).  A stream with kSpanCut -- run-length packed, or a step-0 coefficient
+// stream -- had only its coded symbols [s0, s1) parsed; the rest of its part of `coded` was never written.  The machine is entered
+// at s0 in state0 at output position out0, the symbol in front of s0 is prev0 (never the memory in front, which nobody parsed), and
+// behind s1 - 1 the position, the state and that symbol must be the index's exit values before anything is written.  Blocks stay
+// the stream's own blocks of 2048 coded symbols, so s0 is in general inside a block: symbols of a block outside [s0, s1) are
+// identity pieces, blocks wholly outside leave at once.  Every bound is the host's: s0 <= s1 <= coded_len and out0 <= out1 <= expect
+// are cut here once more (mp_window_rank_kernel<true> has cut them already); no symbol's value bounds anything.
+// ------------------------------------------------------------------------------------------------
+namespace {
+struct CutRange {
+    unsigned long long s0, s1;      // s0 <= s1 <= coded_len
+    unsigned long long out0, out1;  // out0 <= out1 <= expect
+    bool cut, check;
+};
+__device__ __forceinline__ CutRange cut_range(const WindowSpan& sp, const UnpackStream& st) {
+    CutRange c;
+    c.cut = (sp.flags & kSpanCut) != 0u;
+    c.check = c.cut && (sp.flags & kSpanCheck) != 0u;
+    c.s1 = !c.cut ? st.coded_len : sp.s1 < st.coded_len ? sp.s1 : st.coded_len;
+    c.s0 = !c.cut ? 0ull : sp.s0 < c.s1 ? sp.s0 : c.s1;
+    c.out1 = !c.cut ? st.expect : sp.out1 < st.expect ? sp.out1 : st.expect;
+    c.out0 = !c.cut ? 0ull : sp.out0 < c.out1 ? sp.out0 : c.out1;
+    return c;
+}
+// the block holds none of [s0, s1): the whole workgroup
+__device__ __forceinline__ bool block_outside(unsigned long long first, unsigned long long s0, unsigned long long s1) {
+    return s0 >= s1 || first + kUnpackBlock <= s0 || first >= s1;
+}
+// thread_piece with the symbols outside [s0, s1) as identity pieces and prev0 in front of s0
+__device__ __forceinline__ Piece<unsigned> thread_piece_cut(const BlockSpan& s, const uint16_t* sym, unsigned long long s0, unsigned long long s1,
+                                                            unsigned prev0) {
+    Piece<unsigned> p = identity_piece<unsigned>();
+#pragma unroll
+    for (int k = 0; k < kPerThread; ++k) {
+        const unsigned j = threadIdx.x * kPerThread + k;
+        const unsigned long long pos = s.first + j;
+        if (j < s.n && pos >= s0 && pos < s1) {                   // sym[j], sym[j + 1]: j + 1 <= n <= 2048
+            const unsigned cur = sym[j + 1];
+            const unsigned before = pos == s0 ? prev0 : sym[j];  // pos > s0: symbol pos - 1 was parsed
+            const bool repeat = pos != 0 && cur == before;
+            p = compose(p, Piece<unsigned>{repeat ? kMapRepeat : kMapOther, 1u, 1u, cur});
+        }
+    }
+    return p;
+}
+}  // namespace
+
+__global__ __launch_bounds__(kThreads) void mp_unpack_window_map_kernel(const UnpackWindowArgs w)
+{
+    __shared__ uint16_t sym[kUnpackBlock + 2];
+    __shared__ Piece<unsigned> wave_piece[kWaves];
+    const UnpackArgs& a = w.a;
+    const unsigned b = blockIdx.x;                                // < n_blocks (the grid)
+    const int si = stream_of_block(a, b);
+    const UnpackStream& st = a.streams[si];
+    if (!(st.flags & kUnpackPacked)) return;
+    const WindowSpan sp = w.span[si];                             // si < n_streams
+    const CutRange c = cut_range(sp, st);
+    if (block_outside((unsigned long long)(b - st.blk_begin) * kUnpackBlock, c.s0, c.s1)) return;
+    const BlockSpan s = load_block(a, st, b, sym);                // inside the stream's own part of `coded`, parsed or not
+    Piece<unsigned> whole;
+    block_scan(thread_piece_cut(s, sym, c.s0, c.s1, sp.prev0), wave_piece, &whole);
+    if (threadIdx.x == 0) reinterpret_cast<uint4*>(a.blk_piece)[b] = make_uint4(whole.map, whole.out0, whole.out1, whole.out2);
+}
+
+// one wave per stream: the blocks that hold [s0, s1) composed from (state0, out0), and the exit checks
+__global__ __launch_bounds__(64) void mp_unpack_window_carry_kernel(const UnpackWindowArgs w)
+{
+    const UnpackArgs& a = w.a;
+    const int si = blockIdx.x, lane = threadIdx.x;                // si < n_streams (the grid)
+    const UnpackStream& st = a.streams[si];
+    const unsigned nb = a.streams[si + 1].blk_begin - st.blk_begin;
+    const WindowSpan sp = w.span[si];
+    const CutRange c = cut_range(sp, st);
+    bool ok;
+    if (!(st.flags & kUnpackPacked)) {
+        ok = st.coded_len == st.expect;
+    } else if (c.s0 >= c.s1) {
+        ok = c.cut || st.expect == 0;                             // nothing of the stream was parsed, nothing of it is written
+    } else {
+        unsigned state = c.cut ? (sp.state0 < 2u ? sp.state0 : 2u) : 0u;
+        unsigned long long run = c.out0;
+        // blocks [k0, k1) hold [s0, s1); k1 <= nb: s1 <= coded_len and the stream has ceil(coded_len / 2048) blocks
+        const unsigned long long k0 = c.s0 / kUnpackBlock, k1 = (c.s1 + kUnpackBlock - 1) / kUnpackBlock;
+        for (unsigned long long base = k0; base < k1 && base < nb; base += 64) {
+            const unsigned long long k = base + lane;
+            const bool mine_in = k < k1 && k < nb;
+            Piece<unsigned long long> mine = identity_piece<unsigned long long>();
+            if (mine_in) {                                        // blk_begin + k < the next stream's blk_begin <= n_blocks
+                const uint4 v = reinterpret_cast<const uint4*>(a.blk_piece)[st.blk_begin + k];
+                mine = Piece<unsigned long long>{v.x, v.y, v.z, v.w};
+            }
+            Piece<unsigned long long> before;
+            const Piece<unsigned long long> incl = wave_scan(mine, lane, &before);
+            if (mine_in) {
+                a.blk_entry[st.blk_begin + k] = leave(before.map, state);
+                a.blk_out[st.blk_begin + k] = run + emitted(before, state);
+            }
+            const unsigned all_map = __shfl(incl.map, 63);
+            const unsigned long long all_out = shfl64(emitted(incl, state), 63);
+            run += all_out;
+            state = leave(all_map, state);
+        }
+        // the fill writes [out0, run) of the stream: run == out1 <= expect, decided here, before it writes
+        ok = run == c.out1;
+        if (c.check) {
+            // coded_off + s1 - 1: s0 < s1 <= coded_len, the last symbol that was parsed
+            const unsigned last = a.coded[st.coded_off + c.s1 - 1];
+            ok = ok && state == sp.state1 && last == sp.prev1;
+        }                                                         // else the stream's end: a count left dangling is dropped, as on the host
+    }
+    if (lane == 0) {
+        a.stream_ok[si] = ok ? 1u : 0u;
+        if (!ok) atomicOr(a.error, 1);
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void mp_unpack_window_fill_kernel(const UnpackWindowArgs w)
+{
+    __shared__ uint16_t sym[kUnpackBlock + 2];
+    __shared__ uint16_t value[kUnpackBlock];
+    __shared__ unsigned start[kUnpackBlock];
+    __shared__ Piece<unsigned> wave_piece[kWaves];
+    const UnpackArgs& a = w.a;
+    const unsigned b = blockIdx.x;                                // < n_blocks (the grid)
+    const int si = stream_of_block(a, b);
+    const UnpackStream& st = a.streams[si];
+    if (!a.stream_ok[si]) return;
+    const WindowSpan sp = w.span[si];                             // si < n_streams
+    const CutRange c = cut_range(sp, st);
+    const unsigned long long first = (unsigned long long)(b - st.blk_begin) * kUnpackBlock;
+    if (!(st.flags & kUnpackPacked)) {
+        // coded and expanded positions are the same.  A step-0 coefficient stream: what was parsed, [s0, s1); any other stream: the
+        // blocks that hold its window [r0, r1), as mp_unpack_fill_kernel<true> does
+        unsigned long long lo = 0, hi = st.coded_len;
+        if (c.cut) {
+            if (block_outside(first, c.s0, c.s1)) return;         // the whole workgroup
+            lo = c.s0;
+            hi = c.s1;
+        } else if (si != a.dc_stream[0] && si != a.dc_stream[1] && si != a.dc_stream[2]) {
+            const WindowStream win = a.window[si];
+            if (first + kUnpackBlock <= win.r0 || first >= win.r1) return;
+        }
+        const BlockSpan s = load_block(a, st, b, sym);
+        const unsigned long long from = s.first > lo ? s.first : lo, to = s.first + s.n < hi ? s.first + s.n : hi;
+        // stream_ok: coded_len == expect, so [from, to) inside the block's [first, first + n) ends inside [out_off, out_off + expect)
+        if (from < to) store_span(a.symbols, st.out_off + from, (unsigned)(to - from), sym + 1 + (unsigned)(from - s.first));
+        return;
+    }
+    if (block_outside(first, c.s0, c.s1)) return;                 // the whole workgroup
+    const BlockSpan s = load_block(a, st, b, sym);
+    Piece<unsigned> whole;
+    const Piece<unsigned> front = block_scan(thread_piece_cut(s, sym, c.s0, c.s1, sp.prev0), wave_piece, &whole);
+    const unsigned entry = a.blk_entry[b];
+    unsigned state = leave(front.map, entry), at = emitted(front, entry);
+#pragma unroll
+    for (int k = 0; k < kPerThread; ++k) {
+        const unsigned j = threadIdx.x * kPerThread + k;          // < 2048: start[], value[]
+        const unsigned long long pos = s.first + j;
+        start[j] = at;                                            // a symbol outside [s0, s1) emits nothing: the next one's start
+        value[j] = 0;
+        if (j < s.n && pos >= c.s0 && pos < c.s1) {
+            const unsigned cur = sym[j + 1], prev = pos == c.s0 ? sp.prev0 : sym[j];
+            if (state == 2) {
+                value[j] = (uint16_t)prev;
+                at += cur;
+                state = 0;
+            } else {
+                value[j] = (uint16_t)cur;
+                at += 1;
+                state = (state == 1 && pos != 0 && cur == prev) ? 2u : 1u;
+            }
+        }
+    }
+    __syncthreads();
+    // The block's output [blk_out, blk_out + total) in its stream.  stream_ok: the blocks' totals lead from out0 to exactly
+    // out1 <= expect, so every position written lies inside [out0, out1) of the stream's [out_off, out_off + expect).
+    const unsigned total = emitted(whole, entry);
+    const unsigned long long begin = st.out_off + a.blk_out[b], end = begin + total;
+    for (unsigned long long wd = (begin >> 1) + threadIdx.x; wd < ((end + 1) >> 1); wd += kThreads) {
+        uint16_t got[2] = {0, 0};
+        bool in[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const unsigned long long e = 2 * wd + h;
+            in[h] = e >= begin && e < end;
+            if (in[h]) {
+                const unsigned p = (unsigned)(e - begin);         // < total
+                unsigned j = 0;                                   // the last symbol whose output starts at or before p: start[0] = 0 <= p
+#pragma unroll
+                for (unsigned step = kUnpackBlock / 2; step; step >>= 1)
+                    if (start[j + step] <= p) j += step;          // j + step <= 2047
+                got[h] = value[j];
+            }
+        }
+        if (in[0] && in[1]) reinterpret_cast<uint32_t*>(a.symbols)[wd] = (uint32_t)got[0] | ((uint32_t)got[1] << 16);
+        else if (in[0]) a.symbols[2 * wd] = got[0];
+        else if (in[1]) a.symbols[2 * wd + 1] = got[1];
+    }
+}
+
+// The DC sums over [out0, out1) of the expanded stream alone: the blocks of 2048 expanded symbols that hold it, positions in front
+// of out0 contributing nothing, the carry seeded with dc0, and the sum behind out1 - 1 held to dc1 through the error word
+__global__ __launch_bounds__(kThreads) void mp_unpack_window_dc_sum_kernel(const UnpackWindowArgs w)
+{
+    __shared__ uint16_t sym[kUnpackBlock];
+    __shared__ unsigned wave_sum[kWaves];
+    const UnpackArgs& a = w.a;
+    const unsigned d = blockIdx.x;                                // < dc_blk_begin[3] (the grid)
+    unsigned long long first;
+    unsigned n;
+    const int which = dc_block(a, d, &first, &n);
+    const int si = a.dc_stream[which];
+    const UnpackStream& st = a.streams[si];
+    if (!a.stream_ok[si]) return;
+    const CutRange c = cut_range(w.span[si], st);
+    if (block_outside(first, c.out0, c.out1)) return;             // the whole workgroup
+    load_span(a.symbols, st.out_off + first, n, sym);             // first + n <= expect: inside the stream's output
+    __syncthreads();
+    unsigned acc = 0;
+    for (unsigned j = threadIdx.x; j < n; j += kThreads)
+        if (first + j >= c.out0 && first + j < c.out1) acc += (unsigned)zigzag_decode_dev(sym[j]);      // what the fill wrote
+    const unsigned all = block_sum(acc, wave_sum);
+    if (threadIdx.x == 0) a.dc_part[d] = all;
+}
+
+__global__ __launch_bounds__(kThreads) void mp_unpack_window_dc_scan_kernel(const UnpackWindowArgs w)
+{
+    __shared__ uint16_t sym[kUnpackBlock];
+    __shared__ unsigned wave_sum[kWaves];
+    __shared__ unsigned wave_incl[kWaves];
+    const UnpackArgs& a = w.a;
+    const unsigned d = blockIdx.x;                                // < dc_blk_begin[3] (the grid)
+    unsigned long long first;
+    unsigned n;
+    const int which = dc_block(a, d, &first, &n);
+    const int si = a.dc_stream[which];
+    const UnpackStream& st = a.streams[si];
+    if (!a.stream_ok[si]) return;
+    const WindowSpan sp = w.span[si];
+    const CutRange c = cut_range(sp, st);
+    if (block_outside(first, c.out0, c.out1)) return;             // the whole workgroup
+    // the blocks of this stream from the one that holds out0 up to d: dc_blk_begin[which] <= k < d, all of them written by the sum kernel
+    unsigned carry = 0;
+    for (unsigned long long k = a.dc_blk_begin[which] + c.out0 / kUnpackBlock + threadIdx.x; k < d; k += kThreads) carry += a.dc_part[k];
+    carry = block_sum(carry, wave_sum) + (c.cut ? sp.dc0 : 0u);
+    load_span(a.symbols, st.out_off + first, n, sym);
+    __syncthreads();
+    unsigned v[kPerThread], mine = 0;
+#pragma unroll
+    for (int k = 0; k < kPerThread; ++k) {
+        const unsigned j = threadIdx.x * kPerThread + k;          // < 2048
+        const bool in = j < n && first + j >= c.out0 && first + j < c.out1;
+        mine += in ? (unsigned)zigzag_decode_dev(sym[j]) : 0u;
+        v[k] = mine;
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned incl = mine;
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) {
+        const unsigned o = __shfl_up(incl, s);
+        if (lane >= s) incl += o;
+    }
+    if (lane == 63) wave_incl[wave] = incl;
+    __syncthreads();                                              // also: every thread has read its sym[] before they are overwritten
+    unsigned front = carry + incl - mine, all = carry;
+#pragma unroll
+    for (int wv = 0; wv < kWaves; ++wv) {
+        if (wv < wave) front += wave_incl[wv];
+        all += wave_incl[wv];
+    }
+#pragma unroll
+    for (int k = 0; k < kPerThread; ++k) {
+        const unsigned j = threadIdx.x * kPerThread + k;
+        if (j < n) sym[j] = (uint16_t)(front + v[k]);
+    }
+    __syncthreads();
+    const unsigned long long from = first > c.out0 ? first : c.out0, to = first + n < c.out1 ? first + n : c.out1;
+    if (from < to) store_span(a.symbols, st.out_off + from, (unsigned)(to - from), sym + (unsigned)(from - first));   // inside [out0, out1) and this block
+    // the block that holds out1 - 1 has the sum behind it
+    if (c.check && threadIdx.x == 0 && c.out1 <= first + n && (all & 0xFFFFu) != sp.dc1) atomicOr(a.error, 1);
+}
+
 namespace {
 template <bool kWindow>
 int launch_unpack_as(const UnpackArgs& a, void* stream_)
@@ -419,5 +704,20 @@ int launch_unpack_as(const UnpackArgs& a, void* stream_)
 
 int launch_unpack(const UnpackArgs& a, void* stream) { return launch_unpack_as<false>(a, stream); }
 int launch_unpack_window(const UnpackArgs& a, void* stream) { return launch_unpack_as<true>(a, stream); }
+
+int launch_unpack_window_cut(const UnpackWindowArgs& w, void* stream_)
+{
+    hipStream_t s = static_cast<hipStream_t>(stream_);
+    const UnpackArgs& a = w.a;
+    if (a.n_streams < 1 || a.n_streams > 6 * kMaxDeviceK || !a.window || !w.span) return (int)hipErrorInvalidValue;
+    if (a.n_blocks) hipLaunchKernelGGL(mp_unpack_window_map_kernel, dim3(a.n_blocks), dim3(kThreads), 0, s, w);
+    hipLaunchKernelGGL(mp_unpack_window_carry_kernel, dim3((unsigned)a.n_streams), dim3(64), 0, s, w);
+    if (a.n_blocks) hipLaunchKernelGGL(mp_unpack_window_fill_kernel, dim3(a.n_blocks), dim3(kThreads), 0, s, w);
+    if (a.dc_blk_begin[3]) {
+        hipLaunchKernelGGL(mp_unpack_window_dc_sum_kernel, dim3(a.dc_blk_begin[3]), dim3(kThreads), 0, s, w);
+        hipLaunchKernelGGL(mp_unpack_window_dc_scan_kernel, dim3(a.dc_blk_begin[3]), dim3(kThreads), 0, s, w);
+    }
+    return (int)hipGetLastError();
+}
 
 }  // namespace mpc

@@ -145,6 +145,8 @@ struct UnpackJob {
     char* h_result = nullptr;                       // pinned: free once the upload has left it (stream order)
     const void* d_extra[2] = {};
     char* d_behind = nullptr;
+    const unsigned long long* d_aux = nullptr;      // upload_and_parse(with_aux): the index's aux entries and every stream's first
+    const unsigned long long* d_aux_off = nullptr;
     mpc::UnpackArgs ua{};
     double staged_ms = 0.0;                         // trace_ms() with everything in pinned memory, nothing enqueued yet
 };
@@ -213,6 +215,10 @@ struct ParsePlan {
     size_t n_checkpoints = 0, n_counts = 0;
     unsigned n_groups = 0;
     UnpackPlan unpack;
+    // index version 2: the aux entries as in the blob, two words each, stream behind stream, and per stream of the 6K its first
+    // entry (~0: none).  Used by a region decode alone
+    bool expanded = false;
+    std::vector<unsigned long long> aux, aux_off;
 };
 
 // false = the index is not used (the serial route decides what becomes of the frame)
@@ -275,6 +281,20 @@ bool plan_parse(const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_
         ps.table_off = static_cast<unsigned>(p.tables.size());
         p.tables.insert(p.tables.end(), cb.table.begin(), cb.table.end());
     }
+    p.expanded = x.version == 2;
+    if (p.expanded) {
+        p.aux_off.assign(static_cast<size_t>(n), ~0ull);
+        for (int i = 0; i < n; ++i) {
+            const mpc::IndexStream& is = x.streams[static_cast<size_t>(i) + 1];
+            if (is.aux.empty()) continue;                           // read_container_index: else one entry per checkpoint
+            p.aux_off[i] = p.aux.size() / 2;
+            for (const mpc::IndexAux& a : is.aux) {
+                p.aux.push_back(a.out);
+                p.aux.push_back(static_cast<unsigned long long>(a.prev) | (static_cast<unsigned long long>(a.dc) << 16) |
+                                (static_cast<unsigned long long>(a.state) << 32));
+            }
+        }
+    }
     p.streams.back().group_begin = static_cast<unsigned>(groups);
     p.n_groups = static_cast<unsigned>(groups);
     p.n_checkpoints = static_cast<size_t>(checkpoints);
@@ -285,8 +305,10 @@ bool plan_parse(const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_
 // device, the parse kernels behind them; they leave the coded streams and the lengths where upload_and_unpack puts them
 // (j.ua.coded, j.d_extra[0]).  j.extra[0] is not used; the unpack kernels are the caller's to launch.  stamp[5]: behind the parse
 // deferred: the parse kernels are the caller's to launch as well, from *deferred (a frame of which a window is wanted)
+// with_aux: the aux entries of a version-2 index go up behind everything else (j.d_aux, j.d_aux_off); without it the upload is
+// what it is for a version-1 index
 mpc_status upload_and_parse(DecodeSlot& slot, UnpackJob& j, const ParsePlan& pp, const uint8_t* bytes, size_t nbytes,
-                            mpc::ParseArgs* deferred = nullptr) {
+                            mpc::ParseArgs* deferred = nullptr, bool with_aux = false) {
     const UnpackPlan& plan = *j.plan;
     constexpr size_t kHead = 256;
     const size_t padded = ((nbytes + 3) & ~static_cast<size_t>(3)) + 16;      // a lane's window reads up to 12 bytes behind the last bit
@@ -297,6 +319,7 @@ mpc_status upload_and_parse(DecodeSlot& slot, UnpackJob& j, const ParsePlan& pp,
     uint16_t* tables;
     mpc::UnpackStream* table;
     char* extra;
+    unsigned long long *aux = nullptr, *aux_off = nullptr;
     auto upload_layout = [&](char* base) {                          // the same in pinned memory and on the device
         Carve cv{base};
         words = cv.take<uint8_t>(padded);
@@ -307,6 +330,10 @@ mpc_status upload_and_parse(DecodeSlot& slot, UnpackJob& j, const ParsePlan& pp,
         tables = cv.take<uint16_t>(pp.tables.size() + 1);
         table = cv.take<mpc::UnpackStream>(plan.table.size());
         extra = cv.take<char>(j.extra_bytes[1]);
+        if (with_aux) {
+            aux = cv.take<unsigned long long>(pp.aux.size() + 2);
+            aux_off = cv.take<unsigned long long>(pp.aux_off.size());
+        }
         return cv.at;
     };
     const size_t upload_bytes = upload_layout(nullptr);
@@ -347,10 +374,16 @@ mpc_status upload_and_parse(DecodeSlot& slot, UnpackJob& j, const ParsePlan& pp,
     if (!pp.tables.empty()) std::memcpy(tables, pp.tables.data(), sizeof(uint16_t) * pp.tables.size());
     std::memcpy(table, plan.table.data(), sizeof(mpc::UnpackStream) * plan.table.size());
     if (j.extra_bytes[1]) std::memcpy(extra, j.extra[1], j.extra_bytes[1]);
+    if (with_aux) {
+        if (!pp.aux.empty()) std::memcpy(aux, pp.aux.data(), sizeof(unsigned long long) * pp.aux.size());
+        std::memcpy(aux_off, pp.aux_off.data(), sizeof(unsigned long long) * pp.aux_off.size());
+    }
     j.h_flags[0] = j.h_flags[1] = j.h_flags[2] = -1;
     char* dbase = slot.dev.data();
     upload_layout(dbase);
     device_layout(dbase);
+    j.d_aux = aux;
+    j.d_aux_off = aux_off;
     pa.words = reinterpret_cast<const uint32_t*>(words);
     pa.checkpoints = checkpoints;
     pa.streams = streams;
@@ -388,8 +421,12 @@ mpc_status upload_and_parse(DecodeSlot& slot, UnpackJob& j, const ParsePlan& pp,
 // scan over all tiles, the ranks of t0 and t1 (d_window, on the device: no round trip), the parse of the window's chunks and the
 // unpack of the window's blocks.  sa: block_live and sizes carved, counts and symbols set here.  stamp[6]: behind the ranks,
 // [5]: behind the parse, [2]: behind the unpack
+// d_span (index version 2, not "parse all"; the upload was made with_aux): packed and step-0 coefficient streams are cut as well, by
+// mp_window_rank_kernel<true> and launch_unpack_window_cut; null: the launches of a version-1 index.  ranks_only: nothing behind
+// the rank kernel is launched (mpc_window_chunks_device)
 mpc_status parse_and_unpack_window(DecodeSlot& slot, UnpackJob& j, const ParsePlan& pp, mpc::ParseArgs pa, mpc::StreamArgs& sa,
-                                   mpc::WindowStream* d_window, const mpc::TileWindow& win, bool parse_all) {
+                                   mpc::WindowStream* d_window, const mpc::TileWindow& win, bool parse_all, mpc::WindowSpan* d_span = nullptr,
+                                   bool ranks_only = false) {
     hipStream_t st = slot.stream;
     sa.counts = pa.counts;
     sa.symbols = j.ua.symbols;
@@ -405,12 +442,21 @@ mpc_status parse_and_unpack_window(DecodeSlot& slot, UnpackJob& j, const ParsePl
     wa.t0 = static_cast<long long>(win.t0);
     wa.t1 = static_cast<long long>(win.t1);
     wa.window = d_window;
+    if (d_span) {
+        wa.aux = j.d_aux;
+        wa.aux_off = j.d_aux_off;
+        wa.span = d_span;
+    }
     if (const int e = mpc::launch_window_rank(wa, st); e != 0) return launch_failed(e);
     if (j.trace) HIP_TRY(hipEventRecord(slot.stamp[6], st));
+    if (ranks_only) return MPC_OK;
     if (const int e = mpc::launch_parse_window(pa, st); e != 0) return launch_failed(e);
     if (j.trace) HIP_TRY(hipEventRecord(slot.stamp[5], st));
     j.ua.window = d_window;
-    if (const int e = mpc::launch_unpack_window(j.ua, st); e != 0) return launch_failed(e);
+    if (d_span) {
+        if (const int e = mpc::launch_unpack_window_cut(mpc::UnpackWindowArgs{j.ua, d_span}, st); e != 0) return launch_failed(e);
+    } else if (const int e = mpc::launch_unpack_window(j.ua, st); e != 0)
+        return launch_failed(e);
     if (j.trace) HIP_TRY(hipEventRecord(slot.stamp[2], st));
     return MPC_OK;
 }
@@ -439,6 +485,7 @@ mpc_status frame_on_slot(Sequence& q, int f, DecodeSlot& slot, const FrameHead& 
     if (rc && !mpc::tile_window(s.width, s.height, c->block_size, rc->x, rc->y, rc->width, rc->height, win))
         return fail(MPC_ERR_ARGUMENT, "rectangle %dx%d at (%d, %d) in a frame of %dx%d", rc->width, rc->height, rc->x, rc->y, s.width, s.height);
     const bool windowed = rc && pp, crop = rc && !pp;
+    const bool cut = windowed && pp->expanded && !q.parse_all;      // index version 2: packed and step-0 streams through their aux entries
     const size_t out_px = q.out_bytes(f, s.width, s.height);
     // read_compressed_coded refuses any other K; `quant` and UnpackJob::streams are sized by MPC_MAX_K and must not lean on that
     if (K < 1 || K > MPC_MAX_K) return fail(MPC_ERR_BITSTREAM, "Invalid input data");
@@ -449,11 +496,13 @@ mpc_status frame_on_slot(Sequence& q, int f, DecodeSlot& slot, const FrameHead& 
     uint32_t* d_choices;
     uint8_t *d_pixels = nullptr, *d_full = nullptr;
     mpc::WindowStream* d_window = nullptr;
+    mpc::WindowSpan* d_span = nullptr;
     auto behind_layout = [&](char* base) {                          // behind the unpacked streams: records | the gather's scratch | pixels
         Carve cv{base};
         d_choices = cv.take<uint32_t>(n_tc * K);
         carve_stream_buffers(cv, static_cast<long long>(tiles), K, false, &sa);
         if (windowed) d_window = cv.take<mpc::WindowStream>(6 * static_cast<size_t>(K));
+        if (cut) d_span = cv.take<mpc::WindowSpan>(6 * static_cast<size_t>(K));
         if (crop) d_full = cv.take<uint8_t>(px);                    // the whole frame, of which the rectangle is copied out
         else if (!q.d_rgb) d_pixels = cv.take<uint8_t>(out_px);
         return cv.at;
@@ -484,9 +533,9 @@ mpc_status frame_on_slot(Sequence& q, int f, DecodeSlot& slot, const FrameHead& 
         if (trace) HIP_TRY(hipEventRecord(slot.stamp[2], st));
     } else {
         mpc::ParseArgs pa{};
-        if (const mpc_status us = upload_and_parse(slot, j, *pp, q.bytes[f], q.nbytes[f], &pa); us != MPC_OK) return us;
+        if (const mpc_status us = upload_and_parse(slot, j, *pp, q.bytes[f], q.nbytes[f], &pa, cut); us != MPC_OK) return us;
         behind_layout(j.d_behind);
-        if (const mpc_status ws = parse_and_unpack_window(slot, j, *pp, pa, sa, d_window, win, q.parse_all); ws != MPC_OK) return ws;
+        if (const mpc_status ws = parse_and_unpack_window(slot, j, *pp, pa, sa, d_window, win, q.parse_all, d_span); ws != MPC_OK) return ws;
     }
     stamps[0] = j.staged_ms;
     const uint16_t* counts = static_cast<const uint16_t*>(j.d_extra[0]);
@@ -833,11 +882,15 @@ mpc_status mpc_decode_regions_indexed_device(mpc_context* c, const uint8_t* cons
     });
 }
 
-mpc_status mpc_parse_container_window_device(mpc_context* c, const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes,
-                                             const mpc_rect* rect, unsigned flags, uint16_t** symbols, size_t* n_symbols, uint64_t* ranges,
-                                             int* route) {
+}  // extern "C"
+
+namespace {
+// mpc_parse_container_window_device (symbols, n_symbols, ranges) and mpc_window_chunks_device (chunks): one run of the device half
+mpc_status window_on_device(mpc_context* c, const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes,
+                            const mpc_rect* rect, unsigned flags, uint16_t** symbols, size_t* n_symbols, uint64_t* ranges, uint64_t* chunks,
+                            int* route) {
     return guarded([&]() -> mpc_status {
-        if (!c || !bytes || !index || !rect || !symbols || !n_symbols || !ranges || !route) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (!c || !bytes || !index || !rect || !route || (chunks ? false : !symbols || !n_symbols || !ranges)) return fail(MPC_ERR_ARGUMENT, "null argument");
         if (flags & ~MPC_REGION_PARSE_ALL) return fail(MPC_ERR_ARGUMENT, "flags 0x%x", flags);
         if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback");
         const bool parse_all = (flags & MPC_REGION_PARSE_ALL) != 0;
@@ -851,6 +904,15 @@ mpc_status mpc_parse_container_window_device(mpc_context* c, const uint8_t* byte
         };
         // every refusal of the index: the host definition's own route 1 (no index at all)
         const auto serial = [&]() -> mpc_status {
+            if (chunks) {
+                std::vector<uint64_t> none;
+                const int verdict = mpc::window_chunks_by_index(bytes, nbytes, nullptr, 0, rect->x, rect->y, rect->width, rect->height, parse_all, none, route);
+                if (verdict == 1) return fail(MPC_ERR_BITSTREAM, "Invalid input data");
+                if (verdict == 2)
+                    return fail(MPC_ERR_ARGUMENT, "rectangle %dx%d at (%d, %d) is empty or not inside the frame", rect->width, rect->height, rect->x, rect->y);
+                std::memcpy(chunks, none.data(), sizeof(uint64_t) * none.size());
+                return MPC_OK;
+            }
             std::vector<uint16_t> got;
             std::vector<uint64_t> r;
             const int verdict = mpc::read_window_by_index(bytes, nbytes, nullptr, 0, rect->x, rect->y, rect->width, rect->height, parse_all, got, r, route);
@@ -873,10 +935,13 @@ mpc_status mpc_parse_container_window_device(mpc_context* c, const uint8_t* byte
         const size_t n_counts = pp.n_counts, n_out = pp.unpack.n_symbols, n_streams = 6 * static_cast<size_t>(K);
         mpc::StreamArgs sa{};
         mpc::WindowStream* d_window;
+        mpc::WindowSpan* d_span = nullptr;
+        const bool cut = pp.expanded && !parse_all;
         auto behind_layout = [&](char* base) {
             Carve cv{base};
             carve_stream_buffers(cv, static_cast<long long>(pp.ip.tiles), K, false, &sa);
             d_window = cv.take<mpc::WindowStream>(n_streams);
+            if (cut) d_span = cv.take<mpc::WindowSpan>(n_streams);
             return cv.at;
         };
         uint16_t* h_counts;
@@ -895,17 +960,29 @@ mpc_status mpc_parse_container_window_device(mpc_context* c, const uint8_t* byte
         j.behind_bytes = behind_layout(nullptr);
         j.result_bytes = result_layout(nullptr);
         mpc::ParseArgs pa{};
-        if (const mpc_status us = upload_and_parse(slot, j, pp, bytes, nbytes, &pa); us != MPC_OK) return us;
+        if (const mpc_status us = upload_and_parse(slot, j, pp, bytes, nbytes, &pa, cut); us != MPC_OK) return us;
         behind_layout(j.d_behind);
         result_layout(j.h_result);
-        if (const mpc_status ws = parse_and_unpack_window(slot, j, pp, pa, sa, d_window, win, parse_all); ws != MPC_OK) return ws;
+        if (const mpc_status ws = parse_and_unpack_window(slot, j, pp, pa, sa, d_window, win, parse_all, d_span, chunks != nullptr); ws != MPC_OK)
+            return ws;
         hipStream_t st = slot.stream;
         HIP_TRY(hipMemcpyAsync(j.h_flags, j.ua.error, 3 * sizeof(int), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(h_counts, pa.counts, sizeof(uint16_t) * n_counts, hipMemcpyDeviceToHost, st));
-        if (n_out) HIP_TRY(hipMemcpyAsync(h_symbols, j.ua.symbols, sizeof(uint16_t) * n_out, hipMemcpyDeviceToHost, st));
+        if (!chunks) {
+            HIP_TRY(hipMemcpyAsync(h_counts, pa.counts, sizeof(uint16_t) * n_counts, hipMemcpyDeviceToHost, st));
+            if (n_out) HIP_TRY(hipMemcpyAsync(h_symbols, j.ua.symbols, sizeof(uint16_t) * n_out, hipMemcpyDeviceToHost, st));
+        }
         HIP_TRY(hipMemcpyAsync(h_window, d_window, sizeof(mpc::WindowStream) * n_streams, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipEventRecord(slot.done, st));
         HIP_TRY(hipEventSynchronize(slot.done));
+        if (chunks) {                                               // the rank kernel's table; nothing behind that kernel was launched
+            if (j.h_flags[2] != 0) return serial();                 // the lengths are not what the index says: the host's route 1
+            for (size_t i = 0; i < n_streams; ++i) {
+                chunks[2 * i] = h_window[i].c0;
+                chunks[2 * i + 1] = h_window[i].c1;
+            }
+            *route = 0;
+            return MPC_OK;
+        }
         if (j.h_flags[2] != 0 || j.h_flags[0] != 0) return serial();
         // the window's slice of every expanded stream; (r0, r1) are the device's, held to the host's sizes
         std::vector<uint16_t> got(h_counts, h_counts + n_counts);
@@ -919,6 +996,22 @@ mpc_status mpc_parse_container_window_device(mpc_context* c, const uint8_t* byte
         *route = 0;
         return give(got);
     });
+}
+}  // namespace
+
+extern "C" {
+
+mpc_status mpc_parse_container_window_device(mpc_context* c, const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes,
+                                             const mpc_rect* rect, unsigned flags, uint16_t** symbols, size_t* n_symbols, uint64_t* ranges,
+                                             int* route) {
+    if (!symbols || !n_symbols || !ranges) return guarded([&]() -> mpc_status { return fail(MPC_ERR_ARGUMENT, "null argument"); });
+    return window_on_device(c, bytes, nbytes, index, index_bytes, rect, flags, symbols, n_symbols, ranges, nullptr, route);
+}
+
+mpc_status mpc_window_chunks_device(mpc_context* c, const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes,
+                                    const mpc_rect* rect, unsigned flags, uint64_t* chunks, int* route) {
+    if (!chunks) return guarded([&]() -> mpc_status { return fail(MPC_ERR_ARGUMENT, "null argument"); });
+    return window_on_device(c, bytes, nbytes, index, index_bytes, rect, flags, nullptr, nullptr, nullptr, chunks, route);
 }
 
 mpc_status mpc_parse_container_device(mpc_context* c, const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes,

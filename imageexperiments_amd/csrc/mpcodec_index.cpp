@@ -23,6 +23,85 @@ mpc_status mpc_container_index(const uint8_t* bytes, size_t nbytes, int interval
     });
 }
 
+namespace {
+mpc_status give_blob(const std::vector<uint8_t>& blob, uint8_t** index, size_t* index_bytes) {
+    uint8_t* p = static_cast<uint8_t*>(std::malloc(blob.empty() ? 1 : blob.size()));
+    if (!p) return fail(MPC_ERR_ALLOC, "out of memory");
+    if (!blob.empty()) std::memcpy(p, blob.data(), blob.size());
+    *index = p;
+    *index_bytes = blob.size();
+    return MPC_OK;
+}
+}  // namespace
+
+mpc_status mpc_container_index2(const uint8_t* bytes, size_t nbytes, int interval, unsigned flags, uint8_t** index, size_t* index_bytes) {
+    return guarded([&]() -> mpc_status {
+        if (!bytes || !index || !index_bytes) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (flags & ~MPC_INDEX_EXPANDED) return fail(MPC_ERR_ARGUMENT, "flags 0x%x", flags);
+        if (interval != 0 && (interval < static_cast<int>(mpc::kIndexIntervalMin) || interval > static_cast<int>(mpc::kIndexIntervalMax)))
+            return fail(MPC_ERR_ARGUMENT, "interval %d: 0 or %u to %u", interval, mpc::kIndexIntervalMin, mpc::kIndexIntervalMax);
+        std::vector<uint8_t> blob;
+        if (!mpc::build_container_index(bytes, nbytes, static_cast<uint32_t>(interval), blob, (flags & MPC_INDEX_EXPANDED) != 0))
+            return fail(MPC_ERR_BITSTREAM, "Invalid input data");
+        return give_blob(blob, index, index_bytes);
+    });
+}
+
+mpc_status mpc_index_extend(const uint8_t* bytes, size_t nbytes, const uint8_t* index_v1, size_t index_v1_bytes, uint8_t** index,
+                            size_t* index_bytes) {
+    return guarded([&]() -> mpc_status {
+        if (!bytes || !index_v1 || !index || !index_bytes) return fail(MPC_ERR_ARGUMENT, "null argument");
+        std::vector<uint8_t> blob;
+        if (!mpc::extend_container_index(bytes, nbytes, index_v1, index_v1_bytes, blob)) return fail(MPC_ERR_BITSTREAM, "Invalid input data");
+        return give_blob(blob, index, index_bytes);
+    });
+}
+
+int mpc_index_version(const uint8_t* index, size_t index_bytes) {
+    mpc::ContainerIndex x;
+    try {
+        return index && mpc::read_container_index(index, index_bytes, x) ? static_cast<int>(x.version) : 0;
+    } catch (...) {
+        return 0;
+    }
+}
+
+mpc_status mpc_index_aux(const uint8_t* index, size_t index_bytes, int stream, uint64_t* out, uint16_t* prev, uint8_t* state, uint16_t* dc,
+                         size_t capacity, size_t* n_entries) {
+    return guarded([&]() -> mpc_status {
+        if (!index || !n_entries) return fail(MPC_ERR_ARGUMENT, "null argument");
+        mpc::ContainerIndex x;
+        if (!mpc::read_container_index(index, index_bytes, x)) return fail(MPC_ERR_BITSTREAM, "not a seek index");
+        if (stream < 0 || stream >= static_cast<int>(x.streams.size())) return fail(MPC_ERR_ARGUMENT, "stream index %d out of range", stream);
+        const std::vector<mpc::IndexAux>& aux = x.streams[static_cast<size_t>(stream)].aux;
+        *n_entries = aux.size();
+        if (!out && !prev && !state && !dc) return MPC_OK;
+        if (capacity < aux.size()) return fail(MPC_ERR_ARGUMENT, "capacity %zu for %zu entries", capacity, aux.size());
+        for (size_t k = 0; k < aux.size(); ++k) {
+            if (out) out[k] = aux[k].out;
+            if (prev) prev[k] = aux[k].prev;
+            if (state) state[k] = aux[k].state;
+            if (dc) dc[k] = aux[k].dc;
+        }
+        return MPC_OK;
+    });
+}
+
+mpc_status mpc_window_chunks_by_index(const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes, const mpc_rect* rect,
+                                      unsigned flags, uint64_t* chunks, int* route) {
+    return guarded([&]() -> mpc_status {
+        if (!bytes || !index || !rect || !chunks || !route) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (flags & ~MPC_REGION_PARSE_ALL) return fail(MPC_ERR_ARGUMENT, "flags 0x%x", flags);
+        std::vector<uint64_t> got;
+        const int verdict = mpc::window_chunks_by_index(bytes, nbytes, index, index_bytes, rect->x, rect->y, rect->width, rect->height,
+                                                        (flags & MPC_REGION_PARSE_ALL) != 0, got, route);
+        if (verdict == 1) return fail(MPC_ERR_BITSTREAM, "Invalid input data");
+        if (verdict == 2) return fail(MPC_ERR_ARGUMENT, "rectangle %dx%d at (%d, %d) is empty or not inside the frame", rect->width, rect->height, rect->x, rect->y);
+        std::memcpy(chunks, got.data(), sizeof(uint64_t) * got.size());
+        return MPC_OK;
+    });
+}
+
 mpc_status mpc_index_info(const uint8_t* index, size_t index_bytes, mpc_index_header* info) {
     return guarded([&]() -> mpc_status {
         if (!index || !info) return fail(MPC_ERR_ARGUMENT, "null argument");

@@ -437,6 +437,37 @@ typedef struct mpc_index_stream_info {
 mpc_status mpc_index_info(const uint8_t* index, size_t index_bytes, mpc_index_header* info);
 mpc_status mpc_index_stream(const uint8_t* index, size_t index_bytes, int stream, mpc_index_stream_info* info, uint64_t* checkpoints,
                             size_t capacity);
+/* Index version 2 ("expanded"): the version-1 blob with its version word set to 2, followed by an aux section that lets a region
+ * decode cut the streams version 1 cannot cut -- a run-length packed stream (coded positions are not expanded positions) and the
+ * three step-0 coefficient streams 1, 2K + 1, 4K + 1 (prefix sums).  Only those streams have entries (which they are follows
+ * from the stream records: `packed`, or a step-0 coefficient stream; the lengths stream has none).  Section: u64 entries in all,
+ * then, stream behind stream in the blob's order, 16 bytes per checkpoint j (coded symbol j * interval) of each such stream:
+ *   u64 out    expanded symbols emitted by the coded symbols [0, j * interval) under runLengthDecode's machine; j * interval
+ *              for a stream that is not packed
+ *   u64 word   bits 0-15 prev: coded symbol j * interval - 1 (0 for j = 0 and for a stream that is not packed); bits 16-31 dc:
+ *              for a step-0 coefficient stream the low 16 bits of the sum of zigzagDecode over those `out` expanded symbols, else
+ *              0; bits 32-33 state: the machine's state coded symbol j * interval is met in (0 fresh, 1 value, 2 count; 0 for a
+ *              stream that is not packed); the other bits 0
+ * A "serial only" index has no entries.  The blob is a pure function of (container, interval).  Every call that takes an index
+ * takes either version; whole-frame decodes and MPC_REGION_PARSE_ALL check the section's structure and use nothing else of it.
+ *
+ * mpc_container_index2: flags 0 = mpc_container_index's blob, byte for byte; MPC_INDEX_EXPANDED = version 2 (one more linear pass
+ * over the packed and step-0 streams).  Refusals are mpc_container_index's.
+ * mpc_index_extend: from the version-1 index of this container (what the indexed encoders return) the version-2 blob
+ * mpc_container_index2 would build with that index's interval, byte for byte, without the serial parse: the streams come from the
+ * chunked parse.  An index that is refused is answered from the serial parse, with the interval its header word names (the
+ * default where that is none).  A version-2 index comes back as a copy.  MPC_ERR_BITSTREAM for a container
+ * mpc_read_compressed_coded refuses.
+ * mpc_index_version: 1 or 2; 0 = not an index.
+ * mpc_index_aux: a stream's entries read back; *n_entries = 0 for a version-1 index and for a stream without entries.  out, prev,
+ * state, dc: each NULL or room for `capacity` >= *n_entries values (all NULL: the count alone). */
+#define MPC_INDEX_EXPANDED 1u
+mpc_status mpc_container_index2(const uint8_t* bytes, size_t nbytes, int interval, unsigned flags, uint8_t** index, size_t* index_bytes);
+mpc_status mpc_index_extend(const uint8_t* bytes, size_t nbytes, const uint8_t* index_v1, size_t index_v1_bytes, uint8_t** index,
+                            size_t* index_bytes);
+int mpc_index_version(const uint8_t* index, size_t index_bytes);
+mpc_status mpc_index_aux(const uint8_t* index, size_t index_bytes, int stream, uint64_t* out, uint16_t* prev, uint8_t* state, uint16_t* dc,
+                         size_t capacity, size_t* n_entries);
 /* The chunked parse on the host: what mpc_read_compressed_coded yields -- the lengths stream and the 6K coded streams back to back
  * (symbols, mpc_free) -- with every chunk decoded from its checkpoint alone and accepted only under the rule above.  It defines
  * what the device parse computes, checkable without a GPU.  route: 0 = the index was used, 1 = it was refused and the serial
@@ -473,17 +504,26 @@ mpc_status mpc_decode_images_indexed_device(mpc_context* ctx, const uint8_t* con
  * copy of unpacked streams, the gather, the reconstruction, the pixels' way back -- handles the window alone.
  * The cost follows the rectangle's HORIZONTAL extent: [t0, t1) spans every tile column the rectangle touches from top to bottom
  * (but for the first and last), so a wide, short strip spans nearly every column's whole range; ranges per tile column are not
- * built.  Known limit: a run-length packed stream (coded positions are not expanded positions) and the three step-0 coefficient
- * streams (prefix sums) are parsed and expanded whole, whatever the rectangle.
+ * built.  A run-length packed stream (coded positions are not expanded positions) and the three step-0 coefficient streams
+ * (prefix sums) are cut through a version-2 index: with out[], state[], prev[], dc[] of the stream's aux entries, c0 = the largest
+ * j with out[j] <= r0, c1 = the smallest j > c0 with out[j] >= r1, else the stream's chunks (r0 == r1: nothing is parsed).  Only
+ * chunks [c0, c1) are parsed; the expansion starts at coded symbol c0 * interval in (state[c0], prev[c0]) at position out[c0], the
+ * sum seeded with dc[c0].  With a version-1 index, and under MPC_REGION_PARSE_ALL, those streams are parsed and expanded whole.
  *
  * What is trusted.  Without MPC_REGION_PARSE_ALL the chunks outside the window are never read, so the whole-frame rule "a hint,
  * never an authority" cannot hold in full.  What holds instead: (1) every structural check of the whole-frame route is kept --
- * the index against the container on the host; the lengths stream, every packed stream and the three step-0 coefficient streams
- * parsed whole and checked as for a whole frame; the stream sizes recomputed from the decoded lengths equal to the index's;
- * every parsed chunk yielding exactly its symbols and ending on the next checkpoint (on the pseudo-EOF and the stream's end for a
- * last chunk).  Any failure sends the frame to route 1.  (2) With an index that mpc_container_index or the indexed encoders made
- * for this container the result is exactly the crop of the full decode; with any other index that passes all of (1) the pixels
- * are unspecified.  Nothing is read or written out of bounds either way: every bound still comes from the host's tables.
+ * the index against the container on the host, the aux section's structure included (its size exact; per stream out[0] = 0,
+ * state[0] = 0, prev[0] = 0, out strictly increasing and <= expect, state <= 2, out[j] = j * interval for a stream that is not
+ * packed); the lengths stream parsed whole, and with a version-1 index every packed stream and the three step-0 coefficient
+ * streams too, checked as for a whole frame; the stream sizes recomputed from the decoded lengths equal to the index's; every
+ * parsed chunk yielding exactly its symbols and ending on the next checkpoint (on the pseudo-EOF and the stream's end for a last
+ * chunk); for a stream cut through its aux entries, behind the last parsed coded symbol the expansion's position and state equal
+ * to out[c1] and state[c1], that symbol equal to prev[c1] and the running sum to dc[c1] (c1 = the stream's chunks: the position
+ * equal to `expect`, a dangling count dropped) -- checked before anything of the stream is written.  Any failure sends the frame
+ * to route 1.  (2) With an index that mpc_container_index[2], mpc_index_extend or the indexed encoders made for this container
+ * the result is exactly the crop of the full decode; with any other index that passes all of (1) -- checkpoints or aux entries
+ * that were not made for this container -- the pixels are unspecified.  Nothing is read or written out of bounds either way:
+ * every bound still comes from the host's tables and the checked aux entries (out <= expect), never from a symbol's value.
  * With MPC_REGION_PARSE_ALL every chunk of every stream is parsed, the whole-frame acceptance rule applies unchanged, and only
  * the stages behind the parse are windowed.  In either mode the reconstruction's "Invalid bitstream" verdict (a record outside
  * its dictionary) speaks for the window's tiles only.
@@ -512,6 +552,15 @@ mpc_status mpc_parse_container_window_by_index(const uint8_t* bytes, size_t nbyt
 mpc_status mpc_parse_container_window_device(mpc_context* ctx, const uint8_t* bytes, size_t nbytes, const uint8_t* index,
                                              size_t index_bytes, const mpc_rect* rect, unsigned flags, uint16_t** symbols,
                                              size_t* n_symbols, uint64_t* ranges, int* route);
+/* The chunks [chunks[i][0], chunks[i][1]) of each of the 6K streams that the windowed parse reads for this rectangle (all of a
+ * stream's chunks where it is parsed whole).  Host only; needs the lengths stream alone.  route 1 (the index is refused, or the
+ * lengths are not what it says): no chunk is parsed by index, every entry 0.  The _device form (for tests) runs the upload, the
+ * lengths parse and mp_window_rank_kernel, nothing behind it, and downloads the device's own table; where the device's lengths
+ * parse sets its error word the answer is the host's route 1. */
+mpc_status mpc_window_chunks_by_index(const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes, const mpc_rect* rect,
+                                      unsigned flags, uint64_t* chunks /* [6K][2] */, int* route);
+mpc_status mpc_window_chunks_device(mpc_context* ctx, const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes,
+                                    const mpc_rect* rect, unsigned flags, uint64_t* chunks /* [6K][2] */, int* route);
 
 /* ---- "-s" patch statistics, Compression.cpp:200-302 ----
  * The reference seeds one std::mt19937, and for every image draws `patches` origins x = rand() % (width - bs),
