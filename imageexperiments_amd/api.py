@@ -45,6 +45,18 @@ class MpcRect(C.Structure):                          # mpc_rect
     _fields_ = [("x", C.c_int), ("y", C.c_int), ("width", C.c_int), ("height", C.c_int)]
 
 
+class MpcView(C.Structure):                          # mpc_view
+    _fields_ = [("rect", MpcRect), ("steps", C.c_int), ("scale_log2", C.c_int)]
+
+
+def _view(view):
+    """(rect, steps, scale_log2) with rect = (x, y, width, height), (0, 0, 0, 0) or None = the whole frame -> MpcView"""
+    if isinstance(view, MpcView):
+        return view
+    rect, steps, scale_log2 = view
+    return MpcView(MpcRect(*[int(v) for v in (rect or (0, 0, 0, 0))]), int(steps), int(scale_log2))
+
+
 class _IndexStreamInfo(C.Structure):                 # mpc_index_stream_info
     _fields_ = [("mode", C.c_int), ("packed", C.c_int), ("m", C.c_uint32), ("n_coded", C.c_uint64), ("expect", C.c_uint64),
                 ("wrapper_bit", C.c_uint64), ("end_bit", C.c_uint64), ("n_checkpoints", C.c_uint64)]
@@ -167,6 +179,16 @@ def _bind_bitstream(L):
                                              C.c_uint, C.POINTER(_u8p), C.POINTER(C.c_int)]
     L.mpc_decode_regions_indexed_device.argtypes = [vp, C.POINTER(_u8p), C.POINTER(C.c_size_t), C.POINTER(_u8p), C.POINTER(C.c_size_t), _rp,
                                                     C.c_int, C.c_uint, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
+    _vwp = C.POINTER(MpcView)
+    _vparse = [_u8p, C.c_size_t, _u8p, C.c_size_t, _vwp, C.c_uint, C.POINTER(_u16p), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
+    L.mpc_truncate_container.argtypes = [_u8p, C.c_size_t, C.c_int, C.POINTER(_u8p), C.POINTER(C.c_size_t)]
+    L.mpc_parse_container_view_by_index.argtypes = _vparse
+    L.mpc_parse_container_view_device.argtypes = [vp] + _vparse
+    L.mpc_decode_views_indexed.argtypes = [vp, C.POINTER(_u8p), C.POINTER(C.c_size_t), C.POINTER(_u8p), C.POINTER(C.c_size_t), _vwp, C.c_int,
+                                           C.c_uint, C.POINTER(_u8p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.mpc_decode_views_indexed_device.argtypes = [vp, C.POINTER(_u8p), C.POINTER(C.c_size_t), C.POINTER(_u8p), C.POINTER(C.c_size_t), _vwp,
+                                                  C.c_int, C.c_uint, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_int),
+                                                  C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.mpc_decode_images_indexed.argtypes = [vp, C.POINTER(_u8p), C.POINTER(C.c_size_t), C.POINTER(_u8p), C.POINTER(C.c_size_t), C.c_int,
                                             C.POINTER(_u8p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.mpc_decode_images_indexed_device.argtypes = [vp, C.POINTER(_u8p), C.POINTER(C.c_size_t), C.POINTER(_u8p), C.POINTER(C.c_size_t), C.c_int,
@@ -520,6 +542,36 @@ def parse_container_window_by_index(blob, index, rect, parse_all=False):
     was refused and the serial parse gave the result."""
     buf, idx = np.frombuffer(blob, np.uint8), np.frombuffer(index, np.uint8)
     return _window_parse(load_library().mpc_parse_container_window_by_index, (), buf, idx, rect, parse_all)
+
+
+def truncate_container(blob, steps):
+    """mpc_truncate_container: the container cut to its first `steps` pursuit steps (the rate-scalable transcode) -> bytes: every
+    length min(length, steps), the streams of steps at or above `steps` emptied, header, K and quantiser table kept.  steps >= K
+    gives an encoder's container back as it is; steps < 1 is MpcError(MPC_ERR_ARGUMENT); MpcError(MPC_ERR_BITSTREAM) for whatever
+    read_compressed refuses."""
+    L = load_library()
+    buf = np.frombuffer(blob, np.uint8)
+    out, n = _u8p(), C.c_size_t(0)
+    _check(L.mpc_truncate_container(buf.ctypes.data_as(_u8p), buf.size, int(steps), C.byref(out), C.byref(n)))
+    return _take_bytes(L, out, n)
+
+
+def _view_parse(fn, head, buf, idx, view, parse_all):
+    _, _, K, _ = container_info(buf)
+    vw = _view(view)
+    ranges = np.zeros((3 * K, 2), np.uint64)
+    out, n, route = _u16p(), C.c_size_t(0), C.c_int(-1)
+    _check(fn(*head, buf.ctypes.data_as(_u8p), buf.size, idx.ctypes.data_as(_u8p), idx.size, C.byref(vw), 1 if parse_all else 0, C.byref(out),
+              C.byref(n), ranges.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(route)))
+    return _take_u16(load_library(), out, n), ranges, route.value
+
+
+def parse_container_view_by_index(blob, index, view, parse_all=False):
+    """mpc_parse_container_view_by_index: the host definition of a view's device parse, view = (rect, steps, scale_log2) ->
+    (symbols, ranges, route) as parse_container_window_by_index gives them for truncate_container(blob, steps): the lengths cut to
+    `steps`, the streams of steps at or above it empty."""
+    buf, idx = np.frombuffer(blob, np.uint8), np.frombuffer(index, np.uint8)
+    return _view_parse(load_library().mpc_parse_container_view_by_index, (), buf, idx, view, parse_all)
 
 
 def parse_container_by_index(blob, index):
@@ -998,6 +1050,62 @@ class CompressionContext:
         _check(self.L.mpc_decode_regions_indexed_device(self.h, ptrs, sizes, iptrs, isizes, rc, n, 1 if parse_all else 0, d_ptrs, caps,
                                                         routes))
         return [out[i].view(-1)[:3 * rc[i].width * rc[i].height].view(rc[i].height, rc[i].width, 3) for i in range(n)], list(routes)
+
+    @staticmethod
+    def _views(views, n):
+        if len(views) != n:
+            raise ValueError("one view (rect, steps, scale_log2) per container")
+        return (MpcView * n)(*[_view(v) for v in views])
+
+    def decode_views(self, blobs, indexes, views, parse_all=False):
+        """mpc_decode_views_indexed: views[f] = (rect, steps, scale_log2) of every frame -- the rectangle (x, y, width, height),
+        None = the whole frame, reconstructed from the first `steps` records of every tile-channel (0 = all) and reduced by
+        2^scale_log2 (0 ... 3; the rectangle's origin a multiple of it) -> (frames, routes): uint8 [ceil(height / c), ceil(width / c), 3]
+        arrays, routes[f] 0 = through the frame's seek index, the streams of steps at or above `steps` never read, 1 = the serial
+        parse.  parse_all: MPC_VIEW_PARSE_ALL."""
+        bufs, ptrs, sizes = self._containers(blobs)
+        n = len(bufs)
+        ibufs, iptrs, isizes = self._indexes(indexes, n)
+        vw = self._views(views, n)
+        outs, W, H, routes = (_u8p * n)(), (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)()
+        _check(self.L.mpc_decode_views_indexed(self.h, ptrs, sizes, iptrs, isizes, vw, n, 1 if parse_all else 0, outs, W, H, routes))
+        return [_take_view(self.L, outs[i], C.c_size_t(3 * W[i] * H[i])).reshape(H[i], W[i], 3) for i in range(n)], list(routes)
+
+    def decode_views_device(self, blobs, indexes, views, parse_all=False, out=None):
+        """mpc_decode_views_indexed_device: the same with the pixels left on the context's device.  out: a list of contiguous uint8
+        torch tensors there, each of at least 3 * ceil(width / c) * ceil(height / c) elements of its view (bytes behind that are
+        left alone); None = allocated here.  Returns (frames, routes), the frames uint8 tensors."""
+        import torch
+        bufs, ptrs, sizes = self._containers(blobs)
+        n = len(bufs)
+        ibufs, iptrs, isizes = self._indexes(indexes, n)
+        vw = self._views(views, n)
+        if out is None:
+            out = []
+            for b, v in zip(bufs, vw):
+                w, h = v.rect.width, v.rect.height
+                if w == 0 and h == 0:
+                    try:
+                        w, h, _, _ = container_info(b)
+                    except MpcError:                             # the call itself refuses the frame, in its turn, by its index
+                        w, h = 1, 1
+                c = 1 << min(max(v.scale_log2, 0), 3)
+                out.append(torch.empty(3 * max(-(-w // c), 1) * max(-(-h // c), 1), dtype=torch.uint8, device=f"cuda:{self.device}"))
+        if len(out) != n or any(t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous() for t in out):
+            raise ValueError("out: one contiguous uint8 device tensor per container")
+        d_ptrs = (C.c_void_p * n)(*[C.c_void_p(t.data_ptr()) for t in out])
+        caps = (C.c_size_t * n)(*[t.numel() for t in out])
+        W, H, routes = (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)()
+        torch.cuda.synchronize(self.device)                      # `out` may still be being written by the caller's streams
+        _check(self.L.mpc_decode_views_indexed_device(self.h, ptrs, sizes, iptrs, isizes, vw, n, 1 if parse_all else 0, d_ptrs, caps, W, H,
+                                                      routes))
+        return [out[i].view(-1)[:3 * W[i] * H[i]].view(H[i], W[i], 3) for i in range(n)], list(routes)
+
+    def parse_container_view_device(self, blob, index, view, parse_all=False):
+        """mpc_parse_container_view_device: parse_container_view_by_index with the device's lengths parse, lengths cut, ranks,
+        windowed parse and windowed unpack -> (symbols, ranges, route)."""
+        buf, idx = np.frombuffer(blob, np.uint8), np.frombuffer(index, np.uint8)
+        return _view_parse(self.L.mpc_parse_container_view_device, (self.h,), buf, idx, view, parse_all)
 
     def parse_container_window_device(self, blob, index, rect, parse_all=False):
         """mpc_parse_container_window_device: parse_container_window_by_index with the device's lengths parse, ranks, windowed

@@ -221,8 +221,20 @@ void window_ranges(const uint16_t* lengths, int K, size_t t0, size_t t1, uint64_
 // *route = 0: by the index; 1: the index was refused (plan_indexed_parse, a chunk, the lengths, a packed stream's size, an
 // end-of-range check) and read_compressed gave the result.
 // Returns 0, 1 = invalid data (read_compressed's verdict), 2 = the rectangle is empty or not inside the frame
+// steps > 0 (a view, "Decoder: views"): the windowed parse of truncate_container(bytes, steps) from this container and its own
+// index.  The lengths stream is parsed whole and held to the index's sizes UNCUT; behind that check the lengths are cut to
+// min(length, steps), so a stream of a step at or above `steps` owns no position (r0 = r1 = 0) and is never read -- unless
+// parse_all, which parses and checks every stream and still emits nothing of the cut ones.  The lengths returned are the cut ones
 int read_window_by_index(const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes, int x, int y, int w, int h,
-                         bool parse_all, std::vector<uint16_t>& symbols, std::vector<uint64_t>& ranges, int* route);
+                         bool parse_all, std::vector<uint16_t>& symbols, std::vector<uint64_t>& ranges, int* route, int steps = 0);
+
+// ---- the first `steps` records of every tile-channel ("Decoder: views") ----
+// The container is layered by pursuit step: a tile-channel has step i exactly when its length exceeds i, so the container of the
+// same frame pursued for `steps` steps only is the parsed one with every length set to min(length, steps), the streams of steps
+// below `steps` as they are (the same symbols) and the streams of steps at or above it empty; header, K and quantiser table kept,
+// written by the one host coder (write_compressed).  steps >= K: the parsed container coded again.  false = read_compressed
+// refuses the input.  steps >= 1 is the caller's to check
+bool truncate_container(const uint8_t* bytes, size_t nbytes, int steps, std::vector<uint8_t>& out);
 
 // The same index from what an encoder holds when it has just written the container, without parsing anything: the plans of
 // plan_stream, where each stream's codes begin, and the bit of every interval-th coded symbol as the code writer passed it.

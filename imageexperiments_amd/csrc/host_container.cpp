@@ -939,13 +939,20 @@ int window_chunks_by_index(const uint8_t* bytes, size_t nbytes, const uint8_t* i
 }
 
 int read_window_by_index(const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes, int x, int y, int w, int h,
-                         bool parse_all, std::vector<uint16_t>& symbols, std::vector<uint64_t>& ranges, int* route) {
+                         bool parse_all, std::vector<uint16_t>& symbols, std::vector<uint64_t>& ranges, int* route, int steps) {
     *route = 1;
     int width, height, K, block_size;
     if (!container_info(bytes, nbytes, &width, &height, &K, &block_size)) return 1;
     TileWindow win;
     if (!tile_window(width, height, block_size, x, y, w, h, win)) return 2;
     ranges.assign(6 * static_cast<size_t>(K), 0);
+    // a view: the lengths cut as truncate_container cuts them, to min(length, steps), once they have been checked; a stream of a step
+    // at or above `kept` then owns no position
+    const int kept = steps > 0 && steps < K ? steps : K;
+    const auto cut_lengths = [&](std::vector<uint16_t>& lengths) {
+        if (steps > 0)
+            for (uint16_t& length : lengths) length = static_cast<uint16_t>(std::min<int>(length, steps));
+    };
     // the slices [r0, r1) of expanded streams behind the lengths
     auto emit = [&](const std::vector<uint16_t>& lengths, const std::function<const uint16_t*(int)>& expanded) {
         size_t total = lengths.size();
@@ -1008,11 +1015,13 @@ int read_window_by_index(const uint8_t* bytes, size_t nbytes, const uint8_t* ind
         };
         std::vector<size_t> expect;
         if (!lengths_by_index(plan, bytes, nbytes, lengths, expect)) return false;
+        cut_lengths(lengths);                                   // behind the check against the index's (uncut) sizes
         window_ranges(lengths.data(), K, win.t0, win.t1, ranges.data());
         codes.assign(static_cast<size_t>(6 * K), {});
         for (int i = 0; i < 6 * K; ++i) {
             const IndexStream& is = ix.streams[static_cast<size_t>(i) + 1];
             const bool dc = i % (2 * K) == 1;
+            if (!parse_all && (i % (2 * K)) / 2 >= kept) continue;   // a cut stream: never read
             const uint64_t r0 = ranges[2 * (i / 2)], r1 = ranges[2 * (i / 2) + 1];
             std::vector<uint16_t>& v = codes[i];
             if (!parse_all && !is.aux.empty()) {                // version 2: cut by expanded position
@@ -1046,9 +1055,25 @@ int read_window_by_index(const uint8_t* bytes, size_t nbytes, const uint8_t* ind
     }
     Streams s;
     if (!read_compressed(bytes, nbytes, s)) return 1;
+    cut_lengths(s.lengths);
     window_ranges(s.lengths.data(), K, win.t0, win.t1, ranges.data());
     emit(s.lengths, [&](int i) { return s.codes[i].data(); });
     return 0;
+}
+
+bool truncate_container(const uint8_t* bytes, size_t nbytes, int steps, std::vector<uint8_t>& out) {
+    Streams s;
+    if (!read_compressed(bytes, nbytes, s)) return false;
+    const int K = s.K;
+    for (uint16_t& length : s.lengths)
+        if (static_cast<int>(length) > steps) length = static_cast<uint16_t>(steps);
+    for (int ch = 0; ch < 3; ++ch)
+        for (int i = std::max(steps, 0); i < K; ++i) {
+            s.codes[static_cast<size_t>(2 * K * ch + 2 * i)].clear();
+            s.codes[static_cast<size_t>(2 * K * ch + 2 * i + 1)].clear();
+        }
+    out = write_compressed(s);
+    return true;
 }
 
 bool read_compressed(const uint8_t* bytes, size_t nbytes, Streams& s) {

@@ -132,6 +132,15 @@ struct DecodeWindow {
     int tx0, ty0, tx1, ty1;
 };
 int launch_decode_window(const DictDevice& dict, const DecodeParams& p, const DecodeWindow& w, void* stream);
+// A view (mp_decode_view_kernel): the window's tiles reconstructed from the first `steps` records of every tile-channel -- the
+// dynamic dictionary built from those alone -- and reduced by c = 1 << scale_log2: p.rgb receives ceil(rect_h / c) rows of
+// ceil(rect_w / c) pixels, each the rounded mean (sum + n / 2) / n of the stored 8-bit values of its cell's n pixels that lie inside
+// the rectangle.  The caller guarantees what launch_decode_window asks for, steps >= 1, 0 <= scale_log2 <= 3 and rect_x, rect_y
+// multiples of c (a cell then never crosses a tile, and its first pixel lies inside the rectangle if any of it does).
+struct DecodeView {
+    int steps, scale_log2;
+};
+int launch_decode_view(const DictDevice& dict, const DecodeParams& p, const DecodeWindow& w, const DecodeView& v, void* stream);
 
 // distortion (mp_kernels.hip: mp_distortion_kernel): the decode kernel's reconstruction compared with the original frame
 struct DistortionParams {
@@ -352,6 +361,11 @@ int launch_parse(const ParseArgs& a, void* stream);                  // hipError
 // once launch_window_rank has written a.window -- the 6K streams' groups, of which only the chunks [c0, c1) of each stream are read
 int launch_parse_lengths(const ParseArgs& a, void* stream);
 int launch_parse_window(const ParseArgs& a, void* stream);
+// A view of the first `steps` steps: a.counts cut in place to min(count, steps), behind launch_parse_lengths -- whose verify kernel
+// has compared the UNCUT sizes with the index's -- and in front of launch_window_rank, whose count and scan then give a stream of a
+// step at or above `steps` size 0 and the ranks (0, 0), and of the gather, which lays the streams out by these lengths.  The host's
+// UnpackStream / ParseStream tables hold those streams empty (no chunks, no symbols), so both layouts agree
+int launch_clamp_lengths(const ParseArgs& a, int steps, void* stream);
 
 // ---- device-side entropy stage (mp_entropy.hip): everything that touches every symbol of the 1 + 6K streams ----
 constexpr int kEntBlock = 4096;         // symbols per scan block

@@ -700,9 +700,12 @@ __global__ __launch_bounds__(256) void mp_histogram_kernel(const HistParams p, i
 // rounding and clamp.  rgb[] receives the pixel as the decoder stores it (whole numbers 0..255).  Shared by mp_decode_kernel
 // and mp_distortion_kernel so that what the distortion measures is, by construction, what the decoder writes.  A record
 // outside its dynamic dictionary skips that step and sets *error_flag (when given).
+// steps (<= K): the records replayed, min(count, steps) of them; K for a whole decode.  The dynamic dictionary is built from those
+// alone (a view: what a pursuit of `steps` steps would have left), so a row that a later base choice unlocks is outside it.
 template <class T>
 __device__ inline void reconstruct_tile_pixel(const DictDevice& dict, const uint16_t* __restrict__ counts, const uint32_t* __restrict__ choices,
-                                              const double* __restrict__ quant, int K, long long t, int lane, int* error_flag, double rgb[3])
+                                              const double* __restrict__ quant, int K, int steps, long long t, int lane, int* error_flag,
+                                              double rgb[3])
 {
     constexpr bool kFast = std::is_same<T, float>::value;
     const T* const base_rows = reinterpret_cast<const T*>(kFast ? static_cast<const void*>(dict.base32) : static_cast<const void*>(dict.base));
@@ -710,7 +713,7 @@ __device__ inline void reconstruct_tile_pixel(const DictDevice& dict, const uint
     double yuv[3];
     for (int ch = 0; ch < 3; ++ch) {
         const int count = counts[t * 3 + ch];
-        const int n = count < K ? count : K;
+        const int n = count < steps ? count : steps;
         const uint32_t* rec = choices + (t * 3 + ch) * K;
         // lane i < n takes record i: its choice (the running sum of the zig-zag deltas, the first delta taken as is) by a wave
         // scan, then its row in the dynamic dictionary -- the block walk of every step at once instead of one after another
@@ -722,8 +725,8 @@ __device__ inline void reconstruct_tile_pixel(const DictDevice& dict, const uint
             const int up = __shfl_up(choice, o);
             if (lane >= o) choice += up;
         }
-        // the reference builds the dynamic dictionary from ALL `count` choices before summing (FromCoeffsDynamic :111),
-        // so a detail row is resolved against the full list
+        // the reference builds the dynamic dictionary from all the choices it replays before summing (FromCoeffsDynamic :111),
+        // so a detail row is resolved against the full list of the n = min(count, steps) choices, and against no later one
         long long row_at = -1;          // element offset of this lane's row; -1: outside the dictionary
         int in_base = 0;
         if (choice >= 0 && choice < dict.num_base) {
@@ -776,7 +779,7 @@ __global__ __launch_bounds__(64) void mp_decode_kernel(const DictDevice dict, co
     const long long tiles = (long long)p.tiles_x * p.tiles_y;
     for (long long t = blockIdx.x; t < tiles; t += gridDim.x) {
         double px_rgb[3];
-        reconstruct_tile_pixel<T>(dict, p.counts, p.choices, p.quant, p.K, t, lane, p.error_flag, px_rgb);
+        reconstruct_tile_pixel<T>(dict, p.counts, p.choices, p.quant, p.K, p.K, t, lane, p.error_flag, px_rgb);
         const int tx = (int)(t / p.tiles_y), ty = (int)(t - (long long)tx * p.tiles_y);
         const int u = tx * 8 + (lane & 7), v = ty * 8 + (lane >> 3);          // block index = dx + 8*dy
         if (u < p.width && v < p.height) {
@@ -802,13 +805,57 @@ __global__ __launch_bounds__(64) void mp_decode_window_kernel(const DictDevice d
         const int tx = w.tx0 + (int)(k / rows), ty = w.ty0 + (int)(k % rows);
         const long long t = (long long)tx * p.tiles_y + ty;
         double px_rgb[3];
-        reconstruct_tile_pixel<T>(dict, p.counts, p.choices, p.quant, p.K, t, lane, p.error_flag, px_rgb);
+        reconstruct_tile_pixel<T>(dict, p.counts, p.choices, p.quant, p.K, p.K, t, lane, p.error_flag, px_rgb);
         const int u = tx * 8 + (lane & 7) - w.rect_x, v = ty * 8 + (lane >> 3) - w.rect_y;
         if (u >= 0 && u < w.rect_w && v >= 0 && v < w.rect_h) {
             uint8_t* px = p.rgb + 3 * ((long long)v * w.rect_w + u);
             px[0] = (uint8_t)px_rgb[0];
             px[1] = (uint8_t)px_rgb[1];
             px[2] = (uint8_t)px_rgb[2];
+        }
+    }
+}
+
+// A view of the window: the same grid of tiles, one wave per tile, LANE = PIXEL, reconstructed from the first v.steps records and
+// reduced by c = 1 << v.scale_log2.  Tiles are 8 x 8 and the rectangle's origin is a multiple of c, so a cell of c x c pixels lies
+// inside one tile, that is inside one wave: its sum is a butterfly over the lanes, xor 1, 2, 4 across and 8, 16, 32 down, scale_log2
+// rounds of each, over the STORED values (after RGBFromYUV's rounding and clamp) of the pixels inside the rectangle, and over their
+// number n.  Red and green share a word, blue and n another (a cell's sum is at most 64 * 255 < 2^16).  The lane of the cell's
+// first pixel stores (sum + n / 2) / n; that pixel is inside the rectangle if any of the cell is (the rectangle begins on a cell
+// boundary), so n >= 1 there.  cu < ceil(rect_w / c) and cv < ceil(rect_h / c) follow from u < rect_w, v < rect_h and bound every
+// store; scale_log2 = 0 is mp_decode_window_kernel's store.
+template <class T>
+__global__ __launch_bounds__(64) void mp_decode_view_kernel(const DictDevice dict, const DecodeParams p, const DecodeWindow w, const DecodeView v)
+{
+    const int lane = threadIdx.x;
+    const int rows = w.ty1 - w.ty0;
+    const long long tiles = (long long)(w.tx1 - w.tx0) * rows;
+    const int s = v.scale_log2, c = 1 << s;
+    const int out_w = (w.rect_w + c - 1) >> s;
+    for (long long k = blockIdx.x; k < tiles; k += gridDim.x) {
+        const int tx = w.tx0 + (int)(k / rows), ty = w.ty0 + (int)(k % rows);
+        const long long t = (long long)tx * p.tiles_y + ty;
+        double px_rgb[3];
+        reconstruct_tile_pixel<T>(dict, p.counts, p.choices, p.quant, p.K, v.steps, t, lane, p.error_flag, px_rgb);
+        const int pu = tx * 8 + (lane & 7) - w.rect_x, pv = ty * 8 + (lane >> 3) - w.rect_y;
+        const bool inside = pu >= 0 && pu < w.rect_w && pv >= 0 && pv < w.rect_h;
+        unsigned rg = inside ? (unsigned)px_rgb[0] | ((unsigned)px_rgb[1] << 16) : 0u;
+        unsigned bn = inside ? (unsigned)px_rgb[2] | (1u << 16) : 0u;
+        for (int r = 0; r < s; ++r) {                               // uniform: every lane takes part in every exchange
+            rg += (unsigned)__shfl_xor((int)rg, 1 << r);
+            bn += (unsigned)__shfl_xor((int)bn, 1 << r);
+        }
+        for (int r = 0; r < s; ++r) {
+            rg += (unsigned)__shfl_xor((int)rg, 8 << r);
+            bn += (unsigned)__shfl_xor((int)bn, 8 << r);
+        }
+        const bool first = ((lane & 7) & (c - 1)) == 0 && ((lane >> 3) & (c - 1)) == 0;
+        if (first && inside) {
+            const unsigned n = bn >> 16, half = n >> 1;             // 1 <= n <= c * c
+            uint8_t* px = p.rgb + 3 * ((long long)(pv >> s) * out_w + (pu >> s));
+            px[0] = (uint8_t)(((rg & 0xFFFFu) + half) / n);
+            px[1] = (uint8_t)(((rg >> 16) + half) / n);
+            px[2] = (uint8_t)(((bn & 0xFFFFu) + half) / n);
         }
     }
 }
@@ -831,7 +878,7 @@ __global__ __launch_bounds__(64 * kDistortionWaves) void mp_distortion_kernel(co
     unsigned long long mine = 0;
     for (long long t = (long long)blockIdx.x * kDistortionWaves + wave; t < tiles; t += (long long)gridDim.x * kDistortionWaves) {
         double px_rgb[3];
-        reconstruct_tile_pixel<T>(dict, p.counts, p.choices, p.quant, p.K, t, lane, nullptr, px_rgb);
+        reconstruct_tile_pixel<T>(dict, p.counts, p.choices, p.quant, p.K, p.K, t, lane, nullptr, px_rgb);
         const int tx = (int)(t / p.tiles_y), ty = (int)(t - (long long)tx * p.tiles_y);
         const int u = tx * 8 + (lane & 7), v = ty * 8 + (lane >> 3);
         int e = 0;
@@ -1025,6 +1072,19 @@ int launch_decode_window(const DictDevice& dict, const DecodeParams& p, const De
     const unsigned blocks = (unsigned)(tiles < 16384 ? tiles : 16384);
     if (p.fast) hipLaunchKernelGGL(mp_decode_window_kernel<float>, dim3(blocks), dim3(64), 0, (hipStream_t)stream, dict, p, w);
     else hipLaunchKernelGGL(mp_decode_window_kernel<double>, dim3(blocks), dim3(64), 0, (hipStream_t)stream, dict, p, w);
+    return (int)hipGetLastError();
+}
+
+int launch_decode_view(const DictDevice& dict, const DecodeParams& p, const DecodeWindow& w, const DecodeView& v, void* stream)
+{
+    if (w.tx0 < 0 || w.ty0 < 0 || w.tx0 >= w.tx1 || w.ty0 >= w.ty1 || w.tx1 > p.tiles_x || w.ty1 > p.tiles_y || w.rect_w < 1 || w.rect_h < 1 ||
+        w.rect_x < 0 || w.rect_y < 0 || v.steps < 1 || v.steps > p.K || v.scale_log2 < 0 || v.scale_log2 > 3 ||
+        (w.rect_x & ((1 << v.scale_log2) - 1)) != 0 || (w.rect_y & ((1 << v.scale_log2) - 1)) != 0)
+        return (int)hipErrorInvalidValue;
+    const long long tiles = (long long)(w.tx1 - w.tx0) * (w.ty1 - w.ty0);
+    const unsigned blocks = (unsigned)(tiles < 16384 ? tiles : 16384);
+    if (p.fast) hipLaunchKernelGGL(mp_decode_view_kernel<float>, dim3(blocks), dim3(64), 0, (hipStream_t)stream, dict, p, w, v);
+    else hipLaunchKernelGGL(mp_decode_view_kernel<double>, dim3(blocks), dim3(64), 0, (hipStream_t)stream, dict, p, w, v);
     return (int)hipGetLastError();
 }
 

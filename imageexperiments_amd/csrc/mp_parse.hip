@@ -280,6 +280,15 @@ __global__ __launch_bounds__(256) void mp_parse_void_kernel(const ParseArgs a)
         a.counts[i] = 0;
 }
 
+// a view: the lengths cut to its steps (launch_clamp_lengths); i < n_counts, the host's size of `counts`
+__global__ __launch_bounds__(256) void mp_parse_clamp_kernel(const ParseArgs a, unsigned steps)
+{
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < a.n_counts; i += (unsigned long long)gridDim.x * 256) {
+        const unsigned c = a.counts[i];
+        if (c > steps) a.counts[i] = (uint16_t)steps;
+    }
+}
+
 namespace {
 bool parse_args_ok(const ParseArgs& a) {
     return !(a.n_streams < 2 || a.n_streams > 6 * kMaxDeviceK + 1 || a.K < 1 || a.K > kMaxDeviceK || a.interval < 1 || a.n_counts < 3);
@@ -309,6 +318,15 @@ int launch_parse_lengths(const ParseArgs& a, void* stream_)
 {
     if (!parse_args_ok(a) || a.group_first > a.n_groups) return (int)hipErrorInvalidValue;
     return launch_parse_front(a, a.group_first, static_cast<hipStream_t>(stream_));
+}
+
+int launch_clamp_lengths(const ParseArgs& a, int steps, void* stream_)
+{
+    if (!parse_args_ok(a) || steps < 1 || steps > a.K) return (int)hipErrorInvalidValue;
+    const unsigned long long want = (a.n_counts + 255) / 256;
+    const unsigned blocks = (unsigned)(want < 1024 ? want : 1024);
+    hipLaunchKernelGGL(mp_parse_clamp_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream_), a, (unsigned)steps);
+    return (int)hipGetLastError();
 }
 
 int launch_parse_window(const ParseArgs& a, void* stream_)

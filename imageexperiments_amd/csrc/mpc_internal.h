@@ -368,7 +368,27 @@ struct mpc_context {
 // FromCoeffsDynamic + RGBFromYUV for whole tiles on `stream`; d_quant: [3][K] doubles on the device; d_flag: the caller's error
 // word (zeroed on `stream` first, set when a record indexes outside its dictionary)
 mpc_status decode_tiles_on_device(mpc_context* c, const uint16_t* d_counts, const uint32_t* d_choices, const double* d_quant, int K,
-                                  int width, int height, uint8_t* d_rgb, int* d_flag, void* stream, const mpc::DecodeWindow* window = nullptr);
+                                  int width, int height, uint8_t* d_rgb, int* d_flag, void* stream, const mpc::DecodeWindow* window = nullptr,
+                                  const mpc::DecodeView* view = nullptr);
+
+// ---- views (include/mpcodec.h, "views"): what the entry points of mpcodec_index.cpp and mpcodec_decode_seq.cpp share ----
+// a view's own arguments: nullptr, or what is wrong with them
+inline const char* view_argument_error(const mpc_view& v) {
+    if (v.steps < 0) return "steps must not be negative";
+    if (v.scale_log2 < 0 || v.scale_log2 > 3) return "scale_log2 must be 0 ... 3";
+    const int c = 1 << v.scale_log2;
+    if (v.rect.x % c != 0 || v.rect.y % c != 0) return "the rectangle's origin must be a multiple of the reduction";
+    return nullptr;
+}
+// the rectangle a view names in a frame of width x height: (0, 0, 0, 0) is the whole frame
+inline mpc_rect view_rect(const mpc_view& v, int width, int height) {
+    const mpc_rect& r = v.rect;
+    return r.x == 0 && r.y == 0 && r.width == 0 && r.height == 0 ? mpc_rect{0, 0, width, height} : r;
+}
+// pixels of `extent` reduced by 2^scale_log2
+inline int view_extent(int extent, int scale_log2) { return (extent + (1 << scale_log2) - 1) >> scale_log2; }
+// the steps a view keeps of a container of K: 0 = all, above K acts as K
+inline int view_steps(int steps, int K) { return steps > 0 && steps < K ? steps : K; }
 
 // ---- context and tile encode (mpcodec_context.cpp) ----
 mpc::DictDevice dict_device(const mpc_context* c);

@@ -10,9 +10,10 @@
 #include "mpc_internal.h"
 
 // FromCoeffsDynamic + RGBFromYUV for whole tiles on the device.  window: only the tiles a pixel rectangle touches,
-// d_rgb then receiving the rectangle alone
+// d_rgb then receiving the rectangle alone.  view (with a window): the first view->steps records, reduced (mp_decode_view_kernel)
 mpc_status decode_tiles_on_device(mpc_context* c, const uint16_t* d_counts, const uint32_t* d_choices, const double* d_quant,
-                                  int K, int width, int height, uint8_t* d_rgb, int* d_flag, void* stream, const mpc::DecodeWindow* window) {
+                                  int K, int width, int height, uint8_t* d_rgb, int* d_flag, void* stream, const mpc::DecodeWindow* window,
+                                  const mpc::DecodeView* view) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(int), s));
     mpc::DecodeParams p{};
@@ -27,7 +28,10 @@ mpc_status decode_tiles_on_device(mpc_context* c, const uint16_t* d_counts, cons
     p.rgb = d_rgb;
     p.error_flag = d_flag;
     p.fast = c->fast ? 1 : 0;
-    const int err = window ? mpc::launch_decode_window(dict_device(c), p, *window, stream) : mpc::launch_decode(dict_device(c), p, stream);
+    if (view && !window) return fail(MPC_ERR_ARGUMENT, "a view needs its window");
+    const int err = view     ? mpc::launch_decode_view(dict_device(c), p, *window, *view, stream)
+                    : window ? mpc::launch_decode_window(dict_device(c), p, *window, stream)
+                             : mpc::launch_decode(dict_device(c), p, stream);
     if (err != 0) return launch_failed(err);
     return MPC_OK;
 }

@@ -8,6 +8,8 @@
 // into the same buffers; whatever makes the index unusable sends the frame down the serial route from the start.  A call that wants
 // a pixel rectangle of each frame (mpc_decode_regions_indexed*) is one more caller of the same sequence: with an index the window's
 // share of every stage behind the lengths stream (route 0), without one the whole frame by the serial route and a 2-D copy (route 1).
+// A view (mpc_decode_views_indexed*) is a region with a cap on the pursuit steps and a reduction: the streams of the steps it does
+// not want are empty in the host's tables, the lengths are cut behind their check, and mp_decode_view_kernel ends either route.
 #include <algorithm>
 #include <atomic>
 #include <climits>
@@ -99,6 +101,7 @@ struct Sequence {
     int* routes = nullptr;                      // optional: per frame 0 = parsed on the device, 1 = the serial route
     const mpc_rect* rects = nullptr;            // mpc_decode_regions_indexed*: the rectangle wanted of frame f
     bool parse_all = false;                     // ... MPC_REGION_PARSE_ALL
+    const mpc_view* views = nullptr;            // mpc_decode_views_indexed*: steps and reduction of frame f; rects[f] is then its rectangle, resolved
     int* width = nullptr;
     int* height = nullptr;
     std::atomic<int> next{0};                   // frames are handed out in order
@@ -111,6 +114,9 @@ struct Sequence {
 
     // the bytes frame f's pixels take at the caller's, the frame being width x height
     size_t out_bytes(int f, int width, int height) const {
+        if (views)
+            return static_cast<size_t>(view_extent(rects[f].width, views[f].scale_log2)) *
+                   static_cast<size_t>(view_extent(rects[f].height, views[f].scale_log2)) * 3;
         if (rects) return static_cast<size_t>(rects[f].width) * static_cast<size_t>(rects[f].height) * 3;
         return static_cast<size_t>(width) * height * 3;
     }
@@ -222,19 +228,24 @@ struct ParsePlan {
 };
 
 // false = the index is not used (the serial route decides what becomes of the frame)
-bool plan_parse(const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes, bool pooled, ParsePlan& p) {
+// keep_steps (a view; 0 or >= K: every step): a stream of a step at or above it is EMPTY in every table the kernels bound themselves
+// by -- no coded symbols, no chunks, no groups, no expanded symbols, no aux entries -- so it is neither parsed, unpacked nor
+// gathered, and the streams behind it move up.  ParseStream::expect alone stays the index's: mp_parse_verify_kernel compares it
+// with the sizes the uncut lengths give
+bool plan_parse(const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes, bool pooled, ParsePlan& p, int keep_steps = 0) {
     if (!mpc::plan_indexed_parse(bytes, nbytes, index, index_bytes, p.ip, pooled)) return false;
     const mpc::ContainerIndex& x = p.ip.index;
     const int K = x.K, n = 6 * K;
     if (K < 1 || K > MPC_MAX_K) return false;
+    const auto is_cut = [&](int i) { return keep_steps > 0 && (i % (2 * K)) / 2 >= keep_steps; };      // stream i of the 6K
     std::vector<uint8_t> is_packed(static_cast<size_t>(n));
     std::vector<unsigned long long> expect(static_cast<size_t>(n));
     for (int i = 0; i < n; ++i) {
-        is_packed[i] = static_cast<uint8_t>(x.streams[static_cast<size_t>(i) + 1].packed);
-        expect[i] = x.streams[static_cast<size_t>(i) + 1].expect;
+        is_packed[i] = is_cut(i) ? uint8_t(0) : static_cast<uint8_t>(x.streams[static_cast<size_t>(i) + 1].packed);
+        expect[i] = is_cut(i) ? 0ull : x.streams[static_cast<size_t>(i) + 1].expect;
     }
-    if (!plan_unpack(K, [&](int i) { return static_cast<unsigned long long>(x.streams[static_cast<size_t>(i) + 1].n_coded); }, is_packed.data(),
-                     expect.data(), nullptr, p.unpack))
+    if (!plan_unpack(K, [&](int i) { return is_cut(i) ? 0ull : static_cast<unsigned long long>(x.streams[static_cast<size_t>(i) + 1].n_coded); },
+                     is_packed.data(), expect.data(), nullptr, p.unpack))
         return false;
     p.n_counts = 3 * p.ip.tiles;
     p.streams.assign(x.streams.size() + 1, mpc::ParseStream{});
@@ -245,17 +256,19 @@ bool plan_parse(const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_
         const mpc::StreamWrapper& w = p.ip.wrappers[j];
         mpc::ParseStream& ps = p.streams[j];
         if (is.checkpoints.size() > 0xFFFFFFFFull) return false;
+        const bool cut_away = j != 0 && is_cut(static_cast<int>(j) - 1);
+        const size_t chunks = cut_away ? 0 : is.checkpoints.size();
         ps.out_off = j == 0 ? 0 : p.unpack.table[j - 1].coded_off;
-        ps.n_coded = is.n_coded;
+        ps.n_coded = cut_away ? 0 : is.n_coded;
         ps.end_bit = is.end_bit;
         ps.cp_off = checkpoints;
         ps.expect = is.expect;
-        ps.n_chunks = static_cast<unsigned>(is.checkpoints.size());
+        ps.n_chunks = static_cast<unsigned>(chunks);
         ps.group_begin = static_cast<unsigned>(groups);
         ps.flags = (w.mode == 1 ? mpc::kParseGolomb : 0u) | (j == 0 ? mpc::kParseLengths : 0u);
         ps.m = w.m;
-        checkpoints += is.checkpoints.size();
-        groups += (is.checkpoints.size() + mpc::kParseGroup - 1) / mpc::kParseGroup;
+        checkpoints += is.checkpoints.size();                       // the upload holds every stream's: cp_off is the blob's
+        groups += (chunks + mpc::kParseGroup - 1) / mpc::kParseGroup;
         if (groups > 0x7FFFFFFFull) return false;
         if (w.mode != 0 || ps.n_chunks == 0) continue;
         const mpc::HuffmanCodebook& cb = w.cb;
@@ -286,7 +299,7 @@ bool plan_parse(const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_
         p.aux_off.assign(static_cast<size_t>(n), ~0ull);
         for (int i = 0; i < n; ++i) {
             const mpc::IndexStream& is = x.streams[static_cast<size_t>(i) + 1];
-            if (is.aux.empty()) continue;                           // read_container_index: else one entry per checkpoint
+            if (is.aux.empty() || is_cut(i)) continue;              // read_container_index: else one entry per checkpoint
             p.aux_off[i] = p.aux.size() / 2;
             for (const mpc::IndexAux& a : is.aux) {
                 p.aux.push_back(a.out);
@@ -423,16 +436,19 @@ mpc_status upload_and_parse(DecodeSlot& slot, UnpackJob& j, const ParsePlan& pp,
 // [5]: behind the parse, [2]: behind the unpack
 // d_span (index version 2, not "parse all"; the upload was made with_aux): packed and step-0 coefficient streams are cut as well, by
 // mp_window_rank_kernel<true> and launch_unpack_window_cut; null: the launches of a version-1 index.  ranks_only: nothing behind
-// the rank kernel is launched (mpc_window_chunks_device)
+// the rank kernel is launched (mpc_window_chunks_device).  clamp_steps (a view; pp planned with the same keep_steps): the lengths
+// are cut to it between their check and the ranks
 mpc_status parse_and_unpack_window(DecodeSlot& slot, UnpackJob& j, const ParsePlan& pp, mpc::ParseArgs pa, mpc::StreamArgs& sa,
                                    mpc::WindowStream* d_window, const mpc::TileWindow& win, bool parse_all, mpc::WindowSpan* d_span = nullptr,
-                                   bool ranks_only = false) {
+                                   bool ranks_only = false, int clamp_steps = 0) {
     hipStream_t st = slot.stream;
     sa.counts = pa.counts;
     sa.symbols = j.ua.symbols;
     pa.window = d_window;
     pa.group_first = pp.streams[1].group_begin;                     // the lengths stream's groups come first
     if (const int e = mpc::launch_parse_lengths(pa, st); e != 0) return launch_failed(e);
+    if (clamp_steps)
+        if (const int e = mpc::launch_clamp_lengths(pa, clamp_steps, st); e != 0) return launch_failed(e);
     mpc::WindowArgs wa{};
     wa.sa = sa;
     wa.unpack = j.ua.streams;
@@ -484,11 +500,17 @@ mpc_status frame_on_slot(Sequence& q, int f, DecodeSlot& slot, const FrameHead& 
     mpc::TileWindow win;
     if (rc && !mpc::tile_window(s.width, s.height, c->block_size, rc->x, rc->y, rc->width, rc->height, win))
         return fail(MPC_ERR_ARGUMENT, "rectangle %dx%d at (%d, %d) in a frame of %dx%d", rc->width, rc->height, rc->x, rc->y, s.width, s.height);
-    const bool windowed = rc && pp, crop = rc && !pp;
+    // A view: the region's window route, or the whole frame's streams by the serial route (parse_worker has cut them), and either way
+    // mp_decode_view_kernel on the rectangle's tiles: no full-size frame, no 2-D copy
+    const mpc_view* vw = q.views ? &q.views[f] : nullptr;
+    const bool windowed = rc && pp, crop = rc && !pp && !vw;
     const bool cut = windowed && pp->expanded && !q.parse_all;      // index version 2: packed and step-0 streams through their aux entries
     const size_t out_px = q.out_bytes(f, s.width, s.height);
     // read_compressed_coded refuses any other K; `quant` and UnpackJob::streams are sized by MPC_MAX_K and must not lean on that
     if (K < 1 || K > MPC_MAX_K) return fail(MPC_ERR_BITSTREAM, "Invalid input data");
+    const mpc::DecodeView dv{vw ? view_steps(vw->steps, K) : K, vw ? vw->scale_log2 : 0};
+    // pp was planned with the same steps (parse_worker); "parse all" parses, unpacks and gathers every stream, the kernel alone cuts
+    const int clamp_steps = vw && windowed && !q.parse_all && dv.steps < K ? dv.steps : 0;
     double quant[3 * MPC_MAX_K];
     for (int ch = 0; ch < 3; ++ch)
         for (int i = 0; i < K; ++i) quant[ch * K + i] = static_cast<double>(s.quant[ch][i]);
@@ -535,7 +557,8 @@ mpc_status frame_on_slot(Sequence& q, int f, DecodeSlot& slot, const FrameHead& 
         mpc::ParseArgs pa{};
         if (const mpc_status us = upload_and_parse(slot, j, *pp, q.bytes[f], q.nbytes[f], &pa, cut); us != MPC_OK) return us;
         behind_layout(j.d_behind);
-        if (const mpc_status ws = parse_and_unpack_window(slot, j, *pp, pa, sa, d_window, win, q.parse_all, d_span); ws != MPC_OK) return ws;
+        if (const mpc_status ws = parse_and_unpack_window(slot, j, *pp, pa, sa, d_window, win, q.parse_all, d_span, false, clamp_steps); ws != MPC_OK)
+            return ws;
     }
     stamps[0] = j.staged_ms;
     const uint16_t* counts = static_cast<const uint16_t*>(j.d_extra[0]);
@@ -544,14 +567,15 @@ mpc_status frame_on_slot(Sequence& q, int f, DecodeSlot& slot, const FrameHead& 
     sa.counts = counts;
     sa.symbols = j.ua.symbols;
     mpc::DecodeWindow dw{};
+    if (rc) dw = mpc::DecodeWindow{rc->x, rc->y, rc->width, rc->height, win.tx0, win.ty0, win.tx1, win.ty1};
     if (windowed) {
-        dw = mpc::DecodeWindow{rc->x, rc->y, rc->width, rc->height, win.tx0, win.ty0, win.tx1, win.ty1};
         if (const int e = mpc::launch_stream_gather_window(sa, d_choices, static_cast<long long>(win.t0), static_cast<long long>(win.t1), st); e != 0)
             return launch_failed(e);
     } else if (const int e = mpc::launch_stream_gather(sa, d_choices, st); e != 0)
         return launch_failed(e);
     if (const mpc_status ds = decode_tiles_on_device(c, counts, d_choices, static_cast<const double*>(j.d_extra[1]), K, s.width, s.height,
-                                                     crop ? d_full : d_pixels, j.ua.error + 1, st, windowed ? &dw : nullptr);
+                                                     crop ? d_full : d_pixels, j.ua.error + 1, st, windowed || vw ? &dw : nullptr,
+                                                     vw ? &dv : nullptr);
         ds != MPC_OK)
         return ds;
     if (trace) HIP_TRY(hipEventRecord(slot.stamp[3], st));
@@ -589,8 +613,8 @@ mpc_status frame_on_slot(Sequence& q, int f, DecodeSlot& slot, const FrameHead& 
         else if (out_px) copy(0);                                       // the frames' copies run side by side on the call's threads
         q.rgb[f] = out;
     }
-    q.width[f] = s.width;
-    q.height[f] = s.height;
+    q.width[f] = vw ? view_extent(rc->width, vw->scale_log2) : s.width;
+    q.height[f] = vw ? view_extent(rc->height, vw->scale_log2) : s.height;
     stamps[2] = trace_ms();
     return MPC_OK;
 }
@@ -647,7 +671,9 @@ void parse_worker(Sequence& q) {
             HIP_TRY(hipSetDevice(c->device));
             if (!mpc::read_compressed_coded(q.bytes[f], q.nbytes[f], s)) return fail(MPC_ERR_BITSTREAM, "Invalid input data");
             const bool block_size_differs = s.block_size != c->block_size;
-            const bool too_long = std::any_of(s.lengths.begin(), s.lengths.end(), [&](uint16_t length) { return length > s.K; });
+            // a view of the first `steps` steps decodes the truncated container: its lengths are min(length, steps)
+            const int steps = q.views && q.views[f].steps > 0 ? q.views[f].steps : INT_MAX;
+            const bool too_long = std::any_of(s.lengths.begin(), s.lengths.end(), [&](uint16_t length) { return std::min<int>(length, steps) > s.K; });
             if (block_size_differs || too_long) {
                 // Refused here, before the device has expanded a stream.  A container whose streams do not expand either is
                 // invalid data first, whatever else is wrong with it: the host's expansion (the reference for what a decoder
@@ -660,6 +686,22 @@ void parse_worker(Sequence& q) {
             }
             if (q.d_rgb && !q.rects && q.out_bytes(f, s.width, s.height) > q.capacity[f])
                 return fail(MPC_ERR_ARGUMENT, "capacity %zu for a frame of %dx%d", q.capacity[f], s.width, s.height);
+            if (steps < s.K) {
+                // The truncation's cut (mpc::truncate_container) on the coded streams: a stream of a step at or above `steps` is held
+                // to the size the lengths give it, as read_compressed holds it, and emptied; the device sees nothing of it
+                for (int i = 0; i < 6 * s.K; ++i) {
+                    if ((i % (2 * s.K)) / 2 < steps) continue;
+                    std::vector<uint16_t>& v = s.codes[static_cast<size_t>(i)];
+                    size_t expanded = v.size();
+                    if (s.packed[static_cast<size_t>(i)] && !mpc::rle_decoded_size(v.data(), v.size(), s.expect[static_cast<size_t>(i)], &expanded))
+                        return fail(MPC_ERR_BITSTREAM, "Invalid input data");
+                    if (expanded != s.expect[static_cast<size_t>(i)]) return fail(MPC_ERR_BITSTREAM, "Invalid input data");
+                    v.clear();
+                    s.packed[static_cast<size_t>(i)] = 0;
+                    s.expect[static_cast<size_t>(i)] = 0;
+                }
+                for (uint16_t& length : s.lengths) length = std::min<uint16_t>(length, static_cast<uint16_t>(steps));
+            }
             if (!plan_unpack(s.K, [&](int i) { return static_cast<unsigned long long>(s.codes[i].size()); }, s.packed.data(), nullptr,
                              s.expect.data(), plan))
                 return fail(MPC_ERR_BITSTREAM, "Invalid bitstream");
@@ -677,7 +719,9 @@ void parse_worker(Sequence& q) {
             if (q.indexes && q.indexes[f] && !q.failed_before(f)) {
                 HIP_TRY(hipSetDevice(c->device));
                 const mpc::ContainerIndex& x = pp.ip.index;
-                indexed = plan_parse(q.bytes[f], q.nbytes[f], q.indexes[f], q.index_bytes[f], q.n == 1, pp) && x.block_size == c->block_size &&
+                indexed = plan_parse(q.bytes[f], q.nbytes[f], q.indexes[f], q.index_bytes[f], q.n == 1, pp,
+                                     q.views && !q.parse_all ? q.views[f].steps : 0) &&
+                          x.block_size == c->block_size &&
                           !(q.d_rgb && q.out_bytes(f, x.width, x.height) > q.capacity[f]);
                 if (indexed) {
                     head.width = x.width;
@@ -743,7 +787,7 @@ mpc_status ensure_slots(mpc_context* c, int slots) {
 mpc_status decode_sequence(mpc_context* c, const uint8_t* const* bytes, const size_t* nbytes, int n_frames, uint8_t** rgb,
                            uint8_t* const* d_rgb, const size_t* capacity, int* width, int* height, bool single = false,
                            const uint8_t* const* indexes = nullptr, const size_t* index_bytes = nullptr, int* routes = nullptr,
-                           const mpc_rect* rects = nullptr, unsigned region_flags = 0) {
+                           const mpc_rect* rects = nullptr, unsigned region_flags = 0, const mpc_view* views = nullptr) {
     if (indexes && !index_bytes) return fail(MPC_ERR_ARGUMENT, "null argument");
     if (!c || !bytes || !nbytes || !width || !height || (!rgb && !d_rgb) || (d_rgb && !capacity)) return fail(MPC_ERR_ARGUMENT, "null argument");
     if (n_frames < 1) return fail(MPC_ERR_ARGUMENT, "n_frames must be at least 1");
@@ -759,7 +803,11 @@ mpc_status decode_sequence(mpc_context* c, const uint8_t* const* bytes, const si
             if (mpc::container_info(bytes[f], nbytes[f], &w, &h, &K, &bs) && !mpc::tile_window(w, h, bs, r.x, r.y, r.width, r.height, win))
                 return fail(MPC_ERR_ARGUMENT, "frame %d: rectangle %dx%d at (%d, %d) is not inside a frame of %dx%d", f, r.width, r.height, r.x,
                             r.y, w, h);
-            if (d_rgb && static_cast<size_t>(r.width) * static_cast<size_t>(r.height) * 3 > capacity[f])
+            if (views) {
+                const int vw = view_extent(r.width, views[f].scale_log2), vh = view_extent(r.height, views[f].scale_log2);
+                if (d_rgb && static_cast<size_t>(vw) * static_cast<size_t>(vh) * 3 > capacity[f])
+                    return fail(MPC_ERR_ARGUMENT, "frame %d: capacity %zu for a view of %dx%d", f, capacity[f], vw, vh);
+            } else if (d_rgb && static_cast<size_t>(r.width) * static_cast<size_t>(r.height) * 3 > capacity[f])
                 return fail(MPC_ERR_ARGUMENT, "frame %d: capacity %zu for a rectangle of %dx%d", f, capacity[f], r.width, r.height);
         }
     else if (d_rgb)                                                 // before anything is enqueued; a header that does not parse fails in its turn
@@ -786,6 +834,7 @@ mpc_status decode_sequence(mpc_context* c, const uint8_t* const* bytes, const si
     q.routes = routes;
     q.rects = rects;
     q.parse_all = (region_flags & MPC_REGION_PARSE_ALL) != 0;
+    q.views = views;
     if (routes) std::fill(routes, routes + n_frames, 1);
     q.width = width;
     q.height = height;
@@ -882,13 +931,54 @@ mpc_status mpc_decode_regions_indexed_device(mpc_context* c, const uint8_t* cons
     });
 }
 
+namespace {
+// The views' arguments checked ("frame N: ...") and their rectangles resolved against the containers' headers, then the sequence.  A
+// frame whose header does not parse gets a placeholder: it fails in its turn, as in every other call
+mpc_status decode_views(mpc_context* c, const uint8_t* const* bytes, const size_t* nbytes, const uint8_t* const* indexes, const size_t* index_bytes,
+                        const mpc_view* views, int n_frames, unsigned flags, uint8_t** rgb, uint8_t* const* d_rgb, const size_t* capacity,
+                        int* width, int* height, int* routes) {
+    if (!views || !bytes || !nbytes) return fail(MPC_ERR_ARGUMENT, "null argument");
+    if (flags & ~MPC_VIEW_PARSE_ALL) return fail(MPC_ERR_ARGUMENT, "flags 0x%x", flags);
+    if (n_frames < 1) return fail(MPC_ERR_ARGUMENT, "n_frames must be at least 1");
+    std::vector<mpc_rect> rects(static_cast<size_t>(n_frames));
+    for (int f = 0; f < n_frames; ++f) {
+        if (!bytes[f]) return fail(MPC_ERR_ARGUMENT, "frame %d: null argument", f);
+        if (const char* why = view_argument_error(views[f])) return fail(MPC_ERR_ARGUMENT, "frame %d: %s", f, why);
+        int w, h, K, bs;
+        rects[static_cast<size_t>(f)] = mpc::container_info(bytes[f], nbytes[f], &w, &h, &K, &bs) ? view_rect(views[f], w, h) : mpc_rect{0, 0, 1, 1};
+    }
+    static_assert(MPC_VIEW_PARSE_ALL == MPC_REGION_PARSE_ALL, "the sequence knows one parse-all flag");
+    return decode_sequence(c, bytes, nbytes, n_frames, rgb, d_rgb, capacity, width, height, false, indexes, index_bytes, routes, rects.data(),
+                           flags, views);
+}
+}  // namespace
+
+mpc_status mpc_decode_views_indexed(mpc_context* c, const uint8_t* const* bytes, const size_t* nbytes, const uint8_t* const* indexes,
+                                    const size_t* index_bytes, const mpc_view* views, int n_frames, unsigned flags, uint8_t** rgb, int* width,
+                                    int* height, int* routes) {
+    return guarded([&]() -> mpc_status {
+        if (!rgb) return fail(MPC_ERR_ARGUMENT, "null argument");
+        return decode_views(c, bytes, nbytes, indexes, index_bytes, views, n_frames, flags, rgb, nullptr, nullptr, width, height, routes);
+    });
+}
+
+mpc_status mpc_decode_views_indexed_device(mpc_context* c, const uint8_t* const* bytes, const size_t* nbytes, const uint8_t* const* indexes,
+                                           const size_t* index_bytes, const mpc_view* views, int n_frames, unsigned flags,
+                                           uint8_t* const* d_rgb, const size_t* capacity, int* width, int* height, int* routes) {
+    return guarded([&]() -> mpc_status {
+        if (!d_rgb) return fail(MPC_ERR_ARGUMENT, "null argument");
+        return decode_views(c, bytes, nbytes, indexes, index_bytes, views, n_frames, flags, nullptr, d_rgb, capacity, width, height, routes);
+    });
+}
+
 }  // extern "C"
 
 namespace {
 // mpc_parse_container_window_device (symbols, n_symbols, ranges) and mpc_window_chunks_device (chunks): one run of the device half
 mpc_status window_on_device(mpc_context* c, const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes,
                             const mpc_rect* rect, unsigned flags, uint16_t** symbols, size_t* n_symbols, uint64_t* ranges, uint64_t* chunks,
-                            int* route) {
+                            int* route, int steps = 0) {
+    // steps (mpc_parse_container_view_device, never with `chunks`): a view's, 0 = every step
     return guarded([&]() -> mpc_status {
         if (!c || !bytes || !index || !rect || !route || (chunks ? false : !symbols || !n_symbols || !ranges)) return fail(MPC_ERR_ARGUMENT, "null argument");
         if (flags & ~MPC_REGION_PARSE_ALL) return fail(MPC_ERR_ARGUMENT, "flags 0x%x", flags);
@@ -915,7 +1005,7 @@ mpc_status window_on_device(mpc_context* c, const uint8_t* bytes, size_t nbytes,
             }
             std::vector<uint16_t> got;
             std::vector<uint64_t> r;
-            const int verdict = mpc::read_window_by_index(bytes, nbytes, nullptr, 0, rect->x, rect->y, rect->width, rect->height, parse_all, got, r, route);
+            const int verdict = mpc::read_window_by_index(bytes, nbytes, nullptr, 0, rect->x, rect->y, rect->width, rect->height, parse_all, got, r, route, steps);
             if (verdict == 1) return fail(MPC_ERR_BITSTREAM, "Invalid input data");
             if (verdict == 2)
                 return fail(MPC_ERR_ARGUMENT, "rectangle %dx%d at (%d, %d) is empty or not inside the frame", rect->width, rect->height, rect->x, rect->y);
@@ -923,8 +1013,9 @@ mpc_status window_on_device(mpc_context* c, const uint8_t* bytes, size_t nbytes,
             return give(got);
         };
         ParsePlan pp;
-        if (!plan_parse(bytes, nbytes, index, index_bytes, false, pp)) return serial();
+        if (!plan_parse(bytes, nbytes, index, index_bytes, false, pp, parse_all ? 0 : steps)) return serial();
         const mpc::ContainerIndex& x = pp.ip.index;
+        const int kept = view_steps(steps, x.K);                    // the lengths are cut to it on the device, unless "parse all"
         mpc::TileWindow win;
         if (!mpc::tile_window(x.width, x.height, x.block_size, rect->x, rect->y, rect->width, rect->height, win)) return serial();
         std::lock_guard<std::recursive_mutex> one_host_call(c->host_calls);
@@ -963,7 +1054,9 @@ mpc_status window_on_device(mpc_context* c, const uint8_t* bytes, size_t nbytes,
         if (const mpc_status us = upload_and_parse(slot, j, pp, bytes, nbytes, &pa, cut); us != MPC_OK) return us;
         behind_layout(j.d_behind);
         result_layout(j.h_result);
-        if (const mpc_status ws = parse_and_unpack_window(slot, j, pp, pa, sa, d_window, win, parse_all, d_span, chunks != nullptr); ws != MPC_OK)
+        if (const mpc_status ws = parse_and_unpack_window(slot, j, pp, pa, sa, d_window, win, parse_all, d_span, chunks != nullptr,
+                                                          !parse_all && kept < K ? kept : 0);
+            ws != MPC_OK)
             return ws;
         hipStream_t st = slot.stream;
         HIP_TRY(hipMemcpyAsync(j.h_flags, j.ua.error, 3 * sizeof(int), hipMemcpyDeviceToHost, st));
@@ -986,9 +1079,12 @@ mpc_status window_on_device(mpc_context* c, const uint8_t* bytes, size_t nbytes,
         if (j.h_flags[2] != 0 || j.h_flags[0] != 0) return serial();
         // the window's slice of every expanded stream; (r0, r1) are the device's, held to the host's sizes
         std::vector<uint16_t> got(h_counts, h_counts + n_counts);
+        for (uint16_t& length : got) length = std::min<uint16_t>(length, static_cast<uint16_t>(kept));     // "parse all": not cut on the device
         for (size_t i = 0; i < n_streams; ++i) {
             const mpc::UnpackStream& us = pp.unpack.table[i];
-            const unsigned long long r1 = std::min<unsigned long long>(h_window[i].r1, us.expect), r0 = std::min<unsigned long long>(h_window[i].r0, r1);
+            const bool cut_away = static_cast<int>((i % (2 * static_cast<size_t>(K))) / 2) >= kept;          // ... nor are its ranks
+            const unsigned long long r1 = cut_away ? 0 : std::min<unsigned long long>(h_window[i].r1, us.expect),
+                                     r0 = std::min<unsigned long long>(h_window[i].r0, r1);
             got.insert(got.end(), h_symbols + us.out_off + r0, h_symbols + us.out_off + r1);
             ranges[2 * (i / 2)] = r0;
             ranges[2 * (i / 2) + 1] = r1;
@@ -1006,6 +1102,23 @@ mpc_status mpc_parse_container_window_device(mpc_context* c, const uint8_t* byte
                                              int* route) {
     if (!symbols || !n_symbols || !ranges) return guarded([&]() -> mpc_status { return fail(MPC_ERR_ARGUMENT, "null argument"); });
     return window_on_device(c, bytes, nbytes, index, index_bytes, rect, flags, symbols, n_symbols, ranges, nullptr, route);
+}
+
+mpc_status mpc_parse_container_view_device(mpc_context* c, const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes,
+                                           const mpc_view* view, unsigned flags, uint16_t** symbols, size_t* n_symbols, uint64_t* ranges,
+                                           int* route) {
+    mpc_rect rect{};
+    const mpc_status args = guarded([&]() -> mpc_status {
+        if (!bytes || !view || !symbols || !n_symbols || !ranges) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (const char* why = view_argument_error(*view)) return fail(MPC_ERR_ARGUMENT, "%s", why);
+        int w, h, K, bs;
+        if (!mpc::container_info(bytes, nbytes, &w, &h, &K, &bs)) return fail(MPC_ERR_BITSTREAM, "Invalid input data");
+        rect = view_rect(*view, w, h);
+        return MPC_OK;
+    });
+    if (args != MPC_OK) return args;
+    static_assert(MPC_VIEW_PARSE_ALL == MPC_REGION_PARSE_ALL, "window_on_device knows one parse-all flag");
+    return window_on_device(c, bytes, nbytes, index, index_bytes, &rect, flags, symbols, n_symbols, ranges, nullptr, route, view->steps);
 }
 
 mpc_status mpc_window_chunks_device(mpc_context* c, const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes,

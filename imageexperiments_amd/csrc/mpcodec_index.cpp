@@ -188,4 +188,45 @@ mpc_status mpc_parse_container_window_by_index(const uint8_t* bytes, size_t nbyt
     });
 }
 
+mpc_status mpc_truncate_container(const uint8_t* bytes, size_t nbytes, int steps, uint8_t** out, size_t* out_bytes) {
+    return guarded([&]() -> mpc_status {
+        if (!bytes || !out || !out_bytes) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (steps < 1) return fail(MPC_ERR_ARGUMENT, "steps must be at least 1");
+        std::vector<uint8_t> cut;
+        if (!mpc::truncate_container(bytes, nbytes, steps, cut)) return fail(MPC_ERR_BITSTREAM, "Invalid input data");
+        uint8_t* copy = static_cast<uint8_t*>(std::malloc(cut.empty() ? 1 : cut.size()));
+        if (!copy) return fail(MPC_ERR_ALLOC, "out of memory");
+        if (!cut.empty()) std::memcpy(copy, cut.data(), cut.size());
+        *out = copy;
+        *out_bytes = cut.size();
+        return MPC_OK;
+    });
+}
+
+mpc_status mpc_parse_container_view_by_index(const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes,
+                                             const mpc_view* view, unsigned flags, uint16_t** symbols, size_t* n_symbols, uint64_t* ranges,
+                                             int* route) {
+    return guarded([&]() -> mpc_status {
+        if (!bytes || !index || !view || !symbols || !n_symbols || !ranges || !route) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (flags & ~MPC_VIEW_PARSE_ALL) return fail(MPC_ERR_ARGUMENT, "flags 0x%x", flags);
+        if (const char* why = view_argument_error(*view)) return fail(MPC_ERR_ARGUMENT, "%s", why);
+        int width, height, K, block_size;
+        if (!mpc::container_info(bytes, nbytes, &width, &height, &K, &block_size)) return fail(MPC_ERR_BITSTREAM, "Invalid input data");
+        const mpc_rect rect = view_rect(*view, width, height);
+        std::vector<uint16_t> got;
+        std::vector<uint64_t> r;
+        const int verdict = mpc::read_window_by_index(bytes, nbytes, index, index_bytes, rect.x, rect.y, rect.width, rect.height,
+                                                      (flags & MPC_VIEW_PARSE_ALL) != 0, got, r, route, view->steps);
+        if (verdict == 1) return fail(MPC_ERR_BITSTREAM, "Invalid input data");
+        if (verdict == 2) return fail(MPC_ERR_ARGUMENT, "rectangle %dx%d at (%d, %d) is empty or not inside the frame", rect.width, rect.height, rect.x, rect.y);
+        uint16_t* out = static_cast<uint16_t*>(std::malloc(got.empty() ? 2 : 2 * got.size()));
+        if (!out) return fail(MPC_ERR_ALLOC, "out of memory");
+        if (!got.empty()) std::memcpy(out, got.data(), 2 * got.size());
+        std::memcpy(ranges, r.data(), sizeof(uint64_t) * r.size());
+        *symbols = out;
+        *n_symbols = got.size();
+        return MPC_OK;
+    });
+}
+
 }  // extern "C"

@@ -562,6 +562,71 @@ mpc_status mpc_window_chunks_by_index(const uint8_t* bytes, size_t nbytes, const
 mpc_status mpc_window_chunks_device(mpc_context* ctx, const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes,
                                     const mpc_rect* rect, unsigned flags, uint64_t* chunks /* [6K][2] */, int* route);
 
+/* ---- views: the first n steps, reduced 2/4/8x, of a frame or a rectangle of it ("Decoder: views") ----
+ * The container is layered by pursuit step: stream 1 + 2K*ch + 2i and the one behind it hold step i of every tile-channel that has
+ * it, and a tile-channel has step i exactly when its length exceeds i.
+ *
+ * mpc_truncate_container: the container of the same frame cut to its first `steps` steps -- the product's rate-scalable transcode
+ * (a lower-rate file without encoding again).  Host only, no context.  The input is parsed with mpc_read_compressed; every length
+ * becomes min(length, steps); the streams of steps below `steps` are kept (the same symbols), those of steps at or above it are
+ * emptied; header, K and the quantiser table are kept; the result is written by the one host coder.  steps >= K: a copy of what
+ * coding the parsed container again gives, for an encoder's container the input itself.  steps < 1: MPC_ERR_ARGUMENT.  Whatever
+ * mpc_read_compressed refuses: MPC_ERR_BITSTREAM.  out: mpc_free.  (The kept streams are unchanged as symbols for whatever an encoder
+ * writes.  A damaged container whose step-0 coefficient sums move by 2^15 or more from tile to tile is not: the difference coder keeps
+ * 16 bits of a 17-bit zig-zag code, in the reference's writer as here.  A view reads such sums as the decoder does.)
+ *
+ * A view of a frame is a rectangle of it, reconstructed from the first `steps` records of every tile-channel and reduced by
+ * c = 2^scale_log2:
+ *   steps       0 = all; < 0 is MPC_ERR_ARGUMENT; above the container's K acts as K.  The pixels, statuses and error texts of a view
+ *               with steps = m are those of a decode of mpc_truncate_container(m): a tile-channel's dynamic dictionary is built from
+ *               its first m choices only, so a record outside the dictionary at a step at or above m no longer refuses, and a record
+ *               below m whose block only a step at or above m unlocks does ("Invalid bitstream").
+ *   scale_log2  0 ... 3, else MPC_ERR_ARGUMENT; rect.x and rect.y must be multiples of c (else MPC_ERR_ARGUMENT), width and height
+ *               are free.  The output is ceil(height / c) rows of ceil(width / c) pixels x 3 bytes, tightly packed.  Output pixel
+ *               (i, j) covers the full-resolution pixels of the cell [x + i*c, x + (i+1)*c) x [y + j*c, y + (j+1)*c) that lie inside
+ *               the rectangle, n of them, 1 <= n <= c*c; per colour channel its value is (sum + n/2) / n in integers over the STORED
+ *               8-bit values (after RGBFromYUV's rounding and clamp).
+ *   rect        width == 0 && height == 0 with x = y = 0: the whole frame; otherwise the rules of mpc_decode_regions_indexed.
+ * A view with steps = 0 and scale_log2 = 0 equals mpc_decode_regions_indexed of the same rectangle, pixel for pixel.
+ * width[f] / height[f] receive the output's size.  A capacity below 3 * ceil(w / c) * ceil(h / c) is MPC_ERR_ARGUMENT, reported before
+ * anything is enqueued ("frame N: ..."), as are the argument errors above and a rectangle outside the frame.
+ *
+ * Routes.  0 needs a usable index of version 1 or 2 and runs the region decoder's order (see above) with every stream of a step at
+ * or above `steps` given an empty chunk range: it is neither parsed, unpacked nor gathered.  The lengths stream is parsed whole and
+ * the stream sizes recomputed from the UNCUT lengths are compared with the index's; only behind that check are the lengths cut (on
+ * the device, in place), and the host's stream tables hold the cut streams empty, so every bound still comes from the host's
+ * tables, never from a symbol's value.  1 (no index, a refused index, "serial only"): the serial parse of the whole container, the
+ * lengths and streams cut on the host as the truncation cuts them (a cut stream is first held to the size the lengths give it, as
+ * mpc_read_compressed holds it), then the ordinary upload, unpack and gather and the same reconstruction: no full-size frame exists
+ * on either route.
+ *
+ * What is trusted.  Without MPC_VIEW_PARSE_ALL the statement of the regions section holds, extended by "streams of steps >= steps":
+ * like the chunks outside the window they are never read on route 0, so a container damaged only there still yields its view.
+ * With MPC_VIEW_PARSE_ALL every chunk of every stream is parsed and every packed stream expanded, the whole-frame acceptance rule
+ * applies unchanged, and only the stages behind the parse are windowed and cut. */
+typedef struct mpc_view { mpc_rect rect; int steps; int scale_log2; } mpc_view;
+#define MPC_VIEW_PARSE_ALL 1u
+mpc_status mpc_truncate_container(const uint8_t* bytes, size_t nbytes, int steps, uint8_t** out, size_t* out_bytes);
+mpc_status mpc_decode_views_indexed(mpc_context* ctx, const uint8_t* const* bytes, const size_t* nbytes, const uint8_t* const* indexes,
+                                    const size_t* index_bytes, const mpc_view* views, int n_frames, unsigned flags, uint8_t** rgb,
+                                    int* width, int* height, int* routes);
+mpc_status mpc_decode_views_indexed_device(mpc_context* ctx, const uint8_t* const* bytes, const size_t* nbytes,
+                                           const uint8_t* const* indexes, const size_t* index_bytes, const mpc_view* views, int n_frames,
+                                           unsigned flags, uint8_t* const* d_rgb, const size_t* capacity, int* width, int* height,
+                                           int* routes);
+/* The host definition of the device parse of a view, the role mpc_parse_container_window_by_index plays for regions: by
+ * construction the windowed parse of the truncated container, from this container and its own index.  symbols (mpc_free): the
+ * lengths CUT to `steps`, then for each of the 6K streams its expanded symbols [r0, r1) of the window; a stream of a step at or
+ * above `steps` is empty, r0 = r1 = 0.  ranges[3K][2], route, statuses as for mpc_parse_container_window_by_index;
+ * view->scale_log2 is checked and otherwise unused. */
+mpc_status mpc_parse_container_view_by_index(const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes,
+                                             const mpc_view* view, unsigned flags, uint16_t** symbols, size_t* n_symbols,
+                                             uint64_t* ranges, int* route);
+/* The device half (upload, lengths parse, lengths cut, rank, windowed parse, windowed unpack), for tests: host buffers in and out. */
+mpc_status mpc_parse_container_view_device(mpc_context* ctx, const uint8_t* bytes, size_t nbytes, const uint8_t* index,
+                                           size_t index_bytes, const mpc_view* view, unsigned flags, uint16_t** symbols,
+                                           size_t* n_symbols, uint64_t* ranges, int* route);
+
 /* ---- "-s" patch statistics, Compression.cpp:200-302 ----
  * The reference seeds one std::mt19937, and for every image draws `patches` origins x = rand() % (width - bs),
  * y = rand() % (height - bs), runs CalcMPDynamic on the Y, U and V patch with every quantiser 1.0 and feeds
