@@ -782,9 +782,15 @@ class CompressionContext:
     # -- hot path --------------------------------------------------------------------------------
     def encode_tiles(self, rgb, tile_row_begin=0, tile_row_end=None, quant=None):
         """Host-buffer form. rgb: uint8 [H,W,3]. Returns counts[T,3], choices[T,3,K] (structured),
-        energy[T,3], swept[T,3]; tile t = tx*rows + (ty - tile_row_begin)."""
-        rgb = np.ascontiguousarray(rgb, np.uint8)
+        energy[T,3], swept[T,3]; tile t = tx*rows + (ty - tile_row_begin).
+        A view whose pixels are contiguous within a row (strides[1:] == (3, 1), e.g. a window of a larger image) is passed as
+        it is, strides[0] as row_stride, without a copy; anything else is made contiguous first."""
+        rgb = np.asarray(rgb)
+        if not (rgb.dtype == np.uint8 and rgb.ndim == 3 and rgb.shape[2] == 3 and rgb.strides[1:] == (3, 1)
+                and rgb.strides[0] >= 3 * rgb.shape[1]):
+            rgb = np.ascontiguousarray(rgb, np.uint8)
         H, W = rgb.shape[:2]
+        row_stride = rgb.strides[0]
         ty = (H + 7) // 8
         tx = (W + 7) // 8
         tile_row_end = ty if tile_row_end is None else tile_row_end
@@ -797,7 +803,7 @@ class CompressionContext:
         if quant is not None:
             quant = np.ascontiguousarray(quant, np.float64).reshape(3, self.K)
             qp = quant.ctypes.data_as(_dp)
-        _check(self.L.mpc_encode_tiles(self.h, rgb.ctypes.data_as(_u8p), W, H, 3 * W, tile_row_begin, tile_row_end, qp,
+        _check(self.L.mpc_encode_tiles(self.h, rgb.ctypes.data_as(_u8p), W, H, row_stride, tile_row_begin, tile_row_end, qp,
                                        counts.ctypes.data_as(_u16p), choices.ctypes.data_as(C.c_void_p),
                                        energy.ctypes.data_as(_dp), swept.ctypes.data_as(_u32p)))
         return counts, choices, energy, swept

@@ -447,17 +447,15 @@ mpc_status run_pursuit(mpc_context* c, const Tuning& t, const mpc::FrameInput& i
     }
     return MPC_OK;
 }
-}  // namespace
 
-// whole_frame_order: the records go where one launch over the whole frame would put them (FrameInput::out_tile_rows) and the
-// caller has zeroed d_choices for the whole frame (stripes of one frame encoded one by one, encode_sequence's single frames)
-mpc_status encode_batch_device(mpc_context* c, const Tuning& t, const uint8_t* d_rgb, int frames, size_t frame_stride, int width,
-                               int height, size_t row_stride, int tile_row_begin, int tile_row_end, const double* quant,
-                               uint16_t* d_counts, mpc_basis_choice* d_choices, double* d_energy, uint32_t* d_swept, void* stream,
-                               bool whole_frame_order) {
+// What every tile encoder refuses before it touches a frame, the caller's or its own: context, pointers, geometry, stride, tile
+// rows, batch.  The host form checks with this BEFORE it reads the caller's memory, the device forms before anything is enqueued.
+mpc_status check_encode_args(const mpc_context* c, const uint8_t* rgb, int frames, size_t frame_stride, int width, int height,
+                             size_t row_stride, int tile_row_begin, int tile_row_end, const uint16_t* counts,
+                             const mpc_basis_choice* choices) {
     if (!c) return fail(MPC_ERR_ARGUMENT, "null context");
     if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback");
-    if (!d_rgb || !d_counts || !d_choices) return fail(MPC_ERR_ARGUMENT, "null buffer");
+    if (!rgb || !counts || !choices) return fail(MPC_ERR_ARGUMENT, "null buffer");
     if (width < 1 || height < 1 || row_stride < static_cast<size_t>(3) * width)
         return fail(MPC_ERR_ARGUMENT, "bad geometry %dx%d stride %zu", width, height, row_stride);
     const int tiles_x = (width + 7) / 8, tiles_y = (height + 7) / 8;
@@ -467,6 +465,22 @@ mpc_status encode_batch_device(mpc_context* c, const Tuning& t, const uint8_t* d
         return fail(MPC_ERR_ARGUMENT, "bad batch: %d frames, stride %zu", frames, frame_stride);
     const long long tiles = static_cast<long long>(tiles_x) * (tile_row_end - tile_row_begin) * frames;
     if (tiles * 3 >= (1LL << 31)) return fail(MPC_ERR_ARGUMENT, "batch too large");
+    return MPC_OK;
+}
+}  // namespace
+
+// whole_frame_order: the records go where one launch over the whole frame would put them (FrameInput::out_tile_rows) and the
+// caller has zeroed d_choices for the whole frame (stripes of one frame encoded one by one, encode_sequence's single frames)
+mpc_status encode_batch_device(mpc_context* c, const Tuning& t, const uint8_t* d_rgb, int frames, size_t frame_stride, int width,
+                               int height, size_t row_stride, int tile_row_begin, int tile_row_end, const double* quant,
+                               uint16_t* d_counts, mpc_basis_choice* d_choices, double* d_energy, uint32_t* d_swept, void* stream,
+                               bool whole_frame_order) {
+    if (const mpc_status as = check_encode_args(c, d_rgb, frames, frame_stride, width, height, row_stride, tile_row_begin, tile_row_end,
+                                                d_counts, d_choices);
+        as != MPC_OK)
+        return as;
+    const int tiles_x = (width + 7) / 8, tiles_y = (height + 7) / 8;
+    const long long tiles = static_cast<long long>(tiles_x) * (tile_row_end - tile_row_begin) * frames;
     hipStream_t s = static_cast<hipStream_t>(stream);
     HIP_TRY(hipSetDevice(c->device));
     const double* d_q = nullptr;
@@ -643,16 +657,18 @@ mpc_status mpc_encode_tiles_device(mpc_context* c, const uint8_t* d_rgb, int wid
 mpc_status mpc_encode_tiles(mpc_context* c, const uint8_t* rgb, int width, int height, size_t row_stride,
                             int tile_row_begin, int tile_row_end, const double* quant, uint16_t* counts,
                             mpc_basis_choice* choices, double* energy, uint32_t* swept) {
-    if (!c) return fail(MPC_ERR_ARGUMENT, "null context");
-    if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback");
-    if (!rgb || !counts || !choices) return fail(MPC_ERR_ARGUMENT, "null buffer");
+    // refused before the caller's memory is read
+    if (const mpc_status as = check_encode_args(c, rgb, 1, 0, width, height, row_stride, tile_row_begin, tile_row_end, counts, choices);
+        as != MPC_OK)
+        return as;
     const Tuning t = read_tuning();
     std::lock_guard<std::recursive_mutex> one_host_call(c->host_calls);
     HIP_TRY(hipSetDevice(c->device));
     const int tiles_x = (width + 7) / 8;
     const long long tiles = static_cast<long long>(tiles_x) * (tile_row_end - tile_row_begin);
-    if (tiles <= 0) return fail(MPC_ERR_ARGUMENT, "empty stripe");
-    const size_t img_bytes = row_stride * static_cast<size_t>(height);
+    // the bytes the frame occupies: its last row ends with its last pixel, not with a full stride (a view of a larger image
+    // that ends in the parent's last row has nothing behind it)
+    const size_t img_bytes = static_cast<size_t>(height - 1) * row_stride + static_cast<size_t>(3) * width;
     const size_t n_tc = static_cast<size_t>(tiles) * 3;
     uint8_t* d_rgb;
     uint16_t* d_counts;

@@ -117,6 +117,13 @@ mpc_status mpc_context_get_dictionary(const mpc_context* ctx, double* base, int3
  * Encodes the tile rows [tile_row_begin, tile_row_end) of one RGB frame resident in device memory.
  * d_rgb: row-major, 3 bytes per pixel, `row_stride` bytes between rows (img::image<rgb>, image.h:123-131).
  * Tiles outside the image are zero filled (CompressedImage.cpp:548-552).
+ * The frame's layout (this entry point, the batch form and the host form alike): pixel (x, y) is the 3 bytes at
+ * d_rgb + y * row_stride + 3 * x, row_stride >= 3 * width, so the frame may be a window of a larger image.  Only pixel
+ * bytes are read: the last row needs 3 * width bytes, not a full stride, and the bytes between the end of a row and the
+ * next row (and between the frames of a batch) are never read, whatever they hold.  Any alignment of d_rgb, row_stride
+ * and frame_stride is accepted; a base and strides that are multiples of 8 bytes take a faster pixel fetch.
+ * MPC_ERR_ARGUMENT, with nothing read, enqueued or written: a null pointer, width or height < 1, row_stride < 3 * width,
+ * tile rows not within 0 <= tile_row_begin < tile_row_end <= ceil(height / 8).
  * Outputs (device memory, caller allocated), tile index t = tx * rows + (ty - tile_row_begin), rows =
  * tile_row_end - tile_row_begin, i.e. the reference's x-outer / y-inner order within the stripe:
  *   d_counts [tiles][3]      u16   CalcMPDynamic's return value per channel (Y,U,V)
@@ -134,13 +141,16 @@ mpc_status mpc_encode_tiles_device(mpc_context* ctx, const uint8_t* d_rgb, int w
 
 /* Batch form: `frames` equally sized frames, `frame_stride` bytes apart; the same tile rows of every frame are
  * encoded in ONE launch (BASELINE config 4: batches of frames row-striped across GPUs).
- * Output tile index t = frame * tiles_per_stripe + tx * rows + (ty - tile_row_begin). */
+ * Output tile index t = frame * tiles_per_stripe + tx * rows + (ty - tile_row_begin).
+ * Frame f starts at d_rgb + f * frame_stride; frames = 1 ignores frame_stride.  MPC_ERR_ARGUMENT also for frames < 1 and,
+ * with frames > 1, for frame_stride < row_stride * height. */
 mpc_status mpc_encode_batch_device(mpc_context* ctx, const uint8_t* d_rgb, int frames, size_t frame_stride,
                                    int width, int height, size_t row_stride, int tile_row_begin, int tile_row_end,
                                    const double* quant, uint16_t* d_counts, mpc_basis_choice* d_choices,
                                    double* d_energy, uint32_t* d_swept, int waves, void* stream);
 
-/* Same with host buffers: uploads the frame, runs the kernel, copies the records back, synchronises. */
+/* Same with host buffers: uploads the frame, runs the kernel, copies the records back, synchronises.  The arguments are
+ * checked before rgb is read; then exactly (height - 1) * row_stride + 3 * width bytes are read from it. */
 mpc_status mpc_encode_tiles(mpc_context* ctx, const uint8_t* rgb, int width, int height, size_t row_stride,
                             int tile_row_begin, int tile_row_end, const double* quant,
                             uint16_t* counts, mpc_basis_choice* choices, double* energy, uint32_t* swept);

@@ -4,11 +4,10 @@ north_star's 1e-5 relative tolerance AND bit-exactly (the kernel keeps the oracl
 import numpy as np
 import pytest
 
+from parity_compare import REL_TOL_ENERGY, compare as _compare
 from pursuit_cases import adversarial_vectors as _adversarial_vectors, degenerate_frames, nan_vectors, near_tie_vectors
 
 pytestmark = pytest.mark.gpu
-
-REL_TOL_ENERGY = 1e-5      # BASELINE.json north_star: "within 1e-5 relative for the float residual energy"
 
 
 @pytest.fixture(scope="module")
@@ -34,20 +33,6 @@ def ctx8(gpu):
 def _oracle_records(octx, rgb, quant=None):
     """oracle records re-ordered to the C ABI's order for a full-height stripe (identical: tx*tilesY + ty)."""
     return octx.encode_tiles(rgb, quant=quant)
-
-
-def _compare(gpu_out, ora_out, K):
-    counts, choices, energy, swept = gpu_out
-    ocounts, odelta, ocoef, oenergy, oswept = ora_out
-    assert (counts == ocounts).all(), f"{(counts != ocounts).sum()} count mismatches"
-    # records 0..count inclusive (terminating record) are defined; compare them all
-    idx = np.arange(K)[None, None, :]
-    valid = idx <= np.minimum(ocounts[:, :, None], K - 1)
-    assert (choices["deltaId"][valid] == odelta[valid]).all()
-    assert (choices["intCoeff"][valid] == ocoef[valid]).all()
-    assert (swept == oswept).all()
-    assert np.allclose(energy, oenergy, rtol=REL_TOL_ENERGY, atol=0.0)
-    assert (energy.view(np.uint64) == oenergy.view(np.uint64)).all(), "energy not bit-identical"
 
 
 def test_dictionary_on_host_matches_oracle(ctx32, octx32):
@@ -477,8 +462,8 @@ def test_batch_stripe_launch_equals_oracle(gpu, oracle, world, rank):
     import imageexperiments_amd as ia
     from imageexperiments_amd.sharding import stripe_bounds
     torch = gpu
-    K, W, H = 8, 136, 100                                    # 17 x 13 tiles, ragged in both directions
-    tiles_x, tiles_y = (W + 7) // 8, (H + 7) // 8
+    K, W, H = 8, 136, 100                                    # 17 whole tile columns (3 W % 8 == 0), 13 tile rows, the last ragged;
+    tiles_x, tiles_y = (W + 7) // 8, (H + 7) // 8            # a ragged width in a batch: test_gpu_frame_layouts.py, batch-ragged
     r0, r1 = stripe_bounds(tiles_y, world, rank)
     rows = r1 - r0
     frames = world
