@@ -9,6 +9,9 @@
 #                    damaged indexes (what tests/test_asan_index.py runs)
 #   make asan-encode-index  tests/cpp/asan_encode_index: the encoder's seek index on the host -- the by-plan route that records the
 #                    checkpoints, index_from_plan -- against the parsed index (what tests/test_asan_encode_index.py runs)
+#   make asan-encode-index2  tests/cpp/asan_encode_index2: index version 2 as the encoder emits it -- the by-plan route's aux entries,
+#                    index_from_plan's check of them -- against the parsed index, and aux arrays that contradict the plans (what
+#                    tests/test_asan_encode_index2.py runs)
 #   make asan-region  tests/cpp/asan_region: the windowed parse on the host (a pixel rectangle through the seek index) on damaged
 #                    indexes, damaged containers and rectangles of every kind (what tests/test_asan_region.py runs)
 #   make asan-index2  tests/cpp/asan_index2: index version 2 on the host -- the aux section's builder and reader, the extension of a
@@ -39,6 +42,12 @@ tests/cpp/asan_encode_index_bin: tests/cpp/asan_encode_index.cpp $(wildcard imag
 asan-encode-index: tests/cpp/asan_encode_index_bin
 	ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=print_stacktrace=1 MPC_HOST_THREADS=4 ./tests/cpp/asan_encode_index_bin
 
+tests/cpp/asan_encode_index2_bin: tests/cpp/asan_encode_index2.cpp $(wildcard imageexperiments_amd/csrc/host_*.cpp imageexperiments_amd/csrc/host_*.h)
+	g++ -std=c++17 -O1 -g $(SAN) -ffp-contract=off -pthread -Wall -Wno-unused-function tests/cpp/asan_encode_index2.cpp -o $@
+
+asan-encode-index2: tests/cpp/asan_encode_index2_bin
+	ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=print_stacktrace=1 MPC_HOST_THREADS=4 ./tests/cpp/asan_encode_index2_bin
+
 tests/cpp/asan_region_bin: tests/cpp/asan_region.cpp $(wildcard imageexperiments_amd/csrc/host_*.cpp imageexperiments_amd/csrc/host_*.h)
 	g++ -std=c++17 -O1 -g $(SAN) -ffp-contract=off -pthread -Wall -Wno-unused-function tests/cpp/asan_region.cpp -o $@
 
@@ -65,6 +74,6 @@ asan-oracle: oracle/_build/liboracle_asan.so
 	LD_PRELOAD=$$(gcc -print-file-name=libasan.so) ASAN_OPTIONS=detect_leaks=0 ORACLE_LIB=$(CURDIR)/oracle/_build/liboracle_asan.so \
 	    python -m pytest tests/test_oracle_golden.py -x -q -p no:cacheprovider
 
-asan: asan-host asan-index asan-encode-index asan-region asan-index2 asan-view asan-oracle
+asan: asan-host asan-index asan-encode-index asan-encode-index2 asan-region asan-index2 asan-view asan-oracle
 
-.PHONY: asan asan-host asan-index asan-encode-index asan-region asan-index2 asan-view asan-oracle
+.PHONY: asan asan-host asan-index asan-encode-index asan-encode-index2 asan-region asan-index2 asan-view asan-oracle

@@ -14,6 +14,7 @@ MAX_K = 32
 HIST_BINS = 8192
 
 MPC_OK, MPC_ERR_ARGUMENT, MPC_ERR_NO_DEVICE, MPC_ERR_HIP, MPC_ERR_BITSTREAM, MPC_ERR_ALLOC = range(6)
+MPC_INDEX_EXPANDED = 1                                              # `flags` of mpc_container_index2 and the ...indexed2 encoders
 
 
 class MpcError(RuntimeError):
@@ -137,6 +138,15 @@ def _bind_bitstream(L):
                                                 C.POINTER(C.c_size_t), C.POINTER(_u8p), C.POINTER(C.c_size_t)]
         L.mpc_encode_images_indexed_device.argtypes = [vp, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.POINTER(_u8p),
                                                        C.POINTER(C.c_size_t), C.POINTER(_u8p), C.POINTER(C.c_size_t)]
+        _u, _szp = C.c_uint, C.POINTER(C.c_size_t)
+        L.mpc_assemble_symbol_streams_by_plan_indexed2.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, _dp, _u16p, _u16p, _ullp, C.c_int, _u,
+                                                                   C.POINTER(_u8p), _szp, C.POINTER(_u8p), _szp]
+        L.mpc_code_symbol_streams_device_indexed2.argtypes = [vp, C.c_int, C.c_int, _dp, _u16p, _u16p, _ullp, C.c_int, _u, C.POINTER(_u8p),
+                                                              _szp, C.POINTER(_u8p), _szp, C.POINTER(C.c_int)]
+        L.mpc_encode_images_indexed2.argtypes = [vp, C.POINTER(_u8p), C.c_int, C.c_int, C.c_int, _dp, C.c_int, _u, C.POINTER(_u8p), _szp,
+                                                 C.POINTER(_u8p), _szp]
+        L.mpc_encode_images_indexed2_device.argtypes = [vp, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, _dp, C.c_int, _u,
+                                                        C.POINTER(_u8p), _szp, C.POINTER(_u8p), _szp]
     except AttributeError:
         if not os.environ.get("MPCODEC_LIB"):             # an older build may be loaded for A/B timing only
             raise
@@ -377,18 +387,24 @@ def assemble_symbol_streams(width, height, K, block_size, quant, counts, streams
     return _take_bytes(L, out, n)
 
 
-def assemble_symbol_streams_by_plan_indexed(width, height, K, block_size, quant, counts, streams, interval=0):
+def assemble_symbol_streams_by_plan_indexed(width, height, K, block_size, quant, counts, streams, interval=0, expanded=False):
     """mpc_assemble_symbol_streams_by_plan_indexed: assemble_symbol_streams(by_plan=True) with the container's seek index recorded
     while the codes are written -> (container, index): index == container_index(container, interval), or None for streams
-    that do not hold what `counts` implies (no parser accepts their container)."""
+    that do not hold what `counts` implies (no parser accepts their container).  expanded: index version 2
+    (mpc_assemble_symbol_streams_by_plan_indexed2 with MPC_INDEX_EXPANDED), index == container_index(container, interval,
+    expanded=True)."""
     L = load_library()
     q = np.ascontiguousarray(quant, np.float64).reshape(3 * K)
     cn, cp = _u16(counts)
     symbols, off = _symbol_streams(K, streams)
     out, n, idx, ni = _u8p(), C.c_size_t(0), _u8p(), C.c_size_t(0)
-    _check(L.mpc_assemble_symbol_streams_by_plan_indexed(width, height, K, block_size, q.ctypes.data_as(_dp), cp, symbols.ctypes.data_as(_u16p),
-                                                         off.ctypes.data_as(C.POINTER(C.c_ulonglong)), int(interval), C.byref(out), C.byref(n),
-                                                         C.byref(idx), C.byref(ni)))
+    head = (width, height, K, block_size, q.ctypes.data_as(_dp), cp, symbols.ctypes.data_as(_u16p), off.ctypes.data_as(C.POINTER(C.c_ulonglong)),
+            int(interval))
+    tail = (C.byref(out), C.byref(n), C.byref(idx), C.byref(ni))
+    if expanded:
+        _check(L.mpc_assemble_symbol_streams_by_plan_indexed2(*head, MPC_INDEX_EXPANDED, *tail))
+    else:
+        _check(L.mpc_assemble_symbol_streams_by_plan_indexed(*head, *tail))
     return _take_bytes(L, out, n), (_take_bytes(L, idx, ni) if idx else None)
 
 
@@ -901,30 +917,39 @@ class CompressionContext:
         take = _take_view if views else _take_bytes
         return [take(self.L, outs[i], C.c_size_t(sizes[i])) for i in range(n)]
 
-    def _indexed(self, fn, ptrs, n, width, height, interval, quant):
+    def _indexed(self, fn, ptrs, n, width, height, interval, quant, flags=None):
         qp = None
         if quant is not None:
             quant = np.ascontiguousarray(quant, np.float64).reshape(3, self.K)
             qp = quant.ctypes.data_as(_dp)
         outs, sizes, idx, isizes = (_u8p * n)(), (C.c_size_t * n)(), (_u8p * n)(), (C.c_size_t * n)()
-        _check(fn(self.h, ptrs, n, width, height, qp, int(interval), outs, sizes, idx, isizes))
+        if flags is None:
+            _check(fn(self.h, ptrs, n, width, height, qp, int(interval), outs, sizes, idx, isizes))
+        else:                                                       # the ...indexed2 entry points
+            _check(fn(self.h, ptrs, n, width, height, qp, int(interval), int(flags), outs, sizes, idx, isizes))
         return [(_take_bytes(self.L, outs[i], C.c_size_t(sizes[i])), _take_bytes(self.L, idx[i], C.c_size_t(isizes[i]))) for i in range(n)]
 
-    def encode_images_indexed(self, frames, interval=0, quant=None):
+    def encode_images_indexed(self, frames, interval=0, quant=None, expanded=False):
         """mpc_encode_images_indexed: encode_images with every container's seek index from the entropy stage itself ->
-        [(container, index)], index == container_index(container, interval).  interval: 0 = the default, else 32 ... 65536."""
+        [(container, index)], index == container_index(container, interval).  interval: 0 = the default, else 32 ... 65536.
+        expanded: index version 2 (mpc_encode_images_indexed2 with MPC_INDEX_EXPANDED), the aux entries from the entropy stage as
+        well: index == container_index(container, interval, expanded=True)."""
         frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
         H, W = frames[0].shape[:2]
         if any(f.shape[:2] != (H, W) for f in frames):
             raise ValueError("frames must have the same size")
         n = len(frames)
         ptrs = (_u8p * n)(*[f.ctypes.data_as(_u8p) for f in frames])
+        if expanded:
+            return self._indexed(self.L.mpc_encode_images_indexed2, ptrs, n, W, H, interval, quant, MPC_INDEX_EXPANDED)
         return self._indexed(self.L.mpc_encode_images_indexed, ptrs, n, W, H, interval, quant)
 
-    def encode_images_indexed_device(self, d_frames, width, height, interval=0, quant=None):
+    def encode_images_indexed_device(self, d_frames, width, height, interval=0, quant=None, expanded=False):
         """mpc_encode_images_indexed_device: the same for frames in device memory (as encode_images_device takes them)."""
         n = len(d_frames)
         ptrs = (C.c_void_p * n)(*[C.c_void_p(int(p)) for p in d_frames])
+        if expanded:
+            return self._indexed(self.L.mpc_encode_images_indexed2_device, ptrs, n, width, height, interval, quant, MPC_INDEX_EXPANDED)
         return self._indexed(self.L.mpc_encode_images_indexed_device, ptrs, n, width, height, interval, quant)
 
     def encode_image_device(self, d_rgb, width, height, quant=None):
@@ -1177,9 +1202,10 @@ class CompressionContext:
                                                      off.ctypes.data_as(C.POINTER(C.c_ulonglong)), C.byref(out), C.byref(n), C.byref(route)))
         return _take_bytes(self.L, out, n), route.value
 
-    def code_symbol_streams_device_indexed(self, width, height, counts, streams, interval=0, quant=None):
+    def code_symbol_streams_device_indexed(self, width, height, counts, streams, interval=0, quant=None, expanded=False):
         """mpc_code_symbol_streams_device_indexed: code_symbol_streams_device with the container's seek index ->
-        (container, index or None, route); None for streams that do not hold what `counts` implies."""
+        (container, index or None, route); None for streams that do not hold what `counts` implies.  expanded: index version 2
+        (mpc_code_symbol_streams_device_indexed2 with MPC_INDEX_EXPANDED)."""
         qp = None
         if quant is not None:
             quant = np.ascontiguousarray(quant, np.float64).reshape(3, self.K)
@@ -1187,9 +1213,12 @@ class CompressionContext:
         cn, cp = _u16(counts)
         symbols, off = _symbol_streams(self.K, streams)
         out, n, idx, ni, route = _u8p(), C.c_size_t(0), _u8p(), C.c_size_t(0), C.c_int(-1)
-        _check(self.L.mpc_code_symbol_streams_device_indexed(self.h, width, height, qp, cp, symbols.ctypes.data_as(_u16p),
-                                                             off.ctypes.data_as(C.POINTER(C.c_ulonglong)), int(interval), C.byref(out),
-                                                             C.byref(n), C.byref(idx), C.byref(ni), C.byref(route)))
+        head = (self.h, width, height, qp, cp, symbols.ctypes.data_as(_u16p), off.ctypes.data_as(C.POINTER(C.c_ulonglong)), int(interval))
+        tail = (C.byref(out), C.byref(n), C.byref(idx), C.byref(ni), C.byref(route))
+        if expanded:
+            _check(self.L.mpc_code_symbol_streams_device_indexed2(*head, MPC_INDEX_EXPANDED, *tail))
+        else:
+            _check(self.L.mpc_code_symbol_streams_device_indexed(*head, *tail))
         return _take_bytes(self.L, out, n), (_take_bytes(self.L, idx, ni) if idx else None), route.value
 
     def container_job_begin(self, slot, d_counts, d_choices, width, height, quant=None, stream=0):

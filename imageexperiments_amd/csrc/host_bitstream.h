@@ -247,10 +247,15 @@ struct PlannedStream {                              // one per stream, the lengt
 // checkpoints: stream behind stream, ceil(eff_n / interval) each (the blob's own order).  The blob build_container_index gives
 // for that container, provided the streams hold what the lengths stream implies (streams_match_lengths) and no Huffman code is
 // longer than 32 bits.  false = the positions contradict the plans (head_bits, stream behind stream, checkpoints in order);
-// `blob` is then empty
+// `blob` is then empty.
+// expanded: index version 2, with aux (n_aux entries of two words, out then prev | dc << 16 | state << 32) the entries of the streams
+// that have any (index_stream_has_aux), stream behind stream, ceil(eff_n / interval) each: the blob
+// build_container_index(..., expanded) gives.  false as well where the entries contradict the plans: not exactly that many,
+// out[0] != 0, out not strictly increasing or beyond the stream's size, a state above 2, out[c] != c * interval for a stream that
+// is not packed (and whatever else read_container_index would refuse in the blob)
 bool index_from_plan(uint32_t interval, size_t nbytes, int width, int height, int K, int block_size, size_t head_bits,
                      const StreamPlan* plans, const PlannedStream* streams, int n_streams, const uint64_t* checkpoints,
-                     std::vector<uint8_t>& blob);
+                     std::vector<uint8_t>& blob, bool expanded = false, const uint64_t* aux = nullptr, size_t n_aux = 0);
 // every one of the 6K streams holds as many symbols as the lengths stream implies (expected_sizes): what the serial parser
 // goes by.  lengths[3 * tiles], off[6K + 1]
 bool streams_match_lengths(const uint16_t* lengths, size_t tiles, int K, const unsigned long long* off);
@@ -303,10 +308,13 @@ uint8_t* encode_symbol_streams_by_plan_malloc(int width, int height, int K, int 
 
 // The same container together with its seek index, the checkpoints recorded while the codes are written: this defines what
 // the device's code kernel records (mp_entropy.hip).  Streams that do not match the lengths stream: the container alone,
-// `index` empty.  A Huffman code longer than 32 bits: build_container_index of the finished container.  interval: 32 ... 65536
+// `index` empty.  A Huffman code longer than 32 bits: build_container_index of the finished container.  interval: 32 ... 65536.
+// expanded: index version 2, the aux entries by index_aux_pass over the coded streams this route holds -- which defines what the
+// device's pack pass and sum kernels compute
 uint8_t* encode_symbol_streams_by_plan_indexed_malloc(int width, int height, int K, int block_size, const double* quant,
                                                       const uint16_t* counts, const uint16_t* symbols, const unsigned long long* off,
-                                                      uint32_t interval, size_t* nbytes, std::vector<uint8_t>& index);
+                                                      uint32_t interval, size_t* nbytes, std::vector<uint8_t>& index,
+                                                      bool expanded = false);
 
 // Inverse of encode_records_malloc's gathering: per-tile records in the reference's visiting order.  counts[3*tiles],
 // choices[3*tiles*K] (deltaId | intCoeff << 16, zero beyond count).  false = streams inconsistent with `lengths`.

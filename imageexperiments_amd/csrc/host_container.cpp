@@ -223,16 +223,22 @@ uint8_t* encode_symbol_streams_malloc(int width, int height, int K, int block_si
 // host: per-stream statistics -> plan_stream -> codes at the planned bit offsets -> OR the pieces into place.  Exists so that
 // the planning half can be checked against the direct route without a GPU (tests/test_host_bitstream.py).
 namespace {
+void index_aux_pass(const uint16_t* v, size_t n, uint32_t interval, bool packed, bool dc, std::vector<IndexAux>& aux);
+
 // interval 0: the container alone.  Otherwise cps gets, stream behind stream, the container bit of every interval-th coded
-// symbol, and `planned` where each stream's codes begin; *wide: a Huffman code longer than 32 bits, nothing recorded
+// symbol, and `planned` where each stream's codes begin; *wide: a Huffman code longer than 32 bits, nothing recorded.  auxs
+// (optional, with an interval): index version 2's aux entries of the streams that have any, stream behind stream, two words each
+// as the blob holds them -- index_aux_pass over the coded symbols, which is what the device's pack pass and sums must equal
 uint8_t* encode_by_plan(int width, int height, int K, int block_size, const double* quant, const uint16_t* counts, const uint16_t* symbols,
                         const unsigned long long* off, uint32_t interval, size_t* nbytes, std::vector<StreamPlan>& plans,
-                        std::vector<PlannedStream>& planned, std::vector<uint64_t>& cps, bool* wide) {
+                        std::vector<PlannedStream>& planned, std::vector<uint64_t>& cps, bool* wide,
+                        std::vector<uint64_t>* auxs = nullptr) {
     const size_t tiles = tile_count(width, height, block_size);
     const int S = 6 * K + 1;
     plans.assign(static_cast<size_t>(S), StreamPlan());
     planned.assign(static_cast<size_t>(S), PlannedStream());
     cps.clear();
+    if (auxs) auxs->clear();
     *wide = false;
     std::vector<BitWriter> payload(static_cast<size_t>(S));
     size_t bit = container_head(width, height, K, block_size, quant).bit_size();
@@ -262,6 +268,14 @@ uint8_t* encode_by_plan(int width, int height, int K, int block_size, const doub
         ps.shorter = shorter;
         if (p.mode == 0 && p.max_code_length > 32) *wide = true;
         const bool record = interval != 0 && !*wide;
+        if (record && auxs && index_stream_has_aux(static_cast<size_t>(j), K, shorter)) {
+            std::vector<IndexAux> entries;
+            index_aux_pass(coded, coded_n, interval, shorter, (j - 1) % (2 * K) == 1, entries);
+            for (const IndexAux& e : entries) {
+                auxs->push_back(e.out);
+                auxs->push_back(static_cast<uint64_t>(e.prev) | (static_cast<uint64_t>(e.dc) << 16) | (static_cast<uint64_t>(e.state) << 32));
+            }
+        }
         BitWriter& w = payload[static_cast<size_t>(j)];
         if (p.mode == 0) {
             std::vector<uint32_t> code_of(static_cast<size_t>(largest) + 1, 0);
@@ -314,20 +328,20 @@ uint8_t* encode_symbol_streams_by_plan_malloc(int width, int height, int K, int 
 
 uint8_t* encode_symbol_streams_by_plan_indexed_malloc(int width, int height, int K, int block_size, const double* quant,
                                                       const uint16_t* counts, const uint16_t* symbols, const unsigned long long* off,
-                                                      uint32_t interval, size_t* nbytes, std::vector<uint8_t>& index) {
+                                                      uint32_t interval, size_t* nbytes, std::vector<uint8_t>& index, bool expanded) {
     index.clear();
     const bool consistent = streams_match_lengths(counts, tile_count(width, height, block_size), K, off);
     std::vector<StreamPlan> plans;
     std::vector<PlannedStream> planned;
-    std::vector<uint64_t> cps;
+    std::vector<uint64_t> cps, auxs;
     bool wide = false;
     uint8_t* dst = encode_by_plan(width, height, K, block_size, quant, counts, symbols, off, consistent ? interval : 0, nbytes, plans,
-                                  planned, cps, &wide);
+                                  planned, cps, &wide, expanded ? &auxs : nullptr);
     if (!dst || !consistent) return dst;
     const size_t head_bits = container_head(width, height, K, block_size, quant).bit_size();
-    const bool ok = wide ? build_container_index(dst, *nbytes, interval, index)
+    const bool ok = wide ? build_container_index(dst, *nbytes, interval, index, expanded)
                          : index_from_plan(interval, *nbytes, width, height, K, block_size, head_bits, plans.data(), planned.data(),
-                                           6 * K + 1, cps.data(), index);
+                                           6 * K + 1, cps.data(), index, expanded, auxs.data(), auxs.size() / 2);
     if (!ok) {
         std::free(dst);
         return nullptr;
@@ -615,7 +629,7 @@ bool streams_match_lengths(const uint16_t* lengths, size_t tiles, int K, const u
 
 bool index_from_plan(uint32_t interval, size_t nbytes, int width, int height, int K, int block_size, size_t head_bits,
                      const StreamPlan* plans, const PlannedStream* streams, int n_streams, const uint64_t* checkpoints,
-                     std::vector<uint8_t>& blob) {
+                     std::vector<uint8_t>& blob, bool expanded, const uint64_t* aux, size_t n_aux) {
     blob.clear();
     if (interval < kIndexIntervalMin || interval > kIndexIntervalMax || n_streams != 6 * K + 1) return false;
     ContainerIndex x;
@@ -623,6 +637,8 @@ bool index_from_plan(uint32_t interval, size_t nbytes, int width, int height, in
     x.nbytes = nbytes;
     x.width = width; x.height = height; x.K = K; x.block_size = block_size;
     x.streams.resize(static_cast<size_t>(n_streams));
+    if (expanded) x.version = kIndexVersionExpanded;
+    size_t aux_at = 0;                                          // entries taken so far
     uint64_t bit = head_bits;
     const uint64_t* cp = checkpoints;
     for (int j = 0; j < n_streams; ++j) {
@@ -648,8 +664,29 @@ bool index_from_plan(uint32_t interval, size_t nbytes, int width, int height, in
         if (n_cp && before >= ps.first_code_bit + p.payload_bits) return false;
         is.checkpoints.assign(cp, cp + n_cp);
         cp += n_cp;
+        if (!expanded || n_cp == 0 || !index_stream_has_aux(static_cast<size_t>(j), K, is.packed != 0)) continue;
+        // The aux entries: an entry per checkpoint, and what read_container_index asks of a blob's own -- entry 0 fresh at
+        // position 0, positions strictly forward and inside the stream, a state that exists, nothing in the unused bits, a
+        // sum only where the stream is one of sums, an unpacked stream's positions its coded ones
+        if (!aux || n_cp > n_aux - aux_at) return false;
+        const bool dc = (j - 1) % (2 * K) == 1;
+        is.aux.resize(n_cp);
+        for (size_t c = 0; c < n_cp; ++c) {
+            const uint64_t out = aux[2 * (aux_at + c)], word = aux[2 * (aux_at + c) + 1];
+            IndexAux& e = is.aux[c];
+            e.out = out;
+            e.prev = static_cast<uint16_t>(word);
+            e.dc = static_cast<uint16_t>(word >> 16);
+            if ((word >> 32) > 2u) return false;
+            e.state = static_cast<uint8_t>(word >> 32);
+            if (c == 0 ? out != 0 || e.state != 0 || e.prev != 0 || e.dc != 0 : out <= is.aux[c - 1].out) return false;
+            if (out > is.expect || (e.dc != 0 && !dc)) return false;
+            if (!is.packed && (out != static_cast<uint64_t>(c) * interval || e.state != 0 || e.prev != 0)) return false;
+        }
+        aux_at += n_cp;
     }
     if ((bit + 7) / 8 != nbytes) return false;
+    if (expanded && aux_at != n_aux) return false;                   // exactly the entries the plans imply
     blob = index_blob(x);
     return true;
 }

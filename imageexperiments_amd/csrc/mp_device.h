@@ -422,11 +422,20 @@ struct EntropyArgs {
     // behind stream -- the index blob's own layout.  cp_capacity entries; nothing is written beyond them
     unsigned long long* checkpoints;
     unsigned cp_capacity;
+    // seek index version 2 (null: none; phase 1 reads cp_interval with it): the aux entries of the streams that are packed or step-0
+    // coefficient streams, two words each -- out, then prev | dc << 16 | state << 32 -- entry c of stream s at [aux_first[s] + c],
+    // stream behind stream and only those streams: the blob's aux section.  aux_capacity entries; nothing is written beyond them
+    unsigned long long* aux;
+    unsigned aux_capacity;
+    unsigned* aux_first;                // [n_streams] device: entries of the streams in front (ent_aux_offsets_kernel)
+    unsigned* blk_dc;                   // per scan block of a step-0 coefficient stream: wrapping sum of zigzagDecode over its raw symbols
 };
 size_t entropy_max_blocks(unsigned long long symbols, int n_streams);
 // checkpoints the streams of a frame can have at most, whatever the interval (>= 32): sum of ceil(eff_n / interval)
 size_t entropy_max_checkpoints(unsigned long long capacity_symbols, int n_streams);
-// capacity_symbols: upper bound of the symbols in all streams (lengths included); hipError_t as int
+// capacity_symbols: upper bound of the symbols in all streams (lengths included); hipError_t as int.  With a.aux set the pack pass
+// also records the aux entries' out, prev and state and two more kernels add the step-0 streams' sums; otherwise the launches are
+// exactly those of a call without
 int launch_entropy_phase1(const EntropyArgs& a, unsigned long long capacity_symbols, void* stream);
 // raw_symbols: symbols in all streams as assembled (sum of EntStream::n).  With a.checkpoints set the code-writing pass also
 // records the seek index's checkpoints; otherwise the launches are exactly those of a call without an index

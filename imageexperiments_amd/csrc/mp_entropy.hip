@@ -13,7 +13,9 @@
 //              every run that starts inside the block
 //     plan     per stream: the run a block continues (a segmented scan over the blocks), symbols emitted for those in
 //              closed form, output offsets, the reference's decision `packed.size() + 4 < stream.size()`
-//     pack     the run-length coded stream, for the streams where it is shorter
+//     pack     the run-length coded stream, for the streams where it is shorter; for a caller who wants seek index version 2, what
+//              the expansion has reached at every interval-th symbol it writes as well (kAux), and behind it
+//     dc       ... the sums of the step-0 coefficient streams at those positions (two kernels, launched for that caller only)
 //     hist     histogram and first position of every symbol of the stream that will be coded, in LDS (a workgroup per span of
 //              the stream and range of 8192 symbol values), and the number of distinct symbols (a bin's first count)
 //     compact  (symbol, count, first position) of the symbols that occur, per stream, in one list written straight to host memory
@@ -170,8 +172,10 @@ __global__ __launch_bounds__(kThreads) void ent_layout_kernel(const EntropyArgs 
     }
 }
 
-// kPack = false: per-block run structure;  kPack = true: write the run-length coded stream (offsets from the plan)
-template <bool kPack>
+// kPack = false: per-block run structure;  kPack = true: write the run-length coded stream (offsets from the plan);  kAux (with
+// kPack): also the aux entry of every cp_interval-th symbol written -- how many symbols the ones in front of it expand to, the one
+// in front, and the state runLengthDecode meets it in (host_container.cpp: index_aux_pass), all of which this pass holds anyway
+template <bool kPack, bool kAux = false>
 __global__ __launch_bounds__(kThreads) void ent_runs_kernel(const EntropyArgs a)
 {
     __shared__ unsigned scratch[kThreads / 64];
@@ -294,6 +298,32 @@ __global__ __launch_bounds__(kThreads) void ent_runs_kernel(const EntropyArgs a)
     unsigned total;
     unsigned at = a.blk_out[b] + block_excl_add(emitted, scratch, &total);
     uint16_t* dst = a.packed + s.raw_off;
+    // kAux.  The thread writes the coded symbols [at, at + emitted), at most 2 * kPer = 32 of them, and the interval is at least 32:
+    // at most one of them is a checkpoint, cp_at.  A chunk of a run that starts at expanded position g0 is coded as its value
+    // (met at out = g0), the value again (g0 + 1, state 1) and the count c - 1 (g0 + 2, state 2); the first value is met in
+    // state 0 behind a count and at the stream's start, in state 1 behind a chunk of one symbol.  prev_c: the chunk offset of the
+    // symbol in front of the thread's next one -- the last of its chunk whenever that next one starts a chunk.
+    constexpr unsigned kNoState = 3;
+    unsigned cp_at = kNoPos, cp_chunk = 0, prev_c = 0, cp_prev = 0, cp_state = kNoState, cp_out = 0;
+    bool has_prev = false;
+    if (kAux && emitted) {
+        cp_chunk = (at + a.cp_interval - 1) / a.cp_interval;
+        const unsigned first_cp = cp_chunk * a.cp_interval;
+        if (first_cp - at < emitted) {
+            cp_at = first_cp;
+            if (begin + t0 > 0) {
+                has_prev = true;
+                unsigned p_prev;
+                if (t0 > 0) {
+                    p_prev = start >= 0 ? t0 - 1 - (unsigned)start : carry + t0 - 1;
+                } else {                                  // the last symbol of the block in front, a full one of this stream
+                    const unsigned lead = a.blk_lead[b - 1] & 0x7FFFFFFFu;
+                    p_prev = lead == (unsigned)kEntBlock ? a.blk_carry[b - 1] + kEntBlock - 1 : a.blk_tail[b - 1] - 1;
+                }
+                prev_c = p_prev % kChunk;
+            }
+        }
+    }
     {
         int cur = start;
 #pragma unroll
@@ -303,12 +333,37 @@ __global__ __launch_bounds__(kThreads) void ent_runs_kernel(const EntropyArgs a)
                 if (bnd_mask & (1u << k)) cur = (int)i;
                 const unsigned p = cur >= 0 ? i - (unsigned)cur : carry + i;
                 const unsigned c = p % kChunk;
-                if (c <= 1) dst[at++] = v[k + 1];
+                if (c <= 1) {
+                    if (kAux && at == cp_at) {
+                        cp_out = begin + i;
+                        if (c == 1 || (has_prev && prev_c == 0)) { cp_prev = c == 1 ? v[k + 1] : v[k]; cp_state = 1; }
+                        else { cp_prev = has_prev ? prev_c - 1 : 0u; cp_state = 0; }
+                    }
+                    dst[at++] = v[k + 1];
+                }
                 if (c >= 1 && (((end_mask >> k) & 1u) || c == kChunk - 1)) {
+                    if (kAux && at == cp_at) {
+                        cp_out = begin + i - c + 2;
+                        cp_prev = v[k + 1];
+                        cp_state = 2;
+                    }
                     dst[at++] = (uint16_t)(c - 1);
                     largest = max(largest, c - 1);
                 }
+                if (kAux) {
+                    prev_c = c;
+                    has_prev = true;
+                }
             }
+        }
+    }
+    if (kAux && cp_state != kNoState) {
+        const unsigned slot = a.aux_first[j] + cp_chunk;
+        if (slot < a.aux_capacity) {
+            ulonglong2 entry;
+            entry.x = cp_out;
+            entry.y = (unsigned long long)cp_prev | ((unsigned long long)cp_state << 32);
+            reinterpret_cast<ulonglong2*>(a.aux)[slot] = entry;
         }
     }
 #pragma unroll
@@ -362,6 +417,105 @@ __global__ __launch_bounds__(64) void ent_rle_plan_kernel(const EntropyArgs a)
         s.shorter = (j != 0 && (unsigned long long)out_before + 4ULL < s.n) ? 1u : 0u;      // CompressedImage.cpp:450
         s.eff_n = s.shorter ? out_before : s.n;
         a.streams[j] = s;
+    }
+}
+
+// ---- seek index version 2: the aux entries (launched only for a caller who wants them) ----
+namespace {
+__device__ __forceinline__ bool is_dc_stream(const EntropyArgs& a, int j) { return j != 0 && (unsigned)(j - 1) % (unsigned)((a.n_streams - 1) / 3) == 1u; }
+__device__ __forceinline__ unsigned zigzag_value(unsigned x) { return (x >> 1) ^ (0u - (x & 1u)); }
+}  // namespace
+
+// Where each stream's entries go: behind those of the streams in front that have any (packed, or a step-0 coefficient stream),
+// ceil(eff_n / interval) each -- known only behind the plan
+__global__ __launch_bounds__(kThreads) void ent_aux_offsets_kernel(const EntropyArgs a)
+{
+    __shared__ unsigned scratch[kThreads / 64];
+    const int j = threadIdx.x;
+    unsigned mine = 0;
+    if (j < a.n_streams) {
+        const EntStream s = a.streams[j];
+        if (j != 0 && (s.shorter || is_dc_stream(a, j))) mine = (s.eff_n + a.cp_interval - 1) / a.cp_interval;
+    }
+    unsigned total;
+    const unsigned before = block_excl_add(mine, scratch, &total);
+    if (j < a.n_streams) a.aux_first[j] = before;
+}
+
+// The `dc` of a step-0 coefficient stream's entries: the wrapping sum of zigzagDecode over the first `out` symbols of the stream as
+// assembled.  kEntries = false: that sum over each scan block;  kEntries = true: for every entry whose `out` lies in the block,
+// the sums of the blocks in front plus the block's own up to there.  An unpacked stream's entries are written whole here
+// (out = c * interval, no state); a packed one's `out` is the pack pass's, found by a search over the stream's entries.
+template <bool kEntries>
+__global__ __launch_bounds__(kThreads) void ent_dc_kernel(const EntropyArgs a)
+{
+    __shared__ unsigned scratch[kThreads / 64];
+    __shared__ unsigned upto[kThreads + 1];               // the sum in front of each thread's symbols; [kThreads]: the block's
+    __shared__ uint32_t staged[kStageWords];
+    const unsigned b = blockIdx.x;
+    if (b >= a.totals[0]) return;
+    const int j = find_stream(a, b);
+    if (!is_dc_stream(a, j)) return;
+    const EntStream s = a.streams[j];
+    const unsigned lb = b - s.blk_begin;
+    const unsigned begin = lb * kEntBlock, len = min((unsigned)kEntBlock, s.n - begin);
+    const int shift = stage_symbols(raw_stream(a, j, s), begin, len, staged);
+    __syncthreads();
+    const uint16_t* staged16 = reinterpret_cast<const uint16_t*>(staged);
+    const unsigned t0 = threadIdx.x * kPer;
+    unsigned sum = 0;
+#pragma unroll
+    for (int k = 0; k < kPer; ++k)
+        if (t0 + k < len) sum += zigzag_value(staged16[staged_at((int)(t0 + k) + shift)]);
+    unsigned total;
+    const unsigned before = block_excl_add(sum, scratch, &total);
+    if (!kEntries) {
+        if (threadIdx.x == 0) a.blk_dc[b] = total;
+        return;
+    }
+    upto[threadIdx.x] = before;
+    if (threadIdx.x == 0) upto[kThreads] = total;
+    unsigned in_front = 0;                                // the blocks of the stream in front of this one
+    for (unsigned k = threadIdx.x; k < lb; k += kThreads) in_front += a.blk_dc[s.blk_begin + k];
+    unsigned all_in_front;
+    (void)block_excl_add(in_front, scratch, &all_in_front);      // (its barriers also publish upto[])
+    in_front = all_in_front;
+    const unsigned interval = a.cp_interval;
+    const unsigned n_cp = (s.eff_n + interval - 1) / interval, first = a.aux_first[j];
+    // the entries with begin <= out < end; the stream's last block also takes out == n (a count of zero copies at its end)
+    const unsigned end = begin + len + (begin + len == s.n ? 1u : 0u);
+    ulonglong2* entries = reinterpret_cast<ulonglong2*>(a.aux);
+    unsigned c0, c1;
+    if (!s.shorter) {
+        c0 = min(n_cp, (begin + interval - 1) / interval);
+        c1 = min(n_cp, (end + interval - 1) / interval);
+    } else {
+        // out is increasing over a stream's entries: the first at or behind `begin`, the first at or behind `end`.  Every index is
+        // below n_cp, and an entry beyond the array's capacity was never written: it counts as behind everything
+        auto first_at_or_behind = [&](unsigned target) {
+            unsigned lo = 0, hi = n_cp;
+            while (lo < hi) {
+                const unsigned mid = (lo + hi) >> 1;
+                const bool below = first + mid < a.aux_capacity && entries[first + mid].x < (unsigned long long)target;
+                if (below) lo = mid + 1; else hi = mid;
+            }
+            return lo;
+        };
+        c0 = first_at_or_behind(begin);
+        c1 = first_at_or_behind(end);
+    }
+    for (unsigned c = c0 + threadIdx.x; c < c1; c += kThreads) {
+        const unsigned slot = first + c;
+        if (slot >= a.aux_capacity) break;
+        ulonglong2 entry;
+        if (s.shorter) entry = entries[slot];
+        else { entry.x = (unsigned long long)c * interval; entry.y = 0; }
+        if (entry.x < begin || entry.x - begin > len) continue;     // not this block's after all: nothing is indexed by it
+        const unsigned o = (unsigned)(entry.x - begin), t = o / kPer;
+        unsigned dc = in_front + upto[t];
+        for (unsigned k = t * kPer; k < o; ++k) dc += zigzag_value(staged16[staged_at((int)k + shift)]);
+        entry.y = (entry.y & ~0xFFFF0000ull) | ((unsigned long long)(dc & 0xFFFFu) << 16);
+        entries[slot] = entry;
     }
 }
 
@@ -685,7 +839,16 @@ int launch_entropy_phase1(const EntropyArgs& a, unsigned long long capacity_symb
     hipLaunchKernelGGL(ent_layout_kernel, dim3(1), dim3(kThreads), 0, st, a);
     hipLaunchKernelGGL(ent_runs_kernel<false>, dim3(blocks), dim3(kThreads), 0, st, a);
     hipLaunchKernelGGL(ent_rle_plan_kernel, dim3((unsigned)a.n_streams), dim3(64), 0, st, a);
-    hipLaunchKernelGGL(ent_runs_kernel<true>, dim3(blocks), dim3(kThreads), 0, st, a);
+    if (a.aux) {
+        // two checkpoints among the symbols a thread writes, or a stream table the kernels would index past
+        if (a.cp_interval < 32 || !a.aux_first || !a.blk_dc) return (int)hipErrorInvalidValue;
+        hipLaunchKernelGGL(ent_aux_offsets_kernel, dim3(1), dim3(kThreads), 0, st, a);
+        hipLaunchKernelGGL((ent_runs_kernel<true, true>), dim3(blocks), dim3(kThreads), 0, st, a);
+        hipLaunchKernelGGL(ent_dc_kernel<false>, dim3(blocks), dim3(kThreads), 0, st, a);
+        hipLaunchKernelGGL(ent_dc_kernel<true>, dim3(blocks), dim3(kThreads), 0, st, a);
+    } else {
+        hipLaunchKernelGGL(ent_runs_kernel<true>, dim3(blocks), dim3(kThreads), 0, st, a);
+    }
     hipLaunchKernelGGL(ent_hist_kernel, dim3(hblocks), dim3(kThreads), 0, st, a);
     hipLaunchKernelGGL(ent_triple_offsets_kernel, dim3(1), dim3(kThreads), 0, st, a);
     hipLaunchKernelGGL(ent_compact_kernel, dim3(65536 / (4 * kThreads), (unsigned)a.n_streams), dim3(kThreads), 0, st, a);

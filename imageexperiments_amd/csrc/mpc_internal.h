@@ -209,18 +209,22 @@ struct EntropyBuffers {
     uint8_t* h_out = nullptr;
     // the seek index's checkpoints (with_index only): args.checkpoints on the device, their pinned copy
     unsigned long long* h_checkpoints = nullptr;
+    // index version 2's aux entries (with_index == 2 only): args.aux on the device, their pinned copy
+    unsigned long long* h_aux = nullptr;
 };
 
 // carve (and grow) a slot's entropy buffers for frames of `tiles` tiles; the symbols of the streams live in the caller's buffers.
 // with_index: the checkpoint arrays as well, behind everything else -- a slot never used with an index holds none, and one that
-// was keeps them (grow-only) without moving anything when a call comes without
-mpc_status entropy_buffers(EntropySlot& e, size_t tiles, int K, EntropyBuffers* b, bool with_index = false);
+// was keeps them (grow-only) without moving anything when a call comes without.  with_index == 2: behind those, in the same way, what
+// index version 2 needs (the aux entries, their offsets per stream, the step-0 streams' sums per block)
+mpc_status entropy_buffers(EntropySlot& e, size_t tiles, int K, EntropyBuffers* b, int with_index = 0);
 
 // What the host keeps of a frame between the tables step and the collect step of the device route.
 struct EntropyPending {
     std::vector<mpc::StreamPlan> plans;
     mpc::BitWriter head;
     size_t total_bytes = 0;
+    size_t n_aux = 0;                    // index version 2: aux entries on their way to the host
 };
 
 // Records on the device -> container bytes: the only code that does this (the frame pipeline, mpc_container_job_*,
@@ -233,7 +237,9 @@ struct EntropyPending {
 // With index_interval set the job also leaves the container's seek index in `index`, the blob mpc_container_index would build
 // from the finished container: on the device route from the plans and the checkpoints the code kernel recorded (index_from_plan;
 // the pinned copy of the checkpoints travels on `down` behind the container's, in front of `done`), on the host route by
-// build_container_index.
+// build_container_index.  With index_expanded as well the index is version 2: phase 1 leaves the aux entries on the device, their
+// pinned copy travels with the checkpoints', and index_from_plan checks them against the plans; entries it refuses, and the host
+// route, get the blob from build_container_index(..., expanded) of the finished container.
 struct ContainerJob {
     hipStream_t side = nullptr, down = nullptr;
     hipEvent_t phase1 = nullptr, done = nullptr;
@@ -244,6 +250,7 @@ struct ContainerJob {
     const unsigned long long* h_stream_off = nullptr;
     const uint16_t* h_symbols = nullptr;
     unsigned index_interval = 0;         // 0 = no index, else 32 ... 65536; needs `eb` carved with_index
+    bool index_expanded = false;         // index version 2 (MPC_INDEX_EXPANDED); needs `eb` carved with_index == 2
     // set by container_begin
     int width = 0, height = 0, K = 0, block_size = 0;
     std::vector<double> quant;

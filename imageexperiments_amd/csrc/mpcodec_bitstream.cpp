@@ -94,20 +94,22 @@ mpc_status mpc_assemble_symbol_streams_by_plan(int width, int height, int K, int
     });
 }
 
-mpc_status mpc_assemble_symbol_streams_by_plan_indexed(int width, int height, int K, int block_size, const double* quant,
-                                                       const uint16_t* counts, const uint16_t* symbols, const unsigned long long* stream_off,
-                                                       int interval, uint8_t** bytes, size_t* nbytes, uint8_t** index, size_t* index_bytes) {
+namespace {
+mpc_status assemble_by_plan_indexed(int width, int height, int K, int block_size, const double* quant, const uint16_t* counts,
+                                    const uint16_t* symbols, const unsigned long long* stream_off, int interval, unsigned flags,
+                                    uint8_t** bytes, size_t* nbytes, uint8_t** index, size_t* index_bytes) {
     return guarded([&]() -> mpc_status {
     if (!index || !index_bytes) return fail(MPC_ERR_ARGUMENT, "bad argument");
     if (const mpc_status bad = check_symbol_streams(width, height, K, block_size, quant, counts, symbols, stream_off, bytes, nbytes)) return bad;
     if (interval != 0 && (interval < static_cast<int>(mpc::kIndexIntervalMin) || interval > static_cast<int>(mpc::kIndexIntervalMax)))
         return fail(MPC_ERR_ARGUMENT, "interval %d: 0 or %u to %u", interval, mpc::kIndexIntervalMin, mpc::kIndexIntervalMax);
+    if (flags & ~MPC_INDEX_EXPANDED) return fail(MPC_ERR_ARGUMENT, "flags 0x%x: MPC_INDEX_EXPANDED or 0", flags);
     *index = nullptr;
     *index_bytes = 0;
     std::vector<uint8_t> blob;
     uint8_t* container = mpc::encode_symbol_streams_by_plan_indexed_malloc(
         width, height, K, block_size, quant, counts, symbols, stream_off, interval ? static_cast<uint32_t>(interval) : mpc::kIndexIntervalDefault,
-        nbytes, blob);
+        nbytes, blob, (flags & MPC_INDEX_EXPANDED) != 0);
     if (!container) return fail(MPC_ERR_ALLOC, "out of memory or inconsistent plan");
     if (!blob.empty()) {
         *index = give_bytes(blob, index_bytes);
@@ -120,6 +122,22 @@ mpc_status mpc_assemble_symbol_streams_by_plan_indexed(int width, int height, in
     *bytes = container;
     return MPC_OK;
     });
+}
+}  // namespace
+
+mpc_status mpc_assemble_symbol_streams_by_plan_indexed(int width, int height, int K, int block_size, const double* quant,
+                                                       const uint16_t* counts, const uint16_t* symbols, const unsigned long long* stream_off,
+                                                       int interval, uint8_t** bytes, size_t* nbytes, uint8_t** index, size_t* index_bytes) {
+    return assemble_by_plan_indexed(width, height, K, block_size, quant, counts, symbols, stream_off, interval, 0, bytes, nbytes, index,
+                                    index_bytes);
+}
+
+mpc_status mpc_assemble_symbol_streams_by_plan_indexed2(int width, int height, int K, int block_size, const double* quant,
+                                                        const uint16_t* counts, const uint16_t* symbols, const unsigned long long* stream_off,
+                                                        int interval, unsigned flags, uint8_t** bytes, size_t* nbytes, uint8_t** index,
+                                                        size_t* index_bytes) {
+    return assemble_by_plan_indexed(width, height, K, block_size, quant, counts, symbols, stream_off, interval, flags, bytes, nbytes, index,
+                                    index_bytes);
 }
 
 mpc_status mpc_read_compressed(const uint8_t* bytes, size_t nbytes, mpc_streams** out) {

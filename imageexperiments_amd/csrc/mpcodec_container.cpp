@@ -9,13 +9,14 @@
 // than the triple list, a code longer than 32 bits).
 #include <algorithm>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <future>
 #include <utility>
 
 #include "mpc_internal.h"
 
-mpc_status entropy_buffers(EntropySlot& e, size_t tiles, int K, EntropyBuffers* b, bool with_index) {
+mpc_status entropy_buffers(EntropySlot& e, size_t tiles, int K, EntropyBuffers* b, int with_index) {
     const int S = 6 * K + 1;
     const size_t n_tc = 3 * tiles;
     const unsigned long long cap_symbols = n_tc + 2ULL * n_tc * K;
@@ -26,6 +27,8 @@ mpc_status entropy_buffers(EntropySlot& e, size_t tiles, int K, EntropyBuffers* 
     mpc::EntropyArgs& a = b->args;
     a = mpc::EntropyArgs{};
     b->h_checkpoints = nullptr;
+    b->h_aux = nullptr;
+    const bool with_aux = with_index == 2;                              // at most an entry per checkpoint: the same bound
     auto device_layout = [&](char* base) {
         Carve cv{base};
         a.streams = cv.take<mpc::EntStream>(S);
@@ -40,6 +43,11 @@ mpc_status entropy_buffers(EntropySlot& e, size_t tiles, int K, EntropyBuffers* 
         a.ghist = cv.take<unsigned>(table_words);
         a.gfirst = cv.take<unsigned>(table_words);
         if (with_index) a.checkpoints = cv.take<unsigned long long>(max_cp);
+        if (with_aux) {
+            a.aux = cv.take<unsigned long long>(2 * max_cp);
+            a.aux_first = cv.take<unsigned>(S);
+            a.blk_dc = cv.take<unsigned>(blocks);
+        }
         return cv.at;
     };
     auto host_layout = [&](char* base) {
@@ -50,6 +58,7 @@ mpc_status entropy_buffers(EntropySlot& e, size_t tiles, int K, EntropyBuffers* 
         b->h_entries = cv.take<unsigned>(3 * static_cast<size_t>(kTripleCap));
         b->h_out = cv.take<uint8_t>(out_bytes);
         if (with_index) b->h_checkpoints = cv.take<unsigned long long>(max_cp);
+        if (with_aux) b->h_aux = cv.take<unsigned long long>(2 * max_cp);
         return cv.at;
     };
     bool grown = false;
@@ -71,6 +80,7 @@ mpc_status entropy_buffers(EntropySlot& e, size_t tiles, int K, EntropyBuffers* 
     a.triple_cap = kTripleCap;
     a.out32 = reinterpret_cast<unsigned*>(b->d_out);
     a.cp_capacity = static_cast<unsigned>(max_cp);
+    a.aux_capacity = with_aux ? static_cast<unsigned>(max_cp) : 0u;
     if (e.tiles != tiles || e.K != K) {
         // the dense code tables and the histogram are zero between frames (the kernels clear what they set), the first
         // positions all ones; a slot carved for another geometry holds them elsewhere
@@ -107,8 +117,8 @@ hipError_t wait_event(hipEvent_t ev, bool spin) {
 //                    to the host, `done`.  kNeedsHost: nothing enqueued, take the host route.
 //   entropy_collect  waits for `done`, checks the device's bit counts against the tables', patches the host's pieces in.
 EntropyResult entropy_tables(const EntropyBuffers& b, int device_block_size, int width, int height, int K, const double* quant,
-                             unsigned triple_limit, unsigned index_interval, hipStream_t s, hipEvent_t done, EntropyPending* pending,
-                             double* stamps) {
+                             unsigned triple_limit, unsigned index_interval, bool index_expanded, hipStream_t s, hipEvent_t done,
+                             EntropyPending* pending, double* stamps) {
     const mpc::EntropyArgs& a = b.args;
     const int S = a.n_streams;
     if (b.h_totals[3] != 0 || b.h_totals[2] > triple_limit) return EntropyResult::kNeedsHost;
@@ -126,8 +136,9 @@ EntropyResult entropy_tables(const EntropyBuffers& b, int device_block_size, int
     });
     pending->head = mpc::container_head(width, height, K, device_block_size, quant);
     unsigned long long bit = pending->head.bit_size(), raw_symbols = 0;
-    size_t n_entries = 0, n_cp = 0;
+    size_t n_entries = 0, n_cp = 0, n_aux = 0;
     if (index_interval && !(a.checkpoints && b.h_checkpoints)) return EntropyResult::kFailed;
+    if (index_interval && index_expanded && !(a.aux && b.h_aux)) return EntropyResult::kFailed;
     for (int j = 0; j < S; ++j) {
         const mpc::StreamPlan& p = plans[static_cast<size_t>(j)];
         if (p.mode == 0 && p.max_code_length > 32) return EntropyResult::kNeedsHost;
@@ -138,7 +149,10 @@ EntropyResult entropy_tables(const EntropyBuffers& b, int device_block_size, int
         st.m = p.m;
         if (index_interval) {                                   // the stream's checkpoints: behind those of the streams before it
             st.reserved = static_cast<unsigned>(n_cp);
-            n_cp += (static_cast<size_t>(st.eff_n) + index_interval - 1) / index_interval;
+            const size_t chunks = (static_cast<size_t>(st.eff_n) + index_interval - 1) / index_interval;
+            n_cp += chunks;
+            // the aux entries phase 1 has left on the device: the same count the device derived (ent_aux_offsets_kernel)
+            if (index_expanded && mpc::index_stream_has_aux(static_cast<size_t>(j), K, j != 0 && st.shorter != 0)) n_aux += chunks;
         }
         bit += p.payload_bits + p.post.bit_size();
         raw_symbols += st.n;
@@ -146,7 +160,9 @@ EntropyResult entropy_tables(const EntropyBuffers& b, int device_block_size, int
     }
     const size_t total_bytes = static_cast<size_t>((bit + 7) / 8), out_words = (total_bytes + 3) / 4;
     if (out_words * 4 > b.out_capacity || n_entries > kTripleCap || n_cp > a.cp_capacity) return EntropyResult::kNeedsHost;
+    if (index_expanded && n_aux > a.aux_capacity) return EntropyResult::kNeedsHost;
     pending->total_bytes = total_bytes;
+    pending->n_aux = n_aux;
     size_t at = 0;
     for (int j = 0; j < S; ++j) {
         const std::vector<uint32_t>& e = plans[static_cast<size_t>(j)].entries;
@@ -166,6 +182,8 @@ EntropyResult entropy_tables(const EntropyBuffers& b, int device_block_size, int
                     hipMemcpyAsync(b.h_out, b.d_out, out_words * 4, hipMemcpyDeviceToHost, s) == hipSuccess &&
                     (n_cp == 0 || hipMemcpyAsync(b.h_checkpoints, a.checkpoints, sizeof(unsigned long long) * n_cp, hipMemcpyDeviceToHost,
                                                  s) == hipSuccess) &&
+                    (n_aux == 0 || hipMemcpyAsync(b.h_aux, a.aux, 2 * sizeof(unsigned long long) * n_aux, hipMemcpyDeviceToHost, s) ==
+                                       hipSuccess) &&
                     hipEventRecord(done, s) == hipSuccess;
     return ok ? EntropyResult::kDone : EntropyResult::kFailed;
 }
@@ -195,10 +213,24 @@ EntropyResult entropy_collect(const EntropyBuffers& b, const EntropyPending& pen
             ps.eff_n = st.eff_n;
             ps.shorter = st.shorter != 0;
         }
-        if (!mpc::index_from_plan(job.index_interval, pending.total_bytes, job.width, job.height, job.K, job.block_size,
-                                  pending.head.bit_size(), pending.plans.data(), planned.data(), S,
-                                  reinterpret_cast<const uint64_t*>(b.h_checkpoints), *index))
-            return EntropyResult::kFailed;
+        if (!job.index_expanded) {
+            if (!mpc::index_from_plan(job.index_interval, pending.total_bytes, job.width, job.height, job.K, job.block_size,
+                                      pending.head.bit_size(), pending.plans.data(), planned.data(), S,
+                                      reinterpret_cast<const uint64_t*>(b.h_checkpoints), *index))
+                return EntropyResult::kFailed;
+        } else if (!mpc::index_from_plan(job.index_interval, pending.total_bytes, job.width, job.height, job.K, job.block_size,
+                                         pending.head.bit_size(), pending.plans.data(), planned.data(), S,
+                                         reinterpret_cast<const uint64_t*>(b.h_checkpoints), *index, true,
+                                         reinterpret_cast<const uint64_t*>(b.h_aux), pending.n_aux)) {
+            // entries that contradict the plans: never a wrong blob -- the finished container is parsed instead.  MPC_INDEX_STRICT=1
+            // (the device tests): an error, so that a kernel that writes such entries cannot hide behind the parse
+            const char* strict = std::getenv("MPC_INDEX_STRICT");
+            if (strict && std::atoi(strict) != 0) {
+                std::fprintf(stderr, "[mpcodec] the device's aux entries contradict the stream plans (MPC_INDEX_STRICT)\n");
+                return EntropyResult::kFailed;
+            }
+            if (!mpc::build_container_index(b.h_out, pending.total_bytes, job.index_interval, *index, true)) return EntropyResult::kFailed;
+        }
     }
     uint8_t* out = static_cast<uint8_t*>(std::malloc(pending.total_bytes ? pending.total_bytes : 1));
     if (!out) return EntropyResult::kFailed;
@@ -260,7 +292,7 @@ mpc_status container_on_host(ContainerJob& j) {
     j.blob = mpc::encode_symbol_streams_malloc(j.width, j.height, j.K, j.block_size, j.quant.data(), counts, symbols, off, &j.nblob);
     if (!j.blob) return fail(MPC_ERR_ALLOC, "out of memory");
     // the host route's index: the finished container parsed (rare; this is also where a "serial only" index comes from)
-    if (j.index_interval && !mpc::build_container_index(j.blob, j.nblob, j.index_interval, j.index))
+    if (j.index_interval && !mpc::build_container_index(j.blob, j.nblob, j.index_interval, j.index, j.index_expanded))
         return fail(MPC_ERR_BITSTREAM, "the container of the host route does not parse: no index");
     return MPC_OK;
 }
@@ -301,6 +333,12 @@ mpc_status container_begin(ContainerJob& j, const mpc_context* c, const EntropyB
         j.eb.args.counts = d_counts;
         j.eb.args.symbols = sa.symbols;
         j.eb.args.stream_off = sa.stream_off;
+        if (j.index_interval && j.index_expanded) {
+            if (!j.eb.args.aux) return fail(MPC_ERR_ARGUMENT, "entropy buffers carved without the aux entries");
+            j.eb.args.cp_interval = j.index_interval;           // the pack pass records the aux entries
+        } else {
+            j.eb.args.aux = nullptr;                            // a slot carved for them, a call without: the usual kernels
+        }
         if (const int err = mpc::launch_entropy_phase1(j.eb.args, j.eb.capacity_symbols, j.side); err != 0) return launch_failed(err);
     }
     HIP_TRY(hipEventRecord(j.phase1, j.side));
@@ -312,8 +350,8 @@ mpc_status container_tables(ContainerJob& j, const std::function<void()>& enqueu
     j.stamps[0] = trace_ms();
     EntropyResult r = EntropyResult::kNeedsHost;
     if (j.device_entropy)
-        r = entropy_tables(j.eb, j.block_size, j.width, j.height, j.K, j.quant.data(), j.triple_limit, j.index_interval, j.down, j.done,
-                           &j.pending, j.stamps + 1);
+        r = entropy_tables(j.eb, j.block_size, j.width, j.height, j.K, j.quant.data(), j.triple_limit, j.index_interval, j.index_expanded, j.down,
+                           j.done, &j.pending, j.stamps + 1);
     if (enqueued) enqueued();
     if (r == EntropyResult::kFailed) return fail(MPC_ERR_HIP, "device entropy stage failed: %s", hipGetErrorString(hipGetLastError()));
     if (r == EntropyResult::kDone) return MPC_OK;
@@ -336,10 +374,11 @@ mpc_status container_collect(ContainerJob& j, uint8_t** bytes, size_t* nbytes) {
 namespace {
 // compressed::encodeImage for a sequence of equally sized frames: device tile encode, then records -> container (ContainerJob)
 // -- pipelined over kSeqSlots slots.  Frames come from host memory (uploaded through the slot's pinned image on an upload
-// stream) or are already resident on the device.  index_interval != 0: every frame's seek index as well (indexes, index_bytes).
+// stream) or are already resident on the device.  index_interval != 0: every frame's seek index as well (indexes, index_bytes),
+// version 2 if index_expanded.
 mpc_status encode_sequence(mpc_context* c, const uint8_t* const* frames, bool on_device, int n_frames, int width, int height,
                            const double* quant, uint8_t** bytes, size_t* nbytes, unsigned index_interval = 0, uint8_t** indexes = nullptr,
-                           size_t* index_bytes = nullptr) {
+                           size_t* index_bytes = nullptr, bool index_expanded = false) {
     if (!c || !frames || !bytes || !nbytes || n_frames < 1) return fail(MPC_ERR_ARGUMENT, "bad argument");
     if (index_interval && (!indexes || !index_bytes)) return fail(MPC_ERR_ARGUMENT, "bad argument");
     if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback");
@@ -435,7 +474,9 @@ mpc_status encode_sequence(mpc_context* c, const uint8_t* const* frames, bool on
     EntropyBuffers ent[S];
     if (!t.host_entropy)
         for (size_t sl = 0; sl < alloc_slots; ++sl)
-            if (const mpc_status es = entropy_buffers(c->ent[sl], tiles, K, &ent[sl], index_interval != 0); es != MPC_OK) return es;
+            if (const mpc_status es = entropy_buffers(c->ent[sl], tiles, K, &ent[sl], index_interval ? (index_expanded ? 2 : 1) : 0);
+                es != MPC_OK)
+                return es;
     ContainerJob jobs[S];
     struct Pending {
         std::future<std::pair<uint8_t*, size_t>> result;     // malloc'ed container, or {nullptr, 0}
@@ -562,6 +603,7 @@ mpc_status encode_sequence(mpc_context* c, const uint8_t* const* frames, bool on
         job.host_stage = &c->host_stage;
         job.host_offset = sl * host_slot + route_at;
         job.index_interval = index_interval;
+        job.index_expanded = index_expanded;
         MPC_SEQ_TRY(hipEventRecord(c->seq_pursuit_done[sl], pursuit_stream));
         MPC_SEQ_TRY(hipStreamWaitEvent(job.side, c->seq_pursuit_done[sl], 0));
         st = container_begin(job, c, t.host_entropy ? nullptr : &ent[sl], t.triple_limit, dbase + streams_at, d_counts,
@@ -616,15 +658,22 @@ mpc_status index_interval_of(int interval, unsigned* out) {
     return MPC_OK;
 }
 
+// the `flags` argument of the ...indexed2 entry points: MPC_INDEX_EXPANDED or nothing
+mpc_status index_flags_of(unsigned flags, bool* expanded) {
+    if (flags & ~MPC_INDEX_EXPANDED) return fail(MPC_ERR_ARGUMENT, "flags 0x%x: MPC_INDEX_EXPANDED or 0", flags);
+    *expanded = (flags & MPC_INDEX_EXPANDED) != 0;
+    return MPC_OK;
+}
+
 JobSlot* job_slot(mpc_context* c, int slot) {
     if (!c->jobs[slot]) c->jobs[slot] = std::make_unique<JobSlot>();
     return c->jobs[slot].get();
 }
 
-// mpc_code_symbol_streams_device[_indexed]; index_interval != 0: with the container's seek index
+// mpc_code_symbol_streams_device[_indexed[2]]; index_interval != 0: with the container's seek index, version 2 if index_expanded
 mpc_status code_symbol_streams(mpc_context* c, int width, int height, const double* quant, const uint16_t* counts, const uint16_t* symbols,
-                               const unsigned long long* stream_off, unsigned index_interval, uint8_t** bytes, size_t* nbytes,
-                               uint8_t** index, size_t* index_bytes, int* route) {
+                               const unsigned long long* stream_off, unsigned index_interval, bool index_expanded, uint8_t** bytes,
+                               size_t* nbytes, uint8_t** index, size_t* index_bytes, int* route) {
     return guarded([&]() -> mpc_status {
     if (!c || !counts || !stream_off || !bytes || !nbytes || width < 1 || height < 1) return fail(MPC_ERR_ARGUMENT, "bad argument");
     if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device");
@@ -651,11 +700,13 @@ mpc_status code_symbol_streams(mpc_context* c, int width, int height, const doub
     j.h_stream_off = stream_off;
     j.h_symbols = symbols;
     j.index_interval = index_interval;
+    j.index_expanded = index_expanded;
     HIP_TRY(hipEventCreateWithFlags(&j.phase1, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&j.done, hipEventDisableTiming));
     EntropyBuffers eb;
     if (!t.host_entropy) {
-        if (const mpc_status es = entropy_buffers(c->ent[0], tiles, K, &eb, index_interval != 0); es != MPC_OK) return es;
+        if (const mpc_status es = entropy_buffers(c->ent[0], tiles, K, &eb, index_interval ? (index_expanded ? 2 : 1) : 0); es != MPC_OK)
+            return es;
         const size_t n_off = 6 * static_cast<size_t>(K) + 1;
         HIP_TRY(hipMalloc(&d_counts.p, sizeof(uint16_t) * n_tc));
         HIP_TRY(hipMalloc(&d_symbols.p, sizeof(uint16_t) * (total ? total : 1)));
@@ -805,7 +856,7 @@ mpc_status mpc_records_to_container_device(mpc_context* c, const uint16_t* d_cou
 mpc_status mpc_code_symbol_streams_device(mpc_context* c, int width, int height, const double* quant, const uint16_t* counts,
                                           const uint16_t* symbols, const unsigned long long* stream_off, uint8_t** bytes, size_t* nbytes,
                                           int* route) {
-    return code_symbol_streams(c, width, height, quant, counts, symbols, stream_off, 0, bytes, nbytes, nullptr, nullptr, route);
+    return code_symbol_streams(c, width, height, quant, counts, symbols, stream_off, 0, false, bytes, nbytes, nullptr, nullptr, route);
 }
 
 // The same with the container's seek index.  Streams that do not hold what `counts` implies (only a test makes such) give a
@@ -816,7 +867,21 @@ mpc_status mpc_code_symbol_streams_device_indexed(mpc_context* c, int width, int
     unsigned every = 0;
     if (!index || !index_bytes) return fail(MPC_ERR_ARGUMENT, "bad argument");
     if (const mpc_status bad = index_interval_of(interval, &every)) return bad;
-    return code_symbol_streams(c, width, height, quant, counts, symbols, stream_off, every, bytes, nbytes, index, index_bytes, route);
+    return code_symbol_streams(c, width, height, quant, counts, symbols, stream_off, every, false, bytes, nbytes, index, index_bytes, route);
+}
+
+// flags 0: the call above; MPC_INDEX_EXPANDED: *index is the version-2 blob mpc_container_index2 builds from the container
+mpc_status mpc_code_symbol_streams_device_indexed2(mpc_context* c, int width, int height, const double* quant, const uint16_t* counts,
+                                                   const uint16_t* symbols, const unsigned long long* stream_off, int interval,
+                                                   unsigned flags, uint8_t** bytes, size_t* nbytes, uint8_t** index, size_t* index_bytes,
+                                                   int* route) {
+    unsigned every = 0;
+    bool expanded = false;
+    if (!index || !index_bytes) return fail(MPC_ERR_ARGUMENT, "bad argument");
+    if (const mpc_status bad = index_interval_of(interval, &every)) return bad;
+    if (const mpc_status bad = index_flags_of(flags, &expanded)) return bad;
+    return code_symbol_streams(c, width, height, quant, counts, symbols, stream_off, every, expanded, bytes, nbytes, index, index_bytes,
+                               route);
 }
 
 mpc_status mpc_encode_images(mpc_context* c, const uint8_t* const* rgb_frames, int n_frames, int width, int height,
@@ -849,6 +914,33 @@ mpc_status mpc_encode_images_indexed_device(mpc_context* c, const uint8_t* const
         if (!indexes || !index_bytes) return fail(MPC_ERR_ARGUMENT, "bad argument");
         if (const mpc_status bad = index_interval_of(interval, &every)) return bad;
         return encode_sequence(c, d_rgb_frames, true, n_frames, width, height, quant, bytes, nbytes, every, indexes, index_bytes);
+    });
+}
+
+// the two above with `flags`: 0 = the same call, MPC_INDEX_EXPANDED = every index is version 2 (mpc_container_index2's blob)
+mpc_status mpc_encode_images_indexed2(mpc_context* c, const uint8_t* const* rgb_frames, int n_frames, int width, int height,
+                                      const double* quant, int interval, unsigned flags, uint8_t** bytes, size_t* nbytes,
+                                      uint8_t** indexes, size_t* index_bytes) {
+    return guarded([&]() -> mpc_status {
+        unsigned every = 0;
+        bool expanded = false;
+        if (!indexes || !index_bytes) return fail(MPC_ERR_ARGUMENT, "bad argument");
+        if (const mpc_status bad = index_interval_of(interval, &every)) return bad;
+        if (const mpc_status bad = index_flags_of(flags, &expanded)) return bad;
+        return encode_sequence(c, rgb_frames, false, n_frames, width, height, quant, bytes, nbytes, every, indexes, index_bytes, expanded);
+    });
+}
+
+mpc_status mpc_encode_images_indexed2_device(mpc_context* c, const uint8_t* const* d_rgb_frames, int n_frames, int width, int height,
+                                             const double* quant, int interval, unsigned flags, uint8_t** bytes, size_t* nbytes,
+                                             uint8_t** indexes, size_t* index_bytes) {
+    return guarded([&]() -> mpc_status {
+        unsigned every = 0;
+        bool expanded = false;
+        if (!indexes || !index_bytes) return fail(MPC_ERR_ARGUMENT, "bad argument");
+        if (const mpc_status bad = index_interval_of(interval, &every)) return bad;
+        if (const mpc_status bad = index_flags_of(flags, &expanded)) return bad;
+        return encode_sequence(c, d_rgb_frames, true, n_frames, width, height, quant, bytes, nbytes, every, indexes, index_bytes, expanded);
     });
 }
 

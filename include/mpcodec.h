@@ -30,6 +30,9 @@
  *                             would build from it, emitted by the entropy stage instead of parsed out of the finished bytes;
  *                             mpc_code_symbol_streams_device_indexed, mpc_assemble_symbol_streams_by_plan_indexed: the
  *                             entropy stage alone, on the device and on the host)
+ *   mpc_encode_images_indexed2[_device] (same with `flags`: MPC_INDEX_EXPANDED = index version 2, the aux entries from the
+ *                             entropy stage's run-length pack kernel as well; mpc_code_symbol_streams_device_indexed2,
+ *                             mpc_assemble_symbol_streams_by_plan_indexed2)
  *   mpc_decode_image          compressed::decodeImage                     CompressedImage.h:75
  *   mpc_decode_tiles_device   matching::FromCoeffsDynamic per tile        MatchingPursuit.h:25, CompressedImage.cpp:797-831
  *   mpc_psnr                  compressed::calculatePSNR                   CompressedImage.h:57
@@ -319,6 +322,7 @@ mpc_status mpc_encode_images_device(mpc_context* ctx, const uint8_t* const* d_rg
  * interval-th coded symbol's bit anyway.  The containers are those of the calls without an index.  interval as for
  * mpc_container_index (0 = the default; anything else outside 32 ... 65536 is MPC_ERR_ARGUMENT before anything is enqueued).
  * A frame that takes the host route for its entropy stage gets its index from the finished container on the host.
+ * These return index version 1; mpc_encode_images_indexed2[_device] (below, "Index version 2") return version 2.
  * n_frames == 1 is the single-frame route (mpc_encode_image).  Every buffer is released with mpc_free; on failure nothing is
  * returned. */
 mpc_status mpc_encode_images_indexed(mpc_context* ctx, const uint8_t* const* rgb_frames, int n_frames, int width, int height,
@@ -478,6 +482,37 @@ mpc_status mpc_index_extend(const uint8_t* bytes, size_t nbytes, const uint8_t* 
 int mpc_index_version(const uint8_t* index, size_t index_bytes);
 mpc_status mpc_index_aux(const uint8_t* index, size_t index_bytes, int stream, uint64_t* out, uint16_t* prev, uint8_t* state, uint16_t* dc,
                          size_t capacity, size_t* n_entries);
+/* The indexed encoders with `flags`, in the way mpc_container_index2 extends mpc_container_index: the arguments of
+ * mpc_encode_images_indexed[_device], mpc_code_symbol_streams_device_indexed and mpc_assemble_symbol_streams_by_plan_indexed with
+ * `flags` behind `interval`.
+ *   flags == 0                   exactly that call: the same containers, the version-1 blobs, the same kernels
+ *   flags == MPC_INDEX_EXPANDED  indexes[i] is the blob mpc_container_index2(bytes[i], nbytes[i], interval, MPC_INDEX_EXPANDED, ...)
+ *                                returns, byte for byte; the containers are those of the calls without an index
+ *   any other bit                MPC_ERR_ARGUMENT before anything is enqueued
+ * The aux entries come from the device's entropy stage too, so a region or view decode can follow the encode with no pass over the
+ * container on the host (mpc_index_extend) in between: the kernel that writes a run-length packed stream holds, at every symbol it
+ * writes, the expanded position, the symbol in front and the state the decoder will be in, and stores them at every interval-th;
+ * the sums of the step-0 coefficient streams are prefix sums over streams the stage holds.  The host checks the entries against
+ * its plans (an entry per checkpoint, out[0] = 0, strictly increasing, inside the stream, a state that exists, c * interval for a
+ * stream that is not packed) and builds the blob from the finished container instead where they do not hold; a frame whose
+ * entropy stage takes the host route gets it that way as well.  The by-plan form computes the entries on the host from the coded
+ * streams it holds and so defines, without a GPU, what the device computes.  Interval rules, the single-frame route, mpc_free, no
+ * result on failure, and no index (and no error) for streams that do not hold what `counts` implies: as for the calls without
+ * `flags`. */
+mpc_status mpc_encode_images_indexed2(mpc_context* ctx, const uint8_t* const* rgb_frames, int n_frames, int width, int height,
+                                      const double* quant, int interval, unsigned flags, uint8_t** bytes, size_t* nbytes,
+                                      uint8_t** indexes, size_t* index_bytes);
+mpc_status mpc_encode_images_indexed2_device(mpc_context* ctx, const uint8_t* const* d_rgb_frames, int n_frames, int width, int height,
+                                             const double* quant, int interval, unsigned flags, uint8_t** bytes, size_t* nbytes,
+                                             uint8_t** indexes, size_t* index_bytes);
+mpc_status mpc_code_symbol_streams_device_indexed2(mpc_context* ctx, int width, int height, const double* quant, const uint16_t* counts,
+                                                   const uint16_t* symbols, const unsigned long long* stream_off, int interval,
+                                                   unsigned flags, uint8_t** bytes, size_t* nbytes, uint8_t** index, size_t* index_bytes,
+                                                   int* route);
+mpc_status mpc_assemble_symbol_streams_by_plan_indexed2(int width, int height, int K, int block_size, const double* quant,
+                                                        const uint16_t* counts, const uint16_t* symbols,
+                                                        const unsigned long long* stream_off, int interval, unsigned flags,
+                                                        uint8_t** bytes, size_t* nbytes, uint8_t** index, size_t* index_bytes);
 /* The chunked parse on the host: what mpc_read_compressed_coded yields -- the lengths stream and the 6K coded streams back to back
  * (symbols, mpc_free) -- with every chunk decoded from its checkpoint alone and accepted only under the rule above.  It defines
  * what the device parse computes, checkable without a GPU.  route: 0 = the index was used, 1 = it was refused and the serial

@@ -5,11 +5,15 @@ For n frames of a workload (bench.py's: synthetic frames, seeds 12345 + f) resid
     a  encode_images_device                      (mpc_encode_images_device: the containers alone)
     b  encode_images_indexed_device              (mpc_encode_images_indexed_device: containers and indexes from the entropy stage)
     c  a, then container_index on every container (mpc_container_index: one serial parse per container on one host thread)
+    d  encode_images_indexed_device(expanded=True) (mpc_encode_images_indexed2_device: index version 2, the aux entries from the
+       entropy stage as well)
+    e  b, then index_extend on every container   (mpc_index_extend: the aux entries on one host thread, a chunked parse and a linear pass)
 The profiler is off.  Every shape is warmed up, then the legs alternate `rounds` times; host clock around calls that return with
 their results complete.  Prints median and range of ms per frame per leg, and the figure of merit: (b) - (a) against (c) - (a).
-b and c are checked once to give the same indexes.
---legs a: leg a alone -- what a library without the indexed entry points can run (MPCODEC_LIB=<an older build>): its (a) on the
-same box in the same call is what this build's (a) is compared with.
+b and c are checked once to give the same indexes, d and e to give the same version-2 indexes; with both, the second figure of
+merit: what the aux section costs at encode time, (d) - (b), against what it costs on the host, (e) - (b).
+--legs a (or a,b): what a library without the indexed (or the ...indexed2) entry points can run (MPCODEC_LIB=<an older build>): its
+medians on the same box in the same call are what this build's are compared with.
 --once: a warm-up and one pass of leg b, nothing else (for a kernel trace)."""
 import argparse
 import os
@@ -51,8 +55,16 @@ def main():
 
         def c():
             return [(blob, ia.container_index(blob, args.interval)) for blob in ctx.encode_images_device(ptrs, W, H)]
+
+        def d():
+            return ctx.encode_images_indexed_device(ptrs, W, H, args.interval, expanded=True)
+
+        def e():
+            return [(blob, ia.index_extend(blob, index)) for blob, index in b()]
         legs = [leg for leg in (("a", a, "encode_images_device"), ("b", b, "encode_images_indexed_device"),
-                                ("c", c, "encode_images_device + container_index")) if leg[0] in wanted]
+                                ("c", c, "encode_images_device + container_index"),
+                                ("d", d, "encode_images_indexed_device(expanded)"),
+                                ("e", e, "encode_images_indexed_device + index_extend")) if leg[0] in wanted]
         if args.once:
             b()
             torch.cuda.synchronize()
@@ -66,6 +78,9 @@ def main():
             assert results["b"] == results["c"], "the encoder's indexes differ from container_index's"
             print(f"# {name}: {W}x{H} K={K} quality {q}, {n} frames, {sum(len(x) for x, _ in results['b']) / n / 1e6:.2f} MB a container, "
                   f"{sum(len(x) for _, x in results['b']) / n / 1e3:.1f} kB an index (interval {args.interval})", flush=True)
+        if "d" in results and "e" in results:
+            assert results["d"] == results["e"], "the encoder's version-2 indexes differ from index_extend's"
+            print(f"# {name}: {sum(len(x) for _, x in results['d']) / n / 1e3:.1f} kB a version-2 index", flush=True)
         del results
         ms = {key: [] for key, _, _ in legs}
         for _ in range(args.rounds):
@@ -84,6 +99,10 @@ def main():
             spread = max(ms["a"]) - min(ms["a"])
             print(f"{name} n={n} index at encode time (b - a) {med['b'] - med['a']:+.3f} ms/frame; from the container (c - a) "
                   f"{med['c'] - med['a']:+.3f} ms/frame; spread of a {spread:.3f} ms/frame", flush=True)
+        if all(k in med for k in "bde"):
+            spread = max(ms["b"]) - min(ms["b"])
+            print(f"{name} n={n} aux at encode time (d - b) {med['d'] - med['b']:+.3f} ms/frame; on the host (e - b) "
+                  f"{med['e'] - med['b']:+.3f} ms/frame; spread of b {spread:.3f} ms/frame", flush=True)
         ctx.close()
 
 
