@@ -110,8 +110,19 @@ def load_library():
     L.mpc_kernel_timing_read.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.POINTER(C.c_double)]
     L.mpc_kernel_counters_read.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
     _bind_bitstream(L)
+    _bind_debug(L)
     _lib = L
     return L
+
+
+def _bind_debug(L):
+    """The tests' entry points to the pursuit screen's tables (include/mpcodec.h, "test entry points")."""
+    vp = C.c_void_p
+    L.mpc_debug_copy_gram_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
+    L.mpc_debug_gram_device.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp]
+    L.mpc_debug_copy_filter_tiles.argtypes = [vp, C.c_int, C.c_int, _u16p]
+    L.mpc_filter_tiles.argtypes = [_dp, C.c_int, C.c_int, C.c_int, _u16p, _u8p]
+    L.mpc_debug_screen_probe_device.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp]
 
 
 def _bind_bitstream(L):
@@ -1283,6 +1294,23 @@ class CompressionContext:
         _check(self.L.mpc_distortion_device(self.h, d_counts, d_choices, qp, d_rgb, width, height, d_sse, d_tile_sse or None,
                                             stream or None))
 
+    # -- the tests' entry points to the screen's tables -------------------------------------------
+    def debug_copy_gram_device(self, channel, sel_begin, sel_count, col_begin, col_count, d_out, stream=0):
+        """mpc_debug_copy_gram_device: a rectangle of the resident Gram table of `channel` -> dense float32 d_out[sel_count, col_count]."""
+        _check(self.L.mpc_debug_copy_gram_device(self.h, int(channel), int(sel_begin), int(sel_count), int(col_begin), int(col_count),
+                                                 d_out or None, stream or None))
+
+    def debug_copy_filter_tiles(self, channel, block=0):
+        """mpc_debug_copy_filter_tiles: the uploaded tiles as uint16: the 32 base tiles (channel -1) or the 4 of (channel, block)."""
+        out = np.zeros((32 if channel < 0 else 4) * FILTER_TILE_HALVES, np.uint16)
+        _check(self.L.mpc_debug_copy_filter_tiles(self.h, int(channel), int(block), out.ctypes.data_as(_u16p)))
+        return out
+
+    def debug_screen_probe_device(self, channel, block, d_vectors, n, d_approx, d_bound, stream=0):
+        """mpc_debug_screen_probe_device: d_vectors[n,64] f64 -> d_approx[n,576] f32 (base rows 0..511, block rows 0..63), d_bound[n]."""
+        _check(self.L.mpc_debug_screen_probe_device(self.h, int(channel), int(block), d_vectors or None, int(n), d_approx or None,
+                                                    d_bound or None, stream or None))
+
     def calc_mp(self, channel, vectors, quant_k=None):
         """matching::CalcMPDynamic (MatchingPursuit.h:22) on the device for vectors[n,64].
         Returns counts[n], choices[n,K], energy[n], swept[n]."""
@@ -1300,6 +1328,26 @@ class CompressionContext:
                                         choices.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(_u16p),
                                         energy.ctypes.data_as(_dp), swept.ctypes.data_as(_u32p)))
         return counts, choices, energy, swept
+
+
+FILTER_TILE_HALVES = 2048          # 16-bit elements of one filter tile (16 rows x 64 pixels, hi and lo)
+
+
+def filter_tiles(rows, tiles, k_order=0):
+    """mpc_filter_tiles (host only, for the tests): rows[nrows,64] doubles -> (out uint16[tiles * 2048], shadow uint8[nrows])."""
+    L = load_library()
+    rows = np.ascontiguousarray(rows, np.float64).reshape(-1, 64)
+    out = np.full(int(tiles) * FILTER_TILE_HALVES if tiles > 0 else 1, 0xFFFF, np.uint16)
+    shadow = np.full(max(rows.shape[0], 1), 0xFF, np.uint8)
+    _check(L.mpc_filter_tiles(rows.ctypes.data_as(_dp), rows.shape[0], int(tiles), int(k_order), out.ctypes.data_as(_u16p),
+                              shadow.ctypes.data_as(_u8p)))
+    return out, shadow[:rows.shape[0]]
+
+
+def debug_gram_device(d_base, d_detail, d_block_rows, d_block_row_off, d_shadow, num_base, n_sel, d_gram, stream=0):
+    """mpc_debug_gram_device (for the tests): the Gram kernel on the caller's own device arrays (ints from tensor.data_ptr())."""
+    _check(load_library().mpc_debug_gram_device(d_base or None, d_detail or None, d_block_rows or None, d_block_row_off or None,
+                                                d_shadow or None, int(num_base), int(n_sel), d_gram or None, stream or None))
 
 
 def encode_images_multi(contexts, frames, quant=None, views=False):

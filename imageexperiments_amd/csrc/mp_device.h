@@ -207,6 +207,10 @@ int pursuit_units_per_workgroup();
 // Gram table of one channel (see mp_pursuit.hip); shadow[detail_rows]: 1 = row left out of the filter copy
 int launch_gram(const double* base, const double* detail, const int32_t* block_rows, const int32_t* block_row_off,
                 const uint8_t* shadow, float* gram, int num_base, int n_sel, long long stride, void* stream);
+// The tests' probe of the screen (see mp_pursuit.hip): n <= 16 vectors of 64 doubles against the 32 tiles at base_tiles and the 4 at
+// block_tiles; approx[n][576], bound[n].  vectors and approx 16-byte aligned.
+int launch_screen_probe(const uint16_t* base_tiles, const uint16_t* block_tiles, const double* vectors, int n, float* approx, float* bound,
+                        void* stream);
 
 // ---- device-side stream assembly (mp_streams.hip) ----
 struct StreamArgs {

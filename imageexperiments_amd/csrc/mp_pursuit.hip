@@ -277,6 +277,47 @@ __device__ __forceinline__ int lane_id_fresh()
     const int pix0 = 16 * pos_of(h);                                                  \
     (void)slot; (void)h; (void)pix0;
 
+// ---- the screen's arithmetic, shared by the pursuit kernel and the probe kernel of the tests (mp_screen_probe_kernel) ------
+// One tile (16 rows x 64 pixels, split-bf16 in operand order: av = hi, lo of kk = 0, then of kk = 1) times the 16 columns whose
+// split-bf16 halves are hi / lo: the three product groups hi.hi, hi.lo, lo.hi per kk, accumulated in this order in f32.
+__device__ __forceinline__ f32x4 tile_mfma(const uint4 (&av)[4], const bf16x8 (&hi)[2], const bf16x8 (&lo)[2])
+{
+    f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+        bf16x8 ah, al;
+        __builtin_memcpy(&ah, &av[2 * kk + 0], 16);
+        __builtin_memcpy(&al, &av[2 * kk + 1], 16);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, hi[kk], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, lo[kk], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, hi[kk], acc, 0, 0, 0);
+    }
+    return acc;
+}
+// Phase (2a): the B operands of a lane's 16 residual pixels (-> f32, hi = bf16(x), lo = bf16(x - hi)), |r~| of the slot's whole
+// residual (all four lanes) with its rounding allowance, the bound E of this step's MFMA approximations, and "not all zero".
+template <class T>
+__device__ __forceinline__ void screen_operands(const T (&r)[16], bf16x8 (&bh)[2], bf16x8 (&bl)[2], float& rnorm, float& Eb, bool& nz)
+{
+    double ss = 0.0;
+    bool nzl = false;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const T d = r[i];
+        nzl = nzl || (d != 0);
+        const float x = (float)d;
+        ss += (double)x * (double)x;
+        const unsigned short hb = bf16_of(x);
+        const unsigned short lb = bf16_of(x - __uint_as_float((unsigned)hb << 16));
+        bh[i >> 3][i & 7] = (short)hb;
+        bl[i >> 3][i & 7] = (short)lb;
+    }
+    ss = reduce4_add(ss);
+    nz = reduce4_add(nzl ? 1u : 0u) != 0u;
+    rnorm = (float)__builtin_sqrt(ss) * 1.0000002f;
+    Eb = kSlack * rnorm + kAbs;
+}
+
 // In-kernel phase stamps: diagnostic builds only (-DMPC_STAMPS, tools/stamps.sh); the product build has none.
 #ifdef MPC_STAMPS
 #define STAMP(i)                                              \
@@ -385,19 +426,6 @@ __global__ __launch_bounds__(64 * kWaves, kWaves / 4) void mp_pursuit_kernel(con
     }
     bool queue_empty = false;
 
-    auto tile_mfma = [&](const uint4 (&av)[4], const bf16x8 (&hi)[2], const bf16x8 (&lo)[2]) {
-        f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            bf16x8 ah, al;
-            __builtin_memcpy(&ah, &av[2 * kk + 0], 16);
-            __builtin_memcpy(&al, &av[2 * kk + 1], 16);
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, hi[kk], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, lo[kk], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, hi[kk], acc, 0, 0, 0);
-        }
-        return acc;
-    };
     // record index of tile-channel t of this channel: counts[rec], choices[rec * K + step]
     auto rec_of = [&](int t) { return a.vec_in ? (long long)t : (long long)t * 3 + ch; };
     auto lds_tile = [&](uint4 (&dst)[4], int t, int lane) {
@@ -579,23 +607,7 @@ __global__ __launch_bounds__(64 * kWaves, kWaves / 4) void mp_pursuit_kernel(con
         bool nz[kGroups], odd[kGroups];
         static_for<kGroups>([&](auto gc) {
             constexpr int g = decltype(gc)::value;
-            double ss = 0.0;
-            bool nzl = false;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const T d = r[g][i];
-                nzl = nzl || (d != 0);
-                const float x = (float)d;
-                ss += (double)x * (double)x;
-                const unsigned short hb = bf16_of(x);
-                const unsigned short lb = bf16_of(x - __uint_as_float((unsigned)hb << 16));
-                bh[g][i >> 3][i & 7] = (short)hb;
-                bl[g][i >> 3][i & 7] = (short)lb;
-            }
-            ss = reduce4_add(ss);
-            nz[g] = reduce4_add(nzl ? 1u : 0u) != 0u;
-            rnorm[g] = (float)__builtin_sqrt(ss) * 1.0000002f;
-            Eb[g] = kSlack * rnorm[g] + kAbs;
+            screen_operands(r[g], bh[g], bl[g], rnorm[g], Eb[g], nz[g]);
             rbound[g] = rnorm[g];
             odd[g] = !(rnorm[g] < kHuge);                           // NaN, infinity or large enough to overflow the f32 side
         });
@@ -1219,6 +1231,47 @@ int launch_gram(const double* base, const double* detail, const int32_t* block_r
 {
     hipLaunchKernelGGL(mp_gram_kernel, dim3((unsigned)num_base, (unsigned)((n_sel + 63) / 64)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), base, detail, block_rows, block_row_off, shadow, gram, num_base, n_sel, stride);
+    return (int)hipGetLastError();
+}
+
+// --------------------------------------------------------------------------------------------------
+// Test probe of the screen (mpc_debug_screen_probe_device): ONE wave, lane (slot, h) holds pixels 16 pos(h) .. + 15 of vector
+// `slot` as in the pursuit kernel; operands and bound from screen_operands, products from tile_mfma over the 32 base tiles and
+// the 4 tiles of one block, read from the resident tables.  approx[slot][16 tile + 4 h + v] (base rows 0 .. 511, then block rows
+// 0 .. 63: the survivor codes' mapping), bound[slot] = Eb.  Slots >= n hold zero vectors and write nothing.
+// --------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void mp_screen_probe_kernel(const uint16_t* __restrict__ base_tiles, const uint16_t* __restrict__ block_tiles,
+                                                             const double* __restrict__ vectors, int n, float* __restrict__ approx,
+                                                             float* __restrict__ bound)
+{
+    FRESH_LANE
+    double r[16];
+    if (slot < n) load16(r, vectors + (long long)slot * N + pix0);
+    else
+#pragma unroll
+        for (int i = 0; i < 16; ++i) r[i] = 0.0;
+    bf16x8 bh[2], bl[2];
+    float rnorm, Eb;
+    bool nz;
+    screen_operands(r, bh, bl, rnorm, Eb, nz);
+    if (slot < n && h == 0) bound[slot] = Eb;
+    for (int t = 0; t < kTilesLds; ++t) {
+        const uint4* tiles = reinterpret_cast<const uint4*>(t < kBaseFilterTiles ? base_tiles : block_tiles) + lane;
+        const int tt = t < kBaseFilterTiles ? t : t - kBaseFilterTiles;
+        uint4 av[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) av[q] = tiles[tt * 256 + q * 64];
+        const f32x4 acc = tile_mfma(av, bh, bl);
+        if (slot < n)
+            *reinterpret_cast<float4*>(approx + (long long)slot * (16 * kTilesLds) + 16 * t + 4 * h) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+    }
+}
+
+int launch_screen_probe(const uint16_t* base_tiles, const uint16_t* block_tiles, const double* vectors, int n, float* approx, float* bound,
+                        void* stream)
+{
+    hipLaunchKernelGGL(mp_screen_probe_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), base_tiles, block_tiles, vectors, n,
+                       approx, bound);
     return (int)hipGetLastError();
 }
 

@@ -9,6 +9,7 @@
 //   mpcodec_decode.cpp     tile reconstruction from records (mpc_decode_tiles_device), distortion, patch statistics
 //   mpcodec_decode_seq.cpp the decoder of containers (mpc_decode_image, mpc_decode_images*), the device unpack of coded streams
 //   mpcodec_index.cpp      the seek index's host-only entry points (mpc_container_index, mpc_parse_container_by_index)
+//   mpcodec_debug.cpp      the tests' entry points to the screen's tables (mpc_debug_*, mpc_filter_tiles)
 #pragma once
 
 #include "../../include/mpcodec.h"

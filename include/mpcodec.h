@@ -725,6 +725,40 @@ mpc_status mpc_rate_distortion(mpc_context* ctx, const uint8_t* rgb, int width, 
 mpc_status mpc_rate_distortion_device(mpc_context* ctx, const uint8_t* d_rgb, int width, int height, const double* quants,
                                       int n_levels, size_t* nbytes, unsigned long long* sse, double* psnr, uint8_t** bytes);
 
+/* ---- test entry points ----
+ * These exist for the tests of the pursuit screen's tables (tests/test_screen_cases.py, tests/test_gpu_screen_tables.py) and are
+ * on no product path.  The screen decides nothing: a wrong Gram entry, a wrong filter tile or a bound that does not
+ * hold changes no record until a contest happens to fall inside the error, so these three are read back and probed directly.
+ * Every entry checks its arguments before it touches memory: MPC_ERR_ARGUMENT for a null pointer, a channel outside 0 ... 2, a
+ * block outside 0 ... num_base - 1, n outside 1 ... 16 or a rectangle outside the table; MPC_ERR_NO_DEVICE for a host-only context.
+ *
+ * The resident Gram table of `channel` is [num_base + detail_rows][num_base * 64] floats: row sel = base row sel (sel < num_base)
+ * or detail row sel - num_base of the channel; column 64 * blk + row = row `row` of DetailBasis[blk] of the channel (pad rows: 0).
+ * Copies rows [sel_begin, + sel_count) x columns [col_begin, + col_count) to the dense d_out[sel_count][col_count] on `stream`. */
+mpc_status mpc_debug_copy_gram_device(mpc_context* ctx, int channel, int sel_begin, int sel_count, int col_begin, int col_count,
+                                      float* d_out, void* stream);
+/* The Gram kernel on the caller's own device arrays: d_base[num_base][64], d_detail[rows][64], d_block_rows[num_base] (<= 64 each),
+ * d_block_row_off[num_base] (first detail row of each block), d_shadow[rows] (1 = the row's column is left 0), n_sel = num_base +
+ * rows; d_gram[n_sel][num_base * 64] (16-byte aligned) as above, rows beyond n_sel are not written.  Asynchronous on `stream`. */
+mpc_status mpc_debug_gram_device(const double* d_base, const double* d_detail, const int32_t* d_block_rows, const int32_t* d_block_row_off,
+                                 const uint8_t* d_shadow, int num_base, int n_sel, float* d_gram, void* stream);
+/* The uploaded split-bf16 filter tiles as the pursuit kernel reads them, to host memory: channel = -1: the 32 base tiles
+ * (host_out[32 * 2048], block ignored); channel 0 ... 2: the 4 tiles of DetailBasis[block] of that channel (host_out[4 * 2048]). */
+mpc_status mpc_debug_copy_filter_tiles(mpc_context* ctx, int channel, int block, uint16_t* host_out);
+/* Host only, no context: the function that makes those tiles.  rows[nrows][64] doubles, nrows <= 16 * tiles, tiles 1 ... 64;
+ * every element x becomes hi = bf16(float(x)), lo = bf16(float(x) - hi), round to nearest even, at
+ *   out[((tile*4 + 2*kk + part)*64 + lane)*8 + j]   (part 0 = hi, 1 = lo)
+ * of row tile*16 + (lane & 15), pixel 32*kk + 8*(lane >> 4) + j (k_order 0) or 16*pos(lane >> 4) + 8*kk + j with pos = 0, 1, 3, 2
+ * (k_order 1, the pursuit kernel's).  out[tiles * 2048].  A row that is bit for bit an earlier row or its negation is left zero
+ * and marked in shadow[nrows] (optional); so are the rows from nrows on (unmarked). */
+mpc_status mpc_filter_tiles(const double* rows, int nrows, int tiles, int k_order, uint16_t* out, uint8_t* shadow);
+/* One wave of the pursuit's screen on n (1 ... 16) residual vectors d_vectors[n][64] (doubles, 16-byte aligned): the B operands as
+ * the kernel's phase (2a) makes them (f64 -> f32, hi / lo bf16, |r~|, E), the six-MFMA tile product over the 32 resident base tiles
+ * and the 4 resident tiles of DetailBasis[block] of `channel`.  d_approx[n][576] (16-byte aligned): [16*tile + 4*h + v] = the
+ * approximation of base row 0 ... 511, then of block row 0 ... 63; d_bound[n] = E.  Asynchronous on `stream`. */
+mpc_status mpc_debug_screen_probe_device(mpc_context* ctx, int channel, int block, const double* d_vectors, int n, float* d_approx,
+                                         float* d_bound, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
