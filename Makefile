@@ -19,6 +19,9 @@
 #                    (what tests/test_asan_index2.py runs)
 #   make asan-view   tests/cpp/asan_view: the views on the host -- the truncation to the first steps, the view's parse through the
 #                    seek index -- on damaged indexes, damaged containers and views of every kind (what tests/test_asan_view.py runs)
+#   make asan-index-scan  tests/cpp/asan_index_scan: the seek index from a bit scan on the host -- step table, segment maps, chain and
+#                    walk, the proposal and its acceptance -- on damaged and truncated containers, at sizes that make codes span
+#                    segments and streams span windows (what tests/test_asan_index_scan.py runs)
 #
 # GPU AddressSanitizer is not available on the test pool; the kernels are covered by the parity suite instead.
 SAN = -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer
@@ -66,6 +69,12 @@ tests/cpp/asan_view_bin: tests/cpp/asan_view.cpp $(wildcard imageexperiments_amd
 asan-view: tests/cpp/asan_view_bin
 	ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=print_stacktrace=1 MPC_HOST_THREADS=4 ./tests/cpp/asan_view_bin
 
+tests/cpp/asan_index_scan_bin: tests/cpp/asan_index_scan.cpp $(wildcard imageexperiments_amd/csrc/host_*.cpp imageexperiments_amd/csrc/host_*.h)
+	g++ -std=c++17 -O1 -g $(SAN) -ffp-contract=off -pthread -Wall -Wno-unused-function tests/cpp/asan_index_scan.cpp -o $@
+
+asan-index-scan: tests/cpp/asan_index_scan_bin
+	ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=print_stacktrace=1 MPC_HOST_THREADS=4 ./tests/cpp/asan_index_scan_bin $(GOLDEN_MN)
+
 oracle/_build/liboracle_asan.so: $(wildcard oracle/*.c oracle/*.h)
 	mkdir -p oracle/_build
 	gcc -std=c11 -O1 -g $(SAN) -ffp-contract=off -fPIC -shared -o $@ oracle/mpo_*.c -lm
@@ -74,6 +83,6 @@ asan-oracle: oracle/_build/liboracle_asan.so
 	LD_PRELOAD=$$(gcc -print-file-name=libasan.so) ASAN_OPTIONS=detect_leaks=0 ORACLE_LIB=$(CURDIR)/oracle/_build/liboracle_asan.so \
 	    python -m pytest tests/test_oracle_golden.py -x -q -p no:cacheprovider
 
-asan: asan-host asan-index asan-encode-index asan-encode-index2 asan-region asan-index2 asan-view asan-oracle
+asan: asan-host asan-index asan-encode-index asan-encode-index2 asan-region asan-index2 asan-view asan-index-scan asan-oracle
 
-.PHONY: asan asan-host asan-index asan-encode-index asan-encode-index2 asan-region asan-index2 asan-view asan-oracle
+.PHONY: asan asan-host asan-index asan-encode-index asan-encode-index2 asan-region asan-index2 asan-view asan-index-scan asan-oracle

@@ -181,6 +181,8 @@ def _bind_bitstream(L):
     L.mpc_unpack_symbol_streams_device.argtypes = [vp, C.c_int, _u16p, _ullp, _u8p, _ullp, C.POINTER(_u16p), C.POINTER(C.c_size_t)]
     L.mpc_container_index.argtypes = [_u8p, C.c_size_t, C.c_int, C.POINTER(_u8p), C.POINTER(C.c_size_t)]
     L.mpc_container_index2.argtypes = [_u8p, C.c_size_t, C.c_int, C.c_uint, C.POINTER(_u8p), C.POINTER(C.c_size_t)]
+    L.mpc_container_index_scan.argtypes = [_u8p, C.c_size_t, C.c_int, C.c_uint, C.c_int, C.c_int, C.POINTER(_u8p), C.POINTER(C.c_size_t),
+                                           C.POINTER(C.c_int)]
     L.mpc_index_extend.argtypes = [_u8p, C.c_size_t, _u8p, C.c_size_t, C.POINTER(_u8p), C.POINTER(C.c_size_t)]
     L.mpc_index_version.argtypes = [_u8p, C.c_size_t]
     L.mpc_index_version.restype = C.c_int
@@ -188,6 +190,14 @@ def _bind_bitstream(L):
     L.mpc_index_info.argtypes = [_u8p, C.c_size_t, C.POINTER(_IndexHeader)]
     L.mpc_index_stream.argtypes = [_u8p, C.c_size_t, C.c_int, C.POINTER(_IndexStreamInfo), C.POINTER(C.c_uint64), C.c_size_t]
     L.mpc_parse_container_by_index.argtypes = [_u8p, C.c_size_t, _u8p, C.c_size_t, C.POINTER(_u16p), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
+    L.mpc_container_index_device.argtypes = [vp, _u8p, C.c_size_t, C.c_int, C.c_uint, C.POINTER(_u8p), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
+    L.mpc_debug_container_index_device.argtypes = [vp, _u8p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(_u8p), C.POINTER(C.c_size_t),
+                                                   C.POINTER(C.c_int)]
+    L.mpc_decode_images_scan.argtypes = [vp, C.POINTER(_u8p), C.POINTER(C.c_size_t), C.c_int, C.POINTER(_u8p), C.POINTER(C.c_int),
+                                         C.POINTER(C.c_int), C.POINTER(_u8p), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
+    L.mpc_decode_images_scan_device.argtypes = [vp, C.POINTER(_u8p), C.POINTER(C.c_size_t), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                                C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_u8p), C.POINTER(C.c_size_t),
+                                                C.POINTER(C.c_int)]
     L.mpc_parse_container_device.argtypes = [vp, _u8p, C.c_size_t, _u8p, C.c_size_t, C.POINTER(_u16p), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
     _rp = C.POINTER(MpcRect)
     _win = [_u8p, C.c_size_t, _u8p, C.c_size_t, _rp, C.c_uint, C.POINTER(_u16p), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
@@ -480,6 +490,18 @@ def container_index2(blob, interval=0, flags=0):
     out, n = _u8p(), C.c_size_t(0)
     _check(L.mpc_container_index2(buf.ctypes.data_as(_u8p), buf.size, int(interval), int(flags), C.byref(out), C.byref(n)))
     return _take_bytes(L, out, n)
+
+
+def container_index_scan(blob, interval=0, flags=0, segment_bits=0, window_bits=0):
+    """mpc_container_index_scan: container_index2's blob without a serial parse of the container (step table, segment maps, chain
+    and walk per stream, on the host: what the device scan computes) -> (index, route).  route 0 = the scan produced the blob,
+    1 = it gave up and the serial builder answered.  segment_bits, window_bits: 0 = the defaults; other sizes are for tests."""
+    L = load_library()
+    buf = np.frombuffer(blob, np.uint8)
+    out, n, route = _u8p(), C.c_size_t(0), C.c_int(-1)
+    _check(L.mpc_container_index_scan(buf.ctypes.data_as(_u8p), buf.size, int(interval), int(flags), int(segment_bits), int(window_bits),
+                                      C.byref(out), C.byref(n), C.byref(route)))
+    return _take_bytes(L, out, n), route.value
 
 
 def index_extend(blob, index):
@@ -1051,6 +1073,70 @@ class CompressionContext:
         torch.cuda.synchronize(self.device)                      # `out` may still be being written by the caller's streams
         _check(self.L.mpc_decode_images_indexed_device(self.h, ptrs, sizes, iptrs, isizes, n, d_ptrs, caps, W, H, routes))
         return [out[i].view(-1)[:3 * W[i] * H[i]].view(H[i], W[i], 3) for i in range(n)], list(routes)
+
+    def container_index_device(self, blob, interval=0, flags=0):
+        """mpc_container_index_device: container_index2's blob with the checkpoints found by the device's bit scan instead of a
+        serial parse -> (index, route).  route 0 = the scan produced the blob and the device parse accepted it, 1 = the host
+        builder ran.  Status, text and blob are container_index2's for every input."""
+        buf = np.frombuffer(blob, np.uint8)
+        out, n, route = _u8p(), C.c_size_t(0), C.c_int(-1)
+        _check(self.L.mpc_container_index_device(self.h, buf.ctypes.data_as(_u8p), buf.size, int(interval), int(flags), C.byref(out), C.byref(n),
+                                                 C.byref(route)))
+        return _take_bytes(self.L, out, n), route.value
+
+    def debug_container_index_device(self, blob, interval=0, segment_bits=0, window_bits=0):
+        """mpc_debug_container_index_device: container_index_device (flags 0) with the scan's segment and window sizes given, so
+        that a test can make a chain cross windows and a code jump segments on a small container -> (index, route)"""
+        buf = np.frombuffer(blob, np.uint8)
+        out, n, route = _u8p(), C.c_size_t(0), C.c_int(-1)
+        _check(self.L.mpc_debug_container_index_device(self.h, buf.ctypes.data_as(_u8p), buf.size, int(interval), int(segment_bits),
+                                                       int(window_bits), C.byref(out), C.byref(n), C.byref(route)))
+        return _take_bytes(self.L, out, n), route.value
+
+    def _scanned_indexes(self, n, routes, idx, idx_n):
+        return [_take_bytes(self.L, idx[i], C.c_size_t(idx_n[i])) if routes[i] == 0 and idx[i] else None for i in range(n)]
+
+    def decode_images_scan(self, blobs, keep_indexes=False):
+        """mpc_decode_images_scan: decode_images for containers that come without a seek index: per frame one upload, the device's
+        bit scan for the checkpoints, then the indexed route on the bytes already on the device.  Returns (frames, routes),
+        routes[f] 0 = scanned and parsed on the device, 1 = the serial route; with keep_indexes (frames, routes, indexes), indexes[f]
+        the version-1 index of a frame on route 0 (== container_index(blob)), None on route 1.  Pixels and errors are decode_images's."""
+        bufs, ptrs, sizes = self._containers(blobs)
+        n = len(bufs)
+        outs, W, H, routes = (_u8p * n)(), (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)()
+        idx, idx_n = ((_u8p * n)(), (C.c_size_t * n)()) if keep_indexes else (None, None)
+        _check(self.L.mpc_decode_images_scan(self.h, ptrs, sizes, n, outs, W, H, idx, idx_n, routes))
+        frames = [_take_view(self.L, outs[i], C.c_size_t(3 * W[i] * H[i])).reshape(H[i], W[i], 3) for i in range(n)]
+        if not keep_indexes:
+            return frames, list(routes)
+        return frames, list(routes), self._scanned_indexes(n, routes, idx, idx_n)
+
+    def decode_images_scan_device(self, blobs, out=None, keep_indexes=False):
+        """mpc_decode_images_scan_device: the same with the pixels left on the context's device (`out` as for
+        decode_images_device).  Returns (frames, routes), or (frames, routes, indexes) with keep_indexes."""
+        import torch
+        bufs, ptrs, sizes = self._containers(blobs)
+        n = len(bufs)
+        if out is None:
+            out = []
+            for b in bufs:
+                try:
+                    w, h, _, _ = container_info(b)
+                except MpcError:                                 # the call itself refuses the frame, in its turn
+                    w, h = 1, 1
+                out.append(torch.empty(3 * w * h, dtype=torch.uint8, device=f"cuda:{self.device}"))
+        if len(out) != n or any(t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous() for t in out):
+            raise ValueError("out: one contiguous uint8 device tensor per container")
+        d_ptrs = (C.c_void_p * n)(*[C.c_void_p(t.data_ptr()) for t in out])
+        caps = (C.c_size_t * n)(*[t.numel() for t in out])
+        W, H, routes = (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)()
+        idx, idx_n = ((_u8p * n)(), (C.c_size_t * n)()) if keep_indexes else (None, None)
+        torch.cuda.synchronize(self.device)                      # `out` may still be being written by the caller's streams
+        _check(self.L.mpc_decode_images_scan_device(self.h, ptrs, sizes, n, d_ptrs, caps, W, H, idx, idx_n, routes))
+        frames = [out[i].view(-1)[:3 * W[i] * H[i]].view(H[i], W[i], 3) for i in range(n)]
+        if not keep_indexes:
+            return frames, list(routes)
+        return frames, list(routes), self._scanned_indexes(n, routes, idx, idx_n)
 
     @staticmethod
     def _rects(rects, n):

@@ -202,6 +202,44 @@ std::vector<size_t> expected_sizes(const std::vector<uint16_t>& lengths, int K);
 bool read_compressed_coded_by_index(const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes, CodedStreams& out,
                                     int* route);
 
+// ---- the seek index without a serial parse ("Seek index from a bit scan") ----
+// Which code begins at bit p of a stream, and how long it is, depends on the bits at p and the stream's table alone (huffman_step /
+// golomb_step with the container's end as the required end).  Evaluated at every bit of a window, the serial parse is a walk along
+// p -> p + len(p), which composes segment by segment: the checkpoints come out without walking the codes one after another.
+constexpr uint32_t kScanSegmentDefault = 256, kScanWindowDefault = 1u << 22;
+constexpr uint32_t kScanSegmentMin = 32, kScanSegmentMax = 1u << 15, kScanWindowMax = 1u << 26;
+// A Golomb code whose unary run reaches this many bits is "no code here" to the scan (no encoder writes one: a symbol has 16 bits);
+// it bounds the step of a lane on the device.  The scan then gives up and the serial builder answers
+constexpr uint32_t kScanUnaryLimit = 1u << 16;
+// 0 = the default; true = a segment of 32 ... 32768 bits and a window of whole segments, at most 2^26 bits
+bool scan_sizes_ok(uint32_t* segment_bits, uint32_t* window_bits);
+// One stream's checkpoints: from bit b0 the codes of a stream that has `n` of them (Huffman: the pseudo-EOF must follow exactly n;
+// Golomb: the stream ends behind the n-th).  cps gets the bit of code j * interval for j * interval < n, *end_bit the bit behind
+// the stream.  false = the scan gives up on this stream (a dead chain, another count).  n <= the bits behind b0 is the caller's check
+struct StreamScanner {
+    virtual ~StreamScanner() {}
+    virtual bool scan(const StreamWrapper& w, uint64_t b0, uint64_t n, uint32_t interval, std::vector<uint64_t>& cps, uint64_t* end_bit) = 0;
+};
+// The host's scanner: step table, segment maps, chain and emit over windows of window_bits, as mp_scan.hip's kernels do them
+struct HostStreamScanner : StreamScanner {
+    const uint8_t* bytes;
+    size_t nbytes;
+    uint32_t segment_bits, window_bits;
+    HostStreamScanner(const uint8_t* b, size_t n, uint32_t segment, uint32_t window) : bytes(b), nbytes(n), segment_bits(segment), window_bits(window) {}
+    bool scan(const StreamWrapper& w, uint64_t b0, uint64_t n, uint32_t interval, std::vector<uint64_t>& cps, uint64_t* end_bit) override;
+};
+// The version-1 blob of the container from the scanner's checkpoints, stream behind stream in container order (the wrappers by
+// read_stream_wrapper, the sizes of streams 1 ... 6K from the lengths stream decoded chunk by chunk from its fresh checkpoints).
+// false = the scan gives up (the give-up rule); the blob is a proposal: nothing has verified it yet
+bool propose_container_index(const uint8_t* bytes, size_t nbytes, uint32_t interval, StreamScanner& scanner, std::vector<uint8_t>& blob);
+// build_container_index(bytes, nbytes, interval, blob, expanded) by the host scanner: the proposal, accepted only if
+// read_compressed_coded_by_index takes route 0 with it (then it is the serial parser's path: the blob the serial builder makes);
+// *route = 0.  Otherwise *route = 1 and the serial builder's result and verdict
+bool scan_container_index(const uint8_t* bytes, size_t nbytes, uint32_t interval, bool expanded, uint32_t segment_bits, uint32_t window_bits,
+                          std::vector<uint8_t>& blob, int* route);
+// an accepted version-1 proposal in the version asked for: expanded = through extend_container_index.  false = it refuses
+bool accept_proposed_index(const uint8_t* bytes, size_t nbytes, std::vector<uint8_t>& blob, bool expanded);
+
 // ---- a pixel rectangle of a frame through the index ("Decoder: regions") ----
 // The tiles a rectangle touches: the grid [tx0, tx1) x [ty0, ty1), inside the contiguous tile range [t0, t1) of the streams' order
 // (t = tx * tiles_y + ty).  false = the rectangle is empty or not inside the frame

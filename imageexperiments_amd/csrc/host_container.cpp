@@ -819,53 +819,259 @@ bool plan_indexed_parse(const uint8_t* bytes, size_t nbytes, const uint8_t* inde
     return std::find(ok.begin(), ok.end(), 0) == ok.end();
 }
 
-bool read_compressed_coded_by_index(const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes, CodedStreams& out,
-                                    int* route) {
-    *route = 1;
+namespace {
+// the acceptance rule whole: plan_indexed_parse, then every chunk by the chunk decoders; false = the index is not used
+bool read_coded_by_index_alone(const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes, CodedStreams& out) {
     IndexedPlan plan;
-    auto by_index = [&]() -> bool {
-        if (!plan_indexed_parse(bytes, nbytes, index, index_bytes, plan)) return false;
-        const ContainerIndex& x = plan.index;
-        const int K = x.K;
-        auto decode_stream = [&](size_t j, std::vector<uint16_t>& dst) -> bool {
-            const IndexStream& is = x.streams[j];
-            const StreamWrapper& w = plan.wrappers[j];
-            dst.assign(static_cast<size_t>(is.n_coded), 0);
-            const size_t chunks = is.checkpoints.size();
-            for (size_t c = 0; c < chunks; ++c) {
-                const bool last = c + 1 == chunks;
-                const size_t begin = static_cast<size_t>(is.checkpoints[c]);
-                const size_t end = static_cast<size_t>(last ? is.end_bit : is.checkpoints[c + 1]);
-                const size_t first = c * x.interval, count = std::min<size_t>(x.interval, dst.size() - first);
-                if (w.mode == 0 ? !huffman_decode_chunk(w.cb, bytes, nbytes, begin, end, count, last, dst.data() + first)
-                                : !golomb_decode_chunk(w.m, bytes, nbytes, begin, end, count, dst.data() + first))
-                    return false;
-            }
-            return true;
-        };
-        out = CodedStreams();
-        out.width = x.width; out.height = x.height; out.K = K; out.block_size = x.block_size;
-        std::memcpy(out.quant, plan.quant, sizeof(out.quant));
-        if (!decode_stream(0, out.lengths)) return false;
-        for (uint16_t length : out.lengths)
-            if (length > K) return false;
-        out.expect = expected_sizes(out.lengths, K);
-        for (int i = 0; i < 6 * K; ++i)
-            if (out.expect[i] != x.streams[static_cast<size_t>(i) + 1].expect) return false;
-        out.codes.assign(static_cast<size_t>(6 * K), {});
-        out.packed.assign(static_cast<size_t>(6 * K), 0);
-        for (int i = 0; i < 6 * K; ++i) {
-            out.packed[i] = static_cast<uint8_t>(x.streams[static_cast<size_t>(i) + 1].packed);
-            if (!decode_stream(static_cast<size_t>(i) + 1, out.codes[i])) return false;
+    if (!plan_indexed_parse(bytes, nbytes, index, index_bytes, plan)) return false;
+    const ContainerIndex& x = plan.index;
+    const int K = x.K;
+    auto decode_stream = [&](size_t j, std::vector<uint16_t>& dst) -> bool {
+        const IndexStream& is = x.streams[j];
+        const StreamWrapper& w = plan.wrappers[j];
+        dst.assign(static_cast<size_t>(is.n_coded), 0);
+        const size_t chunks = is.checkpoints.size();
+        for (size_t c = 0; c < chunks; ++c) {
+            const bool last = c + 1 == chunks;
+            const size_t begin = static_cast<size_t>(is.checkpoints[c]);
+            const size_t end = static_cast<size_t>(last ? is.end_bit : is.checkpoints[c + 1]);
+            const size_t first = c * x.interval, count = std::min<size_t>(x.interval, dst.size() - first);
+            if (w.mode == 0 ? !huffman_decode_chunk(w.cb, bytes, nbytes, begin, end, count, last, dst.data() + first)
+                            : !golomb_decode_chunk(w.m, bytes, nbytes, begin, end, count, dst.data() + first))
+                return false;
         }
         return true;
     };
-    if (by_index()) {
+    out = CodedStreams();
+    out.width = x.width; out.height = x.height; out.K = K; out.block_size = x.block_size;
+    std::memcpy(out.quant, plan.quant, sizeof(out.quant));
+    if (!decode_stream(0, out.lengths)) return false;
+    for (uint16_t length : out.lengths)
+        if (length > K) return false;
+    out.expect = expected_sizes(out.lengths, K);
+    for (int i = 0; i < 6 * K; ++i)
+        if (out.expect[i] != x.streams[static_cast<size_t>(i) + 1].expect) return false;
+    out.codes.assign(static_cast<size_t>(6 * K), {});
+    out.packed.assign(static_cast<size_t>(6 * K), 0);
+    for (int i = 0; i < 6 * K; ++i) {
+        out.packed[i] = static_cast<uint8_t>(x.streams[static_cast<size_t>(i) + 1].packed);
+        if (!decode_stream(static_cast<size_t>(i) + 1, out.codes[i])) return false;
+    }
+    return true;
+}
+}  // namespace
+
+bool read_compressed_coded_by_index(const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes, CodedStreams& out,
+                                    int* route) {
+    *route = 1;
+    if (read_coded_by_index_alone(bytes, nbytes, index, index_bytes, out)) {
         *route = 0;
         return true;
     }
     out = CodedStreams();
     return read_compressed_coded(bytes, nbytes, out);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The seek index from a bit scan: the checkpoints without walking the codes one after another.  What
+// mp_scan.hip's kernels compute per window, on the host: a step table (the code the serial parser's step finds at every bit), a map
+// per segment (from every bit the first code start at or behind the segment's end, and the codes on the way), the chain through
+// the segments from the stream's first bit, and the walk of every segment from its true entry that writes the checkpoints.
+// Every loop is bounded by the window, the segment or the segment count; none iterates until nothing changes.
+// ------------------------------------------------------------------------------------------------
+namespace {
+// a step: the code's bits in the low 24 | the pseudo-EOF | no code here (or it would pass the container's end)
+constexpr uint32_t kStepDead = 0x80000000u, kStepEof = 0x40000000u, kStepLen = 0x00FFFFFFu;
+// an exit, relative to the window's first bit: a code start at or behind the segment's end | the bit behind the pseudo-EOF | dead
+constexpr uint32_t kExitDead = 0x80000000u, kExitEof = 0x40000000u, kExitPos = 0x3FFFFFFFu;
+constexpr uint32_t kNoEntry = 0xFFFFFFFFu;
+
+uint32_t scan_step(const StreamWrapper& w, BitReader& in, size_t p, size_t total) {
+    in.set_position(p);
+    uint32_t v = 0;
+    if (w.mode == 0) {
+        if (!huffman_step(w.cb, in, total, &v)) return kStepDead;
+        return static_cast<uint32_t>(in.position() - p) | (v + 1u == w.cb.total ? kStepEof : 0u);
+    }
+    uint32_t ones = 0;                                          // the unary run, counted as far as the limit
+    for (size_t q = p; ones < kScanUnaryLimit && q < total; q += 32) {
+        in.set_position(q);
+        const uint32_t window = in.peek32();
+        if (window != 0xFFFFFFFFu) {
+            ones += static_cast<uint32_t>(__builtin_clz(~window));
+            break;
+        }
+        ones += 32;
+    }
+    if (ones >= kScanUnaryLimit) return kStepDead;
+    in.set_position(p);
+    if (!golomb_step(w.m, in, total, &v)) return kStepDead;
+    return static_cast<uint32_t>(in.position() - p);
+}
+}  // namespace
+
+bool scan_sizes_ok(uint32_t* segment_bits, uint32_t* window_bits) {
+    if (*segment_bits == 0) *segment_bits = kScanSegmentDefault;
+    if (*window_bits == 0) *window_bits = std::max(kScanWindowDefault, *segment_bits);
+    if (*segment_bits < kScanSegmentMin || *segment_bits > kScanSegmentMax) return false;
+    return *window_bits >= *segment_bits && *window_bits <= kScanWindowMax && *window_bits % *segment_bits == 0;
+}
+
+bool HostStreamScanner::scan(const StreamWrapper& w, uint64_t b0, uint64_t n, uint32_t interval, std::vector<uint64_t>& cps, uint64_t* end_bit) {
+    const uint64_t total = 8 * static_cast<uint64_t>(nbytes);
+    const bool golomb = w.mode == 1;
+    if (!golomb && w.cb.lut.empty()) return false;              // codes longer than 32 bits: serial only
+    cps.assign(static_cast<size_t>((n + interval - 1) / interval), 0);
+    const uint32_t S = segment_bits;
+    BitReader in(bytes, nbytes);
+    std::vector<uint32_t> step, exit_of, entry;
+    std::vector<uint16_t> count;
+    std::vector<uint64_t> first;
+    uint64_t pos = b0, ord = 0;                                 // the carry from window to window: a code start and its ordinal
+    for (;;) {                                                  // every window moves pos on by its own length at least, or ends the stream
+        if (golomb && ord == n) {
+            *end_bit = pos;
+            return true;
+        }
+        if (pos >= total) return false;
+        const uint32_t wlen = static_cast<uint32_t>(std::min<uint64_t>(window_bits, total - pos));
+        const uint32_t n_seg = (wlen + S - 1) / S;
+        step.resize(wlen);
+        for (uint32_t p = 0; p < wlen; ++p) step[p] = scan_step(w, in, static_cast<size_t>(pos + p), static_cast<size_t>(total));
+        exit_of.resize(wlen);
+        count.resize(wlen);
+        for (uint32_t seg = 0; seg < n_seg; ++seg) {            // right to left: a position's path is its code and the next position's path
+            const uint32_t lo = seg * S, hi = std::min(lo + S, wlen);
+            for (uint32_t p = hi; p-- > lo;) {
+                const uint32_t s = step[p], next = p + (s & kStepLen);
+                if (s & kStepDead) { exit_of[p] = kExitDead; count[p] = 0; }
+                else if (s & kStepEof) { exit_of[p] = kExitEof | next; count[p] = 0; }
+                else if (next >= hi) { exit_of[p] = next; count[p] = 1; }
+                else { exit_of[p] = exit_of[next]; count[p] = static_cast<uint16_t>(count[next] + 1u); }
+            }
+        }
+        entry.assign(n_seg, kNoEntry);
+        first.assign(n_seg, 0);
+        uint64_t rel = 0, o = ord;
+        uint32_t final_seg = kNoEntry;
+        for (uint32_t it = 0; it < n_seg && rel < wlen; ++it) {  // every round enters a later segment
+            const uint32_t seg = static_cast<uint32_t>(rel / S), e = exit_of[rel], c = count[rel];
+            // a Golomb stream ends behind its n-th code, whatever the path behind that runs into: a dead path counts its codes too
+            const bool ends_here = (e & kExitEof) || (golomb && o + c >= n);
+            if ((e & kExitDead) && !ends_here) return false;
+            entry[seg] = static_cast<uint32_t>(rel);
+            first[seg] = o;
+            if (ends_here) { final_seg = seg; break; }
+            rel = e & kExitPos;
+            o += c;
+        }
+        bool done = false;
+        for (uint32_t seg = 0; seg < n_seg; ++seg) {
+            if (entry[seg] == kNoEntry) continue;
+            const uint32_t hi = std::min((seg + 1) * S, wlen);
+            uint32_t p = entry[seg];
+            uint64_t q = first[seg];
+            for (uint32_t k = 0; k <= S; ++k) {                 // a code takes a bit at least: at most S codes begin in a segment
+                if (golomb && q == n) {
+                    if (seg == final_seg) { *end_bit = pos + p; done = true; }
+                    break;
+                }
+                if (p >= hi) break;
+                if (q < n && q % interval == 0) cps[static_cast<size_t>(q / interval)] = pos + p;
+                const uint32_t s = step[p];
+                if (s & kStepDead) return false;
+                if (s & kStepEof) {
+                    if (q != n) return false;                   // another count than the stream must hold
+                    if (seg == final_seg) { *end_bit = pos + p + (s & kStepLen); done = true; }
+                    break;
+                }
+                p += s & kStepLen;
+                ++q;
+            }
+        }
+        if (done) return true;
+        if (final_seg != kNoEntry) return false;
+        pos += rel;
+        ord = o;
+    }
+}
+
+bool propose_container_index(const uint8_t* bytes, size_t nbytes, uint32_t interval, StreamScanner& scanner, std::vector<uint8_t>& blob) {
+    if (interval == 0) interval = kIndexIntervalDefault;
+    BitReader in(bytes, nbytes);
+    ContainerIndex x;
+    if (!read_header(in, &x.width, &x.height, &x.K, &x.block_size)) return false;
+    const int K = x.K;
+    in.skip(static_cast<size_t>(16) * 3 * static_cast<size_t>(K));
+    const size_t tiles = tile_count(x.width, x.height, x.block_size);
+    if (tiles > (static_cast<size_t>(1) << 40) / 3) return false;
+    const uint64_t total = 8 * static_cast<uint64_t>(nbytes);
+    x.interval = interval;
+    x.nbytes = nbytes;
+    x.streams.resize(static_cast<size_t>(6 * K + 1));
+    std::vector<size_t> expect;
+    uint64_t at = in.position();
+    for (size_t j = 0; j < x.streams.size(); ++j) {
+        IndexStream& is = x.streams[j];
+        if (at >= total) return false;
+        BitReader r(bytes, nbytes);
+        r.set_position(static_cast<size_t>(at));
+        StreamWrapper w;
+        if (!read_stream_wrapper(r, j != 0, w)) return false;
+        const uint64_t want = j == 0 ? 3 * tiles : expect[j - 1];
+        const uint64_t n = w.packed ? w.packed_size : want;
+        if (w.packed && n - n / 3 > want) return false;
+        if (n > total - w.first_code_bit) return false;         // every code takes a bit at least
+        is.wrapper_bit = at;
+        is.n_coded = n;
+        is.expect = want;
+        is.packed = w.packed ? 1u : 0u;
+        is.mode = static_cast<uint32_t>(w.mode);
+        is.m = w.m;
+        if (!scanner.scan(w, w.first_code_bit, n, interval, is.checkpoints, &is.end_bit)) return false;
+        if (is.end_bit > total || is.end_bit <= at) return false;
+        if (j == 0) {                                           // the sizes of the 6K streams: the lengths, chunk by chunk
+            std::vector<uint16_t> lengths(static_cast<size_t>(n), 0);
+            const size_t chunks = is.checkpoints.size();
+            for (size_t c = 0; c < chunks; ++c) {
+                const bool last = c + 1 == chunks;
+                const size_t begin = static_cast<size_t>(is.checkpoints[c]);
+                const size_t end = static_cast<size_t>(last ? is.end_bit : is.checkpoints[c + 1]);
+                const size_t from = c * interval, count = std::min<size_t>(interval, lengths.size() - from);
+                if (w.mode == 0 ? !huffman_decode_chunk(w.cb, bytes, nbytes, begin, end, count, last, lengths.data() + from)
+                                : !golomb_decode_chunk(w.m, bytes, nbytes, begin, end, count, lengths.data() + from))
+                    return false;
+            }
+            for (uint16_t length : lengths)
+                if (length > K) return false;
+            expect = expected_sizes(lengths, K);
+        }
+        at = is.end_bit;
+    }
+    blob = index_blob(x);
+    return true;
+}
+
+bool accept_proposed_index(const uint8_t* bytes, size_t nbytes, std::vector<uint8_t>& blob, bool expanded) {
+    if (!expanded) return true;
+    std::vector<uint8_t> v2;
+    if (!extend_container_index(bytes, nbytes, blob.data(), blob.size(), v2)) return false;
+    blob.swap(v2);
+    return true;
+}
+
+bool scan_container_index(const uint8_t* bytes, size_t nbytes, uint32_t interval, bool expanded, uint32_t segment_bits, uint32_t window_bits,
+                          std::vector<uint8_t>& blob, int* route) {
+    *route = 0;
+    HostStreamScanner scanner(bytes, nbytes, segment_bits, window_bits);
+    CodedStreams s;
+    // the scan proposes, the existing verifier decides: an accepted index is the serial parser's path
+    if (propose_container_index(bytes, nbytes, interval, scanner, blob) && read_coded_by_index_alone(bytes, nbytes, blob.data(), blob.size(), s) &&
+        accept_proposed_index(bytes, nbytes, blob, expanded))
+        return true;
+    *route = 1;
+    blob.clear();
+    return build_container_index(bytes, nbytes, interval, blob, expanded);
 }
 
 bool tile_window(int width, int height, int block_size, int x, int y, int w, int h, TileWindow& win) {

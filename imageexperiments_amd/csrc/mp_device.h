@@ -8,6 +8,7 @@
 //   mp_entropy.hip   the per-symbol work of the entropy stage: run lengths, histograms, first appearances, code writing (EntropyArgs)
 //   mp_unpack.hip    the decoder's mirror of those two: run-length expansion and DC sums of coded streams (UnpackArgs)
 //   mp_parse.hip     the entropy codes of a container undone chunk by chunk from a seek index (ParseArgs)
+//   mp_scan.hip      that seek index's checkpoints found by a scan over every bit position of a stream (ScanArgs)
 //   mp_kernels.hip   the decoder, the symbol histogram, and the product's own cross-check of the tile encoder: a STEP-SYNCHRONOUS
 //                    pursuit that correlates every row exactly (a short sequence of kernels per MP step over the active
 //                    tile-channels: init, fill, base sweep, detail sweep, finish, update), behind MPC_PATH=steps / MPC_FILTER=0
@@ -370,6 +371,53 @@ int launch_parse_window(const ParseArgs& a, void* stream);
 // step at or above `steps` size 0 and the ranks (0, 0), and of the gather, which lays the streams out by these lengths.  The host's
 // UnpackStream / ParseStream tables hold those streams empty (no chunks, no symbols), so both layouts agree
 int launch_clamp_lengths(const ParseArgs& a, int steps, void* stream);
+
+// ---- the seek index's checkpoints from a bit scan (mp_scan.hip; the host form is HostStreamScanner, host_container.cpp) ----
+// One window of one stream: bits [win_begin, win_begin + win_bits) of the container, win_begin a code start of the stream with
+// ordinal `ord0` (the stream's first code bit, or the position the window before carried over).  All positions below are relative
+// to win_begin and fit 30 bits: win_bits <= 2^26, a code takes at most kScanUnaryCap + 34 bits.
+constexpr unsigned kScanUnaryCap = 1u << 16;        // a Golomb unary run this long is no code to the scan (host_bitstream.h: kScanUnaryLimit)
+constexpr unsigned kScanSuper = 64;                 // segments a super-segment holds
+// a step: the code's bits in the low 24 | the pseudo-EOF | no code here (or it would pass the container's end)
+constexpr unsigned kScanStepDead = 0x80000000u, kScanStepEof = 0x40000000u, kScanStepLen = 0x00FFFFFFu;
+// an exit: a code start at or behind the segment's (super-segment's) end | the bit behind the pseudo-EOF | the path dies
+constexpr unsigned kScanExitDead = 0x80000000u, kScanExitEof = 0x40000000u, kScanExitPos = 0x3FFFFFFFu;
+constexpr unsigned kScanNoEntry = 0xFFFFFFFFu;
+// ScanResult::state
+constexpr unsigned kScanContinue = 1u, kScanEnded = 2u, kScanDead = 3u, kScanMiscount = 4u;
+struct ScanResult {
+    unsigned state;                     // 0 = nothing written (a defect); continue: the stream goes on behind the window at
+    unsigned final_seg;                 //   `position` with ordinal `ordinal`; ended: `position` is the bit behind the stream and
+    unsigned long long position;        //   `ordinal` its codes; dead / miscount: the scan gives up
+    unsigned long long ordinal;
+};
+struct ScanArgs {
+    ParseArgs tables;                   // words (the container, zero-padded as for the parse), luts, lens, tables: this stream's own
+    ParseStream stream;                 // flags (Golomb), m, lut_off / len_off / table_off (0), total, max_length
+    unsigned long long total_bits;      // 8 * the container's bytes: every step's required end
+    unsigned long long win_begin;       // < total_bits
+    unsigned long long ord0;
+    unsigned long long n;               // the codes the stream must hold
+    unsigned win_bits;                  // <= total_bits - win_begin
+    unsigned seg_bits;                  // 32 ... 32768
+    unsigned n_segs;                    // ceil(win_bits / seg_bits)
+    unsigned n_supers;                  // ceil(n_segs / kScanSuper)
+    unsigned interval;
+    unsigned long long n_cp;            // ceil(n / interval): the stream's share of `checkpoints`
+    unsigned* step;                     // [win_bits]
+    unsigned* exit_of;                  // [win_bits]
+    uint16_t* count;                    // [win_bits] codes on the path to the exit (<= seg_bits)
+    unsigned* sup_exit;                 // [n_supers * seg_bits]: from the bits of a super-segment's first segment, over its segments
+    unsigned* sup_count;                // [n_supers * seg_bits]
+    unsigned* sup_entry;                // [n_supers] the chain's entry (kScanNoEntry: it jumped no such super-segment whole)
+    unsigned long long* sup_ord;        // [n_supers]
+    unsigned* seg_entry;                // [n_segs] the chain's entry into each segment (kScanNoEntry: none)
+    unsigned long long* seg_ord;        // [n_segs] the ordinal of the code at that entry
+    unsigned long long* checkpoints;    // [n_cp] out: the container bit of code j * interval
+    ScanResult* result;                 // out
+};
+// step table, segment maps, super-segment maps, chain, emit: five launches on `stream`.  hipError_t as int
+int launch_scan_window(const ScanArgs& a, void* stream);
 
 // ---- device-side entropy stage (mp_entropy.hip): everything that touches every symbol of the 1 + 6K streams ----
 constexpr int kEntBlock = 4096;         // symbols per scan block

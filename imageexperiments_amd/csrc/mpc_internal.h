@@ -99,6 +99,10 @@ Tuning read_tuning();
 
 double trace_ms();                      // milliseconds since the first call (MPC_TRACE)
 
+// mpc_container_index_device with the scan's sizes given (0 = the defaults): what it and mpc_debug_container_index_device call
+mpc_status container_index_on_device(mpc_context* c, const uint8_t* bytes, size_t nbytes, int interval, unsigned flags, int segment_bits,
+                                     int window_bits, uint8_t** index, size_t* index_bytes, int* route);
+
 // A grow-only device, pinned or mapped pinned buffer.  Growing frees the old buffer after a device synchronisation (the device
 // may still read it): free in steady state, where nothing grows.
 struct GrowBuffer {

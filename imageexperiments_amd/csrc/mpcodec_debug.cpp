@@ -1,7 +1,9 @@
 // mpcodec_debug.cpp -- product: the mpc_debug_* entry points and mpc_filter_tiles (include/mpcodec.h, "test entry points").
 // They exist for the tests of the pursuit screen's tables (tests/test_screen_cases.py, tests/test_gpu_screen_tables.py): the
 // resident Gram table, the uploaded split-bf16 filter tiles and the bound of the MFMA approximations decide nothing by
-// themselves, so no record can show that they are right.  Nothing here is on a product path; every entry validates its arguments
+// themselves, so no record can show that they are right; and mpc_debug_container_index_device, the device scan of the seek index
+// with its segment and window sizes given, so that a test can make chains cross windows on a small container
+// (tests/test_gpu_index_scan.py).  Nothing here is on a product path; every entry validates its arguments
 // before it touches memory.
 #include "../../include/mpcodec.h"
 #include "mpc_internal.h"
@@ -80,6 +82,11 @@ mpc_status mpc_filter_tiles(const double* rows, int nrows, int tiles, int k_orde
         if (shadow && nrows > 0) std::memcpy(shadow, sh.data(), static_cast<size_t>(nrows));
         return MPC_OK;
     });
+}
+
+mpc_status mpc_debug_container_index_device(mpc_context* c, const uint8_t* bytes, size_t nbytes, int interval, int segment_bits, int window_bits,
+                                            uint8_t** index, size_t* index_bytes, int* route) {
+    return container_index_on_device(c, bytes, nbytes, interval, 0, segment_bits, window_bits, index, index_bytes, route);
 }
 
 mpc_status mpc_debug_screen_probe_device(mpc_context* c, int channel, int block, const double* d_vectors, int n, float* d_approx,

@@ -99,6 +99,9 @@ struct Sequence {
     const uint8_t* const* indexes = nullptr;    // optional, and optional per frame: the seek index of frame f
     const size_t* index_bytes = nullptr;
     int* routes = nullptr;                      // optional: per frame 0 = parsed on the device, 1 = the serial route
+    bool scan = false;                          // mpc_decode_images_scan*: no index comes with a frame; the device scan proposes one
+    uint8_t** out_indexes = nullptr;            // ... optional: the version-1 blob of every frame on route 0 (malloc), else NULL
+    size_t* out_index_bytes = nullptr;
     const mpc_rect* rects = nullptr;            // mpc_decode_regions_indexed*: the rectangle wanted of frame f
     bool parse_all = false;                     // ... MPC_REGION_PARSE_ALL
     const mpc_view* views = nullptr;            // mpc_decode_views_indexed*: steps and reduction of frame f; rects[f] is then its rectangle, resolved
@@ -227,6 +230,34 @@ struct ParsePlan {
     std::vector<unsigned long long> aux, aux_off;
 };
 
+// A Huffman stream's tables as the parse and scan kernels read them, appended to the uploads: the window table (symbol | length << 16
+// | pseudo-EOF), and for codes longer than the window the per-length rows and the entry -> symbol table
+void append_code_tables(const mpc::HuffmanCodebook& cb, mpc::ParseStream& ps, std::vector<uint32_t>& luts, std::vector<uint32_t>& lens,
+                        std::vector<uint16_t>& tables) {
+    constexpr size_t kLut = size_t(1) << mpc::kParseLutBits;
+    const uint32_t eof = static_cast<uint32_t>(cb.total) - 1u;
+    ps.total = cb.total;
+    ps.max_length = static_cast<unsigned>(cb.max_length);
+    ps.lut_off = static_cast<unsigned>(luts.size());
+    luts.resize(luts.size() + kLut);
+    uint32_t* lut = luts.data() + ps.lut_off;
+    for (size_t k = 0; k < kLut; ++k) {                         // (entry << 5) | length -> symbol | length << 16 | pseudo-EOF
+        const uint32_t hit = cb.lut[k];
+        if (hit) lut[k] = cb.table[hit >> 5] | ((hit & 31u) << 16) | ((hit >> 5) == eof ? mpc::kParseLutEof : 0u);
+    }
+    if (cb.max_length <= mpc::kParseLutBits) return;            // the window resolves every code: no per-length test, no entry table
+    ps.len_off = static_cast<unsigned>(lens.size());
+    lens.resize(lens.size() + 3 * 33, 0);
+    for (int l = 1; l <= cb.max_length; ++l) {
+        uint32_t* row = lens.data() + ps.len_off + 3 * l;
+        row[0] = cb.counts[l - 1];
+        row[1] = cb.first_code[l];
+        row[2] = cb.first_index[l];
+    }
+    ps.table_off = static_cast<unsigned>(tables.size());
+    tables.insert(tables.end(), cb.table.begin(), cb.table.end());
+}
+
 // false = the index is not used (the serial route decides what becomes of the frame)
 // keep_steps (a view; 0 or >= K: every step): a stream of a step at or above it is EMPTY in every table the kernels bound themselves
 // by -- no coded symbols, no chunks, no groups, no expanded symbols, no aux entries -- so it is neither parsed, unpacked nor
@@ -250,7 +281,6 @@ bool plan_parse(const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_
     p.n_counts = 3 * p.ip.tiles;
     p.streams.assign(x.streams.size() + 1, mpc::ParseStream{});
     unsigned long long groups = 0, checkpoints = 0;
-    constexpr size_t kLut = size_t(1) << mpc::kParseLutBits;
     for (size_t j = 0; j < x.streams.size(); ++j) {
         const mpc::IndexStream& is = x.streams[j];
         const mpc::StreamWrapper& w = p.ip.wrappers[j];
@@ -271,28 +301,7 @@ bool plan_parse(const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_
         groups += (chunks + mpc::kParseGroup - 1) / mpc::kParseGroup;
         if (groups > 0x7FFFFFFFull) return false;
         if (w.mode != 0 || ps.n_chunks == 0) continue;
-        const mpc::HuffmanCodebook& cb = w.cb;
-        const uint32_t eof = static_cast<uint32_t>(cb.total) - 1u;
-        ps.total = cb.total;
-        ps.max_length = static_cast<unsigned>(cb.max_length);
-        ps.lut_off = static_cast<unsigned>(p.luts.size());
-        p.luts.resize(p.luts.size() + kLut);
-        uint32_t* lut = p.luts.data() + ps.lut_off;
-        for (size_t k = 0; k < kLut; ++k) {                         // (entry << 5) | length -> symbol | length << 16 | pseudo-EOF
-            const uint32_t hit = cb.lut[k];
-            if (hit) lut[k] = cb.table[hit >> 5] | ((hit & 31u) << 16) | ((hit >> 5) == eof ? mpc::kParseLutEof : 0u);
-        }
-        if (cb.max_length <= mpc::kParseLutBits) continue;          // the window resolves every code: no per-length test, no entry table
-        ps.len_off = static_cast<unsigned>(p.lens.size());
-        p.lens.resize(p.lens.size() + 3 * 33, 0);
-        for (int l = 1; l <= cb.max_length; ++l) {
-            uint32_t* row = p.lens.data() + ps.len_off + 3 * l;
-            row[0] = cb.counts[l - 1];
-            row[1] = cb.first_code[l];
-            row[2] = cb.first_index[l];
-        }
-        ps.table_off = static_cast<unsigned>(p.tables.size());
-        p.tables.insert(p.tables.end(), cb.table.begin(), cb.table.end());
+        append_code_tables(w.cb, ps, p.luts, p.lens, p.tables);
     }
     p.expanded = x.version == 2;
     if (p.expanded) {
@@ -320,8 +329,10 @@ bool plan_parse(const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_
 // deferred: the parse kernels are the caller's to launch as well, from *deferred (a frame of which a window is wanted)
 // with_aux: the aux entries of a version-2 index go up behind everything else (j.d_aux, j.d_aux_off); without it the upload is
 // what it is for a version-1 index
+// words_resident: the scan route has put this container at the head of the slot's device buffer (DeviceStreamScanner::begin, the
+// same place and padding); unless the buffer has to grow now, the container is not uploaded a second time
 mpc_status upload_and_parse(DecodeSlot& slot, UnpackJob& j, const ParsePlan& pp, const uint8_t* bytes, size_t nbytes,
-                            mpc::ParseArgs* deferred = nullptr, bool with_aux = false) {
+                            mpc::ParseArgs* deferred = nullptr, bool with_aux = false, bool words_resident = false) {
     const UnpackPlan& plan = *j.plan;
     constexpr size_t kHead = 256;
     const size_t padded = ((nbytes + 3) & ~static_cast<size_t>(3)) + 16;      // a lane's window reads up to 12 bytes behind the last bit
@@ -363,11 +374,13 @@ mpc_status upload_and_parse(DecodeSlot& slot, UnpackJob& j, const ParsePlan& pp,
     const size_t behind_at = device_layout(nullptr);
     if (const mpc_status gs = slot.pinned.reserve(kHead + std::max(upload_bytes, Carve::up(j.result_bytes)), "pinned decode staging"); gs != MPC_OK)
         return gs;
-    if (const mpc_status gs = slot.dev.reserve(behind_at + j.behind_bytes, "device decode staging"); gs != MPC_OK) return gs;
+    bool dev_grown = false;
+    if (const mpc_status gs = slot.dev.reserve(behind_at + j.behind_bytes, "device decode staging", &dev_grown); gs != MPC_OK) return gs;
+    const bool keep_words = words_resident && !dev_grown;
     j.h_flags = reinterpret_cast<int*>(slot.pinned.data());
     j.h_result = slot.pinned.data() + kHead;
     upload_layout(j.h_result);
-    const size_t piece = size_t(1) << 20, pieces = (nbytes + piece - 1) / piece;
+    const size_t piece = size_t(1) << 20, pieces = keep_words ? 0 : (nbytes + piece - 1) / piece;
     const auto stage = [&](int job) {
         const size_t lo = piece * static_cast<size_t>(job), hi = std::min(nbytes, lo + piece);
         std::memcpy(words + lo, bytes + lo, hi - lo);
@@ -375,7 +388,7 @@ mpc_status upload_and_parse(DecodeSlot& slot, UnpackJob& j, const ParsePlan& pp,
     if (j.pooled && pieces > 1) mpc::parallel_jobs(static_cast<int>(pieces), stage);
     else
         for (size_t job = 0; job < pieces; ++job) stage(static_cast<int>(job));
-    std::memset(words + nbytes, 0, padded - nbytes);
+    if (!keep_words) std::memset(words + nbytes, 0, padded - nbytes);
     size_t at = 0;
     for (const mpc::IndexStream& is : pp.ip.index.streams) {
         if (!is.checkpoints.empty()) std::memcpy(checkpoints + at, is.checkpoints.data(), sizeof(unsigned long long) * is.checkpoints.size());
@@ -419,7 +432,8 @@ mpc_status upload_and_parse(DecodeSlot& slot, UnpackJob& j, const ParsePlan& pp,
     hipStream_t st = slot.stream;
     if (j.trace) HIP_TRY(hipEventRecord(slot.stamp[0], st));
     HIP_TRY(hipMemsetAsync(j.ua.error, 0, 3 * sizeof(int), st));
-    HIP_TRY(hipMemcpyAsync(dbase, j.h_result, upload_bytes, hipMemcpyHostToDevice, st));
+    const size_t skip = keep_words ? Carve::up(padded) : 0;          // the container's own piece of the layout
+    HIP_TRY(hipMemcpyAsync(dbase + skip, j.h_result + skip, upload_bytes - skip, hipMemcpyHostToDevice, st));
     if (j.trace) HIP_TRY(hipEventRecord(slot.stamp[1], st));
     if (deferred) {
         *deferred = pa;
@@ -427,6 +441,197 @@ mpc_status upload_and_parse(DecodeSlot& slot, UnpackJob& j, const ParsePlan& pp,
     }
     if (const int e = mpc::launch_parse(pa, st); e != 0) return launch_failed(e);
     if (j.trace) HIP_TRY(hipEventRecord(slot.stamp[5], st));
+    return MPC_OK;
+}
+
+// ---- the scan route: the seek index's checkpoints found on the device (mp_scan.hip), for a container that comes without an index ----
+// mpc::HostStreamScanner's counterpart on a decode slot.  begin() puts the container where upload_and_parse puts it -- at the head of
+// the slot's device buffer, through the head of its pinned buffer, zero-padded the same -- so a decode that follows on the same
+// slot need not upload it again; behind it the scratch of one window (grow-only, with the slot: 10 bytes per window bit and the
+// super-segment maps) and the stream's checkpoints.  scan() hands over to the device once per window and reads 24 bytes back.
+struct DeviceStreamScanner : mpc::StreamScanner {
+    DecodeSlot& slot;
+    const uint8_t* bytes;
+    size_t nbytes;
+    uint32_t segment_bits, window_bits;
+    bool trace;
+    mpc_status status = MPC_OK;                 // a HIP failure inside scan(): the caller's status, not a give-up
+    int windows = 0, streams = 0;
+    float device_ms = 0.f;
+    size_t padded = 0;
+    mpc::ScanArgs base{};                       // the pointers, and what does not change from window to window
+    uint32_t* h_luts = nullptr;                 // pinned: the stream's tables on their way up
+    uint32_t* h_lens = nullptr;
+    uint16_t* h_tables = nullptr;
+    mpc::ScanResult* h_result = nullptr;
+    unsigned long long* h_cps = nullptr;
+    uint32_t *d_luts = nullptr, *d_lens = nullptr;
+    uint16_t* d_tables = nullptr;
+    size_t cp_capacity = 0;
+
+    DeviceStreamScanner(DecodeSlot& s, const uint8_t* b, size_t n, uint32_t segment, uint32_t window, bool tr)
+        : slot(s), bytes(b), nbytes(n), segment_bits(segment), window_bits(window), trace(tr) {}
+
+    static size_t padded_size(size_t nbytes) { return ((nbytes + 3) & ~static_cast<size_t>(3)) + 16; }
+
+    mpc_status begin(uint32_t interval, bool pooled) {
+        constexpr size_t kHead = 256, kLut = size_t(1) << mpc::kParseLutBits;
+        const uint64_t total = 8 * static_cast<uint64_t>(nbytes);
+        padded = padded_size(nbytes);
+        const size_t win = static_cast<size_t>(std::min<uint64_t>(window_bits, std::max<uint64_t>(total, 1)));
+        const size_t n_segs = (win + segment_bits - 1) / segment_bits, n_supers = (n_segs + mpc::kScanSuper - 1) / mpc::kScanSuper;
+        cp_capacity = static_cast<size_t>(total / interval) + 2;                  // a stream's codes take a bit each at least
+        uint8_t* words;
+        auto layout = [&](char* b, bool device) {
+            Carve cv{b};
+            words = cv.take<uint8_t>(padded);
+            uint32_t* luts = cv.take<uint32_t>(kLut);
+            uint32_t* lens = cv.take<uint32_t>(3 * 33);
+            uint16_t* tables = cv.take<uint16_t>(65536);
+            unsigned long long* cps = cv.take<unsigned long long>(cp_capacity);
+            if (!device) {
+                h_luts = luts; h_lens = lens; h_tables = tables; h_cps = cps;
+                return cv.at;
+            }
+            d_luts = luts; d_lens = lens; d_tables = tables;
+            base.checkpoints = cps;
+            base.step = cv.take<unsigned>(win);
+            base.exit_of = cv.take<unsigned>(win);
+            base.count = cv.take<uint16_t>(win);
+            base.sup_exit = cv.take<unsigned>(n_supers * segment_bits);
+            base.sup_count = cv.take<unsigned>(n_supers * segment_bits);
+            base.sup_entry = cv.take<unsigned>(n_supers);
+            base.sup_ord = cv.take<unsigned long long>(n_supers);
+            base.seg_entry = cv.take<unsigned>(n_segs);
+            base.seg_ord = cv.take<unsigned long long>(n_segs);
+            base.result = cv.take<mpc::ScanResult>(1);
+            return cv.at;
+        };
+        if (const mpc_status gs = slot.pinned.reserve(kHead + layout(nullptr, false), "pinned decode staging"); gs != MPC_OK) return gs;
+        if (const mpc_status gs = slot.dev.reserve(layout(nullptr, true), "device decode staging"); gs != MPC_OK) return gs;
+        h_result = reinterpret_cast<mpc::ScanResult*>(slot.pinned.data());
+        layout(slot.pinned.data() + kHead, false);
+        uint8_t* h_words = words;
+        layout(slot.dev.data(), true);
+        const size_t piece = size_t(1) << 20, pieces = (nbytes + piece - 1) / piece;
+        const auto stage = [&](int job) {
+            const size_t lo = piece * static_cast<size_t>(job), hi = std::min(nbytes, lo + piece);
+            std::memcpy(h_words + lo, bytes + lo, hi - lo);
+        };
+        if (pooled && pieces > 1) mpc::parallel_jobs(static_cast<int>(pieces), stage);
+        else
+            for (size_t job = 0; job < pieces; ++job) stage(static_cast<int>(job));
+        std::memset(h_words + nbytes, 0, padded - nbytes);
+        HIP_TRY(hipMemcpyAsync(words, h_words, padded, hipMemcpyHostToDevice, slot.stream));
+        base.tables.words = reinterpret_cast<const uint32_t*>(words);
+        base.tables.luts = d_luts;
+        base.tables.lens = d_lens;
+        base.tables.tables = d_tables;
+        base.total_bits = total;
+        base.seg_bits = segment_bits;
+        base.interval = interval;
+        return MPC_OK;
+    }
+
+    bool scan(const mpc::StreamWrapper& w, uint64_t b0, uint64_t n, uint32_t interval, std::vector<uint64_t>& cps, uint64_t* end_bit) override {
+        status = guarded([&]() -> mpc_status { return scan_stream(w, b0, n, interval, cps, end_bit); });
+        return status == MPC_OK && given_up == false;
+    }
+
+    bool given_up = false;
+    mpc_status scan_stream(const mpc::StreamWrapper& w, uint64_t b0, uint64_t n, uint32_t interval, std::vector<uint64_t>& cps, uint64_t* end_bit) {
+        given_up = true;
+        const bool golomb = w.mode == 1;
+        if (!golomb && w.cb.lut.empty()) return MPC_OK;             // codes longer than 32 bits: serial only
+        const uint64_t n_cp = (n + interval - 1) / interval;
+        if (n_cp > cp_capacity || interval != base.interval) return MPC_OK;
+        hipStream_t st = slot.stream;
+        mpc::ScanArgs a = base;
+        a.stream = mpc::ParseStream{};
+        a.stream.flags = golomb ? mpc::kParseGolomb : 0u;
+        a.stream.m = w.m;
+        if (!golomb) {                                              // the stream's tables up: the device reads them at offset 0
+            std::vector<uint32_t> luts, lens;
+            std::vector<uint16_t> tables;
+            append_code_tables(w.cb, a.stream, luts, lens, tables);
+            std::memcpy(h_luts, luts.data(), sizeof(uint32_t) * luts.size());
+            HIP_TRY(hipMemcpyAsync(d_luts, h_luts, sizeof(uint32_t) * luts.size(), hipMemcpyHostToDevice, st));
+            if (!lens.empty()) {
+                std::memcpy(h_lens, lens.data(), sizeof(uint32_t) * lens.size());
+                std::memcpy(h_tables, tables.data(), sizeof(uint16_t) * tables.size());
+                HIP_TRY(hipMemcpyAsync(d_lens, h_lens, sizeof(uint32_t) * lens.size(), hipMemcpyHostToDevice, st));
+                HIP_TRY(hipMemcpyAsync(d_tables, h_tables, sizeof(uint16_t) * tables.size(), hipMemcpyHostToDevice, st));
+            }
+        }
+        a.n = n;
+        a.n_cp = n_cp;
+        ++streams;
+        uint64_t pos = b0, ord = 0;
+        for (;;) {                                                  // every window moves pos on by its own length at least, or ends the stream
+            if (golomb && ord == n) break;
+            if (pos >= base.total_bits) return MPC_OK;
+            a.win_begin = pos;
+            a.ord0 = ord;
+            a.win_bits = static_cast<unsigned>(std::min<uint64_t>(window_bits, base.total_bits - pos));
+            a.n_segs = (a.win_bits + segment_bits - 1) / segment_bits;
+            a.n_supers = (a.n_segs + mpc::kScanSuper - 1) / mpc::kScanSuper;
+            h_result->state = 0;
+            if (trace) HIP_TRY(hipEventRecord(slot.stamp[0], st));
+            if (const int e = mpc::launch_scan_window(a, st); e != 0) return launch_failed(e);
+            if (trace) HIP_TRY(hipEventRecord(slot.stamp[1], st));
+            HIP_TRY(hipMemcpyAsync(h_result, a.result, sizeof(mpc::ScanResult), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipEventRecord(slot.done, st));
+            HIP_TRY(hipEventSynchronize(slot.done));
+            ++windows;
+            if (trace) {
+                float ms = 0.f;
+                (void)hipEventElapsedTime(&ms, slot.stamp[0], slot.stamp[1]);
+                device_ms += ms;
+            }
+            const mpc::ScanResult r = *h_result;
+            if (r.state == mpc::kScanEnded) {
+                if (r.ordinal != n) return MPC_OK;
+                pos = r.position;
+                break;
+            }
+            // the carry: strictly behind the window, or the scan would not end
+            if (r.state != mpc::kScanContinue || r.position < pos + a.win_bits || r.position > base.total_bits + mpc::kScanUnaryCap + 64) return MPC_OK;
+            pos = r.position;
+            ord = r.ordinal;
+        }
+        if (pos > base.total_bits) return MPC_OK;
+        cps.resize(static_cast<size_t>(n_cp));
+        if (n_cp) {
+            HIP_TRY(hipMemcpyAsync(h_cps, base.checkpoints, sizeof(unsigned long long) * n_cp, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipEventRecord(slot.done, st));
+            HIP_TRY(hipEventSynchronize(slot.done));
+            std::memcpy(cps.data(), h_cps, sizeof(unsigned long long) * n_cp);
+        }
+        *end_bit = pos;
+        given_up = false;
+        return MPC_OK;
+    }
+};
+
+// The proposal for one container on `slot`: *proposed = false: the scan gave up.  The blob is version 1 and nothing has verified it
+mpc_status scan_on_slot(DecodeSlot& slot, const uint8_t* bytes, size_t nbytes, uint32_t interval, uint32_t segment, uint32_t window,
+                        bool pooled, bool trace, std::vector<uint8_t>& blob, bool* proposed) {
+    *proposed = false;
+    if (interval == 0) interval = mpc::kIndexIntervalDefault;
+    int width, height, K, block_size;
+    if (nbytes == 0 || nbytes > (size_t(1) << 31) || !mpc::container_info(bytes, nbytes, &width, &height, &K, &block_size)) return MPC_OK;
+    const double t0 = trace_ms();
+    DeviceStreamScanner scanner(slot, bytes, nbytes, segment, window, trace);
+    if (const mpc_status bs = scanner.begin(interval, pooled); bs != MPC_OK) return bs;
+    *proposed = mpc::propose_container_index(bytes, nbytes, interval, scanner, blob);
+    if (scanner.status != MPC_OK) {
+        *proposed = false;
+        (void)hipStreamSynchronize(slot.stream);
+        return scanner.status;
+    }
+    if (trace)
+        std::fprintf(stderr, "[trace] scan: %s after %.2f ms on the host (%d streams, %d windows handed over; their kernels %.2f ms on the device)\n",
+                     *proposed ? "proposed" : "gave up", trace_ms() - t0, scanner.streams, scanner.windows, scanner.device_ms);
     return MPC_OK;
 }
 
@@ -488,7 +693,7 @@ struct FrameHead {
 // s: the serially parsed streams, or pp: the checked index (then *refused = true with MPC_OK says that the device's half of the
 // acceptance rule failed: nothing of the frame counts, the serial route starts over)
 mpc_status frame_on_slot(Sequence& q, int f, DecodeSlot& slot, const FrameHead& s, const UnpackPlan& plan, const mpc::CodedStreams* serial,
-                         const ParsePlan* pp, double stamps[3], bool* refused) {
+                         const ParsePlan* pp, double stamps[3], bool* refused, bool words_resident = false) {
     mpc_context* c = q.c;
     const bool trace = q.tuning.trace;
     const int K = s.K;
@@ -550,7 +755,7 @@ mpc_status frame_on_slot(Sequence& q, int f, DecodeSlot& slot, const FrameHead& 
     if (serial) {
         if (const mpc_status us = upload_and_unpack(slot, j); us != MPC_OK) return us;
     } else if (!windowed) {
-        if (const mpc_status us = upload_and_parse(slot, j, *pp, q.bytes[f], q.nbytes[f]); us != MPC_OK) return us;
+        if (const mpc_status us = upload_and_parse(slot, j, *pp, q.bytes[f], q.nbytes[f], nullptr, false, words_resident); us != MPC_OK) return us;
         if (const int e = mpc::launch_unpack(j.ua, st); e != 0) return launch_failed(e);
         if (trace) HIP_TRY(hipEventRecord(slot.stamp[2], st));
     } else {
@@ -715,11 +920,32 @@ void parse_worker(Sequence& q) {
         // The indexed route's share of the host: the index checked against the container, the code tables built.  It refuses nothing
         // itself: whatever it cannot take, the serial route decides.
         bool indexed = false;
-        mpc_status st = guarded([&]() -> mpc_status {
-            if (q.indexes && q.indexes[f] && !q.failed_before(f)) {
+        // The scan route: the frame takes its slot first (in frame order, as below), puts the container on it and has the device find
+        // the checkpoints; what it proposes is then this frame's index, checked like any other.  It refuses nothing either
+        const int slot_index = f % q.slots;
+        const auto take_slot = [&] {
+            std::unique_lock<std::mutex> hold(q.lock);
+            q.turn.wait(hold, [&] { return q.slot_uses[slot_index] == f / q.slots; });
+        };
+        std::vector<uint8_t> scanned;
+        bool proposed = false;
+        mpc_status st = MPC_OK;
+        if (q.scan) {
+            take_slot();
+            if (!q.failed_before(f))
+                st = guarded([&]() -> mpc_status {
+                    HIP_TRY(hipSetDevice(c->device));
+                    return scan_on_slot(*c->dec[slot_index], q.bytes[f], q.nbytes[f], 0, mpc::kScanSegmentDefault, mpc::kScanWindowDefault, q.n == 1,
+                                        q.tuning.trace, scanned, &proposed);
+                });
+        }
+        const uint8_t* const index = q.scan ? (proposed ? scanned.data() : nullptr) : q.indexes ? q.indexes[f] : nullptr;
+        const size_t index_size = q.scan ? scanned.size() : index ? q.index_bytes[f] : 0;
+        if (st == MPC_OK) st = guarded([&]() -> mpc_status {
+            if (index && !q.failed_before(f)) {
                 HIP_TRY(hipSetDevice(c->device));
                 const mpc::ContainerIndex& x = pp.ip.index;
-                indexed = plan_parse(q.bytes[f], q.nbytes[f], q.indexes[f], q.index_bytes[f], q.n == 1, pp,
+                indexed = plan_parse(q.bytes[f], q.nbytes[f], index, index_size, q.n == 1, pp,
                                      q.views && !q.parse_all ? q.views[f].steps : 0) &&
                           x.block_size == c->block_size &&
                           !(q.d_rgb && q.out_bytes(f, x.width, x.height) > q.capacity[f]);
@@ -736,18 +962,15 @@ void parse_worker(Sequence& q) {
         });
         host[1] = trace_ms();
         // The slot is taken in frame order whatever became of the parse: the frames behind count this slot's uses.
-        const int slot_index = f % q.slots;
-        {
-            std::unique_lock<std::mutex> hold(q.lock);
-            q.turn.wait(hold, [&] { return q.slot_uses[slot_index] == f / q.slots; });
-        }
+        if (!q.scan) take_slot();
         host[2] = trace_ms();
         bool ran = false;
         if (st == MPC_OK && !q.failed_before(f)) {
             DecodeSlot& slot = *c->dec[slot_index];
             bool refused = false, decoded = true;
             st = guarded([&]() -> mpc_status {
-                return frame_on_slot(q, f, slot, head, indexed ? pp.unpack : plan, indexed ? nullptr : &s, indexed ? &pp : nullptr, host + 3, &refused);
+                return frame_on_slot(q, f, slot, head, indexed ? pp.unpack : plan, indexed ? nullptr : &s, indexed ? &pp : nullptr, host + 3, &refused,
+                                     q.scan && proposed);
             });
             if (st == MPC_OK && refused) {                          // the serial route from the start, on the slot this frame holds
                 indexed = false;
@@ -761,6 +984,15 @@ void parse_worker(Sequence& q) {
             if (st != MPC_OK) (void)hipStreamSynchronize(slot.stream);             // nothing of this frame is left on the slot's stream
         }
         if (ran && q.routes) q.routes[f] = indexed ? 0 : 1;
+        if (ran && indexed && q.out_indexes) {                      // the device has accepted it: the serial builder's blob, for a cache
+            uint8_t* copy = static_cast<uint8_t*>(std::malloc(scanned.size()));
+            if (!copy) st = fail(MPC_ERR_ALLOC, "out of memory");
+            else {
+                std::memcpy(copy, scanned.data(), scanned.size());
+                q.out_indexes[f] = copy;
+                q.out_index_bytes[f] = scanned.size();
+            }
+        }
         if (ran && q.tuning.trace) trace_frame(f, slot_index, *c->dec[slot_index], host, indexed, indexed && q.rects);
         {
             std::lock_guard<std::mutex> hold(q.lock);
@@ -787,8 +1019,10 @@ mpc_status ensure_slots(mpc_context* c, int slots) {
 mpc_status decode_sequence(mpc_context* c, const uint8_t* const* bytes, const size_t* nbytes, int n_frames, uint8_t** rgb,
                            uint8_t* const* d_rgb, const size_t* capacity, int* width, int* height, bool single = false,
                            const uint8_t* const* indexes = nullptr, const size_t* index_bytes = nullptr, int* routes = nullptr,
-                           const mpc_rect* rects = nullptr, unsigned region_flags = 0, const mpc_view* views = nullptr) {
+                           const mpc_rect* rects = nullptr, unsigned region_flags = 0, const mpc_view* views = nullptr, bool scan = false,
+                           uint8_t** out_indexes = nullptr, size_t* out_index_bytes = nullptr) {
     if (indexes && !index_bytes) return fail(MPC_ERR_ARGUMENT, "null argument");
+    if (out_indexes && !out_index_bytes) return fail(MPC_ERR_ARGUMENT, "null argument");
     if (!c || !bytes || !nbytes || !width || !height || (!rgb && !d_rgb) || (d_rgb && !capacity)) return fail(MPC_ERR_ARGUMENT, "null argument");
     if (n_frames < 1) return fail(MPC_ERR_ARGUMENT, "n_frames must be at least 1");
     if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback");
@@ -835,6 +1069,13 @@ mpc_status decode_sequence(mpc_context* c, const uint8_t* const* bytes, const si
     q.rects = rects;
     q.parse_all = (region_flags & MPC_REGION_PARSE_ALL) != 0;
     q.views = views;
+    q.scan = scan;
+    q.out_indexes = out_indexes;
+    q.out_index_bytes = out_index_bytes;
+    if (out_indexes) {
+        std::fill(out_indexes, out_indexes + n_frames, nullptr);
+        std::fill(out_index_bytes, out_index_bytes + n_frames, 0);
+    }
     if (routes) std::fill(routes, routes + n_frames, 1);
     q.width = width;
     q.height = height;
@@ -851,6 +1092,12 @@ mpc_status decode_sequence(mpc_context* c, const uint8_t* const* bytes, const si
         for (int f = 0; f < n_frames; ++f) {
             std::free(rgb[f]);
             rgb[f] = nullptr;
+        }
+    if (out_indexes)
+        for (int f = 0; f < n_frames; ++f) {
+            std::free(out_indexes[f]);
+            out_indexes[f] = nullptr;
+            out_index_bytes[f] = 0;
         }
     if (q.single) return fail(q.failed_status, "%s", q.failed_text.c_str());
     return fail(q.failed_status, "frame %d: %s", q.failed_frame, q.failed_text.c_str());
@@ -904,6 +1151,24 @@ mpc_status mpc_decode_images_indexed_device(mpc_context* c, const uint8_t* const
     return guarded([&]() -> mpc_status {
         if (!d_rgb) return fail(MPC_ERR_ARGUMENT, "null argument");
         return decode_sequence(c, bytes, nbytes, n_frames, nullptr, d_rgb, capacity, width, height, false, indexes, index_bytes, routes);
+    });
+}
+
+mpc_status mpc_decode_images_scan(mpc_context* c, const uint8_t* const* bytes, const size_t* nbytes, int n_frames, uint8_t** rgb, int* width,
+                                  int* height, uint8_t** indexes, size_t* index_bytes, int* routes) {
+    return guarded([&]() -> mpc_status {
+        if (!rgb) return fail(MPC_ERR_ARGUMENT, "null argument");
+        return decode_sequence(c, bytes, nbytes, n_frames, rgb, nullptr, nullptr, width, height, false, nullptr, nullptr, routes, nullptr, 0, nullptr,
+                               true, indexes, index_bytes);
+    });
+}
+
+mpc_status mpc_decode_images_scan_device(mpc_context* c, const uint8_t* const* bytes, const size_t* nbytes, int n_frames, uint8_t* const* d_rgb,
+                                         const size_t* capacity, int* width, int* height, uint8_t** indexes, size_t* index_bytes, int* routes) {
+    return guarded([&]() -> mpc_status {
+        if (!d_rgb) return fail(MPC_ERR_ARGUMENT, "null argument");
+        return decode_sequence(c, bytes, nbytes, n_frames, nullptr, d_rgb, capacity, width, height, false, nullptr, nullptr, routes, nullptr, 0,
+                               nullptr, true, indexes, index_bytes);
     });
 }
 
@@ -1095,6 +1360,64 @@ mpc_status window_on_device(mpc_context* c, const uint8_t* bytes, size_t nbytes,
 }
 }  // namespace
 
+// mpc_container_index_device and its debug form: the device scan proposes, the device parse (the decoder's own upload-and-parse
+// step, on the bytes the scan has put on the slot) decides; whatever either refuses, the serial builder answers
+mpc_status container_index_on_device(mpc_context* c, const uint8_t* bytes, size_t nbytes, int interval, unsigned flags, int segment_bits,
+                                     int window_bits, uint8_t** index, size_t* index_bytes, int* route) {
+    return guarded([&]() -> mpc_status {
+        if (!c || !bytes || !index || !index_bytes || !route) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (flags & ~MPC_INDEX_EXPANDED) return fail(MPC_ERR_ARGUMENT, "flags 0x%x", flags);
+        if (interval != 0 && (interval < static_cast<int>(mpc::kIndexIntervalMin) || interval > static_cast<int>(mpc::kIndexIntervalMax)))
+            return fail(MPC_ERR_ARGUMENT, "interval %d: 0 or %u to %u", interval, mpc::kIndexIntervalMin, mpc::kIndexIntervalMax);
+        uint32_t segment = segment_bits < 0 ? 1u : static_cast<uint32_t>(segment_bits), window = window_bits < 0 ? 1u : static_cast<uint32_t>(window_bits);
+        if (!mpc::scan_sizes_ok(&segment, &window))
+            return fail(MPC_ERR_ARGUMENT, "segment of %d bits, window of %d: 0, or a segment of %u to %u bits and a window of whole segments up to %u bits",
+                        segment_bits, window_bits, mpc::kScanSegmentMin, mpc::kScanSegmentMax, mpc::kScanWindowMax);
+        if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback");
+        const bool expanded = (flags & MPC_INDEX_EXPANDED) != 0;
+        std::vector<uint8_t> blob;
+        const auto give = [&]() -> mpc_status {
+            uint8_t* p = static_cast<uint8_t*>(std::malloc(blob.empty() ? 1 : blob.size()));
+            if (!p) return fail(MPC_ERR_ALLOC, "out of memory");
+            if (!blob.empty()) std::memcpy(p, blob.data(), blob.size());
+            *index = p;
+            *index_bytes = blob.size();
+            return MPC_OK;
+        };
+        const auto serial = [&]() -> mpc_status {
+            *route = 1;
+            blob.clear();
+            if (!mpc::build_container_index(bytes, nbytes, static_cast<uint32_t>(interval), blob, expanded)) return fail(MPC_ERR_BITSTREAM, "Invalid input data");
+            return give();
+        };
+        std::lock_guard<std::recursive_mutex> one_host_call(c->host_calls);
+        HIP_TRY(hipSetDevice(c->device));
+        if (const mpc_status ss = ensure_slots(c, 1); ss != MPC_OK) return ss;
+        DecodeSlot& slot = *c->dec[0];
+        const bool trace = read_tuning().trace;
+        bool proposed = false;
+        if (const mpc_status ps = scan_on_slot(slot, bytes, nbytes, static_cast<uint32_t>(interval), segment, window, true, trace, blob, &proposed); ps != MPC_OK)
+            return ps;
+        if (!proposed) return serial();
+        ParsePlan pp;
+        if (!plan_parse(bytes, nbytes, blob.data(), blob.size(), true, pp)) return serial();
+        UnpackJob j;
+        j.plan = &pp.unpack;
+        j.K = pp.ip.index.K;
+        j.pooled = true;
+        if (const mpc_status us = upload_and_parse(slot, j, pp, bytes, nbytes, nullptr, false, true); us != MPC_OK) return us;
+        hipStream_t st = slot.stream;
+        HIP_TRY(hipMemcpyAsync(j.h_flags, j.ua.error, 3 * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipEventRecord(slot.done, st));
+        HIP_TRY(hipEventSynchronize(slot.done));
+        if (j.h_flags[2] != 0) return serial();
+        // accepted: the serial parser's path, so the serial builder's version-1 blob
+        if (!mpc::accept_proposed_index(bytes, nbytes, blob, expanded)) return serial();
+        *route = 0;
+        return give();
+    });
+}
+
 extern "C" {
 
 mpc_status mpc_parse_container_window_device(mpc_context* c, const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes,
@@ -1181,6 +1504,11 @@ mpc_status mpc_parse_container_device(mpc_context* c, const uint8_t* bytes, size
         *route = 0;
         return MPC_OK;
     });
+}
+
+mpc_status mpc_container_index_device(mpc_context* c, const uint8_t* bytes, size_t nbytes, int interval, unsigned flags, uint8_t** index,
+                                      size_t* index_bytes, int* route) {
+    return container_index_on_device(c, bytes, nbytes, interval, flags, 0, 0, index, index_bytes, route);
 }
 
 mpc_status mpc_unpack_symbol_streams_device(mpc_context* c, int K, const uint16_t* coded, const unsigned long long* coded_off,

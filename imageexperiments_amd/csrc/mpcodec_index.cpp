@@ -47,6 +47,24 @@ mpc_status mpc_container_index2(const uint8_t* bytes, size_t nbytes, int interva
     });
 }
 
+mpc_status mpc_container_index_scan(const uint8_t* bytes, size_t nbytes, int interval, unsigned flags, int segment_bits, int window_bits,
+                                    uint8_t** index, size_t* index_bytes, int* route) {
+    return guarded([&]() -> mpc_status {
+        if (!bytes || !index || !index_bytes || !route) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (flags & ~MPC_INDEX_EXPANDED) return fail(MPC_ERR_ARGUMENT, "flags 0x%x", flags);
+        if (interval != 0 && (interval < static_cast<int>(mpc::kIndexIntervalMin) || interval > static_cast<int>(mpc::kIndexIntervalMax)))
+            return fail(MPC_ERR_ARGUMENT, "interval %d: 0 or %u to %u", interval, mpc::kIndexIntervalMin, mpc::kIndexIntervalMax);
+        uint32_t segment = segment_bits < 0 ? 1u : static_cast<uint32_t>(segment_bits), window = window_bits < 0 ? 1u : static_cast<uint32_t>(window_bits);
+        if (!mpc::scan_sizes_ok(&segment, &window))
+            return fail(MPC_ERR_ARGUMENT, "segment of %d bits, window of %d: 0, or a segment of %u to %u bits and a window of whole segments up to %u bits",
+                        segment_bits, window_bits, mpc::kScanSegmentMin, mpc::kScanSegmentMax, mpc::kScanWindowMax);
+        std::vector<uint8_t> blob;
+        if (!mpc::scan_container_index(bytes, nbytes, static_cast<uint32_t>(interval), (flags & MPC_INDEX_EXPANDED) != 0, segment, window, blob, route))
+            return fail(MPC_ERR_BITSTREAM, "Invalid input data");
+        return give_blob(blob, index, index_bytes);
+    });
+}
+
 mpc_status mpc_index_extend(const uint8_t* bytes, size_t nbytes, const uint8_t* index_v1, size_t index_v1_bytes, uint8_t** index,
                             size_t* index_bytes) {
     return guarded([&]() -> mpc_status {

@@ -482,6 +482,41 @@ mpc_status mpc_index_extend(const uint8_t* bytes, size_t nbytes, const uint8_t* 
 int mpc_index_version(const uint8_t* index, size_t index_bytes);
 mpc_status mpc_index_aux(const uint8_t* index, size_t index_bytes, int stream, uint64_t* out, uint16_t* prev, uint8_t* state, uint16_t* dc,
                          size_t capacity, size_t* n_entries);
+/* The seek index without a serial parse of the container ("Seek index from a bit scan").  Which code begins at
+ * bit p of a stream and how long it is depends on the bits at p and the stream's table alone; evaluated at every bit of a window,
+ * the serial parse is a walk along p -> p + len(p) that composes segment by segment.  Per stream, in container order: a step table
+ * over a window of `window_bits` behind the stream's first code, a map per segment of `segment_bits` (from every bit the first code
+ * start at or behind the segment's end and the codes on the way), the chain of those maps from the first code, and a walk of every
+ * segment from its true entry that writes the checkpoints; a stream longer than a window continues in the next from the carried
+ * (position, ordinal).  The host reads each wrapper in between; the sizes of streams 1 ... 6K come from the lengths stream, decoded
+ * from its fresh checkpoints.
+ * mpc_container_index_scan: that on the host, with no context -- it defines what the device scan computes.  Status, error text and
+ * blob are mpc_container_index2's, byte for byte, for every input.  *route: 0 = the scan produced the blob; 1 = the scan gave up
+ * (a wrapper the reader refuses, a Huffman table deeper than 32 bits, a dead chain, a count or size the serial parser would not
+ * accept, a Golomb unary run of 65536 bits or more) and the serial builder produced the result or the refusal.  A proposed blob is
+ * reported on route 0 only once the acceptance rule above has passed it (then it is the serial parser's path), and the scan does
+ * not give up on a container whose serially built index mpc_parse_container_by_index uses.  segment_bits, window_bits: 0 = the
+ * library's defaults (256 and 2^22); else, for tests, a segment of 32 ... 32768 bits and a window of whole segments of at most
+ * 2^26 bits; anything else MPC_ERR_ARGUMENT.
+ * mpc_container_index_device: the same contract with the step table, the maps, the chain and the walk on the device (mp_scan.hip)
+ * and the acceptance by the device parse; route 1 = the host builder ran.
+ * mpc_debug_container_index_device: mpc_container_index_device (flags 0) with the sizes given, for tests.
+ * mpc_decode_images_scan[_device]: mpc_decode_images[_device] for frames that come without an index: per frame the device scan, then
+ * the indexed route with the proposed index.  Pixels, statuses and error texts are those of mpc_decode_images[_device].  routes:
+ * NULL, or per frame 0 = scanned and parsed on the device, 1 = the serial route (the scan gave up or the device refused the index).
+ * indexes: NULL, or per frame the version-1 blob of a frame on route 0 (mpc_free; a cache can keep it), NULL with size 0 for a
+ * frame on route 1; index_bytes goes with it. */
+mpc_status mpc_container_index_scan(const uint8_t* bytes, size_t nbytes, int interval, unsigned flags, int segment_bits, int window_bits,
+                                    uint8_t** index, size_t* index_bytes, int* route);
+mpc_status mpc_container_index_device(mpc_context* ctx, const uint8_t* bytes, size_t nbytes, int interval, unsigned flags, uint8_t** index,
+                                      size_t* index_bytes, int* route);
+mpc_status mpc_debug_container_index_device(mpc_context* ctx, const uint8_t* bytes, size_t nbytes, int interval, int segment_bits,
+                                            int window_bits, uint8_t** index, size_t* index_bytes, int* route);
+mpc_status mpc_decode_images_scan(mpc_context* ctx, const uint8_t* const* bytes, const size_t* nbytes, int n_frames, uint8_t** rgb,
+                                  int* width, int* height, uint8_t** indexes, size_t* index_bytes, int* routes);
+mpc_status mpc_decode_images_scan_device(mpc_context* ctx, const uint8_t* const* bytes, const size_t* nbytes, int n_frames,
+                                         uint8_t* const* d_rgb, const size_t* capacity, int* width, int* height, uint8_t** indexes,
+                                         size_t* index_bytes, int* routes);
 /* The indexed encoders with `flags`, in the way mpc_container_index2 extends mpc_container_index: the arguments of
  * mpc_encode_images_indexed[_device], mpc_code_symbol_streams_device_indexed and mpc_assemble_symbol_streams_by_plan_indexed with
  * `flags` behind `interval`.
