@@ -214,6 +214,11 @@ def _bind_bitstream(L):
     _vparse = [_u8p, C.c_size_t, _u8p, C.c_size_t, _vwp, C.c_uint, C.POINTER(_u16p), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
     L.mpc_truncate_container.argtypes = [_u8p, C.c_size_t, C.c_int, C.POINTER(_u8p), C.POINTER(C.c_size_t)]
     L.mpc_parse_container_view_by_index.argtypes = _vparse
+    L.mpc_transcode_container.argtypes = [_u8p, C.c_size_t, _vwp, C.POINTER(_u8p), C.POINTER(C.c_size_t)]
+    L.mpc_transcode_views_indexed.argtypes = [vp, C.POINTER(_u8p), C.POINTER(C.c_size_t), C.POINTER(_u8p), C.POINTER(C.c_size_t), _vwp, C.c_int,
+                                              C.c_uint, C.POINTER(_u8p), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
+    L.mpc_crop_records_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, _rp, C.c_int, vp, vp, vp]
+    L.mpc_crop_records_check.argtypes = [vp, vp]
     L.mpc_parse_container_view_device.argtypes = [vp] + _vparse
     L.mpc_decode_views_indexed.argtypes = [vp, C.POINTER(_u8p), C.POINTER(C.c_size_t), C.POINTER(_u8p), C.POINTER(C.c_size_t), _vwp, C.c_int,
                                            C.c_uint, C.POINTER(_u8p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -602,6 +607,20 @@ def truncate_container(blob, steps):
     buf = np.frombuffer(blob, np.uint8)
     out, n = _u8p(), C.c_size_t(0)
     _check(L.mpc_truncate_container(buf.ctypes.data_as(_u8p), buf.size, int(steps), C.byref(out), C.byref(n)))
+    return _take_bytes(L, out, n)
+
+
+def transcode_container(blob, view):
+    """mpc_transcode_container: view = (rect, steps, 0) of a container as a container -> bytes.  rect = (x, y, width, height) aligned
+    to the container's tiles (a ragged right or bottom edge only where it is the frame's own), None = the whole frame; steps 0 = all.
+    For an encoder's container the result is byte for byte the encode of the cropped pixels, truncated to `steps`; no pixels and no
+    pursuit are involved.  MpcError(MPC_ERR_ARGUMENT) for a rectangle that is empty, outside the frame or not aligned, steps < 0,
+    scale_log2 != 0; MpcError(MPC_ERR_BITSTREAM) for whatever read_compressed refuses and for a length above K."""
+    L = load_library()
+    buf = np.frombuffer(blob, np.uint8)
+    vw = _view(view)
+    out, n = _u8p(), C.c_size_t(0)
+    _check(L.mpc_transcode_container(buf.ctypes.data_as(_u8p), buf.size, C.byref(vw), C.byref(out), C.byref(n)))
     return _take_bytes(L, out, n)
 
 
@@ -1228,6 +1247,29 @@ class CompressionContext:
         _check(self.L.mpc_decode_views_indexed_device(self.h, ptrs, sizes, iptrs, isizes, vw, n, 1 if parse_all else 0, d_ptrs, caps, W, H,
                                                       routes))
         return [out[i].view(-1)[:3 * W[i] * H[i]].view(H[i], W[i], 3) for i in range(n)], list(routes)
+
+    def transcode_views(self, blobs, indexes, views, parse_all=False):
+        """mpc_transcode_views_indexed: transcode_container(blobs[f], views[f]) for every frame on the device -> (containers, routes):
+        bytes objects, routes[f] 0 = through the frame's seek index (only the rectangle's window of the streams of the kept steps
+        is parsed), 1 = the serial parse.  The container's K must be the context's.  parse_all: MPC_VIEW_PARSE_ALL."""
+        bufs, ptrs, sizes = self._containers(blobs)
+        n = len(bufs)
+        ibufs, iptrs, isizes = self._indexes(indexes, n)
+        vw = self._views(views, n)
+        outs, nout, routes = (_u8p * n)(), (C.c_size_t * n)(), (C.c_int * n)()
+        _check(self.L.mpc_transcode_views_indexed(self.h, ptrs, sizes, iptrs, isizes, vw, n, 1 if parse_all else 0, outs, nout, routes))
+        return [_take_bytes(self.L, outs[i], C.c_size_t(nout[i])) for i in range(n)], list(routes)
+
+    def crop_records_device(self, d_counts, d_choices, width, height, rect, steps, d_out_counts, d_out_choices, stream=0, check=True):
+        """mpc_crop_records_device: whole-frame records of a width x height frame in device memory -> the records of the tile-aligned
+        rectangle rect = (x, y, width, height) (None = the whole frame) as a frame of their own, counts cut to `steps` (0 = all), in
+        d_out_counts[tiles' * 3] (uint16) and d_out_choices[tiles' * 3 * K] (uint32).  check: mpc_crop_records_check behind it, which
+        waits for `stream` and raises MpcError(MPC_ERR_BITSTREAM) if a count above K was met."""
+        rc = MpcRect(*[int(v) for v in (rect or (0, 0, 0, 0))])
+        _check(self.L.mpc_crop_records_device(self.h, d_counts, d_choices, width, height, C.byref(rc), int(steps), d_out_counts, d_out_choices,
+                                              stream or None))
+        if check:
+            _check(self.L.mpc_crop_records_check(self.h, stream or None))
 
     def parse_container_view_device(self, blob, index, view, parse_all=False):
         """mpc_parse_container_view_device: parse_container_view_by_index with the device's lengths parse, lengths cut, ranks,

@@ -14,6 +14,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <functional>
+#include <string>
 #include <vector>
 
 namespace mpc {
@@ -273,6 +274,19 @@ int read_window_by_index(const uint8_t* bytes, size_t nbytes, const uint8_t* ind
 // written by the one host coder (write_compressed).  steps >= K: the parsed container coded again.  false = read_compressed
 // refuses the input.  steps >= 1 is the caller's to check
 bool truncate_container(const uint8_t* bytes, size_t nbytes, int steps, std::vector<uint8_t>& out);
+
+// ---- transcode: a view of a container as a container (include/mpcodec.h, "transcode"; DESIGN.md section 4, "Transcode") ----
+// The container of the rectangle (x, y, w, h) of the frame, cut to its first `steps` steps (0 or above K: every step), from the
+// source's symbols alone: tile (tx - tx0) * nty + (ty - ty0) of the new frame takes the first min(length, steps) records of tile
+// tx * tiles_y + ty; the streams are assembled in the new order and written by the one host coder (write_compressed), which
+// difference codes the step-0 coefficients from zero again and chooses packed-or-not and Huffman-or-Golomb again.  Header: w x h, the
+// source's K, block size and quantiser steps.  No dictionary is involved: a record outside its dynamic dictionary is carried over.
+// Returns 0, 1 = read_compressed refuses the input, 2 = a length above K, 3 = the rectangle is empty or not inside the frame.
+// That the rectangle is tile aligned (transcode_rect_error) is the caller's to check: only then is the result the encode of the crop
+int transcode_container(const uint8_t* bytes, size_t nbytes, int x, int y, int w, int h, int steps, std::vector<uint8_t>& out);
+// empty, or why (x, y, w, h) cannot be transcoded out of a frame of width x height in tiles of block_size: it is empty or not inside
+// the frame; x or y is no multiple of block_size; x + w (y + h) is neither a multiple of block_size nor the frame's width (height)
+std::string transcode_rect_error(int width, int height, int block_size, int x, int y, int w, int h);
 
 // The same index from what an encoder holds when it has just written the container, without parsing anything: the plans of
 // plan_stream, where each stream's codes begin, and the bit of every interval-th coded symbol as the code writer passed it.

@@ -4,6 +4,7 @@
 #include "host_bitstream.h"
 
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 
@@ -1317,6 +1318,63 @@ bool truncate_container(const uint8_t* bytes, size_t nbytes, int steps, std::vec
         }
     out = write_compressed(s);
     return true;
+}
+
+std::string transcode_rect_error(int width, int height, int block_size, int x, int y, int w, int h) {
+    char text[200];
+    TileWindow win;
+    if (!tile_window(width, height, block_size, x, y, w, h, win)) {
+        std::snprintf(text, sizeof text, "rectangle %dx%d at (%d, %d) is empty or not inside a frame of %dx%d", w, h, x, y, width, height);
+        return text;
+    }
+    // inside the frame: x + w <= width and y + h <= height, nothing overflows
+    const bool right = (x + w) % block_size == 0 || x + w == width, bottom = (y + h) % block_size == 0 || y + h == height;
+    if (x % block_size != 0 || y % block_size != 0 || !right || !bottom) {
+        std::snprintf(text, sizeof text, "rectangle %dx%d at (%d, %d) is not aligned to the %d-pixel tiles of a frame of %dx%d", w, h, x, y,
+                      block_size, width, height);
+        return text;
+    }
+    return std::string();
+}
+
+int transcode_container(const uint8_t* bytes, size_t nbytes, int x, int y, int w, int h, int steps, std::vector<uint8_t>& out) {
+    Streams s;
+    if (!read_compressed(bytes, nbytes, s)) return 1;
+    const int K = s.K, m = steps > 0 && steps < K ? steps : K;
+    for (uint16_t length : s.lengths)
+        if (length > K) return 2;
+    TileWindow win;
+    if (!tile_window(s.width, s.height, s.block_size, x, y, w, h, win)) return 3;
+    Streams cropped;
+    cropped.width = w;
+    cropped.height = h;
+    cropped.K = K;
+    cropped.block_size = s.block_size;
+    std::memcpy(cropped.quant, s.quant, sizeof(s.quant));
+    cropped.codes.assign(static_cast<size_t>(6 * K), {});
+    const size_t tiles = s.lengths.size() / 3, nty = static_cast<size_t>(win.ty1 - win.ty0);
+    cropped.lengths.reserve(3 * nty * static_cast<size_t>(win.tx1 - win.tx0));
+    // One pass in the source's tile order, which is the new frame's too (both column-major): every stream pair has a cursor, and a
+    // record moves over when its tile is in the grid and its step is kept.  read_compressed has held every stream to its size
+    std::vector<size_t> cursor(static_cast<size_t>(3 * K), 0);
+    for (size_t t = 0; t < tiles; ++t) {
+        const size_t tx = t / static_cast<size_t>(win.tiles_y), ty = t % static_cast<size_t>(win.tiles_y);
+        const bool inside = tx >= static_cast<size_t>(win.tx0) && tx < static_cast<size_t>(win.tx1) && ty >= static_cast<size_t>(win.ty0) &&
+                            ty < static_cast<size_t>(win.ty1);
+        for (int ch = 0; ch < 3; ++ch) {
+            const int length = s.lengths[3 * t + static_cast<size_t>(ch)];
+            if (inside) cropped.lengths.push_back(static_cast<uint16_t>(std::min(length, m)));
+            for (int i = 0; i < length; ++i) {
+                const size_t at = cursor[static_cast<size_t>(ch * K + i)]++;
+                if (!inside || i >= m) continue;
+                const size_t pair = static_cast<size_t>(2 * K * ch + 2 * i);
+                cropped.codes[pair].push_back(s.codes[pair][at]);
+                cropped.codes[pair + 1].push_back(s.codes[pair + 1][at]);
+            }
+        }
+    }
+    out = write_compressed(cropped);
+    return 0;
 }
 
 bool read_compressed(const uint8_t* bytes, size_t nbytes, Streams& s) {

@@ -273,6 +273,11 @@ int launch_stream_gather_window(const StreamArgs& a, uint32_t* choices, long lon
 // records of the tile rows [row_begin, row_begin + rows) in stripe order -> their places in the whole frame's records
 int launch_interleave_stripe(const uint16_t* part_counts, const uint32_t* part_choices, int tiles_x, int tiles_y, int row_begin, int rows,
                              int K, uint16_t* frame_counts, uint32_t* frame_choices, void* stream);
+// records of the tile grid [tx0, tx1) x [ty0, ty1) of a frame of tiles_x x tiles_y tiles -> the compact frame of that grid:
+// out_counts[t' * 3 + ch] = min(count, steps, K), out_choices[(t' * 3 + ch) * K + i] = the record for i below that, else 0, with
+// t' = (tx - tx0) * (ty1 - ty0) + (ty - ty0).  *error (the caller zeroes it) is set by a count above K in the grid.  steps >= 1
+int launch_crop_records(const uint16_t* counts, const uint32_t* choices, int tiles_x, int tiles_y, int tx0, int ty0, int tx1, int ty1, int K,
+                        int steps, uint16_t* out_counts, uint32_t* out_choices, int* error, void* stream);
 
 // ---- the decoder's per-symbol work in front of the gather (mp_unpack.hip): run-length expansion, DC sums ----
 constexpr int kUnpackBlock = 2048;      // coded symbols per workgroup

@@ -346,6 +346,52 @@ __global__ __launch_bounds__(256) void mp_interleave_stripe_kernel(const uint16_
     }
 }
 
+// The records of the tile grid [tx0, tx1) x [ty0, ty1) of a frame as the frame of that grid alone (a transcode: the container of a
+// rectangle from the source's records): tile (tx - tx0) * nty + (ty - ty0) takes the first min(count, steps) records of tile
+// tx * tiles_y + ty, the steps behind them zero.  A tile column's rows are contiguous on both sides, as for the stripes above, so a
+// thread per OUTPUT word reads and writes consecutive words across a wave whatever K is.  Every address comes from the grid: a
+// count above K is clamped to K where it is used and sets *error, and the host refuses the frame.
+__global__ __launch_bounds__(256) void mp_crop_records_kernel(const uint16_t* __restrict__ counts, const uint32_t* __restrict__ choices,
+                                                              int tiles_y, int tx0, int ty0, int ncols, int nty, int K, int steps,
+                                                              uint16_t* __restrict__ out_counts, uint32_t* __restrict__ out_choices,
+                                                              int* __restrict__ error)
+{
+    const int halves_per_col = nty * 3, words_per_col = halves_per_col * K;      // < 2^31 (the launcher)
+    const long long n_words = (long long)words_per_col * ncols, n_halves = (long long)halves_per_col * ncols;
+    for (long long o = (long long)blockIdx.x * 256 + threadIdx.x; o < n_words; o += (long long)gridDim.x * 256) {
+        const int col = (int)(o / words_per_col), w = (int)(o - (long long)col * words_per_col);
+        const int tc = w / K, i = w - tc * K;                             // tile-channel of the column's rows, step
+        const long long first = ((long long)(tx0 + col) * tiles_y + ty0) * 3;    // the column's first tile-channel in the source
+        int c = counts[first + tc];
+        if (c > K) c = K;
+        if (c > steps) c = steps;
+        out_choices[o] = i < c ? choices[first * K + w] : 0u;
+    }
+    for (long long o = (long long)blockIdx.x * 256 + threadIdx.x; o < n_halves; o += (long long)gridDim.x * 256) {
+        const int col = (int)(o / halves_per_col), tc = (int)(o - (long long)col * halves_per_col);
+        int c = counts[((long long)(tx0 + col) * tiles_y + ty0) * 3 + tc];
+        if (c > K) {
+            *error = 1;
+            c = K;
+        }
+        out_counts[o] = (uint16_t)(c < steps ? c : steps);
+    }
+}
+
+int launch_crop_records(const uint16_t* counts, const uint32_t* choices, int tiles_x, int tiles_y, int tx0, int ty0, int tx1, int ty1, int K,
+                        int steps, uint16_t* out_counts, uint32_t* out_choices, int* error, void* stream_)
+{
+    if (tx0 < 0 || ty0 < 0 || tx0 >= tx1 || ty0 >= ty1 || tx1 > tiles_x || ty1 > tiles_y || K < 1 || K > kMaxDeviceK || steps < 1)
+        return (int)hipErrorInvalidValue;
+    const int ncols = tx1 - tx0, nty = ty1 - ty0;
+    if ((long long)nty * 3 * K >= (1LL << 31)) return (int)hipErrorInvalidValue;
+    const long long n_words = (long long)nty * 3 * K * ncols;
+    const unsigned blocks = (unsigned)((n_words + 255) / 256 < 4096 ? (n_words + 255) / 256 : 4096);
+    hipLaunchKernelGGL(mp_crop_records_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream_), counts, choices, tiles_y, tx0, ty0,
+                       ncols, nty, K, steps < K ? steps : K, out_counts, out_choices, error);
+    return (int)hipGetLastError();
+}
+
 int launch_interleave_stripe(const uint16_t* part_counts, const uint32_t* part_choices, int tiles_x, int tiles_y, int row_begin, int rows,
                              int K, uint16_t* frame_counts, uint32_t* frame_choices, void* stream_)
 {

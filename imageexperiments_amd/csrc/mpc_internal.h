@@ -330,6 +330,7 @@ struct mpc_context {
     unsigned quant_next = 0;
     std::recursive_mutex host_calls;  // the host-buffer entry points share the staging buffers below
     int* d_flag = nullptr;            // mpc_decode_tiles_device: set when a record indexes outside its dictionary
+    int* d_crop_flag = nullptr;       // mpc_crop_records_device: set by a count above K, read by mpc_crop_records_check
     // grow-only staging for the host-buffer encode entry points (mpc_encode_tiles / mpc_encode_image(s)): allocating and freeing
     // them per call cost several times the encode itself.  The decoder stages in its slots' own buffers (DecodeSlot).
     GrowBuffer stage{GrowBuffer::kDevice};
@@ -401,6 +402,13 @@ inline mpc_rect view_rect(const mpc_view& v, int width, int height) {
 inline int view_extent(int extent, int scale_log2) { return (extent + (1 << scale_log2) - 1) >> scale_log2; }
 // the steps a view keeps of a container of K: 0 = all, above K acts as K
 inline int view_steps(int steps, int K) { return steps > 0 && steps < K ? steps : K; }
+
+// a transcode's view (include/mpcodec.h, "transcode"): nullptr, or what is wrong with the arguments that need no container
+inline const char* transcode_argument_error(const mpc_view& v) {
+    if (v.steps < 0) return "steps must not be negative";
+    if (v.scale_log2 != 0) return "scale_log2 must be 0: a transcode does not reduce";
+    return nullptr;
+}
 
 // ---- context and tile encode (mpcodec_context.cpp) ----
 mpc::DictDevice dict_device(const mpc_context* c);

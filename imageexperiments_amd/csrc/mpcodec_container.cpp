@@ -14,6 +14,8 @@
 #include <future>
 #include <utility>
 
+#include <string>
+
 #include "mpc_internal.h"
 
 mpc_status entropy_buffers(EntropySlot& e, size_t tiles, int K, EntropyBuffers* b, int with_index) {
@@ -838,6 +840,48 @@ mpc_status mpc_interleave_stripe_device(mpc_context* c, const uint16_t* d_part_c
                                                   tile_row_end - tile_row_begin, c->K, d_frame_counts, reinterpret_cast<uint32_t*>(d_frame_choices), stream);
     if (err != 0) return launch_failed(err);
     return MPC_OK;
+}
+
+mpc_status mpc_crop_records_device(mpc_context* c, const uint16_t* d_counts, const mpc_basis_choice* d_choices, int width, int height,
+                                   const mpc_rect* rect, int steps, uint16_t* d_out_counts, mpc_basis_choice* d_out_choices, void* stream) {
+    return guarded([&]() -> mpc_status {
+    if (!c || !d_counts || !d_choices || !rect || !d_out_counts || !d_out_choices) return fail(MPC_ERR_ARGUMENT, "null argument");
+    if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device");
+    if (steps < 0) return fail(MPC_ERR_ARGUMENT, "steps must not be negative");
+    if (width < 1 || height < 1) return fail(MPC_ERR_ARGUMENT, "bad geometry");
+    const mpc_rect r = rect->x == 0 && rect->y == 0 && rect->width == 0 && rect->height == 0 ? mpc_rect{0, 0, width, height} : *rect;
+    const std::string why = mpc::transcode_rect_error(width, height, c->block_size, r.x, r.y, r.width, r.height);
+    if (!why.empty()) return fail(MPC_ERR_ARGUMENT, "%s", why.c_str());
+    mpc::TileWindow win;
+    mpc::tile_window(width, height, c->block_size, r.x, r.y, r.width, r.height, win);
+    HIP_TRY(hipSetDevice(c->device));
+    if (!c->d_crop_flag) {
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_crop_flag), sizeof(int)));
+        HIP_TRY(hipMemset(c->d_crop_flag, 0, sizeof(int)));
+        HIP_TRY(hipDeviceSynchronize());
+    }
+    const int bs = c->block_size;
+    const int err = mpc::launch_crop_records(d_counts, reinterpret_cast<const uint32_t*>(d_choices), (width + bs - 1) / bs, win.tiles_y, win.tx0,
+                                             win.ty0, win.tx1, win.ty1, c->K, steps > 0 && steps < c->K ? steps : c->K, d_out_counts,
+                                             reinterpret_cast<uint32_t*>(d_out_choices), c->d_crop_flag, stream);
+    if (err != 0) return launch_failed(err);
+    return MPC_OK;
+    });
+}
+
+mpc_status mpc_crop_records_check(mpc_context* c, void* stream) {
+    return guarded([&]() -> mpc_status {
+    if (!c) return fail(MPC_ERR_ARGUMENT, "null context");
+    if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device");
+    if (!c->d_crop_flag) return MPC_OK;                             // nothing has been cropped yet
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int flag = 0;
+    HIP_TRY(hipMemcpyAsync(&flag, c->d_crop_flag, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemsetAsync(c->d_crop_flag, 0, sizeof(int), s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return flag ? fail(MPC_ERR_BITSTREAM, "Invalid bitstream") : MPC_OK;
+    });
 }
 
 mpc_status mpc_records_to_container_device(mpc_context* c, const uint16_t* d_counts, const mpc_basis_choice* d_choices, int width,

@@ -107,6 +107,10 @@ struct Sequence {
     const mpc_view* views = nullptr;            // mpc_decode_views_indexed*: steps and reduction of frame f; rects[f] is then its rectangle, resolved
     int* width = nullptr;
     int* height = nullptr;
+    // mpc_transcode_views_indexed: no pixels; behind the gather the crop kernel and the records-to-container chain on the job slot
+    // of the decode slot's number leave frame f's container here (malloc)
+    uint8_t** containers = nullptr;
+    size_t* container_bytes = nullptr;
     std::atomic<int> next{0};                   // frames are handed out in order
     std::mutex lock;
     std::condition_variable turn;
@@ -117,6 +121,7 @@ struct Sequence {
 
     // the bytes frame f's pixels take at the caller's, the frame being width x height
     size_t out_bytes(int f, int width, int height) const {
+        if (containers) return 0;
         if (views)
             return static_cast<size_t>(view_extent(rects[f].width, views[f].scale_log2)) *
                    static_cast<size_t>(view_extent(rects[f].height, views[f].scale_log2)) * 3;
@@ -689,6 +694,73 @@ struct FrameHead {
     const uint16_t (*quant)[32] = nullptr;
 };
 
+// A transcode's frame behind the gather, in place of the reconstruction: the crop kernel moves the rectangle's records (frame layout,
+// `counts` / `choices`) into the new frame's tile order, cut to `steps`, and the records-to-container chain (ContainerJob) codes them
+// on the job slot of this decode slot's number, on the slot's own stream.  The error words are read first: records the index route
+// is about to refuse, or a count above K, never enter the chain.  *refused as in frame_on_slot
+mpc_status transcode_on_slot(Sequence& q, int f, DecodeSlot& slot, UnpackJob& j, const uint16_t* counts, const uint32_t* choices, int width,
+                             int height, int K, const mpc::TileWindow& win, int steps, const double* quant, uint16_t* d_crop_counts,
+                             uint32_t* d_crop_choices, bool indexed, double stamps[3], bool* refused) {
+    mpc_context* c = q.c;
+    hipStream_t st = slot.stream;
+    const mpc_rect& rc = q.rects[f];
+    const int bs = c->block_size, tiles_x = (width + bs - 1) / bs;
+    // the reconstruction's error word is this route's "a count above K": the same verdict, "Invalid bitstream"
+    if (const int e = mpc::launch_crop_records(counts, choices, tiles_x, win.tiles_y, win.tx0, win.ty0, win.tx1, win.ty1, K, steps, d_crop_counts,
+                                               d_crop_choices, j.ua.error + 1, st);
+        e != 0)
+        return launch_failed(e);
+    if (q.tuning.trace) HIP_TRY(hipEventRecord(slot.stamp[3], st));
+    HIP_TRY(hipMemcpyAsync(j.h_flags, j.ua.error, 3 * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (q.tuning.trace) HIP_TRY(hipEventRecord(slot.stamp[4], st));
+    HIP_TRY(hipEventRecord(slot.done, st));
+    HIP_TRY(hipEventSynchronize(slot.done));
+    stamps[1] = trace_ms();
+    if (indexed && (j.h_flags[2] != 0 || j.h_flags[0] != 0)) {
+        *refused = true;
+        return MPC_OK;
+    }
+    if (j.h_flags[0] != 0) return fail(MPC_ERR_BITSTREAM, "Invalid input data");
+    if (j.h_flags[1] != 0) return fail(MPC_ERR_BITSTREAM, "Invalid bitstream");
+    JobSlot& js = *c->jobs[static_cast<size_t>(f % q.slots)];      // created, and found idle, by the call
+    const long long tiles = static_cast<long long>(win.tx1 - win.tx0) * (win.ty1 - win.ty0);
+    Carve measure;
+    mpc::StreamArgs measured{};
+    carve_stream_buffers(measure, tiles, K, true, &measured);
+    if (const mpc_status gs = js.dev.reserve(measure.at, "device staging"); gs != MPC_OK) return gs;
+    GrowBuffer host_stage(GrowBuffer::kPinned);                     // the host route's, should the frame take it: this frame's own
+    ContainerJob& job = js.job;
+    job.side = job.down = st;
+    job.spin = q.n == 1;
+    job.host_stage = &host_stage;
+    job.host_offset = 0;
+    job.index_interval = 0;
+    job.index_expanded = false;
+    struct Unhook {
+        ContainerJob& job;
+        ~Unhook() { job.host_stage = nullptr; }
+    } unhook{job};
+    EntropyBuffers eb;
+    if (!q.tuning.host_entropy)
+        if (const mpc_status es = entropy_buffers(js.ent, static_cast<size_t>(tiles), K, &eb); es != MPC_OK) return es;
+    HIP_TRY(hipStreamSynchronize(nullptr));                         // a slot carved for another geometry clears its tables on the null stream
+    if (const mpc_status bs_ = container_begin(job, c, q.tuning.host_entropy ? nullptr : &eb, q.tuning.triple_limit, js.dev.data(), d_crop_counts,
+                                               d_crop_choices, nullptr, nullptr, rc.width, rc.height, quant);
+        bs_ != MPC_OK)
+        return bs_;
+    if (const mpc_status ts = container_tables(job); ts != MPC_OK) return ts;
+    uint8_t* made = nullptr;
+    size_t made_bytes = 0;
+    if (const mpc_status cs = container_collect(job, &made, &made_bytes); cs != MPC_OK) return cs;
+    HIP_TRY(hipStreamSynchronize(st));                              // the job's buffers are the next frame's
+    q.containers[f] = made;
+    q.container_bytes[f] = made_bytes;
+    q.width[f] = rc.width;
+    q.height[f] = rc.height;
+    stamps[2] = trace_ms();
+    return MPC_OK;
+}
+
 // upload | (parse) | unpack | gather | reconstruct | (host form) pixels down, on the slot's stream; returns with the frame complete.
 // s: the serially parsed streams, or pp: the checked index (then *refused = true with MPC_OK says that the device's half of the
 // acceptance rule failed: nothing of the frame counts, the serial route starts over)
@@ -724,13 +796,19 @@ mpc_status frame_on_slot(Sequence& q, int f, DecodeSlot& slot, const FrameHead& 
     uint8_t *d_pixels = nullptr, *d_full = nullptr;
     mpc::WindowStream* d_window = nullptr;
     mpc::WindowSpan* d_span = nullptr;
+    uint16_t* d_crop_counts = nullptr;                              // a transcode: the rectangle's tiles as a frame of their own
+    uint32_t* d_crop_choices = nullptr;
+    const size_t crop_tc = q.containers ? 3 * static_cast<size_t>(win.tx1 - win.tx0) * static_cast<size_t>(win.ty1 - win.ty0) : 0;
     auto behind_layout = [&](char* base) {                          // behind the unpacked streams: records | the gather's scratch | pixels
         Carve cv{base};
         d_choices = cv.take<uint32_t>(n_tc * K);
         carve_stream_buffers(cv, static_cast<long long>(tiles), K, false, &sa);
         if (windowed) d_window = cv.take<mpc::WindowStream>(6 * static_cast<size_t>(K));
         if (cut) d_span = cv.take<mpc::WindowSpan>(6 * static_cast<size_t>(K));
-        if (crop) d_full = cv.take<uint8_t>(px);                    // the whole frame, of which the rectangle is copied out
+        if (q.containers) {
+            d_crop_counts = cv.take<uint16_t>(crop_tc + 2);
+            d_crop_choices = cv.take<uint32_t>(crop_tc * K);
+        } else if (crop) d_full = cv.take<uint8_t>(px);             // the whole frame, of which the rectangle is copied out
         else if (!q.d_rgb) d_pixels = cv.take<uint8_t>(out_px);
         return cv.at;
     };
@@ -778,6 +856,9 @@ mpc_status frame_on_slot(Sequence& q, int f, DecodeSlot& slot, const FrameHead& 
             return launch_failed(e);
     } else if (const int e = mpc::launch_stream_gather(sa, d_choices, st); e != 0)
         return launch_failed(e);
+    if (q.containers)
+        return transcode_on_slot(q, f, slot, j, counts, d_choices, s.width, s.height, K, win, dv.steps, quant, d_crop_counts, d_crop_choices,
+                                 pp != nullptr, stamps, refused);
     if (const mpc_status ds = decode_tiles_on_device(c, counts, d_choices, static_cast<const double*>(j.d_extra[1]), K, s.width, s.height,
                                                      crop ? d_full : d_pixels, j.ua.error + 1, st, windowed || vw ? &dw : nullptr,
                                                      vw ? &dv : nullptr);
@@ -878,8 +959,11 @@ void parse_worker(Sequence& q) {
             const bool block_size_differs = s.block_size != c->block_size;
             // a view of the first `steps` steps decodes the truncated container: its lengths are min(length, steps)
             const int steps = q.views && q.views[f].steps > 0 ? q.views[f].steps : INT_MAX;
-            const bool too_long = std::any_of(s.lengths.begin(), s.lengths.end(), [&](uint16_t length) { return std::min<int>(length, steps) > s.K; });
-            if (block_size_differs || too_long) {
+            // (a transcode refuses a length above K wherever it is cut to, as mpc_transcode_container does, and a K that is not the context's)
+            const int held = q.containers ? INT_MAX : steps;
+            const bool too_long = std::any_of(s.lengths.begin(), s.lengths.end(), [&](uint16_t length) { return std::min<int>(length, held) > s.K; });
+            const bool K_differs = q.containers && s.K != c->K;
+            if (block_size_differs || K_differs || too_long) {
                 // Refused here, before the device has expanded a stream.  A container whose streams do not expand either is
                 // invalid data first, whatever else is wrong with it: the host's expansion (the reference for what a decoder
                 // accepts) gives that verdict, on this path alone.
@@ -887,6 +971,7 @@ void parse_worker(Sequence& q) {
                 if (!mpc::read_compressed(q.bytes[f], q.nbytes[f], expanded)) return fail(MPC_ERR_BITSTREAM, "Invalid input data");
                 if (block_size_differs)
                     return fail(MPC_ERR_ARGUMENT, "stream block size %d, context block size %d", s.block_size, c->block_size);
+                if (K_differs) return fail(MPC_ERR_ARGUMENT, "container K %d, context K %d", s.K, c->K);
                 return fail(MPC_ERR_BITSTREAM, "Invalid bitstream");
             }
             if (q.d_rgb && !q.rects && q.out_bytes(f, s.width, s.height) > q.capacity[f])
@@ -947,7 +1032,7 @@ void parse_worker(Sequence& q) {
                 const mpc::ContainerIndex& x = pp.ip.index;
                 indexed = plan_parse(q.bytes[f], q.nbytes[f], index, index_size, q.n == 1, pp,
                                      q.views && !q.parse_all ? q.views[f].steps : 0) &&
-                          x.block_size == c->block_size &&
+                          x.block_size == c->block_size && !(q.containers && x.K != c->K) &&
                           !(q.d_rgb && q.out_bytes(f, x.width, x.height) > q.capacity[f]);
                 if (indexed) {
                     head.width = x.width;
@@ -1020,10 +1105,14 @@ mpc_status decode_sequence(mpc_context* c, const uint8_t* const* bytes, const si
                            uint8_t* const* d_rgb, const size_t* capacity, int* width, int* height, bool single = false,
                            const uint8_t* const* indexes = nullptr, const size_t* index_bytes = nullptr, int* routes = nullptr,
                            const mpc_rect* rects = nullptr, unsigned region_flags = 0, const mpc_view* views = nullptr, bool scan = false,
-                           uint8_t** out_indexes = nullptr, size_t* out_index_bytes = nullptr) {
+                           uint8_t** out_indexes = nullptr, size_t* out_index_bytes = nullptr, uint8_t** containers = nullptr,
+                           size_t* container_bytes = nullptr) {
+    // containers (with views and their rectangles): a transcode; no pixels in either form
     if (indexes && !index_bytes) return fail(MPC_ERR_ARGUMENT, "null argument");
+    if (containers && (!container_bytes || !views || rgb || d_rgb)) return fail(MPC_ERR_ARGUMENT, "null argument");
     if (out_indexes && !out_index_bytes) return fail(MPC_ERR_ARGUMENT, "null argument");
-    if (!c || !bytes || !nbytes || !width || !height || (!rgb && !d_rgb) || (d_rgb && !capacity)) return fail(MPC_ERR_ARGUMENT, "null argument");
+    if (!c || !bytes || !nbytes || !width || !height || (!rgb && !d_rgb && !containers) || (d_rgb && !capacity))
+        return fail(MPC_ERR_ARGUMENT, "null argument");
     if (n_frames < 1) return fail(MPC_ERR_ARGUMENT, "n_frames must be at least 1");
     if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback");
     for (int f = 0; f < n_frames; ++f)
@@ -1080,6 +1169,22 @@ mpc_status decode_sequence(mpc_context* c, const uint8_t* const* bytes, const si
     q.width = width;
     q.height = height;
     if (const mpc_status ss = ensure_slots(c, q.slots); ss != MPC_OK) return ss;
+    if (containers) {
+        // frame f codes its container on job slot f % slots, its own for as long as it holds the decode slot of that number
+        static_assert(mpc_context::kSeqSlots >= mpc_context::kDecodeSlots, "a container job slot per decode slot");
+        for (int k = 0; k < mpc_context::kSeqSlots; ++k)
+            if (c->jobs[k] && c->jobs[k]->stage != 0) return fail(MPC_ERR_ARGUMENT, "container job slot %d is busy", k);
+        for (int k = 0; k < q.slots; ++k) {
+            if (!c->jobs[k]) c->jobs[k] = std::make_unique<JobSlot>();
+            ContainerJob& job = c->jobs[k]->job;
+            if (!job.phase1) {
+                HIP_TRY(hipEventCreateWithFlags(&job.phase1, hipEventDisableTiming | hipEventBlockingSync));
+                HIP_TRY(hipEventCreateWithFlags(&job.done, hipEventDisableTiming | hipEventBlockingSync));
+            }
+        }
+        q.containers = containers;
+        q.container_bytes = container_bytes;
+    }
     if (rgb) std::fill(rgb, rgb + n_frames, nullptr);
     const int threads = std::min(n_frames, mpc::host_thread_count());
     std::vector<std::thread> workers;
@@ -1098,6 +1203,12 @@ mpc_status decode_sequence(mpc_context* c, const uint8_t* const* bytes, const si
             std::free(out_indexes[f]);
             out_indexes[f] = nullptr;
             out_index_bytes[f] = 0;
+        }
+    if (containers)
+        for (int f = 0; f < n_frames; ++f) {
+            std::free(containers[f]);
+            containers[f] = nullptr;
+            container_bytes[f] = 0;
         }
     if (q.single) return fail(q.failed_status, "%s", q.failed_text.c_str());
     return fail(q.failed_status, "frame %d: %s", q.failed_frame, q.failed_text.c_str());
@@ -1233,6 +1344,39 @@ mpc_status mpc_decode_views_indexed_device(mpc_context* c, const uint8_t* const*
     return guarded([&]() -> mpc_status {
         if (!d_rgb) return fail(MPC_ERR_ARGUMENT, "null argument");
         return decode_views(c, bytes, nbytes, indexes, index_bytes, views, n_frames, flags, nullptr, d_rgb, capacity, width, height, routes);
+    });
+}
+
+// A transcode (include/mpcodec.h, "transcode"): the view decoder's sequence up to the gather, then the crop kernel and the
+// records-to-container chain instead of the reconstruction (transcode_on_slot).  Arguments that need no device are checked first,
+// "frame N: ...", with mpc_transcode_container's own texts
+mpc_status mpc_transcode_views_indexed(mpc_context* c, const uint8_t* const* bytes, const size_t* nbytes, const uint8_t* const* indexes,
+                                       const size_t* index_bytes, const mpc_view* views, int n_frames, unsigned flags, uint8_t** out,
+                                       size_t* out_bytes, int* routes) {
+    return guarded([&]() -> mpc_status {
+        if (!c || !views || !bytes || !nbytes || !out || !out_bytes) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (flags & ~MPC_VIEW_PARSE_ALL) return fail(MPC_ERR_ARGUMENT, "flags 0x%x", flags);
+        if (n_frames < 1) return fail(MPC_ERR_ARGUMENT, "n_frames must be at least 1");
+        std::fill(out, out + n_frames, nullptr);
+        std::fill(out_bytes, out_bytes + n_frames, 0);
+        if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback");
+        std::vector<mpc_rect> rects(static_cast<size_t>(n_frames));
+        for (int f = 0; f < n_frames; ++f) {
+            if (!bytes[f]) return fail(MPC_ERR_ARGUMENT, "frame %d: null argument", f);
+            if (const char* why = transcode_argument_error(views[f])) return fail(MPC_ERR_ARGUMENT, "frame %d: %s", f, why);
+            int w, h, K, bs;
+            if (!mpc::container_info(bytes[f], nbytes[f], &w, &h, &K, &bs)) {           // fails in its turn, as in every other call
+                rects[static_cast<size_t>(f)] = mpc_rect{0, 0, 1, 1};
+                continue;
+            }
+            const mpc_rect r = view_rect(views[f], w, h);
+            const std::string why = mpc::transcode_rect_error(w, h, bs, r.x, r.y, r.width, r.height);
+            if (!why.empty()) return fail(MPC_ERR_ARGUMENT, "frame %d: %s", f, why.c_str());
+            rects[static_cast<size_t>(f)] = r;
+        }
+        std::vector<int> wh(2 * static_cast<size_t>(n_frames));
+        return decode_sequence(c, bytes, nbytes, n_frames, nullptr, nullptr, nullptr, wh.data(), wh.data() + n_frames, false, indexes, index_bytes,
+                               routes, rects.data(), flags, views, false, nullptr, nullptr, out, out_bytes);
     });
 }
 

@@ -2,6 +2,7 @@
 // back, and the chunked parses on the host -- of a whole frame, of a pixel rectangle's window -- that define what the device parse
 // (mp_parse.hip) computes.
 #include <cstring>
+#include <string>
 
 #include "mpc_internal.h"
 
@@ -217,6 +218,29 @@ mpc_status mpc_truncate_container(const uint8_t* bytes, size_t nbytes, int steps
         if (!cut.empty()) std::memcpy(copy, cut.data(), cut.size());
         *out = copy;
         *out_bytes = cut.size();
+        return MPC_OK;
+    });
+}
+
+mpc_status mpc_transcode_container(const uint8_t* bytes, size_t nbytes, const mpc_view* view, uint8_t** out, size_t* out_bytes) {
+    return guarded([&]() -> mpc_status {
+        if (!bytes || !view || !out || !out_bytes) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (const char* why = transcode_argument_error(*view)) return fail(MPC_ERR_ARGUMENT, "%s", why);
+        int width, height, K, block_size;
+        if (!mpc::container_info(bytes, nbytes, &width, &height, &K, &block_size)) return fail(MPC_ERR_BITSTREAM, "Invalid input data");
+        const mpc_rect rect = view_rect(*view, width, height);
+        const std::string why = mpc::transcode_rect_error(width, height, block_size, rect.x, rect.y, rect.width, rect.height);
+        if (!why.empty()) return fail(MPC_ERR_ARGUMENT, "%s", why.c_str());
+        std::vector<uint8_t> made;
+        const int verdict = mpc::transcode_container(bytes, nbytes, rect.x, rect.y, rect.width, rect.height, view->steps, made);
+        if (verdict == 1) return fail(MPC_ERR_BITSTREAM, "Invalid input data");
+        if (verdict == 2) return fail(MPC_ERR_BITSTREAM, "Invalid bitstream");
+        if (verdict != 0) return fail(MPC_ERR_ARGUMENT, "rectangle %dx%d at (%d, %d) is empty or not inside the frame", rect.width, rect.height, rect.x, rect.y);
+        uint8_t* copy = static_cast<uint8_t*>(std::malloc(made.empty() ? 1 : made.size()));
+        if (!copy) return fail(MPC_ERR_ALLOC, "out of memory");
+        if (!made.empty()) std::memcpy(copy, made.data(), made.size());
+        *out = copy;
+        *out_bytes = made.size();
         return MPC_OK;
     });
 }

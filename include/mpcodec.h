@@ -707,6 +707,64 @@ mpc_status mpc_parse_container_view_device(mpc_context* ctx, const uint8_t* byte
                                            size_t index_bytes, const mpc_view* view, unsigned flags, uint16_t** symbols,
                                            size_t* n_symbols, uint64_t* ranges, int* route);
 
+/* ---- transcode: a view of a container as a container ("Transcode") ----
+ * A tile's records depend on that tile's pixels alone, the 6K streams are compactions of the records in tile order, and the step-0
+ * difference coding is a function of that order: for a tile-aligned rectangle the container of the cropped image is a pure function of
+ * the source container's symbols.  No pixels, no pursuit, no second loss.
+ *
+ * mpc_transcode_container: host only, no context; it defines what the device route computes.
+ *   input       parsed with mpc_read_compressed; what that refuses is MPC_ERR_BITSTREAM "Invalid input data"; a length above K anywhere
+ *               in the frame is MPC_ERR_BITSTREAM "Invalid bitstream".
+ *   scale_log2  must be 0, else MPC_ERR_ARGUMENT.
+ *   steps       the views' rule: 0 = all, < 0 is MPC_ERR_ARGUMENT, above K acts as K.  Call the result m.
+ *   rect        (0, 0, 0, 0): the whole frame.  Otherwise non-empty and inside the frame (the region decoder's checks), and aligned to
+ *               the container's own block size b (1 ... 8 on the host): x % b == 0, y % b == 0, x + width a multiple of b or the frame's
+ *               width, y + height a multiple of b or the frame's height; anything else is MPC_ERR_ARGUMENT.  A ragged right or bottom
+ *               edge is legal only where it is the frame's own: there the zero fill of a fresh encode of the crop is the source's.
+ *   result      (mpc_free) the container of width x height of the rectangle with the source's K, block size and 3K u16 quantiser
+ *               values.  Tile t' = (tx - tx0) * nty + (ty - ty0) of the new frame, nty = ty1 - ty0, takes the records of tile
+ *               t = tx * tiles_y + ty of the source; its lengths are min(length, m), records of steps >= m are dropped.  The streams are
+ *               assembled in the new tile order and written by the one host coder: step-0 coefficients are difference coded again from
+ *               zero, packed-or-not and Huffman-or-Golomb are chosen again.
+ * No dictionary is involved: a record outside its dynamic dictionary is carried over as it is, and a decoder refuses the result
+ * exactly where it would have refused those tiles of the source.  mpc_truncate_container's caveat holds here too: step-0 sums that move
+ * by 2^15 or more from tile to tile (no encoder writes them) are not kept by the difference coder.
+ * Consequences: the whole frame with steps 0 is a copy of what coding the parsed container again gives, for an encoder's container
+ * the input itself; the whole frame with steps m is mpc_truncate_container(m); transcodes compose (a rectangle of a rectangle is
+ * the rectangle of the source, and cutting steps commutes with cropping); and for a container an encoder made from pixels P with
+ * quantiser tables q the result is byte for byte mpc_truncate_container(mpc_encode_image(crop of P, q), m).
+ *
+ * mpc_transcode_views_indexed: the same bytes, statuses and error texts per frame from the device (refusals carry "frame N: ").
+ * out[f] (mpc_free) / out_bytes[f]: frame f's container.  routes as for the views.
+ *   route 0     needs a usable index, version 1 or 2: the view decoder's order up to the gather (upload, lengths parsed whole, ranks,
+ *               the windowed parse with the streams of steps >= m given empty chunk ranges, the windowed unpack, the windowed gather),
+ *               then mp_crop_records_kernel and the records-to-container chain (stream assembly, entropy phase 1, host tables, phase 2,
+ *               the copy) instead of the reconstruction.  MPC_VIEW_PARSE_ALL and what is trusted without it are the views', word for
+ *               word: without the flag, chunks outside the window and streams of steps >= m are never read.
+ *   route 1     no index, a refused index, "serial only": the serial parse on the host, cut as the truncation cuts it, the ordinary
+ *               upload, unpack and whole-frame gather, then the same crop kernel and the same chain.  No pixels exist on either route.
+ * The container's block size must be the context's, as for the decoders, and its K must be mpc_context_K(ctx), else MPC_ERR_ARGUMENT
+ * (both reported behind mpc_read_compressed's verdict); a host-only context is MPC_ERR_NO_DEVICE; the fast flag changes nothing.  The
+ * header's u16 quantiser values are passed on as doubles and truncated back to the same values.  The call runs on the context's
+ * container job slots: all of them must be idle (else MPC_ERR_ARGUMENT), and they are left idle.  On failure nothing is returned:
+ * every out[f] is NULL, every size 0, and the context is usable.  Frames of a call overlap on the decode slots; a result depends
+ * neither on n_frames nor on the order of the frames. */
+mpc_status mpc_transcode_container(const uint8_t* bytes, size_t nbytes, const mpc_view* view, uint8_t** out, size_t* out_bytes);
+mpc_status mpc_transcode_views_indexed(mpc_context* ctx, const uint8_t* const* bytes, const size_t* nbytes, const uint8_t* const* indexes,
+                                       const size_t* index_bytes, const mpc_view* views, int n_frames, unsigned flags, uint8_t** out,
+                                       size_t* out_bytes, int* routes);
+/* The crop kernel on the caller's records, e.g. those of mpc_encode_tiles_device for tile rows [0, tiles_y): several containers cut out
+ * of one pursuit (mpc_records_to_container_device of the result with the rectangle's width and height).  Whole-frame records of a
+ * width x height frame (tile t = tx * tiles_y + ty, counts[t * 3 + ch], choices[(t * 3 + ch) * K + i], K the context's) in; rect as for
+ * mpc_transcode_container with b the context's block size; steps 0 = all.  d_out_counts[tiles' * 3], d_out_choices[tiles' * 3 * K] of the
+ * rectangle's tiles' = ntx * nty: counts min(count, steps), the records below that copied, the steps from there to K zero.  Asynchronous
+ * on `stream`; the outputs must not overlap the inputs.  Every address comes from the rectangle's tile grid; a count above K is used as
+ * K and sets the context's crop error word, which mpc_crop_records_check(ctx, stream) reads and clears behind everything enqueued on
+ * `stream` (it synchronises the stream): MPC_ERR_BITSTREAM "Invalid bitstream" if a crop since the last check saw one, else MPC_OK. */
+mpc_status mpc_crop_records_device(mpc_context* ctx, const uint16_t* d_counts, const mpc_basis_choice* d_choices, int width, int height,
+                                   const mpc_rect* rect, int steps, uint16_t* d_out_counts, mpc_basis_choice* d_out_choices, void* stream);
+mpc_status mpc_crop_records_check(mpc_context* ctx, void* stream);
+
 /* ---- "-s" patch statistics, Compression.cpp:200-302 ----
  * The reference seeds one std::mt19937, and for every image draws `patches` origins x = rand() % (width - bs),
  * y = rand() % (height - bs), runs CalcMPDynamic on the Y, U and V patch with every quantiser 1.0 and feeds
