@@ -75,6 +75,12 @@ tests/cpp/asan_transcode_bin: tests/cpp/asan_transcode.cpp $(wildcard imageexper
 asan-transcode: tests/cpp/asan_transcode_bin
 	ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=print_stacktrace=1 MPC_HOST_THREADS=4 ./tests/cpp/asan_transcode_bin
 
+tests/cpp/asan_compose_bin: tests/cpp/asan_compose.cpp $(wildcard imageexperiments_amd/csrc/host_*.cpp imageexperiments_amd/csrc/host_*.h)
+	g++ -std=c++17 -O1 -g $(SAN) -ffp-contract=off -pthread -Wall -Wno-unused-function tests/cpp/asan_compose.cpp -o $@
+
+asan-compose: tests/cpp/asan_compose_bin
+	ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=print_stacktrace=1 MPC_HOST_THREADS=4 ./tests/cpp/asan_compose_bin
+
 tests/cpp/asan_index_scan_bin: tests/cpp/asan_index_scan.cpp $(wildcard imageexperiments_amd/csrc/host_*.cpp imageexperiments_amd/csrc/host_*.h)
 	g++ -std=c++17 -O1 -g $(SAN) -ffp-contract=off -pthread -Wall -Wno-unused-function tests/cpp/asan_index_scan.cpp -o $@
 
@@ -89,6 +95,6 @@ asan-oracle: oracle/_build/liboracle_asan.so
 	LD_PRELOAD=$$(gcc -print-file-name=libasan.so) ASAN_OPTIONS=detect_leaks=0 ORACLE_LIB=$(CURDIR)/oracle/_build/liboracle_asan.so \
 	    python -m pytest tests/test_oracle_golden.py -x -q -p no:cacheprovider
 
-asan: asan-host asan-index asan-encode-index asan-encode-index2 asan-region asan-index2 asan-view asan-transcode asan-index-scan asan-oracle
+asan: asan-host asan-index asan-encode-index asan-encode-index2 asan-region asan-index2 asan-view asan-transcode asan-compose asan-index-scan asan-oracle
 
-.PHONY: asan asan-host asan-index asan-encode-index asan-encode-index2 asan-region asan-index2 asan-view asan-transcode asan-index-scan asan-oracle
+.PHONY: asan asan-host asan-index asan-encode-index asan-encode-index2 asan-region asan-index2 asan-view asan-transcode asan-compose asan-index-scan asan-oracle

@@ -50,6 +50,43 @@ class MpcView(C.Structure):                          # mpc_view
     _fields_ = [("rect", MpcRect), ("steps", C.c_int), ("scale_log2", C.c_int)]
 
 
+class MpcPart(C.Structure):                          # mpc_part
+    _fields_ = [("source", C.c_int), ("rect", MpcRect), ("x", C.c_int), ("y", C.c_int), ("rgb", C.c_void_p), ("row_stride", C.c_size_t)]
+
+
+MPC_COMPOSE_DEVICE_PIXELS = 2                                       # `flags` of mpc_compose_indexed
+
+
+def _parts(parts, device_pixels=False):
+    """[(source, rect, x, y)] -> (MpcPart array, what must stay alive).  source: an int with rect = (x, y, width, height) or None = all
+    of it; or pixels, rect None: an HxWx3 uint8 array (a strided view keeps its row stride), with device_pixels a
+    (data_ptr, width, height, row_stride) tuple"""
+    made, keep = (MpcPart * max(len(parts), 1))(), []                # never a null pointer: no parts is the call's to refuse
+    for at, (source, rect, x, y) in zip(made, parts):
+        at.x, at.y = int(x), int(y)
+        if isinstance(source, (int, np.integer)):
+            at.source = int(source)
+            at.rect = MpcRect(*[int(v) for v in (rect or (0, 0, 0, 0))])
+            continue
+        if rect is not None:
+            raise ValueError("a pixel part has no rectangle")
+        at.source = -1
+        if device_pixels:
+            ptr, width, height, row_stride = source
+            at.rgb, at.row_stride = int(ptr), int(row_stride)
+        else:
+            px = np.asarray(source)
+            if px.dtype != np.uint8 or px.ndim != 3 or px.shape[2] != 3:
+                raise ValueError("pixels: an HxWx3 uint8 array")
+            if px.size and (px.strides[2] != 1 or px.strides[1] != 3 or px.strides[0] < 3 * px.shape[1]):
+                px = np.ascontiguousarray(px)
+            keep.append(px)
+            height, width = px.shape[:2]
+            at.rgb, at.row_stride = px.ctypes.data, px.strides[0]
+        at.rect = MpcRect(0, 0, int(width), int(height))
+    return made, keep
+
+
 def _view(view):
     """(rect, steps, scale_log2) with rect = (x, y, width, height), (0, 0, 0, 0) or None = the whole frame -> MpcView"""
     if isinstance(view, MpcView):
@@ -219,6 +256,13 @@ def _bind_bitstream(L):
                                               C.c_uint, C.POINTER(_u8p), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
     L.mpc_crop_records_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, _rp, C.c_int, vp, vp, vp]
     L.mpc_crop_records_check.argtypes = [vp, vp]
+    _pp = C.POINTER(MpcPart)
+    L.mpc_compose_container.argtypes = [C.POINTER(_u8p), C.POINTER(C.c_size_t), C.c_int, _pp, C.c_int, C.c_int, C.c_int, C.POINTER(_u8p),
+                                        C.POINTER(C.c_size_t)]
+    L.mpc_paste_records_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, _rp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]
+    L.mpc_compose_indexed.argtypes = [vp, C.POINTER(_u8p), C.POINTER(C.c_size_t), C.POINTER(_u8p), C.POINTER(C.c_size_t), C.c_int, _pp, C.c_int,
+                                      C.c_int, C.c_int, C.c_uint, C.c_int, C.POINTER(_u8p), C.POINTER(C.c_size_t), C.POINTER(_u8p),
+                                      C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
     L.mpc_parse_container_view_device.argtypes = [vp] + _vparse
     L.mpc_decode_views_indexed.argtypes = [vp, C.POINTER(_u8p), C.POINTER(C.c_size_t), C.POINTER(_u8p), C.POINTER(C.c_size_t), _vwp, C.c_int,
                                            C.c_uint, C.POINTER(_u8p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -622,6 +666,25 @@ def transcode_container(blob, view):
     out, n = _u8p(), C.c_size_t(0)
     _check(L.mpc_transcode_container(buf.ctypes.data_as(_u8p), buf.size, C.byref(vw), C.byref(out), C.byref(n)))
     return _take_bytes(L, out, n)
+
+
+def compose_container(blobs, parts, width, height):
+    """mpc_compose_container: the container of a width x height frame from rectangles of containers -> bytes.  parts: [(source, rect, x,
+    y)], rect = (x, y, width, height) of blobs[source] (None = all of it) landing at (x, y); applied in order, a later part wins a tile.
+    Everything is aligned to the tiles; a ragged edge only where it is its source's own and lands on the destination's.  K, block size
+    and quantiser values are blobs[0]'s and must be every blob's.  For containers encoded from pixels with one integral quantiser table
+    the result is byte for byte the encode of the pasted pixels; no pixels and no pursuit are involved.  MpcError(MPC_ERR_ARGUMENT)
+    "part N: ..." / "source N: ..." for bad geometry, an uncovered tile, a pixel part; MpcError(MPC_ERR_BITSTREAM) for a header that does
+    not parse and for what read_compressed refuses of a source whose part owns a tile."""
+    L = load_library()
+    bufs = [np.frombuffer(b, np.uint8) for b in blobs]
+    n = len(bufs)
+    ptrs, sizes = (_u8p * n)(*[b.ctypes.data_as(_u8p) for b in bufs]), (C.c_size_t * n)(*[b.size for b in bufs])
+    made, keep = _parts(parts)
+    out, nout = _u8p(), C.c_size_t(0)
+    _check(L.mpc_compose_container(ptrs, sizes, n, made, len(parts), int(width), int(height), C.byref(out), C.byref(nout)))
+    del keep
+    return _take_bytes(L, out, nout)
 
 
 def _view_parse(fn, head, buf, idx, view, parse_all):
@@ -1268,6 +1331,41 @@ class CompressionContext:
         rc = MpcRect(*[int(v) for v in (rect or (0, 0, 0, 0))])
         _check(self.L.mpc_crop_records_device(self.h, d_counts, d_choices, width, height, C.byref(rc), int(steps), d_out_counts, d_out_choices,
                                               stream or None))
+        if check:
+            _check(self.L.mpc_crop_records_check(self.h, stream or None))
+
+    def compose(self, blobs, indexes, parts, width, height, parse_all=False, index_interval=None, device_pixels=False):
+        """mpc_compose_indexed: compose_container(blobs, parts, width, height) on the device, where a part's source may also be pixels
+        (an HxWx3 uint8 array; with device_pixels a (data_ptr, width, height, row_stride) tuple of device memory), which stand for this
+        context's encode of them with the destination's quantiser table -> (container, index or None, routes).  indexes: None, or one
+        seek index (or None) per blob.  routes[p]: 0 = through the source's seek index, 1 = the serial parse, 2 = pixels, -1 = the part
+        owns no tile and was skipped.  index_interval: None = no index, else container_index2(result, interval, expanded=True) comes
+        with the container, from the entropy stage.  With no blobs the call is an encode from patches with the context's tables."""
+        bufs, ptrs, sizes = self._containers(blobs)
+        n = len(bufs)
+        ibufs, iptrs, isizes = self._indexes(indexes if indexes is not None else [None] * n, n)
+        made, keep = _parts(parts, device_pixels)
+        flags = (1 if parse_all else 0) | (MPC_COMPOSE_DEVICE_PIXELS if device_pixels else 0)
+        out, nout, index, nindex = _u8p(), C.c_size_t(0), _u8p(), C.c_size_t(0)
+        routes = (C.c_int * len(made))()
+        _check(self.L.mpc_compose_indexed(self.h, ptrs, sizes, iptrs, isizes, n, made, len(parts), int(width), int(height), flags,
+                                          -1 if index_interval is None else int(index_interval), C.byref(out), C.byref(nout), C.byref(index),
+                                          C.byref(nindex), routes))
+        del keep, bufs, ibufs
+        blob = _take_bytes(self.L, out, nout)
+        return blob, None if index_interval is None else _take_bytes(self.L, index, nindex), list(routes)[:len(parts)]
+
+    def paste_records_device(self, d_src_counts, d_src_choices, src_width, src_height, src_rect, d_dst_counts, d_dst_choices, dst_width,
+                             dst_height, dst_x, dst_y, d_owner=None, part=0, stream=0, check=True):
+        """mpc_paste_records_device: the records of the tile-aligned rectangle src_rect (None = the whole frame) of a src_width x
+        src_height frame into the tiles at (dst_x, dst_y) of a dst_width x dst_height frame's records, both whole-frame records in device
+        memory; counts min(count, K), records below the count copied, the steps behind them zero.  d_owner: None, or int32 per
+        destination tile: only tiles with d_owner[t] == part are written.  check: mpc_crop_records_check behind it, which waits for
+        `stream` and raises MpcError(MPC_ERR_BITSTREAM) if a count above K was met."""
+        rc = MpcRect(*[int(v) for v in (src_rect or (0, 0, 0, 0))])
+        _check(self.L.mpc_paste_records_device(self.h, d_src_counts, d_src_choices, int(src_width), int(src_height), C.byref(rc), d_dst_counts,
+                                               d_dst_choices, int(dst_width), int(dst_height), int(dst_x), int(dst_y), d_owner or None, int(part),
+                                               stream or None))
         if check:
             _check(self.L.mpc_crop_records_check(self.h, stream or None))
 

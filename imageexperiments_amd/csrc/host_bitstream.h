@@ -288,6 +288,44 @@ int transcode_container(const uint8_t* bytes, size_t nbytes, int x, int y, int w
 // the frame; x or y is no multiple of block_size; x + w (y + h) is neither a multiple of block_size nor the frame's width (height)
 std::string transcode_rect_error(int width, int height, int block_size, int x, int y, int w, int h);
 
+// ---- compose: a container from rectangles of containers (include/mpcodec.h, "compose"; DESIGN.md section 4, "Compose") ----
+// The inverse of the transcode: destination tile (dtx0 + i) * tiles_y + (dty0 + j) takes the counts and records of its owner's source
+// tile (stx0 + i) * src_tiles_y + (sty0 + j), the owner being the last part whose destination grid holds the tile.
+struct ComposePart {
+    int source = 0;                 // >= 0: (x, y, w, h) is a rectangle of container `source`, (0, 0, 0, 0) = all of it; -1: w x h pixels
+    int x = 0, y = 0, w = 0, h = 0;
+    int dx = 0, dy = 0;             // where the rectangle's top-left lands in the destination
+    bool has_pixels = false;        // source == -1: the caller gave a pointer
+    int src_width = 0, src_height = 0;      // compose_plan: the frame the rectangle is cut out of; for pixels w x h
+};
+struct ComposeSource {
+    int width = 0, height = 0, K = 0, block_size = 0;
+    uint16_t quant[3][32] = {};
+};
+struct ComposeDevice {              // the device route: pixel parts are legal, and K and block size must be these
+    int K = 0, block_size = 0;
+};
+struct ComposePlan {
+    int K = 0, block_size = 0, tiles_x = 0, tiles_y = 0;
+    std::vector<ComposeSource> sources;
+    std::vector<ComposePart> parts;         // rectangles resolved
+    std::vector<int32_t> owner;             // per destination tile, in the destination's tile order
+    std::vector<char> owns;                 // per part: it owns at least one tile
+};
+// empty, or why `part` (rectangle resolved, src_width x src_height set) cannot be placed into a width x height destination in tiles of
+// bs: check 3 of mpc_compose_container
+std::string compose_part_error(const ComposePart& part, int bs, int width, int height);
+// Checks 1 to 4 of mpc_compose_container in their order and the owner map.  device: null for the host definition (a pixel part and
+// n_sources == 0 are refused), else pixel parts are legal, K and block size are the device's where there is no source, and sources
+// that have another K or block size are refused behind the header checks.  Returns 0, 1 = MPC_ERR_BITSTREAM, 2 = MPC_ERR_ARGUMENT
+// with the text in `why`
+int compose_plan(const uint8_t* const* bytes, const size_t* nbytes, int n_sources, const ComposePart* parts, int n_parts, int width, int height,
+                 const ComposeDevice* device, ComposePlan& plan, std::string& why);
+// mpc_compose_container: the plan, then every source an owning part names through read_compressed, the records placed in the
+// destination's tile order, write_compressed.  Verdicts as compose_plan's
+int compose_container(const uint8_t* const* bytes, const size_t* nbytes, int n_sources, const ComposePart* parts, int n_parts, int width, int height,
+                      std::vector<uint8_t>& out, std::string& why);
+
 // The same index from what an encoder holds when it has just written the container, without parsing anything: the plans of
 // plan_stream, where each stream's codes begin, and the bit of every interval-th coded symbol as the code writer passed it.
 struct StreamPlan;                                  // below

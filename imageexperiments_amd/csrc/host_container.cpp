@@ -4,6 +4,7 @@
 #include "host_bitstream.h"
 
 #include <algorithm>
+#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -1374,6 +1375,188 @@ int transcode_container(const uint8_t* bytes, size_t nbytes, int x, int y, int w
         }
     }
     out = write_compressed(cropped);
+    return 0;
+}
+
+namespace {
+int compose_refuse(std::string& why, int verdict, const char* format, ...) __attribute__((format(printf, 3, 4)));
+int compose_refuse(std::string& why, int verdict, const char* format, ...) {
+    char text[320];
+    va_list args;
+    va_start(args, format);
+    std::vsnprintf(text, sizeof text, format, args);
+    va_end(args);
+    why = text;
+    return verdict;
+}
+}  // namespace
+
+std::string compose_part_error(const ComposePart& part, int bs, int width, int height) {
+    const std::string rect_error = transcode_rect_error(part.src_width, part.src_height, bs, part.x, part.y, part.w, part.h);
+    if (!rect_error.empty()) return rect_error;
+    char text[240];
+    // inside its source: x + w and y + h do not overflow; the destination's sums are taken in 64 bits
+    const long long right = static_cast<long long>(part.dx) + part.w, bottom = static_cast<long long>(part.dy) + part.h;
+    if (part.dx < 0 || part.dy < 0 || part.dx % bs != 0 || part.dy % bs != 0) {
+        std::snprintf(text, sizeof text, "(%d, %d) is not aligned to the %d-pixel tiles of the destination", part.dx, part.dy, bs);
+        return text;
+    }
+    if (right > width || bottom > height) {
+        std::snprintf(text, sizeof text, "%dx%d at (%d, %d) is not inside the destination of %dx%d", part.w, part.h, part.dx, part.dy, width, height);
+        return text;
+    }
+    // a ragged tile carries its zero fill: it is the encode of pasted pixels only where the destination is ragged in the same way
+    if ((part.x + part.w) % bs != 0 && right != width) {
+        std::snprintf(text, sizeof text, "the ragged right edge at %d lands at %lld, not on the destination's edge %d", part.x + part.w, right, width);
+        return text;
+    }
+    if ((part.y + part.h) % bs != 0 && bottom != height) {
+        std::snprintf(text, sizeof text, "the ragged bottom edge at %d lands at %lld, not on the destination's edge %d", part.y + part.h, bottom,
+                      height);
+        return text;
+    }
+    return std::string();
+}
+
+int compose_plan(const uint8_t* const* bytes, const size_t* nbytes, int n_sources, const ComposePart* parts, int n_parts, int width, int height,
+                 const ComposeDevice* device, ComposePlan& plan, std::string& why) {
+    // 1. what needs no container
+    if (!parts || (n_sources > 0 && (!bytes || !nbytes))) return compose_refuse(why, 2, "null argument");
+    if (n_parts < 1) return compose_refuse(why, 2, "n_parts must be at least 1");
+    if (width < 1 || height < 1) return compose_refuse(why, 2, "bad geometry");
+    if (n_sources < 0) return compose_refuse(why, 2, "n_sources must not be negative");
+    for (int s = 0; s < n_sources; ++s)
+        if (!bytes[s]) return compose_refuse(why, 2, "source %d: null argument", s);
+    for (int p = 0; p < n_parts; ++p) {
+        if (parts[p].source < -1 || parts[p].source >= n_sources)
+            return compose_refuse(why, 2, "part %d: source %d of %d", p, parts[p].source, n_sources);
+        if (parts[p].source == -1 && !device) return compose_refuse(why, 2, "part %d: pixels need a device", p);
+        if (parts[p].source == -1 && !parts[p].has_pixels) return compose_refuse(why, 2, "part %d: null argument", p);
+    }
+    if (n_sources == 0 && !device) return compose_refuse(why, 2, "n_sources must be at least 1: the host computes no tiles");
+    // 2. every source's header, named by a part or not: a container holds one quantiser table
+    plan.sources.assign(static_cast<size_t>(n_sources), {});
+    for (int s = 0; s < n_sources; ++s) {
+        ComposeSource& src = plan.sources[static_cast<size_t>(s)];
+        if (!container_info(bytes[s], nbytes[s], &src.width, &src.height, &src.K, &src.block_size))
+            return compose_refuse(why, 1, "source %d: Invalid input data", s);
+        BitReader in(bytes[s], nbytes[s]);
+        int skip[4];
+        read_header(in, &skip[0], &skip[1], &skip[2], &skip[3]);
+        for (int ch = 0; ch < 3; ++ch)
+            for (int i = 0; i < src.K; ++i) src.quant[ch][i] = static_cast<uint16_t>(in.get(16));
+        const ComposeSource& first = plan.sources[0];
+        if (src.K != first.K) return compose_refuse(why, 2, "source %d: K %d, source 0 has K %d", s, src.K, first.K);
+        if (src.block_size != first.block_size)
+            return compose_refuse(why, 2, "source %d: block size %d, source 0 has block size %d", s, src.block_size, first.block_size);
+        for (int ch = 0; ch < 3; ++ch)
+            for (int i = 0; i < src.K; ++i)
+                if (src.quant[ch][i] != first.quant[ch][i])
+                    return compose_refuse(why, 2, "source %d: quantiser value %d of channel %d is %u, source 0 has %u", s, i, ch,
+                                          static_cast<unsigned>(src.quant[ch][i]), static_cast<unsigned>(first.quant[ch][i]));
+    }
+    plan.K = n_sources > 0 ? plan.sources[0].K : device->K;
+    plan.block_size = n_sources > 0 ? plan.sources[0].block_size : device->block_size;
+    if (device && plan.K != device->K) return compose_refuse(why, 2, "container K %d, context K %d", plan.K, device->K);
+    if (device && plan.block_size != device->block_size)
+        return compose_refuse(why, 2, "stream block size %d, context block size %d", plan.block_size, device->block_size);
+    // 3. every part's geometry
+    const int bs = plan.block_size;
+    const long long tiles_x = (static_cast<long long>(width) + bs - 1) / bs, tiles_y = (static_cast<long long>(height) + bs - 1) / bs;
+    if (tiles_x * tiles_y >= (1LL << 31)) return compose_refuse(why, 2, "bad geometry");
+    plan.tiles_x = static_cast<int>(tiles_x);
+    plan.tiles_y = static_cast<int>(tiles_y);
+    plan.parts.assign(parts, parts + n_parts);
+    for (int p = 0; p < n_parts; ++p) {
+        ComposePart& part = plan.parts[static_cast<size_t>(p)];
+        int sw, sh;                                                 // the frame the rectangle is cut out of: pixels are a frame of their own
+        if (part.source >= 0) {
+            sw = plan.sources[static_cast<size_t>(part.source)].width;
+            sh = plan.sources[static_cast<size_t>(part.source)].height;
+            if (part.x == 0 && part.y == 0 && part.w == 0 && part.h == 0) {
+                part.w = sw;
+                part.h = sh;
+            }
+        } else {
+            sw = part.w;
+            sh = part.h;
+        }
+        part.src_width = sw;
+        part.src_height = sh;
+        const std::string geometry = compose_part_error(part, bs, width, height);
+        if (!geometry.empty()) return compose_refuse(why, 2, "part %d: %s", p, geometry.c_str());
+    }
+    // 4. coverage: the owner of a tile is the last part whose grid holds it
+    plan.owner.assign(static_cast<size_t>(tiles_x * tiles_y), -1);
+    plan.owns.assign(static_cast<size_t>(n_parts), 0);
+    for (int p = 0; p < n_parts; ++p) {
+        const ComposePart& part = plan.parts[static_cast<size_t>(p)];
+        const int ntx = (part.x + part.w + bs - 1) / bs - part.x / bs, nty = (part.y + part.h + bs - 1) / bs - part.y / bs;
+        for (int i = 0; i < ntx; ++i)
+            std::fill_n(plan.owner.begin() + (static_cast<long long>(part.dx / bs + i) * tiles_y + part.dy / bs), nty, p);
+    }
+    for (size_t t = 0; t < plan.owner.size(); ++t) {
+        if (plan.owner[t] < 0)
+            return compose_refuse(why, 2, "destination tile %zu (column %zu, row %zu) is covered by no part", t, t / static_cast<size_t>(tiles_y),
+                                  t % static_cast<size_t>(tiles_y));
+        plan.owns[static_cast<size_t>(plan.owner[t])] = 1;
+    }
+    return 0;
+}
+
+int compose_container(const uint8_t* const* bytes, const size_t* nbytes, int n_sources, const ComposePart* parts, int n_parts, int width, int height,
+                      std::vector<uint8_t>& out, std::string& why) {
+    ComposePlan plan;
+    if (!bytes || !nbytes) return compose_refuse(why, 2, "null argument");
+    if (const int verdict = compose_plan(bytes, nbytes, n_sources, parts, n_parts, width, height, nullptr, plan, why); verdict != 0) return verdict;
+    // 5. the sources that owning parts name, as whole-frame records
+    const int K = plan.K, bs = plan.block_size;
+    struct Records {
+        bool read = false;
+        std::vector<uint16_t> counts;
+        std::vector<uint32_t> choices;
+    };
+    std::vector<Records> records(static_cast<size_t>(n_sources));
+    for (int p = 0; p < n_parts; ++p) {
+        if (!plan.owns[static_cast<size_t>(p)]) continue;
+        const int source = plan.parts[static_cast<size_t>(p)].source;
+        Records& r = records[static_cast<size_t>(source)];
+        if (r.read) continue;                                       // a lower part has named it, and it was sound
+        Streams s;
+        if (!read_compressed(bytes[source], nbytes[source], s)) return compose_refuse(why, 1, "part %d: Invalid input data", p);
+        for (uint16_t length : s.lengths)
+            if (length > K) return compose_refuse(why, 1, "part %d: Invalid bitstream", p);
+        if (!disassemble_streams(s, r.counts, r.choices)) return compose_refuse(why, 1, "part %d: Invalid input data", p);
+        r.read = true;
+    }
+    Streams made;
+    made.width = width;
+    made.height = height;
+    made.K = K;
+    made.block_size = bs;
+    std::memcpy(made.quant, plan.sources[0].quant, sizeof(made.quant));
+    made.codes.assign(static_cast<size_t>(6 * K), {});
+    made.lengths.resize(3 * plan.owner.size());
+    // the destination's tile order: every tile takes the counts and the records of its owner's source tile
+    for (size_t t = 0; t < plan.owner.size(); ++t) {
+        const ComposePart& part = plan.parts[static_cast<size_t>(plan.owner[t])];
+        const Records& r = records[static_cast<size_t>(part.source)];
+        const size_t tx = t / static_cast<size_t>(plan.tiles_y), ty = t % static_cast<size_t>(plan.tiles_y);
+        const size_t src_tiles_y = static_cast<size_t>((part.src_height + bs - 1) / bs);
+        const size_t from = (tx - static_cast<size_t>(part.dx / bs) + static_cast<size_t>(part.x / bs)) * src_tiles_y +
+                            (ty - static_cast<size_t>(part.dy / bs) + static_cast<size_t>(part.y / bs));
+        for (size_t ch = 0; ch < 3; ++ch) {
+            const int length = r.counts[3 * from + ch];
+            made.lengths[3 * t + ch] = static_cast<uint16_t>(length);
+            for (int i = 0; i < length; ++i) {
+                const uint32_t record = r.choices[(3 * from + ch) * static_cast<size_t>(K) + static_cast<size_t>(i)];
+                const size_t pair = 2 * static_cast<size_t>(K) * ch + 2 * static_cast<size_t>(i);
+                made.codes[pair].push_back(static_cast<uint16_t>(record & 0xFFFFu));
+                made.codes[pair + 1].push_back(static_cast<uint16_t>(record >> 16));
+            }
+        }
+    }
+    out = write_compressed(made);
     return 0;
 }
 

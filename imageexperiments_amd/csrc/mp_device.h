@@ -278,6 +278,13 @@ int launch_interleave_stripe(const uint16_t* part_counts, const uint32_t* part_c
 // t' = (tx - tx0) * (ty1 - ty0) + (ty - ty0).  *error (the caller zeroes it) is set by a count above K in the grid.  steps >= 1
 int launch_crop_records(const uint16_t* counts, const uint32_t* choices, int tiles_x, int tiles_y, int tx0, int ty0, int tx1, int ty1, int K,
                         int steps, uint16_t* out_counts, uint32_t* out_choices, int* error, void* stream);
+// records of the grid of ncols x nty tiles at (stx0, sty0) of a frame of src_tiles_x x src_tiles_y tiles -> the grid of the same size at
+// (dtx0, dty0) of a frame of dst_tiles_x x dst_tiles_y tiles, both in whole-frame layout: counts min(count, K), the records below that
+// copied, the steps behind them zero.  owner: null, or per destination tile; then only tiles with owner[t] == part are written.
+// *error (the caller zeroes it) is set by a count above K in a written tile
+int launch_paste_records(const uint16_t* src_counts, const uint32_t* src_choices, int src_tiles_x, int src_tiles_y, int stx0, int sty0, int ncols,
+                         int nty, int K, uint16_t* dst_counts, uint32_t* dst_choices, int dst_tiles_x, int dst_tiles_y, int dtx0, int dty0,
+                         const int32_t* owner, int part, int* error, void* stream);
 
 // ---- the decoder's per-symbol work in front of the gather (mp_unpack.hip): run-length expansion, DC sums ----
 constexpr int kUnpackBlock = 2048;      // coded symbols per workgroup

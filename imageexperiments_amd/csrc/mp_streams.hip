@@ -392,6 +392,58 @@ int launch_crop_records(const uint16_t* counts, const uint32_t* choices, int til
     return (int)hipGetLastError();
 }
 
+// The inverse move (a compose: a container from rectangles of containers): the records of the grid of ncols x nty tiles at (stx0, sty0)
+// of one frame into the grid of the same size at (dtx0, dty0) of another, both in whole-frame layout.  A tile column's rows are
+// contiguous on both sides, so a thread per word of the grid reads and writes consecutive words across a wave whatever K is.  Records
+// below the count are copied, the steps from the count to K are written as zero: garbage behind a source count is not carried over.
+// owner: null, or one word per destination tile; a tile is then written only where owner[t] == part, so the pastes of one owner map
+// write disjoint tiles.  Every address comes from the two grids: a count above K is clamped to K where it is used and sets *error.
+__global__ __launch_bounds__(256) void mp_paste_records_kernel(const uint16_t* __restrict__ src_counts, const uint32_t* __restrict__ src_choices,
+                                                               int src_tiles_y, int stx0, int sty0, int ncols, int nty, int K,
+                                                               uint16_t* __restrict__ dst_counts, uint32_t* __restrict__ dst_choices,
+                                                               int dst_tiles_y, int dtx0, int dty0, const int32_t* __restrict__ owner, int part,
+                                                               int* __restrict__ error)
+{
+    const int halves_per_col = nty * 3, words_per_col = halves_per_col * K;      // < 2^31 (the launcher)
+    const long long n_words = (long long)words_per_col * ncols, n_halves = (long long)halves_per_col * ncols;
+    for (long long o = (long long)blockIdx.x * 256 + threadIdx.x; o < n_words; o += (long long)gridDim.x * 256) {
+        const int col = (int)(o / words_per_col), w = (int)(o - (long long)col * words_per_col);
+        const int tc = w / K, i = w - tc * K;                             // tile-channel of the column's rows, step
+        const long long to_tile = (long long)(dtx0 + col) * dst_tiles_y + dty0;  // the column's first tile on either side
+        if (owner && owner[to_tile + tc / 3] != part) continue;
+        const long long from = ((long long)(stx0 + col) * src_tiles_y + sty0) * 3;
+        int c = src_counts[from + tc];
+        if (c > K) c = K;
+        dst_choices[to_tile * 3 * K + w] = i < c ? src_choices[from * K + w] : 0u;
+    }
+    for (long long o = (long long)blockIdx.x * 256 + threadIdx.x; o < n_halves; o += (long long)gridDim.x * 256) {
+        const int col = (int)(o / halves_per_col), tc = (int)(o - (long long)col * halves_per_col);
+        const long long to_tile = (long long)(dtx0 + col) * dst_tiles_y + dty0;
+        if (owner && owner[to_tile + tc / 3] != part) continue;
+        int c = src_counts[((long long)(stx0 + col) * src_tiles_y + sty0) * 3 + tc];
+        if (c > K) {
+            *error = 1;
+            c = K;
+        }
+        dst_counts[to_tile * 3 + tc] = (uint16_t)c;
+    }
+}
+
+int launch_paste_records(const uint16_t* src_counts, const uint32_t* src_choices, int src_tiles_x, int src_tiles_y, int stx0, int sty0, int ncols,
+                         int nty, int K, uint16_t* dst_counts, uint32_t* dst_choices, int dst_tiles_x, int dst_tiles_y, int dtx0, int dty0,
+                         const int32_t* owner, int part, int* error, void* stream_)
+{
+    if (ncols < 1 || nty < 1 || K < 1 || K > kMaxDeviceK || stx0 < 0 || sty0 < 0 || dtx0 < 0 || dty0 < 0) return (int)hipErrorInvalidValue;
+    if (ncols > src_tiles_x - stx0 || nty > src_tiles_y - sty0 || ncols > dst_tiles_x - dtx0 || nty > dst_tiles_y - dty0)
+        return (int)hipErrorInvalidValue;
+    if ((long long)nty * 3 * K >= (1LL << 31)) return (int)hipErrorInvalidValue;
+    const long long n_words = (long long)nty * 3 * K * ncols;
+    const unsigned blocks = (unsigned)((n_words + 255) / 256 < 4096 ? (n_words + 255) / 256 : 4096);
+    hipLaunchKernelGGL(mp_paste_records_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream_), src_counts, src_choices, src_tiles_y,
+                       stx0, sty0, ncols, nty, K, dst_counts, dst_choices, dst_tiles_y, dtx0, dty0, owner, part, error);
+    return (int)hipGetLastError();
+}
+
 int launch_interleave_stripe(const uint16_t* part_counts, const uint32_t* part_choices, int tiles_x, int tiles_y, int row_begin, int rows,
                              int K, uint16_t* frame_counts, uint32_t* frame_choices, void* stream_)
 {

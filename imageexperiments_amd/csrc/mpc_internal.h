@@ -331,6 +331,8 @@ struct mpc_context {
     std::recursive_mutex host_calls;  // the host-buffer entry points share the staging buffers below
     int* d_flag = nullptr;            // mpc_decode_tiles_device: set when a record indexes outside its dictionary
     int* d_crop_flag = nullptr;       // mpc_crop_records_device: set by a count above K, read by mpc_crop_records_check
+    GrowBuffer compose_dev{GrowBuffer::kDevice};     // mpc_compose_indexed: the destination's records, the owner map, the pixel parts' patches
+    hipStream_t compose_side = nullptr;              // ... the pixel parts' stream and the final container job's, made on first use
     // grow-only staging for the host-buffer encode entry points (mpc_encode_tiles / mpc_encode_image(s)): allocating and freeing
     // them per call cost several times the encode itself.  The decoder stages in its slots' own buffers (DecodeSlot).
     GrowBuffer stage{GrowBuffer::kDevice};
@@ -408,6 +410,22 @@ inline const char* transcode_argument_error(const mpc_view& v) {
     if (v.steps < 0) return "steps must not be negative";
     if (v.scale_log2 != 0) return "scale_log2 must be 0: a transcode does not reduce";
     return nullptr;
+}
+
+// a compose's parts (include/mpcodec.h, "compose") as the host's plan takes them
+inline std::vector<mpc::ComposePart> compose_parts(const mpc_part* parts, int n_parts) {
+    std::vector<mpc::ComposePart> made(static_cast<size_t>(n_parts > 0 ? n_parts : 1));      // never empty: data() is no null pointer
+    for (size_t p = 0; n_parts > 0 && p < made.size(); ++p) {
+        made[p].source = parts[p].source;
+        made[p].x = parts[p].rect.x;
+        made[p].y = parts[p].rect.y;
+        made[p].w = parts[p].rect.width;
+        made[p].h = parts[p].rect.height;
+        made[p].dx = parts[p].x;
+        made[p].dy = parts[p].y;
+        made[p].has_pixels = parts[p].rgb != nullptr;
+    }
+    return made;
 }
 
 // ---- context and tile encode (mpcodec_context.cpp) ----

@@ -842,6 +842,15 @@ mpc_status mpc_interleave_stripe_device(mpc_context* c, const uint16_t* d_part_c
     return MPC_OK;
 }
 
+// the context's crop error word, made on first use (the device is current)
+static mpc_status crop_flag(mpc_context* c) {
+    if (c->d_crop_flag) return MPC_OK;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_crop_flag), sizeof(int)));
+    HIP_TRY(hipMemset(c->d_crop_flag, 0, sizeof(int)));
+    HIP_TRY(hipDeviceSynchronize());
+    return MPC_OK;
+}
+
 mpc_status mpc_crop_records_device(mpc_context* c, const uint16_t* d_counts, const mpc_basis_choice* d_choices, int width, int height,
                                    const mpc_rect* rect, int steps, uint16_t* d_out_counts, mpc_basis_choice* d_out_choices, void* stream) {
     return guarded([&]() -> mpc_status {
@@ -855,15 +864,46 @@ mpc_status mpc_crop_records_device(mpc_context* c, const uint16_t* d_counts, con
     mpc::TileWindow win;
     mpc::tile_window(width, height, c->block_size, r.x, r.y, r.width, r.height, win);
     HIP_TRY(hipSetDevice(c->device));
-    if (!c->d_crop_flag) {
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_crop_flag), sizeof(int)));
-        HIP_TRY(hipMemset(c->d_crop_flag, 0, sizeof(int)));
-        HIP_TRY(hipDeviceSynchronize());
-    }
+    if (const mpc_status fs = crop_flag(c); fs != MPC_OK) return fs;
     const int bs = c->block_size;
     const int err = mpc::launch_crop_records(d_counts, reinterpret_cast<const uint32_t*>(d_choices), (width + bs - 1) / bs, win.tiles_y, win.tx0,
                                              win.ty0, win.tx1, win.ty1, c->K, steps > 0 && steps < c->K ? steps : c->K, d_out_counts,
                                              reinterpret_cast<uint32_t*>(d_out_choices), c->d_crop_flag, stream);
+    if (err != 0) return launch_failed(err);
+    return MPC_OK;
+    });
+}
+
+mpc_status mpc_paste_records_device(mpc_context* c, const uint16_t* d_src_counts, const mpc_basis_choice* d_src_choices, int src_width,
+                                    int src_height, const mpc_rect* src_rect, uint16_t* d_dst_counts, mpc_basis_choice* d_dst_choices,
+                                    int dst_width, int dst_height, int dst_x, int dst_y, const int32_t* d_owner, int part, void* stream) {
+    return guarded([&]() -> mpc_status {
+    if (!c || !d_src_counts || !d_src_choices || !src_rect || !d_dst_counts || !d_dst_choices) return fail(MPC_ERR_ARGUMENT, "null argument");
+    if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device");
+    if (src_width < 1 || src_height < 1 || dst_width < 1 || dst_height < 1) return fail(MPC_ERR_ARGUMENT, "bad geometry");
+    const int bs = c->block_size;
+    mpc::ComposePart piece;
+    const bool whole = src_rect->x == 0 && src_rect->y == 0 && src_rect->width == 0 && src_rect->height == 0;
+    piece.x = src_rect->x;
+    piece.y = src_rect->y;
+    piece.w = whole ? src_width : src_rect->width;
+    piece.h = whole ? src_height : src_rect->height;
+    piece.dx = dst_x;
+    piece.dy = dst_y;
+    piece.src_width = src_width;
+    piece.src_height = src_height;
+    const std::string why = mpc::compose_part_error(piece, bs, dst_width, dst_height);
+    if (!why.empty()) return fail(MPC_ERR_ARGUMENT, "%s", why.c_str());
+    const long long dst_tiles_x = (static_cast<long long>(dst_width) + bs - 1) / bs, dst_tiles_y = (static_cast<long long>(dst_height) + bs - 1) / bs;
+    if (dst_tiles_x * dst_tiles_y >= (1LL << 31)) return fail(MPC_ERR_ARGUMENT, "bad geometry");
+    HIP_TRY(hipSetDevice(c->device));
+    if (const mpc_status fs = crop_flag(c); fs != MPC_OK) return fs;
+    const int stx0 = piece.x / bs, sty0 = piece.y / bs;
+    const int err = mpc::launch_paste_records(d_src_counts, reinterpret_cast<const uint32_t*>(d_src_choices), (src_width + bs - 1) / bs,
+                                              (src_height + bs - 1) / bs, stx0, sty0, (piece.x + piece.w + bs - 1) / bs - stx0,
+                                              (piece.y + piece.h + bs - 1) / bs - sty0, c->K, d_dst_counts, reinterpret_cast<uint32_t*>(d_dst_choices),
+                                              static_cast<int>(dst_tiles_x), static_cast<int>(dst_tiles_y), dst_x / bs, dst_y / bs, d_owner, part,
+                                              c->d_crop_flag, stream);
     if (err != 0) return launch_failed(err);
     return MPC_OK;
     });

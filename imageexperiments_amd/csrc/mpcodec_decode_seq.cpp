@@ -86,6 +86,7 @@ void carve_unpack(Carve& cv, const UnpackPlan& p, int K, mpc::UnpackArgs* a) {
 }
 
 // ---- the sequence ----
+struct ComposeTarget;                           // below, with paste_on_slot
 struct Sequence {
     mpc_context* c = nullptr;
     Tuning tuning;
@@ -111,6 +112,7 @@ struct Sequence {
     // of the decode slot's number leave frame f's container here (malloc)
     uint8_t** containers = nullptr;
     size_t* container_bytes = nullptr;
+    const ComposeTarget* compose = nullptr;      // mpc_compose_indexed: frame f is a container part; no pixels, no container of its own
     std::atomic<int> next{0};                   // frames are handed out in order
     std::mutex lock;
     std::condition_variable turn;
@@ -121,7 +123,7 @@ struct Sequence {
 
     // the bytes frame f's pixels take at the caller's, the frame being width x height
     size_t out_bytes(int f, int width, int height) const {
-        if (containers) return 0;
+        if (containers || compose) return 0;
         if (views)
             return static_cast<size_t>(view_extent(rects[f].width, views[f].scale_log2)) *
                    static_cast<size_t>(view_extent(rects[f].height, views[f].scale_log2)) * 3;
@@ -694,6 +696,51 @@ struct FrameHead {
     const uint16_t (*quant)[32] = nullptr;
 };
 
+// What the container parts of a compose (include/mpcodec.h, "compose") write into: the call's destination records in whole-frame
+// layout and its owner map, in device memory; frame f of the sequence is part part_of_frame[f] of the call
+struct ComposeTarget {
+    uint16_t* d_counts = nullptr;
+    uint32_t* d_choices = nullptr;
+    const int32_t* d_owner = nullptr;
+    int tiles_x = 0, tiles_y = 0;
+    const int* part_of_frame = nullptr;
+    const mpc::ComposePart* parts = nullptr;
+};
+
+// A compose's container part behind the gather, the third mode beside the reconstruction and transcode_on_slot: the paste kernel moves
+// the rectangle's records from the slot's (frame layout, `counts` / `choices`) straight into the tiles of the call's destination that
+// the part owns.  It writes nothing but those tiles, whatever the records hold, and the slot's error words are read before the frame
+// counts: a part the index route refuses starts over on the serial route and writes the same tiles again.  *refused as in frame_on_slot
+mpc_status paste_on_slot(Sequence& q, int f, DecodeSlot& slot, UnpackJob& j, const uint16_t* counts, const uint32_t* choices, int width, int K,
+                         const mpc::TileWindow& win, bool indexed, double stamps[3], bool* refused) {
+    const ComposeTarget& to = *q.compose;
+    hipStream_t st = slot.stream;
+    const int part = to.part_of_frame[f], bs = q.c->block_size;
+    const mpc::ComposePart& piece = to.parts[part];
+    // the reconstruction's error word is this route's "a count above K", as for a transcode
+    if (const int e = mpc::launch_paste_records(counts, choices, (width + bs - 1) / bs, win.tiles_y, win.tx0, win.ty0, win.tx1 - win.tx0,
+                                                win.ty1 - win.ty0, K, to.d_counts, to.d_choices, to.tiles_x, to.tiles_y, piece.dx / bs,
+                                                piece.dy / bs, to.d_owner, part, j.ua.error + 1, st);
+        e != 0)
+        return launch_failed(e);
+    if (q.tuning.trace) HIP_TRY(hipEventRecord(slot.stamp[3], st));
+    HIP_TRY(hipMemcpyAsync(j.h_flags, j.ua.error, 3 * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (q.tuning.trace) HIP_TRY(hipEventRecord(slot.stamp[4], st));
+    HIP_TRY(hipEventRecord(slot.done, st));
+    HIP_TRY(hipEventSynchronize(slot.done));                        // the paste has finished: the call waits for every part's
+    stamps[1] = trace_ms();
+    if (indexed && (j.h_flags[2] != 0 || j.h_flags[0] != 0)) {
+        *refused = true;
+        return MPC_OK;
+    }
+    if (j.h_flags[0] != 0) return fail(MPC_ERR_BITSTREAM, "Invalid input data");
+    if (j.h_flags[1] != 0) return fail(MPC_ERR_BITSTREAM, "Invalid bitstream");
+    q.width[f] = q.rects[f].width;
+    q.height[f] = q.rects[f].height;
+    stamps[2] = trace_ms();
+    return MPC_OK;
+}
+
 // A transcode's frame behind the gather, in place of the reconstruction: the crop kernel moves the rectangle's records (frame layout,
 // `counts` / `choices`) into the new frame's tile order, cut to `steps`, and the records-to-container chain (ContainerJob) codes them
 // on the job slot of this decode slot's number, on the slot's own stream.  The error words are read first: records the index route
@@ -856,6 +903,7 @@ mpc_status frame_on_slot(Sequence& q, int f, DecodeSlot& slot, const FrameHead& 
             return launch_failed(e);
     } else if (const int e = mpc::launch_stream_gather(sa, d_choices, st); e != 0)
         return launch_failed(e);
+    if (q.compose) return paste_on_slot(q, f, slot, j, counts, d_choices, s.width, K, win, pp != nullptr, stamps, refused);
     if (q.containers)
         return transcode_on_slot(q, f, slot, j, counts, d_choices, s.width, s.height, K, win, dv.steps, quant, d_crop_counts, d_crop_choices,
                                  pp != nullptr, stamps, refused);
@@ -960,7 +1008,7 @@ void parse_worker(Sequence& q) {
             // a view of the first `steps` steps decodes the truncated container: its lengths are min(length, steps)
             const int steps = q.views && q.views[f].steps > 0 ? q.views[f].steps : INT_MAX;
             // (a transcode refuses a length above K wherever it is cut to, as mpc_transcode_container does, and a K that is not the context's)
-            const int held = q.containers ? INT_MAX : steps;
+            const int held = q.containers || q.compose ? INT_MAX : steps;
             const bool too_long = std::any_of(s.lengths.begin(), s.lengths.end(), [&](uint16_t length) { return std::min<int>(length, held) > s.K; });
             const bool K_differs = q.containers && s.K != c->K;
             if (block_size_differs || K_differs || too_long) {
@@ -1106,12 +1154,14 @@ mpc_status decode_sequence(mpc_context* c, const uint8_t* const* bytes, const si
                            const uint8_t* const* indexes = nullptr, const size_t* index_bytes = nullptr, int* routes = nullptr,
                            const mpc_rect* rects = nullptr, unsigned region_flags = 0, const mpc_view* views = nullptr, bool scan = false,
                            uint8_t** out_indexes = nullptr, size_t* out_index_bytes = nullptr, uint8_t** containers = nullptr,
-                           size_t* container_bytes = nullptr) {
-    // containers (with views and their rectangles): a transcode; no pixels in either form
+                           size_t* container_bytes = nullptr, const ComposeTarget* compose = nullptr) {
+    // containers (with views and their rectangles): a transcode; no pixels in either form.  compose (likewise): the container parts of
+    // a compose, whose error texts name the part
     if (indexes && !index_bytes) return fail(MPC_ERR_ARGUMENT, "null argument");
     if (containers && (!container_bytes || !views || rgb || d_rgb)) return fail(MPC_ERR_ARGUMENT, "null argument");
     if (out_indexes && !out_index_bytes) return fail(MPC_ERR_ARGUMENT, "null argument");
-    if (!c || !bytes || !nbytes || !width || !height || (!rgb && !d_rgb && !containers) || (d_rgb && !capacity))
+    if (compose && (!views || rgb || d_rgb || containers)) return fail(MPC_ERR_ARGUMENT, "null argument");
+    if (!c || !bytes || !nbytes || !width || !height || (!rgb && !d_rgb && !containers && !compose) || (d_rgb && !capacity))
         return fail(MPC_ERR_ARGUMENT, "null argument");
     if (n_frames < 1) return fail(MPC_ERR_ARGUMENT, "n_frames must be at least 1");
     if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback");
@@ -1185,6 +1235,7 @@ mpc_status decode_sequence(mpc_context* c, const uint8_t* const* bytes, const si
         q.containers = containers;
         q.container_bytes = container_bytes;
     }
+    q.compose = compose;
     if (rgb) std::fill(rgb, rgb + n_frames, nullptr);
     const int threads = std::min(n_frames, mpc::host_thread_count());
     std::vector<std::thread> workers;
@@ -1211,6 +1262,7 @@ mpc_status decode_sequence(mpc_context* c, const uint8_t* const* bytes, const si
             container_bytes[f] = 0;
         }
     if (q.single) return fail(q.failed_status, "%s", q.failed_text.c_str());
+    if (compose) return fail(q.failed_status, "part %d: %s", compose->part_of_frame[q.failed_frame], q.failed_text.c_str());
     return fail(q.failed_status, "frame %d: %s", q.failed_frame, q.failed_text.c_str());
 }
 
@@ -1377,6 +1429,216 @@ mpc_status mpc_transcode_views_indexed(mpc_context* c, const uint8_t* const* byt
         std::vector<int> wh(2 * static_cast<size_t>(n_frames));
         return decode_sequence(c, bytes, nbytes, n_frames, nullptr, nullptr, nullptr, wh.data(), wh.data() + n_frames, false, indexes, index_bytes,
                                routes, rects.data(), flags, views, false, nullptr, nullptr, out, out_bytes);
+    });
+}
+
+// A compose (include/mpcodec.h, "compose"): the host's plan (every check that needs no device, the owner map), then per owning part
+// either the view decoder's sequence up to the gather with the paste kernel behind it (paste_on_slot) or, for pixels, the tile encode
+// into a patch of records and the same kernel; one records-to-container job on job slot 0 once every paste has finished
+mpc_status mpc_compose_indexed(mpc_context* c, const uint8_t* const* bytes, const size_t* nbytes, const uint8_t* const* indexes,
+                               const size_t* index_bytes, int n_sources, const mpc_part* parts, int n_parts, int width, int height,
+                               unsigned flags, int index_interval, uint8_t** out, size_t* out_bytes, uint8_t** index, size_t* index_out_bytes,
+                               int* routes) {
+    return guarded([&]() -> mpc_status {
+        if (!c || !parts || !out || !out_bytes || !routes || (n_sources > 0 && (!bytes || !nbytes)) || (indexes && !index_bytes))
+            return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (index_interval >= 0 && (!index || !index_out_bytes)) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (flags & ~(MPC_VIEW_PARSE_ALL | MPC_COMPOSE_DEVICE_PIXELS)) return fail(MPC_ERR_ARGUMENT, "flags 0x%x", flags);
+        if (index_interval > 0 && (index_interval < static_cast<int>(mpc::kIndexIntervalMin) || index_interval > static_cast<int>(mpc::kIndexIntervalMax)))
+            return fail(MPC_ERR_ARGUMENT, "interval %d: 0 or %u to %u", index_interval, mpc::kIndexIntervalMin, mpc::kIndexIntervalMax);
+        const unsigned every = index_interval < 0 ? 0u : index_interval ? static_cast<unsigned>(index_interval) : mpc::kIndexIntervalDefault;
+        *out = nullptr;
+        *out_bytes = 0;
+        if (index) *index = nullptr;
+        if (index_out_bytes) *index_out_bytes = 0;
+        if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback");
+        const std::vector<mpc::ComposePart> pieces = compose_parts(parts, n_parts);
+        const mpc::ComposeDevice device{c->K, c->block_size};
+        mpc::ComposePlan plan;
+        std::string why;
+        if (const int verdict = mpc::compose_plan(bytes, nbytes, n_sources, pieces.data(), n_parts, width, height, &device, plan, why); verdict != 0)
+            return fail(verdict == 1 ? MPC_ERR_BITSTREAM : MPC_ERR_ARGUMENT, "%s", why.c_str());
+        const int K = c->K, bs = c->block_size;
+        for (int p = 0; p < n_parts; ++p)
+            if (parts[p].source == -1 && parts[p].row_stride != 0 && parts[p].row_stride < 3 * static_cast<size_t>(parts[p].rect.width))
+                return fail(MPC_ERR_ARGUMENT, "part %d: row_stride %zu for %d pixels", p, parts[p].row_stride, parts[p].rect.width);
+        struct Routes {                                             // on failure nothing is returned: no part has a route
+            int* at;
+            int n;
+            bool keep = false;
+            ~Routes() {
+                if (!keep) std::fill(at, at + n, -1);
+            }
+        } told{routes, n_parts};
+        std::fill(routes, routes + n_parts, -1);
+        // the destination's quantiser table: source 0's header values, which the tile encode of a pixel part quantises with as well
+        std::vector<double> table;
+        if (n_sources > 0)
+            for (int ch = 0; ch < 3; ++ch)
+                for (int i = 0; i < K; ++i) table.push_back(static_cast<double>(plan.sources[0].quant[ch][i]));
+        const double* quant = n_sources > 0 ? table.data() : nullptr;                // null: the context's, as its encoder writes them
+        std::lock_guard<std::recursive_mutex> one_host_call(c->host_calls);
+        HIP_TRY(hipSetDevice(c->device));
+        const Tuning tuning = read_tuning();
+        for (int k = 0; k < mpc_context::kSeqSlots; ++k)
+            if (c->jobs[k] && c->jobs[k]->stage != 0) return fail(MPC_ERR_ARGUMENT, "container job slot %d is busy", k);
+        if (!c->jobs[0]) c->jobs[0] = std::make_unique<JobSlot>();
+        JobSlot& js = *c->jobs[0];
+        ContainerJob& job = js.job;
+        if (!job.phase1) {
+            HIP_TRY(hipEventCreateWithFlags(&job.phase1, hipEventDisableTiming | hipEventBlockingSync));
+            HIP_TRY(hipEventCreateWithFlags(&job.done, hipEventDisableTiming | hipEventBlockingSync));
+        }
+        // the destination's records and the owner map: every word of the records is written exactly once, by its tile's owner.  They,
+        // the pixel parts' pixels and their patches of records live in one grow-only buffer of the context: free in steady state
+        const size_t tiles = plan.owner.size(), n_tc = 3 * tiles;
+        const bool upload = !(flags & MPC_COMPOSE_DEVICE_PIXELS);
+        struct Patch {
+            uint8_t* d_rgb = nullptr;
+            uint16_t* d_counts = nullptr;
+            mpc_basis_choice* d_choices = nullptr;
+        };
+        std::vector<Patch> patches(static_cast<size_t>(n_parts));
+        ComposeTarget to;
+        int32_t* d_owner = nullptr;
+        const auto layout = [&](char* base) {
+            Carve cv{base};
+            to.d_counts = cv.take<uint16_t>(n_tc + 2);
+            to.d_choices = cv.take<uint32_t>(n_tc * static_cast<size_t>(K));
+            d_owner = cv.take<int32_t>(tiles + 1);                  // behind the map the pixel parts' error word
+            for (int p = 0; p < n_parts; ++p) {
+                const mpc::ComposePart& piece = plan.parts[static_cast<size_t>(p)];
+                if (piece.source != -1 || !plan.owns[static_cast<size_t>(p)]) continue;
+                Patch& patch = patches[static_cast<size_t>(p)];
+                const size_t patch_tc = 3 * static_cast<size_t>((piece.w + bs - 1) / bs) * static_cast<size_t>((piece.h + bs - 1) / bs);
+                if (upload) patch.d_rgb = cv.take<uint8_t>(3 * static_cast<size_t>(piece.w) * static_cast<size_t>(piece.h));
+                patch.d_counts = cv.take<uint16_t>(patch_tc + 2);
+                patch.d_choices = cv.take<mpc_basis_choice>(patch_tc * static_cast<size_t>(K));
+            }
+            return cv.at;
+        };
+        if (const mpc_status gs = c->compose_dev.reserve(layout(nullptr), "compose staging"); gs != MPC_OK) return gs;
+        layout(c->compose_dev.data());
+        if (!c->compose_side) HIP_TRY(hipStreamCreateWithFlags(&c->compose_side, hipStreamNonBlocking));
+        struct Side {                                               // the pixel parts' stream, later the job's: drained whatever happens
+            hipStream_t s;
+            ~Side() { (void)hipStreamSynchronize(s); }
+        } side{c->compose_side};
+        plan.owner.push_back(0);                                    // the error word, cleared
+        HIP_TRY(hipMemcpy(d_owner, plan.owner.data(), sizeof(int32_t) * (tiles + 1), hipMemcpyHostToDevice));
+        int* d_error = d_owner + tiles;                             // no encoder writes a count above K
+        to.d_owner = d_owner;
+        to.tiles_x = plan.tiles_x;
+        to.tiles_y = plan.tiles_y;
+        to.parts = plan.parts.data();
+        // pixel parts: a frame of their own through the tile encode, on the side stream beside the container parts
+        for (int p = 0; p < n_parts; ++p) {
+            const mpc::ComposePart& piece = plan.parts[static_cast<size_t>(p)];
+            if (piece.source != -1 || !plan.owns[static_cast<size_t>(p)]) continue;
+            const Patch& patch = patches[static_cast<size_t>(p)];
+            const size_t row = 3 * static_cast<size_t>(piece.w), stride = parts[p].row_stride ? parts[p].row_stride : row;
+            if (upload) HIP_TRY(hipMemcpy2DAsync(patch.d_rgb, row, parts[p].rgb, stride, row, static_cast<size_t>(piece.h), hipMemcpyHostToDevice, side.s));
+            const int ptx = (piece.w + bs - 1) / bs, pty = (piece.h + bs - 1) / bs;
+            if (const mpc_status es = mpc_encode_tiles_device(c, upload ? patch.d_rgb : parts[p].rgb, piece.w, piece.h, upload ? row : stride, 0, pty,
+                                                              quant, patch.d_counts, patch.d_choices, nullptr, nullptr, 0, side.s);
+                es != MPC_OK)
+                return es;
+            if (const int e = mpc::launch_paste_records(patch.d_counts, reinterpret_cast<const uint32_t*>(patch.d_choices), ptx, pty, 0, 0, ptx, pty, K,
+                                                        to.d_counts, to.d_choices, to.tiles_x, to.tiles_y, piece.dx / bs, piece.dy / bs, to.d_owner, p,
+                                                        d_error, side.s);
+                e != 0)
+                return launch_failed(e);
+            routes[p] = 2;
+        }
+        // container parts that own a tile: the frames of one sequence on the decode slots, in part order
+        std::vector<int> part_of_frame;
+        for (int p = 0; p < n_parts; ++p)
+            if (plan.parts[static_cast<size_t>(p)].source >= 0 && plan.owns[static_cast<size_t>(p)]) part_of_frame.push_back(p);
+        const int n_frames = static_cast<int>(part_of_frame.size());
+        mpc_status st = MPC_OK;
+        if (n_frames > 0) {
+            const size_t n = static_cast<size_t>(n_frames);
+            std::vector<const uint8_t*> f_bytes(n), f_index(n, nullptr);
+            std::vector<size_t> f_nbytes(n), f_index_bytes(n, 0);
+            std::vector<mpc_rect> f_rects(n);
+            std::vector<mpc_view> f_views(n);
+            std::vector<int> f_routes(n, 1), wh(2 * n);
+            for (size_t f = 0; f < n; ++f) {
+                const mpc::ComposePart& piece = plan.parts[static_cast<size_t>(part_of_frame[f])];
+                f_bytes[f] = bytes[piece.source];
+                f_nbytes[f] = nbytes[piece.source];
+                if (indexes && indexes[piece.source]) {
+                    f_index[f] = indexes[piece.source];
+                    f_index_bytes[f] = index_bytes[piece.source];
+                }
+                f_rects[f] = mpc_rect{piece.x, piece.y, piece.w, piece.h};
+                f_views[f] = mpc_view{f_rects[f], 0, 0};
+            }
+            to.part_of_frame = part_of_frame.data();
+            st = decode_sequence(c, f_bytes.data(), f_nbytes.data(), n_frames, nullptr, nullptr, nullptr, wh.data(), wh.data() + n, false,
+                                 f_index.data(), f_index_bytes.data(), f_routes.data(), f_rects.data(), flags & MPC_VIEW_PARSE_ALL, f_views.data(),
+                                 false, nullptr, nullptr, nullptr, nullptr, &to);
+            if (st == MPC_OK)
+                for (size_t f = 0; f < n; ++f) routes[part_of_frame[f]] = f_routes[f];
+        }
+        if (st == MPC_OK) {
+            int flag = 0;
+            HIP_TRY(hipMemcpyAsync(&flag, d_error, sizeof(int), hipMemcpyDeviceToHost, side.s));
+            HIP_TRY(hipStreamSynchronize(side.s));                  // every paste has finished: the container parts' on their slots' events
+            if (flag) st = fail(MPC_ERR_BITSTREAM, "Invalid bitstream");
+        }
+        if (st != MPC_OK) return st;
+        // records -> container on job slot 0, with the seek index from the entropy stage where one is asked for
+        Carve measure;
+        mpc::StreamArgs measured{};
+        carve_stream_buffers(measure, static_cast<long long>(tiles), K, true, &measured);
+        if (const mpc_status gs = js.dev.reserve(measure.at, "device staging"); gs != MPC_OK) return gs;
+        GrowBuffer host_stage(GrowBuffer::kPinned);                 // the host route's, should the frame take it: this call's own
+        job.side = job.down = side.s;
+        job.spin = true;
+        job.host_stage = &host_stage;
+        job.host_offset = 0;
+        job.index_interval = every;
+        job.index_expanded = every != 0;
+        struct Unhook {                                             // the slot is left as mpc_container_job_begin expects it
+            ContainerJob& job;
+            ~Unhook() {
+                job.host_stage = nullptr;
+                job.index_interval = 0;
+                job.index_expanded = false;
+                job.index.clear();
+            }
+        } unhook{job};
+        EntropyBuffers eb;
+        if (!tuning.host_entropy)
+            if (const mpc_status es = entropy_buffers(js.ent, tiles, K, &eb, every ? 2 : 0); es != MPC_OK) return es;
+        HIP_TRY(hipStreamSynchronize(nullptr));                     // a slot carved for another geometry clears its tables on the null stream
+        if (const mpc_status bs_ = container_begin(job, c, tuning.host_entropy ? nullptr : &eb, tuning.triple_limit, js.dev.data(), to.d_counts,
+                                                   to.d_choices, nullptr, nullptr, width, height, quant);
+            bs_ != MPC_OK)
+            return bs_;
+        if (const mpc_status ts = container_tables(job); ts != MPC_OK) return ts;
+        uint8_t* made = nullptr;
+        size_t made_bytes = 0;
+        if (const mpc_status cs = container_collect(job, &made, &made_bytes); cs != MPC_OK) return cs;
+        if (hipStreamSynchronize(side.s) != hipSuccess) {
+            std::free(made);
+            return fail(MPC_ERR_HIP, "the container job failed: %s", hipGetErrorString(hipGetLastError()));
+        }
+        if (every) {
+            uint8_t* copy = job.index.empty() ? nullptr : static_cast<uint8_t*>(std::malloc(job.index.size()));
+            if (!copy) {
+                std::free(made);
+                return fail(MPC_ERR_ALLOC, "no seek index");
+            }
+            std::memcpy(copy, job.index.data(), job.index.size());
+            *index = copy;
+            *index_out_bytes = job.index.size();
+        }
+        *out = made;
+        *out_bytes = made_bytes;
+        told.keep = true;
+        return MPC_OK;
     });
 }
 

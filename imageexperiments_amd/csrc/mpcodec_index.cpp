@@ -245,6 +245,19 @@ mpc_status mpc_transcode_container(const uint8_t* bytes, size_t nbytes, const mp
     });
 }
 
+mpc_status mpc_compose_container(const uint8_t* const* bytes, const size_t* nbytes, int n_sources, const mpc_part* parts, int n_parts,
+                                 int width, int height, uint8_t** out, size_t* out_bytes) {
+    return guarded([&]() -> mpc_status {
+        if (!bytes || !nbytes || !parts || !out || !out_bytes) return fail(MPC_ERR_ARGUMENT, "null argument");
+        const std::vector<mpc::ComposePart> pieces = compose_parts(parts, n_parts);
+        std::vector<uint8_t> made;
+        std::string why;
+        const int verdict = mpc::compose_container(bytes, nbytes, n_sources, pieces.data(), n_parts, width, height, made, why);
+        if (verdict != 0) return fail(verdict == 1 ? MPC_ERR_BITSTREAM : MPC_ERR_ARGUMENT, "%s", why.c_str());
+        return give_blob(made, out, out_bytes);
+    });
+}
+
 mpc_status mpc_parse_container_view_by_index(const uint8_t* bytes, size_t nbytes, const uint8_t* index, size_t index_bytes,
                                              const mpc_view* view, unsigned flags, uint16_t** symbols, size_t* n_symbols, uint64_t* ranges,
                                              int* route) {

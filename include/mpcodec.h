@@ -765,6 +765,81 @@ mpc_status mpc_crop_records_device(mpc_context* ctx, const uint16_t* d_counts, c
                                    const mpc_rect* rect, int steps, uint16_t* d_out_counts, mpc_basis_choice* d_out_choices, void* stream);
 mpc_status mpc_crop_records_check(mpc_context* ctx, void* stream);
 
+/* ---- compose: a container from rectangles of containers and pixels ("Compose") ----
+ * The inverse of the transcode, from the same two facts: the container of an image assembled from tile-aligned pieces is a pure function
+ * of the pieces' records.  Untouched tiles see no pixel, no pursuit and no second loss.
+ *
+ * mpc_compose_container: host only, no context; it defines what the device route computes.  The result (mpc_free) is the container of a
+ * width x height frame with the K, block size b and 3K u16 quantiser values of source 0.  Parts are applied in order and a later part
+ * wins a tile: a tile's OWNER is the last part whose destination grid holds it, and destination tile (dtx0 + i) * tiles_y + (dty0 + j)
+ * takes the counts and records of the owner's source tile (stx0 + i) * src_tiles_y + (sty0 + j).  The streams are assembled in the
+ * destination's tile order and written by the one host coder: step-0 sums are difference coded from zero again, packed-or-not and
+ * Huffman-or-Golomb are chosen again.  No dictionary is involved, and mpc_truncate_container's caveat about step-0 sums that move by
+ * 2^15 or more from tile to tile is inherited.  Checks, in this order, the first failure wins:
+ *   1. arguments that need no container, MPC_ERR_ARGUMENT: null pointers, n_parts < 1, width or height < 1, n_sources < 0, a `source`
+ *      outside [-1, n_sources), a pixel part ("part N: pixels need a device": the host computes no tiles), n_sources == 0.
+ *   2. every source's header, named by a part or not: what the header parse of mpc_container_info refuses is MPC_ERR_BITSTREAM
+ *      "source N: Invalid input data"; a K, block size or one of the 3K u16 quantiser values that is not source 0's is MPC_ERR_ARGUMENT
+ *      "source N: ...".  A container holds one quantiser table.
+ *   3. every part's geometry, MPC_ERR_ARGUMENT "part N: ...": rect passes mpc_transcode_container's checks on its source; x % b == 0,
+ *      y % b == 0, x + w <= width, y + h <= height (in 64 bits); and per axis the rectangle's far edge is a multiple of b, or it is the
+ *      source frame's own ragged edge AND lands on the destination's own edge (x + w == width).  A ragged tile carries its zero fill and
+ *      is the encode of pasted pixels only where the destination is ragged in the same way.
+ *   4. coverage: every destination tile has an owner, else MPC_ERR_ARGUMENT naming the first uncovered tile in tile order.
+ *   5. every source that an OWNING part names is parsed with mpc_read_compressed: what that refuses is MPC_ERR_BITSTREAM "part N: Invalid
+ *      input data", a length above K anywhere in the source "part N: Invalid bitstream", N the lowest failing owning part.  A part that
+ *      owns no tile is not read beyond its header: a body damaged only there changes nothing.
+ * Consequences: one whole-frame part is what coding the parsed container again gives, for an encoder's container the input itself;
+ * composing the tile-aligned pieces of a source that mpc_transcode_container cut gives the source; compose and transcode commute (a
+ * rectangle of a composition is the composition of the rectangles); and containers encoded from pixels with one integral quantiser
+ * table (those of mpc_quant_tables are integral) give, byte for byte, mpc_encode_image of the pasted pixels. */
+typedef struct mpc_part {
+    int source;          /* >= 0: bytes[source] is a container and `rect` a rectangle of it, (0,0,0,0) = all of it;  -1: pixels */
+    mpc_rect rect;       /* source == -1: x = y = 0, width x height of the pixels */
+    int x, y;            /* where the rectangle's top-left lands in the destination */
+    const uint8_t* rgb;  /* source == -1 only: pixel (i, j) is the 3 bytes at rgb + j * row_stride + 3 * i */
+    size_t row_stride;   /* 0 = 3 * width, else >= 3 * width */
+} mpc_part;
+mpc_status mpc_compose_container(const uint8_t* const* bytes, const size_t* nbytes, int n_sources, const mpc_part* parts, int n_parts,
+                                 int width, int height, uint8_t** out, size_t* out_bytes);
+/* The paste kernel (mp_paste_records_kernel) on the caller's records.  Both sides are whole-frame records (t = tx * tiles_y + ty,
+ * counts[t * 3 + ch], choices[(t * 3 + ch) * K + i], K the context's).  For every tile of src_rect's grid ((0,0,0,0) = the whole source)
+ * the destination tile at the same offset from (dst_x, dst_y) gets its three counts and 3K record words: records below the count are
+ * copied, the steps from the count to K are written as zero, so garbage behind a source count is never carried over.  d_owner: NULL, or
+ * one int32 per destination tile in destination order; a tile is then written only where d_owner[t] == part.  Everything else in the
+ * destination stays as it was.  The geometry rules are those of check 3 above with b the context's block size, checked on the host
+ * before anything is enqueued; every address comes from the two grids, never from a record.  A count above K is used as K and sets the
+ * context's crop error word (mpc_crop_records_check reads and clears it).  Asynchronous on `stream`; source and destination must not
+ * overlap.  Pastes that share an owner map write disjoint tiles: they may run on different streams in any order. */
+mpc_status mpc_paste_records_device(mpc_context* ctx, const uint16_t* d_src_counts, const mpc_basis_choice* d_src_choices, int src_width,
+                                    int src_height, const mpc_rect* src_rect, uint16_t* d_dst_counts, mpc_basis_choice* d_dst_choices,
+                                    int dst_width, int dst_height, int dst_x, int dst_y, const int32_t* d_owner, int part, void* stream);
+/* mpc_compose_indexed: the bytes, statuses and error texts of mpc_compose_container from the device, in which every pixel part stands
+ * for "the container this context's mpc_encode_image makes of those pixels with the destination's quantiser table".  indexes /
+ * index_bytes are per source; an entry or the whole array may be NULL.  The quantiser table is source 0's u16 values as doubles; with
+ * n_sources == 0 it is the context's tables as its encoder writes them into a header, and the call is an encode from patches.
+ *   container parts  the view decoder's sequence up to the gather on the decode slots, the part's rectangle as the view's: route 0 with a
+ *                    usable index of version 1 or 2, else route 1.  MPC_VIEW_PARSE_ALL and what is trusted without it are the views',
+ *                    word for word.  Behind the gather the paste kernel writes from the slot's records straight into the call's
+ *                    destination records, after the slot's error words have been read.  A route-0 part the device refuses starts over
+ *                    on route 1.
+ *   pixel parts      uploaded unless MPC_COMPOSE_DEVICE_PIXELS says the rgb pointers are device memory; mpc_encode_tiles_device over all
+ *                    their tile rows with the destination's quantiser table and the context's flavour (a fast context pursues in
+ *                    float); the patch is a frame of its own and is pasted with the same kernel.
+ *   parts that own no tile are skipped entirely.  routes[p]: 0 or 1 for a container part, 2 for pixels, -1 for a skipped part.
+ * When every paste has finished, one records-to-container job on job slot 0 makes the container.  The context's container job slots must
+ * all be idle (else MPC_ERR_ARGUMENT), and they are left idle.  Parts overlap on the decode slots as a transcode's frames do; the result
+ * depends neither on the number of slots nor on the order in which parts finish.
+ *   index_interval < 0: no index, and `index` may be NULL.  Otherwise the interval rules of mpc_container_index (0 = the default), and
+ *   *index (mpc_free) is byte for byte mpc_container_index2(out, ..., interval, MPC_INDEX_EXPANDED), made by the entropy stage.
+ * A K or block size that is not the context's is MPC_ERR_ARGUMENT, reported behind the header checks; a host-only context is
+ * MPC_ERR_NO_DEVICE.  On failure nothing is returned and the context stays usable. */
+#define MPC_COMPOSE_DEVICE_PIXELS 2u     /* the rgb pointers of pixel parts are device memory */
+mpc_status mpc_compose_indexed(mpc_context* ctx, const uint8_t* const* bytes, const size_t* nbytes, const uint8_t* const* indexes,
+                               const size_t* index_bytes, int n_sources, const mpc_part* parts, int n_parts, int width, int height,
+                               unsigned flags, int index_interval, uint8_t** out, size_t* out_bytes, uint8_t** index,
+                               size_t* index_out_bytes, int* routes /* [n_parts] */);
+
 /* ---- "-s" patch statistics, Compression.cpp:200-302 ----
  * The reference seeds one std::mt19937, and for every image draws `patches` origins x = rand() % (width - bs),
  * y = rand() % (height - bs), runs CalcMPDynamic on the Y, U and V patch with every quantiser 1.0 and feeds
