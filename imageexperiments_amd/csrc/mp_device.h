@@ -71,12 +71,24 @@ struct Workspace {
     int max_chunks;
 };
 
+// A launch over a few frames that lie anywhere (the frame pipeline's groups): frame f of the launch is read at rgb[f] and its tile
+// `tile` (stripe order) writes record first[f] + tile.  n == 0: the strided form (rgb + f * frame_stride, records back to back).
+// The kernel reads either form in its refill as PursuitArgs::frame_rgb / frame_first; with a table the records are in stripe
+// order (out_tile_rows == 0).
+constexpr int kFrameTable = 4;
+struct FrameTable {
+    int n;
+    int first[kFrameTable];
+    const uint8_t* rgb[kFrameTable];
+};
+
 struct FrameInput {
     const uint8_t* rgb;              // device, row-major, 3 B/pixel (img::image<rgb>, image.h:123-131)
     int width, height;
     long long row_stride;
     int frames;
     long long frame_stride;
+    FrameTable table;                // n != 0: n == frames, and rgb / frame_stride are not read
     int tile_row_begin, tile_rows, tiles_x;
     int out_tile_rows;               // 0: records in stripe order (tile tx * tile_rows + ty - tile_row_begin); > 0: in the order of a
                                      // whole frame of this many tile rows (tx * out_tile_rows + ty): stripes encoded one by one
@@ -181,12 +193,14 @@ struct PursuitArgs {
     // switch), so a channel's last long tile-channels drain beside the next channel's work instead of beside idle SIMDs.
     int workgroups;
     // input: tile mode (rgb) or vector mode (vec_in != nullptr: CalcMPDynamic on caller vectors of channel vec_channel)
-    const uint8_t* rgb;
+    const uint8_t* frame_rgb[kFrameTable];   // frame f at frame_rgb[min(f, kFrameTable - 1)] + f * frame_stride ...
+    int frame_first[kFrameTable];            // ... and its records moved by frame_first[min(f, kFrameTable - 1)]: FrameInput::table, or
+                                             // the strided form (one base, no offsets)
     int width, height;
     long long row_stride, frame_stride;
     int tile_row_begin, tile_rows, tiles_x;
     int out_tile_rows;               // FrameInput::out_tile_rows
-    int rgb_aligned8;                // rgb, row_stride and frame_stride are multiples of 8: whole tiles are read as 8-byte words
+    int rgb_aligned8;                // every frame's base, row_stride and frame_stride are multiples of 8: whole tiles are read as 8-byte words
     const double* vec_in;
     int vec_channel;
     long long n_tc[3];               // tile-channels of each channel (tiles of the stripe x frames; vector mode: only vec_channel's is not 0)

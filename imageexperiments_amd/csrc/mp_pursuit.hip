@@ -526,7 +526,12 @@ __global__ __launch_bounds__(64 * kWaves, kWaves / 4) void mp_pursuit_kernel(con
                 const int tile = (int)(ts - (long long)frame * tiles_per_frame);
                 const int tx = tile / a.tile_rows, ty = a.tile_row_begin + (tile - tx * a.tile_rows);
                 if (a.out_tile_rows > 0) s.t = (frame * a.tiles_x + tx) * a.out_tile_rows + ty;      // the records' place in a whole frame
-                const uint8_t* img = a.rgb + (long long)frame * a.frame_stride;
+                // the frame's pixels and the place of its records: a launch over a few frames that lie anywhere (FrameTable) gives each
+                // its own base and record offset with a frame stride of 0, a strided launch the same base and no offset for all.
+                // Selects, not an indexed read of the arguments.
+                const bool f1 = frame == 1, f2 = frame == 2, f3 = frame >= 3;
+                const uint8_t* img = (f3 ? a.frame_rgb[3] : (f2 ? a.frame_rgb[2] : (f1 ? a.frame_rgb[1] : a.frame_rgb[0]))) + (long long)frame * a.frame_stride;
+                s.t += f3 ? a.frame_first[3] : (f2 ? a.frame_first[2] : (f1 ? a.frame_first[1] : a.frame_first[0]));
                 unsigned char px[16][3];
                 // the lane's 16 pixels are two rows of 8 (24 bytes each, at 24 tx: 8-byte aligned when the rows are).  Whole tiles
                 // of an 8-byte aligned image take them as six 8-byte loads; ragged edges and odd strides byte by byte, clamped

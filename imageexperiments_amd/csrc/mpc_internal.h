@@ -80,18 +80,25 @@ constexpr unsigned kTripleCap = 1u << 20;              // (symbol, count, first 
 //   MPC_SEQ_WORKGROUPS            seq_workgroups   pursuit workgroups of a frame sequence (7/8 of the CUs; 0 = all)
 //   MPC_SIDE_PRIORITY             side_priority    the frame pipeline's side streams outrank its pursuits (on)
 //   MPC_SHARED_SIDE_STREAMS       shared_sides     two side streams shared by all slots (on)
-//   MPC_LAG_ASSEMBLY              lag_assembly     pursuit(f) waits for assembly + phase 1 of frame f - this (2)
-//   MPC_LAG_PHASE2                lag_phase2       ... and for phase 2 of frame f - this (3)
+//   MPC_SEQ_GROUP                 seq_group        frames of a sequence that share one pursuit launch, 1 .. 3 (kSeqGroupDevice / kSeqGroupHost)
+//   MPC_LAG_ASSEMBLY              lag_assembly     launch(g) waits for assembly + phase 1 of the frames of launch g - this (2)
+//   MPC_LAG_PHASE2                lag_phase2       ... and for phase 2 of the frames of launch g - this (3)
 //   MPC_SINGLE_STRIPES            single_stripes   row stripes of a single host frame (1 below 32 MB, 3, 4 from 80 MB)
 //   MPC_HOST_ENTROPY=1            host_entropy     the entropy stage on the host
 //   MPC_ENTROPY_TRIPLES           triple_limit     distinct symbols per frame above which a frame takes the host route (2^20)
 //   MPC_TRACE=1                   trace            per-frame time stamps of the pipeline and the decoder on stderr
 // MPC_HOST_THREADS (worker threads of the host's table building and parsing) is read by host_pool.cpp (host_thread_count).
+// frames per pursuit launch of a sequence.  Device frames at 4928x3264: 1 / 2 / 3 -> 5 287 / 5 347 / 4 597 Mpix/s
+// (three per launch leave the six slots two groups); host frames -> bytes: 4 879 / 4 826 Mpix/s with 1 / 2 (a launch waits for all
+// its uploads)
+constexpr int kSeqGroupDevice = 2;
+constexpr int kSeqGroupHost = 1;
 struct Tuning {
     bool steps_path = false, side_priority = true, host_entropy = false, trace = false;
     int pipes = 0, workgroups = 0, single_stripes = 0;          // > 0: forced
     int seq_workgroups = -1, shared_sides = -1;                 // >= 0: forced
     int lag_assembly = 2, lag_phase2 = 3;
+    int seq_group = 0;                                          // > 0: forced
     long long max_batch = kMaxBatchDefault;
     unsigned triple_limit = kTripleCap;
 };
@@ -435,9 +442,10 @@ mpc_status call_quant(mpc_context* c, const double* quant, hipStream_t s, const 
 mpc_status ensure_workspace(mpc_context* c, const Tuning& t, long long tile_channels);
 // whole_frame_order: the records go where one launch over the whole frame would put them (FrameInput::out_tile_rows) and the
 // caller has zeroed d_choices for the whole frame (stripes of one frame encoded one by one, encode_sequence's single frames)
+// table: the frames of the launch lie anywhere and so do their records in d_counts / d_choices (mpc::FrameTable)
 mpc_status encode_batch_device(mpc_context* c, const Tuning& t, const uint8_t* d_rgb, int frames, size_t frame_stride, int width,
                                int height, size_t row_stride, int tile_row_begin, int tile_row_end, const double* quant,
                                uint16_t* d_counts, mpc_basis_choice* d_choices, double* d_energy, uint32_t* d_swept, void* stream,
-                               bool whole_frame_order);
+                               bool whole_frame_order, const mpc::FrameTable* table = nullptr);
 
 #pragma GCC visibility pop

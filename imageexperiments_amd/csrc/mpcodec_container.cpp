@@ -402,14 +402,12 @@ mpc_status encode_sequence(mpc_context* c, const uint8_t* const* frames, bool on
     std::lock_guard<std::recursive_mutex> one_host_call(c->host_calls);
     HIP_TRY(hipSetDevice(c->device));
     const size_t img_bytes = static_cast<size_t>(3) * width * height;
-    // device slot: [image] | counts | records | stream assembly;  host slot: [image] | the host route's counts, offsets, symbols
+    // device slot: [image] | stream assembly;  host slot: [image] | the host route's counts, offsets, symbols.  The slots' counts
+    // and records lie in front of the device slots as two arrays [slot][record]: a launch over a group of frames addresses
+    // every frame's records by one record index (mpc::FrameTable)
     Carve dev, host;
     (void)dev.take<uint8_t>(on_device ? 0 : img_bytes);
     (void)host.take<uint8_t>(on_device ? 0 : img_bytes);
-    const size_t counts_at = dev.at;
-    (void)dev.take<uint16_t>(n_tc);
-    const size_t choices_at = dev.at;
-    (void)dev.take<mpc_basis_choice>(n_tc * K);
     const size_t streams_at = dev.at;
     mpc::StreamArgs measured{};
     carve_stream_buffers(dev, static_cast<long long>(tiles), K, true, &measured);
@@ -420,8 +418,14 @@ mpc_status encode_sequence(mpc_context* c, const uint8_t* const* frames, bool on
     // a sequence gets every slot's buffers at once: a later, longer call then finds them (allocating pinned memory takes
     // tens of milliseconds)
     const size_t alloc_slots = n_frames > 1 ? S : 1;
+    Carve records;
+    const size_t counts_at = records.at;
+    (void)records.take<uint16_t>(alloc_slots * n_tc);
+    const size_t choices_at = records.at;
+    (void)records.take<mpc_basis_choice>(alloc_slots * n_tc * K);
+    const size_t slots_at = records.at;
     if (const mpc_status gs = c->host_stage.reserve(alloc_slots * host_slot, "pinned staging"); gs != MPC_OK) return gs;
-    if (const mpc_status gs = c->stage.reserve(alloc_slots * dev_slot, "device staging"); gs != MPC_OK) return gs;
+    if (const mpc_status gs = c->stage.reserve(slots_at + alloc_slots * dev_slot, "device staging"); gs != MPC_OK) return gs;
     if (!c->seq_up) {
         // The side streams at the highest priority, the pursuits' at the lowest: CUs a pursuit gives up at its end go to the
         // waiting chains of small kernels before the next pursuit's workgroups (MPC_SIDE_PRIORITY=0: all equal).  Measured at
@@ -458,10 +462,10 @@ mpc_status encode_sequence(mpc_context* c, const uint8_t* const* frames, bool on
     // The pipeline's streams.  `seq_compute`: the pursuits, one behind the other.  Side stream A: behind pursuit(f) (an event) the
     // stream assembly and entropy phase 1 of frame f.  Side stream B: phase 2 and the container's copy of frame f, enqueued by the
     // frame's worker once it has built the code tables from phase 1's statistics (mapped host memory written by the kernels
-    // themselves; the host waits on events only).  Pursuit(f) waits (events) for the assembly + phase 1 of frame f - 2 and for
-    // the phase 2 of frame f - 3, so nothing piles up; with the CUs the pursuits leave free (above) both chains run beside the
-    // pursuits of the following frames.  The shapes this replaced -- everything on one ordered queue; phase 2 alone on a side
-    // stream -- are in DESIGN.md 4 and 9.
+    // themselves; the host waits on events only).  A pursuit launch covers a group of frames (below); launch L waits (events) for
+    // the assembly + phase 1 of the frames of launch L - 2 and for the phase 2 of those of launch L - 3, so nothing piles up; with
+    // the CUs the pursuits leave free (above) both chains run beside the pursuits of the following frames.  The shapes this
+    // replaced -- everything on one ordered queue; phase 2 alone on a side stream -- are in DESIGN.md 4 and 9.
     hipStream_t pursuit_stream = c->seq_compute;
     // Two side streams for all slots (MPC_SHARED_SIDE_STREAMS=0: one per slot): the runtime maps streams onto a handful
     // of hardware queues, and a slot stream that lands on the pursuit stream's queue lines its kernels up behind the next
@@ -513,7 +517,9 @@ mpc_status encode_sequence(mpc_context* c, const uint8_t* const* frames, bool on
         const hipError_t e_ = (call);                                                             \
         if (e_ != hipSuccess) { st = fail(MPC_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); break; } \
     }
-    auto dev_slot_base = [&](size_t sl) { return c->stage.data() + sl * dev_slot; };
+    auto dev_slot_base = [&](size_t sl) { return c->stage.data() + slots_at + sl * dev_slot; };
+    uint16_t* const all_counts = reinterpret_cast<uint16_t*>(c->stage.data() + counts_at);
+    mpc_basis_choice* const all_choices = reinterpret_cast<mpc_basis_choice*>(c->stage.data() + choices_at);
     auto host_slot_base = [&](size_t sl) { return c->host_stage.data() + sl * host_slot; };
     // Host frames: frame g is copied into its slot's pinned image by a few threads and sent to the device while frame g - 1 is
     // still being enqueued and encoded; its pursuit waits for the event behind the copy.
@@ -543,29 +549,40 @@ mpc_status encode_sequence(mpc_context* c, const uint8_t* const* frames, bool on
                                                     : (img_bytes >= (size_t(80) << 20) ? 4 : (img_bytes >= (size_t(32) << 20) ? 3 : 1));
     const bool striped_single = single && !on_device && single_stripes > 1 && tiles_y >= 4 * single_stripes && !t.steps_path;
     if (!on_device && !striped_single) start_upload(0);
-    for (int f = 0; f < n_frames && st == MPC_OK; ++f) {
-        const int sl = f % static_cast<int>(slots);
-        Pending& slot = pending[sl];
-        collect(slot);                    // frame f - slots is done with this slot: its download and its entropy stage have finished
+    // Frames f .. f + gn - 1 share one pursuit launch (MPC_SEQ_GROUP): the kernel runs them as one batch -- one queue per channel
+    // over all of them -- so the prologue (144 KiB of LDS per workgroup), the tail in which the CUs run dry and the gap between two
+    // launches are paid once per group.  Everything behind the launch stays per frame.  A single frame and the step-synchronous
+    // cross-check path launch frame by frame.
+    const int n_slots = static_cast<int>(slots);
+    const int want_group = t.seq_group > 0 ? t.seq_group : (on_device ? kSeqGroupDevice : kSeqGroupHost);
+    const int G = (single || t.steps_path) ? 1 : std::min({want_group, n_slots, mpc::kFrameTable});
+    for (int f = 0, gn = 1; f < n_frames && st == MPC_OK; f += gn) {
+        gn = std::min(G, n_frames - f);
+        const int sl = f % n_slots;
+        // frame f + k - slots is done with its slot: its download and its entropy stage have finished
+        for (int k = 0; k < gn; ++k) collect(pending[(f + k) % n_slots]);
         if (st != MPC_OK) break;
         // how far the pursuits may run ahead of the small kernels behind them: pursuit(f) waits for the stream assembly + phase 1
         // of frame f - lag_assembly and for the phase 2 of frame f - lag_phase2.  Measured (tools/ab_env_bench.sh, 4928x3264)
         // while the pursuits still filled every CU: lags 2 / 3 -> 4 660 Mpix/s, 3 / 3 -> 4 610 - 4 690, 3 / 4 -> 4 000 - 4 300,
         // 4 / 5 -> 4 090 - 4 680 (more slack let the chains of several frames pile up in front of one pursuit's end); with CUs
         // left free for the chains 2 / 2, 2 / 3 and 3 / 4 are within 1 % of each other.
-        const int back = t.lag_phase2;
-        if (f >= back && phase2_enqueued[(f - back) % static_cast<int>(slots)].valid()) {
-            // frame f - back's phase 2 is on its slot's stream by now: this frame's pursuit starts behind it (the event is the one
+        // The lags count launches: launch L = f / G covers the frames L * G ... (the last one of a call may be short).  A lag
+        // that reaches back further than the slots do meets slots that were collected above: their events are old, the waits empty.
+        const int launch = f / G;
+        for (int p = (launch - t.lag_phase2) * G; p >= 0 && p < (launch - t.lag_phase2 + 1) * G && st == MPC_OK; ++p) {
+            if (!phase2_enqueued[p % n_slots].valid()) continue;
+            // frame p's phase 2 is on its slot's stream by now: this launch starts behind it (the event is the one
             // its worker recorded behind the container's copy; on the host route it is an old one and the wait is empty)
-            phase2_enqueued[(f - back) % static_cast<int>(slots)].get();
-            MPC_SEQ_TRY(hipStreamWaitEvent(pursuit_stream, c->seq_events[(f - back) % static_cast<int>(slots)][2], 0));
+            phase2_enqueued[p % n_slots].get();
+            MPC_SEQ_TRY(hipStreamWaitEvent(pursuit_stream, c->seq_events[p % n_slots][2], 0));
         }
-        if (f >= t.lag_assembly)
-            MPC_SEQ_TRY(hipStreamWaitEvent(pursuit_stream, c->seq_events[(f - t.lag_assembly) % static_cast<int>(slots)][1], 0));
-        char* dbase = dev_slot_base(sl);
-        uint8_t* d_img = reinterpret_cast<uint8_t*>(dbase);
-        uint16_t* d_counts = reinterpret_cast<uint16_t*>(dbase + counts_at);
-        mpc_basis_choice* d_choices = reinterpret_cast<mpc_basis_choice*>(dbase + choices_at);
+        for (int p = (launch - t.lag_assembly) * G; p >= 0 && p < (launch - t.lag_assembly + 1) * G && st == MPC_OK; ++p)
+            MPC_SEQ_TRY(hipStreamWaitEvent(pursuit_stream, c->seq_events[p % n_slots][1], 0));
+        if (st != MPC_OK) break;
+        uint8_t* d_img = reinterpret_cast<uint8_t*>(dev_slot_base(sl));
+        uint16_t* d_counts = all_counts + static_cast<size_t>(sl) * n_tc;
+        mpc_basis_choice* d_choices = all_choices + static_cast<size_t>(sl) * n_tc * K;
         if (striped_single) {
             // One frame from host memory: nothing to overlap its upload with but its own tile encode.  The frame goes up in row
             // stripes and each stripe's tile encode starts behind its own copy (an event), writing its records where one launch
@@ -584,58 +601,80 @@ mpc_status encode_sequence(mpc_context* c, const uint8_t* const* frames, bool on
                                          pursuit_stream, true);
             }
         } else {
-            const uint8_t* d_rgb = frames[f];
-            if (!on_device) {
-                MPC_SEQ_TRY(uploads[sl].get());
-                MPC_SEQ_TRY(hipStreamWaitEvent(pursuit_stream, c->seq_events[sl][0], 0));
-                if (f + 1 < n_frames) start_upload(f + 1);
-                if (st != MPC_OK) break;
-                d_rgb = d_img;
+            // host frames: the launch waits for the uploads of all its frames.  The uploads follow one another: the next one of
+            // the group starts as soon as one is through, the next group's first one behind this group's launch (its slot's
+            // previous frame is the youngest still in flight; with one frame per launch, as ever, in front of it)
+            mpc::FrameTable table{};
+            for (int k = 0; k < gn && st == MPC_OK; ++k) {
+                const int ks = (f + k) % n_slots;
+                table.rgb[k] = frames[f + k];
+                table.first[k] = static_cast<int>(ks * tiles);
+                if (on_device) continue;
+                MPC_SEQ_TRY(uploads[ks].get());
+                MPC_SEQ_TRY(hipStreamWaitEvent(pursuit_stream, c->seq_events[ks][0], 0));
+                if (f + k + 1 < n_frames && (k + 1 < gn || G == 1)) start_upload(f + k + 1);
+                table.rgb[k] = reinterpret_cast<const uint8_t*>(dev_slot_base(ks));
             }
-            st = encode_batch_device(c, t, d_rgb, 1, 0, width, height, static_cast<size_t>(3) * width, 0, tiles_y, quant, d_counts,
-                                     d_choices, nullptr, nullptr, pursuit_stream, false);
+            if (st != MPC_OK) break;
+            table.n = gn;
+            for (int k = gn; k < mpc::kFrameTable; ++k) { table.rgb[k] = table.rgb[0]; table.first[k] = table.first[0]; }
+            if (single || t.steps_path)
+                st = encode_batch_device(c, t, table.rgb[0], 1, 0, width, height, static_cast<size_t>(3) * width, 0, tiles_y, quant, d_counts,
+                                         d_choices, nullptr, nullptr, pursuit_stream, false);
+            else                              // the records beyond a tile-channel's count keep what an earlier frame left there: the
+                                              // stream assembly reads min(count, K) of them (mp_streams.hip) and nothing else reads any
+                st = encode_batch_device(c, t, table.rgb[0], gn, 0, width, height, static_cast<size_t>(3) * width, 0, tiles_y, quant, all_counts,
+                                         all_choices, nullptr, nullptr, pursuit_stream, false, &table);
         }
         if (st != MPC_OK) break;
-        ContainerJob& job = jobs[sl];
-        job.side = shared_sides ? c->seq_down[0] : c->seq_down[sl];
-        job.down = shared_sides ? c->seq_down[1] : c->seq_down[sl];
-        job.phase1 = c->seq_events[sl][1];
-        job.done = c->seq_events[sl][2];
-        job.spin = single;
-        job.host_stage = &c->host_stage;
-        job.host_offset = sl * host_slot + route_at;
-        job.index_interval = index_interval;
-        job.index_expanded = index_expanded;
+        // one event behind the launch; every frame's side stream waits for it
         MPC_SEQ_TRY(hipEventRecord(c->seq_pursuit_done[sl], pursuit_stream));
-        MPC_SEQ_TRY(hipStreamWaitEvent(job.side, c->seq_pursuit_done[sl], 0));
-        st = container_begin(job, c, t.host_entropy ? nullptr : &ent[sl], t.triple_limit, dbase + streams_at, d_counts,
-                             reinterpret_cast<const uint32_t*>(d_choices), nullptr, nullptr, width, height, quant);
-        if (st != MPC_OK) break;
-        auto told = std::make_shared<std::promise<void>>();
-        phase2_enqueued[sl] = told->get_future();
-        slot.frame = f;
-        // the slot's worker: wait for the device, build the code tables, enqueue phase 2, collect the container
-        const int device = c->device;
-        const bool trace = t.trace;
-        const double t_enq = trace_ms();
-        ContainerJob* jp = &job;
-        slot.result = std::async(single ? std::launch::deferred : std::launch::async, [=]() -> std::pair<uint8_t*, size_t> {
-            struct Tell {                                      // whatever happens, the enqueuing thread is released once
-                std::shared_ptr<std::promise<void>> p;
-                bool done = false;
-                void operator()() { if (!done) p->set_value(); done = true; }
-                ~Tell() { (*this)(); }
-            } tell{told};
-            std::pair<uint8_t*, size_t> blob{nullptr, 0};
-            if (hipSetDevice(device) == hipSuccess && container_tables(*jp, [&] { tell(); }) == MPC_OK)
-                (void)container_collect(*jp, &blob.first, &blob.second);
-            if (trace) {
-                const double* e = jp->stamps;
-                std::fprintf(stderr, "[trace] frame %d enqueued %.2f | device done %.2f | symbols on host %.2f | coded %.2f | entropy: stats %.2f tables %.2f bytes %.2f\n",
-                             f, t_enq, e[0], jp->device_entropy ? e[4] : e[3], trace_ms(), e[1], e[2], e[4]);
-            }
-            return blob;
-        });
+        for (int k = 0; k < gn && st == MPC_OK; ++k) {
+            const int fr = f + k, ks = fr % n_slots;
+            Pending& slot = pending[ks];
+            ContainerJob& job = jobs[ks];
+            job.side = shared_sides ? c->seq_down[0] : c->seq_down[ks];
+            job.down = shared_sides ? c->seq_down[1] : c->seq_down[ks];
+            job.phase1 = c->seq_events[ks][1];
+            job.done = c->seq_events[ks][2];
+            job.spin = single;
+            job.host_stage = &c->host_stage;
+            job.host_offset = ks * host_slot + route_at;
+            job.index_interval = index_interval;
+            job.index_expanded = index_expanded;
+            MPC_SEQ_TRY(hipStreamWaitEvent(job.side, c->seq_pursuit_done[sl], 0));
+            st = container_begin(job, c, t.host_entropy ? nullptr : &ent[ks], t.triple_limit, dev_slot_base(ks) + streams_at,
+                                 all_counts + static_cast<size_t>(ks) * n_tc,
+                                 reinterpret_cast<const uint32_t*>(all_choices + static_cast<size_t>(ks) * n_tc * K), nullptr, nullptr, width,
+                                 height, quant);
+            if (st != MPC_OK) break;
+            auto told = std::make_shared<std::promise<void>>();
+            phase2_enqueued[ks] = told->get_future();
+            slot.frame = fr;
+            // the slot's worker: wait for the device, build the code tables, enqueue phase 2, collect the container
+            const int device = c->device;
+            const bool trace = t.trace;
+            const double t_enq = trace_ms();
+            ContainerJob* jp = &job;
+            slot.result = std::async(single ? std::launch::deferred : std::launch::async, [=]() -> std::pair<uint8_t*, size_t> {
+                struct Tell {                                      // whatever happens, the enqueuing thread is released once
+                    std::shared_ptr<std::promise<void>> p;
+                    bool done = false;
+                    void operator()() { if (!done) p->set_value(); done = true; }
+                    ~Tell() { (*this)(); }
+                } tell{told};
+                std::pair<uint8_t*, size_t> blob{nullptr, 0};
+                if (hipSetDevice(device) == hipSuccess && container_tables(*jp, [&] { tell(); }) == MPC_OK)
+                    (void)container_collect(*jp, &blob.first, &blob.second);
+                if (trace) {
+                    const double* e = jp->stamps;
+                    std::fprintf(stderr, "[trace] frame %d enqueued %.2f | device done %.2f | symbols on host %.2f | coded %.2f | entropy: stats %.2f tables %.2f bytes %.2f\n",
+                                 fr, t_enq, e[0], jp->device_entropy ? e[4] : e[3], trace_ms(), e[1], e[2], e[4]);
+                }
+                return blob;
+            });
+        }
+        if (st == MPC_OK && !on_device && !striped_single && G > 1 && f + gn < n_frames) start_upload(f + gn);
     }
 #undef MPC_SEQ_TRY
     for (auto& u : uploads)

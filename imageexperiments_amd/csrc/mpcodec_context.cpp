@@ -46,6 +46,7 @@ Tuning read_tuning() {
     t.shared_sides = env_int("MPC_SHARED_SIDE_STREAMS", -1);
     t.lag_assembly = std::min(4, std::max(2, env_int("MPC_LAG_ASSEMBLY", 2)));
     t.lag_phase2 = std::min(5, std::max(t.lag_assembly, env_int("MPC_LAG_PHASE2", 3)));
+    t.seq_group = std::min(3, std::max(0, env_int("MPC_SEQ_GROUP", 0)));
     t.single_stripes = std::min(static_cast<int>(mpc_context::kSingleStripes), env_int("MPC_SINGLE_STRIPES", 0));
     t.host_entropy = env_int("MPC_HOST_ENTROPY", 0) != 0;
     const int triples = env_int("MPC_ENTROPY_TRIPLES", 0);
@@ -379,7 +380,10 @@ mpc_status run_persistent(mpc_context* c, const Tuning& t, const mpc::FrameInput
     a.K = c->K;
     a.num_base = d.num_base;
     a.rows0 = c->dict.block_rows.empty() ? 0 : c->dict.block_rows[0];
-    a.rgb = in.rgb;
+    for (int f = 0; f < mpc::kFrameTable; ++f) {               // the strided form: one base, records back to back
+        a.frame_rgb[f] = in.rgb;
+        a.frame_first[f] = 0;
+    }
     a.width = in.width;
     a.height = in.height;
     a.row_stride = in.row_stride;
@@ -389,6 +393,17 @@ mpc_status run_persistent(mpc_context* c, const Tuning& t, const mpc::FrameInput
     a.tiles_x = in.tiles_x;
     a.out_tile_rows = in.out_tile_rows;
     a.rgb_aligned8 = (reinterpret_cast<uintptr_t>(in.rgb) % 8 == 0 && in.row_stride % 8 == 0 && (in.frames <= 1 || in.frame_stride % 8 == 0)) ? 1 : 0;
+    if (in.table.n > 0) {                                     // frames that lie anywhere: a base and a record offset each
+        a.frame_stride = 0;
+        a.rgb_aligned8 = in.row_stride % 8 == 0 ? 1 : 0;
+        const long long tiles_per_frame = static_cast<long long>(in.tiles_x) * in.tile_rows;
+        for (int f = 0; f < mpc::kFrameTable; ++f) {
+            const int k = f < in.table.n ? f : 0;
+            a.frame_rgb[f] = in.table.rgb[k];
+            a.frame_first[f] = static_cast<int>(in.table.first[k] - f * tiles_per_frame);
+            if (reinterpret_cast<uintptr_t>(in.table.rgb[k]) % 8 != 0) a.rgb_aligned8 = 0;   // one frame off the 8-byte grid: all read bytes
+        }
+    }
     a.vec_in = in.vec_in;
     a.vec_channel = in.vec_channel;
     a.queue = d.queues;
@@ -415,6 +430,7 @@ mpc_status run_pursuit(mpc_context* c, const Tuning& t, const mpc::FrameInput& i
     // MPC_PATH=steps / MPC_FILTER=0: the step-synchronous exhaustive double sweeps of mp_kernels.hip (the product's own
     // cross-check); default: the persistent kernel
     if (!t.steps_path) return run_persistent(c, t, in, out, d_quant, total_tc, stream);
+    if (in.table.n > 0) return fail(MPC_ERR_ARGUMENT, "a frame table runs on the persistent kernel only (unset MPC_PATH / MPC_FILTER)");
     if (c->fast) return fail(MPC_ERR_ARGUMENT, "the float flavour runs on the persistent kernel only (unset MPC_PATH / MPC_FILTER)");
     mpc_status st = ensure_workspace(c, t, total_tc);
     if (st != MPC_OK) return st;
@@ -471,10 +487,19 @@ mpc_status check_encode_args(const mpc_context* c, const uint8_t* rgb, int frame
 
 // whole_frame_order: the records go where one launch over the whole frame would put them (FrameInput::out_tile_rows) and the
 // caller has zeroed d_choices for the whole frame (stripes of one frame encoded one by one, encode_sequence's single frames)
+// table: the frames of the launch lie anywhere and so do their records in d_counts / d_choices (mpc::FrameTable; d_rgb and
+// frame_stride are the first frame's and 0); the records beyond a tile-channel's count are left as they are, not zeroed
 mpc_status encode_batch_device(mpc_context* c, const Tuning& t, const uint8_t* d_rgb, int frames, size_t frame_stride, int width,
                                int height, size_t row_stride, int tile_row_begin, int tile_row_end, const double* quant,
                                uint16_t* d_counts, mpc_basis_choice* d_choices, double* d_energy, uint32_t* d_swept, void* stream,
-                               bool whole_frame_order) {
+                               bool whole_frame_order, const mpc::FrameTable* table) {
+    if (table) {
+        if (table->n != frames || frames > mpc::kFrameTable || whole_frame_order) return fail(MPC_ERR_ARGUMENT, "bad frame table");
+        for (int f = 0; f < frames; ++f)
+            if (!table->rgb[f] || table->first[f] < 0 || table->first[f] > ((1LL << 31) - 1) / 3 - (width + 7) / 8 * static_cast<long long>((height + 7) / 8))
+                return fail(MPC_ERR_ARGUMENT, "bad frame table");
+        frame_stride = row_stride * static_cast<size_t>(height);  // not read by the kernel; keeps the batch check below meaningful
+    }
     if (const mpc_status as = check_encode_args(c, d_rgb, frames, frame_stride, width, height, row_stride, tile_row_begin, tile_row_end,
                                                 d_counts, d_choices);
         as != MPC_OK)
@@ -485,8 +510,9 @@ mpc_status encode_batch_device(mpc_context* c, const Tuning& t, const uint8_t* d
     HIP_TRY(hipSetDevice(c->device));
     const double* d_q = nullptr;
     if (const mpc_status qs = call_quant(c, quant, s, &d_q); qs != MPC_OK) return qs;
-    if (!whole_frame_order) HIP_TRY(hipMemsetAsync(d_choices, 0, sizeof(mpc_basis_choice) * tiles * 3 * c->K, s));
+    if (!whole_frame_order && !table) HIP_TRY(hipMemsetAsync(d_choices, 0, sizeof(mpc_basis_choice) * tiles * 3 * c->K, s));
     mpc::FrameInput in{};
+    if (table) in.table = *table;
     in.rgb = d_rgb;
     in.width = width;
     in.height = height;

@@ -1,4 +1,5 @@
-"""Two consecutive frames of bench.py's pipelined call, every kernel the device ran, from a rocprofv3 --kernel-trace csv:
+"""Two consecutive pursuit launches of bench.py's pipelined call (a launch covers one frame or a group of frames, MPC_SEQ_GROUP),
+every kernel the device ran, from a rocprofv3 --kernel-trace csv:
     python tools/pipeline_timeline.py <kernel_trace.csv> <out.txt>"""
 import csv
 import sys
@@ -10,9 +11,10 @@ idx = [i for i, r in enumerate(rows) if "mp_pursuit_kernel" in r["Kernel_Name"]]
 pipe = [i for k, i in enumerate(idx[:-1]) if any("mp_stream_count" in rows[j]["Kernel_Name"] for j in range(i + 1, idx[k + 1]))]
 a, b = pipe[-5], pipe[-3]
 t0 = int(rows[a]["Start_Timestamp"])
-out = ["# bench.py: two consecutive frames of the timed call in steady state, every kernel the device ran (rocprofv3 --kernel-trace)\n"
+out = ["# bench.py: two consecutive pursuit launches of the timed call in steady state (each covers one frame, or the frames of a group: two "
+       "by default for frames in device memory), every kernel the device ran (rocprofv3 --kernel-trace)\n"
        "# start_ms end_ms duration_ms kernel   -- pursuits back to back on one stream (224 workgroups on 256 CUs); behind each, on the "
-       "side streams: stream assembly + entropy phase 1 (f), later phase 2 + container copy (f), beside the next pursuits on the CUs "
+       "side streams: stream assembly + entropy phase 1 of each of its frames, later their phase 2 + container copy, beside the next pursuits on the CUs "
        "they leave free.  The copyBuffer kernel is the profiler's doing: without rocprofv3 the container's copy is an SDMA copy "
        "(DESIGN.md 4).  Run bench.py with --no-e2e: the legs behind the timed call would be picked up instead\n"]
 for r in rows[a:b + 1]:
