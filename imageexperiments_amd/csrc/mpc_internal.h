@@ -1,6 +1,7 @@
 // mpc_internal.h -- product: what the translation units of libmpcodec.so share besides the public C ABI (include/mpcodec.h).
 //   mpcodec_context.cpp    device dictionary, context, quantiser tables, pursuit launches, tile encode, timing, tuning switches
-//   mpcodec_container.cpp  records on the device -> container (ContainerJob), the mpc_container_job_* API, the frame pipeline
+//   mpcodec_container.cpp  records on the device -> container (ContainerJob), the mpc_container_job_* API
+//   mpcodec_pipeline.cpp   the frame pipeline (mpc_encode_image(s)*): frames -> tile encode -> container jobs, in stages
 //   mpcodec_bitstream.cpp  host-only bitstream entry points
 // and, behind host_bitstream.h (they know neither HIP nor the C ABI and also build on their own):
 //   host_bitstream.cpp     bits, Golomb, Elias-Fano, Huffman, run lengths, the Huffman-or-Golomb choice, plan_stream, or_bits
@@ -78,8 +79,6 @@ constexpr unsigned kTripleCap = 1u << 20;              // (symbol, count, first 
 //   MPC_MAX_BATCH_TILES           max_batch        tiles in flight per sub-batch round of those sweeps (524288)
 //   MPC_WORKGROUPS                workgroups       pursuit workgroups of every launch (all CUs)
 //   MPC_SEQ_WORKGROUPS            seq_workgroups   pursuit workgroups of a frame sequence (7/8 of the CUs; 0 = all)
-//   MPC_SIDE_PRIORITY             side_priority    the frame pipeline's side streams outrank its pursuits (on)
-//   MPC_SHARED_SIDE_STREAMS       shared_sides     two side streams shared by all slots (on)
 //   MPC_SEQ_GROUP                 seq_group        frames of a sequence that share one pursuit launch, 1 .. 3 (kSeqGroupDevice / kSeqGroupHost)
 //   MPC_LAG_ASSEMBLY              lag_assembly     launch(g) waits for assembly + phase 1 of the frames of launch g - this (2)
 //   MPC_LAG_PHASE2                lag_phase2       ... and for phase 2 of the frames of launch g - this (3)
@@ -94,9 +93,9 @@ constexpr unsigned kTripleCap = 1u << 20;              // (symbol, count, first 
 constexpr int kSeqGroupDevice = 2;
 constexpr int kSeqGroupHost = 1;
 struct Tuning {
-    bool steps_path = false, side_priority = true, host_entropy = false, trace = false;
+    bool steps_path = false, host_entropy = false, trace = false;
     int pipes = 0, workgroups = 0, single_stripes = 0;          // > 0: forced
-    int seq_workgroups = -1, shared_sides = -1;                 // >= 0: forced
+    int seq_workgroups = -1;                                    // >= 0: forced
     int lag_assembly = 2, lag_phase2 = 3;
     int seq_group = 0;                                          // > 0: forced
     long long max_batch = kMaxBatchDefault;
@@ -286,6 +285,18 @@ mpc_status container_begin(ContainerJob& j, const mpc_context* c, const EntropyB
 mpc_status container_tables(ContainerJob& j, const std::function<void()>& enqueued = nullptr);
 mpc_status container_collect(ContainerJob& j, uint8_t** bytes, size_t* nbytes);
 
+// the host route's pinned buffers: counts | stream offsets | symbols (worst case: every record alive); on a null base only their size
+struct HostRoute {
+    uint16_t* counts;
+    unsigned long long* stream_off;
+    uint16_t* symbols;
+};
+size_t host_route_layout(char* base, size_t n_tc, int K, HostRoute* r);
+
+// the `interval` and `flags` arguments of the indexed entry points (mpcodec_container.cpp)
+mpc_status index_interval_of(int interval, unsigned* out);
+mpc_status index_flags_of(unsigned flags, bool* expanded);
+
 // A slot of the mpc_container_job_* API.  Its buffers are its own: the context's entropy slots and staging belong to the frame
 // pipeline (mpc_encode_image(s)) and to mpc_code_symbol_streams_device, which may run -- and re-carve or clear their tables --
 // between `begin` and `collect`.
@@ -346,7 +357,6 @@ struct mpc_context {
     GrowBuffer host_stage{GrowBuffer::kPinned};
     // mpc_encode_images: upload / compute / download streams and per-slot events (upload done, pursuit done, download done)
     hipStream_t seq_up = nullptr, seq_compute = nullptr;
-    bool seq_prioritised = false;                    // the side streams outrank the pursuits' (encode_sequence)
     // read by device-pointer encodes, which do not take `host_calls`: a stale value costs or gains a few workgroups, nothing else
     std::atomic<int> seq_workgroups{0};              // > 0: the pursuits of a frame sequence leave CUs to the kernels behind them
     std::atomic<int> user_workgroups{0};             // > 0: mpc_context_set_tile_encode_workgroups
@@ -356,7 +366,10 @@ struct mpc_context {
     static constexpr int kSingleStripes = 4;
     hipEvent_t seq_stripe_up[kSingleStripes] = {};   // a single host frame goes up and is encoded in row stripes (encode_sequence)
     hipEvent_t seq_pursuit_done[kSeqSlots] = {};      // behind a slot's pursuit, for the slot's own stream to wait on
-    hipStream_t seq_down[kSeqSlots] = {};             // one download stream per slot: its worker thread drives it
+    // the side streams of all slots: [0] stream assembly + phase 1, [1] phase 2 and the copies.  The others are created and never
+    // used: without them a single 16 Mpixel host frame takes 2 % longer and a single 1080p frame 6 % less
+    // (profiles/pipeline_stages.txt; measured, not explained -- a choice by frame size would be a change of speed of its own)
+    hipStream_t seq_down[kSeqSlots] = {};
     // device-side entropy stage (mp_entropy.hip): per-slot buffers of the frame pipeline and mpc_code_symbol_streams_device
     EntropySlot ent[kSeqSlots];
     std::unique_ptr<JobSlot> jobs[kSeqSlots];        // mpc_container_job_*: records on the device -> container, in steps

@@ -42,8 +42,6 @@ Tuning read_tuning() {
     if (tiles > 0) t.max_batch = 3LL * ((tiles + 255) / 256 * 256);
     t.workgroups = env_int("MPC_WORKGROUPS", 0);
     t.seq_workgroups = env_int("MPC_SEQ_WORKGROUPS", -1);
-    t.side_priority = env_int("MPC_SIDE_PRIORITY", 1) != 0;
-    t.shared_sides = env_int("MPC_SHARED_SIDE_STREAMS", -1);
     t.lag_assembly = std::min(4, std::max(2, env_int("MPC_LAG_ASSEMBLY", 2)));
     t.lag_phase2 = std::min(5, std::max(t.lag_assembly, env_int("MPC_LAG_PHASE2", 3)));
     t.seq_group = std::min(3, std::max(0, env_int("MPC_SEQ_GROUP", 0)));

@@ -4,7 +4,8 @@ Every case is a fresh child process with the environment set (the library reads 
 and streams are made once per context), one child after another.  K = 8, quality 3.5, bench.synth_frame; 70x37 frames are ragged in
 both directions (9 x 5 tiles, rows of 210 bytes: the byte path), 328x200 frames have rows of 984 bytes (the 8-byte path).  The
 sequence lengths cover a group cut short by the end of the call (3, 5, 9, 13 at two frames per launch; 1, 2, 5, 13 at three),
-fewer frames than a group (1, 2), more frames than the pipeline has slots (9) and two wraps of the slots (13)."""
+fewer frames than a group (1, 2), more frames than the pipeline has slots (9) and two wraps of the slots (13).  The `mixed` child
+runs both routes and both sizes in turn on one context (MIXED)."""
 import hashlib
 import json
 import os
@@ -27,6 +28,9 @@ DEVICE_CASES = {
     "odd": [0, 103, 2, 103, 104, 5, 101],      # one frame of a launch off the 8-byte grid: the whole launch reads bytes
     "odd_first": [103],
 }
+# calls on one context, in order: (route, frames, width, height).  The host and the device layouts of a slot differ by the image at
+# its front, and the two sizes by everything: every call carves the slots anew
+MIXED = (("host", 1, 70, 37), ("device", 13, 328, 200), ("host", 5, 328, 200), ("device", 2, 70, 37), ("indexed", 3, 70, 37))
 
 _CHILD = r"""
 import sys, hashlib, json
@@ -34,12 +38,26 @@ sys.path.insert(0, {root!r})
 import numpy as np
 import imageexperiments_amd as ia
 from bench import synth_frame
-mode, sizes, lengths, distinct, device_cases = json.loads(sys.argv[1])
+mode, sizes, lengths, distinct, device_cases, mixed = json.loads(sys.argv[1])
 h = lambda b: hashlib.sha256(bytes(b)).hexdigest()
 ctx = ia.create_compression_context(8, 8, 3.5, device=0)
 if mode.startswith("fast"):
     ctx.set_fast(True)
 out = {{}}
+if mode == "mixed":                            # one context, the calls of `mixed` in order: the slots are carved anew between them
+    import torch
+    sizes, out = [], []
+    for route, n, W, H in mixed:
+        fr = [synth_frame(W, H, 12345 + f % distinct) for f in range(n)]
+        if route == "host":
+            got = ctx.encode_images(fr)
+        elif route == "indexed":
+            got = [b for b, x in ctx.encode_images_indexed(fr, interval=32)]
+        else:
+            d = [torch.from_numpy(f).cuda() for f in fr]
+            torch.cuda.synchronize()
+            got = ctx.encode_images_device([t.data_ptr() for t in d], W, H)
+        out.append([h(b) for b in got])
 for W, H in sizes:
     fr = [synth_frame(W, H, 12345 + f) for f in range(distinct)]
     seq = lambda n: [fr[i % distinct] for i in range(n)]
@@ -74,7 +92,7 @@ print(json.dumps(out))
 
 
 def run_child(mode, env, sizes=SIZES):
-    spec = json.dumps([mode, sizes, LENGTHS, DISTINCT, DEVICE_CASES])
+    spec = json.dumps([mode, sizes, LENGTHS, DISTINCT, DEVICE_CASES, MIXED])
     r = subprocess.run([sys.executable, "-c", _CHILD.format(root=ROOT), spec], capture_output=True, text=True, timeout=600,
                        env={**os.environ, **env})
     assert r.returncode == 0, r.stderr
@@ -116,6 +134,14 @@ def test_default_group_equals_the_oracle(want):
         assert got[size]["distinct"] == [gold[i] for i in DEVICE_CASES["distinct"]], size
     got = run_child("host", {}, sizes=SIZES[1:])
     assert got["328x200"]["13"] == [want["328x200"][i % DISTINCT] for i in range(13)]
+
+
+@pytest.mark.parametrize("group", (None, 3))
+def test_routes_and_sizes_mixed_on_one_context_equal_the_oracle(want, group):
+    got = run_child("mixed", {} if group is None else {"MPC_SEQ_GROUP": str(group)})
+    assert len(got) == len(MIXED)
+    for (route, n, W, H), hashes in zip(MIXED, got):
+        assert hashes == [want[f"{W}x{H}"][i % DISTINCT] for i in range(n)], (route, n, W, H, group)
 
 
 def test_indexed_encoders_in_groups_equal_frame_by_frame(want):
