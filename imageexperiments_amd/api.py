@@ -57,6 +57,14 @@ class MpcPart(C.Structure):                          # mpc_part
 MPC_COMPOSE_DEVICE_PIXELS = 2                                       # `flags` of mpc_compose_indexed
 
 
+class MpcDeltaInfo(C.Structure):                     # mpc_delta_info
+    _fields_ = [("tiles", C.c_int), ("changed", C.c_int), ("key", C.c_int)]
+
+
+MPC_DELTA_KEY, MPC_DELTA_DEVICE_PIXELS, MPC_DELTA_PACK_ALWAYS = 1, 2, 4   # `flags` of mpc_delta_encode
+MPC_DELTA_PACK_ROWS = 64
+
+
 def _parts(parts, device_pixels=False):
     """[(source, rect, x, y)] -> (MpcPart array, what must stay alive).  source: an int with rect = (x, y, width, height) or None = all
     of it; or pixels, rect None: an HxWx3 uint8 array (a strided view keeps its row stride), with device_pixels a
@@ -263,6 +271,22 @@ def _bind_bitstream(L):
     L.mpc_compose_indexed.argtypes = [vp, C.POINTER(_u8p), C.POINTER(C.c_size_t), C.POINTER(_u8p), C.POINTER(C.c_size_t), C.c_int, _pp, C.c_int,
                                       C.c_int, C.c_int, C.c_uint, C.c_int, C.POINTER(_u8p), C.POINTER(C.c_size_t), C.POINTER(_u8p),
                                       C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
+    _szp_ = C.POINTER(C.c_size_t)
+    try:
+        L.mpc_changed_tiles.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int, C.c_int, _i32p, C.POINTER(C.c_int)]
+        L.mpc_delta_pack_geometry.argtypes = [C.c_longlong, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), _szp_, _szp_]
+        L.mpc_tile_diff_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_size_t, vp, vp, vp]
+        L.mpc_pack_tiles_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_int, C.c_int, vp, C.c_size_t, vp]
+        L.mpc_scatter_records_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, C.c_int, vp]
+        L.mpc_delta_create.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp)]
+        L.mpc_delta_destroy.argtypes = [vp]
+        L.mpc_delta_destroy.restype = None
+        L.mpc_delta_encode.argtypes = [vp, vp, C.c_size_t, _dp, C.c_uint, C.c_int, C.POINTER(_u8p), _szp_, C.POINTER(_u8p), _szp_,
+                                       C.POINTER(MpcDeltaInfo)]
+        L.mpc_delta_changed.argtypes = [vp, _i32p, C.c_int, C.POINTER(C.c_int)]
+    except AttributeError:
+        if not os.environ.get("MPCODEC_LIB"):             # an older build may be loaded for A/B timing only
+            raise
     L.mpc_parse_container_view_device.argtypes = [vp] + _vparse
     L.mpc_decode_views_indexed.argtypes = [vp, C.POINTER(_u8p), C.POINTER(C.c_size_t), C.POINTER(_u8p), C.POINTER(C.c_size_t), _vwp, C.c_int,
                                            C.c_uint, C.POINTER(_u8p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -685,6 +709,100 @@ def compose_container(blobs, parts, width, height):
     _check(L.mpc_compose_container(ptrs, sizes, n, made, len(parts), int(width), int(height), C.byref(out), C.byref(nout)))
     del keep
     return _take_bytes(L, out, nout)
+
+
+def _pixel_rows(rgb):
+    """an HxWx3 uint8 array whose pixels are contiguous within a row, as it is (strides[0] is its row stride: a window of a larger
+    image, padded rows); anything else made contiguous"""
+    rgb = np.asarray(rgb)
+    if not (rgb.dtype == np.uint8 and rgb.ndim == 3 and rgb.shape[2] == 3 and rgb.strides[1:] == (3, 1) and rgb.strides[0] >= 3 * rgb.shape[1]):
+        rgb = np.ascontiguousarray(rgb, np.uint8)
+        if rgb.ndim != 3 or rgb.shape[2] != 3:
+            raise ValueError("pixels: an HxWx3 uint8 array")
+    return rgb
+
+
+def changed_tiles(prev, cur, block_size=8):
+    """mpc_changed_tiles: the tiles t = tx * tiles_y + ty of two equally sized HxWx3 uint8 frames that differ in any pixel byte, ascending
+    (int32 array): the host's definition of the delta encoder's diff kernel.  Strided views keep their row strides; only pixel bytes
+    are read."""
+    L = load_library()
+    prev, cur = _pixel_rows(prev), _pixel_rows(cur)
+    if prev.shape != cur.shape:
+        raise ValueError("frames must have the same size")
+    H, W = cur.shape[:2]
+    tiles = np.zeros(max(-(-W // max(block_size, 1)) * -(-H // max(block_size, 1)), 1), np.int32)
+    n = C.c_int(0)
+    _check(L.mpc_changed_tiles(prev.ctypes.data, prev.strides[0], cur.ctypes.data, cur.strides[0], W, H, int(block_size),
+                               tiles.ctypes.data_as(_i32p), C.byref(n)))
+    return tiles[:n.value].copy()
+
+
+def delta_pack_geometry(n, rows=MPC_DELTA_PACK_ROWS):
+    """mpc_delta_pack_geometry: the packed frame of n listed tiles with at most `rows` tile rows -> (R, C, stride, bytes): R x C whole
+    tiles, listed tile j at tile (j // R, j % R), `stride` = 24 * C bytes between pixel rows."""
+    R, Cc, stride, nbytes = C.c_int(0), C.c_int(0), C.c_size_t(0), C.c_size_t(0)
+    _check(load_library().mpc_delta_pack_geometry(int(n), int(rows), C.byref(R), C.byref(Cc), C.byref(stride), C.byref(nbytes)))
+    return R.value, Cc.value, stride.value, nbytes.value
+
+
+class DeltaEncoder:
+    """mpc_delta: a session that encodes frames of one size one after the other and pursues only the tiles whose pixels changed since
+    the last call.  Every container is byte for byte CompressionContext.encode_image of that frame.  `info` = (tiles, changed, key)
+    of the last call."""
+
+    def __init__(self, ctx, width, height):
+        self.ctx, self.L = ctx, ctx.L                               # the session must go before its context
+        self.width, self.height = int(width), int(height)
+        h = C.c_void_p()
+        _check(self.L.mpc_delta_create(ctx.h, self.width, self.height, C.byref(h)))
+        self.h = h
+        self.info = None
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.mpc_delta_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _encode(self, ptr, row_stride, quant, flags, index_interval):
+        qp = None
+        if quant is not None:
+            quant = np.ascontiguousarray(quant, np.float64).reshape(3, self.ctx.K)
+            qp = quant.ctypes.data_as(_dp)
+        out, n, index, nindex, info = _u8p(), C.c_size_t(0), _u8p(), C.c_size_t(0), MpcDeltaInfo()
+        _check(self.L.mpc_delta_encode(self.h, ptr, int(row_stride), qp, int(flags), -1 if index_interval is None else int(index_interval),
+                                       C.byref(out), C.byref(n), C.byref(index), C.byref(nindex), C.byref(info)))
+        self.info = (info.tiles, info.changed, info.key)
+        blob = _take_bytes(self.L, out, n)
+        return blob if index_interval is None else (blob, _take_bytes(self.L, index, nindex))
+
+    def encode(self, rgb, quant=None, key=False, index_interval=None, pack_always=False):
+        """mpc_delta_encode of a host frame (HxWx3 uint8; a strided view keeps its row stride) -> the container, or with index_interval
+        (0 = the default interval) (container, container_index2(container, interval, expanded))."""
+        rgb = _pixel_rows(rgb)
+        if rgb.shape[:2] != (self.height, self.width):
+            raise ValueError("the frame is not the session's size")
+        flags = (MPC_DELTA_KEY if key else 0) | (MPC_DELTA_PACK_ALWAYS if pack_always else 0)
+        return self._encode(rgb.ctypes.data, rgb.strides[0], quant, flags, index_interval)
+
+    def encode_device(self, d_rgb, row_stride=0, quant=None, key=False, index_interval=None, pack_always=False):
+        """The same for a frame in device memory: d_rgb an int from tensor.data_ptr(), row_stride bytes between rows (0 = 3 * width)."""
+        flags = MPC_DELTA_DEVICE_PIXELS | (MPC_DELTA_KEY if key else 0) | (MPC_DELTA_PACK_ALWAYS if pack_always else 0)
+        return self._encode(int(d_rgb), row_stride, quant, flags, index_interval)
+
+    def changed(self):
+        """mpc_delta_changed: the tiles the last call pursued, ascending (int32 array); a key frame's: every tile"""
+        n = C.c_int(0)
+        _check(self.L.mpc_delta_changed(self.h, None, 0, C.byref(n)))
+        tiles = np.zeros(max(n.value, 1), np.int32)
+        _check(self.L.mpc_delta_changed(self.h, tiles.ctypes.data_as(_i32p), n.value, C.byref(n)))
+        return tiles[:n.value]
 
 
 def _view_parse(fn, head, buf, idx, view, parse_all):
@@ -1366,6 +1484,30 @@ class CompressionContext:
         _check(self.L.mpc_paste_records_device(self.h, d_src_counts, d_src_choices, int(src_width), int(src_height), C.byref(rc), d_dst_counts,
                                                d_dst_choices, int(dst_width), int(dst_height), int(dst_x), int(dst_y), d_owner or None, int(part),
                                                stream or None))
+        if check:
+            _check(self.L.mpc_crop_records_check(self.h, stream or None))
+
+    def delta_encoder(self, width, height):
+        """mpc_delta_create: a DeltaEncoder for frames of width x height through this context"""
+        return DeltaEncoder(self, width, height)
+
+    def tile_diff_device(self, d_kept, d_rgb, width, height, row_stride, d_list, d_count, stream=0):
+        """mpc_tile_diff_device: the 8 x 8 tiles of the frame at d_rgb (row_stride bytes between rows, 0 = 3 * width) that differ from the
+        tight copy at d_kept -> d_list (int32 per tile, ascending) and d_count (int32); d_kept becomes the new pixels.  Asynchronous."""
+        _check(self.L.mpc_tile_diff_device(self.h, d_kept, d_rgb, int(width), int(height), int(row_stride), d_list, d_count, stream or None))
+
+    def pack_tiles_device(self, d_rgb, width, height, row_stride, d_list, n, rows, d_packed, packed_stride=0, stream=0):
+        """mpc_pack_tiles_device: the n listed tiles of the frame as the packed frame delta_pack_geometry(n, rows) describes, black
+        outside the image and in the padding tiles.  Asynchronous."""
+        _check(self.L.mpc_pack_tiles_device(self.h, d_rgb, int(width), int(height), int(row_stride), d_list, int(n), int(rows), d_packed,
+                                            int(packed_stride), stream or None))
+
+    def scatter_records_device(self, d_packed_counts, d_packed_choices, d_list, n, d_counts, d_choices, tiles, stream=0, check=True):
+        """mpc_scatter_records_device: records j of a packed frame to tile d_list[j] of whole-frame records of `tiles` tiles.  check:
+        mpc_crop_records_check behind it, which waits for `stream` and raises MpcError(MPC_ERR_BITSTREAM) if a list entry was outside
+        [0, tiles) (that entry is skipped)."""
+        _check(self.L.mpc_scatter_records_device(self.h, d_packed_counts, d_packed_choices, d_list, int(n), d_counts, d_choices, int(tiles),
+                                                 stream or None))
         if check:
             _check(self.L.mpc_crop_records_check(self.h, stream or None))
 

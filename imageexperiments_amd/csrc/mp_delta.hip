@@ -1,0 +1,236 @@
+// mp_delta.hip -- product: the delta encoder's kernels (include/mpcodec.h, "delta"; DESIGN.md 4, "Encoder: changed tiles only").
+//
+// A tile's records depend on that tile's pixels alone, so a frame that differs from the last one in a few tiles needs the pursuit for
+// those tiles only.  Three byte shufflers around the unchanged tile encoder:
+//   diff     the new frame against the session's kept copy: a flag per tile, the kept copy brought up to date; then flags -> the
+//            ascending list of changed tiles (count per 1024-tile block, mp_stream_scan_kernel over the blocks, rank by ballots)
+//   pack     the listed tiles side by side in a small frame of whole tiles, which the tile encoder takes as an ordinary frame
+//   scatter  that frame's records to the listed tiles' places in the whole frame's records
+// The diff is the hot one and purely bandwidth-bound: it reads both frames once.  A tile's pixel row is 24 bytes = three 8-byte chunks;
+// a thread owns one chunk column of a strip of 64 horizontally adjacent tiles over the tile's 8 pixel rows, so a wave reads 512
+// contiguous bytes of a pixel row per load, 8 independent loads per frame in flight, and a chunk is written back only where it differs.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "mp_device.h"
+
+namespace mpc {
+
+namespace {
+constexpr int kDiffTiles = 64;                  // tiles of one tile row per workgroup
+constexpr int kDiffThreads = 3 * kDiffTiles;    // a thread per 8-byte chunk of the strip's pixel rows
+constexpr int kListBlock = 1024;                // tiles per workgroup of the flags -> list kernels (thread = tile)
+
+__host__ __device__ inline long long list_blocks(long long tiles) { return (tiles + kListBlock - 1) / kListBlock; }
+}  // namespace
+
+// kWords: both frames' bases and strides are multiples of 8 and so is 3 * width: every chunk is whole and 8-byte aligned on both
+// sides.  Else byte by byte, a chunk cut at the row's end: bytes behind 3 * width are never read.
+template <bool kWords>
+__global__ __launch_bounds__(kDiffThreads) void mp_tile_diff_kernel(uint8_t* __restrict__ kept, const uint8_t* __restrict__ rgb, int width,
+                                                                    int height, long long row_stride, int tiles_x, int tiles_y, int strips,
+                                                                    uint8_t* __restrict__ flags)
+{
+    __shared__ unsigned changed[kDiffTiles];
+    const int ty = blockIdx.x / strips, tx0 = (blockIdx.x - ty * strips) * kDiffTiles;
+    if (threadIdx.x < kDiffTiles) changed[threadIdx.x] = 0u;
+    __syncthreads();
+    const long long row_bytes = 3LL * width;
+    const long long b0 = 24LL * tx0 + 8LL * threadIdx.x;             // the chunk's first byte in its pixel row
+    const int y0 = ty * 8, rows = height - y0 < 8 ? height - y0 : 8;
+    bool differs = false;
+    if (b0 < row_bytes) {
+        if (kWords) {
+            uint2 fresh[8], old[8];
+#pragma unroll
+            for (int r = 0; r < 8; ++r)
+                if (r < rows) {
+                    fresh[r] = *reinterpret_cast<const uint2*>(rgb + (long long)(y0 + r) * row_stride + b0);
+                    old[r] = *reinterpret_cast<const uint2*>(kept + (long long)(y0 + r) * row_bytes + b0);
+                }
+#pragma unroll
+            for (int r = 0; r < 8; ++r)
+                if (r < rows && (fresh[r].x != old[r].x || fresh[r].y != old[r].y)) {
+                    differs = true;
+                    *reinterpret_cast<uint2*>(kept + (long long)(y0 + r) * row_bytes + b0) = fresh[r];
+                }
+        } else {
+            const int nb = row_bytes - b0 < 8 ? (int)(row_bytes - b0) : 8;
+            for (int r = 0; r < rows; ++r) {
+                const uint8_t* p = rgb + (long long)(y0 + r) * row_stride + b0;
+                uint8_t* q = kept + (long long)(y0 + r) * row_bytes + b0;
+                for (int j = 0; j < nb; ++j) {
+                    const uint8_t v = p[j];
+                    if (v != q[j]) {
+                        differs = true;
+                        q[j] = v;
+                    }
+                }
+            }
+        }
+    }
+    if (differs) changed[threadIdx.x / 3] = 1u;                      // every writer writes 1
+    __syncthreads();
+    if (threadIdx.x < kDiffTiles && tx0 + (int)threadIdx.x < tiles_x)
+        flags[(long long)(tx0 + (int)threadIdx.x) * tiles_y + ty] = (uint8_t)changed[threadIdx.x];
+}
+
+// flags -> per block of 1024 tiles the number set, at block_live[3 * block]: column 0 of a StreamArgs table with K = 1, which
+// mp_stream_scan_kernel turns into the blocks' offsets and the total
+__global__ __launch_bounds__(kListBlock) void mp_tile_flag_count_kernel(const uint8_t* __restrict__ flags, long long tiles,
+                                                                        unsigned* __restrict__ block_live)
+{
+    __shared__ unsigned total;
+    if (threadIdx.x == 0) total = 0u;
+    __syncthreads();
+    const long long t = (long long)blockIdx.x * kListBlock + threadIdx.x;
+    const unsigned long long live = __ballot(t < tiles && flags[t < tiles ? t : 0] != 0);
+    if ((threadIdx.x & 63) == 0 && live) atomicAdd(&total, (unsigned)__popcll(live));
+    __syncthreads();
+    if (threadIdx.x == 0) block_live[3LL * blockIdx.x] = total;
+}
+
+// the list: a set tile's place is its block's offset + the set tiles of the waves in front + its rank in its wave -- ascending in t
+__global__ __launch_bounds__(kListBlock) void mp_tile_list_kernel(const uint8_t* __restrict__ flags, long long tiles,
+                                                                  const unsigned* __restrict__ block_live, int32_t* __restrict__ list)
+{
+    __shared__ unsigned wave_live[kListBlock / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long t = (long long)blockIdx.x * kListBlock + threadIdx.x;
+    const bool set = t < tiles && flags[t < tiles ? t : 0] != 0;
+    const unsigned long long live = __ballot(set);
+    if (lane == 0) wave_live[wave] = (unsigned)__popcll(live);
+    __syncthreads();
+    if (!set) return;
+    unsigned at = block_live[3LL * blockIdx.x];
+    for (int w = 0; w < wave; ++w) at += wave_live[w];
+    list[at + (unsigned)__popcll(live & ((1ULL << lane) - 1ULL))] = (int32_t)t;
+}
+
+// A thread per 8-byte chunk of the packed frame.  kWords: the source's base and stride are multiples of 8; a chunk that lies whole
+// inside its pixel row is then one 8-byte load, and every other chunk (and every chunk without kWords) is gathered byte by byte
+template <bool kWords>
+__global__ __launch_bounds__(256) void mp_tile_pack_kernel(const uint8_t* __restrict__ rgb, int width, int height, long long row_stride,
+                                                           int tiles_y, long long tiles, const int32_t* __restrict__ list, long long n, int rows,
+                                                           int cols, uint8_t* __restrict__ packed, long long packed_stride)
+{
+    const long long chunks_per_row = 3LL * cols, total = chunks_per_row * 8 * rows, row_bytes = 3LL * width;
+    for (long long o = (long long)blockIdx.x * 256 + threadIdx.x; o < total; o += (long long)gridDim.x * 256) {
+        const long long py = o / chunks_per_row;
+        const int k = (int)(o - py * chunks_per_row), txp = k / 3, part = k - 3 * txp;
+        const long long j = (long long)txp * rows + (py >> 3);
+        uint2 v = make_uint2(0u, 0u);                                // black: outside the image, a padding tile
+        const long long t = j < n ? (long long)list[j] : -1;
+        if (t >= 0 && t < tiles) {
+            const long long tx = t / tiles_y, y = (t - tx * tiles_y) * 8 + (py & 7), b0 = 24 * tx + 8 * part;
+            if (y < height && b0 < row_bytes) {
+                const uint8_t* p = rgb + y * row_stride + b0;
+                if (kWords && b0 + 8 <= row_bytes) {
+                    v = *reinterpret_cast<const uint2*>(p);
+                } else {
+                    const int nb = row_bytes - b0 < 8 ? (int)(row_bytes - b0) : 8;
+                    unsigned long long bits = 0;
+                    for (int b = 0; b < nb; ++b) bits |= (unsigned long long)p[b] << (8 * b);
+                    v = make_uint2((unsigned)bits, (unsigned)(bits >> 32));
+                }
+            }
+        }
+        *reinterpret_cast<uint2*>(packed + py * packed_stride + 8LL * k) = v;
+    }
+}
+
+// A thread per record word, then per count.  The encoder zeroes the entries beyond a count, so a plain copy carries no garbage.
+// Every address comes from list[j] after its check against `tiles`
+__global__ __launch_bounds__(256) void mp_tile_scatter_records_kernel(const uint16_t* __restrict__ packed_counts,
+                                                                      const uint32_t* __restrict__ packed_choices,
+                                                                      const int32_t* __restrict__ list, long long n, int K,
+                                                                      uint16_t* __restrict__ counts, uint32_t* __restrict__ choices,
+                                                                      long long tiles, int* __restrict__ error)
+{
+    const int words = 3 * K;
+    const long long n_words = n * words, n_halves = n * 3;
+    for (long long o = (long long)blockIdx.x * 256 + threadIdx.x; o < n_words; o += (long long)gridDim.x * 256) {
+        const long long j = o / words, t = list[j];
+        if (t < 0 || t >= tiles) continue;
+        choices[t * words + (o - j * words)] = packed_choices[o];
+    }
+    for (long long o = (long long)blockIdx.x * 256 + threadIdx.x; o < n_halves; o += (long long)gridDim.x * 256) {
+        const long long j = o / 3, t = list[j];
+        if (t < 0 || t >= tiles) {
+            *error = 1;
+            continue;
+        }
+        counts[t * 3 + (o - j * 3)] = packed_counts[o];
+    }
+}
+
+size_t tile_diff_scratch_bytes(long long tiles)
+{
+    return (size_t)((tiles + 255) & ~255LL) + sizeof(unsigned) * 3 * (size_t)list_blocks(tiles);
+}
+
+int launch_tile_diff(uint8_t* kept, const uint8_t* rgb, int width, int height, size_t row_stride, int32_t* list, int32_t* count, void* scratch,
+                     void* stream_)
+{
+    hipStream_t s = static_cast<hipStream_t>(stream_);
+    if (!kept || !rgb || !list || !count || !scratch || width < 1 || height < 1 || row_stride < 3 * (size_t)width) return (int)hipErrorInvalidValue;
+    const long long tiles_x = ((long long)width + 7) / 8, tiles_y = ((long long)height + 7) / 8, tiles = tiles_x * tiles_y;
+    const long long strips = (tiles_x + kDiffTiles - 1) / kDiffTiles;
+    if (tiles >= (1LL << 31) || strips * tiles_y >= (1LL << 31)) return (int)hipErrorInvalidValue;
+    uint8_t* flags = static_cast<uint8_t*>(scratch);
+    unsigned* block_live = reinterpret_cast<unsigned*>(flags + ((tiles + 255) & ~255LL));
+    const size_t row_bytes = 3 * (size_t)width;
+    const bool words = ((reinterpret_cast<uintptr_t>(kept) | reinterpret_cast<uintptr_t>(rgb) | row_stride | row_bytes) & 7) == 0;
+    const dim3 grid((unsigned)(strips * tiles_y));
+    if (words)
+        hipLaunchKernelGGL(mp_tile_diff_kernel<true>, grid, dim3(kDiffThreads), 0, s, kept, rgb, width, height, (long long)row_stride, (int)tiles_x,
+                           (int)tiles_y, (int)strips, flags);
+    else
+        hipLaunchKernelGGL(mp_tile_diff_kernel<false>, grid, dim3(kDiffThreads), 0, s, kept, rgb, width, height, (long long)row_stride, (int)tiles_x,
+                           (int)tiles_y, (int)strips, flags);
+    const int blocks = (int)list_blocks(tiles);
+    hipLaunchKernelGGL(mp_tile_flag_count_kernel, dim3((unsigned)blocks), dim3(kListBlock), 0, s, flags, tiles, block_live);
+    StreamArgs a{};
+    a.K = 1;
+    a.block_live = block_live;
+    a.sizes = reinterpret_cast<unsigned*>(count);
+    if (const int e = launch_stream_scan(a, 1, blocks, s); e != 0) return e;
+    hipLaunchKernelGGL(mp_tile_list_kernel, dim3((unsigned)blocks), dim3(kListBlock), 0, s, flags, tiles, block_live, list);
+    return (int)hipGetLastError();
+}
+
+int launch_tile_pack(const uint8_t* rgb, int width, int height, size_t row_stride, const int32_t* list, long long n, int rows, int cols,
+                     uint8_t* packed, size_t packed_stride, void* stream_)
+{
+    if (!rgb || !list || !packed || width < 1 || height < 1 || row_stride < 3 * (size_t)width || n < 1 || rows < 1 || cols < 1) return (int)hipErrorInvalidValue;
+    if (n > (long long)rows * cols || packed_stride < 24 * (size_t)cols || ((reinterpret_cast<uintptr_t>(packed) | packed_stride) & 7) != 0)
+        return (int)hipErrorInvalidValue;
+    const long long tiles_y = ((long long)height + 7) / 8, tiles = (((long long)width + 7) / 8) * tiles_y;
+    if (tiles >= (1LL << 31)) return (int)hipErrorInvalidValue;
+    const long long total = 3LL * cols * 8 * rows;
+    const unsigned blocks = (unsigned)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+    const bool words = ((reinterpret_cast<uintptr_t>(rgb) | row_stride) & 7) == 0;
+    hipStream_t s = static_cast<hipStream_t>(stream_);
+    if (words)
+        hipLaunchKernelGGL(mp_tile_pack_kernel<true>, dim3(blocks), dim3(256), 0, s, rgb, width, height, (long long)row_stride, (int)tiles_y, tiles, list,
+                           n, rows, cols, packed, (long long)packed_stride);
+    else
+        hipLaunchKernelGGL(mp_tile_pack_kernel<false>, dim3(blocks), dim3(256), 0, s, rgb, width, height, (long long)row_stride, (int)tiles_y, tiles, list,
+                           n, rows, cols, packed, (long long)packed_stride);
+    return (int)hipGetLastError();
+}
+
+int launch_tile_scatter_records(const uint16_t* packed_counts, const uint32_t* packed_choices, const int32_t* list, long long n, int K,
+                                uint16_t* counts, uint32_t* choices, long long tiles, int* error, void* stream_)
+{
+    if (!packed_counts || !packed_choices || !list || !counts || !choices || !error || n < 1 || tiles < 1 || tiles >= (1LL << 31) || K < 1 ||
+        K > kMaxDeviceK)
+        return (int)hipErrorInvalidValue;
+    const long long n_words = n * 3 * K;
+    const unsigned blocks = (unsigned)((n_words + 255) / 256 < 4096 ? (n_words + 255) / 256 : 4096);
+    hipLaunchKernelGGL(mp_tile_scatter_records_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream_), packed_counts, packed_choices,
+                       list, n, K, counts, choices, tiles, error);
+    return (int)hipGetLastError();
+}
+
+}  // namespace mpc

@@ -299,6 +299,28 @@ int launch_crop_records(const uint16_t* counts, const uint32_t* choices, int til
 int launch_paste_records(const uint16_t* src_counts, const uint32_t* src_choices, int src_tiles_x, int src_tiles_y, int stx0, int sty0, int ncols,
                          int nty, int K, uint16_t* dst_counts, uint32_t* dst_choices, int dst_tiles_x, int dst_tiles_y, int dtx0, int dty0,
                          const int32_t* owner, int part, int* error, void* stream);
+// mp_stream_scan_kernel alone: the exclusive scan over the blocks of the first `pairs` columns of a.block_live ([blocks][3 * a.K]),
+// in place, each column's total in a.sizes[column].  Uses a.K, a.block_live and a.sizes only
+int launch_stream_scan(const StreamArgs& a, int pairs, int blocks, void* stream);
+
+// ---- the delta encoder's kernels (mp_delta.hip; include/mpcodec.h, "delta") ----
+// Scratch of launch_tile_diff for a frame of `tiles` tiles: a flag per tile, then the 1024-tile blocks' counts.  One layout for the
+// launch and for whoever allocates it.
+size_t tile_diff_scratch_bytes(long long tiles);
+// Tile t = tx * tiles_y + ty of the width x height frame at `rgb` (row_stride >= 3 * width, any alignment) against the tight copy `kept`
+// (3 * width bytes a row): list[0 .. *count) = the tiles with a differing pixel byte, ascending; kept = the new pixels.  Only pixel
+// bytes of `rgb` are read.  8-byte fetches when both bases, row_stride and 3 * width are multiples of 8, else byte by byte.
+int launch_tile_diff(uint8_t* kept, const uint8_t* rgb, int width, int height, size_t row_stride, int32_t* list, int32_t* count, void* scratch,
+                     void* stream);
+// The listed tiles of the frame as a packed frame of rows x cols whole tiles (host_delta.h: pack_geometry), listed tile j at
+// (j / rows, j % rows); pixels outside the image, padding tiles and list entries outside [0, tiles) are black.  packed: 8-byte
+// aligned, packed_stride a multiple of 8 and >= 24 * cols; bytes of a row behind 24 * cols are not written
+int launch_tile_pack(const uint8_t* rgb, int width, int height, size_t row_stride, const int32_t* list, long long n, int rows, int cols,
+                     uint8_t* packed, size_t packed_stride, void* stream);
+// The packed frame's records j (3 counts, 3 * K words) to the whole-frame records at tile list[j]; an entry outside [0, tiles) is
+// skipped and sets *error.  The entries are distinct
+int launch_tile_scatter_records(const uint16_t* packed_counts, const uint32_t* packed_choices, const int32_t* list, long long n, int K,
+                                uint16_t* counts, uint32_t* choices, long long tiles, int* error, void* stream);
 
 // ---- the decoder's per-symbol work in front of the gather (mp_unpack.hip): run-length expansion, DC sums ----
 constexpr int kUnpackBlock = 2048;      // coded symbols per workgroup

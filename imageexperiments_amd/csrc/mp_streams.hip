@@ -491,6 +491,13 @@ int launch_stream_gather_window(const StreamArgs& a, uint32_t* choices, long lon
     return (int)hipGetLastError();
 }
 
+int launch_stream_scan(const StreamArgs& a, int pairs, int blocks, void* stream_)
+{
+    if (blocks < 1 || a.K < 1 || a.K > kMaxDeviceK || pairs < 1 || pairs > 3 * a.K) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(mp_stream_scan_kernel, dim3((unsigned)pairs), dim3(64), 0, static_cast<hipStream_t>(stream_), a, blocks);
+    return (int)hipGetLastError();
+}
+
 size_t stream_workspace_words(long long tiles, int K)
 {
     const long long blocks = (tiles + kBlockTiles - 1) / kBlockTiles;

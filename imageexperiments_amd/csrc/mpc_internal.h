@@ -11,6 +11,7 @@
 //   mpcodec_decode_seq.cpp the decoder of containers (mpc_decode_image, mpc_decode_images*), the device unpack of coded streams
 //   mpcodec_index.cpp      the seek index's host-only entry points (mpc_container_index, mpc_parse_container_by_index)
 //   mpcodec_debug.cpp      the tests' entry points to the screen's tables (mpc_debug_*, mpc_filter_tiles)
+//   mpcodec_delta.cpp      the delta encoder (mpc_delta_*): diff against the kept frame, pursuit of the changed tiles only
 #pragma once
 
 #include "../../include/mpcodec.h"
@@ -349,6 +350,7 @@ struct mpc_context {
     std::recursive_mutex host_calls;  // the host-buffer entry points share the staging buffers below
     int* d_flag = nullptr;            // mpc_decode_tiles_device: set when a record indexes outside its dictionary
     int* d_crop_flag = nullptr;       // mpc_crop_records_device: set by a count above K, read by mpc_crop_records_check
+    GrowBuffer delta_scratch{GrowBuffer::kDevice};   // mpc_tile_diff_device: the flags and block counts (mpc::tile_diff_scratch_bytes)
     GrowBuffer compose_dev{GrowBuffer::kDevice};     // mpc_compose_indexed: the destination's records, the owner map, the pixel parts' patches
     hipStream_t compose_side = nullptr;              // ... the pixel parts' stream and the final container job's, made on first use
     // grow-only staging for the host-buffer encode entry points (mpc_encode_tiles / mpc_encode_image(s)): allocating and freeing
@@ -447,6 +449,9 @@ inline std::vector<mpc::ComposePart> compose_parts(const mpc_part* parts, int n_
     }
     return made;
 }
+
+// the context's crop error word, made on first use; the device is current (mpcodec_container.cpp)
+extern "C" mpc_status crop_flag(mpc_context* c);
 
 // ---- context and tile encode (mpcodec_context.cpp) ----
 mpc::DictDevice dict_device(const mpc_context* c);

@@ -559,7 +559,7 @@ mpc_status mpc_interleave_stripe_device(mpc_context* c, const uint16_t* d_part_c
 }
 
 // the context's crop error word, made on first use (the device is current)
-static mpc_status crop_flag(mpc_context* c) {
+mpc_status crop_flag(mpc_context* c) {
     if (c->d_crop_flag) return MPC_OK;
     HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_crop_flag), sizeof(int)));
     HIP_TRY(hipMemset(c->d_crop_flag, 0, sizeof(int)));

@@ -1,0 +1,357 @@
+// mpcodec_delta.cpp -- product: the delta encoder (include/mpcodec.h, "delta"; DESIGN.md 4, "Encoder: changed tiles only").
+// A session keeps the last frame and its records in device memory; a call finds the changed tiles on the device (mp_delta.hip),
+// pursues only those through the unchanged tile encoder, and makes the container from the whole frame's records as a compose does.
+#include <cstring>
+#include <string>
+
+#include "host_delta.h"
+#include "mpc_internal.h"
+
+struct mpc_delta {
+    mpc_context* ctx = nullptr;
+    int width = 0, height = 0, tiles_y = 0;
+    long long tiles = 0;
+    // grow-only, all of it: `store` is sized once (the geometry is the session's), the other two by the largest call so far
+    GrowBuffer store{GrowBuffer::kDevice};      // kept frame | counts | records | list | count, error word | the diff's scratch
+    GrowBuffer upload{GrowBuffer::kDevice};     // a host frame's tight copy
+    GrowBuffer pack{GrowBuffer::kDevice};       // packed frame | its counts | its records
+    hipStream_t stream = nullptr;
+    uint8_t* d_kept = nullptr;
+    uint16_t* d_counts = nullptr;
+    mpc_basis_choice* d_choices = nullptr;
+    int32_t* d_list = nullptr;
+    int32_t* d_count = nullptr;                 // [2]: the diff's count, the scatter's error word
+    void* d_scratch = nullptr;
+    // the last successful call: what the records in `store` were pursued with
+    bool valid = false, fast = false;
+    std::vector<double> quant;
+    bool changed_all = false;                   // the last call's list is every tile
+    std::vector<int32_t> changed;               // else this
+    mpc_delta_info info{};
+    ~mpc_delta() {
+        if (stream) {
+            (void)hipStreamSynchronize(stream);
+            (void)hipStreamDestroy(stream);
+        }
+    }
+};
+
+static_assert(mpc::kDeltaPackRows == MPC_DELTA_PACK_ROWS, "one value for the packed frame's tile rows");
+
+namespace {
+mpc_status no_device() { return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback"); }
+}  // namespace
+
+extern "C" {
+
+mpc_status mpc_changed_tiles(const uint8_t* prev, size_t prev_stride, const uint8_t* cur, size_t cur_stride, int width, int height,
+                             int block_size, int32_t* tiles, int* n) {
+    return guarded([&]() -> mpc_status {
+        if (!prev || !cur || !tiles || !n) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (width < 1 || height < 1 || block_size < 1 || block_size > 8) return fail(MPC_ERR_ARGUMENT, "bad geometry");
+        const size_t row = 3 * static_cast<size_t>(width);
+        if ((prev_stride != 0 && prev_stride < row) || (cur_stride != 0 && cur_stride < row))
+            return fail(MPC_ERR_ARGUMENT, "a row stride below %zu for %d pixels", row, width);
+        const long long all = ((static_cast<long long>(width) + block_size - 1) / block_size) * ((static_cast<long long>(height) + block_size - 1) / block_size);
+        if (all >= (1LL << 31)) return fail(MPC_ERR_ARGUMENT, "bad geometry");
+        *n = static_cast<int>(mpc::changed_tiles(prev, prev_stride ? prev_stride : row, cur, cur_stride ? cur_stride : row, width, height, block_size, tiles));
+        return MPC_OK;
+    });
+}
+
+mpc_status mpc_delta_pack_geometry(long long n, int rows, int* packed_rows, int* packed_cols, size_t* packed_stride, size_t* packed_bytes) {
+    if (!packed_rows || !packed_cols || !packed_stride || !packed_bytes) return fail(MPC_ERR_ARGUMENT, "null argument");
+    if (n < 0 || rows < 1 || n >= (1LL << 31)) return fail(MPC_ERR_ARGUMENT, "n %lld, rows %d", n, rows);
+    const mpc::PackGeometry g = mpc::pack_geometry(n, rows);
+    *packed_rows = g.rows;
+    *packed_cols = g.cols;
+    *packed_stride = g.stride;
+    *packed_bytes = g.bytes;
+    return MPC_OK;
+}
+
+mpc_status mpc_tile_diff_device(mpc_context* c, uint8_t* d_kept, const uint8_t* d_rgb, int width, int height, size_t row_stride,
+                                int32_t* d_list, int32_t* d_count, void* stream) {
+    return guarded([&]() -> mpc_status {
+        if (!c || !d_kept || !d_rgb || !d_list || !d_count) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (c->device < 0) return no_device();
+        if (width < 1 || height < 1) return fail(MPC_ERR_ARGUMENT, "bad geometry");
+        const size_t row = 3 * static_cast<size_t>(width), stride = row_stride ? row_stride : row;
+        if (stride < row) return fail(MPC_ERR_ARGUMENT, "row_stride %zu for %d pixels", row_stride, width);
+        const long long tiles = ((static_cast<long long>(width) + 7) / 8) * ((static_cast<long long>(height) + 7) / 8);
+        if (tiles >= (1LL << 31)) return fail(MPC_ERR_ARGUMENT, "bad geometry");
+        std::lock_guard<std::recursive_mutex> one_host_call(c->host_calls);
+        HIP_TRY(hipSetDevice(c->device));
+        if (const mpc_status gs = c->delta_scratch.reserve(mpc::tile_diff_scratch_bytes(tiles), "diff scratch"); gs != MPC_OK) return gs;
+        const int err = mpc::launch_tile_diff(d_kept, d_rgb, width, height, stride, d_list, d_count, c->delta_scratch.data(), stream);
+        if (err != 0) return launch_failed(err);
+        return MPC_OK;
+    });
+}
+
+mpc_status mpc_pack_tiles_device(mpc_context* c, const uint8_t* d_rgb, int width, int height, size_t row_stride, const int32_t* d_list, int n,
+                                 int rows, uint8_t* d_packed, size_t packed_stride, void* stream) {
+    return guarded([&]() -> mpc_status {
+        if (!c || !d_rgb || !d_list || !d_packed) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (c->device < 0) return no_device();
+        if (width < 1 || height < 1 || n < 1 || rows < 1) return fail(MPC_ERR_ARGUMENT, "bad geometry");
+        const size_t row = 3 * static_cast<size_t>(width), stride = row_stride ? row_stride : row;
+        if (stride < row) return fail(MPC_ERR_ARGUMENT, "row_stride %zu for %d pixels", row_stride, width);
+        const mpc::PackGeometry g = mpc::pack_geometry(n, rows);
+        const size_t to = packed_stride ? packed_stride : g.stride;
+        if (to < g.stride || to % 8 != 0 || reinterpret_cast<uintptr_t>(d_packed) % 8 != 0)
+            return fail(MPC_ERR_ARGUMENT, "the packed frame: an 8-byte aligned base and a stride that is a multiple of 8 and at least %zu", g.stride);
+        HIP_TRY(hipSetDevice(c->device));
+        const int err = mpc::launch_tile_pack(d_rgb, width, height, stride, d_list, n, g.rows, g.cols, d_packed, to, stream);
+        if (err != 0) return launch_failed(err);
+        return MPC_OK;
+    });
+}
+
+mpc_status mpc_scatter_records_device(mpc_context* c, const uint16_t* d_packed_counts, const mpc_basis_choice* d_packed_choices,
+                                      const int32_t* d_list, int n, uint16_t* d_counts, mpc_basis_choice* d_choices, int tiles, void* stream) {
+    return guarded([&]() -> mpc_status {
+        if (!c || !d_packed_counts || !d_packed_choices || !d_list || !d_counts || !d_choices) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (c->device < 0) return no_device();
+        if (n < 1 || tiles < 1) return fail(MPC_ERR_ARGUMENT, "n %d, tiles %d", n, tiles);
+        HIP_TRY(hipSetDevice(c->device));
+        if (const mpc_status fs = crop_flag(c); fs != MPC_OK) return fs;
+        const int err = mpc::launch_tile_scatter_records(d_packed_counts, reinterpret_cast<const uint32_t*>(d_packed_choices), d_list, n, c->K, d_counts,
+                                                         reinterpret_cast<uint32_t*>(d_choices), tiles, c->d_crop_flag, stream);
+        if (err != 0) return launch_failed(err);
+        return MPC_OK;
+    });
+}
+
+mpc_status mpc_delta_create(mpc_context* c, int width, int height, mpc_delta** out) {
+    return guarded([&]() -> mpc_status {
+        if (!c || !out) return fail(MPC_ERR_ARGUMENT, "null argument");
+        *out = nullptr;
+        if (width < 1 || height < 1) return fail(MPC_ERR_ARGUMENT, "bad geometry");
+        if (c->device < 0) return no_device();
+        const long long tiles_y = (static_cast<long long>(height) + 7) / 8, tiles = ((static_cast<long long>(width) + 7) / 8) * tiles_y;
+        if (tiles >= (1LL << 31) / (3 * MPC_MAX_K)) return fail(MPC_ERR_ARGUMENT, "bad geometry");
+        std::lock_guard<std::recursive_mutex> one_host_call(c->host_calls);
+        HIP_TRY(hipSetDevice(c->device));
+        std::unique_ptr<mpc_delta> d(new mpc_delta);
+        d->ctx = c;
+        d->width = width;
+        d->height = height;
+        d->tiles_y = static_cast<int>(tiles_y);
+        d->tiles = tiles;
+        const size_t n_tc = 3 * static_cast<size_t>(tiles);
+        const auto layout = [&](char* base) {
+            Carve cv{base};
+            d->d_kept = cv.take<uint8_t>(3 * static_cast<size_t>(width) * static_cast<size_t>(height));
+            d->d_counts = cv.take<uint16_t>(n_tc + 2);
+            d->d_choices = cv.take<mpc_basis_choice>(n_tc * static_cast<size_t>(c->K));
+            d->d_list = cv.take<int32_t>(static_cast<size_t>(tiles));
+            d->d_count = cv.take<int32_t>(2);
+            d->d_scratch = cv.take<char>(mpc::tile_diff_scratch_bytes(tiles));
+            return cv.at;
+        };
+        if (const mpc_status gs = d->store.reserve(layout(nullptr), "delta session"); gs != MPC_OK) return gs;
+        layout(d->store.data());
+        HIP_TRY(hipMemset(d->d_count, 0, 2 * sizeof(int32_t)));
+        HIP_TRY(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
+        *out = d.release();
+        return MPC_OK;
+    });
+}
+
+void mpc_delta_destroy(mpc_delta* d) {
+    if (!d) return;
+    if (d->ctx && d->ctx->device >= 0) (void)hipSetDevice(d->ctx->device);
+    delete d;
+}
+
+mpc_status mpc_delta_changed(const mpc_delta* d, int32_t* tiles, int capacity, int* n) {
+    if (!d || !n || (capacity > 0 && !tiles)) return fail(MPC_ERR_ARGUMENT, "null argument");
+    const long long count = d->changed_all ? d->tiles : static_cast<long long>(d->changed.size());
+    *n = static_cast<int>(count);
+    if (capacity < count) return capacity > 0 ? fail(MPC_ERR_ARGUMENT, "room for %d tiles, %lld changed", capacity, count) : MPC_OK;
+    for (long long t = 0; t < count; ++t) tiles[t] = d->changed_all ? static_cast<int32_t>(t) : d->changed[static_cast<size_t>(t)];
+    return MPC_OK;
+}
+
+mpc_status mpc_delta_encode(mpc_delta* d, const uint8_t* rgb, size_t row_stride, const double* quant, unsigned flags, int index_interval,
+                            uint8_t** bytes, size_t* nbytes, uint8_t** index, size_t* index_bytes, mpc_delta_info* info) {
+    return guarded([&]() -> mpc_status {
+        if (!d || !rgb || !bytes || !nbytes || !info) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (index_interval >= 0 && (!index || !index_bytes)) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (flags & ~(MPC_DELTA_KEY | MPC_DELTA_DEVICE_PIXELS | MPC_DELTA_PACK_ALWAYS)) return fail(MPC_ERR_ARGUMENT, "flags 0x%x", flags);
+        if (index_interval > 0 && (index_interval < static_cast<int>(mpc::kIndexIntervalMin) || index_interval > static_cast<int>(mpc::kIndexIntervalMax)))
+            return fail(MPC_ERR_ARGUMENT, "interval %d: 0 or %u to %u", index_interval, mpc::kIndexIntervalMin, mpc::kIndexIntervalMax);
+        const unsigned every = index_interval < 0 ? 0u : index_interval ? static_cast<unsigned>(index_interval) : mpc::kIndexIntervalDefault;
+        mpc_context* c = d->ctx;
+        const int width = d->width, height = d->height, K = c->K;
+        const size_t row = 3 * static_cast<size_t>(width);
+        if (row_stride != 0 && row_stride < row) return fail(MPC_ERR_ARGUMENT, "row_stride %zu for %d pixels", row_stride, width);
+        if (c->device < 0) return no_device();
+        std::lock_guard<std::recursive_mutex> one_host_call(c->host_calls);
+        for (int k = 0; k < mpc_context::kSeqSlots; ++k)
+            if (c->jobs[k] && c->jobs[k]->stage != 0) return fail(MPC_ERR_ARGUMENT, "container job slot %d is busy", k);
+        // behind the checks: whatever fails from here on leaves a session whose next call is a key frame
+        *bytes = nullptr;
+        *nbytes = 0;
+        if (index) *index = nullptr;
+        if (index_bytes) *index_bytes = 0;
+        struct Session {
+            mpc_delta* d;
+            bool keep = false;
+            ~Session() {
+                if (keep) return;
+                d->valid = false;
+                d->changed_all = false;
+                d->changed.clear();
+                d->info = mpc_delta_info{};
+            }
+        } session{d};
+        HIP_TRY(hipSetDevice(c->device));
+        const Tuning tuning = read_tuning();
+        const double* table = quant ? quant : c->quant.data();
+        const size_t table_bytes = sizeof(double) * 3 * static_cast<size_t>(K);
+        const bool key = !d->valid || (flags & MPC_DELTA_KEY) || d->fast != c->fast || d->quant.size() != 3 * static_cast<size_t>(K) ||
+                         std::memcmp(d->quant.data(), table, table_bytes) != 0;
+        const bool through_pack = !key || (flags & MPC_DELTA_PACK_ALWAYS);
+        hipStream_t s = d->stream;
+        struct Drain {                                              // whatever happens, nothing of this call is left running
+            hipStream_t s;
+            ~Drain() { (void)hipStreamSynchronize(s); }
+        } drain{s};
+        // 1. the frame on the device
+        const uint8_t* frame = rgb;
+        size_t stride = row_stride ? row_stride : row;
+        if (!(flags & MPC_DELTA_DEVICE_PIXELS)) {
+            if (const mpc_status gs = d->upload.reserve(row * static_cast<size_t>(height), "delta upload"); gs != MPC_OK) return gs;
+            uint8_t* up = reinterpret_cast<uint8_t*>(d->upload.data());
+            HIP_TRY(hipMemcpy2DAsync(up, row, rgb, stride, row, static_cast<size_t>(height), hipMemcpyHostToDevice, s));
+            frame = up;
+            stride = row;
+        }
+        // 2., 3. the changed tiles: all of them for a key frame, else the diff's list; either way the kept copy becomes this frame
+        long long n = d->tiles;
+        d->changed.clear();
+        if (key) {
+            HIP_TRY(hipMemcpy2DAsync(d->d_kept, row, frame, stride, row, static_cast<size_t>(height), hipMemcpyDeviceToDevice, s));
+            if (through_pack) {
+                d->changed.resize(static_cast<size_t>(n));
+                for (long long t = 0; t < n; ++t) d->changed[static_cast<size_t>(t)] = static_cast<int32_t>(t);
+                HIP_TRY(hipMemcpyAsync(d->d_list, d->changed.data(), sizeof(int32_t) * d->changed.size(), hipMemcpyHostToDevice, s));
+                HIP_TRY(hipStreamSynchronize(s));
+                d->changed.clear();
+            }
+        } else {
+            if (const int e = mpc::launch_tile_diff(d->d_kept, frame, width, height, stride, d->d_list, d->d_count, d->d_scratch, s); e != 0)
+                return launch_failed(e);
+            int32_t count = -1;
+            HIP_TRY(hipMemcpyAsync(&count, d->d_count, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            if (count < 0 || count > d->tiles) return fail(MPC_ERR_HIP, "the diff counted %d of %lld tiles", count, d->tiles);
+            n = count;
+            d->changed.resize(static_cast<size_t>(n));
+            if (n > 0) {
+                HIP_TRY(hipMemcpyAsync(d->changed.data(), d->d_list, sizeof(int32_t) * static_cast<size_t>(n), hipMemcpyDeviceToHost, s));
+                HIP_TRY(hipStreamSynchronize(s));
+            }
+        }
+        // 4. - 6. pursue: a key frame straight into the record store, else the packed frame of the listed tiles and its records scattered
+        if (!through_pack) {
+            if (const mpc_status es = mpc_encode_tiles_device(c, frame, width, height, stride, 0, d->tiles_y, quant, d->d_counts, d->d_choices, nullptr,
+                                                              nullptr, 0, s);
+                es != MPC_OK)
+                return es;
+        } else if (n > 0) {
+            const mpc::PackGeometry g = mpc::pack_geometry(n, MPC_DELTA_PACK_ROWS);
+            const size_t packed_tc = 3 * static_cast<size_t>(g.rows) * static_cast<size_t>(g.cols);
+            uint8_t* d_packed = nullptr;
+            uint16_t* d_packed_counts = nullptr;
+            mpc_basis_choice* d_packed_choices = nullptr;
+            const auto layout = [&](char* base) {
+                Carve cv{base};
+                d_packed = cv.take<uint8_t>(g.bytes);
+                d_packed_counts = cv.take<uint16_t>(packed_tc + 2);
+                d_packed_choices = cv.take<mpc_basis_choice>(packed_tc * static_cast<size_t>(K));
+                return cv.at;
+            };
+            if (const mpc_status gs = d->pack.reserve(layout(nullptr), "delta packed frame"); gs != MPC_OK) return gs;
+            layout(d->pack.data());
+            if (const int e = mpc::launch_tile_pack(frame, width, height, stride, d->d_list, n, g.rows, g.cols, d_packed, g.stride, s); e != 0)
+                return launch_failed(e);
+            if (const mpc_status es = mpc_encode_tiles_device(c, d_packed, 8 * g.cols, 8 * g.rows, g.stride, 0, g.rows, quant, d_packed_counts,
+                                                              d_packed_choices, nullptr, nullptr, 0, s);
+                es != MPC_OK)
+                return es;
+            if (const int e = mpc::launch_tile_scatter_records(d_packed_counts, reinterpret_cast<const uint32_t*>(d_packed_choices), d->d_list, n, K,
+                                                               d->d_counts, reinterpret_cast<uint32_t*>(d->d_choices), d->tiles, d->d_count + 1, s);
+                e != 0)
+                return launch_failed(e);
+        }
+        // 7. records -> container on job slot 0, as a compose finishes, with the seek index from the entropy stage where one is asked for
+        if (!c->jobs[0]) c->jobs[0] = std::make_unique<JobSlot>();
+        JobSlot& js = *c->jobs[0];
+        ContainerJob& job = js.job;
+        if (!job.phase1) {
+            HIP_TRY(hipEventCreateWithFlags(&job.phase1, hipEventDisableTiming | hipEventBlockingSync));
+            HIP_TRY(hipEventCreateWithFlags(&job.done, hipEventDisableTiming | hipEventBlockingSync));
+        }
+        Carve measure;
+        mpc::StreamArgs measured{};
+        carve_stream_buffers(measure, d->tiles, K, true, &measured);
+        if (const mpc_status gs = js.dev.reserve(measure.at, "device staging"); gs != MPC_OK) return gs;
+        GrowBuffer host_stage(GrowBuffer::kPinned);                 // the host route's, should the frame take it: this call's own
+        job.side = job.down = s;
+        job.spin = true;
+        job.host_stage = &host_stage;
+        job.host_offset = 0;
+        job.index_interval = every;
+        job.index_expanded = every != 0;
+        struct Unhook {                                             // the slot is left as mpc_container_job_begin expects it
+            ContainerJob& job;
+            ~Unhook() {
+                job.host_stage = nullptr;
+                job.index_interval = 0;
+                job.index_expanded = false;
+                job.index.clear();
+            }
+        } unhook{job};
+        EntropyBuffers eb;
+        if (!tuning.host_entropy)
+            if (const mpc_status es = entropy_buffers(js.ent, static_cast<size_t>(d->tiles), K, &eb, every ? 2 : 0); es != MPC_OK) return es;
+        HIP_TRY(hipStreamSynchronize(nullptr));                     // a slot carved for another geometry clears its tables on the null stream
+        if (const mpc_status bs = container_begin(job, c, tuning.host_entropy ? nullptr : &eb, tuning.triple_limit, js.dev.data(), d->d_counts,
+                                                  reinterpret_cast<const uint32_t*>(d->d_choices), nullptr, nullptr, width, height, quant);
+            bs != MPC_OK)
+            return bs;
+        if (const mpc_status ts = container_tables(job); ts != MPC_OK) return ts;
+        uint8_t* made = nullptr;
+        size_t made_bytes = 0;
+        if (const mpc_status cs = container_collect(job, &made, &made_bytes); cs != MPC_OK) return cs;
+        if (hipStreamSynchronize(s) != hipSuccess) {
+            std::free(made);
+            return fail(MPC_ERR_HIP, "the container job failed: %s", hipGetErrorString(hipGetLastError()));
+        }
+        if (every) {
+            uint8_t* copy = job.index.empty() ? nullptr : static_cast<uint8_t*>(std::malloc(job.index.size()));
+            if (!copy) {
+                std::free(made);
+                return fail(MPC_ERR_ALLOC, "no seek index");
+            }
+            std::memcpy(copy, job.index.data(), job.index.size());
+            *index = copy;
+            *index_bytes = job.index.size();
+        }
+        *bytes = made;
+        *nbytes = made_bytes;
+        d->valid = true;
+        d->fast = c->fast;
+        d->quant.assign(table, table + 3 * static_cast<size_t>(K));
+        d->changed_all = key;
+        d->info = mpc_delta_info{static_cast<int>(d->tiles), static_cast<int>(n), key ? 1 : 0};
+        *info = d->info;
+        session.keep = true;
+        return MPC_OK;
+    });
+}
+
+}  // extern "C"

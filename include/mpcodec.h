@@ -840,6 +840,95 @@ mpc_status mpc_compose_indexed(mpc_context* ctx, const uint8_t* const* bytes, co
                                unsigned flags, int index_interval, uint8_t** out, size_t* out_bytes, uint8_t** index,
                                size_t* index_out_bytes, int* routes /* [n_parts] */);
 
+/* ---- delta: encode what changed ("Encoder: changed tiles only") ----
+ * The compose's fact, used from frame to frame: a tile's records depend on that tile's pixels alone, so a container made of the
+ * records kept from the last frame and fresh records of the tiles whose pixels changed is, byte for byte, mpc_encode_image of the new
+ * frame.  A session keeps the last frame and its records in device memory, finds the changed tiles on the device and pursues only
+ * those; every container it returns is a whole frame's, a key frame for any decoder.
+ *
+ * mpc_changed_tiles: host only, no context; it defines what the diff kernel computes.  Tile t = tx * tiles_y + ty (tiles of
+ * block_size x block_size pixels, tiles_y = ceil(height / block_size)) is CHANGED iff any of the three bytes of any pixel (x, y) of
+ * it with x < width and y < height differs between prev and cur; pixel (x, y) is the 3 bytes at base + y * stride + 3 * x, a stride
+ * of 0 means 3 * width.  Bytes are compared, no tile is computed.  Only pixel bytes are read: of the last row 3 * width bytes, of the
+ * bytes between a row's end and the next row none.  tiles[ceil(width / block_size) * ceil(height / block_size)] receives the changed
+ * tiles in ascending order, *n their number.  MPC_ERR_ARGUMENT: a null pointer, width or height < 1, block_size outside 1 ... 8, a
+ * stride that is neither 0 nor at least 3 * width.
+ *
+ * mpc_delta_pack_geometry: host only; the packed frame of n listed tiles with at most `rows` tile rows: *packed_rows = R = min(n, rows),
+ * *packed_cols = C = ceil(n / R), *packed_stride = 24 * C bytes between pixel rows, *packed_bytes = 8 * R * stride.  Listed tile j lies at
+ * tile (j / R, j % R) of it, so the tile encoder's own order tx' * R + ty' over the packed frame is j.  n == 0: all four are 0.
+ * MPC_ERR_ARGUMENT: a null pointer, n < 0 or n >= 2^31, rows < 1.  The one function the pack launch and the tests share. */
+mpc_status mpc_changed_tiles(const uint8_t* prev, size_t prev_stride, const uint8_t* cur, size_t cur_stride, int width, int height,
+                             int block_size, int32_t* tiles, int* n);
+mpc_status mpc_delta_pack_geometry(long long n, int rows, int* packed_rows, int* packed_cols, size_t* packed_stride, size_t* packed_bytes);
+
+/* The three kernels on the caller's buffers, asynchronous on `stream`, tiles of 8 x 8 pixels.  Each: MPC_ERR_ARGUMENT, with nothing
+ * enqueued, for a null pointer, width or height < 1, a row_stride that is neither 0 (= 3 * width) nor at least 3 * width;
+ * MPC_ERR_NO_DEVICE for a host-only context.
+ *   mpc_tile_diff_device      mpc_changed_tiles(d_kept, 0, d_rgb, row_stride, width, height, 8, ...) into d_list[tiles] / *d_count (int32),
+ *                             and d_kept (height rows of 3 * width bytes, tightly packed) overwritten with the new pixels.  d_rgb follows
+ *                             the frame layout rules of mpc_encode_tiles_device: any base, any stride, only pixel bytes are read; 8-byte
+ *                             fetches when both bases, row_stride and 3 * width are multiples of 8, byte by byte otherwise.  The list's
+ *                             order is the tiles' own, whatever the kernels' schedule.  The flags and the per-block counts live in a
+ *                             scratch of the context (grown on demand, which synchronises the device): calls of one context go on one
+ *                             stream, or are ordered by the caller.  d_kept and d_rgb must not overlap.
+ *   mpc_pack_tiles_device     the n listed tiles of the frame, side by side, as the packed frame mpc_delta_pack_geometry(n, rows) describes, in
+ *                             d_packed (8-byte aligned; packed_stride 0 = 24 * C, else a multiple of 8 and at least 24 * C, else
+ *                             MPC_ERR_ARGUMENT; bytes of a row behind 24 * C are not written).  Black (0, 0, 0): the pixels of a listed tile
+ *                             that lie outside the image, the R * C - n padding tiles, and a list entry outside [0, tiles), which reads
+ *                             nothing.  Black is exact: YUVFromRGB(0, 0, 0) is +0.0 in all three channels, which is what the tile encoder's
+ *                             zero fill gives the out-of-image pixels of a ragged tile.  n < 1 or rows < 1: MPC_ERR_ARGUMENT.
+ *   mpc_scatter_records_device  records j of the packed frame (counts[j * 3 + ch], choices[(j * 3 + ch) * K + i], K the context's) copied to
+ *                             tile d_list[j] of the whole-frame records of `tiles` tiles: a plain copy (the tile encoder zeroes the entries
+ *                             beyond a count).  A list entry outside [0, tiles) is skipped and sets the context's crop error word
+ *                             (mpc_crop_records_check reads and clears it).  The entries must be distinct.  n < 1 or tiles < 1:
+ *                             MPC_ERR_ARGUMENT. */
+mpc_status mpc_tile_diff_device(mpc_context* ctx, uint8_t* d_kept, const uint8_t* d_rgb, int width, int height, size_t row_stride,
+                                int32_t* d_list, int32_t* d_count, void* stream);
+mpc_status mpc_pack_tiles_device(mpc_context* ctx, const uint8_t* d_rgb, int width, int height, size_t row_stride, const int32_t* d_list,
+                                 int n, int rows, uint8_t* d_packed, size_t packed_stride, void* stream);
+mpc_status mpc_scatter_records_device(mpc_context* ctx, const uint16_t* d_packed_counts, const mpc_basis_choice* d_packed_choices,
+                                      const int32_t* d_list, int n, uint16_t* d_counts, mpc_basis_choice* d_choices, int tiles, void* stream);
+
+/* A session: frames of width x height, one after the other, through one context.  It owns, on the context's device: the last frame
+ * (tightly packed), the whole frame's records, the list, and -- grow-only, sized by the largest call so far -- a host frame's copy and
+ * the packed frame with its records.  It must be destroyed before its context.  mpc_delta_create: MPC_ERR_ARGUMENT for a null pointer
+ * or width or height < 1, MPC_ERR_NO_DEVICE for a host-only context.
+ *
+ * mpc_delta_encode is synchronous, like mpc_encode_image.  rgb: the frame, host memory unless MPC_DELTA_DEVICE_PIXELS; row_stride 0 =
+ * 3 * width; the frame layout rules of mpc_encode_tiles_device.  quant: 3K doubles or NULL = the context's tables as they are now.
+ * THE CONTRACT: *bytes (mpc_free) is byte for byte what mpc_encode_image_device returns for this frame with this quantiser table and
+ * the context's flavour, whatever the history of the session.  index_interval < 0: no index, `index` may be NULL; otherwise
+ * mpc_container_index's interval rules (0 = the default) and *index (mpc_free) is byte for byte mpc_container_index2(*bytes, ...,
+ * interval, MPC_INDEX_EXPANDED), made by the entropy stage.
+ * A call is a KEY FRAME when it is the session's first, when MPC_DELTA_KEY is set, when any of the 3K doubles of the quantiser table
+ * differs from the previous successful call's, when the context's fast flag does, or when the previous call failed behind its checks.
+ * A key frame is pursued whole, straight into the record store (with MPC_DELTA_PACK_ALWAYS through list -> pack -> encode -> scatter
+ * like any other, with every tile listed); info->changed = info->tiles, info->key = 1.
+ * Any other call: the frame is uploaded unless it is device memory; the diff kernel lists the changed tiles and brings the kept copy
+ * up to date; their number n is read back (the call waits for it); with n > 0 the pack kernel makes the packed frame of
+ * MPC_DELTA_PACK_ROWS tile rows at most, mpc_encode_tiles_device pursues it with the call's table, and the scatter kernel puts its
+ * records into the store; with n == 0 no pursuit is launched (mpc_kernel_timing_read counts 0 launches).  Then, key frame or not, one
+ * records-to-container job on job slot 0 makes the container from the store, exactly as mpc_compose_indexed finishes.
+ * Refused with nothing enqueued and the session unchanged (the next call is still a delta): MPC_ERR_ARGUMENT for a null pointer
+ * (`index` and `index_bytes` only with index_interval >= 0), an unknown flag, an interval outside the rules, row_stride != 0 &&
+ * row_stride < 3 * width, a container job slot that is not idle; MPC_ERR_NO_DEVICE for a host-only context.  A failure behind these
+ * checks returns nothing, leaves the context usable and the slots idle, and invalidates the session: its next call is a key frame.
+ *
+ * mpc_delta_changed: the last successful call's list, ascending (a key frame's: every tile); *n its length, also when `capacity` is
+ * too small for it: then MPC_ERR_ARGUMENT and nothing is copied, except that capacity == 0 only asks for *n. */
+typedef struct mpc_delta mpc_delta;
+typedef struct mpc_delta_info { int tiles, changed, key; } mpc_delta_info;
+#define MPC_DELTA_KEY            1u   /* pursue every tile whatever the diff says */
+#define MPC_DELTA_DEVICE_PIXELS  2u   /* rgb is device memory */
+#define MPC_DELTA_PACK_ALWAYS    4u   /* tests: a key frame too goes list -> pack -> encode -> scatter */
+#define MPC_DELTA_PACK_ROWS      64   /* tile rows of the packed frame; it only shapes the tile encoder's queue order */
+mpc_status mpc_delta_create(mpc_context* ctx, int width, int height, mpc_delta** out);
+void       mpc_delta_destroy(mpc_delta* d);
+mpc_status mpc_delta_encode(mpc_delta* d, const uint8_t* rgb, size_t row_stride, const double* quant, unsigned flags, int index_interval,
+                            uint8_t** bytes, size_t* nbytes, uint8_t** index, size_t* index_bytes, mpc_delta_info* info);
+mpc_status mpc_delta_changed(const mpc_delta* d, int32_t* tiles, int capacity, int* n);   /* the last call's list */
+
 /* ---- "-s" patch statistics, Compression.cpp:200-302 ----
  * The reference seeds one std::mt19937, and for every image draws `patches` origins x = rand() % (width - bs),
  * y = rand() % (height - bs), runs CalcMPDynamic on the Y, U and V patch with every quantiser 1.0 and feeds
