@@ -65,6 +65,14 @@ MPC_DELTA_KEY, MPC_DELTA_DEVICE_PIXELS, MPC_DELTA_PACK_ALWAYS = 1, 2, 4   # `fla
 MPC_DELTA_PACK_ROWS = 64
 
 
+class MpcBudgetInfo(C.Structure):                    # mpc_budget_info
+    _fields_ = [("lambda_index", C.c_int), ("probes", C.c_int), ("full_bytes", C.c_size_t), ("sse", C.c_ulonglong),
+                ("full_sse", C.c_ulonglong), ("records", C.c_ulonglong), ("full_records", C.c_ulonglong)]
+
+
+MPC_BUDGET_LAMBDAS = 256
+
+
 def _parts(parts, device_pixels=False):
     """[(source, rect, x, y)] -> (MpcPart array, what must stay alive).  source: an int with rect = (x, y, width, height) or None = all
     of it; or pixels, rect None: an HxWx3 uint8 array (a strided view keeps its row stride), with device_pixels a
@@ -284,6 +292,19 @@ def _bind_bitstream(L):
         L.mpc_delta_encode.argtypes = [vp, vp, C.c_size_t, _dp, C.c_uint, C.c_int, C.POINTER(_u8p), _szp_, C.POINTER(_u8p), _szp_,
                                        C.POINTER(MpcDeltaInfo)]
         L.mpc_delta_changed.argtypes = [vp, _i32p, C.c_int, C.POINTER(C.c_int)]
+    except AttributeError:
+        if not os.environ.get("MPCODEC_LIB"):             # an older build may be loaded for A/B timing only
+            raise
+    _u64p = C.POINTER(C.c_uint64)
+    try:
+        L.mpc_budget_lambda.argtypes = [C.c_int, _u64p]
+        L.mpc_budget_weights.argtypes = [_u8p, C.c_size_t, _u32p]
+        L.mpc_budget_allocate.argtypes = [_u32p, _u16p, C.c_longlong, C.c_int, _u32p, C.c_int, _u8p, _u16p, _u64p]
+        L.mpc_depth_profile_device.argtypes = [vp, vp, vp, _dp, vp, C.c_int, C.c_int, vp, vp]
+        L.mpc_budget_allocate_device.argtypes = [vp, vp, vp, C.c_longlong, _u32p, C.c_int, vp, vp, vp, vp]
+        for f in ("mpc_encode_image_budget", "mpc_encode_image_budget_device"):
+            getattr(L, f).argtypes = [vp, vp, C.c_int, C.c_int, _dp, C.c_size_t, C.c_int, C.POINTER(_u8p), _szp_, C.POINTER(_u8p), _szp_, _u8p,
+                                      C.POINTER(MpcBudgetInfo)]
     except AttributeError:
         if not os.environ.get("MPCODEC_LIB"):             # an older build may be loaded for A/B timing only
             raise
@@ -803,6 +824,53 @@ class DeltaEncoder:
         tiles = np.zeros(max(n.value, 1), np.int32)
         _check(self.L.mpc_delta_changed(self.h, tiles.ctypes.data_as(_i32p), n.value, C.byref(n)))
         return tiles[:n.value]
+
+
+def budget_lambda(j):
+    """mpc_budget_lambda: the multiplier L[j], j = 0 ... 255: 0, then (8 + (j - 1) % 8) << ((j - 1) // 8)"""
+    v = C.c_uint64(0)
+    _check(load_library().mpc_budget_lambda(int(j), C.byref(v)))
+    return v.value
+
+
+def budget_weights(index):
+    """mpc_budget_weights: the rate weights W[ch, i] (uint32 [3, K], in 1/256 bit) from a seek index of a frame's full container"""
+    L = load_library()
+    buf = np.frombuffer(index, np.uint8)
+    h = _IndexHeader()
+    _check(L.mpc_index_info(buf.ctypes.data_as(_u8p), buf.size, C.byref(h)))
+    weights = np.zeros((3, h.K), np.uint32)
+    _check(L.mpc_budget_weights(buf.ctypes.data_as(_u8p), buf.size, weights.ctypes.data_as(_u32p)))
+    return weights
+
+
+def budget_allocate(profile, counts, weights, j):
+    """mpc_budget_allocate: the allocation at multiplier j on the host: profile uint32 [T, K + 1], counts uint16 [T, 3], weights uint32
+    [3, K] -> (depth uint8 [T], cut counts uint16 [T, 3], totals uint64 [3] = distortion, rate, records kept)"""
+    profile = np.ascontiguousarray(profile, np.uint32)
+    T, K = profile.shape[0], profile.shape[1] - 1
+    counts = np.ascontiguousarray(counts, np.uint16).reshape(T, 3)
+    weights = np.ascontiguousarray(weights, np.uint32).reshape(3, K)
+    depth, cut, totals = np.zeros(max(T, 1), np.uint8), np.zeros((max(T, 1), 3), np.uint16), np.zeros(3, np.uint64)
+    _check(load_library().mpc_budget_allocate(profile.ctypes.data_as(_u32p), counts.ctypes.data_as(_u16p), T, K, weights.ctypes.data_as(_u32p),
+                                              int(j), depth.ctypes.data_as(_u8p), cut.ctypes.data_as(_u16p),
+                                              totals.ctypes.data_as(C.POINTER(C.c_uint64))))
+    return depth[:T], cut[:T], totals
+
+
+class BudgetResult:
+    """What encode_image_budget returns: the container (at most the budget's bytes), its seek index (None unless asked for), the depth per
+    tile (uint8; K everywhere when the full container fits) and mpc_budget_info's fields."""
+    __slots__ = ("container", "index", "depth", "lambda_index", "probes", "full_bytes", "sse", "full_sse", "records", "full_records")
+
+    def __init__(self, container, index, depth, info):
+        self.container, self.index, self.depth = container, index, depth
+        for f, _ in MpcBudgetInfo._fields_:
+            setattr(self, f, int(getattr(info, f)))
+
+    def __repr__(self):
+        return (f"BudgetResult(size={len(self.container)}, lambda_index={self.lambda_index}, probes={self.probes}, full_bytes={self.full_bytes}, "
+                f"sse={self.sse}, full_sse={self.full_sse}, records={self.records}, full_records={self.full_records})")
 
 
 def _view_parse(fn, head, buf, idx, view, parse_all):
@@ -1486,6 +1554,52 @@ class CompressionContext:
                                                stream or None))
         if check:
             _check(self.L.mpc_crop_records_check(self.h, stream or None))
+
+    def _encode_budget(self, fn, frame, width, height, budget, quant, index_interval):
+        qp = None
+        if quant is not None:
+            quant = np.ascontiguousarray(quant, np.float64).reshape(3, self.K)
+            qp = quant.ctypes.data_as(_dp)
+        tiles = -(-int(width) // 8) * -(-int(height) // 8)
+        depth = np.zeros(max(tiles, 1), np.uint8)
+        out, n, index, nindex, info = _u8p(), C.c_size_t(0), _u8p(), C.c_size_t(0), MpcBudgetInfo()
+        _check(fn(self.h, frame, int(width), int(height), qp, int(budget), -1 if index_interval is None else int(index_interval), C.byref(out),
+                  C.byref(n), C.byref(index), C.byref(nindex), depth.ctypes.data_as(_u8p), C.byref(info)))
+        blob = _take_bytes(self.L, out, n)
+        return BudgetResult(blob, None if index_interval is None else _take_bytes(self.L, index, nindex), depth[:tiles], info)
+
+    def encode_image_budget(self, rgb, budget, quant=None, index_interval=None):
+        """mpc_encode_image_budget: the frame (uint8 [H, W, 3]) as a container of at most `budget` bytes, every tile cut to the depth that
+        a Lagrange multiplier found by bisection assigns it -> BudgetResult.  index_interval: None = no index, else (0 = the default
+        interval) container_index2(result, interval, expanded) comes with it."""
+        rgb = np.ascontiguousarray(rgb, np.uint8)
+        if rgb.ndim != 3 or rgb.shape[2] != 3:
+            raise ValueError("pixels: an HxWx3 uint8 array")
+        H, W = rgb.shape[:2]
+        return self._encode_budget(self.L.mpc_encode_image_budget, rgb.ctypes.data_as(C.c_void_p), W, H, budget, quant, index_interval)
+
+    def encode_image_budget_device(self, d_rgb, width, height, budget, quant=None, index_interval=None):
+        """The same with the frame in device memory (int from tensor.data_ptr(), tightly packed RGB)."""
+        return self._encode_budget(self.L.mpc_encode_image_budget_device, C.c_void_p(int(d_rgb)), width, height, budget, quant, index_interval)
+
+    def depth_profile_device(self, d_counts, d_choices, d_rgb, width, height, d_profile, quant=None, stream=0, check=True):
+        """mpc_depth_profile_device: whole-frame records and the frame they came from (device pointers) -> d_profile[tiles, K + 1]
+        (uint32): each tile's squared error with every count cut to n = 0 ... K.  check: mpc_crop_records_check behind it, which waits
+        for `stream` and raises MpcError(MPC_ERR_BITSTREAM) if a record was not prefix-consistent or a count above K."""
+        qp = None
+        if quant is not None:
+            quant = np.ascontiguousarray(quant, np.float64).reshape(3, self.K)
+            qp = quant.ctypes.data_as(_dp)
+        _check(self.L.mpc_depth_profile_device(self.h, d_counts, d_choices, qp, d_rgb, int(width), int(height), d_profile, stream or None))
+        if check:
+            _check(self.L.mpc_crop_records_check(self.h, stream or None))
+
+    def budget_allocate_device(self, d_profile, d_counts, tiles, weights, j, d_depth, d_out_counts, d_totals, stream=0):
+        """mpc_budget_allocate_device: budget_allocate on the device; weights uint32 [3, K] in host memory; d_depth[tiles] (uint8),
+        d_out_counts[tiles, 3] (uint16), d_totals[3] (uint64, zeroed first).  Asynchronous."""
+        weights = np.ascontiguousarray(weights, np.uint32).reshape(3, self.K)
+        _check(self.L.mpc_budget_allocate_device(self.h, d_profile, d_counts, int(tiles), weights.ctypes.data_as(_u32p), int(j), d_depth,
+                                                 d_out_counts, d_totals, stream or None))
 
     def delta_encoder(self, width, height):
         """mpc_delta_create: a DeltaEncoder for frames of width x height through this context"""

@@ -1,0 +1,71 @@
+// host_budget.cpp -- product: the rate control's host definitions (host_budget.h): what mp_budget.hip's allocation kernel computes,
+// and the rate weights the search of mpc_encode_image_budget takes from the full container's seek index.
+#include "host_budget.h"
+
+#include "host_bitstream.h"
+
+namespace mpc {
+
+int budget_weights(const uint8_t* index, size_t index_bytes, uint32_t* weights, int* K_out) {
+    ContainerIndex x;
+    if (!read_container_index(index, index_bytes, x)) return 1;
+    const int K = x.K;
+    if (K < 1 || K > 32 || x.streams.size() != 1 + 6 * static_cast<size_t>(K)) return 1;
+    if (x.serial_only) return 2;
+    if (K_out) *K_out = K;
+    for (int ch = 0; ch < 3; ++ch)
+        for (int i = 0; i < K; ++i) {
+            const size_t a = 1 + 2 * static_cast<size_t>(K) * ch + 2 * static_cast<size_t>(i);
+            const IndexStream& first = x.streams[a];
+            const IndexStream& second = x.streams[a + 1];
+            if (second.end_bit < first.wrapper_bit) return 1;
+            const uint64_t bits = second.end_bit - first.wrapper_bit, n = first.expect;
+            uint64_t w = kBudgetWeightMin;
+            if (n != 0) {
+                // 256 * bits + n / 2 cannot wrap for any container that fits memory; a blob that says otherwise gets the clamp
+                w = bits > (~uint64_t{0} >> 9) ? kBudgetWeightMax : (256 * bits + n / 2) / n;
+                if (w < kBudgetWeightMin) w = kBudgetWeightMin;
+                if (w > kBudgetWeightMax) w = kBudgetWeightMax;
+            }
+            if (weights) weights[ch * K + i] = static_cast<uint32_t>(w);
+        }
+    return 0;
+}
+
+void budget_allocate(const uint32_t* profile, const uint16_t* counts, long long tiles, int K, const uint32_t* weights, int j, uint8_t* depth,
+                     uint16_t* out_counts, uint64_t totals[3]) {
+    const uint64_t L = budget_lambda(j);
+    uint32_t below[3][33];                              // below[ch][m] = W[ch][0] + ... + W[ch][m - 1]
+    for (int ch = 0; ch < 3; ++ch) {
+        below[ch][0] = 0;
+        for (int i = 0; i < K; ++i) below[ch][i + 1] = below[ch][i] + weights[ch * K + i];
+    }
+    totals[0] = totals[1] = totals[2] = 0;
+    for (long long t = 0; t < tiles; ++t) {
+        int cnt[3];
+        for (int ch = 0; ch < 3; ++ch) cnt[ch] = counts[t * 3 + ch] > K ? K : counts[t * 3 + ch];
+        const uint32_t* P = profile + t * (K + 1);
+        uint64_t best = 0, best_rate = 0;
+        int at = 0;
+        for (int n = 0; n <= K; ++n) {
+            uint64_t rate = 0;
+            for (int ch = 0; ch < 3; ++ch) rate += below[ch][n < cnt[ch] ? n : cnt[ch]];
+            const uint64_t J = (static_cast<uint64_t>(P[n]) << kBudgetDistortionShift) + L * rate;
+            if (n == 0 || J < best) {
+                best = J;
+                best_rate = rate;
+                at = n;
+            }
+        }
+        if (depth) depth[t] = static_cast<uint8_t>(at);
+        totals[0] += P[at];
+        totals[1] += best_rate;
+        for (int ch = 0; ch < 3; ++ch) {
+            const int kept = at < cnt[ch] ? at : cnt[ch];
+            if (out_counts) out_counts[t * 3 + ch] = static_cast<uint16_t>(kept);
+            totals[2] += static_cast<uint64_t>(kept);
+        }
+    }
+}
+
+}  // namespace mpc

@@ -1,0 +1,34 @@
+// host_budget.h -- product: the host's definition of the rate control behind mpc_encode_image_budget (include/mpcodec.h, "budget";
+// DESIGN.md 4, "Encoder: a byte budget"): the multiplier table, the rate weights from a seek index, the allocation at one multiplier.
+// Knows neither HIP nor the C ABI and builds on its own with host_bitstream / host_container (tests/cpp/asan_budget.cpp).
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+
+namespace mpc {
+
+constexpr int kBudgetLambdas = 256;                 // multipliers j = 0 ... 255
+constexpr uint32_t kBudgetWeightMin = 256;          // one bit, in 1/256 bit
+constexpr uint32_t kBudgetWeightMax = 1u << 20;     // 4096 bits
+constexpr int kBudgetDistortionShift = 16;          // J = P * 65536 + L * R
+
+// L[0] = 0, L[j] = (8 + (j - 1) % 8) << ((j - 1) / 8): a geometric grid, eight values an octave (steps of 12.5 % down to 6.7 %).
+// L[255] = 14 << 31.  A record weighs at least 256 (one bit), so keeping any record costs at least 14 * 2^39 > 2^42, while a tile's
+// largest possible distortion term is 64 * 3 * 255^2 * 65536 < 2^40: at j = 255 every depth is 0.
+inline uint64_t budget_lambda(int j) { return j <= 0 ? 0 : static_cast<uint64_t>(8 + (j - 1) % 8) << ((j - 1) / 8); }
+
+// W[ch][i] at weights[ch * K + i], K the index's, from a seek index (either version) of the frame's full container: with
+// a = 1 + 2K * ch + 2i, bits = end_bit(a + 1) - wrapper_bit(a), n = expect(a): clamp((256 * bits + n / 2) / n, 256, 2^20), 256 when
+// n = 0.  Returns 0; 1 = not a seek index (or one whose streams do not lie one behind the other); 2 = a serial-only index.
+// weights == nullptr: the verdict alone.  *K_out (optional): the index's K
+int budget_weights(const uint8_t* index, size_t index_bytes, uint32_t* weights, int* K_out = nullptr);
+
+// The allocation at multiplier j over `tiles` tiles: profile[t * (K + 1) + n], counts[t * 3 + ch] (a count above K is used as K),
+// weights[ch * K + i].  R(t, n) = sum over ch, i < min(n, count) of W[ch][i]; J(t, n) = P * 65536 + L[j] * R in u64; depth[t] = the
+// smallest n of 0 ... K that minimises J; out_counts = min(count, depth[t]); totals[0] = sum P[t][depth], [1] = sum R[t][depth],
+// [2] = the records kept.  depth, out_counts: each may be null.  The caller has checked: 1 <= K <= 32, 0 <= j < 256, tiles >= 0
+void budget_allocate(const uint32_t* profile, const uint16_t* counts, long long tiles, int K, const uint32_t* weights, int j, uint8_t* depth,
+                     uint16_t* out_counts, uint64_t totals[3]);
+
+}  // namespace mpc

@@ -1,0 +1,247 @@
+// mp_budget.hip -- product: the rate control's kernels (include/mpcodec.h, "budget"; DESIGN.md 4, "Encoder: a byte budget").
+//
+// The container is layered by pursuit step and nothing reads a record beyond its count, so cutting a tile to its first n steps is a
+// change of three counts.  Two kernels tell the search of mpc_encode_image_budget where to cut:
+//   profile   per tile the decoder's squared error at every depth n = 0 ... K, from one replay of the records
+//   allocate  per tile the depth that minimises distortion + multiplier * rate, the cut counts and the frame's totals
+// Both are one wave per tile and bandwidth-light: the profile reads 3K record words, at most 3K dictionary rows of 64 values and
+// 192 pixel bytes per tile, the allocation K + 1 words.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <type_traits>
+
+#include "mp_device.h"
+
+namespace mpc {
+
+namespace {
+constexpr int kPixels = 64;             // an 8 x 8 tile: a row of the dictionary
+constexpr int kProfileWaves = 4;        // tiles a workgroup works on at a time
+constexpr int kAllocateWaves = 4;
+}  // namespace
+
+// --------------------------------------------------------------------------------------------------
+// depth profile: one wave per tile, LANE = PIXEL, as in mp_decode_kernel.  The rows of all three channels' records are resolved
+// once, the way reconstruct_tile_pixel (mp_kernels.hip) resolves them -- lane i takes record i, its choice by a wave scan over the
+// zig-zag deltas, its row by the walk over the channel's base choices -- with one more condition: the base choice that unlocks a
+// detail row must lie at a step below the record's own.  Then the row of record i is the same whatever depth >= i + 1 the tile is
+// cut to, and the accumulation of depth n is a prefix of that of depth n + 1: the walk n = 1 ... K adds step n - 1 of every channel
+// that has it (one rounding for the product, one for the sum, no FMA: reconstruct_tile_pixel's arithmetic in its order), and after
+// each n RGBFromYUV's rounding and clamp, the integer dr^2 + dg^2 + db^2 of the pixels inside the frame and a wave sum give what
+// mp_distortion_kernel gives for the counts cut to n.  Lane n keeps P[n]; depths above the tile's largest count repeat the last
+// value; the tile's K + 1 words leave in one contiguous store.  A record whose row is not in the dictionary of its earlier steps
+// (a forward reference, a choice outside the dictionary, a negative one) adds nothing and sets *error, and so does a count above
+// K, which is used as K: every address comes from the tile grid and from rows checked against the block table.
+// --------------------------------------------------------------------------------------------------
+template <class T>
+__global__ __launch_bounds__(64 * kProfileWaves) void mp_depth_profile_kernel(const DictDevice dict, const ProfileParams p)
+{
+    constexpr bool kFast = std::is_same<T, float>::value;
+    const T* const base_rows = reinterpret_cast<const T*>(kFast ? static_cast<const void*>(dict.base32) : static_cast<const void*>(dict.base));
+    const T* const detail_rows = reinterpret_cast<const T*>(kFast ? static_cast<const void*>(dict.detail32) : static_cast<const void*>(dict.detail));
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int K = p.K;
+    const long long tiles = (long long)p.tiles_x * p.tiles_y;
+    for (long long t = (long long)blockIdx.x * kProfileWaves + wave; t < tiles; t += (long long)gridDim.x * kProfileWaves) {
+        uint32_t rec[3];
+        long long row_at[3];            // element offset of this lane's record's row; -1: none
+        int in_base[3], cnt[3];
+        int deepest = 0;
+        bool bad = false;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            int count = p.counts[t * 3 + ch];
+            if (count > K) {
+                count = K;
+                bad = true;
+            }
+            cnt[ch] = count;
+            deepest = count > deepest ? count : deepest;
+            const uint32_t* recs = p.choices + (t * 3 + ch) * K;
+            const uint32_t r = lane < count ? recs[lane] : 0u;
+            const unsigned delta = r & 0xFFFFu;
+            int choice = lane == 0 ? (int)delta : (int)((delta >> 1) ^ (0u - (delta & 1u)));
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const int up = __shfl_up(choice, o);
+                if (lane >= o) choice += up;
+            }
+            long long at = -1;
+            int base = 0;
+            if (choice >= 0 && choice < dict.num_base) {
+                at = (long long)choice * kPixels;
+                base = 1;
+            }
+            int off = dict.num_base;
+            bool open = lane < count && choice >= dict.num_base;
+            for (int k = 0; k < count; ++k) {
+                const int walk = __shfl(choice, k);
+                if (walk >= 0 && walk < dict.num_base) {
+                    const int rows = dict.block_rows[walk];
+                    if (open && choice < off + rows) {
+                        if (k < lane) at = ((long long)ch * dict.detail_rows + dict.block_row_off[walk] + (choice - off)) * kPixels;
+                        open = false;
+                    }
+                    off += rows;
+                }
+            }
+            if (lane < count && at < 0) bad = true;
+            rec[ch] = r;
+            row_at[ch] = at;
+            in_base[ch] = base;
+        }
+        if (__any(bad ? 1 : 0) && lane == 0) *p.error = 1;
+        const int tx = (int)(t / p.tiles_y), ty = (int)(t - (long long)tx * p.tiles_y);
+        const int u = tx * 8 + (lane & 7), v = ty * 8 + (lane >> 3);
+        const bool inside = u < p.width && v < p.height;
+        int r0 = 0, g0 = 0, b0 = 0;
+        if (inside) {
+            const uint8_t* px = p.original + 3 * ((long long)v * p.width + u);
+            r0 = px[0];
+            g0 = px[1];
+            b0 = px[2];
+        }
+        T acc[3] = {0, 0, 0};
+        uint32_t mine = 0;
+        int e = 0;
+        for (int n = 0; n <= K; ++n) {
+            if (n <= deepest) {                                     // uniform: every lane takes part in every exchange
+                if (n >= 1) {
+                    const int i = n - 1;
+#pragma unroll
+                    for (int ch = 0; ch < 3; ++ch) {
+                        if (i < cnt[ch]) {
+                            const uint32_t ri = (uint32_t)__shfl((int)rec[ch], i);
+                            const unsigned zz = ri >> 16;
+                            const int q = (int)((zz >> 1) ^ (0u - (zz & 1u)));
+                            const T coeff = (T)p.quant[ch * K + i] * (T)q;
+                            const long long at = __shfl(row_at[ch], i);
+                            const int from_base = __shfl(in_base[ch], i);
+                            if (at >= 0) {
+                                const T* row = (from_base ? base_rows : detail_rows) + at;
+                                const T term = row[lane] * coeff;
+                                acc[ch] = acc[ch] + term;
+                            }
+                        }
+                    }
+                }
+                const double Y = (double)acc[0], U = (double)acc[1], V = (double)acc[2];
+                double rr = __builtin_round(Y + 1.13983 * V);
+                double gg = __builtin_round(Y - 0.39466 * U - 0.58060 * V);
+                double bb = __builtin_round(Y + 2.03211 * U);
+                rr = rr < 0.0 ? 0.0 : (rr > 255.0 ? 255.0 : rr);
+                gg = gg < 0.0 ? 0.0 : (gg > 255.0 ? 255.0 : gg);
+                bb = bb < 0.0 ? 0.0 : (bb > 255.0 ? 255.0 : bb);
+                e = 0;
+                if (inside) {
+                    const int dr = (int)rr - r0, dg = (int)gg - g0, db = (int)bb - b0;
+                    e = dr * dr + dg * dg + db * db;
+                }
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) e += __shfl_xor(e, o);
+            }
+            if (lane == n) mine = (uint32_t)e;
+        }
+        if (lane <= K) p.profile[t * (K + 1) + lane] = mine;
+    }
+}
+
+// --------------------------------------------------------------------------------------------------
+// allocation: one wave per tile, lane n = depth n.  The K + 1 profile words of a tile are one coalesced load; the rate of a depth
+// comes from the per-channel prefix sums of the weights, which the workgroup builds once in LDS from the weights in its arguments;
+// J = P * 65536 + lambda * R (u64: P < 2^24, lambda < 2^35, R < 2^27).  The minimum is taken over the pair (J, n) in that order by a
+// butterfly, so equal J leave the smallest n -- J has no six spare bits to pack n into.  Lanes above K hold J = 2^64 - 1, which no
+// depth reaches.  Lanes 0 ... 2 store the cut counts, lane 0 the depth; a wave adds up its tiles' distortion, rate and records
+// kept, the waves' sums meet in LDS, and threads 0 ... 2 add one total each to the frame's: one 64-bit integer atomic per total
+// and workgroup, as in mp_distortion_kernel, so the totals do not depend on the schedule.  Every address comes from the tile grid;
+// a count above K is used as K.
+// --------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64 * kAllocateWaves) void mp_budget_allocate_kernel(const AllocateParams p)
+{
+    __shared__ uint32_t below[3][kMaxDeviceK + 1];                  // below[ch][m] = W[ch][0] + ... + W[ch][m - 1]
+    __shared__ unsigned long long wave_sum[kAllocateWaves][3];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int K = p.K;
+    if (threadIdx.x < 3) {
+        uint32_t sum = 0;
+        below[threadIdx.x][0] = 0;
+        for (int i = 0; i < K; ++i) {
+            sum += p.weights[threadIdx.x * K + i];
+            below[threadIdx.x][i + 1] = sum;
+        }
+    }
+    __syncthreads();
+    unsigned long long distortion = 0, rate = 0, records = 0;
+    for (long long t = (long long)blockIdx.x * kAllocateWaves + wave; t < p.tiles; t += (long long)gridDim.x * kAllocateWaves) {
+        int cnt[3];
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            const int count = p.counts[t * 3 + ch];
+            cnt[ch] = count > K ? K : count;
+        }
+        uint32_t P = 0, R = 0;
+        unsigned long long J = ~0ull;
+        if (lane <= K) {
+            P = p.profile[t * (K + 1) + lane];
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) R += below[ch][lane < cnt[ch] ? lane : cnt[ch]];
+            J = ((unsigned long long)P << 16) + p.lambda * R;
+        }
+        int depth = lane;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long other = __shfl_xor(J, o);
+            const int other_depth = __shfl_xor(depth, o);
+            if (other < J || (other == J && other_depth < depth)) {
+                J = other;
+                depth = other_depth;
+            }
+        }
+        // every lane holds the winner; depth <= K because lane 0's J is below 2^63
+        const uint32_t kept_P = (uint32_t)__shfl((int)P, depth), kept_R = (uint32_t)__shfl((int)R, depth);
+        if (lane == 0) p.depth[t] = (uint8_t)depth;
+        if (lane < 3) {
+            const int mine = lane == 0 ? cnt[0] : lane == 1 ? cnt[1] : cnt[2];
+            p.out_counts[t * 3 + lane] = (uint16_t)(mine < depth ? mine : depth);
+        }
+        distortion += kept_P;
+        rate += kept_R;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) records += (unsigned)(cnt[ch] < depth ? cnt[ch] : depth);
+    }
+    if (lane == 0) {
+        wave_sum[wave][0] = distortion;
+        wave_sum[wave][1] = rate;
+        wave_sum[wave][2] = records;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        unsigned long long total = 0;
+        for (int w = 0; w < kAllocateWaves; ++w) total += wave_sum[w][threadIdx.x];
+        if (total) atomicAdd(p.totals + threadIdx.x, total);
+    }
+}
+
+int launch_depth_profile(const DictDevice& dict, const ProfileParams& p, void* stream)
+{
+    if (p.K < 1 || p.K > kMaxDeviceK || p.width < 1 || p.height < 1 || p.tiles_x != (p.width + 7) / 8 || p.tiles_y != (p.height + 7) / 8)
+        return (int)hipErrorInvalidValue;
+    const long long tiles = (long long)p.tiles_x * p.tiles_y;
+    const long long groups = (tiles + kProfileWaves - 1) / kProfileWaves;
+    const unsigned blocks = (unsigned)(groups < 4096 ? groups : 4096);
+    if (p.fast) hipLaunchKernelGGL(mp_depth_profile_kernel<float>, dim3(blocks), dim3(64 * kProfileWaves), 0, (hipStream_t)stream, dict, p);
+    else hipLaunchKernelGGL(mp_depth_profile_kernel<double>, dim3(blocks), dim3(64 * kProfileWaves), 0, (hipStream_t)stream, dict, p);
+    return (int)hipGetLastError();
+}
+
+int launch_budget_allocate(const AllocateParams& p, void* stream)
+{
+    if (p.K < 1 || p.K > kMaxDeviceK || p.tiles < 1) return (int)hipErrorInvalidValue;
+    const long long groups = (p.tiles + kAllocateWaves - 1) / kAllocateWaves;
+    const unsigned blocks = (unsigned)(groups < 4096 ? groups : 4096);
+    hipLaunchKernelGGL(mp_budget_allocate_kernel, dim3(blocks), dim3(64 * kAllocateWaves), 0, (hipStream_t)stream, p);
+    return (int)hipGetLastError();
+}
+
+}  // namespace mpc

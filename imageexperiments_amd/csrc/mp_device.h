@@ -9,6 +9,7 @@
 //   mp_unpack.hip    the decoder's mirror of those two: run-length expansion and DC sums of coded streams (UnpackArgs)
 //   mp_parse.hip     the entropy codes of a container undone chunk by chunk from a seek index (ParseArgs)
 //   mp_scan.hip      that seek index's checkpoints found by a scan over every bit position of a stream (ScanArgs)
+//   mp_budget.hip    rate control: a tile's squared error at every depth, the depth that minimises distortion + multiplier * rate
 //   mp_kernels.hip   the decoder, the symbol histogram, and the product's own cross-check of the tile encoder: a STEP-SYNCHRONOUS
 //                    pursuit that correlates every row exactly (a short sequence of kernels per MP step over the active
 //                    tile-channels: init, fill, base sweep, detail sweep, finish, update), behind MPC_PATH=steps / MPC_FILTER=0
@@ -321,6 +322,37 @@ int launch_tile_pack(const uint8_t* rgb, int width, int height, size_t row_strid
 // skipped and sets *error.  The entries are distinct
 int launch_tile_scatter_records(const uint16_t* packed_counts, const uint32_t* packed_choices, const int32_t* list, long long n, int K,
                                 uint16_t* counts, uint32_t* choices, long long tiles, int* error, void* stream);
+
+// ---- rate control (mp_budget.hip; include/mpcodec.h, "budget") ----
+// The depth profile: profile[t * (K + 1) + n] = the tile SSE launch_distortion gives for the same records with every count replaced
+// by min(count, n), n = 0 ... K, for prefix-consistent records (a record's row lies in the dictionary its earlier steps built).  A
+// record that is not, a row outside its dictionary and a count above K (used as K) set *error; no address comes from such a record
+struct ProfileParams {
+    const uint16_t* counts;          // [tiles][3], tile t = tx*tiles_y + ty
+    const uint32_t* choices;         // [tiles][3][K]
+    const double* quant;             // [3][K] (device), the values the container header carries
+    int K;
+    int width, height, tiles_x, tiles_y;
+    const uint8_t* original;         // [height][width][3] (device)
+    uint32_t* profile;               // [tiles][K + 1]
+    int* error;
+    int fast;                        // != 0: FromCoeffsDynamicFast (float)
+};
+int launch_depth_profile(const DictDevice& dict, const ProfileParams& p, void* stream);
+// The allocation at one multiplier (host_budget.h: budget_allocate defines it): depth[tiles], out_counts[tiles][3], and
+// totals[0 .. 2] += the distortion, the rate and the records kept (the caller zeroes them).  The weights travel in the kernel's arguments
+struct AllocateParams {
+    const uint32_t* profile;         // [tiles][K + 1]
+    const uint16_t* counts;          // [tiles][3]
+    long long tiles;
+    int K;
+    unsigned long long lambda;
+    uint8_t* depth;
+    uint16_t* out_counts;
+    unsigned long long* totals;      // [3]
+    uint32_t weights[3 * kMaxDeviceK];   // [3][K]
+};
+int launch_budget_allocate(const AllocateParams& p, void* stream);
 
 // ---- the decoder's per-symbol work in front of the gather (mp_unpack.hip): run-length expansion, DC sums ----
 constexpr int kUnpackBlock = 2048;      // coded symbols per workgroup

@@ -12,6 +12,7 @@
 //   mpcodec_index.cpp      the seek index's host-only entry points (mpc_container_index, mpc_parse_container_by_index)
 //   mpcodec_debug.cpp      the tests' entry points to the screen's tables (mpc_debug_*, mpc_filter_tiles)
 //   mpcodec_delta.cpp      the delta encoder (mpc_delta_*): diff against the kept frame, pursuit of the changed tiles only
+//   mpcodec_budget.cpp     encode to a byte budget (mpc_encode_image_budget): depth profile, allocation, the search over the multiplier
 #pragma once
 
 #include "../../include/mpcodec.h"
@@ -353,6 +354,8 @@ struct mpc_context {
     GrowBuffer delta_scratch{GrowBuffer::kDevice};   // mpc_tile_diff_device: the flags and block counts (mpc::tile_diff_scratch_bytes)
     GrowBuffer compose_dev{GrowBuffer::kDevice};     // mpc_compose_indexed: the destination's records, the owner map, the pixel parts' patches
     hipStream_t compose_side = nullptr;              // ... the pixel parts' stream and the final container job's, made on first use
+    GrowBuffer budget_dev{GrowBuffer::kDevice};      // mpc_encode_image_budget: the frame, its records, the cut counts, the profile, two depth maps
+    hipStream_t budget_stream = nullptr;             // ... everything of such a call, made on first use
     // grow-only staging for the host-buffer encode entry points (mpc_encode_tiles / mpc_encode_image(s)): allocating and freeing
     // them per call cost several times the encode itself.  The decoder stages in its slots' own buffers (DecodeSlot).
     GrowBuffer stage{GrowBuffer::kDevice};

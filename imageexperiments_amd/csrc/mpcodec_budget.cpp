@@ -1,0 +1,381 @@
+// mpcodec_budget.cpp -- product: encode to a byte budget (include/mpcodec.h, "budget"; DESIGN.md 4, "Encoder: a byte budget").
+// One pursuit, the full container with its seek index, the depth profile (mp_budget.hip), then a bisection over the multiplier
+// table: every probe is the allocation kernel and one records-to-container job on the same records with the cut counts array.
+#include <cstring>
+#include <string>
+
+#include "host_budget.h"
+#include "host_codec.h"
+#include "mpc_internal.h"
+
+static_assert(mpc::kBudgetLambdas == MPC_BUDGET_LAMBDAS, "one size for the multiplier table");
+
+namespace {
+
+mpc_status no_device() { return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback"); }
+
+// mpc_rate_distortion's geometry
+mpc_status geometry(int width, int height, long long* tiles) {
+    if (width < 1 || height < 1) return fail(MPC_ERR_ARGUMENT, "bad geometry %dx%d", width, height);
+    *tiles = static_cast<long long>((width + 7) / 8) * ((height + 7) / 8);
+    if (*tiles * 3 >= (1LL << 31)) return fail(MPC_ERR_ARGUMENT, "frame too large");
+    return MPC_OK;
+}
+
+// the quantiser steps the container header carries, on the device for this call
+mpc_status header_quant_device(mpc_context* c, const double* quant, hipStream_t s, const double** d_q) {
+    const double* q = quant ? quant : c->quant.data();
+    std::vector<double> carried(3 * static_cast<size_t>(c->K));
+    for (size_t i = 0; i < carried.size(); ++i) carried[i] = static_cast<double>(mpc::header_quant(q[i]));
+    return call_quant(c, carried.data(), s, d_q);
+}
+
+mpc_status profile_on_device(mpc_context* c, const uint16_t* d_counts, const mpc_basis_choice* d_choices, const double* quant,
+                             const uint8_t* d_rgb, int width, int height, uint32_t* d_profile, int* d_error, hipStream_t s) {
+    const double* d_q = nullptr;
+    if (const mpc_status qs = header_quant_device(c, quant, s, &d_q); qs != MPC_OK) return qs;
+    mpc::ProfileParams p{};
+    p.counts = d_counts;
+    p.choices = reinterpret_cast<const uint32_t*>(d_choices);
+    p.quant = d_q;
+    p.K = c->K;
+    p.width = width;
+    p.height = height;
+    p.tiles_x = (width + 7) / 8;
+    p.tiles_y = (height + 7) / 8;
+    p.original = d_rgb;
+    p.profile = d_profile;
+    p.error = d_error;
+    p.fast = c->fast ? 1 : 0;
+    const int err = mpc::launch_depth_profile(dict_device(c), p, s);
+    if (err != 0) return launch_failed(err);
+    return MPC_OK;
+}
+
+// d_totals zeroed on `s`, then the kernel
+mpc_status allocate_on_device(const mpc_context* c, const uint32_t* d_profile, const uint16_t* d_counts, long long tiles, const uint32_t* weights,
+                              int j, uint8_t* d_depth, uint16_t* d_out_counts, unsigned long long* d_totals, hipStream_t s) {
+    HIP_TRY(hipMemsetAsync(d_totals, 0, 3 * sizeof(unsigned long long), s));
+    mpc::AllocateParams p{};
+    p.profile = d_profile;
+    p.counts = d_counts;
+    p.tiles = tiles;
+    p.K = c->K;
+    p.lambda = mpc::budget_lambda(j);
+    p.depth = d_depth;
+    p.out_counts = d_out_counts;
+    p.totals = d_totals;
+    std::memcpy(p.weights, weights, sizeof(uint32_t) * 3 * static_cast<size_t>(c->K));
+    const int err = mpc::launch_budget_allocate(p, s);
+    if (err != 0) return launch_failed(err);
+    return MPC_OK;
+}
+
+// a container and its seek index in malloc'ed memory, released unless taken
+struct Made {
+    uint8_t* bytes = nullptr;
+    size_t nbytes = 0;
+    std::vector<uint8_t> index;
+    Made() = default;
+    Made(const Made&) = delete;
+    Made& operator=(const Made&) = delete;
+    ~Made() { std::free(bytes); }
+    void swap(Made& o) {
+        std::swap(bytes, o.bytes);
+        std::swap(nbytes, o.nbytes);
+        index.swap(o.index);
+    }
+};
+
+// One records-to-container job on job slot 0 with everything on `s`, as mpc_delta_encode finishes: the container of `d_counts` /
+// `d_choices`, and with `every` != 0 its version-2 seek index from the entropy stage.  The call waits for the container.
+mpc_status container_of(mpc_context* c, const Tuning& tuning, hipStream_t s, const uint16_t* d_counts, const mpc_basis_choice* d_choices,
+                        long long tiles, int width, int height, const double* quant, unsigned every, Made* out) {
+    const int K = c->K;
+    if (!c->jobs[0]) c->jobs[0] = std::make_unique<JobSlot>();
+    JobSlot& js = *c->jobs[0];
+    ContainerJob& job = js.job;
+    if (!job.phase1) {
+        HIP_TRY(hipEventCreateWithFlags(&job.phase1, hipEventDisableTiming | hipEventBlockingSync));
+        HIP_TRY(hipEventCreateWithFlags(&job.done, hipEventDisableTiming | hipEventBlockingSync));
+    }
+    Carve measure;
+    mpc::StreamArgs measured{};
+    carve_stream_buffers(measure, tiles, K, true, &measured);
+    if (const mpc_status gs = js.dev.reserve(measure.at, "device staging"); gs != MPC_OK) return gs;
+    GrowBuffer host_stage(GrowBuffer::kPinned);                 // the host route's, should the frame take it: this job's own
+    job.side = job.down = s;
+    job.spin = true;
+    job.host_stage = &host_stage;
+    job.host_offset = 0;
+    job.index_interval = every;
+    job.index_expanded = every != 0;
+    struct Unhook {                                             // the slot is left as mpc_container_job_begin expects it
+        ContainerJob& job;
+        ~Unhook() {
+            job.host_stage = nullptr;
+            job.index_interval = 0;
+            job.index_expanded = false;
+            job.index.clear();
+        }
+    } unhook{job};
+    EntropyBuffers eb;
+    if (!tuning.host_entropy)
+        if (const mpc_status es = entropy_buffers(js.ent, static_cast<size_t>(tiles), K, &eb, every ? 2 : 0); es != MPC_OK) return es;
+    HIP_TRY(hipStreamSynchronize(nullptr));                     // a slot carved for another geometry clears its tables on the null stream
+    if (const mpc_status bs = container_begin(job, c, tuning.host_entropy ? nullptr : &eb, tuning.triple_limit, js.dev.data(), d_counts,
+                                              reinterpret_cast<const uint32_t*>(d_choices), nullptr, nullptr, width, height, quant);
+        bs != MPC_OK)
+        return bs;
+    if (const mpc_status ts = container_tables(job); ts != MPC_OK) return ts;
+    uint8_t* made = nullptr;
+    size_t made_bytes = 0;
+    if (const mpc_status cs = container_collect(job, &made, &made_bytes); cs != MPC_OK) return cs;
+    if (hipStreamSynchronize(s) != hipSuccess) {
+        std::free(made);
+        return fail(MPC_ERR_HIP, "the container job failed: %s", hipGetErrorString(hipGetLastError()));
+    }
+    if (every && job.index.empty()) {
+        std::free(made);
+        return fail(MPC_ERR_ALLOC, "no seek index");
+    }
+    std::free(out->bytes);
+    out->bytes = made;
+    out->nbytes = made_bytes;
+    out->index.assign(job.index.begin(), job.index.end());
+    return MPC_OK;
+}
+
+mpc_status encode_budget(mpc_context* c, const uint8_t* rgb, bool on_device, int width, int height, const double* quant, size_t budget,
+                         int index_interval, uint8_t** bytes, size_t* nbytes, uint8_t** index, size_t* index_bytes, uint8_t* depth,
+                         mpc_budget_info* info) {
+    return guarded([&]() -> mpc_status {
+        if (!c || !rgb || !bytes || !nbytes || !info) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (index_interval >= 0 && (!index || !index_bytes)) return fail(MPC_ERR_ARGUMENT, "null argument");
+        long long tiles = 0;
+        if (const mpc_status gs = geometry(width, height, &tiles); gs != MPC_OK) return gs;
+        if (budget == 0) return fail(MPC_ERR_ARGUMENT, "a budget of 0 bytes");
+        if (index_interval > 0 && (index_interval < static_cast<int>(mpc::kIndexIntervalMin) || index_interval > static_cast<int>(mpc::kIndexIntervalMax)))
+            return fail(MPC_ERR_ARGUMENT, "interval %d: 0 or %u to %u", index_interval, mpc::kIndexIntervalMin, mpc::kIndexIntervalMax);
+        // the index the caller gets; the full container's is made in any case: the weights come from it
+        const unsigned every = index_interval < 0 ? 0u : index_interval ? static_cast<unsigned>(index_interval) : mpc::kIndexIntervalDefault;
+        if (c->device < 0) return no_device();
+        std::lock_guard<std::recursive_mutex> one_host_call(c->host_calls);
+        for (int k = 0; k < mpc_context::kSeqSlots; ++k)
+            if (c->jobs[k] && c->jobs[k]->stage != 0) return fail(MPC_ERR_ARGUMENT, "container job slot %d is busy", k);
+        *bytes = nullptr;
+        *nbytes = 0;
+        if (index) *index = nullptr;
+        if (index_bytes) *index_bytes = 0;
+        *info = mpc_budget_info{};
+        mpc_budget_info got{};                                      // the caller's only on success
+        HIP_TRY(hipSetDevice(c->device));
+        const Tuning tuning = read_tuning();
+        const int K = c->K, tiles_y = (height + 7) / 8;
+        const size_t n_tc = 3 * static_cast<size_t>(tiles), row = 3 * static_cast<size_t>(width);
+        if (!c->budget_stream) HIP_TRY(hipStreamCreateWithFlags(&c->budget_stream, hipStreamNonBlocking));
+        hipStream_t s = c->budget_stream;
+        struct Drain {                                              // whatever happens, nothing of this call is left running
+            hipStream_t s;
+            ~Drain() { (void)hipStreamSynchronize(s); }
+        } drain{s};
+        uint8_t* d_frame = nullptr;
+        uint16_t* d_counts = nullptr;
+        uint16_t* d_cut = nullptr;
+        mpc_basis_choice* d_choices = nullptr;
+        uint32_t* d_profile = nullptr;
+        uint8_t* d_depth[2] = {nullptr, nullptr};
+        unsigned long long* d_words = nullptr;                      // the allocation's three totals, the full frame's SSE
+        int* d_error = nullptr;
+        const auto layout = [&](char* base) {
+            Carve cv{base};
+            d_frame = cv.take<uint8_t>(on_device ? 0 : row * static_cast<size_t>(height));
+            d_counts = cv.take<uint16_t>(n_tc + 2);
+            d_cut = cv.take<uint16_t>(n_tc + 2);
+            d_choices = cv.take<mpc_basis_choice>(n_tc * static_cast<size_t>(K));
+            d_profile = cv.take<uint32_t>(static_cast<size_t>(tiles) * (static_cast<size_t>(K) + 1));
+            d_depth[0] = cv.take<uint8_t>(static_cast<size_t>(tiles));
+            d_depth[1] = cv.take<uint8_t>(static_cast<size_t>(tiles));
+            d_words = cv.take<unsigned long long>(4);
+            d_error = cv.take<int>(1);
+            return cv.at;
+        };
+        if (const mpc_status gs = c->budget_dev.reserve(layout(nullptr), "budget staging"); gs != MPC_OK) return gs;
+        layout(c->budget_dev.data());
+        const uint8_t* frame = rgb;
+        if (!on_device) {
+            HIP_TRY(hipMemcpyAsync(d_frame, rgb, row * static_cast<size_t>(height), hipMemcpyHostToDevice, s));
+            frame = d_frame;
+        }
+        HIP_TRY(hipMemsetAsync(d_words, 0, 4 * sizeof(unsigned long long), s));
+        HIP_TRY(hipMemsetAsync(d_error, 0, sizeof(int), s));
+        // 1. one pursuit of the whole frame, the records kept; the full frame's SSE behind it
+        if (const mpc_status es = mpc_encode_tiles_device(c, frame, width, height, row, 0, tiles_y, quant, d_counts, d_choices, nullptr, nullptr, 0, s);
+            es != MPC_OK)
+            return es;
+        if (const mpc_status ds = mpc_distortion_device(c, d_counts, d_choices, quant, frame, width, height, d_words + 3, nullptr, s); ds != MPC_OK)
+            return ds;
+        // 2. the full container with its seek index
+        const unsigned full_every = every ? every : mpc::kIndexIntervalDefault;
+        Made full;
+        if (const mpc_status fs = container_of(c, tuning, s, d_counts, d_choices, tiles, width, height, quant, full_every, &full); fs != MPC_OK) return fs;
+        unsigned long long full_sse = 0;
+        HIP_TRY(hipMemcpyAsync(&full_sse, d_words + 3, sizeof(full_sse), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        mpc::ContainerIndex full_index;
+        if (!mpc::read_container_index(full.index.data(), full.index.size(), full_index) || full_index.streams.size() != 1 + 6 * static_cast<size_t>(K))
+            return fail(MPC_ERR_HIP, "the full container's seek index does not read back");
+        unsigned long long full_records = 0;
+        for (int ch = 0; ch < 3; ++ch)
+            for (int i = 0; i < K; ++i) full_records += full_index.streams[1 + 2 * static_cast<size_t>(K) * ch + 2 * static_cast<size_t>(i)].expect;
+        got.full_bytes = full.nbytes;
+        got.full_sse = full_sse;
+        got.full_records = full_records;
+        Made best;
+        int best_depth = -1;                                        // which of d_depth holds the returned container's map; -1: no cut
+        if (full.nbytes <= budget) {
+            // 3. it fits
+            best.swap(full);
+            got.lambda_index = -1;
+            got.probes = 0;
+            got.sse = full_sse;
+            got.records = full_records;
+        } else {
+            // 4. the weights from the full container's index, the profile once
+            uint32_t weights[3 * MPC_MAX_K];
+            const int verdict = mpc::budget_weights(full.index.data(), full.index.size(), weights);
+            if (verdict == 2) return fail(MPC_ERR_ARGUMENT, "the full container's seek index is serial only: no stream sizes to weigh the steps with");
+            if (verdict != 0) return fail(MPC_ERR_HIP, "the full container's seek index does not read back");
+            if (const mpc_status ps = profile_on_device(c, d_counts, d_choices, quant, frame, width, height, d_profile, d_error, s); ps != MPC_OK)
+                return ps;
+            int spare = 0;
+            unsigned long long best_totals[3] = {0, 0, 0};
+            size_t probed_bytes = 0;                                // the last probe's size
+            // 5. size(j): the container of the cut counts at j; kept when it fits
+            const auto probe = [&](int j, bool* fits) -> mpc_status {
+                if (const mpc_status as = allocate_on_device(c, d_profile, d_counts, tiles, weights, j, d_depth[spare], d_cut, d_words, s); as != MPC_OK)
+                    return as;
+                Made made;
+                if (const mpc_status cs = container_of(c, tuning, s, d_cut, d_choices, tiles, width, height, quant, every, &made); cs != MPC_OK) return cs;
+                ++got.probes;
+                probed_bytes = made.nbytes;
+                *fits = made.nbytes <= budget;
+                if (*fits) {
+                    HIP_TRY(hipMemcpyAsync(best_totals, d_words, sizeof(best_totals), hipMemcpyDeviceToHost, s));
+                    HIP_TRY(hipStreamSynchronize(s));
+                    best.swap(made);
+                    best_depth = spare;
+                    spare ^= 1;
+                }
+                return MPC_OK;
+            };
+            bool fits = false;
+            if (const mpc_status ps = probe(mpc::kBudgetLambdas - 1, &fits); ps != MPC_OK) return ps;
+            int error_word = 0;                                     // the profile kernel ran in front of the first probe
+            HIP_TRY(hipMemcpyAsync(&error_word, d_error, sizeof(int), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            if (error_word) return fail(MPC_ERR_BITSTREAM, "Invalid bitstream");
+            // 6. the smallest container there is
+            if (!fits)
+                return fail(MPC_ERR_ARGUMENT, "a budget of %zu bytes: the container with every tile cut to nothing has %zu", budget, probed_bytes);
+            // 7. lo infeasible (-1: the full container), hi feasible
+            int lo = -1, hi = mpc::kBudgetLambdas - 1;
+            while (hi - lo > 1) {
+                const int mid = (lo + hi) >> 1;                     // lo + hi >= -1 + 1: the shift rounds down
+                if (const mpc_status ps = probe(mid, &fits); ps != MPC_OK) return ps;
+                if (fits) hi = mid;
+                else lo = mid;
+            }
+            got.lambda_index = hi;
+            got.sse = best_totals[0];
+            got.records = best_totals[2];
+        }
+        // 8. hi's container, kept from its probe
+        if (depth) {
+            if (best_depth < 0) std::memset(depth, K, static_cast<size_t>(tiles));
+            else {
+                HIP_TRY(hipMemcpyAsync(depth, d_depth[best_depth], static_cast<size_t>(tiles), hipMemcpyDeviceToHost, s));
+                HIP_TRY(hipStreamSynchronize(s));
+            }
+        }
+        if (every) {
+            uint8_t* copy = best.index.empty() ? nullptr : static_cast<uint8_t*>(std::malloc(best.index.size()));
+            if (!copy) return fail(MPC_ERR_ALLOC, "no seek index");
+            std::memcpy(copy, best.index.data(), best.index.size());
+            *index = copy;
+            *index_bytes = best.index.size();
+        }
+        *bytes = best.bytes;
+        *nbytes = best.nbytes;
+        best.bytes = nullptr;
+        *info = got;
+        return MPC_OK;
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+int mpc_budget_lambda(int j, uint64_t* lambda) {
+    if (!lambda || j < 0 || j >= mpc::kBudgetLambdas) return fail(MPC_ERR_ARGUMENT, "multiplier %d: 0 to %d", j, mpc::kBudgetLambdas - 1);
+    *lambda = mpc::budget_lambda(j);
+    return MPC_OK;
+}
+
+mpc_status mpc_budget_weights(const uint8_t* index, size_t index_bytes, uint32_t* weights) {
+    return guarded([&]() -> mpc_status {
+        if (!index || !weights) return fail(MPC_ERR_ARGUMENT, "null argument");
+        const int verdict = mpc::budget_weights(index, index_bytes, weights);
+        if (verdict == 1) return fail(MPC_ERR_BITSTREAM, "not a seek index");
+        if (verdict == 2) return fail(MPC_ERR_ARGUMENT, "a serial-only index holds no stream sizes");
+        return MPC_OK;
+    });
+}
+
+mpc_status mpc_budget_allocate(const uint32_t* profile, const uint16_t* counts, long long tiles, int K, const uint32_t* weights, int j,
+                               uint8_t* depth, uint16_t* out_counts, uint64_t* totals) {
+    return guarded([&]() -> mpc_status {
+        if (!profile || !counts || !weights || !totals) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (tiles < 0 || K < 1 || K > MPC_MAX_K || j < 0 || j >= mpc::kBudgetLambdas) return fail(MPC_ERR_ARGUMENT, "tiles %lld, K %d, multiplier %d", tiles, K, j);
+        mpc::budget_allocate(profile, counts, tiles, K, weights, j, depth, out_counts, totals);
+        return MPC_OK;
+    });
+}
+
+mpc_status mpc_depth_profile_device(mpc_context* c, const uint16_t* d_counts, const mpc_basis_choice* d_choices, const double* quant,
+                                    const uint8_t* d_rgb, int width, int height, uint32_t* d_profile, void* stream) {
+    return guarded([&]() -> mpc_status {
+        if (!c || !d_counts || !d_choices || !d_rgb || !d_profile) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (c->device < 0) return no_device();
+        long long tiles = 0;
+        if (const mpc_status gs = geometry(width, height, &tiles); gs != MPC_OK) return gs;
+        HIP_TRY(hipSetDevice(c->device));
+        if (const mpc_status fs = crop_flag(c); fs != MPC_OK) return fs;
+        return profile_on_device(c, d_counts, d_choices, quant, d_rgb, width, height, d_profile, c->d_crop_flag, static_cast<hipStream_t>(stream));
+    });
+}
+
+mpc_status mpc_budget_allocate_device(mpc_context* c, const uint32_t* d_profile, const uint16_t* d_counts, long long tiles, const uint32_t* weights,
+                                      int j, uint8_t* d_depth, uint16_t* d_out_counts, unsigned long long* d_totals, void* stream) {
+    return guarded([&]() -> mpc_status {
+        if (!c || !d_profile || !d_counts || !weights || !d_depth || !d_out_counts || !d_totals) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (c->device < 0) return no_device();
+        if (tiles < 1 || tiles * 3 >= (1LL << 31) || j < 0 || j >= mpc::kBudgetLambdas) return fail(MPC_ERR_ARGUMENT, "tiles %lld, multiplier %d", tiles, j);
+        HIP_TRY(hipSetDevice(c->device));
+        return allocate_on_device(c, d_profile, d_counts, tiles, weights, j, d_depth, d_out_counts, d_totals, static_cast<hipStream_t>(stream));
+    });
+}
+
+mpc_status mpc_encode_image_budget(mpc_context* c, const uint8_t* rgb, int width, int height, const double* quant, size_t budget, int index_interval,
+                                   uint8_t** bytes, size_t* nbytes, uint8_t** index, size_t* index_bytes, uint8_t* depth, mpc_budget_info* info) {
+    return encode_budget(c, rgb, false, width, height, quant, budget, index_interval, bytes, nbytes, index, index_bytes, depth, info);
+}
+
+mpc_status mpc_encode_image_budget_device(mpc_context* c, const uint8_t* d_rgb, int width, int height, const double* quant, size_t budget,
+                                          int index_interval, uint8_t** bytes, size_t* nbytes, uint8_t** index, size_t* index_bytes, uint8_t* depth,
+                                          mpc_budget_info* info) {
+    return encode_budget(c, d_rgb, true, width, height, quant, budget, index_interval, bytes, nbytes, index, index_bytes, depth, info);
+}
+
+}  // extern "C"

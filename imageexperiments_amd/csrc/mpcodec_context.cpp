@@ -590,6 +590,7 @@ void mpc_context_destroy(mpc_context* c) {
         (void)hipFree(c->d_flag);
         (void)hipFree(c->d_crop_flag);
         if (c->compose_side) (void)hipStreamDestroy(c->compose_side);
+        if (c->budget_stream) (void)hipStreamDestroy(c->budget_stream);
         if (c->seq_up) (void)hipStreamDestroy(c->seq_up);
         if (c->seq_compute) (void)hipStreamDestroy(c->seq_compute);
         for (hipStream_t sd : c->seq_down)

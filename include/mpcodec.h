@@ -929,6 +929,85 @@ mpc_status mpc_delta_encode(mpc_delta* d, const uint8_t* rgb, size_t row_stride,
                             uint8_t** bytes, size_t* nbytes, uint8_t** index, size_t* index_bytes, mpc_delta_info* info);
 mpc_status mpc_delta_changed(const mpc_delta* d, int32_t* tiles, int capacity, int* n);   /* the last call's list */
 
+/* ---- budget: encode to a byte budget ("Encoder: a byte budget") ----
+ * The container is layered by pursuit step, every tile-channel has its own length and nothing reads a record beyond its count: cutting
+ * a tile to its first n steps is a change of three counts, and the result is a container every decoder reads unchanged.  The search
+ * below picks a depth per tile, spending the bytes where they lower the error most, from one pursuit and a handful of container jobs.
+ * Frames of 8 x 8 tiles, T tiles, K the context's; whole-frame records (tile t = tx * tiles_y + ty, counts[t * 3 + ch],
+ * choices[(t * 3 + ch) * K + i]).  Host and device agree bit for bit on everything defined here.
+ *
+ * DEPTH PROFILE  P[t][n], n = 0 ... K, u32 at profile[t * (K + 1) + n]: the value mpc_distortion_device's d_tile_sse[t] has for the same
+ * records with every count replaced by min(count, n) -- the decoder's flavour (the fast flag), the header's u16 quantiser steps, the
+ * integer dr^2 + dg^2 + db^2 over the pixels inside the frame; n = 0 is the all-black tile.  Defined for PREFIX-CONSISTENT records: the
+ * row of record i lies in the dynamic dictionary built from choices 0 ... i - 1, which holds for every encoder's records.  A record that
+ * is not (a forward reference, a row outside its dictionary) and a count above K set the context's crop error word
+ * (mpc_crop_records_check: MPC_ERR_BITSTREAM "Invalid bitstream"); that tile's profile is then unspecified, and no address comes from it.
+ * RATE WEIGHTS  W[ch][i], u32 in 1/256 bit at weights[ch * K + i], from a seek index (either version) of the frame's FULL container:
+ * with a = 1 + 2K * ch + 2i, bits = end_bit(a + 1) - wrapper_bit(a) and n = expect(a): W = clamp((256 * bits + n / 2) / n, 256, 2^20),
+ * and 256 when n = 0 -- the average cost of a record of that channel and step, wrappers and tables included.
+ * RATE OF A DEPTH  R[t][n] = sum over ch and i < min(n, counts[t * 3 + ch]) of W[ch][i], below 2^27.
+ * MULTIPLIERS  L[0] = 0, L[j] = (8 + (j - 1) % 8) << ((j - 1) / 8) for j = 1 ... 255 (MPC_BUDGET_LAMBDAS entries), u64.
+ * ALLOCATION AT j  J(t, n) = P[t][n] * 65536 + L[j] * R[t][n] in u64 (P < 2^24, L < 2^35: no overflow); depth[t] = the smallest n that
+ * minimises J; the cut counts are min(count, depth[t]); totals[0] = sum of P[t][depth[t]], totals[1] = sum of R[t][depth[t]], totals[2] =
+ * the records kept.  A count above K is used as K.  At j = 255 every depth is 0 (for a profile that repeats above a tile's largest count).
+ *
+ * mpc_budget_lambda: *lambda = L[j]; MPC_ERR_ARGUMENT outside 0 ... 255.
+ * mpc_budget_weights: weights[3K], K the index's.  MPC_ERR_BITSTREAM for what mpc_index_info refuses, MPC_ERR_ARGUMENT for a serial-only
+ * index (it holds no stream sizes) and for a null pointer.
+ * mpc_budget_allocate: the allocation on the host; it defines what the kernel computes.  depth[tiles] and out_counts[3 * tiles]: each NULL or
+ * room for that; totals[3].  MPC_ERR_ARGUMENT: a null pointer, tiles < 0, K outside 1 ... 32, j outside 0 ... 255.
+ * The three are host only, need no context and are safe on several threads.
+ *
+ * mpc_depth_profile_device: the profile of the records against the frame they came from (d_rgb: 3 * width bytes a row, tightly packed),
+ * all in device memory, into d_profile[tiles * (K + 1)].  quant as for mpc_distortion_device.  Asynchronous on `stream`.
+ * mpc_budget_allocate_device: the allocation of `tiles` tiles (K the context's) with weights[3K] in HOST memory (they travel in the
+ * kernel's arguments): d_depth[tiles] (u8), d_out_counts[3 * tiles], d_totals[3] (u64; zeroed on `stream` first).  Asynchronous.
+ * Both: MPC_ERR_ARGUMENT with nothing enqueued for a null pointer or a geometry outside mpc_rate_distortion's, MPC_ERR_NO_DEVICE for a
+ * host-only context.
+ *
+ * mpc_encode_image_budget[_device]: a container of at most `budget` bytes of the frame (host: 3 * width bytes a row; _device: device
+ * memory, tightly packed).  Synchronous.
+ *   1. the whole frame is pursued once; the records stay on the device
+ *   2. the full container F with its seek index is made on job slot 0, the way mpc_delta_encode finishes
+ *   3. |F| <= budget: F is returned, byte for byte mpc_encode_image; lambda_index = -1, probes = 0, every depth K
+ *   4. else the weights are taken from F's index and the profile is made, once
+ *   5. size(j) is the container of the cut counts at j: the same job on the same records with the cut counts array
+ *   6. size(255) > budget: MPC_ERR_ARGUMENT, the budget and size(255) in the text
+ *   7. bisection with lo = -1 (infeasible) and hi = 255 (feasible), mid = (lo + hi) / 2 rounded down (127 first): size(mid) <= budget
+ *      moves hi, else lo moves, until hi = lo + 1
+ *   8. hi's container is returned, kept from its probe: nothing is coded twice
+ * At most nine probes, size(255) among them.  The size need not be monotone in j: what the result promises is the two invariants, lo
+ * infeasible and hi feasible.  quant: 3K doubles or NULL = the context's tables.  index_interval < 0: no index, `index` may be NULL;
+ * otherwise mpc_container_index's interval rules (0 = the default) and *index (mpc_free) is byte for byte mpc_container_index2(*bytes,
+ * ..., interval, MPC_INDEX_EXPANDED) of the returned container.  depth: NULL, or host room for the returned container's depth per tile.
+ * info: lambda_index, probes, full_bytes = |F|, sse and records of the returned container (what mpc_decode_image of it differs from the
+ * frame by, exactly), full_sse and full_records of F.
+ * Refused with nothing enqueued: MPC_ERR_ARGUMENT for a null pointer (`index` and `index_bytes` only with index_interval >= 0), a geometry
+ * outside mpc_rate_distortion's, budget = 0, an interval outside the rules, a container job slot that is not idle; MPC_ERR_NO_DEVICE for a
+ * host-only context.  On failure nothing is returned, the slots are idle and the context is usable.  The call leaves the context's quant
+ * tables, fast flag and workgroup limit as it found them. */
+#define MPC_BUDGET_LAMBDAS 256
+typedef struct mpc_budget_info {
+    int lambda_index, probes;
+    size_t full_bytes;
+    unsigned long long sse, full_sse, records, full_records;
+} mpc_budget_info;
+int mpc_budget_lambda(int j, uint64_t* lambda);
+mpc_status mpc_budget_weights(const uint8_t* index, size_t index_bytes, uint32_t* weights /* [3K] */);
+mpc_status mpc_budget_allocate(const uint32_t* profile, const uint16_t* counts, long long tiles, int K, const uint32_t* weights, int j,
+                               uint8_t* depth, uint16_t* out_counts, uint64_t* totals);
+mpc_status mpc_depth_profile_device(mpc_context* ctx, const uint16_t* d_counts, const mpc_basis_choice* d_choices, const double* quant,
+                                    const uint8_t* d_rgb, int width, int height, uint32_t* d_profile, void* stream);
+mpc_status mpc_budget_allocate_device(mpc_context* ctx, const uint32_t* d_profile, const uint16_t* d_counts, long long tiles,
+                                      const uint32_t* weights, int j, uint8_t* d_depth, uint16_t* d_out_counts, unsigned long long* d_totals,
+                                      void* stream);
+mpc_status mpc_encode_image_budget(mpc_context* ctx, const uint8_t* rgb, int width, int height, const double* quant, size_t budget,
+                                   int index_interval, uint8_t** bytes, size_t* nbytes, uint8_t** index, size_t* index_bytes, uint8_t* depth,
+                                   mpc_budget_info* info);
+mpc_status mpc_encode_image_budget_device(mpc_context* ctx, const uint8_t* d_rgb, int width, int height, const double* quant, size_t budget,
+                                          int index_interval, uint8_t** bytes, size_t* nbytes, uint8_t** index, size_t* index_bytes,
+                                          uint8_t* depth, mpc_budget_info* info);
+
 /* ---- "-s" patch statistics, Compression.cpp:200-302 ----
  * The reference seeds one std::mt19937, and for every image draws `patches` origins x = rand() % (width - bs),
  * y = rand() % (height - bs), runs CalcMPDynamic on the Y, U and V patch with every quantiser 1.0 and feeds
