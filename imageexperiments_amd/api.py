@@ -65,6 +65,14 @@ MPC_DELTA_KEY, MPC_DELTA_DEVICE_PIXELS, MPC_DELTA_PACK_ALWAYS = 1, 2, 4   # `fla
 MPC_DELTA_PACK_ROWS = 64
 
 
+class MpcPatchInfo(C.Structure):                     # struct mpc_patch_info
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("sequence", C.c_uint32), ("key", C.c_int), ("n", C.c_int), ("tiles", C.c_int),
+                ("container_offset", C.c_size_t), ("container_bytes", C.c_size_t)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
 class MpcBudgetInfo(C.Structure):                    # mpc_budget_info
     _fields_ = [("lambda_index", C.c_int), ("probes", C.c_int), ("full_bytes", C.c_size_t), ("sse", C.c_ulonglong),
                 ("full_sse", C.c_ulonglong), ("records", C.c_ulonglong), ("full_records", C.c_ulonglong)]
@@ -292,6 +300,19 @@ def _bind_bitstream(L):
         L.mpc_delta_encode.argtypes = [vp, vp, C.c_size_t, _dp, C.c_uint, C.c_int, C.POINTER(_u8p), _szp_, C.POINTER(_u8p), _szp_,
                                        C.POINTER(MpcDeltaInfo)]
         L.mpc_delta_changed.argtypes = [vp, _i32p, C.c_int, C.POINTER(C.c_int)]
+        _pip = C.POINTER(MpcPatchInfo)
+        L.mpc_patch_make.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_int, _i32p, C.c_int, _u8p, C.c_size_t, C.POINTER(_u8p), _szp_]
+        L.mpc_patch_info.argtypes = [_u8p, C.c_size_t, _pip]
+        L.mpc_patch_tiles.argtypes = [_u8p, C.c_size_t, _i32p, C.c_int, C.POINTER(C.c_int)]
+        L.mpc_delta_encode_patch.argtypes = [vp, vp, C.c_size_t, _dp, C.c_uint, C.POINTER(_u8p), _szp_, C.POINTER(MpcDeltaInfo)]
+        L.mpc_unpack_tiles_device.argtypes = [vp, vp, C.c_size_t, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_size_t, vp]
+        L.mpc_patch_decoder_create.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp)]
+        L.mpc_patch_decoder_destroy.argtypes = [vp]
+        L.mpc_patch_decoder_destroy.restype = None
+        L.mpc_patch_apply.argtypes = [vp, _u8p, C.c_size_t, _pip]
+        L.mpc_patch_frame_device.argtypes = [vp, C.POINTER(vp)]
+        L.mpc_patch_read.argtypes = [vp, vp, C.c_size_t]
+        L.mpc_patch_changed.argtypes = [vp, _i32p, C.c_int, C.POINTER(C.c_int)]
     except AttributeError:
         if not os.environ.get("MPCODEC_LIB"):             # an older build may be loaded for A/B timing only
             raise
@@ -823,6 +844,114 @@ class DeltaEncoder:
         _check(self.L.mpc_delta_changed(self.h, None, 0, C.byref(n)))
         tiles = np.zeros(max(n.value, 1), np.int32)
         _check(self.L.mpc_delta_changed(self.h, tiles.ctypes.data_as(_i32p), n.value, C.byref(n)))
+        return tiles[:n.value]
+
+    def _encode_patch(self, ptr, row_stride, quant, flags):
+        qp = None
+        if quant is not None:
+            quant = np.ascontiguousarray(quant, np.float64).reshape(3, self.ctx.K)
+            qp = quant.ctypes.data_as(_dp)
+        out, n, info = _u8p(), C.c_size_t(0), MpcDeltaInfo()
+        _check(self.L.mpc_delta_encode_patch(self.h, ptr, int(row_stride), qp, int(flags), C.byref(out), C.byref(n), C.byref(info)))
+        self.info = (info.tiles, info.changed, info.key)
+        return _take_bytes(self.L, out, n)
+
+    def encode_patch(self, rgb, quant=None, key=False, pack_always=False):
+        """mpc_delta_encode_patch of a host frame -> the patch (bytes): the changed tiles' list and the container of their packed frame,
+        a key patch with the whole frame's container where every tile is listed, 40 bytes where none is."""
+        rgb = _pixel_rows(rgb)
+        if rgb.shape[:2] != (self.height, self.width):
+            raise ValueError("the frame is not the session's size")
+        flags = (MPC_DELTA_KEY if key else 0) | (MPC_DELTA_PACK_ALWAYS if pack_always else 0)
+        return self._encode_patch(rgb.ctypes.data, rgb.strides[0], quant, flags)
+
+    def encode_patch_device(self, d_rgb, row_stride=0, quant=None, key=False, pack_always=False):
+        """The same for a frame in device memory: d_rgb an int from tensor.data_ptr(), row_stride bytes between rows (0 = 3 * width)."""
+        flags = MPC_DELTA_DEVICE_PIXELS | (MPC_DELTA_KEY if key else 0) | (MPC_DELTA_PACK_ALWAYS if pack_always else 0)
+        return self._encode_patch(int(d_rgb), row_stride, quant, flags)
+
+
+def patch_make(width, height, sequence, tiles, container, key=False):
+    """mpc_patch_make: the only writer of a patch -> bytes.  key: `tiles` is not read (None will do) and the container is the whole
+    frame's; else `tiles` ascending with the container of their packed frame, or empty with container None or b""."""
+    L = load_library()
+    buf = np.frombuffer(container if container is not None else b"", np.uint8)
+    listed = np.ascontiguousarray([] if tiles is None else tiles, np.int32)
+    n = -(-int(width) // 8) * -(-int(height) // 8) if key else listed.size
+    out, nbytes = _u8p(), C.c_size_t(0)
+    _check(L.mpc_patch_make(int(width), int(height), int(sequence), int(bool(key)), listed.ctypes.data_as(_i32p) if listed.size else None, n,
+                            buf.ctypes.data_as(_u8p) if buf.size else None, buf.size, C.byref(out), C.byref(nbytes)))
+    return _take_bytes(L, out, nbytes)
+
+
+def patch_info(patch):
+    """mpc_patch_info: validates the patch whole -> dict(width, height, sequence, key, n, tiles, container_offset, container_bytes);
+    MpcError(MPC_ERR_BITSTREAM) for a patch it refuses."""
+    buf = np.frombuffer(patch, np.uint8)
+    info = MpcPatchInfo()
+    _check(load_library().mpc_patch_info(buf.ctypes.data_as(_u8p) if buf.size else C.cast(C.c_char_p(b"\0"), _u8p), buf.size, C.byref(info)))
+    return info.as_dict()
+
+
+def patch_tiles(patch):
+    """mpc_patch_tiles: the patch's tile list, ascending (int32 array); a key patch's: every tile"""
+    L = load_library()
+    buf = np.frombuffer(patch, np.uint8)
+    p = buf.ctypes.data_as(_u8p) if buf.size else C.cast(C.c_char_p(b"\0"), _u8p)
+    n = C.c_int(0)
+    _check(L.mpc_patch_tiles(p, buf.size, None, 0, C.byref(n)))
+    tiles = np.zeros(max(n.value, 1), np.int32)
+    _check(L.mpc_patch_tiles(p, buf.size, tiles.ctypes.data_as(_i32p), n.value, C.byref(n)))
+    return tiles[:n.value]
+
+
+class PatchDecoder:
+    """mpc_patch_decoder: the receiver of a delta stream.  It keeps the current frame in device memory; apply() writes only a patch's
+    listed tiles into it.  A refused patch (MpcError) leaves the frame, the list and the expected sequence as they were."""
+
+    def __init__(self, ctx, width, height):
+        self.ctx, self.L = ctx, ctx.L                               # the session must go before its context
+        self.width, self.height = int(width), int(height)
+        h = C.c_void_p()
+        _check(self.L.mpc_patch_decoder_create(ctx.h, self.width, self.height, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.mpc_patch_decoder_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def apply(self, patch):
+        """mpc_patch_apply -> patch_info's dict of the applied patch"""
+        buf = np.frombuffer(patch, np.uint8)
+        info = MpcPatchInfo()
+        _check(self.L.mpc_patch_apply(self.h, buf.ctypes.data_as(_u8p) if buf.size else C.cast(C.c_char_p(b"\0"), _u8p), buf.size, C.byref(info)))
+        return info.as_dict()
+
+    def frame(self):
+        """mpc_patch_read: the kept frame as a uint8 [H, W, 3] array"""
+        out = np.empty((self.height, self.width, 3), np.uint8)
+        _check(self.L.mpc_patch_read(self.h, out.ctypes.data, 0))
+        return out
+
+    def frame_device(self):
+        """mpc_patch_frame_device: the kept frame's device pointer (an int): height rows of 3 * width bytes, valid until the next apply"""
+        p = C.c_void_p()
+        _check(self.L.mpc_patch_frame_device(self.h, C.byref(p)))
+        return int(p.value or 0)
+
+    def changed(self):
+        """mpc_patch_changed: the last apply's list, ascending (int32 array); a key patch's: every tile"""
+        n = C.c_int(0)
+        _check(self.L.mpc_patch_changed(self.h, None, 0, C.byref(n)))
+        tiles = np.zeros(max(n.value, 1), np.int32)
+        _check(self.L.mpc_patch_changed(self.h, tiles.ctypes.data_as(_i32p), n.value, C.byref(n)))
         return tiles[:n.value]
 
 
@@ -1615,6 +1744,19 @@ class CompressionContext:
         outside the image and in the padding tiles.  Asynchronous."""
         _check(self.L.mpc_pack_tiles_device(self.h, d_rgb, int(width), int(height), int(row_stride), d_list, int(n), int(rows), d_packed,
                                             int(packed_stride), stream or None))
+
+    def patch_decoder(self, width, height):
+        """mpc_patch_decoder_create: a PatchDecoder for a delta stream of width x height frames through this context"""
+        return PatchDecoder(self, width, height)
+
+    def unpack_tiles_device(self, d_packed, packed_stride, d_list, n, rows, d_rgb, width, height, row_stride=0, stream=0, check=True):
+        """mpc_unpack_tiles_device: pack_tiles_device's inverse: listed tile j of the packed frame delta_pack_geometry(n, rows) describes to
+        tile d_list[j] of the frame at d_rgb, only the bytes inside the image.  check: mpc_crop_records_check behind it, which waits for
+        `stream` and raises MpcError(MPC_ERR_BITSTREAM) if a list entry was outside the frame (that entry writes nothing)."""
+        _check(self.L.mpc_unpack_tiles_device(self.h, d_packed, int(packed_stride), d_list, int(n), int(rows), d_rgb, int(width), int(height),
+                                              int(row_stride), stream or None))
+        if check:
+            _check(self.L.mpc_crop_records_check(self.h, stream or None))
 
     def scatter_records_device(self, d_packed_counts, d_packed_choices, d_list, n, d_counts, d_choices, tiles, stream=0, check=True):
         """mpc_scatter_records_device: records j of a packed frame to tile d_list[j] of whole-frame records of `tiles` tiles.  check:

@@ -6,6 +6,8 @@
 //            ascending list of changed tiles (count per 1024-tile block, mp_stream_scan_kernel over the blocks, rank by ballots)
 //   pack     the listed tiles side by side in a small frame of whole tiles, which the tile encoder takes as an ordinary frame
 //   scatter  that frame's records to the listed tiles' places in the whole frame's records
+// and, for the receiver of a delta stream (include/mpcodec.h, "patch"), the pack's inverse:
+//   unpack   a decoded packed frame's tiles to the listed tiles' places in the receiver's kept frame, cut to the image
 // The diff is the hot one and purely bandwidth-bound: it reads both frames once.  A tile's pixel row is 24 bytes = three 8-byte chunks;
 // a thread owns one chunk column of a strip of 64 horizontally adjacent tiles over the tile's 8 pixel rows, so a wave reads 512
 // contiguous bytes of a pixel row per load, 8 independent loads per frame in flight, and a chunk is written back only where it differs.
@@ -139,6 +141,43 @@ __global__ __launch_bounds__(256) void mp_tile_pack_kernel(const uint8_t* __rest
     }
 }
 
+// The pack kernel's inverse, for the receiver of a delta stream (mpcodec_patch.cpp): a thread per 8-byte chunk of the packed frame.
+// The chunk of listed tile j at packed tile (j / rows, j % rows) goes to tile list[j] of the frame, cut to the image: nothing at or
+// behind 3 * width of a row, no row at or below height, nothing for a padding tile (j >= n).  kWords: the frame's base and stride are
+// multiples of 8; a chunk that lies whole inside its pixel row is then one 8-byte store, and every other chunk (and every chunk
+// without kWords) is written byte by byte.  An entry outside [0, tiles) writes nothing and sets *error: every address comes from
+// list[j] after its check against `tiles`
+template <bool kWords>
+__global__ __launch_bounds__(256) void mp_tile_unpack_kernel(const uint8_t* __restrict__ packed, long long packed_stride,
+                                                             const int32_t* __restrict__ list, long long n, int rows, int cols,
+                                                             uint8_t* __restrict__ rgb, int width, int height, long long row_stride,
+                                                             int tiles_y, long long tiles, int* __restrict__ error)
+{
+    const long long chunks_per_row = 3LL * cols, total = chunks_per_row * 8 * rows, row_bytes = 3LL * width;
+    for (long long o = (long long)blockIdx.x * 256 + threadIdx.x; o < total; o += (long long)gridDim.x * 256) {
+        const long long py = o / chunks_per_row;
+        const int k = (int)(o - py * chunks_per_row), txp = k / 3, part = k - 3 * txp;
+        const long long j = (long long)txp * rows + (py >> 3);
+        if (j >= n) continue;                                        // a padding tile
+        const long long t = list[j];
+        if (t < 0 || t >= tiles) {
+            *error = 1;
+            continue;
+        }
+        const long long tx = t / tiles_y, y = (t - tx * tiles_y) * 8 + (py & 7), b0 = 24 * tx + 8 * part;
+        if (y >= height || b0 >= row_bytes) continue;                // the black fill of a ragged tile
+        const uint2 v = *reinterpret_cast<const uint2*>(packed + py * packed_stride + 8LL * k);
+        uint8_t* p = rgb + y * row_stride + b0;
+        if (kWords && b0 + 8 <= row_bytes) {
+            *reinterpret_cast<uint2*>(p) = v;
+        } else {
+            const int nb = row_bytes - b0 < 8 ? (int)(row_bytes - b0) : 8;
+            const unsigned long long bits = (unsigned long long)v.x | (unsigned long long)v.y << 32;
+            for (int b = 0; b < nb; ++b) p[b] = (uint8_t)(bits >> (8 * b));
+        }
+    }
+}
+
 // A thread per record word, then per count.  The encoder zeroes the entries beyond a count, so a plain copy carries no garbage.
 // Every address comes from list[j] after its check against `tiles`
 __global__ __launch_bounds__(256) void mp_tile_scatter_records_kernel(const uint16_t* __restrict__ packed_counts,
@@ -217,6 +256,28 @@ int launch_tile_pack(const uint8_t* rgb, int width, int height, size_t row_strid
     else
         hipLaunchKernelGGL(mp_tile_pack_kernel<false>, dim3(blocks), dim3(256), 0, s, rgb, width, height, (long long)row_stride, (int)tiles_y, tiles, list,
                            n, rows, cols, packed, (long long)packed_stride);
+    return (int)hipGetLastError();
+}
+
+int launch_tile_unpack(const uint8_t* packed, size_t packed_stride, const int32_t* list, long long n, int rows, int cols, uint8_t* rgb, int width,
+                       int height, size_t row_stride, int* error, void* stream_)
+{
+    if (!packed || !list || !rgb || !error || width < 1 || height < 1 || row_stride < 3 * (size_t)width || n < 1 || rows < 1 || cols < 1)
+        return (int)hipErrorInvalidValue;
+    if (n > (long long)rows * cols || packed_stride < 24 * (size_t)cols || ((reinterpret_cast<uintptr_t>(packed) | packed_stride) & 7) != 0)
+        return (int)hipErrorInvalidValue;
+    const long long tiles_y = ((long long)height + 7) / 8, tiles = (((long long)width + 7) / 8) * tiles_y;
+    if (tiles >= (1LL << 31)) return (int)hipErrorInvalidValue;
+    const long long total = 3LL * cols * 8 * rows;
+    const unsigned blocks = (unsigned)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+    const bool words = ((reinterpret_cast<uintptr_t>(rgb) | row_stride) & 7) == 0;
+    hipStream_t s = static_cast<hipStream_t>(stream_);
+    if (words)
+        hipLaunchKernelGGL(mp_tile_unpack_kernel<true>, dim3(blocks), dim3(256), 0, s, packed, (long long)packed_stride, list, n, rows, cols, rgb, width,
+                           height, (long long)row_stride, (int)tiles_y, tiles, error);
+    else
+        hipLaunchKernelGGL(mp_tile_unpack_kernel<false>, dim3(blocks), dim3(256), 0, s, packed, (long long)packed_stride, list, n, rows, cols, rgb, width,
+                           height, (long long)row_stride, (int)tiles_y, tiles, error);
     return (int)hipGetLastError();
 }
 

@@ -318,6 +318,12 @@ int launch_tile_diff(uint8_t* kept, const uint8_t* rgb, int width, int height, s
 // aligned, packed_stride a multiple of 8 and >= 24 * cols; bytes of a row behind 24 * cols are not written
 int launch_tile_pack(const uint8_t* rgb, int width, int height, size_t row_stride, const int32_t* list, long long n, int rows, int cols,
                      uint8_t* packed, size_t packed_stride, void* stream);
+// launch_tile_pack's inverse: the pixel bytes of listed tile j, at packed tile (j / rows, j % rows), to tile list[j] of the frame at
+// `rgb` (row_stride >= 3 * width, any alignment), cut to the image; stride padding, the other tiles and the padding tiles' places are
+// not written.  An entry outside [0, tiles) writes nothing and sets *error.  packed: 8-byte aligned, packed_stride a multiple of 8
+// and >= 24 * cols.  8-byte stores when rgb and row_stride are multiples of 8 and the chunk lies whole in its row, else byte by byte
+int launch_tile_unpack(const uint8_t* packed, size_t packed_stride, const int32_t* list, long long n, int rows, int cols, uint8_t* rgb, int width,
+                       int height, size_t row_stride, int* error, void* stream);
 // The packed frame's records j (3 counts, 3 * K words) to the whole-frame records at tile list[j]; an entry outside [0, tiles) is
 // skipped and sets *error.  The entries are distinct
 int launch_tile_scatter_records(const uint16_t* packed_counts, const uint32_t* packed_choices, const int32_t* list, long long n, int K,

@@ -12,6 +12,7 @@
 //   mpcodec_index.cpp      the seek index's host-only entry points (mpc_container_index, mpc_parse_container_by_index)
 //   mpcodec_debug.cpp      the tests' entry points to the screen's tables (mpc_debug_*, mpc_filter_tiles)
 //   mpcodec_delta.cpp      the delta encoder (mpc_delta_*): diff against the kept frame, pursuit of the changed tiles only
+//   mpcodec_patch.cpp      the delta stream's patches (mpc_patch_*): the format's entry points (host_patch.h) and the receiver session
 //   mpcodec_budget.cpp     encode to a byte budget (mpc_encode_image_budget): depth profile, allocation, the search over the multiplier
 #pragma once
 

@@ -1,10 +1,13 @@
 // mpcodec_delta.cpp -- product: the delta encoder (include/mpcodec.h, "delta"; DESIGN.md 4, "Encoder: changed tiles only").
 // A session keeps the last frame and its records in device memory; a call finds the changed tiles on the device (mp_delta.hip),
-// pursues only those through the unchanged tile encoder, and makes the container from the whole frame's records as a compose does.
+// pursues only those through the unchanged tile encoder, and makes the container from the whole frame's records as a compose does --
+// or, as the sender of a delta stream (mpc_delta_encode_patch; include/mpcodec.h, "patch"), a patch: the list and the container of
+// the packed frame of the listed tiles alone.
 #include <cstring>
 #include <string>
 
 #include "host_delta.h"
+#include "host_patch.h"
 #include "mpc_internal.h"
 
 struct mpc_delta {
@@ -28,6 +31,7 @@ struct mpc_delta {
     bool changed_all = false;                   // the last call's list is every tile
     std::vector<int32_t> changed;               // else this
     mpc_delta_info info{};
+    uint32_t calls = 0;                         // successful calls of either kind so far: the next patch's sequence
     ~mpc_delta() {
         if (stream) {
             (void)hipStreamSynchronize(stream);
@@ -108,6 +112,27 @@ mpc_status mpc_pack_tiles_device(mpc_context* c, const uint8_t* d_rgb, int width
     });
 }
 
+mpc_status mpc_unpack_tiles_device(mpc_context* c, const uint8_t* d_packed, size_t packed_stride, const int32_t* d_list, int n, int rows,
+                                   uint8_t* d_rgb, int width, int height, size_t row_stride, void* stream) {
+    return guarded([&]() -> mpc_status {
+        if (!c || !d_packed || !d_list || !d_rgb) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (c->device < 0) return no_device();
+        if (width < 1 || height < 1 || n < 1 || rows < 1) return fail(MPC_ERR_ARGUMENT, "bad geometry");
+        const size_t row = 3 * static_cast<size_t>(width), stride = row_stride ? row_stride : row;
+        if (stride < row) return fail(MPC_ERR_ARGUMENT, "row_stride %zu for %d pixels", row_stride, width);
+        if (mpc::patch_frame_tiles(width, height) == 0) return fail(MPC_ERR_ARGUMENT, "bad geometry");
+        const mpc::PackGeometry g = mpc::pack_geometry(n, rows);
+        const size_t from = packed_stride ? packed_stride : g.stride;
+        if (from < g.stride || from % 8 != 0 || reinterpret_cast<uintptr_t>(d_packed) % 8 != 0)
+            return fail(MPC_ERR_ARGUMENT, "the packed frame: an 8-byte aligned base and a stride that is a multiple of 8 and at least %zu", g.stride);
+        HIP_TRY(hipSetDevice(c->device));
+        if (const mpc_status fs = crop_flag(c); fs != MPC_OK) return fs;
+        const int err = mpc::launch_tile_unpack(d_packed, from, d_list, n, g.rows, g.cols, d_rgb, width, height, stride, c->d_crop_flag, stream);
+        if (err != 0) return launch_failed(err);
+        return MPC_OK;
+    });
+}
+
 mpc_status mpc_scatter_records_device(mpc_context* c, const uint16_t* d_packed_counts, const mpc_basis_choice* d_packed_choices,
                                       const int32_t* d_list, int n, uint16_t* d_counts, mpc_basis_choice* d_choices, int tiles, void* stream) {
     return guarded([&]() -> mpc_status {
@@ -174,183 +199,296 @@ mpc_status mpc_delta_changed(const mpc_delta* d, int32_t* tiles, int capacity, i
     return MPC_OK;
 }
 
+}  // extern "C"
+
+// ---- a call in stages: mpc_delta_encode and mpc_delta_encode_patch share the first three, so the session's store advances
+// identically whichever is called, and differ in what the container job of the fourth is run on ----
+namespace {
+
+struct DeltaCall {                              // what the stages of one call hand on
+    const double* quant = nullptr;              // the caller's table, NULL = the context's
+    unsigned flags = 0;
+    bool key = false, through_pack = false;
+    const uint8_t* frame = nullptr;             // the frame on the device and its stride
+    size_t stride = 0;
+    long long n = 0;                            // tiles listed
+    mpc::PackGeometry g{0, 0, 0, 0};            // through_pack && n > 0: the packed frame's geometry, its records in d->pack
+    uint16_t* d_packed_counts = nullptr;
+    mpc_basis_choice* d_packed_choices = nullptr;
+};
+
+// 1. the frame on the device
+mpc_status delta_frame(mpc_delta* d, const uint8_t* rgb, size_t row_stride, hipStream_t s, DeltaCall& call) {
+    const size_t row = 3 * static_cast<size_t>(d->width);
+    call.frame = rgb;
+    call.stride = row_stride ? row_stride : row;
+    if (!(call.flags & MPC_DELTA_DEVICE_PIXELS)) {
+        if (const mpc_status gs = d->upload.reserve(row * static_cast<size_t>(d->height), "delta upload"); gs != MPC_OK) return gs;
+        uint8_t* up = reinterpret_cast<uint8_t*>(d->upload.data());
+        HIP_TRY(hipMemcpy2DAsync(up, row, rgb, call.stride, row, static_cast<size_t>(d->height), hipMemcpyHostToDevice, s));
+        call.frame = up;
+        call.stride = row;
+    }
+    return MPC_OK;
+}
+
+// 2., 3. the changed tiles: all of them for a key frame, else the diff's list; either way the kept copy becomes this frame
+mpc_status delta_list(mpc_delta* d, hipStream_t s, DeltaCall& call) {
+    const size_t row = 3 * static_cast<size_t>(d->width);
+    call.n = d->tiles;
+    d->changed.clear();
+    if (call.key) {
+        HIP_TRY(hipMemcpy2DAsync(d->d_kept, row, call.frame, call.stride, row, static_cast<size_t>(d->height), hipMemcpyDeviceToDevice, s));
+        if (call.through_pack) {
+            d->changed.resize(static_cast<size_t>(call.n));
+            for (long long t = 0; t < call.n; ++t) d->changed[static_cast<size_t>(t)] = static_cast<int32_t>(t);
+            HIP_TRY(hipMemcpyAsync(d->d_list, d->changed.data(), sizeof(int32_t) * d->changed.size(), hipMemcpyHostToDevice, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            d->changed.clear();
+        }
+        return MPC_OK;
+    }
+    if (const int e = mpc::launch_tile_diff(d->d_kept, call.frame, d->width, d->height, call.stride, d->d_list, d->d_count, d->d_scratch, s); e != 0)
+        return launch_failed(e);
+    int32_t count = -1;
+    HIP_TRY(hipMemcpyAsync(&count, d->d_count, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (count < 0 || count > d->tiles) return fail(MPC_ERR_HIP, "the diff counted %d of %lld tiles", count, d->tiles);
+    call.n = count;
+    d->changed.resize(static_cast<size_t>(call.n));
+    if (call.n > 0) {
+        HIP_TRY(hipMemcpyAsync(d->changed.data(), d->d_list, sizeof(int32_t) * static_cast<size_t>(call.n), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    return MPC_OK;
+}
+
+// 4. - 6. pursue: a key frame straight into the record store, else the packed frame of the listed tiles and its records scattered
+mpc_status delta_pursue(mpc_delta* d, hipStream_t s, DeltaCall& call) {
+    mpc_context* c = d->ctx;
+    const int K = c->K;
+    if (!call.through_pack)
+        return mpc_encode_tiles_device(c, call.frame, d->width, d->height, call.stride, 0, d->tiles_y, call.quant, d->d_counts, d->d_choices, nullptr,
+                                       nullptr, 0, s);
+    if (call.n == 0) return MPC_OK;
+    const mpc::PackGeometry g = call.g = mpc::pack_geometry(call.n, MPC_DELTA_PACK_ROWS);
+    const size_t packed_tc = 3 * static_cast<size_t>(g.rows) * static_cast<size_t>(g.cols);
+    uint8_t* d_packed = nullptr;
+    const auto layout = [&](char* base) {
+        Carve cv{base};
+        d_packed = cv.take<uint8_t>(g.bytes);
+        call.d_packed_counts = cv.take<uint16_t>(packed_tc + 2);
+        call.d_packed_choices = cv.take<mpc_basis_choice>(packed_tc * static_cast<size_t>(K));
+        return cv.at;
+    };
+    if (const mpc_status gs = d->pack.reserve(layout(nullptr), "delta packed frame"); gs != MPC_OK) return gs;
+    layout(d->pack.data());
+    if (const int e = mpc::launch_tile_pack(call.frame, d->width, d->height, call.stride, d->d_list, call.n, g.rows, g.cols, d_packed, g.stride, s); e != 0)
+        return launch_failed(e);
+    if (const mpc_status es = mpc_encode_tiles_device(c, d_packed, 8 * g.cols, 8 * g.rows, g.stride, 0, g.rows, call.quant, call.d_packed_counts,
+                                                      call.d_packed_choices, nullptr, nullptr, 0, s);
+        es != MPC_OK)
+        return es;
+    if (const int e = mpc::launch_tile_scatter_records(call.d_packed_counts, reinterpret_cast<const uint32_t*>(call.d_packed_choices), d->d_list, call.n,
+                                                       K, d->d_counts, reinterpret_cast<uint32_t*>(d->d_choices), d->tiles, d->d_count + 1, s);
+        e != 0)
+        return launch_failed(e);
+    return MPC_OK;
+}
+
+// 7. records -> container on job slot 0, as a compose finishes, with the seek index from the entropy stage where one is asked for
+// (`every` != 0).  The records and the geometry are the caller's: the store's of the whole frame, or the packed frame's
+mpc_status delta_container(mpc_delta* d, hipStream_t s, const Tuning& tuning, const uint16_t* d_counts, const mpc_basis_choice* d_choices,
+                           long long tiles, int width, int height, const double* quant, unsigned every, uint8_t** bytes, size_t* nbytes,
+                           uint8_t** index, size_t* index_bytes) {
+    mpc_context* c = d->ctx;
+    const int K = c->K;
+    if (!c->jobs[0]) c->jobs[0] = std::make_unique<JobSlot>();
+    JobSlot& js = *c->jobs[0];
+    ContainerJob& job = js.job;
+    if (!job.phase1) {
+        HIP_TRY(hipEventCreateWithFlags(&job.phase1, hipEventDisableTiming | hipEventBlockingSync));
+        HIP_TRY(hipEventCreateWithFlags(&job.done, hipEventDisableTiming | hipEventBlockingSync));
+    }
+    Carve measure;
+    mpc::StreamArgs measured{};
+    carve_stream_buffers(measure, tiles, K, true, &measured);
+    if (const mpc_status gs = js.dev.reserve(measure.at, "device staging"); gs != MPC_OK) return gs;
+    GrowBuffer host_stage(GrowBuffer::kPinned);                 // the host route's, should the frame take it: this call's own
+    job.side = job.down = s;
+    job.spin = true;
+    job.host_stage = &host_stage;
+    job.host_offset = 0;
+    job.index_interval = every;
+    job.index_expanded = every != 0;
+    struct Unhook {                                             // the slot is left as mpc_container_job_begin expects it
+        ContainerJob& job;
+        ~Unhook() {
+            job.host_stage = nullptr;
+            job.index_interval = 0;
+            job.index_expanded = false;
+            job.index.clear();
+        }
+    } unhook{job};
+    EntropyBuffers eb;
+    if (!tuning.host_entropy)
+        if (const mpc_status es = entropy_buffers(js.ent, static_cast<size_t>(tiles), K, &eb, every ? 2 : 0); es != MPC_OK) return es;
+    HIP_TRY(hipStreamSynchronize(nullptr));                     // a slot carved for another geometry clears its tables on the null stream
+    if (const mpc_status bs = container_begin(job, c, tuning.host_entropy ? nullptr : &eb, tuning.triple_limit, js.dev.data(), d_counts,
+                                              reinterpret_cast<const uint32_t*>(d_choices), nullptr, nullptr, width, height, quant);
+        bs != MPC_OK)
+        return bs;
+    if (const mpc_status ts = container_tables(job); ts != MPC_OK) return ts;
+    uint8_t* made = nullptr;
+    size_t made_bytes = 0;
+    if (const mpc_status cs = container_collect(job, &made, &made_bytes); cs != MPC_OK) return cs;
+    if (hipStreamSynchronize(s) != hipSuccess) {
+        std::free(made);
+        return fail(MPC_ERR_HIP, "the container job failed: %s", hipGetErrorString(hipGetLastError()));
+    }
+    if (every) {
+        uint8_t* copy = job.index.empty() ? nullptr : static_cast<uint8_t*>(std::malloc(job.index.size()));
+        if (!copy) {
+            std::free(made);
+            return fail(MPC_ERR_ALLOC, "no seek index");
+        }
+        std::memcpy(copy, job.index.data(), job.index.size());
+        *index = copy;
+        *index_bytes = job.index.size();
+    }
+    *bytes = made;
+    *nbytes = made_bytes;
+    return MPC_OK;
+}
+
+// One call of either kind.  The caller has checked its own pointers; here the refusals both share, then -- behind `clear`, which empties
+// the caller's outputs -- the three shared stages, `finish` (the fourth stage and the caller's result), and the session's new state
+template <class Clear, class Finish>
+mpc_status delta_call(mpc_delta* d, const uint8_t* rgb, size_t row_stride, const double* quant, unsigned flags, mpc_delta_info* info, Clear&& clear,
+                      Finish&& finish) {
+    if (flags & ~(MPC_DELTA_KEY | MPC_DELTA_DEVICE_PIXELS | MPC_DELTA_PACK_ALWAYS)) return fail(MPC_ERR_ARGUMENT, "flags 0x%x", flags);
+    mpc_context* c = d->ctx;
+    const int K = c->K;
+    const size_t row = 3 * static_cast<size_t>(d->width);
+    if (row_stride != 0 && row_stride < row) return fail(MPC_ERR_ARGUMENT, "row_stride %zu for %d pixels", row_stride, d->width);
+    if (c->device < 0) return no_device();
+    std::lock_guard<std::recursive_mutex> one_host_call(c->host_calls);
+    for (int k = 0; k < mpc_context::kSeqSlots; ++k)
+        if (c->jobs[k] && c->jobs[k]->stage != 0) return fail(MPC_ERR_ARGUMENT, "container job slot %d is busy", k);
+    // behind the checks: whatever fails from here on leaves a session whose next call is a key frame
+    clear();
+    struct Session {
+        mpc_delta* d;
+        bool keep = false;
+        ~Session() {
+            if (keep) return;
+            d->valid = false;
+            d->changed_all = false;
+            d->changed.clear();
+            d->info = mpc_delta_info{};
+        }
+    } session{d};
+    HIP_TRY(hipSetDevice(c->device));
+    const Tuning tuning = read_tuning();
+    const double* table = quant ? quant : c->quant.data();
+    const size_t table_bytes = sizeof(double) * 3 * static_cast<size_t>(K);
+    DeltaCall call;
+    call.quant = quant;
+    call.flags = flags;
+    call.key = !d->valid || (flags & MPC_DELTA_KEY) || d->fast != c->fast || d->quant.size() != 3 * static_cast<size_t>(K) ||
+               std::memcmp(d->quant.data(), table, table_bytes) != 0;
+    call.through_pack = !call.key || (flags & MPC_DELTA_PACK_ALWAYS);
+    hipStream_t s = d->stream;
+    struct Drain {                                              // whatever happens, nothing of this call is left running
+        hipStream_t s;
+        ~Drain() { (void)hipStreamSynchronize(s); }
+    } drain{s};
+    if (const mpc_status st = delta_frame(d, rgb, row_stride, s, call); st != MPC_OK) return st;
+    if (const mpc_status st = delta_list(d, s, call); st != MPC_OK) return st;
+    if (const mpc_status st = delta_pursue(d, s, call); st != MPC_OK) return st;
+    if (const mpc_status st = finish(call, s, tuning); st != MPC_OK) return st;
+    d->valid = true;
+    d->fast = c->fast;
+    d->quant.assign(table, table + 3 * static_cast<size_t>(K));
+    d->changed_all = call.key;
+    d->info = mpc_delta_info{static_cast<int>(d->tiles), static_cast<int>(call.n), call.key ? 1 : 0};
+    ++d->calls;
+    *info = d->info;
+    session.keep = true;
+    return MPC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
 mpc_status mpc_delta_encode(mpc_delta* d, const uint8_t* rgb, size_t row_stride, const double* quant, unsigned flags, int index_interval,
                             uint8_t** bytes, size_t* nbytes, uint8_t** index, size_t* index_bytes, mpc_delta_info* info) {
     return guarded([&]() -> mpc_status {
         if (!d || !rgb || !bytes || !nbytes || !info) return fail(MPC_ERR_ARGUMENT, "null argument");
         if (index_interval >= 0 && (!index || !index_bytes)) return fail(MPC_ERR_ARGUMENT, "null argument");
-        if (flags & ~(MPC_DELTA_KEY | MPC_DELTA_DEVICE_PIXELS | MPC_DELTA_PACK_ALWAYS)) return fail(MPC_ERR_ARGUMENT, "flags 0x%x", flags);
         if (index_interval > 0 && (index_interval < static_cast<int>(mpc::kIndexIntervalMin) || index_interval > static_cast<int>(mpc::kIndexIntervalMax)))
             return fail(MPC_ERR_ARGUMENT, "interval %d: 0 or %u to %u", index_interval, mpc::kIndexIntervalMin, mpc::kIndexIntervalMax);
         const unsigned every = index_interval < 0 ? 0u : index_interval ? static_cast<unsigned>(index_interval) : mpc::kIndexIntervalDefault;
-        mpc_context* c = d->ctx;
-        const int width = d->width, height = d->height, K = c->K;
-        const size_t row = 3 * static_cast<size_t>(width);
-        if (row_stride != 0 && row_stride < row) return fail(MPC_ERR_ARGUMENT, "row_stride %zu for %d pixels", row_stride, width);
-        if (c->device < 0) return no_device();
-        std::lock_guard<std::recursive_mutex> one_host_call(c->host_calls);
-        for (int k = 0; k < mpc_context::kSeqSlots; ++k)
-            if (c->jobs[k] && c->jobs[k]->stage != 0) return fail(MPC_ERR_ARGUMENT, "container job slot %d is busy", k);
-        // behind the checks: whatever fails from here on leaves a session whose next call is a key frame
-        *bytes = nullptr;
-        *nbytes = 0;
-        if (index) *index = nullptr;
-        if (index_bytes) *index_bytes = 0;
-        struct Session {
-            mpc_delta* d;
-            bool keep = false;
-            ~Session() {
-                if (keep) return;
-                d->valid = false;
-                d->changed_all = false;
-                d->changed.clear();
-                d->info = mpc_delta_info{};
-            }
-        } session{d};
-        HIP_TRY(hipSetDevice(c->device));
-        const Tuning tuning = read_tuning();
-        const double* table = quant ? quant : c->quant.data();
-        const size_t table_bytes = sizeof(double) * 3 * static_cast<size_t>(K);
-        const bool key = !d->valid || (flags & MPC_DELTA_KEY) || d->fast != c->fast || d->quant.size() != 3 * static_cast<size_t>(K) ||
-                         std::memcmp(d->quant.data(), table, table_bytes) != 0;
-        const bool through_pack = !key || (flags & MPC_DELTA_PACK_ALWAYS);
-        hipStream_t s = d->stream;
-        struct Drain {                                              // whatever happens, nothing of this call is left running
-            hipStream_t s;
-            ~Drain() { (void)hipStreamSynchronize(s); }
-        } drain{s};
-        // 1. the frame on the device
-        const uint8_t* frame = rgb;
-        size_t stride = row_stride ? row_stride : row;
-        if (!(flags & MPC_DELTA_DEVICE_PIXELS)) {
-            if (const mpc_status gs = d->upload.reserve(row * static_cast<size_t>(height), "delta upload"); gs != MPC_OK) return gs;
-            uint8_t* up = reinterpret_cast<uint8_t*>(d->upload.data());
-            HIP_TRY(hipMemcpy2DAsync(up, row, rgb, stride, row, static_cast<size_t>(height), hipMemcpyHostToDevice, s));
-            frame = up;
-            stride = row;
-        }
-        // 2., 3. the changed tiles: all of them for a key frame, else the diff's list; either way the kept copy becomes this frame
-        long long n = d->tiles;
-        d->changed.clear();
-        if (key) {
-            HIP_TRY(hipMemcpy2DAsync(d->d_kept, row, frame, stride, row, static_cast<size_t>(height), hipMemcpyDeviceToDevice, s));
-            if (through_pack) {
-                d->changed.resize(static_cast<size_t>(n));
-                for (long long t = 0; t < n; ++t) d->changed[static_cast<size_t>(t)] = static_cast<int32_t>(t);
-                HIP_TRY(hipMemcpyAsync(d->d_list, d->changed.data(), sizeof(int32_t) * d->changed.size(), hipMemcpyHostToDevice, s));
-                HIP_TRY(hipStreamSynchronize(s));
-                d->changed.clear();
-            }
-        } else {
-            if (const int e = mpc::launch_tile_diff(d->d_kept, frame, width, height, stride, d->d_list, d->d_count, d->d_scratch, s); e != 0)
-                return launch_failed(e);
-            int32_t count = -1;
-            HIP_TRY(hipMemcpyAsync(&count, d->d_count, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            if (count < 0 || count > d->tiles) return fail(MPC_ERR_HIP, "the diff counted %d of %lld tiles", count, d->tiles);
-            n = count;
-            d->changed.resize(static_cast<size_t>(n));
-            if (n > 0) {
-                HIP_TRY(hipMemcpyAsync(d->changed.data(), d->d_list, sizeof(int32_t) * static_cast<size_t>(n), hipMemcpyDeviceToHost, s));
-                HIP_TRY(hipStreamSynchronize(s));
-            }
-        }
-        // 4. - 6. pursue: a key frame straight into the record store, else the packed frame of the listed tiles and its records scattered
-        if (!through_pack) {
-            if (const mpc_status es = mpc_encode_tiles_device(c, frame, width, height, stride, 0, d->tiles_y, quant, d->d_counts, d->d_choices, nullptr,
-                                                              nullptr, 0, s);
-                es != MPC_OK)
-                return es;
-        } else if (n > 0) {
-            const mpc::PackGeometry g = mpc::pack_geometry(n, MPC_DELTA_PACK_ROWS);
-            const size_t packed_tc = 3 * static_cast<size_t>(g.rows) * static_cast<size_t>(g.cols);
-            uint8_t* d_packed = nullptr;
-            uint16_t* d_packed_counts = nullptr;
-            mpc_basis_choice* d_packed_choices = nullptr;
-            const auto layout = [&](char* base) {
-                Carve cv{base};
-                d_packed = cv.take<uint8_t>(g.bytes);
-                d_packed_counts = cv.take<uint16_t>(packed_tc + 2);
-                d_packed_choices = cv.take<mpc_basis_choice>(packed_tc * static_cast<size_t>(K));
-                return cv.at;
-            };
-            if (const mpc_status gs = d->pack.reserve(layout(nullptr), "delta packed frame"); gs != MPC_OK) return gs;
-            layout(d->pack.data());
-            if (const int e = mpc::launch_tile_pack(frame, width, height, stride, d->d_list, n, g.rows, g.cols, d_packed, g.stride, s); e != 0)
-                return launch_failed(e);
-            if (const mpc_status es = mpc_encode_tiles_device(c, d_packed, 8 * g.cols, 8 * g.rows, g.stride, 0, g.rows, quant, d_packed_counts,
-                                                              d_packed_choices, nullptr, nullptr, 0, s);
-                es != MPC_OK)
-                return es;
-            if (const int e = mpc::launch_tile_scatter_records(d_packed_counts, reinterpret_cast<const uint32_t*>(d_packed_choices), d->d_list, n, K,
-                                                               d->d_counts, reinterpret_cast<uint32_t*>(d->d_choices), d->tiles, d->d_count + 1, s);
-                e != 0)
-                return launch_failed(e);
-        }
-        // 7. records -> container on job slot 0, as a compose finishes, with the seek index from the entropy stage where one is asked for
-        if (!c->jobs[0]) c->jobs[0] = std::make_unique<JobSlot>();
-        JobSlot& js = *c->jobs[0];
-        ContainerJob& job = js.job;
-        if (!job.phase1) {
-            HIP_TRY(hipEventCreateWithFlags(&job.phase1, hipEventDisableTiming | hipEventBlockingSync));
-            HIP_TRY(hipEventCreateWithFlags(&job.done, hipEventDisableTiming | hipEventBlockingSync));
-        }
-        Carve measure;
-        mpc::StreamArgs measured{};
-        carve_stream_buffers(measure, d->tiles, K, true, &measured);
-        if (const mpc_status gs = js.dev.reserve(measure.at, "device staging"); gs != MPC_OK) return gs;
-        GrowBuffer host_stage(GrowBuffer::kPinned);                 // the host route's, should the frame take it: this call's own
-        job.side = job.down = s;
-        job.spin = true;
-        job.host_stage = &host_stage;
-        job.host_offset = 0;
-        job.index_interval = every;
-        job.index_expanded = every != 0;
-        struct Unhook {                                             // the slot is left as mpc_container_job_begin expects it
-            ContainerJob& job;
-            ~Unhook() {
-                job.host_stage = nullptr;
-                job.index_interval = 0;
-                job.index_expanded = false;
-                job.index.clear();
-            }
-        } unhook{job};
-        EntropyBuffers eb;
-        if (!tuning.host_entropy)
-            if (const mpc_status es = entropy_buffers(js.ent, static_cast<size_t>(d->tiles), K, &eb, every ? 2 : 0); es != MPC_OK) return es;
-        HIP_TRY(hipStreamSynchronize(nullptr));                     // a slot carved for another geometry clears its tables on the null stream
-        if (const mpc_status bs = container_begin(job, c, tuning.host_entropy ? nullptr : &eb, tuning.triple_limit, js.dev.data(), d->d_counts,
-                                                  reinterpret_cast<const uint32_t*>(d->d_choices), nullptr, nullptr, width, height, quant);
-            bs != MPC_OK)
-            return bs;
-        if (const mpc_status ts = container_tables(job); ts != MPC_OK) return ts;
-        uint8_t* made = nullptr;
-        size_t made_bytes = 0;
-        if (const mpc_status cs = container_collect(job, &made, &made_bytes); cs != MPC_OK) return cs;
-        if (hipStreamSynchronize(s) != hipSuccess) {
-            std::free(made);
-            return fail(MPC_ERR_HIP, "the container job failed: %s", hipGetErrorString(hipGetLastError()));
-        }
-        if (every) {
-            uint8_t* copy = job.index.empty() ? nullptr : static_cast<uint8_t*>(std::malloc(job.index.size()));
-            if (!copy) {
-                std::free(made);
-                return fail(MPC_ERR_ALLOC, "no seek index");
-            }
-            std::memcpy(copy, job.index.data(), job.index.size());
-            *index = copy;
-            *index_bytes = job.index.size();
-        }
-        *bytes = made;
-        *nbytes = made_bytes;
-        d->valid = true;
-        d->fast = c->fast;
-        d->quant.assign(table, table + 3 * static_cast<size_t>(K));
-        d->changed_all = key;
-        d->info = mpc_delta_info{static_cast<int>(d->tiles), static_cast<int>(n), key ? 1 : 0};
-        *info = d->info;
-        session.keep = true;
-        return MPC_OK;
+        return delta_call(
+            d, rgb, row_stride, quant, flags, info,
+            [&] {
+                *bytes = nullptr;
+                *nbytes = 0;
+                if (index) *index = nullptr;
+                if (index_bytes) *index_bytes = 0;
+            },
+            [&](const DeltaCall&, hipStream_t s, const Tuning& tuning) {
+                return delta_container(d, s, tuning, d->d_counts, d->d_choices, d->tiles, d->width, d->height, quant, every, bytes, nbytes, index,
+                                       index_bytes);
+            });
+    });
+}
+
+mpc_status mpc_delta_encode_patch(mpc_delta* d, const uint8_t* rgb, size_t row_stride, const double* quant, unsigned flags, uint8_t** patch,
+                                  size_t* patch_bytes, mpc_delta_info* info) {
+    return guarded([&]() -> mpc_status {
+        if (!d || !rgb || !patch || !patch_bytes || !info) return fail(MPC_ERR_ARGUMENT, "null argument");
+        bool key_patch = false;
+        const mpc_status st = delta_call(
+            d, rgb, row_stride, quant, flags, info,
+            [&] {
+                *patch = nullptr;
+                *patch_bytes = 0;
+            },
+            [&](const DeltaCall& call, hipStream_t s, const Tuning& tuning) -> mpc_status {
+                key_patch = call.key || call.n == d->tiles;
+                uint8_t* made = nullptr;
+                size_t made_bytes = 0;
+                if (key_patch) {                                    // the whole frame's container from the store
+                    if (const mpc_status cs = delta_container(d, s, tuning, d->d_counts, d->d_choices, d->tiles, d->width, d->height, quant, 0, &made,
+                                                              &made_bytes, nullptr, nullptr);
+                        cs != MPC_OK)
+                        return cs;
+                } else if (call.n > 0) {                            // the packed frame's, from its own counts and records
+                    if (const mpc_status cs = delta_container(d, s, tuning, call.d_packed_counts, call.d_packed_choices,
+                                                              static_cast<long long>(call.g.rows) * call.g.cols, 8 * call.g.cols, 8 * call.g.rows, quant,
+                                                              0, &made, &made_bytes, nullptr, nullptr);
+                        cs != MPC_OK)
+                        return cs;
+                }
+                struct Free {
+                    uint8_t* p;
+                    ~Free() { std::free(p); }
+                } made_guard{made};
+                const std::string why = mpc::patch_make_error(d->width, d->height, key_patch, d->changed.data(), call.n, made, made_bytes);
+                if (!why.empty()) return fail(MPC_ERR_HIP, "the patch: %s", why.c_str());
+                const std::vector<uint8_t> blob =
+                    mpc::patch_make(d->width, d->height, d->calls, key_patch, d->changed.data(), call.n, made, made_bytes);
+                uint8_t* out = static_cast<uint8_t*>(std::malloc(blob.size()));
+                if (!out) return fail(MPC_ERR_ALLOC, "no patch");
+                std::memcpy(out, blob.data(), blob.size());
+                *patch = out;
+                *patch_bytes = blob.size();
+                return MPC_OK;
+            });
+        if (st == MPC_OK && key_patch) info->key = 1;               // every tile listed: sent as a key patch
+        return st;
     });
 }
 

@@ -929,6 +929,91 @@ mpc_status mpc_delta_encode(mpc_delta* d, const uint8_t* rgb, size_t row_stride,
                             uint8_t** bytes, size_t* nbytes, uint8_t** index, size_t* index_bytes, mpc_delta_info* info);
 mpc_status mpc_delta_changed(const mpc_delta* d, int32_t* tiles, int capacity, int* n);   /* the last call's list */
 
+/* ---- patch: send only the changed tiles, apply them on the device ("Delta stream") ----
+ * The packed frame of a delta call's listed tiles is an ordinary frame, so its container is an ordinary container.  A PATCH is the
+ * ascending tile list plus that container: what a receiver that holds the previous frame needs, at a few per cent of the bytes.
+ *
+ * THE FORMAT, version 1, little endian:
+ *    0 "MPCP" | 4 u16 version = 1 | 6 u16 flags: bit 0 = key, every other bit 0 | 8 u32 width | 12 u32 height | 16 u32 sequence |
+ *   20 u32 n (tiles listed) | 24 u32 list_bytes | 28 u32 0 | 32 u64 container_bytes | 40 the list, then the container
+ * and the patch is exactly 40 + list_bytes + container_bytes long.  The list holds the gaps of the ascending tile list, g0 = t0,
+ * gj = tj - t(j-1) - 1, each as LEB128: 7 bits a byte, low group first, at most 5 bytes, value below 2^31; a multi-byte value whose
+ * last byte is 0x00 is refused.  Ascending order and distinctness hold by construction; exactly n values fill exactly list_bytes; the
+ * last tile is below tiles = ceil(width / 8) * ceil(height / 8) (tile t = tx * tiles_y + ty, as everywhere).  Three forms:
+ *   key    flag set, n = tiles, list_bytes = 0; the container is the whole frame's (width x height)
+ *   empty  no flag, n = 0, list_bytes = 0, container_bytes = 0: 40 bytes
+ *   tile   no flag, 0 < n < tiles; the container's header says 8C x 8R pixels with (R, C) = mpc_delta_pack_geometry(n,
+ *          MPC_DELTA_PACK_ROWS) -- the 64 is part of format version 1 -- and listed tile j is tile (j / R, j % R) of it
+ * There is no patch with n == tiles and no key flag: the sender writes a key patch instead.
+ *
+ * Host only, no context:
+ *   mpc_patch_make   the only writer: *bytes (mpc_free).  key != 0: n must be the frame's tile count, `tiles` is not read; else n == 0
+ *                    with container_bytes == 0, or 0 < n < tiles with tiles[n] ascending, distinct and inside the frame.  The container's
+ *                    bytes are copied as they are (mpc_patch_info is what checks them), so a whole-frame container from anywhere
+ *                    becomes a key patch.  MPC_ERR_ARGUMENT for anything else.
+ *   mpc_patch_info   validates the patch whole -- header, form, list, length, and the container's own header through
+ *                    mpc_container_info and its size against the form -- and reports it; container_offset is from `bytes`.
+ *   mpc_patch_tiles  the list (a key patch's: every tile); *n its length, also when `capacity` is too small: then MPC_ERR_ARGUMENT and
+ *                    nothing is copied, except that capacity == 0 only asks for *n.
+ * A refused patch is MPC_ERR_BITSTREAM, a null pointer or bad geometry MPC_ERR_ARGUMENT; nothing in a header is trusted, nothing is
+ * read outside [bytes, bytes + nbytes), and no more is allocated than the patch is long.
+ *
+ * THE SENDER, mpc_delta_encode_patch: mpc_delta_encode's flags, refusals and stages up to the records (frame on the device, list,
+ * pursuit and scatter), so a session's store advances identically whichever of the two is called, in any mix.  A call is a key
+ * frame by mpc_delta_encode's rule, and sent as a key patch also when the diff lists every tile (info->key = 1 then too).
+ *   key patch    the container from the store: byte for byte mpc_encode_image_device of the frame
+ *   tile patch   the same container job, on job slot 0, run on the packed frame's counts and records at 8C x 8R: byte for byte
+ *                mpc_encode_image_device of the packed frame mpc_pack_tiles_device makes of the list
+ *   empty patch  no pursuit launch and no container job
+ * `sequence` is the number of successful calls of either kind the session had before this one.  *patch: mpc_free.
+ *
+ * mpc_unpack_tiles_device: mpc_pack_tiles_device's inverse on the caller's buffers, asynchronous on `stream`.  The pixel bytes of listed
+ * tile j, at tile (j / R, j % R) of the packed frame mpc_delta_pack_geometry(n, rows) describes (d_packed 8-byte aligned; packed_stride
+ * 0 = 24 * C, else a multiple of 8 and at least 24 * C), go to tile d_list[j] of the frame at d_rgb (row_stride 0 = 3 * width; any
+ * base, any stride).  Only bytes inside the image are written: none at or behind 3 * width of a row, no row at or below height,
+ * nothing for the R * C - n padding tiles, nothing of any other tile.  8-byte stores where d_rgb and row_stride are multiples of 8
+ * and the chunk lies whole inside its row, byte by byte otherwise.  A list entry outside [0, tiles) writes nothing and sets the
+ * context's crop error word (mpc_crop_records_check reads and clears it).  The argument rules of the three kernels above.
+ *
+ * THE RECEIVER: a session that owns, on the context's device, the current frame (tightly packed, black until the first key patch),
+ * a grow-only staging area for decoded pixels, the list and a stream.  It keeps no records.  Destroy it before its context.
+ * mpc_patch_apply is synchronous:
+ *   1. mpc_patch_info's checks on the host; width and height must be the session's (else MPC_ERR_ARGUMENT)
+ *   2. a key patch sets expected = sequence + 1; any other patch needs a session that has had a key patch and sequence == expected,
+ *      else MPC_ERR_ARGUMENT with both numbers in mpc_last_error
+ *   3. the container's block size and K must be the context's (MPC_ERR_ARGUMENT)
+ *   4. key patch: mpc_decode_image_device into staging, then one device copy to the frame.  Tile patch: the same decode of the packed
+ *      frame into staging, the list uploaded, the unpack kernel.  Empty patch: only the sequence advances.
+ * ATOMIC: a refusal -- a bad patch, a container the decoder refuses (its status and text), one of the wrong size, a wrong sequence,
+ * a wrong block size or K -- leaves the frame, the list and the expected sequence exactly as they were; nothing reaches the frame
+ * before every check has passed and the container is decoded whole.  (A device failure behind that, MPC_ERR_HIP, leaves a session
+ * that wants a key patch.)  The decode takes the context's flavour, as mpc_decode_image does.
+ *   mpc_patch_frame_device  the kept frame, height rows of 3 * width bytes, valid until the next apply
+ *   mpc_patch_read          its copy to the host (row_stride 0 = 3 * width)
+ *   mpc_patch_changed       the last successful apply's list, with mpc_delta_changed's rules */
+struct mpc_patch_info {
+    int width, height;
+    uint32_t sequence;
+    int key;
+    int n, tiles;                              /* tiles listed (a key patch: all), tiles of the frame */
+    size_t container_offset, container_bytes;
+};
+mpc_status mpc_patch_make(int width, int height, uint32_t sequence, int key, const int32_t* tiles, int n, const uint8_t* container,
+                          size_t container_bytes, uint8_t** bytes, size_t* nbytes);
+mpc_status mpc_patch_info(const uint8_t* bytes, size_t nbytes, struct mpc_patch_info* info);
+mpc_status mpc_patch_tiles(const uint8_t* bytes, size_t nbytes, int32_t* tiles, int capacity, int* n);
+mpc_status mpc_delta_encode_patch(mpc_delta* d, const uint8_t* rgb, size_t row_stride, const double* quant, unsigned flags, uint8_t** patch,
+                                  size_t* patch_bytes, mpc_delta_info* info);
+mpc_status mpc_unpack_tiles_device(mpc_context* ctx, const uint8_t* d_packed, size_t packed_stride, const int32_t* d_list, int n, int rows,
+                                   uint8_t* d_rgb, int width, int height, size_t row_stride, void* stream);
+typedef struct mpc_patch_decoder mpc_patch_decoder;
+mpc_status mpc_patch_decoder_create(mpc_context* ctx, int width, int height, mpc_patch_decoder** out);
+void       mpc_patch_decoder_destroy(mpc_patch_decoder* p);
+mpc_status mpc_patch_apply(mpc_patch_decoder* p, const uint8_t* patch, size_t nbytes, struct mpc_patch_info* info);
+mpc_status mpc_patch_frame_device(mpc_patch_decoder* p, uint8_t** d_rgb);
+mpc_status mpc_patch_read(mpc_patch_decoder* p, uint8_t* rgb, size_t row_stride);
+mpc_status mpc_patch_changed(const mpc_patch_decoder* p, int32_t* tiles, int capacity, int* n);
+
 /* ---- budget: encode to a byte budget ("Encoder: a byte budget") ----
  * The container is layered by pursuit step, every tile-channel has its own length and nothing reads a record beyond its count: cutting
  * a tile to its first n steps is a change of three counts, and the result is a container every decoder reads unchanged.  The search
