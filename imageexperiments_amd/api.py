@@ -73,6 +73,11 @@ class MpcPatchInfo(C.Structure):                     # struct mpc_patch_info
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
+class MpcRateInfo(C.Structure):                      # mpc_rate_info
+    _fields_ = [("tiles", C.c_int), ("changed", C.c_int), ("key", C.c_int), ("candidates", C.c_int), ("sent_tiles", C.c_int), ("owed", C.c_int),
+                ("lambda_index", C.c_int), ("probes", C.c_int), ("all_bytes", C.c_size_t), ("sse", C.c_ulonglong)]
+
+
 class MpcBudgetInfo(C.Structure):                    # mpc_budget_info
     _fields_ = [("lambda_index", C.c_int), ("probes", C.c_int), ("full_bytes", C.c_size_t), ("sse", C.c_ulonglong),
                 ("full_sse", C.c_ulonglong), ("records", C.c_ulonglong), ("full_records", C.c_ulonglong)]
@@ -326,6 +331,17 @@ def _bind_bitstream(L):
         for f in ("mpc_encode_image_budget", "mpc_encode_image_budget_device"):
             getattr(L, f).argtypes = [vp, vp, C.c_int, C.c_int, _dp, C.c_size_t, C.c_int, C.POINTER(_u8p), _szp_, C.POINTER(_u8p), _szp_, _u8p,
                                       C.POINTER(MpcBudgetInfo)]
+    except AttributeError:
+        if not os.environ.get("MPCODEC_LIB"):             # an older build may be loaded for A/B timing only
+            raise
+    try:
+        L.mpc_owed_tiles.argtypes = [_u8p, _u16p, C.c_longlong, C.c_int, _i32p, C.c_int, _i32p, _u8p, _u8p, C.POINTER(C.c_int)]
+        L.mpc_budget_allocate_floor.argtypes = [_u32p, _u16p, _u8p, _u8p, C.c_longlong, C.c_int, _u32p, C.c_int, _u8p, _u16p, _u8p, _u64p]
+        L.mpc_owed_tiles_device.argtypes = [vp, vp, vp, C.c_longlong, vp, vp, vp, vp, vp, vp]
+        L.mpc_gather_records_device.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp]
+        L.mpc_budget_allocate_floor_device.argtypes = [vp, vp, vp, vp, vp, C.c_longlong, _u32p, C.c_int, vp, vp, vp, vp, vp]
+        L.mpc_delta_encode_patch_budget.argtypes = [vp, vp, C.c_size_t, _dp, C.c_uint, C.c_size_t, C.POINTER(_u8p), _szp_, C.POINTER(MpcRateInfo)]
+        L.mpc_delta_sent.argtypes = [vp, _u8p, C.c_int, C.POINTER(C.c_int)]
     except AttributeError:
         if not os.environ.get("MPCODEC_LIB"):             # an older build may be loaded for A/B timing only
             raise
@@ -871,6 +887,50 @@ class DeltaEncoder:
         return self._encode_patch(int(d_rgb), row_stride, quant, flags)
 
 
+    def _encode_patch_budget(self, ptr, row_stride, budget, quant, flags):
+        qp = None
+        if quant is not None:
+            quant = np.ascontiguousarray(quant, np.float64).reshape(3, self.ctx.K)
+            qp = quant.ctypes.data_as(_dp)
+        out, n, info = _u8p(), C.c_size_t(0), MpcRateInfo()
+        _check(self.L.mpc_delta_encode_patch_budget(self.h, ptr, int(row_stride), qp, int(flags), int(budget), C.byref(out), C.byref(n),
+                                                    C.byref(info)))
+        self.info = (info.tiles, info.changed, info.key)
+        return _take_bytes(self.L, out, n), RateInfo(info)
+
+    def encode_patch_budget(self, rgb, budget, quant=None, key=False):
+        """mpc_delta_encode_patch_budget of a host frame -> (the patch, at most `budget` bytes; RateInfo): the changed tiles, cut to the
+        depths a multiplier found by bisection assigns them, and as many of the tiles sent thin before as the bytes left pay for."""
+        rgb = _pixel_rows(rgb)
+        if rgb.shape[:2] != (self.height, self.width):
+            raise ValueError("the frame is not the session's size")
+        return self._encode_patch_budget(rgb.ctypes.data, rgb.strides[0], budget, quant, MPC_DELTA_KEY if key else 0)
+
+    def encode_patch_budget_device(self, d_rgb, budget, row_stride=0, quant=None, key=False):
+        """The same for a frame in device memory: d_rgb an int from tensor.data_ptr(), row_stride bytes between rows (0 = 3 * width)."""
+        return self._encode_patch_budget(int(d_rgb), row_stride, budget, quant, MPC_DELTA_DEVICE_PIXELS | (MPC_DELTA_KEY if key else 0))
+
+    def sent(self):
+        """mpc_delta_sent: the depth the receiver holds of each tile after the last budget call (uint8 per tile)"""
+        n = C.c_int(0)
+        _check(self.L.mpc_delta_sent(self.h, None, 0, C.byref(n)))
+        depth = np.zeros(max(n.value, 1), np.uint8)
+        _check(self.L.mpc_delta_sent(self.h, depth.ctypes.data_as(_u8p), n.value, C.byref(n)))
+        return depth[:n.value]
+
+
+class RateInfo:
+    """mpc_rate_info's fields of one DeltaEncoder.encode_patch_budget call"""
+    __slots__ = tuple(f for f, _ in MpcRateInfo._fields_)
+
+    def __init__(self, info):
+        for f, _ in MpcRateInfo._fields_:
+            setattr(self, f, int(getattr(info, f)))
+
+    def __repr__(self):
+        return "RateInfo(" + ", ".join(f"{f}={getattr(self, f)}" for f in self.__slots__) + ")"
+
+
 def patch_make(width, height, sequence, tiles, container, key=False):
     """mpc_patch_make: the only writer of a patch -> bytes.  key: `tiles` is not read (None will do) and the container is the whole
     frame's; else `tiles` ascending with the container of their packed frame, or empty with container None or b""."""
@@ -985,6 +1045,40 @@ def budget_allocate(profile, counts, weights, j):
                                               int(j), depth.ctypes.data_as(_u8p), cut.ctypes.data_as(_u16p),
                                               totals.ctypes.data_as(C.POINTER(C.c_uint64))))
     return depth[:T], cut[:T], totals
+
+
+def owed_tiles(sent, counts, K, changed):
+    """mpc_owed_tiles: sent uint8 [T], counts uint16 [T, 3], changed (ascending tile numbers) -> (candidates int32, ascending: the
+    changed and the owed tiles; floor uint8 [T]; must uint8 [T]): a tile is owed iff sent[t] < max over ch of min(count, K)"""
+    sent = np.ascontiguousarray(sent, np.uint8)
+    T = sent.shape[0]
+    counts = np.ascontiguousarray(counts, np.uint16).reshape(T, 3)
+    changed = np.ascontiguousarray(changed, np.int32).reshape(-1)
+    cand, floor, must, n = np.zeros(max(T, 1), np.int32), np.zeros(max(T, 1), np.uint8), np.zeros(max(T, 1), np.uint8), C.c_int(0)
+    _check(load_library().mpc_owed_tiles(sent.ctypes.data_as(_u8p), counts.ctypes.data_as(_u16p), T, int(K), changed.ctypes.data_as(_i32p),
+                                         changed.size, cand.ctypes.data_as(_i32p), floor.ctypes.data_as(_u8p), must.ctypes.data_as(_u8p),
+                                         C.byref(n)))
+    return cand[:n.value], floor[:T], must[:T]
+
+
+def budget_allocate_floor(profile, counts, floor, must, weights, j):
+    """mpc_budget_allocate_floor: budget_allocate over candidates with a floor each (uint8 [n] or None = 0) and a must byte each (or
+    None = 1) -> (depth uint8 [n], cut counts uint16 [n, 3], send uint8 [n], totals uint64 [4] = distortion, rate, records kept in the
+    candidates sent, candidates sent)"""
+    profile = np.ascontiguousarray(profile, np.uint32)
+    T, K = profile.shape[0], profile.shape[1] - 1
+    counts = np.ascontiguousarray(counts, np.uint16).reshape(T, 3)
+    weights = np.ascontiguousarray(weights, np.uint32).reshape(3, K)
+    floor = None if floor is None else np.ascontiguousarray(floor, np.uint8).reshape(T)
+    must = None if must is None else np.ascontiguousarray(must, np.uint8).reshape(T)
+    depth, cut, send = np.zeros(max(T, 1), np.uint8), np.zeros((max(T, 1), 3), np.uint16), np.zeros(max(T, 1), np.uint8)
+    totals = np.zeros(4, np.uint64)
+    _check(load_library().mpc_budget_allocate_floor(profile.ctypes.data_as(_u32p), counts.ctypes.data_as(_u16p),
+                                                    None if floor is None else floor.ctypes.data_as(_u8p),
+                                                    None if must is None else must.ctypes.data_as(_u8p), T, K, weights.ctypes.data_as(_u32p),
+                                                    int(j), depth.ctypes.data_as(_u8p), cut.ctypes.data_as(_u16p), send.ctypes.data_as(_u8p),
+                                                    totals.ctypes.data_as(C.POINTER(C.c_uint64))))
+    return depth[:T], cut[:T], send[:T], totals
 
 
 class BudgetResult:
@@ -1729,6 +1823,32 @@ class CompressionContext:
         weights = np.ascontiguousarray(weights, np.uint32).reshape(3, self.K)
         _check(self.L.mpc_budget_allocate_device(self.h, d_profile, d_counts, int(tiles), weights.ctypes.data_as(_u32p), int(j), d_depth,
                                                  d_out_counts, d_totals, stream or None))
+
+    def owed_tiles_device(self, d_sent, d_counts, tiles, d_flags, d_floor, d_must, d_list, d_count, stream=0):
+        """mpc_owed_tiles_device: d_flags[tiles] (uint8, != 0: changed) gains the owed tiles of d_sent / d_counts; d_floor and d_must
+        per tile as owed_tiles gives them; the candidates, ascending, in d_list (int32 per tile) and d_count (int32).  Asynchronous."""
+        _check(self.L.mpc_owed_tiles_device(self.h, d_sent, d_counts, int(tiles), d_flags, d_floor, d_must, d_list, d_count, stream or None))
+
+    def gather_records_device(self, d_counts, d_choices, tiles, d_list, m, d_idx, d_depth, n, rows, d_packed_counts, d_packed_choices,
+                              stream=0, check=True):
+        """mpc_gather_records_device: scatter_records_device turned round: packed tile j < n of delta_pack_geometry(n, rows) takes the
+        records of tile d_list[d_idx[j]] (d_idx 0 = the identity) cut to d_depth[d_idx[j]] (0 = uncut), zero above the cut and in the
+        padding tiles.  check: mpc_crop_records_check behind it, which waits for `stream` and raises MpcError(MPC_ERR_BITSTREAM) if an
+        entry was outside its range (that packed tile is all zero)."""
+        _check(self.L.mpc_gather_records_device(self.h, d_counts, d_choices, int(tiles), d_list, int(m), d_idx or None, d_depth or None, int(n),
+                                                int(rows), d_packed_counts, d_packed_choices, stream or None))
+        if check:
+            _check(self.L.mpc_crop_records_check(self.h, stream or None))
+
+    def budget_allocate_floor_device(self, d_profile, d_counts, d_floor, d_must, n, weights, j, d_depth, d_out_counts, d_send, d_totals,
+                                     stream=0):
+        """mpc_budget_allocate_floor_device: budget_allocate_floor on the device; weights uint32 [3, K] in host memory; d_floor, d_must
+        (uint8 [n]; 0 = all 0, all 1); d_depth[n], d_send[n] (uint8), d_out_counts[n, 3] (uint16), d_totals[4] (uint64, zeroed first).
+        Asynchronous."""
+        weights = np.ascontiguousarray(weights, np.uint32).reshape(3, self.K)
+        _check(self.L.mpc_budget_allocate_floor_device(self.h, d_profile, d_counts, d_floor or None, d_must or None, int(n),
+                                                       weights.ctypes.data_as(_u32p), int(j), d_depth, d_out_counts, d_send, d_totals,
+                                                       stream or None))
 
     def delta_encoder(self, width, height):
         """mpc_delta_create: a DeltaEncoder for frames of width x height through this context"""

@@ -9,10 +9,10 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "lib", "libmpcodec.so")
-SOURCES = ["host_dictionary.cpp", "host_bitstream.cpp", "host_container.cpp", "host_pool.cpp", "host_codec.cpp", "host_stats.cpp", "host_delta.cpp", "host_patch.cpp", "host_budget.cpp", "mp_kernels.hip", "mp_pursuit.hip",
-           "mp_streams.hip", "mp_entropy.hip", "mp_unpack.hip", "mp_parse.hip", "mp_scan.hip", "mp_delta.hip", "mp_budget.hip", "mpcodec_context.cpp", "mpcodec_container.cpp", "mpcodec_pipeline.cpp", "mpcodec_bitstream.cpp", "mpcodec_decode.cpp",
-           "mpcodec_decode_seq.cpp", "mpcodec_index.cpp", "mpcodec_multi.cpp", "mpcodec_rd.cpp", "mpcodec_debug.cpp", "mpcodec_delta.cpp", "mpcodec_patch.cpp", "mpcodec_budget.cpp"]
-HEADERS = ["host_dictionary.h", "host_bitstream.h", "host_codec.h", "host_stats.h", "host_delta.h", "host_patch.h", "host_budget.h", "mp_device.h", "mp_codes.h", "mpc_internal.h", os.path.join("..", "..", "include", "mpcodec.h")]
+SOURCES = ["host_dictionary.cpp", "host_bitstream.cpp", "host_container.cpp", "host_pool.cpp", "host_codec.cpp", "host_stats.cpp", "host_delta.cpp", "host_patch.cpp", "host_budget.cpp", "host_rate.cpp", "mp_kernels.hip", "mp_pursuit.hip",
+           "mp_streams.hip", "mp_entropy.hip", "mp_unpack.hip", "mp_parse.hip", "mp_scan.hip", "mp_delta.hip", "mp_budget.hip", "mp_rate.hip", "mpcodec_context.cpp", "mpcodec_container.cpp", "mpcodec_pipeline.cpp", "mpcodec_bitstream.cpp", "mpcodec_decode.cpp",
+           "mpcodec_decode_seq.cpp", "mpcodec_index.cpp", "mpcodec_multi.cpp", "mpcodec_rd.cpp", "mpcodec_debug.cpp", "mpcodec_delta.cpp", "mpcodec_patch.cpp", "mpcodec_budget.cpp", "mpcodec_rate.cpp"]
+HEADERS = ["host_dictionary.h", "host_bitstream.h", "host_codec.h", "host_stats.h", "host_delta.h", "host_patch.h", "host_budget.h", "host_rate.h", "mp_device.h", "mp_codes.h", "mpc_internal.h", "mpc_delta_session.h", os.path.join("..", "..", "include", "mpcodec.h")]
 # -ffp-contract=off: host and device must round every mul and add separately (the reference is built
 # with MSVC /fp:precise and the integer outputs depend on it).
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-pthread",

@@ -217,7 +217,7 @@ int launch_tile_diff(uint8_t* kept, const uint8_t* rgb, int width, int height, s
     const long long strips = (tiles_x + kDiffTiles - 1) / kDiffTiles;
     if (tiles >= (1LL << 31) || strips * tiles_y >= (1LL << 31)) return (int)hipErrorInvalidValue;
     uint8_t* flags = static_cast<uint8_t*>(scratch);
-    unsigned* block_live = reinterpret_cast<unsigned*>(flags + ((tiles + 255) & ~255LL));
+    unsigned* block_live = tile_diff_block_live(scratch, tiles);
     const size_t row_bytes = 3 * (size_t)width;
     const bool words = ((reinterpret_cast<uintptr_t>(kept) | reinterpret_cast<uintptr_t>(rgb) | row_stride | row_bytes) & 7) == 0;
     const dim3 grid((unsigned)(strips * tiles_y));
@@ -227,6 +227,18 @@ int launch_tile_diff(uint8_t* kept, const uint8_t* rgb, int width, int height, s
     else
         hipLaunchKernelGGL(mp_tile_diff_kernel<false>, grid, dim3(kDiffThreads), 0, s, kept, rgb, width, height, (long long)row_stride, (int)tiles_x,
                            (int)tiles_y, (int)strips, flags);
+    return launch_tile_flags_list(flags, tiles, block_live, list, count, s);
+}
+
+unsigned* tile_diff_block_live(void* scratch, long long tiles)
+{
+    return reinterpret_cast<unsigned*>(static_cast<uint8_t*>(scratch) + ((tiles + 255) & ~255LL));
+}
+
+int launch_tile_flags_list(const uint8_t* flags, long long tiles, unsigned* block_live, int32_t* list, int32_t* count, void* stream_)
+{
+    hipStream_t s = static_cast<hipStream_t>(stream_);
+    if (!flags || !block_live || !list || !count || tiles < 1 || tiles >= (1LL << 31)) return (int)hipErrorInvalidValue;
     const int blocks = (int)list_blocks(tiles);
     hipLaunchKernelGGL(mp_tile_flag_count_kernel, dim3((unsigned)blocks), dim3(kListBlock), 0, s, flags, tiles, block_live);
     StreamArgs a{};

@@ -10,6 +10,7 @@
 //   mp_parse.hip     the entropy codes of a container undone chunk by chunk from a seek index (ParseArgs)
 //   mp_scan.hip      that seek index's checkpoints found by a scan over every bit position of a stream (ScanArgs)
 //   mp_budget.hip    rate control: a tile's squared error at every depth, the depth that minimises distortion + multiplier * rate
+//   mp_rate.hip      a delta stream to a byte budget: owed flags, the records gather with a cut, the allocation with a floor
 //   mp_kernels.hip   the decoder, the symbol histogram, and the product's own cross-check of the tile encoder: a STEP-SYNCHRONOUS
 //                    pursuit that correlates every row exactly (a short sequence of kernels per MP step over the active
 //                    tile-channels: init, fill, base sweep, detail sweep, finish, update), behind MPC_PATH=steps / MPC_FILTER=0
@@ -359,6 +360,56 @@ struct AllocateParams {
     uint32_t weights[3 * kMaxDeviceK];   // [3][K]
 };
 int launch_budget_allocate(const AllocateParams& p, void* stream);
+
+// ---- a delta stream to a byte budget (mp_rate.hip; include/mpcodec.h, "rate") ----
+// The tail of launch_tile_diff alone (mp_delta.hip): list[0 .. *count) = the tiles whose flag byte is not 0, ascending.  block_live:
+// 3 words per 1024 tiles, as tile_diff_scratch_bytes lays them out behind the flags
+int launch_tile_flags_list(const uint8_t* flags, long long tiles, unsigned* block_live, int32_t* list, int32_t* count, void* stream);
+unsigned* tile_diff_block_live(void* scratch, long long tiles);
+// host_rate.h: owed_tiles, per tile.  flags[t] != 0 on entry: tile t is changed; on return flags[t] != 0: tile t is a candidate
+// (bit 1 = owed: sent[t] < max over ch of min(counts[t * 3 + ch], K)).  must[t] = changed, floor[t] = changed ? 0 : sent[t]
+int launch_owed_flags(const uint8_t* sent, const uint16_t* counts, long long tiles, int K, uint8_t* flags, uint8_t* floor, uint8_t* must,
+                      void* stream);
+// The scatter turned round, with a cut: packed tile j < n takes the records of candidate c = idx ? idx[j] : j, tile list[c], with the
+// counts min(count, K, depth ? depth[c] : K); every entry at or above that count is 0, and so are the counts and entries of the padding
+// tiles n <= j < padded.  c outside [0, m) or list[c] outside [0, tiles): that packed tile is all 0 and *error is set
+struct GatherParams {
+    const uint16_t* counts;          // [tiles][3]
+    const uint32_t* choices;         // [tiles][3][K]
+    long long tiles;
+    const int32_t* list;             // [m]
+    long long m;
+    const int32_t* idx;              // [n] or null
+    const uint8_t* depth;            // [m] or null
+    long long n, padded;
+    int K;
+    uint16_t* out_counts;            // [padded][3]
+    uint32_t* out_choices;           // [padded][3][K]
+    int* error;
+    const uint8_t* tile_bytes[2];    // each null, or a byte per tile that travels with the records (a call's floor and must) ...
+    uint8_t* out_bytes[2];           // ... to [padded]; 0 for a padding tile
+};
+int launch_gather_records(const GatherParams& p, void* stream);
+// A budget call's commit: sent[list[c]] = depth ? depth[c] : K for c = idx ? idx[j] : j, j < n; entries outside their ranges are skipped
+int launch_sent_commit(const int32_t* list, long long m, const int32_t* idx, const uint8_t* depth, long long n, int K, uint8_t* sent,
+                       long long tiles, void* stream);
+// The allocation with a floor at one multiplier (host_rate.h: budget_allocate_floor defines it): depth[n], out_counts[n][3], send[n],
+// totals[0 .. 3] += (the caller zeroes them).  floor, must: null = all 0, all 1
+struct AllocateFloorParams {
+    const uint32_t* profile;         // [n][K + 1]
+    const uint16_t* counts;          // [n][3]
+    const uint8_t* floor;            // [n] or null
+    const uint8_t* must;             // [n] or null
+    long long n;
+    int K;
+    unsigned long long lambda;
+    uint8_t* depth;
+    uint16_t* out_counts;
+    uint8_t* send;
+    unsigned long long* totals;      // [4]
+    uint32_t weights[3 * kMaxDeviceK];   // [3][K]
+};
+int launch_budget_allocate_floor(const AllocateFloorParams& p, void* stream);
 
 // ---- the decoder's per-symbol work in front of the gather (mp_unpack.hip): run-length expansion, DC sums ----
 constexpr int kUnpackBlock = 2048;      // coded symbols per workgroup

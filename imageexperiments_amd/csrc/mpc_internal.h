@@ -14,6 +14,7 @@
 //   mpcodec_delta.cpp      the delta encoder (mpc_delta_*): diff against the kept frame, pursuit of the changed tiles only
 //   mpcodec_patch.cpp      the delta stream's patches (mpc_patch_*): the format's entry points (host_patch.h) and the receiver session
 //   mpcodec_budget.cpp     encode to a byte budget (mpc_encode_image_budget): depth profile, allocation, the search over the multiplier
+//   mpcodec_rate.cpp       a delta stream to a byte budget (mpc_delta_encode_patch_budget): the sent map, candidates, the search with floors
 #pragma once
 
 #include "../../include/mpcodec.h"
@@ -469,5 +470,31 @@ mpc_status encode_batch_device(mpc_context* c, const Tuning& t, const uint8_t* d
                                int height, size_t row_stride, int tile_row_begin, int tile_row_end, const double* quant,
                                uint16_t* d_counts, mpc_basis_choice* d_choices, double* d_energy, uint32_t* d_swept, void* stream,
                                bool whole_frame_order, const mpc::FrameTable* table = nullptr);
+
+// ---- records -> container for a synchronous caller (mpcodec_delta.cpp): the delta encoder, the budget search and the rate search ----
+// a container and its seek index in malloc'ed memory, released unless taken
+struct ContainerMade {
+    uint8_t* bytes = nullptr;
+    size_t nbytes = 0;
+    std::vector<uint8_t> index;
+    ContainerMade() = default;
+    ContainerMade(const ContainerMade&) = delete;
+    ContainerMade& operator=(const ContainerMade&) = delete;
+    ~ContainerMade() { std::free(bytes); }
+    void swap(ContainerMade& o) {
+        std::swap(bytes, o.bytes);
+        std::swap(nbytes, o.nbytes);
+        index.swap(o.index);
+    }
+};
+// One records-to-container job on job slot 0 with everything on `s`, as a compose finishes: the container of `d_counts` / `d_choices`
+// (the caller's records and geometry), and with `every` != 0 its version-2 seek index from the entropy stage.  The call waits for
+// the container; the slot is left as mpc_container_job_begin expects it
+mpc_status records_container(mpc_context* c, const Tuning& tuning, hipStream_t s, const uint16_t* d_counts, const mpc_basis_choice* d_choices,
+                             long long tiles, int width, int height, const double* quant, unsigned every, ContainerMade* out);
+
+// ---- rate control on the device (mpcodec_budget.cpp): the depth profile of records against the tight frame they came from ----
+mpc_status profile_on_device(mpc_context* c, const uint16_t* d_counts, const mpc_basis_choice* d_choices, const double* quant,
+                             const uint8_t* d_rgb, int width, int height, uint32_t* d_profile, int* d_error, hipStream_t s);
 
 #pragma GCC visibility pop

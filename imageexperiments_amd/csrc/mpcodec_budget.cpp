@@ -30,28 +30,6 @@ mpc_status header_quant_device(mpc_context* c, const double* quant, hipStream_t 
     return call_quant(c, carried.data(), s, d_q);
 }
 
-mpc_status profile_on_device(mpc_context* c, const uint16_t* d_counts, const mpc_basis_choice* d_choices, const double* quant,
-                             const uint8_t* d_rgb, int width, int height, uint32_t* d_profile, int* d_error, hipStream_t s) {
-    const double* d_q = nullptr;
-    if (const mpc_status qs = header_quant_device(c, quant, s, &d_q); qs != MPC_OK) return qs;
-    mpc::ProfileParams p{};
-    p.counts = d_counts;
-    p.choices = reinterpret_cast<const uint32_t*>(d_choices);
-    p.quant = d_q;
-    p.K = c->K;
-    p.width = width;
-    p.height = height;
-    p.tiles_x = (width + 7) / 8;
-    p.tiles_y = (height + 7) / 8;
-    p.original = d_rgb;
-    p.profile = d_profile;
-    p.error = d_error;
-    p.fast = c->fast ? 1 : 0;
-    const int err = mpc::launch_depth_profile(dict_device(c), p, s);
-    if (err != 0) return launch_failed(err);
-    return MPC_OK;
-}
-
 // d_totals zeroed on `s`, then the kernel
 mpc_status allocate_on_device(const mpc_context* c, const uint32_t* d_profile, const uint16_t* d_counts, long long tiles, const uint32_t* weights,
                               int j, uint8_t* d_depth, uint16_t* d_out_counts, unsigned long long* d_totals, hipStream_t s) {
@@ -68,81 +46,6 @@ mpc_status allocate_on_device(const mpc_context* c, const uint32_t* d_profile, c
     std::memcpy(p.weights, weights, sizeof(uint32_t) * 3 * static_cast<size_t>(c->K));
     const int err = mpc::launch_budget_allocate(p, s);
     if (err != 0) return launch_failed(err);
-    return MPC_OK;
-}
-
-// a container and its seek index in malloc'ed memory, released unless taken
-struct Made {
-    uint8_t* bytes = nullptr;
-    size_t nbytes = 0;
-    std::vector<uint8_t> index;
-    Made() = default;
-    Made(const Made&) = delete;
-    Made& operator=(const Made&) = delete;
-    ~Made() { std::free(bytes); }
-    void swap(Made& o) {
-        std::swap(bytes, o.bytes);
-        std::swap(nbytes, o.nbytes);
-        index.swap(o.index);
-    }
-};
-
-// One records-to-container job on job slot 0 with everything on `s`, as mpc_delta_encode finishes: the container of `d_counts` /
-// `d_choices`, and with `every` != 0 its version-2 seek index from the entropy stage.  The call waits for the container.
-mpc_status container_of(mpc_context* c, const Tuning& tuning, hipStream_t s, const uint16_t* d_counts, const mpc_basis_choice* d_choices,
-                        long long tiles, int width, int height, const double* quant, unsigned every, Made* out) {
-    const int K = c->K;
-    if (!c->jobs[0]) c->jobs[0] = std::make_unique<JobSlot>();
-    JobSlot& js = *c->jobs[0];
-    ContainerJob& job = js.job;
-    if (!job.phase1) {
-        HIP_TRY(hipEventCreateWithFlags(&job.phase1, hipEventDisableTiming | hipEventBlockingSync));
-        HIP_TRY(hipEventCreateWithFlags(&job.done, hipEventDisableTiming | hipEventBlockingSync));
-    }
-    Carve measure;
-    mpc::StreamArgs measured{};
-    carve_stream_buffers(measure, tiles, K, true, &measured);
-    if (const mpc_status gs = js.dev.reserve(measure.at, "device staging"); gs != MPC_OK) return gs;
-    GrowBuffer host_stage(GrowBuffer::kPinned);                 // the host route's, should the frame take it: this job's own
-    job.side = job.down = s;
-    job.spin = true;
-    job.host_stage = &host_stage;
-    job.host_offset = 0;
-    job.index_interval = every;
-    job.index_expanded = every != 0;
-    struct Unhook {                                             // the slot is left as mpc_container_job_begin expects it
-        ContainerJob& job;
-        ~Unhook() {
-            job.host_stage = nullptr;
-            job.index_interval = 0;
-            job.index_expanded = false;
-            job.index.clear();
-        }
-    } unhook{job};
-    EntropyBuffers eb;
-    if (!tuning.host_entropy)
-        if (const mpc_status es = entropy_buffers(js.ent, static_cast<size_t>(tiles), K, &eb, every ? 2 : 0); es != MPC_OK) return es;
-    HIP_TRY(hipStreamSynchronize(nullptr));                     // a slot carved for another geometry clears its tables on the null stream
-    if (const mpc_status bs = container_begin(job, c, tuning.host_entropy ? nullptr : &eb, tuning.triple_limit, js.dev.data(), d_counts,
-                                              reinterpret_cast<const uint32_t*>(d_choices), nullptr, nullptr, width, height, quant);
-        bs != MPC_OK)
-        return bs;
-    if (const mpc_status ts = container_tables(job); ts != MPC_OK) return ts;
-    uint8_t* made = nullptr;
-    size_t made_bytes = 0;
-    if (const mpc_status cs = container_collect(job, &made, &made_bytes); cs != MPC_OK) return cs;
-    if (hipStreamSynchronize(s) != hipSuccess) {
-        std::free(made);
-        return fail(MPC_ERR_HIP, "the container job failed: %s", hipGetErrorString(hipGetLastError()));
-    }
-    if (every && job.index.empty()) {
-        std::free(made);
-        return fail(MPC_ERR_ALLOC, "no seek index");
-    }
-    std::free(out->bytes);
-    out->bytes = made;
-    out->nbytes = made_bytes;
-    out->index.assign(job.index.begin(), job.index.end());
     return MPC_OK;
 }
 
@@ -217,8 +120,8 @@ mpc_status encode_budget(mpc_context* c, const uint8_t* rgb, bool on_device, int
             return ds;
         // 2. the full container with its seek index
         const unsigned full_every = every ? every : mpc::kIndexIntervalDefault;
-        Made full;
-        if (const mpc_status fs = container_of(c, tuning, s, d_counts, d_choices, tiles, width, height, quant, full_every, &full); fs != MPC_OK) return fs;
+        ContainerMade full;
+        if (const mpc_status fs = records_container(c, tuning, s, d_counts, d_choices, tiles, width, height, quant, full_every, &full); fs != MPC_OK) return fs;
         unsigned long long full_sse = 0;
         HIP_TRY(hipMemcpyAsync(&full_sse, d_words + 3, sizeof(full_sse), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
@@ -231,7 +134,7 @@ mpc_status encode_budget(mpc_context* c, const uint8_t* rgb, bool on_device, int
         got.full_bytes = full.nbytes;
         got.full_sse = full_sse;
         got.full_records = full_records;
-        Made best;
+        ContainerMade best;
         int best_depth = -1;                                        // which of d_depth holds the returned container's map; -1: no cut
         if (full.nbytes <= budget) {
             // 3. it fits
@@ -255,8 +158,8 @@ mpc_status encode_budget(mpc_context* c, const uint8_t* rgb, bool on_device, int
             const auto probe = [&](int j, bool* fits) -> mpc_status {
                 if (const mpc_status as = allocate_on_device(c, d_profile, d_counts, tiles, weights, j, d_depth[spare], d_cut, d_words, s); as != MPC_OK)
                     return as;
-                Made made;
-                if (const mpc_status cs = container_of(c, tuning, s, d_cut, d_choices, tiles, width, height, quant, every, &made); cs != MPC_OK) return cs;
+                ContainerMade made;
+                if (const mpc_status cs = records_container(c, tuning, s, d_cut, d_choices, tiles, width, height, quant, every, &made); cs != MPC_OK) return cs;
                 ++got.probes;
                 probed_bytes = made.nbytes;
                 *fits = made.nbytes <= budget;
@@ -314,6 +217,28 @@ mpc_status encode_budget(mpc_context* c, const uint8_t* rgb, bool on_device, int
 }
 
 }  // namespace
+
+mpc_status profile_on_device(mpc_context* c, const uint16_t* d_counts, const mpc_basis_choice* d_choices, const double* quant,
+                             const uint8_t* d_rgb, int width, int height, uint32_t* d_profile, int* d_error, hipStream_t s) {
+    const double* d_q = nullptr;
+    if (const mpc_status qs = header_quant_device(c, quant, s, &d_q); qs != MPC_OK) return qs;
+    mpc::ProfileParams p{};
+    p.counts = d_counts;
+    p.choices = reinterpret_cast<const uint32_t*>(d_choices);
+    p.quant = d_q;
+    p.K = c->K;
+    p.width = width;
+    p.height = height;
+    p.tiles_x = (width + 7) / 8;
+    p.tiles_y = (height + 7) / 8;
+    p.original = d_rgb;
+    p.profile = d_profile;
+    p.error = d_error;
+    p.fast = c->fast ? 1 : 0;
+    const int err = mpc::launch_depth_profile(dict_device(c), p, s);
+    if (err != 0) return launch_failed(err);
+    return MPC_OK;
+}
 
 extern "C" {
 

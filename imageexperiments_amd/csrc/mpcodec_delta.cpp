@@ -8,43 +8,11 @@
 
 #include "host_delta.h"
 #include "host_patch.h"
-#include "mpc_internal.h"
-
-struct mpc_delta {
-    mpc_context* ctx = nullptr;
-    int width = 0, height = 0, tiles_y = 0;
-    long long tiles = 0;
-    // grow-only, all of it: `store` is sized once (the geometry is the session's), the other two by the largest call so far
-    GrowBuffer store{GrowBuffer::kDevice};      // kept frame | counts | records | list | count, error word | the diff's scratch
-    GrowBuffer upload{GrowBuffer::kDevice};     // a host frame's tight copy
-    GrowBuffer pack{GrowBuffer::kDevice};       // packed frame | its counts | its records
-    hipStream_t stream = nullptr;
-    uint8_t* d_kept = nullptr;
-    uint16_t* d_counts = nullptr;
-    mpc_basis_choice* d_choices = nullptr;
-    int32_t* d_list = nullptr;
-    int32_t* d_count = nullptr;                 // [2]: the diff's count, the scatter's error word
-    void* d_scratch = nullptr;
-    // the last successful call: what the records in `store` were pursued with
-    bool valid = false, fast = false;
-    std::vector<double> quant;
-    bool changed_all = false;                   // the last call's list is every tile
-    std::vector<int32_t> changed;               // else this
-    mpc_delta_info info{};
-    uint32_t calls = 0;                         // successful calls of either kind so far: the next patch's sequence
-    ~mpc_delta() {
-        if (stream) {
-            (void)hipStreamSynchronize(stream);
-            (void)hipStreamDestroy(stream);
-        }
-    }
-};
+#include "mpc_delta_session.h"
 
 static_assert(mpc::kDeltaPackRows == MPC_DELTA_PACK_ROWS, "one value for the packed frame's tile rows");
 
-namespace {
-mpc_status no_device() { return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback"); }
-}  // namespace
+mpc_status delta_no_device() { return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback"); }
 
 extern "C" {
 
@@ -78,7 +46,7 @@ mpc_status mpc_tile_diff_device(mpc_context* c, uint8_t* d_kept, const uint8_t* 
                                 int32_t* d_list, int32_t* d_count, void* stream) {
     return guarded([&]() -> mpc_status {
         if (!c || !d_kept || !d_rgb || !d_list || !d_count) return fail(MPC_ERR_ARGUMENT, "null argument");
-        if (c->device < 0) return no_device();
+        if (c->device < 0) return delta_no_device();
         if (width < 1 || height < 1) return fail(MPC_ERR_ARGUMENT, "bad geometry");
         const size_t row = 3 * static_cast<size_t>(width), stride = row_stride ? row_stride : row;
         if (stride < row) return fail(MPC_ERR_ARGUMENT, "row_stride %zu for %d pixels", row_stride, width);
@@ -97,7 +65,7 @@ mpc_status mpc_pack_tiles_device(mpc_context* c, const uint8_t* d_rgb, int width
                                  int rows, uint8_t* d_packed, size_t packed_stride, void* stream) {
     return guarded([&]() -> mpc_status {
         if (!c || !d_rgb || !d_list || !d_packed) return fail(MPC_ERR_ARGUMENT, "null argument");
-        if (c->device < 0) return no_device();
+        if (c->device < 0) return delta_no_device();
         if (width < 1 || height < 1 || n < 1 || rows < 1) return fail(MPC_ERR_ARGUMENT, "bad geometry");
         const size_t row = 3 * static_cast<size_t>(width), stride = row_stride ? row_stride : row;
         if (stride < row) return fail(MPC_ERR_ARGUMENT, "row_stride %zu for %d pixels", row_stride, width);
@@ -116,7 +84,7 @@ mpc_status mpc_unpack_tiles_device(mpc_context* c, const uint8_t* d_packed, size
                                    uint8_t* d_rgb, int width, int height, size_t row_stride, void* stream) {
     return guarded([&]() -> mpc_status {
         if (!c || !d_packed || !d_list || !d_rgb) return fail(MPC_ERR_ARGUMENT, "null argument");
-        if (c->device < 0) return no_device();
+        if (c->device < 0) return delta_no_device();
         if (width < 1 || height < 1 || n < 1 || rows < 1) return fail(MPC_ERR_ARGUMENT, "bad geometry");
         const size_t row = 3 * static_cast<size_t>(width), stride = row_stride ? row_stride : row;
         if (stride < row) return fail(MPC_ERR_ARGUMENT, "row_stride %zu for %d pixels", row_stride, width);
@@ -137,7 +105,7 @@ mpc_status mpc_scatter_records_device(mpc_context* c, const uint16_t* d_packed_c
                                       const int32_t* d_list, int n, uint16_t* d_counts, mpc_basis_choice* d_choices, int tiles, void* stream) {
     return guarded([&]() -> mpc_status {
         if (!c || !d_packed_counts || !d_packed_choices || !d_list || !d_counts || !d_choices) return fail(MPC_ERR_ARGUMENT, "null argument");
-        if (c->device < 0) return no_device();
+        if (c->device < 0) return delta_no_device();
         if (n < 1 || tiles < 1) return fail(MPC_ERR_ARGUMENT, "n %d, tiles %d", n, tiles);
         HIP_TRY(hipSetDevice(c->device));
         if (const mpc_status fs = crop_flag(c); fs != MPC_OK) return fs;
@@ -153,7 +121,7 @@ mpc_status mpc_delta_create(mpc_context* c, int width, int height, mpc_delta** o
         if (!c || !out) return fail(MPC_ERR_ARGUMENT, "null argument");
         *out = nullptr;
         if (width < 1 || height < 1) return fail(MPC_ERR_ARGUMENT, "bad geometry");
-        if (c->device < 0) return no_device();
+        if (c->device < 0) return delta_no_device();
         const long long tiles_y = (static_cast<long long>(height) + 7) / 8, tiles = ((static_cast<long long>(width) + 7) / 8) * tiles_y;
         if (tiles >= (1LL << 31) / (3 * MPC_MAX_K)) return fail(MPC_ERR_ARGUMENT, "bad geometry");
         std::lock_guard<std::recursive_mutex> one_host_call(c->host_calls);
@@ -202,20 +170,7 @@ mpc_status mpc_delta_changed(const mpc_delta* d, int32_t* tiles, int capacity, i
 }  // extern "C"
 
 // ---- a call in stages: mpc_delta_encode and mpc_delta_encode_patch share the first three, so the session's store advances
-// identically whichever is called, and differ in what the container job of the fourth is run on ----
-namespace {
-
-struct DeltaCall {                              // what the stages of one call hand on
-    const double* quant = nullptr;              // the caller's table, NULL = the context's
-    unsigned flags = 0;
-    bool key = false, through_pack = false;
-    const uint8_t* frame = nullptr;             // the frame on the device and its stride
-    size_t stride = 0;
-    long long n = 0;                            // tiles listed
-    mpc::PackGeometry g{0, 0, 0, 0};            // through_pack && n > 0: the packed frame's geometry, its records in d->pack
-    uint16_t* d_packed_counts = nullptr;
-    mpc_basis_choice* d_packed_choices = nullptr;
-};
+// identically whichever is called, and differ in what the container job of the fourth is run on (mpc_delta_session.h: the driver) ----
 
 // 1. the frame on the device
 mpc_status delta_frame(mpc_delta* d, const uint8_t* rgb, size_t row_stride, hipStream_t s, DeltaCall& call) {
@@ -297,11 +252,9 @@ mpc_status delta_pursue(mpc_delta* d, hipStream_t s, DeltaCall& call) {
 }
 
 // 7. records -> container on job slot 0, as a compose finishes, with the seek index from the entropy stage where one is asked for
-// (`every` != 0).  The records and the geometry are the caller's: the store's of the whole frame, or the packed frame's
-mpc_status delta_container(mpc_delta* d, hipStream_t s, const Tuning& tuning, const uint16_t* d_counts, const mpc_basis_choice* d_choices,
-                           long long tiles, int width, int height, const double* quant, unsigned every, uint8_t** bytes, size_t* nbytes,
-                           uint8_t** index, size_t* index_bytes) {
-    mpc_context* c = d->ctx;
+// (`every` != 0).  The records and the geometry are the caller's: the store's of the whole frame, or a packed frame's
+mpc_status records_container(mpc_context* c, const Tuning& tuning, hipStream_t s, const uint16_t* d_counts, const mpc_basis_choice* d_choices,
+                             long long tiles, int width, int height, const double* quant, unsigned every, ContainerMade* out) {
     const int K = c->K;
     if (!c->jobs[0]) c->jobs[0] = std::make_unique<JobSlot>();
     JobSlot& js = *c->jobs[0];
@@ -314,7 +267,7 @@ mpc_status delta_container(mpc_delta* d, hipStream_t s, const Tuning& tuning, co
     mpc::StreamArgs measured{};
     carve_stream_buffers(measure, tiles, K, true, &measured);
     if (const mpc_status gs = js.dev.reserve(measure.at, "device staging"); gs != MPC_OK) return gs;
-    GrowBuffer host_stage(GrowBuffer::kPinned);                 // the host route's, should the frame take it: this call's own
+    GrowBuffer host_stage(GrowBuffer::kPinned);                 // the host route's, should the frame take it: this job's own
     job.side = job.down = s;
     job.spin = true;
     job.host_stage = &host_stage;
@@ -346,79 +299,16 @@ mpc_status delta_container(mpc_delta* d, hipStream_t s, const Tuning& tuning, co
         std::free(made);
         return fail(MPC_ERR_HIP, "the container job failed: %s", hipGetErrorString(hipGetLastError()));
     }
-    if (every) {
-        uint8_t* copy = job.index.empty() ? nullptr : static_cast<uint8_t*>(std::malloc(job.index.size()));
-        if (!copy) {
-            std::free(made);
-            return fail(MPC_ERR_ALLOC, "no seek index");
-        }
-        std::memcpy(copy, job.index.data(), job.index.size());
-        *index = copy;
-        *index_bytes = job.index.size();
+    if (every && job.index.empty()) {
+        std::free(made);
+        return fail(MPC_ERR_ALLOC, "no seek index");
     }
-    *bytes = made;
-    *nbytes = made_bytes;
+    std::free(out->bytes);
+    out->bytes = made;
+    out->nbytes = made_bytes;
+    out->index.assign(job.index.begin(), job.index.end());
     return MPC_OK;
 }
-
-// One call of either kind.  The caller has checked its own pointers; here the refusals both share, then -- behind `clear`, which empties
-// the caller's outputs -- the three shared stages, `finish` (the fourth stage and the caller's result), and the session's new state
-template <class Clear, class Finish>
-mpc_status delta_call(mpc_delta* d, const uint8_t* rgb, size_t row_stride, const double* quant, unsigned flags, mpc_delta_info* info, Clear&& clear,
-                      Finish&& finish) {
-    if (flags & ~(MPC_DELTA_KEY | MPC_DELTA_DEVICE_PIXELS | MPC_DELTA_PACK_ALWAYS)) return fail(MPC_ERR_ARGUMENT, "flags 0x%x", flags);
-    mpc_context* c = d->ctx;
-    const int K = c->K;
-    const size_t row = 3 * static_cast<size_t>(d->width);
-    if (row_stride != 0 && row_stride < row) return fail(MPC_ERR_ARGUMENT, "row_stride %zu for %d pixels", row_stride, d->width);
-    if (c->device < 0) return no_device();
-    std::lock_guard<std::recursive_mutex> one_host_call(c->host_calls);
-    for (int k = 0; k < mpc_context::kSeqSlots; ++k)
-        if (c->jobs[k] && c->jobs[k]->stage != 0) return fail(MPC_ERR_ARGUMENT, "container job slot %d is busy", k);
-    // behind the checks: whatever fails from here on leaves a session whose next call is a key frame
-    clear();
-    struct Session {
-        mpc_delta* d;
-        bool keep = false;
-        ~Session() {
-            if (keep) return;
-            d->valid = false;
-            d->changed_all = false;
-            d->changed.clear();
-            d->info = mpc_delta_info{};
-        }
-    } session{d};
-    HIP_TRY(hipSetDevice(c->device));
-    const Tuning tuning = read_tuning();
-    const double* table = quant ? quant : c->quant.data();
-    const size_t table_bytes = sizeof(double) * 3 * static_cast<size_t>(K);
-    DeltaCall call;
-    call.quant = quant;
-    call.flags = flags;
-    call.key = !d->valid || (flags & MPC_DELTA_KEY) || d->fast != c->fast || d->quant.size() != 3 * static_cast<size_t>(K) ||
-               std::memcmp(d->quant.data(), table, table_bytes) != 0;
-    call.through_pack = !call.key || (flags & MPC_DELTA_PACK_ALWAYS);
-    hipStream_t s = d->stream;
-    struct Drain {                                              // whatever happens, nothing of this call is left running
-        hipStream_t s;
-        ~Drain() { (void)hipStreamSynchronize(s); }
-    } drain{s};
-    if (const mpc_status st = delta_frame(d, rgb, row_stride, s, call); st != MPC_OK) return st;
-    if (const mpc_status st = delta_list(d, s, call); st != MPC_OK) return st;
-    if (const mpc_status st = delta_pursue(d, s, call); st != MPC_OK) return st;
-    if (const mpc_status st = finish(call, s, tuning); st != MPC_OK) return st;
-    d->valid = true;
-    d->fast = c->fast;
-    d->quant.assign(table, table + 3 * static_cast<size_t>(K));
-    d->changed_all = call.key;
-    d->info = mpc_delta_info{static_cast<int>(d->tiles), static_cast<int>(call.n), call.key ? 1 : 0};
-    ++d->calls;
-    *info = d->info;
-    session.keep = true;
-    return MPC_OK;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -431,16 +321,30 @@ mpc_status mpc_delta_encode(mpc_delta* d, const uint8_t* rgb, size_t row_stride,
             return fail(MPC_ERR_ARGUMENT, "interval %d: 0 or %u to %u", index_interval, mpc::kIndexIntervalMin, mpc::kIndexIntervalMax);
         const unsigned every = index_interval < 0 ? 0u : index_interval ? static_cast<unsigned>(index_interval) : mpc::kIndexIntervalDefault;
         return delta_call(
-            d, rgb, row_stride, quant, flags, info,
+            d, rgb, row_stride, quant, flags, false, info,
             [&] {
                 *bytes = nullptr;
                 *nbytes = 0;
                 if (index) *index = nullptr;
                 if (index_bytes) *index_bytes = 0;
+                d->sent_valid = false;                              // no budget call: what a receiver holds is no longer tracked
             },
-            [&](const DeltaCall&, hipStream_t s, const Tuning& tuning) {
-                return delta_container(d, s, tuning, d->d_counts, d->d_choices, d->tiles, d->width, d->height, quant, every, bytes, nbytes, index,
-                                       index_bytes);
+            [&](const DeltaCall&, hipStream_t s, const Tuning& tuning) -> mpc_status {
+                ContainerMade made;
+                if (const mpc_status cs = records_container(d->ctx, tuning, s, d->d_counts, d->d_choices, d->tiles, d->width, d->height, quant, every, &made);
+                    cs != MPC_OK)
+                    return cs;
+                if (every) {
+                    uint8_t* copy = static_cast<uint8_t*>(std::malloc(made.index.size()));
+                    if (!copy) return fail(MPC_ERR_ALLOC, "no seek index");
+                    std::memcpy(copy, made.index.data(), made.index.size());
+                    *index = copy;
+                    *index_bytes = made.index.size();
+                }
+                *bytes = made.bytes;
+                *nbytes = made.nbytes;
+                made.bytes = nullptr;
+                return MPC_OK;
             });
     });
 }
@@ -451,35 +355,30 @@ mpc_status mpc_delta_encode_patch(mpc_delta* d, const uint8_t* rgb, size_t row_s
         if (!d || !rgb || !patch || !patch_bytes || !info) return fail(MPC_ERR_ARGUMENT, "null argument");
         bool key_patch = false;
         const mpc_status st = delta_call(
-            d, rgb, row_stride, quant, flags, info,
+            d, rgb, row_stride, quant, flags, false, info,
             [&] {
                 *patch = nullptr;
                 *patch_bytes = 0;
+                d->sent_valid = false;                              // no budget call: what a receiver holds is no longer tracked
             },
             [&](const DeltaCall& call, hipStream_t s, const Tuning& tuning) -> mpc_status {
                 key_patch = call.key || call.n == d->tiles;
-                uint8_t* made = nullptr;
-                size_t made_bytes = 0;
+                ContainerMade made;
                 if (key_patch) {                                    // the whole frame's container from the store
-                    if (const mpc_status cs = delta_container(d, s, tuning, d->d_counts, d->d_choices, d->tiles, d->width, d->height, quant, 0, &made,
-                                                              &made_bytes, nullptr, nullptr);
+                    if (const mpc_status cs = records_container(d->ctx, tuning, s, d->d_counts, d->d_choices, d->tiles, d->width, d->height, quant, 0, &made);
                         cs != MPC_OK)
                         return cs;
                 } else if (call.n > 0) {                            // the packed frame's, from its own counts and records
-                    if (const mpc_status cs = delta_container(d, s, tuning, call.d_packed_counts, call.d_packed_choices,
-                                                              static_cast<long long>(call.g.rows) * call.g.cols, 8 * call.g.cols, 8 * call.g.rows, quant,
-                                                              0, &made, &made_bytes, nullptr, nullptr);
+                    if (const mpc_status cs = records_container(d->ctx, tuning, s, call.d_packed_counts, call.d_packed_choices,
+                                                                static_cast<long long>(call.g.rows) * call.g.cols, 8 * call.g.cols, 8 * call.g.rows, quant,
+                                                                0, &made);
                         cs != MPC_OK)
                         return cs;
                 }
-                struct Free {
-                    uint8_t* p;
-                    ~Free() { std::free(p); }
-                } made_guard{made};
-                const std::string why = mpc::patch_make_error(d->width, d->height, key_patch, d->changed.data(), call.n, made, made_bytes);
+                const std::string why = mpc::patch_make_error(d->width, d->height, key_patch, d->changed.data(), call.n, made.bytes, made.nbytes);
                 if (!why.empty()) return fail(MPC_ERR_HIP, "the patch: %s", why.c_str());
                 const std::vector<uint8_t> blob =
-                    mpc::patch_make(d->width, d->height, d->calls, key_patch, d->changed.data(), call.n, made, made_bytes);
+                    mpc::patch_make(d->width, d->height, d->calls, key_patch, d->changed.data(), call.n, made.bytes, made.nbytes);
                 uint8_t* out = static_cast<uint8_t*>(std::malloc(blob.size()));
                 if (!out) return fail(MPC_ERR_ALLOC, "no patch");
                 std::memcpy(out, blob.data(), blob.size());

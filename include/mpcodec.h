@@ -1093,6 +1093,103 @@ mpc_status mpc_encode_image_budget_device(mpc_context* ctx, const uint8_t* d_rgb
                                           int index_interval, uint8_t** bytes, size_t* nbytes, uint8_t** index, size_t* index_bytes,
                                           uint8_t* depth, mpc_budget_info* info);
 
+/* ---- rate: a delta stream to a byte budget ("Delta stream to a byte budget") ----
+ * A patch is as large as the scene makes it; a link has a byte rate.  A sender that cuts patches to a budget must know what the
+ * receiver holds of each tile, and may refine a thin tile later.  These are the pieces of that sender: the state (a depth per tile),
+ * which tiles a call may send, the allocation when a tile has a floor, and the gather that makes a packed frame's records from the
+ * whole frame's.  8 x 8 tiles, T tiles a frame, K the context's, tile t = tx * tiles_y + ty as everywhere.  Host and device agree bit
+ * for bit on everything defined here.
+ *
+ * SENT DEPTH  sent[t], u8, 0 ... K: the receiver's tile t is the decode of tile t's records with every count cut to min(count, sent[t]).
+ * full(t) = max over ch of min(counts[t * 3 + ch], K).  Tile t is OWED iff sent[t] < full(t).
+ * CANDIDATES of a call: the changed tiles plus the owed tiles, ascending.  A changed tile MUST be sent, its floor is 0.  An owed,
+ * unchanged tile MAY be sent, its floor is sent[t]; not sending it costs no bytes and leaves it as it is.  Sending always sends a tile's
+ * records from step 0.
+ * ALLOCATION WITH A FLOOR at multiplier j, per candidate i with profile P[i][0 ... K], three counts, floor[i] (above K: used as K) and
+ * must[i]; W, L[j] and R[i][n] as in the budget section.  Allowed depths: every n in 0 ... K when must[i], else floor[i] and every n above
+ * it.  R'(i, n) = R[i][n], except R'(i, floor[i]) = 0 for a candidate with must[i] == 0.  J = 65536 * P[i][n] + L[j] * R'(i, n) in u64;
+ * depth[i] = the smallest allowed n that minimises J; send[i] = must[i] || depth[i] > floor[i]; out_counts = min(count, depth[i]);
+ * totals[0] = sum of P at the chosen depths, [1] = sum of R', [2] = the records kept in the candidates that are sent, [3] = the
+ * candidates sent.  With every candidate must and every floor 0 it is mpc_budget_allocate bit for bit (depth, out_counts, totals[0 ... 2]).
+ *
+ * Host only, no context, safe on several threads; they define what the kernels compute:
+ *   mpc_owed_tiles             sent[tiles], counts[3 * tiles], changed[n_changed] (ascending, distinct, inside the frame) -> candidates
+ *                              (room for `tiles`), *n their number, and PER TILE must[t] = 1 iff t is changed, floor[t] = 0 for a
+ *                              changed tile, else sent[t].  candidates, floor, must: each NULL or room for `tiles`.
+ *   mpc_budget_allocate_floor  floor, must: NULL = all 0, all 1.  depth[n], out_counts[3 * n], send[n]: each NULL or room; totals[4].
+ * MPC_ERR_ARGUMENT: a null pointer, tiles or n < 0, K outside 1 ... 32, j outside 0 ... 255, a changed list that breaks its rules.
+ *
+ * On the caller's buffers, asynchronous on `stream`; MPC_ERR_ARGUMENT with nothing enqueued for a null pointer (unless named optional)
+ * or a size below 1, MPC_ERR_NO_DEVICE for a host-only context:
+ *   mpc_owed_tiles_device      d_flags[tiles] (u8) holds, on entry, != 0 for a changed tile (the diff's flag array); the kernel ORs "owed"
+ *                              into it (bit 1), writes d_floor[tiles] and d_must[tiles] as mpc_owed_tiles defines them, and the
+ *                              flags -> list kernels of mpc_tile_diff_device make d_list[tiles] / *d_count (int32): the candidates in
+ *                              the tiles' own order, whatever the schedule.  A count above K is used as K.  The per-block counts live
+ *                              in the context's diff scratch: mpc_tile_diff_device's rule for streams.
+ *   mpc_gather_records_device  mpc_scatter_records_device turned round, with a cut.  Whole-frame records of `tiles` tiles, a list
+ *                              d_list[m], optionally d_idx[n] (entries in [0, m); NULL: the identity, n <= m) and d_depth[m] (NULL:
+ *                              uncut) -> the records of the packed frame mpc_delta_pack_geometry(n, rows) describes: packed tile j < n
+ *                              takes, with c = idx[j], the records of tile d_list[c] with the counts min(count, K, d_depth[c]); every
+ *                              entry at or above that count is written as 0; every padding tile (n <= j < R * C) has counts 0 and
+ *                              entries 0.  d_packed_counts[3 * R * C], d_packed_choices[3 * R * C * K]: any alignment; 16-byte pieces
+ *                              where K is a multiple of 4 and both record bases are 16-byte aligned, word by word otherwise.  An
+ *                              entry of d_idx outside [0, m) or of d_list outside [0, tiles) makes its packed tile all 0 and sets the
+ *                              context's crop error word (mpc_crop_records_check reads and clears it); no address comes from it.
+ *   mpc_budget_allocate_floor_device  the allocation of n candidates with weights[3K] in HOST memory; d_floor, d_must: each optional as
+ *                              on the host; d_depth[n], d_send[n] (u8), d_out_counts[3 * n], d_totals[4] (u64; zeroed on `stream` first). */
+mpc_status mpc_owed_tiles(const uint8_t* sent, const uint16_t* counts, long long tiles, int K, const int32_t* changed, int n_changed,
+                          int32_t* candidates, uint8_t* floor, uint8_t* must, int* n);
+mpc_status mpc_budget_allocate_floor(const uint32_t* profile, const uint16_t* counts, const uint8_t* floor, const uint8_t* must, long long n,
+                                     int K, const uint32_t* weights, int j, uint8_t* depth, uint16_t* out_counts, uint8_t* send,
+                                     uint64_t* totals /* [4] */);
+mpc_status mpc_owed_tiles_device(mpc_context* ctx, const uint8_t* d_sent, const uint16_t* d_counts, long long tiles, uint8_t* d_flags,
+                                 uint8_t* d_floor, uint8_t* d_must, int32_t* d_list, int32_t* d_count, void* stream);
+mpc_status mpc_gather_records_device(mpc_context* ctx, const uint16_t* d_counts, const mpc_basis_choice* d_choices, int tiles,
+                                     const int32_t* d_list, int m, const int32_t* d_idx, const uint8_t* d_depth, int n, int rows,
+                                     uint16_t* d_packed_counts, mpc_basis_choice* d_packed_choices, void* stream);
+mpc_status mpc_budget_allocate_floor_device(mpc_context* ctx, const uint32_t* d_profile, const uint16_t* d_counts, const uint8_t* d_floor,
+                                            const uint8_t* d_must, long long n, const uint32_t* weights, int j, uint8_t* d_depth,
+                                            uint16_t* d_out_counts, uint8_t* d_send, unsigned long long* d_totals, void* stream);
+
+/* THE SESSION.  A delta session (mpc_delta_create) gets the map sent[t].  THE INVARIANT: after every successful budget call, a receiver
+ * session that has applied every patch so far holds exactly -- byte for byte, in the context's flavour -- what mpc_decode_tiles_device
+ * makes of the current frame's full records (mpc_encode_tiles_device's, by the delta encoder's contract) with every count cut to
+ * min(count, sent[t]).  A sender-only feature: patches stay format version 1, mpc_patch_apply and every decoder read them unchanged.
+ *
+ * mpc_delta_encode_patch_budget: a patch of at most `budget` bytes.  Synchronous.
+ *   1. mpc_delta_encode_patch's refusals, flags, key-frame rule and stages up to the records (frame, list, pursuit, scatter), and two
+ *      more: budget < 40 (an empty patch) is MPC_ERR_ARGUMENT with nothing enqueued, and a session whose sent map is not valid -- the
+ *      first budget call, a budget call after an unbudgeted call, after a failure behind the checks -- makes the call a key frame
+ *   2. key frame: every tile is a candidate and must.  Else the owed-flags kernel and the flags -> list kernels make the candidates
+ *   3. no candidates: the empty patch
+ *   4. the candidates' pixels from the kept frame (the pack kernel) and their records from the store (the gather kernel) are an
+ *      ordinary packed frame with its records; every tile a candidate: the frame and the store themselves.  F is its full container
+ *      with its seek index, on job slot 0; all_bytes the length of the patch that carries F.  all_bytes <= budget: that patch is
+ *      sent, sent = K for every candidate; on a session that owes nothing it is byte for byte mpc_delta_encode_patch's
+ *   5. else the weights from F's index and the depth profile of the packed frame, once.  probe(j): the floor allocation, `send`
+ *      compacted to a list, the records of the k candidates sent, cut to their depths, gathered into the packed frame of exactly
+ *      those (mpc_delta_pack_geometry(k, 64); k = T: the whole frame's geometry and a key patch), the container job, mpc_patch_make;
+ *      k = 0: the empty patch and no job.  size(j) is that patch's length
+ *   6. probe(255) first (every must tile at depth 0 and nothing else); larger than the budget: MPC_ERR_ARGUMENT with both figures in
+ *      the text, and the session is invalidated (the store has advanced): its next call is a key frame.  Then
+ *      mpc_encode_image_budget's bisection: lo = -1 infeasible, hi = 255 feasible, at most nine probes, hi's patch kept from its probe
+ *   7. commit: sent[t] = depth for every tile sent; the sequence advances as for mpc_delta_encode_patch
+ * A KEY budget call's container is byte for byte mpc_encode_image_budget_device(frame, budget - 40)'s, with its lambda_index and probes.
+ * info: tiles, changed, key (a key frame, or a patch sent as a key patch); candidates; sent_tiles; owed (after the call); lambda_index
+ * (-1: everything fitted); probes; all_bytes; sse (the sum of P over the candidates at the returned patch's depths).
+ * mpc_delta_encode and mpc_delta_encode_patch keep their behaviour; a successful check of theirs marks the sent map invalid (a flag,
+ * no launch), so the next budget call is a key frame.
+ * mpc_delta_sent: the map after the last successful budget call, with mpc_delta_changed's capacity rules (*n = tiles);
+ * MPC_ERR_ARGUMENT on a session without a valid map. */
+typedef struct mpc_rate_info {
+    int tiles, changed, key, candidates, sent_tiles, owed, lambda_index, probes;
+    size_t all_bytes;
+    unsigned long long sse;
+} mpc_rate_info;
+mpc_status mpc_delta_encode_patch_budget(mpc_delta* d, const uint8_t* rgb, size_t row_stride, const double* quant, unsigned flags,
+                                         size_t budget, uint8_t** patch, size_t* patch_bytes, mpc_rate_info* info);
+mpc_status mpc_delta_sent(const mpc_delta* d, uint8_t* depth, int capacity, int* n);
+
 /* ---- "-s" patch statistics, Compression.cpp:200-302 ----
  * The reference seeds one std::mt19937, and for every image draws `patches` origins x = rand() % (width - bs),
  * y = rand() % (height - bs), runs CalcMPDynamic on the Y, U and V patch with every quantiser 1.0 and feeds
