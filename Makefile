@@ -29,6 +29,9 @@
 #   make asan-patch  tests/cpp/asan_patch: the delta stream's patch format -- its one writer and its one parser -- on exact-size buffers:
 #                    the hostile corpus of tests/patch_cases.py and every single-bit flip of valid patches' headers and lists (what
 #                    tests/test_asan_patch.py runs)
+#   make asan-patch-index  tests/cpp/asan_patch_index: patch format version 2 -- writer, parser, add and strip of the index section -- on
+#                    exact-size buffers: valid and hostile blobs, every single-bit flip of a version-2 header, and the index section read
+#                    by the host's index reader at each of the 8 byte alignments (what tests/test_asan_patch_index.py runs)
 #
 # GPU AddressSanitizer is not available on the test pool; the kernels are covered by the parity suite instead.
 SAN = -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer
@@ -112,6 +115,12 @@ tests/cpp/asan_patch_bin: tests/cpp/asan_patch.cpp $(wildcard imageexperiments_a
 asan-patch: tests/cpp/asan_patch_bin
 	ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=print_stacktrace=1 MPC_HOST_THREADS=4 ./tests/cpp/asan_patch_bin
 
+tests/cpp/asan_patch_index_bin: tests/cpp/asan_patch_index.cpp $(wildcard imageexperiments_amd/csrc/host_*.cpp imageexperiments_amd/csrc/host_*.h)
+	g++ -std=c++17 -O1 -g $(SAN) -ffp-contract=off -pthread -Wall -Wno-unused-function tests/cpp/asan_patch_index.cpp -o $@
+
+asan-patch-index: tests/cpp/asan_patch_index_bin
+	ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=print_stacktrace=1 MPC_HOST_THREADS=4 ./tests/cpp/asan_patch_index_bin
+
 oracle/_build/liboracle_asan.so: $(wildcard oracle/*.c oracle/*.h)
 	mkdir -p oracle/_build
 	gcc -std=c11 -O1 -g $(SAN) -ffp-contract=off -fPIC -shared -o $@ oracle/mpo_*.c -lm
@@ -120,6 +129,6 @@ asan-oracle: oracle/_build/liboracle_asan.so
 	LD_PRELOAD=$$(gcc -print-file-name=libasan.so) ASAN_OPTIONS=detect_leaks=0 ORACLE_LIB=$(CURDIR)/oracle/_build/liboracle_asan.so \
 	    python -m pytest tests/test_oracle_golden.py -x -q -p no:cacheprovider
 
-asan: asan-host asan-index asan-encode-index asan-encode-index2 asan-region asan-index2 asan-view asan-transcode asan-compose asan-index-scan asan-delta asan-budget asan-patch asan-oracle
+asan: asan-host asan-index asan-encode-index asan-encode-index2 asan-region asan-index2 asan-view asan-transcode asan-compose asan-index-scan asan-delta asan-budget asan-patch asan-patch-index asan-oracle
 
-.PHONY: asan asan-host asan-index asan-encode-index asan-encode-index2 asan-region asan-index2 asan-view asan-transcode asan-compose asan-index-scan asan-delta asan-budget asan-patch asan-oracle
+.PHONY: asan asan-host asan-index asan-encode-index asan-encode-index2 asan-region asan-index2 asan-view asan-transcode asan-compose asan-index-scan asan-delta asan-budget asan-patch asan-patch-index asan-oracle

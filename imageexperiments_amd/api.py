@@ -321,6 +321,19 @@ def _bind_bitstream(L):
     except AttributeError:
         if not os.environ.get("MPCODEC_LIB"):             # an older build may be loaded for A/B timing only
             raise
+    try:
+        L.mpc_patch_index.argtypes = [_u8p, C.c_size_t, _szp_, _szp_]
+        L.mpc_patch_make_indexed.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_int, _i32p, C.c_int, _u8p, C.c_size_t, _u8p, C.c_size_t,
+                                             C.POINTER(_u8p), _szp_]
+        L.mpc_patch_add_index.argtypes = [_u8p, C.c_size_t, C.c_int, C.c_size_t, C.POINTER(_u8p), _szp_]
+        L.mpc_patch_strip_index.argtypes = [_u8p, C.c_size_t, C.POINTER(_u8p), _szp_]
+        L.mpc_delta_encode_patch_indexed.argtypes = [vp, vp, C.c_size_t, _dp, C.c_uint, C.c_int, C.c_size_t, C.POINTER(_u8p), _szp_,
+                                                     C.POINTER(MpcDeltaInfo)]
+        L.mpc_patch_last_route.argtypes = [vp]
+        L.mpc_patch_last_route.restype = C.c_int
+    except AttributeError:
+        if not os.environ.get("MPCODEC_LIB"):             # an older build may be loaded for A/B timing only
+            raise
     _u64p = C.POINTER(C.c_uint64)
     try:
         L.mpc_budget_lambda.argtypes = [C.c_int, _u64p]
@@ -804,6 +817,12 @@ def delta_pack_geometry(n, rows=MPC_DELTA_PACK_ROWS):
     return R.value, Cc.value, stride.value, nbytes.value
 
 
+# DeltaEncoder.encode_patch's default index_min_bytes: the smallest container from which applying the version-2 patch won in the median
+# at both measured frame sizes (profiles/patch_index.txt: 12134 bytes, 1 % of a 1920x1080 frame at K = 8; below it -- 8643 bytes at
+# 4928x3264, K = 32, 1482 bytes at 1920x1080 -- the two versions are within 0.03 ms of each other and either wins from run to run)
+PATCH_INDEX_MIN_BYTES = 12134
+
+
 class DeltaEncoder:
     """mpc_delta: a session that encodes frames of one size one after the other and pursues only the tiles whose pixels changed since
     the last call.  Every container is byte for byte CompressionContext.encode_image of that frame.  `info` = (tiles, changed, key)
@@ -862,29 +881,37 @@ class DeltaEncoder:
         _check(self.L.mpc_delta_changed(self.h, tiles.ctypes.data_as(_i32p), n.value, C.byref(n)))
         return tiles[:n.value]
 
-    def _encode_patch(self, ptr, row_stride, quant, flags):
+    def _encode_patch(self, ptr, row_stride, quant, flags, index_interval=None, index_min_bytes=0):
         qp = None
         if quant is not None:
             quant = np.ascontiguousarray(quant, np.float64).reshape(3, self.ctx.K)
             qp = quant.ctypes.data_as(_dp)
         out, n, info = _u8p(), C.c_size_t(0), MpcDeltaInfo()
-        _check(self.L.mpc_delta_encode_patch(self.h, ptr, int(row_stride), qp, int(flags), C.byref(out), C.byref(n), C.byref(info)))
+        if index_interval is None:
+            _check(self.L.mpc_delta_encode_patch(self.h, ptr, int(row_stride), qp, int(flags), C.byref(out), C.byref(n), C.byref(info)))
+        else:
+            _check(self.L.mpc_delta_encode_patch_indexed(self.h, ptr, int(row_stride), qp, int(flags), int(index_interval), int(index_min_bytes),
+                                                         C.byref(out), C.byref(n), C.byref(info)))
         self.info = (info.tiles, info.changed, info.key)
         return _take_bytes(self.L, out, n)
 
-    def encode_patch(self, rgb, quant=None, key=False, pack_always=False):
+    def encode_patch(self, rgb, quant=None, key=False, pack_always=False, index_interval=None, index_min_bytes=PATCH_INDEX_MIN_BYTES):
         """mpc_delta_encode_patch of a host frame -> the patch (bytes): the changed tiles' list and the container of their packed frame,
-        a key patch with the whole frame's container where every tile is listed, 40 bytes where none is."""
+        a key patch with the whole frame's container where every tile is listed, 40 bytes where none is.  With index_interval (0 = the
+        default interval) mpc_delta_encode_patch_indexed: patch_add_index(that patch, index_interval, index_min_bytes), a version-2 patch
+        whose container the receiver parses on the device.  index_min_bytes leaves patches with a smaller container at version 1: the
+        default is the measured size from which version 2 applies faster (PATCH_INDEX_MIN_BYTES); 0 indexes every patch that has a
+        container."""
         rgb = _pixel_rows(rgb)
         if rgb.shape[:2] != (self.height, self.width):
             raise ValueError("the frame is not the session's size")
         flags = (MPC_DELTA_KEY if key else 0) | (MPC_DELTA_PACK_ALWAYS if pack_always else 0)
-        return self._encode_patch(rgb.ctypes.data, rgb.strides[0], quant, flags)
+        return self._encode_patch(rgb.ctypes.data, rgb.strides[0], quant, flags, index_interval, index_min_bytes)
 
-    def encode_patch_device(self, d_rgb, row_stride=0, quant=None, key=False, pack_always=False):
+    def encode_patch_device(self, d_rgb, row_stride=0, quant=None, key=False, pack_always=False, index_interval=None, index_min_bytes=PATCH_INDEX_MIN_BYTES):
         """The same for a frame in device memory: d_rgb an int from tensor.data_ptr(), row_stride bytes between rows (0 = 3 * width)."""
         flags = MPC_DELTA_DEVICE_PIXELS | (MPC_DELTA_KEY if key else 0) | (MPC_DELTA_PACK_ALWAYS if pack_always else 0)
-        return self._encode_patch(int(d_rgb), row_stride, quant, flags)
+        return self._encode_patch(int(d_rgb), row_stride, quant, flags, index_interval, index_min_bytes)
 
 
     def _encode_patch_budget(self, ptr, row_stride, budget, quant, flags):
@@ -931,16 +958,56 @@ class RateInfo:
         return "RateInfo(" + ", ".join(f"{f}={getattr(self, f)}" for f in self.__slots__) + ")"
 
 
-def patch_make(width, height, sequence, tiles, container, key=False):
+def patch_make(width, height, sequence, tiles, container, key=False, index=None):
     """mpc_patch_make: the only writer of a patch -> bytes.  key: `tiles` is not read (None will do) and the container is the whole
-    frame's; else `tiles` ascending with the container of their packed frame, or empty with container None or b""."""
+    frame's; else `tiles` ascending with the container of their packed frame, or empty with container None or b"".  index (bytes, not
+    empty): mpc_patch_make_indexed, a version-2 patch with those bytes as its index section."""
     L = load_library()
     buf = np.frombuffer(container if container is not None else b"", np.uint8)
     listed = np.ascontiguousarray([] if tiles is None else tiles, np.int32)
     n = -(-int(width) // 8) * -(-int(height) // 8) if key else listed.size
     out, nbytes = _u8p(), C.c_size_t(0)
-    _check(L.mpc_patch_make(int(width), int(height), int(sequence), int(bool(key)), listed.ctypes.data_as(_i32p) if listed.size else None, n,
-                            buf.ctypes.data_as(_u8p) if buf.size else None, buf.size, C.byref(out), C.byref(nbytes)))
+    if index is None:
+        _check(L.mpc_patch_make(int(width), int(height), int(sequence), int(bool(key)), listed.ctypes.data_as(_i32p) if listed.size else None, n,
+                                buf.ctypes.data_as(_u8p) if buf.size else None, buf.size, C.byref(out), C.byref(nbytes)))
+    else:
+        ix = np.frombuffer(index, np.uint8)
+        _check(L.mpc_patch_make_indexed(int(width), int(height), int(sequence), int(bool(key)), listed.ctypes.data_as(_i32p) if listed.size else None,
+                                        n, buf.ctypes.data_as(_u8p) if buf.size else None, buf.size, ix.ctypes.data_as(_u8p) if ix.size else None,
+                                        ix.size, C.byref(out), C.byref(nbytes)))
+    return _take_bytes(L, out, nbytes)
+
+
+def _patch_pointer(patch):
+    buf = np.frombuffer(patch, np.uint8)
+    return buf, (buf.ctypes.data_as(_u8p) if buf.size else C.cast(C.c_char_p(b"\0"), _u8p))
+
+
+def patch_index(patch):
+    """mpc_patch_index: validates as patch_info does -> (offset, size) of the patch's index section, (0, 0) for a version-1 patch"""
+    buf, p = _patch_pointer(patch)
+    at, n = C.c_size_t(0), C.c_size_t(0)
+    _check(load_library().mpc_patch_index(p, buf.size, C.byref(at), C.byref(n)))
+    return at.value, n.value
+
+
+def patch_add_index(patch, interval=0, index_min_bytes=0):
+    """mpc_patch_add_index: the patch with container_index(its container, interval) as its index section (version 2) where it has a
+    container of at least max(index_min_bytes, 1) bytes whose index is not "serial only"; else the version-1 patch.  An index the patch
+    carries already is dropped first."""
+    L = load_library()
+    buf, p = _patch_pointer(patch)
+    out, nbytes = _u8p(), C.c_size_t(0)
+    _check(L.mpc_patch_add_index(p, buf.size, int(interval), int(index_min_bytes), C.byref(out), C.byref(nbytes)))
+    return _take_bytes(L, out, nbytes)
+
+
+def patch_strip_index(patch):
+    """mpc_patch_strip_index: the version-1 patch, byte for byte"""
+    L = load_library()
+    buf, p = _patch_pointer(patch)
+    out, nbytes = _u8p(), C.c_size_t(0)
+    _check(L.mpc_patch_strip_index(p, buf.size, C.byref(out), C.byref(nbytes)))
     return _take_bytes(L, out, nbytes)
 
 
@@ -993,6 +1060,11 @@ class PatchDecoder:
         info = MpcPatchInfo()
         _check(self.L.mpc_patch_apply(self.h, buf.ctypes.data_as(_u8p) if buf.size else C.cast(C.c_char_p(b"\0"), _u8p), buf.size, C.byref(info)))
         return info.as_dict()
+
+    def last_route(self):
+        """mpc_patch_last_route of the last successful apply: 0 = the container's codes were parsed on the device (a version-2 patch),
+        1 = serial (a version-1 patch, or the index was refused), -1 = nothing decoded (an empty patch, or no apply yet)"""
+        return int(self.L.mpc_patch_last_route(self.h))
 
     def frame(self):
         """mpc_patch_read: the kept frame as a uint8 [H, W, 3] array"""

@@ -39,10 +39,15 @@ long long patch_frame_tiles(long long width, long long height) {
 }
 
 std::string patch_make_error(int width, int height, bool key, const int32_t* tiles, long long n, const uint8_t* container,
-                             size_t container_bytes) {
+                             size_t container_bytes, const uint8_t* index, size_t index_bytes) {
     const long long all = patch_frame_tiles(width, height);
     if (all == 0) return "bad geometry";
     if (n < 0 || n > all) return "n outside 0 ... the frame's tiles";
+    if (index_bytes != 0) {
+        if (!index) return "no index";
+        if (static_cast<uint64_t>(index_bytes) >= (1ULL << 32)) return "an index of 2^32 bytes or more";
+        if (n == 0) return "an empty patch carries no index";
+    }
     if (key) {
         if (n != all) return "a key patch lists every tile";
     } else if (n == all) {
@@ -61,7 +66,7 @@ std::string patch_make_error(int width, int height, bool key, const int32_t* til
 }
 
 std::vector<uint8_t> patch_make(int width, int height, uint32_t sequence, bool key, const int32_t* tiles, long long n,
-                                const uint8_t* container, size_t container_bytes) {
+                                const uint8_t* container, size_t container_bytes, const uint8_t* index, size_t index_bytes) {
     std::vector<uint8_t> list;
     if (!key) {
         long long last = -1;
@@ -71,20 +76,21 @@ std::vector<uint8_t> patch_make(int width, int height, uint32_t sequence, bool k
         }
     }
     std::vector<uint8_t> out;
-    out.reserve(kPatchHeaderBytes + list.size() + container_bytes);
+    out.reserve(kPatchHeaderBytes + list.size() + container_bytes + index_bytes);
     out.insert(out.end(), {'M', 'P', 'C', 'P'});
-    store16(out, kPatchVersion);
+    store16(out, index_bytes ? kPatchVersionIndexed : kPatchVersion);
     store16(out, key ? 1u : 0u);
     store32(out, static_cast<uint32_t>(width));
     store32(out, static_cast<uint32_t>(height));
     store32(out, sequence);
     store32(out, static_cast<uint32_t>(n));
     store32(out, static_cast<uint32_t>(list.size()));
-    store32(out, 0u);
+    store32(out, static_cast<uint32_t>(index_bytes));
     store32(out, static_cast<uint32_t>(static_cast<uint64_t>(container_bytes)));
     store32(out, static_cast<uint32_t>(static_cast<uint64_t>(container_bytes) >> 32));
     out.insert(out.end(), list.begin(), list.end());
     if (container_bytes) out.insert(out.end(), container, container + container_bytes);
+    if (index_bytes) out.insert(out.end(), index, index + index_bytes);
     return out;
 }
 
@@ -92,26 +98,35 @@ std::string patch_parse(const uint8_t* bytes, size_t nbytes, PatchInfo* info, st
     if (tiles_out) tiles_out->clear();
     if (nbytes < kPatchHeaderBytes) return "shorter than a patch header";
     if (std::memcmp(bytes, "MPCP", 4) != 0) return "not a patch";
-    if (load16(bytes + 4) != kPatchVersion) return "unknown patch version";
+    const unsigned version = load16(bytes + 4);
+    if (version != kPatchVersion && version != kPatchVersionIndexed) return "unknown patch version";
     const unsigned flags = load16(bytes + 6);
     if (flags & ~1u) return "reserved flag bits set";
     PatchInfo p;
     p.key = (flags & 1u) != 0;
     const uint32_t width = load32(bytes + 8), height = load32(bytes + 12), n = load32(bytes + 20), list_bytes = load32(bytes + 24);
     p.sequence = load32(bytes + 16);
-    if (load32(bytes + 28) != 0) return "reserved word not zero";
+    const uint32_t index_bytes = load32(bytes + 28);                // version 1: a reserved word
+    if (version == kPatchVersion ? index_bytes != 0 : index_bytes == 0)
+        return version == kPatchVersion ? "reserved word not zero" : "a version-2 patch without an index";
     const uint64_t container_bytes = load64(bytes + 32);
     p.tiles = patch_frame_tiles(width, height);
     if (p.tiles == 0) return "bad geometry";
     p.width = static_cast<int>(width);
     p.height = static_cast<int>(height);
-    // the length, exactly: nothing below trusts list_bytes or container_bytes beyond it
-    const size_t body = nbytes - kPatchHeaderBytes;
-    if (list_bytes > body || container_bytes != static_cast<uint64_t>(body - list_bytes)) return "the length is not header + list + container";
+    // the length, exactly: nothing below trusts list_bytes, container_bytes or index_bytes beyond it
+    if (index_bytes > nbytes - kPatchHeaderBytes) return "the length is not header + list + container + index";
+    const size_t body = nbytes - kPatchHeaderBytes - index_bytes;
+    if (list_bytes > body || container_bytes != static_cast<uint64_t>(body - list_bytes))
+        return index_bytes ? "the length is not header + list + container + index" : "the length is not header + list + container";
     p.n = n;
     p.list_bytes = list_bytes;
     p.container_offset = kPatchHeaderBytes + list_bytes;
     p.container_bytes = static_cast<size_t>(container_bytes);
+    if (index_bytes) {
+        p.index_offset = p.container_offset + p.container_bytes;
+        p.index_bytes = index_bytes;
+    }
     if (p.n > p.tiles) return "more tiles listed than the frame has";
     if (p.key) {
         if (p.n != p.tiles) return "a key patch lists every tile";
@@ -119,6 +134,7 @@ std::string patch_parse(const uint8_t* bytes, size_t nbytes, PatchInfo* info, st
     } else if (p.n == p.tiles) {
         return "every tile listed without the key flag";
     } else if (p.n == 0) {
+        if (index_bytes != 0) return "an empty patch carries no index";
         if (list_bytes != 0 || container_bytes != 0) return "an empty patch carries neither list nor container";
         *info = p;
         return "";
@@ -161,6 +177,28 @@ std::string patch_parse(const uint8_t* bytes, size_t nbytes, PatchInfo* info, st
     if (tiles_out) tiles_out->swap(list);
     *info = p;
     return "";
+}
+
+std::vector<uint8_t> patch_strip_index(const uint8_t* bytes, const PatchInfo& p) {
+    std::vector<uint8_t> out(bytes, bytes + kPatchHeaderBytes + p.list_bytes + p.container_bytes);
+    out[4] = static_cast<uint8_t>(kPatchVersion);                   // version 2 differs in these two words alone
+    out[5] = 0;
+    out[28] = out[29] = out[30] = out[31] = 0;
+    return out;
+}
+
+std::vector<uint8_t> patch_add_index(const uint8_t* bytes, const PatchInfo& p, uint32_t interval, size_t index_min_bytes) {
+    std::vector<uint8_t> out = patch_strip_index(bytes, p);
+    if (p.n == 0 || p.container_bytes < (index_min_bytes ? index_min_bytes : 1)) return out;
+    std::vector<uint8_t> index;
+    // a container that does not parse has no index, and one whose index says "serial only" has no use for it
+    if (!build_container_index(bytes + p.container_offset, p.container_bytes, interval, index) || index.size() < 16 || (index[12] & 1u) ||
+        static_cast<uint64_t>(index.size()) >= (1ULL << 32))
+        return out;
+    out[4] = static_cast<uint8_t>(kPatchVersionIndexed);
+    for (int k = 0; k < 4; ++k) out[28 + k] = static_cast<uint8_t>(index.size() >> (8 * k));
+    out.insert(out.end(), index.begin(), index.end());
+    return out;
 }
 
 }  // namespace mpc

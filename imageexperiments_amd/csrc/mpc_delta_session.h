@@ -1,5 +1,5 @@
 // mpc_delta_session.h -- product: the delta encoder's session and the driver of one call, shared by the translation units that add a
-// kind of call to it: mpcodec_delta.cpp (mpc_delta_encode, mpc_delta_encode_patch) and mpcodec_rate.cpp
+// kind of call to it: mpcodec_delta.cpp (mpc_delta_encode, mpc_delta_encode_patch[_indexed]) and mpcodec_rate.cpp
 // (mpc_delta_encode_patch_budget).  The stages are mpcodec_delta.cpp's.
 #pragma once
 

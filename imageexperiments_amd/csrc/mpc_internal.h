@@ -488,10 +488,11 @@ struct ContainerMade {
     }
 };
 // One records-to-container job on job slot 0 with everything on `s`, as a compose finishes: the container of `d_counts` / `d_choices`
-// (the caller's records and geometry), and with `every` != 0 its version-2 seek index from the entropy stage.  The call waits for
-// the container; the slot is left as mpc_container_job_begin expects it
+// (the caller's records and geometry), and with `every` != 0 its seek index from the entropy stage: version 2, or with `expanded`
+// false version 1 (what a patch carries).  The call waits for the container; the slot is left as mpc_container_job_begin expects it
 mpc_status records_container(mpc_context* c, const Tuning& tuning, hipStream_t s, const uint16_t* d_counts, const mpc_basis_choice* d_choices,
-                             long long tiles, int width, int height, const double* quant, unsigned every, ContainerMade* out);
+                             long long tiles, int width, int height, const double* quant, unsigned every, ContainerMade* out,
+                             bool expanded = true);
 
 // ---- rate control on the device (mpcodec_budget.cpp): the depth profile of records against the tight frame they came from ----
 mpc_status profile_on_device(mpc_context* c, const uint16_t* d_counts, const mpc_basis_choice* d_choices, const double* quant,

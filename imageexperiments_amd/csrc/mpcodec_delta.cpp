@@ -1,8 +1,8 @@
 // mpcodec_delta.cpp -- product: the delta encoder (include/mpcodec.h, "delta"; DESIGN.md 4, "Encoder: changed tiles only").
 // A session keeps the last frame and its records in device memory; a call finds the changed tiles on the device (mp_delta.hip),
 // pursues only those through the unchanged tile encoder, and makes the container from the whole frame's records as a compose does --
-// or, as the sender of a delta stream (mpc_delta_encode_patch; include/mpcodec.h, "patch"), a patch: the list and the container of
-// the packed frame of the listed tiles alone.
+// or, as the sender of a delta stream (mpc_delta_encode_patch[_indexed]; include/mpcodec.h, "patch"), a patch: the list and the
+// container of the packed frame of the listed tiles alone, with the container's seek index where one is asked for.
 #include <cstring>
 #include <string>
 
@@ -252,9 +252,10 @@ mpc_status delta_pursue(mpc_delta* d, hipStream_t s, DeltaCall& call) {
 }
 
 // 7. records -> container on job slot 0, as a compose finishes, with the seek index from the entropy stage where one is asked for
-// (`every` != 0).  The records and the geometry are the caller's: the store's of the whole frame, or a packed frame's
+// (`every` != 0; version 2, or version 1 without `expanded`).  The records and the geometry are the caller's: the store's of the whole
+// frame, or a packed frame's
 mpc_status records_container(mpc_context* c, const Tuning& tuning, hipStream_t s, const uint16_t* d_counts, const mpc_basis_choice* d_choices,
-                             long long tiles, int width, int height, const double* quant, unsigned every, ContainerMade* out) {
+                             long long tiles, int width, int height, const double* quant, unsigned every, ContainerMade* out, bool expanded) {
     const int K = c->K;
     if (!c->jobs[0]) c->jobs[0] = std::make_unique<JobSlot>();
     JobSlot& js = *c->jobs[0];
@@ -273,7 +274,7 @@ mpc_status records_container(mpc_context* c, const Tuning& tuning, hipStream_t s
     job.host_stage = &host_stage;
     job.host_offset = 0;
     job.index_interval = every;
-    job.index_expanded = every != 0;
+    job.index_expanded = every != 0 && expanded;
     struct Unhook {                                             // the slot is left as mpc_container_job_begin expects it
         ContainerJob& job;
         ~Unhook() {
@@ -285,7 +286,7 @@ mpc_status records_container(mpc_context* c, const Tuning& tuning, hipStream_t s
     } unhook{job};
     EntropyBuffers eb;
     if (!tuning.host_entropy)
-        if (const mpc_status es = entropy_buffers(js.ent, static_cast<size_t>(tiles), K, &eb, every ? 2 : 0); es != MPC_OK) return es;
+        if (const mpc_status es = entropy_buffers(js.ent, static_cast<size_t>(tiles), K, &eb, every ? (expanded ? 2 : 1) : 0); es != MPC_OK) return es;
     HIP_TRY(hipStreamSynchronize(nullptr));                     // a slot carved for another geometry clears its tables on the null stream
     if (const mpc_status bs = container_begin(job, c, tuning.host_entropy ? nullptr : &eb, tuning.triple_limit, js.dev.data(), d_counts,
                                               reinterpret_cast<const uint32_t*>(d_choices), nullptr, nullptr, width, height, quant);
@@ -349,45 +350,78 @@ mpc_status mpc_delta_encode(mpc_delta* d, const uint8_t* rgb, size_t row_stride,
     });
 }
 
+}  // extern "C"
+
+namespace {
+// mpc_delta_encode_patch, and with `every` != 0 mpc_delta_encode_patch_indexed: the container job also leaves the version-1 seek index,
+// and a patch whose container has at least max(index_min_bytes, 1) bytes carries it -- byte for byte host_patch.h's patch_add_index
+mpc_status encode_patch(mpc_delta* d, const uint8_t* rgb, size_t row_stride, const double* quant, unsigned flags, unsigned every,
+                        size_t index_min_bytes, uint8_t** patch, size_t* patch_bytes, mpc_delta_info* info) {
+    bool key_patch = false;
+    const mpc_status st = delta_call(
+        d, rgb, row_stride, quant, flags, false, info,
+        [&] {
+            *patch = nullptr;
+            *patch_bytes = 0;
+            d->sent_valid = false;                                  // no budget call: what a receiver holds is no longer tracked
+        },
+        [&](const DeltaCall& call, hipStream_t s, const Tuning& tuning) -> mpc_status {
+            key_patch = call.key || call.n == d->tiles;
+            ContainerMade made;
+            if (key_patch) {                                        // the whole frame's container from the store
+                if (const mpc_status cs =
+                        records_container(d->ctx, tuning, s, d->d_counts, d->d_choices, d->tiles, d->width, d->height, quant, every, &made, false);
+                    cs != MPC_OK)
+                    return cs;
+            } else if (call.n > 0) {                                // the packed frame's, from its own counts and records
+                if (const mpc_status cs = records_container(d->ctx, tuning, s, call.d_packed_counts, call.d_packed_choices,
+                                                            static_cast<long long>(call.g.rows) * call.g.cols, 8 * call.g.cols, 8 * call.g.rows, quant,
+                                                            every, &made, false);
+                    cs != MPC_OK)
+                    return cs;
+            }
+            // the index goes along unless the patch is too small to gain by it or it says "serial only" (its flags word, bit 0: the
+            // host route's, for a code longer than 32 bits)
+            const bool indexed = every != 0 && call.n > 0 && made.nbytes >= (index_min_bytes ? index_min_bytes : 1) && made.index.size() >= 16 &&
+                                 !(made.index[12] & 1u) && static_cast<uint64_t>(made.index.size()) < (1ULL << 32);
+            const uint8_t* index = indexed ? made.index.data() : nullptr;
+            const size_t index_bytes = indexed ? made.index.size() : 0;
+            const std::string why =
+                mpc::patch_make_error(d->width, d->height, key_patch, d->changed.data(), call.n, made.bytes, made.nbytes, index, index_bytes);
+            if (!why.empty()) return fail(MPC_ERR_HIP, "the patch: %s", why.c_str());
+            const std::vector<uint8_t> blob =
+                mpc::patch_make(d->width, d->height, d->calls, key_patch, d->changed.data(), call.n, made.bytes, made.nbytes, index, index_bytes);
+            uint8_t* out = static_cast<uint8_t*>(std::malloc(blob.size()));
+            if (!out) return fail(MPC_ERR_ALLOC, "no patch");
+            std::memcpy(out, blob.data(), blob.size());
+            *patch = out;
+            *patch_bytes = blob.size();
+            return MPC_OK;
+        });
+    if (st == MPC_OK && key_patch) info->key = 1;                   // every tile listed: sent as a key patch
+    return st;
+}
+}  // namespace
+
+extern "C" {
+
 mpc_status mpc_delta_encode_patch(mpc_delta* d, const uint8_t* rgb, size_t row_stride, const double* quant, unsigned flags, uint8_t** patch,
                                   size_t* patch_bytes, mpc_delta_info* info) {
     return guarded([&]() -> mpc_status {
         if (!d || !rgb || !patch || !patch_bytes || !info) return fail(MPC_ERR_ARGUMENT, "null argument");
-        bool key_patch = false;
-        const mpc_status st = delta_call(
-            d, rgb, row_stride, quant, flags, false, info,
-            [&] {
-                *patch = nullptr;
-                *patch_bytes = 0;
-                d->sent_valid = false;                              // no budget call: what a receiver holds is no longer tracked
-            },
-            [&](const DeltaCall& call, hipStream_t s, const Tuning& tuning) -> mpc_status {
-                key_patch = call.key || call.n == d->tiles;
-                ContainerMade made;
-                if (key_patch) {                                    // the whole frame's container from the store
-                    if (const mpc_status cs = records_container(d->ctx, tuning, s, d->d_counts, d->d_choices, d->tiles, d->width, d->height, quant, 0, &made);
-                        cs != MPC_OK)
-                        return cs;
-                } else if (call.n > 0) {                            // the packed frame's, from its own counts and records
-                    if (const mpc_status cs = records_container(d->ctx, tuning, s, call.d_packed_counts, call.d_packed_choices,
-                                                                static_cast<long long>(call.g.rows) * call.g.cols, 8 * call.g.cols, 8 * call.g.rows, quant,
-                                                                0, &made);
-                        cs != MPC_OK)
-                        return cs;
-                }
-                const std::string why = mpc::patch_make_error(d->width, d->height, key_patch, d->changed.data(), call.n, made.bytes, made.nbytes);
-                if (!why.empty()) return fail(MPC_ERR_HIP, "the patch: %s", why.c_str());
-                const std::vector<uint8_t> blob =
-                    mpc::patch_make(d->width, d->height, d->calls, key_patch, d->changed.data(), call.n, made.bytes, made.nbytes);
-                uint8_t* out = static_cast<uint8_t*>(std::malloc(blob.size()));
-                if (!out) return fail(MPC_ERR_ALLOC, "no patch");
-                std::memcpy(out, blob.data(), blob.size());
-                *patch = out;
-                *patch_bytes = blob.size();
-                return MPC_OK;
-            });
-        if (st == MPC_OK && key_patch) info->key = 1;               // every tile listed: sent as a key patch
-        return st;
+        return encode_patch(d, rgb, row_stride, quant, flags, 0, 0, patch, patch_bytes, info);
+    });
+}
+
+mpc_status mpc_delta_encode_patch_indexed(mpc_delta* d, const uint8_t* rgb, size_t row_stride, const double* quant, unsigned flags,
+                                          int index_interval, size_t index_min_bytes, uint8_t** patch, size_t* patch_bytes,
+                                          mpc_delta_info* info) {
+    return guarded([&]() -> mpc_status {
+        if (!d || !rgb || !patch || !patch_bytes || !info) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (index_interval > 0 && (index_interval < static_cast<int>(mpc::kIndexIntervalMin) || index_interval > static_cast<int>(mpc::kIndexIntervalMax)))
+            return fail(MPC_ERR_ARGUMENT, "interval %d: 0 or %u to %u", index_interval, mpc::kIndexIntervalMin, mpc::kIndexIntervalMax);
+        const unsigned every = index_interval < 0 ? 0u : index_interval ? static_cast<unsigned>(index_interval) : mpc::kIndexIntervalDefault;
+        return encode_patch(d, rgb, row_stride, quant, flags, every, index_min_bytes, patch, patch_bytes, info);
     });
 }
 

@@ -1,7 +1,9 @@
 // mpcodec_patch.cpp -- product: the delta stream's patches (include/mpcodec.h, "patch"; DESIGN.md 4, "Delta stream"): the host-only
 // entry points of the format (host_patch.h) and the receiver, a session that keeps the current frame in device memory and writes only
 // a patch's listed tiles into it: the unchanged mpc_decode_image_device decodes the patch's container -- the packed frame of the
-// listed tiles, an ordinary frame -- into staging, and mp_tile_unpack_kernel (mp_delta.hip) puts its tiles in their places.
+// listed tiles, an ordinary frame -- into staging, and mp_tile_unpack_kernel (mp_delta.hip) puts its tiles in their places.  A
+// version-2 patch carries the container's seek index: its container goes through mpc_decode_images_indexed_device instead, which
+// parses the entropy codes on the device.
 #include <cstring>
 #include <string>
 
@@ -21,6 +23,7 @@ struct mpc_patch_decoder {
     uint32_t expected = 0;                      // the sequence the next non-key patch must carry
     bool changed_all = false;                   // the last apply's list is every tile
     std::vector<int32_t> changed;               // else this
+    int route = -1;                             // the last apply's decode: 0 parsed on the device, 1 serial, -1 none (an empty patch)
     ~mpc_patch_decoder() {
         if (stream) {
             (void)hipStreamSynchronize(stream);
@@ -44,6 +47,15 @@ void report(const mpc::PatchInfo& p, struct mpc_patch_info* info) {
     info->container_bytes = p.container_bytes;
 }
 
+mpc_status give(const std::vector<uint8_t>& blob, uint8_t** bytes, size_t* nbytes) {
+    uint8_t* out = static_cast<uint8_t*>(std::malloc(blob.size()));
+    if (!out) return fail(MPC_ERR_ALLOC, "no patch");
+    std::memcpy(out, blob.data(), blob.size());
+    *bytes = out;
+    *nbytes = blob.size();
+    return MPC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -54,13 +66,51 @@ mpc_status mpc_patch_make(int width, int height, uint32_t sequence, int key, con
         if (!bytes || !nbytes) return fail(MPC_ERR_ARGUMENT, "null argument");
         const std::string why = mpc::patch_make_error(width, height, key != 0, tiles, n, container, container_bytes);
         if (!why.empty()) return fail(MPC_ERR_ARGUMENT, "%s", why.c_str());
-        const std::vector<uint8_t> blob = mpc::patch_make(width, height, sequence, key != 0, tiles, n, container, container_bytes);
-        uint8_t* out = static_cast<uint8_t*>(std::malloc(blob.size()));
-        if (!out) return fail(MPC_ERR_ALLOC, "no patch");
-        std::memcpy(out, blob.data(), blob.size());
-        *bytes = out;
-        *nbytes = blob.size();
+        return give(mpc::patch_make(width, height, sequence, key != 0, tiles, n, container, container_bytes), bytes, nbytes);
+    });
+}
+
+mpc_status mpc_patch_make_indexed(int width, int height, uint32_t sequence, int key, const int32_t* tiles, int n, const uint8_t* container,
+                                  size_t container_bytes, const uint8_t* index, size_t index_bytes, uint8_t** bytes, size_t* nbytes) {
+    return guarded([&]() -> mpc_status {
+        if (!bytes || !nbytes) return fail(MPC_ERR_ARGUMENT, "null argument");
+        const std::string why = mpc::patch_make_error(width, height, key != 0, tiles, n, container, container_bytes, index, index_bytes);
+        if (!why.empty()) return fail(MPC_ERR_ARGUMENT, "%s", why.c_str());
+        return give(mpc::patch_make(width, height, sequence, key != 0, tiles, n, container, container_bytes, index, index_bytes), bytes, nbytes);
+    });
+}
+
+mpc_status mpc_patch_index(const uint8_t* bytes, size_t nbytes, size_t* index_offset, size_t* index_bytes) {
+    return guarded([&]() -> mpc_status {
+        if (!bytes || !index_offset || !index_bytes) return fail(MPC_ERR_ARGUMENT, "null argument");
+        mpc::PatchInfo p;
+        const std::string why = mpc::patch_parse(bytes, nbytes, &p, nullptr);
+        if (!why.empty()) return fail(MPC_ERR_BITSTREAM, "Invalid patch: %s", why.c_str());
+        *index_offset = p.index_offset;
+        *index_bytes = p.index_bytes;
         return MPC_OK;
+    });
+}
+
+mpc_status mpc_patch_add_index(const uint8_t* patch, size_t nbytes, int interval, size_t index_min_bytes, uint8_t** out, size_t* out_bytes) {
+    return guarded([&]() -> mpc_status {
+        if (!patch || !out || !out_bytes) return fail(MPC_ERR_ARGUMENT, "null argument");
+        unsigned every = 0;
+        if (const mpc_status bad = index_interval_of(interval, &every)) return bad;
+        mpc::PatchInfo p;
+        const std::string why = mpc::patch_parse(patch, nbytes, &p, nullptr);
+        if (!why.empty()) return fail(MPC_ERR_BITSTREAM, "Invalid patch: %s", why.c_str());
+        return give(mpc::patch_add_index(patch, p, every, index_min_bytes), out, out_bytes);
+    });
+}
+
+mpc_status mpc_patch_strip_index(const uint8_t* patch, size_t nbytes, uint8_t** out, size_t* out_bytes) {
+    return guarded([&]() -> mpc_status {
+        if (!patch || !out || !out_bytes) return fail(MPC_ERR_ARGUMENT, "null argument");
+        mpc::PatchInfo p;
+        const std::string why = mpc::patch_parse(patch, nbytes, &p, nullptr);
+        if (!why.empty()) return fail(MPC_ERR_BITSTREAM, "Invalid patch: %s", why.c_str());
+        return give(mpc::patch_strip_index(patch, p), out, out_bytes);
     });
 }
 
@@ -139,6 +189,7 @@ mpc_status mpc_patch_apply(mpc_patch_decoder* p, const uint8_t* patch, size_t nb
         std::lock_guard<std::recursive_mutex> one_host_call(c->host_calls);
         HIP_TRY(hipSetDevice(c->device));
         hipStream_t s = p->stream;
+        int route = -1;
         if (pi.n > 0) {
             const uint8_t* container = patch + pi.container_offset;
             int cw = 0, ch = 0, cK = 0, cbs = 0;
@@ -154,8 +205,16 @@ mpc_status mpc_patch_apply(mpc_patch_decoder* p, const uint8_t* patch, size_t nb
                 if (const mpc_status gs = p->list.reserve(256 + sizeof(int32_t) * listed.size(), "patch decoder list"); gs != MPC_OK) return gs;
             uint8_t* staged = reinterpret_cast<uint8_t*>(p->staging.data());
             int w = 0, h = 0;
-            // the decoder's own refusals, status and text: it returns when the pixels are complete and its error words are read
-            if (const mpc_status ds = mpc_decode_image_device(c, container, pi.container_bytes, staged, pixels, &w, &h); ds != MPC_OK) return ds;
+            // the decoder's own refusals, status and text: it returns when the pixels are complete and its error words are read.  A
+            // version-2 patch: the indexed route of the same decoder, the index section read where it lies (its readers go bytewise);
+            // an index the decoder refuses costs the serial route it falls back to, never the patch
+            route = 1;
+            const uint8_t* index = pi.index_bytes ? patch + pi.index_offset : nullptr;
+            if (const mpc_status ds = index ? mpc_decode_images_indexed_device(c, &container, &pi.container_bytes, &index, &pi.index_bytes, 1, &staged,
+                                                                               &pixels, &w, &h, &route)
+                                            : mpc_decode_image_device(c, container, pi.container_bytes, staged, pixels, &w, &h);
+                ds != MPC_OK)
+                return ds;
             if (w != want_w || h != want_h) return fail(MPC_ERR_BITSTREAM, "Invalid patch: decoded %d x %d where %d x %d is due", w, h, want_w, want_h);
             // from here on the kept frame is written: only the device itself can still fail, and then the session wants a key patch
             struct Broken {
@@ -191,6 +250,7 @@ mpc_status mpc_patch_apply(mpc_patch_decoder* p, const uint8_t* patch, size_t nb
         p->expected = pi.sequence + 1;
         p->changed_all = pi.key;
         p->changed.swap(listed);
+        p->route = route;
         report(pi, info);
         return MPC_OK;
     });
@@ -214,6 +274,8 @@ mpc_status mpc_patch_read(mpc_patch_decoder* p, uint8_t* rgb, size_t row_stride)
         return MPC_OK;
     });
 }
+
+int mpc_patch_last_route(const mpc_patch_decoder* p) { return p ? p->route : -1; }
 
 mpc_status mpc_patch_changed(const mpc_patch_decoder* p, int32_t* tiles, int capacity, int* n) {
     if (!p || !n || (capacity > 0 && !tiles)) return fail(MPC_ERR_ARGUMENT, "null argument");

@@ -945,6 +945,9 @@ mpc_status mpc_delta_changed(const mpc_delta* d, int32_t* tiles, int capacity, i
  *   tile   no flag, 0 < n < tiles; the container's header says 8C x 8R pixels with (R, C) = mpc_delta_pack_geometry(n,
  *          MPC_DELTA_PACK_ROWS) -- the 64 is part of format version 1 -- and listed tile j is tile (j / R, j % R) of it
  * There is no patch with n == tiles and no key flag: the sender writes a key patch instead.
+ * VERSION 2 is version 1 with one word given a meaning and one section appended ("patch index", further down): version = 2, the word
+ * at 28 = index_bytes (> 0), and index_bytes of the container's seek index behind the container.  Everything in this section reads a
+ * version-2 patch as it reads the patch without its index; only the receiver's decode (step 4) takes another route to the same pixels.
  *
  * Host only, no context:
  *   mpc_patch_make   the only writer: *bytes (mpc_free).  key != 0: n must be the frame's tile count, `tiles` is not read; else n == 0
@@ -1242,6 +1245,58 @@ mpc_status mpc_rate_distortion(mpc_context* ctx, const uint8_t* rgb, int width, 
 /* The same with the frame already in device memory (3*width bytes per row, tightly packed). */
 mpc_status mpc_rate_distortion_device(mpc_context* ctx, const uint8_t* d_rgb, int width, int height, const double* quants,
                                       int n_levels, size_t* nbytes, unsigned long long* sse, double* psnr, uint8_t** bytes);
+
+/* ---- patch index: a patch that carries its container's seek index ("Delta stream") ----
+ * The receiver of a version-1 patch parses the container's entropy codes on the host, serially: the cost follows the bytes.  A
+ * version-2 patch brings the seek index of its container along, and mpc_patch_apply hands container and index to the sequence
+ * decoder's indexed route, which parses the codes on the device.
+ *
+ * THE FORMAT, version 2, little endian:
+ *    0 "MPCP" | 4 u16 version = 2 | 6 u16 flags (bit 0 = key) | 8 u32 width | 12 u32 height | 16 u32 sequence |
+ *   20 u32 n | 24 u32 list_bytes | 28 u32 index_bytes (> 0) | 32 u64 container_bytes | 40 the list | the container | the index
+ * exactly 40 + list_bytes + container_bytes + index_bytes long; list and container as in version 1.  The forms are key and tile: there
+ * is no version-2 empty patch, and a patch without an index is written as version 1.  A version-2 header with index_bytes == 0 is
+ * refused, as is a version-1 header whose word at 28 is not 0.  The index section is a version-1 seek-index blob ("MPIX", the seek
+ * index section above), but the patch parser checks its framing alone: the index is a hint, a patch whose index section is garbage
+ * is a valid patch, and applying it gives the pixels of the patch without it.  The section starts wherever the list and the
+ * container end, at any alignment: a reader copies it or reads it bytewise.
+ * mpc_patch_info and mpc_patch_tiles accept version 2 and report what they report for the stripped patch.
+ *
+ * Host only, no context, safe on several threads; outputs are mpc_free's:
+ *   mpc_patch_index         validates as mpc_patch_info does; the index section's offset from `bytes` and its size, (0, 0) for version 1
+ *   mpc_patch_make_indexed  mpc_patch_make with an index section: index_bytes == 0 writes the version-1 blob; MPC_ERR_ARGUMENT for an
+ *                           index given for an empty patch, index_bytes >= 2^32, or index == NULL with index_bytes != 0.  The bytes
+ *                           are copied as they are
+ *   mpc_patch_strip_index   the version-1 patch, byte for byte: a version-1 patch's own bytes
+ *   mpc_patch_add_index     what a sender that attaches the index does.  Any index present is stripped.  Where the patch has a
+ *                           container of at least max(index_min_bytes, 1) bytes and mpc_container_index(container, interval) succeeds
+ *                           with an index that is not "serial only", that blob is appended and the patch is version 2; otherwise the
+ *                           version-1 patch comes back.  interval: mpc_container_index's rules (0 = the default, else 32 ... 65536)
+ * A refused patch is MPC_ERR_BITSTREAM and nothing is written.
+ *
+ * THE SENDER, mpc_delta_encode_patch_indexed: mpc_delta_encode_patch's refusals, flags, stages and session effects -- the session
+ * advances identically whichever of mpc_delta_encode, mpc_delta_encode_patch and this call is used, in any mix -- plus
+ * mpc_delta_encode's refusal of an interval that is none.  index_interval < 0: exactly mpc_delta_encode_patch.  Else the result is
+ * byte for byte mpc_patch_add_index(P, index_interval, index_min_bytes) of the patch P mpc_delta_encode_patch returns for the call.
+ * The index comes from the container job's entropy stage (a key patch: the store's job; a tile patch: the packed frame's); the
+ * finished container is parsed only where the frame takes the host entropy route, as for every indexed encoder.  index_min_bytes
+ * leaves small patches at version 1: below some size the device parse's fixed cost (the host's tables for 1 + 6K streams and about a
+ * dozen launches) exceeds the serial parse, and the index adds about a tenth to the bytes.
+ *
+ * THE RECEIVER: mpc_patch_apply decodes a version-2 patch's container as mpc_decode_images_indexed_device does with n = 1 and the
+ * patch's index section; staging, the list upload, the unpack kernel and a key patch's copy are version 1's.  Pixels, statuses and
+ * error texts are those of applying the stripped patch, and so is the atomicity rule.
+ *   mpc_patch_last_route  of the last successful apply: 0 = the codes were parsed on the device; 1 = serial (a version-1 patch, or the
+ *                         decoder refused the index); -1 = nothing was decoded (an empty patch, no apply yet, p == NULL) */
+mpc_status mpc_patch_index(const uint8_t* bytes, size_t nbytes, size_t* index_offset, size_t* index_bytes);
+mpc_status mpc_patch_make_indexed(int width, int height, uint32_t sequence, int key, const int32_t* tiles, int n, const uint8_t* container,
+                                  size_t container_bytes, const uint8_t* index, size_t index_bytes, uint8_t** bytes, size_t* nbytes);
+mpc_status mpc_patch_add_index(const uint8_t* patch, size_t nbytes, int interval, size_t index_min_bytes, uint8_t** out, size_t* out_bytes);
+mpc_status mpc_patch_strip_index(const uint8_t* patch, size_t nbytes, uint8_t** out, size_t* out_bytes);
+mpc_status mpc_delta_encode_patch_indexed(mpc_delta* d, const uint8_t* rgb, size_t row_stride, const double* quant, unsigned flags,
+                                          int index_interval, size_t index_min_bytes, uint8_t** patch, size_t* patch_bytes,
+                                          mpc_delta_info* info);
+int        mpc_patch_last_route(const mpc_patch_decoder* p);
 
 /* ---- test entry points ----
  * These exist for the tests of the pursuit screen's tables (tests/test_screen_cases.py, tests/test_gpu_screen_tables.py) and are
