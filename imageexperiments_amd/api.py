@@ -2048,6 +2048,15 @@ class CompressionContext:
             _check(self.L.mpc_code_symbol_streams_device_indexed(*head, *tail))
         return _take_bytes(self.L, out, n), (_take_bytes(self.L, idx, ni) if idx else None), route.value
 
+    def decode_tiles_device(self, d_counts, d_choices, width, height, d_rgb, quant=None, stream=0):
+        """mpc_decode_tiles_device: whole-frame records in device memory -> d_rgb[height, width, 3] (uint8), reconstructed with `quant`
+        (None = the context's tables) exactly as given, not truncated to the container header's u16.  Asynchronous on `stream`."""
+        qp = None
+        if quant is not None:
+            quant = np.ascontiguousarray(quant, np.float64).reshape(3, self.K)
+            qp = quant.ctypes.data_as(_dp)
+        _check(self.L.mpc_decode_tiles_device(self.h, d_counts, d_choices, qp, int(width), int(height), d_rgb, stream or None))
+
     def container_job_begin(self, slot, d_counts, d_choices, width, height, quant=None, stream=0):
         """mpc_container_job_begin: stream assembly + entropy phase 1 of whole-frame records in device memory, enqueued only."""
         qp = None

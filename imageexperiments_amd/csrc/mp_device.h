@@ -118,7 +118,7 @@ struct HistParams {
 // Enqueue the whole K-step pursuit for the tile-channels [tc_begin, tc_begin + n) of the input on `stream`.
 // Tile-channel numbering: tc = unit*3 + ch, unit = frame*tiles_per_frame_stripe + tx*tile_rows + (ty - begin)
 // (vector mode: tc = vector index, channel fixed).  Returns hipError_t as int.  No host synchronisation,
-// no allocation: graph-capturable.
+// no allocation.
 // base_events: optional array of 2*K hipEvent_t (as void*) recorded right before / after each base-sweep launch
 // (live per-kernel timing for bench.py's roofline); nullptr = none.
 int enqueue_pursuit(const DictDevice& dict, const Workspace& ws, const FrameInput& in, const Outputs& out,
@@ -286,6 +286,11 @@ int launch_window_rank(const WindowArgs& w, void* stream);
 // the gather for the blocks that hold the tiles [t0, t1) alone: other tiles' records are not written (nor their symbols read).
 // a.block_live / a.sizes as launch_window_rank leaves them
 int launch_stream_gather_window(const StreamArgs& a, uint32_t* choices, long long t0, long long t1, void* stream);
+// quant[3 * K] (host memory, read before the call returns) -> dst[3 * K] on `stream`, as a kernel argument (mp_streams.hip)
+struct QuantTable {
+    double q[3 * kMaxDeviceK];
+};
+int launch_quant_table(const double* quant, int K, double* dst, void* stream);
 // records of the tile rows [row_begin, row_begin + rows) in stripe order -> their places in the whole frame's records
 int launch_interleave_stripe(const uint16_t* part_counts, const uint32_t* part_choices, int tiles_x, int tiles_y, int row_begin, int rows,
                              int K, uint16_t* frame_counts, uint32_t* frame_choices, void* stream);

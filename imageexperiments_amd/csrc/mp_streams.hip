@@ -444,6 +444,22 @@ int launch_paste_records(const uint16_t* src_counts, const uint32_t* src_choices
     return (int)hipGetLastError();
 }
 
+// A call's quantiser table to its device slot.  The table travels in the kernel's argument block, which the launch copies before it
+// returns: the caller's memory may go away at once, and nothing waits for the stream as a copy from pageable memory does.
+__global__ __launch_bounds__(64) void mp_quant_table_kernel(const QuantTable t, double* dst, int n)
+{
+    for (int i = threadIdx.x; i < n; i += 64) dst[i] = t.q[i];
+}
+
+int launch_quant_table(const double* quant, int K, double* dst, void* stream_)
+{
+    if (!quant || !dst || K < 1 || K > kMaxDeviceK) return (int)hipErrorInvalidValue;
+    QuantTable t{};
+    for (int i = 0; i < 3 * K; ++i) t.q[i] = quant[i];
+    hipLaunchKernelGGL(mp_quant_table_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream_), t, dst, 3 * K);
+    return (int)hipGetLastError();
+}
+
 int launch_interleave_stripe(const uint16_t* part_counts, const uint32_t* part_choices, int tiles_x, int tiles_y, int row_begin, int rows,
                              int K, uint16_t* frame_counts, uint32_t* frame_choices, void* stream_)
 {

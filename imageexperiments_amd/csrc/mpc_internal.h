@@ -349,7 +349,9 @@ struct mpc_context {
     // slots of their own, so that a later call with quant == NULL still quantises with the context's tables
     static constexpr int kQuantSlots = 16;
     double* d_quant_ring = nullptr;   // [kQuantSlots][3 * MPC_MAX_K]
+    hipEvent_t quant_free[kQuantSlots] = {};         // behind the last reader of each slot (CallQuant)
     unsigned quant_next = 0;
+    std::mutex quant_lock;            // one call with an override at a time per context, from taking its slot to recording quant_free
     std::recursive_mutex host_calls;  // the host-buffer entry points share the staging buffers below
     int* d_flag = nullptr;            // mpc_decode_tiles_device: set when a record indexes outside its dictionary
     int* d_crop_flag = nullptr;       // mpc_crop_records_device: set by a count above K, read by mpc_crop_records_check
@@ -384,8 +386,7 @@ struct mpc_context {
     std::unique_ptr<DecodeSlot> dec[kDecodeSlots];   // created on first use
     // The exhaustive path's pursuit of a call is cut into sub-batches that run on `pipes` internal streams, each with its own
     // workspace: the latency-bound bookkeeping kernels of one sub-batch (finish, update, bucket, fill) overlap the
-    // machine-filling sweeps of the other.  Fork/join with events on the caller's stream: still no host synchronisation,
-    // still capturable.
+    // machine-filling sweeps of the other.  Fork/join with events on the caller's stream: still no host synchronisation.
     struct Pipe {
         hipStream_t stream = nullptr;
         hipEvent_t done = nullptr;
@@ -460,8 +461,29 @@ extern "C" mpc_status crop_flag(mpc_context* c);
 
 // ---- context and tile encode (mpcodec_context.cpp) ----
 mpc::DictDevice dict_device(const mpc_context* c);
-// device table a call quantises with: the context's, or a ring slot holding the call's override (copied on `s`)
-mpc_status call_quant(mpc_context* c, const double* quant, hipStream_t s, const double** d_q);
+// The device table a call quantises with: the context's, or a ring slot holding the call's override.  The override is written on
+// `s` by a kernel that carries it as an argument (`quant` is read before call_quant returns; nothing waits for the stream).  A slot
+// is handed out again only behind the event its last user recorded when it let go of it, so the streams of a context's calls need
+// not be one: the call keeps its CallQuant alive until everything that reads d_q is enqueued on `s`.  Calls with an override from
+// several host threads take turns (quant_lock, held from the slot's hand-out to that record), so the event a slot's next user waits
+// on has always been recorded.
+struct CallQuant {
+    const double* d_q = nullptr;
+    CallQuant() = default;
+    CallQuant(const CallQuant&) = delete;
+    CallQuant& operator=(const CallQuant&) = delete;
+    ~CallQuant();
+    mpc_context* ctx = nullptr;
+    int slot = -1;                    // -1: the context's own table, nothing to let go of
+    hipStream_t stream = nullptr;
+    std::unique_lock<std::mutex> hold;               // mpc_context::quant_lock, while the call has an override
+};
+mpc_status call_quant(mpc_context* c, const double* quant, hipStream_t s, CallQuant* q);
+// the same with the quantiser steps the container header carries (mpc::header_quant of `quant`, or of the context's tables)
+mpc_status header_quant_device(mpc_context* c, const double* quant, hipStream_t s, CallQuant* cq);
+// MPC_ERR_ARGUMENT if `stream` is being captured into a graph (nothing has been enqueued then): the entry points that take a
+// stream use per-context and per-process scratch whose order a replayed graph would not take part in
+mpc_status refuse_capture(void* stream);
 mpc_status ensure_workspace(mpc_context* c, const Tuning& t, long long tile_channels);
 // whole_frame_order: the records go where one launch over the whole frame would put them (FrameInput::out_tile_rows) and the
 // caller has zeroed d_choices for the whole frame (stripes of one frame encoded one by one, encode_sequence's single frames)

@@ -22,14 +22,6 @@ mpc_status geometry(int width, int height, long long* tiles) {
     return MPC_OK;
 }
 
-// the quantiser steps the container header carries, on the device for this call
-mpc_status header_quant_device(mpc_context* c, const double* quant, hipStream_t s, const double** d_q) {
-    const double* q = quant ? quant : c->quant.data();
-    std::vector<double> carried(3 * static_cast<size_t>(c->K));
-    for (size_t i = 0; i < carried.size(); ++i) carried[i] = static_cast<double>(mpc::header_quant(q[i]));
-    return call_quant(c, carried.data(), s, d_q);
-}
-
 // d_totals zeroed on `s`, then the kernel
 mpc_status allocate_on_device(const mpc_context* c, const uint32_t* d_profile, const uint16_t* d_counts, long long tiles, const uint32_t* weights,
                               int j, uint8_t* d_depth, uint16_t* d_out_counts, unsigned long long* d_totals, hipStream_t s) {
@@ -220,12 +212,12 @@ mpc_status encode_budget(mpc_context* c, const uint8_t* rgb, bool on_device, int
 
 mpc_status profile_on_device(mpc_context* c, const uint16_t* d_counts, const mpc_basis_choice* d_choices, const double* quant,
                              const uint8_t* d_rgb, int width, int height, uint32_t* d_profile, int* d_error, hipStream_t s) {
-    const double* d_q = nullptr;
-    if (const mpc_status qs = header_quant_device(c, quant, s, &d_q); qs != MPC_OK) return qs;
+    CallQuant cq;
+    if (const mpc_status qs = header_quant_device(c, quant, s, &cq); qs != MPC_OK) return qs;
     mpc::ProfileParams p{};
     p.counts = d_counts;
     p.choices = reinterpret_cast<const uint32_t*>(d_choices);
-    p.quant = d_q;
+    p.quant = cq.d_q;
     p.K = c->K;
     p.width = width;
     p.height = height;
@@ -276,6 +268,7 @@ mpc_status mpc_depth_profile_device(mpc_context* c, const uint16_t* d_counts, co
         long long tiles = 0;
         if (const mpc_status gs = geometry(width, height, &tiles); gs != MPC_OK) return gs;
         HIP_TRY(hipSetDevice(c->device));
+        if (const mpc_status cs = refuse_capture(stream); cs != MPC_OK) return cs;
         if (const mpc_status fs = crop_flag(c); fs != MPC_OK) return fs;
         return profile_on_device(c, d_counts, d_choices, quant, d_rgb, width, height, d_profile, c->d_crop_flag, static_cast<hipStream_t>(stream));
     });
@@ -288,6 +281,7 @@ mpc_status mpc_budget_allocate_device(mpc_context* c, const uint32_t* d_profile,
         if (c->device < 0) return no_device();
         if (tiles < 1 || tiles * 3 >= (1LL << 31) || j < 0 || j >= mpc::kBudgetLambdas) return fail(MPC_ERR_ARGUMENT, "tiles %lld, multiplier %d", tiles, j);
         HIP_TRY(hipSetDevice(c->device));
+        if (const mpc_status cs = refuse_capture(stream); cs != MPC_OK) return cs;
         return allocate_on_device(c, d_profile, d_counts, tiles, weights, j, d_depth, d_out_counts, d_totals, static_cast<hipStream_t>(stream));
     });
 }

@@ -476,6 +476,7 @@ mpc_status mpc_container_job_begin(mpc_context* c, int slot, const uint16_t* d_c
     const long long tiles = static_cast<long long>((width + 7) / 8) * ((height + 7) / 8);
     std::lock_guard<std::recursive_mutex> one_host_call(c->host_calls);
     HIP_TRY(hipSetDevice(c->device));
+    if (const mpc_status cs = refuse_capture(stream); cs != MPC_OK) return cs;
     JobSlot* js = job_slot(c, slot);
     if (js->stage != 0) return fail(MPC_ERR_ARGUMENT, "container job slot %d is busy", slot);
     Carve measure;
@@ -552,6 +553,7 @@ mpc_status mpc_interleave_stripe_device(mpc_context* c, const uint16_t* d_part_c
     if (tile_row_begin < 0 || tile_row_end > tiles_y || tile_row_begin >= tile_row_end)
         return fail(MPC_ERR_ARGUMENT, "tile rows [%d,%d) outside 0..%d", tile_row_begin, tile_row_end, tiles_y);
     HIP_TRY(hipSetDevice(c->device));
+    if (const mpc_status cs = refuse_capture(stream); cs != MPC_OK) return cs;
     const int err = mpc::launch_interleave_stripe(d_part_counts, reinterpret_cast<const uint32_t*>(d_part_choices), tiles_x, tiles_y, tile_row_begin,
                                                   tile_row_end - tile_row_begin, c->K, d_frame_counts, reinterpret_cast<uint32_t*>(d_frame_choices), stream);
     if (err != 0) return launch_failed(err);
@@ -580,6 +582,7 @@ mpc_status mpc_crop_records_device(mpc_context* c, const uint16_t* d_counts, con
     mpc::TileWindow win;
     mpc::tile_window(width, height, c->block_size, r.x, r.y, r.width, r.height, win);
     HIP_TRY(hipSetDevice(c->device));
+    if (const mpc_status cs = refuse_capture(stream); cs != MPC_OK) return cs;
     if (const mpc_status fs = crop_flag(c); fs != MPC_OK) return fs;
     const int bs = c->block_size;
     const int err = mpc::launch_crop_records(d_counts, reinterpret_cast<const uint32_t*>(d_choices), (width + bs - 1) / bs, win.tiles_y, win.tx0,
@@ -613,6 +616,7 @@ mpc_status mpc_paste_records_device(mpc_context* c, const uint16_t* d_src_counts
     const long long dst_tiles_x = (static_cast<long long>(dst_width) + bs - 1) / bs, dst_tiles_y = (static_cast<long long>(dst_height) + bs - 1) / bs;
     if (dst_tiles_x * dst_tiles_y >= (1LL << 31)) return fail(MPC_ERR_ARGUMENT, "bad geometry");
     HIP_TRY(hipSetDevice(c->device));
+    if (const mpc_status cs = refuse_capture(stream); cs != MPC_OK) return cs;
     if (const mpc_status fs = crop_flag(c); fs != MPC_OK) return fs;
     const int stx0 = piece.x / bs, sty0 = piece.y / bs;
     const int err = mpc::launch_paste_records(d_src_counts, reinterpret_cast<const uint32_t*>(d_src_choices), (src_width + bs - 1) / bs,
@@ -631,6 +635,7 @@ mpc_status mpc_crop_records_check(mpc_context* c, void* stream) {
     if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device");
     if (!c->d_crop_flag) return MPC_OK;                             // nothing has been cropped yet
     HIP_TRY(hipSetDevice(c->device));
+    if (const mpc_status cs = refuse_capture(stream); cs != MPC_OK) return cs;
     hipStream_t s = static_cast<hipStream_t>(stream);
     int flag = 0;
     HIP_TRY(hipMemcpyAsync(&flag, c->d_crop_flag, sizeof(int), hipMemcpyDeviceToHost, s));

@@ -188,13 +188,41 @@ hipError_t acquire_device_dict(int device, const mpc::Dictionary& dict, std::sha
 }
 }  // namespace
 
-// device table a call quantises with: the context's, or a ring slot holding the call's override (copied on `s`)
-mpc_status call_quant(mpc_context* c, const double* quant, hipStream_t s, const double** d_q) {
-    *d_q = c->d_quant;
+// device table a call quantises with: the context's, or a ring slot holding the call's override (mpc_internal.h: CallQuant)
+mpc_status header_quant_device(mpc_context* c, const double* quant, hipStream_t s, CallQuant* cq) {
+    const double* q = quant ? quant : c->quant.data();
+    double carried[3 * MPC_MAX_K];
+    for (int i = 0; i < 3 * c->K; ++i) carried[i] = static_cast<double>(mpc::header_quant(q[i]));
+    return call_quant(c, carried, s, cq);
+}
+
+mpc_status call_quant(mpc_context* c, const double* quant, hipStream_t s, CallQuant* q) {
+    q->d_q = c->d_quant;
     if (!quant) return MPC_OK;
-    double* slot = c->d_quant_ring + static_cast<size_t>(c->quant_next++ % mpc_context::kQuantSlots) * 3 * MPC_MAX_K;
-    HIP_TRY(hipMemcpyAsync(slot, quant, 3 * sizeof(double) * c->K, hipMemcpyHostToDevice, s));
-    *d_q = slot;
+    q->hold = std::unique_lock<std::mutex>(c->quant_lock);     // until ~CallQuant: take, fill, read and let go are one step per context
+    const int slot = static_cast<int>(c->quant_next++ % mpc_context::kQuantSlots);
+    double* table = c->d_quant_ring + static_cast<size_t>(slot) * 3 * MPC_MAX_K;
+    HIP_TRY(hipStreamWaitEvent(s, c->quant_free[slot], 0));    // the slot's last reader, on whatever stream it ran, is through
+    q->ctx = c;
+    q->slot = slot;
+    q->stream = s;
+    const int err = mpc::launch_quant_table(quant, c->K, table, s);
+    if (err != 0) return launch_failed(err);
+    q->d_q = table;
+    return MPC_OK;
+}
+
+CallQuant::~CallQuant() {
+    if (slot >= 0) (void)hipEventRecord(ctx->quant_free[slot], stream);
+}
+
+mpc_status refuse_capture(void* stream) {
+    if (!stream) return MPC_OK;                               // the null stream cannot be captured
+    hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
+    HIP_TRY(hipStreamIsCapturing(static_cast<hipStream_t>(stream), &status));
+    if (status != hipStreamCaptureStatusNone)
+        return fail(MPC_ERR_ARGUMENT, "the stream is being captured into a graph: not supported (the calls of a process share scratch that a "
+                                      "replayed graph would use out of turn)");
     return MPC_OK;
 }
 
@@ -225,7 +253,7 @@ int pipes_for(const Tuning& t, long long tile_channels) {
 }  // namespace
 
 // grow-only workspaces of the step-synchronous exhaustive sweeps (MPC_PATH=steps); allocation synchronises the device, so
-// callers that must not (graph capture) call mpc_reserve() first
+// callers that must not call mpc_reserve() first
 mpc_status ensure_workspace(mpc_context* c, const Tuning& t, long long tile_channels) {
     if (!t.steps_path) return MPC_OK;                 // the persistent kernel's scratch lives in the shared DeviceDict
     const int want_pipes = pipes_for(t, tile_channels);
@@ -333,8 +361,11 @@ hipError_t stamps_report(hipStream_t s, const unsigned long long* d_debug, int w
 
 // The persistent path (mp_pursuit.hip): ONE launch on the caller's stream runs all K steps of every tile-channel; its
 // workgroups are split over the channels (a workgroup's LDS holds one channel's DetailBasis[0]).  No host synchronisation,
-// no allocation: graph-capturable.  Launches of one process are serialised on the device by a lock-ordered event chain,
-// because they share the per-device scratch and queue words.
+// no allocation.  Launches of one process are serialised on the device by a lock-ordered event chain, because they share the
+// per-device scratch and queue words.  That chain is why a capturing stream is refused (refuse_capture, in front of every caller):
+// the wait below would be on an event recorded outside the capture, the record behind the launch would leave done[0] a captured
+// event that the next plain launch cannot wait on, and a replay takes no part in the chain at all, so it would share the queue
+// words with whatever another stream launches beside it.
 mpc_status run_persistent(mpc_context* c, const Tuning& t, const mpc::FrameInput& in, const mpc::Outputs& out, const double* d_quant,
                           long long total_tc, void* stream) {
     DeviceDict& d = *c->dd;
@@ -506,8 +537,9 @@ mpc_status encode_batch_device(mpc_context* c, const Tuning& t, const uint8_t* d
     const long long tiles = static_cast<long long>(tiles_x) * (tile_row_end - tile_row_begin) * frames;
     hipStream_t s = static_cast<hipStream_t>(stream);
     HIP_TRY(hipSetDevice(c->device));
-    const double* d_q = nullptr;
-    if (const mpc_status qs = call_quant(c, quant, s, &d_q); qs != MPC_OK) return qs;
+    if (const mpc_status cs = refuse_capture(stream); cs != MPC_OK) return cs;
+    CallQuant cq;
+    if (const mpc_status qs = call_quant(c, quant, s, &cq); qs != MPC_OK) return qs;
     if (!whole_frame_order && !table) HIP_TRY(hipMemsetAsync(d_choices, 0, sizeof(mpc_basis_choice) * tiles * 3 * c->K, s));
     mpc::FrameInput in{};
     if (table) in.table = *table;
@@ -528,7 +560,7 @@ mpc_status encode_batch_device(mpc_context* c, const Tuning& t, const uint8_t* d
     out.choices = reinterpret_cast<uint32_t*>(d_choices);
     out.energy = d_energy;
     out.swept = d_swept;
-    return run_pursuit(c, t, in, out, d_q, tiles * 3, stream);
+    return run_pursuit(c, t, in, out, cq.d_q, tiles * 3, stream);
 }
 
 extern "C" {
@@ -569,6 +601,8 @@ mpc_status mpc_context_create(int K, int block_size, double bpp, int device, mpc
         if (e == hipSuccess) e = upload(&c->d_quant, c->quant.data(), c->quant.size());
         if (e == hipSuccess)
             e = hipMalloc(reinterpret_cast<void**>(&c->d_quant_ring), sizeof(double) * mpc_context::kQuantSlots * 3 * MPC_MAX_K);
+        for (int k = 0; k < mpc_context::kQuantSlots && e == hipSuccess; ++k)
+            e = hipEventCreateWithFlags(&c->quant_free[k], hipEventDisableTiming);
         if (e != hipSuccess) {
             mpc_context_destroy(c);
             return fail(MPC_ERR_HIP, "device setup failed: %s", hipGetErrorString(e));
@@ -587,6 +621,8 @@ void mpc_context_destroy(mpc_context* c) {
         (void)hipSetDevice(c->device);
         (void)hipFree(c->d_quant);
         (void)hipFree(c->d_quant_ring);
+        for (hipEvent_t e : c->quant_free)
+            if (e) (void)hipEventDestroy(e);
         (void)hipFree(c->d_flag);
         (void)hipFree(c->d_crop_flag);
         if (c->compose_side) (void)hipStreamDestroy(c->compose_side);
@@ -730,6 +766,8 @@ mpc_status mpc_histogram_device(mpc_context* c, const uint16_t* d_counts, const 
     if (!c) return fail(MPC_ERR_ARGUMENT, "null context");
     if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device");
     if (!d_counts || !d_choices || !d_hist || tiles < 1) return fail(MPC_ERR_ARGUMENT, "bad argument");
+    HIP_TRY(hipSetDevice(c->device));
+    if (const mpc_status cs = refuse_capture(stream); cs != MPC_OK) return cs;
     mpc::HistParams h{};
     h.counts = d_counts;
     h.choices = reinterpret_cast<const uint32_t*>(d_choices);

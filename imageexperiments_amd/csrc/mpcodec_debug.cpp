@@ -38,6 +38,7 @@ mpc_status mpc_debug_copy_gram_device(mpc_context* c, int channel, int sel_begin
     if (sel_begin < 0 || sel_count < 1 || sel_begin > n_sel - sel_count || col_begin < 0 || col_count < 1 || col_begin > stride - col_count)
         return fail(MPC_ERR_ARGUMENT, "rectangle outside the Gram table (%lld x %lld)", n_sel, stride);
     HIP_TRY(hipSetDevice(c->device));
+    if (const mpc_status cs = refuse_capture(stream); cs != MPC_OK) return cs;
     const float* src = d.d_gram + (static_cast<long long>(channel) * n_sel + sel_begin) * stride + col_begin;
     HIP_TRY(hipMemcpy2DAsync(d_out, sizeof(float) * col_count, src, sizeof(float) * stride, sizeof(float) * col_count,
                              static_cast<size_t>(sel_count), hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
@@ -51,6 +52,7 @@ mpc_status mpc_debug_gram_device(const double* d_base, const double* d_detail, c
     if (!aligned16(d_gram)) return fail(MPC_ERR_ARGUMENT, "d_gram must be 16-byte aligned");
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count < 1) return fail(MPC_ERR_NO_DEVICE, "no device");
+    if (const mpc_status cs = refuse_capture(stream); cs != MPC_OK) return cs;
     if (const int err = mpc::launch_gram(d_base, d_detail, d_block_rows, d_block_row_off, d_shadow, d_gram, num_base, n_sel,
                                          static_cast<long long>(num_base) * 64, stream))
         return launch_failed(err);
@@ -99,6 +101,7 @@ mpc_status mpc_debug_screen_probe_device(mpc_context* c, int channel, int block,
     if (!d_vectors || !d_approx || !d_bound) return fail(MPC_ERR_ARGUMENT, "null pointer");
     if (!aligned16(d_vectors) || !aligned16(d_approx)) return fail(MPC_ERR_ARGUMENT, "d_vectors and d_approx must be 16-byte aligned");
     HIP_TRY(hipSetDevice(c->device));
+    if (const mpc_status cs = refuse_capture(stream); cs != MPC_OK) return cs;
     const uint16_t* block_tiles =
         d.d_detail_t1 + (static_cast<size_t>(channel) * d.num_base + block) * mpc::kBlockFilterTiles * mpc::kFilterTileHalves;
     if (const int err = mpc::launch_screen_probe(d.d_base_t1, block_tiles, d_vectors, n, d_approx, d_bound, stream)) return launch_failed(err);

@@ -52,10 +52,11 @@ mpc_status mpc_decode_tiles_device(mpc_context* c, const uint16_t* d_counts, con
     if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device");
     if (width < 1 || height < 1) return fail(MPC_ERR_ARGUMENT, "bad geometry");
     HIP_TRY(hipSetDevice(c->device));
-    const double* d_q = nullptr;
-    if (const mpc_status qs = call_quant(c, quant, static_cast<hipStream_t>(stream), &d_q); qs != MPC_OK) return qs;
+    if (const mpc_status cs = refuse_capture(stream); cs != MPC_OK) return cs;
     if (const mpc_status fs = context_flag(c); fs != MPC_OK) return fs;
-    return decode_tiles_on_device(c, d_counts, reinterpret_cast<const uint32_t*>(d_choices), d_q, c->K, width, height, d_rgb,
+    CallQuant cq;
+    if (const mpc_status qs = call_quant(c, quant, static_cast<hipStream_t>(stream), &cq); qs != MPC_OK) return qs;
+    return decode_tiles_on_device(c, d_counts, reinterpret_cast<const uint32_t*>(d_choices), cq.d_q, c->K, width, height, d_rgb,
                                   c->d_flag, stream);
 }
 
@@ -71,15 +72,13 @@ mpc_status mpc_distortion_device(mpc_context* c, const uint16_t* d_counts, const
     const long long tiles = static_cast<long long>((width + 7) / 8) * ((height + 7) / 8);
     if (tiles * 3 >= (1LL << 31)) return fail(MPC_ERR_ARGUMENT, "frame too large");
     HIP_TRY(hipSetDevice(c->device));
-    const double* q = quant ? quant : c->quant.data();
-    std::vector<double> carried(3 * static_cast<size_t>(c->K));
-    for (size_t i = 0; i < carried.size(); ++i) carried[i] = static_cast<double>(mpc::header_quant(q[i]));
-    const double* d_q = nullptr;
-    if (const mpc_status qs = call_quant(c, carried.data(), static_cast<hipStream_t>(stream), &d_q); qs != MPC_OK) return qs;
+    if (const mpc_status cs = refuse_capture(stream); cs != MPC_OK) return cs;
+    CallQuant cq;
+    if (const mpc_status qs = header_quant_device(c, quant, static_cast<hipStream_t>(stream), &cq); qs != MPC_OK) return qs;
     mpc::DistortionParams p{};
     p.counts = d_counts;
     p.choices = reinterpret_cast<const uint32_t*>(d_choices);
-    p.quant = d_q;
+    p.quant = cq.d_q;
     p.K = c->K;
     p.width = width;
     p.height = height;

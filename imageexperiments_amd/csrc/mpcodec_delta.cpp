@@ -54,6 +54,7 @@ mpc_status mpc_tile_diff_device(mpc_context* c, uint8_t* d_kept, const uint8_t* 
         if (tiles >= (1LL << 31)) return fail(MPC_ERR_ARGUMENT, "bad geometry");
         std::lock_guard<std::recursive_mutex> one_host_call(c->host_calls);
         HIP_TRY(hipSetDevice(c->device));
+        if (const mpc_status cs = refuse_capture(stream); cs != MPC_OK) return cs;
         if (const mpc_status gs = c->delta_scratch.reserve(mpc::tile_diff_scratch_bytes(tiles), "diff scratch"); gs != MPC_OK) return gs;
         const int err = mpc::launch_tile_diff(d_kept, d_rgb, width, height, stride, d_list, d_count, c->delta_scratch.data(), stream);
         if (err != 0) return launch_failed(err);
@@ -74,6 +75,7 @@ mpc_status mpc_pack_tiles_device(mpc_context* c, const uint8_t* d_rgb, int width
         if (to < g.stride || to % 8 != 0 || reinterpret_cast<uintptr_t>(d_packed) % 8 != 0)
             return fail(MPC_ERR_ARGUMENT, "the packed frame: an 8-byte aligned base and a stride that is a multiple of 8 and at least %zu", g.stride);
         HIP_TRY(hipSetDevice(c->device));
+        if (const mpc_status cs = refuse_capture(stream); cs != MPC_OK) return cs;
         const int err = mpc::launch_tile_pack(d_rgb, width, height, stride, d_list, n, g.rows, g.cols, d_packed, to, stream);
         if (err != 0) return launch_failed(err);
         return MPC_OK;
@@ -94,6 +96,7 @@ mpc_status mpc_unpack_tiles_device(mpc_context* c, const uint8_t* d_packed, size
         if (from < g.stride || from % 8 != 0 || reinterpret_cast<uintptr_t>(d_packed) % 8 != 0)
             return fail(MPC_ERR_ARGUMENT, "the packed frame: an 8-byte aligned base and a stride that is a multiple of 8 and at least %zu", g.stride);
         HIP_TRY(hipSetDevice(c->device));
+        if (const mpc_status cs = refuse_capture(stream); cs != MPC_OK) return cs;
         if (const mpc_status fs = crop_flag(c); fs != MPC_OK) return fs;
         const int err = mpc::launch_tile_unpack(d_packed, from, d_list, n, g.rows, g.cols, d_rgb, width, height, stride, c->d_crop_flag, stream);
         if (err != 0) return launch_failed(err);
@@ -108,6 +111,7 @@ mpc_status mpc_scatter_records_device(mpc_context* c, const uint16_t* d_packed_c
         if (c->device < 0) return delta_no_device();
         if (n < 1 || tiles < 1) return fail(MPC_ERR_ARGUMENT, "n %d, tiles %d", n, tiles);
         HIP_TRY(hipSetDevice(c->device));
+        if (const mpc_status cs = refuse_capture(stream); cs != MPC_OK) return cs;
         if (const mpc_status fs = crop_flag(c); fs != MPC_OK) return fs;
         const int err = mpc::launch_tile_scatter_records(d_packed_counts, reinterpret_cast<const uint32_t*>(d_packed_choices), d_list, n, c->K, d_counts,
                                                          reinterpret_cast<uint32_t*>(d_choices), tiles, c->d_crop_flag, stream);

@@ -47,6 +47,7 @@ mpc_status mpc_owed_tiles_device(mpc_context* c, const uint8_t* d_sent, const ui
         if (tiles < 1 || tiles >= (1LL << 31)) return fail(MPC_ERR_ARGUMENT, "tiles %lld", tiles);
         std::lock_guard<std::recursive_mutex> one_host_call(c->host_calls);
         HIP_TRY(hipSetDevice(c->device));
+        if (const mpc_status cs = refuse_capture(stream); cs != MPC_OK) return cs;
         if (const mpc_status gs = c->delta_scratch.reserve(mpc::tile_diff_scratch_bytes(tiles), "diff scratch"); gs != MPC_OK) return gs;
         if (const int e = mpc::launch_owed_flags(d_sent, d_counts, tiles, c->K, d_flags, d_floor, d_must, stream); e != 0) return launch_failed(e);
         if (const int e = mpc::launch_tile_flags_list(d_flags, tiles, mpc::tile_diff_block_live(c->delta_scratch.data(), tiles), d_list, d_count, stream);
@@ -67,6 +68,7 @@ mpc_status mpc_gather_records_device(mpc_context* c, const uint16_t* d_counts, c
         const long long padded = static_cast<long long>(g.rows) * g.cols;
         if (padded >= (1LL << 31) / (3 * MPC_MAX_K)) return fail(MPC_ERR_ARGUMENT, "bad geometry");
         HIP_TRY(hipSetDevice(c->device));
+        if (const mpc_status cs = refuse_capture(stream); cs != MPC_OK) return cs;
         if (const mpc_status fs = crop_flag(c); fs != MPC_OK) return fs;
         mpc::GatherParams p{};
         p.counts = d_counts;
@@ -95,6 +97,7 @@ mpc_status mpc_budget_allocate_floor_device(mpc_context* c, const uint32_t* d_pr
         if (c->device < 0) return delta_no_device();
         if (n < 1 || n * 3 >= (1LL << 31) || j < 0 || j >= mpc::kBudgetLambdas) return fail(MPC_ERR_ARGUMENT, "tiles %lld, multiplier %d", n, j);
         HIP_TRY(hipSetDevice(c->device));
+        if (const mpc_status cs = refuse_capture(stream); cs != MPC_OK) return cs;
         hipStream_t s = static_cast<hipStream_t>(stream);
         HIP_TRY(hipMemsetAsync(d_totals, 0, 4 * sizeof(unsigned long long), s));
         mpc::AllocateFloorParams p{};

@@ -136,7 +136,13 @@ mpc_status mpc_context_get_dictionary(const mpc_context* ctx, double* base, int3
  *   d_swept  [tiles][3]      u32   dictionary rows correlated, SURVEY 8(d) "S"
  * d_energy / d_swept may be NULL.  quant: host pointer to 3*K doubles or NULL for the context's tables.
  * stream: hipStream_t (NULL = default stream).  Asynchronous; no synchronisation, and no allocation once the
- * workspace covers the call (mpc_reserve).  waves: reserved, pass 0. */
+ * workspace covers the call (mpc_reserve): that holds with a quant override too, which is read before the call returns.
+ * waves: reserved, pass 0.
+ * Streams and graphs, for this and every other entry point with a `stream` argument (the mpc_debug_* probes included): the work is ordered on `stream` like a
+ * kernel launch of the caller's own (behind what `stream` holds, in front of what is enqueued next), whatever other streams
+ * other calls of the context or the process use.  A stream that is being captured into a graph (hipStreamBeginCapture) is
+ * refused with MPC_ERR_ARGUMENT before anything is enqueued, and the capture stays valid: the calls of a process share scratch
+ * in an order that a replayed graph would take no part in. */
 mpc_status mpc_encode_tiles_device(mpc_context* ctx, const uint8_t* d_rgb, int width, int height, size_t row_stride,
                                    int tile_row_begin, int tile_row_end, const double* quant,
                                    uint16_t* d_counts, mpc_basis_choice* d_choices, double* d_energy, uint32_t* d_swept,
@@ -175,7 +181,7 @@ mpc_status mpc_calc_mp_batch(mpc_context* ctx, int channel, const double* quant_
 
 /* Pre-allocates the device workspace for calls of up to max_tiles tiles (3 tile-channels each).  The encode
  * entry points grow the workspace on demand, which synchronises the device; callers that must not synchronise
- * (stream capture) reserve first.  A call is cut into sub-batches that run on two internal streams (forked from and
+ * reserve first.  A call is cut into sub-batches that run on two internal streams (forked from and
  * joined to the caller's stream with events); at most 262144 tiles are in flight. */
 mpc_status mpc_reserve(mpc_context* ctx, long long max_tiles);
 
