@@ -86,6 +86,11 @@ class MpcBudgetInfo(C.Structure):                    # mpc_budget_info
 MPC_BUDGET_LAMBDAS = 256
 
 
+class MpcQualityInfo(C.Structure):                   # mpc_quality_info
+    _fields_ = [("lambda_index", C.c_int), ("full_bytes", C.c_size_t), ("sse", C.c_ulonglong), ("full_sse", C.c_ulonglong),
+                ("min_sse", C.c_ulonglong), ("records", C.c_ulonglong), ("full_records", C.c_ulonglong), ("model_bits_256", C.c_ulonglong)]
+
+
 def _parts(parts, device_pixels=False):
     """[(source, rect, x, y)] -> (MpcPart array, what must stay alive).  source: an int with rect = (x, y, width, height) or None = all
     of it; or pixels, rect None: an HxWx3 uint8 array (a strided view keeps its row stride), with device_pixels a
@@ -344,6 +349,18 @@ def _bind_bitstream(L):
         for f in ("mpc_encode_image_budget", "mpc_encode_image_budget_device"):
             getattr(L, f).argtypes = [vp, vp, C.c_int, C.c_int, _dp, C.c_size_t, C.c_int, C.POINTER(_u8p), _szp_, C.POINTER(_u8p), _szp_, _u8p,
                                       C.POINTER(MpcBudgetInfo)]
+    except AttributeError:
+        if not os.environ.get("MPCODEC_LIB"):             # an older build may be loaded for A/B timing only
+            raise
+    try:
+        L.mpc_budget_sweep.argtypes = [_u32p, _u16p, C.c_longlong, C.c_int, _u32p, _u64p]
+        L.mpc_quality_pick.argtypes = [_u64p, C.c_uint64]
+        L.mpc_quality_pick.restype = C.c_int
+        L.mpc_sse_for_psnr.argtypes = [C.c_double, C.c_int, C.c_int, _u64p]
+        L.mpc_budget_sweep_device.argtypes = [vp, vp, vp, C.c_longlong, _u32p, vp, vp]
+        for f in ("mpc_encode_image_quality", "mpc_encode_image_quality_device"):
+            getattr(L, f).argtypes = [vp, vp, C.c_int, C.c_int, _dp, C.c_ulonglong, C.c_int, C.POINTER(_u8p), _szp_, C.POINTER(_u8p), _szp_, _u8p,
+                                      C.POINTER(MpcQualityInfo)]
     except AttributeError:
         if not os.environ.get("MPCODEC_LIB"):             # an older build may be loaded for A/B timing only
             raise
@@ -1168,6 +1185,49 @@ class BudgetResult:
                 f"sse={self.sse}, full_sse={self.full_sse}, records={self.records}, full_records={self.full_records})")
 
 
+def budget_sweep(profile, counts, weights):
+    """mpc_budget_sweep: budget_allocate's totals at every multiplier on the host: profile uint32 [T, K + 1], counts uint16 [T, 3],
+    weights uint32 [3, K] -> uint64 [256, 3]: distortion, rate in 1/256 bit and records kept at j = 0 ... 255"""
+    profile = np.ascontiguousarray(profile, np.uint32)
+    T, K = profile.shape[0], profile.shape[1] - 1
+    counts = np.ascontiguousarray(counts, np.uint16).reshape(T, 3)
+    weights = np.ascontiguousarray(weights, np.uint32).reshape(3, K)
+    totals = np.zeros((MPC_BUDGET_LAMBDAS, 3), np.uint64)
+    _check(load_library().mpc_budget_sweep(profile.ctypes.data_as(_u32p), counts.ctypes.data_as(_u16p), T, K, weights.ctypes.data_as(_u32p),
+                                           totals.ctypes.data_as(C.POINTER(C.c_uint64))))
+    return totals
+
+
+def quality_pick(totals, max_sse):
+    """mpc_quality_pick: the largest multiplier j whose distortion totals[j, 0] is at most max_sse, -1 if there is none"""
+    totals = np.ascontiguousarray(totals, np.uint64).reshape(MPC_BUDGET_LAMBDAS, 3)
+    return int(load_library().mpc_quality_pick(totals.ctypes.data_as(C.POINTER(C.c_uint64)), int(max_sse)))
+
+
+def sse_for_psnr(psnr, width, height):
+    """mpc_sse_for_psnr: the largest squared error of a width x height frame whose PSNR (calculate_psnr's formula) is at least `psnr`"""
+    v = C.c_uint64(0)
+    _check(load_library().mpc_sse_for_psnr(float(psnr), int(width), int(height), C.byref(v)))
+    return v.value
+
+
+class QualityResult:
+    """What encode_image_quality returns: the container, its seek index (None unless asked for), the depth per tile (uint8) and
+    mpc_quality_info's fields; sse is at most the target."""
+    __slots__ = ("container", "index", "depth", "lambda_index", "full_bytes", "sse", "full_sse", "min_sse", "records", "full_records",
+                 "model_bits_256")
+
+    def __init__(self, container, index, depth, info):
+        self.container, self.index, self.depth = container, index, depth
+        for f, _ in MpcQualityInfo._fields_:
+            setattr(self, f, int(getattr(info, f)))
+
+    def __repr__(self):
+        return (f"QualityResult(size={len(self.container)}, lambda_index={self.lambda_index}, full_bytes={self.full_bytes}, sse={self.sse}, "
+                f"full_sse={self.full_sse}, min_sse={self.min_sse}, records={self.records}, full_records={self.full_records}, "
+                f"model_bits_256={self.model_bits_256})")
+
+
 def _view_parse(fn, head, buf, idx, view, parse_all):
     _, _, K, _ = container_info(buf)
     vw = _view(view)
@@ -1895,6 +1955,44 @@ class CompressionContext:
         weights = np.ascontiguousarray(weights, np.uint32).reshape(3, self.K)
         _check(self.L.mpc_budget_allocate_device(self.h, d_profile, d_counts, int(tiles), weights.ctypes.data_as(_u32p), int(j), d_depth,
                                                  d_out_counts, d_totals, stream or None))
+
+    def budget_sweep_device(self, d_profile, d_counts, tiles, weights, d_totals, stream=0):
+        """mpc_budget_sweep_device: budget_sweep on the device, one launch for all 256 multipliers; weights uint32 [3, K] in host memory;
+        d_totals[256, 3] (uint64, zeroed first).  Asynchronous."""
+        weights = np.ascontiguousarray(weights, np.uint32).reshape(3, self.K)
+        _check(self.L.mpc_budget_sweep_device(self.h, d_profile, d_counts, int(tiles), weights.ctypes.data_as(_u32p), d_totals, stream or None))
+
+    def _encode_quality(self, fn, frame, width, height, psnr, max_sse, quant, index_interval):
+        if (psnr is None) == (max_sse is None):
+            raise ValueError("exactly one of psnr and max_sse")
+        if max_sse is None:
+            max_sse = sse_for_psnr(psnr, width, height)
+        qp = None
+        if quant is not None:
+            quant = np.ascontiguousarray(quant, np.float64).reshape(3, self.K)
+            qp = quant.ctypes.data_as(_dp)
+        tiles = -(-int(width) // 8) * -(-int(height) // 8)
+        depth = np.zeros(max(tiles, 1), np.uint8)
+        out, n, index, nindex, info = _u8p(), C.c_size_t(0), _u8p(), C.c_size_t(0), MpcQualityInfo()
+        _check(fn(self.h, frame, int(width), int(height), qp, int(max_sse), -1 if index_interval is None else int(index_interval), C.byref(out),
+                  C.byref(n), C.byref(index), C.byref(nindex), depth.ctypes.data_as(_u8p), C.byref(info)))
+        blob = _take_bytes(self.L, out, n)
+        return QualityResult(blob, None if index_interval is None else _take_bytes(self.L, index, nindex), depth[:tiles], info)
+
+    def encode_image_quality(self, rgb, psnr=None, max_sse=None, quant=None, index_interval=None):
+        """mpc_encode_image_quality: the frame (uint8 [H, W, 3]) as the container of the allocation at the largest multiplier whose
+        squared error is at most the target -> QualityResult.  Exactly one target: psnr (dB; through sse_for_psnr) or max_sse.
+        index_interval: as for encode_image_budget.  MpcError(MPC_ERR_ARGUMENT) where no cut of the frame's records is that good."""
+        rgb = np.ascontiguousarray(rgb, np.uint8)
+        if rgb.ndim != 3 or rgb.shape[2] != 3:
+            raise ValueError("pixels: an HxWx3 uint8 array")
+        H, W = rgb.shape[:2]
+        return self._encode_quality(self.L.mpc_encode_image_quality, rgb.ctypes.data_as(C.c_void_p), W, H, psnr, max_sse, quant, index_interval)
+
+    def encode_image_quality_device(self, d_rgb, width, height, psnr=None, max_sse=None, quant=None, index_interval=None):
+        """The same with the frame in device memory (int from tensor.data_ptr(), tightly packed RGB)."""
+        return self._encode_quality(self.L.mpc_encode_image_quality_device, C.c_void_p(int(d_rgb)), width, height, psnr, max_sse, quant,
+                                    index_interval)
 
     def owed_tiles_device(self, d_sent, d_counts, tiles, d_flags, d_floor, d_must, d_list, d_count, stream=0):
         """mpc_owed_tiles_device: d_flags[tiles] (uint8, != 0: changed) gains the owed tiles of d_sent / d_counts; d_floor and d_must

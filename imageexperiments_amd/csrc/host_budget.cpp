@@ -1,5 +1,6 @@
 // host_budget.cpp -- product: the rate control's host definitions (host_budget.h): what mp_budget.hip's allocation kernel computes,
-// and the rate weights the search of mpc_encode_image_budget takes from the full container's seek index.
+// the rate weights the search of mpc_encode_image_budget takes from the full container's seek index, and for mpc_encode_image_quality
+// the allocation's totals at all 256 multipliers (what the sweep kernel computes) and the pick among them.
 #include "host_budget.h"
 
 #include "host_bitstream.h"
@@ -66,6 +67,53 @@ void budget_allocate(const uint32_t* profile, const uint16_t* counts, long long 
             totals[2] += static_cast<uint64_t>(kept);
         }
     }
+}
+
+void budget_sweep(const uint32_t* profile, const uint16_t* counts, long long tiles, int K, const uint32_t* weights, uint64_t totals[3 * kBudgetLambdas]) {
+    uint64_t L[kBudgetLambdas];
+    for (int j = 0; j < kBudgetLambdas; ++j) {
+        L[j] = budget_lambda(j);
+        totals[3 * j] = totals[3 * j + 1] = totals[3 * j + 2] = 0;
+    }
+    uint32_t below[3][33];                              // below[ch][m] = W[ch][0] + ... + W[ch][m - 1]
+    for (int ch = 0; ch < 3; ++ch) {
+        below[ch][0] = 0;
+        for (int i = 0; i < K; ++i) below[ch][i + 1] = below[ch][i] + weights[ch * K + i];
+    }
+    for (long long t = 0; t < tiles; ++t) {
+        // the tile's own: distortion term, rate and records kept of every depth, once for all multipliers
+        uint64_t scaled[33], rate[33], kept[33];
+        for (int n = 0; n <= K; ++n) {
+            scaled[n] = static_cast<uint64_t>(profile[t * (K + 1) + n]) << kBudgetDistortionShift;
+            rate[n] = kept[n] = 0;
+            for (int ch = 0; ch < 3; ++ch) {
+                const int count = counts[t * 3 + ch] > K ? K : counts[t * 3 + ch];
+                const int upto = n < count ? n : count;
+                rate[n] += below[ch][upto];
+                kept[n] += static_cast<uint64_t>(upto);
+            }
+        }
+        for (int j = 0; j < kBudgetLambdas; ++j) {
+            int at = 0;
+            uint64_t best = scaled[0] + L[j] * rate[0];
+            for (int n = 1; n <= K; ++n) {
+                const uint64_t J = scaled[n] + L[j] * rate[n];
+                if (J < best) {                         // the first strict minimum: the smallest n wins ties
+                    best = J;
+                    at = n;
+                }
+            }
+            totals[3 * j] += scaled[at] >> kBudgetDistortionShift;
+            totals[3 * j + 1] += rate[at];
+            totals[3 * j + 2] += kept[at];
+        }
+    }
+}
+
+int quality_pick(const uint64_t totals[3 * kBudgetLambdas], uint64_t max_sse) {
+    for (int j = kBudgetLambdas - 1; j >= 0; --j)
+        if (totals[3 * j] <= max_sse) return j;
+    return -1;
 }
 
 }  // namespace mpc

@@ -1,6 +1,8 @@
 // host_budget.h -- product: the host's definition of the rate control behind mpc_encode_image_budget (include/mpcodec.h, "budget";
-// DESIGN.md 4, "Encoder: a byte budget"): the multiplier table, the rate weights from a seek index, the allocation at one multiplier.
-// Knows neither HIP nor the C ABI and builds on its own with host_bitstream / host_container (tests/cpp/asan_budget.cpp).
+// DESIGN.md 4, "Encoder: a byte budget"): the multiplier table, the rate weights from a seek index, the allocation at one multiplier;
+// and behind mpc_encode_image_quality ("quality"): the allocation's totals at every multiplier, the pick, the squared error of a PSNR.
+// Knows neither HIP nor the C ABI and builds on its own with host_bitstream / host_container (tests/cpp/asan_budget.cpp,
+// asan_quality.cpp).
 #pragma once
 
 #include <cstddef>
@@ -30,5 +32,30 @@ int budget_weights(const uint8_t* index, size_t index_bytes, uint32_t* weights, 
 // [2] = the records kept.  depth, out_counts: each may be null.  The caller has checked: 1 <= K <= 32, 0 <= j < 256, tiles >= 0
 void budget_allocate(const uint32_t* profile, const uint16_t* counts, long long tiles, int K, const uint32_t* weights, int j, uint8_t* depth,
                      uint16_t* out_counts, uint64_t totals[3]);
+
+// ---- encode to a target quality (include/mpcodec.h, "quality"; DESIGN.md 4, "Encoder: a target quality") ----
+// The sweep: totals[3 * j + k], j = 0 ... 255, k = 0 ... 2 = what budget_allocate's totals[k] are at multiplier j for the same profile,
+// counts and weights.  It defines what mp_budget_sweep_kernel computes.  A loop of its own over tiles and multipliers that works out a
+// tile's rates once -- not 256 calls of budget_allocate, so that the two check each other.  The caller has checked what budget_allocate's has
+void budget_sweep(const uint32_t* profile, const uint16_t* counts, long long tiles, int K, const uint32_t* weights, uint64_t totals[3 * kBudgetLambdas]);
+
+// The pick: the largest j with totals[3 * j] <= max_sse, -1 if there is none.  The distortion total does not fall along the ladder
+// (L[j] rises strictly, so a tile's P at its minimiser cannot fall), which makes this the boundary a bisection would find; it is
+// defined, and computed, as the largest j
+int quality_pick(const uint64_t totals[3 * kBudgetLambdas], uint64_t max_sse);
+
+// The largest s in 0 ... limit with psnr(s) >= target, psnr a function that does not rise with s and is +inf at 0 (psnr_from_sse of
+// host_codec.h at one geometry): a binary search on that very function, so the answer agrees with it to the bit.  target: not NaN
+template <class Psnr>
+uint64_t sse_for_psnr(double target, uint64_t limit, Psnr psnr) {
+    uint64_t lo = 0, hi = limit;                        // psnr(lo) >= target always: psnr(0) = +inf
+    if (psnr(hi) >= target) return hi;
+    while (hi - lo > 1) {                               // psnr(hi) < target
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (psnr(mid) >= target) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
 
 }  // namespace mpc

@@ -5,7 +5,8 @@
 //   profile   per tile the decoder's squared error at every depth n = 0 ... K, from one replay of the records
 //   allocate  per tile the depth that minimises distortion + multiplier * rate, the cut counts and the frame's totals
 // Both are one wave per tile and bandwidth-light: the profile reads 3K record words, at most 3K dictionary rows of 64 values and
-// 192 pixel bytes per tile, the allocation K + 1 words.
+// 192 pixel bytes per tile, the allocation K + 1 words.  A third serves mpc_encode_image_quality ("quality"):
+//   sweep     the allocation's totals at all 256 multipliers in one launch, thread = multiplier
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -223,6 +224,98 @@ __global__ __launch_bounds__(64 * kAllocateWaves) void mp_budget_allocate_kernel
     }
 }
 
+// --------------------------------------------------------------------------------------------------
+// sweep: the allocation's three totals at all 256 multipliers in one launch (host_budget.h: budget_sweep), the allocation kernel turned
+// round: THREAD m = MULTIPLIER m, a workgroup of 256 threads holds the whole ladder.  L[m] = mant << shift with mant <= 15, and
+// L * R = (mant * R) << shift in u64, exactly (R < 2^27).  A workgroup takes kSweepTiles consecutive tiles at a time -- their profile
+// words are one contiguous run, loaded coalesced -- and stages per tile and depth n what does not depend on the multiplier: P * 65536,
+// R[n] from the prefix sums in LDS, and the records kept, 16 bytes an entry.  Behind the barrier every thread walks the staged tiles
+// serially, n = 0 ... K: every lane reads the same entry (an LDS broadcast), J = P * 65536 + L * R, and keeps the first strict
+// minimum -- no butterfly, and the smallest n wins ties by construction.  It adds the winner's P, R and records to three u64
+// accumulators that live in registers for the whole grid-stride loop.  At the end the 768 sums pass through LDS, so that a wave adds
+// 64 consecutive words (512 contiguous bytes) per 64-bit integer atomic: 768 atomics a workgroup, at most kSweepGridCap workgroups
+// whatever the frame.  The totals are integers and do not depend on the schedule.  Every address comes from the tile grid; a count
+// above K is used as K.
+// --------------------------------------------------------------------------------------------------
+namespace {
+struct alignas(16) SweepEntry {
+    unsigned long long scaled;          // P * 65536
+    uint32_t rate, kept;
+};
+}  // namespace
+
+__global__ __launch_bounds__(256) void mp_budget_sweep_kernel(const SweepParams p)
+{
+    __shared__ uint32_t below[3][kMaxDeviceK + 1];                  // below[ch][m] = W[ch][0] + ... + W[ch][m - 1]
+    __shared__ SweepEntry staged[kSweepTiles * (kMaxDeviceK + 1)];
+    __shared__ unsigned long long sums[3 * 256];
+    const int m = threadIdx.x;
+    const int K = p.K, depths = K + 1;
+    if (m < 3) {
+        uint32_t sum = 0;
+        below[m][0] = 0;
+        for (int i = 0; i < K; ++i) {
+            sum += p.weights[m * K + i];
+            below[m][i + 1] = sum;
+        }
+    }
+    const unsigned mant = m == 0 ? 0u : 8u + (unsigned)(m - 1) % 8u;   // L[m] = mant << shift (host_budget.h: budget_lambda)
+    const unsigned shift = m == 0 ? 0u : (unsigned)(m - 1) / 8u;
+    unsigned long long distortion = 0, rate = 0, records = 0;
+    const long long chunks = (p.tiles + kSweepTiles - 1) / kSweepTiles;
+    for (long long c = blockIdx.x; c < chunks; c += gridDim.x) {
+        const long long first = c * kSweepTiles;
+        const int here = (int)(p.tiles - first < kSweepTiles ? p.tiles - first : kSweepTiles);
+        __syncthreads();                                            // the walk before has read `staged`; the first time: `below` is built
+        for (int e = m; e < here * depths; e += 256) {
+            const int s = e / depths, n = e - s * depths;
+            const long long t = first + s;
+            uint32_t R = 0, kept = 0;
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) {
+                const int count = p.counts[t * 3 + ch];
+                const int cnt = count > K ? K : count;
+                const int upto = n < cnt ? n : cnt;
+                R += below[ch][upto];
+                kept += (uint32_t)upto;
+            }
+            SweepEntry entry;
+            entry.scaled = (unsigned long long)p.profile[first * depths + e] << 16;
+            entry.rate = R;
+            entry.kept = kept;
+            staged[e] = entry;
+        }
+        __syncthreads();
+        for (int s = 0; s < here; ++s) {
+            const SweepEntry* tile = staged + s * depths;
+            unsigned long long best = tile[0].scaled + (((unsigned long long)mant * tile[0].rate) << shift);
+            int at = 0;
+#pragma unroll 4
+            for (int n = 1; n <= K; ++n) {
+                const SweepEntry e = tile[n];
+                const unsigned long long J = e.scaled + (((unsigned long long)mant * e.rate) << shift);
+                if (J < best) {
+                    best = J;
+                    at = n;
+                }
+            }
+            const SweepEntry won = tile[at];
+            distortion += won.scaled >> 16;
+            rate += won.rate;
+            records += won.kept;
+        }
+    }
+    sums[3 * m] = distortion;
+    sums[3 * m + 1] = rate;
+    sums[3 * m + 2] = records;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const unsigned long long total = sums[k * 256 + m];
+        if (total) atomicAdd(p.totals + k * 256 + m, total);
+    }
+}
+
 int launch_depth_profile(const DictDevice& dict, const ProfileParams& p, void* stream)
 {
     if (p.K < 1 || p.K > kMaxDeviceK || p.width < 1 || p.height < 1 || p.tiles_x != (p.width + 7) / 8 || p.tiles_y != (p.height + 7) / 8)
@@ -241,6 +334,15 @@ int launch_budget_allocate(const AllocateParams& p, void* stream)
     const long long groups = (p.tiles + kAllocateWaves - 1) / kAllocateWaves;
     const unsigned blocks = (unsigned)(groups < 4096 ? groups : 4096);
     hipLaunchKernelGGL(mp_budget_allocate_kernel, dim3(blocks), dim3(64 * kAllocateWaves), 0, (hipStream_t)stream, p);
+    return (int)hipGetLastError();
+}
+
+int launch_budget_sweep(const SweepParams& p, void* stream)
+{
+    if (p.K < 1 || p.K > kMaxDeviceK || p.tiles < 1) return (int)hipErrorInvalidValue;
+    const long long chunks = (p.tiles + kSweepTiles - 1) / kSweepTiles;
+    const unsigned blocks = (unsigned)(chunks < kSweepGridCap ? chunks : kSweepGridCap);
+    hipLaunchKernelGGL(mp_budget_sweep_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
     return (int)hipGetLastError();
 }
 

@@ -9,7 +9,8 @@
 //   mp_unpack.hip    the decoder's mirror of those two: run-length expansion and DC sums of coded streams (UnpackArgs)
 //   mp_parse.hip     the entropy codes of a container undone chunk by chunk from a seek index (ParseArgs)
 //   mp_scan.hip      that seek index's checkpoints found by a scan over every bit position of a stream (ScanArgs)
-//   mp_budget.hip    rate control: a tile's squared error at every depth, the depth that minimises distortion + multiplier * rate
+//   mp_budget.hip    rate control: a tile's squared error at every depth, the depth that minimises distortion + multiplier * rate,
+//                    and that allocation's totals at all 256 multipliers in one launch
 //   mp_rate.hip      a delta stream to a byte budget: owed flags, the records gather with a cut, the allocation with a floor
 //   mp_kernels.hip   the decoder, the symbol histogram, and the product's own cross-check of the tile encoder: a STEP-SYNCHRONOUS
 //                    pursuit that correlates every row exactly (a short sequence of kernels per MP step over the active
@@ -365,6 +366,20 @@ struct AllocateParams {
     uint32_t weights[3 * kMaxDeviceK];   // [3][K]
 };
 int launch_budget_allocate(const AllocateParams& p, void* stream);
+// The allocation's totals at all 256 multipliers in one launch (host_budget.h: budget_sweep defines it):
+// totals[3 * j + 0 .. 2] += the distortion, the rate and the records kept at multiplier j (the caller zeroes the 768 words).
+// At most kSweepGridCap workgroups whatever the frame, each adding 768 totals once.  The weights travel in the kernel's arguments
+constexpr int kSweepGridCap = 512;
+constexpr int kSweepTiles = 16;          // tiles a workgroup stages at a time
+struct SweepParams {
+    const uint32_t* profile;         // [tiles][K + 1]
+    const uint16_t* counts;          // [tiles][3]
+    long long tiles;
+    int K;
+    unsigned long long* totals;      // [256][3]
+    uint32_t weights[3 * kMaxDeviceK];   // [3][K]
+};
+int launch_budget_sweep(const SweepParams& p, void* stream);
 
 // ---- a delta stream to a byte budget (mp_rate.hip; include/mpcodec.h, "rate") ----
 // The tail of launch_tile_diff alone (mp_delta.hip): list[0 .. *count) = the tiles whose flag byte is not 0, ascending.  block_live:

@@ -13,7 +13,8 @@
 //   mpcodec_debug.cpp      the tests' entry points to the screen's tables (mpc_debug_*, mpc_filter_tiles)
 //   mpcodec_delta.cpp      the delta encoder (mpc_delta_*): diff against the kept frame, pursuit of the changed tiles only
 //   mpcodec_patch.cpp      the delta stream's patches (mpc_patch_*): the format's entry points (host_patch.h) and the receiver session
-//   mpcodec_budget.cpp     encode to a byte budget (mpc_encode_image_budget): depth profile, allocation, the search over the multiplier
+//   mpcodec_budget.cpp     encode to a byte budget (mpc_encode_image_budget): depth profile, allocation, the search over the multiplier;
+//                          encode to a target quality (mpc_encode_image_quality): the sweep over all multipliers, the pick, one allocation
 //   mpcodec_rate.cpp       a delta stream to a byte budget (mpc_delta_encode_patch_budget): the sent map, candidates, the search with floors
 #pragma once
 

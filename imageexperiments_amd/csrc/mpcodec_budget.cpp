@@ -1,8 +1,12 @@
 // mpcodec_budget.cpp -- product: encode to a byte budget (include/mpcodec.h, "budget"; DESIGN.md 4, "Encoder: a byte budget").
 // One pursuit, the full container with its seek index, the depth profile (mp_budget.hip), then a bisection over the multiplier
 // table: every probe is the allocation kernel and one records-to-container job on the same records with the cut counts array.
+// And encode to a target quality ("quality"; DESIGN.md 4, "Encoder: a target quality"): the same start, then the sweep kernel's totals
+// at all 256 multipliers, the pick on the host, one allocation and one more container job.
+#include <cmath>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "host_budget.h"
 #include "host_codec.h"
@@ -208,6 +212,158 @@ mpc_status encode_budget(mpc_context* c, const uint8_t* rgb, bool on_device, int
     });
 }
 
+// d_totals[768] zeroed on `s`, then the kernel
+mpc_status sweep_on_device(const mpc_context* c, const uint32_t* d_profile, const uint16_t* d_counts, long long tiles, const uint32_t* weights,
+                           unsigned long long* d_totals, hipStream_t s) {
+    HIP_TRY(hipMemsetAsync(d_totals, 0, 3 * mpc::kBudgetLambdas * sizeof(unsigned long long), s));
+    mpc::SweepParams p{};
+    p.profile = d_profile;
+    p.counts = d_counts;
+    p.tiles = tiles;
+    p.K = c->K;
+    p.totals = d_totals;
+    std::memcpy(p.weights, weights, sizeof(uint32_t) * 3 * static_cast<size_t>(c->K));
+    const int err = mpc::launch_budget_sweep(p, s);
+    if (err != 0) return launch_failed(err);
+    return MPC_OK;
+}
+
+// mpc_encode_image_quality.  Steps 1 to 3 are encode_budget's and are written out again here, not shared: that function's order of
+// enqueues, its early return of the full container and its staging layout stay exactly what they were
+mpc_status encode_quality(mpc_context* c, const uint8_t* rgb, bool on_device, int width, int height, const double* quant, unsigned long long max_sse,
+                          int index_interval, uint8_t** bytes, size_t* nbytes, uint8_t** index, size_t* index_bytes, uint8_t* depth,
+                          mpc_quality_info* info) {
+    return guarded([&]() -> mpc_status {
+        if (!c || !rgb || !bytes || !nbytes || !info) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (index_interval >= 0 && (!index || !index_bytes)) return fail(MPC_ERR_ARGUMENT, "null argument");
+        long long tiles = 0;
+        if (const mpc_status gs = geometry(width, height, &tiles); gs != MPC_OK) return gs;
+        if (index_interval > 0 && (index_interval < static_cast<int>(mpc::kIndexIntervalMin) || index_interval > static_cast<int>(mpc::kIndexIntervalMax)))
+            return fail(MPC_ERR_ARGUMENT, "interval %d: 0 or %u to %u", index_interval, mpc::kIndexIntervalMin, mpc::kIndexIntervalMax);
+        const unsigned every = index_interval < 0 ? 0u : index_interval ? static_cast<unsigned>(index_interval) : mpc::kIndexIntervalDefault;
+        if (c->device < 0) return no_device();
+        std::lock_guard<std::recursive_mutex> one_host_call(c->host_calls);
+        for (int k = 0; k < mpc_context::kSeqSlots; ++k)
+            if (c->jobs[k] && c->jobs[k]->stage != 0) return fail(MPC_ERR_ARGUMENT, "container job slot %d is busy", k);
+        *bytes = nullptr;
+        *nbytes = 0;
+        if (index) *index = nullptr;
+        if (index_bytes) *index_bytes = 0;
+        *info = mpc_quality_info{};
+        mpc_quality_info got{};                                     // the caller's only on success
+        HIP_TRY(hipSetDevice(c->device));
+        const Tuning tuning = read_tuning();
+        const int K = c->K, tiles_y = (height + 7) / 8;
+        const size_t n_tc = 3 * static_cast<size_t>(tiles), row = 3 * static_cast<size_t>(width);
+        if (!c->budget_stream) HIP_TRY(hipStreamCreateWithFlags(&c->budget_stream, hipStreamNonBlocking));
+        hipStream_t s = c->budget_stream;
+        struct Drain {                                              // whatever happens, nothing of this call is left running
+            hipStream_t s;
+            ~Drain() { (void)hipStreamSynchronize(s); }
+        } drain{s};
+        uint8_t* d_frame = nullptr;
+        uint16_t* d_counts = nullptr;
+        uint16_t* d_cut = nullptr;
+        mpc_basis_choice* d_choices = nullptr;
+        uint32_t* d_profile = nullptr;
+        uint8_t* d_depth = nullptr;
+        unsigned long long* d_sweep = nullptr;                      // the sweep's 768 totals
+        unsigned long long* d_words = nullptr;                      // the allocation's three totals, the full frame's SSE
+        int* d_error = nullptr;
+        const auto layout = [&](char* base) {
+            Carve cv{base};
+            d_frame = cv.take<uint8_t>(on_device ? 0 : row * static_cast<size_t>(height));
+            d_counts = cv.take<uint16_t>(n_tc + 2);
+            d_cut = cv.take<uint16_t>(n_tc + 2);
+            d_choices = cv.take<mpc_basis_choice>(n_tc * static_cast<size_t>(K));
+            d_profile = cv.take<uint32_t>(static_cast<size_t>(tiles) * (static_cast<size_t>(K) + 1));
+            d_depth = cv.take<uint8_t>(static_cast<size_t>(tiles));
+            d_sweep = cv.take<unsigned long long>(3 * mpc::kBudgetLambdas);
+            d_words = cv.take<unsigned long long>(4);
+            d_error = cv.take<int>(1);
+            return cv.at;
+        };
+        if (const mpc_status gs = c->budget_dev.reserve(layout(nullptr), "quality staging"); gs != MPC_OK) return gs;
+        layout(c->budget_dev.data());
+        const uint8_t* frame = rgb;
+        if (!on_device) {
+            HIP_TRY(hipMemcpyAsync(d_frame, rgb, row * static_cast<size_t>(height), hipMemcpyHostToDevice, s));
+            frame = d_frame;
+        }
+        HIP_TRY(hipMemsetAsync(d_words, 0, 4 * sizeof(unsigned long long), s));
+        HIP_TRY(hipMemsetAsync(d_error, 0, sizeof(int), s));
+        // 1. one pursuit of the whole frame, the records kept; the full frame's SSE behind it
+        if (const mpc_status es = mpc_encode_tiles_device(c, frame, width, height, row, 0, tiles_y, quant, d_counts, d_choices, nullptr, nullptr, 0, s);
+            es != MPC_OK)
+            return es;
+        if (const mpc_status ds = mpc_distortion_device(c, d_counts, d_choices, quant, frame, width, height, d_words + 3, nullptr, s); ds != MPC_OK)
+            return ds;
+        // 2. the full container with its seek index
+        ContainerMade full;
+        if (const mpc_status fs = records_container(c, tuning, s, d_counts, d_choices, tiles, width, height, quant, every ? every : mpc::kIndexIntervalDefault, &full);
+            fs != MPC_OK)
+            return fs;
+        mpc::ContainerIndex full_index;
+        if (!mpc::read_container_index(full.index.data(), full.index.size(), full_index) || full_index.streams.size() != 1 + 6 * static_cast<size_t>(K))
+            return fail(MPC_ERR_HIP, "the full container's seek index does not read back");
+        for (int ch = 0; ch < 3; ++ch)
+            for (int i = 0; i < K; ++i) got.full_records += full_index.streams[1 + 2 * static_cast<size_t>(K) * ch + 2 * static_cast<size_t>(i)].expect;
+        got.full_bytes = full.nbytes;
+        // 3. the weights from its index, the profile once
+        uint32_t weights[3 * MPC_MAX_K];
+        const int verdict = mpc::budget_weights(full.index.data(), full.index.size(), weights);
+        if (verdict == 2) return fail(MPC_ERR_ARGUMENT, "the full container's seek index is serial only: no stream sizes to weigh the steps with");
+        if (verdict != 0) return fail(MPC_ERR_HIP, "the full container's seek index does not read back");
+        if (const mpc_status ps = profile_on_device(c, d_counts, d_choices, quant, frame, width, height, d_profile, d_error, s); ps != MPC_OK) return ps;
+        // 4. the sweep: one launch for all 256 multipliers, its totals to the host
+        if (const mpc_status ss = sweep_on_device(c, d_profile, d_counts, tiles, weights, d_sweep, s); ss != MPC_OK) return ss;
+        std::vector<unsigned long long> totals(3 * mpc::kBudgetLambdas);
+        unsigned long long full_sse = 0;
+        int error_word = 0;
+        HIP_TRY(hipMemcpyAsync(totals.data(), d_sweep, totals.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(&full_sse, d_words + 3, sizeof(full_sse), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(&error_word, d_error, sizeof(int), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (error_word) return fail(MPC_ERR_BITSTREAM, "Invalid bitstream");
+        got.full_sse = full_sse;
+        got.min_sse = totals[0];
+        // 5. the largest multiplier whose distortion is within the target
+        static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the totals are u64");
+        const int j = mpc::quality_pick(reinterpret_cast<const uint64_t*>(totals.data()), max_sse);
+        // 6. no cut is that good
+        if (j < 0)
+            return fail(MPC_ERR_ARGUMENT, "a squared error of at most %llu: the best that cutting this frame's records reaches is %llu", max_sse, totals[0]);
+        // 7. the allocation at j
+        if (const mpc_status as = allocate_on_device(c, d_profile, d_counts, tiles, weights, j, d_depth, d_cut, d_words, s); as != MPC_OK) return as;
+        // 8. its container, the index with it if asked for
+        ContainerMade made;
+        if (const mpc_status cs = records_container(c, tuning, s, d_cut, d_choices, tiles, width, height, quant, every, &made); cs != MPC_OK) return cs;
+        unsigned long long at_j[3] = {0, 0, 0};
+        HIP_TRY(hipMemcpyAsync(at_j, d_words, sizeof(at_j), hipMemcpyDeviceToHost, s));
+        if (depth) HIP_TRY(hipMemcpyAsync(depth, d_depth, static_cast<size_t>(tiles), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (std::memcmp(at_j, totals.data() + 3 * static_cast<size_t>(j), sizeof(at_j)) != 0)
+            return fail(MPC_ERR_HIP, "the allocation at multiplier %d does not give the sweep's totals", j);
+        got.lambda_index = j;
+        got.sse = at_j[0];
+        got.model_bits_256 = at_j[1];
+        got.records = at_j[2];
+        // 9. returned
+        if (every) {
+            uint8_t* copy = made.index.empty() ? nullptr : static_cast<uint8_t*>(std::malloc(made.index.size()));
+            if (!copy) return fail(MPC_ERR_ALLOC, "no seek index");
+            std::memcpy(copy, made.index.data(), made.index.size());
+            *index = copy;
+            *index_bytes = made.index.size();
+        }
+        *bytes = made.bytes;
+        *nbytes = made.nbytes;
+        made.bytes = nullptr;
+        *info = got;
+        return MPC_OK;
+    });
+}
+
 }  // namespace
 
 mpc_status profile_on_device(mpc_context* c, const uint16_t* d_counts, const mpc_basis_choice* d_choices, const double* quant,
@@ -295,6 +451,53 @@ mpc_status mpc_encode_image_budget_device(mpc_context* c, const uint8_t* d_rgb, 
                                           int index_interval, uint8_t** bytes, size_t* nbytes, uint8_t** index, size_t* index_bytes, uint8_t* depth,
                                           mpc_budget_info* info) {
     return encode_budget(c, d_rgb, true, width, height, quant, budget, index_interval, bytes, nbytes, index, index_bytes, depth, info);
+}
+
+mpc_status mpc_budget_sweep(const uint32_t* profile, const uint16_t* counts, long long tiles, int K, const uint32_t* weights, uint64_t* totals) {
+    return guarded([&]() -> mpc_status {
+        if (!profile || !counts || !weights || !totals) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (tiles < 0 || K < 1 || K > MPC_MAX_K) return fail(MPC_ERR_ARGUMENT, "tiles %lld, K %d", tiles, K);
+        mpc::budget_sweep(profile, counts, tiles, K, weights, totals);
+        return MPC_OK;
+    });
+}
+
+int mpc_quality_pick(const uint64_t* totals, uint64_t max_sse) { return totals ? mpc::quality_pick(totals, max_sse) : -1; }
+
+mpc_status mpc_sse_for_psnr(double psnr, int width, int height, uint64_t* max_sse) {
+    return guarded([&]() -> mpc_status {
+        if (!max_sse) return fail(MPC_ERR_ARGUMENT, "null argument");
+        long long tiles = 0;
+        if (const mpc_status gs = geometry(width, height, &tiles); gs != MPC_OK) return gs;
+        if (std::isnan(psnr) || (std::isinf(psnr) && psnr < 0)) return fail(MPC_ERR_ARGUMENT, "a PSNR of %g", psnr);
+        const uint64_t limit = uint64_t{195075} * 64 * static_cast<uint64_t>(tiles);                                     // 3 * 255^2 a pixel
+        *max_sse = mpc::sse_for_psnr(psnr, limit, [&](uint64_t s) { return mpc::psnr_from_sse(static_cast<double>(s), width, height); });
+        return MPC_OK;
+    });
+}
+
+mpc_status mpc_budget_sweep_device(mpc_context* c, const uint32_t* d_profile, const uint16_t* d_counts, long long tiles, const uint32_t* weights,
+                                   unsigned long long* d_totals, void* stream) {
+    return guarded([&]() -> mpc_status {
+        if (!c || !d_profile || !d_counts || !weights || !d_totals) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (c->device < 0) return no_device();
+        if (tiles < 1 || tiles * 3 >= (1LL << 31)) return fail(MPC_ERR_ARGUMENT, "tiles %lld", tiles);
+        HIP_TRY(hipSetDevice(c->device));
+        if (const mpc_status cs = refuse_capture(stream); cs != MPC_OK) return cs;
+        return sweep_on_device(c, d_profile, d_counts, tiles, weights, d_totals, static_cast<hipStream_t>(stream));
+    });
+}
+
+mpc_status mpc_encode_image_quality(mpc_context* c, const uint8_t* rgb, int width, int height, const double* quant, unsigned long long max_sse,
+                                    int index_interval, uint8_t** bytes, size_t* nbytes, uint8_t** index, size_t* index_bytes, uint8_t* depth,
+                                    mpc_quality_info* info) {
+    return encode_quality(c, rgb, false, width, height, quant, max_sse, index_interval, bytes, nbytes, index, index_bytes, depth, info);
+}
+
+mpc_status mpc_encode_image_quality_device(mpc_context* c, const uint8_t* d_rgb, int width, int height, const double* quant,
+                                           unsigned long long max_sse, int index_interval, uint8_t** bytes, size_t* nbytes, uint8_t** index,
+                                           size_t* index_bytes, uint8_t* depth, mpc_quality_info* info) {
+    return encode_quality(c, d_rgb, true, width, height, quant, max_sse, index_interval, bytes, nbytes, index, index_bytes, depth, info);
 }
 
 }  // extern "C"

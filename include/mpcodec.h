@@ -1102,6 +1102,77 @@ mpc_status mpc_encode_image_budget_device(mpc_context* ctx, const uint8_t* d_rgb
                                           int index_interval, uint8_t** bytes, size_t* nbytes, uint8_t** index, size_t* index_bytes,
                                           uint8_t* depth, mpc_budget_info* info);
 
+/* ---- quality: encode to a target quality ("Encoder: a target quality") ----
+ * The budget section turned round: not "the best frame in N bytes" but "the smallest container whose decode is at least this good".
+ * Distortion, unlike a size, needs no container to be known: the squared error of a cut is the sum of the depth profile at the chosen
+ * depths, exactly.  So the search makes no probe: one kernel evaluates the allocation at all 256 multipliers, the host picks one from
+ * 256 x 3 integers, and one allocation and one container job finish the call.  Everything named here (P, W, R, L[j], J, the allocation
+ * at j and its totals) is the budget section's.  Host and device agree bit for bit.
+ *
+ * SWEEP  S[j][k], j = 0 ... 255, k = 0 ... 2, u64 at totals[3 * j + k]: exactly the totals[k] that mpc_budget_allocate returns at
+ * multiplier j for the same profile, counts and weights -- S[j][0] the distortion, S[j][1] the rate in 1/256 bit, S[j][2] the records
+ * kept.  A count above K is used as K; the smallest n wins on ties.  Weights as mpc_budget_weights makes them (256 ... 2^20).
+ * L[j] rises strictly with j, so S[j][0] never falls and S[j][1] never rises along the ladder, also for a profile that is not monotone
+ * in depth (for one tile, add the optimality inequalities of the minimisers at two multipliers).  S[0][0] is the sum of every tile's
+ * least profile entry: the best quality cutting can reach; it can lie below the full container's squared error.
+ * PICK at max_sse: the largest j with S[j][0] <= max_sse, -1 if there is none.
+ *
+ * mpc_budget_sweep: the sweep on the host; it defines what the kernel computes.  totals[768].  It refuses what mpc_budget_allocate
+ * refuses: MPC_ERR_ARGUMENT for a null pointer, tiles < 0, K outside 1 ... 32.
+ * mpc_quality_pick: the pick among totals[768]; -1 also for totals == NULL.
+ * mpc_sse_for_psnr: *max_sse = the largest integer s in 0 ... 195075 * 64 * tiles (tiles of 8 x 8 of the geometry) whose PSNR at
+ * width x height -- mpc_psnr's formula, 20 log10(765) - 10 log10(s / (width * height)) -- is >= psnr: found by a binary search on
+ * that very function, so it agrees with mpc_psnr and mpc_rate_distortion to the bit.  s = 0 has PSNR +inf, so every target has an
+ * answer: +inf gives 0.  MPC_ERR_ARGUMENT: NaN, -inf, a null pointer, a geometry outside mpc_rate_distortion's.
+ * The three are host only, need no context and are safe on several threads.
+ *
+ * mpc_budget_sweep_device: the sweep of `tiles` tiles (K the context's) with weights[3K] in HOST memory (they travel in the kernel's
+ * arguments) into d_totals[768] (u64; zeroed on `stream` first): one launch for all 256 multipliers.  Asynchronous on `stream`.
+ * mpc_budget_allocate_device's refusals, with nothing enqueued: MPC_ERR_ARGUMENT for a null pointer, tiles outside
+ * mpc_rate_distortion's geometry, a stream that is being captured; MPC_ERR_NO_DEVICE for a host-only context.
+ *
+ * mpc_encode_image_quality[_device]: the frame (host: 3 * width bytes a row; _device: device memory, tightly packed) as the container
+ * of the allocation at the largest multiplier whose squared error is at most max_sse.  Synchronous.
+ *   1. the whole frame is pursued once; the records stay on the device
+ *   2. the full container F with its seek index is made on job slot 0, as in the budget encode
+ *   3. the weights are taken from F's index and the depth profile is made, once
+ *   4. the sweep: one launch; the 768 totals go to the host
+ *   5. j = the pick at max_sse
+ *   6. j = -1: MPC_ERR_ARGUMENT, max_sse and S[0][0] in the text
+ *   7. the allocation kernel at j
+ *   8. one container job on the same records with the cut counts, and with it the index if asked for
+ *   9. that container is returned
+ * Two container jobs, no per-multiplier launch, and no early return of F: a target looser than F's own squared error still yields the
+ * cut at the pick, which keeps no more records than F and as a rule far fewer.  What the result promises: info->sse <= max_sse, and j is the largest multiplier of the
+ * ladder for which that holds.  The returned length is whatever the entropy coder makes of that allocation: the rate model is an
+ * average per stream, so the byte count is NOT promised minimal, nor monotone in max_sse.  max_sse = 0 is a valid request: a lossless
+ * result, or the refusal of step 6.
+ * quant, index_interval, *index, depth: as for mpc_encode_image_budget (*index byte for byte mpc_container_index2(*bytes, ..., interval,
+ * MPC_INDEX_EXPANDED) of the returned container).  info: lambda_index = j; full_bytes = |F|; sse = S[j][0], what mpc_decode_image of the
+ * result differs from the frame by, exactly; full_sse that of F; min_sse = S[0][0]; records = S[j][2] and full_records those of F;
+ * model_bits_256 = S[j][1].
+ * Refusals and side effects are the budget encode's: refused with nothing enqueued, MPC_ERR_ARGUMENT for a null pointer (`index` and
+ * `index_bytes` only with index_interval >= 0), a geometry outside mpc_rate_distortion's, an interval outside the rules, a container
+ * job slot that is not idle; MPC_ERR_NO_DEVICE for a host-only context.  On failure nothing is returned, the slots are idle and the
+ * context is usable.  The call leaves the context's quant tables, fast flag and workgroup limit as it found them. */
+typedef struct mpc_quality_info {
+    int lambda_index;
+    size_t full_bytes;
+    unsigned long long sse, full_sse, min_sse, records, full_records, model_bits_256;
+} mpc_quality_info;
+mpc_status mpc_budget_sweep(const uint32_t* profile, const uint16_t* counts, long long tiles, int K, const uint32_t* weights,
+                            uint64_t* totals /* [256 * 3] */);
+int mpc_quality_pick(const uint64_t* totals /* [256 * 3] */, uint64_t max_sse);
+mpc_status mpc_sse_for_psnr(double psnr, int width, int height, uint64_t* max_sse);
+mpc_status mpc_budget_sweep_device(mpc_context* ctx, const uint32_t* d_profile, const uint16_t* d_counts, long long tiles,
+                                   const uint32_t* weights /* host, [3K] */, unsigned long long* d_totals /* [768] */, void* stream);
+mpc_status mpc_encode_image_quality(mpc_context* ctx, const uint8_t* rgb, int width, int height, const double* quant,
+                                    unsigned long long max_sse, int index_interval, uint8_t** bytes, size_t* nbytes, uint8_t** index,
+                                    size_t* index_bytes, uint8_t* depth, mpc_quality_info* info);
+mpc_status mpc_encode_image_quality_device(mpc_context* ctx, const uint8_t* d_rgb, int width, int height, const double* quant,
+                                           unsigned long long max_sse, int index_interval, uint8_t** bytes, size_t* nbytes,
+                                           uint8_t** index, size_t* index_bytes, uint8_t* depth, mpc_quality_info* info);
+
 /* ---- rate: a delta stream to a byte budget ("Delta stream to a byte budget") ----
  * A patch is as large as the scene makes it; a link has a byte rate.  A sender that cuts patches to a budget must know what the
  * receiver holds of each tile, and may refine a thin tile later.  These are the pieces of that sender: the state (a depth per tile),
