@@ -194,6 +194,11 @@ def _bind_debug(L):
     L.mpc_debug_copy_filter_tiles.argtypes = [vp, C.c_int, C.c_int, _u16p]
     L.mpc_filter_tiles.argtypes = [_dp, C.c_int, C.c_int, C.c_int, _u16p, _u8p]
     L.mpc_debug_screen_probe_device.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp]
+    try:
+        L.mpc_debug_track_probe_device.argtypes = [vp, vp, vp, C.c_float, C.c_int, C.c_int, vp, vp]
+    except AttributeError:
+        if not os.environ.get("MPCODEC_LIB"):             # an older build may be loaded for A/B timing only
+            raise
 
 
 def _bind_bitstream(L):
@@ -2233,6 +2238,12 @@ class CompressionContext:
         """mpc_debug_screen_probe_device: d_vectors[n,64] f64 -> d_approx[n,576] f32 (base rows 0..511, block rows 0..63), d_bound[n]."""
         _check(self.L.mpc_debug_screen_probe_device(self.h, int(channel), int(block), d_vectors or None, int(n), d_approx or None,
                                                     d_bound or None, stream or None))
+
+    def debug_track_probe_device(self, d_row_bits, d_pair_bits, bound, rows, pair, d_out, stream=0):
+        """mpc_debug_track_probe_device: d_row_bits[64,144] u32, d_pair_bits[64,16] u32 -> d_out[64,14] u32: the keys of the kernel's
+        tracking, by the definition and grouped (base, block, pair with the largest |P|)."""
+        _check(self.L.mpc_debug_track_probe_device(self.h, d_row_bits or None, d_pair_bits or None, float(bound), int(rows), int(pair),
+                                                   d_out or None, stream or None))
 
     def calc_mp(self, channel, vectors, quant_k=None):
         """matching::CalcMPDynamic (MatchingPursuit.h:22) on the device for vectors[n,64].

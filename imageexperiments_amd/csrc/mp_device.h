@@ -229,6 +229,9 @@ int launch_gram(const double* base, const double* detail, const int32_t* block_r
 // block_tiles; approx[n][576], bound[n].  vectors and approx 16-byte aligned.
 int launch_screen_probe(const uint16_t* base_tiles, const uint16_t* block_tiles, const double* vectors, int n, float* approx, float* bound,
                         void* stream);
+// The tests' probe of the key tracking (see mp_pursuit.hip): one wave; row_bits[64][144], pair_bits[64][16] (both 16-byte aligned),
+// out[64][14].
+int launch_track_probe(const unsigned* row_bits, const unsigned* pair_bits, float E, int rows, int pair, unsigned* out, void* stream);
 
 // ---- device-side stream assembly (mp_streams.hip) ----
 struct StreamArgs {

@@ -55,6 +55,20 @@ constexpr float kHuge = 1.0e30f;                 // beyond this the f32 side may
 // packed rounds (8b) a wave-step no longer pays for its oldest slot's pair list; measured again: 4 is 1.2 % faster than 16 on the
 // synthetic frame and 2.4 % slower on the natural one, 8 the other way round: 16 stays.
 constexpr int kRefillAt = MPC_REFILL_AT;
+// Measurement switches of DESIGN.md 9 (profiles/track_keys.txt); the defaults are the product.
+//   MPC_GROUPED_TRACK 1: TopKeys::see4 in nine instructions; 0: four sequential see(), twelve.
+//   MPC_TOUCH_WAIT: the cache touch of a new pair's filter tiles in phase (9), an LDS-DMA load into a landing zone nobody reads, and
+//   where vector memory is waited for.  0: touch, no explicit wait (an LDS-DMA load writes LDS, so the compiler then puts
+//   s_waitcnt vmcnt(0) in front of the first LDS read of every path behind it: in pass 1's tile loop); 1: touch, waited for behind
+//   phase (2a); 2: touch, waited for at the top of the step; 3: no touch, no explicit wait (the double kernel's tile loop keeps a
+//   vmcnt(0) all the same); 4: no touch, the wait behind (2a) -- no vmcnt in the tile loop.  3 and 4 are 8 % (synthetic frame) and
+//   11 % (natural) faster than 0, 1 and 2, which lie within 0.5 % of each other; 4 is level with 3 or just ahead of it.
+#ifndef MPC_GROUPED_TRACK
+#define MPC_GROUPED_TRACK 1
+#endif
+#ifndef MPC_TOUCH_WAIT
+#define MPC_TOUCH_WAIT 4
+#endif
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
@@ -169,7 +183,8 @@ __device__ __forceinline__ T chain_sum(const T (&term)[16], int h)
 }
 
 // The two largest approximations a lane has seen, as KEYS: the value's bits with the low mantissa bits replaced by a code
-// that names the row (so one v_and_or + two v_med3 track value and row together, and the runner-up's row is known as well).
+// that names the row (so one v_and_or_b32 and, grouped by four, 5/4 max3 / med3 track value and row together, and the runner-up's
+// row is known as well).
 // A key read as a float is >= the truncated value and < value * (1 + 2^-(23 - bits)): callers widen their thresholds by that.
 // Values are finite and >= 0 (callers divert NaN / infinity / overflow before relying on it), so float order = key order.
 struct TopKeys {
@@ -182,6 +197,33 @@ struct TopKeys {
         const unsigned k1b = __float_as_uint(k1);
         k1 = __uint_as_float(k1b > key ? k1b : key);
     }
+    // Four values at once, to the same (k1, k2) bit for bit as four see() in any order: the top two of {k1, k2, a, b} with
+    // k1 >= k2 are max3(k1, a, b) and max(k2, med3(k1, a, b)) -- no sequential update.  Twice, with the two runners-up joining k2
+    // in one max3: 4 v_and_or_b32 + v_max3_u32, v_med3_f32, v_max3_u32, v_med3_f32, v_max3_u32 = 9 instructions where four
+    // see() take 12.  (Keys are non-negative and finite, so the float median is the integer median.)
+    // kGrouped = false is the definition: four see().  The tests' probe (mp_track_probe_kernel) runs both.
+    template <bool kGrouped = MPC_GROUPED_TRACK != 0>
+    __device__ __forceinline__ void see4(const unsigned (&value_bits)[4], unsigned keep_mask, const unsigned (&code)[4])
+    {
+        if constexpr (kGrouped) {
+            const unsigned a = (value_bits[0] & keep_mask) | code[0], b = (value_bits[1] & keep_mask) | code[1];
+            const unsigned c = (value_bits[2] & keep_mask) | code[2], d = (value_bits[3] & keep_mask) | code[3];
+            const unsigned m1 = umax3(__float_as_uint(k1), a, b);
+            const float s1 = __builtin_amdgcn_fmed3f(k1, __uint_as_float(a), __uint_as_float(b));
+            const unsigned m2 = umax3(m1, c, d);
+            const float s2 = __builtin_amdgcn_fmed3f(__uint_as_float(m1), __uint_as_float(c), __uint_as_float(d));
+            k1 = __uint_as_float(m2);
+            k2 = __uint_as_float(umax3(__float_as_uint(k2), __float_as_uint(s1), __float_as_uint(s2)));
+        } else {
+#pragma unroll
+            for (int v = 0; v < 4; ++v) see(value_bits[v], keep_mask, code[v]);
+        }
+    }
+    static __device__ __forceinline__ unsigned umax3(unsigned x, unsigned y, unsigned z)
+    {
+        const unsigned xy = x > y ? x : y;
+        return xy > z ? xy : z;
+    }
 };
 // The mask of a key lives in a VECTOR register: v_and_or_b32 may read one scalar operand only (the code: an inline constant or a counter), so a
 // scalar or literal mask would split every key into v_and + v_or -- one more VALU instruction per tracked value.
@@ -191,8 +233,58 @@ __device__ __forceinline__ unsigned in_vgpr(unsigned x)
     asm volatile("v_mov_b32 %0, %1" : "=v"(v) : "s"(x));
     return v;
 }
-constexpr unsigned kKeepRow = 0x7FFFFF80u;        // |value| with 7 code bits: tile (5) and row within the lane's four (2)
+__device__ __forceinline__ float fmax3(float x, float y, float z) { return __builtin_fmaxf(__builtin_fmaxf(x, y), z); }
+constexpr unsigned kKeepRow = 0x7FFFFF80u;       // |value| with 7 code bits: tile (5) and row within the lane's four (2)
 constexpr unsigned kKeepPair = 0x7FFFFE00u;      // |value| with 9 code bits: pair (5), tile (2), row (2)
+
+// One tile's four approximations of a lane (rows 16 tile + 4 h + v) tracked as row keys; code0 = 4 * tile, wave-uniform: the four
+// codes go through scalar registers so that each key is one v_and_or_b32 (vector value, vector mask, scalar code).
+template <bool kGrouped = MPC_GROUPED_TRACK != 0>
+__device__ __forceinline__ void track_tile(TopKeys& top, const f32x4& val, unsigned keep_row_mask, unsigned code0)
+{
+    unsigned code[4], bits[4];
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+        code[v] = (unsigned)__builtin_amdgcn_readfirstlane((int)(code0 + v));
+        asm("" : "+s"(code[v]));                                    // opaque: or else code0 | v is pulled apart into v_and_b32 + v_or3_b32
+        bits[v] = __float_as_uint(val[v]);
+    }
+    top.see4<kGrouped>(bits, keep_row_mask, code);
+}
+
+// Upper-bound keys |P_b| + E of the 16 rows a lane holds of one pair (tile t, row v of its four: code_of(t, v) names them), tracked
+// into `top`; `biggest` = the largest |P_b| among them (the pair's lower bound is biggest - E), two values per v_max3_f32.
+template <bool kGrouped = MPC_GROUPED_TRACK != 0, class CodeOf>
+__device__ __forceinline__ void pair_keys(int h, int rows, const float4 (&pv)[4], float E, unsigned keep_pair_mask, CodeOf code_of,
+                                          TopKeys& top, float& biggest)
+{
+    // rows 62 and 63 of a block can be pads (blocks have 62 or 63 rows): lane row h = 3, tile 3, v = 2, 3.  Their P and G
+    // are exactly 0; their upper bound must be 0 too (not E), or a pad could pass for a survivor.
+    const bool pad2 = h == 3 && rows < 63, pad3 = h == 3 && rows < 64;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const float vals[4] = {pv[t].x, pv[t].y, pv[t].z, pv[t].w};
+        unsigned code[4], bits[4];
+        float m[4];
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            m[v] = fabsf(vals[v]);
+            float ub = m[v] + E;
+            if (t == 3 && v == 2) ub = pad2 ? 0.0f : ub;
+            if (t == 3 && v == 3) ub = pad3 ? 0.0f : ub;
+            bits[v] = __float_as_uint(ub);
+            code[v] = code_of(t, v);
+        }
+        top.see4<kGrouped>(bits, keep_pair_mask, code);
+        if constexpr (kGrouped) {
+            biggest = fmax3(biggest, m[0], m[1]);
+            biggest = fmax3(biggest, m[2], m[3]);
+        } else {
+#pragma unroll
+            for (int v = 0; v < 4; ++v) biggest = __builtin_amdgcn_fmed3f(biggest, m[v], __builtin_inff());
+        }
+    }
+}
 
 // Survivors of one lane waiting for their exact evaluation.  code = segment << 16 | pair << 11 | row; segment 0 = base
 // rows, 1 = DetailBasis[0], 2 = pair.  More than four on one lane: the tile-channel falls back to evaluating every row.
@@ -352,7 +444,9 @@ __global__ __launch_bounds__(64 * kWaves, kWaves / 4) void mp_pursuit_kernel(con
 #endif
     __shared__ uint4 s_tiles[kTilesLds * 256];                      // [tile][operand q][lane], 4 KiB per tile
     __shared__ int s_rows[512], s_rowoff[512];                      // block_rows / block_row_off
+#if MPC_TOUCH_WAIT < 3
     __shared__ unsigned s_touch[64 * kWaves];                       // landing zone of the cache-touch loads (never read)
+#endif
     __shared__ double s_quant[3][kMaxDeviceK];                      // the quantisers (steps differ per lane, channels per wave)
     // Tiles 0 .. 31 (base rows) serve every channel; tiles 32 .. 35 hold DetailBasis[0] of ONE channel, the workgroup's "home".
     // A wave whose channel is not the home reads those four tiles from memory instead (16 KiB per step, L2-resident).  The last
@@ -410,7 +504,9 @@ __global__ __launch_bounds__(64 * kWaves, kWaves / 4) void mp_pursuit_kernel(con
     float* const my_p = a.pair_p + wave_global * (kGroups * 16 * kMaxPairs * 64);
     unsigned* const my_meta = a.pair_meta + wave_global * (kGroups * 16 * kMaxPairs * 2);
     float* const my_e = a.pair_e + wave_global * (kGroups * 16 * kMaxPairs);
+#if MPC_TOUCH_WAIT < 3
     unsigned* const my_touch = s_touch + 64 * wave;
+#endif
     const int K = a.K;
 
     const unsigned keep_row_mask = in_vgpr(kKeepRow), keep_pair_mask = in_vgpr(kKeepPair);
@@ -451,34 +547,13 @@ __global__ __launch_bounds__(64 * kWaves, kWaves / 4) void mp_pursuit_kernel(con
     float rbound[kGroups];
 #pragma unroll
     for (int g = 0; g < kGroups; ++g) { lbmax[g] = -3.0e38f; oddp[g] = false; rbound[g] = 0.0f; }
-    // Upper-bound keys |P_b| + E of the 16 rows a lane holds of one pair (tile t, row v of its four: code_of(t, v) names them), tracked
-    // into `top`; `biggest` = the largest |P_b| among them (the pair's lower bound is biggest - E).
-    auto pair_keys = [&](int h, int rows, const float4 (&pv)[4], float E, auto code_of, TopKeys& top, float& biggest) {
-        // rows 62 and 63 of a block can be pads (blocks have 62 or 63 rows): lane row h = 3, tile 3, v = 2, 3.  Their P and G
-        // are exactly 0; their upper bound must be 0 too (not E), or a pad could pass for a survivor.
-        const bool pad2 = h == 3 && rows < 63, pad3 = h == 3 && rows < 64;
-        const unsigned keepp = keep_pair_mask;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const float vals[4] = {pv[t].x, pv[t].y, pv[t].z, pv[t].w};
-#pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                const float m = fabsf(vals[v]);
-                float ub = m + E;
-                if (t == 3 && v == 2) ub = pad2 ? 0.0f : ub;
-                if (t == 3 && v == 3) ub = pad3 ? 0.0f : ub;
-                top.see(__float_as_uint(ub), keepp, code_of(t, v));
-                biggest = __builtin_amdgcn_fmed3f(biggest, m, __builtin_inff());
-            }
-        }
-    };
-    // a pair that was not updated (the fresh one of (2c)): its keys join the lane's own registers
+    // a pair that was not updated (the fresh one of (2c)): its keys (`pair_keys` above) join the lane's own registers
     auto pair_fresh = [&](auto gc, int p, unsigned info, const float4 (&pv)[4], float E) {
         constexpr int g = decltype(gc)::value;
         FRESH_LANE
         oddp[g] = oddp[g] || !(E < kHuge);
         float biggest = 0.0f;
-        pair_keys(h, (int)((info >> 9) & 127u), pv, E, [&](int t, int v) { return (unsigned)((p << 4) | (t << 2) | v); }, tp[g], biggest);
+        pair_keys(h, (int)((info >> 9) & 127u), pv, E, keep_pair_mask, [&](int t, int v) { return (unsigned)((p << 4) | (t << 2) | v); }, tp[g], biggest);
         lbmax[g] = __builtin_amdgcn_fmed3f(lbmax[g], biggest - E, __builtin_inff());
     };
     // the wave's part of the pair rounds' LDS (see (8b)): empty between the steps
@@ -490,6 +565,9 @@ __global__ __launch_bounds__(64 * kWaves, kWaves / 4) void mp_pursuit_kernel(con
         if (lane == 0) s_oddm[wave] = 0u;
     }
     for (;;) {
+#if MPC_TOUCH_WAIT == 2
+        __builtin_amdgcn_s_waitcnt(0x0F70);
+#endif
         // ---- (1) refill: slots whose tile-channel has ended take the next tile-channels from the queue, kRefillAt or more at
         //      a time (one atomic per refill; a wave whose slots are all free refills at once)
         bool any_unit = false;
@@ -617,9 +695,15 @@ __global__ __launch_bounds__(64 * kWaves, kWaves / 4) void mp_pursuit_kernel(con
             odd[g] = !(rnorm[g] < kHuge);                           // NaN, infinity or large enough to overflow the f32 side
         });
         STAMP(1)
+#if MPC_TOUCH_WAIT == 1 || MPC_TOUCH_WAIT == 4
+        // vmcnt(0) alone.  Whatever the last step left in flight (loads whose results no path waited for, its stores) has had the
+        // refill and the B operands to arrive, so this finds next to nothing outstanding; it tells the compiler so, which otherwise
+        // waits with vmcnt(0) inside pass 1's tile loop -- where the stores of (2c) would be waited for with it.
+        __builtin_amdgcn_s_waitcnt(0x0F70);
+#endif
 
-        // ---- (2c) a pair created by the last step: first approximations of its 64 rows from the block's filter tiles (their
-        //      lines were pulled towards the cache when the pair was created)
+        // ---- (2c) a pair created by the last step: first approximations of its 64 rows from the block's filter tiles (16 KiB of
+        //      the channel's 8 MiB, read from the L2 / Infinity Cache as they come: no touch ahead, see (9))
         static_for<kGroups>([&](auto gc) {
             constexpr int g = decltype(gc)::value;
             if (unit[g] < 0) return;
@@ -672,8 +756,9 @@ __global__ __launch_bounds__(64 * kWaves, kWaves / 4) void mp_pursuit_kernel(con
 
         // ---- (3) pass 1 over the LDS tiles: top two approximations per lane as keys, base rows and DetailBasis[0] apart.  Both
         //      groups always run (an empty group computes on stale registers and is ignored): no branch between the MFMAs of a
-        //      tile and the tracking of the previous tile's results, which fills their shadow.  No global memory in here: the
-        //      stores of the pair updates drain meanwhile.
+        //      tile and the tracking of the previous tile's results, which fills their shadow.  No global memory in here and no
+        //      s_waitcnt on vmcnt in the loop over the base tiles: the stores of (2c) and of the pair updates drain meanwhile.  Per
+        //      tile: 6 MFMAs, 4 ds_read_b128, 4 v_and_or_b32 and 5 max3 / med3 (TopKeys::see4).
         TopKeys tb[kGroups], td[kGroups];
         bool any0 = false;
 #pragma unroll
@@ -685,13 +770,8 @@ __global__ __launch_bounds__(64 * kWaves, kWaves / 4) void mp_pursuit_kernel(con
             f32x4 acc[kGroups], prev[kGroups];
             const unsigned keep = keep_row_mask;
             auto track = [&](TopKeys (&trk)[kGroups], const f32x4 (&val)[kGroups], unsigned code0) {
-                unsigned code[4];
 #pragma unroll
-                for (int v = 0; v < 4; ++v) code[v] = (unsigned)__builtin_amdgcn_readfirstlane((int)(code0 + v));    // each in a scalar register
-#pragma unroll
-                for (int g = 0; g < kGroups; ++g)
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) trk[g].see(__float_as_uint(val[g][v]), keep, code[v]);
+                for (int g = 0; g < kGroups; ++g) track_tile(trk[g], val[g], keep, code0);
             };
             // ONE tile buffer: a tile's six MFMAs have read it by the time the next tile's LDS reads land (they are issued
             // behind the last MFMA and return while the matrix pipe works and the previous tile's results are tracked); a second
@@ -1097,7 +1177,7 @@ __global__ __launch_bounds__(64 * kWaves, kWaves / 4) void mp_pursuit_kernel(con
                         const bool oddi = (upd && !(fabsf(ic) < kHuge)) || !(E < kHuge);
                         TopKeys top;
                         float biggest = 0.0f;                       // of this pair's |P|: its lower bound is biggest - E
-                        pair_keys(h, (int)((info >> 9) & 127u), pv, E, [](int t, int v) { return (unsigned)((t << 2) | v); }, top, biggest);
+                        pair_keys(h, (int)((info >> 9) & 127u), pv, E, keep_pair_mask, [](int t, int v) { return (unsigned)((t << 2) | v); }, top, biggest);
                         // the pair's number joins the two keys afterwards (below the value's bits, above tile and row: order kept)
                         const unsigned k1 = __float_as_uint(top.k1) | ((unsigned)ip << 4), k2 = __float_as_uint(top.k2) | ((unsigned)ip << 4);
                         // (K1, K2) stay the two largest of everything merged, in any order, also when two quads serve one slot
@@ -1128,10 +1208,12 @@ __global__ __launch_bounds__(64 * kWaves, kWaves / 4) void mp_pursuit_kernel(con
         });
         STAMP(2)
 
-        // ---- (9) residual update r -= (q * quant) * row: Vector::Scale then Vector::Subtract, two roundings.  Behind it, what
-        //      the next step will read from far away is pulled towards the cache by LDS-DMA into a landing zone nobody reads (no
-        //      register, no wait): the filter tiles of a new pair.  (The Gram rows of the pairs are not touched here: their update
-        //      runs in (8b), before this phase.)
+        // ---- (9) residual update r -= (q * quant) * row: Vector::Scale then Vector::Subtract, two roundings.  Nothing is fetched
+        //      ahead for the next step.  The filter tiles of a new pair used to be pulled towards the cache here by LDS-DMA loads into
+        //      a landing zone nobody reads (MPC_TOUCH_WAIT 0 .. 2 still build that): it took no register, but not "no wait" -- an
+        //      LDS-DMA load writes LDS, so every path's first LDS read behind it waited for all vector memory, the touch's own 128
+        //      lines included, and the kernel is 8 - 11 % faster without the touch than with it wherever that wait is put
+        //      (DESIGN.md 9).
         static_for<kGroups>([&](auto gc) {
             constexpr int g = decltype(gc)::value;
             if (unit[g] < 0) return;
@@ -1152,6 +1234,7 @@ __global__ __launch_bounds__(64 * kWaves, kWaves / 4) void mp_pursuit_kernel(con
                 const T e2 = chain_sum(sq, h);
                 if (s.live && ended[g] && h == 0) a.out.energy[rec_of(s.t)] = (double)e2;
             }
+#if MPC_TOUCH_WAIT < 3
             unsigned long long pend = __ballot(s.live && !ended[g] && s.fresh >= 0 && s.fresh < 4 && h == 0);
             while (pend) {                                          // a new pair's 16 KiB of filter tiles: 128 lines, two per lane
                 const int src = __builtin_ctzll(pend);
@@ -1161,6 +1244,7 @@ __global__ __launch_bounds__(64 * kWaves, kWaves / 4) void mp_pursuit_kernel(con
                 __builtin_amdgcn_global_load_lds(tiles, my_touch, 4, 0, 0);
                 __builtin_amdgcn_global_load_lds(tiles + 4096, my_touch, 4, 0, 0);
             }
+#endif
             if (ended[g]) s.live = false;
             s.step += 1;
             if (!__ballot(s.live)) unit[g] = -1;
@@ -1277,6 +1361,59 @@ int launch_screen_probe(const uint16_t* base_tiles, const uint16_t* block_tiles,
 {
     hipLaunchKernelGGL(mp_screen_probe_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), base_tiles, block_tiles, vectors, n,
                        approx, bound);
+    return (int)hipGetLastError();
+}
+
+// --------------------------------------------------------------------------------------------------
+// Test probe of the key tracking (mpc_debug_track_probe_device): ONE wave runs the pursuit kernel's own track_tile and pair_keys,
+// sequential (four see(), the definition) and grouped (see4), on the caller's bit patterns.  Lane l reads row_bits[l][4 tile + v]
+// (tiles 0 .. 31 as pass 1's base tiles, 32 .. 35 as its DetailBasis[0] tiles, each with the kernel's codes) and
+// pair_bits[l][4 t + v] (the P of one pair; E, rows and the pair's number are the launch's).  out[l][14]: base keys (k1, k2)
+// sequential, grouped; block keys sequential, grouped; then pair (k1, k2, biggest) sequential, grouped.
+// --------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void mp_track_probe_kernel(const unsigned* __restrict__ row_bits, const unsigned* __restrict__ pair_bits,
+                                                            float E, int rows, int pair, unsigned* __restrict__ out)
+{
+    FRESH_LANE
+    (void)slot; (void)pix0;
+    const unsigned keep_row_mask = in_vgpr(kKeepRow), keep_pair_mask = in_vgpr(kKeepPair);
+    TopKeys sb, gb, sd, gd;
+    const auto tile_values = [&](int t) {
+        const uint4 w = *reinterpret_cast<const uint4*>(row_bits + lane * (4 * kTilesLds) + 4 * t);
+        const f32x4 val = {__uint_as_float(w.x), __uint_as_float(w.y), __uint_as_float(w.z), __uint_as_float(w.w)};
+        return val;
+    };
+    for (int t = 0; t < kBaseFilterTiles; ++t) {
+        const f32x4 val = tile_values(t);
+        track_tile<false>(sb, val, keep_row_mask, 4u * t);
+        track_tile<true>(gb, val, keep_row_mask, 4u * t);
+    }
+    for (int t = 0; t < kBlockFilterTiles; ++t) {
+        const f32x4 val = tile_values(kBaseFilterTiles + t);
+        track_tile<false>(sd, val, keep_row_mask, 4u * t);
+        track_tile<true>(gd, val, keep_row_mask, 4u * t);
+    }
+    float4 pv[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const uint4 w = *reinterpret_cast<const uint4*>(pair_bits + lane * 16 + 4 * t);
+        pv[t] = make_float4(__uint_as_float(w.x), __uint_as_float(w.y), __uint_as_float(w.z), __uint_as_float(w.w));
+    }
+    TopKeys sp, gp;
+    float sbig = 0.0f, gbig = 0.0f;
+    const auto code_of = [&](int t, int v) { return (unsigned)((pair << 4) | (t << 2) | v); };      // as the fresh pair of (2c)
+    pair_keys<false>(h, rows, pv, E, keep_pair_mask, code_of, sp, sbig);
+    pair_keys<true>(h, rows, pv, E, keep_pair_mask, code_of, gp, gbig);
+    unsigned* o = out + lane * 14;
+    o[0] = __float_as_uint(sb.k1); o[1] = __float_as_uint(sb.k2); o[2] = __float_as_uint(gb.k1); o[3] = __float_as_uint(gb.k2);
+    o[4] = __float_as_uint(sd.k1); o[5] = __float_as_uint(sd.k2); o[6] = __float_as_uint(gd.k1); o[7] = __float_as_uint(gd.k2);
+    o[8] = __float_as_uint(sp.k1); o[9] = __float_as_uint(sp.k2); o[10] = __float_as_uint(sbig);
+    o[11] = __float_as_uint(gp.k1); o[12] = __float_as_uint(gp.k2); o[13] = __float_as_uint(gbig);
+}
+
+int launch_track_probe(const unsigned* row_bits, const unsigned* pair_bits, float E, int rows, int pair, unsigned* out, void* stream)
+{
+    hipLaunchKernelGGL(mp_track_probe_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), row_bits, pair_bits, E, rows, pair, out);
     return (int)hipGetLastError();
 }
 

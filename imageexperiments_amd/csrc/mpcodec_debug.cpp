@@ -1,7 +1,8 @@
 // mpcodec_debug.cpp -- product: the mpc_debug_* entry points and mpc_filter_tiles (include/mpcodec.h, "test entry points").
 // They exist for the tests of the pursuit screen's tables (tests/test_screen_cases.py, tests/test_gpu_screen_tables.py): the
 // resident Gram table, the uploaded split-bf16 filter tiles and the bound of the MFMA approximations decide nothing by
-// themselves, so no record can show that they are right; and mpc_debug_container_index_device, the device scan of the seek index
+// themselves, so no record can show that they are right; mpc_debug_track_probe_device, the kernel's key tracking by its definition
+// and grouped on given bit patterns (tests/test_gpu_track_keys.py); and mpc_debug_container_index_device, the device scan of the seek index
 // with its segment and window sizes given, so that a test can make chains cross windows on a small container
 // (tests/test_gpu_index_scan.py).  Nothing here is on a product path; every entry validates its arguments
 // before it touches memory.
@@ -105,6 +106,19 @@ mpc_status mpc_debug_screen_probe_device(mpc_context* c, int channel, int block,
     const uint16_t* block_tiles =
         d.d_detail_t1 + (static_cast<size_t>(channel) * d.num_base + block) * mpc::kBlockFilterTiles * mpc::kFilterTileHalves;
     if (const int err = mpc::launch_screen_probe(d.d_base_t1, block_tiles, d_vectors, n, d_approx, d_bound, stream)) return launch_failed(err);
+    return MPC_OK;
+}
+
+mpc_status mpc_debug_track_probe_device(mpc_context* c, const uint32_t* d_row_bits, const uint32_t* d_pair_bits, float bound, int rows,
+                                        int pair, uint32_t* d_out, void* stream) {
+    if (const mpc_status st = need_device(c); st != MPC_OK) return st;
+    if (!d_row_bits || !d_pair_bits || !d_out) return fail(MPC_ERR_ARGUMENT, "null pointer");
+    if (!aligned16(d_row_bits) || !aligned16(d_pair_bits)) return fail(MPC_ERR_ARGUMENT, "d_row_bits and d_pair_bits must be 16-byte aligned");
+    if (rows < 1 || rows > 64) return fail(MPC_ERR_ARGUMENT, "rows must be 1 ... 64");
+    if (pair < 0 || pair >= mpc::kMaxPairs) return fail(MPC_ERR_ARGUMENT, "pair must be 0 ... %d", mpc::kMaxPairs - 1);
+    HIP_TRY(hipSetDevice(c->device));
+    if (const mpc_status cs = refuse_capture(stream); cs != MPC_OK) return cs;
+    if (const int err = mpc::launch_track_probe(d_row_bits, d_pair_bits, bound, rows, pair, d_out, stream)) return launch_failed(err);
     return MPC_OK;
 }
 

@@ -1378,7 +1378,8 @@ int        mpc_patch_last_route(const mpc_patch_decoder* p);
 /* ---- test entry points ----
  * These exist for the tests of the pursuit screen's tables (tests/test_screen_cases.py, tests/test_gpu_screen_tables.py) and are
  * on no product path.  The screen decides nothing: a wrong Gram entry, a wrong filter tile or a bound that does not
- * hold changes no record until a contest happens to fall inside the error, so these three are read back and probed directly.
+ * hold changes no record until a contest happens to fall inside the error, so these three are read back and probed directly;
+ * the kernel's key tracking is probed the same way (mpc_debug_track_probe_device, tests/test_gpu_track_keys.py).
  * Every entry checks its arguments before it touches memory: MPC_ERR_ARGUMENT for a null pointer, a channel outside 0 ... 2, a
  * block outside 0 ... num_base - 1, n outside 1 ... 16 or a rectangle outside the table; MPC_ERR_NO_DEVICE for a host-only context.
  *
@@ -1408,6 +1409,17 @@ mpc_status mpc_filter_tiles(const double* rows, int nrows, int tiles, int k_orde
  * approximation of base row 0 ... 511, then of block row 0 ... 63; d_bound[n] = E.  Asynchronous on `stream`. */
 mpc_status mpc_debug_screen_probe_device(mpc_context* ctx, int channel, int block, const double* d_vectors, int n, float* d_approx,
                                          float* d_bound, void* stream);
+/* One wave of the pursuit's key tracking ("keys"), needing no dictionary: the kernel's own functions on the caller's
+ * bit patterns, once as the definition (one value after the other) and once grouped (four values in nine instructions), which
+ * must agree bit for bit.  Lane l (row h = l >> 4) reads d_row_bits[l][144] (16-byte aligned): [4*tile + v] is taken for the
+ * approximation of tile 0 ... 31 of the base rows, then of tile 0 ... 3 of DetailBasis[0], and tracked with the 7-bit row codes
+ * 4*tile + v; and d_pair_bits[l][16] (16-byte aligned): [4*t + v] is taken for P of row 16*t + 4*h + v of one pair whose bound is
+ * `bound`, whose block has `rows` (1 ... 64) rows and whose number is `pair` (0 ... 31): keys of |P| + bound with the 9-bit codes
+ * pair << 4 | t << 2 | v, zero for the pad rows (row >= rows of rows 62 and 63).  Values must be finite.
+ * d_out[l][14]: base keys k1, k2 by the definition, k1, k2 grouped; block keys likewise; pair k1, k2, largest |P| by the
+ * definition, then grouped.  Asynchronous on `stream`. */
+mpc_status mpc_debug_track_probe_device(mpc_context* ctx, const uint32_t* d_row_bits, const uint32_t* d_pair_bits, float bound, int rows,
+                                        int pair, uint32_t* d_out, void* stream);
 
 #ifdef __cplusplus
 }
