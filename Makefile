@@ -29,6 +29,8 @@
 #   make asan-quality  tests/cpp/asan_quality: the target-quality encode's host definitions -- the allocation's totals at all 256
 #                    multipliers, the pick, the squared error of a PSNR -- on exact-size buffers and hostile arguments (what
 #                    tests/test_asan_quality.py runs)
+#   make asan-emphasis  tests/cpp/asan_emphasis: the emphasis maps' host definitions -- the allocation, the sweep and the floor allocation
+#                    with a map, the map from a pixel mask -- on exact-size buffers and hostile values (what tests/test_asan_emphasis.py runs)
 #   make asan-patch  tests/cpp/asan_patch: the delta stream's patch format -- its one writer and its one parser -- on exact-size buffers:
 #                    the hostile corpus of tests/patch_cases.py and every single-bit flip of valid patches' headers and lists (what
 #                    tests/test_asan_patch.py runs)
@@ -118,6 +120,12 @@ tests/cpp/asan_quality_bin: tests/cpp/asan_quality.cpp $(wildcard imageexperimen
 asan-quality: tests/cpp/asan_quality_bin
 	ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=print_stacktrace=1 MPC_HOST_THREADS=4 ./tests/cpp/asan_quality_bin
 
+tests/cpp/asan_emphasis_bin: tests/cpp/asan_emphasis.cpp $(wildcard imageexperiments_amd/csrc/host_*.cpp imageexperiments_amd/csrc/host_*.h)
+	g++ -std=c++17 -O1 -g $(SAN) -ffp-contract=off -pthread -Wall -Wno-unused-function tests/cpp/asan_emphasis.cpp -o $@
+
+asan-emphasis: tests/cpp/asan_emphasis_bin
+	ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=print_stacktrace=1 MPC_HOST_THREADS=4 ./tests/cpp/asan_emphasis_bin
+
 tests/cpp/asan_patch_bin: tests/cpp/asan_patch.cpp $(wildcard imageexperiments_amd/csrc/host_*.cpp imageexperiments_amd/csrc/host_*.h)
 	g++ -std=c++17 -O1 -g $(SAN) -ffp-contract=off -pthread -Wall -Wno-unused-function tests/cpp/asan_patch.cpp -o $@
 
@@ -138,6 +146,6 @@ asan-oracle: oracle/_build/liboracle_asan.so
 	LD_PRELOAD=$$(gcc -print-file-name=libasan.so) ASAN_OPTIONS=detect_leaks=0 ORACLE_LIB=$(CURDIR)/oracle/_build/liboracle_asan.so \
 	    python -m pytest tests/test_oracle_golden.py -x -q -p no:cacheprovider
 
-asan: asan-host asan-index asan-encode-index asan-encode-index2 asan-region asan-index2 asan-view asan-transcode asan-compose asan-index-scan asan-delta asan-budget asan-quality asan-patch asan-patch-index asan-oracle
+asan: asan-host asan-index asan-encode-index asan-encode-index2 asan-region asan-index2 asan-view asan-transcode asan-compose asan-index-scan asan-delta asan-budget asan-quality asan-emphasis asan-patch asan-patch-index asan-oracle
 
-.PHONY: asan asan-host asan-index asan-encode-index asan-encode-index2 asan-region asan-index2 asan-view asan-transcode asan-compose asan-index-scan asan-delta asan-budget asan-quality asan-patch asan-patch-index asan-oracle
+.PHONY: asan asan-host asan-index asan-encode-index asan-encode-index2 asan-region asan-index2 asan-view asan-transcode asan-compose asan-index-scan asan-delta asan-budget asan-quality asan-emphasis asan-patch asan-patch-index asan-oracle

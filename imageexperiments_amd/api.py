@@ -380,6 +380,27 @@ def _bind_bitstream(L):
     except AttributeError:
         if not os.environ.get("MPCODEC_LIB"):             # an older build may be loaded for A/B timing only
             raise
+    try:
+        L.mpc_budget_allocate_emphasis.argtypes = [_u32p, _u16p, _u8p, C.c_longlong, C.c_int, _u32p, C.c_int, _u8p, _u16p, _u64p]
+        L.mpc_budget_sweep_emphasis.argtypes = [_u32p, _u16p, _u8p, C.c_longlong, C.c_int, _u32p, _u64p]
+        L.mpc_budget_allocate_floor_emphasis.argtypes = [_u32p, _u16p, _u8p, _u8p, _u8p, _i32p, C.c_longlong, C.c_longlong, C.c_int, _u32p,
+                                                         C.c_int, _u8p, _u16p, _u8p, _u64p]
+        L.mpc_emphasis_from_mask.argtypes = [vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, _u8p]
+        L.mpc_budget_allocate_emphasis_device.argtypes = [vp, vp, vp, vp, C.c_longlong, _u32p, C.c_int, vp, vp, vp, vp]
+        L.mpc_budget_sweep_emphasis_device.argtypes = [vp, vp, vp, vp, C.c_longlong, _u32p, vp, vp]
+        L.mpc_budget_allocate_floor_emphasis_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_longlong, C.c_longlong, _u32p, C.c_int, vp, vp,
+                                                                vp, vp, vp]
+        L.mpc_emphasis_from_mask_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, vp, vp]
+        for f in ("mpc_encode_image_budget_emphasis", "mpc_encode_image_budget_emphasis_device"):
+            getattr(L, f).argtypes = [vp, vp, vp, C.c_int, C.c_int, _dp, C.c_size_t, C.c_int, C.POINTER(_u8p), _szp_, C.POINTER(_u8p), _szp_,
+                                      _u8p, C.POINTER(MpcBudgetInfo)]
+        for f in ("mpc_encode_image_quality_emphasis", "mpc_encode_image_quality_emphasis_device"):
+            getattr(L, f).argtypes = [vp, vp, vp, C.c_int, C.c_int, _dp, C.c_ulonglong, C.c_int, C.POINTER(_u8p), _szp_, C.POINTER(_u8p), _szp_,
+                                      _u8p, C.POINTER(MpcQualityInfo)]
+        L.mpc_delta_set_emphasis.argtypes = [vp, _u8p, C.c_int]
+    except AttributeError:
+        if not os.environ.get("MPCODEC_LIB"):             # an older build may be loaded for A/B timing only
+            raise
     L.mpc_parse_container_view_device.argtypes = [vp] + _vparse
     L.mpc_decode_views_indexed.argtypes = [vp, C.POINTER(_u8p), C.POINTER(C.c_size_t), C.POINTER(_u8p), C.POINTER(C.c_size_t), _vwp, C.c_int,
                                            C.c_uint, C.POINTER(_u8p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -959,6 +980,15 @@ class DeltaEncoder:
         """The same for a frame in device memory: d_rgb an int from tensor.data_ptr(), row_stride bytes between rows (0 = 3 * width)."""
         return self._encode_patch_budget(int(d_rgb), row_stride, budget, quant, MPC_DELTA_DEVICE_PIXELS | (MPC_DELTA_KEY if key else 0))
 
+    def set_emphasis(self, emphasis):
+        """mpc_delta_set_emphasis: the emphasis map (uint8 per tile, 16 = neutral, 1 ... 64) that weighs every later encode_patch_budget
+        until set again; None = none.  MpcError(MPC_ERR_ARGUMENT) for a map that is not the session's size; the session stays as it was."""
+        if emphasis is None:
+            _check(self.L.mpc_delta_set_emphasis(self.h, None, 0))
+            return
+        emphasis = np.ascontiguousarray(emphasis, np.uint8).reshape(-1)
+        _check(self.L.mpc_delta_set_emphasis(self.h, emphasis.ctypes.data_as(_u8p), emphasis.size))
+
     def sent(self):
         """mpc_delta_sent: the depth the receiver holds of each tile after the last budget call (uint8 per tile)"""
         n = C.c_int(0)
@@ -1214,6 +1244,89 @@ def sse_for_psnr(psnr, width, height):
     v = C.c_uint64(0)
     _check(load_library().mpc_sse_for_psnr(float(psnr), int(width), int(height), C.byref(v)))
     return v.value
+
+
+MPC_EMPHASIS_NEUTRAL, MPC_EMPHASIS_MAX = 16, 64
+
+
+def _emphasis(emphasis, tiles):
+    """None, or the map as uint8 [tiles]"""
+    if emphasis is None:
+        return None
+    emphasis = np.ascontiguousarray(emphasis, np.uint8).reshape(-1)
+    if emphasis.size != tiles:
+        raise ValueError(f"an emphasis map of {emphasis.size} tiles for {tiles}")
+    return emphasis
+
+
+def budget_allocate_emphasis(profile, counts, emphasis, weights, j):
+    """mpc_budget_allocate_emphasis: budget_allocate with J = P * e[t] * 4096 + L[j] * R: emphasis uint8 [T] (16 = neutral, 0 used as 1,
+    above 64 as 64) or None = neutral -> (depth, cut counts, totals); totals[0] is the unweighted squared error"""
+    profile = np.ascontiguousarray(profile, np.uint32)
+    T, K = profile.shape[0], profile.shape[1] - 1
+    counts = np.ascontiguousarray(counts, np.uint16).reshape(T, 3)
+    weights = np.ascontiguousarray(weights, np.uint32).reshape(3, K)
+    emphasis = _emphasis(emphasis, T)
+    depth, cut, totals = np.zeros(max(T, 1), np.uint8), np.zeros((max(T, 1), 3), np.uint16), np.zeros(3, np.uint64)
+    _check(load_library().mpc_budget_allocate_emphasis(profile.ctypes.data_as(_u32p), counts.ctypes.data_as(_u16p),
+                                                       None if emphasis is None else emphasis.ctypes.data_as(_u8p), T, K,
+                                                       weights.ctypes.data_as(_u32p), int(j), depth.ctypes.data_as(_u8p),
+                                                       cut.ctypes.data_as(_u16p), totals.ctypes.data_as(C.POINTER(C.c_uint64))))
+    return depth[:T], cut[:T], totals
+
+
+def budget_sweep_emphasis(profile, counts, emphasis, weights):
+    """mpc_budget_sweep_emphasis: budget_allocate_emphasis's totals at every multiplier -> uint64 [256, 3]"""
+    profile = np.ascontiguousarray(profile, np.uint32)
+    T, K = profile.shape[0], profile.shape[1] - 1
+    counts = np.ascontiguousarray(counts, np.uint16).reshape(T, 3)
+    weights = np.ascontiguousarray(weights, np.uint32).reshape(3, K)
+    emphasis = _emphasis(emphasis, T)
+    totals = np.zeros((MPC_BUDGET_LAMBDAS, 3), np.uint64)
+    _check(load_library().mpc_budget_sweep_emphasis(profile.ctypes.data_as(_u32p), counts.ctypes.data_as(_u16p),
+                                                    None if emphasis is None else emphasis.ctypes.data_as(_u8p), T, K,
+                                                    weights.ctypes.data_as(_u32p), totals.ctypes.data_as(C.POINTER(C.c_uint64))))
+    return totals
+
+
+def budget_allocate_floor_emphasis(profile, counts, floor, must, emphasis, tile_list, weights, j):
+    """mpc_budget_allocate_floor_emphasis: budget_allocate_floor with an emphasis map of the whole frame (uint8 [tiles] or None);
+    candidate i takes emphasis[tile_list[i]] (int32 [n]; None = the identity), the neutral value where that is outside the frame
+    -> (depth, cut counts, send, totals uint64 [4]); totals[0] is unweighted"""
+    profile = np.ascontiguousarray(profile, np.uint32)
+    T, K = profile.shape[0], profile.shape[1] - 1
+    counts = np.ascontiguousarray(counts, np.uint16).reshape(T, 3)
+    weights = np.ascontiguousarray(weights, np.uint32).reshape(3, K)
+    floor = None if floor is None else np.ascontiguousarray(floor, np.uint8).reshape(T)
+    must = None if must is None else np.ascontiguousarray(must, np.uint8).reshape(T)
+    emphasis = None if emphasis is None else np.ascontiguousarray(emphasis, np.uint8).reshape(-1)
+    tile_list = None if tile_list is None else np.ascontiguousarray(tile_list, np.int32).reshape(T)
+    depth, cut, send = np.zeros(max(T, 1), np.uint8), np.zeros((max(T, 1), 3), np.uint16), np.zeros(max(T, 1), np.uint8)
+    totals = np.zeros(4, np.uint64)
+    _check(load_library().mpc_budget_allocate_floor_emphasis(
+        profile.ctypes.data_as(_u32p), counts.ctypes.data_as(_u16p), None if floor is None else floor.ctypes.data_as(_u8p),
+        None if must is None else must.ctypes.data_as(_u8p), None if emphasis is None else emphasis.ctypes.data_as(_u8p),
+        None if tile_list is None else tile_list.ctypes.data_as(_i32p), 0 if emphasis is None else emphasis.size, T, K,
+        weights.ctypes.data_as(_u32p), int(j), depth.ctypes.data_as(_u8p), cut.ctypes.data_as(_u16p), send.ctypes.data_as(_u8p),
+        totals.ctypes.data_as(C.POINTER(C.c_uint64))))
+    return depth[:T], cut[:T], send[:T], totals
+
+
+def emphasis_from_mask(mask, lo=1, hi=MPC_EMPHASIS_MAX, width=None):
+    """mpc_emphasis_from_mask: a uint8 mask at pixel resolution, [H, W] with any row stride and alignment (a numpy view is read in place
+    when its last axis is contiguous; width: the frame's, where the rows are wider than it) -> emphasis uint8 [tiles], t = tx * tiles_y
+    + ty: lo + ((hi - lo) * m + 127) // 255, m the largest mask byte of the tile's pixels inside the frame"""
+    mask = np.asarray(mask)
+    if mask.dtype != np.uint8 or mask.ndim != 2:
+        raise ValueError("the mask: an HxW uint8 array")
+    if mask.shape[1] > 1 and mask.strides[1] != 1 or mask.shape[0] > 1 and mask.strides[0] < mask.shape[1]:
+        mask = np.ascontiguousarray(mask)
+    H, W = mask.shape[0], mask.shape[1] if width is None else int(width)
+    stride = mask.strides[0] if H > 1 else max(W, 1)
+    tiles = -(-max(W, 0) // 8) * -(-H // 8)
+    out = np.zeros(max(tiles, 1), np.uint8)
+    _check(load_library().mpc_emphasis_from_mask(C.c_void_p(mask.ctypes.data), W, H, stride, int(lo), int(hi), out.ctypes.data_as(_u8p)))
+    return out[:tiles]
 
 
 class QualityResult:
@@ -1915,7 +2028,7 @@ class CompressionContext:
         if check:
             _check(self.L.mpc_crop_records_check(self.h, stream or None))
 
-    def _encode_budget(self, fn, frame, width, height, budget, quant, index_interval):
+    def _encode_budget(self, fn, frame, width, height, budget, quant, index_interval, emphasis=()):
         qp = None
         if quant is not None:
             quant = np.ascontiguousarray(quant, np.float64).reshape(3, self.K)
@@ -1923,8 +2036,8 @@ class CompressionContext:
         tiles = -(-int(width) // 8) * -(-int(height) // 8)
         depth = np.zeros(max(tiles, 1), np.uint8)
         out, n, index, nindex, info = _u8p(), C.c_size_t(0), _u8p(), C.c_size_t(0), MpcBudgetInfo()
-        _check(fn(self.h, frame, int(width), int(height), qp, int(budget), -1 if index_interval is None else int(index_interval), C.byref(out),
-                  C.byref(n), C.byref(index), C.byref(nindex), depth.ctypes.data_as(_u8p), C.byref(info)))
+        _check(fn(self.h, frame, *emphasis, int(width), int(height), qp, int(budget), -1 if index_interval is None else int(index_interval),
+                  C.byref(out), C.byref(n), C.byref(index), C.byref(nindex), depth.ctypes.data_as(_u8p), C.byref(info)))
         blob = _take_bytes(self.L, out, n)
         return BudgetResult(blob, None if index_interval is None else _take_bytes(self.L, index, nindex), depth[:tiles], info)
 
@@ -1967,7 +2080,7 @@ class CompressionContext:
         weights = np.ascontiguousarray(weights, np.uint32).reshape(3, self.K)
         _check(self.L.mpc_budget_sweep_device(self.h, d_profile, d_counts, int(tiles), weights.ctypes.data_as(_u32p), d_totals, stream or None))
 
-    def _encode_quality(self, fn, frame, width, height, psnr, max_sse, quant, index_interval):
+    def _encode_quality(self, fn, frame, width, height, psnr, max_sse, quant, index_interval, emphasis=()):
         if (psnr is None) == (max_sse is None):
             raise ValueError("exactly one of psnr and max_sse")
         if max_sse is None:
@@ -1979,8 +2092,8 @@ class CompressionContext:
         tiles = -(-int(width) // 8) * -(-int(height) // 8)
         depth = np.zeros(max(tiles, 1), np.uint8)
         out, n, index, nindex, info = _u8p(), C.c_size_t(0), _u8p(), C.c_size_t(0), MpcQualityInfo()
-        _check(fn(self.h, frame, int(width), int(height), qp, int(max_sse), -1 if index_interval is None else int(index_interval), C.byref(out),
-                  C.byref(n), C.byref(index), C.byref(nindex), depth.ctypes.data_as(_u8p), C.byref(info)))
+        _check(fn(self.h, frame, *emphasis, int(width), int(height), qp, int(max_sse), -1 if index_interval is None else int(index_interval),
+                  C.byref(out), C.byref(n), C.byref(index), C.byref(nindex), depth.ctypes.data_as(_u8p), C.byref(info)))
         blob = _take_bytes(self.L, out, n)
         return QualityResult(blob, None if index_interval is None else _take_bytes(self.L, index, nindex), depth[:tiles], info)
 
@@ -1998,6 +2111,67 @@ class CompressionContext:
         """The same with the frame in device memory (int from tensor.data_ptr(), tightly packed RGB)."""
         return self._encode_quality(self.L.mpc_encode_image_quality_device, C.c_void_p(int(d_rgb)), width, height, psnr, max_sse, quant,
                                     index_interval)
+
+    # ---- emphasis maps (include/mpcodec.h, "emphasis") ----
+    def encode_image_budget_emphasis(self, rgb, budget, emphasis, quant=None, index_interval=None):
+        """mpc_encode_image_budget_emphasis: encode_image_budget with an emphasis map (uint8 per tile, t = tx * tiles_y + ty; 16 =
+        neutral, 1 ... 64) that weighs every tile's squared error in the allocation; None: encode_image_budget itself.  sse stays the
+        true squared error of the result."""
+        rgb = np.ascontiguousarray(rgb, np.uint8)
+        if rgb.ndim != 3 or rgb.shape[2] != 3:
+            raise ValueError("pixels: an HxWx3 uint8 array")
+        H, W = rgb.shape[:2]
+        emphasis = _emphasis(emphasis, -(-W // 8) * -(-H // 8))
+        return self._encode_budget(self.L.mpc_encode_image_budget_emphasis, rgb.ctypes.data_as(C.c_void_p), W, H, budget, quant, index_interval,
+                                   (None if emphasis is None else C.c_void_p(emphasis.ctypes.data),))
+
+    def encode_image_budget_emphasis_device(self, d_rgb, width, height, budget, d_emphasis, quant=None, index_interval=None):
+        """The same with the frame and the map in device memory (ints from tensor.data_ptr(); d_emphasis 0 or None = neutral)."""
+        return self._encode_budget(self.L.mpc_encode_image_budget_emphasis_device, C.c_void_p(int(d_rgb)), width, height, budget, quant,
+                                   index_interval, (d_emphasis or None,))
+
+    def encode_image_quality_emphasis(self, rgb, emphasis, psnr=None, max_sse=None, quant=None, index_interval=None):
+        """mpc_encode_image_quality_emphasis: encode_image_quality with an emphasis map (as for encode_image_budget_emphasis).  The target
+        stays a promise about the frame's true error; the map decides where the remaining error lies."""
+        rgb = np.ascontiguousarray(rgb, np.uint8)
+        if rgb.ndim != 3 or rgb.shape[2] != 3:
+            raise ValueError("pixels: an HxWx3 uint8 array")
+        H, W = rgb.shape[:2]
+        emphasis = _emphasis(emphasis, -(-W // 8) * -(-H // 8))
+        return self._encode_quality(self.L.mpc_encode_image_quality_emphasis, rgb.ctypes.data_as(C.c_void_p), W, H, psnr, max_sse, quant,
+                                    index_interval, (None if emphasis is None else C.c_void_p(emphasis.ctypes.data),))
+
+    def encode_image_quality_emphasis_device(self, d_rgb, width, height, d_emphasis, psnr=None, max_sse=None, quant=None, index_interval=None):
+        """The same with the frame and the map in device memory."""
+        return self._encode_quality(self.L.mpc_encode_image_quality_emphasis_device, C.c_void_p(int(d_rgb)), width, height, psnr, max_sse,
+                                    quant, index_interval, (d_emphasis or None,))
+
+    def budget_allocate_emphasis_device(self, d_profile, d_counts, d_emphasis, tiles, weights, j, d_depth, d_out_counts, d_totals, stream=0):
+        """mpc_budget_allocate_emphasis_device: budget_allocate_device with d_emphasis[tiles] (uint8; 0 = neutral).  Asynchronous."""
+        weights = np.ascontiguousarray(weights, np.uint32).reshape(3, self.K)
+        _check(self.L.mpc_budget_allocate_emphasis_device(self.h, d_profile, d_counts, d_emphasis or None, int(tiles), weights.ctypes.data_as(_u32p),
+                                                          int(j), d_depth, d_out_counts, d_totals, stream or None))
+
+    def budget_sweep_emphasis_device(self, d_profile, d_counts, d_emphasis, tiles, weights, d_totals, stream=0):
+        """mpc_budget_sweep_emphasis_device: budget_sweep_device with d_emphasis[tiles] (uint8; 0 = neutral).  Asynchronous."""
+        weights = np.ascontiguousarray(weights, np.uint32).reshape(3, self.K)
+        _check(self.L.mpc_budget_sweep_emphasis_device(self.h, d_profile, d_counts, d_emphasis or None, int(tiles), weights.ctypes.data_as(_u32p),
+                                                       d_totals, stream or None))
+
+    def budget_allocate_floor_emphasis_device(self, d_profile, d_counts, d_floor, d_must, d_emphasis, d_list, tiles, n, weights, j, d_depth,
+                                              d_out_counts, d_send, d_totals, stream=0):
+        """mpc_budget_allocate_floor_emphasis_device: budget_allocate_floor_device with the frame's d_emphasis[tiles] (uint8; 0 = neutral)
+        and d_list[n] (int32: candidate -> tile; 0 = the identity).  Asynchronous."""
+        weights = np.ascontiguousarray(weights, np.uint32).reshape(3, self.K)
+        _check(self.L.mpc_budget_allocate_floor_emphasis_device(self.h, d_profile, d_counts, d_floor or None, d_must or None, d_emphasis or None,
+                                                                d_list or None, int(tiles), int(n), weights.ctypes.data_as(_u32p), int(j),
+                                                                d_depth, d_out_counts, d_send, d_totals, stream or None))
+
+    def emphasis_from_mask_device(self, d_mask, width, height, d_emphasis, lo=1, hi=MPC_EMPHASIS_MAX, row_stride=0, stream=0):
+        """mpc_emphasis_from_mask_device: emphasis_from_mask on the device: d_mask (uint8, row_stride bytes a row, 0 = width; a torch
+        tensor's data_ptr()) -> d_emphasis[tiles].  Asynchronous."""
+        _check(self.L.mpc_emphasis_from_mask_device(self.h, d_mask or None, int(width), int(height), int(row_stride) or int(width), int(lo),
+                                                    int(hi), d_emphasis or None, stream or None))
 
     def owed_tiles_device(self, d_sent, d_counts, tiles, d_flags, d_floor, d_must, d_list, d_count, stream=0):
         """mpc_owed_tiles_device: d_flags[tiles] (uint8, != 0: changed) gains the owed tiles of d_sent / d_counts; d_floor and d_must

@@ -35,6 +35,11 @@ int budget_weights(const uint8_t* index, size_t index_bytes, uint32_t* weights, 
 
 void budget_allocate(const uint32_t* profile, const uint16_t* counts, long long tiles, int K, const uint32_t* weights, int j, uint8_t* depth,
                      uint16_t* out_counts, uint64_t totals[3]) {
+    budget_allocate_emphasis(profile, counts, nullptr, tiles, K, weights, j, depth, out_counts, totals);
+}
+
+void budget_allocate_emphasis(const uint32_t* profile, const uint16_t* counts, const uint8_t* emphasis, long long tiles, int K,
+                              const uint32_t* weights, int j, uint8_t* depth, uint16_t* out_counts, uint64_t totals[3]) {
     const uint64_t L = budget_lambda(j);
     uint32_t below[3][33];                              // below[ch][m] = W[ch][0] + ... + W[ch][m - 1]
     for (int ch = 0; ch < 3; ++ch) {
@@ -46,12 +51,13 @@ void budget_allocate(const uint32_t* profile, const uint16_t* counts, long long 
         int cnt[3];
         for (int ch = 0; ch < 3; ++ch) cnt[ch] = counts[t * 3 + ch] > K ? K : counts[t * 3 + ch];
         const uint32_t* P = profile + t * (K + 1);
+        const uint64_t factor = static_cast<uint64_t>(emphasis ? emphasis_used(emphasis[t]) : kEmphasisNeutral) << kEmphasisShift;
         uint64_t best = 0, best_rate = 0;
         int at = 0;
         for (int n = 0; n <= K; ++n) {
             uint64_t rate = 0;
             for (int ch = 0; ch < 3; ++ch) rate += below[ch][n < cnt[ch] ? n : cnt[ch]];
-            const uint64_t J = (static_cast<uint64_t>(P[n]) << kBudgetDistortionShift) + L * rate;
+            const uint64_t J = P[n] * factor + L * rate;
             if (n == 0 || J < best) {
                 best = J;
                 best_rate = rate;
@@ -70,6 +76,11 @@ void budget_allocate(const uint32_t* profile, const uint16_t* counts, long long 
 }
 
 void budget_sweep(const uint32_t* profile, const uint16_t* counts, long long tiles, int K, const uint32_t* weights, uint64_t totals[3 * kBudgetLambdas]) {
+    budget_sweep_emphasis(profile, counts, nullptr, tiles, K, weights, totals);
+}
+
+void budget_sweep_emphasis(const uint32_t* profile, const uint16_t* counts, const uint8_t* emphasis, long long tiles, int K,
+                           const uint32_t* weights, uint64_t totals[3 * kBudgetLambdas]) {
     uint64_t L[kBudgetLambdas];
     for (int j = 0; j < kBudgetLambdas; ++j) {
         L[j] = budget_lambda(j);
@@ -82,9 +93,10 @@ void budget_sweep(const uint32_t* profile, const uint16_t* counts, long long til
     }
     for (long long t = 0; t < tiles; ++t) {
         // the tile's own: distortion term, rate and records kept of every depth, once for all multipliers
+        const uint64_t factor = static_cast<uint64_t>(emphasis ? emphasis_used(emphasis[t]) : kEmphasisNeutral) << kEmphasisShift;
         uint64_t scaled[33], rate[33], kept[33];
         for (int n = 0; n <= K; ++n) {
-            scaled[n] = static_cast<uint64_t>(profile[t * (K + 1) + n]) << kBudgetDistortionShift;
+            scaled[n] = profile[t * (K + 1) + n] * factor;
             rate[n] = kept[n] = 0;
             for (int ch = 0; ch < 3; ++ch) {
                 const int count = counts[t * 3 + ch] > K ? K : counts[t * 3 + ch];
@@ -103,11 +115,26 @@ void budget_sweep(const uint32_t* profile, const uint16_t* counts, long long til
                     at = n;
                 }
             }
-            totals[3 * j] += scaled[at] >> kBudgetDistortionShift;
+            totals[3 * j] += profile[t * (K + 1) + at];
             totals[3 * j + 1] += rate[at];
             totals[3 * j + 2] += kept[at];
         }
     }
+}
+
+void emphasis_from_mask(const uint8_t* mask, int width, int height, size_t row_stride, int lo, int hi, uint8_t* emphasis) {
+    const int tiles_x = (width + 7) / 8, tiles_y = (height + 7) / 8;
+    for (int tx = 0; tx < tiles_x; ++tx)
+        for (int ty = 0; ty < tiles_y; ++ty) {
+            const int x_end = tx * 8 + 8 < width ? tx * 8 + 8 : width, y_end = ty * 8 + 8 < height ? ty * 8 + 8 : height;
+            int m = 0;
+            for (int y = ty * 8; y < y_end; ++y)
+                for (int x = tx * 8; x < x_end; ++x) {
+                    const int v = mask[static_cast<size_t>(y) * row_stride + static_cast<size_t>(x)];
+                    m = v > m ? v : m;
+                }
+            emphasis[static_cast<size_t>(tx) * tiles_y + ty] = static_cast<uint8_t>(lo + ((hi - lo) * m + 127) / 255);
+        }
 }
 
 int quality_pick(const uint64_t totals[3 * kBudgetLambdas], uint64_t max_sse) {

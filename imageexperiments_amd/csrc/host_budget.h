@@ -1,8 +1,9 @@
 // host_budget.h -- product: the host's definition of the rate control behind mpc_encode_image_budget (include/mpcodec.h, "budget";
 // DESIGN.md 4, "Encoder: a byte budget"): the multiplier table, the rate weights from a seek index, the allocation at one multiplier;
 // and behind mpc_encode_image_quality ("quality"): the allocation's totals at every multiplier, the pick, the squared error of a PSNR.
-// Knows neither HIP nor the C ABI and builds on its own with host_bitstream / host_container (tests/cpp/asan_budget.cpp,
-// asan_quality.cpp).
+// And the emphasis map ("emphasis"; DESIGN.md 4, "Encoder: emphasis"): a factor per tile on the distortion term of both, and the map from
+// a pixel mask.  Knows neither HIP nor the C ABI and builds on its own with host_bitstream / host_container (tests/cpp/asan_budget.cpp,
+// asan_quality.cpp, asan_emphasis.cpp).
 #pragma once
 
 #include <cstddef>
@@ -46,6 +47,33 @@ int quality_pick(const uint64_t totals[3 * kBudgetLambdas], uint64_t max_sse);
 
 // The largest s in 0 ... limit with psnr(s) >= target, psnr a function that does not rise with s and is +inf at 0 (psnr_from_sse of
 // host_codec.h at one geometry): a binary search on that very function, so the answer agrees with it to the bit.  target: not NaN
+// ---- emphasis maps (include/mpcodec.h, "emphasis"; DESIGN.md 4, "Encoder: emphasis") ----
+// e[t], one u8 per tile, four fractional bits: 16 is neutral, the range 1 ... 64; a stored 0 is used as 1 and a value above 64 as 64 (no
+// address ever comes from one).  J(t, n) = P * e[t] * 4096 + L[j] * R: with e = 16 the factor is 65536 and J is budget_allocate's.
+// P <= 64 * 3 * 255^2 = 12 484 800, so P * 64 * 4096 <= 3.28e12 < 14 * 2^39 = 7.70e12, the cost of the cheapest record at j = 255: there
+// every depth is still 0, the budget search keeps its feasible end, and J stays below 2^63.
+constexpr int kEmphasisNeutral = 16;
+constexpr int kEmphasisMax = 64;
+constexpr int kEmphasisShift = 12;                  // e * 4096: 16 * 4096 = 1 << kBudgetDistortionShift
+static_assert((kEmphasisNeutral << kEmphasisShift) == (1 << kBudgetDistortionShift), "the neutral value is the plain allocation");
+constexpr uint32_t emphasis_used(uint8_t stored) {  // constexpr: the kernels use it too
+    return stored == 0 ? 1u : stored > kEmphasisMax ? static_cast<uint32_t>(kEmphasisMax) : stored;
+}
+
+// budget_allocate with J(t, n) = P[t][n] * e[t] * 4096 + L[j] * R[t][n]; totals[0] stays the sum of the unweighted P[t][depth[t]], the
+// squared error a decoder shows.  emphasis[tiles], null = neutral: then budget_allocate itself, bit for bit
+void budget_allocate_emphasis(const uint32_t* profile, const uint16_t* counts, const uint8_t* emphasis, long long tiles, int K,
+                              const uint32_t* weights, int j, uint8_t* depth, uint16_t* out_counts, uint64_t totals[3]);
+// budget_sweep with the same J: totals[3 * j + k] = budget_allocate_emphasis's totals[k] at multiplier j.  A loop of its own, as
+// budget_sweep is.  Scaling a tile's P by a positive constant leaves the argument of quality_pick intact: a tile's P at its minimiser
+// does not fall as L rises, so totals[3 * j], the true squared error, still never falls along the ladder
+void budget_sweep_emphasis(const uint32_t* profile, const uint16_t* counts, const uint8_t* emphasis, long long tiles, int K,
+                           const uint32_t* weights, uint64_t totals[3 * kBudgetLambdas]);
+// mask[y * row_stride + x], x < width, y < height (row_stride >= width; the bytes between rows are never read) -> emphasis[t],
+// t = tx * tiles_y + ty over the 8 x 8 tiles: lo + ((hi - lo) * m + 127) / 255, m the maximum of the mask over the tile's pixels inside
+// the frame.  The caller has checked: width, height >= 1, 1 <= lo <= hi <= 64
+void emphasis_from_mask(const uint8_t* mask, int width, int height, size_t row_stride, int lo, int hi, uint8_t* emphasis);
+
 template <class Psnr>
 uint64_t sse_for_psnr(double target, uint64_t limit, Psnr psnr) {
     uint64_t lo = 0, hi = limit;                        // psnr(lo) >= target always: psnr(0) = +inf

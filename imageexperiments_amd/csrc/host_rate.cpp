@@ -29,6 +29,12 @@ long long owed_tiles(const uint8_t* sent, const uint16_t* counts, long long tile
 
 void budget_allocate_floor(const uint32_t* profile, const uint16_t* counts, const uint8_t* floor, const uint8_t* must, long long n, int K,
                            const uint32_t* weights, int j, uint8_t* depth, uint16_t* out_counts, uint8_t* send, uint64_t totals[4]) {
+    budget_allocate_floor_emphasis(profile, counts, floor, must, nullptr, nullptr, 0, n, K, weights, j, depth, out_counts, send, totals);
+}
+
+void budget_allocate_floor_emphasis(const uint32_t* profile, const uint16_t* counts, const uint8_t* floor, const uint8_t* must,
+                                    const uint8_t* emphasis, const int32_t* list, long long tiles, long long n, int K, const uint32_t* weights,
+                                    int j, uint8_t* depth, uint16_t* out_counts, uint8_t* send, uint64_t totals[4]) {
     const uint64_t L = budget_lambda(j);
     uint32_t below[3][33];                              // below[ch][m] = W[ch][0] + ... + W[ch][m - 1]
     for (int ch = 0; ch < 3; ++ch) {
@@ -42,13 +48,15 @@ void budget_allocate_floor(const uint32_t* profile, const uint16_t* counts, cons
         const bool has_to = must ? must[i] != 0 : true;
         const int low = floor ? (floor[i] > K ? K : floor[i]) : 0;
         const uint32_t* P = profile + i * (K + 1);
+        const long long t = list ? static_cast<long long>(list[i]) : i;
+        const uint64_t factor = static_cast<uint64_t>(emphasis && t >= 0 && t < tiles ? emphasis_used(emphasis[t]) : kEmphasisNeutral) << kEmphasisShift;
         uint64_t best = 0, best_rate = 0;
         int at = -1;
         for (int d = has_to ? 0 : low; d <= K; ++d) {
             uint64_t rate = 0;
             if (has_to || d != low)
                 for (int ch = 0; ch < 3; ++ch) rate += below[ch][d < cnt[ch] ? d : cnt[ch]];
-            const uint64_t J = (static_cast<uint64_t>(P[d]) << kBudgetDistortionShift) + L * rate;
+            const uint64_t J = P[d] * factor + L * rate;
             if (at < 0 || J < best) {
                 best = J;
                 best_rate = rate;

@@ -25,4 +25,11 @@ long long owed_tiles(const uint8_t* sent, const uint16_t* counts, long long tile
 void budget_allocate_floor(const uint32_t* profile, const uint16_t* counts, const uint8_t* floor, const uint8_t* must, long long n, int K,
                            const uint32_t* weights, int j, uint8_t* depth, uint16_t* out_counts, uint8_t* send, uint64_t totals[4]);
 
+// budget_allocate_floor with an emphasis map (host_budget.h, "emphasis"): J = P * e * 4096 + L[j] * R', candidate i taking
+// e[list[i]], list == null the identity; a list entry outside [0, tiles) takes the neutral value.  totals[0] stays unweighted.
+// emphasis[tiles], null = neutral: then budget_allocate_floor itself, bit for bit, whatever the list
+void budget_allocate_floor_emphasis(const uint32_t* profile, const uint16_t* counts, const uint8_t* floor, const uint8_t* must,
+                                    const uint8_t* emphasis, const int32_t* list, long long tiles, long long n, int K, const uint32_t* weights,
+                                    int j, uint8_t* depth, uint16_t* out_counts, uint8_t* send, uint64_t totals[4]);
+
 }  // namespace mpc

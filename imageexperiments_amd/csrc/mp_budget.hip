@@ -12,6 +12,7 @@
 
 #include <type_traits>
 
+#include "host_budget.h"
 #include "mp_device.h"
 
 namespace mpc {
@@ -157,7 +158,11 @@ __global__ __launch_bounds__(64 * kProfileWaves) void mp_depth_profile_kernel(co
 // kept, the waves' sums meet in LDS, and threads 0 ... 2 add one total each to the frame's: one 64-bit integer atomic per total
 // and workgroup, as in mp_distortion_kernel, so the totals do not depend on the schedule.  Every address comes from the tile grid;
 // a count above K is used as K.
+// kEmphasis (host_budget.h, "emphasis"): J = P * e[t] * 4096 + lambda * R, e[t] one byte per tile through emphasis_used, so no address
+// comes from it; the totals keep the unweighted P.  P * 64 * 4096 < 2^42, so J stays below 2^63.  The plain kernel is the
+// instantiation without it and reads no emphasis pointer: its code is what it was.
 // --------------------------------------------------------------------------------------------------
+template <bool kEmphasis>
 __global__ __launch_bounds__(64 * kAllocateWaves) void mp_budget_allocate_kernel(const AllocateParams p)
 {
     __shared__ uint32_t below[3][kMaxDeviceK + 1];                  // below[ch][m] = W[ch][0] + ... + W[ch][m - 1]
@@ -181,13 +186,15 @@ __global__ __launch_bounds__(64 * kAllocateWaves) void mp_budget_allocate_kernel
             const int count = p.counts[t * 3 + ch];
             cnt[ch] = count > K ? K : count;
         }
+        unsigned long long factor = 0;
+        if (kEmphasis) factor = (unsigned long long)emphasis_used(p.emphasis[t]) << kEmphasisShift;
         uint32_t P = 0, R = 0;
         unsigned long long J = ~0ull;
         if (lane <= K) {
             P = p.profile[t * (K + 1) + lane];
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch) R += below[ch][lane < cnt[ch] ? lane : cnt[ch]];
-            J = ((unsigned long long)P << 16) + p.lambda * R;
+            J = (kEmphasis ? P * factor : (unsigned long long)P << 16) + p.lambda * R;
         }
         int depth = lane;
 #pragma unroll
@@ -236,14 +243,18 @@ __global__ __launch_bounds__(64 * kAllocateWaves) void mp_budget_allocate_kernel
 // 64 consecutive words (512 contiguous bytes) per 64-bit integer atomic: 768 atomics a workgroup, at most kSweepGridCap workgroups
 // whatever the frame.  The totals are integers and do not depend on the schedule.  Every address comes from the tile grid; a count
 // above K is used as K.
+// kEmphasis: the staged entry carries P * e[t] * 4096 and, since that no longer gives P back by a shift, the true P beside the records
+// kept in one word -- P < 2^24, at most 3 * 32 = 96 records -- so an entry stays 16 bytes and the LDS budget is unchanged.  The walk is
+// the same; the winner's true P is what the distortion total adds.  The plain kernel is the instantiation without it.
 // --------------------------------------------------------------------------------------------------
 namespace {
 struct alignas(16) SweepEntry {
-    unsigned long long scaled;          // P * 65536
-    uint32_t rate, kept;
+    unsigned long long scaled;          // P * 65536; with emphasis P * e * 4096
+    uint32_t rate, kept;                // with emphasis: kept = records kept | P << 8
 };
 }  // namespace
 
+template <bool kEmphasis>
 __global__ __launch_bounds__(256) void mp_budget_sweep_kernel(const SweepParams p)
 {
     __shared__ uint32_t below[3][kMaxDeviceK + 1];                  // below[ch][m] = W[ch][0] + ... + W[ch][m - 1]
@@ -280,9 +291,15 @@ __global__ __launch_bounds__(256) void mp_budget_sweep_kernel(const SweepParams 
                 kept += (uint32_t)upto;
             }
             SweepEntry entry;
-            entry.scaled = (unsigned long long)p.profile[first * depths + e] << 16;
+            const uint32_t P = p.profile[first * depths + e];
+            if (kEmphasis) {
+                entry.scaled = P * ((unsigned long long)emphasis_used(p.emphasis[t]) << kEmphasisShift);
+                entry.kept = kept | P << 8;
+            } else {
+                entry.scaled = (unsigned long long)P << 16;
+                entry.kept = kept;
+            }
             entry.rate = R;
-            entry.kept = kept;
             staged[e] = entry;
         }
         __syncthreads();
@@ -300,9 +317,9 @@ __global__ __launch_bounds__(256) void mp_budget_sweep_kernel(const SweepParams 
                 }
             }
             const SweepEntry won = tile[at];
-            distortion += won.scaled >> 16;
+            distortion += kEmphasis ? (unsigned long long)(won.kept >> 8) : won.scaled >> 16;
             rate += won.rate;
-            records += won.kept;
+            records += kEmphasis ? won.kept & 0xFFu : won.kept;
         }
     }
     sums[3 * m] = distortion;
@@ -313,6 +330,68 @@ __global__ __launch_bounds__(256) void mp_budget_sweep_kernel(const SweepParams 
     for (int k = 0; k < 3; ++k) {
         const unsigned long long total = sums[k * 256 + m];
         if (total) atomicAdd(p.totals + k * 256 + m, total);
+    }
+}
+
+// --------------------------------------------------------------------------------------------------
+// mask to emphasis (host_budget.h: emphasis_from_mask): one pass over a u8 mask at pixel resolution.  A workgroup of 256 threads takes a
+// block of 32 * kPix x kMaskTilesY tiles: thread x reads kPix neighbouring pixels of every pixel row of the block, so a wave's load is
+// 64 * kPix consecutive bytes of one row.  kPix = 4 where the mask's base and stride are multiples of 4: one 32-bit load, taken only
+// where all four pixels lie inside the frame -- the last pixels of a row whose width is no multiple of 4 come byte by byte, so the bytes
+// between rows are never addressed; kPix = 1 for any other alignment.  A thread keeps the maximum of each tile row's eight pixel rows
+// in a register, the 8 / kPix neighbouring lanes of one tile's columns (a tile never straddles a wave) meet in shuffles, and the maxima
+// land in LDS so that the store runs along ty, the inner index of t = tx * tiles_y + ty.  Pixels right of the frame and below it count
+// as 0, the identity of the maximum over u8; every address comes from the geometry.
+// --------------------------------------------------------------------------------------------------
+namespace {
+constexpr int kMaskTilesY = 4;
+}  // namespace
+
+template <int kPix>
+__global__ __launch_bounds__(256) void mp_emphasis_mask_kernel(const uint8_t* __restrict__ mask, int width, int height, size_t row_stride, int lo,
+                                                               int hi, int tiles_x, int tiles_y, int across, uint8_t* __restrict__ emphasis)
+{
+    constexpr int kTilesX = 32 * kPix, kLanes = 8 / kPix;             // tile columns a workgroup takes; lanes that share a tile
+    __shared__ uint8_t top[kTilesX][kMaskTilesY];
+    const int bx = (int)(blockIdx.x % (unsigned)across), by = (int)(blockIdx.x / (unsigned)across);
+    const int x = (bx * 256 + (int)threadIdx.x) * kPix;
+    const int ty0 = by * kMaskTilesY;
+#pragma unroll
+    for (int r = 0; r < kMaskTilesY; ++r) {
+        const int y0 = (ty0 + r) * 8;
+        unsigned m = 0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int y = y0 + k;
+            if (y < height) {
+                const uint8_t* row = mask + (size_t)y * row_stride;
+                if (kPix == 4 && x + 4 <= width) {
+                    const unsigned v = *reinterpret_cast<const unsigned*>(row + x);
+                    const unsigned a = v & 0xFFu, b = (v >> 8) & 0xFFu, c = (v >> 16) & 0xFFu, d = v >> 24;
+                    const unsigned ab = a > b ? a : b, cd = c > d ? c : d, abcd = ab > cd ? ab : cd;
+                    m = abcd > m ? abcd : m;
+                } else {
+#pragma unroll
+                    for (int i = 0; i < kPix; ++i)
+                        if (x + i < width) {
+                            const unsigned v = row[x + i];
+                            m = v > m ? v : m;
+                        }
+                }
+            }
+        }
+#pragma unroll
+        for (int o = 1; o < kLanes; o <<= 1) {
+            const unsigned other = (unsigned)__shfl_xor((int)m, o);
+            m = other > m ? other : m;
+        }
+        if (threadIdx.x % kLanes == 0) top[threadIdx.x / kLanes][r] = (uint8_t)m;
+    }
+    __syncthreads();
+    for (int i = (int)threadIdx.x; i < kTilesX * kMaskTilesY; i += 256) {
+        const int cx = i / kMaskTilesY, cy = i % kMaskTilesY;
+        const int tx = bx * kTilesX + cx, ty = ty0 + cy;
+        if (tx < tiles_x && ty < tiles_y) emphasis[(size_t)tx * tiles_y + ty] = (uint8_t)(lo + ((hi - lo) * (int)top[cx][cy] + 127) / 255);
     }
 }
 
@@ -333,7 +412,8 @@ int launch_budget_allocate(const AllocateParams& p, void* stream)
     if (p.K < 1 || p.K > kMaxDeviceK || p.tiles < 1) return (int)hipErrorInvalidValue;
     const long long groups = (p.tiles + kAllocateWaves - 1) / kAllocateWaves;
     const unsigned blocks = (unsigned)(groups < 4096 ? groups : 4096);
-    hipLaunchKernelGGL(mp_budget_allocate_kernel, dim3(blocks), dim3(64 * kAllocateWaves), 0, (hipStream_t)stream, p);
+    if (p.emphasis) hipLaunchKernelGGL(mp_budget_allocate_kernel<true>, dim3(blocks), dim3(64 * kAllocateWaves), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(mp_budget_allocate_kernel<false>, dim3(blocks), dim3(64 * kAllocateWaves), 0, (hipStream_t)stream, p);
     return (int)hipGetLastError();
 }
 
@@ -342,7 +422,27 @@ int launch_budget_sweep(const SweepParams& p, void* stream)
     if (p.K < 1 || p.K > kMaxDeviceK || p.tiles < 1) return (int)hipErrorInvalidValue;
     const long long chunks = (p.tiles + kSweepTiles - 1) / kSweepTiles;
     const unsigned blocks = (unsigned)(chunks < kSweepGridCap ? chunks : kSweepGridCap);
-    hipLaunchKernelGGL(mp_budget_sweep_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
+    if (p.emphasis) hipLaunchKernelGGL(mp_budget_sweep_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(mp_budget_sweep_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
+    return (int)hipGetLastError();
+}
+
+int launch_emphasis_mask(const uint8_t* mask, int width, int height, size_t row_stride, int lo, int hi, uint8_t* emphasis, void* stream)
+{
+    if (!mask || !emphasis || width < 1 || height < 1 || row_stride < (size_t)width || lo < 1 || hi < lo || hi > kEmphasisMax)
+        return (int)hipErrorInvalidValue;
+    const int tiles_x = (width + 7) / 8, tiles_y = (height + 7) / 8;
+    const bool words = ((reinterpret_cast<uintptr_t>(mask) | row_stride) & 3) == 0;
+    const int per_group = 32 * (words ? 4 : 1);
+    const int across = (tiles_x + per_group - 1) / per_group, down = (tiles_y + kMaskTilesY - 1) / kMaskTilesY;
+    const long long groups = (long long)across * down;
+    if (groups >= (1LL << 31)) return (int)hipErrorInvalidValue;
+    if (words)
+        hipLaunchKernelGGL(mp_emphasis_mask_kernel<4>, dim3((unsigned)groups), dim3(256), 0, (hipStream_t)stream, mask, width, height, row_stride, lo, hi,
+                           tiles_x, tiles_y, across, emphasis);
+    else
+        hipLaunchKernelGGL(mp_emphasis_mask_kernel<1>, dim3((unsigned)groups), dim3(256), 0, (hipStream_t)stream, mask, width, height, row_stride, lo, hi,
+                           tiles_x, tiles_y, across, emphasis);
     return (int)hipGetLastError();
 }
 

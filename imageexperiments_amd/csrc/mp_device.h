@@ -356,7 +356,8 @@ struct ProfileParams {
 };
 int launch_depth_profile(const DictDevice& dict, const ProfileParams& p, void* stream);
 // The allocation at one multiplier (host_budget.h: budget_allocate defines it): depth[tiles], out_counts[tiles][3], and
-// totals[0 .. 2] += the distortion, the rate and the records kept (the caller zeroes them).  The weights travel in the kernel's arguments
+// totals[0 .. 2] += the distortion, the rate and the records kept (the caller zeroes them).  The weights travel in the kernel's arguments.
+// emphasis != null: budget_allocate_emphasis, a code object of its own; null launches the plain kernel as before
 struct AllocateParams {
     const uint32_t* profile;         // [tiles][K + 1]
     const uint16_t* counts;          // [tiles][3]
@@ -367,6 +368,7 @@ struct AllocateParams {
     uint16_t* out_counts;
     unsigned long long* totals;      // [3]
     uint32_t weights[3 * kMaxDeviceK];   // [3][K]
+    const uint8_t* emphasis;         // [tiles] or null (host_budget.h, "emphasis")
 };
 int launch_budget_allocate(const AllocateParams& p, void* stream);
 // The allocation's totals at all 256 multipliers in one launch (host_budget.h: budget_sweep defines it):
@@ -381,7 +383,10 @@ struct SweepParams {
     int K;
     unsigned long long* totals;      // [256][3]
     uint32_t weights[3 * kMaxDeviceK];   // [3][K]
+    const uint8_t* emphasis;         // [tiles] or null: budget_sweep_emphasis, as for AllocateParams
 };
+// host_budget.h: emphasis_from_mask.  mask[height][row_stride] (device, any alignment) -> emphasis[tiles_x * tiles_y], x-outer / y-inner
+int launch_emphasis_mask(const uint8_t* mask, int width, int height, size_t row_stride, int lo, int hi, uint8_t* emphasis, void* stream);
 int launch_budget_sweep(const SweepParams& p, void* stream);
 
 // ---- a delta stream to a byte budget (mp_rate.hip; include/mpcodec.h, "rate") ----
@@ -431,6 +436,9 @@ struct AllocateFloorParams {
     uint8_t* send;
     unsigned long long* totals;      // [4]
     uint32_t weights[3 * kMaxDeviceK];   // [3][K]
+    const uint8_t* emphasis;         // [tiles] or null: budget_allocate_floor_emphasis, candidate i takes emphasis[list ? list[i] : i] ...
+    const int32_t* list;             // [n] or null
+    long long tiles;                 // ... and the neutral value where that tile is outside [0, tiles)
 };
 int launch_budget_allocate_floor(const AllocateFloorParams& p, void* stream);
 

@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "host_budget.h"
 #include "mp_device.h"
 
 namespace mpc {
@@ -139,7 +140,11 @@ __global__ __launch_bounds__(256) void mp_gather_records_kernel(const GatherPara
 // reaches (P < 2^24, lambda < 2^35, R < 2^27); the floor, used as K when above it, is always allowed, so the winner is an allowed
 // depth.  Lanes 0 ... 2 store the cut counts, lane 0 the depth and the send byte; the four totals (distortion, rate, the records of the
 // candidates sent, the candidates sent) meet in LDS and leave in one 64-bit integer atomic each per workgroup.
+// kEmphasis (host_rate.h: budget_allocate_floor_emphasis): J = P * e * 4096 + lambda * R', e the byte of the candidate's tile --
+// list[i], or i without a list -- through emphasis_used, the neutral value where that tile is outside [0, tiles): the list entry is
+// checked before it becomes an address.  The totals keep the unweighted P.  The plain kernel is the instantiation without it.
 // --------------------------------------------------------------------------------------------------
+template <bool kEmphasis>
 __global__ __launch_bounds__(64 * kAllocateWaves) void mp_budget_allocate_floor_kernel(const AllocateFloorParams p)
 {
     __shared__ uint32_t below[3][kMaxDeviceK + 1];                  // below[ch][m] = W[ch][0] + ... + W[ch][m - 1]
@@ -166,6 +171,11 @@ __global__ __launch_bounds__(64 * kAllocateWaves) void mp_budget_allocate_floor_
         const bool must = p.must ? p.must[t] != 0 : true;
         int low = p.floor ? (int)p.floor[t] : 0;
         low = low > K ? K : low;
+        unsigned long long factor = 0;
+        if (kEmphasis) {
+            const long long tile = p.list ? (long long)p.list[t] : t;
+            factor = (unsigned long long)(tile >= 0 && tile < p.tiles ? emphasis_used(p.emphasis[tile]) : (uint32_t)kEmphasisNeutral) << kEmphasisShift;
+        }
         uint32_t P = 0, R = 0;
         unsigned long long J = ~0ull;
         if (lane <= K && (must || lane >= low)) {
@@ -174,7 +184,7 @@ __global__ __launch_bounds__(64 * kAllocateWaves) void mp_budget_allocate_floor_
 #pragma unroll
                 for (int ch = 0; ch < 3; ++ch) R += below[ch][lane < cnt[ch] ? lane : cnt[ch]];
             }
-            J = ((unsigned long long)P << 16) + p.lambda * R;
+            J = (kEmphasis ? P * factor : (unsigned long long)P << 16) + p.lambda * R;
         }
         int depth = lane;
 #pragma unroll
@@ -273,7 +283,10 @@ int launch_budget_allocate_floor(const AllocateFloorParams& p, void* stream)
         return (int)hipErrorInvalidValue;
     const long long groups = (p.n + kAllocateWaves - 1) / kAllocateWaves;
     const unsigned blocks = (unsigned)(groups < 4096 ? groups : 4096);
-    hipLaunchKernelGGL(mp_budget_allocate_floor_kernel, dim3(blocks), dim3(64 * kAllocateWaves), 0, (hipStream_t)stream, p);
+    if (p.emphasis) {
+        if (p.tiles < 1) return (int)hipErrorInvalidValue;
+        hipLaunchKernelGGL(mp_budget_allocate_floor_kernel<true>, dim3(blocks), dim3(64 * kAllocateWaves), 0, (hipStream_t)stream, p);
+    } else hipLaunchKernelGGL(mp_budget_allocate_floor_kernel<false>, dim3(blocks), dim3(64 * kAllocateWaves), 0, (hipStream_t)stream, p);
     return (int)hipGetLastError();
 }
 

@@ -36,6 +36,9 @@ struct mpc_delta {
     bool sent_valid = false;                    // the map at d_sent (in `rate`) describes the receiver
     const uint8_t* d_sent = nullptr;
     long long owed = 0;                         // tiles owed after the last successful budget call
+    // mpc_delta_set_emphasis: the map budget calls weigh the tiles with; it says nothing about the receiver, so it outlives a failed call
+    GrowBuffer emphasis{GrowBuffer::kDevice};   // [tiles]
+    bool has_emphasis = false;
     ~mpc_delta() {
         if (stream) {
             (void)hipStreamSynchronize(stream);

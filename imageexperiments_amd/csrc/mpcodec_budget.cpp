@@ -3,6 +3,8 @@
 // table: every probe is the allocation kernel and one records-to-container job on the same records with the cut counts array.
 // And encode to a target quality ("quality"; DESIGN.md 4, "Encoder: a target quality"): the same start, then the sweep kernel's totals
 // at all 256 multipliers, the pick on the host, one allocation and one more container job.
+// Both with an emphasis map ("emphasis"; DESIGN.md 4, "Encoder: emphasis"): the same bodies with a map handed to the allocation and the
+// sweep, a null map being today's call.
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -13,6 +15,7 @@
 #include "mpc_internal.h"
 
 static_assert(mpc::kBudgetLambdas == MPC_BUDGET_LAMBDAS, "one size for the multiplier table");
+static_assert(mpc::kEmphasisNeutral == MPC_EMPHASIS_NEUTRAL && mpc::kEmphasisMax == MPC_EMPHASIS_MAX, "one range for the emphasis map");
 
 namespace {
 
@@ -26,9 +29,9 @@ mpc_status geometry(int width, int height, long long* tiles) {
     return MPC_OK;
 }
 
-// d_totals zeroed on `s`, then the kernel
-mpc_status allocate_on_device(const mpc_context* c, const uint32_t* d_profile, const uint16_t* d_counts, long long tiles, const uint32_t* weights,
-                              int j, uint8_t* d_depth, uint16_t* d_out_counts, unsigned long long* d_totals, hipStream_t s) {
+// d_totals zeroed on `s`, then the kernel.  d_emphasis: null = the plain allocation
+mpc_status allocate_on_device(const mpc_context* c, const uint32_t* d_profile, const uint16_t* d_counts, const uint8_t* d_emphasis, long long tiles,
+                              const uint32_t* weights, int j, uint8_t* d_depth, uint16_t* d_out_counts, unsigned long long* d_totals, hipStream_t s) {
     HIP_TRY(hipMemsetAsync(d_totals, 0, 3 * sizeof(unsigned long long), s));
     mpc::AllocateParams p{};
     p.profile = d_profile;
@@ -39,14 +42,16 @@ mpc_status allocate_on_device(const mpc_context* c, const uint32_t* d_profile, c
     p.depth = d_depth;
     p.out_counts = d_out_counts;
     p.totals = d_totals;
+    p.emphasis = d_emphasis;
     std::memcpy(p.weights, weights, sizeof(uint32_t) * 3 * static_cast<size_t>(c->K));
     const int err = mpc::launch_budget_allocate(p, s);
     if (err != 0) return launch_failed(err);
     return MPC_OK;
 }
 
-mpc_status encode_budget(mpc_context* c, const uint8_t* rgb, bool on_device, int width, int height, const double* quant, size_t budget,
-                         int index_interval, uint8_t** bytes, size_t* nbytes, uint8_t** index, size_t* index_bytes, uint8_t* depth,
+// emphasis: null = every tile counts the same; else `tiles` bytes, in device memory when on_device, which only the allocation reads
+mpc_status encode_budget(mpc_context* c, const uint8_t* rgb, bool on_device, const uint8_t* emphasis, int width, int height, const double* quant,
+                         size_t budget, int index_interval, uint8_t** bytes, size_t* nbytes, uint8_t** index, size_t* index_bytes, uint8_t* depth,
                          mpc_budget_info* info) {
     return guarded([&]() -> mpc_status {
         if (!c || !rgb || !bytes || !nbytes || !info) return fail(MPC_ERR_ARGUMENT, "null argument");
@@ -86,6 +91,7 @@ mpc_status encode_budget(mpc_context* c, const uint8_t* rgb, bool on_device, int
         uint8_t* d_depth[2] = {nullptr, nullptr};
         unsigned long long* d_words = nullptr;                      // the allocation's three totals, the full frame's SSE
         int* d_error = nullptr;
+        uint8_t* d_map = nullptr;                                   // a host emphasis map's copy
         const auto layout = [&](char* base) {
             Carve cv{base};
             d_frame = cv.take<uint8_t>(on_device ? 0 : row * static_cast<size_t>(height));
@@ -97,6 +103,7 @@ mpc_status encode_budget(mpc_context* c, const uint8_t* rgb, bool on_device, int
             d_depth[1] = cv.take<uint8_t>(static_cast<size_t>(tiles));
             d_words = cv.take<unsigned long long>(4);
             d_error = cv.take<int>(1);
+            d_map = cv.take<uint8_t>(emphasis && !on_device ? static_cast<size_t>(tiles) : 0);   // last: the layout in front is today's
             return cv.at;
         };
         if (const mpc_status gs = c->budget_dev.reserve(layout(nullptr), "budget staging"); gs != MPC_OK) return gs;
@@ -105,6 +112,11 @@ mpc_status encode_budget(mpc_context* c, const uint8_t* rgb, bool on_device, int
         if (!on_device) {
             HIP_TRY(hipMemcpyAsync(d_frame, rgb, row * static_cast<size_t>(height), hipMemcpyHostToDevice, s));
             frame = d_frame;
+        }
+        const uint8_t* d_emphasis = emphasis;
+        if (emphasis && !on_device) {
+            HIP_TRY(hipMemcpyAsync(d_map, emphasis, static_cast<size_t>(tiles), hipMemcpyHostToDevice, s));
+            d_emphasis = d_map;
         }
         HIP_TRY(hipMemsetAsync(d_words, 0, 4 * sizeof(unsigned long long), s));
         HIP_TRY(hipMemsetAsync(d_error, 0, sizeof(int), s));
@@ -152,7 +164,7 @@ mpc_status encode_budget(mpc_context* c, const uint8_t* rgb, bool on_device, int
             size_t probed_bytes = 0;                                // the last probe's size
             // 5. size(j): the container of the cut counts at j; kept when it fits
             const auto probe = [&](int j, bool* fits) -> mpc_status {
-                if (const mpc_status as = allocate_on_device(c, d_profile, d_counts, tiles, weights, j, d_depth[spare], d_cut, d_words, s); as != MPC_OK)
+                if (const mpc_status as = allocate_on_device(c, d_profile, d_counts, d_emphasis, tiles, weights, j, d_depth[spare], d_cut, d_words, s); as != MPC_OK)
                     return as;
                 ContainerMade made;
                 if (const mpc_status cs = records_container(c, tuning, s, d_cut, d_choices, tiles, width, height, quant, every, &made); cs != MPC_OK) return cs;
@@ -212,9 +224,9 @@ mpc_status encode_budget(mpc_context* c, const uint8_t* rgb, bool on_device, int
     });
 }
 
-// d_totals[768] zeroed on `s`, then the kernel
-mpc_status sweep_on_device(const mpc_context* c, const uint32_t* d_profile, const uint16_t* d_counts, long long tiles, const uint32_t* weights,
-                           unsigned long long* d_totals, hipStream_t s) {
+// d_totals[768] zeroed on `s`, then the kernel.  d_emphasis: null = the plain sweep
+mpc_status sweep_on_device(const mpc_context* c, const uint32_t* d_profile, const uint16_t* d_counts, const uint8_t* d_emphasis, long long tiles,
+                           const uint32_t* weights, unsigned long long* d_totals, hipStream_t s) {
     HIP_TRY(hipMemsetAsync(d_totals, 0, 3 * mpc::kBudgetLambdas * sizeof(unsigned long long), s));
     mpc::SweepParams p{};
     p.profile = d_profile;
@@ -222,6 +234,7 @@ mpc_status sweep_on_device(const mpc_context* c, const uint32_t* d_profile, cons
     p.tiles = tiles;
     p.K = c->K;
     p.totals = d_totals;
+    p.emphasis = d_emphasis;
     std::memcpy(p.weights, weights, sizeof(uint32_t) * 3 * static_cast<size_t>(c->K));
     const int err = mpc::launch_budget_sweep(p, s);
     if (err != 0) return launch_failed(err);
@@ -230,8 +243,8 @@ mpc_status sweep_on_device(const mpc_context* c, const uint32_t* d_profile, cons
 
 // mpc_encode_image_quality.  Steps 1 to 3 are encode_budget's and are written out again here, not shared: that function's order of
 // enqueues, its early return of the full container and its staging layout stay exactly what they were
-mpc_status encode_quality(mpc_context* c, const uint8_t* rgb, bool on_device, int width, int height, const double* quant, unsigned long long max_sse,
-                          int index_interval, uint8_t** bytes, size_t* nbytes, uint8_t** index, size_t* index_bytes, uint8_t* depth,
+mpc_status encode_quality(mpc_context* c, const uint8_t* rgb, bool on_device, const uint8_t* emphasis, int width, int height, const double* quant,
+                          unsigned long long max_sse, int index_interval, uint8_t** bytes, size_t* nbytes, uint8_t** index, size_t* index_bytes, uint8_t* depth,
                           mpc_quality_info* info) {
     return guarded([&]() -> mpc_status {
         if (!c || !rgb || !bytes || !nbytes || !info) return fail(MPC_ERR_ARGUMENT, "null argument");
@@ -270,6 +283,7 @@ mpc_status encode_quality(mpc_context* c, const uint8_t* rgb, bool on_device, in
         unsigned long long* d_sweep = nullptr;                      // the sweep's 768 totals
         unsigned long long* d_words = nullptr;                      // the allocation's three totals, the full frame's SSE
         int* d_error = nullptr;
+        uint8_t* d_map = nullptr;                                   // a host emphasis map's copy
         const auto layout = [&](char* base) {
             Carve cv{base};
             d_frame = cv.take<uint8_t>(on_device ? 0 : row * static_cast<size_t>(height));
@@ -281,6 +295,7 @@ mpc_status encode_quality(mpc_context* c, const uint8_t* rgb, bool on_device, in
             d_sweep = cv.take<unsigned long long>(3 * mpc::kBudgetLambdas);
             d_words = cv.take<unsigned long long>(4);
             d_error = cv.take<int>(1);
+            d_map = cv.take<uint8_t>(emphasis && !on_device ? static_cast<size_t>(tiles) : 0);   // last: the layout in front is today's
             return cv.at;
         };
         if (const mpc_status gs = c->budget_dev.reserve(layout(nullptr), "quality staging"); gs != MPC_OK) return gs;
@@ -289,6 +304,11 @@ mpc_status encode_quality(mpc_context* c, const uint8_t* rgb, bool on_device, in
         if (!on_device) {
             HIP_TRY(hipMemcpyAsync(d_frame, rgb, row * static_cast<size_t>(height), hipMemcpyHostToDevice, s));
             frame = d_frame;
+        }
+        const uint8_t* d_emphasis = emphasis;
+        if (emphasis && !on_device) {
+            HIP_TRY(hipMemcpyAsync(d_map, emphasis, static_cast<size_t>(tiles), hipMemcpyHostToDevice, s));
+            d_emphasis = d_map;
         }
         HIP_TRY(hipMemsetAsync(d_words, 0, 4 * sizeof(unsigned long long), s));
         HIP_TRY(hipMemsetAsync(d_error, 0, sizeof(int), s));
@@ -316,7 +336,7 @@ mpc_status encode_quality(mpc_context* c, const uint8_t* rgb, bool on_device, in
         if (verdict != 0) return fail(MPC_ERR_HIP, "the full container's seek index does not read back");
         if (const mpc_status ps = profile_on_device(c, d_counts, d_choices, quant, frame, width, height, d_profile, d_error, s); ps != MPC_OK) return ps;
         // 4. the sweep: one launch for all 256 multipliers, its totals to the host
-        if (const mpc_status ss = sweep_on_device(c, d_profile, d_counts, tiles, weights, d_sweep, s); ss != MPC_OK) return ss;
+        if (const mpc_status ss = sweep_on_device(c, d_profile, d_counts, d_emphasis, tiles, weights, d_sweep, s); ss != MPC_OK) return ss;
         std::vector<unsigned long long> totals(3 * mpc::kBudgetLambdas);
         unsigned long long full_sse = 0;
         int error_word = 0;
@@ -334,7 +354,7 @@ mpc_status encode_quality(mpc_context* c, const uint8_t* rgb, bool on_device, in
         if (j < 0)
             return fail(MPC_ERR_ARGUMENT, "a squared error of at most %llu: the best that cutting this frame's records reaches is %llu", max_sse, totals[0]);
         // 7. the allocation at j
-        if (const mpc_status as = allocate_on_device(c, d_profile, d_counts, tiles, weights, j, d_depth, d_cut, d_words, s); as != MPC_OK) return as;
+        if (const mpc_status as = allocate_on_device(c, d_profile, d_counts, d_emphasis, tiles, weights, j, d_depth, d_cut, d_words, s); as != MPC_OK) return as;
         // 8. its container, the index with it if asked for
         ContainerMade made;
         if (const mpc_status cs = records_container(c, tuning, s, d_cut, d_choices, tiles, width, height, quant, every, &made); cs != MPC_OK) return cs;
@@ -430,27 +450,33 @@ mpc_status mpc_depth_profile_device(mpc_context* c, const uint16_t* d_counts, co
     });
 }
 
-mpc_status mpc_budget_allocate_device(mpc_context* c, const uint32_t* d_profile, const uint16_t* d_counts, long long tiles, const uint32_t* weights,
-                                      int j, uint8_t* d_depth, uint16_t* d_out_counts, unsigned long long* d_totals, void* stream) {
+mpc_status mpc_budget_allocate_emphasis_device(mpc_context* c, const uint32_t* d_profile, const uint16_t* d_counts, const uint8_t* d_emphasis,
+                                               long long tiles, const uint32_t* weights, int j, uint8_t* d_depth, uint16_t* d_out_counts,
+                                               unsigned long long* d_totals, void* stream) {
     return guarded([&]() -> mpc_status {
         if (!c || !d_profile || !d_counts || !weights || !d_depth || !d_out_counts || !d_totals) return fail(MPC_ERR_ARGUMENT, "null argument");
         if (c->device < 0) return no_device();
         if (tiles < 1 || tiles * 3 >= (1LL << 31) || j < 0 || j >= mpc::kBudgetLambdas) return fail(MPC_ERR_ARGUMENT, "tiles %lld, multiplier %d", tiles, j);
         HIP_TRY(hipSetDevice(c->device));
         if (const mpc_status cs = refuse_capture(stream); cs != MPC_OK) return cs;
-        return allocate_on_device(c, d_profile, d_counts, tiles, weights, j, d_depth, d_out_counts, d_totals, static_cast<hipStream_t>(stream));
+        return allocate_on_device(c, d_profile, d_counts, d_emphasis, tiles, weights, j, d_depth, d_out_counts, d_totals, static_cast<hipStream_t>(stream));
     });
+}
+
+mpc_status mpc_budget_allocate_device(mpc_context* c, const uint32_t* d_profile, const uint16_t* d_counts, long long tiles, const uint32_t* weights,
+                                      int j, uint8_t* d_depth, uint16_t* d_out_counts, unsigned long long* d_totals, void* stream) {
+    return mpc_budget_allocate_emphasis_device(c, d_profile, d_counts, nullptr, tiles, weights, j, d_depth, d_out_counts, d_totals, stream);
 }
 
 mpc_status mpc_encode_image_budget(mpc_context* c, const uint8_t* rgb, int width, int height, const double* quant, size_t budget, int index_interval,
                                    uint8_t** bytes, size_t* nbytes, uint8_t** index, size_t* index_bytes, uint8_t* depth, mpc_budget_info* info) {
-    return encode_budget(c, rgb, false, width, height, quant, budget, index_interval, bytes, nbytes, index, index_bytes, depth, info);
+    return encode_budget(c, rgb, false, nullptr, width, height, quant, budget, index_interval, bytes, nbytes, index, index_bytes, depth, info);
 }
 
 mpc_status mpc_encode_image_budget_device(mpc_context* c, const uint8_t* d_rgb, int width, int height, const double* quant, size_t budget,
                                           int index_interval, uint8_t** bytes, size_t* nbytes, uint8_t** index, size_t* index_bytes, uint8_t* depth,
                                           mpc_budget_info* info) {
-    return encode_budget(c, d_rgb, true, width, height, quant, budget, index_interval, bytes, nbytes, index, index_bytes, depth, info);
+    return encode_budget(c, d_rgb, true, nullptr, width, height, quant, budget, index_interval, bytes, nbytes, index, index_bytes, depth, info);
 }
 
 mpc_status mpc_budget_sweep(const uint32_t* profile, const uint16_t* counts, long long tiles, int K, const uint32_t* weights, uint64_t* totals) {
@@ -476,28 +502,111 @@ mpc_status mpc_sse_for_psnr(double psnr, int width, int height, uint64_t* max_ss
     });
 }
 
-mpc_status mpc_budget_sweep_device(mpc_context* c, const uint32_t* d_profile, const uint16_t* d_counts, long long tiles, const uint32_t* weights,
-                                   unsigned long long* d_totals, void* stream) {
+mpc_status mpc_budget_sweep_emphasis_device(mpc_context* c, const uint32_t* d_profile, const uint16_t* d_counts, const uint8_t* d_emphasis,
+                                            long long tiles, const uint32_t* weights, unsigned long long* d_totals, void* stream) {
     return guarded([&]() -> mpc_status {
         if (!c || !d_profile || !d_counts || !weights || !d_totals) return fail(MPC_ERR_ARGUMENT, "null argument");
         if (c->device < 0) return no_device();
         if (tiles < 1 || tiles * 3 >= (1LL << 31)) return fail(MPC_ERR_ARGUMENT, "tiles %lld", tiles);
         HIP_TRY(hipSetDevice(c->device));
         if (const mpc_status cs = refuse_capture(stream); cs != MPC_OK) return cs;
-        return sweep_on_device(c, d_profile, d_counts, tiles, weights, d_totals, static_cast<hipStream_t>(stream));
+        return sweep_on_device(c, d_profile, d_counts, d_emphasis, tiles, weights, d_totals, static_cast<hipStream_t>(stream));
     });
+}
+
+mpc_status mpc_budget_sweep_device(mpc_context* c, const uint32_t* d_profile, const uint16_t* d_counts, long long tiles, const uint32_t* weights,
+                                   unsigned long long* d_totals, void* stream) {
+    return mpc_budget_sweep_emphasis_device(c, d_profile, d_counts, nullptr, tiles, weights, d_totals, stream);
 }
 
 mpc_status mpc_encode_image_quality(mpc_context* c, const uint8_t* rgb, int width, int height, const double* quant, unsigned long long max_sse,
                                     int index_interval, uint8_t** bytes, size_t* nbytes, uint8_t** index, size_t* index_bytes, uint8_t* depth,
                                     mpc_quality_info* info) {
-    return encode_quality(c, rgb, false, width, height, quant, max_sse, index_interval, bytes, nbytes, index, index_bytes, depth, info);
+    return encode_quality(c, rgb, false, nullptr, width, height, quant, max_sse, index_interval, bytes, nbytes, index, index_bytes, depth, info);
 }
 
 mpc_status mpc_encode_image_quality_device(mpc_context* c, const uint8_t* d_rgb, int width, int height, const double* quant,
                                            unsigned long long max_sse, int index_interval, uint8_t** bytes, size_t* nbytes, uint8_t** index,
                                            size_t* index_bytes, uint8_t* depth, mpc_quality_info* info) {
-    return encode_quality(c, d_rgb, true, width, height, quant, max_sse, index_interval, bytes, nbytes, index, index_bytes, depth, info);
+    return encode_quality(c, d_rgb, true, nullptr, width, height, quant, max_sse, index_interval, bytes, nbytes, index, index_bytes, depth, info);
+}
+
+// ---- emphasis maps ----
+mpc_status mpc_budget_allocate_emphasis(const uint32_t* profile, const uint16_t* counts, const uint8_t* emphasis, long long tiles, int K,
+                                        const uint32_t* weights, int j, uint8_t* depth, uint16_t* out_counts, uint64_t* totals) {
+    return guarded([&]() -> mpc_status {
+        if (!profile || !counts || !weights || !totals) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (tiles < 0 || K < 1 || K > MPC_MAX_K || j < 0 || j >= mpc::kBudgetLambdas) return fail(MPC_ERR_ARGUMENT, "tiles %lld, K %d, multiplier %d", tiles, K, j);
+        mpc::budget_allocate_emphasis(profile, counts, emphasis, tiles, K, weights, j, depth, out_counts, totals);
+        return MPC_OK;
+    });
+}
+
+mpc_status mpc_budget_sweep_emphasis(const uint32_t* profile, const uint16_t* counts, const uint8_t* emphasis, long long tiles, int K,
+                                     const uint32_t* weights, uint64_t* totals) {
+    return guarded([&]() -> mpc_status {
+        if (!profile || !counts || !weights || !totals) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (tiles < 0 || K < 1 || K > MPC_MAX_K) return fail(MPC_ERR_ARGUMENT, "tiles %lld, K %d", tiles, K);
+        mpc::budget_sweep_emphasis(profile, counts, emphasis, tiles, K, weights, totals);
+        return MPC_OK;
+    });
+}
+
+namespace {
+mpc_status mask_arguments(const void* mask, int width, int height, size_t row_stride, int lo, int hi, const void* emphasis) {
+    if (!mask || !emphasis) return fail(MPC_ERR_ARGUMENT, "null argument");
+    long long tiles = 0;
+    if (const mpc_status gs = geometry(width, height, &tiles); gs != MPC_OK) return gs;
+    if (row_stride < static_cast<size_t>(width)) return fail(MPC_ERR_ARGUMENT, "row_stride %zu for %d mask bytes", row_stride, width);
+    if (lo < 1 || hi < lo || hi > MPC_EMPHASIS_MAX) return fail(MPC_ERR_ARGUMENT, "emphasis from %d to %d: 1 <= lo <= hi <= %d", lo, hi, MPC_EMPHASIS_MAX);
+    return MPC_OK;
+}
+}  // namespace
+
+mpc_status mpc_emphasis_from_mask(const uint8_t* mask, int width, int height, size_t row_stride, int lo, int hi, uint8_t* emphasis) {
+    return guarded([&]() -> mpc_status {
+        if (const mpc_status as = mask_arguments(mask, width, height, row_stride, lo, hi, emphasis); as != MPC_OK) return as;
+        mpc::emphasis_from_mask(mask, width, height, row_stride, lo, hi, emphasis);
+        return MPC_OK;
+    });
+}
+
+mpc_status mpc_emphasis_from_mask_device(mpc_context* c, const uint8_t* d_mask, int width, int height, size_t row_stride, int lo, int hi,
+                                         uint8_t* d_emphasis, void* stream) {
+    return guarded([&]() -> mpc_status {
+        if (!c) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (const mpc_status as = mask_arguments(d_mask, width, height, row_stride, lo, hi, d_emphasis); as != MPC_OK) return as;
+        if (c->device < 0) return no_device();
+        HIP_TRY(hipSetDevice(c->device));
+        if (const mpc_status cs = refuse_capture(stream); cs != MPC_OK) return cs;
+        const int err = mpc::launch_emphasis_mask(d_mask, width, height, row_stride, lo, hi, d_emphasis, stream);
+        if (err != 0) return launch_failed(err);
+        return MPC_OK;
+    });
+}
+
+mpc_status mpc_encode_image_budget_emphasis(mpc_context* c, const uint8_t* rgb, const uint8_t* emphasis, int width, int height, const double* quant,
+                                            size_t budget, int index_interval, uint8_t** bytes, size_t* nbytes, uint8_t** index, size_t* index_bytes,
+                                            uint8_t* depth, mpc_budget_info* info) {
+    return encode_budget(c, rgb, false, emphasis, width, height, quant, budget, index_interval, bytes, nbytes, index, index_bytes, depth, info);
+}
+
+mpc_status mpc_encode_image_budget_emphasis_device(mpc_context* c, const uint8_t* d_rgb, const uint8_t* d_emphasis, int width, int height,
+                                                   const double* quant, size_t budget, int index_interval, uint8_t** bytes, size_t* nbytes,
+                                                   uint8_t** index, size_t* index_bytes, uint8_t* depth, mpc_budget_info* info) {
+    return encode_budget(c, d_rgb, true, d_emphasis, width, height, quant, budget, index_interval, bytes, nbytes, index, index_bytes, depth, info);
+}
+
+mpc_status mpc_encode_image_quality_emphasis(mpc_context* c, const uint8_t* rgb, const uint8_t* emphasis, int width, int height, const double* quant,
+                                             unsigned long long max_sse, int index_interval, uint8_t** bytes, size_t* nbytes, uint8_t** index,
+                                             size_t* index_bytes, uint8_t* depth, mpc_quality_info* info) {
+    return encode_quality(c, rgb, false, emphasis, width, height, quant, max_sse, index_interval, bytes, nbytes, index, index_bytes, depth, info);
+}
+
+mpc_status mpc_encode_image_quality_emphasis_device(mpc_context* c, const uint8_t* d_rgb, const uint8_t* d_emphasis, int width, int height,
+                                                    const double* quant, unsigned long long max_sse, int index_interval, uint8_t** bytes,
+                                                    size_t* nbytes, uint8_t** index, size_t* index_bytes, uint8_t* depth, mpc_quality_info* info) {
+    return encode_quality(c, d_rgb, true, d_emphasis, width, height, quant, max_sse, index_interval, bytes, nbytes, index, index_bytes, depth, info);
 }
 
 }  // extern "C"

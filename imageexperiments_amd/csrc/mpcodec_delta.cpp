@@ -171,6 +171,27 @@ mpc_status mpc_delta_changed(const mpc_delta* d, int32_t* tiles, int capacity, i
     return MPC_OK;
 }
 
+mpc_status mpc_delta_set_emphasis(mpc_delta* d, const uint8_t* emphasis, int tiles) {
+    return guarded([&]() -> mpc_status {
+        if (!d) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (emphasis && tiles != d->tiles) return fail(MPC_ERR_ARGUMENT, "an emphasis map of %d tiles, the session has %lld", tiles, d->tiles);
+        mpc_context* c = d->ctx;
+        if (c->device < 0) return delta_no_device();
+        std::lock_guard<std::recursive_mutex> one_host_call(c->host_calls);
+        if (!emphasis) {
+            d->has_emphasis = false;
+            return MPC_OK;
+        }
+        HIP_TRY(hipSetDevice(c->device));
+        if (const mpc_status gs = d->emphasis.reserve(static_cast<size_t>(d->tiles), "emphasis map"); gs != MPC_OK) return gs;
+        // the session's calls are synchronous: nothing on its stream reads the old map
+        d->has_emphasis = false;
+        HIP_TRY(hipMemcpy(d->emphasis.data(), emphasis, static_cast<size_t>(d->tiles), hipMemcpyHostToDevice));
+        d->has_emphasis = true;
+        return MPC_OK;
+    });
+}
+
 }  // extern "C"
 
 // ---- a call in stages: mpc_delta_encode and mpc_delta_encode_patch share the first three, so the session's store advances

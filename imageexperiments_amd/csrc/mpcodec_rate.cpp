@@ -89,13 +89,35 @@ mpc_status mpc_gather_records_device(mpc_context* c, const uint16_t* d_counts, c
     });
 }
 
+mpc_status mpc_budget_allocate_floor_emphasis(const uint32_t* profile, const uint16_t* counts, const uint8_t* floor, const uint8_t* must,
+                                              const uint8_t* emphasis, const int32_t* list, long long tiles, long long n, int K,
+                                              const uint32_t* weights, int j, uint8_t* depth, uint16_t* out_counts, uint8_t* send, uint64_t* totals) {
+    return guarded([&]() -> mpc_status {
+        if (!profile || !counts || !weights || !totals) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (n < 0 || K < 1 || K > MPC_MAX_K || j < 0 || j >= mpc::kBudgetLambdas) return fail(MPC_ERR_ARGUMENT, "tiles %lld, K %d, multiplier %d", n, K, j);
+        if (emphasis && (tiles < 1 || (!list && n > tiles))) return fail(MPC_ERR_ARGUMENT, "%lld candidates, an emphasis map of %lld tiles", n, tiles);
+        mpc::budget_allocate_floor_emphasis(profile, counts, floor, must, emphasis, list, tiles, n, K, weights, j, depth, out_counts, send, totals);
+        return MPC_OK;
+    });
+}
+
 mpc_status mpc_budget_allocate_floor_device(mpc_context* c, const uint32_t* d_profile, const uint16_t* d_counts, const uint8_t* d_floor,
                                             const uint8_t* d_must, long long n, const uint32_t* weights, int j, uint8_t* d_depth,
                                             uint16_t* d_out_counts, uint8_t* d_send, unsigned long long* d_totals, void* stream) {
+    return mpc_budget_allocate_floor_emphasis_device(c, d_profile, d_counts, d_floor, d_must, nullptr, nullptr, 0, n, weights, j, d_depth, d_out_counts,
+                                                     d_send, d_totals, stream);
+}
+
+mpc_status mpc_budget_allocate_floor_emphasis_device(mpc_context* c, const uint32_t* d_profile, const uint16_t* d_counts, const uint8_t* d_floor,
+                                                     const uint8_t* d_must, const uint8_t* d_emphasis, const int32_t* d_list, long long tiles,
+                                                     long long n, const uint32_t* weights, int j, uint8_t* d_depth, uint16_t* d_out_counts,
+                                                     uint8_t* d_send, unsigned long long* d_totals, void* stream) {
     return guarded([&]() -> mpc_status {
         if (!c || !d_profile || !d_counts || !weights || !d_depth || !d_out_counts || !d_send || !d_totals) return fail(MPC_ERR_ARGUMENT, "null argument");
         if (c->device < 0) return delta_no_device();
         if (n < 1 || n * 3 >= (1LL << 31) || j < 0 || j >= mpc::kBudgetLambdas) return fail(MPC_ERR_ARGUMENT, "tiles %lld, multiplier %d", n, j);
+        if (d_emphasis && (tiles < 1 || tiles >= (1LL << 31) || (!d_list && n > tiles)))
+            return fail(MPC_ERR_ARGUMENT, "%lld candidates, an emphasis map of %lld tiles", n, tiles);
         HIP_TRY(hipSetDevice(c->device));
         if (const mpc_status cs = refuse_capture(stream); cs != MPC_OK) return cs;
         hipStream_t s = static_cast<hipStream_t>(stream);
@@ -112,6 +134,9 @@ mpc_status mpc_budget_allocate_floor_device(mpc_context* c, const uint32_t* d_pr
         p.out_counts = d_out_counts;
         p.send = d_send;
         p.totals = d_totals;
+        p.emphasis = d_emphasis;
+        p.list = d_emphasis ? d_list : nullptr;
+        p.tiles = tiles;
         std::memcpy(p.weights, weights, sizeof(uint32_t) * 3 * static_cast<size_t>(c->K));
         if (const int e = mpc::launch_budget_allocate_floor(p, s); e != 0) return launch_failed(e);
         return MPC_OK;
@@ -327,6 +352,11 @@ mpc_status rate_finish(mpc_delta* d, const DeltaCall& call, hipStream_t s, const
                 ap.out_counts = b.cut;
                 ap.send = b.send;
                 ap.totals = b.totals;
+                if (d->has_emphasis) {                           // candidate i is tile cand[i]; a key frame's candidates are the tiles themselves
+                    ap.emphasis = reinterpret_cast<const uint8_t*>(d->emphasis.data());
+                    ap.list = call.key ? nullptr : b.cand;
+                    ap.tiles = T;
+                }
                 std::memcpy(ap.weights, weights, sizeof(uint32_t) * 3 * static_cast<size_t>(K));
                 if (const int e = mpc::launch_budget_allocate_floor(ap, s); e != 0) return launch_failed(e);
                 long long k = m;                                 // a key frame sends every tile

@@ -1323,6 +1323,92 @@ mpc_status mpc_rate_distortion(mpc_context* ctx, const uint8_t* rgb, int width, 
 mpc_status mpc_rate_distortion_device(mpc_context* ctx, const uint8_t* d_rgb, int width, int height, const double* quants,
                                       int n_levels, size_t* nbytes, unsigned long long* sse, double* psnr, uint8_t** bytes);
 
+/* ---- emphasis: budget, quality and rate encodes weigh tiles ("Encoder: emphasis") ----
+ * The three encoders that cut a frame to a constraint minimise the plain squared error of the whole frame: every tile counts the same.
+ * An emphasis map says where the bytes matter -- a face, the text under the cursor, a saliency network's output -- as one factor per
+ * tile on the distortion term of the allocation.  Everything downstream (the depth cut, the container job, the patch, every decoder) is
+ * untouched.  P, W, R, L[j], floor, must and the totals are the budget, quality and rate sections'; tile t = tx * tiles_y + ty as
+ * everywhere.  Host and device agree bit for bit on everything defined here.
+ *
+ * EMPHASIS  e[t], one u8 per tile of the frame, four fractional bits: MPC_EMPHASIS_NEUTRAL = 16 is the factor 1, the range is
+ * 1 ... MPC_EMPHASIS_MAX = 64 (1/16 ... 4).  A stored 0 is used as 1 and a value above 64 as 64 (the "count above K is used as K"
+ * rule); no address ever comes from an emphasis value.
+ * ALLOCATION AT j WITH EMPHASIS  J(t, n) = P[t][n] * e[t] * 4096 + L[j] * R[t][n] in u64; depth[t] = the smallest n that minimises J;
+ * out_counts as in mpc_budget_allocate; totals[0] = the sum of the UNWEIGHTED P[t][depth[t]], the true squared error that
+ * mpc_decode_image shows; totals[1] and [2] as there.  With e = 16 everywhere it is mpc_budget_allocate, bit for bit.
+ * BOUNDS  P <= 64 * 3 * 255^2 = 12 484 800, hence P * 64 * 4096 <= 3.28e12 < 14 * 2^39 = 7.70e12, the cost of the cheapest record at
+ * j = 255: there every depth is still 0, the budget search keeps its feasible end, and J stays below 2^63.
+ * SWEEP WITH EMPHASIS  S[j][k] are exactly those totals at every j.  Scaling a tile's P by a positive constant leaves the optimality
+ * argument intact: a tile's P at its minimiser does not fall as L rises, so S[j][0], the true squared error, still never falls along
+ * the ladder, and mpc_quality_pick is used unchanged.  A quality target stays a promise about the frame's true error; emphasis only
+ * decides where the remaining error lies.
+ * FLOOR ALLOCATION WITH EMPHASIS  the rate section's, with the same J over R'.  Candidate i takes e[list[i]], list == NULL the
+ * identity; a list entry outside [0, tiles) takes the neutral value.  totals[0] is unweighted.
+ * MASK TO EMPHASIS  from a u8 mask at pixel resolution, width x height, row_stride >= width bytes a row, any alignment; the bytes
+ * between rows are never read.  e[t] = lo + ((hi - lo) * m + 127) / 255, m the maximum of the mask over the pixels of tile t that lie
+ * inside the frame; 1 <= lo <= hi <= 64.
+ *
+ * Host only, no context, safe on several threads; they define what the kernels compute.  emphasis: `tiles` bytes, NULL = neutral:
+ *   mpc_budget_allocate_emphasis, mpc_budget_sweep_emphasis   mpc_budget_allocate's and mpc_budget_sweep's arguments and refusals
+ *   mpc_budget_allocate_floor_emphasis   mpc_budget_allocate_floor's, and with a map: tiles >= 1, and n <= tiles where list is NULL
+ *   mpc_emphasis_from_mask               emphasis[tiles of the geometry].  MPC_ERR_ARGUMENT: a null pointer, a geometry outside
+ *                                        mpc_rate_distortion's, row_stride < width, lo or hi outside 1 <= lo <= hi <= 64
+ * On the caller's buffers, asynchronous on `stream`, with their siblings' contract: ordered on the caller's stream, a capturing stream
+ * refused with nothing enqueued, MPC_ERR_NO_DEVICE for a host-only context, the host forms' argument refusals:
+ *   mpc_budget_allocate_emphasis_device, mpc_budget_sweep_emphasis_device, mpc_budget_allocate_floor_emphasis_device
+ *                                        d_emphasis (and d_list): device memory, NULL = the sibling itself, the same kernel
+ *   mpc_emphasis_from_mask_device        d_mask and d_emphasis in device memory; one pass over the mask
+ *
+ * mpc_encode_image_budget_emphasis[_device], mpc_encode_image_quality_emphasis[_device]: today's calls with a map (host form: host
+ * memory, `tiles` bytes; _device: device memory) handed to every allocation and to the sweep.  NULL: byte for byte today's call, with
+ * the same info.  The search, the step numbering, the refusals and "leaves the context as it found it" are those calls'; the budget
+ * form still returns F untouched when |F| <= budget, and info->sse stays the true squared error of the result, so the quality form
+ * still promises info->sse <= max_sse at the largest such j.  NOT promised, as today: a minimal byte count, or one monotone in the
+ * constraint.
+ *
+ * mpc_delta_set_emphasis: the map (host memory, `tiles` bytes) is copied into the session's device memory and weighs every later
+ * mpc_delta_encode_patch_budget until set again; NULL (tiles ignored) = none.  It does not invalidate the sent map: depths already sent
+ * stay true.  MPC_ERR_ARGUMENT for a tile count that is not the session's; the session stays as it was.  mpc_delta_encode and
+ * mpc_delta_encode_patch ignore it.  A KEY budget call's container is byte for byte
+ * mpc_encode_image_budget_emphasis_device(frame, budget - 40, the same map)'s, with its lambda_index and probes. */
+#define MPC_EMPHASIS_NEUTRAL 16
+#define MPC_EMPHASIS_MAX 64
+mpc_status mpc_budget_allocate_emphasis(const uint32_t* profile, const uint16_t* counts, const uint8_t* emphasis, long long tiles, int K,
+                                        const uint32_t* weights, int j, uint8_t* depth, uint16_t* out_counts, uint64_t* totals /* [3] */);
+mpc_status mpc_budget_sweep_emphasis(const uint32_t* profile, const uint16_t* counts, const uint8_t* emphasis, long long tiles, int K,
+                                     const uint32_t* weights, uint64_t* totals /* [256 * 3] */);
+mpc_status mpc_budget_allocate_floor_emphasis(const uint32_t* profile, const uint16_t* counts, const uint8_t* floor, const uint8_t* must,
+                                              const uint8_t* emphasis, const int32_t* list, long long tiles, long long n, int K,
+                                              const uint32_t* weights, int j, uint8_t* depth, uint16_t* out_counts, uint8_t* send,
+                                              uint64_t* totals /* [4] */);
+mpc_status mpc_emphasis_from_mask(const uint8_t* mask, int width, int height, size_t row_stride, int lo, int hi, uint8_t* emphasis);
+mpc_status mpc_budget_allocate_emphasis_device(mpc_context* ctx, const uint32_t* d_profile, const uint16_t* d_counts, const uint8_t* d_emphasis,
+                                               long long tiles, const uint32_t* weights, int j, uint8_t* d_depth, uint16_t* d_out_counts,
+                                               unsigned long long* d_totals, void* stream);
+mpc_status mpc_budget_sweep_emphasis_device(mpc_context* ctx, const uint32_t* d_profile, const uint16_t* d_counts, const uint8_t* d_emphasis,
+                                            long long tiles, const uint32_t* weights, unsigned long long* d_totals /* [768] */, void* stream);
+mpc_status mpc_budget_allocate_floor_emphasis_device(mpc_context* ctx, const uint32_t* d_profile, const uint16_t* d_counts,
+                                                     const uint8_t* d_floor, const uint8_t* d_must, const uint8_t* d_emphasis,
+                                                     const int32_t* d_list, long long tiles, long long n, const uint32_t* weights, int j,
+                                                     uint8_t* d_depth, uint16_t* d_out_counts, uint8_t* d_send, unsigned long long* d_totals,
+                                                     void* stream);
+mpc_status mpc_emphasis_from_mask_device(mpc_context* ctx, const uint8_t* d_mask, int width, int height, size_t row_stride, int lo, int hi,
+                                         uint8_t* d_emphasis, void* stream);
+mpc_status mpc_encode_image_budget_emphasis(mpc_context* ctx, const uint8_t* rgb, const uint8_t* emphasis, int width, int height,
+                                            const double* quant, size_t budget, int index_interval, uint8_t** bytes, size_t* nbytes,
+                                            uint8_t** index, size_t* index_bytes, uint8_t* depth, mpc_budget_info* info);
+mpc_status mpc_encode_image_budget_emphasis_device(mpc_context* ctx, const uint8_t* d_rgb, const uint8_t* d_emphasis, int width, int height,
+                                                   const double* quant, size_t budget, int index_interval, uint8_t** bytes, size_t* nbytes,
+                                                   uint8_t** index, size_t* index_bytes, uint8_t* depth, mpc_budget_info* info);
+mpc_status mpc_encode_image_quality_emphasis(mpc_context* ctx, const uint8_t* rgb, const uint8_t* emphasis, int width, int height,
+                                             const double* quant, unsigned long long max_sse, int index_interval, uint8_t** bytes,
+                                             size_t* nbytes, uint8_t** index, size_t* index_bytes, uint8_t* depth, mpc_quality_info* info);
+mpc_status mpc_encode_image_quality_emphasis_device(mpc_context* ctx, const uint8_t* d_rgb, const uint8_t* d_emphasis, int width, int height,
+                                                    const double* quant, unsigned long long max_sse, int index_interval, uint8_t** bytes,
+                                                    size_t* nbytes, uint8_t** index, size_t* index_bytes, uint8_t* depth,
+                                                    mpc_quality_info* info);
+mpc_status mpc_delta_set_emphasis(mpc_delta* d, const uint8_t* emphasis /* host, tiles bytes, or NULL */, int tiles);
+
 /* ---- patch index: a patch that carries its container's seek index ("Delta stream") ----
  * The receiver of a version-1 patch parses the container's entropy codes on the host, serially: the cost follows the bytes.  A
  * version-2 patch brings the seek index of its container along, and mpc_patch_apply hands container and index to the sequence
