@@ -401,6 +401,19 @@ def _bind_bitstream(L):
     except AttributeError:
         if not os.environ.get("MPCODEC_LIB"):             # an older build may be loaded for A/B timing only
             raise
+    try:
+        L.mpc_changed_tiles_tolerance.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_uint32, _i32p, C.POINTER(C.c_int),
+                                                  _u32p]
+        L.mpc_tile_diff_tolerance_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_uint32, vp, vp, vp, vp]
+        L.mpc_delta_set_tolerance.argtypes = [vp, C.c_uint32]
+        L.mpc_delta_tolerance.argtypes = [vp]
+        L.mpc_delta_tolerance.restype = C.c_uint32
+        L.mpc_delta_held.argtypes = [vp, C.POINTER(C.c_int), _u64p]
+        L.mpc_delta_frame.argtypes = [vp, vp, C.c_size_t]
+        L.mpc_delta_frame_device.argtypes = [vp, C.POINTER(vp)]
+    except AttributeError:
+        if not os.environ.get("MPCODEC_LIB"):             # an older build may be loaded for A/B timing only
+            raise
     L.mpc_parse_container_view_device.argtypes = [vp] + _vparse
     L.mpc_decode_views_indexed.argtypes = [vp, C.POINTER(_u8p), C.POINTER(C.c_size_t), C.POINTER(_u8p), C.POINTER(C.c_size_t), _vwp, C.c_int,
                                            C.c_uint, C.POINTER(_u8p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -852,6 +865,30 @@ def changed_tiles(prev, cur, block_size=8):
     return tiles[:n.value].copy()
 
 
+def changed_tiles_tolerance(prev, cur, tolerance, block_size=8):
+    """mpc_changed_tiles_tolerance: the host's definition of the delta encoder's tolerant diff on two equally sized HxWx3 uint8 frames ->
+    (the tiles whose summed squared byte difference exceeds `tolerance`, ascending, int32; every tile's sum, uint32; the composite the
+    encoder keeps: `cur` in the listed tiles, `prev` in every other, HxWx3 uint8).  Strided views keep their row strides; only pixel
+    bytes are read."""
+    L = load_library()
+    prev, cur = _pixel_rows(prev), _pixel_rows(cur)
+    if prev.shape != cur.shape:
+        raise ValueError("frames must have the same size")
+    H, W = cur.shape[:2]
+    bs = max(int(block_size), 1)
+    tx, ty = -(-W // bs), -(-H // bs)
+    tiles = np.zeros(max(tx * ty, 1), np.int32)
+    sse = np.zeros(max(tx * ty, 1), np.uint32)
+    n = C.c_int(0)
+    _check(L.mpc_changed_tiles_tolerance(prev.ctypes.data, prev.strides[0], cur.ctypes.data, cur.strides[0], W, H, int(block_size),
+                                         int(tolerance), tiles.ctypes.data_as(_i32p), C.byref(n), sse.ctypes.data_as(_u32p)))
+    composite = np.array(prev)
+    for t in tiles[:n.value]:
+        cx, cy = divmod(int(t), ty)
+        composite[cy * bs:cy * bs + bs, cx * bs:cx * bs + bs] = cur[cy * bs:cy * bs + bs, cx * bs:cx * bs + bs]
+    return tiles[:n.value].copy(), sse[:tx * ty].copy(), composite
+
+
 def delta_pack_geometry(n, rows=MPC_DELTA_PACK_ROWS):
     """mpc_delta_pack_geometry: the packed frame of n listed tiles with at most `rows` tile rows -> (R, C, stride, bytes): R x C whole
     tiles, listed tile j at tile (j // R, j % R), `stride` = 24 * C bytes between pixel rows."""
@@ -988,6 +1025,38 @@ class DeltaEncoder:
             return
         emphasis = np.ascontiguousarray(emphasis, np.uint8).reshape(-1)
         _check(self.L.mpc_delta_set_emphasis(self.h, emphasis.ctypes.data_as(_u8p), emphasis.size))
+
+    def set_tolerance(self, tolerance):
+        """mpc_delta_set_tolerance: from the next call on a tile is changed iff the summed squared difference of its pixel bytes against
+        the pixels last sent exceeds `tolerance` (uint32; 0 = any differing byte, the default).  No key frame follows from it."""
+        if not 0 <= int(tolerance) < 2**32:
+            raise ValueError("tolerance: 0 ... 2^32 - 1")
+        _check(self.L.mpc_delta_set_tolerance(self.h, int(tolerance)))
+
+    @property
+    def tolerance(self):
+        """mpc_delta_tolerance"""
+        return int(self.L.mpc_delta_tolerance(self.h))
+
+    def held(self):
+        """mpc_delta_held: (held, held_sse) of the last call -- the tiles that differed within the tolerance and the sum of their squared
+        differences; held_sse / (3 * width * height) is the composite's mean squared error against the caller's frame"""
+        n, sse = C.c_int(0), C.c_uint64(0)
+        _check(self.L.mpc_delta_held(self.h, C.byref(n), C.byref(sse)))
+        return n.value, sse.value
+
+    def frame(self):
+        """mpc_delta_frame: the composite the session keeps (HxWx3 uint8): what its last container encodes"""
+        out = np.zeros((self.height, self.width, 3), np.uint8)
+        _check(self.L.mpc_delta_frame(self.h, out.ctypes.data, 0))
+        return out
+
+    def frame_device(self):
+        """mpc_delta_frame_device: the composite's address in device memory (int), height rows of 3 * width bytes, valid until the next
+        call"""
+        p = C.c_void_p()
+        _check(self.L.mpc_delta_frame_device(self.h, C.byref(p)))
+        return p.value
 
     def sent(self):
         """mpc_delta_sent: the depth the receiver holds of each tile after the last budget call (uint8 per tile)"""
@@ -2207,6 +2276,12 @@ class CompressionContext:
         """mpc_tile_diff_device: the 8 x 8 tiles of the frame at d_rgb (row_stride bytes between rows, 0 = 3 * width) that differ from the
         tight copy at d_kept -> d_list (int32 per tile, ascending) and d_count (int32); d_kept becomes the new pixels.  Asynchronous."""
         _check(self.L.mpc_tile_diff_device(self.h, d_kept, d_rgb, int(width), int(height), int(row_stride), d_list, d_count, stream or None))
+
+    def tile_diff_tolerance_device(self, d_kept, d_rgb, width, height, row_stride, tolerance, d_list, d_count, d_sse=0, stream=0):
+        """mpc_tile_diff_tolerance_device: tile_diff_device with a tolerance -- d_list / d_count the tiles whose summed squared byte
+        difference exceeds it; d_kept becomes the new pixels in those tiles only; d_sse (0 = none): uint32 per tile.  Asynchronous."""
+        _check(self.L.mpc_tile_diff_tolerance_device(self.h, d_kept, d_rgb, int(width), int(height), int(row_stride), int(tolerance), d_list,
+                                                     d_count, d_sse or None, stream or None))
 
     def pack_tiles_device(self, d_rgb, width, height, row_stride, d_list, n, rows, d_packed, packed_stride=0, stream=0):
         """mpc_pack_tiles_device: the n listed tiles of the frame as the packed frame delta_pack_geometry(n, rows) describes, black

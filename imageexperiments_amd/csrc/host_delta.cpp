@@ -22,6 +22,30 @@ long long changed_tiles(const uint8_t* prev, size_t prev_stride, const uint8_t* 
     return n;
 }
 
+long long changed_tiles_tolerance(const uint8_t* prev, size_t prev_stride, const uint8_t* cur, size_t cur_stride, int width, int height, int block,
+                                  uint32_t tolerance, int32_t* tiles, uint32_t* sse) {
+    const int tiles_x = (width + block - 1) / block, tiles_y = (height + block - 1) / block;
+    long long n = 0;
+    for (int tx = 0; tx < tiles_x; ++tx)
+        for (int ty = 0; ty < tiles_y; ++ty) {
+            const int x0 = tx * block, x1 = x0 + block < width ? x0 + block : width;
+            const int y0 = ty * block, y1 = y0 + block < height ? y0 + block : height;
+            uint32_t sum = 0;                                       // at most 64 * 3 * 255^2
+            for (int y = y0; y < y1; ++y) {
+                const uint8_t* p = prev + static_cast<size_t>(y) * prev_stride + 3 * static_cast<size_t>(x0);
+                const uint8_t* q = cur + static_cast<size_t>(y) * cur_stride + 3 * static_cast<size_t>(x0);
+                for (int b = 0; b < 3 * (x1 - x0); ++b) {
+                    const int diff = static_cast<int>(q[b]) - static_cast<int>(p[b]);
+                    sum += static_cast<uint32_t>(diff * diff);
+                }
+            }
+            const long long t = static_cast<long long>(tx) * tiles_y + ty;
+            if (sse) sse[t] = sum;
+            if (sum > tolerance) tiles[n++] = static_cast<int32_t>(t);
+        }
+    return n;
+}
+
 PackGeometry pack_geometry(long long n, int max_rows) {
     PackGeometry g{0, 0, 0, 0};
     if (n < 1) return g;

@@ -11,6 +11,8 @@
 // The diff is the hot one and purely bandwidth-bound: it reads both frames once.  A tile's pixel row is 24 bytes = three 8-byte chunks;
 // a thread owns one chunk column of a strip of 64 horizontally adjacent tiles over the tile's 8 pixel rows, so a wave reads 512
 // contiguous bytes of a pixel row per load, 8 independent loads per frame in flight, and a chunk is written back only where it differs.
+// With a change tolerance ("Encoder: a change tolerance") mp_tile_diff_tol_kernel takes its place: the same strip, a
+// tile's summed squared difference against the tolerance, and the kept copy written in changed tiles only.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -75,6 +77,102 @@ __global__ __launch_bounds__(kDiffThreads) void mp_tile_diff_kernel(uint8_t* __r
     __syncthreads();
     if (threadIdx.x < kDiffTiles && tx0 + (int)threadIdx.x < tiles_x)
         flags[(long long)(tx0 + (int)threadIdx.x) * tiles_y + ty] = (uint8_t)changed[threadIdx.x];
+}
+
+// The diff with a tolerance (host_delta.h: changed_tiles_tolerance): the same strip, the same threads, the same 16 loads in flight,
+// but a tile's verdict needs the whole tile, so nothing is written before it.  A thread sums the squared byte differences of its 8 x 8
+// bytes -- per 32-bit word sum a^2 + sum b^2 - 2 sum ab, three v_dot4_u32_u8, at most 2 * 64 * 255^2 in the first accumulator -- and
+// leaves the sum in LDS; a tile's three threads lie side by side but a tile can straddle two waves (64 is no multiple of 3), so they
+// meet there and not in a cross-lane add.  Behind the barrier every thread adds its tile's three sums itself: one barrier, no atomic,
+// no zeroing pass.  Only a changed tile's chunk columns are written, whole; a held or equal tile's kept pixels stay as they are.
+// sse: NULL or one value per tile.  totals: NULL or {held tiles, the sum of their sse}, zeroed by the launch; a strip's 64 tiles are
+// wave 0's lanes, which adds them up and sends one pair of atomics a workgroup that holds any.
+__device__ inline void sq_diff_word(unsigned a, unsigned b, unsigned& squares, unsigned& cross)
+{
+    squares = __builtin_amdgcn_udot4(a, a, squares, false);
+    squares = __builtin_amdgcn_udot4(b, b, squares, false);
+    cross = __builtin_amdgcn_udot4(a, b, cross, false);
+}
+
+template <bool kWords>
+__global__ __launch_bounds__(kDiffThreads) void mp_tile_diff_tol_kernel(uint8_t* __restrict__ kept, const uint8_t* __restrict__ rgb, int width,
+                                                                        int height, long long row_stride, int tiles_x, int tiles_y, int strips,
+                                                                        unsigned tolerance, uint8_t* __restrict__ flags,
+                                                                        uint32_t* __restrict__ sse, unsigned long long* __restrict__ totals)
+{
+    __shared__ unsigned part[kDiffThreads];
+    const int ty = blockIdx.x / strips, tx0 = (blockIdx.x - ty * strips) * kDiffTiles;
+    const long long row_bytes = 3LL * width;
+    const long long b0 = 24LL * tx0 + 8LL * threadIdx.x;             // the chunk's first byte in its pixel row
+    const int y0 = ty * 8, rows = height - y0 < 8 ? height - y0 : 8;
+    const bool inside = b0 < row_bytes;
+    const int nb = !inside ? 0 : row_bytes - b0 < 8 ? (int)(row_bytes - b0) : 8;
+    uint2 fresh[8];
+    unsigned sum = 0u;
+    if (inside) {
+        if (kWords) {
+            uint2 old[8];
+#pragma unroll
+            for (int r = 0; r < 8; ++r) {
+                fresh[r] = old[r] = make_uint2(0u, 0u);
+                if (r < rows) {
+                    fresh[r] = *reinterpret_cast<const uint2*>(rgb + (long long)(y0 + r) * row_stride + b0);
+                    old[r] = *reinterpret_cast<const uint2*>(kept + (long long)(y0 + r) * row_bytes + b0);
+                }
+            }
+            unsigned squares = 0u, cross = 0u;
+#pragma unroll
+            for (int r = 0; r < 8; ++r) {
+                sq_diff_word(fresh[r].x, old[r].x, squares, cross);
+                sq_diff_word(fresh[r].y, old[r].y, squares, cross);
+            }
+            sum = squares - 2u * cross;
+        } else {
+            for (int r = 0; r < rows; ++r) {
+                const uint8_t* p = rgb + (long long)(y0 + r) * row_stride + b0;
+                const uint8_t* q = kept + (long long)(y0 + r) * row_bytes + b0;
+                for (int j = 0; j < nb; ++j) {
+                    const int diff = (int)p[j] - (int)q[j];
+                    sum += (unsigned)(diff * diff);
+                }
+            }
+        }
+    }
+    part[threadIdx.x] = sum;
+    __syncthreads();
+    const int mine = 3 * (int)(threadIdx.x / 3);
+    if (inside && part[mine] + part[mine + 1] + part[mine + 2] > tolerance) {
+        if (kWords) {
+#pragma unroll
+            for (int r = 0; r < 8; ++r)
+                if (r < rows) *reinterpret_cast<uint2*>(kept + (long long)(y0 + r) * row_bytes + b0) = fresh[r];
+        } else {
+            for (int r = 0; r < rows; ++r) {
+                const uint8_t* p = rgb + (long long)(y0 + r) * row_stride + b0;
+                uint8_t* q = kept + (long long)(y0 + r) * row_bytes + b0;
+                for (int j = 0; j < nb; ++j) q[j] = p[j];
+            }
+        }
+    }
+    if (threadIdx.x < kDiffTiles) {                                  // wave 0, a lane per tile of the strip
+        const unsigned tile_sse = part[3 * threadIdx.x] + part[3 * threadIdx.x + 1] + part[3 * threadIdx.x + 2];
+        if (tx0 + (int)threadIdx.x < tiles_x) {
+            const long long t = (long long)(tx0 + (int)threadIdx.x) * tiles_y + ty;
+            flags[t] = tile_sse > tolerance ? 1 : 0;
+            if (sse) sse[t] = tile_sse;
+        }
+        if (totals) {                                                // a tile behind tiles_x has no bytes: its sum is 0
+            const bool held = tile_sse != 0u && tile_sse <= tolerance;
+            const unsigned long long who = __ballot(held);
+            unsigned held_sse = held ? tile_sse : 0u;                // 64 tiles: below 2^30
+#pragma unroll
+            for (int d = 32; d > 0; d >>= 1) held_sse += __shfl_xor(held_sse, d);
+            if (threadIdx.x == 0 && who) {
+                atomicAdd(&totals[0], (unsigned long long)__popcll(who));
+                atomicAdd(&totals[1], (unsigned long long)held_sse);
+            }
+        }
+    }
 }
 
 // flags -> per block of 1024 tiles the number set, at block_live[3 * block]: column 0 of a StreamArgs table with K = 1, which
@@ -227,6 +325,30 @@ int launch_tile_diff(uint8_t* kept, const uint8_t* rgb, int width, int height, s
     else
         hipLaunchKernelGGL(mp_tile_diff_kernel<false>, grid, dim3(kDiffThreads), 0, s, kept, rgb, width, height, (long long)row_stride, (int)tiles_x,
                            (int)tiles_y, (int)strips, flags);
+    return launch_tile_flags_list(flags, tiles, block_live, list, count, s);
+}
+
+int launch_tile_diff_tolerance(uint8_t* kept, const uint8_t* rgb, int width, int height, size_t row_stride, uint32_t tolerance, int32_t* list,
+                               int32_t* count, uint32_t* sse, unsigned long long* totals, void* scratch, void* stream_)
+{
+    hipStream_t s = static_cast<hipStream_t>(stream_);
+    if (!kept || !rgb || !list || !count || !scratch || width < 1 || height < 1 || row_stride < 3 * (size_t)width) return (int)hipErrorInvalidValue;
+    const long long tiles_x = ((long long)width + 7) / 8, tiles_y = ((long long)height + 7) / 8, tiles = tiles_x * tiles_y;
+    const long long strips = (tiles_x + kDiffTiles - 1) / kDiffTiles;
+    if (tiles >= (1LL << 31) || strips * tiles_y >= (1LL << 31)) return (int)hipErrorInvalidValue;
+    uint8_t* flags = static_cast<uint8_t*>(scratch);
+    unsigned* block_live = tile_diff_block_live(scratch, tiles);
+    const size_t row_bytes = 3 * (size_t)width;
+    const bool words = ((reinterpret_cast<uintptr_t>(kept) | reinterpret_cast<uintptr_t>(rgb) | row_stride | row_bytes) & 7) == 0;
+    const dim3 grid((unsigned)(strips * tiles_y));
+    if (totals)
+        if (const hipError_t e = hipMemsetAsync(totals, 0, 2 * sizeof(unsigned long long), s); e != hipSuccess) return (int)e;
+    if (words)
+        hipLaunchKernelGGL(mp_tile_diff_tol_kernel<true>, grid, dim3(kDiffThreads), 0, s, kept, rgb, width, height, (long long)row_stride,
+                           (int)tiles_x, (int)tiles_y, (int)strips, tolerance, flags, sse, totals);
+    else
+        hipLaunchKernelGGL(mp_tile_diff_tol_kernel<false>, grid, dim3(kDiffThreads), 0, s, kept, rgb, width, height, (long long)row_stride,
+                           (int)tiles_x, (int)tiles_y, (int)strips, tolerance, flags, sse, totals);
     return launch_tile_flags_list(flags, tiles, block_live, list, count, s);
 }
 

@@ -323,6 +323,11 @@ size_t tile_diff_scratch_bytes(long long tiles);
 // bytes of `rgb` are read.  8-byte fetches when both bases, row_stride and 3 * width are multiples of 8, else byte by byte.
 int launch_tile_diff(uint8_t* kept, const uint8_t* rgb, int width, int height, size_t row_stride, int32_t* list, int32_t* count, void* scratch,
                      void* stream);
+// The same with a tolerance (host_delta.h: changed_tiles_tolerance): list = the tiles whose summed squared byte difference exceeds
+// `tolerance`, and kept = the new pixels in those tiles only, its old ones in every other.  sse: NULL or [tiles], every tile's sum.
+// totals: NULL or [2], zeroed on the stream first: the held tiles (0 < sum <= tolerance) and the sum of their sums.  Same scratch
+int launch_tile_diff_tolerance(uint8_t* kept, const uint8_t* rgb, int width, int height, size_t row_stride, uint32_t tolerance, int32_t* list,
+                               int32_t* count, uint32_t* sse, unsigned long long* totals, void* scratch, void* stream);
 // The listed tiles of the frame as a packed frame of rows x cols whole tiles (host_delta.h: pack_geometry), listed tile j at
 // (j / rows, j % rows); pixels outside the image, padding tiles and list entries outside [0, tiles) are black.  packed: 8-byte
 // aligned, packed_stride a multiple of 8 and >= 24 * cols; bytes of a row behind 24 * cols are not written

@@ -39,6 +39,12 @@ struct mpc_delta {
     // mpc_delta_set_emphasis: the map budget calls weigh the tiles with; it says nothing about the receiver, so it outlives a failed call
     GrowBuffer emphasis{GrowBuffer::kDevice};   // [tiles]
     bool has_emphasis = false;
+    // mpc_delta_set_tolerance: 0 = any differing byte is a change (mp_tile_diff_kernel), else mp_tile_diff_tol_kernel and the kept copy
+    // is the composite.  Like the emphasis map it is the caller's wish, not the receiver's state, and outlives a failed call
+    uint32_t tolerance = 0;
+    GrowBuffer held_totals{GrowBuffer::kDevice};// [2] of a tolerant diff: held tiles, the sum of their sse; reserved by the first one
+    long long held = 0;                         // the last successful call's
+    uint64_t held_sse = 0;
     ~mpc_delta() {
         if (stream) {
             (void)hipStreamSynchronize(stream);
@@ -56,6 +62,8 @@ struct DeltaCall {                              // what the stages of one call h
     const uint8_t* frame = nullptr;             // the frame on the device and its stride
     size_t stride = 0;
     long long n = 0;                            // tiles listed
+    long long held = 0;                         // a tolerant diff's held tiles and the sum of their sse
+    uint64_t held_sse = 0;
     mpc::PackGeometry g{0, 0, 0, 0};            // through_pack && n > 0: the packed frame's geometry, its records in d->pack
     uint16_t* d_packed_counts = nullptr;
     mpc_basis_choice* d_packed_choices = nullptr;
@@ -64,7 +72,8 @@ struct DeltaCall {                              // what the stages of one call h
 mpc_status delta_no_device();
 // 1. the frame on the device
 mpc_status delta_frame(mpc_delta* d, const uint8_t* rgb, size_t row_stride, hipStream_t s, DeltaCall& call);
-// 2., 3. the changed tiles: all of them for a key frame, else the diff's list; either way the kept copy becomes this frame
+// 2., 3. the changed tiles: all of them for a key frame, else the diff's list; the kept copy becomes this frame -- with a tolerance the
+// composite: this frame in the listed tiles, what it was in every other
 mpc_status delta_list(mpc_delta* d, hipStream_t s, DeltaCall& call);
 // 4. - 6. pursue: a key frame straight into the record store, else the packed frame of the listed tiles and its records scattered
 mpc_status delta_pursue(mpc_delta* d, hipStream_t s, DeltaCall& call);
@@ -96,6 +105,8 @@ mpc_status delta_call(mpc_delta* d, const uint8_t* rgb, size_t row_stride, const
             d->changed_all = false;
             d->changed.clear();
             d->info = mpc_delta_info{};
+            d->held = 0;
+            d->held_sse = 0;
         }
     } session{d};
     HIP_TRY(hipSetDevice(c->device));
@@ -122,6 +133,8 @@ mpc_status delta_call(mpc_delta* d, const uint8_t* rgb, size_t row_stride, const
     d->quant.assign(table, table + 3 * static_cast<size_t>(K));
     d->changed_all = call.key;
     d->info = mpc_delta_info{static_cast<int>(d->tiles), static_cast<int>(call.n), call.key ? 1 : 0};
+    d->held = call.held;
+    d->held_sse = call.held_sse;
     ++d->calls;
     *info = d->info;
     session.keep = true;

@@ -62,6 +62,43 @@ mpc_status mpc_tile_diff_device(mpc_context* c, uint8_t* d_kept, const uint8_t* 
     });
 }
 
+mpc_status mpc_changed_tiles_tolerance(const uint8_t* prev, size_t prev_stride, const uint8_t* cur, size_t cur_stride, int width, int height,
+                                       int block_size, uint32_t tolerance, int32_t* tiles, int* n, uint32_t* sse) {
+    return guarded([&]() -> mpc_status {
+        if (!prev || !cur || !tiles || !n) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (width < 1 || height < 1 || block_size < 1 || block_size > 8) return fail(MPC_ERR_ARGUMENT, "bad geometry");
+        const size_t row = 3 * static_cast<size_t>(width);
+        if ((prev_stride != 0 && prev_stride < row) || (cur_stride != 0 && cur_stride < row))
+            return fail(MPC_ERR_ARGUMENT, "a row stride below %zu for %d pixels", row, width);
+        const long long all = ((static_cast<long long>(width) + block_size - 1) / block_size) * ((static_cast<long long>(height) + block_size - 1) / block_size);
+        if (all >= (1LL << 31)) return fail(MPC_ERR_ARGUMENT, "bad geometry");
+        *n = static_cast<int>(mpc::changed_tiles_tolerance(prev, prev_stride ? prev_stride : row, cur, cur_stride ? cur_stride : row, width, height,
+                                                           block_size, tolerance, tiles, sse));
+        return MPC_OK;
+    });
+}
+
+mpc_status mpc_tile_diff_tolerance_device(mpc_context* c, uint8_t* d_kept, const uint8_t* d_rgb, int width, int height, size_t row_stride,
+                                          uint32_t tolerance, int32_t* d_list, int32_t* d_count, uint32_t* d_sse, void* stream) {
+    return guarded([&]() -> mpc_status {
+        if (!c || !d_kept || !d_rgb || !d_list || !d_count) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (c->device < 0) return delta_no_device();
+        if (width < 1 || height < 1) return fail(MPC_ERR_ARGUMENT, "bad geometry");
+        const size_t row = 3 * static_cast<size_t>(width), stride = row_stride ? row_stride : row;
+        if (stride < row) return fail(MPC_ERR_ARGUMENT, "row_stride %zu for %d pixels", row_stride, width);
+        const long long tiles = ((static_cast<long long>(width) + 7) / 8) * ((static_cast<long long>(height) + 7) / 8);
+        if (tiles >= (1LL << 31)) return fail(MPC_ERR_ARGUMENT, "bad geometry");
+        std::lock_guard<std::recursive_mutex> one_host_call(c->host_calls);
+        HIP_TRY(hipSetDevice(c->device));
+        if (const mpc_status cs = refuse_capture(stream); cs != MPC_OK) return cs;
+        if (const mpc_status gs = c->delta_scratch.reserve(mpc::tile_diff_scratch_bytes(tiles), "diff scratch"); gs != MPC_OK) return gs;
+        const int err = mpc::launch_tile_diff_tolerance(d_kept, d_rgb, width, height, stride, tolerance, d_list, d_count, d_sse, nullptr,
+                                                        c->delta_scratch.data(), stream);
+        if (err != 0) return launch_failed(err);
+        return MPC_OK;
+    });
+}
+
 mpc_status mpc_pack_tiles_device(mpc_context* c, const uint8_t* d_rgb, int width, int height, size_t row_stride, const int32_t* d_list, int n,
                                  int rows, uint8_t* d_packed, size_t packed_stride, void* stream) {
     return guarded([&]() -> mpc_status {
@@ -171,6 +208,47 @@ mpc_status mpc_delta_changed(const mpc_delta* d, int32_t* tiles, int capacity, i
     return MPC_OK;
 }
 
+mpc_status mpc_delta_set_tolerance(mpc_delta* d, uint32_t tolerance) {
+    return guarded([&]() -> mpc_status {
+        if (!d) return fail(MPC_ERR_ARGUMENT, "null argument");
+        std::lock_guard<std::recursive_mutex> one_host_call(d->ctx->host_calls);
+        d->tolerance = tolerance;                                   // read by the next call's diff; the kept copy and the sent map stay true
+        return MPC_OK;
+    });
+}
+
+uint32_t mpc_delta_tolerance(const mpc_delta* d) { return d ? d->tolerance : 0u; }
+
+mpc_status mpc_delta_held(const mpc_delta* d, int* held, uint64_t* held_sse) {
+    if (!d || !held || !held_sse) return fail(MPC_ERR_ARGUMENT, "null argument");
+    *held = static_cast<int>(d->held);
+    *held_sse = d->held_sse;
+    return MPC_OK;
+}
+
+mpc_status mpc_delta_frame_device(mpc_delta* d, uint8_t** d_rgb) {
+    if (!d || !d_rgb) return fail(MPC_ERR_ARGUMENT, "null argument");
+    *d_rgb = nullptr;
+    if (!d->valid) return fail(MPC_ERR_ARGUMENT, "the session has no frame: no call yet, or the last one failed");
+    *d_rgb = d->d_kept;
+    return MPC_OK;
+}
+
+mpc_status mpc_delta_frame(mpc_delta* d, uint8_t* rgb, size_t row_stride) {
+    return guarded([&]() -> mpc_status {
+        if (!d || !rgb) return fail(MPC_ERR_ARGUMENT, "null argument");
+        const size_t row = 3 * static_cast<size_t>(d->width);
+        if (row_stride != 0 && row_stride < row) return fail(MPC_ERR_ARGUMENT, "row_stride %zu for %d pixels", row_stride, d->width);
+        if (!d->valid) return fail(MPC_ERR_ARGUMENT, "the session has no frame: no call yet, or the last one failed");
+        std::lock_guard<std::recursive_mutex> one_host_call(d->ctx->host_calls);
+        HIP_TRY(hipSetDevice(d->ctx->device));
+        // the session's calls are synchronous: nothing on its stream writes the kept copy
+        HIP_TRY(hipMemcpy2DAsync(rgb, row_stride ? row_stride : row, d->d_kept, row, row, static_cast<size_t>(d->height), hipMemcpyDeviceToHost, d->stream));
+        HIP_TRY(hipStreamSynchronize(d->stream));
+        return MPC_OK;
+    });
+}
+
 mpc_status mpc_delta_set_emphasis(mpc_delta* d, const uint8_t* emphasis, int tiles) {
     return guarded([&]() -> mpc_status {
         if (!d) return fail(MPC_ERR_ARGUMENT, "null argument");
@@ -212,7 +290,8 @@ mpc_status delta_frame(mpc_delta* d, const uint8_t* rgb, size_t row_stride, hipS
     return MPC_OK;
 }
 
-// 2., 3. the changed tiles: all of them for a key frame, else the diff's list; either way the kept copy becomes this frame
+// 2., 3. the changed tiles: all of them for a key frame, else the diff's list; the kept copy becomes this frame -- with a tolerance the
+// composite: this frame in the listed tiles, what it was in every other
 mpc_status delta_list(mpc_delta* d, hipStream_t s, DeltaCall& call) {
     const size_t row = 3 * static_cast<size_t>(d->width);
     call.n = d->tiles;
@@ -228,12 +307,26 @@ mpc_status delta_list(mpc_delta* d, hipStream_t s, DeltaCall& call) {
         }
         return MPC_OK;
     }
-    if (const int e = mpc::launch_tile_diff(d->d_kept, call.frame, d->width, d->height, call.stride, d->d_list, d->d_count, d->d_scratch, s); e != 0)
-        return launch_failed(e);
+    unsigned long long held[2] = {0, 0};
+    if (d->tolerance == 0) {
+        if (const int e = mpc::launch_tile_diff(d->d_kept, call.frame, d->width, d->height, call.stride, d->d_list, d->d_count, d->d_scratch, s); e != 0)
+            return launch_failed(e);
+    } else {
+        if (const mpc_status gs = d->held_totals.reserve(sizeof(held), "held totals"); gs != MPC_OK) return gs;
+        unsigned long long* d_held = reinterpret_cast<unsigned long long*>(d->held_totals.data());
+        if (const int e = mpc::launch_tile_diff_tolerance(d->d_kept, call.frame, d->width, d->height, call.stride, d->tolerance, d->d_list, d->d_count,
+                                                          nullptr, d_held, d->d_scratch, s);
+            e != 0)
+            return launch_failed(e);
+        HIP_TRY(hipMemcpyAsync(held, d_held, sizeof(held), hipMemcpyDeviceToHost, s));
+    }
     int32_t count = -1;
     HIP_TRY(hipMemcpyAsync(&count, d->d_count, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (count < 0 || count > d->tiles) return fail(MPC_ERR_HIP, "the diff counted %d of %lld tiles", count, d->tiles);
+    if (held[0] > static_cast<unsigned long long>(d->tiles - count)) return fail(MPC_ERR_HIP, "the diff held %llu of %lld tiles", held[0], d->tiles - count);
+    call.held = static_cast<long long>(held[0]);
+    call.held_sse = held[1];
     call.n = count;
     d->changed.resize(static_cast<size_t>(call.n));
     if (call.n > 0) {

@@ -935,6 +935,49 @@ mpc_status mpc_delta_encode(mpc_delta* d, const uint8_t* rgb, size_t row_stride,
                             uint8_t** bytes, size_t* nbytes, uint8_t** index, size_t* index_bytes, mpc_delta_info* info);
 mpc_status mpc_delta_changed(const mpc_delta* d, int32_t* tiles, int capacity, int* n);   /* the last call's list */
 
+/* ---- delta with a change tolerance ("Encoder: a change tolerance") ----
+ * A camera, a dithered render or a lossy hop changes a few low bits in every tile of every frame; with a tolerance the caller says that
+ * differences this small are not a change.  THE DEFINITION, host, exact, integer: sse(t) = the sum of (cur - kept)^2 over the three
+ * bytes of every pixel of tile t that lies inside the image (mpc_changed_tiles's tiles, order and reads; at most 64 * 3 * 255^2 =
+ * 12 484 800, exact in 32 bits in any order).  Tile t is CHANGED iff sse(t) > tolerance and HELD iff 0 < sse(t) <= tolerance.  After
+ * the diff the kept copy holds cur's pixels in every changed tile and its old pixels, whole, in every other.  So a session keeps the
+ * COMPOSITE C_n: C_n = frame n for a key frame; else, tile by tile, frame n where the tile is changed and C_(n-1) where it is not.  A
+ * held tile is compared with the pixels last SENT, not with the previous frame: a slow drift adds up until it crosses the tolerance
+ * and is sent then, and at every call every tile of C_n is within `tolerance` of frame n's.  tolerance 0 is the rule above exactly
+ * (sse > 0: some byte differs); 12 484 800 or more holds everything but key frames, which is allowed.
+ *
+ * mpc_changed_tiles_tolerance: mpc_changed_tiles's arguments, rules and refusals, plus the tolerance and sse: NULL or one value per
+ * tile, every tile's.  prev is not written: the composite is cur in the listed tiles, prev elsewhere.
+ * mpc_tile_diff_tolerance_device: mpc_tile_diff_device's layout rules, refusals, scratch and stream contract (asynchronous on `stream`,
+ * nothing on the null stream), with d_kept brought up to the composite; d_sse: NULL or tiles values in device memory.
+ *
+ * THE SESSION.  mpc_delta_set_tolerance: session state, 0 at first, read by the next call; it makes no key frame and leaves the sent
+ * map valid.  MPC_ERR_ARGUMENT for a null session.  mpc_delta_tolerance reads it back (0 for a null session).  At tolerance 0 a call
+ * enqueues exactly what it did before there was a tolerance.  Key-frame rules are unchanged and a key frame copies the frame whole.
+ * THE CONTRACTS, restated with the composite:
+ *   mpc_delta_encode                  every container is byte for byte mpc_encode_image_device of C_n, its index that container's
+ *   mpc_delta_encode_patch[_indexed]  a receiver that applied every patch holds, after call n, the decode of C_n's container
+ *   mpc_delta_encode_patch_budget     the invariant of "rate" with "the current frame's full records" read as C_n's; the tiles that
+ *                                     must be sent are the tolerant diff's list
+ *   mpc_delta_changed                 the tolerant list
+ * The emphasis map does not scale the tolerance.
+ * mpc_delta_held: the last successful call's held tiles and the sum of their sse; both 0 for a key frame and at tolerance 0.
+ * held_sse / (3 * width * height) is the mean squared error of C_n against frame n: its PSNR without a decode.
+ * mpc_delta_frame_device: C_n, the session's own buffer, height rows of 3 * width bytes, valid until the next call;
+ * mpc_delta_frame: its copy to the host (row_stride 0 = 3 * width).  Both: MPC_ERR_ARGUMENT for a null pointer, a row_stride below
+ * 3 * width, or a session without a frame (no successful call yet, or the last one failed behind its checks).
+ * A refused encode call leaves the tolerance, the composite and the held totals as they were. */
+mpc_status mpc_changed_tiles_tolerance(const uint8_t* prev, size_t prev_stride, const uint8_t* cur, size_t cur_stride, int width, int height,
+                                       int block_size, uint32_t tolerance, int32_t* tiles, int* n, uint32_t* sse /* NULL or [tiles] */);
+mpc_status mpc_tile_diff_tolerance_device(mpc_context* ctx, uint8_t* d_kept, const uint8_t* d_rgb, int width, int height, size_t row_stride,
+                                          uint32_t tolerance, int32_t* d_list, int32_t* d_count, uint32_t* d_sse /* NULL or [tiles] */,
+                                          void* stream);
+mpc_status mpc_delta_set_tolerance(mpc_delta* d, uint32_t tolerance);
+uint32_t   mpc_delta_tolerance(const mpc_delta* d);
+mpc_status mpc_delta_held(const mpc_delta* d, int* held, uint64_t* held_sse);
+mpc_status mpc_delta_frame(mpc_delta* d, uint8_t* rgb, size_t row_stride);
+mpc_status mpc_delta_frame_device(mpc_delta* d, uint8_t** d_rgb);
+
 /* ---- patch: send only the changed tiles, apply them on the device ("Delta stream") ----
  * The packed frame of a delta call's listed tiles is an ordinary frame, so its container is an ordinary container.  A PATCH is the
  * ascending tile list plus that container: what a receiver that holds the previous frame needs, at a few per cent of the bytes.
