@@ -1328,6 +1328,14 @@ def _emphasis(emphasis, tiles):
     return emphasis
 
 
+def _hwc_u8(rgb):
+    """a host frame of the whole-frame cut encodes -> (the pixels as a contiguous uint8 [H, W, 3] array, W, H)"""
+    rgb = np.ascontiguousarray(rgb, np.uint8)
+    if rgb.ndim != 3 or rgb.shape[2] != 3:
+        raise ValueError("pixels: an HxWx3 uint8 array")
+    return rgb, rgb.shape[1], rgb.shape[0]
+
+
 def budget_allocate_emphasis(profile, counts, emphasis, weights, j):
     """mpc_budget_allocate_emphasis: budget_allocate with J = P * e[t] * 4096 + L[j] * R: emphasis uint8 [T] (16 = neutral, 0 used as 1,
     above 64 as 64) or None = neutral -> (depth, cut counts, totals); totals[0] is the unweighted squared error"""
@@ -2097,27 +2105,37 @@ class CompressionContext:
         if check:
             _check(self.L.mpc_crop_records_check(self.h, stream or None))
 
-    def _encode_budget(self, fn, frame, width, height, budget, quant, index_interval, emphasis=()):
+    def _encode_cut(self, fn, info, result, frame, width, height, target, quant, index_interval, emphasis=()):
+        """The call behind the budget and the quality encodes, their _device and their _emphasis forms: fn takes the frame, the map
+        where `emphasis` holds one, the geometry, quant and the target (a budget in bytes, a squared error); info: the struct it fills;
+        -> result(container, index, depth, info)"""
         qp = None
         if quant is not None:
             quant = np.ascontiguousarray(quant, np.float64).reshape(3, self.K)
             qp = quant.ctypes.data_as(_dp)
         tiles = -(-int(width) // 8) * -(-int(height) // 8)
         depth = np.zeros(max(tiles, 1), np.uint8)
-        out, n, index, nindex, info = _u8p(), C.c_size_t(0), _u8p(), C.c_size_t(0), MpcBudgetInfo()
-        _check(fn(self.h, frame, *emphasis, int(width), int(height), qp, int(budget), -1 if index_interval is None else int(index_interval),
+        out, n, index, nindex, info = _u8p(), C.c_size_t(0), _u8p(), C.c_size_t(0), info()
+        _check(fn(self.h, frame, *emphasis, int(width), int(height), qp, int(target), -1 if index_interval is None else int(index_interval),
                   C.byref(out), C.byref(n), C.byref(index), C.byref(nindex), depth.ctypes.data_as(_u8p), C.byref(info)))
         blob = _take_bytes(self.L, out, n)
-        return BudgetResult(blob, None if index_interval is None else _take_bytes(self.L, index, nindex), depth[:tiles], info)
+        return result(blob, None if index_interval is None else _take_bytes(self.L, index, nindex), depth[:tiles], info)
+
+    def _encode_budget(self, fn, frame, width, height, budget, quant, index_interval, emphasis=()):
+        return self._encode_cut(fn, MpcBudgetInfo, BudgetResult, frame, width, height, budget, quant, index_interval, emphasis)
+
+    def _encode_quality(self, fn, frame, width, height, psnr, max_sse, quant, index_interval, emphasis=()):
+        if (psnr is None) == (max_sse is None):
+            raise ValueError("exactly one of psnr and max_sse")
+        if max_sse is None:
+            max_sse = sse_for_psnr(psnr, width, height)
+        return self._encode_cut(fn, MpcQualityInfo, QualityResult, frame, width, height, max_sse, quant, index_interval, emphasis)
 
     def encode_image_budget(self, rgb, budget, quant=None, index_interval=None):
         """mpc_encode_image_budget: the frame (uint8 [H, W, 3]) as a container of at most `budget` bytes, every tile cut to the depth that
         a Lagrange multiplier found by bisection assigns it -> BudgetResult.  index_interval: None = no index, else (0 = the default
         interval) container_index2(result, interval, expanded) comes with it."""
-        rgb = np.ascontiguousarray(rgb, np.uint8)
-        if rgb.ndim != 3 or rgb.shape[2] != 3:
-            raise ValueError("pixels: an HxWx3 uint8 array")
-        H, W = rgb.shape[:2]
+        rgb, W, H = _hwc_u8(rgb)
         return self._encode_budget(self.L.mpc_encode_image_budget, rgb.ctypes.data_as(C.c_void_p), W, H, budget, quant, index_interval)
 
     def encode_image_budget_device(self, d_rgb, width, height, budget, quant=None, index_interval=None):
@@ -2149,31 +2167,11 @@ class CompressionContext:
         weights = np.ascontiguousarray(weights, np.uint32).reshape(3, self.K)
         _check(self.L.mpc_budget_sweep_device(self.h, d_profile, d_counts, int(tiles), weights.ctypes.data_as(_u32p), d_totals, stream or None))
 
-    def _encode_quality(self, fn, frame, width, height, psnr, max_sse, quant, index_interval, emphasis=()):
-        if (psnr is None) == (max_sse is None):
-            raise ValueError("exactly one of psnr and max_sse")
-        if max_sse is None:
-            max_sse = sse_for_psnr(psnr, width, height)
-        qp = None
-        if quant is not None:
-            quant = np.ascontiguousarray(quant, np.float64).reshape(3, self.K)
-            qp = quant.ctypes.data_as(_dp)
-        tiles = -(-int(width) // 8) * -(-int(height) // 8)
-        depth = np.zeros(max(tiles, 1), np.uint8)
-        out, n, index, nindex, info = _u8p(), C.c_size_t(0), _u8p(), C.c_size_t(0), MpcQualityInfo()
-        _check(fn(self.h, frame, *emphasis, int(width), int(height), qp, int(max_sse), -1 if index_interval is None else int(index_interval),
-                  C.byref(out), C.byref(n), C.byref(index), C.byref(nindex), depth.ctypes.data_as(_u8p), C.byref(info)))
-        blob = _take_bytes(self.L, out, n)
-        return QualityResult(blob, None if index_interval is None else _take_bytes(self.L, index, nindex), depth[:tiles], info)
-
     def encode_image_quality(self, rgb, psnr=None, max_sse=None, quant=None, index_interval=None):
         """mpc_encode_image_quality: the frame (uint8 [H, W, 3]) as the container of the allocation at the largest multiplier whose
         squared error is at most the target -> QualityResult.  Exactly one target: psnr (dB; through sse_for_psnr) or max_sse.
         index_interval: as for encode_image_budget.  MpcError(MPC_ERR_ARGUMENT) where no cut of the frame's records is that good."""
-        rgb = np.ascontiguousarray(rgb, np.uint8)
-        if rgb.ndim != 3 or rgb.shape[2] != 3:
-            raise ValueError("pixels: an HxWx3 uint8 array")
-        H, W = rgb.shape[:2]
+        rgb, W, H = _hwc_u8(rgb)
         return self._encode_quality(self.L.mpc_encode_image_quality, rgb.ctypes.data_as(C.c_void_p), W, H, psnr, max_sse, quant, index_interval)
 
     def encode_image_quality_device(self, d_rgb, width, height, psnr=None, max_sse=None, quant=None, index_interval=None):
@@ -2186,10 +2184,7 @@ class CompressionContext:
         """mpc_encode_image_budget_emphasis: encode_image_budget with an emphasis map (uint8 per tile, t = tx * tiles_y + ty; 16 =
         neutral, 1 ... 64) that weighs every tile's squared error in the allocation; None: encode_image_budget itself.  sse stays the
         true squared error of the result."""
-        rgb = np.ascontiguousarray(rgb, np.uint8)
-        if rgb.ndim != 3 or rgb.shape[2] != 3:
-            raise ValueError("pixels: an HxWx3 uint8 array")
-        H, W = rgb.shape[:2]
+        rgb, W, H = _hwc_u8(rgb)
         emphasis = _emphasis(emphasis, -(-W // 8) * -(-H // 8))
         return self._encode_budget(self.L.mpc_encode_image_budget_emphasis, rgb.ctypes.data_as(C.c_void_p), W, H, budget, quant, index_interval,
                                    (None if emphasis is None else C.c_void_p(emphasis.ctypes.data),))
@@ -2202,10 +2197,7 @@ class CompressionContext:
     def encode_image_quality_emphasis(self, rgb, emphasis, psnr=None, max_sse=None, quant=None, index_interval=None):
         """mpc_encode_image_quality_emphasis: encode_image_quality with an emphasis map (as for encode_image_budget_emphasis).  The target
         stays a promise about the frame's true error; the map decides where the remaining error lies."""
-        rgb = np.ascontiguousarray(rgb, np.uint8)
-        if rgb.ndim != 3 or rgb.shape[2] != 3:
-            raise ValueError("pixels: an HxWx3 uint8 array")
-        H, W = rgb.shape[:2]
+        rgb, W, H = _hwc_u8(rgb)
         emphasis = _emphasis(emphasis, -(-W // 8) * -(-H // 8))
         return self._encode_quality(self.L.mpc_encode_image_quality_emphasis, rgb.ctypes.data_as(C.c_void_p), W, H, psnr, max_sse, quant,
                                     index_interval, (None if emphasis is None else C.c_void_p(emphasis.ctypes.data),))

@@ -69,7 +69,6 @@ struct DeltaCall {                              // what the stages of one call h
     mpc_basis_choice* d_packed_choices = nullptr;
 };
 
-mpc_status delta_no_device();
 // 1. the frame on the device
 mpc_status delta_frame(mpc_delta* d, const uint8_t* rgb, size_t row_stride, hipStream_t s, DeltaCall& call);
 // 2., 3. the changed tiles: all of them for a key frame, else the diff's list; the kept copy becomes this frame -- with a tolerance the
@@ -89,7 +88,7 @@ mpc_status delta_call(mpc_delta* d, const uint8_t* rgb, size_t row_stride, const
     const int K = c->K;
     const size_t row = 3 * static_cast<size_t>(d->width);
     if (row_stride != 0 && row_stride < row) return fail(MPC_ERR_ARGUMENT, "row_stride %zu for %d pixels", row_stride, d->width);
-    if (c->device < 0) return delta_no_device();
+    if (c->device < 0) return no_device();
     std::lock_guard<std::recursive_mutex> one_host_call(c->host_calls);
     for (int k = 0; k < mpc_context::kSeqSlots; ++k)
         if (c->jobs[k] && c->jobs[k]->stage != 0) return fail(MPC_ERR_ARGUMENT, "container job slot %d is busy", k);

@@ -1,6 +1,6 @@
 // mpc_internal.h -- product: what the translation units of libmpcodec.so share besides the public C ABI (include/mpcodec.h).
 //   mpcodec_context.cpp    device dictionary, context, quantiser tables, pursuit launches, tile encode, timing, tuning switches
-//   mpcodec_container.cpp  records on the device -> container (ContainerJob), the mpc_container_job_* API
+//   mpcodec_container.cpp  records on the device -> container (ContainerJob), the mpc_container_job_* API, the synchronous job (records_container)
 //   mpcodec_pipeline.cpp   the frame pipeline (mpc_encode_image(s)*): frames -> tile encode -> container jobs, in stages
 //   mpcodec_bitstream.cpp  host-only bitstream entry points
 // and, behind host_bitstream.h (they know neither HIP nor the C ABI and also build on their own):
@@ -55,6 +55,9 @@ mpc_status fail(mpc_status st, const char* fmt, ...) __attribute__((format(print
 inline mpc_status launch_failed(int err) {
     return fail(MPC_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(static_cast<hipError_t>(err)));
 }
+
+// what every entry point that needs the device answers a context made with device < 0
+inline mpc_status no_device() { return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback"); }
 
 // No exception crosses the C ABI (the reference throws heap-allocated std::range_error*; here: status codes)
 template <class F>
@@ -301,6 +304,12 @@ size_t host_route_layout(char* base, size_t n_tc, int K, HostRoute* r);
 // the `interval` and `flags` arguments of the indexed entry points (mpcodec_container.cpp)
 mpc_status index_interval_of(int interval, unsigned* out);
 mpc_status index_flags_of(unsigned flags, bool* expanded);
+// the `index_interval` argument of the entry points whose index is optional: below 0 = none (*every = 0), else as index_interval_of
+inline mpc_status optional_index_interval_of(int interval, unsigned* every) {
+    if (interval >= 0) return index_interval_of(interval, every);
+    *every = 0;
+    return MPC_OK;
+}
 
 // A slot of the mpc_container_job_* API.  Its buffers are its own: the context's entropy slots and staging belong to the frame
 // pipeline (mpc_encode_image(s)) and to mpc_code_symbol_streams_device, which may run -- and re-carve or clear their tables --
@@ -494,7 +503,7 @@ mpc_status encode_batch_device(mpc_context* c, const Tuning& t, const uint8_t* d
                                uint16_t* d_counts, mpc_basis_choice* d_choices, double* d_energy, uint32_t* d_swept, void* stream,
                                bool whole_frame_order, const mpc::FrameTable* table = nullptr);
 
-// ---- records -> container for a synchronous caller (mpcodec_delta.cpp): the delta encoder, the budget search and the rate search ----
+// ---- records -> container for a synchronous caller (mpcodec_container.cpp): the delta encoder, the cut encodes and the rate search ----
 // a container and its seek index in malloc'ed memory, released unless taken
 struct ContainerMade {
     uint8_t* bytes = nullptr;
@@ -516,9 +525,17 @@ struct ContainerMade {
 mpc_status records_container(mpc_context* c, const Tuning& tuning, hipStream_t s, const uint16_t* d_counts, const mpc_basis_choice* d_choices,
                              long long tiles, int width, int height, const double* quant, unsigned every, ContainerMade* out,
                              bool expanded = true);
+// `made` to the caller of an entry point: the container, and with `every` != 0 a malloc'ed copy of its seek index
+mpc_status deliver_container(ContainerMade& made, unsigned every, uint8_t** bytes, size_t* nbytes, uint8_t** index, size_t* index_bytes);
 
 // ---- rate control on the device (mpcodec_budget.cpp): the depth profile of records against the tight frame they came from ----
 mpc_status profile_on_device(mpc_context* c, const uint16_t* d_counts, const mpc_basis_choice* d_choices, const double* quant,
                              const uint8_t* d_rgb, int width, int height, uint32_t* d_profile, int* d_error, hipStream_t s);
+// The search over the multiplier table (host_budget.h) of the budget encode and of the delta stream's budget call: the smallest
+// multiplier whose result fits.  probe(j, &fits) makes the result at j and keeps it where it fits.  The last multiplier, the smallest
+// result there is, goes first, with `behind_first` once behind it (the error word of the kernels that ran in front of its end); then
+// the bisection between the full result, which does not fit, and that one.  *found: the multiplier, or -1 where not even the last one
+// fits, which the caller refuses in its own words
+mpc_status multiplier_search(const std::function<mpc_status(int, bool*)>& probe, const std::function<mpc_status()>& behind_first, int* found);
 
 #pragma GCC visibility pop

@@ -1,10 +1,11 @@
 // mpcodec_budget.cpp -- product: encode to a byte budget (include/mpcodec.h, "budget"; DESIGN.md 4, "Encoder: a byte budget").
 // One pursuit, the full container with its seek index, the depth profile (mp_budget.hip), then a bisection over the multiplier
-// table: every probe is the allocation kernel and one records-to-container job on the same records with the cut counts array.
-// And encode to a target quality ("quality"; DESIGN.md 4, "Encoder: a target quality"): the same start, then the sweep kernel's totals
-// at all 256 multipliers, the pick on the host, one allocation and one more container job.
+// table (multiplier_search, which the delta stream's budget call in mpcodec_rate.cpp runs too): every probe is the allocation kernel
+// and one records-to-container job on the same records with the cut counts array.
+// And encode to a target quality ("quality"; DESIGN.md 4, "Encoder: a target quality"): the same start (CutEncode, the front end of
+// both), then the sweep kernel's totals at all 256 multipliers, the pick on the host, one allocation and one more container job.
 // Both with an emphasis map ("emphasis"; DESIGN.md 4, "Encoder: emphasis"): the same bodies with a map handed to the allocation and the
-// sweep, a null map being today's call.
+// sweep, a null map being the plain call.
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -18,8 +19,6 @@ static_assert(mpc::kBudgetLambdas == MPC_BUDGET_LAMBDAS, "one size for the multi
 static_assert(mpc::kEmphasisNeutral == MPC_EMPHASIS_NEUTRAL && mpc::kEmphasisMax == MPC_EMPHASIS_MAX, "one range for the emphasis map");
 
 namespace {
-
-mpc_status no_device() { return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback"); }
 
 // mpc_rate_distortion's geometry
 mpc_status geometry(int width, int height, long long* tiles) {
@@ -49,180 +48,149 @@ mpc_status allocate_on_device(const mpc_context* c, const uint32_t* d_profile, c
     return MPC_OK;
 }
 
-// emphasis: null = every tile counts the same; else `tiles` bytes, in device memory when on_device, which only the allocation reads
-mpc_status encode_budget(mpc_context* c, const uint8_t* rgb, bool on_device, const uint8_t* emphasis, int width, int height, const double* quant,
-                         size_t budget, int index_interval, uint8_t** bytes, size_t* nbytes, uint8_t** index, size_t* index_bytes, uint8_t* depth,
-                         mpc_budget_info* info) {
-    return guarded([&]() -> mpc_status {
+// What the whole-frame cut encodes -- to a byte budget, to a target quality, each with or without an emphasis map -- start with, on
+// the stack of the call.  From open() to its end it holds the context's host_calls lock, and whatever happens it leaves nothing of the
+// call running.
+//   arguments()      the checks that need nothing but the arguments: `tiles`
+//   open()           the other refusals, the caller's outputs cleared, the staging in c->budget_dev with the frame and the map in it, one
+//                    pursuit of the whole frame with the records kept, the full frame's SSE, the full container with its seek index:
+//                    `full`, got.full_bytes, got.full_sse, got.full_records
+//   weigh()          the rate weights from the full container's index, the depth profile once
+//   cut_container()  the container of the cut counts, with the index the caller asked for
+//   deliver()        a container, its index and `got` to the caller
+// Info: mpc_budget_info or mpc_quality_info.  emphasis: null = every tile counts the same; else `tiles` bytes, in device memory when
+// on_device, which only the allocation and the sweep read
+template <class Info>
+struct CutEncode {
+    mpc_context* c;
+    const uint8_t* rgb;
+    bool on_device;
+    const uint8_t* emphasis;
+    int width, height;
+    const double* quant;
+    int index_interval;
+    uint8_t** bytes;
+    size_t* nbytes;
+    uint8_t** index;
+    size_t* index_bytes;
+    Info* info;
+
+    long long tiles = 0;
+    unsigned every = 0;                                         // the index the caller gets; the full container's is made in any case: the weights come from it
+    std::unique_lock<std::recursive_mutex> one_host_call;
+    Tuning tuning;
+    hipStream_t s = nullptr;
+    Info got{};                                                 // the caller's only on success
+    ContainerMade full;
+    const uint8_t* frame = nullptr;                             // the frame and the map on the device
+    const uint8_t* d_emphasis = nullptr;
+    uint8_t* d_frame = nullptr;                                 // a host frame's copy
+    uint16_t* d_counts = nullptr;
+    uint16_t* d_cut = nullptr;
+    mpc_basis_choice* d_choices = nullptr;
+    uint32_t* d_profile = nullptr;
+    uint8_t* d_depth = nullptr;
+    void* d_extra = nullptr;                                    // what open()'s caller asked for
+    unsigned long long* d_words = nullptr;                      // the allocation's three totals, the full frame's SSE
+    int* d_error = nullptr;
+    uint8_t* d_map = nullptr;                                   // a host emphasis map's copy
+
+    ~CutEncode() {
+        if (s) (void)hipStreamSynchronize(s);
+    }
+
+    mpc_status arguments() {
         if (!c || !rgb || !bytes || !nbytes || !info) return fail(MPC_ERR_ARGUMENT, "null argument");
         if (index_interval >= 0 && (!index || !index_bytes)) return fail(MPC_ERR_ARGUMENT, "null argument");
-        long long tiles = 0;
-        if (const mpc_status gs = geometry(width, height, &tiles); gs != MPC_OK) return gs;
-        if (budget == 0) return fail(MPC_ERR_ARGUMENT, "a budget of 0 bytes");
-        if (index_interval > 0 && (index_interval < static_cast<int>(mpc::kIndexIntervalMin) || index_interval > static_cast<int>(mpc::kIndexIntervalMax)))
-            return fail(MPC_ERR_ARGUMENT, "interval %d: 0 or %u to %u", index_interval, mpc::kIndexIntervalMin, mpc::kIndexIntervalMax);
-        // the index the caller gets; the full container's is made in any case: the weights come from it
-        const unsigned every = index_interval < 0 ? 0u : index_interval ? static_cast<unsigned>(index_interval) : mpc::kIndexIntervalDefault;
+        return geometry(width, height, &tiles);
+    }
+
+    size_t layout(char* base, size_t extra_bytes) {
+        const size_t n_tc = 3 * static_cast<size_t>(tiles), K = static_cast<size_t>(c->K);
+        Carve cv{base};
+        d_frame = cv.take<uint8_t>(on_device ? 0 : 3 * static_cast<size_t>(width) * static_cast<size_t>(height));
+        d_counts = cv.take<uint16_t>(n_tc + 2);
+        d_cut = cv.take<uint16_t>(n_tc + 2);
+        d_choices = cv.take<mpc_basis_choice>(n_tc * K);
+        d_profile = cv.take<uint32_t>(static_cast<size_t>(tiles) * (K + 1));
+        d_depth = cv.take<uint8_t>(static_cast<size_t>(tiles));
+        d_extra = cv.take<char>(extra_bytes);
+        d_words = cv.take<unsigned long long>(4);
+        d_error = cv.take<int>(1);
+        d_map = cv.take<uint8_t>(emphasis && !on_device ? static_cast<size_t>(tiles) : 0);
+        return cv.at;
+    }
+
+    // extra_bytes: device memory of the caller's own, behind the depth map (d_extra)
+    mpc_status open(size_t extra_bytes) {
+        if (const mpc_status bad = optional_index_interval_of(index_interval, &every)) return bad;
         if (c->device < 0) return no_device();
-        std::lock_guard<std::recursive_mutex> one_host_call(c->host_calls);
+        one_host_call = std::unique_lock<std::recursive_mutex>(c->host_calls);
         for (int k = 0; k < mpc_context::kSeqSlots; ++k)
             if (c->jobs[k] && c->jobs[k]->stage != 0) return fail(MPC_ERR_ARGUMENT, "container job slot %d is busy", k);
         *bytes = nullptr;
         *nbytes = 0;
         if (index) *index = nullptr;
         if (index_bytes) *index_bytes = 0;
-        *info = mpc_budget_info{};
-        mpc_budget_info got{};                                      // the caller's only on success
+        *info = Info{};
         HIP_TRY(hipSetDevice(c->device));
-        const Tuning tuning = read_tuning();
-        const int K = c->K, tiles_y = (height + 7) / 8;
-        const size_t n_tc = 3 * static_cast<size_t>(tiles), row = 3 * static_cast<size_t>(width);
+        tuning = read_tuning();
         if (!c->budget_stream) HIP_TRY(hipStreamCreateWithFlags(&c->budget_stream, hipStreamNonBlocking));
-        hipStream_t s = c->budget_stream;
-        struct Drain {                                              // whatever happens, nothing of this call is left running
-            hipStream_t s;
-            ~Drain() { (void)hipStreamSynchronize(s); }
-        } drain{s};
-        uint8_t* d_frame = nullptr;
-        uint16_t* d_counts = nullptr;
-        uint16_t* d_cut = nullptr;
-        mpc_basis_choice* d_choices = nullptr;
-        uint32_t* d_profile = nullptr;
-        uint8_t* d_depth[2] = {nullptr, nullptr};
-        unsigned long long* d_words = nullptr;                      // the allocation's three totals, the full frame's SSE
-        int* d_error = nullptr;
-        uint8_t* d_map = nullptr;                                   // a host emphasis map's copy
-        const auto layout = [&](char* base) {
-            Carve cv{base};
-            d_frame = cv.take<uint8_t>(on_device ? 0 : row * static_cast<size_t>(height));
-            d_counts = cv.take<uint16_t>(n_tc + 2);
-            d_cut = cv.take<uint16_t>(n_tc + 2);
-            d_choices = cv.take<mpc_basis_choice>(n_tc * static_cast<size_t>(K));
-            d_profile = cv.take<uint32_t>(static_cast<size_t>(tiles) * (static_cast<size_t>(K) + 1));
-            d_depth[0] = cv.take<uint8_t>(static_cast<size_t>(tiles));
-            d_depth[1] = cv.take<uint8_t>(static_cast<size_t>(tiles));
-            d_words = cv.take<unsigned long long>(4);
-            d_error = cv.take<int>(1);
-            d_map = cv.take<uint8_t>(emphasis && !on_device ? static_cast<size_t>(tiles) : 0);   // last: the layout in front is today's
-            return cv.at;
-        };
-        if (const mpc_status gs = c->budget_dev.reserve(layout(nullptr), "budget staging"); gs != MPC_OK) return gs;
-        layout(c->budget_dev.data());
-        const uint8_t* frame = rgb;
+        s = c->budget_stream;
+        if (const mpc_status gs = c->budget_dev.reserve(layout(nullptr, extra_bytes), "budget staging"); gs != MPC_OK) return gs;
+        layout(c->budget_dev.data(), extra_bytes);
+        const size_t row = 3 * static_cast<size_t>(width);
+        frame = rgb;
         if (!on_device) {
             HIP_TRY(hipMemcpyAsync(d_frame, rgb, row * static_cast<size_t>(height), hipMemcpyHostToDevice, s));
             frame = d_frame;
         }
-        const uint8_t* d_emphasis = emphasis;
+        d_emphasis = emphasis;
         if (emphasis && !on_device) {
             HIP_TRY(hipMemcpyAsync(d_map, emphasis, static_cast<size_t>(tiles), hipMemcpyHostToDevice, s));
             d_emphasis = d_map;
         }
         HIP_TRY(hipMemsetAsync(d_words, 0, 4 * sizeof(unsigned long long), s));
         HIP_TRY(hipMemsetAsync(d_error, 0, sizeof(int), s));
-        // 1. one pursuit of the whole frame, the records kept; the full frame's SSE behind it
-        if (const mpc_status es = mpc_encode_tiles_device(c, frame, width, height, row, 0, tiles_y, quant, d_counts, d_choices, nullptr, nullptr, 0, s);
+        // one pursuit of the whole frame, the records kept; the full frame's SSE behind it
+        if (const mpc_status es = mpc_encode_tiles_device(c, frame, width, height, row, 0, (height + 7) / 8, quant, d_counts, d_choices, nullptr, nullptr, 0, s);
             es != MPC_OK)
             return es;
         if (const mpc_status ds = mpc_distortion_device(c, d_counts, d_choices, quant, frame, width, height, d_words + 3, nullptr, s); ds != MPC_OK)
             return ds;
-        // 2. the full container with its seek index
-        const unsigned full_every = every ? every : mpc::kIndexIntervalDefault;
-        ContainerMade full;
-        if (const mpc_status fs = records_container(c, tuning, s, d_counts, d_choices, tiles, width, height, quant, full_every, &full); fs != MPC_OK) return fs;
-        unsigned long long full_sse = 0;
-        HIP_TRY(hipMemcpyAsync(&full_sse, d_words + 3, sizeof(full_sse), hipMemcpyDeviceToHost, s));
+        // the full container with its seek index; the job returns with `s` drained
+        if (const mpc_status fs = records_container(c, tuning, s, d_counts, d_choices, tiles, width, height, quant, every ? every : mpc::kIndexIntervalDefault, &full);
+            fs != MPC_OK)
+            return fs;
+        HIP_TRY(hipMemcpyAsync(&got.full_sse, d_words + 3, sizeof(got.full_sse), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
+        const size_t K = static_cast<size_t>(c->K);
         mpc::ContainerIndex full_index;
-        if (!mpc::read_container_index(full.index.data(), full.index.size(), full_index) || full_index.streams.size() != 1 + 6 * static_cast<size_t>(K))
+        if (!mpc::read_container_index(full.index.data(), full.index.size(), full_index) || full_index.streams.size() != 1 + 6 * K)
             return fail(MPC_ERR_HIP, "the full container's seek index does not read back");
-        unsigned long long full_records = 0;
-        for (int ch = 0; ch < 3; ++ch)
-            for (int i = 0; i < K; ++i) full_records += full_index.streams[1 + 2 * static_cast<size_t>(K) * ch + 2 * static_cast<size_t>(i)].expect;
+        for (size_t ch = 0; ch < 3; ++ch)
+            for (size_t i = 0; i < K; ++i) got.full_records += full_index.streams[1 + 2 * K * ch + 2 * i].expect;
         got.full_bytes = full.nbytes;
-        got.full_sse = full_sse;
-        got.full_records = full_records;
-        ContainerMade best;
-        int best_depth = -1;                                        // which of d_depth holds the returned container's map; -1: no cut
-        if (full.nbytes <= budget) {
-            // 3. it fits
-            best.swap(full);
-            got.lambda_index = -1;
-            got.probes = 0;
-            got.sse = full_sse;
-            got.records = full_records;
-        } else {
-            // 4. the weights from the full container's index, the profile once
-            uint32_t weights[3 * MPC_MAX_K];
-            const int verdict = mpc::budget_weights(full.index.data(), full.index.size(), weights);
-            if (verdict == 2) return fail(MPC_ERR_ARGUMENT, "the full container's seek index is serial only: no stream sizes to weigh the steps with");
-            if (verdict != 0) return fail(MPC_ERR_HIP, "the full container's seek index does not read back");
-            if (const mpc_status ps = profile_on_device(c, d_counts, d_choices, quant, frame, width, height, d_profile, d_error, s); ps != MPC_OK)
-                return ps;
-            int spare = 0;
-            unsigned long long best_totals[3] = {0, 0, 0};
-            size_t probed_bytes = 0;                                // the last probe's size
-            // 5. size(j): the container of the cut counts at j; kept when it fits
-            const auto probe = [&](int j, bool* fits) -> mpc_status {
-                if (const mpc_status as = allocate_on_device(c, d_profile, d_counts, d_emphasis, tiles, weights, j, d_depth[spare], d_cut, d_words, s); as != MPC_OK)
-                    return as;
-                ContainerMade made;
-                if (const mpc_status cs = records_container(c, tuning, s, d_cut, d_choices, tiles, width, height, quant, every, &made); cs != MPC_OK) return cs;
-                ++got.probes;
-                probed_bytes = made.nbytes;
-                *fits = made.nbytes <= budget;
-                if (*fits) {
-                    HIP_TRY(hipMemcpyAsync(best_totals, d_words, sizeof(best_totals), hipMemcpyDeviceToHost, s));
-                    HIP_TRY(hipStreamSynchronize(s));
-                    best.swap(made);
-                    best_depth = spare;
-                    spare ^= 1;
-                }
-                return MPC_OK;
-            };
-            bool fits = false;
-            if (const mpc_status ps = probe(mpc::kBudgetLambdas - 1, &fits); ps != MPC_OK) return ps;
-            int error_word = 0;                                     // the profile kernel ran in front of the first probe
-            HIP_TRY(hipMemcpyAsync(&error_word, d_error, sizeof(int), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            if (error_word) return fail(MPC_ERR_BITSTREAM, "Invalid bitstream");
-            // 6. the smallest container there is
-            if (!fits)
-                return fail(MPC_ERR_ARGUMENT, "a budget of %zu bytes: the container with every tile cut to nothing has %zu", budget, probed_bytes);
-            // 7. lo infeasible (-1: the full container), hi feasible
-            int lo = -1, hi = mpc::kBudgetLambdas - 1;
-            while (hi - lo > 1) {
-                const int mid = (lo + hi) >> 1;                     // lo + hi >= -1 + 1: the shift rounds down
-                if (const mpc_status ps = probe(mid, &fits); ps != MPC_OK) return ps;
-                if (fits) hi = mid;
-                else lo = mid;
-            }
-            got.lambda_index = hi;
-            got.sse = best_totals[0];
-            got.records = best_totals[2];
-        }
-        // 8. hi's container, kept from its probe
-        if (depth) {
-            if (best_depth < 0) std::memset(depth, K, static_cast<size_t>(tiles));
-            else {
-                HIP_TRY(hipMemcpyAsync(depth, d_depth[best_depth], static_cast<size_t>(tiles), hipMemcpyDeviceToHost, s));
-                HIP_TRY(hipStreamSynchronize(s));
-            }
-        }
-        if (every) {
-            uint8_t* copy = best.index.empty() ? nullptr : static_cast<uint8_t*>(std::malloc(best.index.size()));
-            if (!copy) return fail(MPC_ERR_ALLOC, "no seek index");
-            std::memcpy(copy, best.index.data(), best.index.size());
-            *index = copy;
-            *index_bytes = best.index.size();
-        }
-        *bytes = best.bytes;
-        *nbytes = best.nbytes;
-        best.bytes = nullptr;
+        return MPC_OK;
+    }
+
+    mpc_status weigh(uint32_t* weights) {
+        const int verdict = mpc::budget_weights(full.index.data(), full.index.size(), weights);
+        if (verdict == 2) return fail(MPC_ERR_ARGUMENT, "the full container's seek index is serial only: no stream sizes to weigh the steps with");
+        if (verdict != 0) return fail(MPC_ERR_HIP, "the full container's seek index does not read back");
+        return profile_on_device(c, d_counts, d_choices, quant, frame, width, height, d_profile, d_error, s);
+    }
+
+    mpc_status cut_container(ContainerMade* made) {
+        return records_container(c, tuning, s, d_cut, d_choices, tiles, width, height, quant, every, made);
+    }
+
+    mpc_status deliver(ContainerMade& made) {
+        if (const mpc_status ds = deliver_container(made, every, bytes, nbytes, index, index_bytes); ds != MPC_OK) return ds;
         *info = got;
         return MPC_OK;
-    });
-}
+    }
+};
 
 // d_totals[768] zeroed on `s`, then the kernel.  d_emphasis: null = the plain sweep
 mpc_status sweep_on_device(const mpc_context* c, const uint32_t* d_profile, const uint16_t* d_counts, const uint8_t* d_emphasis, long long tiles,
@@ -241,126 +209,112 @@ mpc_status sweep_on_device(const mpc_context* c, const uint32_t* d_profile, cons
     return MPC_OK;
 }
 
-// mpc_encode_image_quality.  Steps 1 to 3 are encode_budget's and are written out again here, not shared: that function's order of
-// enqueues, its early return of the full container and its staging layout stay exactly what they were
+// mpc_encode_image_budget: the full container if it fits, else the search over the multiplier table, every probe the allocation and the
+// container of its cut counts
+mpc_status encode_budget(mpc_context* c, const uint8_t* rgb, bool on_device, const uint8_t* emphasis, int width, int height, const double* quant,
+                         size_t budget, int index_interval, uint8_t** bytes, size_t* nbytes, uint8_t** index, size_t* index_bytes, uint8_t* depth,
+                         mpc_budget_info* info) {
+    return guarded([&]() -> mpc_status {
+        CutEncode<mpc_budget_info> e{c, rgb, on_device, emphasis, width, height, quant, index_interval, bytes, nbytes, index, index_bytes, info};
+        if (const mpc_status as = e.arguments(); as != MPC_OK) return as;
+        if (budget == 0) return fail(MPC_ERR_ARGUMENT, "a budget of 0 bytes");
+        if (const mpc_status os = e.open(static_cast<size_t>(e.tiles)); os != MPC_OK) return os;      // a second depth map
+        uint8_t* const d_depth[2] = {e.d_depth, static_cast<uint8_t*>(e.d_extra)};
+        mpc_budget_info& got = e.got;
+        hipStream_t s = e.s;
+        ContainerMade best;
+        int best_depth = -1;                                        // which of d_depth holds the returned container's map; -1: no cut
+        if (e.full.nbytes <= budget) {
+            best.swap(e.full);
+            got.lambda_index = -1;
+            got.probes = 0;
+            got.sse = got.full_sse;
+            got.records = got.full_records;
+        } else {
+            uint32_t weights[3 * MPC_MAX_K];
+            if (const mpc_status ws = e.weigh(weights); ws != MPC_OK) return ws;
+            int spare = 0;
+            unsigned long long best_totals[3] = {0, 0, 0};
+            size_t probed_bytes = 0;                                // the last probe's size
+            // size(j): the container of the cut counts at j; kept when it fits
+            const auto probe = [&](int j, bool* fits) -> mpc_status {
+                if (const mpc_status as = allocate_on_device(c, e.d_profile, e.d_counts, e.d_emphasis, e.tiles, weights, j, d_depth[spare], e.d_cut, e.d_words, s);
+                    as != MPC_OK)
+                    return as;
+                ContainerMade made;
+                if (const mpc_status cs = e.cut_container(&made); cs != MPC_OK) return cs;
+                ++got.probes;
+                probed_bytes = made.nbytes;
+                *fits = made.nbytes <= budget;
+                if (*fits) {
+                    HIP_TRY(hipMemcpyAsync(best_totals, e.d_words, sizeof(best_totals), hipMemcpyDeviceToHost, s));
+                    HIP_TRY(hipStreamSynchronize(s));
+                    best.swap(made);
+                    best_depth = spare;
+                    spare ^= 1;
+                }
+                return MPC_OK;
+            };
+            const auto read_error_word = [&]() -> mpc_status {      // the profile kernel ran in front of the first probe
+                int error_word = 0;
+                HIP_TRY(hipMemcpyAsync(&error_word, e.d_error, sizeof(int), hipMemcpyDeviceToHost, s));
+                HIP_TRY(hipStreamSynchronize(s));
+                return error_word ? fail(MPC_ERR_BITSTREAM, "Invalid bitstream") : MPC_OK;
+            };
+            if (const mpc_status ss = multiplier_search(probe, read_error_word, &got.lambda_index); ss != MPC_OK) return ss;
+            if (got.lambda_index < 0)                               // the smallest container there is
+                return fail(MPC_ERR_ARGUMENT, "a budget of %zu bytes: the container with every tile cut to nothing has %zu", budget, probed_bytes);
+            got.sse = best_totals[0];
+            got.records = best_totals[2];
+        }
+        // the container kept from the search's last probe that fitted, and its depth map
+        if (depth) {
+            if (best_depth < 0) std::memset(depth, c->K, static_cast<size_t>(e.tiles));
+            else {
+                HIP_TRY(hipMemcpyAsync(depth, d_depth[best_depth], static_cast<size_t>(e.tiles), hipMemcpyDeviceToHost, s));
+                HIP_TRY(hipStreamSynchronize(s));
+            }
+        }
+        return e.deliver(best);
+    });
+}
+
+// mpc_encode_image_quality: the sweep's totals at all 256 multipliers, the pick on the host, one allocation and its container
 mpc_status encode_quality(mpc_context* c, const uint8_t* rgb, bool on_device, const uint8_t* emphasis, int width, int height, const double* quant,
                           unsigned long long max_sse, int index_interval, uint8_t** bytes, size_t* nbytes, uint8_t** index, size_t* index_bytes, uint8_t* depth,
                           mpc_quality_info* info) {
     return guarded([&]() -> mpc_status {
-        if (!c || !rgb || !bytes || !nbytes || !info) return fail(MPC_ERR_ARGUMENT, "null argument");
-        if (index_interval >= 0 && (!index || !index_bytes)) return fail(MPC_ERR_ARGUMENT, "null argument");
-        long long tiles = 0;
-        if (const mpc_status gs = geometry(width, height, &tiles); gs != MPC_OK) return gs;
-        if (index_interval > 0 && (index_interval < static_cast<int>(mpc::kIndexIntervalMin) || index_interval > static_cast<int>(mpc::kIndexIntervalMax)))
-            return fail(MPC_ERR_ARGUMENT, "interval %d: 0 or %u to %u", index_interval, mpc::kIndexIntervalMin, mpc::kIndexIntervalMax);
-        const unsigned every = index_interval < 0 ? 0u : index_interval ? static_cast<unsigned>(index_interval) : mpc::kIndexIntervalDefault;
-        if (c->device < 0) return no_device();
-        std::lock_guard<std::recursive_mutex> one_host_call(c->host_calls);
-        for (int k = 0; k < mpc_context::kSeqSlots; ++k)
-            if (c->jobs[k] && c->jobs[k]->stage != 0) return fail(MPC_ERR_ARGUMENT, "container job slot %d is busy", k);
-        *bytes = nullptr;
-        *nbytes = 0;
-        if (index) *index = nullptr;
-        if (index_bytes) *index_bytes = 0;
-        *info = mpc_quality_info{};
-        mpc_quality_info got{};                                     // the caller's only on success
-        HIP_TRY(hipSetDevice(c->device));
-        const Tuning tuning = read_tuning();
-        const int K = c->K, tiles_y = (height + 7) / 8;
-        const size_t n_tc = 3 * static_cast<size_t>(tiles), row = 3 * static_cast<size_t>(width);
-        if (!c->budget_stream) HIP_TRY(hipStreamCreateWithFlags(&c->budget_stream, hipStreamNonBlocking));
-        hipStream_t s = c->budget_stream;
-        struct Drain {                                              // whatever happens, nothing of this call is left running
-            hipStream_t s;
-            ~Drain() { (void)hipStreamSynchronize(s); }
-        } drain{s};
-        uint8_t* d_frame = nullptr;
-        uint16_t* d_counts = nullptr;
-        uint16_t* d_cut = nullptr;
-        mpc_basis_choice* d_choices = nullptr;
-        uint32_t* d_profile = nullptr;
-        uint8_t* d_depth = nullptr;
-        unsigned long long* d_sweep = nullptr;                      // the sweep's 768 totals
-        unsigned long long* d_words = nullptr;                      // the allocation's three totals, the full frame's SSE
-        int* d_error = nullptr;
-        uint8_t* d_map = nullptr;                                   // a host emphasis map's copy
-        const auto layout = [&](char* base) {
-            Carve cv{base};
-            d_frame = cv.take<uint8_t>(on_device ? 0 : row * static_cast<size_t>(height));
-            d_counts = cv.take<uint16_t>(n_tc + 2);
-            d_cut = cv.take<uint16_t>(n_tc + 2);
-            d_choices = cv.take<mpc_basis_choice>(n_tc * static_cast<size_t>(K));
-            d_profile = cv.take<uint32_t>(static_cast<size_t>(tiles) * (static_cast<size_t>(K) + 1));
-            d_depth = cv.take<uint8_t>(static_cast<size_t>(tiles));
-            d_sweep = cv.take<unsigned long long>(3 * mpc::kBudgetLambdas);
-            d_words = cv.take<unsigned long long>(4);
-            d_error = cv.take<int>(1);
-            d_map = cv.take<uint8_t>(emphasis && !on_device ? static_cast<size_t>(tiles) : 0);   // last: the layout in front is today's
-            return cv.at;
-        };
-        if (const mpc_status gs = c->budget_dev.reserve(layout(nullptr), "quality staging"); gs != MPC_OK) return gs;
-        layout(c->budget_dev.data());
-        const uint8_t* frame = rgb;
-        if (!on_device) {
-            HIP_TRY(hipMemcpyAsync(d_frame, rgb, row * static_cast<size_t>(height), hipMemcpyHostToDevice, s));
-            frame = d_frame;
-        }
-        const uint8_t* d_emphasis = emphasis;
-        if (emphasis && !on_device) {
-            HIP_TRY(hipMemcpyAsync(d_map, emphasis, static_cast<size_t>(tiles), hipMemcpyHostToDevice, s));
-            d_emphasis = d_map;
-        }
-        HIP_TRY(hipMemsetAsync(d_words, 0, 4 * sizeof(unsigned long long), s));
-        HIP_TRY(hipMemsetAsync(d_error, 0, sizeof(int), s));
-        // 1. one pursuit of the whole frame, the records kept; the full frame's SSE behind it
-        if (const mpc_status es = mpc_encode_tiles_device(c, frame, width, height, row, 0, tiles_y, quant, d_counts, d_choices, nullptr, nullptr, 0, s);
-            es != MPC_OK)
-            return es;
-        if (const mpc_status ds = mpc_distortion_device(c, d_counts, d_choices, quant, frame, width, height, d_words + 3, nullptr, s); ds != MPC_OK)
-            return ds;
-        // 2. the full container with its seek index
-        ContainerMade full;
-        if (const mpc_status fs = records_container(c, tuning, s, d_counts, d_choices, tiles, width, height, quant, every ? every : mpc::kIndexIntervalDefault, &full);
-            fs != MPC_OK)
-            return fs;
-        mpc::ContainerIndex full_index;
-        if (!mpc::read_container_index(full.index.data(), full.index.size(), full_index) || full_index.streams.size() != 1 + 6 * static_cast<size_t>(K))
-            return fail(MPC_ERR_HIP, "the full container's seek index does not read back");
-        for (int ch = 0; ch < 3; ++ch)
-            for (int i = 0; i < K; ++i) got.full_records += full_index.streams[1 + 2 * static_cast<size_t>(K) * ch + 2 * static_cast<size_t>(i)].expect;
-        got.full_bytes = full.nbytes;
-        // 3. the weights from its index, the profile once
+        std::vector<unsigned long long> totals(3 * mpc::kBudgetLambdas);     // in front of `e`: it outlives the drain
+        CutEncode<mpc_quality_info> e{c, rgb, on_device, emphasis, width, height, quant, index_interval, bytes, nbytes, index, index_bytes, info};
+        if (const mpc_status as = e.arguments(); as != MPC_OK) return as;
+        if (const mpc_status os = e.open(totals.size() * sizeof(unsigned long long)); os != MPC_OK) return os;   // the sweep's 768 totals
+        unsigned long long* const d_sweep = static_cast<unsigned long long*>(e.d_extra);
+        mpc_quality_info& got = e.got;
+        hipStream_t s = e.s;
         uint32_t weights[3 * MPC_MAX_K];
-        const int verdict = mpc::budget_weights(full.index.data(), full.index.size(), weights);
-        if (verdict == 2) return fail(MPC_ERR_ARGUMENT, "the full container's seek index is serial only: no stream sizes to weigh the steps with");
-        if (verdict != 0) return fail(MPC_ERR_HIP, "the full container's seek index does not read back");
-        if (const mpc_status ps = profile_on_device(c, d_counts, d_choices, quant, frame, width, height, d_profile, d_error, s); ps != MPC_OK) return ps;
-        // 4. the sweep: one launch for all 256 multipliers, its totals to the host
-        if (const mpc_status ss = sweep_on_device(c, d_profile, d_counts, d_emphasis, tiles, weights, d_sweep, s); ss != MPC_OK) return ss;
-        std::vector<unsigned long long> totals(3 * mpc::kBudgetLambdas);
-        unsigned long long full_sse = 0;
+        if (const mpc_status ws = e.weigh(weights); ws != MPC_OK) return ws;
+        // the sweep: one launch for all 256 multipliers, its totals to the host
+        if (const mpc_status ss = sweep_on_device(c, e.d_profile, e.d_counts, e.d_emphasis, e.tiles, weights, d_sweep, s); ss != MPC_OK) return ss;
         int error_word = 0;
         HIP_TRY(hipMemcpyAsync(totals.data(), d_sweep, totals.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(&full_sse, d_words + 3, sizeof(full_sse), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(&error_word, d_error, sizeof(int), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(&error_word, e.d_error, sizeof(int), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         if (error_word) return fail(MPC_ERR_BITSTREAM, "Invalid bitstream");
-        got.full_sse = full_sse;
         got.min_sse = totals[0];
-        // 5. the largest multiplier whose distortion is within the target
+        // the largest multiplier whose distortion is within the target
         static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the totals are u64");
         const int j = mpc::quality_pick(reinterpret_cast<const uint64_t*>(totals.data()), max_sse);
-        // 6. no cut is that good
+        // no cut is that good
         if (j < 0)
             return fail(MPC_ERR_ARGUMENT, "a squared error of at most %llu: the best that cutting this frame's records reaches is %llu", max_sse, totals[0]);
-        // 7. the allocation at j
-        if (const mpc_status as = allocate_on_device(c, d_profile, d_counts, d_emphasis, tiles, weights, j, d_depth, d_cut, d_words, s); as != MPC_OK) return as;
-        // 8. its container, the index with it if asked for
+        // the allocation at j and its container, the index with it if asked for
+        if (const mpc_status as = allocate_on_device(c, e.d_profile, e.d_counts, e.d_emphasis, e.tiles, weights, j, e.d_depth, e.d_cut, e.d_words, s); as != MPC_OK)
+            return as;
         ContainerMade made;
-        if (const mpc_status cs = records_container(c, tuning, s, d_cut, d_choices, tiles, width, height, quant, every, &made); cs != MPC_OK) return cs;
+        if (const mpc_status cs = e.cut_container(&made); cs != MPC_OK) return cs;
         unsigned long long at_j[3] = {0, 0, 0};
-        HIP_TRY(hipMemcpyAsync(at_j, d_words, sizeof(at_j), hipMemcpyDeviceToHost, s));
-        if (depth) HIP_TRY(hipMemcpyAsync(depth, d_depth, static_cast<size_t>(tiles), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(at_j, e.d_words, sizeof(at_j), hipMemcpyDeviceToHost, s));
+        if (depth) HIP_TRY(hipMemcpyAsync(depth, e.d_depth, static_cast<size_t>(e.tiles), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         if (std::memcmp(at_j, totals.data() + 3 * static_cast<size_t>(j), sizeof(at_j)) != 0)
             return fail(MPC_ERR_HIP, "the allocation at multiplier %d does not give the sweep's totals", j);
@@ -368,21 +322,10 @@ mpc_status encode_quality(mpc_context* c, const uint8_t* rgb, bool on_device, co
         got.sse = at_j[0];
         got.model_bits_256 = at_j[1];
         got.records = at_j[2];
-        // 9. returned
-        if (every) {
-            uint8_t* copy = made.index.empty() ? nullptr : static_cast<uint8_t*>(std::malloc(made.index.size()));
-            if (!copy) return fail(MPC_ERR_ALLOC, "no seek index");
-            std::memcpy(copy, made.index.data(), made.index.size());
-            *index = copy;
-            *index_bytes = made.index.size();
-        }
-        *bytes = made.bytes;
-        *nbytes = made.nbytes;
-        made.bytes = nullptr;
-        *info = got;
-        return MPC_OK;
+        return e.deliver(made);
     });
 }
+
 
 }  // namespace
 
@@ -405,6 +348,24 @@ mpc_status profile_on_device(mpc_context* c, const uint16_t* d_counts, const mpc
     p.fast = c->fast ? 1 : 0;
     const int err = mpc::launch_depth_profile(dict_device(c), p, s);
     if (err != 0) return launch_failed(err);
+    return MPC_OK;
+}
+
+mpc_status multiplier_search(const std::function<mpc_status(int, bool*)>& probe, const std::function<mpc_status()>& behind_first, int* found) {
+    *found = -1;
+    bool fits = false;
+    if (const mpc_status ps = probe(mpc::kBudgetLambdas - 1, &fits); ps != MPC_OK) return ps;
+    if (const mpc_status bs = behind_first(); bs != MPC_OK) return bs;
+    if (!fits) return MPC_OK;
+    // lo infeasible (-1: the full result), hi feasible
+    int lo = -1, hi = mpc::kBudgetLambdas - 1;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;                             // lo + hi >= -1 + 1: the shift rounds down
+        if (const mpc_status ps = probe(mid, &fits); ps != MPC_OK) return ps;
+        if (fits) hi = mid;
+        else lo = mid;
+    }
+    *found = hi;
     return MPC_OK;
 }
 

@@ -382,6 +382,80 @@ mpc_status index_flags_of(unsigned flags, bool* expanded) {
     return MPC_OK;
 }
 
+// records -> container on job slot 0 for a caller that waits, as a compose finishes, with the seek index from the entropy stage where
+// one is asked for (`every` != 0; version 2, or version 1 without `expanded`).  The records and the geometry are the caller's: a whole
+// frame's, or a packed frame's
+mpc_status records_container(mpc_context* c, const Tuning& tuning, hipStream_t s, const uint16_t* d_counts, const mpc_basis_choice* d_choices,
+                             long long tiles, int width, int height, const double* quant, unsigned every, ContainerMade* out, bool expanded) {
+    const int K = c->K;
+    if (!c->jobs[0]) c->jobs[0] = std::make_unique<JobSlot>();
+    JobSlot& js = *c->jobs[0];
+    ContainerJob& job = js.job;
+    if (!job.phase1) {
+        HIP_TRY(hipEventCreateWithFlags(&job.phase1, hipEventDisableTiming | hipEventBlockingSync));
+        HIP_TRY(hipEventCreateWithFlags(&job.done, hipEventDisableTiming | hipEventBlockingSync));
+    }
+    Carve measure;
+    mpc::StreamArgs measured{};
+    carve_stream_buffers(measure, tiles, K, true, &measured);
+    if (const mpc_status gs = js.dev.reserve(measure.at, "device staging"); gs != MPC_OK) return gs;
+    GrowBuffer host_stage(GrowBuffer::kPinned);                 // the host route's, should the frame take it: this job's own
+    job.side = job.down = s;
+    job.spin = true;
+    job.host_stage = &host_stage;
+    job.host_offset = 0;
+    job.index_interval = every;
+    job.index_expanded = every != 0 && expanded;
+    struct Unhook {                                             // the slot is left as mpc_container_job_begin expects it
+        ContainerJob& job;
+        ~Unhook() {
+            job.host_stage = nullptr;
+            job.index_interval = 0;
+            job.index_expanded = false;
+            job.index.clear();
+        }
+    } unhook{job};
+    EntropyBuffers eb;
+    if (!tuning.host_entropy)
+        if (const mpc_status es = entropy_buffers(js.ent, static_cast<size_t>(tiles), K, &eb, every ? (expanded ? 2 : 1) : 0); es != MPC_OK) return es;
+    HIP_TRY(hipStreamSynchronize(nullptr));                     // a slot carved for another geometry clears its tables on the null stream
+    if (const mpc_status bs = container_begin(job, c, tuning.host_entropy ? nullptr : &eb, tuning.triple_limit, js.dev.data(), d_counts,
+                                              reinterpret_cast<const uint32_t*>(d_choices), nullptr, nullptr, width, height, quant);
+        bs != MPC_OK)
+        return bs;
+    if (const mpc_status ts = container_tables(job); ts != MPC_OK) return ts;
+    uint8_t* made = nullptr;
+    size_t made_bytes = 0;
+    if (const mpc_status cs = container_collect(job, &made, &made_bytes); cs != MPC_OK) return cs;
+    if (hipStreamSynchronize(s) != hipSuccess) {
+        std::free(made);
+        return fail(MPC_ERR_HIP, "the container job failed: %s", hipGetErrorString(hipGetLastError()));
+    }
+    if (every && job.index.empty()) {
+        std::free(made);
+        return fail(MPC_ERR_ALLOC, "no seek index");
+    }
+    std::free(out->bytes);
+    out->bytes = made;
+    out->nbytes = made_bytes;
+    out->index.assign(job.index.begin(), job.index.end());
+    return MPC_OK;
+}
+
+mpc_status deliver_container(ContainerMade& made, unsigned every, uint8_t** bytes, size_t* nbytes, uint8_t** index, size_t* index_bytes) {
+    if (every) {
+        uint8_t* copy = made.index.empty() ? nullptr : static_cast<uint8_t*>(std::malloc(made.index.size()));
+        if (!copy) return fail(MPC_ERR_ALLOC, "no seek index");
+        std::memcpy(copy, made.index.data(), made.index.size());
+        *index = copy;
+        *index_bytes = made.index.size();
+    }
+    *bytes = made.bytes;
+    *nbytes = made.nbytes;
+    made.bytes = nullptr;
+    return MPC_OK;
+}
+
 namespace {
 JobSlot* job_slot(mpc_context* c, int slot) {
     if (!c->jobs[slot]) c->jobs[slot] = std::make_unique<JobSlot>();

@@ -499,7 +499,7 @@ mpc_status check_encode_args(const mpc_context* c, const uint8_t* rgb, int frame
                              size_t row_stride, int tile_row_begin, int tile_row_end, const uint16_t* counts,
                              const mpc_basis_choice* choices) {
     if (!c) return fail(MPC_ERR_ARGUMENT, "null context");
-    if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback");
+    if (c->device < 0) return no_device();
     if (!rgb || !counts || !choices) return fail(MPC_ERR_ARGUMENT, "null buffer");
     if (width < 1 || height < 1 || row_stride < static_cast<size_t>(3) * width)
         return fail(MPC_ERR_ARGUMENT, "bad geometry %dx%d stride %zu", width, height, row_stride);
@@ -782,7 +782,7 @@ mpc_status mpc_histogram_device(mpc_context* c, const uint16_t* d_counts, const 
 mpc_status mpc_calc_mp_batch(mpc_context* c, int channel, const double* quant_k, const double* inputs, int count,
                              mpc_basis_choice* choices, uint16_t* counts, double* energy, uint32_t* swept) {
     if (!c) return fail(MPC_ERR_ARGUMENT, "null context");
-    if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback");
+    if (c->device < 0) return no_device();
     if (channel < 0 || channel > 2 || !inputs || !choices || !counts || count < 1)
         return fail(MPC_ERR_ARGUMENT, "bad argument");
     HIP_TRY(hipSetDevice(c->device));

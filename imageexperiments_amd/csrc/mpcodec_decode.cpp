@@ -67,7 +67,7 @@ mpc_status mpc_distortion_device(mpc_context* c, const uint16_t* d_counts, const
                                  void* stream) {
     return guarded([&]() -> mpc_status {
     if (!c || !d_counts || !d_choices || !d_rgb || !d_sse) return fail(MPC_ERR_ARGUMENT, "null argument");
-    if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback");
+    if (c->device < 0) return no_device();
     if (width < 1 || height < 1) return fail(MPC_ERR_ARGUMENT, "bad geometry %dx%d", width, height);
     const long long tiles = static_cast<long long>((width + 7) / 8) * ((height + 7) / 8);
     if (tiles * 3 >= (1LL << 31)) return fail(MPC_ERR_ARGUMENT, "frame too large");
@@ -106,7 +106,7 @@ struct mpc_patch_stats {
 
 mpc_status mpc_patch_stats_create(mpc_context* c, unsigned seed, mpc_patch_stats** out) {
     if (!c || !out) return fail(MPC_ERR_ARGUMENT, "null argument");
-    if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback");
+    if (c->device < 0) return no_device();
     try {
         *out = new mpc_patch_stats(c, seed);
     } catch (const std::bad_alloc&) { return fail(MPC_ERR_ALLOC, "out of memory"); }

@@ -1164,7 +1164,7 @@ mpc_status decode_sequence(mpc_context* c, const uint8_t* const* bytes, const si
     if (!c || !bytes || !nbytes || !width || !height || (!rgb && !d_rgb && !containers && !compose) || (d_rgb && !capacity))
         return fail(MPC_ERR_ARGUMENT, "null argument");
     if (n_frames < 1) return fail(MPC_ERR_ARGUMENT, "n_frames must be at least 1");
-    if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback");
+    if (c->device < 0) return no_device();
     for (int f = 0; f < n_frames; ++f)
         if (!bytes[f] || (d_rgb && !d_rgb[f])) return fail(MPC_ERR_ARGUMENT, "frame %d: null argument", f);
     if (rects)                                                      // the same for rectangles: the container's own width and height
@@ -1411,7 +1411,7 @@ mpc_status mpc_transcode_views_indexed(mpc_context* c, const uint8_t* const* byt
         if (n_frames < 1) return fail(MPC_ERR_ARGUMENT, "n_frames must be at least 1");
         std::fill(out, out + n_frames, nullptr);
         std::fill(out_bytes, out_bytes + n_frames, 0);
-        if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback");
+        if (c->device < 0) return no_device();
         std::vector<mpc_rect> rects(static_cast<size_t>(n_frames));
         for (int f = 0; f < n_frames; ++f) {
             if (!bytes[f]) return fail(MPC_ERR_ARGUMENT, "frame %d: null argument", f);
@@ -1444,14 +1444,13 @@ mpc_status mpc_compose_indexed(mpc_context* c, const uint8_t* const* bytes, cons
             return fail(MPC_ERR_ARGUMENT, "null argument");
         if (index_interval >= 0 && (!index || !index_out_bytes)) return fail(MPC_ERR_ARGUMENT, "null argument");
         if (flags & ~(MPC_VIEW_PARSE_ALL | MPC_COMPOSE_DEVICE_PIXELS)) return fail(MPC_ERR_ARGUMENT, "flags 0x%x", flags);
-        if (index_interval > 0 && (index_interval < static_cast<int>(mpc::kIndexIntervalMin) || index_interval > static_cast<int>(mpc::kIndexIntervalMax)))
-            return fail(MPC_ERR_ARGUMENT, "interval %d: 0 or %u to %u", index_interval, mpc::kIndexIntervalMin, mpc::kIndexIntervalMax);
-        const unsigned every = index_interval < 0 ? 0u : index_interval ? static_cast<unsigned>(index_interval) : mpc::kIndexIntervalDefault;
+        unsigned every = 0;
+        if (const mpc_status bad = optional_index_interval_of(index_interval, &every)) return bad;
         *out = nullptr;
         *out_bytes = 0;
         if (index) *index = nullptr;
         if (index_out_bytes) *index_out_bytes = 0;
-        if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback");
+        if (c->device < 0) return no_device();
         const std::vector<mpc::ComposePart> pieces = compose_parts(parts, n_parts);
         const mpc::ComposeDevice device{c->K, c->block_size};
         mpc::ComposePlan plan;
@@ -1653,7 +1652,7 @@ mpc_status window_on_device(mpc_context* c, const uint8_t* bytes, size_t nbytes,
     return guarded([&]() -> mpc_status {
         if (!c || !bytes || !index || !rect || !route || (chunks ? false : !symbols || !n_symbols || !ranges)) return fail(MPC_ERR_ARGUMENT, "null argument");
         if (flags & ~MPC_REGION_PARSE_ALL) return fail(MPC_ERR_ARGUMENT, "flags 0x%x", flags);
-        if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback");
+        if (c->device < 0) return no_device();
         const bool parse_all = (flags & MPC_REGION_PARSE_ALL) != 0;
         const auto give = [&](const std::vector<uint16_t>& got) -> mpc_status {
             uint16_t* out = static_cast<uint16_t*>(std::malloc(got.empty() ? 2 : 2 * got.size()));
@@ -1779,7 +1778,7 @@ mpc_status container_index_on_device(mpc_context* c, const uint8_t* bytes, size_
         if (!mpc::scan_sizes_ok(&segment, &window))
             return fail(MPC_ERR_ARGUMENT, "segment of %d bits, window of %d: 0, or a segment of %u to %u bits and a window of whole segments up to %u bits",
                         segment_bits, window_bits, mpc::kScanSegmentMin, mpc::kScanSegmentMax, mpc::kScanWindowMax);
-        if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback");
+        if (c->device < 0) return no_device();
         const bool expanded = (flags & MPC_INDEX_EXPANDED) != 0;
         std::vector<uint8_t> blob;
         const auto give = [&]() -> mpc_status {
@@ -1860,7 +1859,7 @@ mpc_status mpc_parse_container_device(mpc_context* c, const uint8_t* bytes, size
                                       uint16_t** symbols, size_t* n_symbols, int* route) {
     return guarded([&]() -> mpc_status {
         if (!c || !bytes || !index || !symbols || !n_symbols || !route) return fail(MPC_ERR_ARGUMENT, "null argument");
-        if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback");
+        if (c->device < 0) return no_device();
         // the serial parse's result in this call's form: what every refusal of the index comes down to
         const auto serial = [&]() -> mpc_status {
             *route = 1;
@@ -1923,7 +1922,7 @@ mpc_status mpc_unpack_symbol_streams_device(mpc_context* c, int K, const uint16_
     return guarded([&]() -> mpc_status {
         if (!c || !coded_off || !is_packed || !expect || !symbols || !n_symbols) return fail(MPC_ERR_ARGUMENT, "null argument");
         if (K < 1 || K > MPC_MAX_K) return fail(MPC_ERR_ARGUMENT, "K = %d", K);
-        if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback");
+        if (c->device < 0) return no_device();
         for (int i = 0; i < 6 * K; ++i)
             if (coded_off[i + 1] < coded_off[i]) return fail(MPC_ERR_ARGUMENT, "stream offsets must not decrease");
         if (coded_off[0] != 0 || (!coded && coded_off[6 * K])) return fail(MPC_ERR_ARGUMENT, "bad argument");

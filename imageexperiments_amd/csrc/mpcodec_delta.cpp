@@ -12,8 +12,6 @@
 
 static_assert(mpc::kDeltaPackRows == MPC_DELTA_PACK_ROWS, "one value for the packed frame's tile rows");
 
-mpc_status delta_no_device() { return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback"); }
-
 extern "C" {
 
 mpc_status mpc_changed_tiles(const uint8_t* prev, size_t prev_stride, const uint8_t* cur, size_t cur_stride, int width, int height,
@@ -46,7 +44,7 @@ mpc_status mpc_tile_diff_device(mpc_context* c, uint8_t* d_kept, const uint8_t* 
                                 int32_t* d_list, int32_t* d_count, void* stream) {
     return guarded([&]() -> mpc_status {
         if (!c || !d_kept || !d_rgb || !d_list || !d_count) return fail(MPC_ERR_ARGUMENT, "null argument");
-        if (c->device < 0) return delta_no_device();
+        if (c->device < 0) return no_device();
         if (width < 1 || height < 1) return fail(MPC_ERR_ARGUMENT, "bad geometry");
         const size_t row = 3 * static_cast<size_t>(width), stride = row_stride ? row_stride : row;
         if (stride < row) return fail(MPC_ERR_ARGUMENT, "row_stride %zu for %d pixels", row_stride, width);
@@ -82,7 +80,7 @@ mpc_status mpc_tile_diff_tolerance_device(mpc_context* c, uint8_t* d_kept, const
                                           uint32_t tolerance, int32_t* d_list, int32_t* d_count, uint32_t* d_sse, void* stream) {
     return guarded([&]() -> mpc_status {
         if (!c || !d_kept || !d_rgb || !d_list || !d_count) return fail(MPC_ERR_ARGUMENT, "null argument");
-        if (c->device < 0) return delta_no_device();
+        if (c->device < 0) return no_device();
         if (width < 1 || height < 1) return fail(MPC_ERR_ARGUMENT, "bad geometry");
         const size_t row = 3 * static_cast<size_t>(width), stride = row_stride ? row_stride : row;
         if (stride < row) return fail(MPC_ERR_ARGUMENT, "row_stride %zu for %d pixels", row_stride, width);
@@ -103,7 +101,7 @@ mpc_status mpc_pack_tiles_device(mpc_context* c, const uint8_t* d_rgb, int width
                                  int rows, uint8_t* d_packed, size_t packed_stride, void* stream) {
     return guarded([&]() -> mpc_status {
         if (!c || !d_rgb || !d_list || !d_packed) return fail(MPC_ERR_ARGUMENT, "null argument");
-        if (c->device < 0) return delta_no_device();
+        if (c->device < 0) return no_device();
         if (width < 1 || height < 1 || n < 1 || rows < 1) return fail(MPC_ERR_ARGUMENT, "bad geometry");
         const size_t row = 3 * static_cast<size_t>(width), stride = row_stride ? row_stride : row;
         if (stride < row) return fail(MPC_ERR_ARGUMENT, "row_stride %zu for %d pixels", row_stride, width);
@@ -123,7 +121,7 @@ mpc_status mpc_unpack_tiles_device(mpc_context* c, const uint8_t* d_packed, size
                                    uint8_t* d_rgb, int width, int height, size_t row_stride, void* stream) {
     return guarded([&]() -> mpc_status {
         if (!c || !d_packed || !d_list || !d_rgb) return fail(MPC_ERR_ARGUMENT, "null argument");
-        if (c->device < 0) return delta_no_device();
+        if (c->device < 0) return no_device();
         if (width < 1 || height < 1 || n < 1 || rows < 1) return fail(MPC_ERR_ARGUMENT, "bad geometry");
         const size_t row = 3 * static_cast<size_t>(width), stride = row_stride ? row_stride : row;
         if (stride < row) return fail(MPC_ERR_ARGUMENT, "row_stride %zu for %d pixels", row_stride, width);
@@ -145,7 +143,7 @@ mpc_status mpc_scatter_records_device(mpc_context* c, const uint16_t* d_packed_c
                                       const int32_t* d_list, int n, uint16_t* d_counts, mpc_basis_choice* d_choices, int tiles, void* stream) {
     return guarded([&]() -> mpc_status {
         if (!c || !d_packed_counts || !d_packed_choices || !d_list || !d_counts || !d_choices) return fail(MPC_ERR_ARGUMENT, "null argument");
-        if (c->device < 0) return delta_no_device();
+        if (c->device < 0) return no_device();
         if (n < 1 || tiles < 1) return fail(MPC_ERR_ARGUMENT, "n %d, tiles %d", n, tiles);
         HIP_TRY(hipSetDevice(c->device));
         if (const mpc_status cs = refuse_capture(stream); cs != MPC_OK) return cs;
@@ -162,7 +160,7 @@ mpc_status mpc_delta_create(mpc_context* c, int width, int height, mpc_delta** o
         if (!c || !out) return fail(MPC_ERR_ARGUMENT, "null argument");
         *out = nullptr;
         if (width < 1 || height < 1) return fail(MPC_ERR_ARGUMENT, "bad geometry");
-        if (c->device < 0) return delta_no_device();
+        if (c->device < 0) return no_device();
         const long long tiles_y = (static_cast<long long>(height) + 7) / 8, tiles = ((static_cast<long long>(width) + 7) / 8) * tiles_y;
         if (tiles >= (1LL << 31) / (3 * MPC_MAX_K)) return fail(MPC_ERR_ARGUMENT, "bad geometry");
         std::lock_guard<std::recursive_mutex> one_host_call(c->host_calls);
@@ -254,7 +252,7 @@ mpc_status mpc_delta_set_emphasis(mpc_delta* d, const uint8_t* emphasis, int til
         if (!d) return fail(MPC_ERR_ARGUMENT, "null argument");
         if (emphasis && tiles != d->tiles) return fail(MPC_ERR_ARGUMENT, "an emphasis map of %d tiles, the session has %lld", tiles, d->tiles);
         mpc_context* c = d->ctx;
-        if (c->device < 0) return delta_no_device();
+        if (c->device < 0) return no_device();
         std::lock_guard<std::recursive_mutex> one_host_call(c->host_calls);
         if (!emphasis) {
             d->has_emphasis = false;
@@ -369,66 +367,6 @@ mpc_status delta_pursue(mpc_delta* d, hipStream_t s, DeltaCall& call) {
     return MPC_OK;
 }
 
-// 7. records -> container on job slot 0, as a compose finishes, with the seek index from the entropy stage where one is asked for
-// (`every` != 0; version 2, or version 1 without `expanded`).  The records and the geometry are the caller's: the store's of the whole
-// frame, or a packed frame's
-mpc_status records_container(mpc_context* c, const Tuning& tuning, hipStream_t s, const uint16_t* d_counts, const mpc_basis_choice* d_choices,
-                             long long tiles, int width, int height, const double* quant, unsigned every, ContainerMade* out, bool expanded) {
-    const int K = c->K;
-    if (!c->jobs[0]) c->jobs[0] = std::make_unique<JobSlot>();
-    JobSlot& js = *c->jobs[0];
-    ContainerJob& job = js.job;
-    if (!job.phase1) {
-        HIP_TRY(hipEventCreateWithFlags(&job.phase1, hipEventDisableTiming | hipEventBlockingSync));
-        HIP_TRY(hipEventCreateWithFlags(&job.done, hipEventDisableTiming | hipEventBlockingSync));
-    }
-    Carve measure;
-    mpc::StreamArgs measured{};
-    carve_stream_buffers(measure, tiles, K, true, &measured);
-    if (const mpc_status gs = js.dev.reserve(measure.at, "device staging"); gs != MPC_OK) return gs;
-    GrowBuffer host_stage(GrowBuffer::kPinned);                 // the host route's, should the frame take it: this job's own
-    job.side = job.down = s;
-    job.spin = true;
-    job.host_stage = &host_stage;
-    job.host_offset = 0;
-    job.index_interval = every;
-    job.index_expanded = every != 0 && expanded;
-    struct Unhook {                                             // the slot is left as mpc_container_job_begin expects it
-        ContainerJob& job;
-        ~Unhook() {
-            job.host_stage = nullptr;
-            job.index_interval = 0;
-            job.index_expanded = false;
-            job.index.clear();
-        }
-    } unhook{job};
-    EntropyBuffers eb;
-    if (!tuning.host_entropy)
-        if (const mpc_status es = entropy_buffers(js.ent, static_cast<size_t>(tiles), K, &eb, every ? (expanded ? 2 : 1) : 0); es != MPC_OK) return es;
-    HIP_TRY(hipStreamSynchronize(nullptr));                     // a slot carved for another geometry clears its tables on the null stream
-    if (const mpc_status bs = container_begin(job, c, tuning.host_entropy ? nullptr : &eb, tuning.triple_limit, js.dev.data(), d_counts,
-                                              reinterpret_cast<const uint32_t*>(d_choices), nullptr, nullptr, width, height, quant);
-        bs != MPC_OK)
-        return bs;
-    if (const mpc_status ts = container_tables(job); ts != MPC_OK) return ts;
-    uint8_t* made = nullptr;
-    size_t made_bytes = 0;
-    if (const mpc_status cs = container_collect(job, &made, &made_bytes); cs != MPC_OK) return cs;
-    if (hipStreamSynchronize(s) != hipSuccess) {
-        std::free(made);
-        return fail(MPC_ERR_HIP, "the container job failed: %s", hipGetErrorString(hipGetLastError()));
-    }
-    if (every && job.index.empty()) {
-        std::free(made);
-        return fail(MPC_ERR_ALLOC, "no seek index");
-    }
-    std::free(out->bytes);
-    out->bytes = made;
-    out->nbytes = made_bytes;
-    out->index.assign(job.index.begin(), job.index.end());
-    return MPC_OK;
-}
-
 extern "C" {
 
 mpc_status mpc_delta_encode(mpc_delta* d, const uint8_t* rgb, size_t row_stride, const double* quant, unsigned flags, int index_interval,
@@ -436,9 +374,8 @@ mpc_status mpc_delta_encode(mpc_delta* d, const uint8_t* rgb, size_t row_stride,
     return guarded([&]() -> mpc_status {
         if (!d || !rgb || !bytes || !nbytes || !info) return fail(MPC_ERR_ARGUMENT, "null argument");
         if (index_interval >= 0 && (!index || !index_bytes)) return fail(MPC_ERR_ARGUMENT, "null argument");
-        if (index_interval > 0 && (index_interval < static_cast<int>(mpc::kIndexIntervalMin) || index_interval > static_cast<int>(mpc::kIndexIntervalMax)))
-            return fail(MPC_ERR_ARGUMENT, "interval %d: 0 or %u to %u", index_interval, mpc::kIndexIntervalMin, mpc::kIndexIntervalMax);
-        const unsigned every = index_interval < 0 ? 0u : index_interval ? static_cast<unsigned>(index_interval) : mpc::kIndexIntervalDefault;
+        unsigned every = 0;
+        if (const mpc_status bad = optional_index_interval_of(index_interval, &every)) return bad;
         return delta_call(
             d, rgb, row_stride, quant, flags, false, info,
             [&] {
@@ -453,17 +390,7 @@ mpc_status mpc_delta_encode(mpc_delta* d, const uint8_t* rgb, size_t row_stride,
                 if (const mpc_status cs = records_container(d->ctx, tuning, s, d->d_counts, d->d_choices, d->tiles, d->width, d->height, quant, every, &made);
                     cs != MPC_OK)
                     return cs;
-                if (every) {
-                    uint8_t* copy = static_cast<uint8_t*>(std::malloc(made.index.size()));
-                    if (!copy) return fail(MPC_ERR_ALLOC, "no seek index");
-                    std::memcpy(copy, made.index.data(), made.index.size());
-                    *index = copy;
-                    *index_bytes = made.index.size();
-                }
-                *bytes = made.bytes;
-                *nbytes = made.nbytes;
-                made.bytes = nullptr;
-                return MPC_OK;
+                return deliver_container(made, every, bytes, nbytes, index, index_bytes);
             });
     });
 }
@@ -536,9 +463,8 @@ mpc_status mpc_delta_encode_patch_indexed(mpc_delta* d, const uint8_t* rgb, size
                                           mpc_delta_info* info) {
     return guarded([&]() -> mpc_status {
         if (!d || !rgb || !patch || !patch_bytes || !info) return fail(MPC_ERR_ARGUMENT, "null argument");
-        if (index_interval > 0 && (index_interval < static_cast<int>(mpc::kIndexIntervalMin) || index_interval > static_cast<int>(mpc::kIndexIntervalMax)))
-            return fail(MPC_ERR_ARGUMENT, "interval %d: 0 or %u to %u", index_interval, mpc::kIndexIntervalMin, mpc::kIndexIntervalMax);
-        const unsigned every = index_interval < 0 ? 0u : index_interval ? static_cast<unsigned>(index_interval) : mpc::kIndexIntervalDefault;
+        unsigned every = 0;
+        if (const mpc_status bad = optional_index_interval_of(index_interval, &every)) return bad;
         return encode_patch(d, rgb, row_stride, quant, flags, every, index_min_bytes, patch, patch_bytes, info);
     });
 }

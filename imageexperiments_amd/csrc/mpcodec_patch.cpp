@@ -34,8 +34,6 @@ struct mpc_patch_decoder {
 
 namespace {
 
-mpc_status no_device() { return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback"); }
-
 void report(const mpc::PatchInfo& p, struct mpc_patch_info* info) {
     info->width = p.width;
     info->height = p.height;

@@ -363,7 +363,7 @@ mpc_status encode_sequence(mpc_context* c, const uint8_t* const* frames, bool on
     if (flags)
         if (const mpc_status bad = index_flags_of(*flags, &index_expanded)) return bad;
     if (!c || !frames || !bytes || !nbytes || n_frames < 1) return fail(MPC_ERR_ARGUMENT, "bad argument");
-    if (c->device < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback");
+    if (c->device < 0) return no_device();
     if (width < 1 || height < 1) return fail(MPC_ERR_ARGUMENT, "bad geometry");
     for (int f = 0; f < n_frames; ++f) {
         if (!frames[f]) return fail(MPC_ERR_ARGUMENT, "null frame");

@@ -43,7 +43,7 @@ mpc_status mpc_owed_tiles_device(mpc_context* c, const uint8_t* d_sent, const ui
                                  uint8_t* d_floor, uint8_t* d_must, int32_t* d_list, int32_t* d_count, void* stream) {
     return guarded([&]() -> mpc_status {
         if (!c || !d_sent || !d_counts || !d_flags || !d_floor || !d_must || !d_list || !d_count) return fail(MPC_ERR_ARGUMENT, "null argument");
-        if (c->device < 0) return delta_no_device();
+        if (c->device < 0) return no_device();
         if (tiles < 1 || tiles >= (1LL << 31)) return fail(MPC_ERR_ARGUMENT, "tiles %lld", tiles);
         std::lock_guard<std::recursive_mutex> one_host_call(c->host_calls);
         HIP_TRY(hipSetDevice(c->device));
@@ -62,7 +62,7 @@ mpc_status mpc_gather_records_device(mpc_context* c, const uint16_t* d_counts, c
                                      mpc_basis_choice* d_packed_choices, void* stream) {
     return guarded([&]() -> mpc_status {
         if (!c || !d_counts || !d_choices || !d_list || !d_packed_counts || !d_packed_choices) return fail(MPC_ERR_ARGUMENT, "null argument");
-        if (c->device < 0) return delta_no_device();
+        if (c->device < 0) return no_device();
         if (n < 1 || m < 1 || tiles < 1 || rows < 1 || (!d_idx && n > m)) return fail(MPC_ERR_ARGUMENT, "n %d of %d listed, tiles %d, rows %d", n, m, tiles, rows);
         const mpc::PackGeometry g = mpc::pack_geometry(n, rows);
         const long long padded = static_cast<long long>(g.rows) * g.cols;
@@ -114,7 +114,7 @@ mpc_status mpc_budget_allocate_floor_emphasis_device(mpc_context* c, const uint3
                                                      uint8_t* d_send, unsigned long long* d_totals, void* stream) {
     return guarded([&]() -> mpc_status {
         if (!c || !d_profile || !d_counts || !weights || !d_depth || !d_out_counts || !d_send || !d_totals) return fail(MPC_ERR_ARGUMENT, "null argument");
-        if (c->device < 0) return delta_no_device();
+        if (c->device < 0) return no_device();
         if (n < 1 || n * 3 >= (1LL << 31) || j < 0 || j >= mpc::kBudgetLambdas) return fail(MPC_ERR_ARGUMENT, "tiles %lld, multiplier %d", n, j);
         if (d_emphasis && (tiles < 1 || tiles >= (1LL << 31) || (!d_list && n > tiles)))
             return fail(MPC_ERR_ARGUMENT, "%lld candidates, an emphasis map of %lld tiles", n, tiles);
@@ -414,23 +414,16 @@ mpc_status rate_finish(mpc_delta* d, const DeltaCall& call, hipStream_t s, const
                 }
                 return MPC_OK;
             };
-            // 6. probe(255): every must tile at depth 0 and nothing else
-            bool fits = false;
-            if (const mpc_status ps = probe(mpc::kBudgetLambdas - 1, &fits); ps != MPC_OK) return ps;
             // the profile kernel and the first probe's gather ran in front of the first probe's end
-            HIP_TRY(hipMemcpyAsync(&error_word, d_error, sizeof(int), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            if (error_word) return fail(MPC_ERR_BITSTREAM, "Invalid bitstream");
-            if (!fits)
+            const auto read_error_word = [&]() -> mpc_status {
+                HIP_TRY(hipMemcpyAsync(&error_word, d_error, sizeof(int), hipMemcpyDeviceToHost, s));
+                HIP_TRY(hipStreamSynchronize(s));
+                return error_word ? fail(MPC_ERR_BITSTREAM, "Invalid bitstream") : MPC_OK;
+            };
+            // 6. the search; its first probe, at 255: every must tile at depth 0 and nothing else
+            if (const mpc_status ss = multiplier_search(probe, read_error_word, &got->lambda_index); ss != MPC_OK) return ss;
+            if (got->lambda_index < 0)
                 return fail(MPC_ERR_ARGUMENT, "a budget of %zu bytes: the patch with every tile that must be sent cut to nothing has %zu", budget, probed_bytes);
-            int lo = -1, hi = mpc::kBudgetLambdas - 1;
-            while (hi - lo > 1) {
-                const int mid = (lo + hi) >> 1;                 // lo + hi >= -1 + 1: the shift rounds down
-                if (const mpc_status ps = probe(mid, &fits); ps != MPC_OK) return ps;
-                if (fits) hi = mid;
-                else lo = mid;
-            }
-            got->lambda_index = hi;
             got->sse = kept_totals[0];
         }
         // 7. commit: what the receiver holds once it has applied the patch

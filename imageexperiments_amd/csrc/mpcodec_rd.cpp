@@ -72,7 +72,7 @@ mpc_status check_args(mpc_context* ctx, const void* frame, int width, int height
     if (n_levels < 1) return fail(MPC_ERR_ARGUMENT, "n_levels = %d, at least one level", n_levels);
     if (width < 1 || height < 1) return fail(MPC_ERR_ARGUMENT, "bad geometry %dx%d", width, height);
     if (static_cast<long long>((width + 7) / 8) * ((height + 7) / 8) * 3 >= (1LL << 31)) return fail(MPC_ERR_ARGUMENT, "frame too large");
-    if (mpc_context_device(ctx) < 0) return fail(MPC_ERR_NO_DEVICE, "context was created without a device; there is no CPU fallback");
+    if (mpc_context_device(ctx) < 0) return no_device();
     return MPC_OK;
 }
 

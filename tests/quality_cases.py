@@ -111,6 +111,89 @@ def budget_golden(context, synth_frame, hashlib):
     return out
 
 
+# ---- what tests/golden/cut_bytes_parent.json records of the same frames: the other routes through the cut encodes' front end ----
+QUALITY_MULTIPLES = (1, 2, 4)                # targets of this many times the full frame's squared error
+EMPHASIS_QUARTERS = (3, 2)                   # budgets of the encodes with an emphasis map
+EMPHASIS_MULTIPLE = 2                        # ... and their quality target
+STREAM_FRAMES = 3                            # calls of the delta stream: a key frame, a quarter changed, the same frame again
+
+
+def emphasis_map(tiles):
+    return ((7 * np.arange(tiles)) % 64 + 1).astype(np.uint8)
+
+
+def stream_frames(synth_frame, W, H, seed):
+    """a frame, the same with the top left quarter from another, and that one again: its owed tiles are refined"""
+    first = synth_frame(W, H, seed)
+    second = first.copy()
+    second[:H // 2, :W // 2] = synth_frame(W, H, seed + 1)[:H // 2, :W // 2]
+    return first, second, second
+
+
+def _cut_entry(hashlib, got, fields):
+    out = dict(size=len(got.container), sha256=hashlib.sha256(got.container).hexdigest(), index_sha256=hashlib.sha256(got.index).hexdigest(),
+               depth_sha256=hashlib.sha256(got.depth.tobytes()).hexdigest())
+    out.update({f: getattr(got, f) for f in fields})
+    return out
+
+
+def cut_golden(context, synth_frame, hashlib, to_device):
+    """{key: what the call returns, or the refusal's message}: mpc_encode_image_quality at QUALITY_MULTIPLES of the full frame's error and
+    one target below the best a cut reaches; the budget and the quality encode with emphasis_map, host form and device form; and
+    DeltaEncoder.encode_patch_budget over stream_frames at half the first frame's full container.  to_device(array) -> a device tensor
+    holding it, ready to be read on any stream.  tools/record_budget_hashes.py --all wrote tests/golden/cut_bytes_parent.json with it from
+    the commit in front of the shared front end; test_gpu_target_quality.py compares."""
+    quality = ("lambda_index", "sse", "records", "model_bits_256")
+    budget = ("lambda_index", "probes", "sse", "records")
+    out = {}
+
+    def record(key, call):
+        try:
+            out[key] = call()
+        except RuntimeError as e:
+            out[key] = dict(refused=str(e))
+
+    for name, W, H, seed in FRAMES:
+        rgb = synth_frame(W, H, seed)
+        tiles = -(-W // 8) * -(-H // 8)
+        emphasis = emphasis_map(tiles)
+        d_rgb, d_emphasis = to_device(rgb), to_device(emphasis)
+        for K in FRAME_KS:
+            for fast in (False, True):
+                ctx = context(K, fast)
+                head = f"{name} K{K} {'fast' if fast else 'double'}"
+                full = ctx.encode_image(rgb)
+                loosest = ctx.encode_image_quality(rgb, max_sse=U64_MAX // 2)
+                for m in QUALITY_MULTIPLES:
+                    record(f"{head} quality x{m}",
+                           lambda: _cut_entry(hashlib, ctx.encode_image_quality(rgb, max_sse=loosest.full_sse * m, index_interval=0), quality))
+                if loosest.min_sse > 0:
+                    record(f"{head} quality below the best", lambda: _cut_entry(hashlib, ctx.encode_image_quality(rgb, max_sse=loosest.min_sse - 1), quality))
+                for quarters in EMPHASIS_QUARTERS:
+                    size = len(full) * quarters // 4
+                    record(f"{head} emphasis budget {quarters}/4 host",
+                           lambda: _cut_entry(hashlib, ctx.encode_image_budget_emphasis(rgb, size, emphasis, index_interval=0), budget))
+                    record(f"{head} emphasis budget {quarters}/4 device",
+                           lambda: _cut_entry(hashlib, ctx.encode_image_budget_emphasis_device(d_rgb.data_ptr(), W, H, size, d_emphasis.data_ptr(),
+                                                                                               index_interval=0), budget))
+                target = loosest.full_sse * EMPHASIS_MULTIPLE
+                record(f"{head} emphasis quality x{EMPHASIS_MULTIPLE} host",
+                       lambda: _cut_entry(hashlib, ctx.encode_image_quality_emphasis(rgb, emphasis, max_sse=target, index_interval=0), quality))
+                record(f"{head} emphasis quality x{EMPHASIS_MULTIPLE} device",
+                       lambda: _cut_entry(hashlib, ctx.encode_image_quality_emphasis_device(d_rgb.data_ptr(), W, H, d_emphasis.data_ptr(), max_sse=target,
+                                                                                            index_interval=0), quality))
+                session = ctx.delta_encoder(W, H)
+                for k, frame in enumerate(stream_frames(synth_frame, W, H, seed)):
+                    def call():
+                        patch, info = session.encode_patch_budget(frame, len(full) // 2)
+                        entry = dict(size=len(patch), sha256=hashlib.sha256(patch).hexdigest(), sent_sha256=hashlib.sha256(session.sent().tobytes()).hexdigest())
+                        entry.update({f: getattr(info, f) for f in info.__slots__})
+                        return entry
+                    record(f"{head} stream {k}", call)
+                session.close()
+    return out
+
+
 def cases():
     out = [(name, P, counts, W) for name, P, counts, W, _js in bc.cases()]
     rng = np.random.default_rng(20241020)

@@ -2,8 +2,9 @@
 quality_cases.py, all 768 words; mpc_budget_sweep_device's stream contract through the harness of stream_order.py and its refusal of a
 capturing stream; mpc_encode_image_quality[_device] end to end -- the call replayed with the public pieces alone, the reported error
 against the oracle's decode, the pick against the frame's own sweep, refusals and what the call leaves as it found it; and
-mpc_encode_image_budget against the bytes it returned at the commit in front of this feature (tests/golden/budget_bytes_parent.json).
-Every equality is exact.
+mpc_encode_image_budget against the bytes it returned at the commit in front of this feature (tests/golden/budget_bytes_parent.json),
+and the quality encode, the encodes with an emphasis map and the delta stream to a budget against theirs at the commit in front of
+their shared front end (tests/golden/cut_bytes_parent.json).  Every equality is exact.
 
 The file's name sorts it behind test_gpu_stream_order.py on purpose.  That module's control
 (test_control_the_null_stream_does_not_see_a) needs the null stream's work to run while a side stream is held back, which depends on
@@ -367,3 +368,30 @@ def test_budget_encode_returns_the_bytes_of_the_commit_before(ia, oracle):
     made = [v for v in want.values() if "sha256" in v]
     assert len(made) >= len(want) * 2 // 3 and len({v["sha256"] for v in made}) >= len(made) // 2  # containers, and not all one
     assert any(v["lambda_index"] >= 0 and v["probes"] > 1 for v in made)                          # ... some of them from the search
+
+
+def test_the_other_cut_encodes_return_the_bytes_of_the_commit_before(ia, oracle):
+    """the quality encode, both encodes with an emphasis map in their host and device forms, and the delta stream to a budget, against
+    what they returned at the commit in front of their shared front end and search (tests/golden/cut_bytes_parent.json)"""
+    import torch
+
+    def to_device(array):
+        tensor = torch.from_numpy(array).cuda()
+        torch.cuda.synchronize()
+        return tensor
+
+    with open(os.path.join(GOLDEN, "cut_bytes_parent.json")) as f:
+        want = json.load(f)["entries"]
+    got = qc.cut_golden(lambda K, fast: _context(ia, K, fast), oracle.synth_frame, hashlib, to_device)
+    assert sorted(got) == sorted(want)
+    for key in sorted(want):
+        assert got[key] == want[key], key
+    per_frame = len(qc.QUALITY_MULTIPLES) + 2 * len(qc.EMPHASIS_QUARTERS) + 2 + qc.STREAM_FRAMES
+    assert len(want) >= len(qc.FRAMES) * len(qc.FRAME_KS) * 2 * per_frame
+    for key in want:                                                # the host form and the device form of a call: one result
+        if key.endswith(" host"):
+            assert want[key] == want[key[:-len("host")] + "device"], key
+    made = [v for v in want.values() if "sha256" in v]
+    assert len(made) >= -(-len(want) * 2 // 3)                      # containers and patches, not refusals
+    assert any(v["lambda_index"] > 0 for k, v in want.items() if " quality " in k and "emphasis" not in k and "sha256" in v)
+    assert any(v["probes"] > 1 for k, v in want.items() if " stream " in k and "sha256" in v)
