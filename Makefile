@@ -31,6 +31,9 @@
 #                    tests/test_asan_quality.py runs)
 #   make asan-emphasis  tests/cpp/asan_emphasis: the emphasis maps' host definitions -- the allocation, the sweep and the floor allocation
 #                    with a map, the map from a pixel mask -- on exact-size buffers and hostile values (what tests/test_asan_emphasis.py runs)
+#   make asan-group  tests/cpp/asan_group: the group encodes' host definitions -- the allocation and the sweep over a group of frames with a
+#                    weight table each, the squared error of a PSNR over a group -- on exact-size buffers and hostile values (what
+#                    tests/test_asan_group.py runs)
 #   make asan-tolerance  tests/cpp/asan_tolerance: the delta encoder's change tolerance -- a tile's summed squared difference, the tolerant
 #                    list -- on exact-size frames of widths 1 to 1041, odd bases and padded rows (what tests/test_asan_tolerance.py runs)
 #   make asan-patch  tests/cpp/asan_patch: the delta stream's patch format -- its one writer and its one parser -- on exact-size buffers:
@@ -128,6 +131,12 @@ tests/cpp/asan_emphasis_bin: tests/cpp/asan_emphasis.cpp $(wildcard imageexperim
 asan-emphasis: tests/cpp/asan_emphasis_bin
 	ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=print_stacktrace=1 MPC_HOST_THREADS=4 ./tests/cpp/asan_emphasis_bin
 
+tests/cpp/asan_group_bin: tests/cpp/asan_group.cpp $(wildcard imageexperiments_amd/csrc/host_*.cpp imageexperiments_amd/csrc/host_*.h)
+	g++ -std=c++17 -O1 -g $(SAN) -ffp-contract=off -pthread -Wall -Wno-unused-function tests/cpp/asan_group.cpp -o $@
+
+asan-group: tests/cpp/asan_group_bin
+	ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=print_stacktrace=1 MPC_HOST_THREADS=4 ./tests/cpp/asan_group_bin
+
 tests/cpp/asan_tolerance_bin: tests/cpp/asan_tolerance.cpp $(wildcard imageexperiments_amd/csrc/host_*.cpp imageexperiments_amd/csrc/host_*.h)
 	g++ -std=c++17 -O1 -g $(SAN) -ffp-contract=off -pthread -Wall -Wno-unused-function tests/cpp/asan_tolerance.cpp -o $@
 
@@ -154,6 +163,6 @@ asan-oracle: oracle/_build/liboracle_asan.so
 	LD_PRELOAD=$$(gcc -print-file-name=libasan.so) ASAN_OPTIONS=detect_leaks=0 ORACLE_LIB=$(CURDIR)/oracle/_build/liboracle_asan.so \
 	    python -m pytest tests/test_oracle_golden.py -x -q -p no:cacheprovider
 
-asan: asan-host asan-index asan-encode-index asan-encode-index2 asan-region asan-index2 asan-view asan-transcode asan-compose asan-index-scan asan-delta asan-budget asan-quality asan-emphasis asan-tolerance asan-patch asan-patch-index asan-oracle
+asan: asan-host asan-index asan-encode-index asan-encode-index2 asan-region asan-index2 asan-view asan-transcode asan-compose asan-index-scan asan-delta asan-budget asan-quality asan-emphasis asan-group asan-tolerance asan-patch asan-patch-index asan-oracle
 
-.PHONY: asan asan-host asan-index asan-encode-index asan-encode-index2 asan-region asan-index2 asan-view asan-transcode asan-compose asan-index-scan asan-delta asan-budget asan-quality asan-emphasis asan-tolerance asan-patch asan-patch-index asan-oracle
+.PHONY: asan asan-host asan-index asan-encode-index asan-encode-index2 asan-region asan-index2 asan-view asan-transcode asan-compose asan-index-scan asan-delta asan-budget asan-quality asan-emphasis asan-group asan-tolerance asan-patch asan-patch-index asan-oracle

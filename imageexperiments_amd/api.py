@@ -402,6 +402,19 @@ def _bind_bitstream(L):
         if not os.environ.get("MPCODEC_LIB"):             # an older build may be loaded for A/B timing only
             raise
     try:
+        L.mpc_budget_allocate_group.argtypes = [_u32p, _u16p, _u8p, C.c_int, C.c_longlong, C.c_int, _u32p, C.c_int, _u8p, _u16p, _u64p]
+        L.mpc_budget_sweep_group.argtypes = [_u32p, _u16p, _u8p, C.c_int, C.c_longlong, C.c_int, _u32p, _u64p]
+        L.mpc_sse_for_psnr_group.argtypes = [C.c_double, C.c_int, C.c_int, C.c_int, _u64p]
+        L.mpc_budget_allocate_group_device.argtypes = [vp, vp, vp, vp, C.c_int, C.c_longlong, _u32p, C.c_int, vp, vp, vp, vp]
+        L.mpc_budget_sweep_group_device.argtypes = [vp, vp, vp, vp, C.c_int, C.c_longlong, _u32p, vp, vp]
+        for f, target, info in (("mpc_encode_images_budget", C.c_size_t, MpcBudgetInfo), ("mpc_encode_images_quality", C.c_ulonglong, MpcQualityInfo)):
+            for name in (f, f + "_device"):
+                getattr(L, name).argtypes = [vp, C.POINTER(C.c_void_p), vp, C.c_int, C.c_int, C.c_int, _dp, target, C.c_int, C.POINTER(_u8p), _szp_,
+                                             C.POINTER(_u8p), _szp_, _u8p, C.POINTER(info), C.POINTER(info)]
+    except AttributeError:
+        if not os.environ.get("MPCODEC_LIB"):             # an older build may be loaded for A/B timing only
+            raise
+    try:
         L.mpc_changed_tiles_tolerance.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_uint32, _i32p, C.POINTER(C.c_int),
                                                   _u32p]
         L.mpc_tile_diff_tolerance_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_uint32, vp, vp, vp, vp]
@@ -1423,6 +1436,81 @@ class QualityResult:
                 f"model_bits_256={self.model_bits_256})")
 
 
+MPC_GROUP_MAX_FRAMES = 64
+
+
+def _group_arrays(profile, counts, emphasis, weights):
+    """a group's arrays as the library takes them: profile uint32 [F, T, K + 1], counts uint16 [F, T, 3], emphasis None or uint8 [F, T],
+    weights uint32 [F, 3, K] -> (profile, counts, emphasis, weights, F, T, K)"""
+    profile = np.ascontiguousarray(profile, np.uint32)
+    if profile.ndim != 3:
+        raise ValueError("a group's profile: [frames, tiles, K + 1]")
+    F, T, K = profile.shape[0], profile.shape[1], profile.shape[2] - 1
+    counts = np.ascontiguousarray(counts, np.uint16).reshape(F, T, 3)
+    weights = np.ascontiguousarray(weights, np.uint32).reshape(F, 3, K)
+    return profile, counts, _emphasis(emphasis, F * T), weights, F, T, K
+
+
+def budget_allocate_group(profile, counts, emphasis, weights, j):
+    """mpc_budget_allocate_group: the allocation at multiplier j over a group of frames, every frame with its own weights: profile uint32
+    [F, T, K + 1], counts uint16 [F, T, 3], emphasis uint8 [F, T] or None, weights uint32 [F, 3, K] -> (depth uint8 [F, T], cut counts
+    uint16 [F, T, 3], totals uint64 [F, 3])"""
+    profile, counts, emphasis, weights, F, T, K = _group_arrays(profile, counts, emphasis, weights)
+    depth, cut, totals = np.zeros((F, max(T, 1)), np.uint8), np.zeros((F, max(T, 1), 3), np.uint16), np.zeros((max(F, 1), 3), np.uint64)
+    if T == 0:
+        depth, cut = depth[:, :0], cut[:, :0]
+    _check(load_library().mpc_budget_allocate_group(profile.ctypes.data_as(_u32p), counts.ctypes.data_as(_u16p),
+                                                    None if emphasis is None else emphasis.ctypes.data_as(_u8p), F, T, K,
+                                                    weights.ctypes.data_as(_u32p), int(j), depth.ctypes.data_as(_u8p) if T else None,
+                                                    cut.ctypes.data_as(_u16p) if T else None, totals.ctypes.data_as(C.POINTER(C.c_uint64))))
+    return depth, cut, totals[:F]
+
+
+def budget_sweep_group(profile, counts, emphasis, weights):
+    """mpc_budget_sweep_group: the group allocation's totals, summed over the frames, at every multiplier -> uint64 [256, 3]"""
+    profile, counts, emphasis, weights, F, T, K = _group_arrays(profile, counts, emphasis, weights)
+    totals = np.zeros((MPC_BUDGET_LAMBDAS, 3), np.uint64)
+    _check(load_library().mpc_budget_sweep_group(profile.ctypes.data_as(_u32p), counts.ctypes.data_as(_u16p),
+                                                 None if emphasis is None else emphasis.ctypes.data_as(_u8p), F, T, K,
+                                                 weights.ctypes.data_as(_u32p), totals.ctypes.data_as(C.POINTER(C.c_uint64))))
+    return totals
+
+
+def sse_for_psnr_group(psnr, width, height, frames):
+    """mpc_sse_for_psnr_group: the largest squared error of `frames` width x height frames together whose PSNR over all their pixels
+    (calculate_psnr's formula) is at least `psnr`; frames = 1: sse_for_psnr"""
+    v = C.c_uint64(0)
+    _check(load_library().mpc_sse_for_psnr_group(float(psnr), int(width), int(height), int(frames), C.byref(v)))
+    return v.value
+
+
+class GroupResult:
+    """What encode_images_budget and encode_images_quality return: `frames`, a list of BudgetResult or QualityResult, one per frame in
+    order (len(), indexing and iteration go to it), and `info`, the same info fields summed over the group (lambda_index and probes
+    once), a BudgetResult or QualityResult without container, index and depth."""
+    __slots__ = ("frames", "info")
+
+    def __init__(self, frames, info):
+        self.frames, self.info = frames, info
+
+    def __len__(self):
+        return len(self.frames)
+
+    def __getitem__(self, i):
+        return self.frames[i]
+
+    def __iter__(self):
+        return iter(self.frames)
+
+    @property
+    def size(self):
+        """the containers' bytes together"""
+        return sum(len(f.container) for f in self.frames)
+
+    def __repr__(self):
+        return f"GroupResult(frames={len(self.frames)}, size={self.size}, info={self.info!r})"
+
+
 def _view_parse(fn, head, buf, idx, view, parse_all):
     _, _, K, _ = container_info(buf)
     vw = _view(view)
@@ -2206,6 +2294,93 @@ class CompressionContext:
         """The same with the frame and the map in device memory."""
         return self._encode_quality(self.L.mpc_encode_image_quality_emphasis_device, C.c_void_p(int(d_rgb)), width, height, psnr, max_sse,
                                     quant, index_interval, (d_emphasis or None,))
+
+    # ---- a group of frames (include/mpcodec.h, "group") ----
+    def _encode_group(self, fn, info_type, result, ptrs, emphasis, n, width, height, target, quant, index_interval):
+        """The call behind encode_images_budget, encode_images_quality and their _device forms -> GroupResult"""
+        qp = None
+        if quant is not None:
+            quant = np.ascontiguousarray(quant, np.float64).reshape(3, self.K)
+            qp = quant.ctypes.data_as(_dp)
+        tiles = -(-int(width) // 8) * -(-int(height) // 8)
+        slots = max(n, 1)
+        depth = np.zeros((slots, max(tiles, 1)), np.uint8)
+        outs, sizes, idx, isizes = (_u8p * slots)(), (C.c_size_t * slots)(), (_u8p * slots)(), (C.c_size_t * slots)()
+        frame_info, info = (info_type * slots)(), info_type()
+        _check(fn(self.h, ptrs, emphasis, n, int(width), int(height), qp, int(target), -1 if index_interval is None else int(index_interval),
+                  outs, sizes, idx, isizes, depth.ctypes.data_as(_u8p), frame_info, C.byref(info)))
+        depth = depth.reshape(-1)[:n * tiles].reshape(n, tiles)
+        frames = [result(_take_bytes(self.L, outs[f], C.c_size_t(sizes[f])),
+                         None if index_interval is None else _take_bytes(self.L, idx[f], C.c_size_t(isizes[f])), depth[f], frame_info[f])
+                  for f in range(n)]
+        return GroupResult(frames, result(b"", None, None, info))
+
+    @staticmethod
+    def _host_group(frames, emphasis):
+        """host frames of one size -> (the arrays, kept alive by the caller; their pointers; the map's pointer; n, W, H)"""
+        frames = [_hwc_u8(f)[0] for f in frames]
+        n = len(frames)
+        H, W = frames[0].shape[:2] if n else (0, 0)
+        if any(f.shape[:2] != (H, W) for f in frames):
+            raise ValueError("frames must have the same size")
+        emphasis = _emphasis(emphasis, n * -(-W // 8) * -(-H // 8))
+        ptrs = (C.c_void_p * max(n, 1))(*[C.c_void_p(f.ctypes.data) for f in frames])
+        return frames, emphasis, ptrs, None if emphasis is None else C.c_void_p(emphasis.ctypes.data), n, W, H
+
+    @staticmethod
+    def _device_group(d_frames):
+        n = len(d_frames)
+        return (C.c_void_p * max(n, 1))(*[C.c_void_p(int(p) or None) for p in d_frames]), n
+
+    def encode_images_budget(self, frames, budget, emphasis=None, quant=None, index_interval=None):
+        """mpc_encode_images_budget: equally sized host frames (uint8 [H, W, 3] each, 1 ... 64 of them) as containers of at most `budget`
+        bytes together, one Lagrange multiplier across all tiles of all frames -> GroupResult of BudgetResults.  emphasis: None or uint8
+        [frames, tiles]; index_interval: as for encode_image_budget.  One frame: encode_image_budget's result."""
+        keep, emphasis, ptrs, ep, n, W, H = self._host_group(frames, emphasis)
+        return self._encode_group(self.L.mpc_encode_images_budget, MpcBudgetInfo, BudgetResult, ptrs, ep, n, W, H, budget, quant, index_interval)
+
+    def encode_images_budget_device(self, d_frames, width, height, budget, d_emphasis=None, quant=None, index_interval=None):
+        """The same with the frames (ints from tensor.data_ptr(), tightly packed RGB) and the map (0 or None = none) in device memory."""
+        ptrs, n = self._device_group(d_frames)
+        return self._encode_group(self.L.mpc_encode_images_budget_device, MpcBudgetInfo, BudgetResult, ptrs, d_emphasis or None, n, width, height,
+                                  budget, quant, index_interval)
+
+    def _group_target(self, psnr, max_sse, width, height, n):
+        if (psnr is None) == (max_sse is None):
+            raise ValueError("exactly one of psnr and max_sse")
+        return sse_for_psnr_group(psnr, width, height, n) if max_sse is None else max_sse
+
+    def encode_images_quality(self, frames, psnr=None, max_sse=None, emphasis=None, quant=None, index_interval=None):
+        """mpc_encode_images_quality: equally sized host frames as the containers of the group allocation at the largest multiplier whose
+        squared error over the whole group is at most the target -> GroupResult of QualityResults.  Exactly one target: psnr (dB over
+        all the frames' pixels; through sse_for_psnr_group) or max_sse (the group's total).  One frame: encode_image_quality's result."""
+        keep, emphasis, ptrs, ep, n, W, H = self._host_group(frames, emphasis)
+        return self._encode_group(self.L.mpc_encode_images_quality, MpcQualityInfo, QualityResult, ptrs, ep, n, W, H,
+                                  self._group_target(psnr, max_sse, W, H, n), quant, index_interval)
+
+    def encode_images_quality_device(self, d_frames, width, height, psnr=None, max_sse=None, d_emphasis=None, quant=None, index_interval=None):
+        """The same with the frames and the map in device memory."""
+        ptrs, n = self._device_group(d_frames)
+        return self._encode_group(self.L.mpc_encode_images_quality_device, MpcQualityInfo, QualityResult, ptrs, d_emphasis or None, n, width,
+                                  height, self._group_target(psnr, max_sse, width, height, n), quant, index_interval)
+
+    def budget_allocate_group_device(self, d_profile, d_counts, d_emphasis, frames, tiles, weights, j, d_depth, d_out_counts, d_totals, stream=0):
+        """mpc_budget_allocate_group_device: budget_allocate_group on the device; weights uint32 [frames, 3, K] in host memory; d_emphasis
+        0 = none; d_depth[frames * tiles] (uint8), d_out_counts[frames * tiles * 3], d_totals[frames * 3] (uint64).  Asynchronous."""
+        weights = np.ascontiguousarray(weights, np.uint32).reshape(-1, 3, self.K)
+        if weights.shape[0] != frames and 1 <= frames <= MPC_GROUP_MAX_FRAMES:
+            raise ValueError(f"weights of {weights.shape[0]} frames for {frames}")
+        _check(self.L.mpc_budget_allocate_group_device(self.h, d_profile, d_counts, d_emphasis or None, int(frames), int(tiles),
+                                                       weights.ctypes.data_as(_u32p), int(j), d_depth, d_out_counts, d_totals, stream or None))
+
+    def budget_sweep_group_device(self, d_profile, d_counts, d_emphasis, frames, tiles, weights, d_totals, stream=0):
+        """mpc_budget_sweep_group_device: budget_sweep_group on the device, all 256 multipliers and all frames; d_totals[768] (uint64).
+        Asynchronous."""
+        weights = np.ascontiguousarray(weights, np.uint32).reshape(-1, 3, self.K)
+        if weights.shape[0] != frames and 1 <= frames <= MPC_GROUP_MAX_FRAMES:
+            raise ValueError(f"weights of {weights.shape[0]} frames for {frames}")
+        _check(self.L.mpc_budget_sweep_group_device(self.h, d_profile, d_counts, d_emphasis or None, int(frames), int(tiles),
+                                                    weights.ctypes.data_as(_u32p), d_totals, stream or None))
 
     def budget_allocate_emphasis_device(self, d_profile, d_counts, d_emphasis, tiles, weights, j, d_depth, d_out_counts, d_totals, stream=0):
         """mpc_budget_allocate_emphasis_device: budget_allocate_device with d_emphasis[tiles] (uint8; 0 = neutral).  Asynchronous."""

@@ -137,6 +137,94 @@ void emphasis_from_mask(const uint8_t* mask, int width, int height, size_t row_s
         }
 }
 
+void budget_allocate_group(const uint32_t* profile, const uint16_t* counts, const uint8_t* emphasis, int frames, long long tiles, int K,
+                           const uint32_t* weights, int j, uint8_t* depth, uint16_t* out_counts, uint64_t* totals) {
+    const uint64_t L = budget_lambda(j);
+    const long long all = static_cast<long long>(frames) * tiles;
+    for (int k = 0; k < 3 * frames; ++k) totals[k] = 0;
+    uint32_t below[3][33];                              // the frame's at hand: below[ch][m] = W[f][ch][0] + ... + W[f][ch][m - 1]
+    int built_for = -1;
+    for (long long g = 0; g < all; ++g) {               // one walk over the tiles of the whole group, frame-major
+        const int f = static_cast<int>(g / tiles);
+        if (f != built_for) {
+            const uint32_t* W = weights + static_cast<size_t>(f) * 3 * K;
+            for (int ch = 0; ch < 3; ++ch) {
+                below[ch][0] = 0;
+                for (int i = 0; i < K; ++i) below[ch][i + 1] = below[ch][i] + W[ch * K + i];
+            }
+            built_for = f;
+        }
+        const uint32_t* P = profile + g * (K + 1);
+        const uint64_t factor = static_cast<uint64_t>(emphasis ? emphasis_used(emphasis[g]) : kEmphasisNeutral) << kEmphasisShift;
+        int cnt[3], at = 0;
+        uint64_t rate_at[33];
+        uint64_t best = 0;
+        for (int ch = 0; ch < 3; ++ch) cnt[ch] = counts[g * 3 + ch] > K ? K : counts[g * 3 + ch];
+        for (int n = 0; n <= K; ++n) {
+            rate_at[n] = 0;
+            for (int ch = 0; ch < 3; ++ch) rate_at[n] += below[ch][n < cnt[ch] ? n : cnt[ch]];
+            const uint64_t J = P[n] * factor + L * rate_at[n];
+            if (n == 0 || J < best) {                   // the first strict minimum: the smallest n wins ties
+                best = J;
+                at = n;
+            }
+        }
+        if (depth) depth[g] = static_cast<uint8_t>(at);
+        uint64_t* mine = totals + 3 * static_cast<size_t>(f);
+        mine[0] += P[at];
+        mine[1] += rate_at[at];
+        for (int ch = 0; ch < 3; ++ch) {
+            const int kept = at < cnt[ch] ? at : cnt[ch];
+            if (out_counts) out_counts[g * 3 + ch] = static_cast<uint16_t>(kept);
+            mine[2] += static_cast<uint64_t>(kept);
+        }
+    }
+}
+
+void budget_sweep_group(const uint32_t* profile, const uint16_t* counts, const uint8_t* emphasis, int frames, long long tiles, int K,
+                        const uint32_t* weights, uint64_t totals[3 * kBudgetLambdas]) {
+    for (int k = 0; k < 3 * kBudgetLambdas; ++k) totals[k] = 0;
+    for (int f = 0; f < frames; ++f) {
+        const uint32_t* W = weights + static_cast<size_t>(f) * 3 * K;
+        uint32_t below[3][33];                          // frame f's: below[ch][m] = W[ch][0] + ... + W[ch][m - 1]
+        for (int ch = 0; ch < 3; ++ch) {
+            below[ch][0] = 0;
+            for (int i = 0; i < K; ++i) below[ch][i + 1] = below[ch][i] + W[ch * K + i];
+        }
+        for (long long t = 0; t < tiles; ++t) {
+            const long long g = static_cast<long long>(f) * tiles + t;
+            const uint64_t factor = static_cast<uint64_t>(emphasis ? emphasis_used(emphasis[g]) : kEmphasisNeutral) << kEmphasisShift;
+            uint64_t scaled[33], rate[33], kept[33];
+            for (int n = 0; n <= K; ++n) {
+                scaled[n] = profile[g * (K + 1) + n] * factor;
+                rate[n] = kept[n] = 0;
+                for (int ch = 0; ch < 3; ++ch) {
+                    const int count = counts[g * 3 + ch] > K ? K : counts[g * 3 + ch];
+                    const int upto = n < count ? n : count;
+                    rate[n] += below[ch][upto];
+                    kept[n] += static_cast<uint64_t>(upto);
+                }
+            }
+            // the ladder downwards: L falls, so the walk over n is the same first strict minimum at every j
+            for (int j = kBudgetLambdas - 1; j >= 0; --j) {
+                const uint64_t L = budget_lambda(j);
+                int at = 0;
+                uint64_t best = scaled[0] + L * rate[0];
+                for (int n = 1; n <= K; ++n) {
+                    const uint64_t J = scaled[n] + L * rate[n];
+                    if (J < best) {
+                        best = J;
+                        at = n;
+                    }
+                }
+                totals[3 * j] += profile[g * (K + 1) + at];
+                totals[3 * j + 1] += rate[at];
+                totals[3 * j + 2] += kept[at];
+            }
+        }
+    }
+}
+
 int quality_pick(const uint64_t totals[3 * kBudgetLambdas], uint64_t max_sse) {
     for (int j = kBudgetLambdas - 1; j >= 0; --j)
         if (totals[3 * j] <= max_sse) return j;

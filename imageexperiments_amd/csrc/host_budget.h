@@ -3,7 +3,7 @@
 // and behind mpc_encode_image_quality ("quality"): the allocation's totals at every multiplier, the pick, the squared error of a PSNR.
 // And the emphasis map ("emphasis"; DESIGN.md 4, "Encoder: emphasis"): a factor per tile on the distortion term of both, and the map from
 // a pixel mask.  Knows neither HIP nor the C ABI and builds on its own with host_bitstream / host_container (tests/cpp/asan_budget.cpp,
-// asan_quality.cpp, asan_emphasis.cpp).
+// asan_quality.cpp, asan_emphasis.cpp, asan_group.cpp).
 #pragma once
 
 #include <cstddef>
@@ -73,6 +73,20 @@ void budget_sweep_emphasis(const uint32_t* profile, const uint16_t* counts, cons
 // t = tx * tiles_y + ty over the 8 x 8 tiles: lo + ((hi - lo) * m + 127) / 255, m the maximum of the mask over the tile's pixels inside
 // the frame.  The caller has checked: width, height >= 1, 1 <= lo <= hi <= 64
 void emphasis_from_mask(const uint8_t* mask, int width, int height, size_t row_stride, int lo, int hi, uint8_t* emphasis);
+
+// ---- a group of frames (include/mpcodec.h, "group"; DESIGN.md 4, "Encoder: a group of frames") ----
+// `frames` frames of one geometry, `tiles` tiles each, everything frame-major: tile f * tiles + t, weights[f * 3K + ch * K + i] frame f's
+// own, emphasis null or frames * tiles bytes.  One multiplier across all tiles of all frames: the squared error of a cut is additive over
+// tiles whichever frame a tile belongs to, so this is the equal-slope allocation across frames as well as within them.
+constexpr int kGroupMaxFrames = 64;
+// For every frame f exactly budget_allocate_emphasis of frame f's profile, counts, weights and map slice at j; totals[3 * f + k] are
+// that frame's.  A loop of its own over all tiles of the group -- not `frames` calls of budget_allocate_emphasis, so that the two check
+// each other.  The caller has checked: 1 <= frames <= 64, and what budget_allocate's has
+void budget_allocate_group(const uint32_t* profile, const uint16_t* counts, const uint8_t* emphasis, int frames, long long tiles, int K,
+                           const uint32_t* weights, int j, uint8_t* depth, uint16_t* out_counts, uint64_t* totals);
+// totals[3 * j + k] = the sum over f of budget_sweep_emphasis's of frame f.  A loop of its own, as budget_sweep is
+void budget_sweep_group(const uint32_t* profile, const uint16_t* counts, const uint8_t* emphasis, int frames, long long tiles, int K,
+                        const uint32_t* weights, uint64_t totals[3 * kBudgetLambdas]);
 
 template <class Psnr>
 uint64_t sse_for_psnr(double target, uint64_t limit, Psnr psnr) {

@@ -19,8 +19,10 @@ double psnr(const uint8_t* a, const uint8_t* b, int W, int H) {
     return psnr_from_sse(se, W, H);
 }
 
-double psnr_from_sse(double se, int W, int H) {
-    const double mse = se / static_cast<double>(static_cast<size_t>(W) * static_cast<size_t>(H));
+double psnr_from_sse(double se, int W, int H) { return psnr_from_sse_pixels(se, static_cast<size_t>(W) * static_cast<size_t>(H)); }
+
+double psnr_from_sse_pixels(double se, size_t pixels) {
+    const double mse = se / static_cast<double>(pixels);
     return 20.0 * std::log10(3.0 * 255.0) - 10.0 * std::log10(mse);
 }
 

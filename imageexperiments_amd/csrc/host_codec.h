@@ -12,5 +12,7 @@ namespace mpc {
 double psnr(const uint8_t* original, const uint8_t* decoded, int width, int height);
 // the formula of calculatePSNR from its sum of squared differences (the sum is of integers: exact below 2^53)
 double psnr_from_sse(double se, int width, int height);
+// the same over `pixels` pixels: a group of frames' (psnr_from_sse is this at width * height)
+double psnr_from_sse_pixels(double se, size_t pixels);
 
 }  // namespace mpc

@@ -7,6 +7,8 @@
 // Both are one wave per tile and bandwidth-light: the profile reads 3K record words, at most 3K dictionary rows of 64 values and
 // 192 pixel bytes per tile, the allocation K + 1 words.  A third serves mpc_encode_image_quality ("quality"):
 //   sweep     the allocation's totals at all 256 multipliers in one launch, thread = multiplier
+// and two for a group of frames to one budget or one quality ("group"): the allocation and the sweep over up to eight frames a launch,
+// the frame as blockIdx.y, every frame with its own weights.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -395,6 +397,172 @@ __global__ __launch_bounds__(256) void mp_emphasis_mask_kernel(const uint8_t* __
     }
 }
 
+// --------------------------------------------------------------------------------------------------
+// a group of frames (host_budget.h: budget_allocate_group, budget_sweep_group; include/mpcodec.h, "group"): the allocation and the sweep
+// over up to kGroupChunk frames of one geometry in one launch, siblings of the two kernels above, which stay the code they are.
+// blockIdx.y = the frame, so a workgroup is FRAME-PURE: all its tiles are frame f's, its prefix sums in LDS come from frame f's weights
+// (the chunk's weights travel in the arguments, kGroupChunk * 384 bytes), and its grid-stride loop runs over blockIdx.x inside that
+// frame alone -- the sweep's staging run of kSweepTiles tiles is cut at the frame's last tile like the single frame's, never carried into
+// the next frame.  Tile t of frame f is tile f * tiles + t of every array.  The allocation adds its three totals to totals[f][0 .. 2], the
+// sweep its 768 to the one ladder all frames share: 64-bit integer atomics, so neither depends on the schedule.  Every address comes
+// from the tile grid and the frame index; a count above K is used as K; an emphasis byte passes through emphasis_used.
+// --------------------------------------------------------------------------------------------------
+template <bool kEmphasis>
+__global__ __launch_bounds__(64 * kAllocateWaves) void mp_budget_allocate_group_kernel(const AllocateGroupParams p)
+{
+    __shared__ uint32_t below[3][kMaxDeviceK + 1];                  // frame f's: below[ch][m] = W[f][ch][0] + ... + W[f][ch][m - 1]
+    __shared__ unsigned long long wave_sum[kAllocateWaves][3];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int K = p.K;
+    const int f = (int)blockIdx.y;                                  // < p.frames <= kGroupChunk: the launcher's grid
+    const long long first = (long long)f * p.tiles;                 // the frame's first tile in every array
+    if (threadIdx.x < 3) {
+        const uint32_t* W = p.weights + f * 3 * kMaxDeviceK + threadIdx.x * K;
+        uint32_t sum = 0;
+        below[threadIdx.x][0] = 0;
+        for (int i = 0; i < K; ++i) {
+            sum += W[i];
+            below[threadIdx.x][i + 1] = sum;
+        }
+    }
+    __syncthreads();
+    unsigned long long distortion = 0, rate = 0, records = 0;
+    for (long long t = (long long)blockIdx.x * kAllocateWaves + wave; t < p.tiles; t += (long long)gridDim.x * kAllocateWaves) {
+        const long long g = first + t;
+        int cnt[3];
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            const int count = p.counts[g * 3 + ch];
+            cnt[ch] = count > K ? K : count;
+        }
+        unsigned long long factor = 0;
+        if (kEmphasis) factor = (unsigned long long)emphasis_used(p.emphasis[g]) << kEmphasisShift;
+        uint32_t P = 0, R = 0;
+        unsigned long long J = ~0ull;
+        if (lane <= K) {
+            P = p.profile[g * (K + 1) + lane];
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) R += below[ch][lane < cnt[ch] ? lane : cnt[ch]];
+            J = (kEmphasis ? P * factor : (unsigned long long)P << 16) + p.lambda * R;
+        }
+        int depth = lane;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long other = __shfl_xor(J, o);
+            const int other_depth = __shfl_xor(depth, o);
+            if (other < J || (other == J && other_depth < depth)) {
+                J = other;
+                depth = other_depth;
+            }
+        }
+        // every lane holds the winner; depth <= K because lane 0's J is below 2^63
+        const uint32_t kept_P = (uint32_t)__shfl((int)P, depth), kept_R = (uint32_t)__shfl((int)R, depth);
+        if (lane == 0) p.depth[g] = (uint8_t)depth;
+        if (lane < 3) {
+            const int mine = lane == 0 ? cnt[0] : lane == 1 ? cnt[1] : cnt[2];
+            p.out_counts[g * 3 + lane] = (uint16_t)(mine < depth ? mine : depth);
+        }
+        distortion += kept_P;
+        rate += kept_R;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) records += (unsigned)(cnt[ch] < depth ? cnt[ch] : depth);
+    }
+    if (lane == 0) {
+        wave_sum[wave][0] = distortion;
+        wave_sum[wave][1] = rate;
+        wave_sum[wave][2] = records;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        unsigned long long total = 0;
+        for (int w = 0; w < kAllocateWaves; ++w) total += wave_sum[w][threadIdx.x];
+        if (total) atomicAdd(p.totals + 3 * f + threadIdx.x, total);
+    }
+}
+
+template <bool kEmphasis>
+__global__ __launch_bounds__(256) void mp_budget_sweep_group_kernel(const SweepGroupParams p)
+{
+    __shared__ uint32_t below[3][kMaxDeviceK + 1];                  // frame f's
+    __shared__ SweepEntry staged[kSweepTiles * (kMaxDeviceK + 1)];
+    __shared__ unsigned long long sums[3 * 256];
+    const int m = threadIdx.x;
+    const int K = p.K, depths = K + 1;
+    const int f = (int)blockIdx.y;                                  // < p.frames <= kGroupChunk: the launcher's grid
+    const long long frame_first = (long long)f * p.tiles;
+    if (m < 3) {
+        const uint32_t* W = p.weights + f * 3 * kMaxDeviceK + m * K;
+        uint32_t sum = 0;
+        below[m][0] = 0;
+        for (int i = 0; i < K; ++i) {
+            sum += W[i];
+            below[m][i + 1] = sum;
+        }
+    }
+    const unsigned mant = m == 0 ? 0u : 8u + (unsigned)(m - 1) % 8u;   // L[m] = mant << shift (host_budget.h: budget_lambda)
+    const unsigned shift = m == 0 ? 0u : (unsigned)(m - 1) / 8u;
+    unsigned long long distortion = 0, rate = 0, records = 0;
+    const long long chunks = (p.tiles + kSweepTiles - 1) / kSweepTiles;   // of this frame: the last run ends at the frame's last tile
+    for (long long c = blockIdx.x; c < chunks; c += gridDim.x) {
+        const long long in_frame = c * kSweepTiles;
+        const int here = (int)(p.tiles - in_frame < kSweepTiles ? p.tiles - in_frame : kSweepTiles);
+        const long long first = frame_first + in_frame;
+        __syncthreads();                                            // the walk before has read `staged`; the first time: `below` is built
+        for (int e = m; e < here * depths; e += 256) {
+            const int s = e / depths, n = e - s * depths;
+            const long long g = first + s;
+            uint32_t R = 0, kept = 0;
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) {
+                const int count = p.counts[g * 3 + ch];
+                const int cnt = count > K ? K : count;
+                const int upto = n < cnt ? n : cnt;
+                R += below[ch][upto];
+                kept += (uint32_t)upto;
+            }
+            SweepEntry entry;
+            const uint32_t P = p.profile[first * depths + e];
+            if (kEmphasis) {
+                entry.scaled = P * ((unsigned long long)emphasis_used(p.emphasis[g]) << kEmphasisShift);
+                entry.kept = kept | P << 8;
+            } else {
+                entry.scaled = (unsigned long long)P << 16;
+                entry.kept = kept;
+            }
+            entry.rate = R;
+            staged[e] = entry;
+        }
+        __syncthreads();
+        for (int s = 0; s < here; ++s) {
+            const SweepEntry* tile = staged + s * depths;
+            unsigned long long best = tile[0].scaled + (((unsigned long long)mant * tile[0].rate) << shift);
+            int at = 0;
+#pragma unroll 4
+            for (int n = 1; n <= K; ++n) {
+                const SweepEntry e = tile[n];
+                const unsigned long long J = e.scaled + (((unsigned long long)mant * e.rate) << shift);
+                if (J < best) {
+                    best = J;
+                    at = n;
+                }
+            }
+            const SweepEntry won = tile[at];
+            distortion += kEmphasis ? (unsigned long long)(won.kept >> 8) : won.scaled >> 16;
+            rate += won.rate;
+            records += kEmphasis ? won.kept & 0xFFu : won.kept;
+        }
+    }
+    sums[3 * m] = distortion;
+    sums[3 * m + 1] = rate;
+    sums[3 * m + 2] = records;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const unsigned long long total = sums[k * 256 + m];
+        if (total) atomicAdd(p.totals + k * 256 + m, total);
+    }
+}
+
 int launch_depth_profile(const DictDevice& dict, const ProfileParams& p, void* stream)
 {
     if (p.K < 1 || p.K > kMaxDeviceK || p.width < 1 || p.height < 1 || p.tiles_x != (p.width + 7) / 8 || p.tiles_y != (p.height + 7) / 8)
@@ -425,6 +593,76 @@ int launch_budget_sweep(const SweepParams& p, void* stream)
     if (p.emphasis) hipLaunchKernelGGL(mp_budget_sweep_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL(mp_budget_sweep_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
     return (int)hipGetLastError();
+}
+
+namespace {
+// frames [begin, begin + n) of a group's weights [frames][3][K] to a launch's arguments
+void chunk_weights(const uint32_t* weights, int begin, int n, int K, uint32_t* out)
+{
+    for (int f = 0; f < n; ++f)
+        for (int i = 0; i < 3 * K; ++i) out[f * 3 * kMaxDeviceK + i] = weights[((size_t)(begin + f) * 3) * K + i];
+}
+bool group_fits(int frames, long long tiles, int K)
+{
+    return K >= 1 && K <= kMaxDeviceK && frames >= 1 && tiles >= 1 && tiles * 3 * frames < (1LL << 31);
+}
+}  // namespace
+
+int launch_budget_allocate_group(const uint32_t* profile, const uint16_t* counts, const uint8_t* emphasis, int frames, long long tiles, int K,
+                                 const uint32_t* weights, unsigned long long lambda, uint8_t* depth, uint16_t* out_counts,
+                                 unsigned long long* totals, void* stream)
+{
+    if (!group_fits(frames, tiles, K) || !profile || !counts || !weights || !depth || !out_counts || !totals) return (int)hipErrorInvalidValue;
+    const long long groups = (tiles + kAllocateWaves - 1) / kAllocateWaves;
+    const unsigned blocks = (unsigned)(groups < 4096 ? groups : 4096);
+    for (int begin = 0; begin < frames; begin += kGroupChunk) {
+        const long long first = (long long)begin * tiles;
+        AllocateGroupParams p{};
+        p.profile = profile + first * (K + 1);
+        p.counts = counts + first * 3;
+        p.tiles = tiles;
+        p.K = K;
+        p.frames = frames - begin < kGroupChunk ? frames - begin : kGroupChunk;
+        p.lambda = lambda;
+        p.depth = depth + first;
+        p.out_counts = out_counts + first * 3;
+        p.totals = totals + 3 * begin;
+        p.emphasis = emphasis ? emphasis + first : nullptr;
+        chunk_weights(weights, begin, p.frames, K, p.weights);
+        const dim3 grid(blocks, (unsigned)p.frames);
+        if (emphasis) hipLaunchKernelGGL(mp_budget_allocate_group_kernel<true>, grid, dim3(64 * kAllocateWaves), 0, (hipStream_t)stream, p);
+        else hipLaunchKernelGGL(mp_budget_allocate_group_kernel<false>, grid, dim3(64 * kAllocateWaves), 0, (hipStream_t)stream, p);
+        const int err = (int)hipGetLastError();
+        if (err != 0) return err;
+    }
+    return 0;
+}
+
+int launch_budget_sweep_group(const uint32_t* profile, const uint16_t* counts, const uint8_t* emphasis, int frames, long long tiles, int K,
+                              const uint32_t* weights, unsigned long long* totals, void* stream)
+{
+    if (!group_fits(frames, tiles, K) || !profile || !counts || !weights || !totals) return (int)hipErrorInvalidValue;
+    const long long chunks = (tiles + kSweepTiles - 1) / kSweepTiles;
+    for (int begin = 0; begin < frames; begin += kGroupChunk) {
+        const long long first = (long long)begin * tiles;
+        SweepGroupParams p{};
+        p.profile = profile + first * (K + 1);
+        p.counts = counts + first * 3;
+        p.tiles = tiles;
+        p.K = K;
+        p.frames = frames - begin < kGroupChunk ? frames - begin : kGroupChunk;
+        p.totals = totals;
+        p.emphasis = emphasis ? emphasis + first : nullptr;
+        chunk_weights(weights, begin, p.frames, K, p.weights);
+        // at most kSweepGridCap workgroups a launch, as for one frame: each adds 768 totals once
+        const long long cap = kSweepGridCap / p.frames;
+        const dim3 grid((unsigned)(chunks < cap ? chunks : cap), (unsigned)p.frames);
+        if (emphasis) hipLaunchKernelGGL(mp_budget_sweep_group_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, p);
+        else hipLaunchKernelGGL(mp_budget_sweep_group_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, p);
+        const int err = (int)hipGetLastError();
+        if (err != 0) return err;
+    }
+    return 0;
 }
 
 int launch_emphasis_mask(const uint8_t* mask, int width, int height, size_t row_stride, int lo, int hi, uint8_t* emphasis, void* stream)

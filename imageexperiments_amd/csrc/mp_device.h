@@ -393,6 +393,38 @@ struct SweepParams {
 // host_budget.h: emphasis_from_mask.  mask[height][row_stride] (device, any alignment) -> emphasis[tiles_x * tiles_y], x-outer / y-inner
 int launch_emphasis_mask(const uint8_t* mask, int width, int height, size_t row_stride, int lo, int hi, uint8_t* emphasis, void* stream);
 int launch_budget_sweep(const SweepParams& p, void* stream);
+// The two for a group of frames of one geometry (host_budget.h: budget_allocate_group, budget_sweep_group define them): tile t of frame f
+// is tile f * tiles + t of every array.  A launch takes up to kGroupChunk frames, the frame as blockIdx.y, their weights in the
+// kernel's arguments at weights[f * 3 * kMaxDeviceK + ch * K + i]; the launchers below cut a group into such launches, one behind the
+// other on `stream`.  weights: host memory, [frames][3][K], read before the launcher returns.  totals: the allocation's
+// [frames][3], the sweep's [256][3] summed over the frames; the caller zeroes them.  emphasis: [frames * tiles] or null
+constexpr int kGroupChunk = 8;
+struct AllocateGroupParams {
+    const uint32_t* profile;         // [frames][tiles][K + 1]
+    const uint16_t* counts;          // [frames][tiles][3]
+    long long tiles;                 // of one frame
+    int K, frames;                   // frames of this launch, 1 ... kGroupChunk
+    unsigned long long lambda;
+    uint8_t* depth;
+    uint16_t* out_counts;
+    unsigned long long* totals;      // [frames][3]
+    const uint8_t* emphasis;
+    uint32_t weights[kGroupChunk * 3 * kMaxDeviceK];
+};
+struct SweepGroupParams {
+    const uint32_t* profile;
+    const uint16_t* counts;
+    long long tiles;
+    int K, frames;
+    unsigned long long* totals;      // [256][3]
+    const uint8_t* emphasis;
+    uint32_t weights[kGroupChunk * 3 * kMaxDeviceK];
+};
+int launch_budget_allocate_group(const uint32_t* profile, const uint16_t* counts, const uint8_t* emphasis, int frames, long long tiles, int K,
+                                 const uint32_t* weights, unsigned long long lambda, uint8_t* depth, uint16_t* out_counts,
+                                 unsigned long long* totals, void* stream);
+int launch_budget_sweep_group(const uint32_t* profile, const uint16_t* counts, const uint8_t* emphasis, int frames, long long tiles, int K,
+                              const uint32_t* weights, unsigned long long* totals, void* stream);
 
 // ---- a delta stream to a byte budget (mp_rate.hip; include/mpcodec.h, "rate") ----
 // The tail of launch_tile_diff alone (mp_delta.hip): list[0 .. *count) = the tiles whose flag byte is not 0, ascending.  block_live:

@@ -15,6 +15,7 @@
 //   mpcodec_patch.cpp      the delta stream's patches (mpc_patch_*): the format's entry points (host_patch.h) and the receiver session
 //   mpcodec_budget.cpp     encode to a byte budget (mpc_encode_image_budget): depth profile, allocation, the search over the multiplier;
 //                          encode to a target quality (mpc_encode_image_quality): the sweep over all multipliers, the pick, one allocation
+//                          both for a group of frames (mpc_encode_images_budget, mpc_encode_images_quality): one multiplier for all frames
 //   mpcodec_rate.cpp       a delta stream to a byte budget (mpc_delta_encode_patch_budget): the sent map, candidates, the search with floors
 #pragma once
 

@@ -6,6 +6,8 @@
 // both), then the sweep kernel's totals at all 256 multipliers, the pick on the host, one allocation and one more container job.
 // Both with an emphasis map ("emphasis"; DESIGN.md 4, "Encoder: emphasis"): the same bodies with a map handed to the allocation and the
 // sweep, a null map being the plain call.
+// And both for a group of frames of one geometry ("group"; DESIGN.md 4, "Encoder: a group of frames"): GroupEncode, the same start on n
+// frames with one pursuit launch, then the same search or sweep with the group kernels, one multiplier across all tiles of all frames.
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -326,6 +328,406 @@ mpc_status encode_quality(mpc_context* c, const uint8_t* rgb, bool on_device, co
     });
 }
 
+// ---- a group of frames (include/mpcodec.h, "group"; DESIGN.md 4, "Encoder: a group of frames") ----
+static_assert(mpc::kGroupMaxFrames == MPC_GROUP_MAX_FRAMES, "one limit for the frames of a group");
+
+// d_totals[frames][3] zeroed on `s`, then the kernel, a launch per mpc::kGroupChunk frames.  d_emphasis: null = the plain allocation
+mpc_status allocate_group_on_device(const mpc_context* c, const uint32_t* d_profile, const uint16_t* d_counts, const uint8_t* d_emphasis, int frames,
+                                    long long tiles, const uint32_t* weights, int j, uint8_t* d_depth, uint16_t* d_out_counts,
+                                    unsigned long long* d_totals, hipStream_t s) {
+    HIP_TRY(hipMemsetAsync(d_totals, 0, 3 * static_cast<size_t>(frames) * sizeof(unsigned long long), s));
+    const int err = mpc::launch_budget_allocate_group(d_profile, d_counts, d_emphasis, frames, tiles, c->K, weights, mpc::budget_lambda(j), d_depth,
+                                                      d_out_counts, d_totals, s);
+    if (err != 0) return launch_failed(err);
+    return MPC_OK;
+}
+
+// d_totals[768] zeroed on `s`, then the kernel, a launch per mpc::kGroupChunk frames
+mpc_status sweep_group_on_device(const mpc_context* c, const uint32_t* d_profile, const uint16_t* d_counts, const uint8_t* d_emphasis, int frames,
+                                 long long tiles, const uint32_t* weights, unsigned long long* d_totals, hipStream_t s) {
+    HIP_TRY(hipMemsetAsync(d_totals, 0, 3 * mpc::kBudgetLambdas * sizeof(unsigned long long), s));
+    const int err = mpc::launch_budget_sweep_group(d_profile, d_counts, d_emphasis, frames, tiles, c->K, weights, d_totals, s);
+    if (err != 0) return launch_failed(err);
+    return MPC_OK;
+}
+
+// what the device pieces of a group refuse before anything is enqueued
+mpc_status group_arguments(int frames, long long tiles) {
+    if (frames < 1 || frames > MPC_GROUP_MAX_FRAMES) return fail(MPC_ERR_ARGUMENT, "%d frames: 1 to %d", frames, MPC_GROUP_MAX_FRAMES);
+    if (tiles < 1 || tiles * 3 * frames >= (1LL << 31)) return fail(MPC_ERR_ARGUMENT, "%d frames of %lld tiles", frames, tiles);
+    return MPC_OK;
+}
+
+void add_to(mpc_budget_info& sum, const mpc_budget_info& one) {
+    sum.lambda_index = one.lambda_index;
+    sum.probes = one.probes;
+    sum.full_bytes += one.full_bytes;
+    sum.sse += one.sse;
+    sum.full_sse += one.full_sse;
+    sum.records += one.records;
+    sum.full_records += one.full_records;
+}
+
+void add_to(mpc_quality_info& sum, const mpc_quality_info& one) {
+    sum.lambda_index = one.lambda_index;
+    sum.full_bytes += one.full_bytes;
+    sum.sse += one.sse;
+    sum.full_sse += one.full_sse;
+    sum.min_sse += one.min_sse;
+    sum.records += one.records;
+    sum.full_records += one.full_records;
+    sum.model_bits_256 += one.model_bits_256;
+}
+
+// CutEncode for `n` frames of one geometry: what the group's budget and quality encodes start with.  The same steps in the same order --
+// with n = 1 the same launches and jobs on the same records, so the same bytes -- with one pursuit of the whole group
+// (mpc_encode_batch_device on the frames side by side in the staging: device frames are copied there too, a batch launch takes a stride),
+// and everything per tile frame-major: frame f's records, profile, depth and cut counts at tile f * tiles.
+//   arguments()      `tiles` of one frame
+//   open()           full[f], got[f].full_bytes, .full_sse, .full_records
+//   weigh()          weights[f][3K] from full[f]'s index, frame f's depth profile
+//   cut_container()  frame f's container of the cut counts
+//   deliver()        the containers, their indexes, got[f] and the sums
+template <class Info>
+struct GroupEncode {
+    mpc_context* c;
+    const uint8_t* const* frames;
+    bool on_device;
+    const uint8_t* emphasis;
+    int n, width, height;
+    const double* quant;
+    int index_interval;
+    uint8_t** bytes;
+    size_t* nbytes;
+    uint8_t** indexes;
+    size_t* index_bytes;
+    Info* frame_info;
+    Info* info;
+
+    long long tiles = 0;
+    unsigned every = 0;
+    std::unique_lock<std::recursive_mutex> one_host_call;
+    Tuning tuning;
+    hipStream_t s = nullptr;
+    std::vector<Info> got;                                      // the caller's only on success
+    std::vector<ContainerMade> full;
+    size_t n_tc = 0, frame_bytes = 0;
+    const uint8_t* d_emphasis = nullptr;
+    uint8_t* d_frames = nullptr;                                // the frames side by side
+    uint16_t* d_counts = nullptr;
+    uint16_t* d_cut = nullptr;
+    mpc_basis_choice* d_choices = nullptr;
+    uint32_t* d_profile = nullptr;
+    uint8_t* d_depth = nullptr;
+    void* d_extra = nullptr;
+    unsigned long long* d_words = nullptr;                      // the allocation's 3n totals, then the full frames' n SSEs
+    int* d_error = nullptr;
+    uint8_t* d_map = nullptr;
+
+    ~GroupEncode() {
+        if (s) (void)hipStreamSynchronize(s);
+    }
+
+    mpc_status arguments() {
+        if (!c || !frames || !bytes || !nbytes || !frame_info || !info) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (index_interval >= 0 && (!indexes || !index_bytes)) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (n < 1 || n > MPC_GROUP_MAX_FRAMES) return fail(MPC_ERR_ARGUMENT, "%d frames: 1 to %d", n, MPC_GROUP_MAX_FRAMES);
+        for (int f = 0; f < n; ++f)
+            if (!frames[f]) return fail(MPC_ERR_ARGUMENT, "frame %d is null", f);
+        if (const mpc_status gs = geometry(width, height, &tiles); gs != MPC_OK) return gs;
+        if (tiles * 3 * n >= (1LL << 31)) return fail(MPC_ERR_ARGUMENT, "group too large");
+        n_tc = 3 * static_cast<size_t>(tiles);
+        frame_bytes = 3 * static_cast<size_t>(width) * static_cast<size_t>(height);
+        return MPC_OK;
+    }
+
+    const uint16_t* counts_of(int f) const { return d_counts + static_cast<size_t>(f) * n_tc; }
+    const mpc_basis_choice* choices_of(int f) const { return d_choices + static_cast<size_t>(f) * n_tc * static_cast<size_t>(c->K); }
+    const uint8_t* frame_of(int f) const { return d_frames + static_cast<size_t>(f) * frame_bytes; }
+
+    size_t layout(char* base, size_t extra_bytes) {
+        const size_t N = static_cast<size_t>(n), K = static_cast<size_t>(c->K), T = static_cast<size_t>(tiles);
+        Carve cv{base};
+        d_frames = cv.take<uint8_t>(N * frame_bytes);
+        d_counts = cv.take<uint16_t>(N * n_tc + 2);
+        d_cut = cv.take<uint16_t>(N * n_tc + 2);
+        d_choices = cv.take<mpc_basis_choice>(N * n_tc * K);
+        d_profile = cv.take<uint32_t>(N * T * (K + 1));
+        d_depth = cv.take<uint8_t>(N * T);
+        d_extra = cv.take<char>(extra_bytes);
+        d_words = cv.take<unsigned long long>(4 * N);
+        d_error = cv.take<int>(1);
+        d_map = cv.take<uint8_t>(emphasis && !on_device ? N * T : 0);
+        return cv.at;
+    }
+
+    mpc_status open(size_t extra_bytes) {
+        if (const mpc_status bad = optional_index_interval_of(index_interval, &every)) return bad;
+        if (c->device < 0) return no_device();
+        one_host_call = std::unique_lock<std::recursive_mutex>(c->host_calls);
+        for (int k = 0; k < mpc_context::kSeqSlots; ++k)
+            if (c->jobs[k] && c->jobs[k]->stage != 0) return fail(MPC_ERR_ARGUMENT, "container job slot %d is busy", k);
+        for (int f = 0; f < n; ++f) {
+            bytes[f] = nullptr;
+            nbytes[f] = 0;
+            if (indexes) indexes[f] = nullptr;
+            if (index_bytes) index_bytes[f] = 0;
+            frame_info[f] = Info{};
+        }
+        *info = Info{};
+        got.assign(static_cast<size_t>(n), Info{});
+        full = std::vector<ContainerMade>(static_cast<size_t>(n));
+        HIP_TRY(hipSetDevice(c->device));
+        tuning = read_tuning();
+        if (!c->budget_stream) HIP_TRY(hipStreamCreateWithFlags(&c->budget_stream, hipStreamNonBlocking));
+        s = c->budget_stream;
+        if (const mpc_status gs = c->budget_dev.reserve(layout(nullptr, extra_bytes), "budget staging"); gs != MPC_OK) return gs;
+        layout(c->budget_dev.data(), extra_bytes);
+        const size_t row = 3 * static_cast<size_t>(width), N = static_cast<size_t>(n);
+        for (int f = 0; f < n; ++f)
+            HIP_TRY(hipMemcpyAsync(d_frames + static_cast<size_t>(f) * frame_bytes, frames[f], frame_bytes,
+                                   on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+        d_emphasis = emphasis;
+        if (emphasis && !on_device) {
+            HIP_TRY(hipMemcpyAsync(d_map, emphasis, N * static_cast<size_t>(tiles), hipMemcpyHostToDevice, s));
+            d_emphasis = d_map;
+        }
+        HIP_TRY(hipMemsetAsync(d_words, 0, 4 * N * sizeof(unsigned long long), s));
+        HIP_TRY(hipMemsetAsync(d_error, 0, sizeof(int), s));
+        // one pursuit of the whole group, the records kept; every full frame's SSE behind it
+        if (const mpc_status es = mpc_encode_batch_device(c, d_frames, n, frame_bytes, width, height, row, 0, (height + 7) / 8, quant, d_counts, d_choices,
+                                                          nullptr, nullptr, 0, s);
+            es != MPC_OK)
+            return es;
+        unsigned long long* const d_sse = d_words + 3 * N;
+        for (int f = 0; f < n; ++f)
+            if (const mpc_status ds = mpc_distortion_device(c, counts_of(f), choices_of(f), quant, frame_of(f), width, height, d_sse + f, nullptr, s);
+                ds != MPC_OK)
+                return ds;
+        // every frame's full container with its seek index; a job returns with `s` drained
+        for (int f = 0; f < n; ++f)
+            if (const mpc_status fs = records_container(c, tuning, s, counts_of(f), choices_of(f), tiles, width, height, quant,
+                                                        every ? every : mpc::kIndexIntervalDefault, &full[static_cast<size_t>(f)]);
+                fs != MPC_OK)
+                return fs;
+        std::vector<unsigned long long> sse(N);
+        HIP_TRY(hipMemcpyAsync(sse.data(), d_sse, N * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        const size_t K = static_cast<size_t>(c->K);
+        for (size_t f = 0; f < N; ++f) {
+            mpc::ContainerIndex full_index;
+            if (!mpc::read_container_index(full[f].index.data(), full[f].index.size(), full_index) || full_index.streams.size() != 1 + 6 * K)
+                return fail(MPC_ERR_HIP, "the full container's seek index does not read back");
+            for (size_t ch = 0; ch < 3; ++ch)
+                for (size_t i = 0; i < K; ++i) got[f].full_records += full_index.streams[1 + 2 * K * ch + 2 * i].expect;
+            got[f].full_bytes = full[f].nbytes;
+            got[f].full_sse = sse[f];
+        }
+        return MPC_OK;
+    }
+
+    size_t full_bytes() const {
+        size_t sum = 0;
+        for (const ContainerMade& m : full) sum += m.nbytes;
+        return sum;
+    }
+
+    // weights: [n][3K]
+    mpc_status weigh(uint32_t* weights) {
+        for (int f = 0; f < n; ++f) {
+            const ContainerMade& m = full[static_cast<size_t>(f)];
+            const int verdict = mpc::budget_weights(m.index.data(), m.index.size(), weights + static_cast<size_t>(f) * 3 * static_cast<size_t>(c->K));
+            if (verdict == 2) return fail(MPC_ERR_ARGUMENT, "the full container's seek index is serial only: no stream sizes to weigh the steps with");
+            if (verdict != 0) return fail(MPC_ERR_HIP, "the full container's seek index does not read back");
+        }
+        for (int f = 0; f < n; ++f)
+            if (const mpc_status ps = profile_on_device(c, counts_of(f), choices_of(f), quant, frame_of(f), width, height,
+                                                        d_profile + static_cast<size_t>(f) * static_cast<size_t>(tiles) * static_cast<size_t>(c->K + 1), d_error, s);
+                ps != MPC_OK)
+                return ps;
+        return MPC_OK;
+    }
+
+    mpc_status cut_container(int f, ContainerMade* made) {
+        return records_container(c, tuning, s, d_cut + static_cast<size_t>(f) * n_tc, choices_of(f), tiles, width, height, quant, every, made);
+    }
+
+    // the frames' containers of the cut counts, one job behind the other; *sum: their bytes.  Once the sum is above `stop_above` the
+    // frames behind are not made: a probe that does not fit is known as such from the frames so far
+    mpc_status cut_containers(std::vector<ContainerMade>& made, size_t* sum, size_t stop_above = ~size_t{0}) {
+        *sum = 0;
+        for (int f = 0; f < n && *sum <= stop_above; ++f) {
+            if (const mpc_status cs = cut_container(f, &made[static_cast<size_t>(f)]); cs != MPC_OK) return cs;
+            *sum += made[static_cast<size_t>(f)].nbytes;
+        }
+        return MPC_OK;
+    }
+
+    mpc_status deliver(std::vector<ContainerMade>& made) {
+        for (int f = 0; f < n; ++f) {
+            const mpc_status ds = deliver_container(made[static_cast<size_t>(f)], every, bytes + f, nbytes + f, indexes ? indexes + f : nullptr,
+                                                    index_bytes ? index_bytes + f : nullptr);
+            if (ds != MPC_OK) {                                 // nothing is returned
+                for (int k = 0; k <= f; ++k) {
+                    std::free(bytes[k]);
+                    bytes[k] = nullptr;
+                    nbytes[k] = 0;
+                    if (every) {
+                        std::free(indexes[k]);
+                        indexes[k] = nullptr;
+                        index_bytes[k] = 0;
+                    }
+                }
+                return ds;
+            }
+        }
+        Info sum{};
+        for (int f = 0; f < n; ++f) {
+            frame_info[f] = got[static_cast<size_t>(f)];
+            add_to(sum, got[static_cast<size_t>(f)]);
+        }
+        *info = sum;
+        return MPC_OK;
+    }
+};
+
+// mpc_encode_images_budget: encode_budget over the group -- the full containers if their sum fits, else the search over the multiplier
+// table with size(j) the sum of the frames' containers of the group allocation's cut counts at j
+mpc_status encode_group_budget(mpc_context* c, const uint8_t* const* frames, bool on_device, const uint8_t* emphasis, int n, int width, int height,
+                               const double* quant, size_t budget, int index_interval, uint8_t** bytes, size_t* nbytes, uint8_t** indexes,
+                               size_t* index_bytes, uint8_t* depth, mpc_budget_info* frame_info, mpc_budget_info* info) {
+    return guarded([&]() -> mpc_status {
+        GroupEncode<mpc_budget_info> e{c, frames, on_device, emphasis, n, width, height, quant, index_interval, bytes, nbytes, indexes, index_bytes, frame_info, info};
+        if (const mpc_status as = e.arguments(); as != MPC_OK) return as;
+        if (budget == 0) return fail(MPC_ERR_ARGUMENT, "a budget of 0 bytes");
+        const size_t N = static_cast<size_t>(n), T = static_cast<size_t>(e.tiles);
+        if (const mpc_status os = e.open(N * T); os != MPC_OK) return os;                             // a second depth map
+        uint8_t* const d_depth[2] = {e.d_depth, static_cast<uint8_t*>(e.d_extra)};
+        hipStream_t s = e.s;
+        std::vector<ContainerMade> best(N);
+        int best_depth = -1;                                        // which of d_depth holds the returned containers' map; -1: no cut
+        int found = -1, probes = 0;
+        if (e.full_bytes() <= budget) {
+            best.swap(e.full);
+            for (mpc_budget_info& g : e.got) {
+                g.sse = g.full_sse;
+                g.records = g.full_records;
+            }
+        } else {
+            std::vector<uint32_t> weights(N * 3 * MPC_MAX_K);
+            if (const mpc_status ws = e.weigh(weights.data()); ws != MPC_OK) return ws;
+            int spare = 0;
+            std::vector<unsigned long long> best_totals(3 * N, 0);
+            size_t probed_bytes = 0;                                // the last probe's size
+            const auto probe = [&](int j, bool* fits) -> mpc_status {
+                if (const mpc_status as = allocate_group_on_device(c, e.d_profile, e.d_counts, e.d_emphasis, n, e.tiles, weights.data(), j, d_depth[spare],
+                                                                   e.d_cut, e.d_words, s);
+                    as != MPC_OK)
+                    return as;
+                std::vector<ContainerMade> made(N);
+                // the last multiplier's size is made whole: the refusal names it
+                if (const mpc_status cs = e.cut_containers(made, &probed_bytes, j == mpc::kBudgetLambdas - 1 ? ~size_t{0} : budget); cs != MPC_OK) return cs;
+                ++probes;
+                *fits = probed_bytes <= budget;
+                if (*fits) {
+                    HIP_TRY(hipMemcpyAsync(best_totals.data(), e.d_words, 3 * N * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+                    HIP_TRY(hipStreamSynchronize(s));
+                    best.swap(made);
+                    best_depth = spare;
+                    spare ^= 1;
+                }
+                return MPC_OK;
+            };
+            const auto read_error_word = [&]() -> mpc_status {      // the profile kernels ran in front of the first probe
+                int error_word = 0;
+                HIP_TRY(hipMemcpyAsync(&error_word, e.d_error, sizeof(int), hipMemcpyDeviceToHost, s));
+                HIP_TRY(hipStreamSynchronize(s));
+                return error_word ? fail(MPC_ERR_BITSTREAM, "Invalid bitstream") : MPC_OK;
+            };
+            if (const mpc_status ss = multiplier_search(probe, read_error_word, &found); ss != MPC_OK) return ss;
+            if (found < 0)                                          // the smallest containers there are
+                return fail(MPC_ERR_ARGUMENT, "a budget of %zu bytes: the containers with every tile cut to nothing have %zu", budget, probed_bytes);
+            for (size_t f = 0; f < N; ++f) {
+                e.got[f].sse = best_totals[3 * f];
+                e.got[f].records = best_totals[3 * f + 2];
+            }
+        }
+        for (mpc_budget_info& g : e.got) {
+            g.lambda_index = found;
+            g.probes = probes;
+        }
+        if (depth) {
+            if (best_depth < 0) std::memset(depth, c->K, N * T);
+            else {
+                HIP_TRY(hipMemcpyAsync(depth, d_depth[best_depth], N * T, hipMemcpyDeviceToHost, s));
+                HIP_TRY(hipStreamSynchronize(s));
+            }
+        }
+        return e.deliver(best);
+    });
+}
+
+// mpc_encode_images_quality: encode_quality over the group -- the group sweep's totals, the pick, one group allocation, n container jobs
+mpc_status encode_group_quality(mpc_context* c, const uint8_t* const* frames, bool on_device, const uint8_t* emphasis, int n, int width, int height,
+                                const double* quant, unsigned long long max_sse, int index_interval, uint8_t** bytes, size_t* nbytes,
+                                uint8_t** indexes, size_t* index_bytes, uint8_t* depth, mpc_quality_info* frame_info, mpc_quality_info* info) {
+    return guarded([&]() -> mpc_status {
+        std::vector<unsigned long long> totals(3 * mpc::kBudgetLambdas);     // in front of `e`: they outlive the drain
+        std::vector<unsigned long long> at_0, at_j;
+        GroupEncode<mpc_quality_info> e{c, frames, on_device, emphasis, n, width, height, quant, index_interval, bytes, nbytes, indexes, index_bytes, frame_info, info};
+        if (const mpc_status as = e.arguments(); as != MPC_OK) return as;
+        const size_t N = static_cast<size_t>(n), T = static_cast<size_t>(e.tiles);
+        at_0.assign(3 * N, 0);
+        at_j.assign(3 * N, 0);
+        if (const mpc_status os = e.open(totals.size() * sizeof(unsigned long long)); os != MPC_OK) return os;   // the sweep's 768 totals
+        unsigned long long* const d_sweep = static_cast<unsigned long long*>(e.d_extra);
+        hipStream_t s = e.s;
+        std::vector<uint32_t> weights(N * 3 * MPC_MAX_K);
+        if (const mpc_status ws = e.weigh(weights.data()); ws != MPC_OK) return ws;
+        // the sweep: one launch for all 256 multipliers and all frames; and, the sweep's totals being the group's, the allocation at
+        // multiplier 0 for every frame's own least squared error
+        if (const mpc_status ss = sweep_group_on_device(c, e.d_profile, e.d_counts, e.d_emphasis, n, e.tiles, weights.data(), d_sweep, s); ss != MPC_OK) return ss;
+        if (const mpc_status as = allocate_group_on_device(c, e.d_profile, e.d_counts, e.d_emphasis, n, e.tiles, weights.data(), 0, e.d_depth, e.d_cut, e.d_words, s);
+            as != MPC_OK)
+            return as;
+        int error_word = 0;
+        HIP_TRY(hipMemcpyAsync(totals.data(), d_sweep, totals.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(at_0.data(), e.d_words, 3 * N * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(&error_word, e.d_error, sizeof(int), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (error_word) return fail(MPC_ERR_BITSTREAM, "Invalid bitstream");
+        static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the totals are u64");
+        const int j = mpc::quality_pick(reinterpret_cast<const uint64_t*>(totals.data()), max_sse);
+        if (j < 0)
+            return fail(MPC_ERR_ARGUMENT, "a squared error of at most %llu: the best that cutting these frames' records reaches is %llu", max_sse, totals[0]);
+        if (const mpc_status as = allocate_group_on_device(c, e.d_profile, e.d_counts, e.d_emphasis, n, e.tiles, weights.data(), j, e.d_depth, e.d_cut, e.d_words, s);
+            as != MPC_OK)
+            return as;
+        std::vector<ContainerMade> made(N);
+        size_t made_bytes = 0;
+        if (const mpc_status cs = e.cut_containers(made, &made_bytes); cs != MPC_OK) return cs;
+        HIP_TRY(hipMemcpyAsync(at_j.data(), e.d_words, 3 * N * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        if (depth) HIP_TRY(hipMemcpyAsync(depth, e.d_depth, N * T, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        // the cross-check: the frames' totals at j add up to the sweep's, and those at 0 to its first
+        unsigned long long sum_j[3] = {0, 0, 0}, least = 0;
+        for (size_t f = 0; f < N; ++f) {
+            for (int k = 0; k < 3; ++k) sum_j[k] += at_j[3 * f + static_cast<size_t>(k)];
+            least += at_0[3 * f];
+        }
+        if (std::memcmp(sum_j, totals.data() + 3 * static_cast<size_t>(j), sizeof(sum_j)) != 0 || least != totals[0])
+            return fail(MPC_ERR_HIP, "the allocation at multiplier %d does not give the sweep's totals", j);
+        for (size_t f = 0; f < N; ++f) {
+            mpc_quality_info& g = e.got[f];
+            g.lambda_index = j;
+            g.min_sse = at_0[3 * f];
+            g.sse = at_j[3 * f];
+            g.model_bits_256 = at_j[3 * f + 1];
+            g.records = at_j[3 * f + 2];
+        }
+        return e.deliver(made);
+    });
+}
 
 }  // namespace
 
@@ -568,6 +970,100 @@ mpc_status mpc_encode_image_quality_emphasis_device(mpc_context* c, const uint8_
                                                     const double* quant, unsigned long long max_sse, int index_interval, uint8_t** bytes,
                                                     size_t* nbytes, uint8_t** index, size_t* index_bytes, uint8_t* depth, mpc_quality_info* info) {
     return encode_quality(c, d_rgb, true, d_emphasis, width, height, quant, max_sse, index_interval, bytes, nbytes, index, index_bytes, depth, info);
+}
+
+// ---- a group of frames ----
+mpc_status mpc_budget_allocate_group(const uint32_t* profile, const uint16_t* counts, const uint8_t* emphasis, int frames, long long tiles, int K,
+                                     const uint32_t* weights, int j, uint8_t* depth, uint16_t* out_counts, uint64_t* totals) {
+    return guarded([&]() -> mpc_status {
+        if (!profile || !counts || !weights || !totals) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (frames < 1 || frames > MPC_GROUP_MAX_FRAMES) return fail(MPC_ERR_ARGUMENT, "%d frames: 1 to %d", frames, MPC_GROUP_MAX_FRAMES);
+        if (tiles < 0 || K < 1 || K > MPC_MAX_K || j < 0 || j >= mpc::kBudgetLambdas) return fail(MPC_ERR_ARGUMENT, "tiles %lld, K %d, multiplier %d", tiles, K, j);
+        mpc::budget_allocate_group(profile, counts, emphasis, frames, tiles, K, weights, j, depth, out_counts, totals);
+        return MPC_OK;
+    });
+}
+
+mpc_status mpc_budget_sweep_group(const uint32_t* profile, const uint16_t* counts, const uint8_t* emphasis, int frames, long long tiles, int K,
+                                  const uint32_t* weights, uint64_t* totals) {
+    return guarded([&]() -> mpc_status {
+        if (!profile || !counts || !weights || !totals) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (frames < 1 || frames > MPC_GROUP_MAX_FRAMES) return fail(MPC_ERR_ARGUMENT, "%d frames: 1 to %d", frames, MPC_GROUP_MAX_FRAMES);
+        if (tiles < 0 || K < 1 || K > MPC_MAX_K) return fail(MPC_ERR_ARGUMENT, "tiles %lld, K %d", tiles, K);
+        mpc::budget_sweep_group(profile, counts, emphasis, frames, tiles, K, weights, totals);
+        return MPC_OK;
+    });
+}
+
+mpc_status mpc_sse_for_psnr_group(double psnr, int width, int height, int frames, uint64_t* max_sse) {
+    return guarded([&]() -> mpc_status {
+        if (!max_sse) return fail(MPC_ERR_ARGUMENT, "null argument");
+        long long tiles = 0;
+        if (const mpc_status gs = geometry(width, height, &tiles); gs != MPC_OK) return gs;
+        if (frames < 1 || frames > MPC_GROUP_MAX_FRAMES) return fail(MPC_ERR_ARGUMENT, "%d frames: 1 to %d", frames, MPC_GROUP_MAX_FRAMES);
+        if (std::isnan(psnr) || (std::isinf(psnr) && psnr < 0)) return fail(MPC_ERR_ARGUMENT, "a PSNR of %g", psnr);
+        const uint64_t limit = uint64_t{195075} * 64 * static_cast<uint64_t>(tiles) * static_cast<uint64_t>(frames);     // 3 * 255^2 a pixel
+        const size_t pixels = static_cast<size_t>(width) * static_cast<size_t>(height) * static_cast<size_t>(frames);
+        *max_sse = mpc::sse_for_psnr(psnr, limit, [&](uint64_t s) { return mpc::psnr_from_sse_pixels(static_cast<double>(s), pixels); });
+        return MPC_OK;
+    });
+}
+
+mpc_status mpc_budget_allocate_group_device(mpc_context* c, const uint32_t* d_profile, const uint16_t* d_counts, const uint8_t* d_emphasis, int frames,
+                                            long long tiles, const uint32_t* weights, int j, uint8_t* d_depth, uint16_t* d_out_counts,
+                                            unsigned long long* d_totals, void* stream) {
+    return guarded([&]() -> mpc_status {
+        if (!c || !d_profile || !d_counts || !weights || !d_depth || !d_out_counts || !d_totals) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (c->device < 0) return no_device();
+        if (const mpc_status gs = group_arguments(frames, tiles); gs != MPC_OK) return gs;
+        if (j < 0 || j >= mpc::kBudgetLambdas) return fail(MPC_ERR_ARGUMENT, "multiplier %d", j);
+        HIP_TRY(hipSetDevice(c->device));
+        if (const mpc_status cs = refuse_capture(stream); cs != MPC_OK) return cs;
+        return allocate_group_on_device(c, d_profile, d_counts, d_emphasis, frames, tiles, weights, j, d_depth, d_out_counts, d_totals,
+                                        static_cast<hipStream_t>(stream));
+    });
+}
+
+mpc_status mpc_budget_sweep_group_device(mpc_context* c, const uint32_t* d_profile, const uint16_t* d_counts, const uint8_t* d_emphasis, int frames,
+                                         long long tiles, const uint32_t* weights, unsigned long long* d_totals, void* stream) {
+    return guarded([&]() -> mpc_status {
+        if (!c || !d_profile || !d_counts || !weights || !d_totals) return fail(MPC_ERR_ARGUMENT, "null argument");
+        if (c->device < 0) return no_device();
+        if (const mpc_status gs = group_arguments(frames, tiles); gs != MPC_OK) return gs;
+        HIP_TRY(hipSetDevice(c->device));
+        if (const mpc_status cs = refuse_capture(stream); cs != MPC_OK) return cs;
+        return sweep_group_on_device(c, d_profile, d_counts, d_emphasis, frames, tiles, weights, d_totals, static_cast<hipStream_t>(stream));
+    });
+}
+
+mpc_status mpc_encode_images_budget(mpc_context* c, const uint8_t* const* frames, const uint8_t* emphasis, int n_frames, int width, int height,
+                                    const double* quant, size_t budget, int index_interval, uint8_t** bytes, size_t* nbytes, uint8_t** indexes,
+                                    size_t* index_bytes, uint8_t* depth, mpc_budget_info* frame_info, mpc_budget_info* info) {
+    return encode_group_budget(c, frames, false, emphasis, n_frames, width, height, quant, budget, index_interval, bytes, nbytes, indexes, index_bytes,
+                               depth, frame_info, info);
+}
+
+mpc_status mpc_encode_images_budget_device(mpc_context* c, const uint8_t* const* d_frames, const uint8_t* d_emphasis, int n_frames, int width,
+                                           int height, const double* quant, size_t budget, int index_interval, uint8_t** bytes, size_t* nbytes,
+                                           uint8_t** indexes, size_t* index_bytes, uint8_t* depth, mpc_budget_info* frame_info,
+                                           mpc_budget_info* info) {
+    return encode_group_budget(c, d_frames, true, d_emphasis, n_frames, width, height, quant, budget, index_interval, bytes, nbytes, indexes,
+                               index_bytes, depth, frame_info, info);
+}
+
+mpc_status mpc_encode_images_quality(mpc_context* c, const uint8_t* const* frames, const uint8_t* emphasis, int n_frames, int width, int height,
+                                     const double* quant, unsigned long long max_sse, int index_interval, uint8_t** bytes, size_t* nbytes,
+                                     uint8_t** indexes, size_t* index_bytes, uint8_t* depth, mpc_quality_info* frame_info, mpc_quality_info* info) {
+    return encode_group_quality(c, frames, false, emphasis, n_frames, width, height, quant, max_sse, index_interval, bytes, nbytes, indexes,
+                                index_bytes, depth, frame_info, info);
+}
+
+mpc_status mpc_encode_images_quality_device(mpc_context* c, const uint8_t* const* d_frames, const uint8_t* d_emphasis, int n_frames, int width,
+                                            int height, const double* quant, unsigned long long max_sse, int index_interval, uint8_t** bytes,
+                                            size_t* nbytes, uint8_t** indexes, size_t* index_bytes, uint8_t* depth, mpc_quality_info* frame_info,
+                                            mpc_quality_info* info) {
+    return encode_group_quality(c, d_frames, true, d_emphasis, n_frames, width, height, quant, max_sse, index_interval, bytes, nbytes, indexes,
+                                index_bytes, depth, frame_info, info);
 }
 
 }  // extern "C"

@@ -1452,6 +1452,94 @@ mpc_status mpc_encode_image_quality_emphasis_device(mpc_context* ctx, const uint
                                                     mpc_quality_info* info);
 mpc_status mpc_delta_set_emphasis(mpc_delta* d, const uint8_t* emphasis /* host, tiles bytes, or NULL */, int tiles);
 
+/* ---- group: a group of frames to one byte budget or one quality ("Encoder: a group of frames") ----
+ * A burst, a tile mosaic, a short clip: `frames` frames of one geometry and one constraint for all of them.  The squared error of a cut
+ * is additive over tiles, whichever frame a tile belongs to, so ONE multiplier across all tiles of all frames gives the equal-slope
+ * allocation across frames as well as within them: a flat frame gives its bytes to a textured one.  P, W, R, L[j], J, the allocation at
+ * j, the sweep and the pick are the budget and quality sections', e[t] the emphasis section's, unchanged.  Host and device agree bit for
+ * bit on everything defined here.
+ *
+ * A GROUP is `frames` frames, T tiles each, K the context's, 1 <= frames <= MPC_GROUP_MAX_FRAMES = 64.  Records, profile, depth and cut
+ * counts are FRAME-MAJOR: tile t of frame f is tile f * T + t of every array (what mpc_encode_batch_device writes for whole frames).
+ * WEIGHTS  weights[f * 3K + ch * K + i]: frame f's own, mpc_budget_weights of frame f's full container's index.
+ * EMPHASIS  NULL, or frames * T bytes, frame-major; a neutral byte is the plain allocation, as in the emphasis section.
+ * GROUP ALLOCATION AT j  for every frame f exactly mpc_budget_allocate_emphasis of frame f's profile, counts, weights and map slice at
+ * j; totals[3 * f + k] are that frame's totals.
+ * GROUP SWEEP  S[j][k] = the sum over f of mpc_budget_sweep_emphasis of frame f: 768 u64 words.  A sum of sequences that never fall is one:
+ * mpc_quality_pick is used unchanged.
+ *
+ * Host only, no context, safe on several threads; they define what the kernels compute:
+ *   mpc_budget_allocate_group   depth[frames * T] and out_counts[3 * frames * T]: each NULL or room for that; totals[3 * frames]
+ *   mpc_budget_sweep_group      totals[768]
+ *   mpc_sse_for_psnr_group      *max_sse = the largest s in 0 ... 195075 * 64 * tiles * frames whose PSNR over frames * width * height
+ *                               pixels, by mpc_psnr's formula, is >= psnr: the same binary search; with frames = 1 it is mpc_sse_for_psnr
+ * Their refusals are mpc_budget_allocate_emphasis's, mpc_budget_sweep_emphasis's and mpc_sse_for_psnr's, and MPC_ERR_ARGUMENT for frames
+ * outside 1 ... 64.
+ *
+ * mpc_budget_allocate_group_device, mpc_budget_sweep_group_device: the two on the caller's buffers (device memory; d_emphasis NULL or
+ * device memory) with weights[frames * 3K] in HOST memory, read before the call returns (they travel in the kernels' arguments, eight
+ * frames a launch): d_depth[frames * T], d_out_counts[3 * frames * T], d_totals[3 * frames] resp. d_totals[768] (u64; zeroed on `stream`
+ * first).  Asynchronous on `stream`, with their siblings' contract: ordered on the caller's stream, a capturing stream refused with
+ * nothing enqueued, MPC_ERR_NO_DEVICE for a host-only context; MPC_ERR_ARGUMENT for a null pointer, frames outside 1 ... 64, T < 1 or
+ * 3 * frames * T >= 2^31, j outside 0 ... 255.
+ *
+ * mpc_encode_images_budget[_device]: containers of the frames (host: pointers to host frames of 3 * width bytes a row; _device: pointers,
+ * in host memory, to tightly packed device frames) of at most `budget` bytes together.  Synchronous.
+ *   1. the whole group is pursued in one launch (mpc_encode_batch_device); the records stay on the device
+ *   2. every frame's full container F_f with its seek index is made
+ *   3. sum |F_f| <= budget: the F_f are returned, byte for byte mpc_encode_images; lambda_index = -1, probes = 0, every depth K
+ *   4. else the weights and the depth profile of every frame are made, once each
+ *   5. size(j) = the sum over f of the container of frame f's cut counts at j: one group allocation and n container jobs
+ *      (a probe whose sum is above the budget after fewer frames stops there; size(255) is always made whole)
+ *   6. size(255) > budget: MPC_ERR_ARGUMENT, the budget and size(255) in the text
+ *   7. mpc_encode_image_budget's bisection between -1 and 255; probes counts multipliers, not jobs
+ *   8. hi's containers are returned, kept from their probe
+ * mpc_encode_images_quality[_device]: the frames as the containers of the group allocation at the largest multiplier whose squared
+ * error over the whole group is at most max_sse: the same start, the weights and profiles, one group sweep, the pick (j = -1:
+ * MPC_ERR_ARGUMENT, max_sse and S[0][0] in the text), the group allocation at j, n container jobs; the frames' totals at j are checked
+ * against S[j].  What mpc_encode_image_quality promises and does not promise holds for the group's sums.
+ * bytes[n], nbytes[n]: the containers (mpc_free each).  index_interval < 0: no index, `indexes` and `index_bytes` may be NULL; otherwise
+ * indexes[f] (mpc_free) is byte for byte mpc_container_index2(bytes[f], ..., interval, MPC_INDEX_EXPANDED).  depth: NULL, or host room for
+ * n * T bytes, frame-major.  emphasis: NULL or n * T bytes (host form: host memory; _device: device memory).  frame_info[n]: the single
+ * call's struct for each frame, lambda_index and probes repeated (a frame's min_sse is its own allocation at multiplier 0); info: the
+ * sums over the frames, lambda_index and probes once.
+ * WITH n_frames = 1 BOTH CALLS RETURN BYTE FOR BYTE WHAT mpc_encode_image_budget[_emphasis] AND mpc_encode_image_quality[_emphasis]
+ * RETURN, info included.
+ * Refusals and side effects are the single-frame calls', with nothing enqueued, and MPC_ERR_ARGUMENT for n_frames outside 1 ... 64, a
+ * null frame pointer and 3 * n * T >= 2^31.  On failure nothing is returned, the slots are idle and the context is as it was.  The
+ * staging is the single calls', grown for the group; a group that does not fit in device memory returns that allocation's status.
+ * Frames of different sizes, a group budget for the delta stream and probes that overlap are not built. */
+#define MPC_GROUP_MAX_FRAMES 64
+mpc_status mpc_budget_allocate_group(const uint32_t* profile, const uint16_t* counts, const uint8_t* emphasis, int frames, long long tiles, int K,
+                                     const uint32_t* weights /* [frames][3K] */, int j, uint8_t* depth, uint16_t* out_counts,
+                                     uint64_t* totals /* [frames][3] */);
+mpc_status mpc_budget_sweep_group(const uint32_t* profile, const uint16_t* counts, const uint8_t* emphasis, int frames, long long tiles, int K,
+                                  const uint32_t* weights /* [frames][3K] */, uint64_t* totals /* [256 * 3] */);
+mpc_status mpc_sse_for_psnr_group(double psnr, int width, int height, int frames, uint64_t* max_sse);
+mpc_status mpc_budget_allocate_group_device(mpc_context* ctx, const uint32_t* d_profile, const uint16_t* d_counts, const uint8_t* d_emphasis,
+                                            int frames, long long tiles, const uint32_t* weights /* host, [frames][3K] */, int j,
+                                            uint8_t* d_depth, uint16_t* d_out_counts, unsigned long long* d_totals /* [frames][3] */,
+                                            void* stream);
+mpc_status mpc_budget_sweep_group_device(mpc_context* ctx, const uint32_t* d_profile, const uint16_t* d_counts, const uint8_t* d_emphasis,
+                                         int frames, long long tiles, const uint32_t* weights /* host, [frames][3K] */,
+                                         unsigned long long* d_totals /* [768] */, void* stream);
+mpc_status mpc_encode_images_budget(mpc_context* ctx, const uint8_t* const* frames, const uint8_t* emphasis, int n_frames, int width, int height,
+                                    const double* quant, size_t budget, int index_interval, uint8_t** bytes, size_t* nbytes,
+                                    uint8_t** indexes, size_t* index_bytes, uint8_t* depth, mpc_budget_info* frame_info,
+                                    mpc_budget_info* info);
+mpc_status mpc_encode_images_budget_device(mpc_context* ctx, const uint8_t* const* d_frames, const uint8_t* d_emphasis, int n_frames, int width,
+                                           int height, const double* quant, size_t budget, int index_interval, uint8_t** bytes,
+                                           size_t* nbytes, uint8_t** indexes, size_t* index_bytes, uint8_t* depth,
+                                           mpc_budget_info* frame_info, mpc_budget_info* info);
+mpc_status mpc_encode_images_quality(mpc_context* ctx, const uint8_t* const* frames, const uint8_t* emphasis, int n_frames, int width, int height,
+                                     const double* quant, unsigned long long max_sse, int index_interval, uint8_t** bytes, size_t* nbytes,
+                                     uint8_t** indexes, size_t* index_bytes, uint8_t* depth, mpc_quality_info* frame_info,
+                                     mpc_quality_info* info);
+mpc_status mpc_encode_images_quality_device(mpc_context* ctx, const uint8_t* const* d_frames, const uint8_t* d_emphasis, int n_frames,
+                                            int width, int height, const double* quant, unsigned long long max_sse, int index_interval,
+                                            uint8_t** bytes, size_t* nbytes, uint8_t** indexes, size_t* index_bytes, uint8_t* depth,
+                                            mpc_quality_info* frame_info, mpc_quality_info* info);
+
 /* ---- patch index: a patch that carries its container's seek index ("Delta stream") ----
  * The receiver of a version-1 patch parses the container's entropy codes on the host, serially: the cost follows the bytes.  A
  * version-2 patch brings the seek index of its container along, and mpc_patch_apply hands container and index to the sequence
