@@ -196,6 +196,7 @@ def _bind_debug(L):
     L.mpc_debug_screen_probe_device.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp]
     try:
         L.mpc_debug_track_probe_device.argtypes = [vp, vp, vp, C.c_float, C.c_int, C.c_int, vp, vp]
+        L.mpc_debug_pair_scratch.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_uint32, vp, vp, vp]
     except AttributeError:
         if not os.environ.get("MPCODEC_LIB"):             # an older build may be loaded for A/B timing only
             raise
@@ -2661,6 +2662,17 @@ class CompressionContext:
         _check(self.L.mpc_debug_track_probe_device(self.h, d_row_bits or None, d_pair_bits or None, float(bound), int(rows), int(pair),
                                                    d_out or None, stream or None))
 
+    def debug_pair_scratch(self, wave_begin, wave_count, fill_word=None):
+        """mpc_debug_pair_scratch: the pursuit kernel's pair scratch of waves [wave_begin, + wave_count), every 32-bit word set to
+        `fill_word` first if one is given -> P float32[waves,16,32,64], meta uint32[waves,16,32,2], E float32[waves,16,32]."""
+        n = max(int(wave_count), 1)
+        p = np.zeros((n, 16, PAIR_SCRATCH_PAIRS, 64), np.float32)
+        meta = np.zeros((n, 16, PAIR_SCRATCH_PAIRS, 2), np.uint32)
+        e = np.zeros((n, 16, PAIR_SCRATCH_PAIRS), np.float32)
+        _check(self.L.mpc_debug_pair_scratch(self.h, int(wave_begin), int(wave_count), 0 if fill_word is None else 1,
+                                             int(fill_word or 0), p.ctypes.data, meta.ctypes.data, e.ctypes.data))
+        return p, meta, e
+
     def calc_mp(self, channel, vectors, quant_k=None):
         """matching::CalcMPDynamic (MatchingPursuit.h:22) on the device for vectors[n,64].
         Returns counts[n], choices[n,K], energy[n], swept[n]."""
@@ -2681,6 +2693,7 @@ class CompressionContext:
 
 
 FILTER_TILE_HALVES = 2048          # 16-bit elements of one filter tile (16 rows x 64 pixels, hi and lo)
+PAIR_SCRATCH_PAIRS = 32            # pairs a slot of the pursuit kernel can hold (mp_device.h: kMaxPairs)
 
 
 def filter_tiles(rows, tiles, k_order=0):

@@ -4,7 +4,8 @@
 // themselves, so no record can show that they are right; mpc_debug_track_probe_device, the kernel's key tracking by its definition
 // and grouped on given bit patterns (tests/test_gpu_track_keys.py); and mpc_debug_container_index_device, the device scan of the seek index
 // with its segment and window sizes given, so that a test can make chains cross windows on a small container
-// (tests/test_gpu_index_scan.py).  Nothing here is on a product path; every entry validates its arguments
+// (tests/test_gpu_index_scan.py); and mpc_debug_pair_scratch, which fills and reads the pursuit kernel's per-wave pair scratch
+// (kept approximations, bookkeeping word, bound) around a calc_mp call (tests/test_gpu_pair_drift.py).  Nothing here is on a product path; every entry validates its arguments
 // before it touches memory.
 #include "../../include/mpcodec.h"
 #include "mpc_internal.h"
@@ -106,6 +107,35 @@ mpc_status mpc_debug_screen_probe_device(mpc_context* c, int channel, int block,
     const uint16_t* block_tiles =
         d.d_detail_t1 + (static_cast<size_t>(channel) * d.num_base + block) * mpc::kBlockFilterTiles * mpc::kFilterTileHalves;
     if (const int err = mpc::launch_screen_probe(d.d_base_t1, block_tiles, d_vectors, n, d_approx, d_bound, stream)) return launch_failed(err);
+    return MPC_OK;
+}
+
+mpc_status mpc_debug_pair_scratch(mpc_context* c, int wave_begin, int wave_count, int fill, uint32_t fill_word, float* host_p,
+                                  uint32_t* host_meta, float* host_e) {
+    if (const mpc_status st = need_device(c); st != MPC_OK) return st;
+    DeviceDict& d = *c->dd;
+    // the scratch is [workgroups * kWavesMax][16 slots][kMaxPairs]: the wave count follows from the size of the bounds
+    const size_t per_wave = static_cast<size_t>(16) * mpc::kMaxPairs;
+    const long long waves = static_cast<long long>(mpc::pursuit_scratch_bounds(d.workgroups) / per_wave);
+    if (fill != 0 && fill != 1) return fail(MPC_ERR_ARGUMENT, "fill must be 0 or 1");
+    if (!host_p || !host_meta || !host_e) return fail(MPC_ERR_ARGUMENT, "null output");
+    if (wave_begin < 0 || wave_count < 1 || wave_begin > waves - wave_count)
+        return fail(MPC_ERR_ARGUMENT, "waves outside the scratch (%lld)", waves);
+    HIP_TRY(hipSetDevice(c->device));
+    std::lock_guard<std::mutex> hold(d.launch_lock);          // no pursuit is enqueued meanwhile ...
+    HIP_TRY(hipDeviceSynchronize());                          // ... and none is running
+    const size_t first = static_cast<size_t>(wave_begin) * per_wave, count = static_cast<size_t>(wave_count) * per_wave;
+    float* const p = d.pair_p + first * 64;
+    unsigned* const meta = d.pair_meta + first * 2;
+    float* const e = d.pair_e + first;
+    if (fill) {
+        HIP_TRY(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(p), static_cast<int>(fill_word), count * 64));
+        HIP_TRY(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(meta), static_cast<int>(fill_word), count * 2));
+        HIP_TRY(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(e), static_cast<int>(fill_word), count));
+    }
+    HIP_TRY(hipMemcpy(host_p, p, sizeof(float) * count * 64, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(host_meta, meta, sizeof(unsigned) * count * 2, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(host_e, e, sizeof(float) * count, hipMemcpyDeviceToHost));
     return MPC_OK;
 }
 

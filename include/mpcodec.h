@@ -1637,6 +1637,18 @@ mpc_status mpc_debug_screen_probe_device(mpc_context* ctx, int channel, int bloc
  * definition, then grouped.  Asynchronous on `stream`. */
 mpc_status mpc_debug_track_probe_device(mpc_context* ctx, const uint32_t* d_row_bits, const uint32_t* d_pair_bits, float bound, int rows,
                                         int pair, uint32_t* d_out, void* stream);
+/* The persistent pursuit kernel's pair scratch ("pairs"), filled and read back around a pursuit
+ * (tests/test_gpu_pair_drift.py).  A wave of the kernel (number blockIdx.x * waves per workgroup + wave) keeps, per slot (16) and pair
+ * (32): 64 floats P (the kept approximations of the block's rows; pad rows 0), 2 words of bookkeeping (word 0 = block | rows << 9 |
+ * first dictionary index << 16, word 1 unused) and 1 float E (the bound on |P - exact projection|).  For waves [wave_begin,
+ * wave_begin + wave_count): fill = 1 first sets every 32-bit word of the three arrays to fill_word (fill = 0: nothing is written);
+ * then the three arrays are copied to host_p[wave_count][16][32][64], host_meta[wave_count][16][32][2], host_e[wave_count][16][32].
+ * Synchronous, like mpc_calc_mp_batch: waits for the device and holds off pursuit launches of the process meanwhile.  A batch of at
+ * most 16 vectors of mpc_calc_mp_batch runs in one workgroup on one of waves 0 ... 11, vector s in slot s.
+ * MPC_ERR_ARGUMENT: null context or output, fill other than 0 / 1, waves outside 0 ... 16 * workgroups of the scratch (one workgroup
+ * per compute unit); MPC_ERR_NO_DEVICE for a host-only context; nothing is written then. */
+mpc_status mpc_debug_pair_scratch(mpc_context* ctx, int wave_begin, int wave_count, int fill, uint32_t fill_word, float* host_p,
+                                  uint32_t* host_meta, float* host_e);
 
 #ifdef __cplusplus
 }
